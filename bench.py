@@ -2,6 +2,12 @@
 """Headline benchmark: env steps/sec at N parallel robots (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W [--config laikago4096|minicheetah4096|mixed8192] [--no-randomizer] [--repeats R]
+                  [--full [--no-cpu-baseline]] [--dump-outputs DIR]
+  A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes runs of its own: the
+  back-to-back kernel cross-check (`roofline.kernel_ms_back_to_back`) and, for N = 1, the CPU oracle rows (`cpu_baseline`, ~30 s;
+  --no-cpu-baseline leaves them out).  --dump-outputs DIR writes what the last timed step returned to rank 0 (observations, rewards,
+  dones) as DIR/<name>.npy; with the same arguments the inputs are the same from run to run, so two builds can be compared output
+  for output.
   N > 1 without a launcher around it (WORLD_SIZE unset): this process touches no GPU, starts
   `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...` as a fresh
   child (one rank per GPU over RCCL, like the reference's `mpiexec -n 8 python3 OpenRoboRL/run.py`, README.md:27), forwards rank 0's
@@ -177,6 +183,26 @@ def cpu_baseline(env):
             "rows": rows}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, obs, reward, done):
+    """Host copies of the last timed step's outputs -> out_dir/<name>.npy (float32; robot_index float64).  Batches whose outputs exceed
+    DUMP_MAX_BYTES are written for a fixed, seeded sample of robots (robot_index.npy says which).  The episodes of the rollout-boundary
+    gather are left out: which of them the capped device log lists, and in what order, follows the order the robots' waves reach it."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"obs": obs.float().cpu().numpy(), "reward": reward.float().cpu().numpy(), "done": done.float().cpu().numpy()}
+    n = arrays["obs"].shape[0]
+    keep = DUMP_MAX_BYTES // (arrays["obs"][0].nbytes + 16)     # + reward, done and robot_index
+    if n > keep:
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["robot_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -224,13 +250,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="laikago4096")
     ap.add_argument("--robots-per-gpu", type=int, default=0, help="override the config's robots per GPU (experiments)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: back-to-back kernel time and (N = 1) the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-randomizer", action="store_true",
                     help="second row of SURVEY 8d: domain randomiser off, fixed 2 ms control latency (run.py:205-206, laikago.py:27)")
     ap.add_argument("--repeats", type=int, default=1, help="time R regions of K steps each and report the median (SURVEY 8d: 5)")
     ap.add_argument("--spawn", action="store_true", help="go through the rank launcher even for --gpus 1")
     ap.add_argument("--launch-dry-run", action="store_true", help="print the launcher's argv as JSON and exit")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn or args.launch_dry_run):
         child_args = [a for a in sys.argv[1:] if a not in ("--spawn", "--launch-dry-run")]
@@ -330,14 +361,19 @@ def main():
     regions = [timed_region(r * args.steps) for r in range(max(1, args.repeats))]
     mid = sorted(regions, key=lambda r: r["elapsed"])[len(regions) // 2]
     elapsed, gather_s, n_eps, n_ev = mid["elapsed"], mid["gather_s"], mid["episodes"], mid["launches_timed"]
+    # the last timed step's outputs, before anything else steps the env again
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, env.obs, env.reward, env.done)
 
     # dominant kernel: HIP events on the launch stream around the bracketed timed launches, median
     kern_ms = mid["kern_ms"]
     kern_total_ms = kern_ms * args.steps
-    # cross-check: back-to-back launches without the action kernels in between (C-ABI helper, same stream)
-    act = make_action(env.obs, 0).contiguous()
-    torch.cuda.synchronize(dev)
-    kern_b2b_ms = env.time_steps(act, 50) / 50.0
+    kern_b2b_ms = None
+    if args.full:
+        # cross-check: back-to-back launches without the action kernels in between (C-ABI helper, same stream)
+        act = make_action(env.obs, 0).contiguous()
+        torch.cuda.synchronize(dev)
+        kern_b2b_ms = env.time_steps(act, 50) / 50.0
     b_alg = B_ALG_FIXED_LATENCY if args.no_randomizer else B_ALG
     b_survey = B_ALG_SURVEY_FIXED_LATENCY if args.no_randomizer else B_ALG_SURVEY
     achieved = b_alg * n / (kern_ms * 1e-3) / 1e9
@@ -454,7 +490,7 @@ def main():
                                  "because the north star asks for it, see DESIGN.md section 6"
                                  % ("a lone wave per SIMD" if kernel_wpe == 1 else "two co-resident waves per SIMD")},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(env)
         print(json.dumps(out))
     env.close()

@@ -97,6 +97,29 @@ def test_bench_self_launch_runs_ranks_and_propagates_failure():
     assert "ChildFailedError" in out.stderr or "exitcode" in out.stderr, out.stderr[-2000:]
 
 
+def test_bench_dump_outputs_samples_large_batches(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on host tensors: the whole batch as float32, and a batch over the size cap as a fixed, seeded sample of
+    robots that stays under the cap."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 64
+    obs = torch.arange(n * 160, dtype=torch.float32).reshape(n, 160)
+    rew, done = torch.arange(n, dtype=torch.float32), (torch.arange(n) % 3 == 0).to(torch.uint8)
+    load = lambda d, k: np.load(str(tmp_path / d / (k + ".npy")))     # noqa: E731
+    bench.dump_outputs(str(tmp_path / "all"), obs, rew, done)
+    assert sorted(os.listdir(str(tmp_path / "all"))) == ["done.npy", "obs.npy", "reward.npy"]
+    assert np.array_equal(load("all", "obs"), obs.numpy()) and load("all", "done").dtype == np.float32
+    assert np.array_equal(load("all", "done"), done.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16 * 1024)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), obs, rew, done)
+    idx = load("s1", "robot_index").astype(np.int64)
+    assert 0 < len(idx) < n and np.array_equal(idx, load("s2", "robot_index")) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(load("s1", "obs"), obs.numpy()[idx]) and np.array_equal(load("s1", "reward"), rew.numpy()[idx])
+    assert sum(os.path.getsize(str(f)) for f in (tmp_path / "s1").iterdir()) < 16 * 1024 + 4 * 128    # + the .npy headers
+
+
 SHARD_WORKER = r"""
 import os, sys, numpy as np, torch
 sys.path.insert(0, %r)

@@ -46,6 +46,28 @@ def test_bench_line_contract():
         assert vi is None and r["traffic"] is None and not r["pmc"]
 
 
+def test_bench_plain_run_is_lean_and_full_adds_the_cross_check():
+    d = _run("--steps", "6", "--warmup", "2")
+    assert "cpu_baseline" not in d and d["roofline"]["kernel_ms_back_to_back"] is None and d["steps"] == 6
+    d = _run("--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline")
+    assert "cpu_baseline" not in d and 0.15 < d["roofline"]["kernel_ms_back_to_back"] < 0.5
+
+
+def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path):
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for p in dirs:
+        _run("--steps", "6", "--warmup", "2", "--dump-outputs", str(p))
+    names = ["done", "obs", "reward"]
+    for p in dirs:
+        assert sorted(f.name for f in p.iterdir()) == [n + ".npy" for n in names]
+    a = {n: np.load(dirs[0] / (n + ".npy")) for n in names}
+    assert a["obs"].shape == (4096, 160) and a["reward"].shape == a["done"].shape == (4096,)
+    assert all(x.dtype == np.float32 for x in a.values()) and np.isfinite(a["obs"]).all()
+    for n in names:
+        np.testing.assert_array_equal(a[n], np.load(dirs[1] / (n + ".npy")), err_msg=n)
+
+
 def test_bench_second_row_and_two_wave_config():
     d = _run("--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-randomizer")
     assert d["config"]["randomizer"] is False and d["config"]["control_latency_s"] == 0.002

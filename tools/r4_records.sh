@@ -9,15 +9,15 @@ cd $ROOT
 for P in $PARTS; do
 case $P in
 bench)
-  python3 bench.py > $OUT/r04_laikago4096_bench.json 2> $OUT/bench.err
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r04_driver20_bench.json 2>> $OUT/bench.err
-  python3 bench.py --no-cpu-baseline --repeats 5 > $OUT/r04_laikago4096_median5_bench.json 2>> $OUT/bench.err
-  python3 bench.py --no-cpu-baseline --no-randomizer > $OUT/r04_laikago4096_norand_bench.json 2>> $OUT/bench.err
-  python3 bench.py --no-cpu-baseline --config minicheetah4096 > $OUT/r04_minicheetah4096_bench.json 2>> $OUT/bench.err
-  python3 bench.py --no-cpu-baseline --config mixed8192 > $OUT/r04_mixed8192_bench.json 2>> $OUT/bench.err
-  python3 bench.py --no-cpu-baseline --config mixed8192 --gpus 1 --steps 20 --warmup 5 > $OUT/r04_mixed8192_driver20_bench.json 2>> $OUT/bench.err
-  python3 bench.py --no-cpu-baseline --robots-per-gpu 16384 > $OUT/r04_laikago16384_bench.json 2>> $OUT/bench.err
-  ORR_FORCE_DIST=1 python3 bench.py --spawn --gpus 1 --no-cpu-baseline > $OUT/r04_launcher_rccl_one_rank_bench.json 2>> $OUT/bench.err
+  python3 bench.py --full > $OUT/r04_laikago4096_bench.json 2> $OUT/bench.err
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r04_driver20_bench.json 2>> $OUT/bench.err
+  python3 bench.py --full --no-cpu-baseline --repeats 5 > $OUT/r04_laikago4096_median5_bench.json 2>> $OUT/bench.err
+  python3 bench.py --full --no-cpu-baseline --no-randomizer > $OUT/r04_laikago4096_norand_bench.json 2>> $OUT/bench.err
+  python3 bench.py --full --no-cpu-baseline --config minicheetah4096 > $OUT/r04_minicheetah4096_bench.json 2>> $OUT/bench.err
+  python3 bench.py --full --no-cpu-baseline --config mixed8192 > $OUT/r04_mixed8192_bench.json 2>> $OUT/bench.err
+  python3 bench.py --full --no-cpu-baseline --config mixed8192 --gpus 1 --steps 20 --warmup 5 > $OUT/r04_mixed8192_driver20_bench.json 2>> $OUT/bench.err
+  python3 bench.py --full --no-cpu-baseline --robots-per-gpu 16384 > $OUT/r04_laikago16384_bench.json 2>> $OUT/bench.err
+  ORR_FORCE_DIST=1 python3 bench.py --full --spawn --gpus 1 --no-cpu-baseline > $OUT/r04_launcher_rccl_one_rank_bench.json 2>> $OUT/bench.err
   echo "bench done"; python3 -c "
 import json,glob
 for f in sorted(glob.glob('$OUT/r04_*bench.json')):

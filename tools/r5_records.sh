@@ -21,10 +21,10 @@ survey)    python3 tools/laikago_identify.py --minutes 12 --robots 128 --seed 2 
            python3 tools/laikago_accept_stats.py $OUT/r05_laikago_survey_seed2.jsonl > $OUT/r05_laikago_accept_stats.txt ;;
 probe)     python3 tools/policy_probe.py --robots 1024 --seeds 1 2 --out $OUT/r05_policy_probe.json > $OUT/r05_policy_probe.txt 2>&1 ;;
 drift)     python3 tools/drift_floor_spread.py --runs 12 --out-dir $OUT > $OUT/drift_floor_spread.log 2>&1 ;;
-bench)     python3 bench.py > $OUT/r05_laikago4096_bench.json 2> $OUT/bench.err
-           python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r05_driver20_bench.json 2>> $OUT/bench.err
-           for C in minicheetah4096 mixed8192; do python3 bench.py --no-cpu-baseline --config $C > $OUT/r05_${C}_bench.json 2>> $OUT/bench.err; done
-           python3 bench.py --no-cpu-baseline --no-randomizer > $OUT/r05_laikago4096_norand_bench.json 2>> $OUT/bench.err ;;
+bench)     python3 bench.py --full > $OUT/r05_laikago4096_bench.json 2> $OUT/bench.err
+           python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r05_driver20_bench.json 2>> $OUT/bench.err
+           for C in minicheetah4096 mixed8192; do python3 bench.py --full --no-cpu-baseline --config $C > $OUT/r05_${C}_bench.json 2>> $OUT/bench.err; done
+           python3 bench.py --full --no-cpu-baseline --no-randomizer > $OUT/r05_laikago4096_norand_bench.json 2>> $OUT/bench.err ;;
 profiles)  bash tools/profile_all.sh r05 > $OUT/profile_all.log 2>&1 ;;
 train)     python3 train.py --iters 24000 --log $OUT/r05_train_laikago_pace_fused.json --save $OUT/r05_laikago_pace_scratch.zip > $OUT/train.log 2>&1
            python3 train.py --eval $OUT/r05_laikago_pace_scratch.zip > $OUT/r05_train_eval.txt 2>&1 ;;

@@ -26,10 +26,10 @@ mc)        python3 tools/identify_r6.py run --robot mini_cheetah --fit minicheet
            python3 tools/identify_r6.py minimal --record $OUT/r06_mc_identify.json --out $OUT/r06_mc_minimal.json > $OUT/r06_mc_minimal.txt 2>&1 ;;
 probe)     python3 tools/policy_probe.py --robots 1024 --seeds 1 2 --out $OUT/r06_policy_probe.json > $OUT/r06_policy_probe.txt 2>&1 ;;
 drift)     python3 tools/drift_floor_spread.py --runs 12 --out-dir $OUT > $OUT/drift_floor_spread.log 2>&1 ;;
-bench)     python3 bench.py --repeats 5 > $OUT/r06_laikago4096_bench.json 2> $OUT/bench.err
-           python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r06_driver20_bench.json 2>> $OUT/bench.err
-           for C in minicheetah4096 mixed8192; do python3 bench.py --no-cpu-baseline --repeats 5 --config $C > $OUT/r06_${C}_bench.json 2>> $OUT/bench.err; done
-           python3 bench.py --no-cpu-baseline --no-randomizer > $OUT/r06_laikago4096_norand_bench.json 2>> $OUT/bench.err ;;
+bench)     python3 bench.py --full --repeats 5 > $OUT/r06_laikago4096_bench.json 2> $OUT/bench.err
+           python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r06_driver20_bench.json 2>> $OUT/bench.err
+           for C in minicheetah4096 mixed8192; do python3 bench.py --full --no-cpu-baseline --repeats 5 --config $C > $OUT/r06_${C}_bench.json 2>> $OUT/bench.err; done
+           python3 bench.py --full --no-cpu-baseline --no-randomizer > $OUT/r06_laikago4096_norand_bench.json 2>> $OUT/bench.err ;;
 profiles)  bash tools/profile_all.sh r06 > $OUT/profile_all.log 2>&1 ;;
 train)     python3 train.py --iters 24000 --log $OUT/r06_train_laikago_pace_fused.json --save $OUT/r06_laikago_pace_scratch.zip > $OUT/train.log 2>&1
            python3 train.py --eval $OUT/r06_laikago_pace_scratch.zip > $OUT/r06_train_eval.txt 2>&1 ;;
