@@ -248,6 +248,19 @@ int32_t orr_set_motion(orr_handle* h, int32_t clip_id, const float* frames_dev, 
  * episode log float[ep_log_capacity][2] = (return, length) (may be NULL / 0). */
 int32_t orr_bind(orr_handle* h, void* state_dev, int64_t* counters_dev, float* ep_log_dev, int32_t ep_log_capacity);
 
+/* clip set of a robot type (ImitationTask with several ref_motion_filenames: _sample_ref_motion, imitation_task.py:694-701,1077-1085):
+ * n = 1 .. ORR_MAX_CLIPS ids, each loaded with orr_set_motion (repeats allowed).  At every reset of a robot of that type (orr_reset and
+ * the auto-reset inside orr_step) its CLIP_ID becomes clip_ids[(m * n) >> 24], m = the 24-bit integer of draw 28 of the episode's
+ * (seed, robot index, episode) stream (Philox block 7, word 0; draws 0..27 keep their meaning), before anything reads the clip.
+ * While some type's set has more than one clip, orr_step and orr_reset launch the multi-clip variants of the kernels (one wave per SIMD
+ * at any batch size; refused together with friction anchors).  A type without a set keeps the record's CLIP_ID.  A rejected call
+ * changes nothing. */
+int32_t orr_set_clip_set(orr_handle* h, int32_t robot_type, const int32_t* clip_ids_host, int32_t n);
+
+/* clip log int32[ep_log_capacity] (device; NULL unbinds): while the multi-clip variants run, episode-log row `slot` also gets the
+ * clip the ending episode played in clip_log[slot].  The capacity is orr_bind's. */
+int32_t orr_bind_clip_log(orr_handle* h, int32_t* clip_log_dev);
+
 /* replaces WrapperEnv.reset (wrapper_env.py:87-107): mask_dev NULL = all robots; obs_dev [N,160]
  * (rows of robots that are not reset are left untouched). */
 int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream);

@@ -13,10 +13,11 @@ from . import _abi
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG_DIR, "csrc", "orr_kernels.hip")
 SRC_ANCHOR = os.path.join(PKG_DIR, "csrc", "orr_kernels_anchor.hip")   # the friction-anchor variants of the step kernel (ABI v5): their own translation unit
+SRC_MULTICLIP = os.path.join(PKG_DIR, "csrc", "orr_kernels_multiclip.hip")   # the clip-set variants of the step and reset kernels: their own unit
 SRC_W2 = os.path.join(PKG_DIR, "csrc", "orr_kernels_w2.hip")      # the two-waves-per-SIMD step kernel: its own translation unit + flags
 SRC_POLICY = os.path.join(PKG_DIR, "csrc", "orr_policy.hip")
 SRC_LEARNER = os.path.join(PKG_DIR, "csrc", "orr_learner.hip")    # the non-GEMM part of the PPO update (include/openroborl_learner.h)
-DEPS = [SRC, SRC_W2, SRC_ANCHOR, SRC_POLICY, SRC_LEARNER] + [os.path.join(PKG_DIR, "csrc", h) for h in ("orr_device.h", "orr_robot_io.h", "orr_physics.h", "orr_task.h")] + [
+DEPS = [SRC, SRC_W2, SRC_ANCHOR, SRC_MULTICLIP, SRC_POLICY, SRC_LEARNER] + [os.path.join(PKG_DIR, "csrc", h) for h in ("orr_device.h", "orr_robot_io.h", "orr_physics.h", "orr_task.h")] + [
         os.path.join(os.path.dirname(PKG_DIR), "include", "openroborl_hip.h"),
         os.path.join(os.path.dirname(PKG_DIR), "include", "openroborl_policy.h"),
         os.path.join(os.path.dirname(PKG_DIR), "include", "openroborl_learner.h")]
@@ -50,7 +51,7 @@ HIPCC_FLAGS_W2 = ["-Os" if f == "-O2" else ("-amdgpu-sched-strategy=iterative-ma
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
     "orr_layout_offset", "orr_layout_size", "orr_layout_is_int", "orr_sizeof_config", "orr_sizeof_model",
-    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_bind", "orr_reset", "orr_step",
+    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_bind_clip_log", "orr_bind", "orr_reset", "orr_step",
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
@@ -135,6 +136,7 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
             obj_env = os.path.join(PKG_DIR, "csrc", "orr_kernels%s.o" % tag)
             obj_w2 = os.path.join(PKG_DIR, "csrc", "orr_kernels_w2%s.o" % tag)
             obj_an = os.path.join(PKG_DIR, "csrc", "orr_kernels_anchor%s.o" % tag)
+            obj_mc = os.path.join(PKG_DIR, "csrc", "orr_kernels_multiclip%s.o" % tag)
             obj_pol = os.path.join(PKG_DIR, "csrc", "orr_policy%s.o" % tag)
             obj_lrn = os.path.join(PKG_DIR, "csrc", "orr_learner%s.o" % tag)
             tmp_so = out_path + tag + ".tmp"
@@ -142,10 +144,12 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
                     [HIPCC] + flags_w2 + ["-o", obj_w2, SRC_W2],
                     # the friction-anchor variants of the step kernel (optional physics feature): the main unit's flags, their own unit
                     [HIPCC] + [f for f in flags if not f.startswith("-DORR_SOURCE_HASH")] + ["-o", obj_an, SRC_ANCHOR],
+                    # the clip-set variants of the step and reset kernels (orr_set_clip_set): the main unit's flags, their own unit
+                    [HIPCC] + [f for f in flags if not f.startswith("-DORR_SOURCE_HASH")] + ["-o", obj_mc, SRC_MULTICLIP],
                     # the policy forward pass (matrix cores) is its own translation unit with the compiler's default scheduling
                     [HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", "-o", obj_pol, SRC_POLICY],
                     [HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", "-o", obj_lrn, SRC_LEARNER],
-                    [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp_so, obj_env, obj_w2, obj_an, obj_pol, obj_lrn]]
+                    [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp_so, obj_env, obj_w2, obj_an, obj_mc, obj_pol, obj_lrn]]
             try:
                 procs = []
                 for cmd in cmds[:-1]:           # the compiles are independent: run them side by side
@@ -160,7 +164,7 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
                 subprocess.check_call(cmds[-1])
                 os.replace(tmp_so, out_path)
             finally:
-                for o in (obj_env, obj_w2, obj_an, obj_pol, obj_lrn, tmp_so):
+                for o in (obj_env, obj_w2, obj_an, obj_mc, obj_pol, obj_lrn, tmp_so):
                     if os.path.exists(o):
                         os.remove(o)
         finally:
@@ -216,6 +220,10 @@ def load():
     L.orr_set_model.argtypes = [vp, C.c_int32, C.POINTER(_abi.OrrModel)]
     L.orr_set_motion.restype = C.c_int32
     L.orr_set_motion.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_float)]
+    L.orr_set_clip_set.restype = C.c_int32
+    L.orr_set_clip_set.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+    L.orr_bind_clip_log.restype = C.c_int32
+    L.orr_bind_clip_log.argtypes = [vp, vp]
     L.orr_bind.restype = C.c_int32
     L.orr_bind.argtypes = [vp, vp, vp, vp, C.c_int32]
     L.orr_reset.restype = C.c_int32

@@ -110,6 +110,11 @@ constexpr int kModelLdsWords = (int)(sizeof(ModelHot) / 4);
 struct DevTables {
   DevModel model[ORR_MAX_ROBOT_TYPES];
   DevClip clip[ORR_MAX_CLIPS];
+  // clip sets (orr_set_clip_set): read by the multi-clip variants of the kernels only (orr_kernels_multiclip.hip).  APPENDED: the fields
+  // above keep their offsets, so the default kernels see the table they always saw
+  int clip_set[ORR_MAX_ROBOT_TYPES][ORR_MAX_CLIPS];   // a type's set = 64 bytes, one word per lane of a robot
+  int clip_set_n[ORR_MAX_ROBOT_TYPES];                // 0 = no set: a reset keeps the record's CLIP_ID
+  int* clip_log;                                      // orr_bind_clip_log: clip of each logged episode (row = episode-log slot), or NULL
 };
 
 // Replay inputs of the parity entry points orr_debug_replay_reset / orr_debug_replay_step (kernel MODE 2): the scripted states,

@@ -8,13 +8,14 @@
 // Device code by phase: orr_device.h (LDS image, math, DPP helpers), orr_robot_io.h (record load / store, latency
 // ring), orr_physics.h (one physics sub-step), orr_task.h (motion clips, reward, observation, reset); this file holds
 // the two kernels and the C-ABI.
-// Three translation units are built from this file (the third, orr_kernels_anchor.hip, holds the friction-anchor variants: see launch_step_anchor).  The main one (everything) is compiled with the instruction-level-parallelism
+// Four translation units are built from this file (the third, orr_kernels_anchor.hip, holds the friction-anchor variants: see launch_step_anchor;
+// the fourth, orr_kernels_multiclip.hip, the clip-set variants of the step and reset kernels: see launch_step_multiclip).  The main one (everything) is compiled with the instruction-level-parallelism
 // scheduler: one wave per SIMD, ~300 registers, nothing to hide latency but the wave's own independent instructions.  The second
 // one (orr_kernels_w2.hip: #define ORR_TU_STEP_W2 + #include of this file) holds ONLY the two-waves-per-SIMD instantiation of the step
 // kernel and is compiled with an occupancy-minded scheduler (-Os + iterative-maxocc since the end of round 4: openroborl_amd/_lib.py HIPCC_FLAGS_W2; the compiler's default before): at
 // 256 registers that variant spills, and the ILP schedule's longer live ranges cost it 8 % (0.382 vs 0.352 ms at 8192 robots; the default
 // scheduler costs the one-wave variant 9 %).
-#if defined(ORR_TU_STEP_W2) || defined(ORR_TU_STEP_ANCHOR)
+#if defined(ORR_TU_STEP_W2) || defined(ORR_TU_STEP_ANCHOR) || defined(ORR_TU_MULTICLIP)
 #undef ORR_PHASE_TIMERS      // the development timers live in the main translation unit only
 #define ORR_TU_SECONDARY 1   // a unit that holds only instantiations of the step kernel and their launchers
 #endif
@@ -101,13 +102,15 @@ using namespace orr;
   const int robot = in_range ? robot_raw : 0; /* a padding lane group shadows robot 0 and never stores */ \
   float* rec = P.state + (size_t)robot * ORR_STATE_STRIDE
 
-#ifndef ORR_TU_SECONDARY
+#if !defined(ORR_TU_SECONDARY) || defined(ORR_TU_MULTICLIP)
+// CLIPS: the multi-clip variant (orr_kernels_multiclip.hip): every reset draws the robot's clip from its type's clip set
+template <bool CLIPS = false>
 __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t* mask, float* obs_out, const float* uniforms) {
   ORR_PROLOGUE();
   const bool valid = in_range && !(mask && !mask[robot]);
   load_robot(P, rec, S, lane);
   const long long total = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
-  reset_robot(P, rec, S, lane, valid, total, obs, uniforms ? uniforms + (size_t)robot * 28 : nullptr);
+  reset_robot<CLIPS>(P, rec, S, lane, valid, total, obs, uniforms ? uniforms + (size_t)robot * 28 : nullptr);
   WSYNC();
   store_robot(rec, S, lane, valid);
   // a new episode: no cached contact points (ANCHOR, ANCHOR_VALID: 28 words behind the ring).  Unconditional: friction anchors may be switched
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
   if (obs_out && valid)
     for (int i = lane; i < ORR_OBS_DIM; i += kLanes) obs_out[(size_t)robot * ORR_OBS_DIM + i] = obs[i];
 }
-#endif  // !ORR_TU_SECONDARY
+#endif  // !ORR_TU_SECONDARY || ORR_TU_MULTICLIP
 
 // mode 0: full env step.  mode 1 (debug / parity of row C): nsub physics sub-steps with the given
 // motor torques (actions = torques), no robot or task logic.  mode 2 (parity of everything BUT row C): a full env step in
@@ -143,7 +146,9 @@ constexpr int step_wpb() { return MODE == 0 && WPE == 1 ? ORR_WPB : 1; }
 // ANCHOR (ABI v5): the variant for robot types with orr_model::friction_anchor - Bullet's cached toe contact points (orr_physics.h:
 // AnchorState).  Same source; its own instantiations (one wave per SIMD whatever the batch size: an optional physics feature, not the
 // measured path), so that the default kernels carry nothing of it.
-template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false>
+// CLIPS: the multi-clip variant (orr_kernels_multiclip.hip, one wave per SIMD whatever the batch size): the auto-reset draws the new
+// episode's clip from the robot type's clip set (reset_robot<true>) and the episode log also records the clip of the ending episode
+template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false>
 __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
   ORR_PROLOGUE_W((step_wpb<MODE, WPE>()));
@@ -436,23 +441,29 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
   PT(13);
   if (reason != 0) {
     float log_ret = 0.0f, log_len = 0.0f;
+    int log_clip = 0;     // CLIPS: the clip the ending episode played, read before reset_robot draws the next one
     const bool logs = lane == 0 && valid;
     const unsigned long long slot = log_slot;
     if (lane == 0) {
       log_ret = S.s[O(EP_RETURN)]; log_len = (float)geti(S, O(EP_STEP));
+      if constexpr (CLIPS) log_clip = geti(S, O(CLIP_ID));
       S.s[O(LAST_EP_RETURN)] = log_ret;
       seti(S, O(LAST_EP_LEN), geti(S, O(EP_STEP)));
     }
     WSYNC();
     if (c.flags & ORR_FLAG_AUTO_RESET) {
       PT(31);
-      reset_robot(P, rec, S, lane, valid, total_snapshot, obs);
+      reset_robot<CLIPS>(P, rec, S, lane, valid, total_snapshot, obs);
       if constexpr (ANCHOR) AS = AnchorState{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};   // a new episode: no cached contact points
     }
     if (logs && P.ep_log) {
       if (slot < (unsigned long long)P.ep_log_cap) {
         P.ep_log[2 * slot] = log_ret;
         P.ep_log[2 * slot + 1] = log_len;
+        if constexpr (CLIPS) {
+          int* const clip_log = P.tab->clip_log;
+          if (clip_log) clip_log[slot] = log_clip;
+        }
       } else {
         atomicAdd((unsigned long long*)&P.counters[ORR_CNT_EPLOG_DROPPED], 1ull);
       }
@@ -501,8 +512,23 @@ hipError_t launch_step_w2(const KParams& P, int waves, hipStream_t stream, const
 // share its functions (round 5: +6 instructions per sub-step, +0.7 % run time with the anchor variants compiled alongside)
 hipError_t launch_step_anchor(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done);
 hipError_t launch_physics_anchor(const KParams& P, int waves, hipStream_t stream, const float* torques, uint8_t* fall, int nsub);
+// launchers of the multi-clip instantiations (env step; reset), defined in the fourth translation unit (orr_kernels_multiclip.hip) for the
+// same reason
+hipError_t launch_step_multiclip(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done);
+hipError_t launch_reset_multiclip(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs);
 }
-#ifdef ORR_TU_STEP_ANCHOR
+#ifdef ORR_TU_MULTICLIP
+namespace orr {
+hipError_t launch_step_multiclip(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done) {
+  hipLaunchKernelGGL((orr_step_kernel<0, 1, false, true>), dim3(waves), dim3(64), 0, stream, P, actions, obs, reward, done, 0, ReplayArgs{});
+  return hipGetLastError();
+}
+hipError_t launch_reset_multiclip(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs) {
+  hipLaunchKernelGGL((orr_reset_kernel<true>), dim3(waves), dim3(64), 0, stream, P, mask, obs, (const float*)nullptr);
+  return hipGetLastError();
+}
+}  // namespace orr
+#elif defined(ORR_TU_STEP_ANCHOR)
 namespace orr {
 hipError_t launch_step_anchor(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done) {
   hipLaunchKernelGGL((orr_step_kernel<0, 1, true>), dim3(waves), dim3(64), 0, stream, P, actions, obs, reward, done, 0, ReplayArgs{});
@@ -585,6 +611,7 @@ struct orr_handle {
   int simds;          // SIMDs of the device (4 per CU): a batch of more waves than that runs the two-waves-per-SIMD variant of the step kernel
   int force_wpe;      // ORR_STEP_WAVES_PER_EU (0 = automatic)
   uint32_t anchor_types;   // bit t = robot type t has orr_model::friction_anchor: launches run the ANCHOR variant of the step kernel
+  uint32_t multiclip_types;   // bit t = robot type t has a clip set of more than one clip: orr_step / orr_reset run the multi-clip variants
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -801,6 +828,34 @@ int32_t orr_set_motion(orr_handle* h, int32_t clip_id, const float* frames_dev, 
   return 0;
 }
 
+int32_t orr_set_clip_set(orr_handle* h, int32_t robot_type, const int32_t* clip_ids_host, int32_t n) {
+  if (!h || !clip_ids_host) return fail(-1, "orr_set_clip_set: null argument");
+  if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_clip_set: robot_type out of range");
+  if (n < 1 || n > ORR_MAX_CLIPS) return fail(-1, "orr_set_clip_set: a clip set holds 1 .. ORR_MAX_CLIPS clips");
+  int ids[ORR_MAX_CLIPS] = {0};
+  for (int i = 0; i < n; i++) {
+    const int id = clip_ids_host[i];
+    if (id < 0 || id >= ORR_MAX_CLIPS) return fail(-1, "orr_set_clip_set: clip id out of range");
+    if (!h->tab_host.clip[id].frames) return fail(-1, "orr_set_clip_set: clip id was not loaded with orr_set_motion");
+    ids[i] = id;
+  }
+  // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->clip_set[robot_type][0], ids, sizeof(ids), hipMemcpyHostToDevice), "orr_set_clip_set: hipMemcpy");
+  HIPCHK(hipMemcpy(&h->tab_dev->clip_set_n[robot_type], &n, sizeof(int), hipMemcpyHostToDevice), "orr_set_clip_set: hipMemcpy");
+  memcpy(h->tab_host.clip_set[robot_type], ids, sizeof(ids));
+  h->tab_host.clip_set_n[robot_type] = n;
+  if (n > 1) h->multiclip_types |= 1u << robot_type; else h->multiclip_types &= ~(1u << robot_type);
+  return 0;
+}
+
+int32_t orr_bind_clip_log(orr_handle* h, int32_t* clip_log_dev) {
+  if (!h) return fail(-1, "orr_bind_clip_log: null handle");
+  int* p = clip_log_dev;
+  HIPCHK(hipMemcpy(&h->tab_dev->clip_log, &p, sizeof(p), hipMemcpyHostToDevice), "orr_bind_clip_log: hipMemcpy");
+  h->tab_host.clip_log = p;
+  return 0;
+}
+
 int32_t orr_bind(orr_handle* h, void* state_dev, int64_t* counters_dev, float* ep_log_dev, int32_t ep_log_capacity) {
   if (!h || !state_dev || !counters_dev) return fail(-1, "orr_bind: null argument (state and counters are required)");
   if (((uintptr_t)state_dev & 15u) != 0) return fail(-1, "orr_bind: the state buffer must be 16-byte aligned (records move in 16-byte pieces)");
@@ -832,9 +887,16 @@ static KParams make_params(const orr_handle* h) {
   return P;
 }
 
+static const char kAnchorClipsMsg[] = ": friction anchors (orr_model::friction_anchor) and a clip set of more than one clip cannot be combined";
+
 int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
   if (!h || !h->state) return fail(-1, "orr_reset: handle not bound");
-  hipLaunchKernelGGL(orr_reset_kernel, dim3((h->cfg.num_robots + kRPW - 1) / kRPW), dim3(64), 0, (hipStream_t)stream, make_params(h), mask_dev, obs_dev,
+  if (h->multiclip_types) {   // some robot type has a clip set of more than one clip: every reset draws the episode's clip
+    if (h->anchor_types) { char m[256]; snprintf(m, sizeof(m), "orr_reset%s", kAnchorClipsMsg); return fail(-1, m); }
+    HIPCHK(launch_reset_multiclip(make_params(h), (h->cfg.num_robots + kRPW - 1) / kRPW, (hipStream_t)stream, mask_dev, obs_dev), "orr_reset: launch (clip sets)");
+    return 0;
+  }
+  hipLaunchKernelGGL(orr_reset_kernel<>, dim3((h->cfg.num_robots + kRPW - 1) / kRPW), dim3(64), 0, (hipStream_t)stream, make_params(h), mask_dev, obs_dev,
                      (const float*)nullptr);
   HIPCHK(hipGetLastError(), "orr_reset: launch");
   return 0;
@@ -846,7 +908,10 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
   if (((uintptr_t)obs_dev & 15u) != 0) return fail(-1, "orr_step: the observation buffer must be 16-byte aligned (it is written in 16-byte pieces)");
   const int waves = (h->cfg.num_robots + kRPW - 1) / kRPW;
   const bool two = h->force_wpe ? h->force_wpe == 2 : waves > h->simds;
-  if (h->anchor_types) {   // some robot type has friction anchors: the ANCHOR variant (one wave per SIMD, any batch size)
+  if (h->multiclip_types) {   // some robot type has a clip set of more than one clip: the multi-clip variant (one wave per SIMD, any batch size)
+    if (h->anchor_types) { char m[256]; snprintf(m, sizeof(m), "orr_step%s", kAnchorClipsMsg); return fail(-1, m); }
+    HIPCHK(launch_step_multiclip(make_params(h), waves, (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev), "orr_step: launch (clip sets)");
+  } else if (h->anchor_types) {   // some robot type has friction anchors: the ANCHOR variant (one wave per SIMD, any batch size)
     HIPCHK(launch_step_anchor(make_params(h), waves, (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev), "orr_step: launch (friction anchors)");
   } else if (two) {
     HIPCHK(launch_step_w2(make_params(h), waves, (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev), "orr_step: launch (two waves per SIMD)");
@@ -910,7 +975,7 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
 }
 int32_t orr_debug_replay_reset(orr_handle* h, const float* uniforms_dev, float* obs_dev, void* stream) {
   if (!h || !h->state || !uniforms_dev) return fail(-1, "orr_debug_replay_reset: bad argument");
-  hipLaunchKernelGGL(orr_reset_kernel, dim3((h->cfg.num_robots + kRPW - 1) / kRPW), dim3(64), 0, (hipStream_t)stream, make_params(h),
+  hipLaunchKernelGGL(orr_reset_kernel<>, dim3((h->cfg.num_robots + kRPW - 1) / kRPW), dim3(64), 0, (hipStream_t)stream, make_params(h),
                      (const uint8_t*)nullptr, obs_dev, uniforms_dev);
   HIPCHK(hipGetLastError(), "orr_debug_replay_reset: launch");
   return 0;

@@ -367,6 +367,9 @@ __device__ static void sensors_push(Shared& S, int lane, bool fill_all) {
 // imitation_task.py:166-199); SURVEY.md Appendix A.2.  Writes the 160-d observation into obs (LDS).
 // ================================================================================================
 // uni_replay (parity replay only, else NULL): 28 draws in [0, 1) that replace the Philox stream
+// CLIPS (the multi-clip variants, orr_kernels_multiclip.hip): the episode's clip is drawn from the robot type's clip set (DevTables::clip_set)
+// with draw 28 (Philox block 7, word 0) before anything reads the clip, and CLIP_ID / S.clip hold it from then on
+template <bool CLIPS = false>
 __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int lane, bool valid, long long total_step_count, float* obs,
                                    const float* uni_replay = nullptr) {
   const orr_config& c = P.cfg;
@@ -404,15 +407,35 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
   // frames; the model's mass table), the stages that need nothing from memory run while those loads are in flight.
   // 4a. all 28 draws of the episode (0..25 randomiser, 26 ref-state-init, 27 time offset) = 7 Philox blocks: lane b < 7 evaluates
   // block b once and parks its four numbers in LDS
-  float* draws = S.ph.end.red + 24;    // 28 words
+  float* draws = S.ph.end.red + 24;    // 28 words (CLIPS: 32, block 7 in red[52..55], free until ring entry #2 takes red[56..75])
   static_assert(kLanes == 16, "reset_robot / sample_poses assume 16 lanes per robot");
-  if (lane < 7) {
+  int set_id = 0, set_n = 0;
+  if constexpr (CLIPS) {   // the type's clip set, one id per lane, in flight while the Philox blocks are evaluated
+    static_assert(ORR_MAX_CLIPS == kLanes, "one clip-set entry per lane");
+    typedef const int __attribute__((address_space(1)))* gip;
+    const int type = geti(S, O(ROBOT_TYPE));
+    set_id = ((gip)&P.tab->clip_set[type][0])[lane];
+    set_n = ((gip)&P.tab->clip_set_n[0])[type];
+  }
+  if (lane < (CLIPS ? 8 : 7)) {
     float u4[4];
-    if (uni_replay) { u4[0] = uni_replay[4 * lane]; u4[1] = uni_replay[4 * lane + 1]; u4[2] = uni_replay[4 * lane + 2]; u4[3] = uni_replay[4 * lane + 3]; }
+    if (uni_replay && (!CLIPS || lane < 7)) { u4[0] = uni_replay[4 * lane]; u4[1] = uni_replay[4 * lane + 1]; u4[2] = uni_replay[4 * lane + 2]; u4[3] = uni_replay[4 * lane + 3]; }
     else philox_block(c.seed, robot, ep, (uint32_t)lane, u4);
     draws[4 * lane] = u4[0]; draws[4 * lane + 1] = u4[1]; draws[4 * lane + 2] = u4[2]; draws[4 * lane + 3] = u4[3];
   }
   WSYNC();
+  if constexpr (CLIPS) {
+    // draw 28 -> k = (m n) >> 24, m = its 24-bit integer (u = m / 2^24 exactly): integer arithmetic, uniform over the n entries.  The lane
+    // that holds set[k] writes CLIP_ID; then the clip header is staged again, one word per lane (as load_robot does)
+    const uint32_t m = (uint32_t)(draws[28] * 16777216.0f);
+    const int k = (int)((m * (uint32_t)set_n) >> 24);
+    if (set_n > 0 && lane == k) seti(S, O(CLIP_ID), set_id);
+    WSYNC();
+    const unsigned int* cg = reinterpret_cast<const unsigned int*>(&P.tab->clip[geti(S, O(CLIP_ID))]);
+    unsigned int* cl = reinterpret_cast<unsigned int*>(&S.clip);
+    if (lane < (int)(sizeof(DevClip) / 4)) cl[lane] = cg[lane];
+    WSYNC();
+  }
   PT(24);
   // 5a. task reset (imitation_task.py:183-199, 694-732, 1103-1110): start time -> frame loads issued
   const DevClip& clip = S.clip;

@@ -68,6 +68,52 @@ def observation_space(clips):
     return Box(np.concatenate([pl, tl]), np.concatenate([ph, th]), dtype=np.float32)
 
 
+def motion_spec(motion_file, robot_names, mixed=False):
+    """The motion-file argument -> (files in clip-id order, {robot name: clip set = list of clip ids}).
+
+    Homogeneous batch (robot_names[0]): a path, or a list of paths = the robot's clip set (ImitationTask's ref_motion_filenames:
+    every reset draws the episode's clip from it, imitation_task.py:694-701,1077-1085).  Mixed batch: one entry per robot name, each a
+    path or a list.  Nothing is de-duplicated: a file listed twice is two clips (twice the weight).  A robot's initial CLIP_ID is its
+    set's first entry."""
+    def as_list(e):
+        if isinstance(e, (list, tuple)):
+            if not e:
+                raise ValueError("a motion-file list must not be empty")
+            for f in e:
+                if isinstance(f, (list, tuple)):
+                    raise ValueError("a clip set is a flat list of motion files")
+            return list(e)
+        if e is None:
+            raise ValueError("no input robot or task")
+        return [e]
+    names = list(robot_names)
+    if mixed:
+        if not isinstance(motion_file, (list, tuple)) or len(motion_file) != len(names):
+            raise ValueError("mixed batch needs one motion file (or list of motion files) per robot name")
+        entries = list(motion_file)
+    else:
+        names, entries = names[:1], [motion_file]
+    files, sets = [], {}
+    for name, e in zip(names, entries):
+        ids = []
+        for f in as_list(e):
+            ids.append(len(files))
+            files.append(f)
+        sets[name] = ids
+    if len(files) > _abi.MAX_CLIPS:
+        raise ValueError("%d motion clips; a batch holds at most %d" % (len(files), _abi.MAX_CLIPS))
+    return files, sets
+
+
+CLIP_DRAW = 28      # index of the clip draw in a reset's Philox stream (block 7, word 0; draws 0..27: randomiser, ref-state-init, time offset)
+
+
+def clip_draw_index(m, n):
+    """The entry of an n-clip set a reset picks (csrc/orr_task.h, reset_robot<true>): (m * n) >> 24, m = the 24-bit integer of draw
+    CLIP_DRAW (the draw in [0, 1) is m / 2^24).  Integer arithmetic; works on numpy integer arrays."""
+    return (np.asarray(m, dtype=np.int64) * int(n)) >> 24
+
+
 def action_space():
     """minitaur.py:145-148."""
     return Box(np.array([-2 * math.pi] * 12), np.array([2 * math.pi] * 12), dtype=np.float32)
@@ -102,10 +148,9 @@ class VecQuadrupedEnv(object):
             enable_randomizer = bool(params.get("enable_env_randomizer", True)) and mode == "train"   # run.py:205-206
         num_robot = int(num_robot if num_robot is not None else params.get("num_robot", 1))
         seed = int(seed if seed is not None else params.get("seed", 0))
-        motion_file = motion_file or params.get("motion_file")
+        motion_file = motion_file if motion_file is not None else params.get("motion_file")
         if motion_file is None:
             raise ValueError("no input robot or task")                   # quadruped_gym_env.py:50-51
-        motion_files = list(motion_file) if isinstance(motion_file, (list, tuple)) else [motion_file]
         self.num_robot = num_robot
         self.mode = mode
         self.cfg = cfgmod.make_config(num_robot, sim_params=sim, mode=mode, enable_randomizer=enable_randomizer, seed=seed,
@@ -136,15 +181,12 @@ class VecQuadrupedEnv(object):
                 if k not in m:
                     raise ValueError("unknown model table entry %r" % (k,))
                 m[k] = np.asarray(v, dtype=np.asarray(m[k]).dtype).reshape(np.shape(m[k])) if np.ndim(m[k]) else type(m[k])(v)
-        # clips: one per robot type in a mixed batch, else the task's clip
+        # clips: a clip set per robot type (one clip or several: every reset draws the episode's clip from the set), see motion_spec
+        motion_files, self.clip_sets = motion_spec(motion_file, self.robot_names, mixed=bool(mixed_robots))
         self.clips = [motion.MotionClip(f) for f in motion_files]
-        if mixed_robots:
-            if len(self.clips) != len(self.robot_names):
-                raise ValueError("mixed batch needs one motion file per robot name")
-            type_to_clip = {robots.ROBOT_TYPE_ID[n]: i for i, n in enumerate(self.robot_names)}
-            clip_id = np.array([type_to_clip[t] for t in robot_type], dtype=np.int32)
-        else:
-            clip_id = np.zeros(num_robot, dtype=np.int32)
+        type_to_clip = {robots.ROBOT_TYPE_ID[n]: ids[0] for n, ids in self.clip_sets.items()}
+        clip_id = np.array([type_to_clip[t] for t in robot_type], dtype=np.int32)
+        self.multi_clip = any(len(ids) > 1 for ids in self.clip_sets.values())
         self.robot_type = robot_type
         self.clip_id = clip_id
 
@@ -162,6 +204,9 @@ class VecQuadrupedEnv(object):
             cd = (C.c_float * 4)(*[float(x) for x in c.cycle_delta])
             _lib.check(self.L.orr_set_motion(self.h, i, fr.data_ptr(), fv.data_ptr(), c.num_frames,
                                              float(c.frame_duration), c.flags, cd), self.L)
+        for name, ids in self.clip_sets.items():
+            arr = (C.c_int32 * len(ids))(*ids)
+            _lib.check(self.L.orr_set_clip_set(self.h, robots.ROBOT_TYPE_ID[name], arr, len(ids)), self.L)
         self.layout = statemod.Layout(self.L, "orr")
         idx = np.arange(num_robot, dtype=np.int32) + int(robot_index_offset)
         st = statemod.default_state(self.layout, num_robot, self.models, robot_type, clip_id, idx,
@@ -172,6 +217,11 @@ class VecQuadrupedEnv(object):
         self.ep_log = torch.zeros((max(int(ep_log_capacity), 1), 2), dtype=torch.float32, device=self.device)
         _lib.check(self.L.orr_bind(self.h, self.state.data_ptr(), self.counters.data_ptr(), self.ep_log.data_ptr(),
                                    int(ep_log_capacity)), self.L)
+        # clip of each logged episode (row = episode-log row): only where some set has more than one clip (the multi-clip kernels write it)
+        self.clip_log = None
+        if self.multi_clip:
+            self.clip_log = torch.zeros(max(int(ep_log_capacity), 1), dtype=torch.int32, device=self.device)
+            _lib.check(self.L.orr_bind_clip_log(self.h, self.clip_log.data_ptr()), self.L)
         # the three outputs of a step are views into ONE device buffer [obs N x 160 f32 | reward N f32 | done N u8], so that a host-side
         # consumer (LegacyListEnv) fetches them with a single copy
         nb_obs, nb_rew = num_robot * _abi.OBS_DIM * 4, num_robot * 4
@@ -326,6 +376,20 @@ class VecQuadrupedEnv(object):
                 "last_done_reason": {k: int(((reasons & bit) != 0).sum()) for k, bit in names},
                 "max_episode_steps": int(self.field_int("MAX_EP_STEPS").max().item())}
 
+    def active_clip_ids(self):
+        """The clip each robot is playing (its CLIP_ID word): int32 [N] on the device."""
+        return self.field_int("CLIP_ID")[:, 0].clone()
+
+    def episode_returns_by_clip(self):
+        """{clip id: (mean return, episodes)} of the episodes logged since the log was last cleared, without clearing it (syncs).
+        Needs a clip set of more than one clip (see episode_log)."""
+        if self.clip_log is None:
+            raise ValueError("no clip log: no robot type of this env has a clip set of more than one clip")
+        k = int(self.torch.clamp(self.counters[_abi.CNT_EPISODES], max=self.ep_log.shape[0]).item())
+        ret = self.ep_log[:k, 0].double().cpu().numpy()
+        cid = self.clip_log[:k].cpu().numpy()
+        return {int(c): (float(ret[cid == c].mean()), int((cid == c).sum())) for c in np.unique(cid)}
+
     def episode_log_device(self):
         """(log[K,2] snapshot, count, dropped) of the episodes finished since the last call, all on the device and
         without a host sync (count / dropped are 0-d int64 tensors; rows >= count are stale); clears the log."""
@@ -342,14 +406,19 @@ class VecQuadrupedEnv(object):
         _lib.check(self.L.orr_episode_stats(self.h, float(total_timesteps), int(capacity), out.data_ptr(), self._stream()), self.L)
         return out
 
-    def episode_log(self, with_dropped=False):
-        """(returns[K], lengths[K]) of the episodes finished since the last call (+ the number of episodes that did not fit
-        the device log when with_dropped); clears the log.  Syncs."""
+    def episode_log(self, with_dropped=False, with_clip=False):
+        """(returns[K], lengths[K]) of the episodes finished since the last call (+ clip_ids[K] int32, the clip each of them played,
+        when with_clip; + the number of episodes that did not fit the device log when with_dropped); clears the log.  Syncs.
+        with_clip needs a clip set of more than one clip (the clip log exists only then): ValueError otherwise."""
+        if with_clip and self.clip_log is None:
+            raise ValueError("no clip log: no robot type of this env has a clip set of more than one clip")
+        clip_log = self.clip_log.clone() if with_clip else None
         log, cnt, dropped = self.episode_log_device()
         k = int(cnt.item())
+        out = (log[:k, 0], log[:k, 1]) + ((clip_log[:k],) if with_clip else ())
         if with_dropped:
-            return log[:k, 0], log[:k, 1], int(dropped.item())
-        return log[:k, 0], log[:k, 1]
+            return out + (int(dropped.item()),)
+        return out
 
 
 class LegacyListEnv(object):

@@ -12,6 +12,8 @@ import os
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -26,6 +28,9 @@ def main():
     ap.add_argument("--minibatch", type=int, default=16384)
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--model-file", default="")
+    ap.add_argument("--motion-file", action="append", default=None,
+                    help="reference motion clip (repeatable; overrides the task YAML's motion_file): several = the clip set every reset "
+                         "draws the episode's clip from (ImitationTask's ref_motion_filenames)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
     ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip")
@@ -59,7 +64,7 @@ def main():
     dev = torch.device("cuda", 0 if os.environ.get("ORR_BENCH_SINGLE_DEVICE") else local)
     torch.cuda.set_device(dev)
     env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
-                          device=dev, num_procs=world, robot_index_offset=rank * args.num_robot)
+                          device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     model = ppo.ActorCritic(dev, params=params, seed=args.seed)                     # same seed -> identical replicas
     if not args.torch_policy:
@@ -106,13 +111,18 @@ def main():
         # (> 1 rank, or ORR_FORCE_DIST=1: the one-rank rehearsal of the several-ranks path on RCCL runs the check too)
         if (world > 1 or os.environ.get("ORR_FORCE_DIST", "0") == "1") and args.sync_check_every > 0 and it % args.sync_check_every == args.sync_check_every - 1 and hasattr(learner, "check_synced"):
             learner.check_synced()                            # like MpiAdam every 100 updates (mpi_adam.py:47-48)
+        log_it = rank == 0 and (it % 10 == 0 or it == args.iters - 1)
+        # this rank's episodes of the segment by clip (read before the gather below clears the log)
+        by_clip = env.episode_returns_by_clip() if log_it and env.multi_clip else None
         stats = odist.gather_env_episodes(env, args.horizon)   # means come from the exact per-rank sums, not the truncated list
-        if rank == 0 and (it % 10 == 0 or it == args.iters - 1):
+        if log_it:
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2),
                    "mean_step_reward": round(float(buf["rewards"].mean()), 4),
                    "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2),
                    "episodes": stats.sums[0], "episodes_unlogged": stats[3] - max(stats.sums[0] - int(stats[0].numel()), 0),
                    "max_ep_steps": int(env.field_int("MAX_EP_STEPS").max()), "surr": round(float(surr), 4), "vf": round(float(vf), 4)}
+            if by_clip is not None:
+                rec["ep_ret_mean_by_clip"] = {clip_name(env, c): round(r, 2) for c, (r, _) in sorted(by_clip.items())}
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if rank == 0 and args.save:
@@ -125,15 +135,22 @@ def main():
         torch.distributed.destroy_process_group()
 
 
+def clip_name(env, clip_id):
+    """'<id>:<file name>' of a clip of the env (ids keep a file listed twice apart)."""
+    return "%d:%s" % (clip_id, os.path.splitext(os.path.basename(env.clips[clip_id].path))[0])
+
+
 def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     """run.py:151-183 (test): one full episode per robot with the policy mean; prints return / length statistics."""
     dev = torch.device("cuda", 0)
     n = min(args.num_robot, 1024)
-    env = VecQuadrupedEnv(task_name=args.task, num_robot=n, mode="test", auto_reset=False, seed=args.seed, device=dev)
+    env = VecQuadrupedEnv(task_name=args.task, num_robot=n, mode="test", auto_reset=False, seed=args.seed, device=dev,
+                          motion_file=args.motion_file)
     model = ppo.ActorCritic(dev, params=pol.load_parameters(args.eval))
     if not args.torch_policy:
         model.enable_fused()
     obs = env.reset()
+    clip_ids = env.active_clip_ids()             # the clip each robot's episode plays
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     ret = torch.zeros(n, device=dev)
     length = torch.zeros(n, device=dev)
@@ -146,10 +163,16 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
         alive &= ~done.bool()
         if not bool(alive.any()):
             break
-    print(json.dumps({"policy": args.eval, "task": args.task, "robots": n, "episode_limit": limit,
-                      "return_mean": round(float(ret.mean()), 2), "return_min": round(float(ret.min()), 2),
-                      "length_mean": round(float(length.mean()), 1), "full_length_fraction": round(float((length >= limit).float().mean()), 3),
-                      "reward_per_step": round(float((ret / length).mean()), 3)}))
+    rec = {"policy": args.eval, "task": args.task, "robots": n, "episode_limit": limit,
+           "return_mean": round(float(ret.mean()), 2), "return_min": round(float(ret.min()), 2),
+           "length_mean": round(float(length.mean()), 1), "full_length_fraction": round(float((length >= limit).float().mean()), 3),
+           "reward_per_step": round(float((ret / length).mean()), 3)}
+    if env.multi_clip:       # finish rate (full-length episodes) and robots per clip
+        full = (length >= limit).cpu().numpy()
+        cid = clip_ids.cpu().numpy()
+        rec["full_length_fraction_by_clip"] = {clip_name(env, int(c)): round(float(full[cid == c].mean()), 3) for c in np.unique(cid)}
+        rec["robots_by_clip"] = {clip_name(env, int(c)): int((cid == c).sum()) for c in np.unique(cid)}
+    print(json.dumps(rec))
     env.close()
 
 
