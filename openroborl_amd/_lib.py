@@ -65,9 +65,8 @@ def tuning_defines():
     """-D flags taken from the environment (tuning experiments).  They are part of the hash: a library built with them is not the
     shipped library, and setting them makes the in-tree library stale."""
     defs = []
-    for var in ("ORR_WAVES_PER_EU", "ORR_LANES_PER_ROBOT"):
-        if os.environ.get(var):
-            defs.append("-D%s=%d" % (var, int(os.environ[var])))
+    if os.environ.get("ORR_WAVES_PER_EU"):
+        defs.append("-DORR_WAVES_PER_EU=%d" % int(os.environ["ORR_WAVES_PER_EU"]))
     for d in os.environ.get("ORR_EXTRA_DEFS", "").split():
         defs.append("-D" + d)
     return defs

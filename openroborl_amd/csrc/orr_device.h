@@ -1,6 +1,6 @@
 // orr_device.h -- device-side building blocks of the quadruped env kernels (gfx950, wave64).
 //
-// A wavefront serves kRPW = 4 robots, 16 lanes each (ORR_LANES_PER_ROBOT; 32 / 64 are kept for experiments).
+// A wavefront serves kRPW = 4 robots, 16 lanes each.
 // Lane roles inside a robot's lane group change phase by phase:
 //   motors      lanes 0..11   action filter / interpolation / clip / PD torque (minitaur.py:280-293,438-460,706-769)
 //   legs        leg = lane & 3, link = lane >> 2: forward dynamics of the 3-link leg chains (pybullet stepSimulation)
@@ -28,16 +28,11 @@
     __builtin_amdgcn_wave_barrier();        \
     asm volatile("" ::: "memory");          \
   } while (0)
-#define SCHED_FENCE()  // measured: fencing the scheduler RAISES spills (104 vs 0 at 256 VGPRs); kept for experiments
 
 namespace orr {
 
-#ifndef ORR_LANES_PER_ROBOT
-#define ORR_LANES_PER_ROBOT 16
-#endif
-constexpr int kLanes = ORR_LANES_PER_ROBOT;  // lanes of a wavefront that serve one robot (16 -> four robots per wave)
-constexpr int kRPW = 64 / kLanes;            // robots per wavefront
-static_assert(kLanes == 16 || kLanes == 32 || kLanes == 64, "a robot needs 16 row lanes");
+constexpr int kLanes = 16;        // lanes of a wavefront that serve one robot: one DPP row
+constexpr int kRPW = 64 / kLanes;  // robots per wavefront
 constexpr int kMaxRows = 28;  // 4 knee-friction + <=12 joint-limit + 12 contact rows
 constexpr int kHead = 308;    // words of the state record staged in LDS: everything before the ring (307) + one spare word (the non-finite guard's flag)
 
@@ -237,7 +232,6 @@ __device__ __forceinline__ void cross3(const float a[3], const float b[3], float
   float x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
   o[0] = x; o[1] = y; o[2] = z;
 }
-__device__ __forceinline__ float dot3(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ __forceinline__ void mv3(const float M[9], const float v[3], float o[3]) {
   float a = M[0] * v[0] + M[1] * v[1] + M[2] * v[2];
   float b = M[3] * v[0] + M[4] * v[1] + M[5] * v[2];
@@ -250,130 +244,11 @@ __device__ __forceinline__ void mtv3(const float M[9], const float v[3], float o
   float c = M[2] * v[0] + M[5] * v[1] + M[8] * v[2];
   o[0] = a; o[1] = b; o[2] = c;
 }
-__device__ __forceinline__ void mm3(const float A[9], const float B[9], float C[9]) {
-  float t[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) t[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
-#pragma unroll
-  for (int i = 0; i < 9; i++) C[i] = t[i];
-}
-// C = A * B^T
-__device__ __forceinline__ void mmt3(const float A[9], const float B[9], float C[9]) {
-  float t[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) t[i * 3 + j] = A[i * 3] * B[j * 3] + A[i * 3 + 1] * B[j * 3 + 1] + A[i * 3 + 2] * B[j * 3 + 2];
-#pragma unroll
-  for (int i = 0; i < 9; i++) C[i] = t[i];
-}
-// skew(r) * M
-__device__ __forceinline__ void skewmul(const float r[3], const float M[9], float C[9]) {
-  float t[9];
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    t[0 + j] = -r[2] * M[3 + j] + r[1] * M[6 + j];
-    t[3 + j] = r[2] * M[0 + j] - r[0] * M[6 + j];
-    t[6 + j] = -r[1] * M[0 + j] + r[0] * M[3 + j];
-  }
-#pragma unroll
-  for (int i = 0; i < 9; i++) C[i] = t[i];
-}
-// M * skew(r)
-__device__ __forceinline__ void mulskew(const float M[9], const float r[3], float C[9]) {
-  float t[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    t[i * 3 + 0] = M[i * 3 + 1] * r[2] - M[i * 3 + 2] * r[1];
-    t[i * 3 + 1] = -M[i * 3 + 0] * r[2] + M[i * 3 + 2] * r[0];
-    t[i * 3 + 2] = M[i * 3 + 0] * r[1] - M[i * 3 + 1] * r[0];
-  }
-#pragma unroll
-  for (int i = 0; i < 9; i++) C[i] = t[i];
-}
-__device__ __forceinline__ void sym_to_m3(const float s[6], float M[9]) {
-  M[0] = s[0]; M[4] = s[1]; M[8] = s[2];
-  M[1] = M[3] = s[3]; M[2] = M[6] = s[4]; M[5] = M[7] = s[5];
-}
-// Rodrigues rotation about unit axis: maps child-frame coordinates to parent-frame coordinates
-__device__ __forceinline__ void rodrigues(const float ax[3], float ang, float R[9]) {
-  float s, c;
-  sincosf(ang, &s, &c);
-  float t = 1.0f - c, x = ax[0], y = ax[1], z = ax[2];
-  R[0] = t * x * x + c; R[1] = t * x * y - s * z; R[2] = t * x * z + s * y;
-  R[3] = t * x * y + s * z; R[4] = t * y * y + c; R[5] = t * y * z - s * x;
-  R[6] = t * x * z - s * y; R[7] = t * y * z + s * x; R[8] = t * z * z + c;
-}
-
-// ------------------------------------------------------------------------------------------------
-// rotations about a coordinate axis AX (0 = x, 1 = y) by the angle with cosine c, sine s.
-// R maps child-frame coordinates to parent-frame coordinates.
-// ------------------------------------------------------------------------------------------------
-template <int AX>
-__device__ __forceinline__ void rot_fwd(float c, float s, const float v[3], float o[3]) {  // o = R v
-  const float v0 = v[0], v1 = v[1], v2 = v[2];
-  if (AX == 0) { o[0] = v0; o[1] = c * v1 - s * v2; o[2] = s * v1 + c * v2; }
-  else { o[0] = c * v0 + s * v2; o[1] = v1; o[2] = -s * v0 + c * v2; }
-}
-template <int AX>
-__device__ __forceinline__ void rot_inv(float c, float s, const float v[3], float o[3]) {  // o = R^T v
-  const float v0 = v[0], v1 = v[1], v2 = v[2];
-  if (AX == 0) { o[0] = v0; o[1] = c * v1 + s * v2; o[2] = -s * v1 + c * v2; }
-  else { o[0] = c * v0 - s * v2; o[1] = v1; o[2] = s * v0 + c * v2; }
-}
-// O = R S R^T for symmetric S = (xx yy zz xy xz yz)
-template <int AX>
-__device__ __forceinline__ void rot_sym(float c, float s, const float S[6], float O[6]) {
-  const float cc = c * c, ss = s * s, cs = c * s;
-  const float xx = S[0], yy = S[1], zz = S[2], xy = S[3], xz = S[4], yz = S[5];
-  if (AX == 0) {
-    O[0] = xx;
-    O[1] = cc * yy - 2.0f * cs * yz + ss * zz;
-    O[2] = ss * yy + 2.0f * cs * yz + cc * zz;
-    O[3] = c * xy - s * xz;
-    O[4] = s * xy + c * xz;
-    O[5] = cs * (yy - zz) + (cc - ss) * yz;
-  } else {
-    O[0] = cc * xx + 2.0f * cs * xz + ss * zz;
-    O[1] = yy;
-    O[2] = ss * xx - 2.0f * cs * xz + cc * zz;
-    O[3] = c * xy + s * yz;
-    O[4] = cs * (zz - xx) + (cc - ss) * xz;
-    O[5] = -s * xy + c * yz;
-  }
-}
-// O = R H R^T for a general 3x3 H (row-major)
-template <int AX>
-__device__ __forceinline__ void rot_gen(float c, float s, const float H[9], float O[9]) {
-  float T[9];
-#pragma unroll
-  for (int j = 0; j < 3; j++) {  // T = R H : rotate every column
-    const float col[3] = {H[j], H[3 + j], H[6 + j]};
-    float o[3];
-    rot_fwd<AX>(c, s, col, o);
-    T[j] = o[0]; T[3 + j] = o[1]; T[6 + j] = o[2];
-  }
-#pragma unroll
-  for (int i = 0; i < 3; i++) {  // O = T R^T : rotate every row
-    float o[3];
-    rot_fwd<AX>(c, s, &T[3 * i], o);
-    O[3 * i] = o[0]; O[3 * i + 1] = o[1]; O[3 * i + 2] = o[2];
-  }
-}
 __device__ __forceinline__ void symv(const float S[6], const float v[3], float o[3]) {
   const float a = S[0] * v[0] + S[3] * v[1] + S[4] * v[2];
   const float b = S[3] * v[0] + S[1] * v[1] + S[5] * v[2];
   const float c = S[4] * v[0] + S[5] * v[1] + S[2] * v[2];
   o[0] = a; o[1] = b; o[2] = c;
-}
-
-// sum of x over the 4 lanes of a quad (lanes 4q..4q+3), in every lane of the quad
-__device__ __forceinline__ float quad_sum(float x) {
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true));  // quad_perm:[1,0,3,2]
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, true));  // quad_perm:[2,3,0,1]
-  return x;
 }
 
 // sum of x over the 16 lanes of this robot (one DPP row), in every lane: quad butterflies, then the two mirror permutes
@@ -390,39 +265,9 @@ __device__ __forceinline__ float row_sum16(float x) {
 template <int R>
 __device__ __forceinline__ float bcast_lane(float x, int sub) {
   const int v = __float_as_int(x);
-  if (kRPW == 1) return __int_as_float(__builtin_amdgcn_readlane(v, R));
-  if (kRPW == 2) {
-    const int a = __builtin_amdgcn_readlane(v, R), b = __builtin_amdgcn_readlane(v, R + 32);
-    return __int_as_float(sub ? b : a);
-  }
   // old = 0 with bound_ctrl (every source lane of a row_newbcast is valid, so neither matters): the form the compiler's DPP
   // combiner folds into the consuming VOP2 (v_mul_f32_dpp / v_fmac_f32_dpp / v_max_f32_dpp ...) instead of a separate v_mov_b32_dpp
   return __int_as_float(__builtin_amdgcn_update_dpp(0, v, 0x150 + R, 0xF, 0xF, true));
-}
-// sum_k x_k(lane R of this robot) * w_k(own lane), k < 9: the broadcast rides as the DPP operand of the multiply-adds
-// (v_fmac_f32_dpp ... row_newbcast:R; the compiler's DPP combiner only folds v_mov_b32_dpp into v_mul, not into v_fmac).
-// Two accumulators halve the dependent chain.  The leading s_nop covers the "VALU write -> DPP read" hazard (2 wait states)
-// for whatever the compiler placed in front of the block: it does not look inside inline assembly.
-template <int R>
-__device__ __forceinline__ float dpp_dot9(float x0, float x1, float x2, float x3, float x4, float x5, float x6, float x7, float x8,
-                                          float w0, float w1, float w2, float w3, float w4, float w5, float w6, float w7, float w8) {
-  static_assert(kRPW == 4, "row_newbcast needs 16 lanes per robot");
-  float a, t;
-  asm("s_nop 1\n\t"
-      "v_mul_f32_dpp %0, %2, %11 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
-      "v_mul_f32_dpp %1, %3, %12 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f32_dpp %0, %4, %13 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f32_dpp %1, %5, %14 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f32_dpp %0, %6, %15 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f32_dpp %1, %7, %16 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f32_dpp %0, %8, %17 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f32_dpp %1, %9, %18 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f32_dpp %0, %10, %19 row_newbcast:%20 row_mask:0xf bank_mask:0xf\n\t"
-      "v_add_f32 %0, %0, %1"
-      : "=&v"(a), "=&v"(t)
-      : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(x4), "v"(x5), "v"(x6), "v"(x7), "v"(x8),
-        "v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(w4), "v"(w5), "v"(w6), "v"(w7), "v"(w8), "n"(R));
-  return a;
 }
 // The three Delassus entries of one leg's contact rows (normal z, friction x, friction y) for the impulse response (wa, wq) held
 // by this lane: t = wa_lin + wa_ang x rr + sum_k ck[k] wq[k], where rr (contact point relative to the base COM) and ck[k]
@@ -469,17 +314,6 @@ __device__ __forceinline__ float dpp_bcast_max0(float x, float zero) {
   float o;
   asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "=v"(o) : "v"(x), "v"(zero), "n"(R));
   return o;
-}
-// same with r a loop counter of an unrolled loop (the switch folds to one case)
-__device__ __forceinline__ float bcast_row(float x, int r, int sub) {
-  switch (r) {
-    case 0: return bcast_lane<0>(x, sub);   case 1: return bcast_lane<1>(x, sub);   case 2: return bcast_lane<2>(x, sub);
-    case 3: return bcast_lane<3>(x, sub);   case 4: return bcast_lane<4>(x, sub);   case 5: return bcast_lane<5>(x, sub);
-    case 6: return bcast_lane<6>(x, sub);   case 7: return bcast_lane<7>(x, sub);   case 8: return bcast_lane<8>(x, sub);
-    case 9: return bcast_lane<9>(x, sub);   case 10: return bcast_lane<10>(x, sub); case 11: return bcast_lane<11>(x, sub);
-    case 12: return bcast_lane<12>(x, sub); case 13: return bcast_lane<13>(x, sub); case 14: return bcast_lane<14>(x, sub);
-    default: return bcast_lane<15>(x, sub);
-  }
 }
 
 // sine / cosine of a joint angle (|a| is a few radians at most).  Cody-Waite reduction to [-pi/4, pi/4] with a
@@ -530,9 +364,6 @@ __device__ __forceinline__ float atan2_bf(float y, float x) {
 }
 __device__ __forceinline__ float asin_bf(float x) {   // |x| <= 1
   return atan2_bf(x, __builtin_amdgcn_sqrtf(fmaxf((1.0f - x) * (1.0f + x), 0.0f)));
-}
-__device__ __forceinline__ float acos_bf(float x) {   // |x| <= 1
-  return atan2_bf(__builtin_amdgcn_sqrtf(fmaxf((1.0f - x) * (1.0f + x), 0.0f)), x);
 }
 
 // transformations.quaternion_multiply(a, b): Hamilton product (pose3d.py:228-230)
@@ -647,21 +478,6 @@ __device__ __forceinline__ void qslerp(const float a[4], const float b[4], float
 // ------------------------------------------------------------------------------------------------
 // Philox4x32-10 (same stream definition as oracle/orr_oracle.c: key = seed, ctr = (robot, episode, idx>>2, "ORRL"))
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float philox_uniform(unsigned long long seed, uint32_t robot, uint32_t episode, uint32_t idx) {
-  uint32_t c0 = robot, c1 = episode, c2 = idx >> 2, c3 = 0x4F52524Cu;
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  uint32_t sel = idx & 3u;
-  uint32_t x = sel == 0 ? c0 : (sel == 1 ? c1 : (sel == 2 ? c2 : c3));
-  return (float)(x >> 8) * (1.0f / 16777216.0f);
-}
 // one whole block: draws 4 * block .. 4 * block + 3 of stream (robot, episode)
 __device__ __forceinline__ void philox_block(unsigned long long seed, uint32_t robot, uint32_t episode, uint32_t block, float u[4]) {
   uint32_t c0 = robot, c1 = episode, c2 = block, c3 = 0x4F52524Cu;

@@ -68,7 +68,7 @@ __device__ long long g_wave_timeline[4 * 2048];   // per wave of the last launch
 // one per touching shape: DESIGN.md section 9).  One-wave kernel only.
 #if defined(ORR_COUNT_DUAL_CONTACT) && !defined(ORR_TU_SECONDARY)
 __device__ unsigned long long g_dual_contact[8];
-// (called inside the contact branch of row_setup, where lanes 0..3 of every robot are inactive: the first ACTIVE lane adds the wave's count)
+// (called from row_setup_bank_a in every lane of the wave: the first ACTIVE lane adds the wave's count)
 #define ORR_DUAL_COUNT(k, cond) do { const unsigned long long b_ = __ballot(cond), act_ = __ballot(1); \
     if (b_ && (int)(threadIdx.x & 63u) == __ffsll((long long)act_) - 1) atomicAdd(&g_dual_contact[k], (unsigned long long)__popcll(b_)); } while (0)
 #else
@@ -303,23 +303,19 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
     // stays so that the unit's code is the measured one
     constexpr int kPrioTurn = 4, kPrioHi = 1, kPrioOffset = 1, kPrioEqualFrom = 1000;
     if (WPE == 2 && prio_turns) { if (sstep < kPrioEqualFrom && ((((sstep + kPrioOffset) / kPrioTurn) ^ prio_phase) & 1)) __builtin_amdgcn_s_setprio(kPrioHi); else __builtin_amdgcn_s_setprio(0); }
-    if (kLanes != 16 && sstep > 0) ctrl_obs(P, rec, S, lane);
     {  // every lane (no divergent `if`: it would cost more than it skips); lanes 12..15 repeat motor 0 and store into dump slots
       const float lerp = (float)(sstep + 1) * inv_repeat;  // process_action (minitaur.py:438-460)
-      const bool carry = kLanes == 16;
-      const float cur = map_pi(carry ? co_own : S.co[ml]);
+      const float cur = map_pi(co_own);
       const float prev = m_has_prev ? m_prev : cur;
       float cmd = prev + lerp * (m_target - prev);
       cmd = fminf(fmaxf(cmd, cur - c.max_angle_change), cur + c.max_angle_change);  // _clip_motor_commands (:706-723)
-      const float qm = carry ? qm_c : (S.s[O(Q) + mj] - m_off) * m_dir;  // pd latency 0 (:359-363)
-      const float qdm = carry ? qdm_c : S.s[O(QD) + mj] * m_dir;
-      // MotorModel.convert_to_torque, POSITION mode (minitaur_motor.py:163-171)
-      S.tau[lane < 12 ? mj : lane] = m_gain * (-1.0f * (m_kp * (qm - cmd)) - m_kd * qdm);
+      // MotorModel.convert_to_torque, POSITION mode (minitaur_motor.py:163-171); pd latency 0 (:359-363): the carried angle and rate
+      S.tau[lane < 12 ? mj : lane] = m_gain * (-1.0f * (m_kp * (qm_c - cmd)) - m_kd * qdm_c);
     }
     WSYNC();
     action_counter++;  // robot_step bookkeeping (minitaur.py:287-293); written back after the loop
     PT(2);
-    if (kLanes == 16) {  // receive_obs, then the control observation of the next sub-step / of get_obs
+    {  // receive_obs, then the control observation of the next sub-step / of get_obs
       RingFetch F;
       ring_prefetch(rlat, rec, ring, lane, F);
       if constexpr (MODE == 2) {
@@ -334,9 +330,6 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
       qm_c = (S.s[O(Q) + mj] - m_off) * m_dir;
       qdm_c = S.s[O(QD) + mj] * m_dir;
       ring_push_and_ctrl_obs(rec, S, lane, valid, F, ring, qm_c, &co_own);
-    } else {
-      fall = physics_substep<ANCHOR>(P, S, K, lane, sub, sstep == c.action_repeat - 1, X, limit_idle, ANCHOR ? &AS : nullptr, anchor_robot);
-      receive_obs(P, rec, S, lane, valid);
     }
     PT(10);
   }
@@ -344,7 +337,7 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
   // partner: it costs the partner next to nothing and shortens the tail (8192 robots: -0.1 %; with -Os for this unit -0.4 %, profiles/r04_ab29_8192.log)
   if (WPE == 2) __builtin_amdgcn_s_setprio(3);
   if (lane == 0) {  // end of robot_step (minitaur.py:287-293)
-    if (kLanes == 16) { seti(S, O(RING_HEAD), ring.head); seti(S, O(RING_LEN), ring.len); }
+    seti(S, O(RING_HEAD), ring.head); seti(S, O(RING_LEN), ring.len);
     seti(S, O(STATE_ACTION_COUNTER), action_counter);
     seti(S, O(FILTER_VALID), 1);
     seti(S, O(STEP_COUNTER), geti(S, O(STEP_COUNTER)) + 1);
@@ -352,7 +345,6 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
   if (lane < 12) S.s[O(FILTER_ACTION) + lane] = m_target;
   WSYNC();
   // ---- get_obs: sensors on_step (minitaur.py:295-299) ----
-  if (kLanes != 16) ctrl_obs(P, rec, S, lane);
   sensors_push(S, lane, false);
   PT(11);
   // ---- reward -> update -> done (quadruped_gym_env.py:230-233) ----

@@ -537,197 +537,53 @@ struct ContactGeom {
   float rr0, rr1, rr2, c00, c01, c02, c10, c11, c12, c20, c21, c22;   // scalars (not arrays): stays in registers for the inline-asm operands
 };
 
-// Jacobian, right-hand side (not yet scaled by 1/diag) and bounds of row slot `slot`.  BANK 0: knee-friction and contact slots
-// (0..3, 16..27), BANK 1: joint-limit slots (4..15) -- two instantiations, so that the joint-limit bank carries no contact code
-// and its base Jacobian is the compile-time constant zero.
-template <int BANK>
-__device__ __forceinline__ void row_setup(const Shared& S, const orr_config& cfg, int slot, bool enable, float dt, float inv_dt,
-                                          float erp_dt, Row& R, ContactGeom& G, float* limit_margin = nullptr) {
-  if (BANK == 0) G = ContactGeom{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  R.active = false; R.leg = 0; R.nrm_slot = -1; R.warm = -1;
+// Joint-limit row of slot `slot` (4..15: joint slot - 4, bank B): Jacobian +-1 on the joint and zero on the base, right-hand side (not
+// yet scaled by 1/diag) and bounds [0, inf).  *limit_margin: how far the joint is from getting a limit row.
+__device__ __forceinline__ void row_setup_limit(const Shared& S, const orr_config& cfg, int slot, bool enable, float inv_dt, float erp_dt,
+                                                Row& R, float* limit_margin) {
+  R.nrm_slot = -1; R.warm = -1;
 #pragma unroll
   for (int i = 0; i < 6; i++) R.Jb[i] = 0.0f;
-  R.jl[0] = R.jl[1] = R.jl[2] = 0.0f;
-  R.rhs = 0.0f; R.jdi = 0.0f; R.lam = 0.0f; R.w = 0.0f; R.lam_n = 0.0f; R.cfm = 0.0f;
-  float lo = 0.0f, hi = 0.0f, mu = 0.0f;
-  if (BANK == 0 && slot < 4) {
-    R.leg = slot;
-    const float fr = S.s[O(KNEE_FRICTION) + R.leg];
-    R.active = fr > 0.0f;
-    R.jl[2] = 1.0f;
-    lo = -fr * dt; hi = fr * dt;
-    R.rhs = -S.ustar[6 + 3 * R.leg + 2];
-  } else if (BANK == 1) {
-    const int j = slot - 4;
-    R.leg = j / 3;
-    const int kk = j - 3 * R.leg;
-    const float a = S.m.jdir[j] * (S.s[O(Q) + j] - S.m.joff[j]);
-    const float pen_lo = a - S.m.joint_lo[j], pen_hi = S.m.joint_hi[j] - a;
-    if (limit_margin) *limit_margin = fminf(pen_lo, pen_hi) - cfg.limit_activation;   // how far the joint is from getting a limit row
-    const bool use_lo = pen_lo < cfg.limit_activation;
-    const bool use_hi = (!use_lo) && pen_hi < cfg.limit_activation;
-    R.active = use_lo || use_hi;
-    const float sgn = use_lo ? 1.0f : -1.0f, pen = use_lo ? pen_lo : pen_hi;
-    R.jl[0] = kk == 0 ? sgn : 0.0f; R.jl[1] = kk == 1 ? sgn : 0.0f; R.jl[2] = kk == 2 ? sgn : 0.0f;
-    const float rel = sgn * S.ustar[6 + j];
-    lo = 0.0f; hi = 1e30f;
-    R.rhs = pen > 0.0f ? -rel - pen * inv_dt : -rel - pen * erp_dt;
-  } else {
-    int d;
-    if (slot < 20) { R.leg = slot - 16; d = 0; }
-    else { R.leg = (slot - 20) >> 1; d = 1 + ((slot - 20) & 1); }
-    const int leg = R.leg;
-    const LinkCache& Lb = S.ph.sub.dyn.lc[3 * leg + 2];
-    // lower legs are feet (minitaur.py:842-844): the leg touches the ground with its toe sphere or its shank sphere, whichever is
-    // lower (one contact point per leg and sub-step; shank_radius 0 = toe only)
-    float cw[3], cs[3];
-    mv3(Lb.Rw, S.m.toe_pos[leg], cw);
-    mv3(Lb.Rw, S.m.shank_pos[leg], cs);
-    const float dist_t = cw[2] + Lb.ow[2] - S.m.toe_radius, dist_s = cs[2] + Lb.ow[2] - S.m.shank_radius;
-    const bool shank = S.m.shank_radius > 0.0f && dist_s < dist_t;
-    const float dist = shank ? dist_s : dist_t;
-    R.active = dist < cfg.contact_margin;
-    {   // instrumented build only (tools/dual_contact.py): normal-row lanes count the leg-sub-steps by which spheres touch
-      const bool cnt = enable && d == 0, has_s = S.m.shank_radius > 0.0f;
-      const bool t_in = dist_t < cfg.contact_margin, s_in = has_s && dist_s < cfg.contact_margin;
-      ORR_DUAL_COUNT(0, cnt);                                        // leg-sub-steps
-      ORR_DUAL_COUNT(1, cnt && (t_in || s_in));                      // ... with a contact row
-      ORR_DUAL_COUNT(2, cnt && t_in && s_in);                        // both spheres within the contact margin (Bullet: two contact points)
-      ORR_DUAL_COUNT(3, cnt && dist_t < 0.0f && has_s && dist_s < 0.0f);   // both spheres penetrating
-      ORR_DUAL_COUNT(4, cnt && s_in && !t_in);                       // shank only
-      ORR_DUAL_COUNT(5, cnt && shank && R.active);                   // the row was made at the shank sphere
-      (void)cnt; (void)has_s; (void)t_in; (void)s_in;
-    }
-    const float Pw[3] = {(shank ? cs[0] : cw[0]) + Lb.ow[0], (shank ? cs[1] : cw[1]) + Lb.ow[1], dist};
-    const float dir[3] = {d == 1 ? 1.0f : 0.0f, d == 2 ? 1.0f : 0.0f, d == 0 ? 1.0f : 0.0f};
-    float rr[3] = {Pw[0] - S.s[O(POS)], Pw[1] - S.s[O(POS) + 1], Pw[2] - S.s[O(POS) + 2]};
-    cross3(rr, dir, &R.Jb[0]);
-    R.Jb[3] = dir[0]; R.Jb[4] = dir[1]; R.Jb[5] = dir[2];
-    float rel = R.Jb[0] * S.ustar[0] + R.Jb[1] * S.ustar[1] + R.Jb[2] * S.ustar[2] + R.Jb[3] * S.ustar[3] + R.Jb[4] * S.ustar[4] + R.Jb[5] * S.ustar[5];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      // velocity of the contact point per unit joint rate: s x (P - o) = s x rr + (d x s), rr and d relative to the base COM
-      const LinkCache& L = S.ph.sub.dyn.lc[3 * leg + k];
-      float cr[3];
-      cross3(L.s, rr, cr);
-      cr[0] += L.sv[0]; cr[1] += L.sv[1]; cr[2] += L.sv[2];
-      if (k == 0) { G.c00 = cr[0]; G.c01 = cr[1]; G.c02 = cr[2]; }
-      else if (k == 1) { G.c10 = cr[0]; G.c11 = cr[1]; G.c12 = cr[2]; }
-      else { G.c20 = cr[0]; G.c21 = cr[1]; G.c22 = cr[2]; }
-      R.jl[k] = dir[0] * cr[0] + dir[1] * cr[1] + dir[2] * cr[2];
-      rel += R.jl[k] * S.ustar[6 + 3 * leg + k];
-    }
-    G.rr0 = rr[0]; G.rr1 = rr[1]; G.rr2 = rr[2];
-    R.warm = 3 * leg + d;
-    if (d == 0) {
-      lo = 0.0f; hi = 1e30f;
-      // a TOE contact may be soft (URDF <contact><stiffness/><damping/>, see ModelHot): its own erp, and cfm on the row's diagonal
-      R.rhs = dist > 0.0f ? -rel - dist * inv_dt : -rel - dist * (shank ? erp_dt : S.m.contact_erp_dt);
-      R.cfm = shank ? 0.0f : S.m.contact_cfm;
-    } else {
-      R.nrm_slot = 16 + leg;
-      mu = S.s[O(FOOT_MU)] * cfg.plane_friction;  // combined friction = product of the two coefficients
-      R.rhs = -rel;
-    }
-  }
-  if (!enable) R.active = false;
-  // bounds as (constant part) + mu * lambda_normal: friction rows have a zero constant part, the others mu = 0;
-  // an inactive row is pinned to zero
-  R.mu_e = (R.active && R.nrm_slot >= 0) ? mu : 0.0f;
-  R.hi_c = (R.active && R.nrm_slot < 0) ? hi : 0.0f;
-  R.lo_c = (R.active && R.nrm_slot < 0) ? lo : 0.0f;
+  R.jdi = 0.0f; R.lam = 0.0f; R.w = 0.0f; R.lam_n = 0.0f; R.cfm = 0.0f;
+  const int j = slot - 4;
+  R.leg = j / 3;
+  const int kk = j - 3 * R.leg;
+  const float a = S.m.jdir[j] * (S.s[O(Q) + j] - S.m.joff[j]);
+  const float pen_lo = a - S.m.joint_lo[j], pen_hi = S.m.joint_hi[j] - a;
+  if (limit_margin) *limit_margin = fminf(pen_lo, pen_hi) - cfg.limit_activation;   // never NULL; without the test the two-wave unit's code changes
+  const bool use_lo = pen_lo < cfg.limit_activation;
+  const bool use_hi = (!use_lo) && pen_hi < cfg.limit_activation;
+  R.active = use_lo || use_hi;
+  const float sgn = use_lo ? 1.0f : -1.0f, pen = use_lo ? pen_lo : pen_hi;
+  R.jl[0] = kk == 0 ? sgn : 0.0f; R.jl[1] = kk == 1 ? sgn : 0.0f; R.jl[2] = kk == 2 ? sgn : 0.0f;
+  const float rel = sgn * S.ustar[6 + j];
+  R.rhs = pen > 0.0f ? -rel - pen * inv_dt : -rel - pen * erp_dt;
+  if (!enable) R.active = false;   // a statement of its own: folded into `R.active = ...` above, it changes the step kernel's code
+  // bounds [0, inf) as (constant part) + mu * lambda_normal with mu = 0; an inactive row is pinned to zero
+  R.mu_e = 0.0f;
+  R.hi_c = R.active ? 1e30f : 0.0f;
+  R.lo_c = 0.0f;
   if (!R.active) R.rhs = 0.0f;
 }
 
-// Bank A (knee-friction slots 0..3, contact slots 16..27) WITHOUT divergent control flow.  The generic form above sends the knee lanes
-// and the contact lanes (and inside those the normal and the friction lanes) through separate exec-masked regions; each region costs a
-// lone wave its saveexec / branch overhead, ~30 moves that set the other branch's values at the merge, and - the expensive part - an LDS
-// round trip that cannot overlap with anything (the region's own loads: friction coefficient, knee friction, contact softness).  Here
-// every lane loads all of these up front, computes the contact geometry of "its" leg (knee lane l: leg l; the result is discarded) and
-// picks its row's values with selects on lane-constant masks.  Same arithmetic per row, bit for bit.
-__device__ __forceinline__ void row_setup_bank_a(const Shared& S, const orr_config& cfg, int slot, bool enable, float dt, float inv_dt,
-                                                 float erp_dt, Row& R, ContactGeom& G) {
-  const bool knee = slot < 4;
-  const int leg = knee ? slot : (slot < 20 ? slot - 16 : (slot - 20) >> 1);
-  const int d = (knee || slot < 20) ? 0 : 1 + ((slot - 20) & 1);
-  const bool normal = !knee && d == 0, fric = d != 0;
-  // everything that comes out of LDS, for every lane, before any use (opaque copies keep the loads here)
-  float fr = S.s[O(KNEE_FRICTION) + leg], uknee = S.ustar[6 + 3 * leg + 2], mu_s = S.s[O(FOOT_MU)];
-  float cfm_m = S.m.contact_cfm, erp_m = S.m.contact_erp_dt;
-  asm volatile("" : "+v"(fr), "+v"(uknee), "+v"(mu_s), "+v"(cfm_m), "+v"(erp_m));
-  R.leg = leg;
-  const LinkCache& Lb = S.ph.sub.dyn.lc[3 * leg + 2];
-  float cw[3], cs[3];
-  mv3(Lb.Rw, S.m.toe_pos[leg], cw);
-  mv3(Lb.Rw, S.m.shank_pos[leg], cs);
-  const float dist_t = cw[2] + Lb.ow[2] - S.m.toe_radius, dist_s = cs[2] + Lb.ow[2] - S.m.shank_radius;
-  const bool shank = S.m.shank_radius > 0.0f && dist_s < dist_t;
-  const float dist = shank ? dist_s : dist_t;
-  {   // instrumented build only (tools/dual_contact.py): normal-row lanes count the leg-sub-steps by which spheres touch
-    const bool cnt = enable && normal, has_s = S.m.shank_radius > 0.0f;
-    const bool t_in = dist_t < cfg.contact_margin, s_in = has_s && dist_s < cfg.contact_margin;
-    ORR_DUAL_COUNT(0, cnt);
-    ORR_DUAL_COUNT(1, cnt && (t_in || s_in));
-    ORR_DUAL_COUNT(2, cnt && t_in && s_in);
-    ORR_DUAL_COUNT(3, cnt && dist_t < 0.0f && has_s && dist_s < 0.0f);
-    ORR_DUAL_COUNT(4, cnt && s_in && !t_in);
-    ORR_DUAL_COUNT(5, cnt && shank && dist < cfg.contact_margin);
-    (void)cnt; (void)has_s; (void)t_in; (void)s_in;
-  }
-  const float Pw[3] = {(shank ? cs[0] : cw[0]) + Lb.ow[0], (shank ? cs[1] : cw[1]) + Lb.ow[1], dist};
-  const float dir[3] = {d == 1 ? 1.0f : 0.0f, d == 2 ? 1.0f : 0.0f, d == 0 ? 1.0f : 0.0f};
-  float rr[3] = {Pw[0] - S.s[O(POS)], Pw[1] - S.s[O(POS) + 1], Pw[2] - S.s[O(POS) + 2]};
-  float Jb[6];
-  cross3(rr, dir, &Jb[0]);
-  Jb[3] = dir[0]; Jb[4] = dir[1]; Jb[5] = dir[2];
-  float rel = Jb[0] * S.ustar[0] + Jb[1] * S.ustar[1] + Jb[2] * S.ustar[2] + Jb[3] * S.ustar[3] + Jb[4] * S.ustar[4] + Jb[5] * S.ustar[5];
-  float jl[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    // velocity of the contact point per unit joint rate: s x (P - o) = s x rr + (d x s), rr and d relative to the base COM
-    const LinkCache& L = S.ph.sub.dyn.lc[3 * leg + k];
-    const float cr[3] = {fmaf(L.s[1], rr[2], fmaf(-L.s[2], rr[1], L.sv[0])), fmaf(L.s[2], rr[0], fmaf(-L.s[0], rr[2], L.sv[1])),
-                         fmaf(L.s[0], rr[1], fmaf(-L.s[1], rr[0], L.sv[2]))};
-    if (k == 0) { G.c00 = cr[0]; G.c01 = cr[1]; G.c02 = cr[2]; }
-    else if (k == 1) { G.c10 = cr[0]; G.c11 = cr[1]; G.c12 = cr[2]; }
-    else { G.c20 = cr[0]; G.c21 = cr[1]; G.c22 = cr[2]; }
-    jl[k] = dir[0] * cr[0] + dir[1] * cr[1] + dir[2] * cr[2];
-    rel += jl[k] * S.ustar[6 + 3 * leg + k];
-  }
-  G.rr0 = rr[0]; G.rr1 = rr[1]; G.rr2 = rr[2];   // only the contact lanes' geometry is ever read (dpp_contact_triplet<4 + g>)
-  // the row of this lane
-  const bool active = enable && (knee ? fr > 0.0f : dist < cfg.contact_margin);
-#pragma unroll
-  for (int i = 0; i < 6; i++) R.Jb[i] = knee ? 0.0f : Jb[i];
-  R.jl[0] = knee ? 0.0f : jl[0]; R.jl[1] = knee ? 0.0f : jl[1]; R.jl[2] = knee ? 1.0f : jl[2];
-  // right-hand side: knee motor -u*; friction -rel; normal -rel - dist / dt (open) or -rel - dist erp / dt (penetrating; a toe may be soft)
-  const float kpen = normal ? (dist > 0.0f ? inv_dt : (shank ? erp_dt : erp_m)) : 0.0f;     // one multiply-add, as in the generic form
-  const float rhs = knee ? -uknee : -rel - dist * kpen;
-  R.rhs = active ? rhs : 0.0f;
-  R.cfm = (normal && !shank) ? cfm_m : 0.0f;
-  R.nrm_slot = fric ? 16 + leg : -1;
-  R.warm = knee ? -1 : 3 * leg + d;
-  R.active = active;
-  R.jdi = 0.0f; R.lam = 0.0f; R.w = 0.0f; R.lam_n = 0.0f;
-  // bounds as (constant part) + mu * lambda_normal: friction rows have a zero constant part, the others mu = 0; an inactive row is
-  // pinned to zero
-  const float hi = knee ? fr * dt : 1e30f, lo = knee ? -fr * dt : 0.0f;
-  R.mu_e = (active && fric) ? mu_s * cfg.plane_friction : 0.0f;
-  R.hi_c = (active && !fric) ? hi : 0.0f;
-  R.lo_c = (active && !fric) ? lo : 0.0f;
-}
-
-// The same row setup with Bullet's friction anchors: a COPY of the function above with the cached contact point worked in (the default
-// kernels keep the function above token for token: a semantically neutral rewrite of it moved the one-wave kernel by six instructions
-// per sub-step and 0.7 % of run time, round 5).
 // Bullet's friction anchor (orr_model::friction_anchor, ABI v5; the ANCHOR variant of the kernels): the cached contact point of the lane's
 // leg - the point on the toe in the lower-leg link frame, the point on the plane in world - carried in REGISTERS over the sub-steps of a
 // launch by each of the leg's three contact lanes (normal + two friction rows).  They make the same decisions from the same inputs
 // (link pose and last sub-step's impulses from LDS), so the copies stay equal; the normal-row lane loads / stores the record's words.
 struct AnchorState { float la[3], wb[3]; int valid; };
-__device__ __forceinline__ void row_setup_bank_a_anchor(const Shared& S, const orr_config& cfg, int slot, bool enable, float dt, float inv_dt,
+
+// Bank A (knee-friction slots 0..3, contact slots 16..27) WITHOUT divergent control flow.  Separate exec-masked regions for the knee
+// lanes and the contact lanes (and inside those for the normal and the friction lanes) would each cost a lone wave its saveexec / branch
+// overhead, ~30 moves that set the other branch's values at the merge, and - the expensive part - an LDS round trip that cannot overlap
+// with anything (the region's own loads: friction coefficient, knee friction, contact softness).  Here every lane loads all of these up
+// front, computes the contact geometry of "its" leg (knee lane l: leg l; the result is discarded) and picks its row's values with selects
+// on lane-constant masks.
+// ANCHOR (the friction-anchor variant of the kernels) works Bullet's cached contact point in under `if constexpr`.  With ANCHOR = false
+// the default kernels' device assembly must not change, instruction for instruction: compare it before and after any edit here (a
+// semantically neutral rewrite of this function once moved the one-wave kernel by six instructions per sub-step and 0.7 % of run time).
+template <bool ANCHOR>
+__device__ __forceinline__ void row_setup_bank_a(const Shared& S, const orr_config& cfg, int slot, bool enable, float dt, float inv_dt,
                                                  float erp_dt, Row& R, ContactGeom& G, AnchorState* AS, bool anchor_robot) {
-  constexpr bool ANCHOR = true;
   const bool knee = slot < 4;
   const int leg = knee ? slot : (slot < 20 ? slot - 16 : (slot - 20) >> 1);
   const int d = (knee || slot < 20) ? 0 : 1 + ((slot - 20) & 1);
@@ -738,6 +594,8 @@ __device__ __forceinline__ void row_setup_bank_a_anchor(const Shared& S, const o
   asm volatile("" : "+v"(fr), "+v"(uknee), "+v"(mu_s), "+v"(cfm_m), "+v"(erp_m));
   R.leg = leg;
   const LinkCache& Lb = S.ph.sub.dyn.lc[3 * leg + 2];
+  // lower legs are feet (minitaur.py:842-844): the leg touches the ground with its toe sphere or its shank sphere, whichever is
+  // lower (one contact point per leg and sub-step; shank_radius 0 = toe only)
   float cw[3], cs[3];
   mv3(Lb.Rw, S.m.toe_pos[leg], cw);
   mv3(Lb.Rw, S.m.shank_pos[leg], cs);
@@ -784,12 +642,12 @@ __device__ __forceinline__ void row_setup_bank_a_anchor(const Shared& S, const o
   {   // instrumented build only (tools/dual_contact.py): normal-row lanes count the leg-sub-steps by which spheres touch
     const bool cnt = enable && normal, has_s = S.m.shank_radius > 0.0f;
     const bool t_in = dist_t < cfg.contact_margin, s_in = has_s && dist_s < cfg.contact_margin;
-    ORR_DUAL_COUNT(0, cnt);
-    ORR_DUAL_COUNT(1, cnt && (t_in || s_in));
-    ORR_DUAL_COUNT(2, cnt && t_in && s_in);
-    ORR_DUAL_COUNT(3, cnt && dist_t < 0.0f && has_s && dist_s < 0.0f);
-    ORR_DUAL_COUNT(4, cnt && s_in && !t_in);
-    ORR_DUAL_COUNT(5, cnt && shank && dist < cfg.contact_margin);
+    ORR_DUAL_COUNT(0, cnt);                                        // leg-sub-steps
+    ORR_DUAL_COUNT(1, cnt && (t_in || s_in));                      // ... with a contact row
+    ORR_DUAL_COUNT(2, cnt && t_in && s_in);                        // both spheres within the contact margin (Bullet: two contact points)
+    ORR_DUAL_COUNT(3, cnt && dist_t < 0.0f && has_s && dist_s < 0.0f);   // both spheres penetrating
+    ORR_DUAL_COUNT(4, cnt && s_in && !t_in);                       // shank only
+    ORR_DUAL_COUNT(5, cnt && shank && dist < cfg.contact_margin);  // the row was made at the shank sphere
     (void)cnt; (void)has_s; (void)t_in; (void)s_in;
   }
   const float Pw[3] = {Pw0, Pw1, dist};
@@ -819,7 +677,7 @@ __device__ __forceinline__ void row_setup_bank_a_anchor(const Shared& S, const o
   for (int i = 0; i < 6; i++) R.Jb[i] = knee ? 0.0f : Jb[i];
   R.jl[0] = knee ? 0.0f : jl[0]; R.jl[1] = knee ? 0.0f : jl[1]; R.jl[2] = knee ? 1.0f : jl[2];
   // right-hand side: knee motor -u*; friction -rel; normal -rel - dist / dt (open) or -rel - dist erp / dt (penetrating; a toe may be soft)
-  const float kpen = normal ? (dist > 0.0f ? inv_dt : (shank ? erp_dt : erp_m)) : 0.0f;     // one multiply-add, as in the generic form
+  const float kpen = normal ? (dist > 0.0f ? inv_dt : (shank ? erp_dt : erp_m)) : 0.0f;     // one multiply-add for every row kind
   float rhs = knee ? -uknee : -rel - dist * kpen;
   // friction anchor: positionalError = -distance * frictionERP / dt along the friction direction (setupMultiBodyContactConstraint)
   if constexpr (ANCHOR) rhs -= (d == 1 ? drift_x : (d == 2 ? drift_y : 0.0f)) * (cfg.friction_erp * inv_dt);
@@ -832,7 +690,7 @@ __device__ __forceinline__ void row_setup_bank_a_anchor(const Shared& S, const o
   // bounds as (constant part) + mu * lambda_normal: friction rows have a zero constant part, the others mu = 0; an inactive row is
   // pinned to zero
   const float hi = knee ? fr * dt : 1e30f, lo = knee ? -fr * dt : 0.0f;
-  R.mu_e = (active && fric) ? mu_s * cfg.plane_friction : 0.0f;
+  R.mu_e = (active && fric) ? mu_s * cfg.plane_friction : 0.0f;   // combined friction = product of the two coefficients
   R.hi_c = (active && !fric) ? hi : 0.0f;
   R.lo_c = (active && !fric) ? lo : 0.0f;
 }
@@ -1285,11 +1143,8 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
   // a joint near its limit.
   Row A, B;
   const bool rowlane = lane < 16;
-  ContactGeom G, Gunused;
-  if constexpr (ANCHOR) row_setup_bank_a_anchor(S, cfg, rowlane ? (lane < 4 ? lane : lane + 12) : 0, rowlane, dt, inv_dt, erp_dt, A, G, AS, anchor_robot);
-  else {
-  row_setup_bank_a(S, cfg, rowlane ? (lane < 4 ? lane : lane + 12) : 0, rowlane, dt, inv_dt, erp_dt, A, G);
-  }
+  ContactGeom G;
+  row_setup_bank_a<ANCHOR>(S, cfg, rowlane ? (lane < 4 ? lane : lane + 12) : 0, rowlane, dt, inv_dt, erp_dt, A, G, AS, anchor_robot);
   unsigned long long balB = 0ull;
   if (limit_idle > 0) {
     limit_idle--;
@@ -1297,7 +1152,7 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
     B.active = false;
   } else {
     float margin = 1e30f;
-    row_setup<1>(S, cfg, (rowlane && lane >= 4) ? lane : 4, rowlane && lane >= 4, dt, inv_dt, erp_dt, B, Gunused, &margin);
+    row_setup_limit(S, cfg, (rowlane && lane >= 4) ? lane : 4, rowlane && lane >= 4, inv_dt, erp_dt, B, &margin);
     balB = __ballot(B.active);
     // sub-steps that can be skipped from here: the minimum over the wave's joints of floor(margin / (vmax dt)) - 1 (one sub-step of
     // slack against rounding), found with five ballots (powers of two up to 16 are enough: the check itself is cheap)
@@ -1358,7 +1213,7 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
     auto add_row = [&](auto rc) __attribute__((always_inline)) {
       constexpr int r = decltype(rc)::value;
       du0 += S.ph.sub.W[r][k0] * lam[r];
-      if (kLanes < 18) du1 += S.ph.sub.W[r][k1] * lam[r];
+      du1 += S.ph.sub.W[r][k1] * lam[r];
     };
     static_for<0, 4>(add_row);
     if (anyB) {
@@ -1369,7 +1224,7 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
     v0 = __builtin_amdgcn_fmed3f(S.ustar[k0] + du0, -vmax, vmax);
     v1 = __builtin_amdgcn_fmed3f(S.ustar[k1] + du1, -vmax, vmax);
   }
-  if (kLanes == 16) {
+  {
     // quaternion: exponential map of the world angular velocity (DOFs 0..2, broadcast from their lanes), then normalise
     const float w0 = bcast_lane<0>(v0, sub), w1 = bcast_lane<1>(v0, sub), w2 = bcast_lane<2>(v0, sub);
     const float ww = w0 * w0 + w1 * w1 + w2 * w2, h2 = 0.25f * dt * dt * ww;  // h = |w| dt / 2
@@ -1397,32 +1252,6 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
     *pv1 = v1 * K.int_c1;
     *px1 = X.x1;
     *pq = pick4(lane, qn[0], qn[1], qn[2], qn[3]) * nn;
-  } else {
-    // wider lane groups (tuning builds): through LDS
-    if (lane < 18) S.ustar[lane] = v0;
-    WSYNC();
-    const float w0 = S.ustar[0], w1 = S.ustar[1], w2 = S.ustar[2];
-    const float wn = sqrtf(w0 * w0 + w1 * w1 + w2 * w2), half = 0.5f * wn * dt;
-    float sc, ch;
-    if (wn < 1e-12f) { sc = 0.5f * dt; ch = 1.0f; }
-    else { float sh; sincosf(half, &sh, &ch); sc = sh / wn; }
-    float dq[4] = {w0 * sc, w1 * sc, w2 * sc, ch}, qn[4];
-    qmul(dq, &S.s[O(QUAT)], qn);
-    const float nn = rsq(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
-    WSYNC();
-    for (int i = lane; i < 22; i += kLanes) {
-      if (i < 3) S.s[O(ANGVEL) + i] = S.ustar[i];
-      else if (i < 6) { S.s[O(LINVEL) + i - 3] = S.ustar[i]; S.s[O(POS) + i - 3] += dt * S.ustar[i]; }
-      else if (i < 18) {
-        const int j = i - 6;
-        const float a = S.m.jdir[j] * (S.s[O(Q) + j] - S.m.joff[j]) + dt * S.ustar[i];
-        S.s[O(Q) + j] = a * S.m.jdir[j] + S.m.joff[j];
-        S.s[O(QD) + j] = S.ustar[i] * S.m.jdir[j];
-      } else {
-        const int q = i - 18;
-        S.s[O(QUAT) + q] = (q == 0 ? qn[0] : (q == 1 ? qn[1] : (q == 2 ? qn[2] : qn[3]))) * nn;
-      }
-    }
   }
   WSYNC();
   PT(9);

@@ -164,11 +164,6 @@ __device__ static void sample_poses_finish(const KParams& P, Shared& S, int lane
   }
   WSYNC();
 }
-__device__ static void sample_poses(const KParams& P, Shared& S, int lane, double t_lane, bool with_vel, int pt_slot = 32) {
-  PoseLoads L;
-  sample_poses_issue(P, S, lane, t_lane, L, pt_slot);
-  sample_poses_finish(P, S, lane, t_lane, with_vel, L, pt_slot);
-}
 
 // apply the origin offset (imitation_task.py:938-951) to S.ph.end.pose[l] in place (lane l < nt)
 __device__ static void apply_origin(Shared& S, int lane, int nt) {
@@ -191,7 +186,6 @@ __device__ __forceinline__ double motion_time(const KParams& P, const Shared& S)
 // build the 76-d target observation into obs76 (LDS) from S.ph.end.pose[1..4] (already origin-offset) -- imitation_task.py:254-301.
 // The control observation S.co must be current (it is after the last sub-step's ring push and after reset_robot's local blend).
 __device__ static void target_obs(const KParams& P, const float* rec, Shared& S, int lane, float* obs76) {
-  if (kLanes != 16) ctrl_obs(P, rec, S, lane);
   if (lane >= 1 && lane <= 4) {
     float rpy[3];
     euler_from_quat(&S.co[12], rpy);
@@ -408,7 +402,7 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
   // 4a. all 28 draws of the episode (0..25 randomiser, 26 ref-state-init, 27 time offset) = 7 Philox blocks: lane b < 7 evaluates
   // block b once and parks its four numbers in LDS
   float* draws = S.ph.end.red + 24;    // 28 words (CLIPS: 32, block 7 in red[52..55], free until ring entry #2 takes red[56..75])
-  static_assert(kLanes == 16, "reset_robot / sample_poses assume 16 lanes per robot");
+  static_assert(kLanes == 16, "reset_robot / the pose sampler assume 16 lanes per robot");
   int set_id = 0, set_n = 0;
   if constexpr (CLIPS) {   // the type's clip set, one id per lane, in flight while the Philox blocks are evaluated
     static_assert(ORR_MAX_CLIPS == kLanes, "one clip-set entry per lane");

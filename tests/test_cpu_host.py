@@ -151,11 +151,12 @@ def test_the_kernel_tuning_knobs_still_compile(defs):
     source; their measurements stay in HISTORY.md / profiles/r04_ab*): the development aids - the readable twin of the hand-scheduled PGS
     block, the phase timers, the dual-contact counter, the wave timeline - and the two launch-shape experiments the tools still drive
     (tools/wave_pairing.py).  Each goes through the device compiler's front end here (syntax + templates + static_asserts; well under a
-    second each), in all three translation units."""
+    second each), in all four translation units of the env kernels."""
     import subprocess
     base = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + ["--cuda-device-only", "-fsyntax-only", "-Wno-unused-command-line-argument"]
     csrc = os.path.dirname(_lib.SRC)
-    for src in (_lib.SRC, os.path.join(csrc, "orr_kernels_w2.hip"), os.path.join(csrc, "orr_kernels_anchor.hip")):
+    for src in (_lib.SRC, os.path.join(csrc, "orr_kernels_w2.hip"), os.path.join(csrc, "orr_kernels_anchor.hip"),
+                os.path.join(csrc, "orr_kernels_multiclip.hip")):
         r = subprocess.run([_lib.HIPCC] + base + defs + [src], capture_output=True, text=True)
         assert r.returncode == 0, "%s %s:\n%s" % (os.path.basename(src), " ".join(defs), r.stderr[-1500:])
 
