@@ -87,7 +87,10 @@ extern "C" {
   /* ABI v5, behind the ring (never staged with the head): Bullet's friction anchors, one cached contact point per toe             \
    * (btPersistentManifold::replaceContactPoint): the point on the toe in the lower-leg link frame (3) and on the plane in world (3) */ \
   X(ANCHOR, 4 * 6, F)                                                                         \
-  X(ANCHOR_VALID, 4, I)  /* per leg: 1 = that toe holds a cached point */
+  X(ANCHOR_VALID, 4, I)  /* per leg: 1 = that toe holds a cached point */                    \
+  /* behind the anchors (never staged with the head): motion time at which the next clip is drawn (orr_set_clip_switch); written by   \
+   * the multi-clip variants only, +inf = never (state.default_state's initial value) */                                        \
+  X(CLIP_CHANGE_TIME, 1, F)
 
 enum orr_state_offset_e {
 #define ORR_X_OFF(name, words, kind) ORR_OFF_##name, ORR_OFFEND_##name = ORR_OFF_##name + (words)-1,
@@ -260,6 +263,21 @@ int32_t orr_set_clip_set(orr_handle* h, int32_t robot_type, const int32_t* clip_
 /* clip log int32[ep_log_capacity] (device; NULL unbinds): while the multi-clip variants run, episode-log row `slot` also gets the
  * clip the ending episode played in clip_log[slot].  The capacity is orr_bind's. */
 int32_t orr_bind_clip_log(orr_handle* h, int32_t* clip_log_dev);
+
+/* mid-episode clip switching of a robot type (ImitationTask's clip_time_min / clip_time_max: _reset_clip_change_time, _check_change_clip,
+ * _update_ref_motion, imitation_task.py:734-761,1057-1069,1096-1101).  tmin = tmax = +inf (the default) = never; otherwise
+ * 0 <= tmin <= tmax < inf.  Turning switching off on a running handle stops it from the next step on (a record keeps its finite
+ * CLIP_CHANGE_TIME until its next reset writes +inf, but no step switches it).  Refused: NaN, a negative value, tmin > tmax, exactly one infinite bound, friction anchors on the handle;
+ * a rejected call changes nothing.  A type whose clip set has one clip (or none) never switches.  Draw rule, on the episode's
+ * (seed, robot index, episode) stream u_d (d = 4 * Philox block + word):
+ *   reset: CLIP_CHANGE_TIME = t0 + tmin + u_29 (tmax - tmin), t0 = the motion time after the reset (warm-up shift included);
+ *   step whose env-step counter before the step is s, when the motion time t (old offset) >= CLIP_CHANGE_TIME and the set has n > 1
+ *   clips: with d = 32 + 4 s (Philox block 8 + s), CLIP_ID = set[(m_d n) >> 24] (as at a reset), CLIP_CHANGE_TIME = t + tmin +
+ *   u_(d+1) (tmax - tmin), TIME_OFFSET = u_(d+2) * the new clip's duration, PREV_PHASE = the new clip's phase at t, and the
+ *   reference origin is synchronised in heading (relative to the robot's init orientation) and horizontal position at the new time.
+ * Pose, velocity, target frames and termination of that step use the new clip at the new time.  The multi-clip kernel variants do
+ * this (orr_set_clip_set); the parity replays (orr_debug_replay_step / _reset) run them while some type has a switch range. */
+int32_t orr_set_clip_switch(orr_handle* h, int32_t robot_type, float tmin, float tmax);
 
 /* replaces WrapperEnv.reset (wrapper_env.py:87-107): mask_dev NULL = all robots; obs_dev [N,160]
  * (rows of robots that are not reset are left untouched). */

@@ -51,7 +51,7 @@ HIPCC_FLAGS_W2 = ["-Os" if f == "-O2" else ("-amdgpu-sched-strategy=iterative-ma
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
     "orr_layout_offset", "orr_layout_size", "orr_layout_is_int", "orr_sizeof_config", "orr_sizeof_model",
-    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_bind_clip_log", "orr_bind", "orr_reset", "orr_step",
+    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_bind_clip_log", "orr_bind", "orr_reset", "orr_step",
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
@@ -221,6 +221,8 @@ def load():
     L.orr_set_motion.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_float)]
     L.orr_set_clip_set.restype = C.c_int32
     L.orr_set_clip_set.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+    L.orr_set_clip_switch.restype = C.c_int32
+    L.orr_set_clip_switch.argtypes = [vp, C.c_int32, C.c_float, C.c_float]
     L.orr_bind_clip_log.restype = C.c_int32
     L.orr_bind_clip_log.argtypes = [vp, vp]
     L.orr_bind.restype = C.c_int32

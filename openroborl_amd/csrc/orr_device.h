@@ -110,6 +110,8 @@ struct DevTables {
   int clip_set[ORR_MAX_ROBOT_TYPES][ORR_MAX_CLIPS];   // a type's set = 64 bytes, one word per lane of a robot
   int clip_set_n[ORR_MAX_ROBOT_TYPES];                // 0 = no set: a reset keeps the record's CLIP_ID
   int* clip_log;                                      // orr_bind_clip_log: clip of each logged episode (row = episode-log slot), or NULL
+  // mid-episode clip switching (orr_set_clip_switch), read by the multi-clip variants only.  APPENDED like the clip sets
+  float clip_switch[ORR_MAX_ROBOT_TYPES][2];          // (tmin, tmax) of a type's switch interval; (+inf, +inf) = never
 };
 
 // Replay inputs of the parity entry points orr_debug_replay_reset / orr_debug_replay_step (kernel MODE 2): the scripted states,

@@ -147,7 +147,8 @@ constexpr int step_wpb() { return MODE == 0 && WPE == 1 ? ORR_WPB : 1; }
 // AnchorState).  Same source; its own instantiations (one wave per SIMD whatever the batch size: an optional physics feature, not the
 // measured path), so that the default kernels carry nothing of it.
 // CLIPS: the multi-clip variant (orr_kernels_multiclip.hip, one wave per SIMD whatever the batch size): the auto-reset draws the new
-// episode's clip from the robot type's clip set (reset_robot<true>) and the episode log also records the clip of the ending episode
+// episode's clip from the robot type's clip set (reset_robot<true>), the episode log also records the clip of the ending episode, and
+// a robot whose motion time has reached the record's CLIP_CHANGE_TIME switches to a newly drawn clip mid-episode (orr_set_clip_switch)
 template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false>
 __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
@@ -160,6 +161,9 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
   // read here, far ahead of its only use (the time limit of an episode that starts in this launch)
   const long long total_snapshot = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
   load_robot(P, rec, S, lane);
+  // CLIPS: the motion time of the next clip change (behind the ring, never staged): read at the start, first used after the sub-steps
+  float clip_change = 0.0f;
+  if constexpr (CLIPS) clip_change = rec[O(CLIP_CHANGE_TIME)];
   {
     // Non-finite guard, entry half: a NaN in the INCOMING rigid state (POS..QD) does not survive the step - the velocity clamp (+-100,
     // v_med3) and the branch-free inverse trigonometric functions turn NaNs into finite numbers - so it is recorded here, in a spare
@@ -350,7 +354,45 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
   // ---- reward -> update -> done (quadruped_gym_env.py:230-233) ----
   // the frames of the new reference poses are fetched while the reward is computed (their round trip to L2 is not waited for)
   const DevClip& clip = S.clip;
-  const double t = motion_time(P, S);                       // f64: see DevClip
+  double t = motion_time(P, S);                             // f64: see DevClip
+  // CLIPS: the clip change of _update_ref_motion (imitation_task.py:734-761, 1096-1101), decided before anything samples the clip.  The
+  // phase of the update is the NEW clip's at the OLD offset's time (t_phase, :749-750); pose, targets and termination use the new time
+  double t_phase = t;
+  bool switched = false;
+  if constexpr (CLIPS) {
+    if (t >= (double)clip_change) {
+      typedef const int __attribute__((address_space(1)))* gip;
+      typedef const float __attribute__((address_space(1)))* gfp;
+      const int type = geti(S, O(ROBOT_TYPE));
+      const int set_n = ((gip)&P.tab->clip_set_n[0])[type];
+      const float sw_min = ((gfp)&P.tab->clip_switch[type][0])[0], sw_max = ((gfp)&P.tab->clip_switch[type][0])[1];
+      // num_motions > 1 (:1099), and the type still has an interval: switching turned off (orr_set_clip_switch(+inf, +inf)) stops at once,
+      // although the records keep their finite change times until their next reset
+      if (set_n > 1 && sw_max < INFINITY) {
+        // draws 32 + 4 s .. 34 + 4 s of the episode's stream (Philox block 8 + s, s = the env step counter before this step): the clip
+        // (as reset_robot<true> draws it), the next change, the new time offset (_sample_time_offset, :1112-1123)
+        float u4[4];
+        philox_block(c.seed, (uint32_t)geti(S, O(ROBOT_INDEX)), (uint32_t)geti(S, O(EPISODE_IDX)), 8u + (uint32_t)geti(S, O(EP_STEP)), u4);
+        const uint32_t m = (uint32_t)(u4[0] * 16777216.0f);
+        const int k = (int)((m * (uint32_t)set_n) >> 24);
+        const int id = ((gip)&P.tab->clip_set[type][0])[k];
+        clip_change = clip_change_time(t, sw_min, sw_max, u4[1]);
+        WSYNC();
+        if (lane == 0) seti(S, O(CLIP_ID), id);
+        const unsigned int* cg = reinterpret_cast<const unsigned int*>(&P.tab->clip[id]);
+        unsigned int* cl = reinterpret_cast<unsigned int*>(&S.clip);
+        if (lane < (int)(sizeof(DevClip) / 4)) cl[lane] = cg[lane];
+        WSYNC();
+        if (lane == 0) {
+          S.s[O(TIME_OFFSET)] = u4[2] * (float)clip.dur_d;
+          if (valid) rec[O(CLIP_CHANGE_TIME)] = clip_change;   // an auto-reset later in this step overwrites it (same lane, in order)
+        }
+        WSYNC();
+        t = motion_time(P, S);
+        switched = true;
+      }
+    }
+  }
   const double step_dt = clip.sim_dt_d * c.action_repeat;
   double tl = t;
   {  // lanes 1..4: the four target times.  Selects over the four scalars: indexing the kernel argument with the lane makes the
@@ -365,9 +407,16 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
   sample_poses_finish(P, S, lane, tl, true, PL);
   {
     // _update_ref_motion (imitation_task.py:734-761) with _sync_ref_origin (:1020-1055)
-    const float ph = clip_phase(clip, t);
+    const float ph = clip_phase(clip, t_phase);
     if (lane == 0) {
-      if ((c.flags & ORR_FLAG_CYCLE_SYNC) && ph < S.s[O(PREV_PHASE)]) {
+      bool sync_pos = (c.flags & ORR_FLAG_CYCLE_SYNC) && ph < S.s[O(PREV_PHASE)];
+      if constexpr (CLIPS) {
+        if (switched) {   // a clip change syncs the heading (relative to the init orientation, _calc_heading) first, then the position
+          q_about_z(task_heading(S, &S.s[O(QUAT)]) - task_heading(S, &S.ph.end.pose[0][3]), &S.s[O(ORIGIN_ROT)]);
+          sync_pos = true;
+        }
+      }
+      if (sync_pos) {
         float pr[3];
         qrot(&S.ph.end.pose[0][0], &S.s[O(ORIGIN_ROT)], pr);
         S.s[O(ORIGIN_POS)] = S.s[O(POS)] - pr[0];
@@ -508,6 +557,10 @@ hipError_t launch_physics_anchor(const KParams& P, int waves, hipStream_t stream
 // same reason
 hipError_t launch_step_multiclip(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done);
 hipError_t launch_reset_multiclip(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs);
+// ... and their parity replays (kernel MODE 2; reset with the draws 0..27 given), run while some type has a clip switch interval
+hipError_t launch_replay_step_multiclip(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done,
+                                        const ReplayArgs& rp);
+hipError_t launch_replay_reset_multiclip(const KParams& P, int waves, hipStream_t stream, const float* uniforms, float* obs);
 }
 #ifdef ORR_TU_MULTICLIP
 namespace orr {
@@ -517,6 +570,15 @@ hipError_t launch_step_multiclip(const KParams& P, int waves, hipStream_t stream
 }
 hipError_t launch_reset_multiclip(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs) {
   hipLaunchKernelGGL((orr_reset_kernel<true>), dim3(waves), dim3(64), 0, stream, P, mask, obs, (const float*)nullptr);
+  return hipGetLastError();
+}
+hipError_t launch_replay_step_multiclip(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done,
+                                        const ReplayArgs& rp) {
+  hipLaunchKernelGGL((orr_step_kernel<2, 1, false, true>), dim3(waves), dim3(64), 0, stream, P, actions, obs, reward, done, 0, rp);
+  return hipGetLastError();
+}
+hipError_t launch_replay_reset_multiclip(const KParams& P, int waves, hipStream_t stream, const float* uniforms, float* obs) {
+  hipLaunchKernelGGL((orr_reset_kernel<true>), dim3(waves), dim3(64), 0, stream, P, (const uint8_t*)nullptr, obs, uniforms);
   return hipGetLastError();
 }
 }  // namespace orr
@@ -604,6 +666,7 @@ struct orr_handle {
   int force_wpe;      // ORR_STEP_WAVES_PER_EU (0 = automatic)
   uint32_t anchor_types;   // bit t = robot type t has orr_model::friction_anchor: launches run the ANCHOR variant of the step kernel
   uint32_t multiclip_types;   // bit t = robot type t has a clip set of more than one clip: orr_step / orr_reset run the multi-clip variants
+  uint32_t switch_types;      // bit t = robot type t has a finite clip switch interval: the parity replays run the multi-clip variants
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -696,6 +759,9 @@ int32_t orr_create(const orr_config* cfg, orr_handle** out) {
   if (e != hipSuccess) { delete h; return fail(-2, "orr_create: hipMalloc", e); }
   e = hipMemset(h->tab_dev, 0, sizeof(DevTables));
   if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemset", e); }
+  for (int t = 0; t < ORR_MAX_ROBOT_TYPES; t++) h->tab_host.clip_switch[t][0] = h->tab_host.clip_switch[t][1] = INFINITY;   // no switching
+  e = hipMemcpy(h->tab_dev->clip_switch, h->tab_host.clip_switch, sizeof(h->tab_host.clip_switch), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemcpy", e); }
   hipEventCreate(&h->ev0);
   hipEventCreate(&h->ev1);
   *out = h;
@@ -848,6 +914,24 @@ int32_t orr_bind_clip_log(orr_handle* h, int32_t* clip_log_dev) {
   return 0;
 }
 
+int32_t orr_set_clip_switch(orr_handle* h, int32_t robot_type, float tmin, float tmax) {
+  if (!h) return fail(-1, "orr_set_clip_switch: null handle");
+  if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_clip_switch: robot_type out of range");
+  if (isnan(tmin) || isnan(tmax)) return fail(-1, "orr_set_clip_switch: NaN bound");
+  if (tmin < 0.0f || tmax < 0.0f) return fail(-1, "orr_set_clip_switch: negative bound");
+  if (tmin > tmax) return fail(-1, "orr_set_clip_switch: tmin > tmax");
+  const bool off = isinf(tmin) && isinf(tmax);
+  if (!off && (isinf(tmin) || isinf(tmax))) return fail(-1, "orr_set_clip_switch: both bounds finite, or both +inf (off)");
+  if (!off && h->anchor_types)
+    return fail(-1, "orr_set_clip_switch: friction anchors (orr_model::friction_anchor) and clip switching cannot be combined");
+  const float v[2] = {tmin, tmax};
+  HIPCHK(hipMemcpy(&h->tab_dev->clip_switch[robot_type][0], v, sizeof(v), hipMemcpyHostToDevice), "orr_set_clip_switch: hipMemcpy");
+  h->tab_host.clip_switch[robot_type][0] = tmin;
+  h->tab_host.clip_switch[robot_type][1] = tmax;
+  if (off) h->switch_types &= ~(1u << robot_type); else h->switch_types |= 1u << robot_type;
+  return 0;
+}
+
 int32_t orr_bind(orr_handle* h, void* state_dev, int64_t* counters_dev, float* ep_log_dev, int32_t ep_log_capacity) {
   if (!h || !state_dev || !counters_dev) return fail(-1, "orr_bind: null argument (state and counters are required)");
   if (((uintptr_t)state_dev & 15u) != 0) return fail(-1, "orr_bind: the state buffer must be 16-byte aligned (records move in 16-byte pieces)");
@@ -960,6 +1044,12 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
     return fail(-1, "orr_debug_replay_step: null buffer");
   if (h->cfg.flags & ORR_FLAG_AUTO_RESET) return fail(-1, "orr_debug_replay_step: needs a handle without ORR_FLAG_AUTO_RESET");
   ReplayArgs rp{traj_dev, eff_dev, fall_dev, tau_out_dev, nullptr};
+  if (h->switch_types) {   // a clip switch interval: the multi-clip replay (its draws from 28 on come from the Philox stream)
+    if (h->anchor_types) { char m[256]; snprintf(m, sizeof(m), "orr_debug_replay_step%s", kAnchorClipsMsg); return fail(-1, m); }
+    HIPCHK(launch_replay_step_multiclip(make_params(h), (h->cfg.num_robots + kRPW - 1) / kRPW, (hipStream_t)stream, actions_dev, obs_dev, reward_dev,
+                                        done_dev, rp), "orr_debug_replay_step: launch (clip switching)");
+    return 0;
+  }
   hipLaunchKernelGGL(orr_step_kernel<2>, dim3((h->cfg.num_robots + kRPW - 1) / kRPW), dim3(64), 0, (hipStream_t)stream, make_params(h), actions_dev,
                      obs_dev, reward_dev, done_dev, 0, rp);
   HIPCHK(hipGetLastError(), "orr_debug_replay_step: launch");
@@ -967,6 +1057,12 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
 }
 int32_t orr_debug_replay_reset(orr_handle* h, const float* uniforms_dev, float* obs_dev, void* stream) {
   if (!h || !h->state || !uniforms_dev) return fail(-1, "orr_debug_replay_reset: bad argument");
+  if (h->switch_types) {   // a clip switch interval: the multi-clip reset (draws 0..27 from uniforms_dev, 28 on from the Philox stream)
+    if (h->anchor_types) { char m[256]; snprintf(m, sizeof(m), "orr_debug_replay_reset%s", kAnchorClipsMsg); return fail(-1, m); }
+    HIPCHK(launch_replay_reset_multiclip(make_params(h), (h->cfg.num_robots + kRPW - 1) / kRPW, (hipStream_t)stream, uniforms_dev, obs_dev),
+           "orr_debug_replay_reset: launch (clip switching)");
+    return 0;
+  }
   hipLaunchKernelGGL(orr_reset_kernel<>, dim3((h->cfg.num_robots + kRPW - 1) / kRPW), dim3(64), 0, (hipStream_t)stream, make_params(h),
                      (const uint8_t*)nullptr, obs_dev, uniforms_dev);
   HIPCHK(hipGetLastError(), "orr_debug_replay_reset: launch");

@@ -245,6 +245,19 @@ __device__ __forceinline__ void task_heading_rot(const Shared& S, const float q[
   qmul(q, dc, rel);
   q_about_z(qheading(rel), out);
 }
+__device__ __forceinline__ float task_heading(const Shared& S, const float q[4]) {  // _calc_heading, imitation_task.py:1143-1166
+  float dc[4], rel[4];
+  qconj(S.m.init_quat, dc);
+  qmul(q, dc, rel);
+  return qheading(rel);
+}
+
+// the motion time of the next clip change (_reset_clip_change_time, imitation_task.py:1057-1069): t + U(tmin, tmax) in float64 as the
+// reference computes it (numpy's uniform: low + (high - low) u), rounded to the record's float32; +inf where switching is off
+__device__ __forceinline__ float clip_change_time(double t, float tmin, float tmax, float u) {
+  if (!(tmax < INFINITY)) return INFINITY;   // orr_set_clip_switch: both bounds finite, or both +inf
+  return (float)(t + ((double)tmin + ((double)tmax - (double)tmin) * (double)u));
+}
 
 // ImitationTask.reward (imitation_task.py:341-516); every lane returns the same value
 // eff_replay (parity replay only, else NULL): [2][8][3] link positions that replace the forward kinematics
@@ -362,7 +375,8 @@ __device__ static void sensors_push(Shared& S, int lane, bool fill_all) {
 // ================================================================================================
 // uni_replay (parity replay only, else NULL): 28 draws in [0, 1) that replace the Philox stream
 // CLIPS (the multi-clip variants, orr_kernels_multiclip.hip): the episode's clip is drawn from the robot type's clip set (DevTables::clip_set)
-// with draw 28 (Philox block 7, word 0) before anything reads the clip, and CLIP_ID / S.clip hold it from then on
+// with draw 28 (Philox block 7, word 0) before anything reads the clip, and CLIP_ID / S.clip hold it from then on; the record's
+// CLIP_CHANGE_TIME (behind the ring: written here, in memory) gets the episode's first clip change, draw 29 (orr_set_clip_switch)
 template <bool CLIPS = false>
 __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int lane, bool valid, long long total_step_count, float* obs,
                                    const float* uni_replay = nullptr) {
@@ -404,12 +418,16 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
   float* draws = S.ph.end.red + 24;    // 28 words (CLIPS: 32, block 7 in red[52..55], free until ring entry #2 takes red[56..75])
   static_assert(kLanes == 16, "reset_robot / the pose sampler assume 16 lanes per robot");
   int set_id = 0, set_n = 0;
-  if constexpr (CLIPS) {   // the type's clip set, one id per lane, in flight while the Philox blocks are evaluated
+  float sw_min = 0.0f, sw_max = 0.0f;
+  if constexpr (CLIPS) {   // the type's clip set, one id per lane, and switch interval, in flight while the Philox blocks are evaluated
     static_assert(ORR_MAX_CLIPS == kLanes, "one clip-set entry per lane");
     typedef const int __attribute__((address_space(1)))* gip;
+    typedef const float __attribute__((address_space(1)))* gfp;
     const int type = geti(S, O(ROBOT_TYPE));
     set_id = ((gip)&P.tab->clip_set[type][0])[lane];
     set_n = ((gip)&P.tab->clip_set_n[0])[type];
+    sw_min = ((gfp)&P.tab->clip_switch[type][0])[0];
+    sw_max = ((gfp)&P.tab->clip_switch[type][0])[1];
   }
   if (lane < (CLIPS ? 8 : 7)) {
     float u4[4];
@@ -418,9 +436,11 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
     draws[4 * lane] = u4[0]; draws[4 * lane + 1] = u4[1]; draws[4 * lane + 2] = u4[2]; draws[4 * lane + 3] = u4[3];
   }
   WSYNC();
+  float u_change = 0.0f;   // CLIPS: draw 29, the first clip change (red[] is reused before it is needed)
   if constexpr (CLIPS) {
     // draw 28 -> k = (m n) >> 24, m = its 24-bit integer (u = m / 2^24 exactly): integer arithmetic, uniform over the n entries.  The lane
     // that holds set[k] writes CLIP_ID; then the clip header is staged again, one word per lane (as load_robot does)
+    u_change = draws[29];
     const uint32_t m = (uint32_t)(draws[28] * 16777216.0f);
     const int k = (int)((m * (uint32_t)set_n) >> 24);
     if (set_n > 0 && lane == k) seti(S, O(CLIP_ID), set_id);
@@ -498,6 +518,7 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
     const float dh = qheading(&S.s[O(QUAT)]) - qheading(&S.ph.end.pose[0][3]);
     q_about_z(dh, &S.s[O(ORIGIN_ROT)]);
     S.s[O(PREV_PHASE)] = clip_phase(clip, t);
+    if constexpr (CLIPS) { if (valid) rec[O(CLIP_CHANGE_TIME)] = clip_change_time(t, sw_min, sw_max, u_change); }
   }
   WSYNC();
   apply_origin(S, lane, 5);

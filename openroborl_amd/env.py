@@ -114,6 +114,55 @@ def clip_draw_index(m, n):
     return (np.asarray(m, dtype=np.int64) * int(n)) >> 24
 
 
+CLIP_CHANGE_DRAW = 29   # the first clip change of an episode: draw 29 of the reset's stream (block 7, word 1)
+
+
+def clip_switch_draws(ep_step):
+    """Draw indices (clip, next change, time offset) of a mid-episode clip switch in the step whose env-step counter before the step
+    is ep_step (csrc/orr_kernels.hip, orr_step_kernel<.., CLIPS>): 32 + 4 s, 33 + 4 s, 34 + 4 s = Philox block 8 + s, words 0..2 of the
+    episode's (seed, robot index, episode) stream.  The clip is set[clip_draw_index(m, n)] with m the 24-bit integer of the first."""
+    d = 32 + 4 * np.asarray(ep_step, dtype=np.int64)
+    return d, d + 1, d + 2
+
+
+def clip_change_time(t, tmin, tmax, u):
+    """The next clip change at motion time t (_reset_clip_change_time, imitation_task.py:1057-1069): t + tmin + (tmax - tmin) u in
+    float64, stored as float32 (the record's CLIP_CHANGE_TIME); +inf where switching is off."""
+    if not math.isfinite(tmax):
+        return np.float32(np.inf)
+    return np.float32(float(t) + (float(np.float32(tmin)) + (float(np.float32(tmax)) - float(np.float32(tmin))) * float(u)))
+
+
+def clip_switch_spec(clip_time_min, clip_time_max, robot_names):
+    """clip_time_min / clip_time_max (ImitationTask's kwargs: a float, or a dict by robot name for mixed batches; None = +inf) ->
+    {robot name: (tmin, tmax)}.  (+inf, +inf) = no switching (the reference's default); otherwise both finite, 0 <= tmin <= tmax.
+    ValueError on anything the C-ABI (orr_set_clip_switch) would refuse."""
+    def per_name(v, name, what):
+        if isinstance(v, dict):
+            unknown = set(v) - set(robot_names)
+            if unknown:
+                raise ValueError("%s names robots that are not in this batch: %s" % (what, sorted(unknown)))
+            v = v.get(name)
+        if v is None:
+            return math.inf
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number or a dict by robot name, not %r" % (what, v))
+        return float(v)
+    out = {}
+    for name in robot_names:
+        lo, hi = per_name(clip_time_min, name, "clip_time_min"), per_name(clip_time_max, name, "clip_time_max")
+        if math.isnan(lo) or math.isnan(hi):
+            raise ValueError("clip_time_min / clip_time_max of %s: NaN" % name)
+        if lo < 0 or hi < 0:
+            raise ValueError("clip_time_min / clip_time_max of %s must not be negative" % name)
+        if lo > hi:
+            raise ValueError("clip_time_min > clip_time_max for %s" % name)
+        if math.isinf(lo) != math.isinf(hi):
+            raise ValueError("clip_time_min / clip_time_max of %s: both finite, or both inf (no switching)" % name)
+        out[name] = (lo, hi)
+    return out
+
+
 def action_space():
     """minitaur.py:145-148."""
     return Box(np.array([-2 * math.pi] * 12), np.array([2 * math.pi] * 12), dtype=np.float32)
@@ -125,7 +174,7 @@ class VecQuadrupedEnv(object):
     def __init__(self, task_name=None, training_yaml=None, sim_yaml=None, device="cuda", num_robot=None, seed=None,
                  robot=None, motion_file=None, mode=None, enable_randomizer=None, auto_reset=True, num_procs=1,
                  robot_index_offset=0, legacy_grid=False, mixed_robots=None, ep_log_capacity=65536, config_overrides=None,
-                 model_overrides=None):
+                 model_overrides=None, clip_time_min=None, clip_time_max=None):
         import torch
         self.torch = torch
         if not torch.cuda.is_available():
@@ -187,6 +236,11 @@ class VecQuadrupedEnv(object):
         type_to_clip = {robots.ROBOT_TYPE_ID[n]: ids[0] for n, ids in self.clip_sets.items()}
         clip_id = np.array([type_to_clip[t] for t in robot_type], dtype=np.int32)
         self.multi_clip = any(len(ids) > 1 for ids in self.clip_sets.values())
+        # mid-episode clip switching (ImitationTask's clip_time_min / clip_time_max; the task YAML may carry the same keys): every
+        # U(tmin, tmax) seconds of motion time a robot draws a new clip from its set.  Off (inf) by default, as in the reference
+        clip_time_min = clip_time_min if clip_time_min is not None else params.get("clip_time_min")
+        clip_time_max = clip_time_max if clip_time_max is not None else params.get("clip_time_max")
+        self.clip_switch = clip_switch_spec(clip_time_min, clip_time_max, sorted(set(self.robot_names)))
         self.robot_type = robot_type
         self.clip_id = clip_id
 
@@ -207,6 +261,9 @@ class VecQuadrupedEnv(object):
         for name, ids in self.clip_sets.items():
             arr = (C.c_int32 * len(ids))(*ids)
             _lib.check(self.L.orr_set_clip_set(self.h, robots.ROBOT_TYPE_ID[name], arr, len(ids)), self.L)
+        for name, (lo, hi) in self.clip_switch.items():
+            if math.isfinite(lo):
+                _lib.check(self.L.orr_set_clip_switch(self.h, robots.ROBOT_TYPE_ID[name], lo, hi), self.L)
         self.layout = statemod.Layout(self.L, "orr")
         idx = np.arange(num_robot, dtype=np.int32) + int(robot_index_offset)
         st = statemod.default_state(self.layout, num_robot, self.models, robot_type, clip_id, idx,

@@ -71,6 +71,7 @@ def default_state(layout, n, models, robot_type, clip_id, robot_index, legacy_gr
     st[:, layout.sl("BASE_DAMPING")] = np.asarray(base_damping, dtype=np.float32)
     st[:, layout.sl("ORIGIN_ROT")] = np.array([0, 0, 0, 1], dtype=np.float32)
     st[:, layout.sl("QUAT")] = np.array([0, 0, 0, 1], dtype=np.float32)
+    st[:, layout.sl("CLIP_CHANGE_TIME")] = np.inf          # no clip change (written by the multi-clip kernels only: orr_set_clip_switch)
     for t, m in enumerate(models):
         sel = robot_type == t
         if m is not None and sel.any():

@@ -31,6 +31,9 @@ def main():
     ap.add_argument("--motion-file", action="append", default=None,
                     help="reference motion clip (repeatable; overrides the task YAML's motion_file): several = the clip set every reset "
                          "draws the episode's clip from (ImitationTask's ref_motion_filenames)")
+    ap.add_argument("--clip-time", type=float, nargs=2, metavar=("MIN", "MAX"), default=None,
+                    help="switch to a newly drawn clip of the set every U(MIN, MAX) seconds of motion time, mid-episode (ImitationTask's "
+                         "clip_time_min / clip_time_max; overrides the task YAML's; default: never)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
     ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip")
@@ -64,7 +67,8 @@ def main():
     dev = torch.device("cuda", 0 if os.environ.get("ORR_BENCH_SINGLE_DEVICE") else local)
     torch.cuda.set_device(dev)
     env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
-                          device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file)
+                          device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
+                          **clip_time_kwargs(args))
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     model = ppo.ActorCritic(dev, params=params, seed=args.seed)                     # same seed -> identical replicas
     if not args.torch_policy:
@@ -135,6 +139,11 @@ def main():
         torch.distributed.destroy_process_group()
 
 
+def clip_time_kwargs(args):
+    """--clip-time MIN MAX -> the env's clip_time_min / clip_time_max (nothing given: the task YAML's, else no switching)."""
+    return {} if args.clip_time is None else dict(clip_time_min=args.clip_time[0], clip_time_max=args.clip_time[1])
+
+
 def clip_name(env, clip_id):
     """'<id>:<file name>' of a clip of the env (ids keep a file listed twice apart)."""
     return "%d:%s" % (clip_id, os.path.splitext(os.path.basename(env.clips[clip_id].path))[0])
@@ -145,7 +154,7 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     dev = torch.device("cuda", 0)
     n = min(args.num_robot, 1024)
     env = VecQuadrupedEnv(task_name=args.task, num_robot=n, mode="test", auto_reset=False, seed=args.seed, device=dev,
-                          motion_file=args.motion_file)
+                          motion_file=args.motion_file, **clip_time_kwargs(args))
     model = ppo.ActorCritic(dev, params=pol.load_parameters(args.eval))
     if not args.torch_policy:
         model.enable_fused()
