@@ -207,8 +207,8 @@ typedef struct orr_model {
 /* device-side global counters, caller-owned int64[ORR_NUM_COUNTERS], zero-initialised */
 enum orr_counter_e {
   ORR_CNT_TOTAL_STEP_COUNT = 0, /* wrapper_env.py:47,82-83 curriculum counter */
-  ORR_CNT_DONE_ACCUM = 1,       /* per-launch scratch */
-  ORR_CNT_TICKET = 2,           /* per-launch scratch */
+  ORR_CNT_DONE_ACCUM = 1,       /* per-launch scratch (unused; zero) */
+  ORR_CNT_TICKET = 2,           /* per-launch scratch: the launch tally, done count << 32 | robots counted; zero between launches */
   ORR_CNT_TOTAL_TIMESTEPS = 3,  /* robot-steps executed (ppo_imitation.py:421) */
   ORR_CNT_EPISODES = 4,         /* finished episodes appended to the episode log */
   ORR_CNT_EPLOG_DROPPED = 5,

@@ -110,7 +110,8 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
   const bool valid = in_range && !(mask && !mask[robot]);
   load_robot(P, rec, S, lane);
   const long long total = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
-  reset_robot<CLIPS>(P, rec, S, lane, valid, total, obs, uniforms ? uniforms + (size_t)robot * 28 : nullptr);
+  const ResetConst RC = load_reset_const(P, S, lane);
+  reset_robot<CLIPS>(P, rec, S, lane, valid, total, obs, RC, uniforms ? uniforms + (size_t)robot * 28 : nullptr);
   WSYNC();
   store_robot(rec, S, lane, valid);
   // a new episode: no cached contact points (ANCHOR, ANCHOR_VALID: 28 words behind the ring).  Unconditional: friction anchors may be switched
@@ -340,6 +341,10 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
   // past its sub-step loop (reward, observation, reset, store: few vector instructions between long memory waits) a wave issues ahead of its
   // partner: it costs the partner next to nothing and shortens the tail (8192 robots: -0.1 %; with -Os for this unit -0.4 %, profiles/r04_ab29_8192.log)
   if (WPE == 2) __builtin_amdgcn_s_setprio(3);
+  // the cold-table constants of an auto-reset (ResetConst), issued here, ahead of the step end's stores and atomics.  Loaded again
+  // rather than taken from the registers that hold some of them over the sub-steps (m_init is dead by now): keeping those live up to
+  // the reset moved the sub-step loop's register allocation (+10 instructions) for a launch no faster
+  const ResetConst RC = load_reset_const(P, S, lane);
   if (lane == 0) {  // end of robot_step (minitaur.py:287-293)
     seti(S, O(RING_HEAD), ring.head); seti(S, O(RING_LEN), ring.len);
     seti(S, O(STATE_ACTION_COUNTER), action_counter);
@@ -494,7 +499,7 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
     WSYNC();
     if (c.flags & ORR_FLAG_AUTO_RESET) {
       PT(31);
-      reset_robot<CLIPS>(P, rec, S, lane, valid, total_snapshot, obs);
+      reset_robot<CLIPS>(P, rec, S, lane, valid, total_snapshot, obs, RC);
       if constexpr (ANCHOR) AS = AnchorState{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};   // a new episode: no cached contact points
     }
     if (logs && P.ep_log) {
@@ -525,20 +530,23 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
   PT(15);
   PT_FLUSH();
   // One counter update per WAVE (the compiler's own atomic combining is switched off, see _lib.HIPCC_FLAGS: it makes the issuing
-  // lane wait for the returned value on the spot): thread 0 adds the wave's finished episodes to the launch accumulator and takes
-  // a ticket for the wave's robots; the last wave to finish folds the launch's done count into the curriculum counter
-  // (wrapper_env.py:82-83).
+  // lane wait for the returned value on the spot).  The launch tally is ONE 64-bit word (ORR_CNT_TICKET: finished episodes in the
+  // high half, robots counted in the low half), so one returning atomic both adds the wave's finished episodes and takes its ticket:
+  // there is no second word to order it against, and no fence (it cost 7 % of the launch: a write-back of the wave's ~18 KB of fresh
+  // stores, an L2 invalidate and two waits).  The wave that completes the count folds the done count into the
+  // curriculum counter (wrapper_env.py:82-83) and clears the word with non-returning atomics.  The fold may land while other waves
+  // still run: every wave read its snapshot of the curriculum counter when it started, and the last ticket can only be taken once
+  // every wave of the launch has started (and taken its own).  The episode log and the records are read after the kernel boundary only.
+  // Issued HERE, not with the episode-log slot: held across the reset, the returned value moved the sub-step loop's register
+  // allocation (+6 instructions) and the launch got slower (0.1993 against 0.1976 ms).
   const unsigned long long fin_mask = __ballot(valid && lane == 0 && reason != 0), val_mask = __ballot(valid && lane == 0);
   if (wtid == 0) {
-    const unsigned long long nfin = (unsigned long long)__popcll(fin_mask), nval = (unsigned long long)__popcll(val_mask);
-    if (nfin) atomicAdd((unsigned long long*)&P.counters[ORR_CNT_DONE_ACCUM], nfin);
-    __threadfence();  // this wave's DONE_ACCUM / episode-log writes are visible before its ticket is
-    const unsigned long long ticket = atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TICKET], nval);
-    if (ticket + nval == (unsigned long long)P.cfg.num_robots) {
-      const unsigned long long nd = atomicExch((unsigned long long*)&P.counters[ORR_CNT_DONE_ACCUM], 0ull);
-      atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TOTAL_STEP_COUNT], nd);
+    const unsigned long long add = ((unsigned long long)__popcll(fin_mask) << 32) | (unsigned long long)__popcll(val_mask);
+    const unsigned long long now = atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TICKET], add) + add;
+    if ((unsigned int)now == (unsigned int)P.cfg.num_robots) {   // the low half never carries: it counts up to num_robots
+      atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TOTAL_STEP_COUNT], now >> 32);
       atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TOTAL_TIMESTEPS], (unsigned long long)P.cfg.num_robots);
-      atomicExch((unsigned long long*)&P.counters[ORR_CNT_TICKET], 0ull);
+      atomicExch((unsigned long long*)&P.counters[ORR_CNT_TICKET], 0ull);   // every other wave's update came before this wave's
     }
   }
   PT_TIMELINE((long long)((fin_mask & 1ull) | ((fin_mask >> 15) & 2ull) | ((fin_mask >> 30) & 4ull) | ((fin_mask >> 45) & 8ull)));   // one bit per robot of the wave

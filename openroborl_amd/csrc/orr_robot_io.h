@@ -91,19 +91,35 @@ __device__ __forceinline__ void base_rotation(Shared& S, int lane, float rel[4],
   for (int i = 0; i < 9; i++) S.Rb[i] = Rb[i];   // the same in every lane: all of them store it (no divergent `if`)
 }
 
+// The cold-table constants of a reset, per lane: those of the lane's motor (lane = motor; lanes 12..15 repeat motor 0) and one word
+// of the initial base position (lanes 0..2; the others repeat word 0).  The step kernel issues these loads right past its sub-steps,
+// ahead of the step end's stores and atomics: reset_robot / receive_obs loading them behind those added a dependent round trip
+// (~30 k cycles) to the auto-reset's critical path.
+struct ResetConst {
+  int j;              // joint_of_motor
+  float off, dir;     // motor_offset, motor_dir
+  float init;         // init_motor_angles
+  float p0;           // init_pos
+};
+__device__ __forceinline__ ResetConst load_reset_const(const KParams& P, const Shared& S, int lane) {
+  const ColdPtr mc = model_cold(P, geti(S, O(ROBOT_TYPE)));
+  const int ml = lane < 12 ? lane : 0;
+  return ResetConst{mc->joint_of_motor[ml], mc->motor_offset[ml], mc->motor_dir[ml], mc->init_motor_angles[ml], mc->init_pos[lane < 3 ? lane : 0]};
+}
+
 // Minitaur.receive_obs + get_true_obs (minitaur.py:304-334): push the true observation.  entry: optional copy of the pushed
 // entry (20 words, LDS) for callers that build the control observation without reading the ring back (reset_robot).
-__device__ static void receive_obs(const KParams& P, float* rec, Shared& S, int lane, bool valid, float* entry = nullptr) {
-  const ColdPtr mc = model_cold(P, geti(S, O(ROBOT_TYPE)));
+// RC: the lane's constants (load_reset_const; only the motor's joint, offset and direction are read)
+__device__ static void receive_obs(const KParams& P, float* rec, Shared& S, int lane, bool valid, const ResetConst& RC, float* entry = nullptr) {
   const int head = (geti(S, O(RING_HEAD)) + 1) % ORR_RING_DEPTH, len = geti(S, O(RING_LEN));
   float rel[4], Rb[9], rate[3];
   base_rotation(S, lane, rel, Rb);
   mtv3(Rb, &S.s[O(ANGVEL)], rate);  // get_true_base_rpy_rate (minitaur.py:640-672): angular velocity in the base frame
   for (int i = lane; i < ORR_RING_ENTRY; i += kLanes) {
     float val = 0.0f;
-    if (i < 12) {
-      int j = mc->joint_of_motor[i];
-      val = (S.s[O(Q) + j] - mc->motor_offset[i]) * mc->motor_dir[i];  // get_true_motor_angles (:543-553)
+    if (i < 12) {   // i == lane (kLanes > 12): the lane's own motor
+      static_assert(kLanes >= 12, "the first pass of the loop covers the twelve motors");
+      val = (S.s[O(Q) + RC.j] - RC.off) * RC.dir;  // get_true_motor_angles (:543-553)
     } else if (i < 16) {
       val = i == 12 ? rel[0] : (i == 13 ? rel[1] : (i == 14 ? rel[2] : rel[3]));
     } else if (i < 19) {

@@ -377,20 +377,19 @@ __device__ static void sensors_push(Shared& S, int lane, bool fill_all) {
 // CLIPS (the multi-clip variants, orr_kernels_multiclip.hip): the episode's clip is drawn from the robot type's clip set (DevTables::clip_set)
 // with draw 28 (Philox block 7, word 0) before anything reads the clip, and CLIP_ID / S.clip hold it from then on; the record's
 // CLIP_CHANGE_TIME (behind the ring: written here, in memory) gets the episode's first clip change, draw 29 (orr_set_clip_switch)
+// RC: the lane's cold-table constants (load_reset_const; the step kernel issues those loads right past its sub-steps)
 template <bool CLIPS = false>
 __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int lane, bool valid, long long total_step_count, float* obs,
-                                   const float* uni_replay = nullptr) {
+                                   const ResetConst& RC, const float* uni_replay = nullptr) {
   const orr_config& c = P.cfg;
   // every reset starts a new episode = a new RNG stream (robot, episode)
   const uint32_t robot = (uint32_t)geti(S, O(ROBOT_INDEX)), ep = (uint32_t)geti(S, O(EPISODE_IDX)) + 1u;
   WSYNC();
   if (lane == 0) seti(S, O(EPISODE_IDX), (int)ep);
-  // 1-2. default pose at the grid slot, counters, ring, filter (minitaur.py:246-268, 465-483).  The per-motor reset constants come from
-  // the cold table: all lanes load (clamped index), no divergent `if` around the loads
-  const ColdPtr mc = model_cold(P, geti(S, O(ROBOT_TYPE)));
-  const int lm = lane < 12 ? lane : 0, l3 = lane < 3 ? lane : 0;
-  const int rj = mc->joint_of_motor[lm];
-  const float r_q0 = mc->init_motor_angles[lm] + mc->motor_offset[lm], r_p0 = mc->init_pos[l3];
+  // 1-2. default pose at the grid slot, counters, ring, filter (minitaur.py:246-268, 465-483).  The per-motor reset constants are the
+  // caller's (RC), like the initial base position
+  const int rj = RC.j;
+  const float r_q0 = RC.init + RC.off, r_p0 = RC.p0;
   if (lane < 3) {
     S.s[O(POS) + lane] = r_p0 + (lane < 2 ? S.s[O(GRID_OFFSET) + lane] : 0.0f);
     S.s[O(LINVEL) + lane] = 0.0f; S.s[O(ANGVEL) + lane] = 0.0f;
@@ -481,7 +480,7 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
   // ring entries #1 and #2 of the new episode are kept (LDS) so that the control observations of the reset are blended from them
   // directly: reading the ring back would be a store -> load round trip through memory each time
   float* e1 = S.ph.end.red;            // 20 words each
-  receive_obs(P, rec, S, lane, valid, e1);  // ring entry #1
+  receive_obs(P, rec, S, lane, valid, RC, e1);  // ring entry #1
   // 3. sensor histories <- 3 copies of the current readings (minitaur.py:270-271; sensor_wrappers.py:122-129)
   PT(17);
   WSYNC();
@@ -537,7 +536,7 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
   WSYNC();
   PT(22);
   float* e2 = S.ph.end.red + 56;         // ring entry #2; entry #1 was saved in registers below before red[] was reused
-  receive_obs(P, rec, S, lane, valid, e2);  // ring entry #2 (imitation_task.py:792)
+  receive_obs(P, rec, S, lane, valid, RC, e2);  // ring entry #2 (imitation_task.py:792)
   {
     // control observation with two entries in the ring (Minitaur._get_delay_obs, minitaur.py:336-357): latency <= 0 -> newest;
     // int(latency / dt) + 1 >= 2 -> the OLDEST entry (#1, the default pose: SURVEY 8a quirk 3); else blend newest / #1

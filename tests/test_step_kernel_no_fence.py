@@ -1,0 +1,52 @@
+"""Compile-only (no GPU): the env step kernels end without a device-wide cache write-back.
+
+The launch tally is one packed 64-bit word (orr_kernels.hip, end of orr_step_kernel), so no wave needs a fence between its counter
+updates.  A `__threadfence()` compiles to `buffer_wbl2` (+ an L2 invalidate and waits) on gfx950; it cost 7 % of the 4096-robot launch.
+Checked in the full env step (MODE 0) and its parity replay (MODE 2) of every translation unit that holds them.
+"""
+import os
+import re
+import subprocess
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+from openroborl_amd import _lib
+
+UNITS = [(_lib.SRC, _lib.HIPCC_FLAGS), (_lib.SRC_W2, _lib.HIPCC_FLAGS_W2), (_lib.SRC_ANCHOR, _lib.HIPCC_FLAGS),
+         (_lib.SRC_MULTICLIP, _lib.HIPCC_FLAGS)]
+
+
+def kernel_bodies(asm):
+    """{symbol: instructions} of every orr_step_kernel instantiation in a device assembly listing"""
+    lines = asm.split("\n")
+    out = {}
+    for i, l in enumerate(lines):
+        m = re.match(r"^(_Z15orr_step_kernel\S*):", l)
+        if m:
+            end = next(j for j in range(i, len(lines)) if lines[j].strip().startswith("s_endpgm"))
+            out[m.group(1)] = [t.split(";")[0].strip() for t in lines[i:end + 1]]
+    return out
+
+
+def compile_unit(src, flags, out_dir):
+    out = os.path.join(out_dir, os.path.basename(src) + ".s")
+    f = [x for x in flags if x not in ("-shared", "-fPIC")]
+    subprocess.check_call([_lib.HIPCC] + f + ["-S", "--cuda-device-only", "-o", out, src], stderr=subprocess.DEVNULL)
+    with open(out) as fh:
+        return fh.read()
+
+
+def test_no_cache_writeback_in_step_kernels():
+    with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(len(UNITS)) as ex:
+        asms = list(ex.map(lambda u: compile_unit(u[0], u[1], d), UNITS))
+    checked = []
+    for (src, _), asm in zip(UNITS, asms):
+        for sym, body in kernel_bodies(asm).items():
+            mode = int(re.match(r"_Z15orr_step_kernelILi(\d+)E", sym).group(1))
+            if mode not in (0, 2):
+                continue
+            checked.append((os.path.basename(src), sym))
+            bad = [t for t in body if t.startswith("buffer_wbl2") or t.startswith("buffer_inv")]
+            assert not bad, (os.path.basename(src), sym, bad[:4])
+    # MODE 0 in all four units (one-wave, two-wave, friction anchors, clip sets), MODE 2 in the main and the clip-set units
+    assert len(checked) == 6, checked
