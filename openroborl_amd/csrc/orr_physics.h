@@ -302,6 +302,60 @@ __device__ __forceinline__ float part_suffix_sum(float x) {
   const float b = __int_as_float(__builtin_amdgcn_update_dpp(0, v, 0x108, 0xF, 0xD, true));  // row_shl:8, not into bank 1
   return x + a + b;
 }
+// The same sums inside the sub-step loop: IN PLACE, several values per block, two instructions per value,
+//   v_add_f32_dpp x, x, x row_shl:4 bank_mask:0xb      parts (0, 1) += parts (1, 2); part 2 is the disabled bank and keeps x
+//   v_add_f32_dpp x, x, x row_shl:8 bank_mask:0xd      part 0 += part 2, which the first step left alone: (x + a) + b as above
+// (a shift from beyond the row adds 0: bound_ctrl).  The compiler cannot make this form out of part_suffix_sum: its DPP combiner folds
+// a bank-masked v_mov_b32_dpp into the consuming operation only when `old` is that operation's identity, and it knows none for a float
+// add (x + 0.0 is not x for x = -0.0), so every value cost two `v_mov 0`, two v_mov_b32_dpp and two adds.  That is also the one
+// difference: a lane of a disabled bank used to get x + 0.0f and now keeps x, which shows in the part-1 lanes alone (parts 2 and 3 still
+// add the 0 from beyond the row, part 0 has no disabled step that matters) and only where the own and the part-2 value are both -0.0f
+// (the sum was +0.0f, now -0.0f).
+// A DPP operand must not have been written by the two instructions in front of it, and the assembler inserts no wait inside an
+// `asm`: one s_nop covers the values' producers, and a value's second add sits behind the other values' adds.
+#define ORR_SUBTREE_ADD(x, shl, bank) "v_add_f32_dpp " x ", " x ", " x " row_shl:" shl " row_mask:0xf bank_mask:" bank " bound_ctrl:0\n\t"
+// The first moments h = m c are the exception: their own term is a PRODUCT, and the compiler contracts it into the first add of
+// part_suffix_sum (x + a with x = m * c is fma(m, c, a): the product is not rounded on its way into the sum, while the other lanes read
+// the rounded h).  The same value from a zeroed accumulator: t = 0;  t += shl4(h) (DPP add);  t = fma(m, c, t);  t += shl8(h) (DPP add),
+// four instructions per value instead of six.  The three `v_mov 0` in front are also the wait states between h's producer and its
+// first DPP read.  (0 + a instead of a: shows only where a and m c are both -0.0f.)
+// WITH_M (the units that do not carry the subtree mass in a register): the mass itself is summed in place in the same block, behind
+// the multiply-adds that still want the own link's.
+#define ORR_H_ADD(t, h, shl, bank) "v_add_f32_dpp " t ", " h ", " t " row_shl:" shl " row_mask:0xf bank_mask:" bank " bound_ctrl:0\n\t"
+template <bool WITH_M>
+__device__ __forceinline__ void part_suffix_sum_first_moment(float& m, const float (&c)[3], float (&h)[3]) {
+  static_assert(kRPW == 4, "a robot is one DPP row: lane = leg + 4 part, part = DPP bank");
+  float t0, t1, t2;
+  if constexpr (WITH_M) {
+    asm("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\t"
+        ORR_H_ADD("%0", "%4", "4", "0xb") ORR_H_ADD("%1", "%5", "4", "0xb") ORR_H_ADD("%2", "%6", "4", "0xb")
+        "v_fmac_f32 %0, %3, %7\n\tv_fmac_f32 %1, %3, %8\n\tv_fmac_f32 %2, %3, %9\n\t"
+        ORR_SUBTREE_ADD("%3", "4", "0xb")
+        ORR_H_ADD("%0", "%4", "8", "0xd") ORR_H_ADD("%1", "%5", "8", "0xd") ORR_H_ADD("%2", "%6", "8", "0xd")
+        ORR_SUBTREE_ADD("%3", "8", "0xd")
+        : "=&v"(t0), "=&v"(t1), "=&v"(t2), "+v"(m)
+        : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(c[0]), "v"(c[1]), "v"(c[2]));
+  } else {
+    asm("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\t"
+        ORR_H_ADD("%0", "%4", "4", "0xb") ORR_H_ADD("%1", "%5", "4", "0xb") ORR_H_ADD("%2", "%6", "4", "0xb")
+        "v_fmac_f32 %0, %3, %7\n\tv_fmac_f32 %1, %3, %8\n\tv_fmac_f32 %2, %3, %9\n\t"
+        ORR_H_ADD("%0", "%4", "8", "0xd") ORR_H_ADD("%1", "%5", "8", "0xd") ORR_H_ADD("%2", "%6", "8", "0xd")
+        : "=&v"(t0), "=&v"(t1), "=&v"(t2)
+        : "v"(m), "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(c[0]), "v"(c[1]), "v"(c[2]));
+  }
+  h[0] = t0; h[1] = t1; h[2] = t2;
+}
+#undef ORR_H_ADD
+__device__ __forceinline__ void part_suffix_sum_inplace(float (&v)[6]) {
+  static_assert(kRPW == 4, "a robot is one DPP row: lane = leg + 4 part, part = DPP bank");
+  asm("s_nop 1\n\t"
+      ORR_SUBTREE_ADD("%0", "4", "0xb") ORR_SUBTREE_ADD("%1", "4", "0xb") ORR_SUBTREE_ADD("%2", "4", "0xb")
+      ORR_SUBTREE_ADD("%3", "4", "0xb") ORR_SUBTREE_ADD("%4", "4", "0xb") ORR_SUBTREE_ADD("%5", "4", "0xb")
+      ORR_SUBTREE_ADD("%0", "8", "0xd") ORR_SUBTREE_ADD("%1", "8", "0xd") ORR_SUBTREE_ADD("%2", "8", "0xd")
+      ORR_SUBTREE_ADD("%3", "8", "0xd") ORR_SUBTREE_ADD("%4", "8", "0xd") ORR_SUBTREE_ADD("%5", "8", "0xd")
+      : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
+}
+#undef ORR_SUBTREE_ADD
 
 struct BaseFactor { Chol6Pk F; };
 __device__ static void leg_dynamics(const KParams& P, Shared& S, const LegConst& K, int lane, BaseFactor& BF) {
@@ -364,11 +418,11 @@ __device__ static void leg_dynamics(const KParams& P, Shared& S, const LegConst&
     for (int i = 0; i < 3; i++) { L.ow[i] = S.s[O(POS) + i] + d[i]; L.s[i] = so[i]; L.sv[i] = svo[i]; }
   }
   // ---- own link: spatial inertia about O and bias force f = I A + V x* (I V) ----
-  float I[6], h[3], m = K.m, f[6], pacc[6];
+  float I[6], h[3], hcom[3], m = K.m, f[6], pacc[6];   // hcom: the link's COM about O (h = m hcom), for the subtree sums of h below
   {
     float c[3];
 #pragma unroll
-    for (int i = 0; i < 3; i++) c[i] = fmaf(Rw[3 * i], K.com[0], fmaf(Rw[3 * i + 1], K.com[1], fmaf(Rw[3 * i + 2], K.com[2], d[i])));
+    for (int i = 0; i < 3; i++) hcom[i] = c[i] = fmaf(Rw[3 * i], K.com[0], fmaf(Rw[3 * i + 1], K.com[1], fmaf(Rw[3 * i + 2], K.com[2], d[i])));
     h[0] = m * c[0]; h[1] = m * c[1]; h[2] = m * c[2];
     rot_sym_full(Rw, K.Ic, I);
     // Bias force f = I A + V x* (I V) evaluated at the link's COM and shifted to O (round 4: 54 instead of ~80 instructions; the same
@@ -414,11 +468,11 @@ __device__ static void leg_dynamics(const KParams& P, Shared& S, const LegConst&
     Macc[0] = Macc[1] = Macc[2] = m; Macc[3] = Macc[4] = Macc[5] = 0.0f;
   }
   // ---- way up: composite inertia and force sum of the subtree behind the own joint (sum over the leg's later parts) ----
-#pragma unroll
-  for (int i = 0; i < 6; i++) { I[i] = part_suffix_sum(I[i]); f[i] = part_suffix_sum(f[i]); }
-#pragma unroll
-  for (int i = 0; i < 3; i++) h[i] = part_suffix_sum(h[i]);
-  m = kCarrySubtreeMass ? K.msub : part_suffix_sum(m);
+  // (Iacc / pacc above are the own link's values: copied before these sums run in place)
+  part_suffix_sum_inplace(I);
+  part_suffix_sum_inplace(f);
+  part_suffix_sum_first_moment<!kCarrySubtreeMass>(m, hcom, h);
+  if (kCarrySubtreeMass) m = K.msub;
   // own column of F and of the leg's joint-space inertia H (entries H[i][part], i <= part), own bias torque
   float Fo[6], bo;
   {
@@ -1040,7 +1094,12 @@ template <bool HAS_B>
 __device__ __forceinline__ void delassus_columns(const Shared& S, unsigned int mask, int lane, int sub, Row& A, Row& B, const ContactGeom& G,
                                                  float (&AcA)[kMaxRows], float (&AcB)[kMaxRows], float (&lam)[kMaxRows]) {
 #pragma unroll
-  for (int r = 0; r < kMaxRows; r++) { AcA[r] = 0.0f; AcB[r] = 0.0f; lam[r] = 0.0f; }
+  for (int r = 0; r < kMaxRows; r++) {
+    AcA[r] = 0.0f; AcB[r] = 0.0f;
+    // without the joint-limit bank nothing reads lam[4..15] (physics_substep's velocity update visits those rows behind a test of the same
+    // anyB): left unset, the join of the two instantiations has nothing to fill them with (it was twelve `v_mov 0` in nearly every sub-step)
+    if (HAS_B || r < 4 || r >= 16) lam[r] = 0.0f;
+  }
   // bookkeeping of one column once its entries a (this lane's bank-A row) and b (bank-B row) are known
   auto finish = [&](auto rc, float a, float b) __attribute__((always_inline)) {
     constexpr int r = decltype(rc)::value;

@@ -46,69 +46,112 @@ def classify(m):
     return "other"
 
 
-def main():
-    flags = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + sys.argv[1:]
+STEP_KERNELS = (("_Z15orr_step_kernelILi0ELi1ELb0E", "step kernel, one wave per SIMD"), ("_Z15orr_step_kernelILi0ELi2ELb0E", "step kernel, two waves per SIMD"),
+                ("_Z15orr_step_kernelILi0ELi1ELb1E", "step kernel with friction anchors (one wave per SIMD)"))
+
+
+def compile_units(extra_flags=(), only_main=False):
+    """Device assembly of the env kernels' translation units with the product's flags (+ extra_flags): one list of lines per unit
+    (main, two-wave, friction anchors)."""
+    flags = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + list(extra_flags)
     out = os.path.join(tempfile.mkdtemp(), "step.s")
     src = os.environ.get("ORR_ISA_SRC", _lib.SRC)      # another tree's orr_kernels.hip (A/B of code generation)
     subprocess.check_call([_lib.HIPCC] + flags + ["-S", "--cuda-device-only", "-o", out, src], stderr=subprocess.DEVNULL)
-    lines = open(out).read().split("\n")
+    units = [open(out).read().split("\n")]
+    if only_main:
+        return units
     src_w2 = os.path.join(os.path.dirname(src), "orr_kernels_w2.hip")
     if os.path.exists(src_w2):       # the two-waves-per-SIMD variant is its own translation unit with its own flags
-        flags_w2 = [f for f in _lib.HIPCC_FLAGS_W2 if f not in ("-shared", "-fPIC")] + sys.argv[1:]
+        flags_w2 = [f for f in _lib.HIPCC_FLAGS_W2 if f not in ("-shared", "-fPIC")] + list(extra_flags)
         subprocess.check_call([_lib.HIPCC] + flags_w2 + ["-S", "--cuda-device-only", "-o", out + "2", src_w2], stderr=subprocess.DEVNULL)
-        lines += open(out + "2").read().split("\n")
+        units.append(open(out + "2").read().split("\n"))
     src_an = os.path.join(os.path.dirname(src), "orr_kernels_anchor.hip")
     if os.path.exists(src_an):       # the friction-anchor variants: third translation unit, the main unit's flags
         subprocess.check_call([_lib.HIPCC] + flags + ["-S", "--cuda-device-only", "-o", out + "3", src_an], stderr=subprocess.DEVNULL)
-        lines += open(out + "3").read().split("\n")
+        units.append(open(out + "3").read().split("\n"))
+    return units
+
+
+def parse_kernel(lines, sym):
+    """Instructions of the kernel `sym` in an assembly listing, or None: (insts, labels, locs, under) with labels = {label: index of the
+    instruction behind it}, locs[i] = (file number, line) of the last .loc directive in front of instruction i (None without debug
+    lines) and under[i] = the last label in front of it."""
+    try:
+        start = next(i for i, l in enumerate(lines) if re.match(r"^%s.*:" % sym, l))
+    except StopIteration:
+        return None
+    end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith("s_endpgm"))
+    labels = {}
+    insts, locs, under = [], [], []
+    loc = lab = None
+    for l in lines[start:end + 1]:
+        t = l.split(";")[0].strip()
+        if not t:
+            continue
+        m = re.match(r"^(\.?[A-Za-z_0-9$]+):$", t)
+        if m:
+            labels[m.group(1)] = len(insts)
+            lab = m.group(1)
+            continue
+        if t.startswith("."):
+            m = re.match(r"^\.loc\s+(\d+)\s+(\d+)", t)
+            if m:
+                loc = (int(m.group(1)), int(m.group(2)))
+            continue
+        insts.append(t)
+        locs.append(loc)
+        under.append(lab)
+    return insts, labels, locs, under
+
+
+def substep_loop(insts, labels):
+    """(first, last) instruction of the sub-step loop = the backward branch whose body holds the most DPP instructions (the Gauss-Seidel
+    sweeps live there); the largest backward branch alone can be some other loop of the step-end / reset code"""
+    best = (0, 0, 0)
+    dpp_prefix = [0]
+    for t in insts:
+        dpp_prefix.append(dpp_prefix[-1] + ("dpp" in t.split()[0]))
+    best_key = (-1, -1)
+    for i, t in enumerate(insts):
+        m = re.match(r"^s_c?branch\S*\s+(\S+)$", t)
+        if m and m.group(1) in labels and labels[m.group(1)] < i:
+            lo = labels[m.group(1)]
+            key = (dpp_prefix[i + 1] - dpp_prefix[lo], i - lo)
+            if key > best_key:
+                best_key, best = key, (i - lo, lo, i)
+    return best[1], best[2]
+
+
+def scratch_accesses(seg):
+    return sum(1 for t in seg if t.startswith("scratch_") or t.startswith("buffer_") and "offen" in t)
+
+
+def resources(meta, sym):
+    """(LDS bytes, scratch bytes per lane, sgprs, spilled sgprs, vgprs, spilled vgprs) from the kernel's metadata, as strings, or None"""
+    m = re.search(r"\.group_segment_fixed_size:\s+(\d+)(?:(?!\.group_segment_fixed_size).)*?\.name:\s+%s.*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.sgpr_spill_count:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)" % sym, meta, re.S)
+    return m.groups() if m else None
+
+
+def main():
+    lines = [l for u in compile_units(sys.argv[1:]) for l in u]
     meta = "\n".join(lines)
     # one report per variant of the step kernel (WPE 1: one wave per SIMD, WPE 2: two; see orr_kernels.hip)
-    for sym, title in (("_Z15orr_step_kernelILi0ELi1ELb0E", "step kernel, one wave per SIMD"), ("_Z15orr_step_kernelILi0ELi2ELb0E", "step kernel, two waves per SIMD"),
-                       ("_Z15orr_step_kernelILi0ELi1ELb1E", "step kernel with friction anchors (one wave per SIMD)")):
-        try:
-            start = next(i for i, l in enumerate(lines) if re.match(r"^%s.*:" % sym, l))
-        except StopIteration:
+    for sym, title in STEP_KERNELS:
+        k = parse_kernel(lines, sym)
+        if k is None:
             continue
-        end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith("s_endpgm"))
-        body = lines[start:end + 1]
-        labels = {}
-        insts = []
-        for l in body:
-            t = l.split(";")[0].strip()
-            if not t:
-                continue
-            m = re.match(r"^(\.?[A-Za-z_0-9$]+):$", t)
-            if m:
-                labels[m.group(1)] = len(insts)
-                continue
-            if t.startswith("."):
-                continue
-            insts.append(t)
-        # the sub-step loop = the backward branch whose body holds the most DPP instructions (the Gauss-Seidel sweeps live there); the
-        # largest backward branch alone can be some other loop of the step-end / reset code
-        best = (0, 0, 0)
-        dpp_prefix = [0]
-        for t in insts:
-            dpp_prefix.append(dpp_prefix[-1] + ("dpp" in t.split()[0]))
-        best_key = (-1, -1)
-        for i, t in enumerate(insts):
-            m = re.match(r"^s_c?branch\S*\s+(\S+)$", t)
-            if m and m.group(1) in labels and labels[m.group(1)] < i:
-                lo = labels[m.group(1)]
-                key = (dpp_prefix[i + 1] - dpp_prefix[lo], i - lo)
-                if key > best_key:
-                    best_key, best = key, (i - lo, lo, i)
+        insts, labels = k[0], k[1]
+        lo, hi = substep_loop(insts, labels)
         print("==== %s" % title)
-        for name, seg in (("whole kernel", insts), ("largest loop (sub-steps)", insts[best[1]:best[2] + 1])):
+        for name, seg in (("whole kernel", insts), ("largest loop (sub-steps)", insts[lo:hi + 1])):
             c = collections.Counter(classify(t.split()[0]) for t in seg)
             tot = sum(c.values())
-            scratch = sum(1 for t in seg if t.startswith("scratch_") or t.startswith("buffer_") and "offen" in t)
-            print("%s: %d instructions (scratch accesses: %d)" % (name, tot, scratch))
+            print("%s: %d instructions (scratch accesses: %d)" % (name, tot, scratch_accesses(seg)))
             for k, v in c.most_common():
                 print("   %-18s %6d  %5.1f%%" % (k, v, 100.0 * v / tot))
-        m = re.search(r"\.group_segment_fixed_size:\s+(\d+)(?:(?!\.group_segment_fixed_size).)*?\.name:\s+%s.*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.sgpr_spill_count:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)" % sym, meta, re.S)
-        if m:
-            print(" LDS %s B, scratch %s B per lane, sgpr %s (spilled %s), vgpr %s (spilled %s)" % m.groups())
+        r = resources(meta, sym)
+        if r:
+            print(" LDS %s B, scratch %s B per lane, sgpr %s (spilled %s), vgpr %s (spilled %s)" % r)
 
 
 if __name__ == "__main__":
