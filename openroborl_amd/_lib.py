@@ -11,16 +11,16 @@ import subprocess
 from . import _abi
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(PKG_DIR, "csrc", "orr_kernels.hip")
-SRC_ANCHOR = os.path.join(PKG_DIR, "csrc", "orr_kernels_anchor.hip")   # the friction-anchor variants of the step kernel (ABI v5): their own translation unit
-SRC_MULTICLIP = os.path.join(PKG_DIR, "csrc", "orr_kernels_multiclip.hip")   # the clip-set variants of the step and reset kernels: their own unit
-SRC_W2 = os.path.join(PKG_DIR, "csrc", "orr_kernels_w2.hip")      # the two-waves-per-SIMD step kernel: its own translation unit + flags
-SRC_POLICY = os.path.join(PKG_DIR, "csrc", "orr_policy.hip")
-SRC_LEARNER = os.path.join(PKG_DIR, "csrc", "orr_learner.hip")    # the non-GEMM part of the PPO update (include/openroborl_learner.h)
-DEPS = [SRC, SRC_W2, SRC_ANCHOR, SRC_MULTICLIP, SRC_POLICY, SRC_LEARNER] + [os.path.join(PKG_DIR, "csrc", h) for h in ("orr_device.h", "orr_robot_io.h", "orr_physics.h", "orr_task.h")] + [
-        os.path.join(os.path.dirname(PKG_DIR), "include", "openroborl_hip.h"),
-        os.path.join(os.path.dirname(PKG_DIR), "include", "openroborl_policy.h"),
-        os.path.join(os.path.dirname(PKG_DIR), "include", "openroborl_learner.h")]
+CSRC = os.path.join(PKG_DIR, "csrc")
+SRC = os.path.join(CSRC, "orr_kernels.hip")                      # the default env kernels + the C-ABI
+SRC_W2 = os.path.join(CSRC, "orr_kernels_w2.hip")                # the two-waves-per-SIMD step kernel: its own translation unit + flags
+SRC_ANCHOR = os.path.join(CSRC, "orr_kernels_anchor.hip")        # the friction-anchor variants of the step kernel (ABI v5): their own unit
+SRC_MULTICLIP = os.path.join(CSRC, "orr_kernels_multiclip.hip")  # the clip-set variants of the step and reset kernels: their own unit
+SRC_POLICY = os.path.join(CSRC, "orr_policy.hip")
+SRC_LEARNER = os.path.join(CSRC, "orr_learner.hip")              # the non-GEMM part of the PPO update (include/openroborl_learner.h)
+# what the library is built from = what the stale-library check hashes: every source and header under csrc/ + the public headers
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [
+    os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("openroborl_hip.h", "openroborl_policy.h", "openroborl_learner.h")]
 LIB_PATH = os.path.join(PKG_DIR, "libopenroborl_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -47,6 +47,19 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O2", "-fPIC", "-shared", "-std=c++17",
 # is within the noise (0.2987), -Oz costs 1 %.  (What -Os changes here is the register allocation's luck, not the amount of code: every
 # function of the kernel is forced inline and every loop unrolled by pragma.)
 HIPCC_FLAGS_W2 = ["-Os" if f == "-O2" else ("-amdgpu-sched-strategy=iterative-maxocc" if "amdgpu-sched-strategy" in f else f) for f in HIPCC_FLAGS]
+
+# the policy forward pass (matrix cores) and the learner kernels: the compiler's default scheduling
+HIPCC_FLAGS_PLAIN = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"]
+
+# The translation units of the library: (name, source, flags, carries the source hash?).  build(), the tools that read the env kernels'
+# assembly (tools/isa_stats.py) and the compile-only tests all take the units from here.
+UNITS = [("env", SRC, HIPCC_FLAGS, True),
+         ("w2", SRC_W2, HIPCC_FLAGS_W2, False),
+         ("anchor", SRC_ANCHOR, HIPCC_FLAGS, False),          # optional physics feature: the main unit's flags, its own unit
+         ("multiclip", SRC_MULTICLIP, HIPCC_FLAGS, False),    # likewise
+         ("policy", SRC_POLICY, HIPCC_FLAGS_PLAIN, False),
+         ("learner", SRC_LEARNER, HIPCC_FLAGS_PLAIN, False)]
+ENV_UNITS = UNITS[:4]      # the units of the env kernels (csrc/orr_env_kernels.h): the ones that tuning defines and extra_flags reach
 
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
@@ -128,27 +141,19 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
         try:
             if not dev_build and not force and not needs_build():
                 return LIB_PATH              # another rank built it while this one waited for the lock
-            flags = [f for f in HIPCC_FLAGS if f != "-shared"] + ["-c", '-DORR_SOURCE_HASH="%s"' % source_hash(extra_flags)]
-            flags += tuning_defines() + list(extra_flags)
-            flags_w2 = [f for f in HIPCC_FLAGS_W2 if f != "-shared"] + ["-c"] + tuning_defines() + list(extra_flags)
             tag = ".%d" % os.getpid()
-            obj_env = os.path.join(PKG_DIR, "csrc", "orr_kernels%s.o" % tag)
-            obj_w2 = os.path.join(PKG_DIR, "csrc", "orr_kernels_w2%s.o" % tag)
-            obj_an = os.path.join(PKG_DIR, "csrc", "orr_kernels_anchor%s.o" % tag)
-            obj_mc = os.path.join(PKG_DIR, "csrc", "orr_kernels_multiclip%s.o" % tag)
-            obj_pol = os.path.join(PKG_DIR, "csrc", "orr_policy%s.o" % tag)
-            obj_lrn = os.path.join(PKG_DIR, "csrc", "orr_learner%s.o" % tag)
             tmp_so = out_path + tag + ".tmp"
-            cmds = [[HIPCC] + flags + ["-o", obj_env, SRC],
-                    [HIPCC] + flags_w2 + ["-o", obj_w2, SRC_W2],
-                    # the friction-anchor variants of the step kernel (optional physics feature): the main unit's flags, their own unit
-                    [HIPCC] + [f for f in flags if not f.startswith("-DORR_SOURCE_HASH")] + ["-o", obj_an, SRC_ANCHOR],
-                    # the clip-set variants of the step and reset kernels (orr_set_clip_set): the main unit's flags, their own unit
-                    [HIPCC] + [f for f in flags if not f.startswith("-DORR_SOURCE_HASH")] + ["-o", obj_mc, SRC_MULTICLIP],
-                    # the policy forward pass (matrix cores) is its own translation unit with the compiler's default scheduling
-                    [HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", "-o", obj_pol, SRC_POLICY],
-                    [HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", "-o", obj_lrn, SRC_LEARNER],
-                    [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp_so, obj_env, obj_w2, obj_an, obj_mc, obj_pol, obj_lrn]]
+            objs, cmds = [], []
+            for unit in UNITS:
+                name, src, flags, hashed = unit
+                flags = [f for f in flags if f != "-shared"] + ["-c"]
+                if hashed:
+                    flags.append('-DORR_SOURCE_HASH="%s"' % source_hash(extra_flags))
+                if unit in ENV_UNITS:
+                    flags += tuning_defines() + list(extra_flags)
+                objs.append(os.path.splitext(src)[0] + tag + ".o")
+                cmds.append([HIPCC] + flags + ["-o", objs[-1], src])
+            cmds.append([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp_so] + objs)
             try:
                 procs = []
                 for cmd in cmds[:-1]:           # the compiles are independent: run them side by side
@@ -163,7 +168,7 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
                 subprocess.check_call(cmds[-1])
                 os.replace(tmp_so, out_path)
             finally:
-                for o in (obj_env, obj_w2, obj_an, obj_mc, obj_pol, obj_lrn, tmp_so):
+                for o in objs + [tmp_so]:
                     if os.path.exists(o):
                         os.remove(o)
         finally:

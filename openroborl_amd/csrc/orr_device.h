@@ -223,7 +223,7 @@ struct alignas(16) Shared {
   alignas(16) float co[20];    // control (latency-delayed) observation
   alignas(16) PhaseBuf ph;
 #ifdef ORR_PHASE_TIMERS
-  long long pt_acc[kPhaseSlots], pt_last, pt_t0, pt_r0;  // development aid, see PT() in orr_kernels.hip
+  long long pt_acc[kPhaseSlots], pt_last, pt_t0, pt_r0;  // development aid, see PT() in orr_env_kernels.h
 #endif
 };
 
@@ -345,7 +345,7 @@ __device__ __forceinline__ void joint_sincos(float a, float* sn, float* cs) {
 // Cephes atanf kernel on [0, tan(pi/8)] (t -> (t - 1) / (t + 1) above it); absolute error < 3e-7 (checked against float64 on 2 M
 // random arguments).
 // NaN arguments come out FINITE (fmax / fmin and the selects drop NaNs): non-finite numbers
-// are detected in ONE place, the |state| < 1e30 sweep + reward check at the end of the step (ORR_DONE_NAN, orr_kernels.hip), never through
+// are detected in ONE place, the |state| < 1e30 sweep + reward check at the end of the step (ORR_DONE_NAN, orr_env_kernels.h), never through
 // these functions (tests/test_gpu_parity.py::test_non_finite_state_is_caught_by_the_state_guard).
 __device__ __forceinline__ float atan2_bf(float y, float x) {
   const float ax = fabsf(x), ay = fabsf(y);

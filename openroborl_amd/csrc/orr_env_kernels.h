@@ -1,0 +1,583 @@
+// orr_env_kernels.h -- the two env kernels (orr_reset_kernel, orr_step_kernel) and their launchers, as templates.
+//
+// Included by the four translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
+// four: DESIGN.md section 3).  orr_kernels.hip: the default kernels + the C-ABI, instruction-level-parallelism scheduler (one wave per
+// SIMD, ~300 registers, nothing to hide latency but the wave's own independent instructions).  orr_kernels_w2.hip: the
+// two-waves-per-SIMD step kernel, its own flags.  orr_kernels_anchor.hip: the friction-anchor variants.  orr_kernels_multiclip.hip:
+// the clip-set variants.  An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
+// per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
+// template` only (bottom of this file).
+// Device code by phase: orr_device.h (LDS image, math, DPP helpers), orr_robot_io.h (record load / store, latency ring),
+// orr_physics.h (one physics sub-step), orr_task.h (motion clips, reward, observation, reset).
+// A unit may set two properties before the include: ORR_TU_STEP_W2 + ORR_PARITY (orr_kernels_w2.hip; orr_physics.h, orr_device.h)
+// and ORR_TU_MAIN (orr_kernels.hip: the unit that holds the development timers' and counters' globals).
+#pragma once
+#ifndef ORR_TU_MAIN
+#undef ORR_PHASE_TIMERS      // the development timers live in the main translation unit only
+#endif
+#include <hip/hip_runtime.h>
+#include <type_traits>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+// The constraint rows need A0^-1 (Jb - T_L jl): every row lane solves with the Cholesky factor of A0, which stays in registers (15 entries + 6 reciprocal pivots, Chol6Pk) from
+// the leg dynamics on (-54 instructions per sub-step there: no unit-column solve, no A0^-1 through LDS; +15 per bank in the row
+// response).  4096 robots 0.2338 -> 0.2295 ms; the two-wave unit (256 registers, spilling) is neutral (8192 robots 0.3265 vs 0.3255 ms)
+// and takes it too, so that both variants of the kernel keep giving the same bits.
+#include "orr_device.h"
+
+// Development aid (tools/phase_cycles.py): -DORR_PHASE_TIMERS makes lane 0 of one wave accumulate shader-clock cycles
+// per phase (Shared::pt_acc) and add them to g_phase_cycles at the end of the launch.
+#ifdef ORR_PHASE_TIMERS
+__device__ long long g_phase_cycles[orr::kPhaseSlots];   // 0..15: phases of the step, 16..23: stages of reset_robot, 24..: finer marks inside the reset
+__device__ long long g_wave_phases[2048 * 40];   // per wave of the last launch: its own phase totals (tools/wave_phases.py)
+__device__ long long g_wave_timeline[4 * 2048];   // per wave of the last launch: realtime start, realtime end, shader cycles, reset flag
+#define PT_INIT() do { if (threadIdx.x == 0) { S.pt_t0 = clock64(); S.pt_r0 = wall_clock64(); } if (threadIdx.x == 0) { for (int i_ = 0; i_ < orr::kPhaseSlots; i_++) S.pt_acc[i_] = 0; S.pt_last = clock64(); } } while (0)
+#define PT(k) do { if (threadIdx.x == 0) { const long long t_ = clock64(); S.pt_acc[k] += t_ - S.pt_last; S.pt_last = clock64(); } } while (0)
+#define PT_TIMELINE(flag) do { if (threadIdx.x == 0 && blockIdx.x < 2048) { g_wave_timeline[4 * blockIdx.x] = S.pt_r0; g_wave_timeline[4 * blockIdx.x + 1] = wall_clock64(); g_wave_timeline[4 * blockIdx.x + 2] = clock64() - S.pt_t0; g_wave_timeline[4 * blockIdx.x + 3] = ((flag) & 0xFF) | ((long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8) | ((long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 40); } } while (0)   /* bits 8..39: HW_REG_HW_ID (wave, simd, cu, sh, se), 40..43: HW_REG_XCC_ID */
+#define PT_FLUSH() do { if (threadIdx.x == 0 && blockIdx.x == gridDim.x / 2) for (int i_ = 0; i_ < orr::kPhaseSlots; i_++) atomicAdd((unsigned long long*)&g_phase_cycles[i_], (unsigned long long)S.pt_acc[i_]); \
+                        if (threadIdx.x == 0 && blockIdx.x < 2048) for (int i_ = 0; i_ < orr::kPhaseSlots; i_++) g_wave_phases[blockIdx.x * 40 + i_] = S.pt_acc[i_]; } while (0)
+#else
+#define PT_INIT()
+#define PT(k)
+#define PT_FLUSH()
+#define PT_TIMELINE(flag)
+#endif
+
+// Development aid (tools/wave_times.py): -DORR_WAVE_TIMELINE makes every wave of the step kernel - BOTH variants, product code otherwise -
+// record when it started and ended (100 MHz realtime counter), its shader cycles and the hardware slot it ran on (nothing else is
+// instrumented: two s_memrealtime / s_memtime pairs and one 32-byte store per wave)
+#ifdef ORR_WAVE_TIMELINE
+#define WT_INIT() const long long wt_r0 = wall_clock64(), wt_c0 = clock64()
+#define WT_STORE(flag) do { if ((threadIdx.x & 63u) == 0 && P.wave_times) { long long* w_ = P.wave_times + 4 * (size_t)wave_id; w_[0] = wt_r0; w_[1] = wall_clock64(); w_[2] = clock64() - wt_c0; \
+    w_[3] = ((flag) & 0xFF) | ((long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8) | ((long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 40); } } while (0)
+#else
+#define WT_INIT()
+#define WT_STORE(flag)
+#endif
+
+// Development aid (tools/dual_contact.py): -DORR_COUNT_DUAL_CONTACT counts, per leg and sub-step, how often the toe sphere and the shank
+// sphere of a lower leg are within the contact margin / penetrating at the same time (the engine makes ONE contact point per leg, Bullet
+// one per touching shape: DESIGN.md section 9).  One-wave kernel only.
+#if defined(ORR_COUNT_DUAL_CONTACT) && defined(ORR_TU_MAIN)
+__device__ unsigned long long g_dual_contact[8];
+// (called from row_setup_bank_a in every lane of the wave: the first ACTIVE lane adds the wave's count)
+#define ORR_DUAL_COUNT(k, cond) do { const unsigned long long b_ = __ballot(cond), act_ = __ballot(1); \
+    if (b_ && (int)(threadIdx.x & 63u) == __ffsll((long long)act_) - 1) atomicAdd(&g_dual_contact[k], (unsigned long long)__popcll(b_)); } while (0)
+#else
+#define ORR_DUAL_COUNT(k, cond)
+#endif
+
+using namespace orr;
+
+#define O(name) ORR_OFF_##name
+
+#include "orr_robot_io.h"
+#include "orr_physics.h"
+#include "orr_task.h"
+
+// ================================================================================================
+// kernels
+// ================================================================================================
+// lane group bookkeeping shared by the kernels: `sub` = which robot of this wave, `lane` = lane within the robot
+// WPB = wavefronts per workgroup (each wave is an independent quad of robots; nothing is shared between the waves of a workgroup)
+#define ORR_PROLOGUE() ORR_PROLOGUE_W(1)
+#define ORR_PROLOGUE_W(WPB)                                                              \
+  __shared__ Shared Sarr[kRPW * (WPB)];                                                  \
+  const int wtid = (WPB) > 1 ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;              \
+  const int wave_in_wg = (WPB) > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0; \
+  const int wave_id = (int)blockIdx.x * (WPB) + wave_in_wg;                              \
+  const int sub = wtid / kLanes, lane = wtid % kLanes;                                   \
+  Shared& S = Sarr[wave_in_wg * kRPW + sub];                                             \
+  float* obs = S.ph.end.obs;                                                             \
+  const int robot_raw = wave_id * kRPW + sub;                                            \
+  const bool in_range = robot_raw < P.cfg.num_robots;                                    \
+  const int robot = in_range ? robot_raw : 0; /* a padding lane group shadows robot 0 and never stores */ \
+  float* rec = P.state + (size_t)robot * ORR_STATE_STRIDE
+
+// CLIPS: the multi-clip variant (orr_kernels_multiclip.hip): every reset draws the robot's clip from its type's clip set
+template <bool CLIPS = false>
+__global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t* mask, float* obs_out, const float* uniforms) {
+  ORR_PROLOGUE();
+  const bool valid = in_range && !(mask && !mask[robot]);
+  load_robot(P, rec, S, lane);
+  const long long total = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
+  const ResetConst RC = load_reset_const(P, S, lane);
+  reset_robot<CLIPS>(P, rec, S, lane, valid, total, obs, RC, uniforms ? uniforms + (size_t)robot * 28 : nullptr);
+  WSYNC();
+  store_robot(rec, S, lane, valid);
+  // a new episode: no cached contact points (ANCHOR, ANCHOR_VALID: 28 words behind the ring).  Unconditional: friction anchors may be switched
+  // on (orr_set_model) after this reset, and a caller-bound record need not have been zeroed
+  if (valid)
+    for (int i = lane; i < ORR_OFFEND_ANCHOR_VALID - ORR_OFF_ANCHOR + 1; i += kLanes) rec[O(ANCHOR) + i] = 0.0f;
+  if (obs_out && valid)
+    for (int i = lane; i < ORR_OBS_DIM; i += kLanes) obs_out[(size_t)robot * ORR_OBS_DIM + i] = obs[i];
+}
+
+// mode 0: full env step.  mode 1 (debug / parity of row C): nsub physics sub-steps with the given
+// motor torques (actions = torques), no robot or task logic.  mode 2 (parity of everything BUT row C): a full env step in
+// which the physics sub-step is replaced by the recorded states of ReplayArgs, the end-effector reward reads recorded link
+// positions and the fall flag is given -- the device-side counterpart of the oracle's replay mode, fed with the fixtures that the
+// reference's own Python produced (tests/test_gpu_golden_task.py).
+// WPE = waves per SIMD the kernel is compiled for.  WPE 1: up to 512 VGPRs (~300 used), one wave on each of the 1024 SIMDs = 4096 robots
+// resident at once: the best a batch of <= 4096 robots can do.  WPE 2 (<= 256 VGPRs, 28 of them spilled, one scratch access inside the sub-step loop; LDS 19.3 KB per wave, so
+// eight waves fit a CU): for larger batches.  A lone wave issues one vector instruction per ~5 cycles, the SIMD can take one per 2:
+// two co-resident waves of this kernel take 1.12x as long as one alone (tools/wave_pairing.py), i.e. 1.8x the throughput per SIMD,
+// where the WPE-1 kernel would run the second thousand waves after the first.  orr_step picks the variant from the batch size and the
+// device's CU count (ORR_STEP_WAVES_PER_EU = 1 | 2 overrides, for measurements).
+// (min, max) waves per SIMD are pinned to the same value: with a higher maximum this LLVM's iterative-ilp scheduler tries
+// occupancy-improving reschedules once the kernel fits 256 VGPRs and then crashes in the register allocator.
+#ifndef ORR_WAVES_PER_EU
+#define ORR_WAVES_PER_EU 1   // development builds (-DORR_WAVES_PER_EU=2) force every instantiation to that occupancy
+#endif
+#ifndef ORR_WPB
+#define ORR_WPB 1            // wavefronts per workgroup of the one-wave-per-SIMD env step (tuning experiments: 2, 4)
+#endif
+template <int MODE, int WPE>
+constexpr int step_wpb() { return MODE == 0 && WPE == 1 ? ORR_WPB : 1; }
+// ANCHOR (ABI v5): the variant for robot types with orr_model::friction_anchor - Bullet's cached toe contact points (orr_physics.h:
+// AnchorState).  Same source; its own instantiations (one wave per SIMD whatever the batch size: an optional physics feature, not the
+// measured path), so that the default kernels carry nothing of it.
+// CLIPS: the multi-clip variant (orr_kernels_multiclip.hip, one wave per SIMD whatever the batch size): the auto-reset draws the new
+// episode's clip from the robot type's clip set (reset_robot<true>), the episode log also records the clip of the ending episode, and
+// a robot whose motion time has reached the record's CLIP_CHANGE_TIME switches to a newly drawn clip mid-episode (orr_set_clip_switch)
+template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false>
+__global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
+                                                      uint8_t* done_out, int nsub, ReplayArgs RP) {
+  ORR_PROLOGUE_W((step_wpb<MODE, WPE>()));
+  const bool valid = in_range;
+  const orr_config& c = P.cfg;
+  PT_INIT();
+  WT_INIT();
+  // curriculum counter as of the start of the launch (the last wave of the previous launch folded that launch's episodes in):
+  // read here, far ahead of its only use (the time limit of an episode that starts in this launch)
+  const long long total_snapshot = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
+  load_robot(P, rec, S, lane);
+  // CLIPS: the motion time of the next clip change (behind the ring, never staged): read at the start, first used after the sub-steps
+  float clip_change = 0.0f;
+  if constexpr (CLIPS) clip_change = rec[O(CLIP_CHANGE_TIME)];
+  {
+    // Non-finite guard, entry half: a NaN in the INCOMING rigid state (POS..QD) does not survive the step - the velocity clamp (+-100,
+    // v_med3) and the branch-free inverse trigonometric functions turn NaNs into finite numbers - so it is recorded here, in a spare
+    // word of the LDS image behind the state head (never stored), and ORed into the exit half of the guard (ORR_DONE_NAN below).
+    static_assert(kHead > ORR_OFF_RING, "spare LDS word behind the state head (the head = everything in front of the ring)");
+    bool bad_in = false;
+    for (int i = lane; i < 37; i += kLanes) bad_in = bad_in || !(fabsf(S.s[O(POS) + i]) < 1e30f);
+    const bool any_bad = ((__ballot(bad_in) >> (sub * kLanes)) & ((1ull << (kLanes - 1)) * 2ull - 1ull)) != 0ull;
+    if (lane == 0) S.s[kHead - 1] = any_bad ? 1.0f : 0.0f;
+  }
+  // impulse-response table: stale rows are multiplied by zero impulses, so they only have to be finite
+  for (int i = lane; i < kMaxRows * kWStride; i += kLanes) (&S.ph.sub.W[0][0])[i] = 0.0f;
+  WSYNC();
+  LegConst K;
+  load_leg_const(P, S, lane, K);
+  {
+    float rel[4], Rb[9];
+    base_rotation(S, lane, rel, Rb);  // Shared::Rb for the first sub-step; the ring push keeps it current afterwards
+  }
+  // friction anchors (ANCHOR variant only): the cached contact point of the lane's leg, from the record's words behind the ring
+  AnchorState AS = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};
+  bool anchor_robot = false;
+  const int aleg = lane < 4 ? lane : (lane < 8 ? lane - 4 : (lane - 8) >> 1);   // leg of the lane's bank-A row (knee, normal, friction)
+  if constexpr (ANCHOR) {
+    static_assert(kLanes == 16, "ANCHOR: aleg indexes the record's four cached points by the 16-lane row layout");
+    anchor_robot = model_cold(P, geti(S, O(ROBOT_TYPE)))->friction_anchor != 0;
+    const float* an = rec + O(ANCHOR) + 6 * aleg;
+    AS.la[0] = an[0]; AS.la[1] = an[1]; AS.la[2] = an[2]; AS.wb[0] = an[3]; AS.wb[1] = an[4]; AS.wb[2] = an[5];
+    AS.valid = anchor_robot ? __float_as_int(rec[O(ANCHOR_VALID) + aleg]) : 0;
+  }
+  auto store_anchor = [&]() __attribute__((always_inline)) {      // the normal-row lanes (4..7) own the record's words
+    if constexpr (ANCHOR) {
+      if (valid && lane >= 4 && lane < 8) {
+        float* an = rec + O(ANCHOR) + 6 * aleg;
+        an[0] = AS.la[0]; an[1] = AS.la[1]; an[2] = AS.la[2]; an[3] = AS.wb[0]; an[4] = AS.wb[1]; an[5] = AS.wb[2];
+        rec[O(ANCHOR_VALID) + aleg] = __int_as_float(AS.valid);
+      }
+    }
+  };
+  PT(0);
+
+  if (MODE == 1) {
+    if (lane < 12) {
+      const ColdPtr mc = model_cold(P, geti(S, O(ROBOT_TYPE)));
+      const int j = mc->joint_of_motor[lane];
+      S.tau[j] = mc->tau_sign_motor[lane] * actions[(size_t)robot * 12 + lane];
+    }
+    WSYNC();
+    int fall = 0;
+    OwnCoord X;
+    load_own_coord(S, lane, X);
+    int limit_idle = 0;
+    for (int s = 0; s < nsub; s++) {
+      fall = physics_substep<ANCHOR>(P, S, K, lane, sub, true, X, limit_idle, ANCHOR ? &AS : nullptr, anchor_robot);
+      float rel[4], Rb[9];
+      base_rotation(S, lane, rel, Rb);
+      WSYNC();
+    }
+    if (valid && lane == 0 && done_out) done_out[robot] = (uint8_t)fall;
+    store_robot(rec, S, lane, valid);
+    store_anchor();
+    return;
+  }
+
+  // per-motor constants of the PD loop (lane = motor; lanes 12..15 repeat motor 0), from the cold model table into registers: issued
+  // here, first used after the control observation's ring reads
+  const int ml = lane < 12 ? lane : 0;
+  const ColdPtr mc = model_cold(P, geti(S, O(ROBOT_TYPE)));
+  const int mj = mc->joint_of_motor[ml];
+  const float m_off = mc->motor_offset[ml], m_dir = mc->motor_dir[ml], m_kp = mc->kp[ml], m_kd = mc->kd[ml];
+  const float m_tsign = mc->tau_sign_motor[ml], m_init = mc->init_motor_angles[ml];
+  // ---- set_act (minitaur.py:280-285): offset, last action, Butterworth filter ----
+  ctrl_obs(P, rec, S, lane);
+  // Non-finite guard, action half: the +-0.2 rad clip of the motor command (fmin / fmax) would silently DROP a NaN action while the
+  // last-action sensor and the filter history keep it.  A non-finite action is recorded like a non-finite incoming state (ORR_DONE_NAN
+  // at the end of the step) and replaced by 0, so that nothing non-finite enters the record.
+  float act_in = actions[(size_t)robot * 12 + ml];
+  {
+    const bool bad_act = !(fabsf(act_in) < 1e30f);
+    if (bad_act) act_in = 0.0f;
+    const bool any_bad = ((__ballot(bad_act) >> (sub * kLanes)) & ((1ull << (kLanes - 1)) * 2ull - 1ull)) != 0ull;
+    if (lane == 0 && any_bad) S.s[kHead - 1] = 1.0f;
+  }
+  if (lane < 12) {
+    const float act = act_in + m_init;
+    S.s[O(LAST_ACTION) + lane] = act;
+    float x1 = S.s[O(XHIST) + lane], x2 = S.s[O(XHIST) + 12 + lane], y1 = S.s[O(YHIST) + lane], y2 = S.s[O(YHIST) + 12 + lane];
+    if (geti(S, O(STATE_ACTION_COUNTER)) == 0) {  // _filter (minitaur.py:1169-1178): init_history(current delayed angles)
+      const float d = map_pi(S.co[lane]);
+      x1 = x2 = y1 = y2 = d;
+    }
+    const float y = act * P.fb[0] + (x1 * P.fb[1] + x2 * P.fb[2]) - (y1 * P.fa[1] + y2 * P.fa[2]);  // action_filter.py:111-120
+    S.s[O(XHIST) + 12 + lane] = x1; S.s[O(XHIST) + lane] = act;
+    S.s[O(YHIST) + 12 + lane] = y1; S.s[O(YHIST) + lane] = y;
+    S.s[O(ACTION) + lane] = y;
+  }
+  WSYNC();
+  PT(1);
+  int fall = 0;
+  const float inv_repeat = 1.0f / (float)c.action_repeat;
+  const RingLatency rlat = ring_latency(P, S);
+  // the step's filtered target and the motor gain, in registers over the sub-steps (lane = motor)
+  const float m_gain = m_tsign * S.s[O(STRENGTH) + ml];
+  const float m_target = S.s[O(ACTION) + ml], m_prev = S.s[O(FILTER_ACTION) + ml];
+  const bool m_has_prev = geti(S, O(FILTER_VALID)) != 0;
+  int action_counter = geti(S, O(STATE_ACTION_COUNTER));
+  RingCursor ring = {geti(S, O(RING_HEAD)), geti(S, O(RING_LEN))};
+  OwnCoord X;
+  load_own_coord(S, lane, X);
+  int limit_idle = 0;      // see physics_substep
+  // Two waves per SIMD: VALU issue is arbitrated by priority, then AGE - the older wave of a SIMD runs nearly unimpeded, the younger on
+  // the leftover slots, and when the older one has finished the younger runs on alone at a lone wave's pace (half the SIMD idle).  The
+  // two waves of a SIMD come from consecutive dispatch rounds (workgroup b: round b / #SIMDs), so raising the priority of the even rounds
+  // in even sub-steps and of the odd rounds in odd sub-steps lets them take turns at being the favoured one and finish together.
+  // 8192 robots: 0.349 -> 0.331 ms (-5.3 %, round 3; turns of 2 or 4 sub-steps or a second flip in the middle of a sub-step were no
+  // better then: 0.332 / 0.332 / 0.335).  Round 4, final code: turns of FOUR sub-steps 0.3015 -> 0.2991 ms (2: 0.2995, 8 / 16: 0.3032 /
+  // 0.3027; without the alternation 0.317; profiles/r04_ab25..28_8192.log).
+  const int prio_phase = WPE == 2 ? (int)(((unsigned)wave_id / (unsigned)(P.simds > 0 ? P.simds : 1)) & 1u) : 0;
+  // Taking turns pairs the dispatch rounds (0, 1), (2, 3) ...: with an ODD number of rounds the last one has no partner of its own, and the
+  // plain age order - the oldest wave of a SIMD runs at nearly a lone wave's pace, the next one moves up when it ends - is the better
+  // pipeline (12288 robots = 3 rounds: 0.4925 -> 0.4693 ms without the turns; 16384 / 32768 robots = 4 / 8 rounds: 0.5767 / 1.103 ms with
+  // them against 0.5847 / 1.109 without; profiles/r04_ab34_large.log)
+  const bool prio_turns = WPE == 2 && ((((unsigned)gridDim.x * (unsigned)step_wpb<MODE, WPE>() + (unsigned)(P.simds > 0 ? P.simds : 1) - 1u) /
+                                        (unsigned)(P.simds > 0 ? P.simds : 1)) & 1u) == 0u;
+  // What the PD law of a sub-step reads - the delayed angle of the lane's motor (control observation), the joint's true angle and rate -
+  // is produced at the END of the previous sub-step: the control-observation word by this very lane, angle and rate by the integration
+  // (read from LDS there anyway, for the ring entry).  Carried over in registers, the top of the loop has no LDS round
+  // trip of its own: a lone wave has nothing to overlap one with there.  Same values, bit for bit.  4096 robots 0.2235 -> 0.2205 ms.
+  // The two-wave build lost 1 % with it when it was introduced (8192 robots 0.3130 -> 0.3160 ms: three more registers across the sub-step)
+  // and takes it since the end of round 4: a wave pair runs 1.33 x the LONE time of its build whatever the scheduling (DESIGN.md section
+  // 10), and on the final code the carry is worth 0.3014 -> 0.2991 ms (profiles/r04_ab39_8192.log).  Measured and NOT kept in the one-wave build:
+  // carrying the base rotation the same way (nine words that leg_dynamics reads back from LDS: 0.2206, neutral), and issuing the loads
+  // of the leg dynamics' first reads (base rotation / velocity, own joint angle, the leg's joint rates: 19 registers) in front of the
+  // PD law (0.2208 -> 0.2223: worse).
+  float co_own = S.co[ml], qm_c = (S.s[O(Q) + mj] - m_off) * m_dir, qdm_c = S.s[O(QD) + mj] * m_dir;
+  for (int sstep = 0; sstep < c.action_repeat; sstep++) {
+    // priority turns of the two-wave variant (measured: profiles/r04_ab25..30_8192.log): a wave is favoured for kPrioTurn sub-steps at a time; the turns
+    // start kPrioOffset sub-steps early, i.e. the younger wave of a SIMD leads with a turn of three and has the last two sub-steps (8192 robots
+    // 0.3012 -> 0.2998 ms; offsets 2 / 3 / 4 (= the older wave leads): 0.3030 / 0.3042 / 0.3046; equal priority for the last 4 / 8 sub-steps:
+    // 0.3026 / 0.3014, not kept).  kPrioEqualFrom: equal priority from that sub-step on; 1000 = never (action_repeat is 33), the comparison
+    // stays so that the unit's code is the measured one
+    constexpr int kPrioTurn = 4, kPrioHi = 1, kPrioOffset = 1, kPrioEqualFrom = 1000;
+    if (WPE == 2 && prio_turns) { if (sstep < kPrioEqualFrom && ((((sstep + kPrioOffset) / kPrioTurn) ^ prio_phase) & 1)) __builtin_amdgcn_s_setprio(kPrioHi); else __builtin_amdgcn_s_setprio(0); }
+    {  // every lane (no divergent `if`: it would cost more than it skips); lanes 12..15 repeat motor 0 and store into dump slots
+      const float lerp = (float)(sstep + 1) * inv_repeat;  // process_action (minitaur.py:438-460)
+      const float cur = map_pi(co_own);
+      const float prev = m_has_prev ? m_prev : cur;
+      float cmd = prev + lerp * (m_target - prev);
+      cmd = fminf(fmaxf(cmd, cur - c.max_angle_change), cur + c.max_angle_change);  // _clip_motor_commands (:706-723)
+      // MotorModel.convert_to_torque, POSITION mode (minitaur_motor.py:163-171); pd latency 0 (:359-363): the carried angle and rate
+      S.tau[lane < 12 ? mj : lane] = m_gain * (-1.0f * (m_kp * (qm_c - cmd)) - m_kd * qdm_c);
+    }
+    WSYNC();
+    action_counter++;  // robot_step bookkeeping (minitaur.py:287-293); written back after the loop
+    PT(2);
+    {  // receive_obs, then the control observation of the next sub-step / of get_obs
+      RingFetch F;
+      ring_prefetch(rlat, rec, ring, lane, F);
+      if constexpr (MODE == 2) {
+        const size_t slot = (size_t)robot * c.action_repeat + sstep;
+        if (lane < 12 && valid) RP.tau_out[slot * 12 + lane] = S.tau[mj] * m_tsign;  // motor torque, motor order
+        WSYNC();
+        for (int i = lane; i < 37; i += kLanes) S.s[O(POS) + i] = RP.traj[slot * 37 + i];        // POS QUAT LINVEL ANGVEL Q QD
+        WSYNC();
+        fall = RP.fall[robot];
+      } else
+      fall = physics_substep<ANCHOR>(P, S, K, lane, sub, sstep == c.action_repeat - 1, X, limit_idle, ANCHOR ? &AS : nullptr, anchor_robot);
+      qm_c = (S.s[O(Q) + mj] - m_off) * m_dir;
+      qdm_c = S.s[O(QD) + mj] * m_dir;
+      ring_push_and_ctrl_obs(rec, S, lane, valid, F, ring, qm_c, &co_own);
+    }
+    PT(10);
+  }
+  // past its sub-step loop (reward, observation, reset, store: few vector instructions between long memory waits) a wave issues ahead of its
+  // partner: it costs the partner next to nothing and shortens the tail (8192 robots: -0.1 %; with -Os for this unit -0.4 %, profiles/r04_ab29_8192.log)
+  if (WPE == 2) __builtin_amdgcn_s_setprio(3);
+  // the cold-table constants of an auto-reset (ResetConst), issued here, ahead of the step end's stores and atomics.  Loaded again
+  // rather than taken from the registers that hold some of them over the sub-steps (m_init is dead by now): keeping those live up to
+  // the reset moved the sub-step loop's register allocation (+10 instructions) for a launch no faster
+  const ResetConst RC = load_reset_const(P, S, lane);
+  if (lane == 0) {  // end of robot_step (minitaur.py:287-293)
+    seti(S, O(RING_HEAD), ring.head); seti(S, O(RING_LEN), ring.len);
+    seti(S, O(STATE_ACTION_COUNTER), action_counter);
+    seti(S, O(FILTER_VALID), 1);
+    seti(S, O(STEP_COUNTER), geti(S, O(STEP_COUNTER)) + 1);
+  }
+  if (lane < 12) S.s[O(FILTER_ACTION) + lane] = m_target;
+  WSYNC();
+  // ---- get_obs: sensors on_step (minitaur.py:295-299) ----
+  sensors_push(S, lane, false);
+  PT(11);
+  // ---- reward -> update -> done (quadruped_gym_env.py:230-233) ----
+  // the frames of the new reference poses are fetched while the reward is computed (their round trip to L2 is not waited for)
+  const DevClip& clip = S.clip;
+  double t = motion_time(P, S);                             // f64: see DevClip
+  // CLIPS: the clip change of _update_ref_motion (imitation_task.py:734-761, 1096-1101), decided before anything samples the clip.  The
+  // phase of the update is the NEW clip's at the OLD offset's time (t_phase, :749-750); pose, targets and termination use the new time
+  double t_phase = t;
+  bool switched = false;
+  if constexpr (CLIPS) {
+    if (t >= (double)clip_change) {
+      typedef const int __attribute__((address_space(1)))* gip;
+      typedef const float __attribute__((address_space(1)))* gfp;
+      const int type = geti(S, O(ROBOT_TYPE));
+      const int set_n = ((gip)&P.tab->clip_set_n[0])[type];
+      const float sw_min = ((gfp)&P.tab->clip_switch[type][0])[0], sw_max = ((gfp)&P.tab->clip_switch[type][0])[1];
+      // num_motions > 1 (:1099), and the type still has an interval: switching turned off (orr_set_clip_switch(+inf, +inf)) stops at once,
+      // although the records keep their finite change times until their next reset
+      if (set_n > 1 && sw_max < INFINITY) {
+        // draws 32 + 4 s .. 34 + 4 s of the episode's stream (Philox block 8 + s, s = the env step counter before this step): the clip
+        // (as reset_robot<true> draws it), the next change, the new time offset (_sample_time_offset, :1112-1123)
+        float u4[4];
+        philox_block(c.seed, (uint32_t)geti(S, O(ROBOT_INDEX)), (uint32_t)geti(S, O(EPISODE_IDX)), 8u + (uint32_t)geti(S, O(EP_STEP)), u4);
+        const uint32_t m = (uint32_t)(u4[0] * 16777216.0f);
+        const int k = (int)((m * (uint32_t)set_n) >> 24);
+        const int id = ((gip)&P.tab->clip_set[type][0])[k];
+        clip_change = clip_change_time(t, sw_min, sw_max, u4[1]);
+        WSYNC();
+        if (lane == 0) seti(S, O(CLIP_ID), id);
+        const unsigned int* cg = reinterpret_cast<const unsigned int*>(&P.tab->clip[id]);
+        unsigned int* cl = reinterpret_cast<unsigned int*>(&S.clip);
+        if (lane < (int)(sizeof(DevClip) / 4)) cl[lane] = cg[lane];
+        WSYNC();
+        if (lane == 0) {
+          S.s[O(TIME_OFFSET)] = u4[2] * (float)clip.dur_d;
+          if (valid) rec[O(CLIP_CHANGE_TIME)] = clip_change;   // an auto-reset later in this step overwrites it (same lane, in order)
+        }
+        WSYNC();
+        t = motion_time(P, S);
+        switched = true;
+      }
+    }
+  }
+  const double step_dt = clip.sim_dt_d * c.action_repeat;
+  double tl = t;
+  {  // lanes 1..4: the four target times.  Selects over the four scalars: indexing the kernel argument with the lane makes the
+     // compiler read it from memory with a vector load, whose wait also drains every store and atomic issued before it
+    const int k = lane - 1;
+    const int steps = (k & 2) ? ((k & 1) ? c.tar_frame_steps[3] : c.tar_frame_steps[2]) : ((k & 1) ? c.tar_frame_steps[1] : c.tar_frame_steps[0]);
+    if (lane >= 1 && lane <= 4) tl = t + steps * step_dt;
+  }
+  PoseLoads PL;
+  sample_poses_issue(P, S, lane, tl, PL);
+  float rew = calc_reward(P, S, lane, MODE == 2 ? RP.eff + (size_t)robot * 48 : nullptr);
+  sample_poses_finish(P, S, lane, tl, true, PL);
+  {
+    // _update_ref_motion (imitation_task.py:734-761) with _sync_ref_origin (:1020-1055)
+    const float ph = clip_phase(clip, t_phase);
+    if (lane == 0) {
+      bool sync_pos = (c.flags & ORR_FLAG_CYCLE_SYNC) && ph < S.s[O(PREV_PHASE)];
+      if constexpr (CLIPS) {
+        if (switched) {   // a clip change syncs the heading (relative to the init orientation, _calc_heading) first, then the position
+          q_about_z(task_heading(S, &S.s[O(QUAT)]) - task_heading(S, &S.ph.end.pose[0][3]), &S.s[O(ORIGIN_ROT)]);
+          sync_pos = true;
+        }
+      }
+      if (sync_pos) {
+        float pr[3];
+        qrot(&S.ph.end.pose[0][0], &S.s[O(ORIGIN_ROT)], pr);
+        S.s[O(ORIGIN_POS)] = S.s[O(POS)] - pr[0];
+        S.s[O(ORIGIN_POS) + 1] = S.s[O(POS) + 1] - pr[1];
+        S.s[O(ORIGIN_POS) + 2] = 0.0f;
+      }
+      S.s[O(PREV_PHASE)] = ph;
+      float v[3];
+      qrot(&S.ph.end.vel[0], &S.s[O(ORIGIN_ROT)], v); S.ph.end.vel[0] = v[0]; S.ph.end.vel[1] = v[1]; S.ph.end.vel[2] = v[2];
+      qrot(&S.ph.end.vel[3], &S.s[O(ORIGIN_ROT)], v); S.ph.end.vel[3] = v[0]; S.ph.end.vel[4] = v[1]; S.ph.end.vel[5] = v[2];
+    }
+    WSYNC();
+    apply_origin(S, lane, 5);
+    for (int i = lane; i < 19; i += kLanes) S.s[O(REF_POSE) + i] = S.ph.end.pose[0][i];
+    for (int i = lane; i < 18; i += kLanes) S.s[O(REF_VEL) + i] = S.ph.end.vel[i];
+    WSYNC();
+  }
+  PT(12);
+  // _terminal_condition (imitation_task.py:518-572) + time limit (wrapper_env.py:79) + non-finite guard
+  int reason = 0;
+  // the slot is only defined where the atomic was issued (lane 0 of a robot whose episode ended) and only read there.  A frozen
+  // nondeterministic value instead of an uninitialised variable: reading it is defined behaviour in every lane, and unlike a constant
+  // it gives the compiler nothing to merge with the atomic's result (a merged value made it wait for the atomic right away)
+  unsigned long long log_slot = __builtin_nondeterministic_value(log_slot);
+  {
+    const float* rp = &S.s[O(REF_POSE)];
+    float pe = 0.0f, qc[4], dq[4];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { float d = rp[k] - S.s[O(POS) + k]; pe += d * d; }
+    qconj(&S.s[O(QUAT)], qc);
+    qmul(rp + 3, qc, dq);
+    const float ang = q_norm_angle(dq);
+    if (geti(S, O(STEP_COUNTER)) > 0 && fall) reason |= ORR_DONE_CONTACT_FALL;
+    if (pe > c.dist_fail_threshold * c.dist_fail_threshold) reason |= ORR_DONE_ROOT_POS;
+    if (fabsf(ang) > c.rot_fail_threshold) reason |= ORR_DONE_ROOT_ROT;
+    if (!(clip.flags & ORR_CLIP_WRAP) && t >= clip.dur_d) reason |= ORR_DONE_MOTION_OVER;  // is_motion_over (:224-233)
+    bool bad = false;
+    for (int i = lane; i < 37; i += kLanes) bad = bad || !(fabsf(S.s[O(POS) + i]) < 1e30f);
+    if (((__ballot(bad) >> (sub * kLanes)) & ((1ull << (kLanes - 1)) * 2ull - 1ull)) != 0ull || S.s[kHead - 1] != 0.0f) reason |= ORR_DONE_NAN;
+    if (!(fabsf(rew) < 1e30f)) reason |= ORR_DONE_NAN;
+    if (reason & ORR_DONE_NAN) rew = 0.0f;      // whatever was computed from a non-finite state is not a reward
+    const int ep_step = geti(S, O(EP_STEP)) + 1;  // quadruped_gym_env.py:237
+    if (ep_step >= geti(S, O(MAX_EP_STEPS))) reason |= ORR_DONE_TIME_LIMIT;
+    // episode log (imitation_runners.py:185-197): the slot comes from a returning atomic on a counter shared by the whole device (a
+    // round trip of several microseconds).  It is issued HERE, as soon as the end of the episode is known, and consumed after the
+    // reset: the observation, the target observation and the first stages of the reset run while it is in flight
+    if (lane == 0 && valid && reason != 0) log_slot = atomicAdd((unsigned long long*)&P.counters[ORR_CNT_EPISODES], 1ull);
+    WSYNC();
+    if (lane == 0) {
+      seti(S, O(EP_STEP), ep_step);
+      seti(S, O(DONE_REASON), reason);
+      S.s[O(EP_RETURN)] += rew;
+    }
+  }
+  // observation (wrapper_env.py:109-125)
+  if (lane < 12) obs[lane] = S.s[O(IMU_HIST) + lane];
+  for (int i = lane; i < 36; i += kLanes) { obs[12 + i] = S.s[O(LASTACT_HIST) + i]; obs[48 + i] = S.s[O(MOTORANG_HIST) + i]; }
+  target_obs(P, rec, S, lane, obs + ORR_PROPRIO_DIM);
+  if (valid && lane == 0) {
+    reward_out[robot] = rew;
+    done_out[robot] = reason != 0;
+  }
+  PT(13);
+  if (reason != 0) {
+    float log_ret = 0.0f, log_len = 0.0f;
+    int log_clip = 0;     // CLIPS: the clip the ending episode played, read before reset_robot draws the next one
+    const bool logs = lane == 0 && valid;
+    const unsigned long long slot = log_slot;
+    if (lane == 0) {
+      log_ret = S.s[O(EP_RETURN)]; log_len = (float)geti(S, O(EP_STEP));
+      if constexpr (CLIPS) log_clip = geti(S, O(CLIP_ID));
+      S.s[O(LAST_EP_RETURN)] = log_ret;
+      seti(S, O(LAST_EP_LEN), geti(S, O(EP_STEP)));
+    }
+    WSYNC();
+    if (c.flags & ORR_FLAG_AUTO_RESET) {
+      PT(31);
+      reset_robot<CLIPS>(P, rec, S, lane, valid, total_snapshot, obs, RC);
+      if constexpr (ANCHOR) AS = AnchorState{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};   // a new episode: no cached contact points
+    }
+    if (logs && P.ep_log) {
+      if (slot < (unsigned long long)P.ep_log_cap) {
+        P.ep_log[2 * slot] = log_ret;
+        P.ep_log[2 * slot + 1] = log_len;
+        if constexpr (CLIPS) {
+          int* const clip_log = P.tab->clip_log;
+          if (clip_log) clip_log[slot] = log_clip;
+        }
+      } else {
+        atomicAdd((unsigned long long*)&P.counters[ORR_CNT_EPLOG_DROPPED], 1ull);
+      }
+    }
+  }
+  WSYNC();
+  PT(14);
+  store_robot(rec, S, lane, valid);
+  store_anchor();
+  if (valid) {   // the observation, in 16-byte pieces like the record (40 per robot)
+    typedef f4 __attribute__((address_space(1))) * g4ptr;
+    static_assert(ORR_OBS_DIM % 4 == 0, "16-byte pieces");
+    const g4ptr od = (g4ptr)reinterpret_cast<f4*>(obs_out + (size_t)robot * ORR_OBS_DIM);
+    const f4* os = reinterpret_cast<const f4*>(obs);
+#pragma unroll
+    for (int k = 0; k < (ORR_OBS_DIM / 4 + kLanes - 1) / kLanes; k++) { const int q = lane + k * kLanes; if (q < ORR_OBS_DIM / 4) od[q] = os[q]; }
+  }
+  PT(15);
+  PT_FLUSH();
+  // One counter update per WAVE (the compiler's own atomic combining is switched off, see _lib.HIPCC_FLAGS: it makes the issuing
+  // lane wait for the returned value on the spot).  The launch tally is ONE 64-bit word (ORR_CNT_TICKET: finished episodes in the
+  // high half, robots counted in the low half), so one returning atomic both adds the wave's finished episodes and takes its ticket:
+  // there is no second word to order it against, and no fence (it cost 7 % of the launch: a write-back of the wave's ~18 KB of fresh
+  // stores, an L2 invalidate and two waits).  The wave that completes the count folds the done count into the
+  // curriculum counter (wrapper_env.py:82-83) and clears the word with non-returning atomics.  The fold may land while other waves
+  // still run: every wave read its snapshot of the curriculum counter when it started, and the last ticket can only be taken once
+  // every wave of the launch has started (and taken its own).  The episode log and the records are read after the kernel boundary only.
+  // Issued HERE, not with the episode-log slot: held across the reset, the returned value moved the sub-step loop's register
+  // allocation (+6 instructions) and the launch got slower (0.1993 against 0.1976 ms).
+  const unsigned long long fin_mask = __ballot(valid && lane == 0 && reason != 0), val_mask = __ballot(valid && lane == 0);
+  if (wtid == 0) {
+    const unsigned long long add = ((unsigned long long)__popcll(fin_mask) << 32) | (unsigned long long)__popcll(val_mask);
+    const unsigned long long now = atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TICKET], add) + add;
+    if ((unsigned int)now == (unsigned int)P.cfg.num_robots) {   // the low half never carries: it counts up to num_robots
+      atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TOTAL_STEP_COUNT], now >> 32);
+      atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TOTAL_TIMESTEPS], (unsigned long long)P.cfg.num_robots);
+      atomicExch((unsigned long long*)&P.counters[ORR_CNT_TICKET], 0ull);   // every other wave's update came before this wave's
+    }
+  }
+  PT_TIMELINE((long long)((fin_mask & 1ull) | ((fin_mask >> 15) & 2ull) | ((fin_mask >> 30) & 4ull) | ((fin_mask >> 45) & 8ull)));   // one bit per robot of the wave
+  WT_STORE((long long)((fin_mask & 1ull) | ((fin_mask >> 15) & 2ull) | ((fin_mask >> 30) & 4ull) | ((fin_mask >> 45) & 8ull)));
+}
+
+
+// ================================================================================================
+// launchers
+// ================================================================================================
+// One launcher per kernel template: `waves` = robots / kRPW rounded up, step_wpb() of them to a workgroup (1 in the shipped build).
+// Each instantiation belongs to ONE unit, which instantiates it explicitly (`template orr::StepLaunch orr::launch_step<...>;`, in the
+// order its kernels are to have in the code object); the `extern template` declarations below keep every other unit from
+// instantiating it, kernel included.
+namespace orr {
+using StepLaunch = hipError_t(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done,
+                              int nsub, const ReplayArgs& rp);
+using ResetLaunch = hipError_t(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs, const float* uniforms);
+
+template <int MODE, int WPE, bool ANCHOR, bool CLIPS>
+hipError_t launch_step(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done, int nsub,
+                       const ReplayArgs& rp) {
+  constexpr int wpb = step_wpb<MODE, WPE>();
+  hipLaunchKernelGGL((orr_step_kernel<MODE, WPE, ANCHOR, CLIPS>), dim3((waves + wpb - 1) / wpb), dim3(64 * wpb), 0, stream, P, actions, obs, reward,
+                     done, nsub, rp);
+  return hipGetLastError();
+}
+template <bool CLIPS>
+hipError_t launch_reset(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs, const float* uniforms) {
+  hipLaunchKernelGGL((orr_reset_kernel<CLIPS>), dim3(waves), dim3(64), 0, stream, P, mask, obs, uniforms);
+  return hipGetLastError();
+}
+
+extern template StepLaunch launch_step<0, 2, false, false>;                  // orr_kernels_w2.hip
+extern template StepLaunch launch_step<0, 1, true, false>;                   // orr_kernels_anchor.hip: env step,
+extern template StepLaunch launch_step<1, 1, true, false>;                   //   debug physics
+extern template StepLaunch launch_step<0, 1, false, true>;                   // orr_kernels_multiclip.hip: env step,
+extern template StepLaunch launch_step<2, 1, false, true>;                   //   its parity replay,
+extern template ResetLaunch launch_reset<true>;                              //   reset (and, with the draws given, its parity replay)
+}  // namespace orr

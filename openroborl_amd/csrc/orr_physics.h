@@ -1,5 +1,5 @@
 // orr_physics.h -- one physics sub-step: leg dynamics, constraint rows, Gauss-Seidel sweeps, integration (pybullet stepSimulation)
-// (device code of libopenroborl_hip.so, included by orr_kernels.hip after orr_device.h; see DESIGN.md sections 3-5)
+// (device code of libopenroborl_hip.so, included by orr_env_kernels.h after orr_device.h; see DESIGN.md sections 3-5)
 #pragma once
 
 // ================================================================================================
@@ -133,7 +133,7 @@ __device__ __forceinline__ void chol6_solve_pk(const Chol6Pk& F, float b0, float
 // hide the LDS round trips of re-reading them every sub-step).  Lane (leg = lane & 3, part = (lane >> 2) & 3) walks the
 // joints 0..min(part, 2) of its leg and owns link `part` (part 3: an idle copy with zero inertia): the chain constants of
 // the joints beyond its own are zeroed, so that walking "through" them is the identity.
-// Two choices differ between the translation units (orr_kernels.hip: why there are several); they are properties of the unit, not -D knobs:
+// Two choices differ between the translation units (orr_env_kernels.h: why there are several); they are properties of the unit, not -D knobs:
 //   kCarrySubtreeMass  the subtree mass lives in a register across the launch in the one-wave build only: the 256-register build pays more
 //                      for the live register than for the two adds that rebuild it every sub-step
 //   kOwnLegFactor      row_response's variant (b), see there: four more live registers cost the two-wave unit 30 spilled ones

@@ -1,5 +1,5 @@
 // orr_robot_io.h -- per-robot record load / store and the latency ring (Minitaur.receive_obs / _get_delay_obs)
-// (device code of libopenroborl_hip.so, included by orr_kernels.hip after orr_device.h; see DESIGN.md sections 3-5)
+// (device code of libopenroborl_hip.so, included by orr_env_kernels.h after orr_device.h; see DESIGN.md sections 3-5)
 #pragma once
 
 // ================================================================================================

@@ -1,5 +1,5 @@
 // orr_task.h -- motion clips, imitation reward / observation / termination, sensors, reset (ImitationTask, sensors, Minitaur.reset)
-// (device code of libopenroborl_hip.so, included by orr_kernels.hip after orr_device.h; see DESIGN.md sections 3-5)
+// (device code of libopenroborl_hip.so, included by orr_env_kernels.h after orr_device.h; see DESIGN.md sections 3-5)
 #pragma once
 
 // ================================================================================================

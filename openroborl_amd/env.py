@@ -119,7 +119,7 @@ CLIP_CHANGE_DRAW = 29   # the first clip change of an episode: draw 29 of the re
 
 def clip_switch_draws(ep_step):
     """Draw indices (clip, next change, time offset) of a mid-episode clip switch in the step whose env-step counter before the step
-    is ep_step (csrc/orr_kernels.hip, orr_step_kernel<.., CLIPS>): 32 + 4 s, 33 + 4 s, 34 + 4 s = Philox block 8 + s, words 0..2 of the
+    is ep_step (csrc/orr_env_kernels.h, orr_step_kernel<.., CLIPS>): 32 + 4 s, 33 + 4 s, 34 + 4 s = Philox block 8 + s, words 0..2 of the
     episode's (seed, robot index, episode) stream.  The clip is set[clip_draw_index(m, n)] with m the 24-bit integer of the first."""
     d = 32 + 4 * np.asarray(ep_step, dtype=np.int64)
     return d, d + 1, d + 2
@@ -169,7 +169,7 @@ def action_space():
 
 
 class VecQuadrupedEnv(object):
-    """N independent quadrupeds on one GPU; four robots per wavefront, 16 lanes each (see csrc/orr_kernels.hip, orr_physics.h)."""
+    """N independent quadrupeds on one GPU; four robots per wavefront, 16 lanes each (see csrc/orr_env_kernels.h, orr_physics.h)."""
 
     def __init__(self, task_name=None, training_yaml=None, sim_yaml=None, device="cuda", num_robot=None, seed=None,
                  robot=None, motion_file=None, mode=None, enable_randomizer=None, auto_reset=True, num_procs=1,

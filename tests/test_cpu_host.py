@@ -154,9 +154,8 @@ def test_the_kernel_tuning_knobs_still_compile(defs):
     second each), in all four translation units of the env kernels."""
     import subprocess
     base = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + ["--cuda-device-only", "-fsyntax-only", "-Wno-unused-command-line-argument"]
-    csrc = os.path.dirname(_lib.SRC)
-    for src in (_lib.SRC, os.path.join(csrc, "orr_kernels_w2.hip"), os.path.join(csrc, "orr_kernels_anchor.hip"),
-                os.path.join(csrc, "orr_kernels_multiclip.hip")):
+    assert len(_lib.ENV_UNITS) == 4
+    for _, src, _, _ in _lib.ENV_UNITS:
         r = subprocess.run([_lib.HIPCC] + base + defs + [src], capture_output=True, text=True)
         assert r.returncode == 0, "%s %s:\n%s" % (os.path.basename(src), " ".join(defs), r.stderr[-1500:])
 
@@ -228,6 +227,54 @@ def test_stale_library_is_rebuilt_and_the_new_build_is_what_gets_loaded(tmp_path
                          env={k: v for k, v in os.environ.items() if not k.startswith("ORR_")})
     assert out.returncode == 0, out.stdout + out.stderr
     assert "LOADED" in out.stdout and _lib.source_hash() in out.stdout.split("OLD")[1]
+
+
+def test_every_source_is_a_dependency_of_the_stale_library_check(tmp_path):
+    """_lib.DEPS is every *.h / *.hip under csrc/ plus the public headers (a header nobody listed would drop out of the hash), the unit
+    table names existing sources, and an edit of the env kernels' header changes source_hash().  No rebuild: a copy of the package."""
+    import shutil
+    import subprocess
+    import sys
+    csrc = os.path.join(ROOT, "openroborl_amd", "csrc")
+    want = {os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".hip"))}
+    want |= {os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")}
+    assert want == set(_lib.DEPS) and len(_lib.DEPS) == len(want)
+    assert len(_lib.UNITS) == 6 and _lib.ENV_UNITS == _lib.UNITS[:4]
+    for name, src, flags, hashed in _lib.UNITS:
+        assert os.path.isfile(src) and src in _lib.DEPS, name
+    assert [u[0] for u in _lib.UNITS if u[3]] == ["env"]          # the unit that defines orr_source_hash()
+    pkg = tmp_path / "openroborl_amd"
+    shutil.copytree(os.path.join(ROOT, "openroborl_amd"), pkg, ignore=shutil.ignore_patterns("__pycache__", "data", "*.o", "*.so"))
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    with open(pkg / "csrc" / "orr_env_kernels.h", "a") as f:
+        f.write("\n// edited by the dependency test\n")
+    code = "import sys; sys.path.insert(0, %r)\nfrom openroborl_amd import _lib\nprint('HASH', _lib.source_hash())\n" % str(tmp_path)
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600,
+                         env={k: v for k, v in os.environ.items() if not k.startswith("ORR_")})
+    assert out.returncode == 0, out.stdout + out.stderr
+    edited = out.stdout.split("HASH")[1].split()[0]
+    assert len(edited) == 32 and edited != _lib.source_hash()
+
+
+def undefined_project_symbols(lib_path):
+    """Undefined dynamic symbols of a built library that can only be the project's own: a launcher or kernel that no unit instantiated"""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--undefined-only", lib_path], capture_output=True, text=True, check=True).stdout
+    return [l.split()[-1] for l in out.splitlines() if l.strip() and ("orr" in l.split()[-1] or "launch_" in l.split()[-1])]
+
+
+@pytest.mark.parametrize("define", ["-DORR_WAVES_PER_EU=2", "-DORR_WPB=2"])
+def test_the_launch_shape_builds_still_link(tmp_path, define):
+    """The two launch-shape experiments (tools/wave_pairing.py) as whole builds: every unit instantiates its launchers explicitly, and
+    with -DORR_WAVES_PER_EU=2 the main unit's default step IS the two-wave unit's instantiation - both emit it, and that has to link."""
+    out = str(tmp_path / "lib_shape.so")
+    assert _lib.build(out_path=out, extra_flags=[define]) == out and os.path.getsize(out) > 0
+    assert undefined_project_symbols(out) == []
+
+
+def test_the_product_build_has_no_undefined_project_symbol():
+    assert _lib.library_hash() == _lib.source_hash(), "in-tree library is stale"
+    assert undefined_project_symbols(_lib.LIB_PATH) == []
 
 
 def test_tuning_defines_are_part_of_the_source_hash(monkeypatch):

@@ -1,6 +1,6 @@
 """Compile-only (no GPU): the env step kernels end without a device-wide cache write-back.
 
-The launch tally is one packed 64-bit word (orr_kernels.hip, end of orr_step_kernel), so no wave needs a fence between its counter
+The launch tally is one packed 64-bit word (orr_env_kernels.h, end of orr_step_kernel), so no wave needs a fence between its counter
 updates.  A `__threadfence()` compiles to `buffer_wbl2` (+ an L2 invalidate and waits) on gfx950; it cost 7 % of the 4096-robot launch.
 Checked in the full env step (MODE 0) and its parity replay (MODE 2) of every translation unit that holds them.
 """
@@ -12,8 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 from openroborl_amd import _lib
 
-UNITS = [(_lib.SRC, _lib.HIPCC_FLAGS), (_lib.SRC_W2, _lib.HIPCC_FLAGS_W2), (_lib.SRC_ANCHOR, _lib.HIPCC_FLAGS),
-         (_lib.SRC_MULTICLIP, _lib.HIPCC_FLAGS)]
+UNITS = [(src, flags) for _, src, flags, _ in _lib.ENV_UNITS]
 
 
 def kernel_bodies(asm):

@@ -1,22 +1,13 @@
 #!/bin/bash
 # A/B of the working tree against a git commit on ONE GPU box (development aid).
-#   here (build container):  tools/ab_commit.sh build <commit>     -> openroborl_amd/lib_ab_old.so from that commit's kernels
+#   here (build container):  tools/ab_commit.sh build <commit>     -> openroborl_amd/lib_ab_old.so = that commit's library
 #   on the GPU box (gpurun): tools/ab_commit.sh run [rounds]        -> alternating bench runs old / new
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 if [ "$1" = build ]; then
   C=${2:-HEAD}; TMP=$(mktemp -d)
-  git -C "$ROOT" archive "$C" openroborl_amd/csrc include | tar -x -C "$TMP"
-  # the SAME compiler flags as the shipped library (openroborl_amd/_lib.py HIPCC_FLAGS)
-  python3 - "$ROOT" "$TMP" <<'PY' && echo "built lib_ab_old.so from $C"
-import subprocess, sys
-root, tmp = sys.argv[1], sys.argv[2]
-sys.path.insert(0, root)
-from openroborl_amd import _lib
-fl = [f for f in _lib.HIPCC_FLAGS if f != "-shared"]
-subprocess.check_call([_lib.HIPCC] + fl + ["-c", "-o", tmp + "/k.o", tmp + "/openroborl_amd/csrc/orr_kernels.hip"])
-subprocess.check_call([_lib.HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", "-o", tmp + "/p.o", tmp + "/openroborl_amd/csrc/orr_policy.hip"])
-subprocess.check_call([_lib.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", root + "/openroborl_amd/lib_ab_old.so", tmp + "/k.o", tmp + "/p.o"])
-PY
+  git -C "$ROOT" archive "$C" openroborl_amd include | tar -x -C "$TMP"
+  # every unit of that commit, by that commit's own build recipe (its openroborl_amd/_lib.py)
+  (cd "$TMP" && python3 -c "from openroborl_amd import _lib; _lib.build(out_path='$ROOT/openroborl_amd/lib_ab_old.so')") && echo "built lib_ab_old.so from $C"
   python3 -c "import sys; sys.path.insert(0, '$ROOT'); from openroborl_amd import _lib; _lib.build()" && echo "working-tree library up to date"
   exit 0
 fi

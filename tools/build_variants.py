@@ -2,13 +2,13 @@
 """Build differently compiled copies of the library for tools/ab_variants.sh (development aid; build container).
 
 usage: python tools/build_variants.py name=[main|w2|both]:flag,flag,... [name=...]      ("base=main:" = the shipped flags)
-The flags replace / extend those of ONE translation unit (main = orr_kernels.hip: everything incl. the one-wave step kernel, ILP
-scheduler; w2 = orr_kernels_w2.hip: the two-waves-per-SIMD step kernel, default scheduler); the other unit keeps its shipped flags.
-A flag set that names an -amdgpu-sched-strategy replaces the unit's own; "nosched" removes it; -O1/-O2/-O3 replace -O2.
+The flags replace / extend one of the two flag sets of the env kernels' units (openroborl_amd/_lib.py: UNITS): main = HIPCC_FLAGS
+(orr_kernels.hip: the one-wave step kernel, ILP scheduler, and the friction-anchor and clip-set units, which share its flags);
+w2 = HIPCC_FLAGS_W2 (orr_kernels_w2.hip: the two-waves-per-SIMD step kernel); the other set keeps its shipped flags.
+A flag set that names an -amdgpu-sched-strategy replaces the unit's own; "nosched" removes it; -O1/-O2/-O3/-Os replace -O2.
 Example: python tools/build_variants.py base=main: w2ilp=w2:-mllvm,-amdgpu-sched-strategy=iterative-ilp w2o3=w2:-O3
 """
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,19 +34,13 @@ def apply(base, extra):
     return base + extra
 
 
+SHIPPED = (list(_lib.HIPCC_FLAGS), list(_lib.HIPCC_FLAGS_W2))
 for spec in sys.argv[1:]:
     name, _, rest = spec.partition("=")
     tu, _, fl = rest.partition(":")
     extra = [f for f in fl.split(",") if f]
-    fm = apply(_lib.HIPCC_FLAGS, extra if tu in ("main", "both") else [])
-    fw = apply(_lib.HIPCC_FLAGS_W2, extra if tu in ("w2", "both") else [])
-    out = os.path.join(ROOT, "openroborl_amd", "lib_var_%s.so" % name)
-    tmp = "/tmp/var_%s" % name
-    os.makedirs(tmp, exist_ok=True)
-    procs = [subprocess.Popen([_lib.HIPCC] + fm + ["-c", '-DORR_SOURCE_HASH="variant-%s"' % name, "-o", tmp + "/k.o", _lib.SRC]),
-             subprocess.Popen([_lib.HIPCC] + fw + ["-c", "-o", tmp + "/w.o", _lib.SRC_W2]),
-             subprocess.Popen([_lib.HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", "-o", tmp + "/p.o", _lib.SRC_POLICY]),
-             subprocess.Popen([_lib.HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", "-o", tmp + "/l.o", _lib.SRC_LEARNER])]
-    assert all(p.wait() == 0 for p in procs), spec
-    subprocess.check_call([_lib.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, tmp + "/k.o", tmp + "/w.o", tmp + "/p.o", tmp + "/l.o"])
+    # the unit table refers to these two lists: change them in place, and _lib.build() compiles and links ALL units with them
+    _lib.HIPCC_FLAGS[:] = apply(SHIPPED[0], extra if tu in ("main", "both") else [])
+    _lib.HIPCC_FLAGS_W2[:] = apply(SHIPPED[1], extra if tu in ("w2", "both") else [])
+    out = _lib.build(out_path=os.path.join(ROOT, "openroborl_amd", "lib_var_%s.so" % name))
     print("built", out, tu, " ".join(extra))

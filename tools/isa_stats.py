@@ -2,7 +2,7 @@
 """Static instruction statistics of orr_step_kernel<0> from the compiler's assembly (development aid).
 
 usage: python tools/isa_stats.py [extra hipcc flags...]
-Compiles csrc/orr_kernels.hip to gfx950 assembly with the product's flags, finds the step kernel, and prints instruction
+Compiles the env kernels' units (csrc/orr_kernels*.hip) to gfx950 assembly with the product's flags, finds the step kernels, and prints instruction
 counts by class for the whole kernel and for its hottest region (the sub-step loop = the largest backward-branch body)."""
 import collections
 import os
@@ -47,29 +47,26 @@ def classify(m):
 
 
 STEP_KERNELS = (("_Z15orr_step_kernelILi0ELi1ELb0E", "step kernel, one wave per SIMD"), ("_Z15orr_step_kernelILi0ELi2ELb0E", "step kernel, two waves per SIMD"),
-                ("_Z15orr_step_kernelILi0ELi1ELb1E", "step kernel with friction anchors (one wave per SIMD)"))
+                ("_Z15orr_step_kernelILi0ELi1ELb1E", "step kernel with friction anchors (one wave per SIMD)"),
+                ("_Z15orr_step_kernelILi0ELi1ELb0ELb1E", "step kernel with clip sets (one wave per SIMD)"))
 
 
-def compile_units(extra_flags=(), only_main=False):
-    """Device assembly of the env kernels' translation units with the product's flags (+ extra_flags): one list of lines per unit
-    (main, two-wave, friction anchors)."""
-    flags = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + list(extra_flags)
-    out = os.path.join(tempfile.mkdtemp(), "step.s")
-    src = os.environ.get("ORR_ISA_SRC", _lib.SRC)      # another tree's orr_kernels.hip (A/B of code generation)
-    subprocess.check_call([_lib.HIPCC] + flags + ["-S", "--cuda-device-only", "-o", out, src], stderr=subprocess.DEVNULL)
-    units = [open(out).read().split("\n")]
-    if only_main:
-        return units
-    src_w2 = os.path.join(os.path.dirname(src), "orr_kernels_w2.hip")
-    if os.path.exists(src_w2):       # the two-waves-per-SIMD variant is its own translation unit with its own flags
-        flags_w2 = [f for f in _lib.HIPCC_FLAGS_W2 if f not in ("-shared", "-fPIC")] + list(extra_flags)
-        subprocess.check_call([_lib.HIPCC] + flags_w2 + ["-S", "--cuda-device-only", "-o", out + "2", src_w2], stderr=subprocess.DEVNULL)
-        units.append(open(out + "2").read().split("\n"))
-    src_an = os.path.join(os.path.dirname(src), "orr_kernels_anchor.hip")
-    if os.path.exists(src_an):       # the friction-anchor variants: third translation unit, the main unit's flags
-        subprocess.check_call([_lib.HIPCC] + flags + ["-S", "--cuda-device-only", "-o", out + "3", src_an], stderr=subprocess.DEVNULL)
-        units.append(open(out + "3").read().split("\n"))
-    return units
+def compile_units(extra_flags=(), only_main=False, units=("env", "w2", "anchor")):
+    """Device assembly of the env kernels' translation units, each with the product's flags for it (+ extra_flags): one list of lines
+    per unit.  `units` = names of _lib.ENV_UNITS, compiled in the table's order; the default is the three that tools/isa_lines.py and
+    tests/test_isa_budget.py address by index (0 main, 1 two-wave, 2 friction anchors), "multiclip" adds the clip-set unit."""
+    src_dir = os.path.dirname(os.environ.get("ORR_ISA_SRC", _lib.SRC))      # another tree's orr_kernels.hip (A/B of code generation)
+    out_dir = tempfile.mkdtemp()
+    listings = []
+    for name, src, flags, _ in _lib.ENV_UNITS[:1 if only_main else None]:
+        src = os.path.join(src_dir, os.path.basename(src))
+        if name not in units or not os.path.exists(src):      # (an older tree has fewer units)
+            continue
+        out = os.path.join(out_dir, name + ".s")
+        flags = [f for f in flags if f not in ("-shared", "-fPIC")] + list(extra_flags)
+        subprocess.check_call([_lib.HIPCC] + flags + ["-S", "--cuda-device-only", "-o", out, src], stderr=subprocess.DEVNULL)
+        listings.append(open(out).read().split("\n"))
+    return listings
 
 
 def parse_kernel(lines, sym):
@@ -133,9 +130,9 @@ def resources(meta, sym):
 
 
 def main():
-    lines = [l for u in compile_units(sys.argv[1:]) for l in u]
+    lines = [l for u in compile_units(sys.argv[1:], units=[u[0] for u in _lib.ENV_UNITS]) for l in u]
     meta = "\n".join(lines)
-    # one report per variant of the step kernel (WPE 1: one wave per SIMD, WPE 2: two; see orr_kernels.hip)
+    # one report per variant of the step kernel (WPE 1: one wave per SIMD, WPE 2: two; see orr_env_kernels.h)
     for sym, title in STEP_KERNELS:
         k = parse_kernel(lines, sym)
         if k is None:
