@@ -319,7 +319,8 @@ __device__ __forceinline__ float dpp_bcast_max0(float x, float zero) {
 }
 
 // sine / cosine of a joint angle (|a| is a few radians at most).  Cody-Waite reduction to [-pi/4, pi/4] with a
-// two-part pi/2 and minimax polynomials (~25 instructions, error < 1e-7, no large-argument branch): +2.3 % env steps/s
+// two-part pi/2 and minimax polynomials (~25 instructions, no approximate hardware instruction; error < 1e-7 for |a| <= 100,
+// measured on the device: tests/test_gpu_device_primitives.py, profiles/device_primitives.txt; no large-argument branch): +2.3 % env steps/s
 // over libm's sincosf at unchanged parity tolerances.
 __device__ __forceinline__ void joint_sincos(float a, float* sn, float* cs) {
   const float k = rintf(a * 0.63661977236758134f);       // a * 2/pi
@@ -342,15 +343,22 @@ __device__ __forceinline__ void joint_sincos(float a, float* sn, float* cs) {
 
 // Inverse trigonometric functions without branches (libm's atan2f / asinf / acosf cost a lone wave several taken or skipped
 // branches each, 13-30 ticks apiece: profiles/r02_issue_costs.txt).  atan2: octant reduction to t = min / max in [0, 1], then the
-// Cephes atanf kernel on [0, tan(pi/8)] (t -> (t - 1) / (t + 1) above it); absolute error < 3e-7 (checked against float64 on 2 M
-// random arguments).
+// Cephes atanf kernel on [0, tan(pi/8)] (t -> (t - 1) / (t + 1) above it); absolute error < 3e-7 with a correctly rounded
+// reciprocal (float64 check on 2 M random arguments); the device's 1-ulp v_rcp_f32 is on the path once, twice above the switch, and adds up
+// to 1.2e-7: the tested bound is 4.2e-7 over magnitudes 4.7e-38 .. 1e30 (tests/test_gpu_device_primitives.py; the measured maximum is
+// in profiles/device_primitives.txt).  asin_bf and everything built on these inherit both figures.
 // NaN arguments come out FINITE (fmax / fmin and the selects drop NaNs): non-finite numbers
 // are detected in ONE place, the |state| < 1e30 sweep + reward check at the end of the step (ORR_DONE_NAN, orr_env_kernels.h), never through
 // these functions (tests/test_gpu_parity.py::test_non_finite_state_is_caught_by_the_state_guard).
 __device__ __forceinline__ float atan2_bf(float y, float x) {
   const float ax = fabsf(x), ay = fabsf(y);
   const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-  const float t = mx > 0.0f ? mn * __builtin_amdgcn_rcpf(mx) : 0.0f;
+  // v_rcp_f32 takes a subnormal argument for zero (-> +inf; 0 * inf = NaN, and a subnormal mn gives inf, then NaN in the (t - 1) / (t + 1)
+  // branch): arguments below 2^-63 are scaled by 2^64 first, both alike, which is exact (tests/test_gpu_device_primitives.py).  This
+  // relies on the env units keeping float32 denormals (the compiler's default for gfx950, .amdhsa_float_denorm_mode_32 3): were they
+  // flushed (-fgpu-flush-denormals-to-zero), mx * sc would be 0 again and the NaN back.  Four instructions per call, asin_bf included.
+  const float sc = mx < 1.0842022e-19f ? 1.8446744e19f : 1.0f;
+  const float t = mx > 0.0f ? (mn * sc) * __builtin_amdgcn_rcpf(mx * sc) : 0.0f;
   const bool big = t > 0.41421356237f;
   const float u = big ? (t - 1.0f) * __builtin_amdgcn_rcpf(t + 1.0f) : t;
   const float z = u * u;
@@ -423,7 +431,8 @@ __device__ __forceinline__ float pick4(int lane, float x0, float x1, float x2, f
 }
 __device__ __forceinline__ float map_pi(float a) {  // pose3d.MapToMinusPiToPi (pose3d.py:358-374)
   // fmod(a, 2 pi) without libm's loop and branches (a taken or skipped branch costs a lone wave 3-6 multiply-adds): whole turns
-  // k = trunc(a / 2 pi), removed with a two-part 2 pi; exact (k = 0) for |a| < 2 pi, i.e. for every joint angle
+  // k = trunc(a / 2 pi), removed with a two-part 2 pi; exact (k = 0: m = a) for |a| < 2 pi, i.e. for every joint angle;
+  // beyond that within one ulp of |a| + 2.4e-7 for |a| <= 1000 (both tested on the device: tests/test_gpu_device_primitives.py)
   const float k = truncf(a * 0.15915494309189535f);
   float m = fmaf(-k, 6.2831854820251465f, a);       // 2 pi rounded to float ...
   m = fmaf(-k, -1.7484555e-07f, m);                 // ... and the rest of it

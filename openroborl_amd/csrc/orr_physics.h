@@ -47,7 +47,9 @@ __device__ __forceinline__ void chol6_solve(const float L[21], const float invdi
 // The factor is kept by COLUMNS with the rows below the diagonal paired (2,3) and (4,5): a rank-1 update of the trailing columns and a
 // forward substitution step then work on whole pairs with the scalar factor as an op_sel broadcast.  Every entry sees the operations of
 // chol6 / chol6_solve in the same order (the sums run over k ascending either way; the backward substitution stays scalar: by columns it
-// would subtract in descending order), each step ONE fused multiply-add.  Packed: the factorisation
+// would subtract in descending order), each step ONE fused multiply-add -
+// the same BITS as chol6 only where the compiler contracts chol6's `s -= a * b` into a fused multiply-add too, which is its choice:
+// tests/test_gpu_device_primitives.py prints whether the two agree bit for bit, profiles/device_primitives.txt has the answer.  Packed: the factorisation
 // and the solves, and also the column of T, the elimination terms -T_k F_k^T / T_k b_k and the 16-lane sums in that layout (leg_dynamics).
 // 4096 robots 0.2187 -> 0.2164 ms, 8192 robots 0.3033 -> 0.3005 ms (interleaved A/B, profiles/r04_ab17_*.log).
 typedef float pk2 __attribute__((ext_vector_type(2)));
