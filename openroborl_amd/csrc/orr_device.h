@@ -136,7 +136,8 @@ struct KParams {
   int simds;           // SIMDs of the device: workgroup b belongs to dispatch round b / simds (two-waves-per-SIMD variant: priority alternation)
   int anchor_on;       // some robot type has orr_model::friction_anchor: the launches run the anchor variant of the step kernel, resets clear the anchors
 #ifdef ORR_WAVE_TIMELINE
-  long long* wave_times;   // development aid (tools/wave_times.py): 4 words per wave of the step kernel, either variant
+  long long* wave_times;   // development aid (orr_debug_wave_times): 4 words per wave of the step kernel, every variant
+  int wave_times_cap;      // waves it has room for (0 until it is allocated)
 #endif
 };
 // The cold part of a robot type's model, as a GLOBAL-address-space pointer: loads through it are global_load instructions (a generic
@@ -223,7 +224,7 @@ struct alignas(16) Shared {
   alignas(16) float co[20];    // control (latency-delayed) observation
   alignas(16) PhaseBuf ph;
 #ifdef ORR_PHASE_TIMERS
-  long long pt_acc[kPhaseSlots], pt_last, pt_t0, pt_r0;  // development aid, see PT() in orr_env_kernels.h
+  long long pt_acc[kPhaseSlots], pt_last;  // development aid, see PT() in orr_env_kernels.h
 #endif
 };
 

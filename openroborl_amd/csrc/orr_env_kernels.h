@@ -12,6 +12,12 @@
 // A unit may set two properties before the include: ORR_TU_STEP_W2 + ORR_PARITY (orr_kernels_w2.hip; orr_physics.h, orr_device.h)
 // and ORR_TU_MAIN (orr_kernels.hip: the unit that holds the development timers' and counters' globals).
 #pragma once
+// The phase timers' build also records the per-wave timeline.  Decided HERE, in front of the line that keeps the timers to the main
+// unit: KParams (which carries the timeline's buffer) is a by-value kernel argument built in the main unit and consumed by the other
+// units' launchers, so all four have to see the same struct.
+#if defined(ORR_PHASE_TIMERS) && !defined(ORR_WAVE_TIMELINE)
+#define ORR_WAVE_TIMELINE 1
+#endif
 #ifndef ORR_TU_MAIN
 #undef ORR_PHASE_TIMERS      // the development timers live in the main translation unit only
 #endif
@@ -30,30 +36,28 @@
 #include "orr_device.h"
 
 // Development aid (tools/phase_cycles.py): -DORR_PHASE_TIMERS makes lane 0 of one wave accumulate shader-clock cycles
-// per phase (Shared::pt_acc) and add them to g_phase_cycles at the end of the launch.
+// per phase (Shared::pt_acc) and add them to g_phase_cycles at the end of the launch.  It implies -DORR_WAVE_TIMELINE (top of this file).
 #ifdef ORR_PHASE_TIMERS
 __device__ long long g_phase_cycles[orr::kPhaseSlots];   // 0..15: phases of the step, 16..23: stages of reset_robot, 24..: finer marks inside the reset
 __device__ long long g_wave_phases[2048 * 40];   // per wave of the last launch: its own phase totals (tools/wave_phases.py)
-__device__ long long g_wave_timeline[4 * 2048];   // per wave of the last launch: realtime start, realtime end, shader cycles, reset flag
-#define PT_INIT() do { if (threadIdx.x == 0) { S.pt_t0 = clock64(); S.pt_r0 = wall_clock64(); } if (threadIdx.x == 0) { for (int i_ = 0; i_ < orr::kPhaseSlots; i_++) S.pt_acc[i_] = 0; S.pt_last = clock64(); } } while (0)
+#define PT_INIT() do { if (threadIdx.x == 0) { for (int i_ = 0; i_ < orr::kPhaseSlots; i_++) S.pt_acc[i_] = 0; S.pt_last = clock64(); } } while (0)
 #define PT(k) do { if (threadIdx.x == 0) { const long long t_ = clock64(); S.pt_acc[k] += t_ - S.pt_last; S.pt_last = clock64(); } } while (0)
-#define PT_TIMELINE(flag) do { if (threadIdx.x == 0 && blockIdx.x < 2048) { g_wave_timeline[4 * blockIdx.x] = S.pt_r0; g_wave_timeline[4 * blockIdx.x + 1] = wall_clock64(); g_wave_timeline[4 * blockIdx.x + 2] = clock64() - S.pt_t0; g_wave_timeline[4 * blockIdx.x + 3] = ((flag) & 0xFF) | ((long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8) | ((long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 40); } } while (0)   /* bits 8..39: HW_REG_HW_ID (wave, simd, cu, sh, se), 40..43: HW_REG_XCC_ID */
 #define PT_FLUSH() do { if (threadIdx.x == 0 && blockIdx.x == gridDim.x / 2) for (int i_ = 0; i_ < orr::kPhaseSlots; i_++) atomicAdd((unsigned long long*)&g_phase_cycles[i_], (unsigned long long)S.pt_acc[i_]); \
                         if (threadIdx.x == 0 && blockIdx.x < 2048) for (int i_ = 0; i_ < orr::kPhaseSlots; i_++) g_wave_phases[blockIdx.x * 40 + i_] = S.pt_acc[i_]; } while (0)
 #else
 #define PT_INIT()
 #define PT(k)
 #define PT_FLUSH()
-#define PT_TIMELINE(flag)
 #endif
 
-// Development aid (tools/wave_times.py): -DORR_WAVE_TIMELINE makes every wave of the step kernel - BOTH variants, product code otherwise -
-// record when it started and ended (100 MHz realtime counter), its shader cycles and the hardware slot it ran on (nothing else is
-// instrumented: two s_memrealtime / s_memtime pairs and one 32-byte store per wave)
+// Development aid (tools/wave_times.py, and the phase timers' tools): -DORR_WAVE_TIMELINE makes every wave of the step kernel - EVERY
+// variant, product code otherwise - record when it started and ended (100 MHz realtime counter), its shader cycles, which of its robots
+// finished an episode and the hardware slot it ran on (nothing else is instrumented: two s_memrealtime / s_memtime pairs and one
+// 32-byte store per wave, into KParams::wave_times once orr_debug_wave_times has allocated it, for the waves it has room for)
 #ifdef ORR_WAVE_TIMELINE
 #define WT_INIT() const long long wt_r0 = wall_clock64(), wt_c0 = clock64()
-#define WT_STORE(flag) do { if ((threadIdx.x & 63u) == 0 && P.wave_times) { long long* w_ = P.wave_times + 4 * (size_t)wave_id; w_[0] = wt_r0; w_[1] = wall_clock64(); w_[2] = clock64() - wt_c0; \
-    w_[3] = ((flag) & 0xFF) | ((long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8) | ((long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 40); } } while (0)
+#define WT_STORE(flag) do { if (threadIdx.x == 0 && wave_id < P.wave_times_cap) { long long* w_ = P.wave_times + 4 * (size_t)wave_id; w_[0] = wt_r0; w_[1] = wall_clock64(); w_[2] = clock64() - wt_c0; \
+    w_[3] = ((flag) & 0xFF) | ((long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8) | ((long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 40); } } while (0)   /* bits 8..39: HW_REG_HW_ID (wave, simd, cu, sh, se), 40..43: HW_REG_XCC_ID */
 #else
 #define WT_INIT()
 #define WT_STORE(flag)
@@ -83,15 +87,13 @@ using namespace orr;
 // kernels
 // ================================================================================================
 // lane group bookkeeping shared by the kernels: `sub` = which robot of this wave, `lane` = lane within the robot
-// WPB = wavefronts per workgroup (each wave is an independent quad of robots; nothing is shared between the waves of a workgroup)
-#define ORR_PROLOGUE() ORR_PROLOGUE_W(1)
-#define ORR_PROLOGUE_W(WPB)                                                              \
-  __shared__ Shared Sarr[kRPW * (WPB)];                                                  \
-  const int wtid = (WPB) > 1 ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;              \
-  const int wave_in_wg = (WPB) > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0; \
-  const int wave_id = (int)blockIdx.x * (WPB) + wave_in_wg;                              \
+// (a workgroup is one wave: an independent quad of robots)
+#define ORR_PROLOGUE()                                                                   \
+  __shared__ Shared Sarr[kRPW];                                                          \
+  const int wtid = (int)threadIdx.x;                                                     \
+  const int wave_id = (int)blockIdx.x;                                                   \
   const int sub = wtid / kLanes, lane = wtid % kLanes;                                   \
-  Shared& S = Sarr[wave_in_wg * kRPW + sub];                                             \
+  Shared& S = Sarr[sub];                                                                 \
   float* obs = S.ph.end.obs;                                                             \
   const int robot_raw = wave_id * kRPW + sub;                                            \
   const bool in_range = robot_raw < P.cfg.num_robots;                                    \
@@ -133,11 +135,6 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
 #ifndef ORR_WAVES_PER_EU
 #define ORR_WAVES_PER_EU 1   // development builds (-DORR_WAVES_PER_EU=2) force every instantiation to that occupancy
 #endif
-#ifndef ORR_WPB
-#define ORR_WPB 1            // wavefronts per workgroup of the one-wave-per-SIMD env step (tuning experiments: 2, 4)
-#endif
-template <int MODE, int WPE>
-constexpr int step_wpb() { return MODE == 0 && WPE == 1 ? ORR_WPB : 1; }
 // ANCHOR (ABI v5): the variant for robot types with orr_model::friction_anchor - Bullet's cached toe contact points (orr_physics.h:
 // AnchorState).  Same source; its own instantiations (one wave per SIMD whatever the batch size: an optional physics feature, not the
 // measured path), so that the default kernels carry nothing of it.
@@ -145,9 +142,9 @@ constexpr int step_wpb() { return MODE == 0 && WPE == 1 ? ORR_WPB : 1; }
 // episode's clip from the robot type's clip set (reset_robot<true>), the episode log also records the clip of the ending episode, and
 // a robot whose motion time has reached the record's CLIP_CHANGE_TIME switches to a newly drawn clip mid-episode (orr_set_clip_switch)
 template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false>
-__global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
-  ORR_PROLOGUE_W((step_wpb<MODE, WPE>()));
+  ORR_PROLOGUE();
   const bool valid = in_range;
   const orr_config& c = P.cfg;
   PT_INIT();
@@ -281,7 +278,7 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
   // plain age order - the oldest wave of a SIMD runs at nearly a lone wave's pace, the next one moves up when it ends - is the better
   // pipeline (12288 robots = 3 rounds: 0.4925 -> 0.4693 ms without the turns; 16384 / 32768 robots = 4 / 8 rounds: 0.5767 / 1.103 ms with
   // them against 0.5847 / 1.109 without; profiles/r04_ab34_large.log)
-  const bool prio_turns = WPE == 2 && ((((unsigned)gridDim.x * (unsigned)step_wpb<MODE, WPE>() + (unsigned)(P.simds > 0 ? P.simds : 1) - 1u) /
+  const bool prio_turns = WPE == 2 && ((((unsigned)gridDim.x + (unsigned)(P.simds > 0 ? P.simds : 1) - 1u) /
                                         (unsigned)(P.simds > 0 ? P.simds : 1)) & 1u) == 0u;
   // What the PD law of a sub-step reads - the delayed angle of the lane's motor (control observation), the joint's true angle and rate -
   // is produced at the END of the previous sub-step: the control-observation word by this very lane, angle and rate by the integration
@@ -543,15 +540,14 @@ __global__ __launch_bounds__((MODE == 0 && WPE == 1 ? 64 * ORR_WPB : 64)) __attr
       atomicExch((unsigned long long*)&P.counters[ORR_CNT_TICKET], 0ull);   // every other wave's update came before this wave's
     }
   }
-  PT_TIMELINE((long long)((fin_mask & 1ull) | ((fin_mask >> 15) & 2ull) | ((fin_mask >> 30) & 4ull) | ((fin_mask >> 45) & 8ull)));   // one bit per robot of the wave
-  WT_STORE((long long)((fin_mask & 1ull) | ((fin_mask >> 15) & 2ull) | ((fin_mask >> 30) & 4ull) | ((fin_mask >> 45) & 8ull)));
+  WT_STORE((long long)((fin_mask & 1ull) | ((fin_mask >> 15) & 2ull) | ((fin_mask >> 30) & 4ull) | ((fin_mask >> 45) & 8ull)));   // one bit per robot of the wave
 }
 
 
 // ================================================================================================
 // launchers
 // ================================================================================================
-// One launcher per kernel template: `waves` = robots / kRPW rounded up, step_wpb() of them to a workgroup (1 in the shipped build).
+// One launcher per kernel template: `waves` = robots / kRPW rounded up, each a workgroup of its own.
 // Each instantiation belongs to ONE unit, which instantiates it explicitly (`template orr::StepLaunch orr::launch_step<...>;`, in the
 // order its kernels are to have in the code object); the `extern template` declarations below keep every other unit from
 // instantiating it, kernel included.
@@ -563,9 +559,7 @@ using ResetLaunch = hipError_t(const KParams& P, int waves, hipStream_t stream, 
 template <int MODE, int WPE, bool ANCHOR, bool CLIPS>
 hipError_t launch_step(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done, int nsub,
                        const ReplayArgs& rp) {
-  constexpr int wpb = step_wpb<MODE, WPE>();
-  hipLaunchKernelGGL((orr_step_kernel<MODE, WPE, ANCHOR, CLIPS>), dim3((waves + wpb - 1) / wpb), dim3(64 * wpb), 0, stream, P, actions, obs, reward,
-                     done, nsub, rp);
+  hipLaunchKernelGGL((orr_step_kernel<MODE, WPE, ANCHOR, CLIPS>), dim3(waves), dim3(64), 0, stream, P, actions, obs, reward, done, nsub, rp);
   return hipGetLastError();
 }
 template <bool CLIPS>

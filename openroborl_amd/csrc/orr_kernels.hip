@@ -374,6 +374,7 @@ static KParams make_params(const orr_handle* h) {
   P.anchor_on = h->anchor_types != 0;
 #ifdef ORR_WAVE_TIMELINE
   P.wave_times = g_wave_times_dev;
+  P.wave_times_cap = g_wave_times_cap;
 #endif
   return P;
 }
@@ -515,13 +516,15 @@ int orr_debug_dual_contact(unsigned long long* out8, int reset) {
 }
 #endif
 #ifdef ORR_WAVE_TIMELINE
-// development aid: per-wave timeline of the last step launch of either variant (4 words per wave: realtime start / end in 100 MHz ticks,
+// development aid (-DORR_WAVE_TIMELINE, which -DORR_PHASE_TIMERS implies): per-wave timeline of the last step launch of any variant (4 words per wave: realtime start / end in 100 MHz ticks,
 // shader cycles, bits 0..7 mask of the robots that finished an episode | bits 8..39 HW_ID (wave slot, SIMD, CU, SE) | bits 40..43 XCC id).
 // The first call (waves > 0, out may be null) allocates the device buffer; launches after it are recorded.
 int orr_debug_wave_times(long long* out, int waves) {
   HIPCHK(hipDeviceSynchronize(), "orr_debug_wave_times: sync");
   if (waves > g_wave_times_cap) {
+    g_wave_times_cap = 0;      // nothing is recorded until the new buffer stands
     if (g_wave_times_dev) HIPCHK(hipFree(g_wave_times_dev), "orr_debug_wave_times: free");
+    g_wave_times_dev = nullptr;
     HIPCHK(hipMalloc((void**)&g_wave_times_dev, (size_t)waves * 4 * sizeof(long long)), "orr_debug_wave_times: alloc");
     HIPCHK(hipMemset(g_wave_times_dev, 0, (size_t)waves * 4 * sizeof(long long)), "orr_debug_wave_times: clear");
     g_wave_times_cap = waves;
@@ -542,16 +545,10 @@ int orr_debug_phase_cycles(long long* out40, int reset) {
   }
   return 0;
 }
-// development aid: per-wave timeline of the last step launch (4 words per wave: realtime start / end in 100 MHz ticks, shader cycles,
-// bits 0..7 mask of the robots that finished an episode, bits 8..39 HW_ID register of the wave (SIMD / CU / SE), bits 40..43 XCC id)
+// development aid: the phase totals (kPhaseSlots words) of each of the first 2048 waves of the last step launch of the main unit's kernel
 int orr_debug_wave_phases(long long* out, int waves) {
   HIPCHK(hipDeviceSynchronize(), "orr_debug_wave_phases: sync");
   HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_phases), (size_t)waves * 40 * sizeof(long long)), "orr_debug_wave_phases: read");
-  return 0;
-}
-int orr_debug_wave_timeline(long long* out, int waves) {
-  HIPCHK(hipDeviceSynchronize(), "orr_debug_wave_timeline: sync");
-  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_timeline), (size_t)waves * 4 * sizeof(long long)), "orr_debug_wave_timeline: read");
   return 0;
 }
 #endif

@@ -145,12 +145,12 @@ def test_headers_are_plain_c():
 
 
 @pytest.mark.parametrize("defs", [
-    ["-DORR_GENERIC_PGS"], ["-DORR_PHASE_TIMERS"], ["-DORR_COUNT_DUAL_CONTACT"], ["-DORR_WPB=2"], ["-DORR_WAVE_TIMELINE"], ["-DORR_WAVES_PER_EU=2"]])
+    ["-DORR_GENERIC_PGS"], ["-DORR_PHASE_TIMERS"], ["-DORR_COUNT_DUAL_CONTACT"], ["-DORR_WAVE_TIMELINE"], ["-DORR_WAVES_PER_EU=2"]])
 def test_the_kernel_tuning_knobs_still_compile(defs):
     """What is left of the step kernel's preprocessor switches after round 6's clean-up (the A/B alternatives that lost are gone from the
     source; their measurements stay in HISTORY.md / profiles/r04_ab*): the development aids - the readable twin of the hand-scheduled PGS
-    block, the phase timers, the dual-contact counter, the wave timeline - and the two launch-shape experiments the tools still drive
-    (tools/wave_pairing.py).  Each goes through the device compiler's front end here (syntax + templates + static_asserts; well under a
+    block, the phase timers (which imply the wave timeline), the dual-contact counter, the wave timeline on its own - and the one
+    launch-shape experiment a tool still drives (-DORR_WAVES_PER_EU=2: tools/wave_pairing.py).  Each goes through the device compiler's front end here (syntax + templates + static_asserts; well under a
     second each), in all four translation units of the env kernels."""
     import subprocess
     base = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + ["--cuda-device-only", "-fsyntax-only", "-Wno-unused-command-line-argument"]
@@ -263,10 +263,12 @@ def undefined_project_symbols(lib_path):
     return [l.split()[-1] for l in out.splitlines() if l.strip() and ("orr" in l.split()[-1] or "launch_" in l.split()[-1])]
 
 
-@pytest.mark.parametrize("define", ["-DORR_WAVES_PER_EU=2", "-DORR_WPB=2"])
+@pytest.mark.parametrize("define", ["-DORR_WAVES_PER_EU=2", "-DORR_PHASE_TIMERS"])
 def test_the_launch_shape_builds_still_link(tmp_path, define):
-    """The two launch-shape experiments (tools/wave_pairing.py) as whole builds: every unit instantiates its launchers explicitly, and
-    with -DORR_WAVES_PER_EU=2 the main unit's default step IS the two-wave unit's instantiation - both emit it, and that has to link."""
+    """The development builds that change what the units share, as whole builds: every unit instantiates its launchers explicitly, and
+    with -DORR_WAVES_PER_EU=2 (tools/wave_pairing.py) the main unit's default step IS the two-wave unit's instantiation - both emit it,
+    and that has to link.  -DORR_PHASE_TIMERS keeps its timers to the main unit but adds the wave timeline's fields to KParams, the
+    by-value argument that the main unit builds and every unit's kernels take."""
     out = str(tmp_path / "lib_shape.so")
     assert _lib.build(out_path=out, extra_flags=[define]) == out and os.path.getsize(out) > 0
     assert undefined_project_symbols(out) == []

@@ -6,15 +6,12 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
-LIB = os.path.join(ROOT, "openroborl_amd", "libopenroborl_phase_timers.so")
-from openroborl_amd import _lib as _build  # noqa: E402
-_build.build(out_path=LIB, extra_flags=["-DORR_PHASE_TIMERS"])
-os.environ["ORR_LIB_PATH"] = LIB
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import dev_build  # noqa: E402
+from dev_build import PHASE_NAMES as NAMES  # noqa: E402
+L = dev_build.load(*dev_build.PHASE_TIMERS)
 
 import torch  # noqa: E402
-from openroborl_amd import _lib  # noqa: E402
 from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
@@ -27,12 +24,7 @@ const = torch.tensor(m["motor_offset"], dtype=torch.float32, device=dev) * mdir 
 gen = torch.Generator(device=dev).manual_seed(1)
 pool = torch.randn(64, N, 12, generator=gen, device=dev) * 0.125 - const
 obs = env.reset()
-L = _lib.load()
-L.orr_debug_wave_timeline.argtypes = [C.POINTER(C.c_longlong), C.c_int]
-L.orr_debug_wave_phases.argtypes = [C.POINTER(C.c_longlong), C.c_int]
-NAMES = ["load+leg consts", "set_act/filter", "substep control", "leg dynamics", "fall proxies", "row setup", "row response",
-         "Delassus columns", "PGS sweeps", "du+integrate", "receive_obs (ring)", "ctrl_obs+sensors", "reward+ref update",
-         "termination+obs", "episode end/reset", "store"]
+dev_build.wave_rows(L, W)          # allocate: the launches from here on are recorded
 
 
 def step(k):
@@ -42,24 +34,20 @@ def step(k):
 
 for k in range(3000):
     step(k)
-buf = (C.c_longlong * (4 * W))()
 pbuf = (C.c_longlong * (40 * W))()
 phases = []
 dur, cyc, start, xcc, cu, se, simd, reset = [], [], [], [], [], [], [], []
 for k in range(n):
     step(3000 + k)
-    L.orr_debug_wave_timeline(buf, W)
+    a = dev_build.wave_rows(L, W)
     L.orr_debug_wave_phases(pbuf, W)
     phases.append(np.frombuffer(pbuf, dtype=np.int64).reshape(W, 40)[:, :16].astype(np.float64).copy())
-    a = np.frombuffer(buf, dtype=np.int64).reshape(W, 4).copy()
     t0 = a[:, 0].min()
     start.append((a[:, 0] - t0) / 100.0)
     dur.append((a[:, 1] - a[:, 0]) / 100.0)
     cyc.append(a[:, 2].astype(np.float64))
-    hw = (a[:, 3] >> 8) & 0xFFFFFFFF            # HW_REG_HW_ID: wave 3:0, simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13 (gfx9 layout)
-    simd.append((hw >> 4) & 3); cu.append((hw >> 8) & 15); se.append((hw >> 13) & 7)
-    xcc.append((a[:, 3] >> 40) & 15)
-    reset.append((a[:, 3] & 0xFF) != 0)
+    fin, x_, se_, _, cu_, simd_ = dev_build.decode_slot(a)
+    simd.append(simd_); cu.append(cu_); se.append(se_); xcc.append(x_); reset.append(fin != 0)
 dur, cyc, start, xcc, cu, se, simd, reset = (np.array(x) for x in (dur, cyc, start, xcc, cu, se, simd, reset))
 ok = ~reset
 print("launches %d; wave duration (us): mean %.2f, p50 %.2f, p99 %.2f, max %.2f; launch length mean %.2f; without-reset waves only below"

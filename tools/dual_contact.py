@@ -14,22 +14,16 @@ import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-LIB = os.path.join(ROOT, "openroborl_amd", "libopenroborl_dual_contact.so")
-from openroborl_amd import _lib as _build  # noqa: E402  (build only; the library is loaded below)
-_build.build(out_path=LIB, extra_flags=["-DORR_COUNT_DUAL_CONTACT"])
-os.environ["ORR_LIB_PATH"] = LIB
-os.environ["ORR_STEP_WAVES_PER_EU"] = "1"      # the counters live in the one-wave kernel
+import dev_build
+from dev_build import ROOT
+L = dev_build.load("dual_contact", ["-DORR_COUNT_DUAL_CONTACT"], step_waves_per_eu=1)      # the counters live in the one-wave kernel
 
 import torch  # noqa: E402
-from openroborl_amd import _lib, policy as polmod  # noqa: E402
+from openroborl_amd import policy as polmod  # noqa: E402
 from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
 
 STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 TRAIN_ITERS = int(sys.argv[2]) if len(sys.argv) > 2 else 300
-L = _lib.load()
-L.orr_debug_dual_contact.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
 buf = (C.c_ulonglong * 8)()
 NAMES = ("leg_substeps", "with_contact_row", "both_within_margin", "both_penetrating", "shank_only_within_margin", "row_at_shank")
 rows = []

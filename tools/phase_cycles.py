@@ -4,31 +4,15 @@ usage (GPU box):  python tools/phase_cycles.py [steps]
 Builds a second library with -DORR_PHASE_TIMERS next to the shipped one and runs the bench workload through it.
 """
 import ctypes as C
-import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-LIB = os.path.join(ROOT, "openroborl_amd", "libopenroborl_phase_timers.so")
-from openroborl_amd import _lib as _build  # noqa: E402  (build only; the library is loaded below)
-_build.build(out_path=LIB, extra_flags=["-DORR_PHASE_TIMERS"])
-os.environ["ORR_LIB_PATH"] = LIB
+import torch
 
-import torch  # noqa: E402
-from openroborl_amd import _lib  # noqa: E402
-from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
+import dev_build
 
-NAMES = ["load+leg consts", "set_act/filter", "substep control", "leg dynamics", "fall proxies", "row setup", "row response",
-         "Delassus columns", "PGS sweeps", "du+integrate", "receive_obs (ring)", "ctrl_obs+sensors", "reward+ref update",
-         "termination+obs", "episode end/reset", "store"]
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-env = VecQuadrupedEnv(task_name="imitation_learning_laikago", num_robot=4096, seed=0)
-env.reset()
-g = torch.Generator().manual_seed(0)
-act = (torch.randn(4096, 12, generator=g) * 0.1).to(env.device)
-L = _lib.load()
-L.orr_debug_phase_cycles.argtypes = [C.POINTER(C.c_longlong), C.c_int]
+L = dev_build.load(*dev_build.PHASE_TIMERS)
+env, act = dev_build.laikago_env(4096)
 buf = (C.c_longlong * 40)()
 for _ in range(50):
     env.step(act)
@@ -42,7 +26,7 @@ for _ in range(steps):
 L.orr_debug_phase_cycles(buf, 1)
 tot = float(sum(buf[:16]))
 print("cycles per env step (one wave, %d steps): %.0f" % (steps, tot / steps))
-for n, v in zip(NAMES, buf[:16]):
+for n, v in zip(dev_build.PHASE_NAMES, buf[:16]):
     print("  %-22s %9.0f  %5.1f%%" % (n, v / steps, 100.0 * v / tot))
 print("steps with a reset in the instrumented wave: %d of %d (robot resets: %s); cycles per such step in 'episode end/reset': %.0f"
       % (events, steps, dones.tolist(), buf[14] / max(events, 1)))

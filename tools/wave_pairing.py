@@ -7,46 +7,28 @@ else ran on ITS SIMD (same XCC, SE, CU, SIMD) while it ran: alone the whole time
 its life.  If co-resident waves overlapped perfectly a paired wave would take as long as a lone one; if VALU issue were the only
 resource and already saturated by one wave, twice as long.
 """
-import ctypes as C
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import dev_build
+
 robots = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
 launches = int(sys.argv[2]) if len(sys.argv) > 2 else 30
 wpe = int(sys.argv[3]) if len(sys.argv) > 3 else 2
-LIB = os.path.join(ROOT, "openroborl_amd", "libopenroborl_pairing_w%d.so" % wpe)
-from openroborl_amd import _lib as _build  # noqa: E402
-_build.build(out_path=LIB, extra_flags=["-DORR_PHASE_TIMERS", "-DORR_WAVES_PER_EU=%d" % wpe])
-os.environ["ORR_LIB_PATH"] = LIB
-os.environ["ORR_STEP_WAVES_PER_EU"] = "1"     # = the main translation unit's kernel, which this build compiled for `wpe` waves per SIMD + timers
-
-import torch  # noqa: E402
-from openroborl_amd import _lib  # noqa: E402
-from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
-
-env = VecQuadrupedEnv(task_name="imitation_learning_laikago", num_robot=robots, seed=0)
-env.reset()
-g = torch.Generator().manual_seed(0)
-act = (torch.randn(robots, 12, generator=g) * 0.1).to(env.device)
-L = _lib.load()
-L.orr_debug_wave_timeline.argtypes = [C.POINTER(C.c_longlong), C.c_int]
+# ORR_STEP_WAVES_PER_EU=1 = the main translation unit's kernel, which this build compiled for `wpe` waves per SIMD + timers
+L = dev_build.load("pairing_w%d" % wpe, ["-DORR_PHASE_TIMERS", "-DORR_WAVES_PER_EU=%d" % wpe], step_waves_per_eu=1)
+env, act = dev_build.laikago_env(robots)
+W = min(robots // 4, 2048)
+dev_build.wave_rows(L, W)          # allocate: the launches from here on are recorded
 for _ in range(200):
     env.step(act)
-W = min(robots // 4, 2048)
-buf = (C.c_longlong * (4 * W))()
 dur_alone, dur_paired, frac_all, launch_len, cyc_alone, cyc_paired, simd_load = [], [], [], [], [], [], []
 for _ in range(launches):
     env.step(act)
-    L.orr_debug_wave_timeline(buf, W)
-    a = np.frombuffer(buf, dtype=np.int64).reshape(W, 4).copy()
+    a = dev_build.wave_rows(L, W)
     start, end, cyc = a[:, 0].astype(np.float64) / 100.0, a[:, 1].astype(np.float64) / 100.0, a[:, 2].astype(np.float64)
-    hw = (a[:, 3] >> 8) & 0xFFFFFFFF
-    xcc = (a[:, 3] >> 40) & 0xF
-    simd, cu, sh, se = (hw >> 4) & 3, (hw >> 8) & 0xF, (hw >> 12) & 1, (hw >> 13) & 7
+    _, xcc, se, sh, cu, simd = dev_build.decode_slot(a)
     key = (((xcc * 8 + se) * 2 + sh) * 16 + cu) * 4 + simd
     launch_len.append(end.max() - start.min())
     order = np.argsort(key, kind="stable")

@@ -6,45 +6,27 @@ Every wave of the instrumented build keeps its own per-phase shader-clock totals
 (the launch ends with its slowest wave: tools/wave_timeline.py).
 """
 import ctypes as C
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-LIB = os.path.join(ROOT, "openroborl_amd", "libopenroborl_phase_timers.so")
-from openroborl_amd import _lib as _build  # noqa: E402
-_build.build(out_path=LIB, extra_flags=["-DORR_PHASE_TIMERS"])
-os.environ["ORR_LIB_PATH"] = LIB
+import dev_build
+from dev_build import PHASE_NAMES as NAMES
 
-import torch  # noqa: E402
-from openroborl_amd import _lib  # noqa: E402
-from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
-
-NAMES = ["load+leg consts", "set_act/filter", "substep control", "leg dynamics", "fall proxies", "row setup", "row response",
-         "Delassus columns", "PGS sweeps", "du+integrate", "receive_obs (ring)", "ctrl_obs+sensors", "reward+ref update",
-         "termination+obs", "episode end/reset", "store"]
 launches = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 W = 1024
-env = VecQuadrupedEnv(task_name="imitation_learning_laikago", num_robot=4 * W, seed=0)
-env.reset()
-g = torch.Generator().manual_seed(0)
-act = (torch.randn(4 * W, 12, generator=g) * 0.1).to(env.device)
-L = _lib.load()
-L.orr_debug_wave_phases.argtypes = [C.POINTER(C.c_longlong), C.c_int]
-L.orr_debug_wave_timeline.argtypes = [C.POINTER(C.c_longlong), C.c_int]
+L = dev_build.load(*dev_build.PHASE_TIMERS)
+env, act = dev_build.laikago_env(4 * W)
+dev_build.wave_rows(L, W)          # allocate: the launches from here on are recorded
 for _ in range(300):
     env.step(act)
-pb, tb = (C.c_longlong * (40 * W))(), (C.c_longlong * (4 * W))()
+pb = (C.c_longlong * (40 * W))()
 gap_all, gap_nr, med_all, tot_rows, lim_rows = [], [], [], [], []
 for _ in range(launches):
     env.step(act)
     L.orr_debug_wave_phases(pb, W)
-    L.orr_debug_wave_timeline(tb, W)
     ph = np.frombuffer(pb, dtype=np.int64).reshape(W, 40).astype(np.float64).copy()
-    tl = np.frombuffer(tb, dtype=np.int64).reshape(W, 4).copy()
-    reset = (tl[:, 3] & 0xFF) != 0
+    reset = dev_build.decode_slot(dev_build.wave_rows(L, W))[0] != 0
     tot = ph[:, :16].sum(axis=1)
     order = np.argsort(tot)
     slow = order[-W // 50:]

@@ -9,24 +9,18 @@ nothing else instrumented.  Drives the env like bench.py (stress actions) and re
     (the partner already gone) and at the start (the partner not yet there)
   * which SIMDs end last: their waves' durations, reset flags, and how the two waves of a pair compare (older / younger)
 """
-import ctypes as C
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import dev_build
+
 config = sys.argv[1] if len(sys.argv) > 1 else "mixed8192"
 launches = int(sys.argv[2]) if len(sys.argv) > 2 else 60
-LIB = os.path.join(ROOT, "openroborl_amd", "libopenroborl_wave_times.so")
-from openroborl_amd import _lib as _build  # noqa: E402
-_build.build(out_path=LIB, extra_flags=["-DORR_WAVE_TIMELINE"])
-os.environ["ORR_LIB_PATH"] = LIB
+L = dev_build.load("wave_times", ["-DORR_WAVE_TIMELINE"])
 
 import torch  # noqa: E402
-import bench  # noqa: E402
-from openroborl_amd import _lib  # noqa: E402
+import bench  # noqa: E402  (the repository root is on sys.path since dev_build's import)
 from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
 
 kw, n, _ = bench.CONFIGS[config]
@@ -34,10 +28,8 @@ if len(sys.argv) > 3:
     n = int(sys.argv[3])
 env = VecQuadrupedEnv(num_robot=n, seed=0, **kw)
 obs = env.reset()
-L = _lib.load()
-L.orr_debug_wave_times.argtypes = [C.POINTER(C.c_longlong), C.c_int]
 W = (n + 3) // 4
-L.orr_debug_wave_times(None, W)                       # allocate: the launches from here on are recorded
+dev_build.wave_rows(L, W)                             # allocate: the launches from here on are recorded
 gen = torch.Generator(device=env.device).manual_seed(0)
 noise = 0.125 * torch.randn(16, n, 12, device=env.device, generator=gen)
 act = torch.empty(n, 12, device=env.device)
@@ -51,7 +43,6 @@ def step(k):
 
 for k in range(400):
     step(k)
-buf = (C.c_longlong * (4 * W))()
 acc = {}
 
 
@@ -62,15 +53,12 @@ def add(name, v):
 last_simd_rows = []
 for k in range(launches):
     step(400 + k)
-    L.orr_debug_wave_times(buf, W)
-    a = np.frombuffer(buf, dtype=np.int64).reshape(W, 4).copy()
+    a = dev_build.wave_rows(L, W)
     start, end, cyc = a[:, 0] / 100.0, a[:, 1] / 100.0, a[:, 2].astype(np.float64)      # us
     t0 = start.min()
     start, end = start - t0, end - t0
-    reset = (a[:, 3] & 0xFF) != 0
-    hw = (a[:, 3] >> 8) & 0xFFFFFFFF
-    xcc = (a[:, 3] >> 40) & 0xF
-    simd, cu, sh, se = (hw >> 4) & 3, (hw >> 8) & 0xF, (hw >> 12) & 1, (hw >> 13) & 7
+    fin, xcc, se, sh, cu, simd = dev_build.decode_slot(a)
+    reset = fin != 0
     key = (((xcc * 8 + se) * 2 + sh) * 16 + cu) * 4 + simd
     dur = end - start
     add("launch length (last end - first start), us", end.max())
