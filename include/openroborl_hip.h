@@ -279,6 +279,33 @@ int32_t orr_bind_clip_log(orr_handle* h, int32_t* clip_log_dev);
  * this (orr_set_clip_set); the parity replays (orr_debug_replay_step / _reset) run them while some type has a switch range. */
 int32_t orr_set_clip_switch(orr_handle* h, int32_t robot_type, float tmin, float tmax);
 
+/* task noise of the handle (ImitationTask's perturb_init_state_prob with _apply_state_perturb, and tar_obs_noise[0]: imitation_task.py:
+ * 192-197, 273-275, 778-793, 1195-1243).  A task option, not a robot-type one: one setting per handle, read from the next launch on. */
+typedef struct orr_task_noise {
+  float perturb_init_state_prob;   /* 0 = off */
+  float root_pos_std, root_rot_std, joint_pose_std, root_vel_std, root_ang_vel_std, joint_vel_std;  /* the reference's six:
+                                      0.025, 0.025 pi, 0.05 pi, 0.1, 0.05 pi, 0.05 pi (imitation_task.py:1201-1206) */
+  float tar_heading_std;           /* tar_obs_noise[0]; 0 = off */
+} orr_task_noise;
+/* noise_host NULL = all off.  Refused: NaN, a probability outside [0, 1], a negative or infinite standard deviation (the message names
+ * the field), friction anchors on the handle; a rejected call changes nothing.  While perturb_init_state_prob and tar_heading_std are
+ * both 0 the handle runs exactly the kernels it runs without this call; otherwise orr_step, orr_reset and the parity replays launch the
+ * noise variants (the clip-set variants + noise: one wave per SIMD at any batch size, refused together with friction anchors; a type
+ * without a clip set keeps its CLIP_ID).  Draw rule, on the episode's (seed, robot index, episode) stream u_d (d = 4 * Philox block +
+ * word; draws 0..29 and the clip-switch blocks 8 + s keep their meaning; in the parity replays these blocks always come from Philox):
+ *   normal pair of two uniforms (ua, ub):  r = sqrt(-2 ln(1 - ua)),  z0 = r cos(2 pi ub),  z1 = r sin(2 pi ub);
+ *   reset: U(k) = word k of blocks 0x20000000 .. 0x20000008 (k = 0..35).  The robot is perturbed iff U(0) < perturb_init_state_prob.
+ *     Axis a_i = -1 + 2 U(i), i = 1..3, normalised (squared norm below 1e-30: no rotation).  Pair j = 0..15 of (U(4 + 2j), U(5 + 2j))
+ *     gives z_2j, z_2j+1, assigned in the reference's call order: z0 z1 root position x y, z2 rotation angle, z3..z14 joint angles,
+ *     z15 z16 root velocity x y, z17..z19 root angular velocity, z20..z31 joint rates.  What the reset writes into POS / QUAT / LINVEL /
+ *     ANGVEL / Q / QD is the reference state + std * z, the orientation quaternion_about_axis(root_rot_std z2, a) (x) reference rotation
+ *     (not renormalised); REF_POSE, REF_VEL, the origin and PREV_PHASE stay the unperturbed ones;
+ *   target observation: block 0x30000000 + i, i = 0 for the observation of a reset of that episode (the auto-reset inside a step
+ *     included), i = 1 + s for the step whose env-step counter before the step is s: heading += tar_heading_std * z0 of the pair
+ *     (word 0, word 1) before the target frames are expressed in it.  Nothing but the observation depends on it. */
+int32_t orr_set_task_noise(orr_handle* h, const orr_task_noise* noise_host);
+int32_t orr_sizeof_task_noise(void);
+
 /* replaces WrapperEnv.reset (wrapper_env.py:87-107): mask_dev NULL = all robots; obs_dev [N,160]
  * (rows of robots that are not reset are left untouched). */
 int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream);

@@ -102,6 +102,12 @@ class OrrModel(C.Structure):
     ]
 
 
+class OrrTaskNoise(C.Structure):
+    """include/openroborl_hip.h: orr_task_noise (orr_set_task_noise)."""
+    _fields_ = [(n, C.c_float) for n in ("perturb_init_state_prob", "root_pos_std", "root_rot_std", "joint_pose_std", "root_vel_std",
+                                         "root_ang_vel_std", "joint_vel_std", "tar_heading_std")]
+
+
 def fill(struct, name, values):
     """Assign a (nested) python sequence / scalar to a ctypes struct field."""
     import numpy as np

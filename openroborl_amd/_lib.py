@@ -16,6 +16,7 @@ SRC = os.path.join(CSRC, "orr_kernels.hip")                      # the default e
 SRC_W2 = os.path.join(CSRC, "orr_kernels_w2.hip")                # the two-waves-per-SIMD step kernel: its own translation unit + flags
 SRC_ANCHOR = os.path.join(CSRC, "orr_kernels_anchor.hip")        # the friction-anchor variants of the step kernel (ABI v5): their own unit
 SRC_MULTICLIP = os.path.join(CSRC, "orr_kernels_multiclip.hip")  # the clip-set variants of the step and reset kernels: their own unit
+SRC_NOISE = os.path.join(CSRC, "orr_kernels_noise.hip")          # the task-noise variants (clip sets + perturbed initial states + heading noise)
 SRC_POLICY = os.path.join(CSRC, "orr_policy.hip")
 SRC_LEARNER = os.path.join(CSRC, "orr_learner.hip")              # the non-GEMM part of the PPO update (include/openroborl_learner.h)
 # what the library is built from = what the stale-library check hashes: every source and header under csrc/ + the public headers
@@ -60,11 +61,18 @@ UNITS = [("env", SRC, HIPCC_FLAGS, True),
          ("policy", SRC_POLICY, HIPCC_FLAGS_PLAIN, False),
          ("learner", SRC_LEARNER, HIPCC_FLAGS_PLAIN, False)]
 ENV_UNITS = UNITS[:4]      # the units of the env kernels (csrc/orr_env_kernels.h): the ones that tuning defines and extra_flags reach
+# The fifth unit of the env kernels, the task-noise variants (orr_set_task_noise): the main unit's flags, its own unit like "anchor".  A
+# table of its own behind the two above, whose lengths and order tests and tools address by position (tests/test_cpu_host.py,
+# tools/isa_lines.py); build() compiles ALL_UNITS, and tuning defines and extra_flags reach ALL_ENV_UNITS (every unit has to see the
+# same KParams)
+NOISE_UNITS = [("noise", SRC_NOISE, HIPCC_FLAGS, False)]
+ALL_UNITS = UNITS + NOISE_UNITS
+ALL_ENV_UNITS = ENV_UNITS + NOISE_UNITS
 
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
     "orr_layout_offset", "orr_layout_size", "orr_layout_is_int", "orr_sizeof_config", "orr_sizeof_model",
-    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_bind_clip_log", "orr_bind", "orr_reset", "orr_step",
+    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_bind_clip_log", "orr_bind", "orr_reset", "orr_step",
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
@@ -144,12 +152,12 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
             tag = ".%d" % os.getpid()
             tmp_so = out_path + tag + ".tmp"
             objs, cmds = [], []
-            for unit in UNITS:
+            for unit in ALL_UNITS:
                 name, src, flags, hashed = unit
                 flags = [f for f in flags if f != "-shared"] + ["-c"]
                 if hashed:
                     flags.append('-DORR_SOURCE_HASH="%s"' % source_hash(extra_flags))
-                if unit in ENV_UNITS:
+                if unit in ALL_ENV_UNITS:
                     flags += tuning_defines() + list(extra_flags)
                 objs.append(os.path.splitext(src)[0] + tag + ".o")
                 cmds.append([HIPCC] + flags + ["-o", objs[-1], src])
@@ -228,6 +236,9 @@ def load():
     L.orr_set_clip_set.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
     L.orr_set_clip_switch.restype = C.c_int32
     L.orr_set_clip_switch.argtypes = [vp, C.c_int32, C.c_float, C.c_float]
+    L.orr_set_task_noise.restype = C.c_int32
+    L.orr_set_task_noise.argtypes = [vp, C.POINTER(_abi.OrrTaskNoise)]
+    L.orr_sizeof_task_noise.restype = C.c_int32
     L.orr_bind_clip_log.restype = C.c_int32
     L.orr_bind_clip_log.argtypes = [vp, vp]
     L.orr_bind.restype = C.c_int32
@@ -278,7 +289,8 @@ def load():
     L.orr_adam_step.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp]
     if L.orr_abi_version() != _abi.ABI_VERSION:
         raise RuntimeError("libopenroborl_hip.so ABI version mismatch")
-    if L.orr_sizeof_config() != C.sizeof(_abi.OrrConfig) or L.orr_sizeof_model() != C.sizeof(_abi.OrrModel):
+    if (L.orr_sizeof_config() != C.sizeof(_abi.OrrConfig) or L.orr_sizeof_model() != C.sizeof(_abi.OrrModel)
+            or L.orr_sizeof_task_noise() != C.sizeof(_abi.OrrTaskNoise)):
         raise RuntimeError("ctypes struct layout does not match include/openroborl_hip.h")
     _lib = L
     return L

@@ -112,7 +112,10 @@ struct DevTables {
   int* clip_log;                                      // orr_bind_clip_log: clip of each logged episode (row = episode-log slot), or NULL
   // mid-episode clip switching (orr_set_clip_switch), read by the multi-clip variants only.  APPENDED like the clip sets
   float clip_switch[ORR_MAX_ROBOT_TYPES][2];          // (tmin, tmax) of a type's switch interval; (+inf, +inf) = never
+  // task noise of the handle (orr_set_task_noise), read by the noise variants only (orr_kernels_noise.hip).  APPENDED likewise
+  orr_task_noise noise;                               // all zero = off
 };
+static_assert(sizeof(orr_task_noise) == 32, "the noise variants read it as eight words");
 
 // Replay inputs of the parity entry points orr_debug_replay_reset / orr_debug_replay_step (kernel MODE 2): the scripted states,
 // link positions, contact flags and random draws recorded while the reference's own Python was driven with a scripted pybullet
@@ -504,6 +507,52 @@ __device__ __forceinline__ void philox_block(unsigned long long seed, uint32_t r
   }
   u[0] = (float)(c0 >> 8) * (1.0f / 16777216.0f); u[1] = (float)(c1 >> 8) * (1.0f / 16777216.0f);
   u[2] = (float)(c2 >> 8) * (1.0f / 16777216.0f); u[3] = (float)(c3 >> 8) * (1.0f / 16777216.0f);
+}
+
+// A pair of standard normals from two of the stream's 24-bit uniforms (ua, ub = m / 2^24, either can be exactly 0): Box-Muller,
+//   r = sqrt(-2 ln(1 - ua)),  z0 = r cos(2 pi ub),  z1 = r sin(2 pi ub),
+// to |z - z_float64| <= 1e-6 for EVERY ua (the bound the task noise needs: orr_task.h; 5.1e-7 in a host emulation of this code and 7.7e-7
+// provable, profiles/init_noise.txt; measured by tests/test_gpu_init_noise.py).  1 - ua is exact and lies in [2^-24, 1], so r is finite and at most 5.77.  What float32 cannot do here:
+// r reaches 5.77, where its own rounding is 2.4e-7 and that of the product another 2.4e-7, so a 1-ulp logarithm (v_log_f32, which also
+// loses RELATIVE accuracy next to 1, i.e. for small ua), a 1-ulp square root and a float32 2 pi ub (3.7e-7 of angle at 5.77) each take
+// the rest of the budget on their own.  So: the radius in float64 - ln(1 - ua) = e ln 2 + 2 atanh((m - 1) / (m + 1)) with the
+// mantissa m in [sqrt 1/2, sqrt 2), seven terms of the series (|s| <= 0.172: 1e-12), reciprocal and square root from the hardware's
+// float32 seeds (v_rcp_f32, v_rsq_f32) and one Newton step each - and the angle reduced EXACTLY: ub - k / 4 (k = the quarter turn) is
+// a multiple of 2^-24 below 1/8, its product with a two-part 2 pi goes to joint_sincos as |a| <= pi / 4, the quarter turns are
+// applied to the result.  What is left is joint_sincos' own error (6e-8) times r and the final rounding.  No libm, no branch; a few
+// dozen f64 instructions, once per reset (sixteen lanes, a pair each) or once per target observation.
+__device__ __forceinline__ void normal_pair(float ua, float ub, float* z0, float* z1) {
+  const int wb = __float_as_int(1.0f - ua);                      // exact: 1 - ua = (2^24 - m) / 2^24, a normal float in [2^-24, 1]
+  float mf = __int_as_float((wb & 0x007FFFFF) | 0x3F800000);     // mantissa in [1, 2)
+  int e = (wb >> 23) - 127;
+  const bool up = mf > 1.41421354f;
+  mf = up ? 0.5f * mf : mf;
+  e = up ? e + 1 : e;
+  const double m = (double)mf, den = m + 1.0;
+  double y = (double)__builtin_amdgcn_rcpf((float)den);          // 1 / (m + 1): 1e-7, one Newton step -> 1e-14
+  y = y * (2.0 - den * y);
+  const double s = (m - 1.0) * y, s2 = s * s;
+  double p = 1.0 / 13.0;
+  p = p * s2 + 1.0 / 11.0;
+  p = p * s2 + 1.0 / 9.0;
+  p = p * s2 + 1.0 / 7.0;
+  p = p * s2 + 1.0 / 5.0;
+  p = p * s2 + 1.0 / 3.0;
+  p = p * s2 + 1.0;
+  const double x = -2.0 * ((double)e * 0.69314718055994530942 + 2.0 * s * p);   // -2 ln(1 - ua) >= 0 (0 exactly for ua = 0: e = 0, s = 0)
+  const double g = (double)__builtin_amdgcn_rsqf(fmaxf((float)x, 1e-30f));      // 1 / sqrt(x); ua = 0: a finite seed times x = 0
+  double r = x * g;
+  r = r + 0.5 * g * (x - r * r);                                                  // one Newton step
+  const float k = rintf(4.0f * ub);                              // quarter turns, 0..4
+  const float f = fmaf(-0.25f, k, ub);                           // exact, |f| <= 1/8
+  const float a = fmaf(f, 6.2831854820251465f, f * -1.7484555e-07f);   // 2 pi f with a two-part 2 pi (as map_pi): half an ulp of a
+  float sn, cs;
+  joint_sincos(a, &sn, &cs);
+  const int q = (int)k & 3;
+  const float ss = (q & 1) ? cs : sn, cc = (q & 1) ? sn : cs;
+  const float sq = (q & 2) ? -ss : ss, cq = ((q + 1) & 2) ? -cc : cc;
+  *z0 = (float)(r * (double)cq);
+  *z1 = (float)(r * (double)sq);
 }
 
 // ------------------------------------------------------------------------------------------------

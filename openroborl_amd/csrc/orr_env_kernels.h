@@ -1,10 +1,11 @@
 // orr_env_kernels.h -- the two env kernels (orr_reset_kernel, orr_step_kernel) and their launchers, as templates.
 //
-// Included by the four translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
-// four: DESIGN.md section 3).  orr_kernels.hip: the default kernels + the C-ABI, instruction-level-parallelism scheduler (one wave per
+// Included by the five translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
+// several: DESIGN.md section 3).  orr_kernels.hip: the default kernels + the C-ABI, instruction-level-parallelism scheduler (one wave per
 // SIMD, ~300 registers, nothing to hide latency but the wave's own independent instructions).  orr_kernels_w2.hip: the
 // two-waves-per-SIMD step kernel, its own flags.  orr_kernels_anchor.hip: the friction-anchor variants.  orr_kernels_multiclip.hip:
-// the clip-set variants.  An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
+// the clip-set variants.  orr_kernels_noise.hip: the task-noise variants (clip sets + perturbed initial states + target-heading noise).
+// An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
 // per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
 // template` only (bottom of this file).
 // Device code by phase: orr_device.h (LDS image, math, DPP helpers), orr_robot_io.h (record load / store, latency ring),
@@ -101,14 +102,15 @@ using namespace orr;
   float* rec = P.state + (size_t)robot * ORR_STATE_STRIDE
 
 // CLIPS: the multi-clip variant (orr_kernels_multiclip.hip): every reset draws the robot's clip from its type's clip set
-template <bool CLIPS = false>
+// NOISE: the noise variant (orr_kernels_noise.hip, with CLIPS): perturbed initial states and target-heading noise (orr_set_task_noise)
+template <bool CLIPS = false, bool NOISE = false>
 __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t* mask, float* obs_out, const float* uniforms) {
   ORR_PROLOGUE();
   const bool valid = in_range && !(mask && !mask[robot]);
   load_robot(P, rec, S, lane);
   const long long total = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
   const ResetConst RC = load_reset_const(P, S, lane);
-  reset_robot<CLIPS>(P, rec, S, lane, valid, total, obs, RC, uniforms ? uniforms + (size_t)robot * 28 : nullptr);
+  reset_robot<CLIPS, NOISE>(P, rec, S, lane, valid, total, obs, RC, uniforms ? uniforms + (size_t)robot * 28 : nullptr);
   WSYNC();
   store_robot(rec, S, lane, valid);
   // a new episode: no cached contact points (ANCHOR, ANCHOR_VALID: 28 words behind the ring).  Unconditional: friction anchors may be switched
@@ -141,7 +143,11 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
 // CLIPS: the multi-clip variant (orr_kernels_multiclip.hip, one wave per SIMD whatever the batch size): the auto-reset draws the new
 // episode's clip from the robot type's clip set (reset_robot<true>), the episode log also records the clip of the ending episode, and
 // a robot whose motion time has reached the record's CLIP_CHANGE_TIME switches to a newly drawn clip mid-episode (orr_set_clip_switch)
-template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false>
+// NOISE: the noise variant (orr_kernels_noise.hip; instantiated with CLIPS only - a superset: a type without a clip set keeps its CLIP_ID -
+// and one wave per SIMD whatever the batch size): the auto-reset may start the episode on a perturbed state and every target
+// observation is expressed in a noisy heading (orr_set_task_noise; reset_robot<.., true>, target_obs<true>).  Both sit outside the
+// sub-step loop.  LAST parameter: the mangled names of the other variants keep their prefixes (tools/isa_stats.py)
+template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false, bool NOISE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
   ORR_PROLOGUE();
@@ -437,6 +443,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   // nondeterministic value instead of an uninitialised variable: reading it is defined behaviour in every lane, and unlike a constant
   // it gives the compiler nothing to merge with the atomic's result (a merged value made it wait for the atomic right away)
   unsigned long long log_slot = __builtin_nondeterministic_value(log_slot);
+  uint32_t noise_i = 0u;     // NOISE: 1 + the env-step counter before this step (target_obs<true>)
   {
     const float* rp = &S.s[O(REF_POSE)];
     float pe = 0.0f, qc[4], dq[4];
@@ -455,6 +462,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     if (!(fabsf(rew) < 1e30f)) reason |= ORR_DONE_NAN;
     if (reason & ORR_DONE_NAN) rew = 0.0f;      // whatever was computed from a non-finite state is not a reward
     const int ep_step = geti(S, O(EP_STEP)) + 1;  // quadruped_gym_env.py:237
+    if constexpr (NOISE) noise_i = (uint32_t)ep_step;
     if (ep_step >= geti(S, O(MAX_EP_STEPS))) reason |= ORR_DONE_TIME_LIMIT;
     // episode log (imitation_runners.py:185-197): the slot comes from a returning atomic on a counter shared by the whole device (a
     // round trip of several microseconds).  It is issued HERE, as soon as the end of the episode is known, and consumed after the
@@ -470,7 +478,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   // observation (wrapper_env.py:109-125)
   if (lane < 12) obs[lane] = S.s[O(IMU_HIST) + lane];
   for (int i = lane; i < 36; i += kLanes) { obs[12 + i] = S.s[O(LASTACT_HIST) + i]; obs[48 + i] = S.s[O(MOTORANG_HIST) + i]; }
-  target_obs(P, rec, S, lane, obs + ORR_PROPRIO_DIM);
+  target_obs<NOISE>(P, rec, S, lane, obs + ORR_PROPRIO_DIM, (uint32_t)geti(S, O(EPISODE_IDX)), noise_i);
   if (valid && lane == 0) {
     reward_out[robot] = rew;
     done_out[robot] = reason != 0;
@@ -490,7 +498,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     WSYNC();
     if (c.flags & ORR_FLAG_AUTO_RESET) {
       PT(31);
-      reset_robot<CLIPS>(P, rec, S, lane, valid, total_snapshot, obs, RC);
+      reset_robot<CLIPS, NOISE>(P, rec, S, lane, valid, total_snapshot, obs, RC);
       if constexpr (ANCHOR) AS = AnchorState{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};   // a new episode: no cached contact points
     }
     if (logs && P.ep_log) {
@@ -556,15 +564,15 @@ using StepLaunch = hipError_t(const KParams& P, int waves, hipStream_t stream, c
                               int nsub, const ReplayArgs& rp);
 using ResetLaunch = hipError_t(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs, const float* uniforms);
 
-template <int MODE, int WPE, bool ANCHOR, bool CLIPS>
+template <int MODE, int WPE, bool ANCHOR, bool CLIPS, bool NOISE = false>
 hipError_t launch_step(const KParams& P, int waves, hipStream_t stream, const float* actions, float* obs, float* reward, uint8_t* done, int nsub,
                        const ReplayArgs& rp) {
-  hipLaunchKernelGGL((orr_step_kernel<MODE, WPE, ANCHOR, CLIPS>), dim3(waves), dim3(64), 0, stream, P, actions, obs, reward, done, nsub, rp);
+  hipLaunchKernelGGL((orr_step_kernel<MODE, WPE, ANCHOR, CLIPS, NOISE>), dim3(waves), dim3(64), 0, stream, P, actions, obs, reward, done, nsub, rp);
   return hipGetLastError();
 }
-template <bool CLIPS>
+template <bool CLIPS, bool NOISE = false>
 hipError_t launch_reset(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs, const float* uniforms) {
-  hipLaunchKernelGGL((orr_reset_kernel<CLIPS>), dim3(waves), dim3(64), 0, stream, P, mask, obs, uniforms);
+  hipLaunchKernelGGL((orr_reset_kernel<CLIPS, NOISE>), dim3(waves), dim3(64), 0, stream, P, mask, obs, uniforms);
   return hipGetLastError();
 }
 
@@ -574,4 +582,7 @@ extern template StepLaunch launch_step<1, 1, true, false>;                   // 
 extern template StepLaunch launch_step<0, 1, false, true>;                   // orr_kernels_multiclip.hip: env step,
 extern template StepLaunch launch_step<2, 1, false, true>;                   //   its parity replay,
 extern template ResetLaunch launch_reset<true>;                              //   reset (and, with the draws given, its parity replay)
+extern template StepLaunch launch_step<0, 1, false, true, true>;             // orr_kernels_noise.hip: env step,
+extern template StepLaunch launch_step<2, 1, false, true, true>;             //   its parity replay,
+extern template ResetLaunch launch_reset<true, true>;                        //   reset (and its parity replay)
 }  // namespace orr

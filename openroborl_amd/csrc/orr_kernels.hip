@@ -7,8 +7,8 @@
 // this device: 33 physics sub-steps, observation, reward, termination, optional auto-reset.
 // Specification of every stage: DESIGN.md section 4; CPU restatement: oracle/orr_oracle.c.
 // The kernels and their launchers are templates in orr_env_kernels.h.  This unit instantiates the default ones (env step, debug
-// physics, parity replay, reset) and chooses among all variants (variant_of); the two-wave, friction-anchor and clip-set
-// instantiations are compiled in units of their own (orr_kernels_w2.hip, _anchor.hip, _multiclip.hip; why: orr_env_kernels.h).
+// physics, parity replay, reset) and chooses among all variants (variant_of); the two-wave, friction-anchor, clip-set and task-noise
+// instantiations are compiled in units of their own (orr_kernels_w2.hip, _anchor.hip, _multiclip.hip, _noise.hip; why: orr_env_kernels.h).
 #define ORR_TU_MAIN 1
 #include "orr_env_kernels.h"
 // <0, ORR_WAVES_PER_EU>: one wave per SIMD in the shipped build; development builds (-DORR_WAVES_PER_EU=2 with the timers of this
@@ -82,6 +82,7 @@ struct orr_handle {
   uint32_t anchor_types;   // bit t = robot type t has orr_model::friction_anchor: launches run the ANCHOR variant of the step kernel
   uint32_t multiclip_types;   // bit t = robot type t has a clip set of more than one clip: orr_step / orr_reset run the multi-clip variants
   uint32_t switch_types;      // bit t = robot type t has a finite clip switch interval: the parity replays run the multi-clip variants
+  bool noise_on;              // orr_set_task_noise: a probability or a heading deviation above 0: every entry point but the debug physics runs the noise variants
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -140,6 +141,7 @@ int32_t orr_layout_size(int32_t i) { return g_fields[i].size; }
 int32_t orr_layout_is_int(int32_t i) { return g_fields[i].is_int; }
 int32_t orr_sizeof_config(void) { return (int32_t)sizeof(orr_config); }
 int32_t orr_sizeof_model(void) { return (int32_t)sizeof(orr_model); }
+int32_t orr_sizeof_task_noise(void) { return (int32_t)sizeof(orr_task_noise); }
 
 int32_t orr_create(const orr_config* cfg, orr_handle** out) {
   if (!cfg || !out) return fail(-1, "orr_create: null argument");
@@ -347,6 +349,32 @@ int32_t orr_set_clip_switch(orr_handle* h, int32_t robot_type, float tmin, float
   return 0;
 }
 
+int32_t orr_set_task_noise(orr_handle* h, const orr_task_noise* noise_host) {
+  if (!h) return fail(-1, "orr_set_task_noise: null handle");
+  orr_task_noise n;
+  memset(&n, 0, sizeof(n));
+  if (noise_host) n = *noise_host;
+  const struct { const char* name; float v; } stds[] = {
+      {"root_pos_std", n.root_pos_std}, {"root_rot_std", n.root_rot_std}, {"joint_pose_std", n.joint_pose_std}, {"root_vel_std", n.root_vel_std},
+      {"root_ang_vel_std", n.root_ang_vel_std}, {"joint_vel_std", n.joint_vel_std}, {"tar_heading_std", n.tar_heading_std}};
+  char m[160];
+  if (!(n.perturb_init_state_prob >= 0.0f && n.perturb_init_state_prob <= 1.0f))      // NaN fails the comparison
+    return fail(-1, "orr_set_task_noise: perturb_init_state_prob must be a probability in [0, 1]");
+  for (const auto& f : stds)
+    if (!(f.v >= 0.0f && f.v < INFINITY)) {
+      snprintf(m, sizeof(m), "orr_set_task_noise: %s must be a finite standard deviation >= 0", f.name);
+      return fail(-1, m);
+    }
+  const bool on = n.perturb_init_state_prob > 0.0f || n.tar_heading_std > 0.0f;
+  if (on && h->anchor_types)
+    return fail(-1, "orr_set_task_noise: friction anchors (orr_model::friction_anchor) and task noise cannot be combined");
+  // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->noise, &n, sizeof(n), hipMemcpyHostToDevice), "orr_set_task_noise: hipMemcpy");
+  h->tab_host.noise = n;
+  h->noise_on = on;
+  return 0;
+}
+
 int32_t orr_bind(orr_handle* h, void* state_dev, int64_t* counters_dev, float* ep_log_dev, int32_t ep_log_capacity) {
   if (!h || !state_dev || !counters_dev) return fail(-1, "orr_bind: null argument (state and counters are required)");
   if (((uintptr_t)state_dev & 15u) != 0) return fail(-1, "orr_bind: the state buffer must be 16-byte aligned (records move in 16-byte pieces)");
@@ -382,11 +410,19 @@ static KParams make_params(const orr_handle* h) {
 static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1) / kRPW; }
 
 // Which instantiation of the kernels a launch runs.  `clip_types` = the feature mask that selects the clip-set variants: multiclip_types
-// for orr_step / orr_reset, switch_types for the parity replays.  Clip sets come first (and refuse friction anchors: kRefused, the
-// message starts with the entry point's name `who`), then friction anchors, then the batch size; only the env step has a two-wave
-// and only the env step and the debug physics have an anchor instantiation, every other entry point runs its default one instead.
-enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips };
+// for orr_step / orr_reset, switch_types for the parity replays.  Task noise comes first (its variants hold the clip-set code too), then
+// clip sets (both refuse friction anchors: kRefused, the message starts with the entry point's name `who`), then friction anchors, then
+// the batch size; only the env step has a two-wave and only the env step and the debug physics have an anchor instantiation, every other
+// entry point runs its default one instead.
+enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise };
 static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who) {
+  if (h->noise_on && h->anchor_types) {
+    char m[256];
+    snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and task noise (orr_set_task_noise) cannot be combined", who);
+    fail(-1, m);
+    return kRefused;
+  }
+  if (h->noise_on) return kNoise;
   if (clip_types && h->anchor_types) {
     char m[256];
     snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and a clip set of more than one clip cannot be combined", who);
@@ -402,7 +438,9 @@ int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* 
   if (!h || !h->state) return fail(-1, "orr_reset: handle not bound");
   const Variant v = variant_of(h, h->multiclip_types, "orr_reset");
   if (v == kRefused) return -1;
-  if (v == kClips)   // some robot type has a clip set of more than one clip: every reset draws the episode's clip
+  if (v == kNoise)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
+    HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (task noise)");
+  else if (v == kClips)   // some robot type has a clip set of more than one clip: every reset draws the episode's clip
     HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr), "orr_reset: launch (clip sets)");
   else
     HIPCHK(launch_reset<false>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr), "orr_reset: launch");
@@ -413,14 +451,15 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
   if (!h || !h->state) return fail(-1, "orr_step: handle not bound");
   if (!actions_dev || !obs_dev || !reward_dev || !done_dev) return fail(-1, "orr_step: null buffer");
   if (((uintptr_t)obs_dev & 15u) != 0) return fail(-1, "orr_step: the observation buffer must be 16-byte aligned (it is written in 16-byte pieces)");
-#define ORR_STEP(WPE, ANCHOR, CLIPS, msg) \
-  HIPCHK((launch_step<0, WPE, ANCHOR, CLIPS>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{})), msg)
+#define ORR_STEP(WPE, ANCHOR, CLIPS, NOISE, msg) \
+  HIPCHK((launch_step<0, WPE, ANCHOR, CLIPS, NOISE>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{})), msg)
   switch (variant_of(h, h->multiclip_types, "orr_step")) {
     case kRefused: return -1;
-    case kClips: ORR_STEP(1, false, true, "orr_step: launch (clip sets)"); break;              // one wave per SIMD, any batch size
-    case kAnchor: ORR_STEP(1, true, false, "orr_step: launch (friction anchors)"); break;      // one wave per SIMD, any batch size
-    case kTwoWave: ORR_STEP(2, false, false, "orr_step: launch (two waves per SIMD)"); break;
-    case kDefault: ORR_STEP(ORR_WAVES_PER_EU, false, false, "orr_step: launch"); break;
+    case kNoise: ORR_STEP(1, false, true, true, "orr_step: launch (task noise)"); break;              // one wave per SIMD, any batch size
+    case kClips: ORR_STEP(1, false, true, false, "orr_step: launch (clip sets)"); break;              // one wave per SIMD, any batch size
+    case kAnchor: ORR_STEP(1, true, false, false, "orr_step: launch (friction anchors)"); break;      // one wave per SIMD, any batch size
+    case kTwoWave: ORR_STEP(2, false, false, false, "orr_step: launch (two waves per SIMD)"); break;
+    case kDefault: ORR_STEP(ORR_WAVES_PER_EU, false, false, false, "orr_step: launch"); break;
   }
 #undef ORR_STEP
   return 0;
@@ -469,7 +508,10 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
   const ReplayArgs rp{traj_dev, eff_dev, fall_dev, tau_out_dev, nullptr};
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_step");
   if (v == kRefused) return -1;
-  if (v == kClips)   // a clip switch interval: the multi-clip replay (its draws from 28 on come from the Philox stream)
+  if (v == kNoise)   // task noise: the noise replay (its draws from 28 on, the heading noise included, come from the Philox stream)
+    HIPCHK((launch_step<2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
+           "orr_debug_replay_step: launch (task noise)");
+  else if (v == kClips)   // a clip switch interval: the multi-clip replay (its draws from 28 on come from the Philox stream)
     HIPCHK((launch_step<2, 1, false, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
            "orr_debug_replay_step: launch (clip switching)");
   else
@@ -481,7 +523,9 @@ int32_t orr_debug_replay_reset(orr_handle* h, const float* uniforms_dev, float* 
   if (!h || !h->state || !uniforms_dev) return fail(-1, "orr_debug_replay_reset: bad argument");
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_reset");
   if (v == kRefused) return -1;
-  if (v == kClips)   // a clip switch interval: the multi-clip reset (draws 0..27 from uniforms_dev, 28 on from the Philox stream)
+  if (v == kNoise)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
+    HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (task noise)");
+  else if (v == kClips)   // a clip switch interval: the multi-clip reset (draws 0..27 from uniforms_dev, 28 on from the Philox stream)
     HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev), "orr_debug_replay_reset: launch (clip switching)");
   else
     HIPCHK(launch_reset<false>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev), "orr_debug_replay_reset: launch");

@@ -183,9 +183,17 @@ __device__ __forceinline__ double motion_time(const KParams& P, const Shared& S)
   return t;
 }
 
+// Philox blocks of the task noise (orr_set_task_noise; below 2^30: a draw index is 4 * block + word, 32 bits)
+constexpr uint32_t kNoiseResetBlock = 0x20000000u, kNoiseHeadingBlock = 0x30000000u;
+
 // build the 76-d target observation into obs76 (LDS) from S.ph.end.pose[1..4] (already origin-offset) -- imitation_task.py:254-301.
 // The control observation S.co must be current (it is after the last sub-step's ring push and after reset_robot's local blend).
-__device__ static void target_obs(const KParams& P, const float* rec, Shared& S, int lane, float* obs76) {
+// NOISE (the noise variants, orr_kernels_noise.hip): tar_obs_noise[0] of the reference (:273-275) - the heading the target frames are
+// expressed in gets orr_task_noise::tar_heading_std times a normal from block 0x30000000 + noise_i of the stream (robot index, episode):
+// noise_i = 0 for the observation of a reset, 1 + s for the step whose env-step counter before the step is s.  Both come from the
+// caller's registers: the record's EP_STEP / EPISODE_IDX words are rewritten by lane 0 right before the calls
+template <bool NOISE = false>
+__device__ static void target_obs(const KParams& P, const float* rec, Shared& S, int lane, float* obs76, uint32_t episode = 0u, uint32_t noise_i = 0u) {
   if (lane >= 1 && lane <= 4) {
     float rpy[3];
     euler_from_quat(&S.co[12], rpy);
@@ -194,7 +202,15 @@ __device__ static void target_obs(const KParams& P, const float* rec, Shared& S,
     float sy, cy, spch, cpch;
     joint_sincos(rpy[1], &spch, &cpch);
     joint_sincos(rpy[2], &sy, &cy);
-    const float heading = atan2_bf(sy * cpch, cy * cpch);
+    float heading = atan2_bf(sy * cpch, cy * cpch);
+    if constexpr (NOISE) {   // lanes 1..4 evaluate the same draw: one lane's cost for the wave
+      typedef const float __attribute__((address_space(1)))* gfp;
+      const float sigma = ((gfp)&P.tab->noise.tar_heading_std)[0];
+      float u4[4], z0, z1;
+      philox_block(P.cfg.seed, (uint32_t)geti(S, O(ROBOT_INDEX)), episode, kNoiseHeadingBlock + noise_i, u4);
+      normal_pair(u4[0], u4[1], &z0, &z1);
+      heading = fmaf(sigma, z0, heading);     // sigma = 0: the heading itself (z0 is finite)
+    }
     float ih[4], p[3], pr[3], q[4];
     q_about_z(-heading, ih);
     const float* pose = S.ph.end.pose[lane];
@@ -378,7 +394,10 @@ __device__ static void sensors_push(Shared& S, int lane, bool fill_all) {
 // with draw 28 (Philox block 7, word 0) before anything reads the clip, and CLIP_ID / S.clip hold it from then on; the record's
 // CLIP_CHANGE_TIME (behind the ring: written here, in memory) gets the episode's first clip change, draw 29 (orr_set_clip_switch)
 // RC: the lane's cold-table constants (load_reset_const; the step kernel issues those loads right past its sub-steps)
-template <bool CLIPS = false>
+// NOISE (the noise variants, orr_kernels_noise.hip; always with CLIPS): perturb_init_state_prob / _apply_state_perturb of the reference
+// (:192-197, 1195-1243) - with probability orr_task_noise::perturb_init_state_prob stage 6 puts the robot on a Gaussian-perturbed copy
+// of the reference state (draw rule: include/openroborl_hip.h, orr_set_task_noise) - and the noisy heading of target_obs<true>
+template <bool CLIPS = false, bool NOISE = false>
 __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int lane, bool valid, long long total_step_count, float* obs,
                                    const ResetConst& RC, const float* uni_replay = nullptr) {
   const orr_config& c = P.cfg;
@@ -447,6 +466,30 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
     const unsigned int* cg = reinterpret_cast<const unsigned int*>(&P.tab->clip[geti(S, O(CLIP_ID))]);
     unsigned int* cl = reinterpret_cast<unsigned int*>(&S.clip);
     if (lane < (int)(sizeof(DevClip) / 4)) cl[lane] = cg[lane];
+    WSYNC();
+  }
+  // NOISE: the 36 uniforms U(k) of blocks 0x20000000 .. 0x20000008 (lane b < 9 evaluates block b) and the 32 normals made of them
+  // (lane j: pair j of (U(4 + 2j), U(5 + 2j)), written over its own two uniforms) live in nz[0..35] = U(0..3), z0..z31 until stage 6.
+  // Their home is the end-effector buffer of the reward (StepEndBuf::ee, 48 words): only calc_reward touches it, no reset stage does,
+  // and in the step kernel the reward of the step is done before the auto-reset begins.  (red[] is full: draws in red[24..55], the
+  // ring entries in red[0..19] and red[56..75]; frames / pose / vel are written by stages 5a-5b and read by stage 6.)
+  float* nz = &S.ph.end.ee[0][0][0];
+  float n_prob = 0.0f, n_pos = 0.0f, n_rot = 0.0f, n_jp = 0.0f, n_vel = 0.0f, n_ang = 0.0f, n_jv = 0.0f;
+  if constexpr (NOISE) {
+    static_assert(sizeof(S.ph.end.ee) >= 36 * sizeof(float), "U(0..3) + 32 normals");
+    typedef const float __attribute__((address_space(1)))* gfp;
+    const gfp ns = (gfp)&P.tab->noise.perturb_init_state_prob;     // the handle's setting, in flight while the blocks are evaluated
+    n_prob = ns[0]; n_pos = ns[1]; n_rot = ns[2]; n_jp = ns[3]; n_vel = ns[4]; n_ang = ns[5]; n_jv = ns[6];
+    if (lane < 9) {
+      float u4[4];
+      philox_block(c.seed, robot, ep, kNoiseResetBlock + (uint32_t)lane, u4);
+      nz[4 * lane] = u4[0]; nz[4 * lane + 1] = u4[1]; nz[4 * lane + 2] = u4[2]; nz[4 * lane + 3] = u4[3];
+    }
+    WSYNC();
+    float z0, z1;
+    normal_pair(nz[4 + 2 * lane], nz[5 + 2 * lane], &z0, &z1);
+    WSYNC();
+    nz[4 + 2 * lane] = z0; nz[5 + 2 * lane] = z1;
     WSYNC();
   }
   PT(24);
@@ -533,6 +576,27 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
   if (lane < 3) { S.s[O(POS) + lane] = S.ph.end.pose[0][lane]; S.s[O(LINVEL) + lane] = S.ph.end.vel[lane]; S.s[O(ANGVEL) + lane] = S.ph.end.vel[3 + lane]; }
   if (lane < 4) S.s[O(QUAT) + lane] = S.ph.end.pose[0][3 + lane];
   if (lane < 12) { S.s[O(Q) + lane] = S.ph.end.pose[0][7 + lane]; S.s[O(QD) + lane] = S.ph.end.vel[6 + lane]; }
+  if constexpr (NOISE) {
+    // _apply_state_perturb (:1199-1243) on what was just written, by the lanes that wrote it (same lane, same word, in order); REF_POSE,
+    // REF_VEL, the origin and PREV_PHASE above keep the unperturbed state.  One fused multiply-add per word: reference + std z, rounded once
+    if (nz[0] < n_prob) {
+      const float* z = nz + 4;
+      if (lane < 2) { S.s[O(POS) + lane] = fmaf(n_pos, z[lane], S.ph.end.pose[0][lane]); S.s[O(LINVEL) + lane] = fmaf(n_vel, z[15 + lane], S.ph.end.vel[lane]); }
+      if (lane < 3) S.s[O(ANGVEL) + lane] = fmaf(n_ang, z[17 + lane], S.ph.end.vel[3 + lane]);
+      if (lane < 12) { S.s[O(Q) + lane] = fmaf(n_jp, z[3 + lane], S.ph.end.pose[0][7 + lane]); S.s[O(QD) + lane] = fmaf(n_jv, z[20 + lane], S.ph.end.vel[6 + lane]); }
+      // quaternion_about_axis(std z2, a) (x) reference rotation, a_i = -1 + 2 U(i) normalised, not renormalised afterwards.  A zero axis
+      // (squared norm below 1e-30, probability 2^-72: the reference divides by zero there) is no rotation.  Every lane evaluates it, lanes 0..3 store
+      const float a0 = fmaf(2.0f, nz[1], -1.0f), a1 = fmaf(2.0f, nz[2], -1.0f), a2 = fmaf(2.0f, nz[3], -1.0f);
+      const float n2 = a0 * a0 + a1 * a1 + a2 * a2;
+      float sh, ch;
+      joint_sincos(0.5f * (n_rot * z[2]), &sh, &ch);
+      const float ax = n2 < 1e-30f ? 0.0f : sh * rsq(n2);
+      const float dq[4] = {a0 * ax, a1 * ax, a2 * ax, n2 < 1e-30f ? 1.0f : ch};
+      float qp[4];
+      qmul(dq, &S.ph.end.pose[0][3], qp);
+      if (lane < 4) S.s[O(QUAT) + lane] = pick4(lane, qp[0], qp[1], qp[2], qp[3]);
+    }
+  }
   WSYNC();
   PT(22);
   float* e2 = S.ph.end.red + 56;         // ring entry #2; entry #1 was saved in registers below before red[] was reused
@@ -555,6 +619,6 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
   if (lane < 12) obs[lane] = S.s[O(IMU_HIST) + lane];
   for (int i = lane; i < 36; i += kLanes) { obs[12 + i] = S.s[O(LASTACT_HIST) + i]; obs[48 + i] = S.s[O(MOTORANG_HIST) + i]; }
   PT(23);
-  target_obs(P, rec, S, lane, obs + ORR_PROPRIO_DIM);
+  target_obs<NOISE>(P, rec, S, lane, obs + ORR_PROPRIO_DIM, ep, 0u);
   PT(30);
 }

@@ -163,6 +163,86 @@ def clip_switch_spec(clip_time_min, clip_time_max, robot_names):
     return out
 
 
+# ---- task noise (orr_set_task_noise; ImitationTask's perturb_init_state_prob and tar_obs_noise) ------------------------------------
+NOISE_RESET_BLOCK = 0x20000000      # Philox blocks 0x20000000 .. 0x20000008 of the episode's stream: the 36 uniforms U(k) of a reset's perturbation
+NOISE_HEADING_BLOCK = 0x30000000    # block 0x30000000 + i: the heading noise of target observation i of the episode (tar_noise_block)
+# _apply_state_perturb's standard deviations (imitation_task.py:1201-1206), by the names of orr_task_noise's fields
+INIT_PERTURB_STD = {"root_pos_std": 0.025, "root_rot_std": 0.025 * math.pi, "joint_pose_std": 0.05 * math.pi, "root_vel_std": 0.1,
+                    "root_ang_vel_std": 0.05 * math.pi, "joint_vel_std": 0.05 * math.pi}
+
+
+def normal_pair(ua, ub):
+    """The pair of standard normals the device makes of two stream uniforms (csrc/orr_device.h, normal_pair), in float64:
+    r = sqrt(-2 ln(1 - ua)), (z0, z1) = r (cos, sin)(2 pi ub).  ua, ub in [0, 1) (either may be 0); works on arrays."""
+    ua, ub = np.asarray(ua, dtype=np.float64), np.asarray(ub, dtype=np.float64)
+    r = np.sqrt(-2.0 * np.log1p(-ua))
+    phi = 2.0 * np.pi * ub
+    return r * np.cos(phi), r * np.sin(phi)
+
+
+def init_perturb_draw_indices():
+    """Draw indices (4 * block + word) of U(0) .. U(35), the uniforms of a reset's perturbation."""
+    return 4 * NOISE_RESET_BLOCK + np.arange(36, dtype=np.int64)
+
+
+def init_perturb_draws(U, prob, std=None):
+    """What a reset does with its 36 uniforms U(k) (the stream's draws init_perturb_draw_indices(); shape [..., 36]) - the draw rule of
+    include/openroborl_hip.h, orr_set_task_noise, in float64 with the float32 deviations the device holds.  Returns a dict:
+    perturbed [...] bool (U(0) < prob), z [..., 32] the normals, axis [..., 3] (normalised; zero where its squared norm is below 1e-30),
+    and the offsets the perturbed robots get on top of the reference state - pos [..., 2] (x, y), angle [...] (about axis), joints
+    [..., 12], vel [..., 2], ang_vel [..., 3], joint_vel [..., 12] - and rot [..., 4], the xyzw quaternion that multiplies the reference
+    rotation from the left."""
+    U = np.asarray(U, dtype=np.float64)
+    sd = {k: float(np.float32(v)) for k, v in dict(INIT_PERTURB_STD, **(std or {})).items()}
+    z0, z1 = normal_pair(U[..., 4:36:2], U[..., 5:36:2])
+    z = np.stack([z0, z1], axis=-1).reshape(U.shape[:-1] + (32,))
+    a = -1.0 + 2.0 * U[..., 1:4]
+    n2 = (a * a).sum(axis=-1, keepdims=True)
+    axis = np.where(n2 < 1e-30, 0.0, a / np.sqrt(np.maximum(n2, 1e-300)))
+    angle = sd["root_rot_std"] * z[..., 2]
+    rot = np.concatenate([axis * np.sin(0.5 * angle)[..., None], np.cos(0.5 * angle)[..., None]], axis=-1)
+    rot = np.where(n2 < 1e-30, np.array([0.0, 0.0, 0.0, 1.0]), rot)
+    return {"perturbed": U[..., 0] < float(np.float32(prob)), "z": z, "axis": axis, "pos": sd["root_pos_std"] * z[..., 0:2], "angle": angle,
+            "joints": sd["joint_pose_std"] * z[..., 3:15], "vel": sd["root_vel_std"] * z[..., 15:17],
+            "ang_vel": sd["root_ang_vel_std"] * z[..., 17:20], "joint_vel": sd["joint_vel_std"] * z[..., 20:32], "rot": rot}
+
+
+def tar_noise_block(ep_step_or_reset=None):
+    """Philox block of a target observation's heading noise: NOISE_HEADING_BLOCK for the observation of a reset (None; the auto-reset
+    inside a step included: the NEW episode's stream), NOISE_HEADING_BLOCK + 1 + s for the step whose env-step counter before the step
+    is s.  The noise is tar_heading_std * z0 of normal_pair(word 0, word 1) = draws 4 * block, 4 * block + 1.  Works on integer arrays."""
+    if ep_step_or_reset is None:
+        return NOISE_HEADING_BLOCK
+    return NOISE_HEADING_BLOCK + 1 + np.asarray(ep_step_or_reset, dtype=np.int64)
+
+
+def task_noise_spec(perturb_init_state_prob=0.0, tar_obs_noise=None, init_perturb_std=None):
+    """ImitationTask's perturb_init_state_prob / tar_obs_noise (a float, or a list whose first entry is used: the reference reads only
+    [0]; None = off) and an optional dict overriding some of INIT_PERTURB_STD -> the orr_task_noise struct.  ValueError on anything
+    the C-ABI (orr_set_task_noise) would refuse."""
+    def number(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number, not %r" % (what, v))
+        return float(v)
+    prob = number(0.0 if perturb_init_state_prob is None else perturb_init_state_prob, "perturb_init_state_prob")
+    if not (0.0 <= prob <= 1.0):
+        raise ValueError("perturb_init_state_prob must be a probability in [0, 1], not %r" % (prob,))
+    if isinstance(tar_obs_noise, (list, tuple, np.ndarray)):
+        if len(tar_obs_noise) == 0:
+            raise ValueError("tar_obs_noise must not be empty (its first entry is the heading's standard deviation)")
+        tar_obs_noise = number(tar_obs_noise[0], "tar_obs_noise[0]")
+    vals = dict(INIT_PERTURB_STD, tar_heading_std=0.0 if tar_obs_noise is None else number(tar_obs_noise, "tar_obs_noise"))
+    unknown = set(init_perturb_std or {}) - set(INIT_PERTURB_STD)
+    if unknown:
+        raise ValueError("init_perturb_std: unknown entries %s (known: %s)" % (sorted(unknown), sorted(INIT_PERTURB_STD)))
+    for k, v in (init_perturb_std or {}).items():
+        vals[k] = number(v, "init_perturb_std[%r]" % k)
+    for k, v in vals.items():
+        if not (0.0 <= v < math.inf):
+            raise ValueError("%s must be a finite standard deviation >= 0, not %r" % ("tar_obs_noise" if k == "tar_heading_std" else k, v))
+    return _abi.OrrTaskNoise(perturb_init_state_prob=prob, **vals)
+
+
 def action_space():
     """minitaur.py:145-148."""
     return Box(np.array([-2 * math.pi] * 12), np.array([2 * math.pi] * 12), dtype=np.float32)
@@ -174,7 +254,8 @@ class VecQuadrupedEnv(object):
     def __init__(self, task_name=None, training_yaml=None, sim_yaml=None, device="cuda", num_robot=None, seed=None,
                  robot=None, motion_file=None, mode=None, enable_randomizer=None, auto_reset=True, num_procs=1,
                  robot_index_offset=0, legacy_grid=False, mixed_robots=None, ep_log_capacity=65536, config_overrides=None,
-                 model_overrides=None, clip_time_min=None, clip_time_max=None):
+                 model_overrides=None, clip_time_min=None, clip_time_max=None, perturb_init_state_prob=None, tar_obs_noise=None,
+                 init_perturb_std=None):
         import torch
         self.torch = torch
         if not torch.cuda.is_available():
@@ -241,6 +322,15 @@ class VecQuadrupedEnv(object):
         clip_time_min = clip_time_min if clip_time_min is not None else params.get("clip_time_min")
         clip_time_max = clip_time_max if clip_time_max is not None else params.get("clip_time_max")
         self.clip_switch = clip_switch_spec(clip_time_min, clip_time_max, sorted(set(self.robot_names)))
+        # task noise (ImitationTask's perturb_init_state_prob / tar_obs_noise; the task YAML may carry the same keys): off by default, as in
+        # the reference.  Validated here, ahead of anything that needs the device
+        if perturb_init_state_prob is None:
+            perturb_init_state_prob = params.get("perturb_init_state_prob", 0.0)
+        if tar_obs_noise is None:
+            tar_obs_noise = params.get("tar_obs_noise")
+        if init_perturb_std is None:
+            init_perturb_std = params.get("init_perturb_std")
+        self.task_noise = task_noise_spec(perturb_init_state_prob, tar_obs_noise, init_perturb_std)
         self.robot_type = robot_type
         self.clip_id = clip_id
 
@@ -264,6 +354,8 @@ class VecQuadrupedEnv(object):
         for name, (lo, hi) in self.clip_switch.items():
             if math.isfinite(lo):
                 _lib.check(self.L.orr_set_clip_switch(self.h, robots.ROBOT_TYPE_ID[name], lo, hi), self.L)
+        if self.task_noise.perturb_init_state_prob > 0.0 or self.task_noise.tar_heading_std > 0.0:
+            _lib.check(self.L.orr_set_task_noise(self.h, C.byref(self.task_noise)), self.L)
         self.layout = statemod.Layout(self.L, "orr")
         idx = np.arange(num_robot, dtype=np.int32) + int(robot_index_offset)
         st = statemod.default_state(self.layout, num_robot, self.models, robot_type, clip_id, idx,
@@ -325,6 +417,14 @@ class VecQuadrupedEnv(object):
             self.close()
         except Exception:
             pass
+
+    def set_task_noise(self, perturb_init_state_prob=0.0, tar_obs_noise=None, init_perturb_std=None):
+        """Change the task noise of a running env (orr_set_task_noise): read from the next launch on.  All defaults = off.  A launch
+        takes nothing of it by value, but it selects the kernel variant: holders of captured graphs re-capture (launch_params_generation)."""
+        spec = task_noise_spec(perturb_init_state_prob, tar_obs_noise, init_perturb_std)
+        _lib.check(self.L.orr_set_task_noise(self.h, C.byref(spec)), self.L)
+        self.task_noise = spec
+        self.launch_params_generation += 1
 
     # ---- hot path ------------------------------------------------------------------------------
     def _stream(self):

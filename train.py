@@ -34,6 +34,12 @@ def main():
     ap.add_argument("--clip-time", type=float, nargs=2, metavar=("MIN", "MAX"), default=None,
                     help="switch to a newly drawn clip of the set every U(MIN, MAX) seconds of motion time, mid-episode (ImitationTask's "
                          "clip_time_min / clip_time_max; overrides the task YAML's; default: never)")
+    ap.add_argument("--perturb-init-state-prob", type=float, default=None,
+                    help="probability that a reset starts the robot on a Gaussian-perturbed copy of the reference state (ImitationTask's "
+                         "perturb_init_state_prob; overrides the task YAML's; default: 0)")
+    ap.add_argument("--tar-obs-noise", type=float, default=None,
+                    help="standard deviation (rad) of the noise on the heading the target observations are expressed in (ImitationTask's "
+                         "tar_obs_noise[0]; overrides the task YAML's; default: none)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
     ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip")
@@ -68,7 +74,7 @@ def main():
     torch.cuda.set_device(dev)
     env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
                           device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
-                          **clip_time_kwargs(args))
+                          perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise, **clip_time_kwargs(args))
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     model = ppo.ActorCritic(dev, params=params, seed=args.seed)                     # same seed -> identical replicas
     if not args.torch_policy:
