@@ -139,10 +139,20 @@ __device__ __forceinline__ void chol6_solve_pk(const Chol6Pk& F, float b0, float
 //   kCarrySubtreeMass  the subtree mass lives in a register across the launch in the one-wave build only: the 256-register build pays more
 //                      for the live register than for the two adds that rebuild it every sub-step
 //   kOwnLegFactor      row_response's variant (b), see there: four more live registers cost the two-wave unit 30 spilled ones
+//   kPackedVelocityUpdate  physics_substep's velocity update on packed pairs, see there: the two-wave unit spills 28 registers with it (26 without)
+//   ORR_COMMON / ORR_RARE  the wave-uniform tests of the sub-step whose outcome is nearly always the same (no joint-limit row in the wave, a
+//                      leg in contact in some robot of the wave, the joint-limit setup idle, not the env step's last sub-step) carry a branch
+//                      weight in the one-wave units, so that the common side falls through and the rare block sits behind the loop: a
+//                      lone wave pays 25-30 ticks per TAKEN branch.  The two-wave unit spills 98 registers with the same block order.
+//                      Macros, not functions: the hint has to sit in the condition of the `if` itself.
 #ifdef ORR_TU_STEP_W2
-constexpr bool kCarrySubtreeMass = false, kOwnLegFactor = false;
+constexpr bool kCarrySubtreeMass = false, kOwnLegFactor = false, kPackedVelocityUpdate = false;
+#define ORR_COMMON(x) (x)
+#define ORR_RARE(x) (x)
 #else
-constexpr bool kCarrySubtreeMass = true, kOwnLegFactor = true;
+constexpr bool kCarrySubtreeMass = true, kOwnLegFactor = true, kPackedVelocityUpdate = true;
+#define ORR_COMMON(x) __builtin_expect(!!(x), 1)
+#define ORR_RARE(x) __builtin_expect(!!(x), 0)
 #endif
 struct LegConst {
   float r[3][3], jdir[3], joff[3];  // chain: joint origin in the parent frame, internal angle = jdir * (q - joff)
@@ -1139,7 +1149,7 @@ __device__ __forceinline__ void delassus_columns(const Shared& S, unsigned int m
   const unsigned int cm = (mask >> 16) & 0xFu;
   static_for<0, 4>([&](auto gc) __attribute__((always_inline)) {      // the three contact rows of leg g at once
     constexpr int g = decltype(gc)::value;
-    if ((cm >> g) & 1u) {
+    if (ORR_COMMON((cm >> g) & 1u)) {
       float ax, ay, az, bx = 0.0f, by = 0.0f, bz = 0.0f;
       dpp_contact_triplet<4 + g>(G.rr0, G.rr1, G.rr2, G.c00, G.c01, G.c02, G.c10, G.c11, G.c12, G.c20, G.c21, G.c22, A.wa[0], A.wa[1], A.wa[2],
                                  A.wa[3], A.wa[4], A.wa[5], A.wq[3 * g], A.wq[3 * g + 1], A.wq[3 * g + 2], ax, ay, az);
@@ -1167,7 +1177,7 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
   // (lane i = proxy i); the loads are issued here and consumed after the leg dynamics, which cover their round trip
   int fp_body = 0, fp_n = 0;
   float fp_x = 0.0f, fp_y = 0.0f, fp_z = 0.0f, fp_r = 0.0f;
-  if (want_fall) {
+  if (ORR_RARE(want_fall)) {
     const ColdPtr mc = model_cold(P, geti(S, O(ROBOT_TYPE)));
     static_assert(ORR_MAX_FALL_PROXIES <= kLanes, "one fall proxy per lane");
     fp_body = mc->fall_body[lane]; fp_x = mc->fall_pos[lane][0]; fp_y = mc->fall_pos[lane][1]; fp_z = mc->fall_pos[lane][2]; fp_r = mc->fall_radius[lane];
@@ -1181,7 +1191,7 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
   // `lane < fp_n` up to the load and waits out the global-memory round trip on the spot, in front of the leg dynamics)
   asm volatile("" : "+v"(fp_n));
   int fall = 0;
-  if (want_fall) {
+  if (ORR_RARE(want_fall)) {
     bool hit = false;
     if (lane < fp_n) {
       const int b = fp_body;
@@ -1207,9 +1217,11 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
   ContactGeom G;
   row_setup_bank_a<ANCHOR>(S, cfg, rowlane ? (lane < 4 ? lane : lane + 12) : 0, rowlane, dt, inv_dt, erp_dt, A, G, AS, anchor_robot);
   unsigned long long balB = 0ull;
-  if (limit_idle > 0) {
+  if (ORR_COMMON(limit_idle > 0)) {
     limit_idle--;
-    B = Row{};                  // never read: without an active joint-limit row in the wave the bank-B paths below are not taken
+    // B stays unset: balB is 0 on this side, so anyB is false and none of the bank-B paths below (all behind anyB or HAS_B) is taken:
+    // nothing reads B.  Code that reads a field of B outside those paths has to set it here.  A zeroed B
+    // (`B = Row{}`) was 25 `v_mov 0` in nearly every sub-step: the fill of this side of the join, and of the join behind row_response(B)
     B.active = false;
   } else {
     float margin = 1e30f;
@@ -1238,12 +1250,12 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
   PT(5);
   // ---------------- impulse responses M^-1 J^T, diagonal, warm start ----------------
   row_response(S, cfg, A, rowlane ? (lane < 4 ? lane : lane + 12) : 0, BF);
-  if (anyB) row_response(S, cfg, B, (rowlane && lane >= 4) ? lane : kMaxRows, BF);   // lanes without a joint-limit row: dump slot
+  if (ORR_RARE(anyB)) row_response(S, cfg, B, (rowlane && lane >= 4) ? lane : kMaxRows, BF);   // lanes without a joint-limit row: dump slot
   WSYNC();
   PT(6);
   // Delassus columns, then the Gauss-Seidel sweeps; two instantiations: with and without the joint-limit bank
   float AcA[kMaxRows], AcB[kMaxRows], lam[kMaxRows];
-  if (anyB) {
+  if (ORR_RARE(anyB)) {
     delassus_columns<true>(S, mask, lane, sub, A, B, G, AcA, AcB, lam);
     PT(7);
     pgs_sweeps<true>(cfg.solver_iters, mask, lane, sub, A, B, AcA, AcB, lam);
@@ -1268,19 +1280,49 @@ __device__ static int physics_substep(const KParams& P, Shared& S, const LegCons
   // lane l owns DOF l (v0) and, for l < 2, DOF 16 + l (v1); the new coordinates are written by the owning lane
   float v0, v1;
   {
-    float du0 = 0.0f, du1 = 0.0f;
     const int k1 = lane + 16 < 18 ? lane + 16 : 0;
     const int k0 = lane < 18 ? lane : 0;
-    auto add_row = [&](auto rc) __attribute__((always_inline)) {
-      constexpr int r = decltype(rc)::value;
-      du0 += S.ph.sub.W[r][k0] * lam[r];
-      du1 += S.ph.sub.W[r][k1] * lam[r];
-    };
-    static_for<0, 4>(add_row);
-    if (anyB) {
-      for_active_limit_rows(mask, add_row);
+    float du0 = 0.0f, du1 = 0.0f;
+    if constexpr (kPackedVelocityUpdate) {
+      // (du0, du1) as ONE packed pair: a row's two words W[r][k0], W[r][k0 + 16] come out of LDS with one ds_read2_b32 into a register
+      // pair, and v_pk_fma_f32 with lam[r] as the broadcast operand does the two multiply-adds (the same two fused operations, the
+      // same rounding, the same order of the rows) in one issue slot.  k0 + 16 is DOF 16 + lane in the lanes 0, 1 that own one; in the
+      // other lanes it is a word of the row's padding or of the next row (W has a 29th row behind the last one read, the dump row, which
+      // no prologue zeroes): du1 is junk there, possibly NaN or Inf.  It cannot spread: v1 = med3(u* + du1, -vmax, vmax) is finite
+      // whatever du1 is (v_med3_f32 returns the minimum of the other operands for a NaN), int_c1 is 0 in those lanes, so X.x1 keeps its 0,
+      // and v1 * int_c1 and X.x1 go to the dump slot.  Nothing else may read du1, v1 or X.x1 in lanes >= 2.
+      // The sixteen rows of the common path are read in one batch in front of the first multiply-add (one wait, not one per row).
+      static_assert(kLanes + 16 + (kMaxRows - 1) * kWStride < (kMaxRows + 1) * kWStride, "the second word of the last row's pair lies inside W");
+      v2f du = {0.0f, 0.0f};
+      const float* const wk = &S.ph.sub.W[0][k0];
+      auto row_pair = [&](auto rc) __attribute__((always_inline)) {
+        constexpr int r = decltype(rc)::value;
+        return v2f{wk[r * kWStride], wk[r * kWStride + 16]};
+      };
+      v2f wr[kMaxRows];
+      static_for<0, 4>([&](auto rc) __attribute__((always_inline)) { wr[decltype(rc)::value] = row_pair(rc); });
+      static_for<16, 28>([&](auto rc) __attribute__((always_inline)) { wr[decltype(rc)::value] = row_pair(rc); });
+      asm volatile("" : "+v"(wr[0]), "+v"(wr[1]), "+v"(wr[2]), "+v"(wr[3]), "+v"(wr[16]), "+v"(wr[17]), "+v"(wr[18]), "+v"(wr[19]),
+                        "+v"(wr[20]), "+v"(wr[21]), "+v"(wr[22]), "+v"(wr[23]), "+v"(wr[24]), "+v"(wr[25]), "+v"(wr[26]), "+v"(wr[27]));
+      auto add_row = [&](auto rc) __attribute__((always_inline)) { du += wr[decltype(rc)::value] * lam[decltype(rc)::value]; };
+      static_for<0, 4>(add_row);
+      if (ORR_RARE(anyB)) {
+        for_active_limit_rows(mask, [&](auto rc) __attribute__((always_inline)) { du += row_pair(rc) * lam[decltype(rc)::value]; });
+      }
+      static_for<16, 28>(add_row);
+      du0 = du.x; du1 = du.y;
+    } else {
+      auto add_row = [&](auto rc) __attribute__((always_inline)) {
+        constexpr int r = decltype(rc)::value;
+        du0 += S.ph.sub.W[r][k0] * lam[r];
+        du1 += S.ph.sub.W[r][k1] * lam[r];
+      };
+      static_for<0, 4>(add_row);
+      if (anyB) {
+        for_active_limit_rows(mask, add_row);
+      }
+      static_for<16, 28>(add_row);
     }
-    static_for<16, 28>(add_row);
     const float vmax = cfg.max_coord_velocity;
     v0 = __builtin_amdgcn_fmed3f(S.ustar[k0] + du0, -vmax, vmax);
     v1 = __builtin_amdgcn_fmed3f(S.ustar[k1] + du1, -vmax, vmax);

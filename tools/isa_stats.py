@@ -121,6 +121,36 @@ def substep_loop(insts, labels):
     return best[1], best[2]
 
 
+def loop_side_blocks(insts, labels, lo, hi):
+    """The instructions of the loop [lo, hi] that lie OUTSIDE its span: code that the block placement put behind the back edge (rare
+    paths: orr_physics.h, ORR_RARE).  The loop is the set of instructions that can be reached from its first instruction and from
+    which that one can be reached again (control flow at instruction granularity: a conditional branch has two successors, s_branch
+    one, s_endpgm none); what the step kernel runs past the loop never comes back.  -> sorted indices outside lo .. hi"""
+    n = len(insts)
+    succ = [[] for _ in range(n)]
+    for i, t in enumerate(insts):
+        m = re.match(r"^s_(c?)branch\S*\s+(\S+)$", t)
+        if m and m.group(2) in labels:
+            succ[i].append(labels[m.group(2)])
+        if not (m and not m.group(1)) and not t.startswith("s_endpgm") and i + 1 < n:
+            succ[i].append(i + 1)
+    pred = [[] for _ in range(n)]
+    for i, ss in enumerate(succ):
+        for j in ss:
+            if j < n:
+                pred[j].append(i)
+
+    def reach(edges):
+        seen, todo = {lo}, [lo]
+        while todo:
+            for j in edges[todo.pop()]:
+                if j < n and j not in seen:
+                    seen.add(j)
+                    todo.append(j)
+        return seen
+    return sorted(i for i in reach(succ) & reach(pred) if not lo <= i <= hi)
+
+
 def scratch_accesses(seg):
     return sum(1 for t in seg if t.startswith("scratch_") or t.startswith("buffer_") and "offen" in t)
 
@@ -148,6 +178,11 @@ def main():
             print("%s: %d instructions (scratch accesses: %d)" % (name, tot, scratch_accesses(seg)))
             for k, v in c.most_common():
                 print("   %-18s %6d  %5.1f%%" % (k, v, 100.0 * v / tot))
+        side = loop_side_blocks(insts, labels, lo, hi)
+        if side:
+            seg = [insts[i] for i in side]
+            print("code of the loop outside that span (behind its back edge): %d instructions (scratch accesses: %d); loop with it: %d" % (
+                len(seg), scratch_accesses(seg), hi - lo + 1 + len(seg)))
         r = resources(meta, sym)
         if r:
             print(" LDS %s B, scratch %s B per lane, sgpr %s (spilled %s), vgpr %s (spilled %s)" % r)
