@@ -1,8 +1,15 @@
 // orr_probe.hip -- TEST-ONLY probe of the env kernels' device primitives (tests/probe_lib.py, tests/test_gpu_device_primitives.py).
 //
-// Not part of libopenroborl_hip.so: it includes the env kernels' header, instantiates no step or reset kernel, and wraps every device
-// helper of orr_device.h / orr_physics.h / orr_task.h that the step kernel is built from in a small kernel of its own:
+// Not part of libopenroborl_hip.so: it includes the env kernels' header, instantiates no step or reset kernel, and wraps the LEAF device
+// helpers of orr_device.h / orr_physics.h / orr_task.h in a small kernel each:
 //   extern "C" int orrp_<name>(const void* in, void* out, int n, void* stream)
+// Probed here: joint_sincos, atan2_bf, asin_bf, map_pi, q_norm_angle, euler_from_quat, qheading, qslerp, q_to_mat, qrot, pick4; row_sum16,
+// bcast_lane, dpp_bcast_max0, dpp_contact_triplet, part_suffix_sum (+ _inplace, _first_moment), zero_in_lane; chol6 / chol6_solve and
+// chol6_pk / chol6_solve_pk; philox_block, time_limit.  Probed by the siblings: normal_pair (orr_probe_noise.hip); the two solver stages
+// built from these leaves, delassus_columns and pgs_sweeps, which take their operands in registers (orr_probe_solver.hip).
+// NOT probed: row_setup_bank_a / row_setup_limit, row_response and leg_dynamics read and write the per-robot LDS image (Shared), so they
+// cannot be driven with chosen register inputs; they stay with the sub-step parity tests (tests/test_gpu_parity.py,
+// tests/test_gpu_substep_paths.py).
 // `in` / `out` are DEVICE pointers to n records of the helper's arguments / results (array of records, 4-byte words; the layouts
 // are listed at each entry point and mirrored by tests/probe_lib.py: SPECS).  Returns 0, or -1 for a bad n, or the hipError_t of the
 // launch.  One lane serves one record; every kernel checks its bounds and has no data-dependent loop.

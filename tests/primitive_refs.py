@@ -512,3 +512,401 @@ def gen_time_limit_totals(steps, start, end):
             tot += [np.floor(t) + d for d in (-2, -1, 0, 1, 2)]
         tot.append(steps + np.arange(-3, 4.0))
     return np.unique(np.concatenate(tot).astype(np.int64))
+
+
+# =====================================================================================================================
+# E. the constraint solver's register stages: Delassus columns and projected Gauss-Seidel sweeps
+# =====================================================================================================================
+# A robot's problem is indexed by row SLOT (solve order): 0..3 knee friction motors, 4..15 joint limits (joint = slot - 4),
+# 16..19 toe normals (leg = slot - 16), 20..27 friction (leg = (slot - 20) // 2, direction x / y).  Generalised velocities: 6 base
+# (angular, linear) + 12 joints (3 per leg).  On the device lane l of a robot holds bank-A slot (l if l < 4 else l + 12) and, for
+# l >= 4, bank-B slot l.  A batch of problems is a dict of arrays with the robots along axis 0 (see gen_solver_bucket).
+N_SLOTS, N_DOF = 28, 18
+SLOT_ORDER = tuple(range(N_SLOTS))
+LANE_SLOT_A = np.array([l if l < 4 else l + 12 for l in range(16)])
+NRM_SLOT = np.array([-1] * 20 + [16 + (r - 20) // 2 for r in range(20, 28)])        # friction row -> its toe's normal row
+SLOT_LEG = np.array([r for r in range(4)] + [(r - 4) // 3 for r in range(4, 16)] + [r - 16 for r in range(16, 20)] +
+                    [(r - 20) // 2 for r in range(20, 28)])
+SLOT_DIR = np.array([-1] * 16 + [2] * 4 + [0, 1] * 4)                               # contact rows: z (normal), x, y
+SOLVER_BUCKETS = ("standing", "sliding", "limits", "missing_legs", "soft", "idle")
+SOLVER_ROBOTS = 1024                                                                 # per bucket: 16384 lanes, 256 waves
+SOLVER_ITERS = 10
+BIG = F32(1e30)                                                                      # "no upper bound" of the unilateral rows
+
+
+def solver_jacobians(P):
+    """J[R, 28, 18] in float64 from the float32 geometry, built as row_setup_bank_a / row_setup_limit build (Jb, jl): knee rows e_knee,
+    limit rows sgn e_joint, contact rows ((rr x dir, dir), dir . ck[k] on the joints of their own leg)."""
+    n = len(P["rr"])
+    J = np.zeros((n, N_SLOTS, N_DOF))
+    for r in range(4):
+        J[:, r, 6 + 3 * r + 2] = 1.0
+    for r in range(4, 16):
+        J[:, r, 6 + r - 4] = P["sgn"][:, r - 4]
+    rr, ck = P["rr"].astype(np.float64), P["ck"].astype(np.float64)
+    for r in range(16, 28):
+        g, d = SLOT_LEG[r], SLOT_DIR[r]
+        dirv = np.zeros(3)
+        dirv[d] = 1.0
+        J[:, r, 0:3] = np.cross(rr[:, g], dirv)
+        J[:, r, 3:6] = dirv
+        J[:, r, 6 + 3 * g:9 + 3 * g] = ck[:, g, :, d]
+    return J
+
+
+def visited_columns(P, has_b):
+    """[R, 28] bool: the columns delassus_columns<HAS_B> computes for the robot's WAVE mask (knee rows always, a joint-limit row by its
+    bit, the three contact rows of a leg by the leg's normal bit); every other slot reads 0 and is not swept (joint limits) or is a
+    no-op in the sweeps (contact rows of a leg that no robot of the wave has on the ground)."""
+    m = np.repeat(np.asarray(P["mask"], dtype=np.uint32), 4)
+    v = np.zeros((len(m), N_SLOTS), dtype=bool)
+    v[:, 0:4] = True
+    for r in range(4, 16):
+        v[:, r] = has_b & (((m >> np.uint32(r)) & 1) == 1)
+    for r in range(16, 28):
+        v[:, r] = ((m >> np.uint32(16 + SLOT_LEG[r])) & 1) == 1
+    return v
+
+
+def delassus_ref64(P, has_b):
+    """The expression the device evaluates, A[row][r] = J_r . W[row], in float64 from the float32 inputs (NOT J_row . W[r]: the W are
+    rounded, the two differ in the last bits), and the sum of the terms' magnitudes; 0 where the column is not visited.
+    -> (A[R, 28 row, 28 r], mag the same shape)"""
+    J = solver_jacobians(P)
+    W = P["W"].astype(np.float64)
+    v = visited_columns(P, has_b)[:, None, :]
+    A = np.einsum("nck,nrk->nrc", J, W)
+    mag = np.einsum("nck,nrk->nrc", np.abs(J), np.abs(W))
+    return np.where(v, A, 0.0), np.where(v, mag, 0.0)
+
+
+def delassus_ref64_brute(P, has_b, i):
+    """the same for robot i, by loops"""
+    J = solver_jacobians(P)[i]
+    W = P["W"][i].astype(np.float64)
+    v = visited_columns(P, has_b)[i]
+    A, mag = np.zeros((N_SLOTS, N_SLOTS)), np.zeros((N_SLOTS, N_SLOTS))
+    for row in range(N_SLOTS):
+        for r in range(N_SLOTS):
+            if v[r]:
+                for k in range(N_DOF):
+                    A[row, r] += J[r, k] * W[row, k]
+                    mag[row, r] += abs(J[r, k] * W[row, k])
+    return A, mag
+
+
+def scaled_system64(P, has_b, A=None):
+    """What the sweeps work on, in float64: Ac[row][r] = -A[row][r] jdi_row off the diagonal (0 on it and in unvisited columns),
+    w = cfm lam + (A lam) of the warm start over the visited columns, lam0 (0 in unvisited slots) and y0 = lam0 + rhs - w jdi."""
+    if A is None:
+        A, _ = delassus_ref64(P, has_b)
+    v = visited_columns(P, has_b)
+    jdi, cfm, rhs = P["jdi"].astype(np.float64), P["cfm"].astype(np.float64), P["rhs"].astype(np.float64)
+    lam_row = P["lam"].astype(np.float64)
+    lam0 = np.where(v, lam_row, 0.0)
+    Ac = -A * jdi[:, :, None]
+    Ac[:, np.arange(N_SLOTS), np.arange(N_SLOTS)] = 0.0
+    w = cfm * lam_row + np.einsum("nrc,nc->nr", A, lam0)
+    return {"Ac": Ac, "w": w, "lam0": lam0, "y0": lam_row + rhs - w * jdi, "swept": swept_rows(P, has_b)}
+
+
+def swept_rows(P, has_b):
+    """[R, 28] bool: knee and contact rows are swept unconditionally, joint-limit rows by the wave's mask bit"""
+    s = visited_columns(P, has_b)
+    s[:, 16:] = True
+    return s
+
+
+def pgs_ref64_brute(y0, Ac, lam0, lo_c, hi_c, mu, swept, iters):
+    """ONE robot, the oracle's row update (oracle/orr_oracle.c, projected Gauss-Seidel) in float64, slots in solve order:
+        lam_r <- clamp(lam_r + (rhs_r - A_r . lam - cfm_r lam_r) / (A_rr + cfm_r)),  friction bounds -/+ mu lam[normal] of the moment.
+    Divided through by (A_rr + cfm_r) and written with the inputs the device gets (Ac = -A / (A_rr + cfm) off the diagonal, and
+    y0 = the right-hand side of the warm start lam0) that is  lam_r <- clamp(y0_r + sum_{c != r} Ac[r][c] (lam_c - lam0_c)).
+    -> lam after each sweep [iters + 1, 28] (row 0: lam0)."""
+    lam = np.array(lam0, dtype=np.float64)
+    out = [lam.copy()]
+    for _ in range(iters):
+        for r in SLOT_ORDER:
+            if not swept[r]:
+                continue
+            v = y0[r]
+            for c in range(N_SLOTS):
+                if c != r:
+                    v += Ac[r, c] * (lam[c] - lam0[c])
+            if NRM_SLOT[r] >= 0:
+                hi = mu[r] * lam[NRM_SLOT[r]]
+                lo = -hi
+            else:
+                lo, hi = lo_c[r], hi_c[r]
+            lam[r] = min(max(v, lo), hi)
+        out.append(lam.copy())
+    return np.array(out)
+
+
+def pgs_ref64(S, P, iters):
+    """pgs_ref64_brute for every robot at once: S = a scaled system (scaled_system64, or float32 inputs cast up), P the problem (bounds).
+    -> [iters + 1, R, 28]"""
+    y0, Ac, lam0, swept = (np.asarray(S[k], dtype=np.float64) if k != "swept" else S[k] for k in ("y0", "Ac", "lam0", "swept"))
+    lo_c, hi_c, mu = P["lo_c"].astype(np.float64), P["hi_c"].astype(np.float64), P["mu"].astype(np.float64)
+    lam = lam0.copy()
+    out = [lam.copy()]
+    for _ in range(iters):
+        for r in SLOT_ORDER:
+            v = y0[:, r] + np.einsum("nc,nc->n", Ac[:, r], lam - lam0)       # Ac[r][r] = 0
+            if NRM_SLOT[r] >= 0:
+                hi = mu[:, r] * lam[:, NRM_SLOT[r]]
+                lo = -hi
+            else:
+                lo, hi = lo_c[:, r], hi_c[:, r]
+            lam[:, r] = np.where(swept[:, r], np.minimum(np.maximum(v, lo), hi), lam[:, r])
+        out.append(lam.copy())
+    return np.array(out)
+
+
+def _fma(a, b, c):
+    """a b + c rounded once to the operands' type (float32: the product-sum in float64, rounded once more; float64: as numpy has it)"""
+    if a.dtype == F32:
+        return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F32)
+    return a * b + c
+
+
+def pgs_yform(I, has_b, iters):
+    """The generic pgs_sweeps of csrc/orr_physics.h (the C++ form behind ORR_GENERIC_PGS) restated in numpy, in the type of the inputs:
+    float32 inputs give the float32 FLOOR (one rounding per fused operation), float64 inputs the same algorithm in float64.
+    I = lane-space inputs (solver_lane_inputs): rows lamA wA jdiA rhsA loA hiA muA lam_nA [R, 16], the same for bank B, AcA / AcB
+    [R, 16, 28], lam [R, 28], swept [R, 28].  A row lane keeps y (its unclamped value), the robot keeps lam[28].
+    -> lam after each sweep [iters + 1, R, 28]"""
+    dt = I["lam"].dtype
+    yA = I["lamA"] + _fma(-I["wA"], I["jdiA"], I["rhsA"])
+    yB = I["lamB"] + _fma(-I["wB"], I["jdiB"], I["rhsB"])
+    hiE, loE = _fma(I["muA"], I["lam_nA"], I["hiA"]), _fma(-I["muA"], I["lam_nA"], I["loA"])
+    AcA, AcB, swept = I["AcA"], I["AcB"], I["swept"]
+    lam = I["lam"].copy()
+    zero = dt.type(0)
+    mun = [np.where(NRM_SLOT[LANE_SLOT_A][None, :] == 16 + g, I["muA"], zero) for g in range(4)]
+    out = [lam.copy()]
+    for _ in range(iters):
+        for r in SLOT_ORDER:
+            old = lam[:, r:r + 1]
+            if r < 4 or r >= 16:
+                src = r if r < 4 else r - 12
+                yp = _fma(-AcA[:, :, r], old, yA)
+                if 16 <= r < 20:
+                    sb = np.maximum(yA[:, src], zero)
+                else:
+                    sb = np.minimum(np.maximum(yA[:, src], loE[:, src]), hiE[:, src])       # lo <= hi always: the median of the three
+                sb = sb[:, None]
+                yA = _fma(AcA[:, :, r], sb, yp)
+                if has_b:
+                    yB = _fma(AcB[:, :, r], sb - old, yB)
+                if 16 <= r < 20:
+                    d = sb - old
+                    hiE, loE = _fma(mun[r - 16], d, hiE), _fma(-mun[r - 16], d, loE)
+                lam[:, r] = sb[:, 0]
+            elif has_b:
+                on = swept[:, r:r + 1]
+                yp = _fma(-AcB[:, :, r], old, yB)
+                sb = np.maximum(yB[:, r], zero)[:, None]
+                yB = np.where(on, _fma(AcB[:, :, r], sb, yp), yB)
+                yA = np.where(on, _fma(AcA[:, :, r], sb - old, yA), yA)
+                lam[:, r] = np.where(on[:, 0], sb[:, 0], lam[:, r])
+        out.append(lam.copy())
+    return np.array(out)
+
+
+def solver_lane_inputs(P, has_b, dt=F32):
+    """The sweeps' inputs per lane, as the test hands them to orrp_pgs_a / _ab: the columns of delassus_ref64 scaled and rounded ONCE to
+    float32 (dt = float64: not rounded), w and lam_n of the warm start."""
+    S = scaled_system64(P, has_b)
+    n = len(P["rr"])
+    rd = lambda x: np.asarray(x, dtype=np.float64).astype(dt)     # noqa: E731
+    I = {"lam": rd(S["lam0"]), "swept": S["swept"]}
+    la = LANE_SLOT_A
+    nrm = NRM_SLOT[la]
+    lam_n = np.where(nrm[None, :] >= 0, S["lam0"][:, np.maximum(nrm, 0)], 0.0)
+    for key, src in (("lam", P["lam"]), ("w", S["w"]), ("jdi", P["jdi"]), ("rhs", P["rhs"]), ("cfm", P["cfm"]), ("lo", P["lo_c"]),
+                     ("hi", P["hi_c"]), ("mu", P["mu"])):
+        I[key + "A"] = rd(src[:, la])
+        b = rd(src[:, :16]).copy()
+        b[:, :4] = 0
+        I[key + "B"] = b
+    I["lam_nA"], I["lam_nB"] = rd(lam_n), np.zeros((n, 16), dtype=dt)
+    I["AcA"] = rd(S["Ac"][:, la, :])
+    I["AcB"] = rd(S["Ac"][:, :16, :]).copy()
+    I["AcB"][:, :4] = 0
+    if not has_b:
+        I["AcB"][:] = 0
+    return I
+
+
+def pgs_records(P, I):
+    """[R * 16, 105] float32 records of orrp_pgs_a / _ab from lane inputs (layout: tests/device_probe/orr_probe_solver.hip)"""
+    n = len(I["lam"])
+    rec = np.zeros((n, 16, 105), dtype=F32)
+    for off, bank in ((0, "A"), (10, "B")):
+        for k, key in enumerate(("lam", "w", "jdi", "rhs", "cfm", "lo", "hi", "mu", "lam_n")):
+            rec[:, :, off + k] = I[key + bank]
+    rec[:, :, 9] = NRM_SLOT[LANE_SLOT_A][None, :]
+    rec[:, :, 19] = -1
+    rec[:, :, 20:48], rec[:, :, 48:76] = I["AcA"], I["AcB"]
+    rec[:, :, 76:104] = I["lam"][:, None, :]
+    rec[:, :, 104] = np.repeat(np.asarray(P["mask"], dtype=np.uint32), 4).view(F32)[:, None]
+    return rec.reshape(n * 16, 105)
+
+
+def delassus_records(P):
+    """[R * 16, 75] float32 records of orrp_delassus_pgs_a / _ab.  The ContactGeom of a leg sits in its normal row's lane (4 + leg), the
+    only lane dpp_contact_triplet reads it from; every other lane carries P["gfill"], values nothing may depend on."""
+    n = len(P["rr"])
+    rec = np.zeros((n, 16, 75), dtype=F32)
+
+    def row(off, slots, valid):
+        jl = np.zeros((n, 16, 3), dtype=F32)
+        J = solver_jacobians(P)
+        for l, r in enumerate(slots):
+            g = SLOT_LEG[r]
+            jl[:, l] = J[:, r, 6 + 3 * g:9 + 3 * g]
+        fields = [P["active"][:, slots].astype(F32), np.broadcast_to(SLOT_LEG[slots].astype(F32), (n, 16)),
+                  np.broadcast_to(NRM_SLOT[slots].astype(F32), (n, 16)), jl[:, :, 0], jl[:, :, 1], jl[:, :, 2], P["rhs"][:, slots],
+                  P["jdi"][:, slots], P["lam"][:, slots], P["cfm"][:, slots], P["lo_c"][:, slots], P["hi_c"][:, slots], P["mu"][:, slots]]
+        for k, f in enumerate(fields):
+            rec[:, :, off + k] = f
+        rec[:, :, off + 13:off + 31] = P["W"][:, slots]
+        rec[:, ~valid, off:off + 31] = 0
+        rec[:, ~valid, off + 2] = -1
+    row(0, LANE_SLOT_A, np.ones(16, dtype=bool))
+    row(31, np.arange(16), np.arange(16) >= 4)
+    rec[:, :, 62:74] = P["gfill"]
+    for g in range(4):
+        rec[:, 4 + g, 62:65] = P["rr"][:, g]
+        rec[:, 4 + g, 65:74] = P["ck"][:, g].reshape(n, 9)
+    rec[:, :, 74] = np.repeat(np.asarray(P["mask"], dtype=np.uint32), 4).view(F32)[:, None]
+    return rec.reshape(n * 16, 75)
+
+
+def wave_masks(active):
+    """the wave's row mask as physics_substep lays it out: the union over its four robots of the active slots, bit = slot for 0..15,
+    bit 16 + (lane - 4) for the bank-A lanes 4..15 (slots 16..27)"""
+    a = np.asarray(active, dtype=bool).reshape(-1, 4, N_SLOTS).any(axis=1)
+    return (a.astype(np.uint32) << np.arange(N_SLOTS, dtype=np.uint32)[None, :]).sum(axis=1).astype(np.uint32)
+
+
+def gen_solver_bucket(name, n=SOLVER_ROBOTS, seed=0):
+    """One named bucket of n robots' solver problems (n a multiple of 4: whole waves).  M^-1 is a random SPD 18 x 18 matrix with its
+    eigenvalues spread over 2.5 decades, W = M^-1 J^T rounded to float32, jdi = 1 / (J_r . W_r + cfm) rounded to float32 (0 for an
+    inactive row), rhs already multiplied by jdi; half of the robots carry a warm start.  Inactive rows are pinned as the row setup pins
+    them (rhs, jdi, impulse and bounds 0) but keep a Jacobian and a response, as on the device.
+      standing      all four legs down, friction 0.5 .. 1, low tangential velocities
+      sliding       friction 0.2 .. 0.5, high tangential velocities
+      limits        a quarter of the joints has a limit row (the wave's mask then carries bits of rows other robots lack)
+      missing_legs  every wave lacks one leg in all four robots; the others come and go
+      soft          cfm > 0 on the toe normals
+      idle          no active row at all"""
+    assert name in SOLVER_BUCKETS and n % 4 == 0
+    rng = np.random.RandomState(1000 + 17 * SOLVER_BUCKETS.index(name) + seed)
+    Q, _ = np.linalg.qr(rng.standard_normal((n, N_DOF, N_DOF)))
+    ev = 10.0 ** rng.uniform(-1.25, 1.25, (n, N_DOF))
+    ev[:, 0], ev[:, 1] = 10.0 ** -1.25, 10.0 ** 1.25
+    Minv = np.einsum("nij,nj,nkj->nik", Q, ev, Q)
+    P = {"rr": (rng.uniform(-1, 1, (n, 4, 3)) * np.array([0.3, 0.2, 0.4])).astype(F32),
+         "ck": (rng.standard_normal((n, 4, 3, 3)) * 0.3).astype(F32),                    # ck[leg][k] = (c_k0, c_k1, c_k2)
+         "sgn": rng.choice([-1.0, 1.0], (n, 12)).astype(F32),
+         "gfill": (rng.standard_normal((n, 16, 12)) * 0.3).astype(F32)}
+    J = solver_jacobians(P)
+    P["W"] = np.einsum("nij,nrj->nri", Minv, J).astype(F32)
+    diag = np.einsum("nrk,nrk->nr", J, P["W"].astype(np.float64))
+    # which rows exist
+    act = np.zeros((n, N_SLOTS), dtype=bool)
+    if name != "idle":
+        act[:, 0:4] = rng.uniform(size=(n, 4)) < 0.9
+        down = np.ones((n, 4), dtype=bool) if name == "standing" else rng.uniform(size=(n, 4)) < 0.75
+        if name == "missing_legs":
+            down[np.arange(n), np.repeat(rng.randint(0, 4, n // 4), 4)] = False
+        if name == "limits":
+            act[:, 4:16] = rng.uniform(size=(n, 12)) < 0.25
+        act[:, 16:20] = down
+        act[:, 20:28] = np.repeat(down, 2, axis=1)
+    P["active"] = act
+    P["mask"] = wave_masks(act)
+    cfm = np.zeros((n, N_SLOTS))
+    if name == "soft":
+        cfm[:, 16:20] = diag[:, 16:20] * 10.0 ** rng.uniform(-2, 0, (n, 4))
+    cfm = np.where(act, cfm, 0.0).astype(F32)
+    jdi = np.where(act, 1.0 / (diag + cfm), 0.0).astype(F32)
+    # right-hand sides in units of sqrt(diag) (an impulse of ~1 / sqrt(diag) per unit): normals biased to push, limits symmetric,
+    # tangential velocities small (standing) or large (sliding) against the normal ones
+    sd = np.sqrt(diag)
+    tang = {"standing": 0.5, "sliding": 1.1}.get(name, 1.0)
+    g = rng.standard_normal((n, N_SLOTS))
+    g[:, 16:20] += {"standing": 1.5, "sliding": 1.0}.get(name, 0.5)
+    g[:, 20:28] *= tang
+    rhs = np.where(act, g * sd * jdi.astype(np.float64), 0.0).astype(F32)
+    mu = np.zeros((n, N_SLOTS))
+    mu[:, 20:28] = np.repeat(rng.uniform(0.2, 0.5, (n, 4)) if name == "sliding" else rng.uniform(0.5, 1.0, (n, 4)), 2, axis=1)
+    P["mu"] = np.where(act, mu, 0.0).astype(F32)
+    # knee bounds +-fr dt, scaled over two decades around the size of the unclamped impulse so that rows end on either side
+    hi = np.zeros((n, N_SLOTS))
+    hi[:, 0:4] = 10.0 ** rng.uniform(-1.5, 0.5, (n, 4)) / sd[:, 0:4]
+    hi[:, 4:20] = BIG
+    hi = np.where(act, hi, 0.0).astype(F32)
+    hi[:, 20:28] = 0
+    lo = np.zeros((n, N_SLOTS), dtype=F32)
+    lo[:, 0:4] = -hi[:, 0:4]
+    P["hi_c"], P["lo_c"], P["cfm"], P["jdi"], P["rhs"] = hi, lo, cfm, jdi, rhs
+    # warm start (half of the robots): inside the bounds for knee, normal and limit rows; friction rows may sit outside their cone
+    warm = (rng.uniform(size=(n, 1)) < 0.5) & act
+    l0 = np.abs(rng.standard_normal((n, N_SLOTS))) / sd
+    l0[:, 0:4] = np.minimum(l0[:, 0:4], hi[:, 0:4].astype(np.float64)) * rng.choice([-1.0, 1.0], (n, 4))
+    l0[:, 20:28] *= 0.7 * rng.choice([-1.0, 1.0], (n, 8))
+    P["lam"] = np.where(warm, l0, 0.0).astype(F32)
+    P["name"] = name
+    return P
+
+
+def select_robots(P, idx):
+    """the problems of robots idx (a new batch; the wave masks are rebuilt for the new grouping)"""
+    idx = np.asarray(idx)
+    Q = {k: v[idx] for k, v in P.items() if k not in ("mask", "name")}
+    Q["mask"] = wave_masks(Q["active"])
+    Q["name"] = P["name"]
+    return Q
+
+
+def solver_row_kinds(P):
+    """{kind: [R, 28] bool} of the ACTIVE rows"""
+    a = P["active"]
+    k = {"knee": np.zeros_like(a), "limit": np.zeros_like(a), "normal": np.zeros_like(a), "friction": np.zeros_like(a)}
+    k["knee"][:, 0:4], k["limit"][:, 4:16], k["normal"][:, 16:20], k["friction"][:, 20:28] = a[:, 0:4], a[:, 4:16], a[:, 16:20], a[:, 20:28]
+    return k
+
+
+def solver_bucket_stats(P, L):
+    """What the bucket conditions are checked on: L = pgs_ref64(...)[: 12] (float64, 11 sweeps).  Fractions of the ACTIVE rows of each kind
+    by where they end after 10 sweeps, and the median over the robots of the 11th sweep's largest change relative to the robot's
+    largest impulse."""
+    lam = L[SOLVER_ITERS]
+    k = solver_row_kinds(P)
+    bound = P["mu"].astype(np.float64) * lam[:, np.maximum(NRM_SLOT, 0)]
+    frac = lambda m, kind: m.sum() / max(k[kind].sum(), 1)      # noqa: E731
+    scale = np.abs(lam).max(axis=1)
+    ok = scale > 0
+    change = np.abs(L[SOLVER_ITERS + 1] - lam).max(axis=1)
+    return {"friction_on_cone": frac(k["friction"] & (bound > 0) & (np.abs(lam) == bound), "friction"),
+            "friction_inside": frac(k["friction"] & (np.abs(lam) < bound), "friction"),
+            "normal_zero": frac(k["normal"] & (lam == 0), "normal"), "normal_positive": frac(k["normal"] & (lam > 0), "normal"),
+            "limit_zero": frac(k["limit"] & (lam == 0), "limit"), "limit_positive": frac(k["limit"] & (lam > 0), "limit"),
+            "knee_on_bound": frac(k["knee"] & (np.abs(lam) == P["hi_c"].astype(np.float64)), "knee"),
+            "knee_inside": frac(k["knee"] & (np.abs(lam) < P["hi_c"].astype(np.float64)), "knee"),
+            "last_sweep_change": float(np.median(change[ok] / scale[ok])) if ok.any() else 0.0}
+
+
+def system_from_lane_inputs(I):
+    """the scaled system (as scaled_system64 returns it) that the float32 lane inputs of orrp_pgs_a / _ab state, cast up to float64"""
+    f = lambda k: I[k].astype(np.float64)     # noqa: E731
+    n = len(I["lam"])
+    Ac, y0 = np.zeros((n, N_SLOTS, N_SLOTS)), np.zeros((n, N_SLOTS))
+    Ac[:, LANE_SLOT_A] = f("AcA")
+    Ac[:, 4:16] = f("AcB")[:, 4:]
+    y0[:, LANE_SLOT_A] = f("lamA") + f("rhsA") - f("wA") * f("jdiA")
+    y0[:, 4:16] = (f("lamB") + f("rhsB") - f("wB") * f("jdiB"))[:, 4:]
+    return {"Ac": Ac, "y0": y0, "lam0": f("lam"), "swept": I["swept"]}

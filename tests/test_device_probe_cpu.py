@@ -1,7 +1,9 @@
-"""No GPU: the device-primitive probe compiles for gfx950 with both flag sets, the vectorised references of
-tests/primitive_refs.py agree with brute-force definitions and with the oracle's own functions, and every input generator of
-tests/test_gpu_device_primitives.py fills the buckets it names (none empty, none below 1000 inputs, no input outside every bucket)."""
+"""No GPU: the device-primitive probe compiles for gfx950 with both flag sets and the solver-stage probe with its three, the
+vectorised references of tests/primitive_refs.py agree with brute-force definitions and with the oracle's own functions, and every
+input generator of tests/test_gpu_device_primitives.py and tests/test_gpu_solver_primitives.py fills the buckets it names (none empty,
+none below 1000 inputs, no input outside every bucket; the solver's buckets: rows on both sides of every bound)."""
 import ctypes as C
+import functools
 import math
 import os
 import sys
@@ -12,22 +14,37 @@ import pytest
 from tests import oracle_lib as ol
 from tests import primitive_refs as R
 from tests import probe_lib
+from tests import probe_solver_lib
 
 F32 = np.float32
 
 
 # ---- the probe builds ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("build", ["one", "w2"])
+@pytest.mark.parametrize("build", ["one", "w2", "solver_one", "solver_w2", "solver_generic"])
 def test_probe_compiles_for_gfx950(build):
-    """A header change that breaks the probe shows here, on the CPU suite.  Not a forced compile: a library whose hash (probe source +
-    _lib.DEPS + flags) still matches is taken as it is, so any change of those files compiles here and nothing else does."""
-    so = probe_lib.build(build)
-    assert os.path.exists(so) and not probe_lib.needs_build(build)
+    """A header change that breaks a probe shows here, on the CPU suite.  Not a forced compile: a library whose hash (probe source +
+    _lib.DEPS + flags) still matches is taken as it is, so any change of those files compiles here and nothing else does.
+    solver_*: the solver-stage probe (orr_probe_solver.hip) in its three builds, `generic` with -DORR_GENERIC_PGS."""
+    if build.startswith("solver_"):
+        mod, build, names = probe_solver_lib, build[len("solver_"):], list(probe_solver_lib.SPECS)
+        assert ("-DORR_GENERIC_PGS" in mod.compile_command(build, "x")) == (build == "generic")
+    else:
+        mod, names = probe_lib, list(probe_lib.SPECS) + list(probe_lib.INT_ENTRIES)
+    so = mod.build(build)
+    assert os.path.exists(so) and not mod.needs_build(build)
     with open(so, "rb") as f:
         blob = f.read()
     assert b"gfx950" in blob
-    for name in list(probe_lib.SPECS) + list(probe_lib.INT_ENTRIES):
+    for name in names:
         assert b"orrp_" + name.encode() in blob, name
+
+
+def test_solver_probe_builds_differ_only_in_their_flags():
+    from openroborl_amd import _lib
+    B = probe_solver_lib.BUILDS
+    assert B["one"][1] == list(_lib.HIPCC_FLAGS) and B["w2"][1] == list(_lib.HIPCC_FLAGS_W2)
+    assert B["generic"][1] == list(_lib.HIPCC_FLAGS) + ["-DORR_GENERIC_PGS"]
+    assert len({v[0] for v in B.values()}) == 3 and not {v[0] for v in B.values()} & {v[0] for v in probe_lib.BUILDS.values()}
 
 
 def test_probe_is_no_part_of_the_product_library():
@@ -304,3 +321,173 @@ def test_philox_and_time_limit_inputs_cover_what_the_test_names():
             cfg.flags, cfg.curriculum_steps, cfg.ep_len_start, cfg.ep_len_end = _abi.FLAG_CURRICULUM, steps, start, end
             lim = {L.orc_time_limit(C.byref(cfg), int(t)) for t in tot}
             assert lim == set(range(min(start, end), max(start, end) + 1)), (steps, start, end)     # every boundary is crossed
+
+
+# ---- E: the solver stages' references and generators ----------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def solver_bucket(name):
+    P = R.gen_solver_bucket(name)
+    return P, R.pgs_ref64(R.scaled_system64(P, True), P, R.SOLVER_ITERS + 1)
+
+
+def test_solver_jacobians_are_the_row_setup_ones():
+    """contact rows: ((rr x dir, dir), dir . ck[k]) on the base and on the joints of the row's own leg only; knee rows e_knee; limit
+    rows +-e_joint"""
+    P, _ = solver_bucket("limits")
+    J = R.solver_jacobians(P)
+    rr, ck = P["rr"].astype(np.float64), P["ck"].astype(np.float64)
+    for i in (0, 5, 1023):
+        for r in range(28):
+            want = np.zeros(18)
+            if r < 4:
+                want[6 + 3 * r + 2] = 1.0
+            elif r < 16:
+                want[6 + r - 4] = P["sgn"][i, r - 4]
+            else:
+                leg = r - 16 if r < 20 else (r - 20) // 2
+                d = np.eye(3)[2 if r < 20 else (r - 20) % 2]
+                want[0:3], want[3:6] = np.cross(rr[i, leg], d), d
+                for k in range(3):
+                    want[6 + 3 * leg + k] = d @ ck[i, leg, k]
+            assert np.array_equal(J[i, r], want), (i, r)
+    assert set(np.unique(P["sgn"])) == {-1.0, 1.0}
+    # W = M^-1 J^T, rounded to float32: M^-1 recovered from the eighteen independent columns is symmetric positive definite with its
+    # eigenvalues 2.5 decades apart
+    W = P["W"].astype(np.float64)
+    for i in (0, 7):
+        Minv = np.linalg.lstsq(J[i], W[i], rcond=None)[0]
+        assert np.abs(Minv - Minv.T).max() < 1e-5 * np.abs(Minv).max()
+        ev = np.linalg.eigvalsh((Minv + Minv.T) / 2)
+        assert ev[0] > 0 and abs(np.log10(ev[-1] / ev[0]) - 2.5) < 0.01
+
+
+def test_solver_references_are_the_per_robot_loops():
+    for name, has_b in (("limits", True), ("limits", False), ("missing_legs", False), ("soft", True)):
+        P, _ = solver_bucket(name)
+        A, mag = R.delassus_ref64(P, has_b)
+        S = R.scaled_system64(P, has_b, A)
+        L = R.pgs_ref64(S, P, 4)
+        for i in (0, 3, 514):
+            Ab, magb = R.delassus_ref64_brute(P, has_b, i)
+            assert np.abs(A[i] - Ab).max() <= 1e-13 * max(np.abs(Ab).max(), 1) and np.abs(mag[i] - magb).max() <= 1e-13 * magb.max()
+            assert (mag[i] >= np.abs(A[i]) * (1 - 1e-12)).all()
+            Lb = R.pgs_ref64_brute(S["y0"][i], S["Ac"][i], S["lam0"][i], P["lo_c"][i].astype(np.float64), P["hi_c"][i].astype(np.float64),
+                                   P["mu"][i].astype(np.float64), S["swept"][i], 4)
+            assert np.abs(L[:, i] - Lb).max() <= 1e-12, (name, has_b, i)
+        v = R.visited_columns(P, has_b)
+        assert (A[~np.broadcast_to(v[:, None, :], A.shape)] == 0).all() and (S["lam0"][~v] == 0).all()
+        assert not v[:, 4:16].any() if not has_b else v[:, 4:16].any() == (name == "limits")
+
+
+def test_solver_ref64_is_the_oracle_row_update():
+    """pgs_ref64 is stated with scaled inputs; here the oracle's own statement, unscaled, on one robot:
+    lam_r <- clamp(lam_r + (rhs_r - A_r . lam - cfm_r lam_r) / (A_rr + cfm_r)) with the exact reciprocal"""
+    P, _ = solver_bucket("soft")
+    A, _ = R.delassus_ref64(P, True)
+    for i in (1, 2, 600):
+        act = P["active"][i]
+        D = A[i].diagonal() + P["cfm"][i]
+        jdi = np.where(act, 1.0 / np.where(act, D, 1.0), 0.0)
+        rhs = np.where(act, P["rhs"][i].astype(np.float64) / np.where(act, P["jdi"][i], 1.0), 0.0)       # unscaled
+        lam = P["lam"][i].astype(np.float64)
+        for _ in range(3):
+            for r in range(28):
+                if not act[r]:
+                    continue
+                v = lam[r] + (rhs[r] - A[i, r] @ lam - P["cfm"][i, r] * lam[r]) * jdi[r]
+                hi = P["mu"][i, r] * lam[R.NRM_SLOT[r]] if R.NRM_SLOT[r] >= 0 else float(P["hi_c"][i, r])
+                lo = -hi if R.NRM_SLOT[r] >= 0 else float(P["lo_c"][i, r])
+                lam[r] = min(max(v, lo), hi)
+        # the scaled form takes the float32 jdi for 1 / (A_rr + cfm): they differ by its rounding, 2^-24 relative, per row
+        S = R.scaled_system64(P, True, A)
+        got = R.pgs_ref64({k: (x[i:i + 1] if k != "swept" else x[i:i + 1]) for k, x in S.items()}, {k: P[k][i:i + 1] for k in ("lo_c", "hi_c", "mu")}, 3)[3, 0]
+        assert np.abs(got - lam).max() <= 2e-6 * np.abs(lam).max(), i
+
+
+def test_solver_yform_in_float64_is_pgs_ref64():
+    for name in R.SOLVER_BUCKETS:
+        for has_b in (False, True):
+            if name == "limits" and not has_b:
+                continue
+            P, _ = solver_bucket(name)
+            I = R.solver_lane_inputs(P, has_b, np.float64)
+            Y = R.pgs_yform(I, has_b, R.SOLVER_ITERS)
+            L = R.pgs_ref64(R.scaled_system64(P, has_b), P, R.SOLVER_ITERS)
+            assert Y.dtype == np.float64 and np.abs(Y - L).max() <= 1e-12, (name, has_b, np.abs(Y - L).max())
+    I = R.solver_lane_inputs(P, True)
+    assert R.pgs_yform(I, True, 1).dtype == F32 and all(I[k].dtype == F32 for k in I if k != "swept")
+
+
+def test_solver_buckets_are_what_they_say():
+    frac = {}
+    for name in R.SOLVER_BUCKETS:
+        P, L = solver_bucket(name)
+        n = len(P["rr"])
+        assert n >= R.MIN_BUCKET and n % 4 == 0 and P["W"].dtype == F32 and all(np.isfinite(v).all() for k, v in P.items() if k != "name")
+        act, st = P["active"], R.solver_bucket_stats(P, L)
+        frac[name] = st
+        print("SOLVER_BUCKET", name, " ".join("%s=%.3g" % kv for kv in st.items()))
+        warm = (P["lam"] != 0).any(axis=1)
+        if name == "idle":
+            assert not act.any() and P["mask"].max() == 0 and (L == 0).all() and not warm.any()
+            assert (P["jdi"] == 0).all() and (P["rhs"] == 0).all() and np.abs(P["W"]).min(axis=(1, 2)).max() > 0     # responses stay
+            continue
+        assert 0.4 < warm.mean() < 0.6 and (P["lam"][~act] == 0).all() and (P["jdi"][~act] == 0).all() and (P["hi_c"][~act] == 0).all()
+        assert (P["lam"][:, 4:20] >= 0).all() and (np.abs(P["lam"][:, 0:4]) <= P["hi_c"][:, 0:4]).all()
+        assert (P["lo_c"][:, 0:4] == -P["hi_c"][:, 0:4]).all() and (P["mu"][:, :20] == 0).all()
+        assert np.array_equal(act[:, 20:28], np.repeat(act[:, 16:20], 2, axis=1))
+        assert (act[:, 4:16].any()) == (name == "limits") and ((P["cfm"] > 0).any()) == (name == "soft")
+        for key in ("friction_on_cone", "friction_inside", "normal_zero", "normal_positive", "knee_on_bound", "knee_inside"):
+            assert st[key] >= 0.10, (name, key, st[key])
+        mu = P["mu"][:, 20:28][act[:, 20:28]]
+        lo, hi = (0.2, 0.5) if name == "sliding" else (0.5, 1.0)
+        assert mu.min() >= F32(lo) and mu.max() <= F32(hi) and mu.max() - mu.min() > 0.9 * (hi - lo)
+    P, _ = solver_bucket("standing")
+    assert P["active"][:, 16:].all()
+    assert frac["standing"]["last_sweep_change"] > 1e-6 and frac["limits"]["last_sweep_change"] > 1e-6
+    # sliding: higher tangential right-hand sides against lower friction than standing
+    Ps, _ = solver_bucket("sliding")
+    tang = lambda Q: np.abs(Q["rhs"][:, 20:28][Q["active"][:, 20:28]] / Q["jdi"][:, 20:28][Q["active"][:, 20:28]]).mean()   # noqa: E731
+    assert tang(Ps) > 1.5 * tang(P) and frac["sliding"]["friction_on_cone"] > 1.5 * frac["standing"]["friction_on_cone"]
+    P, L = solver_bucket("limits")
+    st = frac["limits"]
+    assert st["limit_zero"] >= 0.10 and st["limit_positive"] >= 0.10
+    assert 0.2 < P["active"][:, 4:16].mean() < 0.3
+    bits = ((np.repeat(P["mask"], 4)[:, None] >> np.arange(4, 16, dtype=np.uint32)[None, :]) & 1).astype(bool)
+    assert (bits | ~P["active"][:, 4:16]).all() and (bits & ~P["active"][:, 4:16]).mean() > 0.2     # bits of rows the robot lacks
+    P, _ = solver_bucket("missing_legs")
+    legs = (P["mask"] >> np.uint32(16)) & np.uint32(0xF)
+    assert (legs != 0xF).all() and len(set(legs.tolist())) > 4
+    P, _ = solver_bucket("soft")
+    assert ((P["cfm"][:, 16:20] > 0) == P["active"][:, 16:20]).all() and (P["cfm"][:, :16] == 0).all() and (P["cfm"][:, 20:] == 0).all()
+
+
+def test_solver_records_carry_the_problem():
+    P, _ = solver_bucket("limits")
+    rec = R.delassus_records(P).reshape(-1, 16, probe_solver_lib.DEL_IN)
+    assert rec.dtype == F32
+    for lane in range(16):
+        r = R.LANE_SLOT_A[lane]
+        assert np.array_equal(rec[:, lane, 0], P["active"][:, r].astype(F32)) and np.array_equal(rec[:, lane, 7], P["jdi"][:, r])
+        assert (rec[:, lane, 1] == R.SLOT_LEG[r]).all() and (rec[:, lane, 2] == R.NRM_SLOT[r]).all()
+        assert np.array_equal(rec[:, lane, 13:31], P["W"][:, r])
+        if lane >= 4:
+            assert np.array_equal(rec[:, lane, 31 + 8], P["lam"][:, lane]) and np.array_equal(rec[:, lane, 31 + 13:62], P["W"][:, lane])
+            assert np.array_equal(rec[:, lane, 31 + 3 + (lane - 4) % 3], P["sgn"][:, lane - 4])
+        else:
+            assert (rec[:, lane, 31:62] == np.array([0, 0, -1] + [0] * 28, dtype=F32)).all()
+        if 4 <= lane < 8:
+            assert np.array_equal(rec[:, lane, 62:65], P["rr"][:, lane - 4]) and np.array_equal(rec[:, lane, 65:68], P["ck"][:, lane - 4, 0])
+    assert np.array_equal(rec[:, :, 74].view(np.uint32), np.repeat(np.repeat(P["mask"], 4)[:, None], 16, axis=1))
+    assert np.array_equal(rec[0::4, 0, 74].view(np.uint32), R.wave_masks(P["active"]))
+    # the mask's layout: bit = slot below 16, the bank-A lanes 4..15 above
+    a = np.zeros((4, 28), dtype=bool)
+    a[1, 2] = a[3, 9] = a[0, 17] = a[2, 26] = True
+    assert R.wave_masks(a)[0] == (1 << 2) | (1 << 9) | (1 << 17) | (1 << 26)
+    I = R.solver_lane_inputs(P, True)
+    rec = R.pgs_records(P, I).reshape(-1, 16, probe_solver_lib.PGS_IN)
+    assert np.array_equal(rec[:, 5, 76:104], I["lam"]) and np.array_equal(rec[:, 9, 20:48], I["AcA"][:, 9]) and np.array_equal(rec[:, 9, 48:76], I["AcB"][:, 9])
+    assert (I["AcA"][:, np.arange(16), R.LANE_SLOT_A] == 0).all() and (I["AcB"][:, np.arange(16), np.arange(16)] == 0).all()
+    assert np.array_equal(rec[:, 10, 8], I["lam"][:, 17]) and (rec[:, 10, 9] == 17).all()          # slot 22: friction of toe 1
+    Q = R.select_robots(P, np.arange(8)[::-1])
+    assert np.array_equal(Q["W"][0], P["W"][7]) and len(Q["mask"]) == 2

@@ -1,8 +1,13 @@
 """The env kernels' device primitives, one by one, on the GPU (through the test-only probe, tests/probe_lib.py).
 
-Every helper of csrc/orr_device.h / orr_physics.h / orr_task.h that the step kernel is built from is called from a small kernel of its
-own and compared with a plain definition (tests/primitive_refs.py): lane movement exactly against float32 numpy, the branch-free math
-against float64 of the float32 inputs, the Cholesky by its backward error, the RNG and the step limit exactly against the oracle.
+The leaf helpers of csrc/orr_device.h / orr_physics.h / orr_task.h are each called from a small kernel of their own and compared with a
+plain definition (tests/primitive_refs.py): lane movement exactly against float32 numpy (row_sum16, bcast_lane, pick4, zero_in_lane,
+dpp_bcast_max0, the part_suffix_sum family, dpp_contact_triplet), the branch-free math against float64 of the float32 inputs
+(joint_sincos, atan2_bf, asin_bf, map_pi, euler_from_quat, qheading, q_norm_angle, q_to_mat, qrot, qslerp), the Cholesky (chol6, chol6_pk)
+by its backward error, the RNG and the step limit (philox_block, time_limit) exactly against the oracle.
+Elsewhere: normal_pair in tests/test_gpu_init_noise.py; the solver stages built from these leaves (delassus_columns, pgs_sweeps) in
+tests/test_gpu_solver_primitives.py.  Not probed at all: row_setup_*, row_response and leg_dynamics work on the per-robot LDS image, not
+on register operands; they stay with the sub-step parity tests (tests/test_gpu_parity.py, tests/test_gpu_substep_paths.py).
 Both probe builds are tested: `one` has the flags of the one-wave env unit, `w2` those of the two-wave unit (-Os, other scheduler).
 Each test prints `PRIMITIVE <name> <build> max_err=... bound=... n=...` (profiles/device_primitives.txt keeps the lines of one run).
 
