@@ -306,6 +306,23 @@ typedef struct orr_task_noise {
 int32_t orr_set_task_noise(orr_handle* h, const orr_task_noise* noise_host);
 int32_t orr_sizeof_task_noise(void);
 
+/* reward terms (ImitationTask._calc_reward_pose / _velocity / _end_effector / _root_pose / _root_velocity, imitation_task.py:358-516).
+ * terms_dev float[N][5] (device): every orr_step and orr_debug_replay_step writes, for every robot of the shard, the five UNWEIGHTED
+ *   terms r_k = exp(-scale_k err_k) of the reward it wrote to reward_dev, in orr_config::reward_w's order: pose, velocity, end effector,
+ *   root pose, root velocity.  reward == sum_k reward_w[k] r_k, built from the very values stored.  A step that sets ORR_DONE_NAN
+ *   writes five zeros (its reward is 0).
+ * term_sums_dev float[N][5] (device): the running sums of the terms over the robot's current episode.  A step whose EP_STEP before
+ *   the step is 0 OVERWRITES the row with that step's terms, every other step adds to it: after the step that ends an episode the row
+ *   holds that episode's totals - with auto-reset too - until the robot's next step overwrites it.  No reset touches it.
+ * term_log_dev float[ep_log_capacity][5] (device), or NULL: episode-log row `slot` also gets the ending episode's five sums, as
+ *   orr_bind_clip_log adds the clip.  The capacity is orr_bind's; a dropped row (slot >= capacity) writes nothing.
+ * terms_dev == NULL unbinds everything: the handle then launches exactly the kernels it launched before.  Otherwise term_sums_dev must
+ * be non-NULL too.  While bound, orr_step and orr_debug_replay_step launch the terms variants of the step kernel (the task-noise variant
+ * + these stores: one wave per SIMD at any batch size; with no clip set and all noise zero they compute what the default kernels
+ * compute) and the resets the task-noise variant.  Refused, nothing changed: a null handle, terms_dev without term_sums_dev, a robot
+ * type with friction anchors (a launch refuses the combination too when such a model is set afterwards). */
+int32_t orr_bind_reward_terms(orr_handle* h, float* terms_dev, float* term_sums_dev, float* term_log_dev);
+
 /* replaces WrapperEnv.reset (wrapper_env.py:87-107): mask_dev NULL = all robots; obs_dev [N,160]
  * (rows of robots that are not reset are left untouched). */
 int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream);

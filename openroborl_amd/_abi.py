@@ -32,6 +32,10 @@ CNT_TOTAL_TIMESTEPS = 3
 CNT_EPISODES = 4
 CNT_EPLOG_DROPPED = 5
 NUM_COUNTERS = 8
+# orr_bind_reward_terms: int32_t (orr_handle*, float* terms_dev [N][5], float* term_sums_dev [N][5], float* term_log_dev [ep_log_capacity][5] | NULL);
+# the columns, in orr_config::reward_w's order
+NUM_REWARD_TERMS = 5
+REWARD_TERM_NAMES = ("pose", "velocity", "end_effector", "root_pose", "root_velocity")
 
 
 class OrrConfig(C.Structure):

@@ -114,7 +114,14 @@ struct DevTables {
   float clip_switch[ORR_MAX_ROBOT_TYPES][2];          // (tmin, tmax) of a type's switch interval; (+inf, +inf) = never
   // task noise of the handle (orr_set_task_noise), read by the noise variants only (orr_kernels_noise.hip).  APPENDED likewise
   orr_task_noise noise;                               // all zero = off
+  // per-term reward outputs (orr_bind_reward_terms), read by the terms variant only (orr_kernels_terms.hip).  APPENDED likewise
+  float* terms;                                       // [N][5] the unweighted terms of the step's reward, or NULL = not bound
+  float* term_sums;                                   // [N][5] their running sums over the robot's current episode
+  float* term_log;                                    // [ep_log_capacity][5] sums of each logged episode (row = episode-log slot), or NULL
 };
+// Flag bit of orr_step_kernel's MODE: the variant that also writes the reward terms.  MODE & 3 is the mode proper (0 env step, 1 debug
+// physics, 2 parity replay).  A bit of MODE rather than a template parameter of its own: the older variants keep their mangled names
+constexpr int kModeTerms = 4;
 static_assert(sizeof(orr_task_noise) == 32, "the noise variants read it as eight words");
 
 // Replay inputs of the parity entry points orr_debug_replay_reset / orr_debug_replay_step (kernel MODE 2): the scripted states,

@@ -1,10 +1,11 @@
 // orr_env_kernels.h -- the two env kernels (orr_reset_kernel, orr_step_kernel) and their launchers, as templates.
 //
-// Included by the five translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
+// Included by the six translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
 // several: DESIGN.md section 3).  orr_kernels.hip: the default kernels + the C-ABI, instruction-level-parallelism scheduler (one wave per
 // SIMD, ~300 registers, nothing to hide latency but the wave's own independent instructions).  orr_kernels_w2.hip: the
 // two-waves-per-SIMD step kernel, its own flags.  orr_kernels_anchor.hip: the friction-anchor variants.  orr_kernels_multiclip.hip:
 // the clip-set variants.  orr_kernels_noise.hip: the task-noise variants (clip sets + perturbed initial states + target-heading noise).
+// orr_kernels_terms.hip: the noise variant of the step that also writes the per-term reward outputs (orr_bind_reward_terms).
 // An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
 // per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
 // template` only (bottom of this file).
@@ -147,9 +148,15 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
 // and one wave per SIMD whatever the batch size): the auto-reset may start the episode on a perturbed state and every target
 // observation is expressed in a noisy heading (orr_set_task_noise; reset_robot<.., true>, target_obs<true>).  Both sit outside the
 // sub-step loop.  LAST parameter: the mangled names of the other variants keep their prefixes (tools/isa_stats.py)
+// TERMS = MODE & kModeTerms (orr_kernels_terms.hip; instantiated with CLIPS and NOISE only - a superset - and one wave per SIMD whatever the
+// batch size): lanes 0..4 of a robot also store the five unweighted terms of the step's reward, keep their running sums over the episode
+// in a caller-owned buffer and add the sums to the episode-log row (orr_bind_reward_terms).  All of it outside the sub-step loop.  A bit
+// of MODE, not a sixth parameter: the names above stay as they are
 template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false, bool NOISE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
+  constexpr bool TERMS = (MODE & kModeTerms) != 0;
+  static_assert(!TERMS || (MODE & 3) != 1, "the debug physics computes no reward");
   ORR_PROLOGUE();
   const bool valid = in_range;
   const orr_config& c = P.cfg;
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   };
   PT(0);
 
-  if (MODE == 1) {
+  if ((MODE & 3) == 1) {
     if (lane < 12) {
       const ColdPtr mc = model_cold(P, geti(S, O(ROBOT_TYPE)));
       const int j = mc->joint_of_motor[lane];
@@ -320,7 +327,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     {  // receive_obs, then the control observation of the next sub-step / of get_obs
       RingFetch F;
       ring_prefetch(rlat, rec, ring, lane, F);
-      if constexpr (MODE == 2) {
+      if constexpr ((MODE & 3) == 2) {
         const size_t slot = (size_t)robot * c.action_repeat + sstep;
         if (lane < 12 && valid) RP.tau_out[slot * 12 + lane] = S.tau[mj] * m_tsign;  // motor torque, motor order
         WSYNC();
@@ -405,7 +412,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   }
   PoseLoads PL;
   sample_poses_issue(P, S, lane, tl, PL);
-  float rew = calc_reward(P, S, lane, MODE == 2 ? RP.eff + (size_t)robot * 48 : nullptr);
+  // TERMS: lanes 0..4 own the robot's row of running sums (one term each); its load is issued here, with the frame loads, and first used
+  // at the step's end.  A padding lane group shadows robot 0: it loads that row and never stores
+  typedef float __attribute__((address_space(1)))* gterm;
+  float term = 0.0f, term_sum = 0.0f;
+  if constexpr (TERMS) {
+    if (lane < 5) term_sum = ((gterm)P.tab->term_sums)[(size_t)robot * 5 + lane];
+  }
+  float rew;
+  if constexpr (TERMS) {
+    float tk[5];
+    rew = calc_reward<true>(P, S, lane, (MODE & 3) == 2 ? RP.eff + (size_t)robot * 48 : nullptr, tk);
+    term = lane == 0 ? tk[0] : (lane == 1 ? tk[1] : (lane == 2 ? tk[2] : (lane == 3 ? tk[3] : tk[4])));
+  } else {
+    rew = calc_reward(P, S, lane, (MODE & 3) == 2 ? RP.eff + (size_t)robot * 48 : nullptr);
+  }
   sample_poses_finish(P, S, lane, tl, true, PL);
   {
     // _update_ref_motion (imitation_task.py:734-761) with _sync_ref_origin (:1020-1055)
@@ -462,6 +483,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     if (!(fabsf(rew) < 1e30f)) reason |= ORR_DONE_NAN;
     if (reason & ORR_DONE_NAN) rew = 0.0f;      // whatever was computed from a non-finite state is not a reward
     const int ep_step = geti(S, O(EP_STEP)) + 1;  // quadruped_gym_env.py:237
+    if constexpr (TERMS) {   // the first step of an episode restarts the sums (no reset kernel touches them); a non-finite step counts as five zeros
+      if (reason & ORR_DONE_NAN) term = 0.0f;
+      term_sum = (ep_step == 1 ? 0.0f : term_sum) + term;
+    }
     if constexpr (NOISE) noise_i = (uint32_t)ep_step;
     if (ep_step >= geti(S, O(MAX_EP_STEPS))) reason |= ORR_DONE_TIME_LIMIT;
     // episode log (imitation_runners.py:185-197): the slot comes from a returning atomic on a counter shared by the whole device (a
@@ -482,6 +507,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   if (valid && lane == 0) {
     reward_out[robot] = rew;
     done_out[robot] = reason != 0;
+  }
+  if constexpr (TERMS) {
+    if (valid && lane < 5) {
+      ((gterm)P.tab->terms)[(size_t)robot * 5 + lane] = term;
+      ((gterm)P.tab->term_sums)[(size_t)robot * 5 + lane] = term_sum;
+    }
   }
   PT(13);
   if (reason != 0) {
@@ -512,6 +543,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       } else {
         atomicAdd((unsigned long long*)&P.counters[ORR_CNT_EPLOG_DROPPED], 1ull);
       }
+    }
+    if constexpr (TERMS) {
+      // the ending episode's five sums into the log row: the slot lives in lane 0 only, lanes 0..4 get it by a lane broadcast (every lane
+      // of the robot is active here: `reason` is uniform over them)
+      const int src = sub * kLanes;
+      const unsigned long long tslot = ((unsigned long long)(unsigned)__shfl((int)(slot >> 32), src) << 32) | (unsigned)__shfl((int)slot, src);
+      gterm const term_log = (gterm)P.tab->term_log;
+      if (valid && lane < 5 && P.ep_log && term_log && tslot < (unsigned long long)P.ep_log_cap) term_log[tslot * 5 + lane] = term_sum;
     }
   }
   WSYNC();
@@ -585,4 +624,6 @@ extern template ResetLaunch launch_reset<true>;                              // 
 extern template StepLaunch launch_step<0, 1, false, true, true>;             // orr_kernels_noise.hip: env step,
 extern template StepLaunch launch_step<2, 1, false, true, true>;             //   its parity replay,
 extern template ResetLaunch launch_reset<true, true>;                        //   reset (and its parity replay)
+extern template StepLaunch launch_step<kModeTerms | 0, 1, false, true, true>;   // orr_kernels_terms.hip: env step with the reward terms,
+extern template StepLaunch launch_step<kModeTerms | 2, 1, false, true, true>;   //   its parity replay (resets: the noise unit's)
 }  // namespace orr

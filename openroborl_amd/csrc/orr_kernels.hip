@@ -7,8 +7,9 @@
 // this device: 33 physics sub-steps, observation, reward, termination, optional auto-reset.
 // Specification of every stage: DESIGN.md section 4; CPU restatement: oracle/orr_oracle.c.
 // The kernels and their launchers are templates in orr_env_kernels.h.  This unit instantiates the default ones (env step, debug
-// physics, parity replay, reset) and chooses among all variants (variant_of); the two-wave, friction-anchor, clip-set and task-noise
-// instantiations are compiled in units of their own (orr_kernels_w2.hip, _anchor.hip, _multiclip.hip, _noise.hip; why: orr_env_kernels.h).
+// physics, parity replay, reset) and chooses among all variants (variant_of); the two-wave, friction-anchor, clip-set, task-noise
+// and reward-terms instantiations are compiled in units of their own (orr_kernels_w2.hip, _anchor.hip, _multiclip.hip, _noise.hip,
+// _terms.hip; why: orr_env_kernels.h).
 #define ORR_TU_MAIN 1
 #include "orr_env_kernels.h"
 // <0, ORR_WAVES_PER_EU>: one wave per SIMD in the shipped build; development builds (-DORR_WAVES_PER_EU=2 with the timers of this
@@ -83,6 +84,7 @@ struct orr_handle {
   uint32_t multiclip_types;   // bit t = robot type t has a clip set of more than one clip: orr_step / orr_reset run the multi-clip variants
   uint32_t switch_types;      // bit t = robot type t has a finite clip switch interval: the parity replays run the multi-clip variants
   bool noise_on;              // orr_set_task_noise: a probability or a heading deviation above 0: every entry point but the debug physics runs the noise variants
+  bool terms_on;              // orr_bind_reward_terms: the steps run the terms variant (orr_kernels_terms.hip), the resets the noise variant
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -331,6 +333,22 @@ int32_t orr_bind_clip_log(orr_handle* h, int32_t* clip_log_dev) {
   return 0;
 }
 
+int32_t orr_bind_reward_terms(orr_handle* h, float* terms_dev, float* term_sums_dev, float* term_log_dev) {
+  if (!h) return fail(-1, "orr_bind_reward_terms: null handle");
+  const bool on = terms_dev != nullptr;
+  if (on && !term_sums_dev) return fail(-1, "orr_bind_reward_terms: terms_dev needs term_sums_dev (the running sums of the current episode)");
+  if (on && h->anchor_types)
+    return fail(-1, "orr_bind_reward_terms: friction anchors (orr_model::friction_anchor) and reward terms cannot be combined");
+  float* p[3] = {terms_dev, on ? term_sums_dev : nullptr, on ? term_log_dev : nullptr};
+  static_assert(offsetof(DevTables, term_sums) == offsetof(DevTables, terms) + sizeof(float*) &&
+                offsetof(DevTables, term_log) == offsetof(DevTables, terms) + 2 * sizeof(float*), "copied as three consecutive pointers");
+  // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->terms, p, sizeof(p), hipMemcpyHostToDevice), "orr_bind_reward_terms: hipMemcpy");
+  h->tab_host.terms = p[0]; h->tab_host.term_sums = p[1]; h->tab_host.term_log = p[2];
+  h->terms_on = on;
+  return 0;
+}
+
 int32_t orr_set_clip_switch(orr_handle* h, int32_t robot_type, float tmin, float tmax) {
   if (!h) return fail(-1, "orr_set_clip_switch: null handle");
   if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_clip_switch: robot_type out of range");
@@ -410,12 +428,20 @@ static KParams make_params(const orr_handle* h) {
 static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1) / kRPW; }
 
 // Which instantiation of the kernels a launch runs.  `clip_types` = the feature mask that selects the clip-set variants: multiclip_types
-// for orr_step / orr_reset, switch_types for the parity replays.  Task noise comes first (its variants hold the clip-set code too), then
+// for orr_step / orr_reset, switch_types for the parity replays.  The reward terms come first (their step variants hold the noise and the
+// clip-set code; the resets of such a handle run the noise variant), then task noise (its variants hold the clip-set code too), then
 // clip sets (both refuse friction anchors: kRefused, the message starts with the entry point's name `who`), then friction anchors, then
 // the batch size; only the env step has a two-wave and only the env step and the debug physics have an anchor instantiation, every other
 // entry point runs its default one instead.
-enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise };
+enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms };
 static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who) {
+  if (h->terms_on && h->anchor_types) {   // (a model with anchors set after orr_bind_reward_terms)
+    char m[256];
+    snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and reward terms (orr_bind_reward_terms) cannot be combined", who);
+    fail(-1, m);
+    return kRefused;
+  }
+  if (h->terms_on) return kTerms;
   if (h->noise_on && h->anchor_types) {
     char m[256];
     snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and task noise (orr_set_task_noise) cannot be combined", who);
@@ -438,7 +464,7 @@ int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* 
   if (!h || !h->state) return fail(-1, "orr_reset: handle not bound");
   const Variant v = variant_of(h, h->multiclip_types, "orr_reset");
   if (v == kRefused) return -1;
-  if (v == kNoise)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
+  if (v == kNoise || v == kTerms)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (task noise)");
   else if (v == kClips)   // some robot type has a clip set of more than one clip: every reset draws the episode's clip
     HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr), "orr_reset: launch (clip sets)");
@@ -455,6 +481,8 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
   HIPCHK((launch_step<0, WPE, ANCHOR, CLIPS, NOISE>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{})), msg)
   switch (variant_of(h, h->multiclip_types, "orr_step")) {
     case kRefused: return -1;
+    case kTerms: HIPCHK((launch_step<kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0,
+                                                                           ReplayArgs{})), "orr_step: launch (reward terms)"); break;   // one wave per SIMD, any batch size
     case kNoise: ORR_STEP(1, false, true, true, "orr_step: launch (task noise)"); break;              // one wave per SIMD, any batch size
     case kClips: ORR_STEP(1, false, true, false, "orr_step: launch (clip sets)"); break;              // one wave per SIMD, any batch size
     case kAnchor: ORR_STEP(1, true, false, false, "orr_step: launch (friction anchors)"); break;      // one wave per SIMD, any batch size
@@ -508,7 +536,10 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
   const ReplayArgs rp{traj_dev, eff_dev, fall_dev, tau_out_dev, nullptr};
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_step");
   if (v == kRefused) return -1;
-  if (v == kNoise)   // task noise: the noise replay (its draws from 28 on, the heading noise included, come from the Philox stream)
+  if (v == kTerms)   // reward terms: the noise replay that also writes the terms
+    HIPCHK((launch_step<kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
+           "orr_debug_replay_step: launch (reward terms)");
+  else if (v == kNoise)   // task noise: the noise replay (its draws from 28 on, the heading noise included, come from the Philox stream)
     HIPCHK((launch_step<2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
            "orr_debug_replay_step: launch (task noise)");
   else if (v == kClips)   // a clip switch interval: the multi-clip replay (its draws from 28 on come from the Philox stream)
@@ -523,7 +554,7 @@ int32_t orr_debug_replay_reset(orr_handle* h, const float* uniforms_dev, float* 
   if (!h || !h->state || !uniforms_dev) return fail(-1, "orr_debug_replay_reset: bad argument");
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_reset");
   if (v == kRefused) return -1;
-  if (v == kNoise)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
+  if (v == kNoise || v == kTerms)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (task noise)");
   else if (v == kClips)   // a clip switch interval: the multi-clip reset (draws 0..27 from uniforms_dev, 28 on from the Philox stream)
     HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev), "orr_debug_replay_reset: launch (clip switching)");

@@ -277,7 +277,10 @@ __device__ __forceinline__ float clip_change_time(double t, float tmin, float tm
 
 // ImitationTask.reward (imitation_task.py:341-516); every lane returns the same value
 // eff_replay (parity replay only, else NULL): [2][8][3] link positions that replace the forward kinematics
-__device__ static float calc_reward(const KParams& P, Shared& S, int lane, const float* eff_replay = nullptr) {
+// terms (TERMS, the terms variant, only; else NULL): gets the five unweighted terms exp(-scale_k err_k) in reward_w's order - pose, velocity, end
+// effector, root pose, root velocity (_calc_reward_pose .. _calc_reward_root_velocity, :358-516) - and the reward is summed from them
+template <bool TERMS = false>
+__device__ static float calc_reward(const KParams& P, Shared& S, int lane, const float* eff_replay = nullptr, float* terms = nullptr) {
   const float* rp = &S.s[O(REF_POSE)];
   const float* rv = &S.s[O(REF_VEL)];
   if (lane < 8) {
@@ -340,6 +343,13 @@ __device__ static float calc_reward(const KParams& P, Shared& S, int lane, const
       d = rv[3 + k] - S.s[O(ANGVEL) + k]; we += d * d;
     }
     root_vel_err = ve + 0.1f * we;
+  }
+  if constexpr (TERMS) {
+    terms[0] = expf(-c.reward_scale[0] * pose_err); terms[1] = expf(-c.reward_scale[1] * vel_err); terms[2] = expf(-c.reward_scale[2] * ee_err);
+    terms[3] = expf(-c.reward_scale[4] * root_pose_err); terms[4] = expf(-c.reward_scale[5] * root_vel_err);
+    const float r = c.reward_w[0] * terms[0] + c.reward_w[1] * terms[1] + c.reward_w[2] * terms[2] + c.reward_w[3] * terms[3] + c.reward_w[4] * terms[4];
+    WSYNC();
+    return r;
   }
   const float r = c.reward_w[0] * expf(-c.reward_scale[0] * pose_err) + c.reward_w[1] * expf(-c.reward_scale[1] * vel_err) +
                   c.reward_w[2] * expf(-c.reward_scale[2] * ee_err) + c.reward_w[3] * expf(-c.reward_scale[4] * root_pose_err) +

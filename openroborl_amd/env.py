@@ -251,12 +251,16 @@ def action_space():
 class VecQuadrupedEnv(object):
     """N independent quadrupeds on one GPU; four robots per wavefront, 16 lanes each (see csrc/orr_env_kernels.h, orr_physics.h)."""
 
+    TERM_NAMES = _abi.REWARD_TERM_NAMES      # the columns of reward_terms / episode_term_sums / the term log, in orr_config::reward_w's order
+
     def __init__(self, task_name=None, training_yaml=None, sim_yaml=None, device="cuda", num_robot=None, seed=None,
                  robot=None, motion_file=None, mode=None, enable_randomizer=None, auto_reset=True, num_procs=1,
                  robot_index_offset=0, legacy_grid=False, mixed_robots=None, ep_log_capacity=65536, config_overrides=None,
                  model_overrides=None, clip_time_min=None, clip_time_max=None, perturb_init_state_prob=None, tar_obs_noise=None,
-                 init_perturb_std=None):
+                 init_perturb_std=None, reward_terms=False):
         import torch
+        if not isinstance(reward_terms, (bool, np.bool_)):
+            raise ValueError("reward_terms must be True or False, got %r" % (reward_terms,))
         self.torch = torch
         if not torch.cuda.is_available():
             raise RuntimeError("VecQuadrupedEnv needs a ROCm GPU (the HIP path has no CPU fallback)")
@@ -371,6 +375,10 @@ class VecQuadrupedEnv(object):
         if self.multi_clip:
             self.clip_log = torch.zeros(max(int(ep_log_capacity), 1), dtype=torch.int32, device=self.device)
             _lib.check(self.L.orr_bind_clip_log(self.h, self.clip_log.data_ptr()), self.L)
+        # per-term reward outputs (orr_bind_reward_terms): the five unweighted terms of every step's reward, their running sums over each
+        # robot's current episode and, next to the episode log, the sums of every logged episode.  While bound, the steps run the
+        # terms variant of the kernel
+        self.reward_terms = self.episode_term_sums = self.term_log = None
         # the three outputs of a step are views into ONE device buffer [obs N x 160 f32 | reward N f32 | done N u8], so that a host-side
         # consumer (LegacyListEnv) fetches them with a single copy
         nb_obs, nb_rew = num_robot * _abi.OBS_DIM * 4, num_robot * 4
@@ -383,6 +391,8 @@ class VecQuadrupedEnv(object):
         self._env_step_counter = 0
         self._closed = False
         self.launch_params_generation = 0     # bumped whenever something a launch takes by value changes (seed()): see there
+        if reward_terms:
+            self.bind_reward_terms(True)
 
     # ---- reference attribute surface -------------------------------------------------------
     @property
@@ -424,6 +434,23 @@ class VecQuadrupedEnv(object):
         spec = task_noise_spec(perturb_init_state_prob, tar_obs_noise, init_perturb_std)
         _lib.check(self.L.orr_set_task_noise(self.h, C.byref(spec)), self.L)
         self.task_noise = spec
+        self.launch_params_generation += 1
+
+    def bind_reward_terms(self, on=True):
+        """Bind (allocating on first use) or unbind the per-term reward outputs (orr_bind_reward_terms): env.reward_terms [N, 5], valid
+        after step / replay_step, env.episode_term_sums [N, 5] and env.term_log [ep_log_capacity, 5]; all None while unbound.  It
+        selects the kernel variant: holders of captured graphs re-capture (launch_params_generation)."""
+        t = self.torch
+        if on:
+            n = _abi.NUM_REWARD_TERMS
+            bufs = (t.zeros((self.num_robot, n), dtype=t.float32, device=self.device), t.zeros((self.num_robot, n), dtype=t.float32, device=self.device),
+                    t.zeros((self.ep_log.shape[0], n), dtype=t.float32, device=self.device))
+            _lib.check(self.L.orr_bind_reward_terms(self.h, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr()), self.L)
+            self.reward_terms, self.episode_term_sums, self.term_log = bufs
+        else:
+            t.cuda.synchronize(self.device)      # launches in flight still write the buffers
+            _lib.check(self.L.orr_bind_reward_terms(self.h, None, None, None), self.L)
+            self.reward_terms = self.episode_term_sums = self.term_log = None
         self.launch_params_generation += 1
 
     # ---- hot path ------------------------------------------------------------------------------
@@ -547,6 +574,19 @@ class VecQuadrupedEnv(object):
         cid = self.clip_log[:k].cpu().numpy()
         return {int(c): (float(ret[cid == c].mean()), int((cid == c).sum())) for c in np.unique(cid)}
 
+    def episode_reward_terms(self):
+        """{term name: mean of the term per step} over the episodes logged since the log was last cleared (sum of the episodes' term
+        sums / sum of their lengths), without clearing it (syncs); {} when no episode is logged.  Read it before a gather clears the
+        log, like episode_returns_by_clip.  Needs reward_terms=True."""
+        if self.term_log is None:
+            raise ValueError("no term log: the env was built without reward_terms=True")
+        k = int(self.torch.clamp(self.counters[_abi.CNT_EPISODES], max=self.ep_log.shape[0]).item())
+        if k == 0:
+            return {}
+        steps = float(self.ep_log[:k, 1].double().sum().item())
+        sums = self.term_log[:k].double().sum(0).cpu().numpy()
+        return {name: float(sums[i] / steps) for i, name in enumerate(self.TERM_NAMES)}
+
     def episode_log_device(self):
         """(log[K,2] snapshot, count, dropped) of the episodes finished since the last call, all on the device and
         without a host sync (count / dropped are 0-d int64 tensors; rows >= count are stale); clears the log."""
@@ -563,16 +603,21 @@ class VecQuadrupedEnv(object):
         _lib.check(self.L.orr_episode_stats(self.h, float(total_timesteps), int(capacity), out.data_ptr(), self._stream()), self.L)
         return out
 
-    def episode_log(self, with_dropped=False, with_clip=False):
+    def episode_log(self, with_dropped=False, with_clip=False, with_terms=False):
         """(returns[K], lengths[K]) of the episodes finished since the last call (+ clip_ids[K] int32, the clip each of them played,
-        when with_clip; + the number of episodes that did not fit the device log when with_dropped); clears the log.  Syncs.
-        with_clip needs a clip set of more than one clip (the clip log exists only then): ValueError otherwise."""
+        when with_clip; + term_sums[K, 5], each episode's sums of the five reward terms, when with_terms; + the number of episodes
+        that did not fit the device log when with_dropped); clears the log.  Syncs.
+        with_clip needs a clip set of more than one clip (the clip log exists only then), with_terms reward_terms=True: ValueError
+        otherwise."""
         if with_clip and self.clip_log is None:
             raise ValueError("no clip log: no robot type of this env has a clip set of more than one clip")
+        if with_terms and self.term_log is None:
+            raise ValueError("no term log: the env was built without reward_terms=True")
         clip_log = self.clip_log.clone() if with_clip else None
+        term_log = self.term_log.clone() if with_terms else None
         log, cnt, dropped = self.episode_log_device()
         k = int(cnt.item())
-        out = (log[:k, 0], log[:k, 1]) + ((clip_log[:k],) if with_clip else ())
+        out = (log[:k, 0], log[:k, 1]) + ((clip_log[:k],) if with_clip else ()) + ((term_log[:k],) if with_terms else ())
         if with_dropped:
             return out + (int(dropped.item()),)
         return out

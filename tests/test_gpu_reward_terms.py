@@ -1,0 +1,431 @@
+"""The per-term reward outputs of the HIP path (orr_bind_reward_terms; run with -m gpu on an MI355X): the five unweighted terms of every
+step's reward, their running sums over the episode and the episode log's term rows -
+
+  1. against the reference's own Python: the fixtures of tests/test_gpu_golden_task.py replayed with reward_terms=True, terms against
+     `step/terms`, bound per term 2 x (the float32 parity oracle's worst deviation on the same fixture and term) + 2^-22;
+  2. against the oracle on the product path: every robot and step of a mixed batch, orc_reward_probe in float64 as the reference and
+     in float32 as the floor, same rule;
+  3. identity (reward == w . terms) and bookkeeping (sums, log rows) with auto-reset;  4. the log's capacity;  5. the neighbours:
+     the step without the binding, large batches, clip sets + switching, task noise, friction anchors, unbinding.
+
+Measured maxima: profiles/reward_terms.txt."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from openroborl_amd import _abi, robots, state as statemod
+from tests import oracle_lib as ol
+from tests import reward_terms_lib as rt
+
+pytestmark = pytest.mark.gpu
+CLIP = {"laikago": "laikago_pace", "mini_cheetah": "minicheetah_trot"}
+EPS = 2.0 ** -24
+NAMES = _abi.REWARD_TERM_NAMES
+
+
+def identity_bound(w):
+    """|reward - sum_k w_k terms_k|: five products and four adds of values <= 1 in float32, whatever their order or contraction"""
+    return 16.0 * EPS * np.abs(w).sum()
+
+
+def stress(env, obs, rng):
+    import torch
+    noise = torch.from_numpy(rng.normal(0.0, 0.05, (env.num_robot, 12)).astype(np.float32)).to(env.device)
+    return env.stress_actions(obs, noise, torch.empty_like(noise))
+
+
+def mixed_env(n, **kw):
+    from openroborl_amd.env import VecQuadrupedEnv
+    mixed = ["laikago", "mini_cheetah"]
+    kw.setdefault("seed", 3)
+    kw.setdefault("mode", "train")
+    kw.setdefault("enable_randomizer", True)
+    return VecQuadrupedEnv(num_robot=n, mixed_robots=mixed, motion_file=[CLIP[m] for m in mixed], **kw)
+
+
+def short_episodes():
+    """ep_len_start = 8, ep_len_end = 24 with the curriculum as the fixtures set it"""
+    g = rt.fixture(rt.FIXTURES[0])
+    return dict(ep_len_start=8, ep_len_end=24, curriculum_steps=int(g["curriculum_steps"]))
+
+
+# ---- 1. against the reference's Python --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", rt.FIXTURES)
+def test_terms_reproduce_the_reference_python(name):
+    """The fixture replayed as tests/test_gpu_golden_task.py replays it, through the terms variant of the parity replay: observations,
+    torques, reward and done at that file's tolerances (the terms variant reproduces the reference with noise off), `terms` against
+    `step/terms` within 2 x the float32 parity oracle's worst deviation + 2^-22 per term, `term_sums` against the float64 cumulative
+    sums per episode within L x that bound + L^2 x 2^-25."""
+    import torch
+    from openroborl_amd.env import VecQuadrupedEnv
+    g = rt.fixture(name)
+    bound = rt.term_bound(rt.f32_floor(name))             # from the oracle (the reference), never from the device
+    ref_sums, length = rt.episode_sums(g)
+    robot, n = str(g["robot"]), int(g["num_robot"])
+    env = VecQuadrupedEnv(num_robot=n, robot=robot, motion_file=str(g["clip"]), mode="train", enable_randomizer=bool(g["randomizer"]), auto_reset=False,
+                          legacy_grid=True, seed=0, reward_terms=True,
+                          config_overrides=dict(ep_len_start=int(g["ep_start"]), ep_len_end=int(g["ep_end"]), curriculum_steps=int(g["curriculum_steps"])))
+    assert tuple(env.reward_terms.shape) == (n, 5) and tuple(env.episode_term_sums.shape) == (n, 5) and env.TERM_NAMES == NAMES
+    dev = env.device
+    m = env.models[int(env.robot_type[0])]
+    jom, mdir = np.asarray(m["joint_of_motor"]), np.asarray(m["motor_dir"])
+    traj = g["step/traj_f32"].astype(np.float64)
+    traj[..., 3:7] = g["step/traj_quat"]
+    f32 = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float32, device=dev)
+    w = rt.weights(env.cfg)
+    tau_out = torch.zeros((n, 33, 12), dtype=torch.float32, device=dev)
+    count, steps, worst, worst_sum, failures = 0, 0, np.zeros(5), np.zeros(5), []
+    for kind, idx in g["marks"]:
+        idx = int(idx)
+        if kind == 0.0:
+            env.counters[_abi.CNT_TOTAL_STEP_COUNT] = count
+            obs = env.replay_reset(f32(g["reset/uniforms"][idx])).cpu().numpy()
+            np.testing.assert_allclose(obs, g["reset/obs"][idx], atol=2e-5, err_msg="reset %d observation" % idx)
+            np.testing.assert_allclose(env.field("REF_POSE").cpu().numpy(), g["reset/ref_pose"][idx], atol=5e-6)
+            continue
+        S = lambda key: g["step/" + key][idx]
+        eff = np.stack([S("eff_sim"), S("eff_ref")], axis=1)
+        fall = torch.tensor(S("fall").astype(np.uint8), device=dev)
+        obs, rew, done = env.replay_step(f32(S("action")), f32(traj[idx]), f32(eff), fall, tau_out)
+        obs, rew, done = obs.cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy().astype(bool)
+        terms, sums = env.reward_terms.cpu().numpy(), env.episode_term_sums.cpu().numpy().astype(np.float64)
+        what = "%s step %d " % (name, idx)
+        tau = tau_out.cpu().numpy().astype(np.float64) * mdir[None, None, :]
+        np.testing.assert_allclose(tau, S("tau_urdf")[:, :, jom], atol=2e-3, rtol=2e-5, err_msg=what + "motor torques")
+        ro = S("obs")
+        np.testing.assert_allclose(obs[:, 0:12].reshape(n, 3, 4)[:, :, 0:2], ro[:, 0:12].reshape(n, 3, 4)[:, :, 0:2], atol=1e-5, err_msg=what + "IMU roll / pitch")
+        np.testing.assert_allclose(obs[:, 0:12].reshape(n, 3, 4)[:, :, 2:4], ro[:, 0:12].reshape(n, 3, 4)[:, :, 2:4], atol=1e-3, rtol=1e-5, err_msg=what + "IMU rates")
+        np.testing.assert_allclose(obs[:, 12:], ro[:, 12:], atol=1e-5, err_msg=what + "last actions / motor angles / target frames")
+        np.testing.assert_allclose(rew, S("reward"), atol=5e-6, err_msg=what + "reward")
+        np.testing.assert_array_equal(done, S("done").astype(bool), err_msg=what + "done")
+        np.testing.assert_allclose(env.field("REF_POSE").cpu().numpy(), S("ref_pose"), atol=1e-5, err_msg=what + "reference pose")
+        assert (np.abs(rew.astype(np.float64) - terms.astype(np.float64) @ w) <= identity_bound(w)).all(), what + "reward == w . terms"
+        e = np.abs(terms.astype(np.float64) - S("terms")).max(axis=0)
+        es = np.abs(sums - ref_sums[idx]).max(axis=0)
+        worst, worst_sum = np.maximum(worst, e), np.maximum(worst_sum, es / rt.sum_bound(length[idx], bound))
+        if (e > bound).any() or (es > rt.sum_bound(length[idx], bound)).any():
+            failures.append((idx, e, es))
+        steps += 1
+        if done.any():
+            count += n
+    print("REWARD_TERMS %s (%d steps): device max |d term| %s | bound %s | sums at most %.2f of their bound" % (
+        name, steps, " ".join("%s %.2e" % p for p in zip(NAMES, worst)), " ".join("%.2e" % b for b in bound), worst_sum.max()))
+    env.close()
+    assert steps == g["step/terms"].shape[0] and not failures, failures[:3]
+
+
+# ---- 2. against the oracle on the product path ------------------------------------------------------------------------------------
+def test_terms_match_the_oracle_on_every_robot_and_step():
+    """N = 37 (ten waves, the last with one valid robot), Laikago and mini-cheetah mixed, no auto-reset, randomiser on, 40 steps of
+    stress actions.  The post-step record with REF_POSE / REF_VEL of before the step put back is what the reward was computed from:
+    orc_reward_probe in float64 is the reference, the same probe of the float32 parity oracle the floor; every robot and step within
+    2 x (the floor's worst deviation per term) + 2^-22.  A non-finite record shows five zeros, reward 0 and ORR_DONE_NAN."""
+    import torch
+    n, nsteps = 37, 40
+    env = mixed_env(n, auto_reset=False, reward_terms=True)
+    kw = dict(robot_type=env.robot_type, clip_id=env.clip_id)
+    o64 = ol.OracleEnv(env.cfg, env.models, env.clips, n, **kw)
+    o32 = ol.OracleEnv(env.cfg, env.models, env.clips, n, f32="parity", **kw)
+    rt.declare_f32_probes(o32.L)
+    lay = env.layout
+    rng = np.random.RandomState(11)
+    obs = env.reset()
+    dev_terms, ref_terms, floor_terms = np.zeros((nsteps, n, 5)), np.zeros((nsteps, n, 5)), np.zeros((nsteps, n, 5))
+    finite = np.ones((nsteps, n), dtype=bool)
+    w = rt.weights(env.cfg)
+    for k in range(nsteps):
+        act = stress(env, obs, rng)
+        ref_pose, ref_vel = env.field("REF_POSE").clone(), env.field("REF_VEL").clone()
+        obs, rew, done, _ = env.step(act)
+        rec = env.state.clone()
+        rec[:, lay.sl("REF_POSE")] = ref_pose
+        rec[:, lay.sl("REF_VEL")] = ref_vel
+        st64 = statemod.to_float64(lay, rec.cpu().numpy())
+        st32 = np.ascontiguousarray(st64.astype(np.float32))
+        terms, rew = env.reward_terms.cpu().numpy(), rew.cpu().numpy()
+        reason = env.field_int("DONE_REASON")[:, 0].cpu().numpy()
+        assert (np.abs(rew.astype(np.float64) - terms.astype(np.float64) @ w) <= identity_bound(w)).all()
+        for i in range(n):
+            if reason[i] & _abi.DONE_NAN or not np.isfinite(st64[i, 0:37]).all():
+                finite[k, i] = False
+                assert not terms[i].any() and rew[i] == 0.0 and reason[i] & _abi.DONE_NAN, (k, i, terms[i], rew[i], reason[i])
+                continue
+            t64, t32 = np.zeros(5), np.zeros(5, dtype=np.float32)
+            o64.L.orc_reward_probe(o64.h, ol.P(np.ascontiguousarray(st64[i])), ol.P(t64))
+            o32.L.orc_reward_probe(o32.h, st32[i].ctypes.data_as(rt.fp), t32.ctypes.data_as(rt.fp))
+            dev_terms[k, i], ref_terms[k, i], floor_terms[k, i] = terms[i], t64, t32
+    floor = np.abs(floor_terms - ref_terms)[finite].max(axis=0)
+    bound = rt.term_bound(floor)
+    err = np.abs(dev_terms - ref_terms)[finite]
+    print("REWARD_TERMS product path (%d robots x %d steps, %d non-finite records): device max |d term| %s | float32 oracle %s | terms span %.3g .. %.3g" % (
+        n, nsteps, (~finite).sum(), " ".join("%s %.2e" % p for p in zip(NAMES, err.max(axis=0))), " ".join("%.2e" % f for f in floor),
+        dev_terms[finite].min(), dev_terms[finite].max()))
+    env.close(); o64.close(); o32.close()
+    assert np.isfinite(floor).all() and (floor > 0).all()
+    assert finite.sum() > 0.9 * finite.size and dev_terms[finite].min() < 0.9 and dev_terms[finite].max() > 0.9     # the run covers small and large terms
+    assert (err <= bound).all(), (err.max(axis=0), bound)
+
+
+# ---- 3. identity and bookkeeping --------------------------------------------------------------------------------------------------
+def bookkeeping_run(n=37, nsteps=80, seed=3, ep_log_capacity=65536, bind=None, **kw):
+    """`nsteps` stress-action steps with auto-reset and short episodes.  Checks the identity every step and the sums at every episode
+    end; returns the device's terms / sums of every step (float32 bits), the host's per-episode records [(robot, length, float64 sums,
+    the device's float32 sums, return)] and the env (open)."""
+    kw.setdefault("config_overrides", short_episodes())
+    kw.setdefault("auto_reset", True)
+    env = mixed_env(n, seed=seed, ep_log_capacity=ep_log_capacity, reward_terms=bind is None, **kw)
+    if bind is not None:
+        bind(env)
+    w = rt.weights(env.cfg)
+    rng = np.random.RandomState(7)
+    obs = env.reset()
+    acc, length = np.zeros((n, 5)), np.zeros(n, dtype=int)
+    all_terms, all_sums, episodes = [], [], []
+    for k in range(nsteps):
+        act = stress(env, obs, rng)
+        obs, rew, done, _ = env.step(act)
+        terms, sums = env.reward_terms.cpu().numpy(), env.episode_term_sums.cpu().numpy()
+        rew, done = rew.cpu().numpy(), done.cpu().numpy().astype(bool)
+        last_ret = env.field("LAST_EP_RETURN")[:, 0].cpu().numpy()
+        assert np.isfinite(terms).all() and (terms >= 0).all() and (terms <= 1).all()
+        assert (np.abs(rew.astype(np.float64) - terms.astype(np.float64) @ w) <= identity_bound(w)).all(), "step %d: reward == w . terms" % k
+        acc += terms
+        length += 1
+        # the running sums: the row holds the current episode's totals after every step, the ending one included
+        assert (np.abs(sums - acc) <= (length * length * 2.0 ** -25)[:, None]).all(), "step %d: running sums" % k
+        for i in np.nonzero(done)[0]:
+            episodes.append((int(i), int(length[i]), acc[i].copy(), sums[i].copy(), float(last_ret[i])))
+            if env.cfg.flags & _abi.FLAG_AUTO_RESET:
+                acc[i], length[i] = 0.0, 0
+        all_terms.append(terms)
+        all_sums.append(sums)
+    return np.stack(all_terms), np.stack(all_sums), episodes, env
+
+
+def check_log(env, episodes, logged=None):
+    """Every logged row: |w . term_log[slot] - ep_log[slot, 0]| <= L x 16 x 2^-24 + L^2 x 2^-25 with L = ep_log[slot, 1], and the log's
+    (return, length, term row) triples are the host's per-episode ones (the device's own float32 sums at the ending step) as a multiset."""
+    w = rt.weights(env.cfg)
+    k = len(episodes) if logged is None else logged
+    assert int(env.counters[_abi.CNT_EPISODES].item()) == len(episodes)
+    ep_log, term_log = env.ep_log[:k].cpu().numpy(), env.term_log[:k].cpu().numpy()
+    L = ep_log[:, 1].astype(np.float64)
+    assert (np.abs(term_log.astype(np.float64) @ w - ep_log[:, 0]) <= L * 16 * EPS + L * L * 2.0 ** -25).all()
+    rows = sorted((np.float32(r).tobytes(), l, s.astype(np.float32).tobytes()) for _, l, _, s, r in episodes)
+    got = sorted((ep_log[j, 0].tobytes(), int(ep_log[j, 1]), term_log[j].tobytes()) for j in range(k))
+    if logged is None:
+        assert got == rows
+    else:
+        assert all(g in rows for g in got) and len(got) == logged
+    return ep_log, term_log
+
+
+def canonical_log(env, k):
+    """The first k rows of the episode log with their term rows, in an order that does not depend on which wave's slot request
+    arrived first (the slots of one launch go by arrival)"""
+    rows = np.concatenate([env.ep_log[:k].cpu().numpy(), env.term_log[:k].cpu().numpy()], axis=1)
+    return rows[np.lexsort(rows.T[::-1])].tobytes()
+
+
+def test_identity_sums_and_log_rows_with_auto_reset():
+    """N = 37, auto-reset, episodes of 8 .. 24 steps, 80 steps: the identity every step, the host's float64 accumulation of `terms`
+    per robot and episode against term_sums right after the ending step (L^2 x 2^-25), the log's rows, and a second run giving
+    identical bytes in all three buffers (the log up to the arrival order of one launch's slots)."""
+    terms_a, sums_a, episodes, env = bookkeeping_run()
+    assert len(episodes) >= 3 * 37 and len({l for _, l, _, _, _ in episodes}) >= 3          # several lengths: the curriculum moves the limit
+    for i, l, acc, s, _ in episodes:
+        assert (np.abs(acc - s) <= l * l * 2.0 ** -25).all(), (i, l)
+    check_log(env, episodes)
+    names = env.episode_reward_terms()
+    tot = sum(l for _, l, _, _, _ in episodes)
+    want = np.sum([s.astype(np.float64) for _, _, _, s, _ in episodes], axis=0) / tot
+    assert list(names) == list(NAMES) and np.allclose([names[k] for k in NAMES], want, rtol=1e-12)
+    ret, ln, tl = env.episode_log(with_terms=True)
+    assert tuple(tl.shape) == (len(episodes), 5) and ret.shape[0] == len(episodes)
+    log_a = np.concatenate([ret.cpu().numpy()[:, None], ln.cpu().numpy()[:, None], tl.cpu().numpy()], axis=1)
+    assert env.episode_reward_terms() == {}                       # the gather cleared the log
+    env.close()
+    terms_b, sums_b, episodes_b, env = bookkeeping_run()
+    assert terms_a.tobytes() == terms_b.tobytes() and sums_a.tobytes() == sums_b.tobytes()
+    assert log_a[np.lexsort(log_a.T[::-1])].tobytes() == canonical_log(env, len(episodes_b))
+    env.close()
+
+
+def test_episode_log_with_terms_needs_the_binding():
+    env = mixed_env(5)
+    assert env.reward_terms is None and env.episode_term_sums is None
+    with pytest.raises(ValueError, match="reward_terms"):
+        env.episode_log(with_terms=True)
+    with pytest.raises(ValueError, match="reward_terms"):
+        env.episode_reward_terms()
+    # terms without sums: refused, nothing changed
+    buf = env.torch.zeros((5, 5), device=env.device)
+    assert env.L.orr_bind_reward_terms(env.h, buf.data_ptr(), None, None) == -1 and b"term_sums_dev" in env.L.orr_last_error()
+    env.close()
+
+
+# ---- 4. log capacity --------------------------------------------------------------------------------------------------------------
+def test_a_full_log_drops_the_term_rows_too():
+    """ep_log_capacity = 4 and a term_log of 8 rows whose last 4 hold a canary: rows 0..3 are written, the canary rows are untouched,
+    ORR_CNT_EPLOG_DROPPED counts the episodes beyond 4."""
+    bufs = {}
+
+    def bind(env):
+        t = env.torch
+        bufs["terms"], bufs["sums"] = t.zeros((env.num_robot, 5), device=env.device), t.zeros((env.num_robot, 5), device=env.device)
+        bufs["log"] = t.full((8, 5), -7.0, device=env.device)
+        assert env.ep_log.shape[0] == 4
+        assert env.L.orr_bind_reward_terms(env.h, bufs["terms"].data_ptr(), bufs["sums"].data_ptr(), bufs["log"].data_ptr()) == 0
+        env.reward_terms, env.episode_term_sums, env.term_log = bufs["terms"], bufs["sums"], bufs["log"]
+    _, _, episodes, env = bookkeeping_run(ep_log_capacity=4, bind=bind)
+    assert len(episodes) > 4
+    log = bufs["log"].cpu().numpy()
+    assert (log[4:] == -7.0).all() and (log[:4] != -7.0).all()
+    assert int(env.counters[_abi.CNT_EPLOG_DROPPED].item()) == len(episodes) - 4
+    check_log(env, episodes, logged=4)
+    env.close()
+
+
+# ---- 5. neighbours ----------------------------------------------------------------------------------------------------------------
+def test_one_step_with_and_without_the_binding_agrees():
+    """One reset state, one action batch, one env step through the terms variant and through the default kernel: different
+    translation units, so closeness at the one-sub-step parity bounds of tests/test_gpu_parity.py (positions 2e-6, velocities 1.5e-4,
+    absolute + relative), not bit equality.  Whether 40 steps stay bit-identical is printed, not asserted."""
+    import torch
+    n = 37
+    a, b = mixed_env(n, auto_reset=False, reward_terms=True), mixed_env(n, auto_reset=False)
+    oa, ob = a.reset(), b.reset()
+    assert torch.equal(oa, ob) and torch.equal(a.state.view(torch.int32), b.state.view(torch.int32))      # noise off: the noise reset is the default one
+    rng = np.random.RandomState(2)
+    act = stress(a, oa, rng)
+    (oa, ra, da, _), (ob, rb, db, _) = a.step(act), b.step(act)
+    sa, sb = a.state.cpu().numpy().astype(np.float64), b.state.cpu().numpy().astype(np.float64)
+    for names, tol in ((("POS", "QUAT", "Q"), 2e-6), (("LINVEL", "ANGVEL", "QD"), 1.5e-4)):
+        for name in names:
+            sl = a.layout.sl(name)
+            np.testing.assert_allclose(sa[:, sl], sb[:, sl], atol=tol, rtol=tol, err_msg=name)
+    np.testing.assert_allclose(ra.cpu().numpy(), rb.cpu().numpy(), atol=5e-6)
+    assert torch.equal(da, db)
+    same = True
+    for k in range(39):
+        act = stress(b, ob, rng)
+        (oa, ra, da, _), (ob, rb, db, _) = a.step(act), b.step(act)
+        same = same and torch.equal(a.state.view(torch.int32), b.state.view(torch.int32)) and torch.equal(ra, rb)
+    print("REWARD_TERMS 40 steps with and without the binding bit-identical: %s" % bool(same))
+    a.close(); b.close()
+
+
+def test_more_waves_than_simds_stay_on_the_terms_kernel():
+    """N = 4100: one step writes finite terms for every robot (a fall-back to the two-wave kernel would leave the canary) and the
+    identity holds."""
+    import torch
+    n = 4100
+    env = mixed_env(n, auto_reset=True, reward_terms=True)
+    obs = env.reset()
+    env.reward_terms.fill_(-7.0); env.episode_term_sums.fill_(-7.0)
+    obs, rew, done, _ = env.step(stress(env, obs, np.random.RandomState(0)))
+    terms, sums, w = env.reward_terms.cpu().numpy(), env.episode_term_sums.cpu().numpy(), rt.weights(env.cfg)
+    assert np.isfinite(terms).all() and (terms >= 0).all() and (terms <= 1).all() and (terms > 0).any()
+    assert (terms == sums).all()                                           # the first step of the episode overwrites the row
+    assert (np.abs(rew.cpu().numpy().astype(np.float64) - terms.astype(np.float64) @ w) <= identity_bound(w)).all()
+    env.close()
+
+
+def test_with_clip_sets_and_switching(tmp_path):
+    """A four-clip set with a switch interval: the identity and the log rows hold with auto-reset; without it (a robot's CLIP_ID after
+    its ending step is the clip the episode played) the (clip, return, term row) triples of the log's slots are the host's, i.e.
+    clip_log and term_log rows of one slot belong to the same episode."""
+    from tests.test_gpu_clip_switch import set4
+    from openroborl_amd.env import VecQuadrupedEnv
+
+    def run(auto_reset):
+        env = VecQuadrupedEnv(num_robot=37, robot="laikago", motion_file=set4(tmp_path), mode="train", enable_randomizer=True, auto_reset=auto_reset, seed=5,
+                              clip_time_min=0.1, clip_time_max=0.3, reward_terms=True, config_overrides=short_episodes())
+        assert env.clip_log is not None
+        w = rt.weights(env.cfg)
+        rng = np.random.RandomState(3)
+        obs = env.reset()
+        triples, clips_seen = [], set()
+        for k in range(40):
+            obs, rew, done, _ = env.step(stress(env, obs, rng))
+            terms = env.reward_terms.cpu().numpy().astype(np.float64)
+            assert (np.abs(rew.cpu().numpy().astype(np.float64) - terms @ w) <= identity_bound(w)).all()
+            d = done.cpu().numpy().astype(bool)
+            cid, ret, sums = env.field_int("CLIP_ID")[:, 0].cpu().numpy(), env.field("LAST_EP_RETURN")[:, 0].cpu().numpy(), env.episode_term_sums.cpu().numpy()
+            clips_seen |= set(cid.tolist())
+            triples += [(int(cid[i]), ret[i].tobytes(), sums[i].tobytes()) for i in np.nonzero(d)[0]]
+        k = int(env.counters[_abi.CNT_EPISODES].item())
+        assert k == len(triples) >= 37 and len(clips_seen) >= 3
+        ep_log, term_log, clip_log = env.ep_log[:k].cpu().numpy(), env.term_log[:k].cpu().numpy(), env.clip_log[:k].cpu().numpy()
+        L = ep_log[:, 1].astype(np.float64)
+        assert (np.abs(term_log.astype(np.float64) @ w - ep_log[:, 0]) <= L * 16 * EPS + L * L * 2.0 ** -25).all()
+        got = sorted((int(clip_log[j]), ep_log[j, 0].tobytes(), term_log[j].tobytes()) for j in range(k))
+        if auto_reset:           # (CLIP_ID is the next episode's by now: the pairs without the clip)
+            assert sorted(g[1:] for g in got) == sorted(t[1:] for t in triples)
+        else:
+            assert got == sorted(triples)
+        env.close()
+    run(True)
+    run(False)
+
+
+def test_with_task_noise():
+    """Perturbed initial states and target-heading noise on: the identity, the sums and the log rows hold as without."""
+    _, _, episodes, env = bookkeeping_run(nsteps=40, perturb_init_state_prob=0.5, tar_obs_noise=[0.1])
+    assert len(episodes) >= 37
+    check_log(env, episodes)
+    env.close()
+
+
+def test_friction_anchors_are_refused_at_bind_and_at_launch():
+    import torch
+    from openroborl_amd.env import VecQuadrupedEnv
+    kw = dict(num_robot=8, robot="laikago", motion_file="laikago_pace", mode="test", enable_randomizer=False, seed=5)
+    with pytest.raises(RuntimeError, match="orr_bind_reward_terms: friction anchors"):
+        VecQuadrupedEnv(reward_terms=True, model_overrides={"laikago": {"friction_anchor": 1}}, **kw)
+    anchored = VecQuadrupedEnv(model_overrides={"laikago": {"friction_anchor": 1}}, **kw)
+    assert anchored.L.orr_bind_reward_terms(anchored.h, None, None, None) == 0             # unbinding an anchor handle is fine
+    with pytest.raises(RuntimeError, match="friction anchors"):
+        anchored.bind_reward_terms(True)
+    assert anchored.reward_terms is None
+    anchored.reset(); anchored.step(torch.zeros(8, 12, device=anchored.device))               # nothing changed: the anchor kernels run
+    anchored.close()
+    # an anchor model set on a handle with the terms bound: every launch is refused and nothing runs
+    env = VecQuadrupedEnv(reward_terms=True, **kw)
+    env.reset()
+    act = torch.zeros(8, 12, device=env.device)
+    env.step(act)
+    t = robots.ROBOT_TYPE_ID["laikago"]
+    m = dict(env.models[t])
+    m["friction_anchor"] = 1
+    assert env.L.orr_set_model(env.h, t, C.byref(robots.to_struct(m))) == 0
+    torch.cuda.synchronize()
+    before = env.state.clone(), env.reward_terms.clone(), env.episode_term_sums.clone()
+    with pytest.raises(RuntimeError, match=r"orr_reset: friction anchors \(orr_model::friction_anchor\) and reward terms \(orr_bind_reward_terms\) cannot be combined"):
+        env.reset()
+    with pytest.raises(RuntimeError, match=r"orr_step: friction anchors .* reward terms"):
+        env.step(act)
+    torch.cuda.synchronize()
+    assert torch.equal(env.state.view(torch.int32), before[0].view(torch.int32)) and torch.equal(env.reward_terms, before[1]) and torch.equal(env.episode_term_sums, before[2])
+    env.close()
+
+
+def test_after_unbinding_the_env_is_the_one_that_never_bound():
+    """Bound, unbound again, then reset + 20 steps: observations, rewards, dones and records byte-identical to an env that never bound
+    (the handle launches exactly the kernels it launched before)."""
+    import torch
+    a, b = mixed_env(37, auto_reset=True, reward_terms=True, config_overrides=short_episodes()), mixed_env(37, auto_reset=True, config_overrides=short_episodes())
+    gen = a.launch_params_generation
+    a.bind_reward_terms(False)
+    assert a.reward_terms is None and a.term_log is None and a.launch_params_generation == gen + 1
+    oa, ob = a.reset(), b.reset()
+    rng = np.random.RandomState(4)
+    for k in range(20):
+        act = stress(b, ob, rng)
+        (oa, ra, da, _), (ob, rb, db, _) = a.step(act), b.step(act)
+        assert torch.equal(oa, ob) and torch.equal(ra, rb) and torch.equal(da, db), k
+    assert torch.equal(a.state.view(torch.int32), b.state.view(torch.int32)) and torch.equal(a.counters, b.counters)
+    la, lb = a.ep_log.cpu().numpy(), b.ep_log.cpu().numpy()                 # (the slots of one launch go by arrival: rows in a canonical order)
+    assert la[np.lexsort(la.T[::-1])].tobytes() == lb[np.lexsort(lb.T[::-1])].tobytes() and int(a.counters[_abi.CNT_EPISODES].item()) >= 37
+    a.close(); b.close()

@@ -40,6 +40,10 @@ def main():
     ap.add_argument("--tar-obs-noise", type=float, default=None,
                     help="standard deviation (rad) of the noise on the heading the target observations are expressed in (ImitationTask's "
                          "tar_obs_noise[0]; overrides the task YAML's; default: none)")
+    ap.add_argument("--reward-terms", action="store_true",
+                    help="also output the five unweighted terms of the imitation reward on the device (pose, velocity, end effector, root pose, "
+                         "root velocity): every logged record gains \"reward_terms\": {name: mean per step} over the episodes THIS rank finished "
+                         "in the segment (rank-local, unlike the gathered episode means); --eval: over each robot's episode")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
     ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip")
@@ -74,7 +78,8 @@ def main():
     torch.cuda.set_device(dev)
     env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
                           device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
-                          perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise, **clip_time_kwargs(args))
+                          perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise,
+                          reward_terms=args.reward_terms, **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     model = ppo.ActorCritic(dev, params=params, seed=args.seed)                     # same seed -> identical replicas
     if not args.torch_policy:
@@ -124,6 +129,7 @@ def main():
         log_it = rank == 0 and (it % 10 == 0 or it == args.iters - 1)
         # this rank's episodes of the segment by clip (read before the gather below clears the log)
         by_clip = env.episode_returns_by_clip() if log_it and env.multi_clip else None
+        by_term = env.episode_reward_terms() if log_it and args.reward_terms else None     # likewise; rank-local
         stats = odist.gather_env_episodes(env, args.horizon)   # means come from the exact per-rank sums, not the truncated list
         if log_it:
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2),
@@ -133,6 +139,8 @@ def main():
                    "max_ep_steps": int(env.field_int("MAX_EP_STEPS").max()), "surr": round(float(surr), 4), "vf": round(float(vf), 4)}
             if by_clip is not None:
                 rec["ep_ret_mean_by_clip"] = {clip_name(env, c): round(r, 2) for c, (r, _) in sorted(by_clip.items())}
+            if by_term is not None:
+                rec["reward_terms"] = {k: round(v, 4) for k, v in by_term.items()}
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if rank == 0 and args.save:
@@ -160,7 +168,7 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     dev = torch.device("cuda", 0)
     n = min(args.num_robot, 1024)
     env = VecQuadrupedEnv(task_name=args.task, num_robot=n, mode="test", auto_reset=False, seed=args.seed, device=dev,
-                          motion_file=args.motion_file, **clip_time_kwargs(args))
+                          motion_file=args.motion_file, reward_terms=args.reward_terms, **clip_time_kwargs(args))
     model = ppo.ActorCritic(dev, params=pol.load_parameters(args.eval))
     if not args.torch_policy:
         model.enable_fused()
@@ -169,11 +177,14 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     ret = torch.zeros(n, device=dev)
     length = torch.zeros(n, device=dev)
+    term_sum = torch.zeros(len(env.TERM_NAMES), dtype=torch.float64, device=dev)      # --reward-terms: over every robot's steps up to its first done
     limit = int(env.field_int("MAX_EP_STEPS").max())
     for _ in range(limit):
         act, _, _ = model.act(obs, deterministic=True)
         obs, rew, done, _ = env.step(act)
         ret += rew * alive
+        if args.reward_terms:
+            term_sum += (env.reward_terms * alive[:, None]).sum(0)
         length += alive.float()
         alive &= ~done.bool()
         if not bool(alive.any()):
@@ -187,6 +198,8 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
         cid = clip_ids.cpu().numpy()
         rec["full_length_fraction_by_clip"] = {clip_name(env, int(c)): round(float(full[cid == c].mean()), 3) for c in np.unique(cid)}
         rec["robots_by_clip"] = {clip_name(env, int(c)): int((cid == c).sum()) for c in np.unique(cid)}
+    if args.reward_terms:
+        rec["reward_terms"] = {k: round(float(v), 4) for k, v in zip(env.TERM_NAMES, (term_sum / length.sum()).tolist())}
     print(json.dumps(rec))
     env.close()
 
