@@ -323,6 +323,30 @@ int32_t orr_sizeof_task_noise(void);
  * type with friction anchors (a launch refuses the combination too when such a model is set afterwards). */
 int32_t orr_bind_reward_terms(orr_handle* h, float* terms_dev, float* term_sums_dev, float* term_log_dev);
 
+/* foot contact outputs: what the step kernel's ground-contact solver found, per robot and leg.  Legs in the order of the record's
+ * LAMBDA field (slot 3 leg + d: normal, friction along world x, friction along world y).  Impulses in N s.
+ * contact_dev float[N][16] (device), row = [leg 0..3][4]: every orr_step (orr_time_steps) and every orr_debug_physics writes, for every
+ *   robot of the shard, per leg: [0] the sum over the launch's sub-steps (action_repeat of them; orr_debug_physics: its nsub) of the
+ *   leg's normal contact impulse, [1] [2] the sums of its two friction impulses, [3] the largest normal impulse of any one sub-step.
+ *   sum / (action_repeat * sim_dt) = the mean force over the step, in N.  The sums are plain float32 adds in sub-step order from 0, the
+ *   maximum starts from 0 too; a leg without a contact row in a sub-step contributes the zeros that LAMBDA holds for it.  A step that
+ *   sets ORR_DONE_NAN writes sixteen zeros.  With auto-reset the row is the step's that ended the episode; no reset touches the buffer.
+ * contact_ep_dev float[N][8] (device), row = [leg 0..3][2], updated by orr_step only: [0] the number of env steps of the robot's
+ *   current episode whose normal sum was > 0 (a float), [1] the sum of those normal sums.  A step whose EP_STEP before the step is 0
+ *   OVERWRITES the row, every other step adds to it: after the step that ends an episode the row holds that episode's totals - with
+ *   auto-reset too - until the robot's next step.  No reset touches it.
+ * contact_log_dev float[ep_log_capacity][8] (device), or NULL: episode-log row `slot` also gets the ending episode's contact_ep row, as
+ *   orr_bind_reward_terms adds the term sums.  The capacity is orr_bind's; a dropped row (slot >= capacity) writes nothing.
+ * contact_dev == NULL unbinds everything: the handle then launches exactly the kernels it launched before.  Otherwise contact_ep_dev
+ * must be non-NULL too, and every buffer given 16-byte aligned.  While bound, orr_step and orr_debug_physics launch the contact variants
+ * of the step kernel (orr_step: the task-noise variant + the sums, also together with orr_bind_reward_terms; one wave per SIMD at any
+ * batch size; with no clip set and all noise zero they compute what the default kernels compute) and the resets the task-noise
+ * variant.  The parity replays (orr_debug_replay_step / _reset) replace the physics by recorded states: they run what they run
+ * without the binding and leave the buffers alone.  Refused, nothing changed: a null handle, contact_dev without contact_ep_dev, a
+ * misaligned buffer, a robot type with friction anchors (a launch refuses the combination too, and launches nothing, when such a
+ * model is set afterwards). */
+int32_t orr_bind_contact_outputs(orr_handle* h, float* contact_dev, float* contact_ep_dev, float* contact_log_dev);
+
 /* replaces WrapperEnv.reset (wrapper_env.py:87-107): mask_dev NULL = all robots; obs_dev [N,160]
  * (rows of robots that are not reset are left untouched). */
 int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream);

@@ -36,6 +36,11 @@ NUM_COUNTERS = 8
 # the columns, in orr_config::reward_w's order
 NUM_REWARD_TERMS = 5
 REWARD_TERM_NAMES = ("pose", "velocity", "end_effector", "root_pose", "root_velocity")
+# orr_bind_contact_outputs: int32_t (orr_handle*, float* contact_dev [N][16], float* contact_ep_dev [N][8], float* contact_log_dev [ep_log_capacity][8] | NULL);
+# contact_dev row = [leg][normal sum, friction x sum, friction y sum, largest normal], contact_ep_dev row = [leg][stance steps, normal sum]
+CONTACT_OUT_DIM = 16
+CONTACT_EP_DIM = 8
+CONTACT_COLUMNS = ("normal", "friction_x", "friction_y", "normal_max")
 
 
 class OrrConfig(C.Structure):

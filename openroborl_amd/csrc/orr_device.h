@@ -118,10 +118,16 @@ struct DevTables {
   float* terms;                                       // [N][5] the unweighted terms of the step's reward, or NULL = not bound
   float* term_sums;                                   // [N][5] their running sums over the robot's current episode
   float* term_log;                                    // [ep_log_capacity][5] sums of each logged episode (row = episode-log slot), or NULL
+  // foot contact outputs (orr_bind_contact_outputs), read by the contact variants only (orr_kernels_contacts.hip).  APPENDED likewise
+  float* contact_out;                                 // [N][16] per leg: sums of the launch's normal / friction x / friction y impulses, largest normal impulse; NULL = not bound
+  float* contact_ep;                                  // [N][8] per leg: stance steps and sum of the normal sums over the robot's current episode
+  float* contact_log;                                 // [ep_log_capacity][8] contact_ep row of each logged episode (row = episode-log slot), or NULL
 };
 // Flag bit of orr_step_kernel's MODE: the variant that also writes the reward terms.  MODE & 3 is the mode proper (0 env step, 1 debug
 // physics, 2 parity replay).  A bit of MODE rather than a template parameter of its own: the older variants keep their mangled names
 constexpr int kModeTerms = 4;
+// Likewise: the variant that also sums the sub-steps' foot contact impulses (orr_bind_contact_outputs).  Env step and debug physics only
+constexpr int kModeContacts = 8;
 static_assert(sizeof(orr_task_noise) == 32, "the noise variants read it as eight words");
 
 // Replay inputs of the parity entry points orr_debug_replay_reset / orr_debug_replay_step (kernel MODE 2): the scripted states,

@@ -1,11 +1,12 @@
 // orr_env_kernels.h -- the two env kernels (orr_reset_kernel, orr_step_kernel) and their launchers, as templates.
 //
-// Included by the six translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
+// Included by the seven translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
 // several: DESIGN.md section 3).  orr_kernels.hip: the default kernels + the C-ABI, instruction-level-parallelism scheduler (one wave per
 // SIMD, ~300 registers, nothing to hide latency but the wave's own independent instructions).  orr_kernels_w2.hip: the
 // two-waves-per-SIMD step kernel, its own flags.  orr_kernels_anchor.hip: the friction-anchor variants.  orr_kernels_multiclip.hip:
 // the clip-set variants.  orr_kernels_noise.hip: the task-noise variants (clip sets + perturbed initial states + target-heading noise).
 // orr_kernels_terms.hip: the noise variant of the step that also writes the per-term reward outputs (orr_bind_reward_terms).
+// orr_kernels_contacts.hip: the variants that also sum the sub-steps' foot contact impulses (orr_bind_contact_outputs).
 // An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
 // per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
 // template` only (bottom of this file).
@@ -152,11 +153,19 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
 // batch size): lanes 0..4 of a robot also store the five unweighted terms of the step's reward, keep their running sums over the episode
 // in a caller-owned buffer and add the sums to the episode-log row (orr_bind_reward_terms).  All of it outside the sub-step loop.  A bit
 // of MODE, not a sixth parameter: the names above stay as they are
+// CONTACTS = MODE & kModeContacts (orr_kernels_contacts.hip; the env step on top of CLIPS and NOISE, with and without TERMS, and the debug
+// physics; one wave per SIMD whatever the batch size): after every sub-step lanes 0..11 of a robot read their own word of the record's
+// LAMBDA (slot 3 leg + d: the sub-step's normal and two friction impulses of a leg, 0 for an open contact) back from the LDS image and
+// keep a running sum and a running maximum in registers: one LDS read, an add and a max per sub-step, nothing inside physics_substep.
+// The row of the episode's totals is loaded with the reference frames, the stores come at the step's end, the log row goes where
+// term_log's goes (orr_bind_contact_outputs)
 template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false, bool NOISE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
   constexpr bool TERMS = (MODE & kModeTerms) != 0;
   static_assert(!TERMS || (MODE & 3) != 1, "the debug physics computes no reward");
+  constexpr bool CONTACTS = (MODE & kModeContacts) != 0;
+  static_assert(!CONTACTS || (MODE & 3) != 2, "the parity replay replaces the physics by recorded states: it has no impulses");
   ORR_PROLOGUE();
   const bool valid = in_range;
   const orr_config& c = P.cfg;
@@ -208,6 +217,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       }
     }
   };
+  // CONTACTS: lane l < 12 owns LAMBDA word l = (leg l / 3, direction l % 3: normal, friction x, friction y); lanes 12..15 repeat word 0.
+  // The sum over the launch's sub-steps and the largest single value (read from the normal lanes only), both from 0
+  typedef float __attribute__((address_space(1)))* gcontact;
+  const int cw = lane < 12 ? lane : 0;
+  float c_sum = 0.0f, c_max = 0.0f;
+  auto accumulate_contacts = [&]() __attribute__((always_inline)) {      // behind physics_substep's closing WSYNC
+    if constexpr (CONTACTS) {
+      const float lw = S.s[O(LAMBDA) + cw];
+      c_sum += lw;
+      c_max = fmaxf(c_max, lw);
+    }
+  };
+  auto store_contacts = [&]() __attribute__((always_inline)) {           // row [leg][sum n, sum t1, sum t2, max n]: the normal lanes store two words
+    if constexpr (CONTACTS) {
+      if (valid && lane < 12) {
+        const int cleg = lane / 3, cd = lane - 3 * cleg;
+        gcontact const row = (gcontact)P.tab->contact_out + (size_t)robot * 16 + 4 * cleg;
+        row[cd] = c_sum;
+        if (cd == 0) row[3] = c_max;
+      }
+    }
+  };
   PT(0);
 
   if ((MODE & 3) == 1) {
@@ -223,6 +254,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     int limit_idle = 0;
     for (int s = 0; s < nsub; s++) {
       fall = physics_substep<ANCHOR>(P, S, K, lane, sub, true, X, limit_idle, ANCHOR ? &AS : nullptr, anchor_robot);
+      accumulate_contacts();
       float rel[4], Rb[9];
       base_rotation(S, lane, rel, Rb);
       WSYNC();
@@ -230,6 +262,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     if (valid && lane == 0 && done_out) done_out[robot] = (uint8_t)fall;
     store_robot(rec, S, lane, valid);
     store_anchor();
+    store_contacts();
     return;
   }
 
@@ -336,6 +369,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
         fall = RP.fall[robot];
       } else
       fall = physics_substep<ANCHOR>(P, S, K, lane, sub, sstep == c.action_repeat - 1, X, limit_idle, ANCHOR ? &AS : nullptr, anchor_robot);
+      accumulate_contacts();
       qm_c = (S.s[O(Q) + mj] - m_off) * m_dir;
       qdm_c = S.s[O(QD) + mj] * m_dir;
       ring_push_and_ctrl_obs(rec, S, lane, valid, F, ring, qm_c, &co_own);
@@ -419,6 +453,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   if constexpr (TERMS) {
     if (lane < 5) term_sum = ((gterm)P.tab->term_sums)[(size_t)robot * 5 + lane];
   }
+  // CONTACTS: lanes 0..7 own the robot's row of episode totals ([leg][stance steps, sum of the normal sums]); loaded here likewise
+  float c_ep = 0.0f;
+  if constexpr (CONTACTS) {
+    if (lane < 8) c_ep = ((gcontact)P.tab->contact_ep)[(size_t)robot * 8 + lane];
+  }
   float rew;
   if constexpr (TERMS) {
     float tk[5];
@@ -487,6 +526,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       if (reason & ORR_DONE_NAN) term = 0.0f;
       term_sum = (ep_step == 1 ? 0.0f : term_sum) + term;
     }
+    if constexpr (CONTACTS) {   // likewise; a non-finite step counts as sixteen zeros.  Lane 2 leg + k gets the leg's normal sum from lane 3 leg
+      if (reason & ORR_DONE_NAN) c_sum = c_max = 0.0f;
+      const float nsum = __shfl(c_sum, sub * kLanes + 3 * ((lane & 7) >> 1));
+      const float add = nsum > 0.0f ? ((lane & 1) ? nsum : 1.0f) : 0.0f;
+      c_ep = (ep_step == 1 ? 0.0f : c_ep) + add;
+    }
     if constexpr (NOISE) noise_i = (uint32_t)ep_step;
     if (ep_step >= geti(S, O(MAX_EP_STEPS))) reason |= ORR_DONE_TIME_LIMIT;
     // episode log (imitation_runners.py:185-197): the slot comes from a returning atomic on a counter shared by the whole device (a
@@ -513,6 +558,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       ((gterm)P.tab->terms)[(size_t)robot * 5 + lane] = term;
       ((gterm)P.tab->term_sums)[(size_t)robot * 5 + lane] = term_sum;
     }
+  }
+  if constexpr (CONTACTS) {
+    store_contacts();
+    if (valid && lane < 8) ((gcontact)P.tab->contact_ep)[(size_t)robot * 8 + lane] = c_ep;
   }
   PT(13);
   if (reason != 0) {
@@ -551,6 +600,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       const unsigned long long tslot = ((unsigned long long)(unsigned)__shfl((int)(slot >> 32), src) << 32) | (unsigned)__shfl((int)slot, src);
       gterm const term_log = (gterm)P.tab->term_log;
       if (valid && lane < 5 && P.ep_log && term_log && tslot < (unsigned long long)P.ep_log_cap) term_log[tslot * 5 + lane] = term_sum;
+    }
+    if constexpr (CONTACTS) {   // the ending episode's contact totals into the log row, lanes 0..7: the slot by a lane broadcast as above
+      const int src = sub * kLanes;
+      const unsigned long long cslot = ((unsigned long long)(unsigned)__shfl((int)(slot >> 32), src) << 32) | (unsigned)__shfl((int)slot, src);
+      gcontact const contact_log = (gcontact)P.tab->contact_log;
+      if (valid && lane < 8 && P.ep_log && contact_log && cslot < (unsigned long long)P.ep_log_cap) contact_log[cslot * 8 + lane] = c_ep;
     }
   }
   WSYNC();
@@ -626,4 +681,7 @@ extern template StepLaunch launch_step<2, 1, false, true, true>;             // 
 extern template ResetLaunch launch_reset<true, true>;                        //   reset (and its parity replay)
 extern template StepLaunch launch_step<kModeTerms | 0, 1, false, true, true>;   // orr_kernels_terms.hip: env step with the reward terms,
 extern template StepLaunch launch_step<kModeTerms | 2, 1, false, true, true>;   //   its parity replay (resets: the noise unit's)
+extern template StepLaunch launch_step<kModeContacts | 0, 1, false, true, true>;                // orr_kernels_contacts.hip: env step with the contact sums,
+extern template StepLaunch launch_step<kModeContacts | kModeTerms | 0, 1, false, true, true>;   //   the same with the reward terms,
+extern template StepLaunch launch_step<kModeContacts | 1, 1, false, false>;                     //   debug physics (resets: the noise unit's; no parity replay)
 }  // namespace orr

@@ -7,9 +7,9 @@
 // this device: 33 physics sub-steps, observation, reward, termination, optional auto-reset.
 // Specification of every stage: DESIGN.md section 4; CPU restatement: oracle/orr_oracle.c.
 // The kernels and their launchers are templates in orr_env_kernels.h.  This unit instantiates the default ones (env step, debug
-// physics, parity replay, reset) and chooses among all variants (variant_of); the two-wave, friction-anchor, clip-set, task-noise
-// and reward-terms instantiations are compiled in units of their own (orr_kernels_w2.hip, _anchor.hip, _multiclip.hip, _noise.hip,
-// _terms.hip; why: orr_env_kernels.h).
+// physics, parity replay, reset) and chooses among all variants (variant_of); the two-wave, friction-anchor, clip-set, task-noise,
+// reward-terms and contact-output instantiations are compiled in units of their own (orr_kernels_w2.hip, _anchor.hip, _multiclip.hip,
+// _noise.hip, _terms.hip, _contacts.hip; why: orr_env_kernels.h).
 #define ORR_TU_MAIN 1
 #include "orr_env_kernels.h"
 // <0, ORR_WAVES_PER_EU>: one wave per SIMD in the shipped build; development builds (-DORR_WAVES_PER_EU=2 with the timers of this
@@ -85,6 +85,7 @@ struct orr_handle {
   uint32_t switch_types;      // bit t = robot type t has a finite clip switch interval: the parity replays run the multi-clip variants
   bool noise_on;              // orr_set_task_noise: a probability or a heading deviation above 0: every entry point but the debug physics runs the noise variants
   bool terms_on;              // orr_bind_reward_terms: the steps run the terms variant (orr_kernels_terms.hip), the resets the noise variant
+  bool contacts_on;           // orr_bind_contact_outputs: env step and debug physics run the contact variants (orr_kernels_contacts.hip), the resets the noise variant
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -349,6 +350,24 @@ int32_t orr_bind_reward_terms(orr_handle* h, float* terms_dev, float* term_sums_
   return 0;
 }
 
+int32_t orr_bind_contact_outputs(orr_handle* h, float* contact_dev, float* contact_ep_dev, float* contact_log_dev) {
+  if (!h) return fail(-1, "orr_bind_contact_outputs: null handle");
+  const bool on = contact_dev != nullptr;
+  if (on && !contact_ep_dev) return fail(-1, "orr_bind_contact_outputs: contact_dev needs contact_ep_dev (the totals of the current episode)");
+  if (on && ((((uintptr_t)contact_dev | (uintptr_t)contact_ep_dev | (uintptr_t)contact_log_dev) & 15u) != 0))
+    return fail(-1, "orr_bind_contact_outputs: the contact buffers must be 16-byte aligned (rows of 16 and 8 floats)");
+  if (on && h->anchor_types)
+    return fail(-1, "orr_bind_contact_outputs: friction anchors (orr_model::friction_anchor) and contact outputs cannot be combined");
+  float* p[3] = {contact_dev, on ? contact_ep_dev : nullptr, on ? contact_log_dev : nullptr};
+  static_assert(offsetof(DevTables, contact_ep) == offsetof(DevTables, contact_out) + sizeof(float*) &&
+                offsetof(DevTables, contact_log) == offsetof(DevTables, contact_out) + 2 * sizeof(float*), "copied as three consecutive pointers");
+  // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->contact_out, p, sizeof(p), hipMemcpyHostToDevice), "orr_bind_contact_outputs: hipMemcpy");
+  h->tab_host.contact_out = p[0]; h->tab_host.contact_ep = p[1]; h->tab_host.contact_log = p[2];
+  h->contacts_on = on;
+  return 0;
+}
+
 int32_t orr_set_clip_switch(orr_handle* h, int32_t robot_type, float tmin, float tmax) {
   if (!h) return fail(-1, "orr_set_clip_switch: null handle");
   if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_clip_switch: robot_type out of range");
@@ -428,13 +447,24 @@ static KParams make_params(const orr_handle* h) {
 static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1) / kRPW; }
 
 // Which instantiation of the kernels a launch runs.  `clip_types` = the feature mask that selects the clip-set variants: multiclip_types
-// for orr_step / orr_reset, switch_types for the parity replays.  The reward terms come first (their step variants hold the noise and the
+// for orr_step / orr_reset, switch_types for the parity replays.  The contact outputs come first (`contacts` = the entry point has a
+// contact variant: not the parity replays, which have no impulses and run what they run without the binding; the env step has one with
+// and one without the reward terms, the resets run the noise variant), then the reward terms (their step variants hold the noise and the
 // clip-set code; the resets of such a handle run the noise variant), then task noise (its variants hold the clip-set code too), then
 // clip sets (both refuse friction anchors: kRefused, the message starts with the entry point's name `who`), then friction anchors, then
 // the batch size; only the env step has a two-wave and only the env step and the debug physics have an anchor instantiation, every other
 // entry point runs its default one instead.
-enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms };
-static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who) {
+enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts };
+static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {   // (a model with anchors set after orr_bind_contact_outputs)
+  if (!(h->contacts_on && h->anchor_types)) return false;
+  char m[256];
+  snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and contact outputs (orr_bind_contact_outputs) cannot be combined", who);
+  fail(-1, m);
+  return true;
+}
+static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who, bool contacts = true) {
+  if (contacts && refuse_contacts_with_anchors(h, who)) return kRefused;
+  if (contacts && h->contacts_on) return kContacts;
   if (h->terms_on && h->anchor_types) {   // (a model with anchors set after orr_bind_reward_terms)
     char m[256];
     snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and reward terms (orr_bind_reward_terms) cannot be combined", who);
@@ -464,7 +494,7 @@ int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* 
   if (!h || !h->state) return fail(-1, "orr_reset: handle not bound");
   const Variant v = variant_of(h, h->multiclip_types, "orr_reset");
   if (v == kRefused) return -1;
-  if (v == kNoise || v == kTerms)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
+  if (v == kNoise || v == kTerms || v == kContacts)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (task noise)");
   else if (v == kClips)   // some robot type has a clip set of more than one clip: every reset draws the episode's clip
     HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr), "orr_reset: launch (clip sets)");
@@ -481,6 +511,14 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
   HIPCHK((launch_step<0, WPE, ANCHOR, CLIPS, NOISE>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{})), msg)
   switch (variant_of(h, h->multiclip_types, "orr_step")) {
     case kRefused: return -1;
+    case kContacts:   // one wave per SIMD, any batch size; with the reward terms bound as well, the variant that writes both
+      if (h->terms_on)
+        HIPCHK((launch_step<kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev,
+                                                                                  done_dev, 0, ReplayArgs{})), "orr_step: launch (contact outputs + reward terms)");
+      else
+        HIPCHK((launch_step<kModeContacts | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0,
+                                                                     ReplayArgs{})), "orr_step: launch (contact outputs)");
+      break;
     case kTerms: HIPCHK((launch_step<kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0,
                                                                            ReplayArgs{})), "orr_step: launch (reward terms)"); break;   // one wave per SIMD, any batch size
     case kNoise: ORR_STEP(1, false, true, true, "orr_step: launch (task noise)"); break;              // one wave per SIMD, any batch size
@@ -496,7 +534,11 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
 // parity / debug entry point (not part of the drop-in surface): nsub physics sub-steps with fixed motor torques
 int32_t orr_debug_physics(orr_handle* h, const float* torques_dev, uint8_t* fall_dev, int32_t nsub, void* stream) {
   if (!h || !h->state || !torques_dev) return fail(-1, "orr_debug_physics: bad argument");
-  if (h->anchor_types)
+  if (refuse_contacts_with_anchors(h, "orr_debug_physics")) return -1;
+  if (h->contacts_on)   // the debug physics that also sums the nsub sub-steps' contact impulses
+    HIPCHK((launch_step<kModeContacts | 1, 1, false, false>(make_params(h), waves_of(h), (hipStream_t)stream, torques_dev, nullptr, nullptr, fall_dev, nsub, ReplayArgs{})),
+           "orr_debug_physics: launch (contact outputs)");
+  else if (h->anchor_types)
     HIPCHK((launch_step<1, 1, true, false>(make_params(h), waves_of(h), (hipStream_t)stream, torques_dev, nullptr, nullptr, fall_dev, nsub, ReplayArgs{})),
            "orr_debug_physics: launch (friction anchors)");
   else
@@ -534,7 +576,7 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
     return fail(-1, "orr_debug_replay_step: null buffer");
   if (h->cfg.flags & ORR_FLAG_AUTO_RESET) return fail(-1, "orr_debug_replay_step: needs a handle without ORR_FLAG_AUTO_RESET");
   const ReplayArgs rp{traj_dev, eff_dev, fall_dev, tau_out_dev, nullptr};
-  const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_step");
+  const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_step", false);   // no contact variant: contact_out is left alone
   if (v == kRefused) return -1;
   if (v == kTerms)   // reward terms: the noise replay that also writes the terms
     HIPCHK((launch_step<kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
@@ -552,7 +594,7 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
 }
 int32_t orr_debug_replay_reset(orr_handle* h, const float* uniforms_dev, float* obs_dev, void* stream) {
   if (!h || !h->state || !uniforms_dev) return fail(-1, "orr_debug_replay_reset: bad argument");
-  const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_reset");
+  const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_reset", false);
   if (v == kRefused) return -1;
   if (v == kNoise || v == kTerms)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (task noise)");

@@ -257,10 +257,12 @@ class VecQuadrupedEnv(object):
                  robot=None, motion_file=None, mode=None, enable_randomizer=None, auto_reset=True, num_procs=1,
                  robot_index_offset=0, legacy_grid=False, mixed_robots=None, ep_log_capacity=65536, config_overrides=None,
                  model_overrides=None, clip_time_min=None, clip_time_max=None, perturb_init_state_prob=None, tar_obs_noise=None,
-                 init_perturb_std=None, reward_terms=False):
+                 init_perturb_std=None, reward_terms=False, contact_outputs=False):
         import torch
         if not isinstance(reward_terms, (bool, np.bool_)):
             raise ValueError("reward_terms must be True or False, got %r" % (reward_terms,))
+        if not isinstance(contact_outputs, (bool, np.bool_)):
+            raise ValueError("contact_outputs must be True or False, got %r" % (contact_outputs,))
         self.torch = torch
         if not torch.cuda.is_available():
             raise RuntimeError("VecQuadrupedEnv needs a ROCm GPU (the HIP path has no CPU fallback)")
@@ -379,6 +381,10 @@ class VecQuadrupedEnv(object):
         # robot's current episode and, next to the episode log, the sums of every logged episode.  While bound, the steps run the
         # terms variant of the kernel
         self.reward_terms = self.episode_term_sums = self.term_log = None
+        # foot contact outputs (orr_bind_contact_outputs): per leg the sums of every step's normal and friction impulses and its largest
+        # normal impulse, stance steps and normal sum over each robot's current episode and, next to the episode log, those of every
+        # logged episode.  While bound, the steps and the debug physics run the contact variants of the kernel
+        self.contact_out = self.episode_contact = self.contact_log = None
         # the three outputs of a step are views into ONE device buffer [obs N x 160 f32 | reward N f32 | done N u8], so that a host-side
         # consumer (LegacyListEnv) fetches them with a single copy
         nb_obs, nb_rew = num_robot * _abi.OBS_DIM * 4, num_robot * 4
@@ -393,6 +399,8 @@ class VecQuadrupedEnv(object):
         self.launch_params_generation = 0     # bumped whenever something a launch takes by value changes (seed()): see there
         if reward_terms:
             self.bind_reward_terms(True)
+        if contact_outputs:
+            self.bind_contact_outputs(True)
 
     # ---- reference attribute surface -------------------------------------------------------
     @property
@@ -452,6 +460,43 @@ class VecQuadrupedEnv(object):
             _lib.check(self.L.orr_bind_reward_terms(self.h, None, None, None), self.L)
             self.reward_terms = self.episode_term_sums = self.term_log = None
         self.launch_params_generation += 1
+
+    def bind_contact_outputs(self, on=True):
+        """Bind (allocating on first use) or unbind the foot contact outputs (orr_bind_contact_outputs): env.contact_out [N, 16] (row =
+        [leg][normal sum, friction x sum, friction y sum, largest normal], N s; valid after step / debug_physics), env.episode_contact
+        [N, 8] (row = [leg][stance steps, normal sum] of the robot's current episode) and env.contact_log [ep_log_capacity, 8]; all None
+        while unbound.  It selects the kernel variant: holders of captured graphs re-capture (launch_params_generation); the variant's
+        first launch in a process loads its code object, so step once eagerly before a capture (GraphRollout's first segment does)."""
+        t = self.torch
+        if on:
+            bufs = (t.zeros((self.num_robot, _abi.CONTACT_OUT_DIM), dtype=t.float32, device=self.device),
+                    t.zeros((self.num_robot, _abi.CONTACT_EP_DIM), dtype=t.float32, device=self.device),
+                    t.zeros((self.ep_log.shape[0], _abi.CONTACT_EP_DIM), dtype=t.float32, device=self.device))
+            _lib.check(self.L.orr_bind_contact_outputs(self.h, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr()), self.L)
+            self.contact_out, self.episode_contact, self.contact_log = bufs
+        else:
+            t.cuda.synchronize(self.device)      # launches in flight still write the buffers
+            _lib.check(self.L.orr_bind_contact_outputs(self.h, None, None, None), self.L)
+            self.contact_out = self.episode_contact = self.contact_log = None
+        self.launch_params_generation += 1
+
+    def _contact_rows(self):
+        if self.contact_out is None:
+            raise ValueError("no contact outputs: the env was built without contact_outputs=True")
+        return self.contact_out.view(self.num_robot, 4, 4)
+
+    def foot_contact(self):
+        """bool [N, 4]: the leg touched the ground in the last step (its normal impulse sum is > 0).  Needs contact_outputs=True."""
+        return self._contact_rows()[:, :, 0] > 0
+
+    def foot_forces(self):
+        """float32 [N, 4, 3]: each leg's mean contact force over the last step in N (normal, friction along world x, along world y):
+        the impulse sums divided by action_repeat * sim_dt.  Needs contact_outputs=True."""
+        return self._contact_rows()[:, :, 0:3] / (self.cfg.action_repeat * self.cfg.sim_dt)
+
+    def foot_peak_force(self):
+        """float32 [N, 4]: each leg's largest normal force of any one sub-step of the last step, in N.  Needs contact_outputs=True."""
+        return self._contact_rows()[:, :, 3] / self.cfg.sim_dt
 
     # ---- hot path ------------------------------------------------------------------------------
     def _stream(self):
@@ -587,6 +632,20 @@ class VecQuadrupedEnv(object):
         sums = self.term_log[:k].double().sum(0).cpu().numpy()
         return {name: float(sums[i] / steps) for i, name in enumerate(self.TERM_NAMES)}
 
+    def episode_gait(self):
+        """{"duty": [4], "normal_force": [4]} per leg over the episodes logged since the log was last cleared, without clearing it
+        (syncs): duty = stance steps / steps, normal_force = the mean normal force in N (sum of the normal impulse sums / (steps x
+        action_repeat x sim_dt)); {} when no episode is logged.  Read it before a gather clears the log.  Needs contact_outputs=True."""
+        if self.contact_log is None:
+            raise ValueError("no contact log: the env was built without contact_outputs=True")
+        k = int(self.torch.clamp(self.counters[_abi.CNT_EPISODES], max=self.ep_log.shape[0]).item())
+        if k == 0:
+            return {}
+        steps = float(self.ep_log[:k, 1].double().sum().item())
+        sums = self.contact_log[:k].double().sum(0).cpu().numpy().reshape(4, 2)
+        return {"duty": [float(x / steps) for x in sums[:, 0]],
+                "normal_force": [float(x / (steps * self.cfg.action_repeat * self.cfg.sim_dt)) for x in sums[:, 1]]}
+
     def episode_log_device(self):
         """(log[K,2] snapshot, count, dropped) of the episodes finished since the last call, all on the device and
         without a host sync (count / dropped are 0-d int64 tensors; rows >= count are stale); clears the log."""
@@ -603,21 +662,27 @@ class VecQuadrupedEnv(object):
         _lib.check(self.L.orr_episode_stats(self.h, float(total_timesteps), int(capacity), out.data_ptr(), self._stream()), self.L)
         return out
 
-    def episode_log(self, with_dropped=False, with_clip=False, with_terms=False):
+    def episode_log(self, with_dropped=False, with_clip=False, with_terms=False, with_contacts=False):
         """(returns[K], lengths[K]) of the episodes finished since the last call (+ clip_ids[K] int32, the clip each of them played,
-        when with_clip; + term_sums[K, 5], each episode's sums of the five reward terms, when with_terms; + the number of episodes
-        that did not fit the device log when with_dropped); clears the log.  Syncs.
-        with_clip needs a clip set of more than one clip (the clip log exists only then), with_terms reward_terms=True: ValueError
-        otherwise."""
+        when with_clip; + term_sums[K, 5], each episode's sums of the five reward terms, when with_terms; + contacts[K, 8], each
+        episode's [leg][stance steps, normal impulse sum], when with_contacts; + the number of episodes that did not fit the device
+        log when with_dropped); clears the log.  Syncs.
+        with_clip needs a clip set of more than one clip (the clip log exists only then), with_terms reward_terms=True, with_contacts
+        contact_outputs=True: ValueError otherwise."""
         if with_clip and self.clip_log is None:
             raise ValueError("no clip log: no robot type of this env has a clip set of more than one clip")
         if with_terms and self.term_log is None:
             raise ValueError("no term log: the env was built without reward_terms=True")
         clip_log = self.clip_log.clone() if with_clip else None
+        if with_contacts and self.contact_log is None:
+            raise ValueError("no contact log: the env was built without contact_outputs=True")
         term_log = self.term_log.clone() if with_terms else None
+        contact_log = self.contact_log.clone() if with_contacts else None
         log, cnt, dropped = self.episode_log_device()
         k = int(cnt.item())
         out = (log[:k, 0], log[:k, 1]) + ((clip_log[:k],) if with_clip else ()) + ((term_log[:k],) if with_terms else ())
+        if with_contacts:
+            out += (contact_log[:k],)
         if with_dropped:
             return out + (int(dropped.item()),)
         return out

@@ -19,6 +19,10 @@ Two measurements, nothing fitted:
     Variants: the shipped table (mu 0.5, soft toes), mu 1.0, friction anchors on, mu 1.0 + anchors.
 
 usage: python tools/lag_diagnosis.py [--policy laikago_pace] [--robots 8] [--steps 300] [--skip 100] [--out profiles/r06_lag_diagnosis.json]
+       python tools/lag_diagnosis.py --device [--robots 4096] ...   B from the HIP path's foot contact outputs (VecQuadrupedEnv(contact_outputs=True),
+       needs a GPU): the same table per leg at ENV-STEP granularity (a leg is in stance in a step whose normal impulse sum is > 0), without the
+       columns that need the toe-point velocity or single sub-steps (slip, at bound), plus the peak normal force; friction anchors have no
+       contact variant and are left out.
 """
 import argparse
 import ctypes as C
@@ -163,6 +167,56 @@ def simulate(policy, clip_name, model, n, steps, skip, cfg_over=None, seed=1, th
             "no_contact_share": float((~contact.any(axis=2)).mean()), "legs": legs}
 
 
+def simulate_device(policy, clip_name, build_kw, n, steps, skip, seed=1):
+    """B on the device: the policy on VecQuadrupedEnv with the contact outputs bound; statistics over the steps after `skip`, env-step
+    granularity (contact_out holds each step's impulse sums per leg)."""
+    import torch
+    from openroborl_amd.env import VecQuadrupedEnv
+    W = np.load(os.path.join(ol.GOLDEN, "policy_%s.npz" % policy))
+    env = VecQuadrupedEnv(num_robot=n, robot="laikago", motion_file=clip_name, mode="test", enable_randomizer=False, auto_reset=False, seed=seed,
+                          contact_outputs=True, model_overrides={"laikago": {"_build": dict(build_kw)}})
+    model = env.models[robots.ROBOT_TYPE_ID["laikago"]]
+    w = {k: torch.tensor(W[k], dtype=torch.float32, device=env.device) for k in W.files}
+    obs = env.reset()
+    env.field("FOOT_MU")[:] = float(model["foot_friction"])
+    dt_step = float(env.env_time_step)
+    mass = float(model["base_mass"] + np.sum(model["link_mass"]))
+    alive = torch.ones(n, dtype=torch.bool, device=env.device)
+    reason = env.field_int("DONE_REASON")[:, 0]
+    rec, rew_sum, vx_sum, vref_sum, cnt = [], 0.0, 0.0, 0.0, 0
+    for s in range(steps):
+        h = torch.relu(obs @ w["model__pi_fc0__w_0"] + w["model__pi_fc0__b_0"])
+        h = torch.relu(h @ w["model__pi_fc1__w_0"] + w["model__pi_fc1__b_0"])
+        a = torch.clamp(h @ w["model__pi__w_0"] + w["model__pi__b_0"], -2 * np.pi, 2 * np.pi)
+        obs, rew, done, _ = env.step(a.contiguous())
+        alive &= ~(done.bool() & ((reason & ~8) != 0))
+        if s >= skip:
+            rec.append(env.contact_out.view(n, 4, 4).clone())
+            if bool(alive.any()):
+                rew_sum += float(rew[alive].mean())
+                vx_sum += float(env.field("LINVEL")[alive, 0].mean())
+                vref_sum += float(env.field("REF_VEL")[alive, 0].mean())
+                cnt += 1
+    T = torch.stack(rec, dim=1)[alive].double().cpu().numpy()          # [robots alive to the end, steps, leg, (n, t1, t2, max n)]
+    env.close()
+    contact = T[..., 0] > 0
+    legs = []
+    for leg in range(4):
+        c = contact[:, :, leg]
+        ln, lx = T[:, :, leg, 0], T[:, :, leg, 1]
+        starts = (c[:, 1:] & ~c[:, :-1]).sum() + c[:, 0].sum()
+        nst = max(int(starts), 1)
+        legs.append({"leg": LEGS[leg], "stances": int(starts), "duty": float(c.mean()), "stance_ms": float(c.sum() * dt_step * 1e3 / nst),
+                     "normal_impulse_per_stance": float(ln.sum() / nst), "push_impulse_per_stance": float(np.maximum(lx, 0).sum() / nst),
+                     "brake_impulse_per_stance": float(np.minimum(lx, 0).sum() / nst),
+                     "peak_normal_force": float(T[:, :, leg, 3].max() / float(env.cfg.sim_dt)) if T.size else 0.0})
+    total_n = float(T[..., 0].sum() / max(T.shape[0] * T.shape[1], 1) / dt_step)        # mean normal force [N]
+    return {"policy": policy, "finished_window": float(alive.float().mean()), "robots": n, "steps": steps, "skip": skip,
+            "mu": float(model["foot_friction"]) * float(env.cfg.plane_friction), "mass": mass, "v_sim": vx_sum / max(cnt, 1), "v_ref": vref_sum / max(cnt, 1),
+            "reward_per_step": rew_sum / max(cnt, 1), "mean_normal_force_over_weight": total_n / (mass * 10.0),
+            "no_contact_share": float((~contact.any(axis=2)).mean()), "legs": legs}
+
+
 VARIANTS = [
     ("shipped table", {}, {}),
     ("mu 1.0", {"foot_friction": 1.0}, {}),
@@ -201,6 +255,20 @@ def fmt_sim(name, o, kin):
     return "\n".join(lines)
 
 
+def fmt_dev(name, o, kin):
+    lines = ["B. %-24s mu %.2f (device, env-step granularity): v_sim %.3f m/s, clip %.3f (lag %+.3f), r/step %.3f, up %.2f, "
+             "mean normal force / weight %.2f, flight share %.2f"
+             % (name, o["mu"], o["v_sim"], o["v_ref"], o["v_sim"] - o["v_ref"], o["reward_per_step"], o["finished_window"],
+                o["mean_normal_force_over_weight"], o["no_contact_share"]),
+             "   leg  duty  stance[ms]  N impulse [N s]  push  brake [N s]  need [N s]  peak N [N]"]
+    for r, kr in zip(o["legs"], kin["legs"]):
+        need = o["mass"] * (kr["root_dv_over_stance"] if kr else 0.0)
+        lines.append("   %-3s  %.2f  %7.0f     %6.2f        %+.2f  %+.2f      %+.2f     %7.1f" % (
+            r["leg"], r["duty"], r["stance_ms"], r["normal_impulse_per_stance"], r["push_impulse_per_stance"], r["brake_impulse_per_stance"], need,
+            r["peak_normal_force"]))
+    return "\n".join(lines)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--policy", default="laikago_pace")
@@ -210,6 +278,7 @@ def main():
     ap.add_argument("--skip", type=int, default=100)
     ap.add_argument("--stance-mm", type=float, default=6.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--device", action="store_true", help="B from the HIP path's contact outputs (needs a GPU), per env step; see the module text")
     ap.add_argument("--table", default="shipped", choices=["shipped", "r05", "r04"], help="r05: round 5's table, on which the diagnosis was first made")
     args = ap.parse_args()
     clip = args.clip or args.policy.rstrip("0")
@@ -220,6 +289,15 @@ def main():
     print(fmt_kin(kin), flush=True)
     res = {"kinematics": kin, "variants": []}
     for name, mo, co in VARIANTS:
+        if args.device:
+            if mo.get("friction_anchor"):
+                print("B. %-24s left out: friction anchors have no contact-output variant" % name, flush=True)
+                continue
+            o = simulate_device(args.policy, clip, dict(tab, **mo), args.robots, args.steps, args.skip)
+            o["variant"] = name
+            res["variants"].append(o)
+            print(fmt_dev(name, o, kin), flush=True)
+            continue
         o = simulate(args.policy, clip, robots.laikago(**dict(tab, **mo)), args.robots, args.steps, args.skip, co)
         o["variant"] = name
         res["variants"].append(o)

@@ -44,6 +44,10 @@ def main():
                     help="also output the five unweighted terms of the imitation reward on the device (pose, velocity, end effector, root pose, "
                          "root velocity): every logged record gains \"reward_terms\": {name: mean per step} over the episodes THIS rank finished "
                          "in the segment (rank-local, unlike the gathered episode means); --eval: over each robot's episode")
+    ap.add_argument("--contact-outputs", action="store_true",
+                    help="also output the foot contact impulses on the device: every logged record gains \"gait\": {\"duty\": [4], \"normal_force\": [4]} "
+                         "(per leg: stance steps / steps, mean normal force in N) over the episodes THIS rank finished in the segment (rank-local); "
+                         "--eval: over each robot's episode")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
     ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip")
@@ -79,7 +83,8 @@ def main():
     env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
                           device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
                           perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise,
-                          reward_terms=args.reward_terms, **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
+                          reward_terms=args.reward_terms, contact_outputs=args.contact_outputs,
+                          **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     model = ppo.ActorCritic(dev, params=params, seed=args.seed)                     # same seed -> identical replicas
     if not args.torch_policy:
@@ -130,6 +135,7 @@ def main():
         # this rank's episodes of the segment by clip (read before the gather below clears the log)
         by_clip = env.episode_returns_by_clip() if log_it and env.multi_clip else None
         by_term = env.episode_reward_terms() if log_it and args.reward_terms else None     # likewise; rank-local
+        gait = env.episode_gait() if log_it and args.contact_outputs else None             # likewise
         stats = odist.gather_env_episodes(env, args.horizon)   # means come from the exact per-rank sums, not the truncated list
         if log_it:
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2),
@@ -141,6 +147,8 @@ def main():
                 rec["ep_ret_mean_by_clip"] = {clip_name(env, c): round(r, 2) for c, (r, _) in sorted(by_clip.items())}
             if by_term is not None:
                 rec["reward_terms"] = {k: round(v, 4) for k, v in by_term.items()}
+            if gait is not None:
+                rec["gait"] = {k: [round(x, 3) for x in v] for k, v in gait.items()}
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if rank == 0 and args.save:
@@ -168,7 +176,8 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     dev = torch.device("cuda", 0)
     n = min(args.num_robot, 1024)
     env = VecQuadrupedEnv(task_name=args.task, num_robot=n, mode="test", auto_reset=False, seed=args.seed, device=dev,
-                          motion_file=args.motion_file, reward_terms=args.reward_terms, **clip_time_kwargs(args))
+                          motion_file=args.motion_file, reward_terms=args.reward_terms, contact_outputs=args.contact_outputs,
+                          **clip_time_kwargs(args))
     model = ppo.ActorCritic(dev, params=pol.load_parameters(args.eval))
     if not args.torch_policy:
         model.enable_fused()
@@ -178,6 +187,8 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     ret = torch.zeros(n, device=dev)
     length = torch.zeros(n, device=dev)
     term_sum = torch.zeros(len(env.TERM_NAMES), dtype=torch.float64, device=dev)      # --reward-terms: over every robot's steps up to its first done
+    stance = torch.zeros(4, dtype=torch.float64, device=dev)       # --contact-outputs: per leg, likewise
+    normal = torch.zeros(4, dtype=torch.float64, device=dev)
     limit = int(env.field_int("MAX_EP_STEPS").max())
     for _ in range(limit):
         act, _, _ = model.act(obs, deterministic=True)
@@ -185,6 +196,9 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
         ret += rew * alive
         if args.reward_terms:
             term_sum += (env.reward_terms * alive[:, None]).sum(0)
+        if args.contact_outputs:
+            stance += (env.foot_contact() & alive[:, None]).sum(0).double()
+            normal += (env.contact_out.view(n, 4, 4)[:, :, 0] * alive[:, None]).sum(0).double()
         length += alive.float()
         alive &= ~done.bool()
         if not bool(alive.any()):
@@ -200,6 +214,10 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
         rec["robots_by_clip"] = {clip_name(env, int(c)): int((cid == c).sum()) for c in np.unique(cid)}
     if args.reward_terms:
         rec["reward_terms"] = {k: round(float(v), 4) for k, v in zip(env.TERM_NAMES, (term_sum / length.sum()).tolist())}
+    if args.contact_outputs:
+        steps = float(length.sum())
+        rec["gait"] = {"duty": [round(x / steps, 3) for x in stance.tolist()],
+                       "normal_force": [round(x / (steps * env.env_time_step), 3) for x in normal.tolist()]}
     print(json.dumps(rec))
     env.close()
 
