@@ -9,9 +9,8 @@ import numpy as np
 
 from openroborl_amd import _abi, config, motion, robots
 from tests import oracle_lib as ol
+from tests.gpu_kit import CLIP, MIXED
 
-MIXED = ("laikago", "mini_cheetah")
-CLIP = {"laikago": "laikago_pace", "mini_cheetah": "minicheetah_trot"}
 POLICY = {"laikago": "policy_laikago_pace.npz", "mini_cheetah": "policy_minicheetah_trot.npz"}
 N, STEPS, SEED, ACTION_SEED, ACTION_STD = 37, 40, 3, 11, 0.05      # the product-path comparison: ten waves, the last with one valid robot
 F32_SHARE, DEVICE_SHARE, MIN_LIVE = 0.005, 0.02, 1000               # shares of live leg-steps that may hold a cell over the bound

@@ -4,8 +4,7 @@ import numpy as np
 
 from openroborl_amd import _abi, config, motion, robots, state as statemod
 from tests import oracle_lib as ol
-
-CLIP = {"laikago": "laikago_pace", "mini_cheetah": "minicheetah_trot"}
+from tests.gpu_kit import CLIP
 
 
 def substep_parity_inputs(robot, n=64, seed=3):

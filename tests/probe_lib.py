@@ -36,59 +36,66 @@ SPECS = {
 INT_ENTRIES = ("philox_block", "time_limit")
 
 
-def lib_path(build_name):
-    return os.path.join(PROBE_DIR, BUILDS[build_name][0])
+class ProbeBuilds:
+    """The builds of one probe source: `builds` maps a build name to (library file name, flags).  Every library lies next to the sources
+    in PROBE_DIR, with a `.hash` side file that says what it was built from."""
 
+    def __init__(self, src, builds):
+        self.src, self.builds = src, builds
 
-def probe_hash(build_name):
-    """What a probe library is built from: its source, everything the env kernels are built from (_lib.DEPS) and the flags."""
-    h = hashlib.sha256()
-    for d in [SRC] + sorted(_lib.DEPS):
-        h.update(os.path.basename(d).encode())
-        with open(d, "rb") as f:
-            h.update(f.read())
-    h.update(" ".join(BUILDS[build_name][1]).encode())
-    return h.hexdigest()[:32]
+    def lib_path(self, build_name):
+        return os.path.join(PROBE_DIR, self.builds[build_name][0])
 
+    def probe_hash(self, build_name):
+        """What a probe library is built from: its source, everything the env kernels are built from (_lib.DEPS) and the flags."""
+        h = hashlib.sha256()
+        for d in [self.src] + sorted(_lib.DEPS):
+            h.update(os.path.basename(d).encode())
+            with open(d, "rb") as f:
+                h.update(f.read())
+        h.update(" ".join(self.builds[build_name][1]).encode())
+        return h.hexdigest()[:32]
 
-def needs_build(build_name):
-    try:
-        with open(lib_path(build_name) + ".hash") as f:
-            return f.read().strip() != probe_hash(build_name) or not os.path.exists(lib_path(build_name))
-    except OSError:
-        return True
-
-
-def compile_command(build_name, out):
-    return [_lib.HIPCC] + list(BUILDS[build_name][1]) + ["-I", _lib.CSRC, "-I", os.path.join(ROOT, "include"), "-o", out, SRC]
-
-
-def build(build_name, force=False):
-    """Compile one probe library for gfx950 (no GPU needed).  File lock + atomic rename: concurrent callers never load half a file."""
-    import fcntl
-    so = lib_path(build_name)
-    with open(os.path.join(PROBE_DIR, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
+    def needs_build(self, build_name):
+        so = self.lib_path(build_name)
         try:
-            if force or needs_build(build_name):
-                tmp = so + ".%d.tmp" % os.getpid()
-                try:
-                    subprocess.check_call(compile_command(build_name, tmp))
-                    os.replace(tmp, so)
-                finally:
-                    if os.path.exists(tmp):
-                        os.remove(tmp)
-                with open(so + ".hash.tmp", "w") as f:
-                    f.write(probe_hash(build_name) + "\n")
-                os.replace(so + ".hash.tmp", so + ".hash")
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return so
+            with open(so + ".hash") as f:
+                return f.read().strip() != self.probe_hash(build_name) or not os.path.exists(so)
+        except OSError:
+            return True
+
+    def compile_command(self, build_name, out):
+        return [_lib.HIPCC] + list(self.builds[build_name][1]) + ["-I", _lib.CSRC, "-I", os.path.join(ROOT, "include"), "-o", out, self.src]
+
+    def build(self, build_name, force=False):
+        """Compile one probe library for gfx950 (no GPU needed).  File lock + atomic rename: concurrent callers never load half a file."""
+        import fcntl
+        so = self.lib_path(build_name)
+        with open(os.path.join(PROBE_DIR, ".build.lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            try:
+                if force or self.needs_build(build_name):
+                    tmp = so + ".%d.tmp" % os.getpid()
+                    try:
+                        subprocess.check_call(self.compile_command(build_name, tmp))
+                        os.replace(tmp, so)
+                    finally:
+                        if os.path.exists(tmp):
+                            os.remove(tmp)
+                    with open(so + ".hash.tmp", "w") as f:
+                        f.write(self.probe_hash(build_name) + "\n")
+                    os.replace(so + ".hash.tmp", so + ".hash")
+            finally:
+                fcntl.flock(lock, fcntl.LOCK_UN)
+        return so
+
+    def build_all(self, force=False):
+        return [self.build(b, force=force) for b in self.builds]
 
 
-def build_all(force=False):
-    return [build(b, force=force) for b in BUILDS]
-
+_builds = ProbeBuilds(SRC, BUILDS)
+lib_path, probe_hash, needs_build, compile_command = _builds.lib_path, _builds.probe_hash, _builds.needs_build, _builds.compile_command
+build, build_all = _builds.build, _builds.build_all
 
 _libs = {}
 

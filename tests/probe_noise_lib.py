@@ -1,13 +1,12 @@
 """Builder + ctypes loader of the task-noise probe (tests/device_probe/orr_probe_noise.hip) -- test infrastructure only.
 
-A sibling of tests/probe_lib.py (whose machinery - flags, hash file, file lock, atomic rename - it reuses): normal_pair of
+A sibling of tests/probe_lib.py (one more ProbeBuilds: flags, hash file, file lock, atomic rename): normal_pair of
 csrc/orr_device.h behind two entry points, built once with the flags of the unit that uses it (_lib.HIPCC_FLAGS, orr_kernels_noise.hip),
 next to its source; no part of libopenroborl_hip.so, of _lib.DEPS or of the source hash.
 """
 import ctypes as C
-import hashlib
+import functools
 import os
-import subprocess
 
 import numpy as np
 
@@ -17,50 +16,10 @@ from tests import probe_lib
 SRC = os.path.join(probe_lib.PROBE_DIR, "orr_probe_noise.hip")
 LIB = os.path.join(probe_lib.PROBE_DIR, "liborr_probe_noise.so")
 
-
-def probe_hash():
-    h = hashlib.sha256()
-    for d in [SRC] + sorted(_lib.DEPS):
-        h.update(os.path.basename(d).encode())
-        with open(d, "rb") as f:
-            h.update(f.read())
-    h.update(" ".join(_lib.HIPCC_FLAGS).encode())
-    return h.hexdigest()[:32]
-
-
-def needs_build():
-    try:
-        with open(LIB + ".hash") as f:
-            return f.read().strip() != probe_hash() or not os.path.exists(LIB)
-    except OSError:
-        return True
-
-
-def compile_command(out):
-    return [_lib.HIPCC] + list(_lib.HIPCC_FLAGS) + ["-I", _lib.CSRC, "-I", os.path.join(probe_lib.ROOT, "include"), "-o", out, SRC]
-
-
-def build(force=False):
-    """Compile the probe for gfx950 (no GPU needed); same locking and renaming as probe_lib.build."""
-    import fcntl
-    with open(os.path.join(probe_lib.PROBE_DIR, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if force or needs_build():
-                tmp = LIB + ".%d.tmp" % os.getpid()
-                try:
-                    subprocess.check_call(compile_command(tmp))
-                    os.replace(tmp, LIB)
-                finally:
-                    if os.path.exists(tmp):
-                        os.remove(tmp)
-                with open(LIB + ".hash.tmp", "w") as f:
-                    f.write(probe_hash() + "\n")
-                os.replace(LIB + ".hash.tmp", LIB + ".hash")
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB
-
+_builds = probe_lib.ProbeBuilds(SRC, {"noise": (os.path.basename(LIB), _lib.HIPCC_FLAGS)})
+# a single build: the module-level functions take no build name
+probe_hash, needs_build = functools.partial(_builds.probe_hash, "noise"), functools.partial(_builds.needs_build, "noise")
+compile_command, build = functools.partial(_builds.compile_command, "noise"), functools.partial(_builds.build, "noise")
 
 _lib_handle = None
 
@@ -84,9 +43,7 @@ def normal_pair(ua, ub):
     x = np.ascontiguousarray(np.stack([np.asarray(ua, dtype=np.float32), np.asarray(ub, dtype=np.float32)], axis=1))
     tin = torch.from_numpy(x).to("cuda:0")
     tout = torch.full(x.shape, float("nan"), dtype=torch.float32, device="cuda:0")
-    rc = lib().orrp_normal_pair(tin.data_ptr(), tout.data_ptr(), len(x), torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("orrp_normal_pair failed: %d" % rc)
+    probe_lib._launch(lib(), "normal_pair", tin, tout, len(x))
     out = tout.cpu().numpy()
     return out[:, 0], out[:, 1]
 

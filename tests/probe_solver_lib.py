@@ -1,14 +1,12 @@
 """Builder + ctypes loader of the solver-stage probe (tests/device_probe/orr_probe_solver.hip) -- test infrastructure only.
 
-A sibling of tests/probe_lib.py (whose flags, hash file, file lock and atomic rename it reuses): delassus_columns<HAS_B> and
+A sibling of tests/probe_lib.py (one more ProbeBuilds: flags, hash file, file lock, atomic rename): delassus_columns<HAS_B> and
 pgs_sweeps<HAS_B> of csrc/orr_physics.h behind four entry points.  Built three times next to its source: `one` and `w2` with the flags
 of the two env units (the hand-scheduled sweeps), `generic` with the `one` flags plus -DORR_GENERIC_PGS (the readable C++ sweeps);
 no part of libopenroborl_hip.so, of _lib.DEPS or of the source hash.
 """
 import ctypes as C
-import hashlib
 import os
-import subprocess
 
 import numpy as np
 
@@ -27,58 +25,9 @@ SPECS = {"pgs_a": (PGS_IN, PGS_OUT), "pgs_ab": (PGS_IN, PGS_OUT), "delassus_pgs_
 MAX_ITERS = 32
 
 
-def lib_path(build_name):
-    return os.path.join(probe_lib.PROBE_DIR, BUILDS[build_name][0])
-
-
-def probe_hash(build_name):
-    h = hashlib.sha256()
-    for d in [SRC] + sorted(_lib.DEPS):
-        h.update(os.path.basename(d).encode())
-        with open(d, "rb") as f:
-            h.update(f.read())
-    h.update(" ".join(BUILDS[build_name][1]).encode())
-    return h.hexdigest()[:32]
-
-
-def needs_build(build_name):
-    try:
-        with open(lib_path(build_name) + ".hash") as f:
-            return f.read().strip() != probe_hash(build_name) or not os.path.exists(lib_path(build_name))
-    except OSError:
-        return True
-
-
-def compile_command(build_name, out):
-    return [_lib.HIPCC] + BUILDS[build_name][1] + ["-I", _lib.CSRC, "-I", os.path.join(probe_lib.ROOT, "include"), "-o", out, SRC]
-
-
-def build(build_name, force=False):
-    """Compile one probe library for gfx950 (no GPU needed); same locking and renaming as probe_lib.build."""
-    import fcntl
-    so = lib_path(build_name)
-    with open(os.path.join(probe_lib.PROBE_DIR, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if force or needs_build(build_name):
-                tmp = so + ".%d.tmp" % os.getpid()
-                try:
-                    subprocess.check_call(compile_command(build_name, tmp))
-                    os.replace(tmp, so)
-                finally:
-                    if os.path.exists(tmp):
-                        os.remove(tmp)
-                with open(so + ".hash.tmp", "w") as f:
-                    f.write(probe_hash(build_name) + "\n")
-                os.replace(so + ".hash.tmp", so + ".hash")
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return so
-
-
-def build_all(force=False):
-    return [build(b, force=force) for b in BUILDS]
-
+_builds = probe_lib.ProbeBuilds(SRC, BUILDS)
+lib_path, probe_hash, needs_build, compile_command = _builds.lib_path, _builds.probe_hash, _builds.needs_build, _builds.compile_command
+build, build_all = _builds.build, _builds.build_all
 
 _libs = {}
 

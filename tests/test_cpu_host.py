@@ -152,11 +152,10 @@ def test_the_kernel_tuning_knobs_still_compile(defs):
     block, the phase timers (which imply the wave timeline), the dual-contact counter, the wave timeline on its own - and the one
     launch-shape experiment a tool still drives (-DORR_WAVES_PER_EU=2: tools/wave_pairing.py).  Each goes through the device compiler's front end here (syntax + templates + static_asserts; well under a
     second each), in all four translation units of the env kernels."""
-    import subprocess
-    base = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + ["--cuda-device-only", "-fsyntax-only", "-Wno-unused-command-line-argument"]
+    from tests.test_step_kernel_no_fence import front_end_compiles
     assert len(_lib.ENV_UNITS) == 4
     for _, src, _, _ in _lib.ENV_UNITS:
-        r = subprocess.run([_lib.HIPCC] + base + defs + [src], capture_output=True, text=True)
+        r = front_end_compiles(src, defs)
         assert r.returncode == 0, "%s %s:\n%s" % (os.path.basename(src), " ".join(defs), r.stderr[-1500:])
 
 

@@ -47,6 +47,23 @@ def test_solver_probe_builds_differ_only_in_their_flags():
     assert len({v[0] for v in B.values()}) == 3 and not {v[0] for v in B.values()} & {v[0] for v in probe_lib.BUILDS.values()}
 
 
+def test_every_probe_build_has_one_command_shape_and_a_library_of_its_own():
+    """All six builds go through one ProbeBuilds: the compiler, the build's flags, the two include paths, the output, the source."""
+    from openroborl_amd import _lib
+    from tests import probe_noise_lib
+    include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+    libs = []
+    for mod in (probe_lib, probe_solver_lib):
+        for b, (name, flags) in mod.BUILDS.items():
+            assert mod.compile_command(b, "out.so") == [_lib.HIPCC] + list(flags) + ["-I", _lib.CSRC, "-I", include, "-o", "out.so", mod.SRC]
+            libs.append(mod.lib_path(b))
+    assert probe_noise_lib.compile_command("out.so") == (
+        [_lib.HIPCC] + list(_lib.HIPCC_FLAGS) + ["-I", _lib.CSRC, "-I", include, "-o", "out.so", probe_noise_lib.SRC])
+    libs.append(probe_noise_lib.LIB)
+    assert all(os.path.dirname(p) == probe_lib.PROBE_DIR for p in libs)
+    assert len(libs) == 6 and len({os.path.basename(p) for p in libs}) == 6
+
+
 def test_probe_is_no_part_of_the_product_library():
     from openroborl_amd import _lib
     assert not any("device_probe" in d or "orr_probe" in d for d in _lib.DEPS)

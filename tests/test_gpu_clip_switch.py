@@ -12,6 +12,7 @@ import pytest
 from openroborl_amd import _abi, _lib, motion, robots, state as statemod
 from openroborl_amd.env import CLIP_CHANGE_DRAW, CLIP_DRAW, clip_change_time, clip_draw_index, clip_switch_draws
 from tests import oracle_lib as ol
+from tests.gpu_kit import make_env, stress
 
 pytestmark = pytest.mark.gpu
 
@@ -30,16 +31,6 @@ def clamped_sidesteps(tmp_path):
     return dst
 
 
-def make_env(n, files, **kw):
-    from openroborl_amd.env import VecQuadrupedEnv
-    kw.setdefault("robot", "laikago")
-    kw.setdefault("mode", "test")
-    kw.setdefault("enable_randomizer", False)
-    kw.setdefault("auto_reset", True)
-    kw.setdefault("seed", 5)
-    return VecQuadrupedEnv(num_robot=n, motion_file=files, **kw)
-
-
 def set4(tmp_path):
     return ["laikago_pace", "laikago_trot", "laikago_spin", clamped_sidesteps(tmp_path)]
 
@@ -54,12 +45,6 @@ def rec(env):
 
 def motion_time(env, r, counter):
     return counter * 0.001 + r["offset"].astype(np.float64) - WARMUP * r["warm"]     # sim_dt 0.001: dec7 in the kernel, exact decimal
-
-
-def stress(env, obs, rng):
-    import torch
-    noise = torch.from_numpy(rng.normal(0.0, 0.05, (env.num_robot, 12)).astype(np.float32)).to(env.device)
-    return env.stress_actions(obs, noise, torch.empty_like(noise))
 
 
 def test_switches_follow_the_host_prediction(tmp_path):

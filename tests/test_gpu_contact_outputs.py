@@ -15,48 +15,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from openroborl_amd import _abi, robots, state as statemod
+from openroborl_amd import _abi, robots
 from tests import contact_lib as cl
 from tests import oracle_lib as ol
+from tests.gpu_kit import CLIP, EPS, SOFT_TOES, canonical_log, gpu_state64, log_rows_match, mixed_env, push_state, short_episodes, stress
 
 pytestmark = pytest.mark.gpu
-CLIP = cl.CLIP
-EPS = 2.0 ** -24
-SOFT_TOES = {"contact_stiffness": 30000.0, "contact_damping": 1000.0, "foot_friction": 3.0}      # tests/test_gpu_parity.py's
-
-
-def stress(env, obs, rng):
-    import torch
-    noise = torch.from_numpy(rng.normal(0.0, 0.05, (env.num_robot, 12)).astype(np.float32)).to(env.device)
-    return env.stress_actions(obs, noise, torch.empty_like(noise))
-
-
-def mixed_env(n, **kw):
-    from openroborl_amd.env import VecQuadrupedEnv
-    kw.setdefault("seed", cl.SEED)
-    kw.setdefault("mode", "train")
-    kw.setdefault("enable_randomizer", True)
-    return VecQuadrupedEnv(num_robot=n, mixed_robots=list(cl.MIXED), motion_file=[CLIP[m] for m in cl.MIXED], **kw)
-
-
-def short_episodes():
-    """ep_len_start = 8, ep_len_end = 24 with the curriculum as the task fixtures set it"""
-    g = np.load(ol.GOLDEN + "/task_laikago.npz")
-    return dict(ep_len_start=8, ep_len_end=24, curriculum_steps=int(g["curriculum_steps"]))
 
 
 def rows(env):
     """contact_out as float32 [n, 4, 4] on the host"""
     return env.contact_out.cpu().numpy().reshape(env.num_robot, 4, 4)
-
-
-def gpu_state64(env):
-    return statemod.to_float64(env.layout, env.state.detach().cpu().numpy())
-
-
-def push_state(env, st64):
-    import torch
-    env.state.copy_(torch.from_numpy(statemod.from_float64(env.layout, st64)).to(env.device))
 
 
 def substep_env(robot, soft, n, **kw):
@@ -235,17 +204,7 @@ def check_log(env, episodes, logged=None):
     assert int(env.counters[_abi.CNT_EPISODES].item()) == len(episodes)
     ep_log, contact_log = env.ep_log[:k].cpu().numpy(), env.contact_log[:k].cpu().numpy()
     assert (contact_log.reshape(k, 4, 2)[:, :, 0] <= ep_log[:, 1:2]).all()                 # stance steps <= length
-    want = sorted((np.float32(r).tobytes(), l, row.astype(np.float32).tobytes()) for _, l, row, r in episodes)
-    got = sorted((ep_log[j, 0].tobytes(), int(ep_log[j, 1]), contact_log[j].tobytes()) for j in range(k))
-    if logged is None:
-        assert got == want
-    else:
-        assert all(g in want for g in got) and len(got) == logged
-
-
-def canonical_log(env, k):
-    r = np.concatenate([env.ep_log[:k].cpu().numpy(), env.contact_log[:k].cpu().numpy()], axis=1)
-    return r[np.lexsort(r.T[::-1])].tobytes()
+    log_rows_match(ep_log, contact_log, [(r, l, row) for _, l, row, r in episodes], logged)
 
 
 def test_stance_counts_normal_sums_and_log_rows_with_auto_reset():
@@ -268,7 +227,7 @@ def test_stance_counts_normal_sums_and_log_rows_with_auto_reset():
     env.close()
     rows_b, ep_b, episodes_b, env = bookkeeping_run()
     assert rows_a.tobytes() == rows_b.tobytes() and ep_a.tobytes() == ep_b.tobytes()
-    assert log_a[np.lexsort(log_a.T[::-1])].tobytes() == canonical_log(env, len(episodes_b))
+    assert log_a[np.lexsort(log_a.T[::-1])].tobytes() == canonical_log(env, len(episodes_b), env.contact_log)
     env.close()
 
 

@@ -14,10 +14,10 @@ import pytest
 
 from openroborl_amd import _abi, state as statemod
 from tests import drift, oracle_lib as ol
+from tests.gpu_kit import CLIP
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLIP = {"laikago": "laikago_pace", "mini_cheetah": "minicheetah_trot"}
 
 FLOOR = drift.FLOOR
 

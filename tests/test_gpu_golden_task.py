@@ -18,7 +18,6 @@ from openroborl_amd import _abi
 from tests import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
-CLIP = {"laikago": "laikago_pace", "mini_cheetah": "minicheetah_trot"}
 
 
 def _replay(name):

@@ -17,26 +17,12 @@ import pytest
 from openroborl_amd import _abi, _lib, robots
 from openroborl_amd import env as envmod
 from tests import oracle_lib as ol
+from tests.gpu_kit import make_env, stress
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = "task_laikago_noise.npz"
 STD = {k: float(np.float32(v)) for k, v in envmod.INIT_PERTURB_STD.items()}     # what the device holds
-
-
-def make_env(n, files="laikago_pace", **kw):
-    kw.setdefault("robot", "laikago")
-    kw.setdefault("mode", "test")
-    kw.setdefault("enable_randomizer", False)
-    kw.setdefault("auto_reset", True)
-    kw.setdefault("seed", 5)
-    return envmod.VecQuadrupedEnv(num_robot=n, motion_file=files, **kw)
-
-
-def stress(env, obs, rng):
-    import torch
-    noise = torch.from_numpy(rng.normal(0.0, 0.05, (env.num_robot, 12)).astype(np.float32)).to(env.device)
-    return env.stress_actions(obs, noise, torch.empty_like(noise))
 
 
 def qmul(a, b):      # Hamilton product, xyzw, on [..., 4] arrays (transformations.quaternion_multiply)

@@ -7,9 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from openroborl_amd import _abi, robots, state as statemod
+from openroborl_amd import _abi, robots
 from openroborl_amd.env import CLIP_DRAW, clip_draw_index
-from tests import oracle_lib as ol
+from tests import gpu_kit, oracle_lib as ol
+from tests.gpu_kit import gpu_state64
 
 pytestmark = pytest.mark.gpu
 
@@ -17,18 +18,8 @@ SET4 = ["laikago_pace", "laikago_trot", "laikago_spin", "laikago_sidesteps"]
 TYPE_NAME = {v: k for k, v in robots.ROBOT_TYPE_ID.items()}
 
 
-def gpu_state64(env):
-    return statemod.to_float64(env.layout, env.state.detach().cpu().numpy())
-
-
 def make_env(n, motion_file, **kw):
-    from openroborl_amd.env import VecQuadrupedEnv
-    kw.setdefault("robot", "laikago")
-    kw.setdefault("mode", "test")
-    kw.setdefault("enable_randomizer", False)
-    kw.setdefault("auto_reset", False)
-    kw.setdefault("seed", 3)
-    return VecQuadrupedEnv(num_robot=n, motion_file=motion_file, **kw)
+    return gpu_kit.make_env(n, motion_file, **{"auto_reset": False, "seed": 3, **kw})
 
 
 def predicted_clips(env):

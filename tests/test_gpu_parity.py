@@ -9,10 +9,9 @@ import pytest
 
 from openroborl_amd import _abi, config, motion, robots, state as statemod
 from tests import oracle_lib as ol
+from tests.gpu_kit import CLIP, SOFT_TOES, gpu_state64, push_state
 
 pytestmark = pytest.mark.gpu
-
-CLIP = {"laikago": "laikago_pace", "mini_cheetah": "minicheetah_trot"}
 
 
 def make_pair(robot="laikago", n=32, randomizer=False, auto_reset=False, seed=3, mode="test", mixed=None, legacy_grid=False,
@@ -50,15 +49,6 @@ def compare_to_floor(env, orc, o32, names, what, mask=None):
                                           np.abs(o32.state[m][:, sl].astype(np.float64) - orc.state[m][:, sl]).max(axis=1), "%s %s" % (what, name))
 
 
-def gpu_state64(env):
-    return statemod.to_float64(env.layout, env.state.detach().cpu().numpy())
-
-
-def push_state(env, st64):
-    import torch
-    env.state.copy_(torch.from_numpy(statemod.from_float64(env.layout, st64)).to(env.device))
-
-
 def compare_fields(env, orc, names, atol, rtol=0.0, what="", outlier_robots=0, floor=None):
     """floor: the float32 build of the ORACLE (f32_twin) stepped like `orc` - a robot whose largest error stays within 1.5 x what the same
     algorithm in float32 does to that robot passes even beyond the hand-set tolerance (ill-conditioned inputs: a robot lying on its shanks
@@ -85,9 +75,6 @@ def compare_fields(env, orc, names, atol, rtol=0.0, what="", outlier_robots=0, f
 
 
 RIGID = ["POS", "QUAT", "LINVEL", "ANGVEL", "Q", "QD"]
-SOFT_TOES = {"contact_stiffness": 30000.0, "contact_damping": 1000.0, "foot_friction": 3.0}
-
-
 ANCHOR_TOES = {"friction_anchor": 1}
 
 

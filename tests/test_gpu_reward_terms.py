@@ -17,37 +17,15 @@ import pytest
 from openroborl_amd import _abi, robots, state as statemod
 from tests import oracle_lib as ol
 from tests import reward_terms_lib as rt
+from tests.gpu_kit import EPS, canonical_log, log_rows_match, mixed_env, short_episodes, stress
 
 pytestmark = pytest.mark.gpu
-CLIP = {"laikago": "laikago_pace", "mini_cheetah": "minicheetah_trot"}
-EPS = 2.0 ** -24
 NAMES = _abi.REWARD_TERM_NAMES
 
 
 def identity_bound(w):
     """|reward - sum_k w_k terms_k|: five products and four adds of values <= 1 in float32, whatever their order or contraction"""
     return 16.0 * EPS * np.abs(w).sum()
-
-
-def stress(env, obs, rng):
-    import torch
-    noise = torch.from_numpy(rng.normal(0.0, 0.05, (env.num_robot, 12)).astype(np.float32)).to(env.device)
-    return env.stress_actions(obs, noise, torch.empty_like(noise))
-
-
-def mixed_env(n, **kw):
-    from openroborl_amd.env import VecQuadrupedEnv
-    mixed = ["laikago", "mini_cheetah"]
-    kw.setdefault("seed", 3)
-    kw.setdefault("mode", "train")
-    kw.setdefault("enable_randomizer", True)
-    return VecQuadrupedEnv(num_robot=n, mixed_robots=mixed, motion_file=[CLIP[m] for m in mixed], **kw)
-
-
-def short_episodes():
-    """ep_len_start = 8, ep_len_end = 24 with the curriculum as the fixtures set it"""
-    g = rt.fixture(rt.FIXTURES[0])
-    return dict(ep_len_start=8, ep_len_end=24, curriculum_steps=int(g["curriculum_steps"]))
 
 
 # ---- 1. against the reference's Python --------------------------------------------------------------------------------------------
@@ -212,20 +190,8 @@ def check_log(env, episodes, logged=None):
     ep_log, term_log = env.ep_log[:k].cpu().numpy(), env.term_log[:k].cpu().numpy()
     L = ep_log[:, 1].astype(np.float64)
     assert (np.abs(term_log.astype(np.float64) @ w - ep_log[:, 0]) <= L * 16 * EPS + L * L * 2.0 ** -25).all()
-    rows = sorted((np.float32(r).tobytes(), l, s.astype(np.float32).tobytes()) for _, l, _, s, r in episodes)
-    got = sorted((ep_log[j, 0].tobytes(), int(ep_log[j, 1]), term_log[j].tobytes()) for j in range(k))
-    if logged is None:
-        assert got == rows
-    else:
-        assert all(g in rows for g in got) and len(got) == logged
+    log_rows_match(ep_log, term_log, [(r, l, s) for _, l, _, s, r in episodes], logged)
     return ep_log, term_log
-
-
-def canonical_log(env, k):
-    """The first k rows of the episode log with their term rows, in an order that does not depend on which wave's slot request
-    arrived first (the slots of one launch go by arrival)"""
-    rows = np.concatenate([env.ep_log[:k].cpu().numpy(), env.term_log[:k].cpu().numpy()], axis=1)
-    return rows[np.lexsort(rows.T[::-1])].tobytes()
 
 
 def test_identity_sums_and_log_rows_with_auto_reset():
@@ -248,7 +214,7 @@ def test_identity_sums_and_log_rows_with_auto_reset():
     env.close()
     terms_b, sums_b, episodes_b, env = bookkeeping_run()
     assert terms_a.tobytes() == terms_b.tobytes() and sums_a.tobytes() == sums_b.tobytes()
-    assert log_a[np.lexsort(log_a.T[::-1])].tobytes() == canonical_log(env, len(episodes_b))
+    assert log_a[np.lexsort(log_a.T[::-1])].tobytes() == canonical_log(env, len(episodes_b), env.term_log)
     env.close()
 
 

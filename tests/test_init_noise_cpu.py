@@ -31,8 +31,7 @@ def test_the_noise_unit_compiles_for_gfx950_with_its_three_kernels_and_no_fence(
     bodies = nf.kernel_bodies(asm)
     assert sorted(bodies) == sorted(s for s in bodies if re.match(r"_Z15orr_step_kernelILi[02]ELi1ELb0ELb1ELb1EE", s)) and len(bodies) == 2, sorted(bodies)
     assert re.search(r"^_Z16orr_reset_kernelILb1ELb1EE\S*:", asm, re.M)
-    for sym, body in bodies.items():
-        assert not [t for t in body if t.startswith("buffer_wbl2") or t.startswith("buffer_inv")], sym
+    nf.assert_no_cache_writeback(bodies)
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_stats
@@ -49,8 +48,8 @@ def test_the_noise_unit_compiles_for_gfx950_with_its_three_kernels_and_no_fence(
 def test_the_kernel_tuning_knobs_compile_in_the_noise_unit_too(defs):
     """The development builds (tools/dev_build.py) pass their defines to every env unit, this one included: each of the knobs that
     tests/test_cpu_host.py keeps compiling in the four older units goes through the device compiler's front end here."""
-    base = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + ["--cuda-device-only", "-fsyntax-only", "-Wno-unused-command-line-argument"]
-    r = subprocess.run([_lib.HIPCC] + base + defs + [_lib.SRC_NOISE], capture_output=True, text=True)
+    from tests import test_step_kernel_no_fence as nf
+    r = nf.front_end_compiles(_lib.SRC_NOISE, defs)
     assert r.returncode == 0, "%s:\n%s" % (" ".join(defs), r.stderr[-1500:])
 
 

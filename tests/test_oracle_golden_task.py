@@ -26,7 +26,6 @@ from tests import oracle_lib as ol
 
 GOLD = ol.GOLDEN
 TOL = 1e-9
-CLIP = {"laikago": "laikago_pace", "mini_cheetah": "minicheetah_trot"}
 dp = ol.dp
 
 

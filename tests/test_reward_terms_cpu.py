@@ -6,7 +6,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
@@ -31,8 +30,7 @@ def test_the_terms_unit_compiles_for_gfx950_with_its_two_kernels_no_fence_and_no
     assert sorted(re.match(r"(_Z15orr_step_kernelILi\dELi\dELb\dELb\dELb\dEE)", s).group(1) for s in bodies) == [
         "_Z15orr_step_kernelILi4ELi1ELb0ELb1ELb1EE", "_Z15orr_step_kernelILi6ELi1ELb0ELb1ELb1EE"], sorted(bodies)
     assert not re.search(r"^_Z16orr_reset_kernel\S*:", asm, re.M)            # the resets are the noise unit's
-    for sym, body in bodies.items():
-        assert not [t for t in body if t.startswith("buffer_wbl2") or t.startswith("buffer_inv")], sym
+    nf.assert_no_cache_writeback(bodies)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_stats
     assert "noise" in isa_stats.STEP_KERNELS[-1][1] and "terms" not in isa_stats.STEP_KERNELS[-1][1]
@@ -51,8 +49,8 @@ def test_the_terms_unit_compiles_for_gfx950_with_its_two_kernels_no_fence_and_no
 
 @pytest.mark.parametrize("defs", [["-DORR_GENERIC_PGS"], ["-DORR_PHASE_TIMERS"], ["-DORR_COUNT_DUAL_CONTACT"], ["-DORR_WAVE_TIMELINE"], ["-DORR_WAVES_PER_EU=2"]])
 def test_the_kernel_tuning_knobs_compile_in_the_terms_unit_too(defs):
-    base = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + ["--cuda-device-only", "-fsyntax-only", "-Wno-unused-command-line-argument"]
-    r = subprocess.run([_lib.HIPCC] + base + defs + [_lib.SRC_TERMS], capture_output=True, text=True)
+    from tests import test_step_kernel_no_fence as nf
+    r = nf.front_end_compiles(_lib.SRC_TERMS, defs)
     assert r.returncode == 0, "%s:\n%s" % (" ".join(defs), r.stderr[-1500:])
 
 

@@ -35,17 +35,25 @@ def compile_unit(src, flags, out_dir):
         return fh.read()
 
 
+def front_end_compiles(src, defs):
+    """`src` with the extra defines through the device compiler's front end only (syntax, templates, static_asserts); the completed process"""
+    base = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + ["--cuda-device-only", "-fsyntax-only", "-Wno-unused-command-line-argument"]
+    return subprocess.run([_lib.HIPCC] + base + defs + [src], capture_output=True, text=True)
+
+
+def assert_no_cache_writeback(bodies, what=""):
+    for sym, body in bodies.items():
+        bad = [t for t in body if t.startswith("buffer_wbl2") or t.startswith("buffer_inv")]
+        assert not bad, (what, sym, bad[:4])
+
+
 def test_no_cache_writeback_in_step_kernels():
     with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(len(UNITS)) as ex:
         asms = list(ex.map(lambda u: compile_unit(u[0], u[1], d), UNITS))
     checked = []
     for (src, _), asm in zip(UNITS, asms):
-        for sym, body in kernel_bodies(asm).items():
-            mode = int(re.match(r"_Z15orr_step_kernelILi(\d+)E", sym).group(1))
-            if mode not in (0, 2):
-                continue
-            checked.append((os.path.basename(src), sym))
-            bad = [t for t in body if t.startswith("buffer_wbl2") or t.startswith("buffer_inv")]
-            assert not bad, (os.path.basename(src), sym, bad[:4])
+        bodies = {sym: body for sym, body in kernel_bodies(asm).items() if int(re.match(r"_Z15orr_step_kernelILi(\d+)E", sym).group(1)) in (0, 2)}
+        checked += [(os.path.basename(src), sym) for sym in bodies]
+        assert_no_cache_writeback(bodies, os.path.basename(src))
     # MODE 0 in all four units (one-wave, two-wave, friction anchors, clip sets), MODE 2 in the main and the clip-set units
     assert len(checked) == 6, checked
