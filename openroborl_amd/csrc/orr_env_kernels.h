@@ -646,6 +646,135 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
 }
 
 
+#ifdef ORR_STAGE_DUMP
+// Development aid (tests/test_gpu_substep_stages.py, tools/dev_build.py STAGE_DUMP): -DORR_STAGE_DUMP adds a kernel that runs the FIRST
+// HALF of one physics sub-step - leg_dynamics, row_setup_bank_a / row_setup_limit, row_response for both banks, the functions of
+// orr_physics.h themselves, called in physics_substep's order with its arguments - on the records as they are and writes what the stages
+// hand to each other to a caller's buffer, kStageWords float32 words per robot (integers as values).  Up to the first sub-step it is
+// the debug physics (MODE & 3 == 1) of orr_step_kernel; it never stores the record.  The joint-limit bank is always set up and answered
+// (no limit_idle skipping, no `anyB` test).  Layout of a robot's words (tests/stage_refs.py mirrors it):
+//   kStageUstar   ustar[18]                                          after leg_dynamics
+//   kStageLc      lc[12][18]: Rw[9], ow[3], s[3], sv[3]              (dumped before row_response: W shares the space of dyn)
+//   kStageLeg     leg[4][24]: T[3][6], Hi[6]
+//   kStageBf      per lane 27: the factor L of A0 packed row-wise, (i, j) -> i (i + 1) / 2 + j (its diagonal as 1 / idg: Chol6Pk keeps
+//                 the reciprocals only), then idg[6]
+//   kStageRow     per lane and bank (A, B) 40: active, leg, nrm_slot, warm, Jb[6], jl[3], rhs (unscaled), cfm, lo_c, hi_c, mu_e after the
+//                 setup; wa[6], wq[12], jdi, rhs (scaled), lam, w after the response
+//   kStageGeom    per lane 20: ContactGeom[12], the joint-limit margin, AnchorState after the setup (la[3], wb[3], valid; zeros without ANCHOR)
+//   kStageW       the LDS copy W[28][18] after the responses
+// Whole waves, no data-dependent loop, every store behind a bounds check, a padding lane group stores nothing.
+namespace orr {
+constexpr int kStageUstar = 0, kStageLc = kStageUstar + 18, kStageLeg = kStageLc + 12 * 18, kStageBf = kStageLeg + 4 * 24;
+constexpr int kStageRowWords = 40, kStageRow = kStageBf + kLanes * 27, kStageGeom = kStageRow + kLanes * 2 * kStageRowWords;
+constexpr int kStageW = kStageGeom + kLanes * 20, kStageWords = kStageW + kMaxRows * 18;
+}
+template <bool ANCHOR, int WPE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_stage_dump_kernel(KParams P, const float* torques, float* out, long long out_words) {
+  ORR_PROLOGUE();
+  (void)obs;
+  const bool valid = in_range;
+  const orr_config& cfg = P.cfg;
+  const long long base = (long long)robot * kStageWords;
+  auto put = [&](int k, float v) __attribute__((always_inline)) {
+    if (valid && k >= 0 && k < kStageWords && base + k < out_words) out[base + k] = v;
+  };
+  load_robot(P, rec, S, lane);
+  for (int i = lane; i < kMaxRows * kWStride; i += kLanes) (&S.ph.sub.W[0][0])[i] = 0.0f;
+  WSYNC();
+  LegConst K;
+  load_leg_const(P, S, lane, K);
+  {
+    float rel[4], Rb[9];
+    base_rotation(S, lane, rel, Rb);
+  }
+  AnchorState AS = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};
+  bool anchor_robot = false;
+  const int aleg = lane < 4 ? lane : (lane < 8 ? lane - 4 : (lane - 8) >> 1);
+  if constexpr (ANCHOR) {
+    anchor_robot = model_cold(P, geti(S, O(ROBOT_TYPE)))->friction_anchor != 0;
+    const float* an = rec + O(ANCHOR) + 6 * aleg;
+    AS.la[0] = an[0]; AS.la[1] = an[1]; AS.la[2] = an[2]; AS.wb[0] = an[3]; AS.wb[1] = an[4]; AS.wb[2] = an[5];
+    AS.valid = anchor_robot ? __float_as_int(rec[O(ANCHOR_VALID) + aleg]) : 0;
+  }
+  if (lane < 12) {
+    const ColdPtr mc = model_cold(P, geti(S, O(ROBOT_TYPE)));
+    const int j = mc->joint_of_motor[lane];
+    S.tau[j] = mc->tau_sign_motor[lane] * torques[(size_t)robot * 12 + lane];
+  }
+  WSYNC();
+  // ---- physics_substep's first half ----
+  const float dt = cfg.sim_dt, inv_dt = 1.0f / cfg.sim_dt, erp_dt = cfg.contact_erp / cfg.sim_dt;
+  BaseFactor BF;
+  leg_dynamics(P, S, K, lane, BF);
+  WSYNC();
+  for (int i = lane; i < 18; i += kLanes) put(kStageUstar + i, S.ustar[i]);
+  for (int i = lane; i < 12 * 18; i += kLanes) {
+    const LinkCache& L = S.ph.sub.dyn.lc[i / 18];
+    const int k = i % 18;
+    put(kStageLc + i, k < 9 ? L.Rw[k] : (k < 12 ? L.ow[k - 9] : (k < 15 ? L.s[k - 12] : L.sv[k - 15])));
+  }
+  for (int i = lane; i < 4 * 24; i += kLanes) {
+    const LegSolve& Q = S.leg[i / 24];
+    const int k = i % 24;
+    put(kStageLeg + i, k < 18 ? Q.T[k / 6][k % 6] : Q.Hi[k - 18]);
+  }
+  {
+    const Chol6Pk& F = BF.F;
+    const float Lp[21] = {1.0f / F.idg[0],
+                          F.l10, 1.0f / F.idg[1],
+                          F.c0a.x, F.c1a.x, 1.0f / F.idg[2],
+                          F.c0a.y, F.c1a.y, F.l32, 1.0f / F.idg[3],
+                          F.c0b.x, F.c1b.x, F.c2b.x, F.c3b.x, 1.0f / F.idg[4],
+                          F.c0b.y, F.c1b.y, F.c2b.y, F.c3b.y, F.l54, 1.0f / F.idg[5]};
+#pragma unroll
+    for (int i = 0; i < 21; i++) put(kStageBf + lane * 27 + i, Lp[i]);
+#pragma unroll
+    for (int i = 0; i < 6; i++) put(kStageBf + lane * 27 + 21 + i, F.idg[i]);
+  }
+  auto put_setup = [&](int bank, const Row& R) __attribute__((always_inline)) {
+    const int o = kStageRow + (lane * 2 + bank) * kStageRowWords;
+    put(o, R.active ? 1.0f : 0.0f); put(o + 1, (float)R.leg); put(o + 2, (float)R.nrm_slot); put(o + 3, (float)R.warm);
+#pragma unroll
+    for (int i = 0; i < 6; i++) put(o + 4 + i, R.Jb[i]);
+#pragma unroll
+    for (int i = 0; i < 3; i++) put(o + 10 + i, R.jl[i]);
+    put(o + 13, R.rhs); put(o + 14, R.cfm); put(o + 15, R.lo_c); put(o + 16, R.hi_c); put(o + 17, R.mu_e);
+  };
+  auto put_response = [&](int bank, const Row& R) __attribute__((always_inline)) {
+    const int o = kStageRow + (lane * 2 + bank) * kStageRowWords + 18;
+#pragma unroll
+    for (int i = 0; i < 6; i++) put(o + i, R.wa[i]);
+#pragma unroll
+    for (int i = 0; i < 12; i++) put(o + 6 + i, R.wq[i]);
+    put(o + 18, R.jdi); put(o + 19, R.rhs); put(o + 20, R.lam); put(o + 21, R.w);
+  };
+  Row A, B;
+  const bool rowlane = lane < 16;
+  ContactGeom G;
+  row_setup_bank_a<ANCHOR>(S, cfg, rowlane ? (lane < 4 ? lane : lane + 12) : 0, rowlane, dt, inv_dt, erp_dt, A, G, ANCHOR ? &AS : nullptr, anchor_robot);
+  float margin = 1e30f;
+  row_setup_limit(S, cfg, (rowlane && lane >= 4) ? lane : 4, rowlane && lane >= 4, inv_dt, erp_dt, B, &margin);
+  put_setup(0, A);
+  put_setup(1, B);
+  {
+    const int o = kStageGeom + lane * 20;
+    const float g[12] = {G.rr0, G.rr1, G.rr2, G.c00, G.c01, G.c02, G.c10, G.c11, G.c12, G.c20, G.c21, G.c22};
+#pragma unroll
+    for (int i = 0; i < 12; i++) put(o + i, g[i]);
+    put(o + 12, margin);
+#pragma unroll
+    for (int i = 0; i < 3; i++) { put(o + 13 + i, AS.la[i]); put(o + 16 + i, AS.wb[i]); }
+    put(o + 19, (float)AS.valid);
+  }
+  row_response(S, cfg, A, rowlane ? (lane < 4 ? lane : lane + 12) : 0, BF);
+  row_response(S, cfg, B, (rowlane && lane >= 4) ? lane : kMaxRows, BF);   // lanes without a joint-limit row: dump slot
+  put_response(0, A);
+  put_response(1, B);
+  WSYNC();
+  for (int i = lane; i < kMaxRows * 18; i += kLanes) put(kStageW + i, S.ph.sub.W[i / 18][i % 18]);
+}
+#endif
+
 // ================================================================================================
 // launchers
 // ================================================================================================
@@ -684,4 +813,23 @@ extern template StepLaunch launch_step<kModeTerms | 2, 1, false, true, true>;   
 extern template StepLaunch launch_step<kModeContacts | 0, 1, false, true, true>;                // orr_kernels_contacts.hip: env step with the contact sums,
 extern template StepLaunch launch_step<kModeContacts | kModeTerms | 0, 1, false, true, true>;   //   the same with the reward terms,
 extern template StepLaunch launch_step<kModeContacts | 1, 1, false, false>;                     //   debug physics (resets: the noise unit's; no parity replay)
+
+#ifdef ORR_STAGE_DUMP
+// the stage dump: instantiated in BOTH step units (orr_kernels.hip: WPE 1, orr_kernels_w2.hip: WPE 2), which compile different forms of
+// the very functions it calls (kCarrySubtreeMass, kOwnLegFactor, their flags)
+using StageDumpLaunch = hipError_t(const KParams& P, int waves, hipStream_t stream, const float* torques, float* out, long long out_words);
+template <bool ANCHOR, int WPE>
+hipError_t launch_stage_dump(const KParams& P, int waves, hipStream_t stream, const float* torques, float* out, long long out_words) {
+  hipLaunchKernelGGL((orr_stage_dump_kernel<ANCHOR, WPE>), dim3(waves), dim3(64), 0, stream, P, torques, out, out_words);
+  return hipGetLastError();
+}
+#ifndef ORR_TU_MAIN
+extern template StageDumpLaunch launch_stage_dump<false, 1>;                  // orr_kernels.hip
+extern template StageDumpLaunch launch_stage_dump<true, 1>;
+#endif
+#ifndef ORR_TU_STEP_W2
+extern template StageDumpLaunch launch_stage_dump<false, 2>;                  // orr_kernels_w2.hip
+extern template StageDumpLaunch launch_stage_dump<true, 2>;
+#endif
+#endif
 }  // namespace orr

@@ -18,6 +18,10 @@ template orr::ResetLaunch orr::launch_reset<false>;
 template orr::StepLaunch orr::launch_step<0, ORR_WAVES_PER_EU, false, false>;
 template orr::StepLaunch orr::launch_step<1, ORR_WAVES_PER_EU, false, false>;
 template orr::StepLaunch orr::launch_step<2, ORR_WAVES_PER_EU, false, false>;
+#ifdef ORR_STAGE_DUMP
+template orr::StageDumpLaunch orr::launch_stage_dump<false, 1>;     // development aid (orr_debug_stage_dump below)
+template orr::StageDumpLaunch orr::launch_stage_dump<true, 1>;
+#endif
 
 // Rollout boundary (agents/ppo_imitation.py:405-423): pack this rank's episode log into the fixed-size float64 payload of the
 // all-gather -- [n_listed, total_timesteps, n_dropped, n_episodes, sum_ret, sum_len, ret[K], len[K]] -- and clear the log, in
@@ -620,6 +624,23 @@ int32_t orr_time_steps(orr_handle* h, const float* actions_dev, float* obs_dev, 
   return 0;
 }
 
+#ifdef ORR_STAGE_DUMP
+// development aid (-DORR_STAGE_DUMP; tests/test_gpu_substep_stages.py): what the first half of ONE physics sub-step hands from stage to
+// stage (orr_stage_dump_kernel, orr_env_kernels.h), for the bound records as they are and the given motor torques [N][12]; the records
+// are not changed.  out_dev takes orr_debug_stage_words() float32 words per robot.  The unit is the one whose step kernel the handle
+// runs (batch size, ORR_STEP_WAVES_PER_EU), the friction-anchor form that of a handle with an anchor model.
+int32_t orr_debug_stage_words(void) { return kStageWords; }
+int32_t orr_debug_stage_dump(orr_handle* h, const float* torques_dev, float* out_dev, int64_t out_words, void* stream) {
+  if (!h || !h->state) return fail(-1, "orr_debug_stage_dump: handle not bound");
+  if (!torques_dev || !out_dev) return fail(-1, "orr_debug_stage_dump: null buffer");
+  if (out_words < (int64_t)h->cfg.num_robots * kStageWords) return fail(-1, "orr_debug_stage_dump: out_words is less than num_robots * orr_debug_stage_words()");
+  const bool two = h->force_wpe ? h->force_wpe == 2 : waves_of(h) > h->simds, anchor = h->anchor_types != 0;
+  StageDumpLaunch* const launch = two ? (anchor ? launch_stage_dump<true, 2> : launch_stage_dump<false, 2>)
+                                      : (anchor ? launch_stage_dump<true, 1> : launch_stage_dump<false, 1>);
+  HIPCHK(launch(make_params(h), waves_of(h), (hipStream_t)stream, torques_dev, out_dev, (long long)out_words), "orr_debug_stage_dump: launch");
+  return 0;
+}
+#endif
 #if defined(ORR_COUNT_DUAL_CONTACT)
 // development aid: read (and optionally clear) the toe / shank contact counters of the -DORR_COUNT_DUAL_CONTACT build
 int orr_debug_dual_contact(unsigned long long* out8, int reset) {

@@ -10,3 +10,7 @@
 #endif
 #include "orr_env_kernels.h"
 template orr::StepLaunch orr::launch_step<0, 2, false, false>;
+#ifdef ORR_STAGE_DUMP
+template orr::StageDumpLaunch orr::launch_stage_dump<false, 2>;     // development aid: this unit's forms of the sub-step's first half
+template orr::StageDumpLaunch orr::launch_stage_dump<true, 2>;
+#endif

@@ -7,9 +7,11 @@
 // bcast_lane, dpp_bcast_max0, dpp_contact_triplet, part_suffix_sum (+ _inplace, _first_moment), zero_in_lane; chol6 / chol6_solve and
 // chol6_pk / chol6_solve_pk; philox_block, time_limit.  Probed by the siblings: normal_pair (orr_probe_noise.hip); the two solver stages
 // built from these leaves, delassus_columns and pgs_sweeps, which take their operands in registers (orr_probe_solver.hip).
-// NOT probed: row_setup_bank_a / row_setup_limit, row_response and leg_dynamics read and write the per-robot LDS image (Shared), so they
-// cannot be driven with chosen register inputs; they stay with the sub-step parity tests (tests/test_gpu_parity.py,
-// tests/test_gpu_substep_paths.py).
+// NOT probed HERE: row_setup_bank_a / row_setup_limit, row_response and leg_dynamics read and write the per-robot LDS image (Shared) and
+// need KParams and the device tables, so they cannot be driven with chosen register inputs.  Their outputs are read stage by stage
+// through the -DORR_STAGE_DUMP build of the library itself (orr_stage_dump_kernel, csrc/orr_env_kernels.h) and compared with float64
+// by tests/test_gpu_substep_stages.py; the sub-step parity tests (tests/test_gpu_parity.py, tests/test_gpu_substep_paths.py) see them
+// through a whole sub-step.
 // `in` / `out` are DEVICE pointers to n records of the helper's arguments / results (array of records, 4-byte words; the layouts
 // are listed at each entry point and mirrored by tests/probe_lib.py: SPECS).  Returns 0, or -1 for a bad n, or the hipError_t of the
 // launch.  One lane serves one record; every kernel checks its bounds and has no data-dependent loop.

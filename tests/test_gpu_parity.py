@@ -51,7 +51,7 @@ def compare_to_floor(env, orc, o32, names, what, mask=None):
 
 def compare_fields(env, orc, names, atol, rtol=0.0, what="", outlier_robots=0, floor=None):
     """floor: the float32 build of the ORACLE (f32_twin) stepped like `orc` - a robot whose largest error stays within 1.5 x what the same
-    algorithm in float32 does to that robot passes even beyond the hand-set tolerance (ill-conditioned inputs: a robot lying on its shanks
+    algorithm in float32 does to that robot passes beyond the hand-set tolerance, up to 10 x it (ill-conditioned inputs: a robot lying on its shanks
     with a 0.25 kg toe; measured round 6: float32 oracle 4.0e-4 on one joint rate of 384, HIP 3.0e-4, tolerance 2.2e-4).
     outlier_robots: that many robots may miss both - by at most 10 x the tolerance - at a multi-sub-step horizon, where a contact row
     that one side creates a sub-step earlier than the other (float32 distance against the contact margin) is a discrete event, not an
@@ -63,13 +63,14 @@ def compare_fields(env, orc, names, atol, rtol=0.0, what="", outlier_robots=0, f
             np.testing.assert_array_equal(g[:, sl], orc.state[:, sl], err_msg="%s %s" % (what, name))
         elif outlier_robots or floor is not None:
             e = np.abs(g[:, sl] - orc.state[:, sl])
-            bad = (e > atol + rtol * np.abs(orc.state[:, sl])).any(axis=1)
+            beyond = bad = (e > atol + rtol * np.abs(orc.state[:, sl])).any(axis=1)
             if floor is not None:
                 e32 = np.abs(floor.state[:, sl].astype(np.float64) - orc.state[:, sl])
-                bad &= e.max(axis=1) > 1.5 * e32.max(axis=1)
+                bad = beyond & (e.max(axis=1) > 1.5 * e32.max(axis=1))
             assert bad.sum() <= outlier_robots, "%s %s: %d robots beyond tolerance and float32 floor (largest error %.3g)" % (what, name, bad.sum(), e[bad].max())
-            if bad.any():
-                np.testing.assert_allclose(g[bad][:, sl], orc.state[bad][:, sl], atol=10 * atol, rtol=10 * rtol, err_msg="%s %s (outlier bound)" % (what, name))
+            if beyond.any():     # whichever exemption a robot used - the float32 floor's or an outlier's - it stays within 10 x the tolerance
+                print("%s %s: %d robots cleared by the float32 floor, %d outliers" % (what, name, (beyond & ~bad).sum(), bad.sum()))
+                np.testing.assert_allclose(g[beyond][:, sl], orc.state[beyond][:, sl], atol=10 * atol, rtol=10 * rtol, err_msg="%s %s (bound of the exempted robots)" % (what, name))
         else:
             np.testing.assert_allclose(g[:, sl], orc.state[:, sl], atol=atol, rtol=rtol, err_msg="%s %s" % (what, name))
 

@@ -6,7 +6,7 @@ Three probe builds: `one` and `w2` carry the hand-scheduled sweeps (pgs_sweeps_b
 `generic` the readable C++ form behind ORR_GENERIC_PGS.  Inputs: six named buckets of 1024 robots (standing, sliding, limits,
 missing_legs, soft, idle; tests/test_device_probe_cpu.py checks that rows end on both sides of every bound).  Each test prints
 `PRIMITIVE <name> <build> max_err=... bound=... n=...` lines in the format of tests/test_gpu_device_primitives.py (run with -s; the
-lines of one MI355X run belong in profiles/device_primitives.txt beside the leaves', and are not there yet).
+lines of one MI355X run are in profiles/device_primitives.txt beside the leaves': per entry and build the line nearest its bound).
 
 Bounds.  Exact tests compare bit patterns (values where the sign of a zero is free: med3(y, -0, +0) and max(-0, 0) may give either).
 Columns: (chained roundings on the entry's path + 1) x 2^-24 of the sum of its terms' magnitudes, counted at COLUMN_ROUNDINGS.

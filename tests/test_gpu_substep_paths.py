@@ -7,7 +7,7 @@ Seven robots = one full wave and one partly filled wave.  The debug physics entr
 (the second and third sub-step of a launch take the path that skips the joint-limit row setup) against the float64 oracle, at the
 tolerances tests/test_gpu_parity.py uses for ONE sub-step: 2e-6 on positions, 1.5e-4 on velocities, 5e-4 on the stored impulses.
 
-The states are built here (robot_state, on tests/phys_ref.py's kinematics, the way tests/parity_inputs.py's shank_contact_inputs does it)
+The states are built by tests/gpu_kit.py's robot_state (on tests/phys_ref.py's kinematics, the way tests/parity_inputs.py's shank_contact_inputs does it)
 and not drawn with substep_parity_inputs: the cases need an exact contact pattern per robot and joints a millimetre-radian from a
 bound, and each test checks that its inputs are that.  A joint-limit row only shows in the result when its impulse is non-zero, i.e.
 when the joint would cross the bound within the sub-step (rate * dt > gap): the limited joints sit 0.001 rad inside the bound at
@@ -19,14 +19,13 @@ import pytest
 
 from openroborl_amd import state as statemod
 from tests import oracle_lib as ol
-from tests import phys_ref as pr
+from tests.gpu_kit import HIP, KNEE, THIGH, robot_state
 from tests.test_gpu_parity import CLIP, compare_fields, gpu_state64, push_state
 
 pytestmark = pytest.mark.gpu
 
 N = 7                       # robots 0..3: a full wave; robots 4..6: a wave with one empty slot
 PTOL, VTOL, LTOL = 2e-6, 1.5e-4, 5e-4      # test_physics_substep_parity, nsub = 1
-HIP, THIGH, KNEE = 0, 1, 2
 GAP, RATE = 0.001, 2.0      # a limited joint: GAP inside its bound, moving into it at RATE (it would cross in half a sub-step of 1 ms)
 
 
@@ -48,59 +47,6 @@ def pair():
     env, orc, free = make_env()
     yield env, orc, free
     env.close(); orc.close(); free.close()
-
-
-def leg_clearance(m, pos, quat, q):
-    """height of the lowest contact sphere (toe or shank) of each leg above the plane"""
-    bodies, _ = pr.kinematics(m, pos, quat, q)
-    out = []
-    for leg in range(4):
-        b = bodies[1 + 3 * leg + 2]
-        h = (b["o"] + b["R"] @ m["toe_pos"][leg])[2] - m["toe_radius"]
-        if m["shank_radius"] > 0:
-            h = min(h, (b["o"] + b["R"] @ m["shank_pos"][leg])[2] - m["shank_radius"])
-        out.append(h)
-    return np.array(out)
-
-
-def robot_state(env, base_row, rng, lifted=(), height=0.0, limits=(), qd=None):
-    """One record: the robot standing level in its initial pose, every toe 1 mm inside the plane; the legs in `lifted` folded at the knee
-    until their toe is clear of the contact margin; `height` added to the base; limits = ((leg, part, side, gap, rate), ...): that joint
-    `gap` away from its lower (side 0) / upper (side 1) bound, moving towards it at `rate`.  Small random velocities otherwise
-    (qd: the twelve joint rates instead).  -> (record, down [4] bool, limited [12] bool) as the device will see them."""
-    lay, m, cfg = env.layout, env.models[int(np.asarray(env.robot_type).flat[0])], env.cfg      # one robot type in the batch
-    dirj, offj, _ = pr.joint_maps(m)
-    ang = np.zeros(12)                                                  # kinematic angle a = dirj (q - offj) = the motor's angle
-    for mot in range(12):
-        ang[int(m["joint_of_motor"][mot])] = m["init_motor_angles"][mot]
-    rate = rng.uniform(-0.5, 0.5, 12) if qd is None else np.array(qd, dtype=float)
-    stand = leg_clearance(m, np.zeros(3), m["init_quat"], ang * dirj + offj)
-    assert np.ptp(stand) < 1e-4, stand                                   # the initial pose stands level
-    for leg in lifted:
-        ang[3 * leg + KNEE] -= 0.3                                       # folds the leg (the bound is at -2.775, the pose at -1.25)
-    for leg, part, side, gap, speed in limits:
-        j = 3 * leg + part
-        ang[j] = (m["joint_hi"][j] - gap) if side else (m["joint_lo"][j] + gap)
-        rate[j] = speed if side else -speed
-    q = ang * dirj + offj
-    pos = np.array([rng.uniform(-1, 1), rng.uniform(-1, 1), -stand.min() - 0.001 + height])
-    st = base_row.copy()
-    st[lay.sl("POS")] = pos
-    st[lay.sl("QUAT")] = m["init_quat"]
-    st[lay.sl("Q")] = q
-    st[lay.sl("QD")] = rate * dirj
-    st[lay.sl("LINVEL")] = rng.uniform(-0.1, 0.1, 3)
-    st[lay.sl("ANGVEL")] = rng.uniform(-0.2, 0.2, 3)
-    st[lay.sl("LAMBDA")] = 0.0
-    st[lay.sl("KNEE_FRICTION")] = rng.uniform(0.0, 0.05, 4)
-    st[lay.sl("FOOT_MU")] = rng.uniform(0.5, 1.25)
-    clear = leg_clearance(m, pos, m["init_quat"], q)
-    margin = float(cfg.contact_margin)
-    assert (np.abs(clear - margin) > 5e-4).all(), clear                  # nobody sits on the threshold
-    a = dirj * (q - offj)
-    room = np.minimum(a - m["joint_lo"], m["joint_hi"] - a) - float(cfg.limit_activation)
-    assert (np.abs(room) > 0.02).all(), room
-    return st, clear < margin, room < 0.0
 
 
 def build(env, orc, specs, seed):

@@ -16,8 +16,10 @@ PHASE_NAMES = ["load+leg consts", "set_act/filter", "substep control", "leg dyna
                "Delassus columns", "PGS sweeps", "du+integrate", "receive_obs (ring)", "ctrl_obs+sensors", "reward+ref update",
                "termination+obs", "episode end/reset", "store"]
 DEBUG_ARGTYPES = {"orr_debug_phase_cycles": [C.POINTER(C.c_longlong), C.c_int], "orr_debug_wave_phases": [C.POINTER(C.c_longlong), C.c_int],
-                  "orr_debug_wave_times": [C.POINTER(C.c_longlong), C.c_int], "orr_debug_dual_contact": [C.POINTER(C.c_ulonglong), C.c_int]}
+                  "orr_debug_wave_times": [C.POINTER(C.c_longlong), C.c_int], "orr_debug_dual_contact": [C.POINTER(C.c_ulonglong), C.c_int],
+                  "orr_debug_stage_words": [], "orr_debug_stage_dump": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]}
 PHASE_TIMERS = ("phase_timers", ["-DORR_PHASE_TIMERS"])      # load(*PHASE_TIMERS): the build that four of the tools and tests/test_gpu_tools.py share
+STAGE_DUMP = ("stage_dump", ["-DORR_STAGE_DUMP"])            # the build with orr_debug_stage_dump (tests/test_gpu_substep_stages.py)
 
 
 def build(name, flags):
