@@ -347,6 +347,34 @@ int32_t orr_bind_reward_terms(orr_handle* h, float* terms_dev, float* term_sums_
  * model is set afterwards). */
 int32_t orr_bind_contact_outputs(orr_handle* h, float* contact_dev, float* contact_ep_dev, float* contact_log_dev);
 
+/* motor torque limits and per-motor torque / work outputs: what the actuator chain did, per robot and motor (motor order).
+ * MotorModel torque_limits (minitaur_motor.py:166-171): limits_host[12] in motor order, N m, applied to the
+ * strength-scaled PD torque of every sub-step; +inf = no limit for that motor; NULL = none for the type.
+ * 0 is legal (the motor is off).  The limits are the caller's data: a handle starts with none, and no shipped robot table carries any.
+ * Refused, nothing changed: a null handle, a robot type out of range, a NaN or negative limit (the message names limits_host[i]), a
+ * finite limit on a handle that has a robot type with friction anchors. */
+int32_t orr_set_torque_limits(orr_handle* h, int32_t robot_type, const float* limits_host);
+
+/* act_dev float[N][12][4], row [motor] = {sum tau, max |tau|, sum tau^2, W} over the launch's sub-steps (orr_step,
+ *   orr_time_steps, orr_debug_replay_step); a step that sets ORR_DONE_NAN writes zeros; with auto-reset the row
+ *   is that of the step that ended the episode; no reset touches it.
+ *   tau = the motor-convention torque that went into the physics, after strength and limit (what orr_debug_replay_step's tau_out
+ *   reports), N m.  W = sim_dt * sum tau_s * qd_s, qd_s = the motor-convention joint rate after sub-step s: with the semi-implicit
+ *   integrator sim_dt * qd_s is the sub-step's change of the angle, so W is the discrete mechanical work in J.  All from 0, float32, in
+ *   sub-step order; sum tau^2 and W by fused multiply-adds.
+ * act_ep_dev float[N][4] = {sum over the episode's steps and the 12 motors of W,  the same of sum tau^2,
+ *   the largest |tau| of the episode,  the number of env steps in which some motor's peak equalled its limit};
+ *   overwritten by the step whose EP_STEP before it is 0, added to otherwise (orr_step only).
+ * act_log_dev float[ep_log_capacity][4] or NULL: the ending episode's act_ep row, next to term_log / contact_log.
+ * act_dev == NULL unbinds everything.  16-byte alignment required (one 16-byte store per motor lane).
+ * While a robot type has a finite limit or the outputs are bound, orr_step and orr_debug_replay_step launch the actuator variants of the
+ * step kernel (one wave per SIMD at any batch size; supersets of the task-noise, reward-terms and - orr_step - contact variants, which
+ * serve orr_bind_reward_terms and orr_bind_contact_outputs where those are bound as well) and the resets the task-noise variant.  With
+ * neither the handle launches exactly the kernels it launched before.  orr_debug_physics takes its torques as given: it applies no limit
+ * and leaves these buffers alone.  Refused, nothing changed: a null handle, act_dev without act_ep_dev, a misaligned buffer, a robot
+ * type with friction anchors (a launch refuses the combination too, and launches nothing, when such a model is set afterwards). */
+int32_t orr_bind_actuator_outputs(orr_handle* h, float* act_dev, float* act_ep_dev, float* act_log_dev);
+
 /* replaces WrapperEnv.reset (wrapper_env.py:87-107): mask_dev NULL = all robots; obs_dev [N,160]
  * (rows of robots that are not reset are left untouched). */
 int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream);

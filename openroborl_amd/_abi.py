@@ -41,6 +41,13 @@ REWARD_TERM_NAMES = ("pose", "velocity", "end_effector", "root_pose", "root_velo
 CONTACT_OUT_DIM = 16
 CONTACT_EP_DIM = 8
 CONTACT_COLUMNS = ("normal", "friction_x", "friction_y", "normal_max")
+# orr_set_torque_limits: int32_t (orr_handle*, int32_t robot_type, const float* limits_host [12] | NULL); +inf = no limit
+# orr_bind_actuator_outputs: int32_t (orr_handle*, float* act_dev [N][12][4], float* act_ep_dev [N][4], float* act_log_dev [ep_log_capacity][4] | NULL);
+# act_dev row [motor] = ACTUATOR_COLUMNS, act_ep_dev row = ACTUATOR_EP_COLUMNS
+ACTUATOR_OUT_DIM = 4
+ACTUATOR_EP_DIM = 4
+ACTUATOR_COLUMNS = ("torque_sum", "torque_peak", "torque_sq_sum", "work")
+ACTUATOR_EP_COLUMNS = ("work", "torque_sq_sum", "torque_peak", "saturated_steps")
 
 
 class OrrConfig(C.Structure):

@@ -122,12 +122,21 @@ struct DevTables {
   float* contact_out;                                 // [N][16] per leg: sums of the launch's normal / friction x / friction y impulses, largest normal impulse; NULL = not bound
   float* contact_ep;                                  // [N][8] per leg: stance steps and sum of the normal sums over the robot's current episode
   float* contact_log;                                 // [ep_log_capacity][8] contact_ep row of each logged episode (row = episode-log slot), or NULL
+  // motor torque limits and actuator outputs (orr_set_torque_limits, orr_bind_actuator_outputs), read by the actuator variants only
+  // (orr_kernels_actuator.hip).  APPENDED likewise
+  float* act_out;                                     // [N][12][4] per motor: sum tau, max |tau|, sum tau^2, work over the launch's sub-steps; NULL = not bound
+  float* act_ep;                                      // [N][4] work, sum tau^2, largest |tau|, saturated steps over the robot's current episode
+  float* act_log;                                     // [ep_log_capacity][4] act_ep row of each logged episode (row = episode-log slot), or NULL
+  float torque_limit[ORR_MAX_ROBOT_TYPES][12];        // per motor, N m, on the strength-scaled PD torque; +inf = none (orr_create fills the table with it)
 };
 // Flag bit of orr_step_kernel's MODE: the variant that also writes the reward terms.  MODE & 3 is the mode proper (0 env step, 1 debug
 // physics, 2 parity replay).  A bit of MODE rather than a template parameter of its own: the older variants keep their mangled names
 constexpr int kModeTerms = 4;
 // Likewise: the variant that also sums the sub-steps' foot contact impulses (orr_bind_contact_outputs).  Env step and debug physics only
 constexpr int kModeContacts = 8;
+// Likewise: the variant that clips the sub-steps' motor torques to the type's limits and keeps per-motor torque / work accumulators
+// (orr_set_torque_limits, orr_bind_actuator_outputs).  Env step and parity replay only: orr_debug_physics takes its torques as given
+constexpr int kModeActuator = 16;
 static_assert(sizeof(orr_task_noise) == 32, "the noise variants read it as eight words");
 
 // Replay inputs of the parity entry points orr_debug_replay_reset / orr_debug_replay_step (kernel MODE 2): the scripted states,
@@ -276,6 +285,15 @@ __device__ __forceinline__ float row_sum16(float x) {
   x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, true));   // quad_perm:[2,3,0,1]
   x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xF, 0xF, true));  // row_half_mirror
   x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xF, 0xF, true));  // row_mirror
+  return x;
+}
+
+// largest x over the 16 lanes of this robot, in every lane: the same four steps
+__device__ __forceinline__ float row_max16(float x) {
+  x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true)));   // quad_perm:[1,0,3,2]
+  x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, true)));   // quad_perm:[2,3,0,1]
+  x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xF, 0xF, true)));  // row_half_mirror
+  x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xF, 0xF, true)));  // row_mirror
   return x;
 }
 

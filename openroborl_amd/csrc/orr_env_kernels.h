@@ -1,12 +1,14 @@
 // orr_env_kernels.h -- the two env kernels (orr_reset_kernel, orr_step_kernel) and their launchers, as templates.
 //
-// Included by the seven translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
+// Included by the eight translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
 // several: DESIGN.md section 3).  orr_kernels.hip: the default kernels + the C-ABI, instruction-level-parallelism scheduler (one wave per
 // SIMD, ~300 registers, nothing to hide latency but the wave's own independent instructions).  orr_kernels_w2.hip: the
 // two-waves-per-SIMD step kernel, its own flags.  orr_kernels_anchor.hip: the friction-anchor variants.  orr_kernels_multiclip.hip:
 // the clip-set variants.  orr_kernels_noise.hip: the task-noise variants (clip sets + perturbed initial states + target-heading noise).
 // orr_kernels_terms.hip: the noise variant of the step that also writes the per-term reward outputs (orr_bind_reward_terms).
 // orr_kernels_contacts.hip: the variants that also sum the sub-steps' foot contact impulses (orr_bind_contact_outputs).
+// orr_kernels_actuator.hip: the variants that clip the motor torques and keep per-motor torque / work accumulators (orr_set_torque_limits,
+// orr_bind_actuator_outputs).
 // An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
 // per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
 // template` only (bottom of this file).
@@ -159,6 +161,14 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
 // keep a running sum and a running maximum in registers: one LDS read, an add and a max per sub-step, nothing inside physics_substep.
 // The row of the episode's totals is loaded with the reference frames, the stores come at the step's end, the log row goes where
 // term_log's goes (orr_bind_contact_outputs)
+// ACT = MODE & kModeActuator (orr_kernels_actuator.hip; the env step on top of CLIPS, NOISE, TERMS and CONTACTS and the parity replay on top
+// of CLIPS, NOISE and TERMS - supersets: the loads and stores of the reward-terms and contact buffers are skipped where that binding's
+// pointer is null - one wave per SIMD whatever the batch size): lane = motor clamps the sub-step's strength-scaled PD torque to +-the
+// limit of its motor (DevTables::torque_limit, +inf = none: a select, so that the torque's bits pass) and keeps, in registers over the
+// sub-steps, sum tau, max |tau|, sum tau^2 and sum tau qd of the motor-convention torque and the joint rate after the sub-step; the
+// sub-step's torque stays in a register across physics_substep.  Nothing inside physics_substep.  The row of the episode's totals is
+// loaded with the reference frames, the stores come at the step's end (one 16-byte store per motor lane), the log row goes where
+// term_log's goes (orr_set_torque_limits, orr_bind_actuator_outputs)
 template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false, bool NOISE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
@@ -166,6 +176,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   static_assert(!TERMS || (MODE & 3) != 1, "the debug physics computes no reward");
   constexpr bool CONTACTS = (MODE & kModeContacts) != 0;
   static_assert(!CONTACTS || (MODE & 3) != 2, "the parity replay replaces the physics by recorded states: it has no impulses");
+  constexpr bool ACT = (MODE & kModeActuator) != 0;
+  static_assert(!ACT || (MODE & 3) != 1, "the debug physics takes its torques as given");
+  static_assert(!ACT || TERMS, "the actuator variants are supersets: instantiated with the reward terms only");
   ORR_PROLOGUE();
   const bool valid = in_range;
   const orr_config& c = P.cfg;
@@ -175,6 +188,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   // read here, far ahead of its only use (the time limit of an episode that starts in this launch)
   const long long total_snapshot = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
   load_robot(P, rec, S, lane);
+  // ACT: which of the three bindings this superset serves (wave-uniform); the other variants are instantiated for what is bound
+  bool terms_bound = true, contacts_bound = true, act_bound = false;
+  if constexpr (ACT) {
+    terms_bound = P.tab->terms != nullptr;
+    contacts_bound = P.tab->contact_out != nullptr;
+    act_bound = P.tab->act_out != nullptr;
+  }
   // CLIPS: the motion time of the next clip change (behind the ring, never staged): read at the start, first used after the sub-steps
   float clip_change = 0.0f;
   if constexpr (CLIPS) clip_change = rec[O(CLIP_CHANGE_TIME)];
@@ -231,7 +251,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   };
   auto store_contacts = [&]() __attribute__((always_inline)) {           // row [leg][sum n, sum t1, sum t2, max n]: the normal lanes store two words
     if constexpr (CONTACTS) {
-      if (valid && lane < 12) {
+      if (valid && lane < 12 && contacts_bound) {
         const int cleg = lane / 3, cd = lane - 3 * cleg;
         gcontact const row = (gcontact)P.tab->contact_out + (size_t)robot * 16 + 4 * cleg;
         row[cd] = c_sum;
@@ -273,6 +293,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   const int mj = mc->joint_of_motor[ml];
   const float m_off = mc->motor_offset[ml], m_dir = mc->motor_dir[ml], m_kp = mc->kp[ml], m_kd = mc->kd[ml];
   const float m_tsign = mc->tau_sign_motor[ml], m_init = mc->init_motor_angles[ml];
+  // ACT: the torque limit of the lane's motor, and the launch's accumulators of its motor-convention torque (a_tau: the sub-step's)
+  typedef float __attribute__((address_space(1)))* gact;
+  float a_lim = INFINITY, a_tau = 0.0f, a_s1 = 0.0f, a_pk = 0.0f, a_s2 = 0.0f, a_w = 0.0f;
+  if constexpr (ACT) a_lim = ((const float __attribute__((address_space(1)))*)&P.tab->torque_limit[geti(S, O(ROBOT_TYPE))][0])[ml];
   // ---- set_act (minitaur.py:280-285): offset, last action, Butterworth filter ----
   ctrl_obs(P, rec, S, lane);
   // Non-finite guard, action half: the +-0.2 rad clip of the motor command (fmin / fmax) would silently DROP a NaN action while the
@@ -352,7 +376,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       float cmd = prev + lerp * (m_target - prev);
       cmd = fminf(fmaxf(cmd, cur - c.max_angle_change), cur + c.max_angle_change);  // _clip_motor_commands (:706-723)
       // MotorModel.convert_to_torque, POSITION mode (minitaur_motor.py:163-171); pd latency 0 (:359-363): the carried angle and rate
-      S.tau[lane < 12 ? mj : lane] = m_gain * (-1.0f * (m_kp * (qm_c - cmd)) - m_kd * qdm_c);
+      float tq = m_gain * (-1.0f * (m_kp * (qm_c - cmd)) - m_kd * qdm_c);
+      if constexpr (ACT) {   // strength first, then the clip (minitaur_motor.py:165-171; |m_tsign| = 1); selects: without a limit the bits pass
+        tq = tq > a_lim ? a_lim : (tq < -a_lim ? -a_lim : tq);
+        a_tau = tq * m_tsign;
+        a_s1 += a_tau;
+        a_pk = fmaxf(a_pk, fabsf(a_tau));
+        a_s2 = fmaf(a_tau, a_tau, a_s2);
+      }
+      S.tau[lane < 12 ? mj : lane] = tq;
     }
     WSYNC();
     action_counter++;  // robot_step bookkeeping (minitaur.py:287-293); written back after the loop
@@ -372,6 +404,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       accumulate_contacts();
       qm_c = (S.s[O(Q) + mj] - m_off) * m_dir;
       qdm_c = S.s[O(QD) + mj] * m_dir;
+      if constexpr (ACT) a_w = fmaf(a_tau, qdm_c, a_w);   // sim_dt qd = the sub-step's change of the angle: the work, scaled after the loop
       ring_push_and_ctrl_obs(rec, S, lane, valid, F, ring, qm_c, &co_own);
     }
     PT(10);
@@ -451,12 +484,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   typedef float __attribute__((address_space(1)))* gterm;
   float term = 0.0f, term_sum = 0.0f;
   if constexpr (TERMS) {
-    if (lane < 5) term_sum = ((gterm)P.tab->term_sums)[(size_t)robot * 5 + lane];
+    if (lane < 5 && terms_bound) term_sum = ((gterm)P.tab->term_sums)[(size_t)robot * 5 + lane];
   }
   // CONTACTS: lanes 0..7 own the robot's row of episode totals ([leg][stance steps, sum of the normal sums]); loaded here likewise
   float c_ep = 0.0f;
   if constexpr (CONTACTS) {
-    if (lane < 8) c_ep = ((gcontact)P.tab->contact_ep)[(size_t)robot * 8 + lane];
+    if (lane < 8 && contacts_bound) c_ep = ((gcontact)P.tab->contact_ep)[(size_t)robot * 8 + lane];
+  }
+  // ACT: lanes 0..3 own the robot's row of episode totals (work, sum tau^2, largest |tau|, saturated steps); loaded here likewise.  Env step only
+  float a_ep = 0.0f;
+  if constexpr (ACT && (MODE & 3) == 0) {
+    if (lane < 4 && act_bound) a_ep = ((gact)P.tab->act_ep)[(size_t)robot * 4 + lane];
   }
   float rew;
   if constexpr (TERMS) {
@@ -532,6 +570,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       const float add = nsum > 0.0f ? ((lane & 1) ? nsum : 1.0f) : 0.0f;
       c_ep = (ep_step == 1 ? 0.0f : c_ep) + add;
     }
+    if constexpr (ACT) {   // likewise; a non-finite step counts as zeros.  The twelve motors' totals by row reductions, lanes 12..15 (motor 0 again) as 0
+      a_w *= c.sim_dt;
+      if (reason & ORR_DONE_NAN) a_s1 = a_pk = a_s2 = a_w = 0.0f;
+      if constexpr ((MODE & 3) == 0) {
+        const bool motor = lane < 12;
+        const float w_all = row_sum16(motor ? a_w : 0.0f), s2_all = row_sum16(motor ? a_s2 : 0.0f), pk_all = row_max16(motor ? a_pk : 0.0f);
+        const float sat_all = row_max16(motor && !(reason & ORR_DONE_NAN) && a_pk == a_lim ? 1.0f : 0.0f);
+        const float old = ep_step == 1 ? 0.0f : a_ep;
+        a_ep = lane == 2 ? fmaxf(old, pk_all) : old + (lane == 0 ? w_all : (lane == 1 ? s2_all : sat_all));
+      }
+    }
     if constexpr (NOISE) noise_i = (uint32_t)ep_step;
     if (ep_step >= geti(S, O(MAX_EP_STEPS))) reason |= ORR_DONE_TIME_LIMIT;
     // episode log (imitation_runners.py:185-197): the slot comes from a returning atomic on a counter shared by the whole device (a
@@ -554,14 +603,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     done_out[robot] = reason != 0;
   }
   if constexpr (TERMS) {
-    if (valid && lane < 5) {
+    if (valid && lane < 5 && terms_bound) {
       ((gterm)P.tab->terms)[(size_t)robot * 5 + lane] = term;
       ((gterm)P.tab->term_sums)[(size_t)robot * 5 + lane] = term_sum;
     }
   }
   if constexpr (CONTACTS) {
     store_contacts();
-    if (valid && lane < 8) ((gcontact)P.tab->contact_ep)[(size_t)robot * 8 + lane] = c_ep;
+    if (valid && lane < 8 && contacts_bound) ((gcontact)P.tab->contact_ep)[(size_t)robot * 8 + lane] = c_ep;
+  }
+  if constexpr (ACT) {   // row [motor] = {sum tau, max |tau|, sum tau^2, work}: one 16-byte store per motor lane
+    if (valid && lane < 12 && act_bound) {
+      typedef f4 __attribute__((address_space(1)))* gact4;
+      ((gact4)reinterpret_cast<f4*>(P.tab->act_out))[(size_t)robot * 12 + lane] = f4{a_s1, a_pk, a_s2, a_w};
+    }
+    if constexpr ((MODE & 3) == 0) {
+      if (valid && lane < 4 && act_bound) ((gact)P.tab->act_ep)[(size_t)robot * 4 + lane] = a_ep;
+    }
   }
   PT(13);
   if (reason != 0) {
@@ -606,6 +664,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       const unsigned long long cslot = ((unsigned long long)(unsigned)__shfl((int)(slot >> 32), src) << 32) | (unsigned)__shfl((int)slot, src);
       gcontact const contact_log = (gcontact)P.tab->contact_log;
       if (valid && lane < 8 && P.ep_log && contact_log && cslot < (unsigned long long)P.ep_log_cap) contact_log[cslot * 8 + lane] = c_ep;
+    }
+    if constexpr (ACT && (MODE & 3) == 0) {   // the ending episode's actuator totals into the log row, lanes 0..3: likewise
+      const int src = sub * kLanes;
+      const unsigned long long aslot = ((unsigned long long)(unsigned)__shfl((int)(slot >> 32), src) << 32) | (unsigned)__shfl((int)slot, src);
+      gact const act_log = (gact)P.tab->act_log;
+      if (valid && lane < 4 && P.ep_log && act_log && aslot < (unsigned long long)P.ep_log_cap) act_log[aslot * 4 + lane] = a_ep;
     }
   }
   WSYNC();
@@ -813,6 +877,8 @@ extern template StepLaunch launch_step<kModeTerms | 2, 1, false, true, true>;   
 extern template StepLaunch launch_step<kModeContacts | 0, 1, false, true, true>;                // orr_kernels_contacts.hip: env step with the contact sums,
 extern template StepLaunch launch_step<kModeContacts | kModeTerms | 0, 1, false, true, true>;   //   the same with the reward terms,
 extern template StepLaunch launch_step<kModeContacts | 1, 1, false, false>;                     //   debug physics (resets: the noise unit's; no parity replay)
+extern template StepLaunch launch_step<kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>;   // orr_kernels_actuator.hip: env step with torque limits + actuator outputs,
+extern template StepLaunch launch_step<kModeActuator | kModeTerms | 2, 1, false, true, true>;                   //   its parity replay (resets: the noise unit's; no debug physics)
 
 #ifdef ORR_STAGE_DUMP
 // the stage dump: instantiated in BOTH step units (orr_kernels.hip: WPE 1, orr_kernels_w2.hip: WPE 2), which compile different forms of

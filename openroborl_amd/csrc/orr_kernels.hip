@@ -8,8 +8,8 @@
 // Specification of every stage: DESIGN.md section 4; CPU restatement: oracle/orr_oracle.c.
 // The kernels and their launchers are templates in orr_env_kernels.h.  This unit instantiates the default ones (env step, debug
 // physics, parity replay, reset) and chooses among all variants (variant_of); the two-wave, friction-anchor, clip-set, task-noise,
-// reward-terms and contact-output instantiations are compiled in units of their own (orr_kernels_w2.hip, _anchor.hip, _multiclip.hip,
-// _noise.hip, _terms.hip, _contacts.hip; why: orr_env_kernels.h).
+// reward-terms, contact-output and actuator instantiations are compiled in units of their own (orr_kernels_w2.hip, _anchor.hip,
+// _multiclip.hip, _noise.hip, _terms.hip, _contacts.hip, _actuator.hip; why: orr_env_kernels.h).
 #define ORR_TU_MAIN 1
 #include "orr_env_kernels.h"
 // <0, ORR_WAVES_PER_EU>: one wave per SIMD in the shipped build; development builds (-DORR_WAVES_PER_EU=2 with the timers of this
@@ -90,6 +90,8 @@ struct orr_handle {
   bool noise_on;              // orr_set_task_noise: a probability or a heading deviation above 0: every entry point but the debug physics runs the noise variants
   bool terms_on;              // orr_bind_reward_terms: the steps run the terms variant (orr_kernels_terms.hip), the resets the noise variant
   bool contacts_on;           // orr_bind_contact_outputs: env step and debug physics run the contact variants (orr_kernels_contacts.hip), the resets the noise variant
+  uint32_t limit_types;       // orr_set_torque_limits: bit t = robot type t has a finite torque limit on some motor
+  bool act_on;                // orr_bind_actuator_outputs.  With either, env step and parity replay run the actuator variants (orr_kernels_actuator.hip), the resets the noise variant
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -185,6 +187,10 @@ int32_t orr_create(const orr_config* cfg, orr_handle** out) {
   if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemset", e); }
   for (int t = 0; t < ORR_MAX_ROBOT_TYPES; t++) h->tab_host.clip_switch[t][0] = h->tab_host.clip_switch[t][1] = INFINITY;   // no switching
   e = hipMemcpy(h->tab_dev->clip_switch, h->tab_host.clip_switch, sizeof(h->tab_host.clip_switch), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemcpy", e); }
+  for (int t = 0; t < ORR_MAX_ROBOT_TYPES; t++)
+    for (int i = 0; i < 12; i++) h->tab_host.torque_limit[t][i] = INFINITY;   // no torque limit
+  e = hipMemcpy(h->tab_dev->torque_limit, h->tab_host.torque_limit, sizeof(h->tab_host.torque_limit), hipMemcpyHostToDevice);
   if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemcpy", e); }
   hipEventCreate(&h->ev0);
   hipEventCreate(&h->ev1);
@@ -372,6 +378,47 @@ int32_t orr_bind_contact_outputs(orr_handle* h, float* contact_dev, float* conta
   return 0;
 }
 
+int32_t orr_set_torque_limits(orr_handle* h, int32_t robot_type, const float* limits_host) {
+  if (!h) return fail(-1, "orr_set_torque_limits: null handle");
+  if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_torque_limits: robot_type out of range");
+  float v[12];
+  bool finite = false;
+  for (int i = 0; i < 12; i++) {
+    v[i] = limits_host ? limits_host[i] : INFINITY;
+    if (!(v[i] >= 0.0f)) {      // NaN fails the comparison
+      char m[160];
+      snprintf(m, sizeof(m), "orr_set_torque_limits: limits_host[%d] must be a torque >= 0 or +inf (no limit)", i);
+      return fail(-1, m);
+    }
+    finite = finite || v[i] < INFINITY;
+  }
+  if (finite && h->anchor_types)
+    return fail(-1, "orr_set_torque_limits: friction anchors (orr_model::friction_anchor) and torque limits cannot be combined");
+  // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->torque_limit[robot_type][0], v, sizeof(v), hipMemcpyHostToDevice), "orr_set_torque_limits: hipMemcpy");
+  memcpy(h->tab_host.torque_limit[robot_type], v, sizeof(v));
+  if (finite) h->limit_types |= 1u << robot_type; else h->limit_types &= ~(1u << robot_type);
+  return 0;
+}
+
+int32_t orr_bind_actuator_outputs(orr_handle* h, float* act_dev, float* act_ep_dev, float* act_log_dev) {
+  if (!h) return fail(-1, "orr_bind_actuator_outputs: null handle");
+  const bool on = act_dev != nullptr;
+  if (on && !act_ep_dev) return fail(-1, "orr_bind_actuator_outputs: act_dev needs act_ep_dev (the totals of the current episode)");
+  if (on && ((((uintptr_t)act_dev | (uintptr_t)act_ep_dev | (uintptr_t)act_log_dev) & 15u) != 0))
+    return fail(-1, "orr_bind_actuator_outputs: the actuator buffers (act_dev, act_ep_dev, act_log_dev) must be 16-byte aligned (rows of 4 floats)");
+  if (on && h->anchor_types)
+    return fail(-1, "orr_bind_actuator_outputs: friction anchors (orr_model::friction_anchor) and actuator outputs cannot be combined");
+  float* p[3] = {act_dev, on ? act_ep_dev : nullptr, on ? act_log_dev : nullptr};
+  static_assert(offsetof(DevTables, act_ep) == offsetof(DevTables, act_out) + sizeof(float*) &&
+                offsetof(DevTables, act_log) == offsetof(DevTables, act_out) + 2 * sizeof(float*), "copied as three consecutive pointers");
+  // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->act_out, p, sizeof(p), hipMemcpyHostToDevice), "orr_bind_actuator_outputs: hipMemcpy");
+  h->tab_host.act_out = p[0]; h->tab_host.act_ep = p[1]; h->tab_host.act_log = p[2];
+  h->act_on = on;
+  return 0;
+}
+
 int32_t orr_set_clip_switch(orr_handle* h, int32_t robot_type, float tmin, float tmax) {
   if (!h) return fail(-1, "orr_set_clip_switch: null handle");
   if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_clip_switch: robot_type out of range");
@@ -451,14 +498,16 @@ static KParams make_params(const orr_handle* h) {
 static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1) / kRPW; }
 
 // Which instantiation of the kernels a launch runs.  `clip_types` = the feature mask that selects the clip-set variants: multiclip_types
-// for orr_step / orr_reset, switch_types for the parity replays.  The contact outputs come first (`contacts` = the entry point has a
+// for orr_step / orr_reset, switch_types for the parity replays.  Torque limits and actuator outputs come first (env step, parity replay
+// and the resets, which run the noise variant; the two step variants are supersets that serve the reward terms and - the env step - the
+// contact outputs too, whichever are bound; friction anchors are refused), then the contact outputs (`contacts` = the entry point has a
 // contact variant: not the parity replays, which have no impulses and run what they run without the binding; the env step has one with
 // and one without the reward terms, the resets run the noise variant), then the reward terms (their step variants hold the noise and the
 // clip-set code; the resets of such a handle run the noise variant), then task noise (its variants hold the clip-set code too), then
 // clip sets (both refuse friction anchors: kRefused, the message starts with the entry point's name `who`), then friction anchors, then
 // the batch size; only the env step has a two-wave and only the env step and the debug physics have an anchor instantiation, every other
 // entry point runs its default one instead.
-enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts };
+enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts, kActuator };
 static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {   // (a model with anchors set after orr_bind_contact_outputs)
   if (!(h->contacts_on && h->anchor_types)) return false;
   char m[256];
@@ -467,6 +516,15 @@ static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {
   return true;
 }
 static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who, bool contacts = true) {
+  if (h->act_on || h->limit_types) {
+    if (h->anchor_types) {   // (a model with anchors set after orr_set_torque_limits / orr_bind_actuator_outputs)
+      char m[256];
+      snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and torque limits / actuator outputs (orr_set_torque_limits, orr_bind_actuator_outputs) cannot be combined", who);
+      fail(-1, m);
+      return kRefused;
+    }
+    return kActuator;
+  }
   if (contacts && refuse_contacts_with_anchors(h, who)) return kRefused;
   if (contacts && h->contacts_on) return kContacts;
   if (h->terms_on && h->anchor_types) {   // (a model with anchors set after orr_bind_reward_terms)
@@ -498,7 +556,7 @@ int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* 
   if (!h || !h->state) return fail(-1, "orr_reset: handle not bound");
   const Variant v = variant_of(h, h->multiclip_types, "orr_reset");
   if (v == kRefused) return -1;
-  if (v == kNoise || v == kTerms || v == kContacts)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
+  if (v == kNoise || v == kTerms || v == kContacts || v == kActuator)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (task noise)");
   else if (v == kClips)   // some robot type has a clip set of more than one clip: every reset draws the episode's clip
     HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr), "orr_reset: launch (clip sets)");
@@ -515,6 +573,10 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
   HIPCHK((launch_step<0, WPE, ANCHOR, CLIPS, NOISE>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{})), msg)
   switch (variant_of(h, h->multiclip_types, "orr_step")) {
     case kRefused: return -1;
+    case kActuator:   // one wave per SIMD, any batch size; the superset that also serves the reward terms and the contact outputs where bound
+      HIPCHK((launch_step<kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev,
+                                                                                                reward_dev, done_dev, 0, ReplayArgs{})), "orr_step: launch (actuator)");
+      break;
     case kContacts:   // one wave per SIMD, any batch size; with the reward terms bound as well, the variant that writes both
       if (h->terms_on)
         HIPCHK((launch_step<kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev,
@@ -582,7 +644,10 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
   const ReplayArgs rp{traj_dev, eff_dev, fall_dev, tau_out_dev, nullptr};
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_step", false);   // no contact variant: contact_out is left alone
   if (v == kRefused) return -1;
-  if (v == kTerms)   // reward terms: the noise replay that also writes the terms
+  if (v == kActuator)   // torque limits / actuator outputs: the noise replay that clips and accumulates the torques (and writes the terms where bound)
+    HIPCHK((launch_step<kModeActuator | kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0,
+                                                                              rp)), "orr_debug_replay_step: launch (actuator)");
+  else if (v == kTerms)   // reward terms: the noise replay that also writes the terms
     HIPCHK((launch_step<kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
            "orr_debug_replay_step: launch (reward terms)");
   else if (v == kNoise)   // task noise: the noise replay (its draws from 28 on, the heading noise included, come from the Philox stream)
@@ -600,7 +665,7 @@ int32_t orr_debug_replay_reset(orr_handle* h, const float* uniforms_dev, float* 
   if (!h || !h->state || !uniforms_dev) return fail(-1, "orr_debug_replay_reset: bad argument");
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_reset", false);
   if (v == kRefused) return -1;
-  if (v == kNoise || v == kTerms)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
+  if (v == kNoise || v == kTerms || v == kActuator)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (task noise)");
   else if (v == kClips)   // a clip switch interval: the multi-clip reset (draws 0..27 from uniforms_dev, 28 on from the Philox stream)
     HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev), "orr_debug_replay_reset: launch (clip switching)");

@@ -163,6 +163,34 @@ def clip_switch_spec(clip_time_min, clip_time_max, robot_names):
     return out
 
 
+def torque_limit_spec(torque_limits, robot_names):
+    """torque_limits (MotorModel's kwarg, minitaur_motor.py:57-66: None, a float, 12 floats in motor order, or a dict of robot name to
+    either, for mixed batches) -> {robot name: float32 [12]}, +inf = no limit.  ValueError on anything the C-ABI
+    (orr_set_torque_limits) would refuse: NaN, a negative limit, a wrong length."""
+    def one(v, name):
+        if v is None:
+            return np.full(12, np.inf, dtype=np.float32)
+        if isinstance(v, (bool, np.bool_, str, dict)):
+            raise ValueError("torque_limits of %s must be None, a number or 12 numbers in motor order, not %r" % (name, v))
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("torque_limits of %s must be None, a number or 12 numbers in motor order, not %r" % (name, v))
+        if a.ndim == 0:
+            a = np.full(12, float(a))
+        if a.shape != (12,):
+            raise ValueError("torque_limits of %s must be a number or 12 numbers in motor order, got shape %s" % (name, a.shape))
+        if np.isnan(a).any() or (a < 0).any():
+            raise ValueError("torque_limits of %s must be >= 0 (0 = the motor is off, inf = no limit), got %r" % (name, v))
+        return a.astype(np.float32)
+    if isinstance(torque_limits, dict):
+        unknown = set(torque_limits) - set(robot_names)
+        if unknown:
+            raise ValueError("torque_limits names robots that are not in this batch: %s" % sorted(unknown))
+        return {name: one(torque_limits.get(name), name) for name in robot_names}
+    return {name: one(torque_limits, name) for name in robot_names}
+
+
 # ---- task noise (orr_set_task_noise; ImitationTask's perturb_init_state_prob and tar_obs_noise) ------------------------------------
 NOISE_RESET_BLOCK = 0x20000000      # Philox blocks 0x20000000 .. 0x20000008 of the episode's stream: the 36 uniforms U(k) of a reset's perturbation
 NOISE_HEADING_BLOCK = 0x30000000    # block 0x30000000 + i: the heading noise of target observation i of the episode (tar_noise_block)
@@ -257,12 +285,16 @@ class VecQuadrupedEnv(object):
                  robot=None, motion_file=None, mode=None, enable_randomizer=None, auto_reset=True, num_procs=1,
                  robot_index_offset=0, legacy_grid=False, mixed_robots=None, ep_log_capacity=65536, config_overrides=None,
                  model_overrides=None, clip_time_min=None, clip_time_max=None, perturb_init_state_prob=None, tar_obs_noise=None,
-                 init_perturb_std=None, reward_terms=False, contact_outputs=False):
+                 init_perturb_std=None, reward_terms=False, contact_outputs=False, torque_limits=None, actuator_outputs=False):
         import torch
         if not isinstance(reward_terms, (bool, np.bool_)):
             raise ValueError("reward_terms must be True or False, got %r" % (reward_terms,))
         if not isinstance(contact_outputs, (bool, np.bool_)):
             raise ValueError("contact_outputs must be True or False, got %r" % (contact_outputs,))
+        if not isinstance(actuator_outputs, (bool, np.bool_)):
+            raise ValueError("actuator_outputs must be True or False, got %r" % (actuator_outputs,))
+        # the values here, ahead of everything that needs the device; a dict's robot names below, once the batch's robots are known
+        torque_limit_spec(torque_limits, sorted(torque_limits) if isinstance(torque_limits, dict) else ["every robot"])
         self.torch = torch
         if not torch.cuda.is_available():
             raise RuntimeError("VecQuadrupedEnv needs a ROCm GPU (the HIP path has no CPU fallback)")
@@ -337,6 +369,8 @@ class VecQuadrupedEnv(object):
         if init_perturb_std is None:
             init_perturb_std = params.get("init_perturb_std")
         self.task_noise = task_noise_spec(perturb_init_state_prob, tar_obs_noise, init_perturb_std)
+        # motor torque limits (MotorModel's torque_limits): the user's data, none by default - no shipped robot table carries any
+        self.torque_limits = torque_limit_spec(torque_limits, sorted(set(self.robot_names)))
         self.robot_type = robot_type
         self.clip_id = clip_id
 
@@ -385,6 +419,10 @@ class VecQuadrupedEnv(object):
         # normal impulse, stance steps and normal sum over each robot's current episode and, next to the episode log, those of every
         # logged episode.  While bound, the steps and the debug physics run the contact variants of the kernel
         self.contact_out = self.episode_contact = self.contact_log = None
+        # actuator outputs (orr_bind_actuator_outputs): per motor the sum, the peak and the sum of squares of every step's sub-step torques
+        # and its mechanical work, work / sum of squares / peak / saturated steps over each robot's current episode and, next to the
+        # episode log, those of every logged episode.  While bound or while a type has a torque limit, the steps run the actuator variant
+        self.actuator_out = self.episode_actuator = self.actuator_log = None
         # the three outputs of a step are views into ONE device buffer [obs N x 160 f32 | reward N f32 | done N u8], so that a host-side
         # consumer (LegacyListEnv) fetches them with a single copy
         nb_obs, nb_rew = num_robot * _abi.OBS_DIM * 4, num_robot * 4
@@ -401,6 +439,10 @@ class VecQuadrupedEnv(object):
             self.bind_reward_terms(True)
         if contact_outputs:
             self.bind_contact_outputs(True)
+        if any(np.isfinite(v).any() for v in self.torque_limits.values()):
+            self.set_torque_limits(torque_limits)
+        if actuator_outputs:
+            self.bind_actuator_outputs(True)
 
     # ---- reference attribute surface -------------------------------------------------------
     @property
@@ -497,6 +539,63 @@ class VecQuadrupedEnv(object):
     def foot_peak_force(self):
         """float32 [N, 4]: each leg's largest normal force of any one sub-step of the last step, in N.  Needs contact_outputs=True."""
         return self._contact_rows()[:, :, 3] / self.cfg.sim_dt
+
+    def set_torque_limits(self, torque_limits=None):
+        """Set the motors' torque limits (orr_set_torque_limits; MotorModel's torque_limits): None = none, a float, 12 floats in motor
+        order, or a dict of robot name to either.  In N m, applied to the strength-scaled PD torque of every sub-step, read from the
+        next launch on.  It selects the kernel variant: holders of captured graphs re-capture (launch_params_generation)."""
+        spec = torque_limit_spec(torque_limits, sorted(set(self.robot_names)))
+        for name, lim in spec.items():
+            arr = (C.c_float * 12)(*[float(x) for x in lim])
+            _lib.check(self.L.orr_set_torque_limits(self.h, robots.ROBOT_TYPE_ID[name], arr), self.L)
+        self.torque_limits = spec
+        self.launch_params_generation += 1
+
+    def bind_actuator_outputs(self, on=True):
+        """Bind (allocating on first use) or unbind the actuator outputs (orr_bind_actuator_outputs): env.actuator_out [N, 12, 4] (row
+        [motor] = [sum tau, max |tau|, sum tau^2, work] over the step's sub-steps; valid after step / replay_step), env.episode_actuator
+        [N, 4] (work, sum tau^2, largest |tau|, saturated steps of the robot's current episode) and env.actuator_log [ep_log_capacity,
+        4]; all None while unbound.  It selects the kernel variant: holders of captured graphs re-capture (launch_params_generation); the
+        variant's first launch in a process loads its code object, so step once eagerly before a capture."""
+        t = self.torch
+        if on:
+            bufs = (t.zeros((self.num_robot, _abi.NUM_MOTORS, _abi.ACTUATOR_OUT_DIM), dtype=t.float32, device=self.device),
+                    t.zeros((self.num_robot, _abi.ACTUATOR_EP_DIM), dtype=t.float32, device=self.device),
+                    t.zeros((self.ep_log.shape[0], _abi.ACTUATOR_EP_DIM), dtype=t.float32, device=self.device))
+            _lib.check(self.L.orr_bind_actuator_outputs(self.h, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr()), self.L)
+            self.actuator_out, self.episode_actuator, self.actuator_log = bufs
+        else:
+            t.cuda.synchronize(self.device)      # launches in flight still write the buffers
+            _lib.check(self.L.orr_bind_actuator_outputs(self.h, None, None, None), self.L)
+            self.actuator_out = self.episode_actuator = self.actuator_log = None
+        self.launch_params_generation += 1
+
+    def _actuator_rows(self):
+        if self.actuator_out is None:
+            raise ValueError("no actuator outputs: the env was built without actuator_outputs=True")
+        return self.actuator_out
+
+    def motor_torque_mean(self):
+        """float32 [N, 12]: each motor's mean torque over the last step's sub-steps, N m.  Needs actuator_outputs=True."""
+        return self._actuator_rows()[:, :, 0] / self.cfg.action_repeat
+
+    def motor_torque_peak(self):
+        """float32 [N, 12]: each motor's largest |torque| of any one sub-step of the last step, N m.  Needs actuator_outputs=True."""
+        return self._actuator_rows()[:, :, 1]
+
+    def motor_torque_rms(self):
+        """float32 [N, 12]: each motor's root mean square torque over the last step's sub-steps, N m.  Needs actuator_outputs=True."""
+        return (self._actuator_rows()[:, :, 2] / self.cfg.action_repeat).sqrt()
+
+    def motor_work(self):
+        """float32 [N, 12]: each motor's mechanical work over the last step, J (sim_dt x sum of torque x joint rate after the
+        sub-step).  Needs actuator_outputs=True."""
+        return self._actuator_rows()[:, :, 3]
+
+    def torque_saturated(self):
+        """bool [N, 12]: the motor's peak torque of the last step equalled its limit.  Needs actuator_outputs=True."""
+        lim = np.stack([self.torque_limits[self.robot_names[i % len(self.robot_names)]] for i in range(self.num_robot)])
+        return self._actuator_rows()[:, :, 1] == self.torch.from_numpy(lim).to(self.device)
 
     # ---- hot path ------------------------------------------------------------------------------
     def _stream(self):
@@ -646,6 +745,22 @@ class VecQuadrupedEnv(object):
         return {"duty": [float(x / steps) for x in sums[:, 0]],
                 "normal_force": [float(x / (steps * self.cfg.action_repeat * self.cfg.sim_dt)) for x in sums[:, 1]]}
 
+    def episode_actuator_stats(self):
+        """{"work_per_step": J, "torque_rms": N m, "torque_peak": N m, "saturated_share": share of env steps} over the episodes logged
+        since the log was last cleared, without clearing it (syncs): the work of all twelve motors per env step, the root mean square
+        torque over motors and sub-steps, the largest |torque| and the share of env steps in which some motor's peak equalled its limit;
+        {} when no episode is logged.  Read it before a gather clears the log.  Needs actuator_outputs=True."""
+        if self.actuator_log is None:
+            raise ValueError("no actuator log: the env was built without actuator_outputs=True")
+        k = int(self.torch.clamp(self.counters[_abi.CNT_EPISODES], max=self.ep_log.shape[0]).item())
+        if k == 0:
+            return {}
+        steps = float(self.ep_log[:k, 1].double().sum().item())
+        rows = self.actuator_log[:k].double().cpu().numpy()
+        return {"work_per_step": float(rows[:, 0].sum() / steps),
+                "torque_rms": float(np.sqrt(rows[:, 1].sum() / (steps * self.cfg.action_repeat * _abi.NUM_MOTORS))),
+                "torque_peak": float(rows[:, 2].max()), "saturated_share": float(rows[:, 3].sum() / steps)}
+
     def episode_log_device(self):
         """(log[K,2] snapshot, count, dropped) of the episodes finished since the last call, all on the device and
         without a host sync (count / dropped are 0-d int64 tensors; rows >= count are stale); clears the log."""
@@ -699,9 +814,15 @@ class LegacyListEnv(object):
     INIT_MOTOR_ANGLES added in place (minitaur.py:281).
     """
 
-    def __init__(self, env, mutate_actions=True):
+    def __init__(self, env, mutate_actions=True, torque_limits=None, actuator_outputs=False):
         if env.cfg.flags & _abi.FLAG_AUTO_RESET:
             raise ValueError("LegacyListEnv needs a VecQuadrupedEnv created with auto_reset=False")
+        if not isinstance(actuator_outputs, (bool, np.bool_)):
+            raise ValueError("actuator_outputs must be True or False, got %r" % (actuator_outputs,))
+        if torque_limits is not None:        # MotorModel's torque_limits / the actuator outputs, passed through to the env
+            env.set_torque_limits(torque_limits)
+        if actuator_outputs:
+            env.bind_actuator_outputs(True)
         self._env = env
         self._mutate = mutate_actions
         self.num_robot = env.num_robot

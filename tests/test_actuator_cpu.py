@@ -1,0 +1,314 @@
+"""No GPU: the host side of the motor torque limits and actuator outputs (orr_set_torque_limits, orr_bind_actuator_outputs) - the new
+translation unit compiles for gfx950 with exactly its two step kernels, the loader's tables and exports, the entry points' host-side
+refusals, the env's keywords, the Python sub-step driver that the GPU test (tests/test_gpu_actuator.py) compares with - without limits
+it is orc_step, exactly - its reductions, and that test's floor rule run with the oracle alone: float64 against the float32 parity
+build in the device's place, without limits and with 20 / 30 / 40 N m."""
+import ctypes as C
+import inspect
+import os
+import re
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+from openroborl_amd import _abi, _lib, env as envmod
+from tests import actuator_lib as al
+from tests import contact_lib as cl
+from tests import oracle_lib as ol
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENV_STEP, REPLAY = "_Z15orr_step_kernelILi28ELi1ELb0ELb1ELb1EE", "_Z15orr_step_kernelILi22ELi1ELb0ELb1ELb1EE"
+
+
+# ---- 1. the unit, the tables, the refusals ---------------------------------------------------------------------------------------------
+def test_the_actuator_unit_compiles_for_gfx950_with_its_two_kernels_no_fence_and_no_spill():
+    """orr_kernels_actuator.hip with the flags of its row: the env step with everything (MODE 16 | 8 | 4 | 0 = 28) and the parity replay
+    (MODE 16 | 4 | 2 = 22), both with CLIPS and NOISE, nothing else; no cache write-back, no spilled vector register, no scratch access
+    in the sub-step loop."""
+    from tests import test_step_kernel_no_fence as nf
+    (name, src, flags, hashed), = _lib.ACTUATOR_UNITS
+    assert name == "actuator" and not hashed and flags is _lib.HIPCC_FLAGS and src in _lib.DEPS and src == _lib.SRC_ACTUATOR
+    with tempfile.TemporaryDirectory() as d:
+        asm = nf.compile_unit(src, flags, d)
+    bodies = nf.kernel_bodies(asm)
+    assert sorted(re.match(r"(_Z15orr_step_kernelILi\d+ELi\dELb\dELb\dELb\dEE)", s).group(1) for s in bodies) == sorted([ENV_STEP, REPLAY]), sorted(bodies)
+    assert not re.search(r"^_Z16orr_reset_kernel\S*:", asm, re.M)            # the resets are the noise unit's
+    nf.assert_no_cache_writeback(bodies)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import isa_stats
+    assert "noise" in isa_stats.STEP_KERNELS[-1][1] and len(isa_stats.TERMS_STEP_KERNELS) == 1 and len(isa_stats.CONTACT_STEP_KERNELS) == 2   # the older tables stay
+    assert [s + "E" for s, _ in isa_stats.ACTUATOR_STEP_KERNELS] == [ENV_STEP] and all("actuator" in t for _, t in isa_stats.ACTUATOR_STEP_KERNELS)
+    for sym in (ENV_STEP, REPLAY):
+        res = isa_stats.resources(asm, sym)
+        assert res is not None and int(res[5]) == 0, (sym, res)          # no spilled VGPR
+        assert int(res[4]) <= 512, res                                   # one wave per SIMD
+    insts, labels = isa_stats.parse_kernel(asm.split("\n"), ENV_STEP[:-1])[:2]
+    lo, hi = isa_stats.substep_loop(insts, labels)
+    assert hi - lo > 2000 and isa_stats.scratch_accesses(insts[lo:hi + 1]) == 0
+    side = isa_stats.loop_side_blocks(insts, labels, lo, hi)
+    assert isa_stats.scratch_accesses([insts[i] for i in side]) == 0
+
+
+@pytest.mark.parametrize("defs", [["-DORR_GENERIC_PGS"], ["-DORR_PHASE_TIMERS"], ["-DORR_COUNT_DUAL_CONTACT"], ["-DORR_WAVE_TIMELINE"], ["-DORR_WAVES_PER_EU=2"]])
+def test_the_kernel_tuning_knobs_compile_in_the_actuator_unit_too(defs):
+    from tests import test_step_kernel_no_fence as nf
+    r = nf.front_end_compiles(_lib.SRC_ACTUATOR, defs)
+    assert r.returncode == 0, "%s:\n%s" % (" ".join(defs), r.stderr[-1500:])
+
+
+def test_unit_tables_exports_and_refusal_texts():
+    assert [u[0] for u in _lib.ACTUATOR_UNITS] == ["actuator"]
+    assert not [u for u in _lib.ACTUATOR_UNITS if u in _lib.ALL_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ALL_ENV_UNITS]
+    assert len(_lib.NOISE_UNITS) == 1 and len(_lib.TERMS_UNITS) == 1 and len(_lib.CONTACT_UNITS) == 1 and _lib.ALL_UNITS == _lib.UNITS + _lib.NOISE_UNITS
+    src = inspect.getsource(_lib.build)
+    assert "ALL_UNITS + TERMS_UNITS + CONTACT_UNITS" in src and "ALL_ENV_UNITS + TERMS_UNITS + CONTACT_UNITS" in src     # what existing tests look for
+    assert "ALL_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS" in src and "ALL_ENV_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS" in src
+    with open(os.path.join(ROOT, "tools", "isa_stats.py")) as f:
+        assert "_lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS" in f.read()
+    assert "orr_set_torque_limits" in _lib.EXPORTS and "orr_bind_actuator_outputs" in _lib.EXPORTS
+    with open(os.path.join(ROOT, "include", "openroborl_hip.h")) as f:
+        header = f.read()
+    declared = set(re.findall(r"\b(orr_[a-z0-9_]+)\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))
+    assert {"orr_set_torque_limits", "orr_bind_actuator_outputs"} <= declared and declared <= set(_lib.EXPORTS), declared - set(_lib.EXPORTS)
+    assert re.search(r"#define ORR_ABI_VERSION 5\b", header) and _abi.ABI_VERSION == 5          # two added entry points, no struct change
+    assert re.search(r"int32_t orr_set_torque_limits\(orr_handle\* h, int32_t robot_type, const float\* limits_host\);", header)
+    assert re.search(r"int32_t orr_bind_actuator_outputs\(orr_handle\* h, float\* act_dev, float\* act_ep_dev, float\* act_log_dev\);", header)
+    assert "orr_debug_physics takes its torques as given" in header
+    assert (_abi.ACTUATOR_OUT_DIM, _abi.ACTUATOR_EP_DIM) == (4, 4) and len(_abi.ACTUATOR_COLUMNS) == 4 and len(_abi.ACTUATOR_EP_COLUMNS) == 4
+    with open(os.path.join(_lib.CSRC, "orr_device.h")) as f:
+        device_h = f.read()
+    for text in ("constexpr int kModeTerms = 4;", "constexpr int kModeContacts = 8;", "constexpr int kModeActuator = 16;",
+                 "float torque_limit[ORR_MAX_ROBOT_TYPES][12];"):
+        assert text in device_h, text
+    with open(_lib.SRC) as f:
+        main = f.read()
+    for text in ("orr_set_torque_limits: null handle", "orr_set_torque_limits: robot_type out of range",
+                 "orr_set_torque_limits: limits_host[%d] must be a torque >= 0 or +inf (no limit)",
+                 "orr_set_torque_limits: friction anchors (orr_model::friction_anchor) and torque limits cannot be combined",
+                 "orr_bind_actuator_outputs: null handle", "orr_bind_actuator_outputs: act_dev needs act_ep_dev",
+                 "orr_bind_actuator_outputs: the actuator buffers (act_dev, act_ep_dev, act_log_dev) must be 16-byte aligned",
+                 "orr_bind_actuator_outputs: friction anchors (orr_model::friction_anchor) and actuator outputs cannot be combined",
+                 "%s: friction anchors (orr_model::friction_anchor) and torque limits / actuator outputs (orr_set_torque_limits, orr_bind_actuator_outputs) cannot be combined"):
+        assert text in main, text
+    # variant_of tests the actuator variant first
+    body = main[main.index("static Variant variant_of("):]
+    assert body.index("return kActuator;") < body.index("return kContacts;") < body.index("return kTerms;")
+    # the main unit calls the actuator variants and cannot compile them
+    with open(os.path.join(_lib.CSRC, "orr_env_kernels.h")) as f:
+        kernels_h = f.read()
+    for inst in ("launch_step<kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>", "launch_step<kModeActuator | kModeTerms | 2, 1, false, true, true>"):
+        assert "extern template StepLaunch " + inst + ";" in kernels_h, inst
+    with open(_lib.SRC_ACTUATOR) as f:
+        assert len(re.findall(r"^template orr::StepLaunch", f.read(), re.M)) == 2
+    L = _lib.load()
+    for name in _lib.EXPORTS:
+        assert hasattr(L, name), name
+    assert L.orr_bind_actuator_outputs.argtypes == [C.c_void_p] * 4 and L.orr_bind_actuator_outputs.restype is C.c_int32
+    assert L.orr_set_torque_limits.argtypes == [C.c_void_p, C.c_int32, C.POINTER(C.c_float)] and L.orr_set_torque_limits.restype is C.c_int32
+
+
+def test_a_null_handle_is_refused_by_name():
+    L = _lib.load()
+    buf = (C.c_float * 16)()
+    lim = (C.c_float * 12)(*[20.0] * 12)
+    assert L.orr_bind_actuator_outputs(None, None, None, None) == -1 and b"orr_bind_actuator_outputs: null handle" in L.orr_last_error()
+    assert L.orr_bind_actuator_outputs(None, C.addressof(buf), C.addressof(buf), None) == -1 and b"orr_bind_actuator_outputs: null handle" in L.orr_last_error()
+    assert L.orr_set_torque_limits(None, 0, lim) == -1 and b"orr_set_torque_limits: null handle" in L.orr_last_error()
+    assert L.orr_set_torque_limits(None, 0, None) == -1 and b"orr_set_torque_limits: null handle" in L.orr_last_error()
+
+
+def test_kwarg_validation():
+    sig = inspect.signature(envmod.VecQuadrupedEnv.__init__)
+    assert sig.parameters["actuator_outputs"].default is False and sig.parameters["torque_limits"].default is None
+    legacy = inspect.signature(envmod.LegacyListEnv.__init__).parameters
+    assert legacy["actuator_outputs"].default is False and legacy["torque_limits"].default is None and "contact_outputs" not in legacy
+    for name in ("set_torque_limits", "bind_actuator_outputs", "motor_torque_mean", "motor_torque_peak", "motor_torque_rms", "motor_work", "torque_saturated",
+                 "episode_actuator_stats"):
+        assert callable(getattr(envmod.VecQuadrupedEnv, name)), name
+    kw = dict(num_robot=1, robot="laikago", motion_file="laikago_pace")
+    import torch
+    if not torch.cuda.is_available():          # with a GPU the constructor goes on; tests/test_gpu_actuator.py covers that side
+        with pytest.raises(RuntimeError, match="ROCm GPU"):
+            envmod.VecQuadrupedEnv(actuator_outputs=True, torque_limits=[20.0, 30.0, 40.0] * 4, **kw)
+    # refused ahead of everything that needs the device
+    for bad in (1, 0, "yes", None, [True], 1.0):
+        with pytest.raises(ValueError, match="actuator_outputs"):
+            envmod.VecQuadrupedEnv(actuator_outputs=bad, **kw)
+    for bad in (-1.0, float("nan"), [20.0] * 11, [20.0] * 13, [[20.0] * 12], "20", True, [20.0] * 11 + [-0.5], [20.0] * 11 + [float("nan")]):
+        with pytest.raises(ValueError, match="torque_limits"):
+            envmod.VecQuadrupedEnv(torque_limits=bad, **kw)
+    # the spec: None, a float, twelve floats, a dict by robot name
+    names = ["laikago", "mini_cheetah"]
+    spec = envmod.torque_limit_spec(None, names)
+    assert sorted(spec) == names and all(np.isinf(v).all() and v.dtype == np.float32 and v.shape == (12,) for v in spec.values())
+    assert (envmod.torque_limit_spec(25, names)["mini_cheetah"] == 25.0).all() and (envmod.torque_limit_spec(0.0, names)["laikago"] == 0.0).all()
+    assert (envmod.torque_limit_spec(list(al.LEG_LIMITS), names)["laikago"] == al.LEG_LIMITS).all()
+    spec = envmod.torque_limit_spec({"laikago": 30.0}, names)
+    assert (spec["laikago"] == 30.0).all() and np.isinf(spec["mini_cheetah"]).all()
+    spec = envmod.torque_limit_spec({"laikago": [float("inf")] * 11 + [5.0], "mini_cheetah": None}, names)
+    assert spec["laikago"][11] == 5.0 and np.isinf(spec["laikago"][:11]).all() and np.isinf(spec["mini_cheetah"]).all()
+    for bad in ({"minitaur": 20.0}, {"laikago": -1.0}, {"laikago": {"a": 1}}, {"laikago": [1.0, 2.0]}):
+        with pytest.raises(ValueError, match="torque_limits"):
+            envmod.torque_limit_spec(bad, names)
+
+
+# ---- 2. the driver --------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def setup():
+    return cl.mixed_setup()
+
+
+def test_the_driver_without_limits_is_orc_step_exactly(setup):
+    """37 mixed robots, 6 steps of the shipped policies, float64: rigid state, LAMBDA and the trace's torque words (32..43) of the oracle's
+    own orc_step against the Python driver's, difference exactly 0; the float32 parity build likewise."""
+    cfg, models, clips, robot_type, clip_id = setup
+    for f32 in (False, True):
+        drv = al.SubstepDriver(cfg, models, clips, cl.N, robot_type, clip_id, f32=f32)
+        tr = cl.TracedOracle(cfg, models, clips, cl.N, robot_type, clip_id, f32=f32)
+        rng = np.random.RandomState(cl.ACTION_SEED)
+        obs = tr.orc.reset()
+        lay, seen = drv.lay, 0.0
+        for k in range(6):
+            act = cl.policy_actions(obs, robot_type, rng)
+            st, counters = tr.orc.state.astype(np.float64), tr.orc.counters.copy()
+            r = drv.step_from(st, counters, act)
+            tr.step_from(st, counters, act)
+            post = tr.orc.state
+            assert (r["rigid"] == al.rigid_of(lay, post)).all() and np.isfinite(r["rigid"]).all(), k
+            assert (r["lam"] == post[:, lay.sl("LAMBDA")]).all(), k
+            assert (r["tau"] == tr.trace[:, :, 32:44]).all(), k
+            assert (al.rigid_of(lay, r["orc"]) == al.rigid_of(lay, post)).all(), k
+            assert (r["qd"][:, -1] == (post[np.arange(cl.N)[:, None], lay.sl("QD").start + drv.jom] * drv.dir)).all()
+            seen = max(seen, float(np.abs(r["tau"]).max()))
+            obs = tr.orc.obs.astype(np.float64)
+        assert seen > 40.0                          # torques beyond the limits the other tests set
+        drv.close(); tr.close()
+
+
+def test_with_limits_the_work_is_torque_times_the_change_of_the_drivers_own_angles(setup):
+    """With 20 / 30 / 40 N m: every torque within its limit and some at it, the rigid state differs from the unlimited step's, and W =
+    sim_dt sum tau_s qd_s equals sum tau_s (q_s - q_s-1) of the driver's own motor angles to rounding: the semi-implicit integrator makes
+    sim_dt qd_s the sub-step's change of the angle.  Bound per motor: the angles are differences of numbers of size |q| <= 4, each
+    carrying the rounding of q + sim_dt qd (2^-53 |q|) and of the offset / direction map (2 x 2^-53 |q|) at both ends: sum |tau| x 8 x
+    2^-53 x max(1, |q|), plus 2^-50 sum |tau dq| for the products and the 33 adds."""
+    cfg, models, clips, robot_type, clip_id = setup
+    drv = al.SubstepDriver(cfg, models, clips, cl.N, robot_type, clip_id)
+    obs = drv.orc.reset()
+    rng = np.random.RandomState(cl.ACTION_SEED)
+    lim = al.limits_of(robot_type)
+    sim_dt = ol_dec(cfg.sim_dt)
+    at_limit, moved, worst = 0, 0.0, 0.0
+    for k in range(4):
+        act = cl.policy_actions(obs, robot_type, rng)
+        st, counters = drv.orc.state.copy(), drv.orc.counters.copy()
+        r = drv.step_from(st, counters, act, limits=lim)
+        tau, qd, qm = r["tau"], r["qd"], r["qm"]
+        assert (np.abs(tau) <= lim[:, None, :]).all()
+        at_limit += int((np.abs(tau) == lim[:, None, :]).sum())
+        moved = max(moved, float(np.abs(r["rigid"] - al.rigid_of(drv.lay, r["orc"])).max()))
+        W = al.reduce_substeps(tau, qd, sim_dt)[:, :, 3]
+        dq = qm[:, 1:] - qm[:, :-1]
+        want = (tau * dq).sum(axis=1)
+        bound = np.abs(tau).sum(axis=1) * 8 * 2.0 ** -53 * np.maximum(1.0, np.abs(qm).max(axis=1)) + 2.0 ** -50 * np.abs(tau * dq).sum(axis=1)
+        worst = max(worst, float((np.abs(W - want) / bound).max()))
+        assert (np.abs(W - want) <= bound).all(), k
+        drv.orc.state[:] = st                      # the run goes on with the oracle's own (unlimited) step
+        drv.orc.counters[:] = counters
+        obs = drv.orc.step(act)[0]
+    print("ACTUATOR work identity: largest |W - sum tau dq| / bound %.3f, %d sub-step torques at their limit, rigid state moved by up to %.3g" % (worst, at_limit, moved))
+    assert at_limit > 100 and moved > 1e-3
+    drv.close()
+
+
+def ol_dec(x):
+    return float(ol.dec32(x))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_reductions_against_plain_per_substep_loops(dtype):
+    rng = np.random.RandomState(0)
+    n, rep, steps = 3, 33, 4
+    lim = np.full((n, 12), np.inf)
+    lim[0], lim[1, 5] = al.LEG_LIMITS, 7.0
+    rows = []
+    for k in range(steps):
+        tau = np.clip(rng.normal(0.0, 25.0, (n, rep, 12)), -lim[:, None, :], lim[:, None, :]).astype(dtype)
+        if k == 2:
+            tau[1, :, 5] *= dtype(0.5)                                   # a step in which motor 5 of robot 1 stays below its limit
+        qd = rng.normal(0.0, 3.0, (n, rep, 12)).astype(dtype)
+        got = al.reduce_substeps(tau, qd, 0.001)
+        assert got.shape == (n, 12, 4) and got.dtype == dtype
+        for i in range(n):
+            for m in range(12):
+                s1, pk, s2, w = dtype(0), dtype(0), dtype(0), dtype(0)
+                for s in range(rep):
+                    t = tau[i, s, m]
+                    s1 = dtype(s1 + t)
+                    pk = max(pk, abs(t))
+                    s2 = dtype(s2 + dtype(t * t))
+                    w = dtype(w + dtype(t * qd[i, s, m]))
+                w = dtype(w * dtype(0.001))
+                assert [x.tobytes() for x in got[i, m]] == [dtype(x).tobytes() for x in (s1, pk, s2, w)], (i, m)
+        rows.append(got)
+    rows = np.stack(rows)
+    ep = al.episode_row(rows, lim)
+    assert ep.shape == (n, 4) and ep.dtype == np.float64
+    for i in range(n):
+        work = sq = top = 0.0
+        sat = 0
+        for k in range(steps):
+            hit = False
+            for m in range(12):
+                work += float(rows[k, i, m, 3]); sq += float(rows[k, i, m, 2]); top = max(top, float(rows[k, i, m, 1]))
+                hit = hit or float(rows[k, i, m, 1]) == lim[i, m]
+            sat += hit
+        assert np.allclose(ep[i], [work, sq, top, sat], rtol=1e-12, atol=0) and ep[i, 2] == top and ep[i, 3] == sat
+    assert ep[0, 3] == steps and ep[1, 3] == steps - 1 and ep[2, 3] == 0
+
+
+# ---- 3. the floor rule with the oracle alone ------------------------------------------------------------------------------------------
+def test_floor_rule_with_the_float32_oracle_in_the_devices_place(setup):
+    """The inputs of contact_lib.mixed_setup (N = 37 mixed, train mode, randomiser on, no auto-reset, seed 3, 40 steps, each robot's
+    shipped policy on the float64 oracle's observation + N(0, 0.05) from RandomState(11)).  Every step starts from the float64 oracle
+    run's record (the oracle's own, unlimited orc_step carries the run on); from it the float64 and the float32 driver each make the
+    step without limits and with 20 / 30 / 40 N m, and the float32 build stands where the device stands on the GPU.  Per column of [steps,
+    n, 12] cells: q = the 99th percentile of |f32 - f64|, cell bound 4 q + 2^-22 max(1, |ref|), at most 0.5 % of the motor steps over it.
+    Measured: see the printed lines (profiles/actuator_outputs.txt)."""
+    cfg, models, clips, robot_type, clip_id = setup
+    d64 = al.SubstepDriver(cfg, models, clips, cl.N, robot_type, clip_id)
+    d32 = al.SubstepDriver(cfg, models, clips, cl.N, robot_type, clip_id, f32=True)
+    run = cl.TracedOracle(cfg, models, clips, cl.N, robot_type, clip_id)
+    rng = np.random.RandomState(cl.ACTION_SEED)
+    obs = run.orc.reset()
+    lim = al.limits_of(robot_type)
+    sim_dt = ol_dec(cfg.sim_dt)
+    rows = {(lims, f32): [] for lims in (False, True) for f32 in (False, True)}
+    at_limit = total = 0
+    for k in range(cl.STEPS):
+        act = cl.policy_actions(obs, robot_type, rng)
+        state, counters = run.orc.state.copy(), run.orc.counters.copy()
+        for lims in (False, True):
+            for f32, drv in ((False, d64), (True, d32)):
+                r = drv.step_from(state, counters, act, limits=lim if lims else None)
+                rows[lims, f32].append(al.reduce_substeps(r["tau"], r["qd"], sim_dt).astype(np.float64))
+                if lims and not f32:
+                    at_limit += int((np.abs(r["tau"]) == lim[:, None, :]).sum())
+                    total += r["tau"].size
+        run.orc.step(act)
+        obs = run.orc.obs.copy()
+    d64.close(); d32.close(); run.close()
+    print("ACTUATOR floor rule, oracle alone: %.2f %% of the motor sub-steps at their limit" % (100.0 * at_limit / total))
+    assert at_limit > 0.01 * total
+    for lims in (False, True):
+        ref, f32 = np.stack(rows[lims, False]), np.stack(rows[lims, True])
+        assert ref.shape == (cl.STEPS, cl.N, 12, 4) and np.isfinite(ref).all()
+        if lims:
+            assert (ref[..., 1] <= lim[None]).all() and (f32[..., 1] <= lim[None]).all()
+        for c, name in enumerate(al.COLUMNS):
+            r = al.floor_rule(ref[..., c], f32[..., c], dev=f32[..., c])
+            print("ACTUATOR floor rule, oracle alone, %s, %s: %s" % ("limits 20 / 30 / 40" if lims else "no limits", name, al.describe(r)))
+            assert r["q"] > 0                                     # float32 is not exact
+            assert r["f32_share"] <= al.F32_SHARE, (lims, name)
+            assert r["dev_share"] <= al.DEVICE_SHARE

@@ -1,9 +1,15 @@
 """Step time of a variant of the step kernel against its baseline, 4096 robots, same process, alternated (train semantics):
-python tools/diag/variant_time.py --case noise|terms|contacts|anchor
+python tools/diag/variant_time.py --case noise|terms|contacts|actuator|anchor
 
   noise     the task-noise variant against the clip-set variant (a two-clip set, so that the plain env runs the clip-set variant)
   terms     reward terms on top of task noise               (two-clip set, noise on in all at one setting: prob 0.5, sigma 0.1)
   contacts  contact outputs, then reward terms as well, on top of task noise (the same set and noise); also the logged episodes' gait
+  actuator  torque limits 20 / 30 / 40 N m per leg + actuator outputs on top of contact outputs + reward terms (all three bindings on)
+            against that variant (MODE 12), the same set and noise; in between the actuator variant WITHOUT limits, which computes what
+            MODE 12 computes: the kernel's own cost apart from what the limits do to the robots (a robot that cannot hold itself up
+            falls or folds into its joint limits: an episode's end is an auto-reset inside the launch, a joint near its bound a
+            joint-limit row in the solver, off the sub-step's common path); also the episodes each env finished while timed, the
+            share of its robots with a joint-limit row at the end, and the logged episodes' actuator statistics
   anchor    the friction-anchor variant against the default kernel (the task's own clip, no noise)
 
 Every env gets 300 warm-up steps of stress actions, then 5 rounds of 300 back-to-back launches with fixed actions go round the envs in
@@ -13,9 +19,11 @@ profiles/r11_ab.txt) are not comparable with what this prints."""
 import argparse
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, '.')
+from openroborl_amd import _abi  # noqa: E402
 from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
 
 N, WARMUP, ROUNDS, LAUNCHES = 4096, 300, 5, 300
@@ -27,6 +35,10 @@ CASES = {
     "terms": (dict(TWO_CLIPS, **NOISE), (("task noise", {}), ("task noise + reward terms", dict(reward_terms=True)))),
     "contacts": (dict(TWO_CLIPS, **NOISE), (("task noise", {}), ("task noise + contact outputs", dict(contact_outputs=True)),
                                             ("task noise + contact outputs + reward terms", dict(contact_outputs=True, reward_terms=True)))),
+    "actuator": (dict(TWO_CLIPS, contact_outputs=True, reward_terms=True, **NOISE),
+                 (("task noise + contact outputs + reward terms", {}),
+                  ("the same + actuator outputs, no limits", dict(actuator_outputs=True)),
+                  ("the same + torque limits 20 / 30 / 40 + actuator outputs", dict(torque_limits=[20.0, 30.0, 40.0] * 4, actuator_outputs=True)))),
     "anchor": ({}, (("default", {}), ("friction anchors", dict(model_overrides={"laikago": {"friction_anchor": 1}})))),
 }
 
@@ -46,6 +58,7 @@ for name, kw in variants:
         obs, r, d, _ = env.step(act)
     envs.append(env); acts.append(act)
 ms = [[] for _ in variants]
+finished = [-int(env.counters[_abi.CNT_EPISODES].item()) for env in envs]
 for rnd in range(ROUNDS):                 # alternated: every variant sees the same clocks
     for j, env in enumerate(envs):
         ms[j].append(env.time_steps(acts[j], LAUNCHES) / LAUNCHES)
@@ -59,5 +72,16 @@ if case == "contacts":
     gait = envs[1].episode_gait()
     print("gait of the logged episodes (stress actions): duty %s, mean normal force [N] %s" % (
         " ".join("%.3f" % x for x in gait.get("duty", [])), " ".join("%.1f" % x for x in gait.get("normal_force", []))))
+if case == "actuator":
+    for (name, _), env, f0 in zip(variants, envs, finished):
+        m = env.models[int(env.robot_type[0])]
+        dirj, offj = np.zeros(12), np.zeros(12)
+        for mot in range(12):
+            dirj[int(m["joint_of_motor"][mot])], offj[int(m["joint_of_motor"][mot])] = m["motor_dir"][mot], m["motor_offset"][mot]
+        a = dirj * (env.field("Q").cpu().numpy().astype(np.float64) - offj)             # the kinematic angle the bounds are given for
+        room = np.minimum(a - np.asarray(m["joint_lo"]), np.asarray(m["joint_hi"]) - a) - float(env.cfg.limit_activation)
+        print("%-58s %.1f episodes ended (auto-resets) per launch while timed; %.1f %% of the robots end with a joint-limit row" % (
+            name, (f0 + int(env.counters[_abi.CNT_EPISODES].item())) / float(ROUNDS * LAUNCHES), 100.0 * (room < 0).any(axis=1).mean()))
+    print("actuator statistics of the logged episodes (stress actions): %s" % " ".join("%s %.4g" % kv for kv in sorted(envs[2].episode_actuator_stats().items())))
 for env in envs:
     env.close()

@@ -55,18 +55,20 @@ TERMS_STEP_KERNELS = (("_Z15orr_step_kernelILi4ELi1ELb0ELb1ELb1E", "step kernel 
 # the contact-output unit's (orr_kernels_contacts.hip; MODE = kModeContacts | 0 and kModeContacts | kModeTerms | 0), likewise
 CONTACT_STEP_KERNELS = (("_Z15orr_step_kernelILi8ELi1ELb0ELb1ELb1E", "step kernel with clip sets, task noise and contact outputs (one wave per SIMD)"),
                         ("_Z15orr_step_kernelILi12ELi1ELb0ELb1ELb1E", "step kernel with clip sets, task noise, reward terms and contact outputs (one wave per SIMD)"))
+# the actuator unit's (orr_kernels_actuator.hip; MODE = kModeActuator | kModeContacts | kModeTerms | 0), likewise
+ACTUATOR_STEP_KERNELS = (("_Z15orr_step_kernelILi28ELi1ELb0ELb1ELb1E", "step kernel with clip sets, task noise, reward terms, contact outputs, torque limits and actuator outputs (one wave per SIMD)"),)
 
 
 def compile_units(extra_flags=(), only_main=False, units=("env", "w2", "anchor")):
     """Device assembly of the env kernels' translation units, each with the product's flags for it (+ extra_flags): one list of lines
     per unit.  `units` = names of _lib.ALL_ENV_UNITS, compiled in the table's order; the default is the three that tools/isa_lines.py and
     tests/test_isa_budget.py address by index (0 main, 1 two-wave, 2 friction anchors), "multiclip" adds the clip-set unit, "noise" the
-    task-noise unit, "terms" (_lib.TERMS_UNITS, behind them) the reward-terms unit, "contacts" (_lib.CONTACT_UNITS, last) the
-    contact-output unit."""
+    task-noise unit, "terms" (_lib.TERMS_UNITS, behind them) the reward-terms unit, "contacts" (_lib.CONTACT_UNITS) the
+    contact-output unit, "actuator" (_lib.ACTUATOR_UNITS, last) the actuator unit."""
     src_dir = os.path.dirname(os.environ.get("ORR_ISA_SRC", _lib.SRC))      # another tree's orr_kernels.hip (A/B of code generation)
     out_dir = tempfile.mkdtemp()
     listings = []
-    for name, src, flags, _ in (_lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS)[:1 if only_main else None]:
+    for name, src, flags, _ in (_lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS)[:1 if only_main else None]:
         src = os.path.join(src_dir, os.path.basename(src))
         if name not in units or not os.path.exists(src):      # (an older tree has fewer units)
             continue
@@ -168,10 +170,10 @@ def resources(meta, sym):
 
 
 def main():
-    lines = [l for u in compile_units(sys.argv[1:], units=[u[0] for u in _lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS]) for l in u]
+    lines = [l for u in compile_units(sys.argv[1:], units=[u[0] for u in _lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS]) for l in u]
     meta = "\n".join(lines)
     # one report per variant of the step kernel (WPE 1: one wave per SIMD, WPE 2: two; see orr_env_kernels.h)
-    for sym, title in STEP_KERNELS + TERMS_STEP_KERNELS + CONTACT_STEP_KERNELS:
+    for sym, title in STEP_KERNELS + TERMS_STEP_KERNELS + CONTACT_STEP_KERNELS + ACTUATOR_STEP_KERNELS:
         k = parse_kernel(lines, sym)
         if k is None:
             continue
