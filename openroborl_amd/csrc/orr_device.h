@@ -221,15 +221,15 @@ struct alignas(16) StepEndBuf {           // live only at reset / end of step
       float frames[11][19];   // staged clip frames: 5 sample times x (f0, f1) + frame 0
       float fvel[2][18];
     };
-    // the observation being assembled shares the space of the staged frames: it is written (step end, end of reset_robot) only after
-    // the frames were blended into pose[] / vel[] (sample_poses_finish), and a reset that follows a step inside the same launch
-    // rewrites all 160 values at its end
+    // the observation being assembled shares the space of the staged frames: it is written (build_obs: once per robot, at the end of
+    // the step and behind an inline reset, or at the end of the reset kernel) only after the frames were blended into pose[] / vel[]
+    // (sample_poses_finish)
     float obs[ORR_OBS_DIM];
   };
   float pose[5][19];          // sampled reference poses (update time + 4 target times)
   float vel[18];
   float ee[2][8][3];          // end-effector world positions, [0] sim [1] ref
-  float red[80];              // small cross-lane reductions of the step-end code; reset_robot: ring entries #1 / #2 and the 28 draws
+  float red[80];              // small cross-lane reductions of the step-end code; reset_robot_state: ring entries #1 / #2 and the 28 draws
 };
 static_assert(sizeof(StepEndBuf) <= sizeof(SubstepBuf), "LDS budget: the step-end buffers fit into the sub-step buffers' space");
 union PhaseBuf {

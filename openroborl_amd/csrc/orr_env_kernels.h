@@ -43,7 +43,7 @@
 // Development aid (tools/phase_cycles.py): -DORR_PHASE_TIMERS makes lane 0 of one wave accumulate shader-clock cycles
 // per phase (Shared::pt_acc) and add them to g_phase_cycles at the end of the launch.  It implies -DORR_WAVE_TIMELINE (top of this file).
 #ifdef ORR_PHASE_TIMERS
-__device__ long long g_phase_cycles[orr::kPhaseSlots];   // 0..15: phases of the step, 16..23: stages of reset_robot, 24..: finer marks inside the reset
+__device__ long long g_phase_cycles[orr::kPhaseSlots];   // 0..15: phases of the step, 16..23: stages of reset_robot_state, 24..: finer marks inside the reset
 __device__ long long g_wave_phases[2048 * 40];   // per wave of the last launch: its own phase totals (tools/wave_phases.py)
 #define PT_INIT() do { if (threadIdx.x == 0) { for (int i_ = 0; i_ < orr::kPhaseSlots; i_++) S.pt_acc[i_] = 0; S.pt_last = clock64(); } } while (0)
 #define PT(k) do { if (threadIdx.x == 0) { const long long t_ = clock64(); S.pt_acc[k] += t_ - S.pt_last; S.pt_last = clock64(); } } while (0)
@@ -114,8 +114,11 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
   load_robot(P, rec, S, lane);
   const long long total = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
   const ResetConst RC = load_reset_const(P, S, lane);
-  reset_robot<CLIPS, NOISE>(P, rec, S, lane, valid, total, obs, RC, uniforms ? uniforms + (size_t)robot * 28 : nullptr);
+  float clip_change = 0.0f;
+  const uint32_t ep = reset_robot_state<CLIPS, NOISE>(P, S, lane, total, RC, &clip_change, uniforms ? uniforms + (size_t)robot * 28 : nullptr);
+  build_obs<NOISE>(P, rec, S, lane, obs, ep, 0u);
   WSYNC();
+  store_reset_extras<CLIPS>(rec, S, lane, valid, clip_change);
   store_robot(rec, S, lane, valid);
   // a new episode: no cached contact points (ANCHOR, ANCHOR_VALID: 28 words behind the ring).  Unconditional: friction anchors may be switched
   // on (orr_set_model) after this reset, and a caller-bound record need not have been zeroed
@@ -145,11 +148,11 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
 // AnchorState).  Same source; its own instantiations (one wave per SIMD whatever the batch size: an optional physics feature, not the
 // measured path), so that the default kernels carry nothing of it.
 // CLIPS: the multi-clip variant (orr_kernels_multiclip.hip, one wave per SIMD whatever the batch size): the auto-reset draws the new
-// episode's clip from the robot type's clip set (reset_robot<true>), the episode log also records the clip of the ending episode, and
+// episode's clip from the robot type's clip set (reset_robot_state<true>), the episode log also records the clip of the ending episode, and
 // a robot whose motion time has reached the record's CLIP_CHANGE_TIME switches to a newly drawn clip mid-episode (orr_set_clip_switch)
 // NOISE: the noise variant (orr_kernels_noise.hip; instantiated with CLIPS only - a superset: a type without a clip set keeps its CLIP_ID -
 // and one wave per SIMD whatever the batch size): the auto-reset may start the episode on a perturbed state and every target
-// observation is expressed in a noisy heading (orr_set_task_noise; reset_robot<.., true>, target_obs<true>).  Both sit outside the
+// observation is expressed in a noisy heading (orr_set_task_noise; reset_robot_state<.., true>, target_obs<true>).  Both sit outside the
 // sub-step loop.  LAST parameter: the mangled names of the other variants keep their prefixes (tools/isa_stats.py)
 // TERMS = MODE & kModeTerms (orr_kernels_terms.hip; instantiated with CLIPS and NOISE only - a superset - and one wave per SIMD whatever the
 // batch size): lanes 0..4 of a robot also store the five unweighted terms of the step's reward, keep their running sums over the episode
@@ -412,9 +415,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   // past its sub-step loop (reward, observation, reset, store: few vector instructions between long memory waits) a wave issues ahead of its
   // partner: it costs the partner next to nothing and shortens the tail (8192 robots: -0.1 %; with -Os for this unit -0.4 %, profiles/r04_ab29_8192.log)
   if (WPE == 2) __builtin_amdgcn_s_setprio(3);
-  // the cold-table constants of an auto-reset (ResetConst), issued here, ahead of the step end's stores and atomics.  Loaded again
-  // rather than taken from the registers that hold some of them over the sub-steps (m_init is dead by now): keeping those live up to
-  // the reset moved the sub-step loop's register allocation (+10 instructions) for a launch no faster
+  // the cold-table constants of an auto-reset (ResetConst), issued here, with the step end's other loads (every store and atomic of
+  // the step comes behind the reset).  Loaded again rather than taken from the registers that hold some of them over the sub-steps
+  // (m_init is dead by now): keeping those live up to the reset moved the sub-step loop's register allocation (+10 instructions) for
+  // a launch no faster
   const ResetConst RC = load_reset_const(P, S, lane);
   if (lane == 0) {  // end of robot_step (minitaur.py:287-293)
     seti(S, O(RING_HEAD), ring.head); seti(S, O(RING_LEN), ring.len);
@@ -446,7 +450,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       // although the records keep their finite change times until their next reset
       if (set_n > 1 && sw_max < INFINITY) {
         // draws 32 + 4 s .. 34 + 4 s of the episode's stream (Philox block 8 + s, s = the env step counter before this step): the clip
-        // (as reset_robot<true> draws it), the next change, the new time offset (_sample_time_offset, :1112-1123)
+        // (as reset_robot_state<true> draws it), the next change, the new time offset (_sample_time_offset, :1112-1123)
         float u4[4];
         philox_block(c.seed, (uint32_t)geti(S, O(ROBOT_INDEX)), (uint32_t)geti(S, O(EPISODE_IDX)), 8u + (uint32_t)geti(S, O(EP_STEP)), u4);
         const uint32_t m = (uint32_t)(u4[0] * 16777216.0f);
@@ -471,12 +475,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   }
   const double step_dt = clip.sim_dt_d * c.action_repeat;
   double tl = t;
-  {  // lanes 1..4: the four target times.  Selects over the four scalars: indexing the kernel argument with the lane makes the
-     // compiler read it from memory with a vector load, whose wait also drains every store and atomic issued before it
-    const int k = lane - 1;
-    const int steps = (k & 2) ? ((k & 1) ? c.tar_frame_steps[3] : c.tar_frame_steps[2]) : ((k & 1) ? c.tar_frame_steps[1] : c.tar_frame_steps[0]);
-    if (lane >= 1 && lane <= 4) tl = t + steps * step_dt;
-  }
+  if (lane >= 1 && lane <= 4) tl = t + target_frame_steps(c, lane) * step_dt;   // lanes 1..4: the four target times
   PoseLoads PL;
   sample_poses_issue(P, S, lane, tl, PL);
   // TERMS: lanes 0..4 own the robot's row of running sums (one term each); its load is issued here, with the frame loads, and first used
@@ -537,10 +536,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   PT(12);
   // _terminal_condition (imitation_task.py:518-572) + time limit (wrapper_env.py:79) + non-finite guard
   int reason = 0;
-  // the slot is only defined where the atomic was issued (lane 0 of a robot whose episode ended) and only read there.  A frozen
-  // nondeterministic value instead of an uninitialised variable: reading it is defined behaviour in every lane, and unlike a constant
-  // it gives the compiler nothing to merge with the atomic's result (a merged value made it wait for the atomic right away)
-  unsigned long long log_slot = __builtin_nondeterministic_value(log_slot);
   uint32_t noise_i = 0u;     // NOISE: 1 + the env-step counter before this step (target_obs<true>)
   {
     const float* rp = &S.s[O(REF_POSE)];
@@ -583,10 +578,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     }
     if constexpr (NOISE) noise_i = (uint32_t)ep_step;
     if (ep_step >= geti(S, O(MAX_EP_STEPS))) reason |= ORR_DONE_TIME_LIMIT;
-    // episode log (imitation_runners.py:185-197): the slot comes from a returning atomic on a counter shared by the whole device (a
-    // round trip of several microseconds).  It is issued HERE, as soon as the end of the episode is known, and consumed after the
-    // reset: the observation, the target observation and the first stages of the reset run while it is in flight
-    if (lane == 0 && valid && reason != 0) log_slot = atomicAdd((unsigned long long*)&P.counters[ORR_CNT_EPISODES], 1ull);
     WSYNC();
     if (lane == 0) {
       seti(S, O(EP_STEP), ep_step);
@@ -594,10 +585,36 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       S.s[O(EP_RETURN)] += rew;
     }
   }
-  // observation (wrapper_env.py:109-125)
-  if (lane < 12) obs[lane] = S.s[O(IMU_HIST) + lane];
-  for (int i = lane; i < 36; i += kLanes) { obs[12 + i] = S.s[O(LASTACT_HIST) + i]; obs[48 + i] = S.s[O(MOTORANG_HIST) + i]; }
-  target_obs<NOISE>(P, rec, S, lane, obs + ORR_PROPRIO_DIM, (uint32_t)geti(S, O(EPISODE_IDX)), noise_i);
+  PT(13);
+  // ---- episode end: what the log row needs, then the inline auto-reset.  From here to the stores below NOTHING is stored and no
+  // atomic is issued: loads, stores and atomics share one in-order counter (vmcnt), so the reset's wait for its clip frames would sit
+  // out the round trip of whatever store or atomic was issued in front of it (the episode-log atomic: several microseconds) ----
+  float log_ret = 0.0f, log_len = 0.0f;
+  int log_clip = 0;     // CLIPS: the clip the ending episode played, read before the reset draws the next one
+  uint32_t obs_episode = (uint32_t)geti(S, O(EPISODE_IDX));
+  bool was_reset = false;
+  if (reason != 0) {
+    if (lane == 0) {
+      log_ret = S.s[O(EP_RETURN)]; log_len = (float)geti(S, O(EP_STEP));
+      if constexpr (CLIPS) log_clip = geti(S, O(CLIP_ID));
+      S.s[O(LAST_EP_RETURN)] = log_ret;
+      seti(S, O(LAST_EP_LEN), geti(S, O(EP_STEP)));
+    }
+    WSYNC();
+    if (c.flags & ORR_FLAG_AUTO_RESET) {
+      PT(31);
+      obs_episode = reset_robot_state<CLIPS, NOISE>(P, S, lane, total_snapshot, RC, &clip_change);
+      noise_i = 0u;
+      was_reset = true;
+      if constexpr (ANCHOR) AS = AnchorState{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};   // a new episode: no cached contact points
+    }
+  }
+  WSYNC();
+  PT(14);
+  // ---- observation (wrapper_env.py:109-125), ONCE per robot: of the step that ended, or of the episode that just began ----
+  build_obs<NOISE>(P, rec, S, lane, obs, obs_episode, noise_i);
+  PT(13);
+  // ---- every store of the step, behind every load ----
   if (valid && lane == 0) {
     reward_out[robot] = rew;
     done_out[robot] = reason != 0;
@@ -621,24 +638,47 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       if (valid && lane < 4 && act_bound) ((gact)P.tab->act_ep)[(size_t)robot * 4 + lane] = a_ep;
     }
   }
-  PT(13);
-  if (reason != 0) {
-    float log_ret = 0.0f, log_len = 0.0f;
-    int log_clip = 0;     // CLIPS: the clip the ending episode played, read before reset_robot draws the next one
+  if (was_reset) store_reset_extras<CLIPS>(rec, S, lane, valid, clip_change);   // ring entries #1 / #2 of the new episode (still in LDS)
+  store_robot(rec, S, lane, valid);
+  store_anchor();
+  if (valid) {   // the observation, in 16-byte pieces like the record (40 per robot)
+    typedef f4 __attribute__((address_space(1))) * g4ptr;
+    static_assert(ORR_OBS_DIM % 4 == 0, "16-byte pieces");
+    const g4ptr od = (g4ptr)reinterpret_cast<f4*>(obs_out + (size_t)robot * ORR_OBS_DIM);
+    const f4* os = reinterpret_cast<const f4*>(obs);
+#pragma unroll
+    for (int k = 0; k < (ORR_OBS_DIM / 4 + kLanes - 1) / kLanes; k++) { const int q = lane + k * kLanes; if (q < ORR_OBS_DIM / 4) od[q] = os[q]; }
+  }
+  PT(15);
+  PT_FLUSH();
+  // ---- the two returning atomics of the step end, back to back, and ONE wait for both ----
+  // Episode log (imitation_runners.py:185-197): lane 0 of a robot whose episode ended takes its slot from a cursor shared by the
+  // whole device - whether or not a log is bound: the cursor counts the finished episodes.
+  // Launch tally: one counter update per WAVE (the compiler's own atomic combining is switched off, see _lib.HIPCC_FLAGS: it makes the
+  // issuing lane wait for the returned value on the spot).  The tally is ONE 64-bit word (ORR_CNT_TICKET: finished episodes in the
+  // high half, robots counted in the low half), so one returning atomic both adds the wave's finished episodes and takes its ticket:
+  // there is no second word to order it against, and no fence (it cost 7 % of the launch: a write-back of the wave's ~18 KB of fresh
+  // stores, an L2 invalidate and two waits, DESIGN.md section 6).  The wave that completes the count folds the done count into the
+  // curriculum counter (wrapper_env.py:82-83) and clears the word with non-returning atomics.  The fold may land while other waves
+  // still run: every wave read its snapshot of the curriculum counter when it started, and the last ticket can only be taken once
+  // every wave of the launch has started (and taken its own).  The episode log and the records are read after the kernel boundary only.
+  // Both are issued HERE, not where the end of the episode becomes known: a returned value held across the reset moved the sub-step
+  // loop's register allocation, and an atomic in flight across the reset is waited for by the reset's first load.
+  // The values are only defined where the atomics were issued and only read there.  Frozen nondeterministic values instead of
+  // uninitialised variables: reading them is defined behaviour in every lane, and unlike a constant they give the compiler nothing to
+  // merge with an atomic's result.  The empty asm reads both in every lane: the wait for the two sits in front of it, once.
+  const unsigned long long fin_mask = __ballot(valid && lane == 0 && reason != 0), val_mask = __ballot(valid && lane == 0);
+  const unsigned long long add = ((unsigned long long)__popcll(fin_mask) << 32) | (unsigned long long)__popcll(val_mask);
+  unsigned long long log_slot = __builtin_nondeterministic_value(log_slot), ticket = __builtin_nondeterministic_value(ticket);
+  if (lane == 0 && valid && reason != 0) log_slot = atomicAdd((unsigned long long*)&P.counters[ORR_CNT_EPISODES], 1ull);
+  // (the two-wave build keeps `wtid` in scratch by now: reloading it between the two atomics would put a wait for the first in front of
+  // the second, so that build computes the lane's number afresh)
+  const int tally_lane = WPE == 2 ? (int)__lane_id() : wtid;
+  if (tally_lane == 0) ticket = atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TICKET], add);
+  asm volatile("" : "+v"(log_slot), "+v"(ticket));
+  if (reason != 0) {   // the log rows of the ended episode (the cap test and the drop counter: per slot)
     const bool logs = lane == 0 && valid;
     const unsigned long long slot = log_slot;
-    if (lane == 0) {
-      log_ret = S.s[O(EP_RETURN)]; log_len = (float)geti(S, O(EP_STEP));
-      if constexpr (CLIPS) log_clip = geti(S, O(CLIP_ID));
-      S.s[O(LAST_EP_RETURN)] = log_ret;
-      seti(S, O(LAST_EP_LEN), geti(S, O(EP_STEP)));
-    }
-    WSYNC();
-    if (c.flags & ORR_FLAG_AUTO_RESET) {
-      PT(31);
-      reset_robot<CLIPS, NOISE>(P, rec, S, lane, valid, total_snapshot, obs, RC);
-      if constexpr (ANCHOR) AS = AnchorState{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};   // a new episode: no cached contact points
-    }
     if (logs && P.ep_log) {
       if (slot < (unsigned long long)P.ep_log_cap) {
         P.ep_log[2 * slot] = log_ret;
@@ -672,34 +712,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       if (valid && lane < 4 && P.ep_log && act_log && aslot < (unsigned long long)P.ep_log_cap) act_log[aslot * 4 + lane] = a_ep;
     }
   }
-  WSYNC();
-  PT(14);
-  store_robot(rec, S, lane, valid);
-  store_anchor();
-  if (valid) {   // the observation, in 16-byte pieces like the record (40 per robot)
-    typedef f4 __attribute__((address_space(1))) * g4ptr;
-    static_assert(ORR_OBS_DIM % 4 == 0, "16-byte pieces");
-    const g4ptr od = (g4ptr)reinterpret_cast<f4*>(obs_out + (size_t)robot * ORR_OBS_DIM);
-    const f4* os = reinterpret_cast<const f4*>(obs);
-#pragma unroll
-    for (int k = 0; k < (ORR_OBS_DIM / 4 + kLanes - 1) / kLanes; k++) { const int q = lane + k * kLanes; if (q < ORR_OBS_DIM / 4) od[q] = os[q]; }
-  }
-  PT(15);
-  PT_FLUSH();
-  // One counter update per WAVE (the compiler's own atomic combining is switched off, see _lib.HIPCC_FLAGS: it makes the issuing
-  // lane wait for the returned value on the spot).  The launch tally is ONE 64-bit word (ORR_CNT_TICKET: finished episodes in the
-  // high half, robots counted in the low half), so one returning atomic both adds the wave's finished episodes and takes its ticket:
-  // there is no second word to order it against, and no fence (it cost 7 % of the launch: a write-back of the wave's ~18 KB of fresh
-  // stores, an L2 invalidate and two waits, DESIGN.md section 6).  The wave that completes the count folds the done count into the
-  // curriculum counter (wrapper_env.py:82-83) and clears the word with non-returning atomics.  The fold may land while other waves
-  // still run: every wave read its snapshot of the curriculum counter when it started, and the last ticket can only be taken once
-  // every wave of the launch has started (and taken its own).  The episode log and the records are read after the kernel boundary only.
-  // Issued HERE, not with the episode-log slot: held across the reset, the returned value moved the sub-step loop's register
-  // allocation (+6 instructions) and the launch got slower (0.1993 against 0.1976 ms).
-  const unsigned long long fin_mask = __ballot(valid && lane == 0 && reason != 0), val_mask = __ballot(valid && lane == 0);
-  if (wtid == 0) {
-    const unsigned long long add = ((unsigned long long)__popcll(fin_mask) << 32) | (unsigned long long)__popcll(val_mask);
-    const unsigned long long now = atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TICKET], add) + add;
+  if (tally_lane == 0) {
+    const unsigned long long now = ticket + add;
     if ((unsigned int)now == (unsigned int)P.cfg.num_robots) {   // the low half never carries: it counts up to num_robots
       atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TOTAL_STEP_COUNT], now >> 32);
       atomicAdd((unsigned long long*)&P.counters[ORR_CNT_TOTAL_TIMESTEPS], (unsigned long long)P.cfg.num_robots);

@@ -92,9 +92,8 @@ __device__ __forceinline__ void base_rotation(Shared& S, int lane, float rel[4],
 }
 
 // The cold-table constants of a reset, per lane: those of the lane's motor (lane = motor; lanes 12..15 repeat motor 0) and one word
-// of the initial base position (lanes 0..2; the others repeat word 0).  The step kernel issues these loads right past its sub-steps,
-// ahead of the step end's stores and atomics: reset_robot / receive_obs loading them behind those added a dependent round trip
-// (~30 k cycles) to the auto-reset's critical path.
+// of the initial base position (lanes 0..2; the others repeat word 0).  The step kernel issues these loads right past its sub-steps:
+// the reset loading them where it needs them added a dependent round trip (~30 k cycles) to the auto-reset's critical path.
 struct ResetConst {
   int j;              // joint_of_motor
   float off, dir;     // motor_offset, motor_dir
@@ -107,10 +106,12 @@ __device__ __forceinline__ ResetConst load_reset_const(const KParams& P, const S
   return ResetConst{mc->joint_of_motor[ml], mc->motor_offset[ml], mc->motor_dir[ml], mc->init_motor_angles[ml], mc->init_pos[lane < 3 ? lane : 0]};
 }
 
-// Minitaur.receive_obs + get_true_obs (minitaur.py:304-334): push the true observation.  entry: optional copy of the pushed
-// entry (20 words, LDS) for callers that build the control observation without reading the ring back (reset_robot).
-// RC: the lane's constants (load_reset_const; only the motor's joint, offset and direction are read)
-__device__ static void receive_obs(const KParams& P, float* rec, Shared& S, int lane, bool valid, const ResetConst& RC, float* entry = nullptr) {
+// Minitaur.receive_obs + get_true_obs (minitaur.py:304-334): push the true observation.  The reset's form: the pushed entry is BUILT
+// here, into `entry` (20 words, LDS), and the ring cursor advanced; the caller blends the control observation from the entries it
+// keeps (reading the ring back would be a store -> load round trip) and stores them with store_ring_entry at the END of its kernel,
+// behind every load: loads and stores share one in-order counter (vmcnt), so a load waited for behind a fresh store sits out the
+// store's whole round trip.  RC: the lane's constants (load_reset_const; only the motor's joint, offset and direction are read)
+__device__ static void receive_obs(Shared& S, int lane, const ResetConst& RC, float* entry) {
   const int head = (geti(S, O(RING_HEAD)) + 1) % ORR_RING_DEPTH, len = geti(S, O(RING_LEN));
   float rel[4], Rb[9], rate[3];
   base_rotation(S, lane, rel, Rb);
@@ -125,8 +126,7 @@ __device__ static void receive_obs(const KParams& P, float* rec, Shared& S, int 
     } else if (i < 19) {
       val = i == 16 ? rate[0] : (i == 17 ? rate[1] : rate[2]);
     }
-    if (valid) rec[O(RING) + head * ORR_RING_ENTRY + i] = val;
-    if (entry) entry[i] = val;
+    entry[i] = val;
   }
   WSYNC();
   if (lane == 0) {
@@ -134,6 +134,15 @@ __device__ static void receive_obs(const KParams& P, float* rec, Shared& S, int 
     seti(S, O(RING_LEN), len + 1 > ORR_RING_DEPTH ? ORR_RING_DEPTH : len + 1);
   }
   WSYNC();
+}
+// ring entry `head` of the record <- the 20 words that receive_obs built (LDS): lane i stores word i, lanes 0..3 also word 16 + i
+__device__ __forceinline__ void store_ring_entry(float* rec, int lane, bool valid, int head, const float* entry) {
+  static_assert(ORR_RING_ENTRY == 20 && kLanes == 16, "lane mapping of an entry's words");
+  if (valid) {
+    float* dst = rec + O(RING) + head * ORR_RING_ENTRY;
+    dst[lane] = entry[lane];
+    if (lane < 4) dst[16 + lane] = entry[16 + lane];
+  }
 }
 
 // Sub-step fast path of (receive_obs; ctrl_obs): the ring entries that the control observation after the next push will

@@ -183,11 +183,26 @@ __device__ __forceinline__ double motion_time(const KParams& P, const Shared& S)
   return t;
 }
 
+// The frame-step count of the lane's target time: lanes 1..4 get tar_frame_steps[0..3] (the other lanes get one of them and do not use
+// it).  The four counts are kernel arguments.  Indexing them with the lane makes the compiler read the kernel-argument segment with a
+// vector load - and so does a chain of selects over the four fields, which it folds back into a select of the byte offset followed by
+// that load - whose wait (loads, stores and atomics share one in-order counter) also drains every store and atomic issued before it.
+// Each count is therefore made opaque to the optimiser while it sits in its scalar register; the selects then stay register selects
+// (tests/test_step_end_isa.py).
+__device__ __forceinline__ int target_frame_steps(const orr_config& c, int lane) {
+  int i0 = 0;
+  asm("" : "+s"(i0));
+  int s0 = c.tar_frame_steps[i0], s1 = c.tar_frame_steps[i0 + 1], s2 = c.tar_frame_steps[i0 + 2], s3 = c.tar_frame_steps[i0 + 3];
+  asm("" : "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3));
+  const int k = lane - 1;
+  return (k & 2) ? ((k & 1) ? s3 : s2) : ((k & 1) ? s1 : s0);
+}
+
 // Philox blocks of the task noise (orr_set_task_noise; below 2^30: a draw index is 4 * block + word, 32 bits)
 constexpr uint32_t kNoiseResetBlock = 0x20000000u, kNoiseHeadingBlock = 0x30000000u;
 
 // build the 76-d target observation into obs76 (LDS) from S.ph.end.pose[1..4] (already origin-offset) -- imitation_task.py:254-301.
-// The control observation S.co must be current (it is after the last sub-step's ring push and after reset_robot's local blend).
+// The control observation S.co must be current (it is after the last sub-step's ring push and after reset_robot_state's local blend).
 // NOISE (the noise variants, orr_kernels_noise.hip): tar_obs_noise[0] of the reference (:273-275) - the heading the target frames are
 // expressed in gets orr_task_noise::tar_heading_std times a normal from block 0x30000000 + noise_i of the stream (robot index, episode):
 // noise_i = 0 for the observation of a reset, 1 + s for the step whose env-step counter before the step is s.  Both come from the
@@ -397,54 +412,40 @@ __device__ static void sensors_push(Shared& S, int lane, bool fill_all) {
 
 // ================================================================================================
 // reset of one robot (wrapper_env.py:87-107 -> quadruped_gym_env.py:63-104 -> minitaur.py:232-278 ->
-// imitation_task.py:166-199); SURVEY.md Appendix A.2.  Writes the 160-d observation into obs (LDS).
+// imitation_task.py:166-199); SURVEY.md Appendix A.2.
 // ================================================================================================
 // uni_replay (parity replay only, else NULL): 28 draws in [0, 1) that replace the Philox stream
 // CLIPS (the multi-clip variants, orr_kernels_multiclip.hip): the episode's clip is drawn from the robot type's clip set (DevTables::clip_set)
 // with draw 28 (Philox block 7, word 0) before anything reads the clip, and CLIP_ID / S.clip hold it from then on; the record's
-// CLIP_CHANGE_TIME (behind the ring: written here, in memory) gets the episode's first clip change, draw 29 (orr_set_clip_switch)
+// CLIP_CHANGE_TIME (behind the ring, in memory: store_reset_extras) gets the episode's first clip change, draw 29 (orr_set_clip_switch)
 // RC: the lane's cold-table constants (load_reset_const; the step kernel issues those loads right past its sub-steps)
 // NOISE (the noise variants, orr_kernels_noise.hip; always with CLIPS): perturb_init_state_prob / _apply_state_perturb of the reference
 // (:192-197, 1195-1243) - with probability orr_task_noise::perturb_init_state_prob stage 6 puts the robot on a Gaussian-perturbed copy
 // of the reference state (draw rule: include/openroborl_hip.h, orr_set_task_noise) - and the noisy heading of target_obs<true>
+// Two parts.  reset_robot_state puts the robot's LDS image on the new episode: everything but the observation.  It issues every load
+// first and STORES NOTHING - the ring entries #1 / #2 of the new episode stay in LDS (reset_entry1 / reset_entry2) and the CLIPS
+// variants' change time comes back in *clip_change; the caller stores them with store_reset_extras at the end of its kernel, with the
+// record.  build_obs then writes the observation; the step kernel calls it once for all its robots, reset or not.  -> the new episode index
+__device__ __forceinline__ float* reset_entry1(Shared& S) { return S.ph.end.red; }        // 20 words each; no step-end code past the reset
+__device__ __forceinline__ float* reset_entry2(Shared& S) { return S.ph.end.red + 56; }   // touches red[]
 template <bool CLIPS = false, bool NOISE = false>
-__device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int lane, bool valid, long long total_step_count, float* obs,
-                                   const ResetConst& RC, const float* uni_replay = nullptr) {
+__device__ static uint32_t reset_robot_state(const KParams& P, Shared& S, int lane, long long total_step_count, const ResetConst& RC,
+                                             float* clip_change, const float* uni_replay = nullptr) {
   const orr_config& c = P.cfg;
   // every reset starts a new episode = a new RNG stream (robot, episode)
   const uint32_t robot = (uint32_t)geti(S, O(ROBOT_INDEX)), ep = (uint32_t)geti(S, O(EPISODE_IDX)) + 1u;
   WSYNC();
-  if (lane == 0) seti(S, O(EPISODE_IDX), (int)ep);
-  // 1-2. default pose at the grid slot, counters, ring, filter (minitaur.py:246-268, 465-483).  The per-motor reset constants are the
-  // caller's (RC), like the initial base position
-  const int rj = RC.j;
-  const float r_q0 = RC.init + RC.off, r_p0 = RC.p0;
-  if (lane < 3) {
-    S.s[O(POS) + lane] = r_p0 + (lane < 2 ? S.s[O(GRID_OFFSET) + lane] : 0.0f);
-    S.s[O(LINVEL) + lane] = 0.0f; S.s[O(ANGVEL) + lane] = 0.0f;
-  }
-  if (lane < 4) S.s[O(QUAT) + lane] = S.m.init_quat[lane];
-  if (lane < 12) {
-    const int j = rj;
-    S.s[O(Q) + j] = r_q0;  // no direction factor (minitaur.py:481)
-    S.s[O(QD) + j] = 0.0f;
-    S.s[O(LAST_ACTION) + lane] = 0.0f; S.s[O(ACTION) + lane] = 0.0f; S.s[O(FILTER_ACTION) + lane] = 0.0f; S.s[O(LAMBDA) + lane] = 0.0f;
-    S.s[O(XHIST) + lane] = 0.0f; S.s[O(XHIST) + 12 + lane] = 0.0f; S.s[O(YHIST) + lane] = 0.0f; S.s[O(YHIST) + 12 + lane] = 0.0f;
-  }
   if (lane == 0) {
-    seti(S, O(RING_LEN), 0); seti(S, O(RING_HEAD), ORR_RING_DEPTH - 1);
-    seti(S, O(STATE_ACTION_COUNTER), 0); seti(S, O(STEP_COUNTER), 0); seti(S, O(FILTER_VALID), 0);
-    seti(S, O(EP_STEP), 0);   // DONE_REASON keeps the reason the PREVIOUS episode ended with until the next step overwrites it (env.stats())
-    S.s[O(EP_RETURN)] = 0.0f;
+    seti(S, O(EPISODE_IDX), (int)ep);
+    seti(S, O(STATE_ACTION_COUNTER), 0);    // of stage 1-2 below: the start time (motion_time) reads it
   }
-  WSYNC();
   PT(16);
   // Order of the stages below: what needs global memory is started first (the episode's draws fix the start time, hence the clip
-  // frames; the model's mass table), the stages that need nothing from memory run while those loads are in flight.
+  // frames), the stages that need nothing from memory run while those loads are in flight, then comes the ONE wait for the frames.
   // 4a. all 28 draws of the episode (0..25 randomiser, 26 ref-state-init, 27 time offset) = 7 Philox blocks: lane b < 7 evaluates
   // block b once and parks its four numbers in LDS
   float* draws = S.ph.end.red + 24;    // 28 words (CLIPS: 32, block 7 in red[52..55], free until ring entry #2 takes red[56..75])
-  static_assert(kLanes == 16, "reset_robot / the pose sampler assume 16 lanes per robot");
+  static_assert(kLanes == 16, "reset_robot_state / the pose sampler assume 16 lanes per robot");
   int set_id = 0, set_n = 0;
   float sw_min = 0.0f, sw_max = 0.0f;
   if constexpr (CLIPS) {   // the type's clip set, one id per lane, and switch interval, in flight while the Philox blocks are evaluated
@@ -520,20 +521,38 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
   const double t = motion_time(P, S);
   const double step_dt = S.clip.sim_dt_d * c.action_repeat;
   double tl = t;
-  {  // lanes 1..4: the four target times.  Selects over the four scalars: indexing the kernel argument with the lane makes the
-     // compiler read it from memory with a vector load, whose wait also drains every store and atomic issued before it
-    const int k = lane - 1;
-    const int steps = (k & 2) ? ((k & 1) ? c.tar_frame_steps[3] : c.tar_frame_steps[2]) : ((k & 1) ? c.tar_frame_steps[1] : c.tar_frame_steps[0]);
-    if (lane >= 1 && lane <= 4) tl = t + steps * step_dt;
-  }
+  if (lane >= 1 && lane <= 4) tl = t + target_frame_steps(c, lane) * step_dt;   // lanes 1..4: the four target times
   PT(20);
   PoseLoads PL;
   sample_poses_issue(P, S, lane, tl, PL, 26);     // uses red[0..9] until it returns
   PT(19);
+  // 1-2. default pose at the grid slot, counters, ring, filter (minitaur.py:246-268, 465-483).  The per-motor reset constants are the
+  // caller's (RC), like the initial base position
+  const int rj = RC.j;
+  const float r_q0 = RC.init + RC.off, r_p0 = RC.p0;
+  if (lane < 3) {
+    S.s[O(POS) + lane] = r_p0 + (lane < 2 ? S.s[O(GRID_OFFSET) + lane] : 0.0f);
+    S.s[O(LINVEL) + lane] = 0.0f; S.s[O(ANGVEL) + lane] = 0.0f;
+  }
+  if (lane < 4) S.s[O(QUAT) + lane] = S.m.init_quat[lane];
+  if (lane < 12) {
+    const int j = rj;
+    S.s[O(Q) + j] = r_q0;  // no direction factor (minitaur.py:481)
+    S.s[O(QD) + j] = 0.0f;
+    S.s[O(LAST_ACTION) + lane] = 0.0f; S.s[O(ACTION) + lane] = 0.0f; S.s[O(FILTER_ACTION) + lane] = 0.0f; S.s[O(LAMBDA) + lane] = 0.0f;
+    S.s[O(XHIST) + lane] = 0.0f; S.s[O(XHIST) + 12 + lane] = 0.0f; S.s[O(YHIST) + lane] = 0.0f; S.s[O(YHIST) + 12 + lane] = 0.0f;
+  }
+  if (lane == 0) {
+    seti(S, O(RING_LEN), 0); seti(S, O(RING_HEAD), ORR_RING_DEPTH - 1);
+    seti(S, O(STEP_COUNTER), 0); seti(S, O(FILTER_VALID), 0);     // (STATE_ACTION_COUNTER: at the top)
+    seti(S, O(EP_STEP), 0);   // DONE_REASON keeps the reason the PREVIOUS episode ended with until the next step overwrites it (env.stats())
+    S.s[O(EP_RETURN)] = 0.0f;
+  }
+  WSYNC();
   // ring entries #1 and #2 of the new episode are kept (LDS) so that the control observations of the reset are blended from them
-  // directly: reading the ring back would be a store -> load round trip through memory each time
-  float* e1 = S.ph.end.red;            // 20 words each
-  receive_obs(P, rec, S, lane, valid, RC, e1);  // ring entry #1
+  // directly, and stored by the caller at the end of its kernel (ring slots 0 and 1: the ring restarts behind its last slot)
+  float* e1 = reset_entry1(S);
+  receive_obs(S, lane, RC, e1);  // ring entry #1
   // 3. sensor histories <- 3 copies of the current readings (minitaur.py:270-271; sensor_wrappers.py:122-129)
   PT(17);
   WSYNC();
@@ -558,7 +577,7 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
     WSYNC();   // the new mass / inertia ratios take effect in the next launch's load_leg_const (no staged mass table any more)
   }
   PT(25);
-  // 5b. the reference poses of the start time
+  // 5b. the reference poses of the start time: the wait for the frames, with no store or atomic of this wave in front of it
   sample_poses_finish(P, S, lane, tl, true, PL, 26);
   PT(21);
   if (lane == 0) {
@@ -570,8 +589,8 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
     const float dh = qheading(&S.s[O(QUAT)]) - qheading(&S.ph.end.pose[0][3]);
     q_about_z(dh, &S.s[O(ORIGIN_ROT)]);
     S.s[O(PREV_PHASE)] = clip_phase(clip, t);
-    if constexpr (CLIPS) { if (valid) rec[O(CLIP_CHANGE_TIME)] = clip_change_time(t, sw_min, sw_max, u_change); }
   }
+  if constexpr (CLIPS) *clip_change = clip_change_time(t, sw_min, sw_max, u_change);   // the record's CLIP_CHANGE_TIME: store_reset_extras
   WSYNC();
   apply_origin(S, lane, 5);
   for (int i = lane; i < 19; i += kLanes) S.s[O(REF_POSE) + i] = S.ph.end.pose[0][i];
@@ -609,8 +628,8 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
   }
   WSYNC();
   PT(22);
-  float* e2 = S.ph.end.red + 56;         // ring entry #2; entry #1 was saved in registers below before red[] was reused
-  receive_obs(P, rec, S, lane, valid, RC, e2);  // ring entry #2 (imitation_task.py:792)
+  float* e2 = reset_entry2(S);
+  receive_obs(S, lane, RC, e2);  // ring entry #2 (imitation_task.py:792)
   {
     // control observation with two entries in the ring (Minitaur._get_delay_obs, minitaur.py:336-357): latency <= 0 -> newest;
     // int(latency / dt) + 1 >= 2 -> the OLDEST entry (#1, the default pose: SURVEY 8a quirk 3); else blend newest / #1
@@ -624,11 +643,25 @@ __device__ static void reset_robot(const KParams& P, float* rec, Shared& S, int 
     }
     WSYNC();
   }
-  // 7. observation = histories from step 3 + target observation (quadruped_gym_env.py:100-102; wrapper_env.py:101-105)
   if (lane == 0) seti(S, O(MAX_EP_STEPS), time_limit(c, total_step_count));
+  PT(23);
+  return ep;
+}
+
+// The record's words that a reset writes outside the state head: ring slots 0 and 1 (entries #1 and #2 of reset_robot_state, still in
+// LDS) and, CLIPS, the first clip change of the new episode.  Called at the end of the kernel, with the record's other stores
+template <bool CLIPS = false>
+__device__ __forceinline__ void store_reset_extras(float* rec, Shared& S, int lane, bool valid, float clip_change) {
+  store_ring_entry(rec, lane, valid, 0, reset_entry1(S));
+  store_ring_entry(rec, lane, valid, 1, reset_entry2(S));
+  if constexpr (CLIPS) { if (valid && lane == 0) rec[O(CLIP_CHANGE_TIME)] = clip_change; }
+}
+
+// 7. observation = sensor histories + target observation (quadruped_gym_env.py:100-102; wrapper_env.py:101-105, 109-125), for the
+// step that just ended and for a reset alike: `episode` / `noise_i` are the robot's own (a reset: the new episode, 0)
+template <bool NOISE = false>
+__device__ static void build_obs(const KParams& P, const float* rec, Shared& S, int lane, float* obs, uint32_t episode, uint32_t noise_i) {
   if (lane < 12) obs[lane] = S.s[O(IMU_HIST) + lane];
   for (int i = lane; i < 36; i += kLanes) { obs[12 + i] = S.s[O(LASTACT_HIST) + i]; obs[48 + i] = S.s[O(MOTORANG_HIST) + i]; }
-  PT(23);
-  target_obs<NOISE>(P, rec, S, lane, obs + ORR_PROPRIO_DIM, ep, 0u);
-  PT(30);
+  target_obs<NOISE>(P, rec, S, lane, obs + ORR_PROPRIO_DIM, episode, noise_i);
 }

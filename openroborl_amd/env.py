@@ -109,7 +109,7 @@ CLIP_DRAW = 28      # index of the clip draw in a reset's Philox stream (block 7
 
 
 def clip_draw_index(m, n):
-    """The entry of an n-clip set a reset picks (csrc/orr_task.h, reset_robot<true>): (m * n) >> 24, m = the 24-bit integer of draw
+    """The entry of an n-clip set a reset picks (csrc/orr_task.h, reset_robot_state<true>): (m * n) >> 24, m = the 24-bit integer of draw
     CLIP_DRAW (the draw in [0, 1) is m / 2^24).  Integer arithmetic; works on numpy integer arrays."""
     return (np.asarray(m, dtype=np.int64) * int(n)) >> 24
 

@@ -31,11 +31,12 @@ for n, v in zip(dev_build.PHASE_NAMES, buf[:16]):
 print("steps with a reset in the instrumented wave: %d of %d (robot resets: %s); cycles per such step in 'episode end/reset': %.0f"
       % (events, steps, dones.tolist(), buf[14] / max(events, 1)))
 print("PGS sweeps in sub-steps with the joint-limit bank (not in the table above): %.0f cycles per env step" % (buf[34] / steps))
-print("stages of reset_robot in program order, cycles per reset of robot 0 of the wave (a mark closes the interval since the previous one):")
-RESET = [(16, "state defaults"), (24, "Philox blocks (28 draws)"), (20, "task draws: start time"), (26, "frame indices (clip_index)"),
-         (19, "frame + mass-table loads issued"), (17, "ring entry #1"), (29, "control observation copy"), (18, "sensor histories"),
-         (25, "randomiser scatter + mass refresh"), (27, "frames staged to LDS"), (21, "pose blend"), (22, "origin + teleport"),
-         (23, "ring entry #2 + time limit"), (30, "target observation"), (31, "episode log + entry (before reset_robot)")]
+print("stages of reset_robot_state in program order, cycles per reset of robot 0 of the wave (a mark closes the interval since the previous one;")
+print("the observation of a reset robot is built with every other robot's, in 'termination+obs' above):")
+RESET = [(31, "episode log entry (before the reset)"), (16, "episode index"), (24, "Philox blocks (28 draws)"), (20, "task draws: start time"),
+         (26, "frame indices (clip_index)"), (19, "frame loads issued"), (17, "state defaults + ring entry #1"), (29, "control observation copy"),
+         (18, "sensor histories"), (25, "randomiser scatter"), (27, "frames staged to LDS"), (21, "pose blend"), (22, "origin + teleport"),
+         (23, "ring entry #2 + time limit")]
 tot_r = 0.0
 for k, n in RESET:
     v = buf[k] / max(int(dones[0]), 1)
