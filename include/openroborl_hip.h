@@ -306,6 +306,43 @@ typedef struct orr_task_noise {
 int32_t orr_set_task_noise(orr_handle* h, const orr_task_noise* noise_host);
 int32_t orr_sizeof_task_noise(void);
 
+/* sensor noise of the handle (Minitaur._observation_noise_stdev, minitaur.py:67,126,370-375: zero-mean Gaussian noise on every reading
+ * of the "noisy" getters get_motor_angles, get_base_rpy and get_base_rpy_rate).  One setting per handle, read from the next launch on. */
+typedef struct orr_sensor_noise {   /* Minitaur._observation_noise_stdev, in its order */
+  float motor_angle_std, motor_velocity_std, motor_torque_std, base_rpy_std, base_rpy_rate_std;
+} orr_sensor_noise;
+/* noise_host NULL = all off.  Refused: a NaN, a negative or an infinite value (the message names the field), friction anchors on the
+ * handle (a launch refuses the combination too, and launches nothing, when such a model is set afterwards); a rejected call changes
+ * nothing.  motor_velocity_std and motor_torque_std are stored for schema fidelity and have NO consumer on this path: in the reference
+ * only get_energy_consumption_per_step reads the getters they belong to.  While motor_angle_std, base_rpy_std and base_rpy_rate_std are
+ * all 0 the handle launches exactly the kernels it launches without this call; otherwise orr_step, orr_reset and the parity replays
+ * launch the sensor variants (supersets of the actuator, contact, reward-terms and task-noise variants: one wave per SIMD at any batch
+ * size).  With sa, sr, sd = the angle, rpy and rate deviations, co = the control (latency-delayed) observation and map_pi =
+ * MapToMinusPiToPi, every reading has a normal z of its own:
+ *   sub-step k of a step, motor m: cur = map_pi(co[m] + sa z) is what the +-max_angle_change clip of the motor command is centred on
+ *     (_clip_motor_commands, :706-723); while the episode has no filtered action yet (its first step) the interpolation starts from
+ *     map_pi(co[m] + sa z') with a separate draw, redrawn every sub-step (process_action, :449-456).  The PD law's own angle and rate
+ *     stay the true ones;
+ *   the Butterworth history of an episode's first step is initialised with map_pi(co[m] + sa z) (_filter, :1169-1178);
+ *   the sensor histories (robot_sensors.py:74-83,153-190): the motor-angle columns get map_pi(co[m] + sa z), roll and pitch rpy + sr z,
+ *     the two rates rate + sd z.  At a reset the three history entries are three separate readings (sensor_wrappers.py:122-129), the
+ *     first of which ends up as the oldest entry;
+ *   the target observation: pitch and yaw of the delayed rpy each get sr z before the heading is formed (get_base_orientation,
+ *     :630-638); orr_task_noise::tar_heading_std's term, if on, is added after.
+ * Draw rule, on the episode's (seed, robot index, episode) stream; every older block keeps its meaning, and in the parity replays
+ * these blocks always come from Philox, like the task-noise blocks:
+ *   block = 0x10000000 + (i << 9) + (slot << 4) + lane   (below 0x20000000 for i < 2^19)
+ *   i = 0 for a reset of that episode (the auto-reset inside a step included), 1 + s for the step whose env-step counter before it is s;
+ *   normal pairs as in orr_set_task_noise: (z0, z1) of the uniforms (word 0, word 1) and of (word 2, word 3);
+ *   slot 0..16 (steps), lane = motor m: sub-step 2 slot uses the pair (0, 1), sub-step 2 slot + 1 the pair (2, 3); z0 = the clip's
+ *     reading, z1 = the interpolation start's;
+ *   slot 17, lane = history column (0..11 motor angle, 12 roll, 13 pitch, 14 roll rate, 15 pitch rate): a step takes z0 of the pair
+ *     (0, 1); a reset z0, z1 of the pair (0, 1), then z0 of the pair (2, 3), in reading order;
+ *   slot 18, lane = motor m: z0 of the pair (0, 1), the filter history's initial value;
+ *   slot 19, lane 0: the pair (0, 1) -> roll (unused), pitch; z0 of the pair (2, 3) -> yaw: the target observation's rpy. */
+int32_t orr_set_sensor_noise(orr_handle* h, const orr_sensor_noise* noise_host);
+int32_t orr_sizeof_sensor_noise(void);
+
 /* reward terms (ImitationTask._calc_reward_pose / _velocity / _end_effector / _root_pose / _root_velocity, imitation_task.py:358-516).
  * terms_dev float[N][5] (device): every orr_step and orr_debug_replay_step writes, for every robot of the shard, the five UNWEIGHTED
  *   terms r_k = exp(-scale_k err_k) of the reward it wrote to reward_dev, in orr_config::reward_w's order: pose, velocity, end effector,

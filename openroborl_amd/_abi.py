@@ -124,6 +124,14 @@ class OrrTaskNoise(C.Structure):
                                          "root_ang_vel_std", "joint_vel_std", "tar_heading_std")]
 
 
+SENSOR_NOISE_FIELDS = ("motor_angle_std", "motor_velocity_std", "motor_torque_std", "base_rpy_std", "base_rpy_rate_std")
+
+
+class OrrSensorNoise(C.Structure):
+    """include/openroborl_hip.h: orr_sensor_noise (orr_set_sensor_noise), Minitaur._observation_noise_stdev in its order."""
+    _fields_ = [(n, C.c_float) for n in SENSOR_NOISE_FIELDS]
+
+
 def fill(struct, name, values):
     """Assign a (nested) python sequence / scalar to a ctypes struct field."""
     import numpy as np

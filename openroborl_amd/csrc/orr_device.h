@@ -128,6 +128,8 @@ struct DevTables {
   float* act_ep;                                      // [N][4] work, sum tau^2, largest |tau|, saturated steps over the robot's current episode
   float* act_log;                                     // [ep_log_capacity][4] act_ep row of each logged episode (row = episode-log slot), or NULL
   float torque_limit[ORR_MAX_ROBOT_TYPES][12];        // per motor, N m, on the strength-scaled PD torque; +inf = none (orr_create fills the table with it)
+  // sensor noise of the handle (orr_set_sensor_noise), read by the sensor variants only (orr_kernels_sensor.hip).  APPENDED likewise
+  orr_sensor_noise sensor;                            // all zero = off; motor_velocity_std / motor_torque_std have no consumer
 };
 // Flag bit of orr_step_kernel's MODE: the variant that also writes the reward terms.  MODE & 3 is the mode proper (0 env step, 1 debug
 // physics, 2 parity replay).  A bit of MODE rather than a template parameter of its own: the older variants keep their mangled names
@@ -137,6 +139,15 @@ constexpr int kModeContacts = 8;
 // Likewise: the variant that clips the sub-steps' motor torques to the type's limits and keeps per-motor torque / work accumulators
 // (orr_set_torque_limits, orr_bind_actuator_outputs).  Env step and parity replay only: orr_debug_physics takes its torques as given
 constexpr int kModeActuator = 16;
+// Likewise: the variant whose sensor readings carry Gaussian noise (orr_set_sensor_noise).  Env step and parity replay, on top of the
+// actuator variants
+constexpr int kModeSensor = 32;
+static_assert(sizeof(orr_sensor_noise) == 20, "the sensor variants read it as five words");
+// The three deviations of orr_sensor_noise that have a consumer, wave-uniform (one setting per handle): motor angle, base rpy, base rpy
+// rate.  All zero in every variant but the sensor ones, whose code for them is compiled out
+struct SensorNoise {
+  float a = 0.0f, r = 0.0f, d = 0.0f;
+};
 static_assert(sizeof(orr_task_noise) == 32, "the noise variants read it as eight words");
 
 // Replay inputs of the parity entry points orr_debug_replay_reset / orr_debug_replay_step (kernel MODE 2): the scripted states,

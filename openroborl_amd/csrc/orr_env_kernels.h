@@ -1,6 +1,6 @@
 // orr_env_kernels.h -- the two env kernels (orr_reset_kernel, orr_step_kernel) and their launchers, as templates.
 //
-// Included by the eight translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
+// Included by the nine translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
 // several: DESIGN.md section 3).  orr_kernels.hip: the default kernels + the C-ABI, instruction-level-parallelism scheduler (one wave per
 // SIMD, ~300 registers, nothing to hide latency but the wave's own independent instructions).  orr_kernels_w2.hip: the
 // two-waves-per-SIMD step kernel, its own flags.  orr_kernels_anchor.hip: the friction-anchor variants.  orr_kernels_multiclip.hip:
@@ -8,7 +8,7 @@
 // orr_kernels_terms.hip: the noise variant of the step that also writes the per-term reward outputs (orr_bind_reward_terms).
 // orr_kernels_contacts.hip: the variants that also sum the sub-steps' foot contact impulses (orr_bind_contact_outputs).
 // orr_kernels_actuator.hip: the variants that clip the motor torques and keep per-motor torque / work accumulators (orr_set_torque_limits,
-// orr_bind_actuator_outputs).
+// orr_bind_actuator_outputs).  orr_kernels_sensor.hip: the variants whose sensor readings carry Gaussian noise (orr_set_sensor_noise).
 // An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
 // per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
 // template` only (bottom of this file).
@@ -128,6 +128,29 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
     for (int i = lane; i < ORR_OBS_DIM; i += kLanes) obs_out[(size_t)robot * ORR_OBS_DIM + i] = obs[i];
 }
 
+// The reset of the sensor variants (orr_kernels_sensor.hip; orr_set_sensor_noise): orr_reset_kernel<CLIPS, true> with noisy sensor
+// histories - three separate readings - and a noisy heading of the target observation.  A kernel of its own rather than a third
+// parameter of orr_reset_kernel: the names of that kernel's instantiations stay exactly as they are
+template <bool CLIPS = true>
+__global__ __launch_bounds__(64) void orr_sensor_reset_kernel(KParams P, const uint8_t* mask, float* obs_out, const float* uniforms) {
+  ORR_PROLOGUE();
+  const bool valid = in_range && !(mask && !mask[robot]);
+  load_robot(P, rec, S, lane);
+  const long long total = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
+  const ResetConst RC = load_reset_const(P, S, lane);
+  const SensorNoise SN = load_sensor_noise(P);
+  float clip_change = 0.0f;
+  const uint32_t ep = reset_robot_state<CLIPS, true, true>(P, S, lane, total, RC, &clip_change, uniforms ? uniforms + (size_t)robot * 28 : nullptr, SN);
+  build_obs<true, true>(P, rec, S, lane, obs, ep, 0u, SN);
+  WSYNC();
+  store_reset_extras<CLIPS>(rec, S, lane, valid, clip_change);
+  store_robot(rec, S, lane, valid);
+  if (valid)      // a new episode: no cached contact points (as orr_reset_kernel)
+    for (int i = lane; i < ORR_OFFEND_ANCHOR_VALID - ORR_OFF_ANCHOR + 1; i += kLanes) rec[O(ANCHOR) + i] = 0.0f;
+  if (obs_out && valid)
+    for (int i = lane; i < ORR_OBS_DIM; i += kLanes) obs_out[(size_t)robot * ORR_OBS_DIM + i] = obs[i];
+}
+
 // mode 0: full env step.  mode 1 (debug / parity of row C): nsub physics sub-steps with the given
 // motor torques (actions = torques), no robot or task logic.  mode 2 (parity of everything BUT row C): a full env step in
 // which the physics sub-step is replaced by the recorded states of ReplayArgs, the end-effector reward reads recorded link
@@ -172,6 +195,14 @@ __global__ __launch_bounds__(64) void orr_reset_kernel(KParams P, const uint8_t*
 // sub-step's torque stays in a register across physics_substep.  Nothing inside physics_substep.  The row of the episode's totals is
 // loaded with the reference frames, the stores come at the step's end (one 16-byte store per motor lane), the log row goes where
 // term_log's goes (orr_set_torque_limits, orr_bind_actuator_outputs)
+// SENS = MODE & kModeSensor (orr_kernels_sensor.hip; on top of the two actuator variants - supersets - one wave per SIMD whatever the batch
+// size): Minitaur._observation_noise_stdev (minitaur.py:370-375).  Lane = motor: every sub-step's +-max_angle_change clip reads a noisy
+// motor angle, and so does the interpolation's start value while the episode has no filtered action yet, each with its own normal of
+// the sub-step (one Philox block per motor and two sub-steps, the second pair of words kept in registers over the odd sub-step); the PD
+// law keeps the true angle and rate.  Outside physics_substep, and skipped wave-uniformly while motor_angle_std is 0 (one setting per
+// handle).  The filter history's initial value, the sensor histories' readings and the rpy that the target observation's heading is
+// formed from are noisy too (sensors_push_noisy, target_obs<.., true>, reset_robot_state<.., true>): draw rule in
+// include/openroborl_hip.h, orr_set_sensor_noise
 template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false, bool NOISE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
@@ -182,6 +213,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   constexpr bool ACT = (MODE & kModeActuator) != 0;
   static_assert(!ACT || (MODE & 3) != 1, "the debug physics takes its torques as given");
   static_assert(!ACT || TERMS, "the actuator variants are supersets: instantiated with the reward terms only");
+  constexpr bool SENS = (MODE & kModeSensor) != 0;
+  static_assert(!SENS || (ACT && NOISE), "the sensor variants are supersets: instantiated on top of the actuator variants only");
   ORR_PROLOGUE();
   const bool valid = in_range;
   const orr_config& c = P.cfg;
@@ -300,6 +333,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   typedef float __attribute__((address_space(1)))* gact;
   float a_lim = INFINITY, a_tau = 0.0f, a_s1 = 0.0f, a_pk = 0.0f, a_s2 = 0.0f, a_w = 0.0f;
   if constexpr (ACT) a_lim = ((const float __attribute__((address_space(1)))*)&P.tab->torque_limit[geti(S, O(ROBOT_TYPE))][0])[ml];
+  // SENS: the handle's deviations (scalar), the robot's stream (robot index, episode) and the step's first block for the lane's motor
+  SensorNoise SN;
+  uint32_t sn_robot = 0u, sn_ep = 0u, sn_i = 0u;
+  if constexpr (SENS) {
+    SN = load_sensor_noise(P);
+    sn_robot = (uint32_t)geti(S, O(ROBOT_INDEX)); sn_ep = (uint32_t)geti(S, O(EPISODE_IDX)); sn_i = 1u + (uint32_t)geti(S, O(EP_STEP));
+  }
   // ---- set_act (minitaur.py:280-285): offset, last action, Butterworth filter ----
   ctrl_obs(P, rec, S, lane);
   // Non-finite guard, action half: the +-0.2 rad clip of the motor command (fmin / fmax) would silently DROP a NaN action while the
@@ -317,7 +357,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     S.s[O(LAST_ACTION) + lane] = act;
     float x1 = S.s[O(XHIST) + lane], x2 = S.s[O(XHIST) + 12 + lane], y1 = S.s[O(YHIST) + lane], y2 = S.s[O(YHIST) + 12 + lane];
     if (geti(S, O(STATE_ACTION_COUNTER)) == 0) {  // _filter (minitaur.py:1169-1178): init_history(current delayed angles)
-      const float d = map_pi(S.co[lane]);
+      float d = map_pi(S.co[lane]);
+      if constexpr (SENS) {   // get_motor_angles' reading, with a draw of its own (slot 18)
+        if (SN.a > 0.0f) {
+          float u4[4], z0, z1;
+          philox_block(c.seed, sn_robot, sn_ep, sensor_block(sn_i, kSensorSlotFilter, (uint32_t)lane), u4);
+          normal_pair(u4[0], u4[1], &z0, &z1);
+          d = map_pi(fmaf(SN.a, z0, S.co[lane]));
+        }
+      }
       x1 = x2 = y1 = y2 = d;
     }
     const float y = act * P.fb[0] + (x1 * P.fb[1] + x2 * P.fb[2]) - (y1 * P.fa[1] + y2 * P.fa[2]);  // action_filter.py:111-120
@@ -364,6 +412,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   // of the leg dynamics' first reads (base rotation / velocity, own joint angle, the leg's joint rates: 19 registers) in front of the
   // PD law (0.2208 -> 0.2223: worse).
   float co_own = S.co[ml], qm_c = (S.s[O(Q) + mj] - m_off) * m_dir, qdm_c = S.s[O(QD) + mj] * m_dir;
+  const uint32_t sn_blk = sensor_block(sn_i, 0u, (uint32_t)ml);
+  float sn_u2 = 0.0f, sn_u3 = 0.0f;    // SENS: words 2, 3 of the even sub-step's block, for the odd one
   for (int sstep = 0; sstep < c.action_repeat; sstep++) {
     // priority turns of the two-wave variant (measured: profiles/r04_ab25..30_8192.log): a wave is favoured for kPrioTurn sub-steps at a time; the turns
     // start kPrioOffset sub-steps early, i.e. the younger wave of a SIMD leads with a turn of three and has the last two sub-steps (8192 robots
@@ -374,8 +424,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     if (WPE == 2 && prio_turns) { if (sstep < kPrioEqualFrom && ((((sstep + kPrioOffset) / kPrioTurn) ^ prio_phase) & 1)) __builtin_amdgcn_s_setprio(kPrioHi); else __builtin_amdgcn_s_setprio(0); }
     {  // every lane (no divergent `if`: it would cost more than it skips); lanes 12..15 repeat motor 0 and store into dump slots
       const float lerp = (float)(sstep + 1) * inv_repeat;  // process_action (minitaur.py:438-460)
-      const float cur = map_pi(co_own);
-      const float prev = m_has_prev ? m_prev : cur;
+      float cur = map_pi(co_own), cur_lerp = cur;
+      if constexpr (SENS) {
+        if (SN.a > 0.0f) {   // wave-uniform, like the test of the sub-step's parity
+          float ua, ub, z0, z1;
+          if ((sstep & 1) == 0) {
+            float u4[4];
+            philox_block(c.seed, sn_robot, sn_ep, sn_blk + ((uint32_t)(sstep >> 1) << 4), u4);
+            ua = u4[0]; ub = u4[1]; sn_u2 = u4[2]; sn_u3 = u4[3];
+          } else {
+            ua = sn_u2; ub = sn_u3;
+          }
+          normal_pair(ua, ub, &z0, &z1);
+          cur = map_pi(fmaf(SN.a, z0, co_own));        // _clip_motor_commands' reading
+          cur_lerp = map_pi(fmaf(SN.a, z1, co_own));   // process_action's, redrawn every sub-step
+        }
+      }
+      const float prev = m_has_prev ? m_prev : cur_lerp;
       float cmd = prev + lerp * (m_target - prev);
       cmd = fminf(fmaxf(cmd, cur - c.max_angle_change), cur + c.max_angle_change);  // _clip_motor_commands (:706-723)
       // MotorModel.convert_to_torque, POSITION mode (minitaur_motor.py:163-171); pd latency 0 (:359-363): the carried angle and rate
@@ -429,7 +494,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   if (lane < 12) S.s[O(FILTER_ACTION) + lane] = m_target;
   WSYNC();
   // ---- get_obs: sensors on_step (minitaur.py:295-299) ----
-  sensors_push(S, lane, false);
+  if constexpr (SENS) sensors_push_noisy(S, lane, false, SN, c.seed, sn_ep, sn_i);
+  else sensors_push(S, lane, false);
   PT(11);
   // ---- reward -> update -> done (quadruped_gym_env.py:230-233) ----
   // the frames of the new reference poses are fetched while the reward is computed (their round trip to L2 is not waited for)
@@ -603,7 +669,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     WSYNC();
     if (c.flags & ORR_FLAG_AUTO_RESET) {
       PT(31);
-      obs_episode = reset_robot_state<CLIPS, NOISE>(P, S, lane, total_snapshot, RC, &clip_change);
+      obs_episode = reset_robot_state<CLIPS, NOISE, SENS>(P, S, lane, total_snapshot, RC, &clip_change, nullptr, SN);
       noise_i = 0u;
       was_reset = true;
       if constexpr (ANCHOR) AS = AnchorState{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};   // a new episode: no cached contact points
@@ -612,7 +678,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   WSYNC();
   PT(14);
   // ---- observation (wrapper_env.py:109-125), ONCE per robot: of the step that ended, or of the episode that just began ----
-  build_obs<NOISE>(P, rec, S, lane, obs, obs_episode, noise_i);
+  build_obs<NOISE, SENS>(P, rec, S, lane, obs, obs_episode, noise_i, SN);
   PT(13);
   // ---- every store of the step, behind every load ----
   if (valid && lane == 0) {
@@ -876,6 +942,11 @@ hipError_t launch_reset(const KParams& P, int waves, hipStream_t stream, const u
   hipLaunchKernelGGL((orr_reset_kernel<CLIPS, NOISE>), dim3(waves), dim3(64), 0, stream, P, mask, obs, uniforms);
   return hipGetLastError();
 }
+template <bool CLIPS>
+hipError_t launch_sensor_reset(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs, const float* uniforms) {
+  hipLaunchKernelGGL((orr_sensor_reset_kernel<CLIPS>), dim3(waves), dim3(64), 0, stream, P, mask, obs, uniforms);
+  return hipGetLastError();
+}
 
 extern template StepLaunch launch_step<0, 2, false, false>;                  // orr_kernels_w2.hip
 extern template StepLaunch launch_step<0, 1, true, false>;                   // orr_kernels_anchor.hip: env step,
@@ -893,6 +964,9 @@ extern template StepLaunch launch_step<kModeContacts | kModeTerms | 0, 1, false,
 extern template StepLaunch launch_step<kModeContacts | 1, 1, false, false>;                     //   debug physics (resets: the noise unit's; no parity replay)
 extern template StepLaunch launch_step<kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>;   // orr_kernels_actuator.hip: env step with torque limits + actuator outputs,
 extern template StepLaunch launch_step<kModeActuator | kModeTerms | 2, 1, false, true, true>;                   //   its parity replay (resets: the noise unit's; no debug physics)
+extern template StepLaunch launch_step<kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>;   // orr_kernels_sensor.hip: env step with sensor noise,
+extern template StepLaunch launch_step<kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>;                   //   its parity replay,
+extern template ResetLaunch launch_sensor_reset<true>;                                                                       //   reset (and its parity replay)
 
 #ifdef ORR_STAGE_DUMP
 // the stage dump: instantiated in BOTH step units (orr_kernels.hip: WPE 1, orr_kernels_w2.hip: WPE 2), which compile different forms of

@@ -92,6 +92,7 @@ struct orr_handle {
   bool contacts_on;           // orr_bind_contact_outputs: env step and debug physics run the contact variants (orr_kernels_contacts.hip), the resets the noise variant
   uint32_t limit_types;       // orr_set_torque_limits: bit t = robot type t has a finite torque limit on some motor
   bool act_on;                // orr_bind_actuator_outputs.  With either, env step and parity replay run the actuator variants (orr_kernels_actuator.hip), the resets the noise variant
+  bool sensor_on;             // orr_set_sensor_noise: a motor-angle, rpy or rpy-rate deviation above 0: env step, parity replays and resets run the sensor variants (orr_kernels_sensor.hip)
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -151,6 +152,7 @@ int32_t orr_layout_is_int(int32_t i) { return g_fields[i].is_int; }
 int32_t orr_sizeof_config(void) { return (int32_t)sizeof(orr_config); }
 int32_t orr_sizeof_model(void) { return (int32_t)sizeof(orr_model); }
 int32_t orr_sizeof_task_noise(void) { return (int32_t)sizeof(orr_task_noise); }
+int32_t orr_sizeof_sensor_noise(void) { return (int32_t)sizeof(orr_sensor_noise); }
 
 int32_t orr_create(const orr_config* cfg, orr_handle** out) {
   if (!cfg || !out) return fail(-1, "orr_create: null argument");
@@ -463,6 +465,30 @@ int32_t orr_set_task_noise(orr_handle* h, const orr_task_noise* noise_host) {
   return 0;
 }
 
+int32_t orr_set_sensor_noise(orr_handle* h, const orr_sensor_noise* noise_host) {
+  if (!h) return fail(-1, "orr_set_sensor_noise: null handle");
+  orr_sensor_noise n;
+  memset(&n, 0, sizeof(n));
+  if (noise_host) n = *noise_host;
+  const struct { const char* name; float v; } stds[] = {
+      {"motor_angle_std", n.motor_angle_std}, {"motor_velocity_std", n.motor_velocity_std}, {"motor_torque_std", n.motor_torque_std},
+      {"base_rpy_std", n.base_rpy_std}, {"base_rpy_rate_std", n.base_rpy_rate_std}};
+  for (const auto& f : stds)
+    if (!(f.v >= 0.0f && f.v < INFINITY)) {      // NaN fails the comparison
+      char m[160];
+      snprintf(m, sizeof(m), "orr_set_sensor_noise: %s must be a finite standard deviation >= 0", f.name);
+      return fail(-1, m);
+    }
+  const bool on = n.motor_angle_std > 0.0f || n.base_rpy_std > 0.0f || n.base_rpy_rate_std > 0.0f;
+  if (on && h->anchor_types)
+    return fail(-1, "orr_set_sensor_noise: friction anchors (orr_model::friction_anchor) and sensor noise cannot be combined");
+  // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->sensor, &n, sizeof(n), hipMemcpyHostToDevice), "orr_set_sensor_noise: hipMemcpy");
+  h->tab_host.sensor = n;
+  h->sensor_on = on;
+  return 0;
+}
+
 int32_t orr_bind(orr_handle* h, void* state_dev, int64_t* counters_dev, float* ep_log_dev, int32_t ep_log_capacity) {
   if (!h || !state_dev || !counters_dev) return fail(-1, "orr_bind: null argument (state and counters are required)");
   if (((uintptr_t)state_dev & 15u) != 0) return fail(-1, "orr_bind: the state buffer must be 16-byte aligned (records move in 16-byte pieces)");
@@ -498,7 +524,8 @@ static KParams make_params(const orr_handle* h) {
 static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1) / kRPW; }
 
 // Which instantiation of the kernels a launch runs.  `clip_types` = the feature mask that selects the clip-set variants: multiclip_types
-// for orr_step / orr_reset, switch_types for the parity replays.  Torque limits and actuator outputs come first (env step, parity replay
+// for orr_step / orr_reset, switch_types for the parity replays.  Sensor noise comes first (env step, parity replays and resets: supersets
+// of everything below but the friction anchors, which are refused).  Then torque limits and actuator outputs come first (env step, parity replay
 // and the resets, which run the noise variant; the two step variants are supersets that serve the reward terms and - the env step - the
 // contact outputs too, whichever are bound; friction anchors are refused), then the contact outputs (`contacts` = the entry point has a
 // contact variant: not the parity replays, which have no impulses and run what they run without the binding; the env step has one with
@@ -507,7 +534,7 @@ static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1)
 // clip sets (both refuse friction anchors: kRefused, the message starts with the entry point's name `who`), then friction anchors, then
 // the batch size; only the env step has a two-wave and only the env step and the debug physics have an anchor instantiation, every other
 // entry point runs its default one instead.
-enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts, kActuator };
+enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts, kActuator, kSensor };
 static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {   // (a model with anchors set after orr_bind_contact_outputs)
   if (!(h->contacts_on && h->anchor_types)) return false;
   char m[256];
@@ -516,6 +543,15 @@ static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {
   return true;
 }
 static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who, bool contacts = true) {
+  if (h->sensor_on) {
+    if (h->anchor_types) {   // (a model with anchors set after orr_set_sensor_noise)
+      char m[256];
+      snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and sensor noise (orr_set_sensor_noise) cannot be combined", who);
+      fail(-1, m);
+      return kRefused;
+    }
+    return kSensor;
+  }
   if (h->act_on || h->limit_types) {
     if (h->anchor_types) {   // (a model with anchors set after orr_set_torque_limits / orr_bind_actuator_outputs)
       char m[256];
@@ -556,7 +592,9 @@ int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* 
   if (!h || !h->state) return fail(-1, "orr_reset: handle not bound");
   const Variant v = variant_of(h, h->multiclip_types, "orr_reset");
   if (v == kRefused) return -1;
-  if (v == kNoise || v == kTerms || v == kContacts || v == kActuator)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
+  if (v == kSensor)   // sensor noise: three noisy readings per history, a noisy heading of the target observation
+    HIPCHK((launch_sensor_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (sensor noise)");
+  else if (v == kNoise || v == kTerms || v == kContacts || v == kActuator)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (task noise)");
   else if (v == kClips)   // some robot type has a clip set of more than one clip: every reset draws the episode's clip
     HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr), "orr_reset: launch (clip sets)");
@@ -573,6 +611,11 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
   HIPCHK((launch_step<0, WPE, ANCHOR, CLIPS, NOISE>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{})), msg)
   switch (variant_of(h, h->multiclip_types, "orr_step")) {
     case kRefused: return -1;
+    case kSensor:   // one wave per SIMD, any batch size; the superset that also serves torque limits and every output binding
+      HIPCHK((launch_step<kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev,
+                                                                                                              obs_dev, reward_dev, done_dev, 0, ReplayArgs{})),
+             "orr_step: launch (sensor noise)");
+      break;
     case kActuator:   // one wave per SIMD, any batch size; the superset that also serves the reward terms and the contact outputs where bound
       HIPCHK((launch_step<kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev,
                                                                                                 reward_dev, done_dev, 0, ReplayArgs{})), "orr_step: launch (actuator)");
@@ -644,7 +687,10 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
   const ReplayArgs rp{traj_dev, eff_dev, fall_dev, tau_out_dev, nullptr};
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_step", false);   // no contact variant: contact_out is left alone
   if (v == kRefused) return -1;
-  if (v == kActuator)   // torque limits / actuator outputs: the noise replay that clips and accumulates the torques (and writes the terms where bound)
+  if (v == kSensor)   // sensor noise: the actuator replay with noisy readings (their draws come from the Philox stream)
+    HIPCHK((launch_step<kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev,
+                                                                                            done_dev, 0, rp)), "orr_debug_replay_step: launch (sensor noise)");
+  else if (v == kActuator)   // torque limits / actuator outputs: the noise replay that clips and accumulates the torques (and writes the terms where bound)
     HIPCHK((launch_step<kModeActuator | kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0,
                                                                               rp)), "orr_debug_replay_step: launch (actuator)");
   else if (v == kTerms)   // reward terms: the noise replay that also writes the terms
@@ -665,7 +711,9 @@ int32_t orr_debug_replay_reset(orr_handle* h, const float* uniforms_dev, float* 
   if (!h || !h->state || !uniforms_dev) return fail(-1, "orr_debug_replay_reset: bad argument");
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_reset", false);
   if (v == kRefused) return -1;
-  if (v == kNoise || v == kTerms || v == kActuator)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
+  if (v == kSensor)   // sensor noise: the sensor reset (draws 0..27 from uniforms_dev; everything else from the Philox stream)
+    HIPCHK((launch_sensor_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (sensor noise)");
+  else if (v == kNoise || v == kTerms || v == kActuator)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (task noise)");
   else if (v == kClips)   // a clip switch interval: the multi-clip reset (draws 0..27 from uniforms_dev, 28 on from the Philox stream)
     HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev), "orr_debug_replay_reset: launch (clip switching)");

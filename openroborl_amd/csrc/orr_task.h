@@ -200,6 +200,23 @@ __device__ __forceinline__ int target_frame_steps(const orr_config& c, int lane)
 
 // Philox blocks of the task noise (orr_set_task_noise; below 2^30: a draw index is 4 * block + word, 32 bits)
 constexpr uint32_t kNoiseResetBlock = 0x20000000u, kNoiseHeadingBlock = 0x30000000u;
+// Philox blocks of the sensor noise (orr_set_sensor_noise): 0x10000000 + (i << 9) + (slot << 4) + lane, i = 0 for a reset of the episode,
+// 1 + s for the step whose env-step counter before it is s.  Slots 0..16: the sub-steps' motor-angle readings (lane = motor; sub-step
+// 2 slot: words 0, 1, sub-step 2 slot + 1: words 2, 3; z0 = the command clip's reading, z1 = the interpolation start's), 17: the sensor
+// histories' readings (lane = column), 18: the filter history's initial value (lane = motor), 19: the target observation's rpy
+constexpr uint32_t kSensorBlock = 0x10000000u, kSensorSlotHist = 17u, kSensorSlotFilter = 18u, kSensorSlotTarget = 19u;
+__device__ __forceinline__ uint32_t sensor_block(uint32_t i, uint32_t slot, uint32_t lane) { return kSensorBlock + (i << 9) + (slot << 4) + lane; }
+// the handle's three deviations, each the same in every lane (scalar registers from here on)
+__device__ __forceinline__ SensorNoise load_sensor_noise(const KParams& P) {
+  typedef const float __attribute__((address_space(1)))* gfp;
+  const gfp sp = (gfp)&P.tab->sensor.motor_angle_std;
+  static_assert(offsetof(orr_sensor_noise, base_rpy_std) == 12 && offsetof(orr_sensor_noise, base_rpy_rate_std) == 16, "words 0, 3, 4");
+  SensorNoise SN;
+  SN.a = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sp[0])));
+  SN.r = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sp[3])));
+  SN.d = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sp[4])));
+  return SN;
+}
 
 // build the 76-d target observation into obs76 (LDS) from S.ph.end.pose[1..4] (already origin-offset) -- imitation_task.py:254-301.
 // The control observation S.co must be current (it is after the last sub-step's ring push and after reset_robot_state's local blend).
@@ -207,11 +224,24 @@ constexpr uint32_t kNoiseResetBlock = 0x20000000u, kNoiseHeadingBlock = 0x300000
 // expressed in gets orr_task_noise::tar_heading_std times a normal from block 0x30000000 + noise_i of the stream (robot index, episode):
 // noise_i = 0 for the observation of a reset, 1 + s for the step whose env-step counter before the step is s.  Both come from the
 // caller's registers: the record's EP_STEP / EPISODE_IDX words are rewritten by lane 0 right before the calls
-template <bool NOISE = false>
-__device__ static void target_obs(const KParams& P, const float* rec, Shared& S, int lane, float* obs76, uint32_t episode = 0u, uint32_t noise_i = 0u) {
+// SENS (the sensor variants, orr_kernels_sensor.hip; always with NOISE): the heading is formed from get_base_rpy's noisy reading
+// (minitaur.py:630-638) - pitch and yaw each get SN.r times a normal of slot 19 of the same (episode, noise_i); roll's draw is unused
+template <bool NOISE = false, bool SENS = false>
+__device__ static void target_obs(const KParams& P, const float* rec, Shared& S, int lane, float* obs76, uint32_t episode = 0u, uint32_t noise_i = 0u,
+                                  const SensorNoise& SN = SensorNoise{}) {
   if (lane >= 1 && lane <= 4) {
     float rpy[3];
     euler_from_quat(&S.co[12], rpy);
+    if constexpr (SENS) {
+      if (SN.r > 0.0f) {   // wave-uniform
+        float u4[4], zr, zp, zy, zu;
+        philox_block(P.cfg.seed, (uint32_t)geti(S, O(ROBOT_INDEX)), episode, sensor_block(noise_i, kSensorSlotTarget, 0u), u4);
+        normal_pair(u4[0], u4[1], &zr, &zp);
+        normal_pair(u4[2], u4[3], &zy, &zu);
+        rpy[1] = fmaf(SN.r, zp, rpy[1]);
+        rpy[2] = fmaf(SN.r, zy, rpy[2]);
+      }
+    }
     // robot.get_base_orientation (minitaur.py:630-638) = quaternion of the delayed rpy; its heading is the
     // direction of the rotated x axis = atan2(sin(yaw) cos(pitch), cos(yaw) cos(pitch))
     float sy, cy, spch, cpch;
@@ -410,6 +440,70 @@ __device__ static void sensors_push(Shared& S, int lane, bool fill_all) {
   WSYNC();
 }
 
+// sensors_push of the sensor variants (orr_kernels_sensor.hip; a function of its own: the other variants keep theirs as it is): the motor-angle columns read map_pi(angle + SN.a z), roll and pitch rpy + SN.r z, the two rates rate +
+// SN.d z, z from slot 17 of (episode, noise_i), lane = column (a lane's first column).  A step takes z0 of the pair (word 0, word 1).  A
+// reset (fill_all) takes three separate readings (HistoricSensorWrapper.on_reset, sensor_wrappers.py:122-129) - z0, z1 of that pair, then
+// z0 of the pair (word 2, word 3) - and the first one ends up as the oldest entry.  A deviation of 0 passes the reading's bits
+__device__ static void sensors_push_noisy(Shared& S, int lane, bool fill_all, const SensorNoise& SN, unsigned long long seed, uint32_t episode,
+                                          uint32_t noise_i) {
+  constexpr bool SENS = true;
+  float rpy[3];
+  euler_from_quat(&S.co[12], rpy);
+  static_assert(!SENS || kLanes == 16, "SENS: the sixteen noisy columns are the lanes' first columns");
+  float sg = 0.0f, zs[3] = {0.0f, 0.0f, 0.0f};
+  if constexpr (SENS) {
+    if (SN.a > 0.0f || SN.r > 0.0f || SN.d > 0.0f) {   // wave-uniform
+      sg = lane < 12 ? SN.a : (lane < 14 ? SN.r : SN.d);
+      float u4[4], zu;
+      philox_block(seed, (uint32_t)geti(S, O(ROBOT_INDEX)), episode, sensor_block(noise_i, kSensorSlotHist, (uint32_t)lane), u4);
+      normal_pair(u4[0], u4[1], &zs[0], &zs[1]);
+      if (fill_all) normal_pair(u4[2], u4[3], &zs[2], &zu);
+    }
+  }
+  // 28 history columns: 0..11 motor angle k, 12..15 IMU channel, 16..27 last action; a lane owns columns lane, lane+kLanes
+  constexpr int kCols = (28 + kLanes - 1) / kLanes;
+  float newest[kCols], h0[kCols], h1[kCols];
+  float rd1 = 0.0f, rd2 = 0.0f;   // SENS: the second and third reading of a reset, first column
+  int base[kCols], w[kCols], kk[kCols];
+#pragma unroll
+  for (int c = 0; c < kCols; c++) {
+    const int col = lane + c * kLanes;
+    base[c] = 0; w[c] = 0; kk[c] = 0; newest[c] = 0.0f; h0[c] = 0.0f; h1[c] = 0.0f;
+    if (col < 12) { base[c] = O(MOTORANG_HIST); w[c] = 12; kk[c] = col; newest[c] = map_pi(S.co[col]); }
+    else if (col < 16) { base[c] = O(IMU_HIST); w[c] = 4; kk[c] = col - 12; newest[c] = kk[c] == 0 ? rpy[0] : (kk[c] == 1 ? rpy[1] : (kk[c] == 2 ? S.co[16] : S.co[17])); }
+    else if (col < 28) { base[c] = O(LASTACT_HIST); w[c] = 12; kk[c] = col - 16; newest[c] = S.s[O(LAST_ACTION) + kk[c]]; }
+    if constexpr (SENS) {
+      if (c == 0) {
+        rd1 = rd2 = newest[0];
+        if (sg > 0.0f) {
+          const float x = lane < 12 ? S.co[lane] : newest[0];
+          const float r0 = fmaf(sg, zs[0], x), r1 = fmaf(sg, zs[1], x), r2 = fmaf(sg, zs[2], x);
+          newest[0] = lane < 12 ? map_pi(r0) : r0;
+          rd1 = lane < 12 ? map_pi(r1) : r1;
+          rd2 = lane < 12 ? map_pi(r2) : r2;
+        }
+      }
+    }
+    if (col < 28) { h0[c] = S.s[base[c] + kk[c]]; h1[c] = S.s[base[c] + w[c] + kk[c]]; }
+  }
+  WSYNC();
+#pragma unroll
+  for (int c = 0; c < kCols; c++) {
+    if (lane + c * kLanes < 28) {
+      if (SENS && c == 0 && fill_all) {   // three readings: newest[0] was the first
+        S.s[base[c] + kk[c]] = rd2;
+        S.s[base[c] + w[c] + kk[c]] = rd1;
+        S.s[base[c] + 2 * w[c] + kk[c]] = newest[c];
+        continue;
+      }
+      S.s[base[c] + kk[c]] = newest[c];
+      S.s[base[c] + w[c] + kk[c]] = fill_all ? newest[c] : h0[c];
+      S.s[base[c] + 2 * w[c] + kk[c]] = fill_all ? newest[c] : h1[c];
+    }
+  }
+  WSYNC();
+}
+
 // ================================================================================================
 // reset of one robot (wrapper_env.py:87-107 -> quadruped_gym_env.py:63-104 -> minitaur.py:232-278 ->
 // imitation_task.py:166-199); SURVEY.md Appendix A.2.
@@ -428,9 +522,11 @@ __device__ static void sensors_push(Shared& S, int lane, bool fill_all) {
 // record.  build_obs then writes the observation; the step kernel calls it once for all its robots, reset or not.  -> the new episode index
 __device__ __forceinline__ float* reset_entry1(Shared& S) { return S.ph.end.red; }        // 20 words each; no step-end code past the reset
 __device__ __forceinline__ float* reset_entry2(Shared& S) { return S.ph.end.red + 56; }   // touches red[]
-template <bool CLIPS = false, bool NOISE = false>
+// SENS (the sensor variants, orr_kernels_sensor.hip; always with NOISE): stage 3 fills the sensor histories with three separate noisy
+// readings (sensors_push_noisy; i = 0 of the new episode's stream)
+template <bool CLIPS = false, bool NOISE = false, bool SENS = false>
 __device__ static uint32_t reset_robot_state(const KParams& P, Shared& S, int lane, long long total_step_count, const ResetConst& RC,
-                                             float* clip_change, const float* uni_replay = nullptr) {
+                                             float* clip_change, const float* uni_replay = nullptr, const SensorNoise& SN = SensorNoise{}) {
   const orr_config& c = P.cfg;
   // every reset starts a new episode = a new RNG stream (robot, episode)
   const uint32_t robot = (uint32_t)geti(S, O(ROBOT_INDEX)), ep = (uint32_t)geti(S, O(EPISODE_IDX)) + 1u;
@@ -559,7 +655,8 @@ __device__ static uint32_t reset_robot_state(const KParams& P, Shared& S, int la
   for (int i = lane; i < 19; i += kLanes) S.co[i] = e1[i];   // one entry in the ring: _get_delay_obs returns it (minitaur.py:345-346)
   WSYNC();
   PT(29);
-  sensors_push(S, lane, true);
+  if constexpr (SENS) sensors_push_noisy(S, lane, true, SN, c.seed, ep, 0u);
+  else sensors_push(S, lane, true);
   const float e1_keep[2] = {e1[lane], e1[lane < 3 ? 16 + lane : lane]};   // ring entry #1: words lane and (lanes 0..2) 16 + lane
   PT(18);
   // 4b. randomiser (controllable_env_randomizer_from_config.py:92-122), sorted-name draw order:
@@ -659,9 +756,10 @@ __device__ __forceinline__ void store_reset_extras(float* rec, Shared& S, int la
 
 // 7. observation = sensor histories + target observation (quadruped_gym_env.py:100-102; wrapper_env.py:101-105, 109-125), for the
 // step that just ended and for a reset alike: `episode` / `noise_i` are the robot's own (a reset: the new episode, 0)
-template <bool NOISE = false>
-__device__ static void build_obs(const KParams& P, const float* rec, Shared& S, int lane, float* obs, uint32_t episode, uint32_t noise_i) {
+template <bool NOISE = false, bool SENS = false>
+__device__ static void build_obs(const KParams& P, const float* rec, Shared& S, int lane, float* obs, uint32_t episode, uint32_t noise_i,
+                                 const SensorNoise& SN = SensorNoise{}) {
   if (lane < 12) obs[lane] = S.s[O(IMU_HIST) + lane];
   for (int i = lane; i < 36; i += kLanes) { obs[12 + i] = S.s[O(LASTACT_HIST) + i]; obs[48 + i] = S.s[O(MOTORANG_HIST) + i]; }
-  target_obs<NOISE>(P, rec, S, lane, obs + ORR_PROPRIO_DIM, episode, noise_i);
+  target_obs<NOISE, SENS>(P, rec, S, lane, obs + ORR_PROPRIO_DIM, episode, noise_i, SN);
 }

@@ -271,6 +271,55 @@ def task_noise_spec(perturb_init_state_prob=0.0, tar_obs_noise=None, init_pertur
     return _abi.OrrTaskNoise(perturb_init_state_prob=prob, **vals)
 
 
+# ---- sensor noise (orr_set_sensor_noise; Minitaur._observation_noise_stdev) ---------------------------------------------------------
+SENSOR_NOISE_BLOCK = 0x10000000     # block 0x10000000 + (i << 9) + (slot << 4) + lane of the episode's stream (sensor_noise_block)
+SENSOR_SLOT_HIST, SENSOR_SLOT_FILTER, SENSOR_SLOT_TARGET = 17, 18, 19   # slots 0..16: the sub-steps' motor-angle readings, two sub-steps a slot
+
+
+def sensor_noise_block(i, slot, lane):
+    """Philox block of a sensor-noise draw (include/openroborl_hip.h, orr_set_sensor_noise): i = 0 for a reset of the episode (the
+    auto-reset inside a step included: the NEW episode's stream), 1 + s for the step whose env-step counter before it is s; slot
+    0..16 = sub-steps 2 slot (words 0, 1) and 2 slot + 1 (words 2, 3), lane = motor; 17 = the sensor histories, lane = column (0..11
+    motor angle, 12 roll, 13 pitch, 14 roll rate, 15 pitch rate); 18 = the filter history's initial value, lane = motor; 19 = the
+    target observation's rpy, lane 0.  Works on integer arrays."""
+    i, slot, lane = np.asarray(i, dtype=np.int64), np.asarray(slot, dtype=np.int64), np.asarray(lane, dtype=np.int64)
+    if (i < 0).any() or (i >= 1 << 19).any() or (slot < 0).any() or (slot >= 32).any() or (lane < 0).any() or (lane >= 16).any():
+        raise ValueError("sensor_noise_block: i in [0, 2^19), slot in [0, 32), lane in [0, 16)")
+    return SENSOR_NOISE_BLOCK + (i << 9) + (slot << 4) + lane
+
+
+def sensor_noise_normals(u4):
+    """The four normals of a sensor-noise block from its four uniforms (shape [..., 4]): z0, z1 of the pair (word 0, word 1), then z0,
+    z1 of the pair (word 2, word 3), by normal_pair, in float64.  Which of them a slot uses: sensor_noise_block."""
+    u4 = np.asarray(u4, dtype=np.float64)
+    a0, a1 = normal_pair(u4[..., 0], u4[..., 1])
+    b0, b1 = normal_pair(u4[..., 2], u4[..., 3])
+    return np.stack([a0, a1, b0, b1], axis=-1)
+
+
+def sensor_noise_spec(observation_noise_stdev=None):
+    """Minitaur._observation_noise_stdev (None = off, or five numbers: motor angle, motor velocity, motor torque, base rpy, base rpy
+    rate; velocity and torque are kept and have no consumer on this path) -> the orr_sensor_noise struct.  ValueError on anything the
+    C-ABI (orr_set_sensor_noise) would refuse; the message names the field."""
+    if observation_noise_stdev is None:
+        return _abi.OrrSensorNoise()
+    if isinstance(observation_noise_stdev, (str, dict, bool, np.bool_)) or np.ndim(observation_noise_stdev) != 1 or len(observation_noise_stdev) != 5:
+        raise ValueError("observation_noise_stdev must be None or five numbers (%s), not %r" % (", ".join(_abi.SENSOR_NOISE_FIELDS), observation_noise_stdev))
+    vals = {}
+    for name, v in zip(_abi.SENSOR_NOISE_FIELDS, observation_noise_stdev):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number, not %r" % (name, v))
+        if not (0.0 <= float(v) < math.inf):       # NaN fails the comparison
+            raise ValueError("%s must be a finite standard deviation >= 0, not %r" % (name, v))
+        vals[name] = float(v)
+    return _abi.OrrSensorNoise(**vals)
+
+
+def sensor_noise_on(spec):
+    """Whether the setting selects the sensor variants of the kernels: a deviation with a consumer is above 0."""
+    return spec.motor_angle_std > 0.0 or spec.base_rpy_std > 0.0 or spec.base_rpy_rate_std > 0.0
+
+
 def action_space():
     """minitaur.py:145-148."""
     return Box(np.array([-2 * math.pi] * 12), np.array([2 * math.pi] * 12), dtype=np.float32)
@@ -285,7 +334,8 @@ class VecQuadrupedEnv(object):
                  robot=None, motion_file=None, mode=None, enable_randomizer=None, auto_reset=True, num_procs=1,
                  robot_index_offset=0, legacy_grid=False, mixed_robots=None, ep_log_capacity=65536, config_overrides=None,
                  model_overrides=None, clip_time_min=None, clip_time_max=None, perturb_init_state_prob=None, tar_obs_noise=None,
-                 init_perturb_std=None, reward_terms=False, contact_outputs=False, torque_limits=None, actuator_outputs=False):
+                 init_perturb_std=None, reward_terms=False, contact_outputs=False, torque_limits=None, actuator_outputs=False,
+                 observation_noise_stdev=None):
         import torch
         if not isinstance(reward_terms, (bool, np.bool_)):
             raise ValueError("reward_terms must be True or False, got %r" % (reward_terms,))
@@ -295,6 +345,8 @@ class VecQuadrupedEnv(object):
             raise ValueError("actuator_outputs must be True or False, got %r" % (actuator_outputs,))
         # the values here, ahead of everything that needs the device; a dict's robot names below, once the batch's robots are known
         torque_limit_spec(torque_limits, sorted(torque_limits) if isinstance(torque_limits, dict) else ["every robot"])
+        # sensor noise (Minitaur._observation_noise_stdev): off by default, as the reference ships it
+        self.sensor_noise = sensor_noise_spec(observation_noise_stdev)
         self.torch = torch
         if not torch.cuda.is_available():
             raise RuntimeError("VecQuadrupedEnv needs a ROCm GPU (the HIP path has no CPU fallback)")
@@ -443,6 +495,8 @@ class VecQuadrupedEnv(object):
             self.set_torque_limits(torque_limits)
         if actuator_outputs:
             self.bind_actuator_outputs(True)
+        if sensor_noise_on(self.sensor_noise):
+            self.set_sensor_noise(observation_noise_stdev)
 
     # ---- reference attribute surface -------------------------------------------------------
     @property
@@ -484,6 +538,15 @@ class VecQuadrupedEnv(object):
         spec = task_noise_spec(perturb_init_state_prob, tar_obs_noise, init_perturb_std)
         _lib.check(self.L.orr_set_task_noise(self.h, C.byref(spec)), self.L)
         self.task_noise = spec
+        self.launch_params_generation += 1
+
+    def set_sensor_noise(self, observation_noise_stdev=None):
+        """Change the sensor noise of a running env (orr_set_sensor_noise; Minitaur._observation_noise_stdev: None = off, or the five
+        standard deviations of motor angle, motor velocity, motor torque, base rpy and base rpy rate): read from the next launch on.
+        It selects the kernel variant: holders of captured graphs re-capture (launch_params_generation)."""
+        spec = sensor_noise_spec(observation_noise_stdev)
+        _lib.check(self.L.orr_set_sensor_noise(self.h, C.byref(spec)), self.L)
+        self.sensor_noise = spec
         self.launch_params_generation += 1
 
     def bind_reward_terms(self, on=True):
@@ -814,7 +877,7 @@ class LegacyListEnv(object):
     INIT_MOTOR_ANGLES added in place (minitaur.py:281).
     """
 
-    def __init__(self, env, mutate_actions=True, torque_limits=None, actuator_outputs=False):
+    def __init__(self, env, mutate_actions=True, torque_limits=None, actuator_outputs=False, observation_noise_stdev=None):
         if env.cfg.flags & _abi.FLAG_AUTO_RESET:
             raise ValueError("LegacyListEnv needs a VecQuadrupedEnv created with auto_reset=False")
         if not isinstance(actuator_outputs, (bool, np.bool_)):
@@ -823,6 +886,8 @@ class LegacyListEnv(object):
             env.set_torque_limits(torque_limits)
         if actuator_outputs:
             env.bind_actuator_outputs(True)
+        if observation_noise_stdev is not None:     # Minitaur._observation_noise_stdev, passed through to the env
+            env.set_sensor_noise(observation_noise_stdev)
         self._env = env
         self._mutate = mutate_actions
         self.num_robot = env.num_robot

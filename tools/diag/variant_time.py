@@ -1,5 +1,5 @@
 """Step time of a variant of the step kernel against its baseline, 4096 robots, same process, alternated (train semantics):
-python tools/diag/variant_time.py --case noise|terms|contacts|actuator|anchor
+python tools/diag/variant_time.py --case noise|terms|contacts|actuator|sensor|anchor
 
   noise     the task-noise variant against the clip-set variant (a two-clip set, so that the plain env runs the clip-set variant)
   terms     reward terms on top of task noise               (two-clip set, noise on in all at one setting: prob 0.5, sigma 0.1)
@@ -10,6 +10,9 @@ python tools/diag/variant_time.py --case noise|terms|contacts|actuator|anchor
             falls or folds into its joint limits: an episode's end is an auto-reset inside the launch, a joint near its bound a
             joint-limit row in the solver, off the sub-step's common path); also the episodes each env finished while timed, the
             share of its robots with a joint-limit row at the end, and the logged episodes' actuator statistics
+  sensor    sensor noise (motor angle 0.01 rad, rpy 0.02 rad, rpy rate 0.1 rad/s) on top of the actuator variant with all three bindings on
+            and no limits, the same set and task noise; in between the sensor variant with motor_angle_std = 0, which skips the
+            sub-steps' draws: the cost of the step end's draws apart from the sub-step loop's
   anchor    the friction-anchor variant against the default kernel (the task's own clip, no noise)
 
 Every env gets 300 warm-up steps of stress actions, then 5 rounds of 300 back-to-back launches with fixed actions go round the envs in
@@ -39,6 +42,10 @@ CASES = {
                  (("task noise + contact outputs + reward terms", {}),
                   ("the same + actuator outputs, no limits", dict(actuator_outputs=True)),
                   ("the same + torque limits 20 / 30 / 40 + actuator outputs", dict(torque_limits=[20.0, 30.0, 40.0] * 4, actuator_outputs=True)))),
+    "sensor": (dict(TWO_CLIPS, contact_outputs=True, reward_terms=True, actuator_outputs=True, **NOISE),
+               (("task noise + contact outputs + reward terms + actuator outputs", {}),
+                ("the same + sensor noise on rpy 0.02 / rpy rate 0.1 only", dict(observation_noise_stdev=[0.0, 0.0, 0.0, 0.02, 0.1])),
+                ("the same + sensor noise on motor angle 0.01 / rpy 0.02 / rpy rate 0.1", dict(observation_noise_stdev=[0.01, 0.0, 0.0, 0.02, 0.1])))),
     "anchor": ({}, (("default", {}), ("friction anchors", dict(model_overrides={"laikago": {"friction_anchor": 1}})))),
 }
 

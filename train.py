@@ -40,6 +40,10 @@ def main():
     ap.add_argument("--tar-obs-noise", type=float, default=None,
                     help="standard deviation (rad) of the noise on the heading the target observations are expressed in (ImitationTask's "
                          "tar_obs_noise[0]; overrides the task YAML's; default: none)")
+    ap.add_argument("--sensor-noise", type=sensor_noise_arg, default=None, metavar="A,V,T,R,D",
+                    help="standard deviations of the sensor noise: motor angle (rad), motor velocity, motor torque, base roll / pitch / yaw (rad) "
+                         "and their rates (rad/s), the reference robot's _observation_noise_stdev; velocity and torque are accepted and have no "
+                         "consumer (default: none)")
     ap.add_argument("--reward-terms", action="store_true",
                     help="also output the five unweighted terms of the imitation reward on the device (pose, velocity, end effector, root pose, "
                          "root velocity): every logged record gains \"reward_terms\": {name: mean per step} over the episodes THIS rank finished "
@@ -83,7 +87,7 @@ def main():
     env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
                           device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
                           perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise,
-                          reward_terms=args.reward_terms, contact_outputs=args.contact_outputs,
+                          reward_terms=args.reward_terms, contact_outputs=args.contact_outputs, observation_noise_stdev=args.sensor_noise,
                           **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     model = ppo.ActorCritic(dev, params=params, seed=args.seed)                     # same seed -> identical replicas
@@ -161,6 +165,17 @@ def main():
         torch.distributed.destroy_process_group()
 
 
+def sensor_noise_arg(text):
+    """--sensor-noise a,v,t,r,d -> five floats (validated by the env: openroborl_amd.env.sensor_noise_spec)."""
+    parts = text.split(",")
+    if len(parts) != 5:
+        raise argparse.ArgumentTypeError("five comma-separated numbers: motor angle, motor velocity, motor torque, base rpy, base rpy rate")
+    try:
+        return [float(x) for x in parts]
+    except ValueError:
+        raise argparse.ArgumentTypeError("not a number in %r" % (text,))
+
+
 def clip_time_kwargs(args):
     """--clip-time MIN MAX -> the env's clip_time_min / clip_time_max (nothing given: the task YAML's, else no switching)."""
     return {} if args.clip_time is None else dict(clip_time_min=args.clip_time[0], clip_time_max=args.clip_time[1])
@@ -177,7 +192,7 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     n = min(args.num_robot, 1024)
     env = VecQuadrupedEnv(task_name=args.task, num_robot=n, mode="test", auto_reset=False, seed=args.seed, device=dev,
                           motion_file=args.motion_file, reward_terms=args.reward_terms, contact_outputs=args.contact_outputs,
-                          **clip_time_kwargs(args))
+                          observation_noise_stdev=args.sensor_noise, **clip_time_kwargs(args))
     model = ppo.ActorCritic(dev, params=pol.load_parameters(args.eval))
     if not args.torch_policy:
         model.enable_fused()
