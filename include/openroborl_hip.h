@@ -343,6 +343,46 @@ typedef struct orr_sensor_noise {   /* Minitaur._observation_noise_stdev, in its
 int32_t orr_set_sensor_noise(orr_handle* h, const orr_sensor_noise* noise_host);
 int32_t orr_sizeof_sensor_noise(void);
 
+/* domain randomisation of the handle (ControllableEnvRandomizerFromConfig, controllable_env_randomizer_from_config.py:92-172; the
+ * parameter dictionary of minitaur_env_randomizer_config.py: name -> [lower, upper]).  Ten of the reference's sixteen names, in its
+ * application order (sorted by name); "battery" and "motor friction" are no-ops in the reference, "control step", "individual mass",
+ * "individual inertia" and "restitution" have nothing to act on in this engine. */
+enum { ORR_RAND_BASE_MASS, ORR_RAND_GLOBAL_MOTOR_STRENGTH, ORR_RAND_INERTIA, ORR_RAND_JOINT_FRICTION, ORR_RAND_LATENCY,
+       ORR_RAND_LATERAL_FRICTION, ORR_RAND_LEG_WEAKEN, ORR_RAND_MASS, ORR_RAND_MOTOR_STRENGTH, ORR_RAND_SINGLE_LEG_WEAKEN,
+       ORR_RAND_NUM_PARAMS };                       /* the reference's application order: sorted by name */
+typedef struct orr_randomizer { int32_t enabled[ORR_RAND_NUM_PARAMS]; float lo[ORR_RAND_NUM_PARAMS], hi[ORR_RAND_NUM_PARAMS]; } orr_randomizer;
+/* Everything below holds while ORR_FLAG_RANDOMIZER is set; without the flag no reset randomises anything and no row is written.
+ * host NULL = the built-in six ranges (inertia 0.5-1.5, joint friction 0-0.05, latency 0-0.04, lateral friction 0.5-1.25, mass 0.8-1.2,
+ *   motor strength 0.8-1.2; the other four disabled) and the kernels the handle launched before.  A non-NULL host - whatever its
+ *   ranges - or a bound params buffer selects the randomiser variants of orr_step, orr_reset and the parity replays (supersets of the
+ *   sensor variants: one wave per SIMD at any batch size, unbound outputs skipped, zero noise passes the reading).
+ * Value of an enabled parameter: fmaf(u, hi - lo, lo) in float32, u in [0, 1) its draw, hi - lo one float32 subtraction on the device.
+ *   A disabled parameter leaves its record words as they are.  Parameters apply in enum order, a later one overwrites an earlier one's
+ *   words: base mass -> MASS_RATIO[0]; global motor strength -> all 12 STRENGTH words; inertia, mass -> their two ratios (mass over
+ *   base mass in MASS_RATIO[0]); joint friction -> the four KNEE_FRICTION words, from the even ones of its eight draws; latency ->
+ *   LATENCY; lateral friction -> FOOT_MU; leg weaken -> 1.0 on all 12 STRENGTH words, then the value on the three motors 3 leg ..
+ *   3 leg + 2 of the drawn leg; motor strength -> the 12 STRENGTH words, a draw each; single leg weaken -> as leg weaken, on leg 0.
+ * Draws, on the episode's (seed, robot index, episode) stream; every older block keeps its meaning: draws 0..25 as ever (inertia 0..1,
+ *   joint friction 2..9, latency 10, lateral friction 11, mass 12..13, motor strength 14..25); block 0x40000000: word 0 base mass, word 1
+ *   global motor strength, word 2 the weakened leg = (m * 4) >> 24 with m the draw's 24-bit integer, word 3 leg weaken's ratio; block
+ *   0x40000001: word 0 single leg weaken.  In the parity replays these two blocks always come from Philox; draws 0..27 from uniforms_dev.
+ * Refused, nothing changed (the message names the parameter): a null handle; for an enabled entry (a disabled one's bounds are not read) a NaN or infinite
+ *   bound, lo > hi, lo <= 0 for base mass, mass or inertia, lo < 0 for the rest; a latency hi above (ORR_RING_DEPTH - 2) * sim_dt - the
+ *   ring reader blends entries int(latency / sim_dt) and int(latency / sim_dt) + 1 back from the newest, and a ring of ORR_RING_DEPTH
+ *   entries holds those for int(latency / sim_dt) + 1 <= ORR_RING_DEPTH - 1 (0.042 s at sim_dt 0.001); friction anchors on the handle
+ *   (a launch refuses that combination too). */
+int32_t orr_set_randomizer(orr_handle* h, const orr_randomizer* host);
+int32_t orr_sizeof_randomizer(void);
+/* The episode's normalised samples per robot (get_randomization_parameters / set_env_from_randomization_parameters).  Row of a robot:
+ *   [0..25] draws 0..25, [26] base mass, [27] global motor strength, [28] the weakened leg as a float 0..3, [29] leg weaken's ratio
+ *   draw, [30] single leg weaken, [31] 0.
+ * suspend == 0: every reset (orr_reset, the auto-reset inside orr_step, orr_debug_replay_reset) writes the new episode's row - the
+ *   draws, those of disabled parameters included.  suspend != 0 (suspend_randomization): a reset draws none of these; it reads the
+ *   robot's row, applies it by the same rule and order and leaves the row alone.  The caller owns the row's contents.
+ * params_dev NULL unbinds.  Refused, nothing changed: a null handle, a buffer that is not 16-byte aligned, friction anchors. */
+#define ORR_RAND_ROW 32
+int32_t orr_bind_randomizer_params(orr_handle* h, float* params_dev /* [N][ORR_RAND_ROW] */, int32_t suspend);
+
 /* reward terms (ImitationTask._calc_reward_pose / _velocity / _end_effector / _root_pose / _root_velocity, imitation_task.py:358-516).
  * terms_dev float[N][5] (device): every orr_step and orr_debug_replay_step writes, for every robot of the shard, the five UNWEIGHTED
  *   terms r_k = exp(-scale_k err_k) of the reward it wrote to reward_dev, in orr_config::reward_w's order: pose, velocity, end effector,

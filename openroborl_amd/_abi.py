@@ -132,6 +132,19 @@ class OrrSensorNoise(C.Structure):
     _fields_ = [(n, C.c_float) for n in SENSOR_NOISE_FIELDS]
 
 
+# include/openroborl_hip.h: ORR_RAND_*, the reference's parameter names in its application order (sorted by name)
+RAND_PARAM_NAMES = ("base mass", "global motor strength", "inertia", "joint friction", "latency", "lateral friction", "leg weaken", "mass",
+                    "motor strength", "single leg weaken")
+RAND_NUM_PARAMS = len(RAND_PARAM_NAMES)
+RAND_ROW = 32                       # ORR_RAND_ROW: floats per robot in the params buffer (orr_bind_randomizer_params)
+RAND_BLOCK = 0x40000000             # Philox block of base mass, global motor strength, weakened leg, leg weaken's ratio; + 1: single leg weaken
+
+
+class OrrRandomizer(C.Structure):
+    """include/openroborl_hip.h: orr_randomizer (orr_set_randomizer)."""
+    _fields_ = [("enabled", C.c_int32 * RAND_NUM_PARAMS), ("lo", C.c_float * RAND_NUM_PARAMS), ("hi", C.c_float * RAND_NUM_PARAMS)]
+
+
 def fill(struct, name, values):
     """Assign a (nested) python sequence / scalar to a ctypes struct field."""
     import numpy as np

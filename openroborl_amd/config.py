@@ -36,6 +36,13 @@ BULLET_LIBRARY_DEFAULTS = {"contact_erp": 0.2, "warmstart_factor": 0.85, "fricti
 PYBULLET_REMEMBERED = {"contact_erp": 0.08, "warmstart_factor": 0.1, "friction_erp": 0.2, "contact_margin": 0.004}
 
 
+# The reference's randomiser configuration "all_params" (minitaur_env_randomizer_config.py:22-36), name -> [lower, upper]: what
+# ORR_FLAG_RANDOMIZER alone applies.  A task section of the training YAML may carry a dictionary of this form (or the name "all_params")
+# under the key `env_randomizer_config`; env.randomizer_spec lists the accepted names
+RANDOMIZER_ALL_PARAMS = {"mass": [0.8, 1.2], "inertia": [0.5, 1.5], "motor strength": [0.8, 1.2], "motor friction": [0, 0.05],
+                         "latency": [0.0, 0.04], "lateral friction": [0.5, 1.25], "battery": [14.0, 16.8], "joint friction": [0, 0.05]}
+
+
 def load_training_params(task_name, path=None):
     """run.py:194-200: section lookup by --task; ValueError when missing."""
     path = path or DEFAULT_TRAINING_YAML

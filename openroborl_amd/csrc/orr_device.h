@@ -130,6 +130,11 @@ struct DevTables {
   float torque_limit[ORR_MAX_ROBOT_TYPES][12];        // per motor, N m, on the strength-scaled PD torque; +inf = none (orr_create fills the table with it)
   // sensor noise of the handle (orr_set_sensor_noise), read by the sensor variants only (orr_kernels_sensor.hip).  APPENDED likewise
   orr_sensor_noise sensor;                            // all zero = off; motor_velocity_std / motor_torque_std have no consumer
+  // domain randomisation of the handle (orr_set_randomizer, orr_bind_randomizer_params), read by the randomiser variants only
+  // (orr_kernels_randomizer.hip).  APPENDED likewise
+  orr_randomizer rnd;                                 // orr_create fills in the built-in six ranges
+  float* rand_params;                                 // [N][ORR_RAND_ROW] the episode's normalised samples per robot, or NULL = not bound
+  int rand_suspend;                                   // != 0: resets apply the rows instead of drawing, and do not write them
 };
 // Flag bit of orr_step_kernel's MODE: the variant that also writes the reward terms.  MODE & 3 is the mode proper (0 env step, 1 debug
 // physics, 2 parity replay).  A bit of MODE rather than a template parameter of its own: the older variants keep their mangled names
@@ -142,6 +147,19 @@ constexpr int kModeActuator = 16;
 // Likewise: the variant whose sensor readings carry Gaussian noise (orr_set_sensor_noise).  Env step and parity replay, on top of the
 // actuator variants
 constexpr int kModeSensor = 32;
+// Likewise: the variant whose auto-reset runs the table-driven randomiser (orr_set_randomizer, orr_bind_randomizer_params).  Env step and
+// parity replay, on top of the sensor variants
+constexpr int kModeRandomizer = 64;
+static_assert(sizeof(orr_randomizer) == 12 * ORR_RAND_NUM_PARAMS && ORR_RAND_NUM_PARAMS == 10 && ORR_RAND_ROW == 32,
+              "the randomiser variants read it as three tables of ten words; a row is two words per lane");
+// What the caller of reset_robot_state<.., RAND> hands in and gets back.  row: the robot's row of the params buffer (NULL = not bound),
+// suspend: apply the row instead of drawing.  a, b: the lane's two words of the new episode's row (words lane and 16 + lane), which the
+// caller stores at the end of its kernel, behind every load (store_rand_row)
+struct RandRow {
+  const float* row = nullptr;
+  bool suspend = false;
+  float a = 0.0f, b = 0.0f;
+};
 static_assert(sizeof(orr_sensor_noise) == 20, "the sensor variants read it as five words");
 // The three deviations of orr_sensor_noise that have a consumer, wave-uniform (one setting per handle): motor angle, base rpy, base rpy
 // rate.  All zero in every variant but the sensor ones, whose code for them is compiled out

@@ -1,6 +1,6 @@
 // orr_env_kernels.h -- the two env kernels (orr_reset_kernel, orr_step_kernel) and their launchers, as templates.
 //
-// Included by the nine translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
+// Included by the ten translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
 // several: DESIGN.md section 3).  orr_kernels.hip: the default kernels + the C-ABI, instruction-level-parallelism scheduler (one wave per
 // SIMD, ~300 registers, nothing to hide latency but the wave's own independent instructions).  orr_kernels_w2.hip: the
 // two-waves-per-SIMD step kernel, its own flags.  orr_kernels_anchor.hip: the friction-anchor variants.  orr_kernels_multiclip.hip:
@@ -9,6 +9,7 @@
 // orr_kernels_contacts.hip: the variants that also sum the sub-steps' foot contact impulses (orr_bind_contact_outputs).
 // orr_kernels_actuator.hip: the variants that clip the motor torques and keep per-motor torque / work accumulators (orr_set_torque_limits,
 // orr_bind_actuator_outputs).  orr_kernels_sensor.hip: the variants whose sensor readings carry Gaussian noise (orr_set_sensor_noise).
+// orr_kernels_randomizer.hip: the variants whose resets run the table-driven randomiser (orr_set_randomizer, orr_bind_randomizer_params).
 // An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
 // per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
 // template` only (bottom of this file).
@@ -151,6 +152,32 @@ __global__ __launch_bounds__(64) void orr_sensor_reset_kernel(KParams P, const u
     for (int i = lane; i < ORR_OBS_DIM; i += kLanes) obs_out[(size_t)robot * ORR_OBS_DIM + i] = obs[i];
 }
 
+// The reset of the randomiser variants (orr_kernels_randomizer.hip; orr_set_randomizer, orr_bind_randomizer_params):
+// orr_sensor_reset_kernel with the table-driven stage 4b and the params row.  Suspended, the row's load is issued inside
+// reset_robot_state with its first loads; otherwise the new row is stored here, with the record.  A kernel of its own for the same
+// reason as orr_sensor_reset_kernel
+template <bool CLIPS = true>
+__global__ __launch_bounds__(64) void orr_randomizer_reset_kernel(KParams P, const uint8_t* mask, float* obs_out, const float* uniforms) {
+  ORR_PROLOGUE();
+  const bool valid = in_range && !(mask && !mask[robot]);
+  load_robot(P, rec, S, lane);
+  const long long total = P.counters[ORR_CNT_TOTAL_STEP_COUNT];
+  const ResetConst RC = load_reset_const(P, S, lane);
+  const SensorNoise SN = load_sensor_noise(P);
+  RandRow RR = load_rand_row(P, robot);
+  float clip_change = 0.0f;
+  const uint32_t ep = reset_robot_state<CLIPS, true, true, true>(P, S, lane, total, RC, &clip_change, uniforms ? uniforms + (size_t)robot * 28 : nullptr, SN, &RR);
+  build_obs<true, true>(P, rec, S, lane, obs, ep, 0u, SN);
+  WSYNC();
+  store_reset_extras<CLIPS>(rec, S, lane, valid, clip_change);
+  store_rand_row(P, RR, lane, valid);
+  store_robot(rec, S, lane, valid);
+  if (valid)      // a new episode: no cached contact points (as orr_reset_kernel)
+    for (int i = lane; i < ORR_OFFEND_ANCHOR_VALID - ORR_OFF_ANCHOR + 1; i += kLanes) rec[O(ANCHOR) + i] = 0.0f;
+  if (obs_out && valid)
+    for (int i = lane; i < ORR_OBS_DIM; i += kLanes) obs_out[(size_t)robot * ORR_OBS_DIM + i] = obs[i];
+}
+
 // mode 0: full env step.  mode 1 (debug / parity of row C): nsub physics sub-steps with the given
 // motor torques (actions = torques), no robot or task logic.  mode 2 (parity of everything BUT row C): a full env step in
 // which the physics sub-step is replaced by the recorded states of ReplayArgs, the end-effector reward reads recorded link
@@ -203,6 +230,10 @@ __global__ __launch_bounds__(64) void orr_sensor_reset_kernel(KParams P, const u
 // handle).  The filter history's initial value, the sensor histories' readings and the rpy that the target observation's heading is
 // formed from are noisy too (sensors_push_noisy, target_obs<.., true>, reset_robot_state<.., true>): draw rule in
 // include/openroborl_hip.h, orr_set_sensor_noise
+// RAND = MODE & kModeRandomizer (orr_kernels_randomizer.hip; on top of the two sensor variants - supersets - one wave per SIMD whatever
+// the batch size): the inline auto-reset runs the table-driven randomiser (reset_robot_state<.., RAND>; orr_set_randomizer) and writes
+// or, suspended, applies the robot's row of the params buffer (orr_bind_randomizer_params).  Nothing in front of the episode's end: the
+// buffer's address and the suspend switch are read at the start (scalars), the row's store comes with the record's
 template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false, bool NOISE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
@@ -215,6 +246,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   static_assert(!ACT || TERMS, "the actuator variants are supersets: instantiated with the reward terms only");
   constexpr bool SENS = (MODE & kModeSensor) != 0;
   static_assert(!SENS || (ACT && NOISE), "the sensor variants are supersets: instantiated on top of the actuator variants only");
+  constexpr bool RAND = (MODE & kModeRandomizer) != 0;
+  static_assert(!RAND || SENS, "the randomiser variants are supersets: instantiated on top of the sensor variants only");
   ORR_PROLOGUE();
   const bool valid = in_range;
   const orr_config& c = P.cfg;
@@ -231,6 +264,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     contacts_bound = P.tab->contact_out != nullptr;
     act_bound = P.tab->act_out != nullptr;
   }
+  RandRow RR;   // RAND: the robot's row of the params buffer (wave-uniform address and switch)
+  if constexpr (RAND) RR = load_rand_row(P, robot);
   // CLIPS: the motion time of the next clip change (behind the ring, never staged): read at the start, first used after the sub-steps
   float clip_change = 0.0f;
   if constexpr (CLIPS) clip_change = rec[O(CLIP_CHANGE_TIME)];
@@ -669,7 +704,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     WSYNC();
     if (c.flags & ORR_FLAG_AUTO_RESET) {
       PT(31);
-      obs_episode = reset_robot_state<CLIPS, NOISE, SENS>(P, S, lane, total_snapshot, RC, &clip_change, nullptr, SN);
+      if constexpr (RAND) obs_episode = reset_robot_state<CLIPS, NOISE, SENS, true>(P, S, lane, total_snapshot, RC, &clip_change, nullptr, SN, &RR);
+      else obs_episode = reset_robot_state<CLIPS, NOISE, SENS>(P, S, lane, total_snapshot, RC, &clip_change, nullptr, SN);
       noise_i = 0u;
       was_reset = true;
       if constexpr (ANCHOR) AS = AnchorState{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0};   // a new episode: no cached contact points
@@ -705,6 +741,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     }
   }
   if (was_reset) store_reset_extras<CLIPS>(rec, S, lane, valid, clip_change);   // ring entries #1 / #2 of the new episode (still in LDS)
+  if constexpr (RAND) { if (was_reset) store_rand_row(P, RR, lane, valid); }    // and its row of the params buffer
   store_robot(rec, S, lane, valid);
   store_anchor();
   if (valid) {   // the observation, in 16-byte pieces like the record (40 per robot)
@@ -947,6 +984,11 @@ hipError_t launch_sensor_reset(const KParams& P, int waves, hipStream_t stream, 
   hipLaunchKernelGGL((orr_sensor_reset_kernel<CLIPS>), dim3(waves), dim3(64), 0, stream, P, mask, obs, uniforms);
   return hipGetLastError();
 }
+template <bool CLIPS>
+hipError_t launch_randomizer_reset(const KParams& P, int waves, hipStream_t stream, const uint8_t* mask, float* obs, const float* uniforms) {
+  hipLaunchKernelGGL((orr_randomizer_reset_kernel<CLIPS>), dim3(waves), dim3(64), 0, stream, P, mask, obs, uniforms);
+  return hipGetLastError();
+}
 
 extern template StepLaunch launch_step<0, 2, false, false>;                  // orr_kernels_w2.hip
 extern template StepLaunch launch_step<0, 1, true, false>;                   // orr_kernels_anchor.hip: env step,
@@ -966,7 +1008,10 @@ extern template StepLaunch launch_step<kModeActuator | kModeContacts | kModeTerm
 extern template StepLaunch launch_step<kModeActuator | kModeTerms | 2, 1, false, true, true>;                   //   its parity replay (resets: the noise unit's; no debug physics)
 extern template StepLaunch launch_step<kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>;   // orr_kernels_sensor.hip: env step with sensor noise,
 extern template StepLaunch launch_step<kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>;                   //   its parity replay,
-extern template ResetLaunch launch_sensor_reset<true>;                                                                       //   reset (and its parity replay)
+extern template ResetLaunch launch_sensor_reset<true>;
+extern template StepLaunch launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>;   // orr_kernels_randomizer.hip: env step with the table-driven randomiser,
+extern template StepLaunch launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>;                   //   its parity replay,
+extern template ResetLaunch launch_randomizer_reset<true>;                                                                                     //   reset (and its parity replay)                                                                       //   reset (and its parity replay)
 
 #ifdef ORR_STAGE_DUMP
 // the stage dump: instantiated in BOTH step units (orr_kernels.hip: WPE 1, orr_kernels_w2.hip: WPE 2), which compile different forms of

@@ -93,6 +93,8 @@ struct orr_handle {
   uint32_t limit_types;       // orr_set_torque_limits: bit t = robot type t has a finite torque limit on some motor
   bool act_on;                // orr_bind_actuator_outputs.  With either, env step and parity replay run the actuator variants (orr_kernels_actuator.hip), the resets the noise variant
   bool sensor_on;             // orr_set_sensor_noise: a motor-angle, rpy or rpy-rate deviation above 0: env step, parity replays and resets run the sensor variants (orr_kernels_sensor.hip)
+  bool rand_on;               // orr_set_randomizer with a table (not NULL), or
+  bool rand_bound;            // orr_bind_randomizer_params with a buffer: env step, parity replays and resets run the randomiser variants (orr_kernels_randomizer.hip)
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -133,6 +135,18 @@ static double dec7(float x) {
   return (float)d == x ? d : (double)x;
 }
 
+// The randomiser's parameters by name, in enum order, and the six ranges that reset_robot_state has built in
+static const char* const g_rand_names[ORR_RAND_NUM_PARAMS] = {"base mass", "global motor strength", "inertia", "joint friction", "latency",
+                                                              "lateral friction", "leg weaken", "mass", "motor strength", "single leg weaken"};
+static orr_randomizer builtin_randomizer() {
+  orr_randomizer r;
+  memset(&r, 0, sizeof(r));
+  const struct { int p; float lo, hi; } six[] = {{ORR_RAND_INERTIA, 0.5f, 1.5f}, {ORR_RAND_JOINT_FRICTION, 0.0f, 0.05f}, {ORR_RAND_LATENCY, 0.0f, 0.04f},
+                                                 {ORR_RAND_LATERAL_FRICTION, 0.5f, 1.25f}, {ORR_RAND_MASS, 0.8f, 1.2f}, {ORR_RAND_MOTOR_STRENGTH, 0.8f, 1.2f}};
+  for (const auto& e : six) { r.enabled[e.p] = 1; r.lo[e.p] = e.lo; r.hi[e.p] = e.hi; }
+  return r;
+}
+
 extern "C" {
 
 #ifndef ORR_SOURCE_HASH
@@ -153,6 +167,7 @@ int32_t orr_sizeof_config(void) { return (int32_t)sizeof(orr_config); }
 int32_t orr_sizeof_model(void) { return (int32_t)sizeof(orr_model); }
 int32_t orr_sizeof_task_noise(void) { return (int32_t)sizeof(orr_task_noise); }
 int32_t orr_sizeof_sensor_noise(void) { return (int32_t)sizeof(orr_sensor_noise); }
+int32_t orr_sizeof_randomizer(void) { return (int32_t)sizeof(orr_randomizer); }
 
 int32_t orr_create(const orr_config* cfg, orr_handle** out) {
   if (!cfg || !out) return fail(-1, "orr_create: null argument");
@@ -193,6 +208,9 @@ int32_t orr_create(const orr_config* cfg, orr_handle** out) {
   for (int t = 0; t < ORR_MAX_ROBOT_TYPES; t++)
     for (int i = 0; i < 12; i++) h->tab_host.torque_limit[t][i] = INFINITY;   // no torque limit
   e = hipMemcpy(h->tab_dev->torque_limit, h->tab_host.torque_limit, sizeof(h->tab_host.torque_limit), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemcpy", e); }
+  h->tab_host.rnd = builtin_randomizer();   // what a bound params buffer applies until orr_set_randomizer gives a table
+  e = hipMemcpy(&h->tab_dev->rnd, &h->tab_host.rnd, sizeof(h->tab_host.rnd), hipMemcpyHostToDevice);
   if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemcpy", e); }
   hipEventCreate(&h->ev0);
   hipEventCreate(&h->ev1);
@@ -489,6 +507,52 @@ int32_t orr_set_sensor_noise(orr_handle* h, const orr_sensor_noise* noise_host) 
   return 0;
 }
 
+int32_t orr_set_randomizer(orr_handle* h, const orr_randomizer* host) {
+  if (!h) return fail(-1, "orr_set_randomizer: null handle");
+  orr_randomizer r = host ? *host : builtin_randomizer();
+  // the ring reader (ctrl_obs / ring_prefetch, orr_robot_io.h) blends the entries n = int(latency / sim_dt) and n + 1 back from the
+  // newest one, and clamps to the oldest where n + 1 >= the ring's length: exact while n + 1 <= ORR_RING_DEPTH - 1
+  const float latency_max = (float)(ORR_RING_DEPTH - 2) * h->cfg.sim_dt;
+  char m[200];
+  for (int p = 0; p < ORR_RAND_NUM_PARAMS; p++) {
+    r.enabled[p] = r.enabled[p] != 0;
+    if (!r.enabled[p]) { r.lo[p] = r.hi[p] = 0.0f; continue; }   // not read: kept as zeros
+    const float lo = r.lo[p], hi = r.hi[p];
+    const bool positive = p == ORR_RAND_BASE_MASS || p == ORR_RAND_MASS || p == ORR_RAND_INERTIA;
+    const char* why = nullptr;
+    if (!(fabsf(lo) < INFINITY && fabsf(hi) < INFINITY)) why = "bounds must be finite numbers";     // NaN fails the comparison
+    else if (lo > hi) why = "lo > hi";
+    else if (positive && !(lo > 0.0f)) why = "lo must be > 0 (a ratio of a mass or an inertia)";
+    else if (lo < 0.0f) why = "lo must be >= 0";
+    else if (p == ORR_RAND_LATENCY && hi > latency_max) why = "hi is beyond what the latency ring holds, (ORR_RING_DEPTH - 2) * sim_dt";
+    if (why) {
+      snprintf(m, sizeof(m), "orr_set_randomizer: %s: %s", g_rand_names[p], why);
+      return fail(-1, m);
+    }
+  }
+  if (host && h->anchor_types)
+    return fail(-1, "orr_set_randomizer: friction anchors (orr_model::friction_anchor) and a randomiser table cannot be combined");
+  // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->rnd, &r, sizeof(r), hipMemcpyHostToDevice), "orr_set_randomizer: hipMemcpy");
+  h->tab_host.rnd = r;
+  h->rand_on = host != nullptr;
+  return 0;
+}
+
+int32_t orr_bind_randomizer_params(orr_handle* h, float* params_dev, int32_t suspend) {
+  if (!h) return fail(-1, "orr_bind_randomizer_params: null handle");
+  if (((uintptr_t)params_dev & 15u) != 0) return fail(-1, "orr_bind_randomizer_params: params_dev must be 16-byte aligned (rows of ORR_RAND_ROW floats)");
+  if (params_dev && h->anchor_types)
+    return fail(-1, "orr_bind_randomizer_params: friction anchors (orr_model::friction_anchor) and a randomiser params buffer cannot be combined");
+  struct { float* p; int s; } v = {params_dev, params_dev && suspend ? 1 : 0};
+  static_assert(offsetof(DevTables, rand_suspend) == offsetof(DevTables, rand_params) + sizeof(float*), "copied as a pointer and the word behind it");
+  HIPCHK(hipMemcpy(&h->tab_dev->rand_params, &v, sizeof(float*) + sizeof(int), hipMemcpyHostToDevice), "orr_bind_randomizer_params: hipMemcpy");
+  h->tab_host.rand_params = v.p;
+  h->tab_host.rand_suspend = v.s;
+  h->rand_bound = params_dev != nullptr;
+  return 0;
+}
+
 int32_t orr_bind(orr_handle* h, void* state_dev, int64_t* counters_dev, float* ep_log_dev, int32_t ep_log_capacity) {
   if (!h || !state_dev || !counters_dev) return fail(-1, "orr_bind: null argument (state and counters are required)");
   if (((uintptr_t)state_dev & 15u) != 0) return fail(-1, "orr_bind: the state buffer must be 16-byte aligned (records move in 16-byte pieces)");
@@ -524,7 +588,8 @@ static KParams make_params(const orr_handle* h) {
 static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1) / kRPW; }
 
 // Which instantiation of the kernels a launch runs.  `clip_types` = the feature mask that selects the clip-set variants: multiclip_types
-// for orr_step / orr_reset, switch_types for the parity replays.  Sensor noise comes first (env step, parity replays and resets: supersets
+// for orr_step / orr_reset, switch_types for the parity replays.  A randomiser table or params buffer comes first of all (env step,
+// parity replays and resets: supersets of the sensor variants; friction anchors are refused).  Then sensor noise comes first (env step, parity replays and resets: supersets
 // of everything below but the friction anchors, which are refused).  Then torque limits and actuator outputs come first (env step, parity replay
 // and the resets, which run the noise variant; the two step variants are supersets that serve the reward terms and - the env step - the
 // contact outputs too, whichever are bound; friction anchors are refused), then the contact outputs (`contacts` = the entry point has a
@@ -534,7 +599,7 @@ static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1)
 // clip sets (both refuse friction anchors: kRefused, the message starts with the entry point's name `who`), then friction anchors, then
 // the batch size; only the env step has a two-wave and only the env step and the debug physics have an anchor instantiation, every other
 // entry point runs its default one instead.
-enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts, kActuator, kSensor };
+enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts, kActuator, kSensor, kRandomizer };
 static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {   // (a model with anchors set after orr_bind_contact_outputs)
   if (!(h->contacts_on && h->anchor_types)) return false;
   char m[256];
@@ -543,6 +608,15 @@ static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {
   return true;
 }
 static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who, bool contacts = true) {
+  if (h->rand_on || h->rand_bound) {   // ahead of sensor noise: supersets of its variants
+    if (h->anchor_types) {   // (a model with anchors set after orr_set_randomizer / orr_bind_randomizer_params)
+      char m[256];
+      snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and the randomiser (orr_set_randomizer, orr_bind_randomizer_params) cannot be combined", who);
+      fail(-1, m);
+      return kRefused;
+    }
+    return kRandomizer;
+  }
   if (h->sensor_on) {
     if (h->anchor_types) {   // (a model with anchors set after orr_set_sensor_noise)
       char m[256];
@@ -592,7 +666,9 @@ int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* 
   if (!h || !h->state) return fail(-1, "orr_reset: handle not bound");
   const Variant v = variant_of(h, h->multiclip_types, "orr_reset");
   if (v == kRefused) return -1;
-  if (v == kSensor)   // sensor noise: three noisy readings per history, a noisy heading of the target observation
+  if (v == kRandomizer)   // a randomiser table or a params buffer: the sensor reset with the table-driven randomiser
+    HIPCHK((launch_randomizer_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (randomiser)");
+  else if (v == kSensor)   // sensor noise: three noisy readings per history, a noisy heading of the target observation
     HIPCHK((launch_sensor_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (sensor noise)");
   else if (v == kNoise || v == kTerms || v == kContacts || v == kActuator)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (task noise)");
@@ -611,6 +687,12 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
   HIPCHK((launch_step<0, WPE, ANCHOR, CLIPS, NOISE>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{})), msg)
   switch (variant_of(h, h->multiclip_types, "orr_step")) {
     case kRefused: return -1;
+    case kRandomizer:   // one wave per SIMD, any batch size; the superset that also serves sensor noise, torque limits and every output binding
+      HIPCHK((launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream,
+                                                                                                                                actions_dev, obs_dev, reward_dev, done_dev, 0,
+                                                                                                                                ReplayArgs{})),
+             "orr_step: launch (randomiser)");
+      break;
     case kSensor:   // one wave per SIMD, any batch size; the superset that also serves torque limits and every output binding
       HIPCHK((launch_step<kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev,
                                                                                                               obs_dev, reward_dev, done_dev, 0, ReplayArgs{})),
@@ -687,7 +769,10 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
   const ReplayArgs rp{traj_dev, eff_dev, fall_dev, tau_out_dev, nullptr};
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_step", false);   // no contact variant: contact_out is left alone
   if (v == kRefused) return -1;
-  if (v == kSensor)   // sensor noise: the actuator replay with noisy readings (their draws come from the Philox stream)
+  if (v == kRandomizer)   // the sensor replay of a handle with a randomiser table or params buffer (no reset inside: the same computation)
+    HIPCHK((launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev,
+                                                                                                              reward_dev, done_dev, 0, rp)), "orr_debug_replay_step: launch (randomiser)");
+  else if (v == kSensor)   // sensor noise: the actuator replay with noisy readings (their draws come from the Philox stream)
     HIPCHK((launch_step<kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev,
                                                                                             done_dev, 0, rp)), "orr_debug_replay_step: launch (sensor noise)");
   else if (v == kActuator)   // torque limits / actuator outputs: the noise replay that clips and accumulates the torques (and writes the terms where bound)
@@ -711,7 +796,9 @@ int32_t orr_debug_replay_reset(orr_handle* h, const float* uniforms_dev, float* 
   if (!h || !h->state || !uniforms_dev) return fail(-1, "orr_debug_replay_reset: bad argument");
   const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_reset", false);
   if (v == kRefused) return -1;
-  if (v == kSensor)   // sensor noise: the sensor reset (draws 0..27 from uniforms_dev; everything else from the Philox stream)
+  if (v == kRandomizer)   // the randomiser reset (draws 0..27 from uniforms_dev; the two newer blocks and everything else from the Philox stream)
+    HIPCHK((launch_randomizer_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (randomiser)");
+  else if (v == kSensor)   // sensor noise: the sensor reset (draws 0..27 from uniforms_dev; everything else from the Philox stream)
     HIPCHK((launch_sensor_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (sensor noise)");
   else if (v == kNoise || v == kTerms || v == kActuator)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
     HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (task noise)");

@@ -200,6 +200,9 @@ __device__ __forceinline__ int target_frame_steps(const orr_config& c, int lane)
 
 // Philox blocks of the task noise (orr_set_task_noise; below 2^30: a draw index is 4 * block + word, 32 bits)
 constexpr uint32_t kNoiseResetBlock = 0x20000000u, kNoiseHeadingBlock = 0x30000000u;
+// Philox blocks of the randomiser's four newer parameters (orr_set_randomizer): block 0x40000000 = base mass, global motor strength, the
+// weakened leg, leg weaken's ratio; block 0x40000001 word 0 = single leg weaken
+constexpr uint32_t kRandBlock = 0x40000000u;
 // Philox blocks of the sensor noise (orr_set_sensor_noise): 0x10000000 + (i << 9) + (slot << 4) + lane, i = 0 for a reset of the episode,
 // 1 + s for the step whose env-step counter before it is s.  Slots 0..16: the sub-steps' motor-angle readings (lane = motor; sub-step
 // 2 slot: words 0, 1, sub-step 2 slot + 1: words 2, 3; z0 = the command clip's reading, z1 = the interpolation start's), 17: the sensor
@@ -524,9 +527,14 @@ __device__ __forceinline__ float* reset_entry1(Shared& S) { return S.ph.end.red;
 __device__ __forceinline__ float* reset_entry2(Shared& S) { return S.ph.end.red + 56; }   // touches red[]
 // SENS (the sensor variants, orr_kernels_sensor.hip; always with NOISE): stage 3 fills the sensor histories with three separate noisy
 // readings (sensors_push_noisy; i = 0 of the new episode's stream)
-template <bool CLIPS = false, bool NOISE = false, bool SENS = false>
+// RAND (the randomiser variants, orr_kernels_randomizer.hip; always with SENS): stage 4b is table-driven (orr_set_randomizer: ten
+// parameters, each enabled or not, with its own range) and controllable (orr_bind_randomizer_params: RR->row is the robot's row of the
+// params buffer; the lane's two words of the new episode's row come back in RR->a / RR->b for the caller to store with the record, or,
+// suspended, the row is loaded here with the reset's first loads and applied instead of the draws)
+template <bool CLIPS = false, bool NOISE = false, bool SENS = false, bool RAND = false>
 __device__ static uint32_t reset_robot_state(const KParams& P, Shared& S, int lane, long long total_step_count, const ResetConst& RC,
-                                             float* clip_change, const float* uni_replay = nullptr, const SensorNoise& SN = SensorNoise{}) {
+                                             float* clip_change, const float* uni_replay = nullptr, const SensorNoise& SN = SensorNoise{},
+                                             RandRow* RR = nullptr) {
   const orr_config& c = P.cfg;
   // every reset starts a new episode = a new RNG stream (robot, episode)
   const uint32_t robot = (uint32_t)geti(S, O(ROBOT_INDEX)), ep = (uint32_t)geti(S, O(EPISODE_IDX)) + 1u;
@@ -554,7 +562,43 @@ __device__ static uint32_t reset_robot_state(const KParams& P, Shared& S, int la
     sw_min = ((gfp)&P.tab->clip_switch[type][0])[0];
     sw_max = ((gfp)&P.tab->clip_switch[type][0])[1];
   }
-  if (lane < (CLIPS ? 8 : 7)) {
+  // RAND: the handle's table - the lane's own parameter (that of draw `lane`, the existing loop's mapping) and the five that every
+  // lane needs (motor strength, global motor strength, leg weaken, single leg weaken for the STRENGTH word that lanes 0..11 own, base
+  // mass for lane 12's MASS_RATIO[0]) - and, suspended, the robot's row: all in flight while the Philox blocks are evaluated.  The two
+  // new blocks' words park in xb[0..7] = ee[36..43], behind the noise stage's 36 words (ee: see nz below)
+  float* xb = &S.ph.end.ee[0][0][0] + 36;
+  int rn_en = 0, rn_en_u[5] = {0, 0, 0, 0, 0};
+  float rn_lo = 0.0f, rn_hi = 0.0f, rn_lo_u[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, rn_hi_u[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  float row_a = 0.0f, row_ms = 0.0f, row_x[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // suspended: row words lane, 14 + lane, 26..30
+  constexpr int kRandU[5] = {ORR_RAND_MOTOR_STRENGTH, ORR_RAND_GLOBAL_MOTOR_STRENGTH, ORR_RAND_LEG_WEAKEN, ORR_RAND_SINGLE_LEG_WEAKEN, ORR_RAND_BASE_MASS};
+  if constexpr (RAND) {
+    static_assert(sizeof(S.ph.end.ee) >= 44 * sizeof(float), "36 words of the noise stage + two blocks");
+    typedef const int __attribute__((address_space(1)))* gip;
+    typedef const float __attribute__((address_space(1)))* gfp;
+    const gip en = (gip)&P.tab->rnd.enabled[0];
+    const gfp lo = (gfp)&P.tab->rnd.lo[0], hi = (gfp)&P.tab->rnd.hi[0];
+    const int pa = lane < 2 ? ORR_RAND_INERTIA : (lane < 10 ? ORR_RAND_JOINT_FRICTION : (lane == 10 ? ORR_RAND_LATENCY : (lane == 11 ? ORR_RAND_LATERAL_FRICTION
+                   : (lane < 14 ? ORR_RAND_MASS : ORR_RAND_MOTOR_STRENGTH))));
+    rn_en = en[pa]; rn_lo = lo[pa]; rn_hi = hi[pa];
+#pragma unroll
+    for (int k = 0; k < 5; k++) { rn_en_u[k] = en[kRandU[k]]; rn_lo_u[k] = lo[kRandU[k]]; rn_hi_u[k] = hi[kRandU[k]]; }
+    if (RR->suspend) {   // wave-uniform.  Words 14 + lane of lanes 12..15 are not motor-strength draws: they repeat word 31
+      const gfp r = (gfp)RR->row;
+      row_a = r[lane]; row_ms = r[lane < 12 ? 14 + lane : ORR_RAND_ROW - 1];
+#pragma unroll
+      for (int k = 0; k < 5; k++) row_x[k] = r[26 + k];
+    }
+  }
+  if constexpr (RAND) {   // blocks 0..7 as below and, in lanes 8 and 9, blocks 0x40000000 and 0x40000001 (always from Philox)
+    static_assert(CLIPS, "the randomiser variants hold the clip-set code");
+    if (lane < 10) {
+      float u4[4];
+      if (uni_replay && lane < 7) { u4[0] = uni_replay[4 * lane]; u4[1] = uni_replay[4 * lane + 1]; u4[2] = uni_replay[4 * lane + 2]; u4[3] = uni_replay[4 * lane + 3]; }
+      else philox_block(c.seed, robot, ep, lane < 8 ? (uint32_t)lane : kRandBlock + (uint32_t)(lane - 8), u4);
+      float* dst = lane < 8 ? draws + 4 * lane : xb + 4 * (lane - 8);
+      dst[0] = u4[0]; dst[1] = u4[1]; dst[2] = u4[2]; dst[3] = u4[3];
+    }
+  } else if (lane < (CLIPS ? 8 : 7)) {
     float u4[4];
     if (uni_replay && (!CLIPS || lane < 7)) { u4[0] = uni_replay[4 * lane]; u4[1] = uni_replay[4 * lane + 1]; u4[2] = uni_replay[4 * lane + 2]; u4[3] = uni_replay[4 * lane + 3]; }
     else philox_block(c.seed, robot, ep, (uint32_t)lane, u4);
@@ -661,7 +705,42 @@ __device__ static uint32_t reset_robot_state(const KParams& P, Shared& S, int la
   PT(18);
   // 4b. randomiser (controllable_env_randomizer_from_config.py:92-122), sorted-name draw order:
   //    inertia 2 | joint friction 8 | latency 1 | lateral friction 1 | mass 2 | motor strength 12
-  if (c.flags & ORR_FLAG_RANDOMIZER) {
+  if constexpr (RAND) {
+    // Table-driven (orr_set_randomizer): value = fmaf(u, hi - lo, lo); a disabled parameter leaves its words alone; the reference's
+    // application order (sorted by name) decides where two parameters write the same word.  ONE lane owns each word and picks the last
+    // enabled writer's value in registers - no order of LDS stores by different lanes to lean on: lanes 0..11 their STRENGTH word
+    // (single leg weaken over motor strength over leg weaken over global motor strength), lanes 0..13 the word of draw `lane` as in the
+    // loop below (lane 12: mass over base mass).  u comes from the draws or, suspended, from the row
+    if (c.flags & ORR_FLAG_RANDOMIZER) {
+      const bool susp = RR->suspend;
+      const float u_a = susp ? row_a : draws[lane], u_ms = susp ? row_ms : draws[lane < 12 ? 14 + lane : 0];
+      const float u_g = susp ? row_x[1] : xb[1], u_lw = susp ? row_x[3] : xb[3], u_s = susp ? row_x[4] : xb[4], u_bm = susp ? row_x[0] : xb[0];
+      // the weakened leg: (m * 4) >> 24, m = the draw's 24-bit integer (as the clip draw)
+      const float f_leg = susp ? row_x[2] : (float)((((uint32_t)(xb[2] * 16777216.0f)) * 4u) >> 24);
+      // the new episode's row, words lane and 16 + lane (the caller stores it; not while suspended)
+      RR->a = u_a;
+      RR->b = lane < 10 ? draws[16 + lane]
+                        : (lane == 10 ? u_bm : (lane == 11 ? u_g : (lane == 12 ? f_leg : (lane == 13 ? u_lw : (lane == 14 ? u_s : 0.0f)))));
+      const float v_a = fmaf(u_a, rn_hi - rn_lo, rn_lo);
+      const float v_ms = fmaf(u_ms, rn_hi_u[0] - rn_lo_u[0], rn_lo_u[0]), v_g = fmaf(u_g, rn_hi_u[1] - rn_lo_u[1], rn_lo_u[1]);
+      const float v_lw = fmaf(u_lw, rn_hi_u[2] - rn_lo_u[2], rn_lo_u[2]), v_s = fmaf(u_s, rn_hi_u[3] - rn_lo_u[3], rn_lo_u[3]);
+      const float v_bm = fmaf(u_bm, rn_hi_u[4] - rn_lo_u[4], rn_lo_u[4]);
+      if (lane < 12) {
+        float v = v_g;
+        if (rn_en_u[2]) v = (float)(lane / 3) == f_leg ? v_lw : 1.0f;
+        if (rn_en_u[0]) v = v_ms;
+        if (rn_en_u[3]) v = lane < 3 ? v_s : 1.0f;
+        if (rn_en_u[0] | rn_en_u[1] | rn_en_u[2] | rn_en_u[3]) S.s[O(STRENGTH) + lane] = v;
+      }
+      if (lane < 2) { if (rn_en) S.s[O(INERTIA_RATIO) + lane] = v_a; }
+      else if (lane < 10) { if (rn_en && (lane & 1) == 0) S.s[O(KNEE_FRICTION) + ((lane - 2) >> 1)] = v_a; }
+      else if (lane == 10) { if (rn_en) S.s[O(LATENCY)] = v_a; }
+      else if (lane == 11) { if (rn_en) S.s[O(FOOT_MU)] = v_a; }
+      else if (lane == 12) { if (rn_en | rn_en_u[4]) S.s[O(MASS_RATIO)] = rn_en ? v_a : v_bm; }
+      else if (lane == 13) { if (rn_en) S.s[O(MASS_RATIO) + 1] = v_a; }
+      WSYNC();
+    }
+  } else if (c.flags & ORR_FLAG_RANDOMIZER) {
     for (int i = lane; i < 26; i += kLanes) {
       const float u = draws[i];
       if (i < 2) S.s[O(INERTIA_RATIO) + i] = 0.5f + u * 1.0f;
@@ -752,6 +831,27 @@ __device__ __forceinline__ void store_reset_extras(float* rec, Shared& S, int la
   store_ring_entry(rec, lane, valid, 0, reset_entry1(S));
   store_ring_entry(rec, lane, valid, 1, reset_entry2(S));
   if constexpr (CLIPS) { if (valid && lane == 0) rec[O(CLIP_CHANGE_TIME)] = clip_change; }
+}
+
+// RAND: the params buffer of the handle (orr_bind_randomizer_params), the same in every lane: `robot`'s row, and whether resets apply
+// it instead of drawing.  A padding lane group shadows robot 0's row and never stores
+__device__ __forceinline__ RandRow load_rand_row(const KParams& P, int robot) {
+  const unsigned long long p = *(const unsigned long long __attribute__((address_space(1)))*)&P.tab->rand_params;
+  const int s = *(const int __attribute__((address_space(1)))*)&P.tab->rand_suspend;
+  const unsigned int plo = __builtin_amdgcn_readfirstlane((unsigned int)p), phi = __builtin_amdgcn_readfirstlane((unsigned int)(p >> 32));
+  float* const base = reinterpret_cast<float*>(((unsigned long long)phi << 32) | plo);
+  RandRow RR;
+  RR.row = base ? base + (size_t)robot * ORR_RAND_ROW : nullptr;
+  RR.suspend = base != nullptr && __builtin_amdgcn_readfirstlane(s) != 0;
+  return RR;
+}
+// The new episode's row, words lane and 16 + lane: with the record's stores, behind every load.  Not while suspended (the caller owns
+// the rows), not without ORR_FLAG_RANDOMIZER (nothing was drawn)
+__device__ __forceinline__ void store_rand_row(const KParams& P, const RandRow& RR, int lane, bool valid) {
+  if (valid && RR.row && !RR.suspend && (P.cfg.flags & ORR_FLAG_RANDOMIZER)) {
+    float __attribute__((address_space(1)))* const r = (float __attribute__((address_space(1)))*)RR.row;
+    r[lane] = RR.a; r[16 + lane] = RR.b;
+  }
 }
 
 // 7. observation = sensor histories + target observation (quadruped_gym_env.py:100-102; wrapper_env.py:101-105, 109-125), for the

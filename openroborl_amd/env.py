@@ -320,6 +320,131 @@ def sensor_noise_on(spec):
     return spec.motor_angle_std > 0.0 or spec.base_rpy_std > 0.0 or spec.base_rpy_rate_std > 0.0
 
 
+# ---- domain randomisation (orr_set_randomizer, orr_bind_randomizer_params; ControllableEnvRandomizerFromConfig) ----------------------
+RAND_NOOP_NAMES = ("battery", "motor friction")       # accepted and ignored: no-ops in the reference (minitaur_motor.py:86-102)
+RAND_REFUSED_NAMES = {"control step": "every robot of a batch takes the same number of sub-steps per step",
+                      "individual mass": "the engine scales masses by two ratios (base, legs), not per link",
+                      "individual inertia": "the engine scales inertias by two ratios (base, legs), not per link",
+                      "restitution": "the contact model has no restitution"}
+RAND_POSITIVE_NAMES = ("base mass", "inertia", "mass")   # ratios that scale a mass or an inertia: lo > 0
+# row words of the params buffer (include/openroborl_hip.h, orr_bind_randomizer_params) by parameter
+RAND_ROW_WORDS = {"inertia": slice(0, 2), "joint friction": slice(2, 10), "latency": slice(10, 11), "lateral friction": slice(11, 12),
+                  "mass": slice(12, 14), "motor strength": slice(14, 26), "base mass": slice(26, 27), "global motor strength": slice(27, 28),
+                  "leg weaken": slice(28, 30), "single leg weaken": slice(30, 31)}
+RAND_LEG_WORD = 28                                       # the weakened leg, as a float 0..3: not a draw in [0, 1)
+
+
+def randomizer_latency_max(sim_dt=0.001):
+    """The largest latency bound orr_set_randomizer accepts, in float32 as the C-ABI computes it: the ring reader blends the entries
+    int(latency / sim_dt) and int(latency / sim_dt) + 1 back from the newest, and a ring of RING_DEPTH entries holds those while
+    int(latency / sim_dt) + 1 <= RING_DEPTH - 1."""
+    return float(np.float32(_abi.RING_DEPTH - 2) * np.float32(sim_dt))
+
+
+def randomizer_spec(config, sim_dt=0.001):
+    """The reference's randomiser configuration -> the orr_randomizer struct.  config: None (the built-in six ranges: what
+    orr_set_randomizer(NULL) restores), "all_params" (the reference's dictionary of that name: the same six, as a table), or a dict of
+    name -> [lo, hi] with the reference's names (_abi.RAND_PARAM_NAMES; "battery" and "motor friction" are accepted and ignored).
+    ValueError, naming the entry, on "control step", "individual mass", "individual inertia", "restitution", an unknown name, a
+    four-entry rejection range and anything the C-ABI would refuse."""
+    if config is None or (isinstance(config, str) and config == "all_params"):
+        config = cfgmod.RANDOMIZER_ALL_PARAMS
+    if not isinstance(config, dict):
+        raise ValueError("randomizer config must be None, \"all_params\" or a dict of parameter name to [lo, hi], not %r" % (config,))
+    spec = _abi.OrrRandomizer()
+    for name, rng in config.items():
+        if name in RAND_REFUSED_NAMES:
+            raise ValueError("randomizer parameter %r is not supported: %s" % (name, RAND_REFUSED_NAMES[name]))
+        if name not in _abi.RAND_PARAM_NAMES and name not in RAND_NOOP_NAMES:
+            raise ValueError("unknown randomizer parameter %r (known: %s)" % (name, ", ".join(_abi.RAND_PARAM_NAMES + RAND_NOOP_NAMES)))
+        if isinstance(rng, (str, dict, bool, np.bool_)) or np.ndim(rng) != 1:
+            raise ValueError("randomizer parameter %r: the range must be [lo, hi], not %r" % (name, rng))
+        if len(rng) == 4:
+            raise ValueError("randomizer parameter %r: four-entry rejection ranges [lo, hi, reject_lo, reject_hi] are not supported" % (name,))
+        if len(rng) != 2:
+            raise ValueError("randomizer parameter %r: the range must be [lo, hi], not %r" % (name, rng))
+        for v in rng:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("randomizer parameter %r: the bounds must be numbers, not %r" % (name, rng))
+        lo, hi = float(np.float32(rng[0])), float(np.float32(rng[1]))    # as the device holds them
+        if not (math.isfinite(lo) and math.isfinite(hi)):
+            raise ValueError("randomizer parameter %r: the bounds must be finite numbers, not %r" % (name, rng))
+        if lo > hi:
+            raise ValueError("randomizer parameter %r: lo > hi in %r" % (name, rng))
+        if name in RAND_NOOP_NAMES:
+            continue
+        if name in RAND_POSITIVE_NAMES and not lo > 0.0:
+            raise ValueError("randomizer parameter %r: lo must be > 0 (a ratio of a mass or an inertia), not %r" % (name, rng))
+        if lo < 0.0:
+            raise ValueError("randomizer parameter %r: lo must be >= 0, not %r" % (name, rng))
+        if name == "latency" and hi > randomizer_latency_max(sim_dt):
+            raise ValueError("randomizer parameter 'latency': hi = %r is beyond what the latency ring holds, (RING_DEPTH - 2) * sim_dt = %g s"
+                             % (rng[1], randomizer_latency_max(sim_dt)))
+        p = _abi.RAND_PARAM_NAMES.index(name)
+        spec.enabled[p], spec.lo[p], spec.hi[p] = 1, lo, hi
+    return spec
+
+
+def randomizer_draw_indices():
+    """Draw indices (4 * block + word; beyond 32 bits) on the episode's stream of the 31 uniforms behind a row of the params buffer, in
+    row order: draws 0..25, then block RAND_BLOCK words 0..3 (base mass, global motor strength, the weakened leg's draw, leg weaken's
+    ratio) and block RAND_BLOCK + 1 word 0 (single leg weaken).  Row word 28 is not the draw itself but the leg made of it
+    (randomizer_row)."""
+    return np.concatenate([np.arange(26, dtype=np.int64), 4 * _abi.RAND_BLOCK + np.arange(4, dtype=np.int64),
+                           4 * (_abi.RAND_BLOCK + 1) + np.arange(1, dtype=np.int64)])
+
+
+def randomizer_row(U):
+    """The params-buffer row [..., RAND_ROW] (float64) that a reset writes for the 31 uniforms U [..., 31] of randomizer_draw_indices():
+    the draws as they are, word 28 = the weakened leg (m * 4) >> 24 with m the draw's 24-bit integer, word 31 = 0."""
+    U = np.asarray(U, dtype=np.float64)
+    row = np.zeros(U.shape[:-1] + (_abi.RAND_ROW,))
+    row[..., :31] = U
+    m = np.floor(U[..., RAND_LEG_WORD] * 16777216.0).astype(np.int64)
+    row[..., RAND_LEG_WORD] = ((m * 4) >> 24).astype(np.float64)
+    return row
+
+
+def randomizer_apply(spec, row):
+    """What a reset writes into the record for a params-buffer row [..., RAND_ROW] under the table `spec` (randomizer_spec's struct):
+    float64 predictions by the C-ABI's rule - value = lo + u (hi - lo) with the float32 bounds the device holds, a disabled parameter
+    writes nothing, parameters apply in the reference's order (sorted by name) and a later one overwrites an earlier one's words.
+    Returns a dict of record field -> array: STRENGTH [..., 12], MASS_RATIO [..., 2], INERTIA_RATIO [..., 2], KNEE_FRICTION [..., 4],
+    LATENCY [..., 1], FOOT_MU [..., 1]; NaN marks a word that no enabled parameter writes (the record keeps its value)."""
+    row = np.asarray(row, dtype=np.float64)
+    lead = row.shape[:-1]
+    out = {k: np.full(lead + (n,), np.nan) for k, n in (("STRENGTH", 12), ("MASS_RATIO", 2), ("INERTIA_RATIO", 2), ("KNEE_FRICTION", 4),
+                                                        ("LATENCY", 1), ("FOOT_MU", 1))}
+    leg = row[..., RAND_LEG_WORD]
+    for p, name in enumerate(_abi.RAND_PARAM_NAMES):        # the application order
+        if not spec.enabled[p]:
+            continue
+        lo, hi = float(spec.lo[p]), float(spec.hi[p])
+        w = row[..., RAND_ROW_WORDS[name]]
+        v = lo + (w[..., -1:] if name == "leg weaken" else w) * (hi - lo)
+        if name == "base mass":
+            out["MASS_RATIO"][..., 0:1] = v
+        elif name == "global motor strength":
+            out["STRENGTH"][...] = v
+        elif name == "inertia":
+            out["INERTIA_RATIO"][...] = v
+        elif name == "joint friction":
+            out["KNEE_FRICTION"][...] = v[..., 0::2]      # the knee joints take the even ones of the eight draws
+        elif name == "latency":
+            out["LATENCY"][...] = v
+        elif name == "lateral friction":
+            out["FOOT_MU"][...] = v
+        elif name == "mass":
+            out["MASS_RATIO"][...] = v
+        elif name == "motor strength":
+            out["STRENGTH"][...] = v
+        else:                                             # leg weaken (the drawn leg), single leg weaken (leg 0)
+            which = leg if name == "leg weaken" else np.zeros(lead)
+            on = (np.arange(12) // 3) == which[..., None]
+            out["STRENGTH"][...] = np.where(on, v, 1.0)
+    return out
+
+
 def action_space():
     """minitaur.py:145-148."""
     return Box(np.array([-2 * math.pi] * 12), np.array([2 * math.pi] * 12), dtype=np.float32)
@@ -335,8 +460,10 @@ class VecQuadrupedEnv(object):
                  robot_index_offset=0, legacy_grid=False, mixed_robots=None, ep_log_capacity=65536, config_overrides=None,
                  model_overrides=None, clip_time_min=None, clip_time_max=None, perturb_init_state_prob=None, tar_obs_noise=None,
                  init_perturb_std=None, reward_terms=False, contact_outputs=False, torque_limits=None, actuator_outputs=False,
-                 observation_noise_stdev=None):
+                 observation_noise_stdev=None, randomizer_config=None, randomizer_params=False):
         import torch
+        if not isinstance(randomizer_params, (bool, np.bool_)):
+            raise ValueError("randomizer_params must be True or False, got %r" % (randomizer_params,))
         if not isinstance(reward_terms, (bool, np.bool_)):
             raise ValueError("reward_terms must be True or False, got %r" % (reward_terms,))
         if not isinstance(contact_outputs, (bool, np.bool_)):
@@ -421,6 +548,12 @@ class VecQuadrupedEnv(object):
         if init_perturb_std is None:
             init_perturb_std = params.get("init_perturb_std")
         self.task_noise = task_noise_spec(perturb_init_state_prob, tar_obs_noise, init_perturb_std)
+        # the randomiser's table (ControllableEnvRandomizerFromConfig's config; the task YAML may carry it as env_randomizer_config):
+        # None = the built-in six ranges and the kernels that have them built in.  Validated here, ahead of anything that needs the device
+        if randomizer_config is None:
+            randomizer_config = params.get("env_randomizer_config")
+        self.randomizer = randomizer_spec(randomizer_config, self.cfg.sim_dt)
+        self.randomizer_config = randomizer_config
         # motor torque limits (MotorModel's torque_limits): the user's data, none by default - no shipped robot table carries any
         self.torque_limits = torque_limit_spec(torque_limits, sorted(set(self.robot_names)))
         self.robot_type = robot_type
@@ -497,6 +630,13 @@ class VecQuadrupedEnv(object):
             self.bind_actuator_outputs(True)
         if sensor_noise_on(self.sensor_noise):
             self.set_sensor_noise(observation_noise_stdev)
+        # the episode's normalised samples per robot (orr_bind_randomizer_params): None while unbound
+        self.randomizer_rows = None
+        self.randomizer_suspended = False
+        if randomizer_config is not None:
+            self.set_randomizer(randomizer_config)
+        if randomizer_params:
+            self.bind_randomizer_params(True)
 
     # ---- reference attribute surface -------------------------------------------------------
     @property
@@ -548,6 +688,82 @@ class VecQuadrupedEnv(object):
         _lib.check(self.L.orr_set_sensor_noise(self.h, C.byref(spec)), self.L)
         self.sensor_noise = spec
         self.launch_params_generation += 1
+
+    def set_randomizer(self, config=None):
+        """Change the randomiser's table of a running env (orr_set_randomizer; see randomizer_spec for `config`): read by every reset
+        from the next launch on, while the env randomises at all (enable_randomizer).  None restores the built-in six ranges and the
+        kernels that have them built in; anything else - "all_params" too - runs the randomiser variants.  It selects the kernel
+        variant: holders of captured graphs re-capture (launch_params_generation)."""
+        spec = randomizer_spec(config, self.cfg.sim_dt)
+        _lib.check(self.L.orr_set_randomizer(self.h, None if config is None else C.byref(spec)), self.L)
+        self.randomizer, self.randomizer_config = spec, config
+        self.launch_params_generation += 1
+
+    def bind_randomizer_params(self, on=True, suspend=False):
+        """Bind (allocating on first use) or unbind the randomiser's params buffer (orr_bind_randomizer_params): env.randomizer_rows
+        [N, 32], a robot's row = the normalised samples of its current episode (layout: include/openroborl_hip.h).  suspend=False: every
+        reset writes the new episode's row.  suspend=True (the reference's suspend_randomization): resets draw nothing and apply the
+        rows as they stand (set_randomization_parameters).  It selects the kernel variant: holders of captured graphs re-capture
+        (launch_params_generation); the variant's first launch in a process loads its code object, so step once eagerly before a capture."""
+        t = self.torch
+        if on:
+            rows = self.randomizer_rows
+            if rows is None:
+                rows = t.zeros((self.num_robot, _abi.RAND_ROW), dtype=t.float32, device=self.device)
+                rows[:, :31] = 0.5          # mid-range until a reset writes them (suspended from the start: every parameter at its centre)
+                rows[:, RAND_LEG_WORD] = 0.0
+            t.cuda.synchronize(self.device)
+            _lib.check(self.L.orr_bind_randomizer_params(self.h, rows.data_ptr(), 1 if suspend else 0), self.L)
+            self.randomizer_rows, self.randomizer_suspended = rows, bool(suspend)
+        else:
+            t.cuda.synchronize(self.device)      # launches in flight still write the buffer
+            _lib.check(self.L.orr_bind_randomizer_params(self.h, None, 0), self.L)
+            self.randomizer_rows, self.randomizer_suspended = None, False
+        self.launch_params_generation += 1
+
+    def get_randomization_parameters(self):
+        """ControllableEnvRandomizerFromConfig.get_randomization_parameters for the whole batch: a dict of parameter name -> tensor [N,
+        k] of the current episodes' samples in the reference's param_bounds units, -1 + 2 u ("leg weaken": [leg index as it is, -1 + 2 u]),
+        for the enabled parameters.  Needs the params buffer (randomizer_params=True / bind_randomizer_params)."""
+        if self.randomizer_rows is None:
+            raise ValueError("no randomizer params: the env was built without randomizer_params=True")
+        out = {}
+        for p, name in enumerate(_abi.RAND_PARAM_NAMES):
+            if self.randomizer.enabled[p]:
+                v = 2.0 * self.randomizer_rows[:, RAND_ROW_WORDS[name]] - 1.0
+                if name == "leg weaken":
+                    v[:, 0] = self.randomizer_rows[:, RAND_LEG_WORD]
+                out[name] = v
+        return out
+
+    def set_randomization_parameters(self, parameters):
+        """set_env_from_randomization_parameters for the whole batch: write the rows from a dict like get_randomization_parameters' (name
+        -> [N, k] or [k], samples in [-1, 1]; "leg weaken": [leg 0..3, sample]).  Resets apply them while the buffer is bound with
+        suspend=True; parameters that are left out keep their words."""
+        if self.randomizer_rows is None:
+            raise ValueError("no randomizer params: the env was built without randomizer_params=True")
+        t = self.torch
+        rows = self.randomizer_rows.clone()
+        for name, v in parameters.items():
+            if name not in RAND_ROW_WORDS:
+                raise ValueError("unknown randomizer parameter %r (known: %s)" % (name, ", ".join(_abi.RAND_PARAM_NAMES)))
+            sl = RAND_ROW_WORDS[name]
+            v = t.as_tensor(v, dtype=t.float32, device=self.device)
+            v = v.reshape(-1, sl.stop - sl.start).clone()
+            if v.shape[0] not in (1, self.num_robot):
+                raise ValueError("randomizer parameter %r: expected %d values per robot for 1 or %d robots" % (name, sl.stop - sl.start, self.num_robot))
+            u = (v + 1.0) * 0.5
+            if name == "leg weaken":
+                u[:, 0] = v[:, 0]
+                if bool(((v[:, 0] != v[:, 0].round()) | (v[:, 0] < 0) | (v[:, 0] > 3)).any()):
+                    raise ValueError("randomizer parameter 'leg weaken': the leg must be 0, 1, 2 or 3")
+                smp = v[:, 1]
+            else:
+                smp = v
+            if bool(((smp < -1.0) | (smp > 1.0) | (smp != smp)).any()):
+                raise ValueError("randomizer parameter %r: samples must lie in [-1, 1]" % (name,))
+            rows[:, sl] = u
+        self.randomizer_rows.copy_(rows)
 
     def bind_reward_terms(self, on=True):
         """Bind (allocating on first use) or unbind the per-term reward outputs (orr_bind_reward_terms): env.reward_terms [N, 5], valid

@@ -1,5 +1,5 @@
 """Step time of a variant of the step kernel against its baseline, 4096 robots, same process, alternated (train semantics):
-python tools/diag/variant_time.py --case noise|terms|contacts|actuator|sensor|anchor
+python tools/diag/variant_time.py --case noise|terms|contacts|actuator|sensor|randomizer|anchor
 
   noise     the task-noise variant against the clip-set variant (a two-clip set, so that the plain env runs the clip-set variant)
   terms     reward terms on top of task noise               (two-clip set, noise on in all at one setting: prob 0.5, sigma 0.1)
@@ -13,6 +13,9 @@ python tools/diag/variant_time.py --case noise|terms|contacts|actuator|sensor|an
   sensor    sensor noise (motor angle 0.01 rad, rpy 0.02 rad, rpy rate 0.1 rad/s) on top of the actuator variant with all three bindings on
             and no limits, the same set and task noise; in between the sensor variant with motor_angle_std = 0, which skips the
             sub-steps' draws: the cost of the step end's draws apart from the sub-step loop's
+  randomizer the table-driven randomiser ("all_params": the built-in six ranges as a table), then the params buffer as well, on top of the
+            sensor variant (all three deviations and bindings on, the same set and task noise): the cost of the table-driven reset and
+            of the row's store, both outside the sub-step loop; also the episodes each env finished (auto-resets) while timed
   anchor    the friction-anchor variant against the default kernel (the task's own clip, no noise)
 
 Every env gets 300 warm-up steps of stress actions, then 5 rounds of 300 back-to-back launches with fixed actions go round the envs in
@@ -46,6 +49,10 @@ CASES = {
                (("task noise + contact outputs + reward terms + actuator outputs", {}),
                 ("the same + sensor noise on rpy 0.02 / rpy rate 0.1 only", dict(observation_noise_stdev=[0.0, 0.0, 0.0, 0.02, 0.1])),
                 ("the same + sensor noise on motor angle 0.01 / rpy 0.02 / rpy rate 0.1", dict(observation_noise_stdev=[0.01, 0.0, 0.0, 0.02, 0.1])))),
+    "randomizer": (dict(TWO_CLIPS, contact_outputs=True, reward_terms=True, actuator_outputs=True, observation_noise_stdev=[0.01, 0.0, 0.0, 0.02, 0.1], **NOISE),
+                   (("task noise + all three outputs + sensor noise", {}),
+                    ("the same + the randomiser's table (all_params)", dict(randomizer_config="all_params")),
+                    ("the same + the randomiser's table (all_params) + params buffer", dict(randomizer_config="all_params", randomizer_params=True)))),
     "anchor": ({}, (("default", {}), ("friction anchors", dict(model_overrides={"laikago": {"friction_anchor": 1}})))),
 }
 
@@ -79,6 +86,9 @@ if case == "contacts":
     gait = envs[1].episode_gait()
     print("gait of the logged episodes (stress actions): duty %s, mean normal force [N] %s" % (
         " ".join("%.3f" % x for x in gait.get("duty", [])), " ".join("%.1f" % x for x in gait.get("normal_force", []))))
+if case == "randomizer":
+    for (name, _), env, f0 in zip(variants, envs, finished):
+        print("%-68s %.1f episodes ended (auto-resets) per launch while timed" % (name, (f0 + int(env.counters[_abi.CNT_EPISODES].item())) / float(ROUNDS * LAUNCHES)))
 if case == "actuator":
     for (name, _), env, f0 in zip(variants, envs, finished):
         m = env.models[int(env.robot_type[0])]

@@ -59,6 +59,8 @@ CONTACT_STEP_KERNELS = (("_Z15orr_step_kernelILi8ELi1ELb0ELb1ELb1E", "step kerne
 ACTUATOR_STEP_KERNELS = (("_Z15orr_step_kernelILi28ELi1ELb0ELb1ELb1E", "step kernel with clip sets, task noise, reward terms, contact outputs, torque limits and actuator outputs (one wave per SIMD)"),)
 # the sensor unit's (orr_kernels_sensor.hip; MODE = kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0), likewise
 SENSOR_STEP_KERNELS = (("_Z15orr_step_kernelILi60ELi1ELb0ELb1ELb1E", "step kernel with sensor noise on top of the actuator variant (one wave per SIMD)"),)
+# the randomiser unit's (orr_kernels_randomizer.hip; MODE = kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0), likewise
+RANDOMIZER_STEP_KERNELS = (("_Z15orr_step_kernelILi124ELi1ELb0ELb1ELb1E", "step kernel with the table-driven randomiser on top of the sensor variant (one wave per SIMD)"),)
 
 
 def compile_units(extra_flags=(), only_main=False, units=("env", "w2", "anchor")):
@@ -66,11 +68,12 @@ def compile_units(extra_flags=(), only_main=False, units=("env", "w2", "anchor")
     per unit.  `units` = names of _lib.ALL_ENV_UNITS, compiled in the table's order; the default is the three that tools/isa_lines.py and
     tests/test_isa_budget.py address by index (0 main, 1 two-wave, 2 friction anchors), "multiclip" adds the clip-set unit, "noise" the
     task-noise unit, "terms" (_lib.TERMS_UNITS, behind them) the reward-terms unit, "contacts" (_lib.CONTACT_UNITS) the
-    contact-output unit, "actuator" (_lib.ACTUATOR_UNITS) the actuator unit, "sensor" (_lib.SENSOR_UNITS, last) the sensor-noise unit."""
+    contact-output unit, "actuator" (_lib.ACTUATOR_UNITS) the actuator unit, "sensor" (_lib.SENSOR_UNITS) the sensor-noise unit, "randomizer"
+    (_lib.RANDOMIZER_UNITS, last) the randomiser unit."""
     src_dir = os.path.dirname(os.environ.get("ORR_ISA_SRC", _lib.SRC))      # another tree's orr_kernels.hip (A/B of code generation)
     out_dir = tempfile.mkdtemp()
     listings = []
-    for name, src, flags, _ in (_lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS + _lib.SENSOR_UNITS)[:1 if only_main else None]:
+    for name, src, flags, _ in (_lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS + _lib.SENSOR_UNITS + _lib.RANDOMIZER_UNITS)[:1 if only_main else None]:
         src = os.path.join(src_dir, os.path.basename(src))
         if name not in units or not os.path.exists(src):      # (an older tree has fewer units)
             continue
@@ -172,10 +175,10 @@ def resources(meta, sym):
 
 
 def main():
-    lines = [l for u in compile_units(sys.argv[1:], units=[u[0] for u in _lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS + _lib.SENSOR_UNITS]) for l in u]
+    lines = [l for u in compile_units(sys.argv[1:], units=[u[0] for u in _lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS + _lib.SENSOR_UNITS + _lib.RANDOMIZER_UNITS]) for l in u]
     meta = "\n".join(lines)
     # one report per variant of the step kernel (WPE 1: one wave per SIMD, WPE 2: two; see orr_env_kernels.h)
-    for sym, title in STEP_KERNELS + TERMS_STEP_KERNELS + CONTACT_STEP_KERNELS + ACTUATOR_STEP_KERNELS + SENSOR_STEP_KERNELS:
+    for sym, title in STEP_KERNELS + TERMS_STEP_KERNELS + CONTACT_STEP_KERNELS + ACTUATOR_STEP_KERNELS + SENSOR_STEP_KERNELS + RANDOMIZER_STEP_KERNELS:
         k = parse_kernel(lines, sym)
         if k is None:
             continue
