@@ -383,6 +383,53 @@ int32_t orr_sizeof_randomizer(void);
 #define ORR_RAND_ROW 32
 int32_t orr_bind_randomizer_params(orr_handle* h, float* params_dev /* [N][ORR_RAND_ROW] */, int32_t suspend);
 
+/* external pushes of the handle (the push randomiser of legged-robot training recipes; the reference ships none).  A push is a
+ * velocity kick of the whole robot at the start of an env step: the record's LINVEL gets + dv and ANGVEL + dw, both world frame, after
+ * the record is loaded and before anything reads the rigid state for the first sub-step.  Not a force: independent of mass, so one
+ * setting serves a mixed batch; the joint rates are relative, so the legs move with the base; the sensors see the kick from the first
+ * sub-step's ring entry on. */
+typedef struct orr_push {
+  float   prob;         /* probability of a kick per robot and env step, [0, 1] */
+  float   lin_lo;       /* horizontal speed of the kick, m/s, 0 <= lin_lo <= lin_hi */
+  float   lin_hi;
+  float   lin_z;        /* vertical component in U(-lin_z, lin_z), >= 0 */
+  float   ang;          /* each component of dw in U(-ang, ang), rad/s, >= 0 */
+  int32_t grace_steps;  /* no kick while the episode's env-step counter is below it, >= 0 */
+} orr_push;
+/* host NULL = off.  While prob is 0 and no outputs are bound (orr_bind_push_outputs) the handle launches exactly the kernels it
+ *   launched before; otherwise orr_step launches the push variant (a superset of the randomiser variant: one wave per SIMD at any batch
+ *   size, unbound outputs skipped, zero noise passes the reading; its auto-reset is the table-driven one only while the handle has a
+ *   randomiser table or params buffer, otherwise the one the handle ran before).  There is no reset and no replay kernel with pushes:
+ *   orr_reset, orr_debug_replay_reset and orr_debug_replay_step of such a handle launch exactly what they launch without this call.
+ *   The parity replay and orr_debug_physics IGNORE pushes: the replay replaces the physics by recorded states, the debug physics has no
+ *   env step.  The variant's first launch in a process loads its code object: it must not happen inside a stream capture.
+ * Draw rule, on the episode's (seed, robot index, episode) stream, ROBOT_INDEX and EPISODE_IDX as they are before the step; every older
+ *   block keeps its meaning (sensor noise below 0x20000000, task noise 0x2... and 0x3..., the randomiser 0x40000000 and 0x40000001):
+ *   s = EP_STEP before the step; block A = 0x50000000 + 2 s, block B = A + 1 (below 0x60000000 for s < 2^27); words are the stream's
+ *   24-bit uniforms m / 2^24.
+ *   The robot is kicked iff s >= grace_steps and A.word0 < prob (a float32 comparison of an exact fraction: the host can decide it).
+ *   theta = 2 pi A.word1, formed as the normal pairs form their angle: k = rint(4 u) quarter turns, f = u - k / 4 exactly, a =
+ *     fmaf(f, 2pi_hi, f 2pi_lo) with the two-part 2 pi, sine and cosine of a by the joint polynomial, the quarter turns applied after;
+ *   m = fmaf(A.word2, lin_hi - lin_lo, lin_lo), lin_hi - lin_lo one float32 subtraction on the device;
+ *   dv = (m cos theta, m sin theta, fmaf(A.word3, 2 lin_z, -lin_z));   dw_k = fmaf(B.word_k, 2 ang, -ang), k = 0..2.
+ *   Block B is computed only while ang > 0 (dw = 0 otherwise).  A robot that is not kicked has dv = dw = 0 and its velocities pass
+ *   as they are (selects, not + 0: a velocity of -0.0 keeps its sign), so "no kick" is bit for bit "no push variant".
+ * Refused, nothing changed (the message names the field): a null handle; a NaN or infinite value; prob outside [0, 1]; a negative
+ *   lin_lo, lin_hi, lin_z, ang or grace_steps; lin_lo > lin_hi; lin_hi, lin_z or ang above orr_config::max_coord_velocity (the physics
+ *   clamps every coordinate velocity there anyway); friction anchors on the handle while prob > 0 (a launch refuses that combination
+ *   too, and launches nothing, when such a model is set afterwards). */
+int32_t orr_set_push(orr_handle* h, const orr_push* push_host);
+int32_t orr_sizeof_push(void);
+/* What the step did to each robot.  push_dev float[N][ORR_PUSH_ROW] (device, 16-byte aligned); NULL unbinds.  Every orr_step writes the
+ *   row of every robot of the shard: words 0..5 {dv x y z, dw x y z} of this step, word 6 = 1.0 if the robot was kicked in this step else
+ *   0.0, word 7 = the number of kicks in the robot's current episode including this step.  Word 7 restarts in the step whose EP_STEP
+ *   before it is 0; no reset touches the buffer, so the caller zeroes it once.  With auto-reset the row is that of the step that ended
+ *   the episode.  A step that ends with ORR_DONE_NAN still reports what was applied.  Padding lanes store nothing.  A bound buffer
+ *   selects the push variant whatever prob is.
+ * Refused, nothing changed: a null handle, a buffer that is not 16-byte aligned, friction anchors. */
+#define ORR_PUSH_ROW 8
+int32_t orr_bind_push_outputs(orr_handle* h, float* push_dev /* [N][ORR_PUSH_ROW] */);
+
 /* reward terms (ImitationTask._calc_reward_pose / _velocity / _end_effector / _root_pose / _root_velocity, imitation_task.py:358-516).
  * terms_dev float[N][5] (device): every orr_step and orr_debug_replay_step writes, for every robot of the shard, the five UNWEIGHTED
  *   terms r_k = exp(-scale_k err_k) of the reward it wrote to reward_dev, in orr_config::reward_w's order: pose, velocity, end effector,

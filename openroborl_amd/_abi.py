@@ -145,6 +145,17 @@ class OrrRandomizer(C.Structure):
     _fields_ = [("enabled", C.c_int32 * RAND_NUM_PARAMS), ("lo", C.c_float * RAND_NUM_PARAMS), ("hi", C.c_float * RAND_NUM_PARAMS)]
 
 
+# include/openroborl_hip.h: orr_push (orr_set_push), ORR_PUSH_ROW (orr_bind_push_outputs)
+PUSH_FIELDS = ("prob", "lin_lo", "lin_hi", "lin_z", "ang")
+PUSH_ROW = 8                        # floats per robot in the outputs buffer: dv x y z, dw x y z, kicked, kicks of the episode
+PUSH_BLOCK = 0x50000000             # Philox blocks of the step whose env-step counter before it is s: PUSH_BLOCK + 2 s (A) and + 2 s + 1 (B)
+
+
+class OrrPush(C.Structure):
+    """include/openroborl_hip.h: orr_push (orr_set_push)."""
+    _fields_ = [(n, C.c_float) for n in PUSH_FIELDS] + [("grace_steps", C.c_int32)]
+
+
 def fill(struct, name, values):
     """Assign a (nested) python sequence / scalar to a ctypes struct field."""
     import numpy as np

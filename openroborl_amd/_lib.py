@@ -22,6 +22,7 @@ SRC_CONTACTS = os.path.join(CSRC, "orr_kernels_contacts.hip")    # the variants 
 SRC_ACTUATOR = os.path.join(CSRC, "orr_kernels_actuator.hip")    # the variants of the step that clip the motor torques and keep per-motor torque / work sums
 SRC_SENSOR = os.path.join(CSRC, "orr_kernels_sensor.hip")        # the variants of step and reset whose sensor readings carry Gaussian noise
 SRC_RANDOMIZER = os.path.join(CSRC, "orr_kernels_randomizer.hip")  # the variants of step and reset with the table-driven, controllable randomiser
+SRC_PUSH = os.path.join(CSRC, "orr_kernels_push.hip")            # the variant of the step that kicks the robot's base twist (external pushes)
 SRC_POLICY = os.path.join(CSRC, "orr_policy.hip")
 SRC_LEARNER = os.path.join(CSRC, "orr_learner.hip")              # the non-GEMM part of the PPO update (include/openroborl_learner.h)
 # what the library is built from = what the stale-library check hashes: every source and header under csrc/ + the public headers
@@ -92,11 +93,14 @@ SENSOR_UNITS = [("sensor", SRC_SENSOR, HIPCC_FLAGS, False)]
 # The tenth unit of the env kernels, the randomiser variants of step and reset (orr_set_randomizer, orr_bind_randomizer_params): likewise,
 # a table of its own behind SENSOR_UNITS.  build() compiles them all, and tuning defines and extra_flags reach every env unit
 RANDOMIZER_UNITS = [("randomizer", SRC_RANDOMIZER, HIPCC_FLAGS, False)]
+# The eleventh unit of the env kernels, the push variant of the step (orr_set_push, orr_bind_push_outputs): likewise, a table of its own
+# behind RANDOMIZER_UNITS
+PUSH_UNITS = [("push", SRC_PUSH, HIPCC_FLAGS, False)]
 
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
     "orr_layout_offset", "orr_layout_size", "orr_layout_is_int", "orr_sizeof_config", "orr_sizeof_model",
-    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
+    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_set_push", "orr_sizeof_push", "orr_bind_push_outputs", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
@@ -176,12 +180,12 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
             tag = ".%d" % os.getpid()
             tmp_so = out_path + tag + ".tmp"
             objs, cmds = [], []
-            for unit in ALL_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS:
+            for unit in ALL_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS + PUSH_UNITS:
                 name, src, flags, hashed = unit
                 flags = [f for f in flags if f != "-shared"] + ["-c"]
                 if hashed:
                     flags.append('-DORR_SOURCE_HASH="%s"' % source_hash(extra_flags))
-                if unit in ALL_ENV_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS:
+                if unit in ALL_ENV_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS + PUSH_UNITS:
                     flags += tuning_defines() + list(extra_flags)
                 objs.append(os.path.splitext(src)[0] + tag + ".o")
                 cmds.append([HIPCC] + flags + ["-o", objs[-1], src])
@@ -271,6 +275,11 @@ def load():
     L.orr_sizeof_randomizer.restype = C.c_int32
     L.orr_bind_randomizer_params.restype = C.c_int32
     L.orr_bind_randomizer_params.argtypes = [vp, vp, C.c_int32]
+    L.orr_set_push.restype = C.c_int32
+    L.orr_set_push.argtypes = [vp, C.POINTER(_abi.OrrPush)]
+    L.orr_sizeof_push.restype = C.c_int32
+    L.orr_bind_push_outputs.restype = C.c_int32
+    L.orr_bind_push_outputs.argtypes = [vp, vp]
     L.orr_bind_clip_log.restype = C.c_int32
     L.orr_bind_clip_log.argtypes = [vp, vp]
     L.orr_bind_reward_terms.restype = C.c_int32
@@ -331,7 +340,7 @@ def load():
         raise RuntimeError("libopenroborl_hip.so ABI version mismatch")
     if (L.orr_sizeof_config() != C.sizeof(_abi.OrrConfig) or L.orr_sizeof_model() != C.sizeof(_abi.OrrModel)
             or L.orr_sizeof_task_noise() != C.sizeof(_abi.OrrTaskNoise) or L.orr_sizeof_sensor_noise() != C.sizeof(_abi.OrrSensorNoise)
-            or L.orr_sizeof_randomizer() != C.sizeof(_abi.OrrRandomizer)):
+            or L.orr_sizeof_randomizer() != C.sizeof(_abi.OrrRandomizer) or L.orr_sizeof_push() != C.sizeof(_abi.OrrPush)):
         raise RuntimeError("ctypes struct layout does not match include/openroborl_hip.h")
     _lib = L
     return L

@@ -43,6 +43,11 @@ RANDOMIZER_ALL_PARAMS = {"mass": [0.8, 1.2], "inertia": [0.5, 1.5], "motor stren
                          "latency": [0.0, 0.04], "lateral friction": [0.5, 1.25], "battery": [14.0, 16.8], "joint friction": [0, 0.05]}
 
 
+# External pushes (orr_set_push): a task section of the training YAML may carry the env's `push` dictionary under the key `push`, e.g.
+# push: {interval_s: 5.0, lin_vel: [0.2, 0.6], lin_vel_z: 0.2, ang_vel: 0.5, grace_steps: 10}; env.push_spec lists the accepted keys
+PUSH_KEY = "push"
+
+
 def load_training_params(task_name, path=None):
     """run.py:194-200: section lookup by --task; ValueError when missing."""
     path = path or DEFAULT_TRAINING_YAML

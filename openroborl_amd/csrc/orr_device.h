@@ -135,6 +135,11 @@ struct DevTables {
   orr_randomizer rnd;                                 // orr_create fills in the built-in six ranges
   float* rand_params;                                 // [N][ORR_RAND_ROW] the episode's normalised samples per robot, or NULL = not bound
   int rand_suspend;                                   // != 0: resets apply the rows instead of drawing, and do not write them
+  // external pushes of the handle (orr_set_push, orr_bind_push_outputs), read by the push variant only (orr_kernels_push.hip).
+  // APPENDED likewise
+  orr_push push;                                      // all zero = off
+  float* push_out;                                    // [N][ORR_PUSH_ROW] dv, dw, kicked, kicks of the episode per robot, or NULL = not bound
+  int push_table;                                     // != 0: the handle has a randomiser table or params buffer, so the push variant's auto-reset is the table-driven one; 0: the built-in literal ranges, as in the kernels below the randomiser variants
 };
 // Flag bit of orr_step_kernel's MODE: the variant that also writes the reward terms.  MODE & 3 is the mode proper (0 env step, 1 debug
 // physics, 2 parity replay).  A bit of MODE rather than a template parameter of its own: the older variants keep their mangled names
@@ -155,6 +160,17 @@ static_assert(sizeof(orr_randomizer) == 12 * ORR_RAND_NUM_PARAMS && ORR_RAND_NUM
 // What the caller of reset_robot_state<.., RAND> hands in and gets back.  row: the robot's row of the params buffer (NULL = not bound),
 // suspend: apply the row instead of drawing.  a, b: the lane's two words of the new episode's row (words lane and 16 + lane), which the
 // caller stores at the end of its kernel, behind every load (store_rand_row)
+// Likewise: the variant that kicks the robot's base twist at the start of the step (orr_set_push, orr_bind_push_outputs).  Env step only,
+// on top of the randomiser variant
+constexpr int kModePush = 128;
+static_assert(sizeof(orr_push) == 24 && ORR_PUSH_ROW == 8, "the push variant reads it as six words; a row is one word per lane 0..7");
+// The handle's push settings, wave-uniform (one setting per handle), and the outputs buffer (NULL = not bound).  span = lin_hi - lin_lo
+struct PushSet {
+  float prob = 0.0f, lin_lo = 0.0f, span = 0.0f, lin_z = 0.0f, ang = 0.0f;
+  int grace = 0;
+  float* out = nullptr;
+  bool table = false;   // the auto-reset runs the table-driven randomiser (DevTables::push_table)
+};
 struct RandRow {
   const float* row = nullptr;
   bool suspend = false;
@@ -613,6 +629,22 @@ __device__ __forceinline__ void normal_pair(float ua, float ub, float* z0, float
   const float sq = (q & 2) ? -ss : ss, cq = ((q + 1) & 2) ? -cc : cc;
   *z0 = (float)(r * (double)cq);
   *z1 = (float)(r * (double)sq);
+}
+
+// Sine and cosine of the angle 2 pi u of one of the stream's 24-bit uniforms (u = m / 2^24 in [0, 1)), as normal_pair forms its angle:
+// the quarter turn k = rint(4 u) comes off exactly (u - k / 4 is a multiple of 2^-24, |f| <= 1/8), the rest times a two-part 2 pi goes
+// to joint_sincos as |a| <= pi / 4, the quarter turns are applied to the result.  Error: joint_sincos' own (< 1e-7) + half an ulp of a
+// (orr_set_push: the heading of a kick)
+__device__ __forceinline__ void unit_sincos(float u, float* sn, float* cs) {
+  const float k = rintf(4.0f * u);                               // quarter turns, 0..4
+  const float f = fmaf(-0.25f, k, u);                            // exact, |f| <= 1/8
+  const float a = fmaf(f, 6.2831854820251465f, f * -1.7484555e-07f);   // 2 pi f with a two-part 2 pi (as map_pi)
+  float s, c;
+  joint_sincos(a, &s, &c);
+  const int q = (int)k & 3;
+  const float ss = (q & 1) ? c : s, cc = (q & 1) ? s : c;
+  *sn = (q & 2) ? -ss : ss;
+  *cs = ((q + 1) & 2) ? -cc : cc;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // orr_env_kernels.h -- the two env kernels (orr_reset_kernel, orr_step_kernel) and their launchers, as templates.
 //
-// Included by the ten translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
+// Included by the eleven translation units of the env kernels; each unit instantiates its own variants and nothing else (why there are
 // several: DESIGN.md section 3).  orr_kernels.hip: the default kernels + the C-ABI, instruction-level-parallelism scheduler (one wave per
 // SIMD, ~300 registers, nothing to hide latency but the wave's own independent instructions).  orr_kernels_w2.hip: the
 // two-waves-per-SIMD step kernel, its own flags.  orr_kernels_anchor.hip: the friction-anchor variants.  orr_kernels_multiclip.hip:
@@ -10,6 +10,7 @@
 // orr_kernels_actuator.hip: the variants that clip the motor torques and keep per-motor torque / work accumulators (orr_set_torque_limits,
 // orr_bind_actuator_outputs).  orr_kernels_sensor.hip: the variants whose sensor readings carry Gaussian noise (orr_set_sensor_noise).
 // orr_kernels_randomizer.hip: the variants whose resets run the table-driven randomiser (orr_set_randomizer, orr_bind_randomizer_params).
+// orr_kernels_push.hip: the env step that kicks the robot's base twist (orr_set_push, orr_bind_push_outputs).
 // An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
 // per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
 // template` only (bottom of this file).
@@ -234,6 +235,10 @@ __global__ __launch_bounds__(64) void orr_randomizer_reset_kernel(KParams P, con
 // the batch size): the inline auto-reset runs the table-driven randomiser (reset_robot_state<.., RAND>; orr_set_randomizer) and writes
 // or, suspended, applies the robot's row of the params buffer (orr_bind_randomizer_params).  Nothing in front of the episode's end: the
 // buffer's address and the suspend switch are read at the start (scalars), the row's store comes with the record's
+// PUSH = MODE & kModePush (orr_kernels_push.hip; the env step on top of the randomiser variant - a superset - one wave per SIMD whatever
+// the batch size): a velocity kick of the base twist at the start of the step (orr_set_push), two Philox blocks and one sine / cosine per
+// robot and step, on the LDS image ahead of the WSYNC that precedes load_own_coord.  Nothing inside the sub-step loop.  The settings are
+// read at the start (scalars), the old count of the outputs row (orr_bind_push_outputs) with them, the row is stored at the step's end
 template <int MODE, int WPE = ORR_WAVES_PER_EU, bool ANCHOR = false, bool CLIPS = false, bool NOISE = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void orr_step_kernel(KParams P, const float* actions, float* obs_out, float* reward_out,
                                                       uint8_t* done_out, int nsub, ReplayArgs RP) {
@@ -248,6 +253,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   static_assert(!SENS || (ACT && NOISE), "the sensor variants are supersets: instantiated on top of the actuator variants only");
   constexpr bool RAND = (MODE & kModeRandomizer) != 0;
   static_assert(!RAND || SENS, "the randomiser variants are supersets: instantiated on top of the sensor variants only");
+  constexpr bool PUSH = (MODE & kModePush) != 0;
+  static_assert(!PUSH || RAND, "the push variant is a superset: instantiated on top of the randomiser variant only");
+  static_assert(!PUSH || (MODE & 3) == 0, "the parity replay replaces the physics by recorded states, the debug physics has no env step: neither is pushed");
   ORR_PROLOGUE();
   const bool valid = in_range;
   const orr_config& c = P.cfg;
@@ -266,6 +274,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   }
   RandRow RR;   // RAND: the robot's row of the params buffer (wave-uniform address and switch)
   if constexpr (RAND) RR = load_rand_row(P, robot);
+  // PUSH: the handle's settings (scalars) and the old count of kicks in the robot's row of the outputs (word 7; a padding lane group
+  // shadows robot 0's and never stores): read here, first and last used at the kick below - nothing of PS lives across the sub-step
+  // loop (the step end reads the buffer's address and the reset's switch again: scalars held over the loop cost it spill code)
+  typedef float __attribute__((address_space(1)))* gpush;
+  PushSet PS;
+  float push_old = 0.0f, push_w = 0.0f;   // push_w: the lane's word of the row (lanes 0..7), stored at the step's end
+  if constexpr (PUSH) {
+    PS = load_push(P);
+    if (PS.out) push_old = ((gpush)PS.out)[(size_t)robot * ORR_PUSH_ROW + 7];
+  }
   // CLIPS: the motion time of the next clip change (behind the ring, never staged): read at the start, first used after the sub-steps
   float clip_change = 0.0f;
   if constexpr (CLIPS) clip_change = rec[O(CLIP_CHANGE_TIME)];
@@ -408,6 +426,31 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     S.s[O(YHIST) + 12 + lane] = y1; S.s[O(YHIST) + lane] = y;
     S.s[O(ACTION) + lane] = y;
   }
+  // PUSH (orr_set_push; draw rule in include/openroborl_hip.h): the kick of this step, on the LDS image before anything reads the rigid
+  // state for the first sub-step.  Every lane of the robot evaluates the same blocks (no divergence; block B behind a wave-uniform
+  // test, like the sensor variant's of its deviation); lane k < 6 owns word k of LINVEL / ANGVEL.  A robot that is not kicked keeps its
+  // words by a select, not by + 0: the sign of a -0.0 passes
+  if constexpr (PUSH) {
+    static_assert(ORR_OFF_ANGVEL == ORR_OFF_LINVEL + 3, "LINVEL and ANGVEL are six consecutive words");
+    const uint32_t ps = sn_i - 1u;   // EP_STEP before the step
+    float ua[4], ub[4] = {0.5f, 0.5f, 0.5f, 0.5f};
+    philox_block(c.seed, sn_robot, sn_ep, kPushBlock + 2u * ps, ua);
+    const bool kicked = (int)ps >= PS.grace && ua[0] < PS.prob;
+    float sn, cs;
+    unit_sincos(ua[1], &sn, &cs);
+    const float pm = fmaf(ua[2], PS.span, PS.lin_lo);
+    if (PS.ang > 0.0f) philox_block(c.seed, sn_robot, sn_ep, kPushBlock + 2u * ps + 1u, ub);
+    const float two_ang = PS.ang > 0.0f ? 2.0f * PS.ang : 0.0f;   // ang = 0: fmaf(0.5, 0, -0) = 0
+    const float mine = lane == 0 ? __fmul_rn(pm, cs) : (lane == 1 ? __fmul_rn(pm, sn) : (lane == 2 ? fmaf(ua[3], 2.0f * PS.lin_z, -PS.lin_z)
+                       : fmaf(lane == 3 ? ub[0] : (lane == 4 ? ub[1] : ub[2]), two_ang, -PS.ang)));
+    const float dk = kicked && lane < 6 ? mine : 0.0f;
+    if (lane < 6) {
+      const float v = S.s[O(LINVEL) + lane];
+      S.s[O(LINVEL) + lane] = kicked ? __fadd_rn(v, dk) : v;
+    }
+    const float one = kicked ? 1.0f : 0.0f;
+    push_w = lane < 6 ? dk : (lane == 6 ? one : (ps == 0u ? 0.0f : push_old) + one);
+  }
   WSYNC();
   PT(1);
   int fall = 0;
@@ -520,6 +563,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
   // (m_init is dead by now): keeping those live up to the reset moved the sub-step loop's register allocation (+10 instructions) for
   // a launch no faster
   const ResetConst RC = load_reset_const(P, S, lane);
+  float* push_out = nullptr;     // PUSH: the outputs buffer and the reset's switch, read again (see PS)
+  bool push_table = false;
+  if constexpr (PUSH) load_push_end(P, &push_out, &push_table);
   if (lane == 0) {  // end of robot_step (minitaur.py:287-293)
     seti(S, O(RING_HEAD), ring.head); seti(S, O(RING_LEN), ring.len);
     seti(S, O(STATE_ACTION_COUNTER), action_counter);
@@ -704,6 +750,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     WSYNC();
     if (c.flags & ORR_FLAG_AUTO_RESET) {
       PT(31);
+      // PUSH: a handle without a randomiser table or params buffer keeps the reset it had (the literal ranges: the table-driven form of
+      // the same ranges rounds hi - lo once more); wave-uniform
+      if constexpr (PUSH) {
+        if (push_table) obs_episode = reset_robot_state<CLIPS, NOISE, SENS, true>(P, S, lane, total_snapshot, RC, &clip_change, nullptr, SN, &RR);
+        else obs_episode = reset_robot_state<CLIPS, NOISE, SENS>(P, S, lane, total_snapshot, RC, &clip_change, nullptr, SN);
+      } else
       if constexpr (RAND) obs_episode = reset_robot_state<CLIPS, NOISE, SENS, true>(P, S, lane, total_snapshot, RC, &clip_change, nullptr, SN, &RR);
       else obs_episode = reset_robot_state<CLIPS, NOISE, SENS>(P, S, lane, total_snapshot, RC, &clip_change, nullptr, SN);
       noise_i = 0u;
@@ -739,6 +791,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     if constexpr ((MODE & 3) == 0) {
       if (valid && lane < 4 && act_bound) ((gact)P.tab->act_ep)[(size_t)robot * 4 + lane] = a_ep;
     }
+  }
+  if constexpr (PUSH) {   // row = {dv, dw, kicked, kicks of the episode}: what was applied at the start of this step, one word per lane 0..7
+    if (valid && lane < ORR_PUSH_ROW && push_out) ((gpush)push_out)[(size_t)robot * ORR_PUSH_ROW + lane] = push_w;
   }
   if (was_reset) store_reset_extras<CLIPS>(rec, S, lane, valid, clip_change);   // ring entries #1 / #2 of the new episode (still in LDS)
   if constexpr (RAND) { if (was_reset) store_rand_row(P, RR, lane, valid); }    // and its row of the params buffer
@@ -1011,6 +1066,7 @@ extern template StepLaunch launch_step<kModeSensor | kModeActuator | kModeTerms 
 extern template ResetLaunch launch_sensor_reset<true>;
 extern template StepLaunch launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>;   // orr_kernels_randomizer.hip: env step with the table-driven randomiser,
 extern template StepLaunch launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>;                   //   its parity replay,
+extern template StepLaunch launch_step<kModePush | kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>;   // orr_kernels_push.hip: env step with pushes (replays and resets: the randomiser unit's)
 extern template ResetLaunch launch_randomizer_reset<true>;                                                                                     //   reset (and its parity replay)                                                                       //   reset (and its parity replay)
 
 #ifdef ORR_STAGE_DUMP

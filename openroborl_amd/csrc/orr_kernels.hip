@@ -95,6 +95,8 @@ struct orr_handle {
   bool sensor_on;             // orr_set_sensor_noise: a motor-angle, rpy or rpy-rate deviation above 0: env step, parity replays and resets run the sensor variants (orr_kernels_sensor.hip)
   bool rand_on;               // orr_set_randomizer with a table (not NULL), or
   bool rand_bound;            // orr_bind_randomizer_params with a buffer: env step, parity replays and resets run the randomiser variants (orr_kernels_randomizer.hip)
+  bool push_on;               // orr_set_push with prob > 0, or
+  bool push_bound;            // orr_bind_push_outputs with a buffer: the env step runs the push variant (orr_kernels_push.hip); every other entry point launches what it launches without
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -168,6 +170,7 @@ int32_t orr_sizeof_model(void) { return (int32_t)sizeof(orr_model); }
 int32_t orr_sizeof_task_noise(void) { return (int32_t)sizeof(orr_task_noise); }
 int32_t orr_sizeof_sensor_noise(void) { return (int32_t)sizeof(orr_sensor_noise); }
 int32_t orr_sizeof_randomizer(void) { return (int32_t)sizeof(orr_randomizer); }
+int32_t orr_sizeof_push(void) { return (int32_t)sizeof(orr_push); }
 
 int32_t orr_create(const orr_config* cfg, orr_handle** out) {
   if (!cfg || !out) return fail(-1, "orr_create: null argument");
@@ -507,6 +510,15 @@ int32_t orr_set_sensor_noise(orr_handle* h, const orr_sensor_noise* noise_host) 
   return 0;
 }
 
+// DevTables::push_table follows rand_on / rand_bound: whether the push variant's auto-reset is the table-driven one
+static int32_t sync_push_table(orr_handle* h, const char* what) {
+  const int t = h->rand_on || h->rand_bound ? 1 : 0;
+  if (t == h->tab_host.push_table) return 0;
+  HIPCHK(hipMemcpy(&h->tab_dev->push_table, &t, sizeof(t), hipMemcpyHostToDevice), what);
+  h->tab_host.push_table = t;
+  return 0;
+}
+
 int32_t orr_set_randomizer(orr_handle* h, const orr_randomizer* host) {
   if (!h) return fail(-1, "orr_set_randomizer: null handle");
   orr_randomizer r = host ? *host : builtin_randomizer();
@@ -536,7 +548,7 @@ int32_t orr_set_randomizer(orr_handle* h, const orr_randomizer* host) {
   HIPCHK(hipMemcpy(&h->tab_dev->rnd, &r, sizeof(r), hipMemcpyHostToDevice), "orr_set_randomizer: hipMemcpy");
   h->tab_host.rnd = r;
   h->rand_on = host != nullptr;
-  return 0;
+  return sync_push_table(h, "orr_set_randomizer: hipMemcpy");
 }
 
 int32_t orr_bind_randomizer_params(orr_handle* h, float* params_dev, int32_t suspend) {
@@ -550,6 +562,49 @@ int32_t orr_bind_randomizer_params(orr_handle* h, float* params_dev, int32_t sus
   h->tab_host.rand_params = v.p;
   h->tab_host.rand_suspend = v.s;
   h->rand_bound = params_dev != nullptr;
+  return sync_push_table(h, "orr_bind_randomizer_params: hipMemcpy");
+}
+
+int32_t orr_set_push(orr_handle* h, const orr_push* push_host) {
+  if (!h) return fail(-1, "orr_set_push: null handle");
+  orr_push p;
+  memset(&p, 0, sizeof(p));
+  if (push_host) p = *push_host;
+  const float vmax = h->cfg.max_coord_velocity;   // the physics clamps every coordinate velocity there: a larger kick would not arrive
+  const struct { const char* name; float v; bool speed; } fields[] = {
+      {"prob", p.prob, false}, {"lin_lo", p.lin_lo, true}, {"lin_hi", p.lin_hi, true}, {"lin_z", p.lin_z, true}, {"ang", p.ang, true}};
+  char m[200];
+  for (const auto& f : fields) {
+    const char* why = nullptr;
+    if (!(fabsf(f.v) < INFINITY)) why = "must be a finite number";      // NaN fails the comparison
+    else if (f.v < 0.0f) why = "must be >= 0";
+    else if (!f.speed && f.v > 1.0f) why = "must be a probability in [0, 1]";
+    else if (f.speed && f.v > vmax) why = "is above orr_config::max_coord_velocity";
+    if (why) {
+      snprintf(m, sizeof(m), "orr_set_push: %s %s", f.name, why);
+      return fail(-1, m);
+    }
+  }
+  if (p.lin_lo > p.lin_hi) return fail(-1, "orr_set_push: lin_lo > lin_hi");
+  if (p.grace_steps < 0) return fail(-1, "orr_set_push: grace_steps must be >= 0");
+  const bool on = p.prob > 0.0f;
+  if (on && h->anchor_types)
+    return fail(-1, "orr_set_push: friction anchors (orr_model::friction_anchor) and pushes cannot be combined");
+  // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->push, &p, sizeof(p), hipMemcpyHostToDevice), "orr_set_push: hipMemcpy");
+  h->tab_host.push = p;
+  h->push_on = on;
+  return 0;
+}
+
+int32_t orr_bind_push_outputs(orr_handle* h, float* push_dev) {
+  if (!h) return fail(-1, "orr_bind_push_outputs: null handle");
+  if (((uintptr_t)push_dev & 15u) != 0) return fail(-1, "orr_bind_push_outputs: push_dev must be 16-byte aligned (rows of ORR_PUSH_ROW floats)");
+  if (push_dev && h->anchor_types)
+    return fail(-1, "orr_bind_push_outputs: friction anchors (orr_model::friction_anchor) and push outputs cannot be combined");
+  HIPCHK(hipMemcpy(&h->tab_dev->push_out, &push_dev, sizeof(push_dev), hipMemcpyHostToDevice), "orr_bind_push_outputs: hipMemcpy");
+  h->tab_host.push_out = push_dev;
+  h->push_bound = push_dev != nullptr;
   return 0;
 }
 
@@ -599,7 +654,7 @@ static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1)
 // clip sets (both refuse friction anchors: kRefused, the message starts with the entry point's name `who`), then friction anchors, then
 // the batch size; only the env step has a two-wave and only the env step and the debug physics have an anchor instantiation, every other
 // entry point runs its default one instead.
-enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts, kActuator, kSensor, kRandomizer };
+enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts, kActuator, kSensor, kRandomizer, kPush };
 static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {   // (a model with anchors set after orr_bind_contact_outputs)
   if (!(h->contacts_on && h->anchor_types)) return false;
   char m[256];
@@ -607,7 +662,16 @@ static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {
   fail(-1, m);
   return true;
 }
-static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who, bool contacts = true) {
+static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who, bool contacts = true, bool push = false) {
+  if (h->push_on || h->push_bound) {   // ahead of the randomiser: a superset of its env step.  `push` = the entry point has a push variant (orr_step only)
+    if (h->anchor_types) {   // (a model with anchors set after orr_set_push / orr_bind_push_outputs)
+      char m[256];
+      snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and pushes (orr_set_push, orr_bind_push_outputs) cannot be combined", who);
+      fail(-1, m);
+      return kRefused;
+    }
+    if (push) return kPush;
+  }
   if (h->rand_on || h->rand_bound) {   // ahead of sensor noise: supersets of its variants
     if (h->anchor_types) {   // (a model with anchors set after orr_set_randomizer / orr_bind_randomizer_params)
       char m[256];
@@ -685,8 +749,14 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
   if (((uintptr_t)obs_dev & 15u) != 0) return fail(-1, "orr_step: the observation buffer must be 16-byte aligned (it is written in 16-byte pieces)");
 #define ORR_STEP(WPE, ANCHOR, CLIPS, NOISE, msg) \
   HIPCHK((launch_step<0, WPE, ANCHOR, CLIPS, NOISE>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{})), msg)
-  switch (variant_of(h, h->multiclip_types, "orr_step")) {
+  switch (variant_of(h, h->multiclip_types, "orr_step", true, true)) {
     case kRefused: return -1;
+    case kPush:   // one wave per SIMD, any batch size; the superset that also serves the randomiser's table, sensor noise, torque limits and every output binding
+      HIPCHK((launch_step<kModePush | kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream,
+                                                                                                                                            actions_dev, obs_dev, reward_dev, done_dev, 0,
+                                                                                                                                            ReplayArgs{})),
+             "orr_step: launch (push)");
+      break;
     case kRandomizer:   // one wave per SIMD, any batch size; the superset that also serves sensor noise, torque limits and every output binding
       HIPCHK((launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream,
                                                                                                                                 actions_dev, obs_dev, reward_dev, done_dev, 0,

@@ -854,6 +854,33 @@ __device__ __forceinline__ void store_rand_row(const KParams& P, const RandRow& 
   }
 }
 
+// Philox blocks of the pushes (orr_set_push): A = 0x50000000 + 2 s, B = A + 1, s = the env-step counter before the step
+constexpr uint32_t kPushBlock = 0x50000000u;
+// PUSH: the outputs buffer of the handle (NULL = not bound) and whether its auto-reset is the table-driven one, the same in every lane
+__device__ __forceinline__ void load_push_end(const KParams& P, float** out, bool* table) {
+  const unsigned long long p = *(const unsigned long long __attribute__((address_space(1)))*)&P.tab->push_out;
+  const int t = *(const int __attribute__((address_space(1)))*)&P.tab->push_table;
+  const unsigned int plo = __builtin_amdgcn_readfirstlane((unsigned int)p), phi = __builtin_amdgcn_readfirstlane((unsigned int)(p >> 32));
+  *out = reinterpret_cast<float*>(((unsigned long long)phi << 32) | plo);
+  *table = __builtin_amdgcn_readfirstlane(t) != 0;
+}
+// PUSH: the handle's push settings and outputs buffer, each the same in every lane (scalar registers from here on)
+__device__ __forceinline__ PushSet load_push(const KParams& P) {
+  typedef const float __attribute__((address_space(1)))* gfp;
+  const gfp pp = (gfp)&P.tab->push.prob;
+  static_assert(offsetof(orr_push, lin_lo) == 4 && offsetof(orr_push, lin_hi) == 8 && offsetof(orr_push, lin_z) == 12 && offsetof(orr_push, ang) == 16 &&
+                offsetof(orr_push, grace_steps) == 20, "words 0..5");
+  PushSet PS;
+  load_push_end(P, &PS.out, &PS.table);
+  PS.prob = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pp[0])));
+  PS.lin_lo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pp[1])));
+  PS.span = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pp[2]))) - PS.lin_lo;
+  PS.lin_z = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pp[3])));
+  PS.ang = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pp[4])));
+  PS.grace = __builtin_amdgcn_readfirstlane(__float_as_int(pp[5]));
+  return PS;
+}
+
 // 7. observation = sensor histories + target observation (quadruped_gym_env.py:100-102; wrapper_env.py:101-105, 109-125), for the
 // step that just ended and for a reset alike: `episode` / `noise_i` are the robot's own (a reset: the new episode, 0)
 template <bool NOISE = false, bool SENS = false>

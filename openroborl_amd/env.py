@@ -445,6 +445,94 @@ def randomizer_apply(spec, row):
     return out
 
 
+# ---- external pushes (orr_set_push, orr_bind_push_outputs) --------------------------------------------------------------------------
+PUSH_KEYS = ("prob", "interval_s", "lin_vel", "lin_vel_z", "ang_vel", "grace_steps")
+
+
+def push_spec(push=None, action_repeat=cfgmod.ACTION_REPEAT, sim_dt=0.001, max_coord_velocity=100.0):
+    """The push setting -> the orr_push struct.  push: None (off) or a dict with `prob` (probability of a kick per robot and env step) or
+    `interval_s` (mean time between kicks: prob = action_repeat * sim_dt / interval_s), `lin_vel` = (lo, hi) the kick's horizontal
+    speed in m/s, `lin_vel_z` (vertical component in U(-z, z)), `ang_vel` (each component of the angular kick in U(-a, a), rad/s) and
+    `grace_steps` (no kick while the episode's env-step counter is below it); every key but one of prob / interval_s is optional (0).
+    ValueError on anything the C-ABI (orr_set_push) would refuse; the message names the field."""
+    if push is None:
+        return _abi.OrrPush()
+    if not isinstance(push, dict):
+        raise ValueError("push must be None or a dict with the keys %s, not %r" % (", ".join(PUSH_KEYS), push))
+    for k in push:
+        if k not in PUSH_KEYS:
+            raise ValueError("unknown push key %r (known: %s)" % (k, ", ".join(PUSH_KEYS)))
+
+    def number(name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("push: %s must be a number, not %r" % (name, v))
+        if not math.isfinite(float(v)):
+            raise ValueError("push: %s must be a finite number, not %r" % (name, v))
+        if float(v) < 0.0:
+            raise ValueError("push: %s must be >= 0, not %r" % (name, v))
+        return float(v)
+
+    if ("prob" in push) == ("interval_s" in push):
+        raise ValueError("push: give exactly one of prob and interval_s")
+    if "prob" in push:
+        prob = number("prob", push["prob"])
+    else:
+        interval = number("interval_s", push["interval_s"])
+        if not interval > 0.0:
+            raise ValueError("push: interval_s must be > 0, not %r" % (push["interval_s"],))
+        prob = float(action_repeat) * float(sim_dt) / interval
+    if prob > 1.0:
+        raise ValueError("push: %s gives a probability of %r per env step; it must lie in [0, 1]" % ("prob" if "prob" in push else "interval_s", prob))
+    lin = push.get("lin_vel", (0.0, 0.0))
+    if isinstance(lin, (str, dict)) or np.ndim(lin) != 1 or len(lin) != 2:
+        raise ValueError("push: lin_vel must be (lo, hi), not %r" % (lin,))
+    lo, hi = number("lin_vel lo", lin[0]), number("lin_vel hi", lin[1])
+    if lo > hi:
+        raise ValueError("push: lin_vel lo > hi in %r" % (lin,))
+    z, ang = number("lin_vel_z", push.get("lin_vel_z", 0.0)), number("ang_vel", push.get("ang_vel", 0.0))
+    for name, v in (("lin_vel hi", hi), ("lin_vel_z", z), ("ang_vel", ang)):
+        if float(np.float32(v)) > float(np.float32(max_coord_velocity)):
+            raise ValueError("push: %s = %r is above max_coord_velocity = %g (the physics clamps every coordinate velocity there)" % (name, v, max_coord_velocity))
+    grace = push.get("grace_steps", 0)
+    if isinstance(grace, (bool, np.bool_)) or not isinstance(grace, (int, np.integer)):
+        raise ValueError("push: grace_steps must be an integer, not %r" % (grace,))
+    if grace < 0 or grace >= 1 << 31:
+        raise ValueError("push: grace_steps must be >= 0 (and below 2^31), not %r" % (grace,))
+    return _abi.OrrPush(prob=prob, lin_lo=lo, lin_hi=hi, lin_z=z, ang=ang, grace_steps=int(grace))
+
+
+def push_on(spec):
+    """Whether the setting selects the push variant of the step kernel: the probability is above 0."""
+    return spec.prob > 0.0
+
+
+def push_block(s):
+    """Philox blocks (A, B) of the push of the step whose env-step counter before it is s (include/openroborl_hip.h, orr_set_push):
+    A = PUSH_BLOCK + 2 s, B = A + 1, on the stream (seed, robot index, episode) as they are before the step.  Works on integer arrays."""
+    s = np.asarray(s, dtype=np.int64)
+    if (s < 0).any() or (s >= 1 << 27).any():
+        raise ValueError("push_block: s in [0, 2^27)")
+    return _abi.PUSH_BLOCK + 2 * s, _abi.PUSH_BLOCK + 2 * s + 1
+
+
+def push_kick(spec, u8, s=None):
+    """What a step does with the eight uniforms u8 [..., 8] of its blocks A (words 0..3) and B (4..7) under the setting `spec`
+    (push_spec's struct) - the draw rule of orr_set_push in float64, with the float32 settings the device holds (lin_hi - lin_lo as
+    its one float32 subtraction).  s: the env-step counter(s) before the step, for the grace period (None = past it).
+    -> (kicked [...] bool, dv [..., 3], dw [..., 3]); dv = dw = 0 where not kicked."""
+    u8 = np.asarray(u8, dtype=np.float64)
+    prob, lo, z, ang = (float(np.float32(getattr(spec, k))) for k in ("prob", "lin_lo", "lin_z", "ang"))
+    span = float(np.float32(spec.lin_hi) - np.float32(spec.lin_lo))
+    kicked = u8[..., 0] < prob
+    if s is not None:
+        kicked = kicked & (np.asarray(s, dtype=np.int64) >= int(spec.grace_steps))
+    theta = 2.0 * np.pi * u8[..., 1]
+    m = u8[..., 2] * span + lo
+    dv = np.stack([m * np.cos(theta), m * np.sin(theta), u8[..., 3] * (2.0 * z) - z], axis=-1)
+    dw = u8[..., 4:7] * (2.0 * ang) - ang if ang > 0.0 else np.zeros(u8.shape[:-1] + (3,))
+    return kicked, np.where(kicked[..., None], dv, 0.0), np.where(kicked[..., None], dw, 0.0)
+
+
 def action_space():
     """minitaur.py:145-148."""
     return Box(np.array([-2 * math.pi] * 12), np.array([2 * math.pi] * 12), dtype=np.float32)
@@ -460,8 +548,10 @@ class VecQuadrupedEnv(object):
                  robot_index_offset=0, legacy_grid=False, mixed_robots=None, ep_log_capacity=65536, config_overrides=None,
                  model_overrides=None, clip_time_min=None, clip_time_max=None, perturb_init_state_prob=None, tar_obs_noise=None,
                  init_perturb_std=None, reward_terms=False, contact_outputs=False, torque_limits=None, actuator_outputs=False,
-                 observation_noise_stdev=None, randomizer_config=None, randomizer_params=False):
+                 observation_noise_stdev=None, randomizer_config=None, randomizer_params=False, push=None, push_outputs=False):
         import torch
+        if not isinstance(push_outputs, (bool, np.bool_)):
+            raise ValueError("push_outputs must be True or False, got %r" % (push_outputs,))
         if not isinstance(randomizer_params, (bool, np.bool_)):
             raise ValueError("randomizer_params must be True or False, got %r" % (randomizer_params,))
         if not isinstance(reward_terms, (bool, np.bool_)):
@@ -554,6 +644,11 @@ class VecQuadrupedEnv(object):
             randomizer_config = params.get("env_randomizer_config")
         self.randomizer = randomizer_spec(randomizer_config, self.cfg.sim_dt)
         self.randomizer_config = randomizer_config
+        # external pushes (orr_set_push; the task YAML may carry the dict under `push`, which applies in train mode only, like its
+        # enable_env_randomizer): off by default.  Validated here likewise
+        if push is None and mode == "train":
+            push = params.get(cfgmod.PUSH_KEY)
+        self.push = push_spec(push, self.cfg.action_repeat, self.cfg.sim_dt, self.cfg.max_coord_velocity)
         # motor torque limits (MotorModel's torque_limits): the user's data, none by default - no shipped robot table carries any
         self.torque_limits = torque_limit_spec(torque_limits, sorted(set(self.robot_names)))
         self.robot_type = robot_type
@@ -637,6 +732,12 @@ class VecQuadrupedEnv(object):
             self.set_randomizer(randomizer_config)
         if randomizer_params:
             self.bind_randomizer_params(True)
+        # what the pushes did to each robot (orr_bind_push_outputs): None while unbound
+        self.push_out = None
+        if push_on(self.push):
+            self.set_push(push)
+        if push_outputs:
+            self.bind_push_outputs(True)
 
     # ---- reference attribute surface -------------------------------------------------------
     @property
@@ -719,6 +820,32 @@ class VecQuadrupedEnv(object):
             t.cuda.synchronize(self.device)      # launches in flight still write the buffer
             _lib.check(self.L.orr_bind_randomizer_params(self.h, None, 0), self.L)
             self.randomizer_rows, self.randomizer_suspended = None, False
+        self.launch_params_generation += 1
+
+    def set_push(self, push=None):
+        """Change the external pushes of a running env (orr_set_push; see push_spec for `push`, None = off): read from the next step on.
+        A probability above 0 selects the push variant of the step kernel: holders of captured graphs re-capture
+        (launch_params_generation); the variant's first launch in a process loads its code object, so step once eagerly before a capture."""
+        spec = push_spec(push, self.cfg.action_repeat, self.cfg.sim_dt, self.cfg.max_coord_velocity)
+        _lib.check(self.L.orr_set_push(self.h, None if push is None else C.byref(spec)), self.L)
+        self.push = spec
+        self.launch_params_generation += 1
+
+    def bind_push_outputs(self, on=True):
+        """Bind (allocating on first use) or unbind the push outputs (orr_bind_push_outputs): env.push_out [N, 8], a robot's row = dv x y
+        z, dw x y z of the last step (world frame, zeros where the robot was not kicked), 1.0 / 0.0 whether it was kicked, and the
+        number of kicks in its current episode including that step; None while unbound.  Privileged information: no observation holds
+        it.  A bound buffer selects the push variant whatever the probability: holders of captured graphs re-capture
+        (launch_params_generation); the variant's first launch in a process loads its code object, so step once eagerly before a capture."""
+        t = self.torch
+        t.cuda.synchronize(self.device)          # launches in flight still write the buffer
+        if on:
+            out = self.push_out if self.push_out is not None else t.zeros((self.num_robot, _abi.PUSH_ROW), dtype=t.float32, device=self.device)
+            _lib.check(self.L.orr_bind_push_outputs(self.h, out.data_ptr()), self.L)
+            self.push_out = out
+        else:
+            _lib.check(self.L.orr_bind_push_outputs(self.h, None), self.L)
+            self.push_out = None
         self.launch_params_generation += 1
 
     def get_randomization_parameters(self):
@@ -1093,7 +1220,7 @@ class LegacyListEnv(object):
     INIT_MOTOR_ANGLES added in place (minitaur.py:281).
     """
 
-    def __init__(self, env, mutate_actions=True, torque_limits=None, actuator_outputs=False, observation_noise_stdev=None):
+    def __init__(self, env, mutate_actions=True, torque_limits=None, actuator_outputs=False, observation_noise_stdev=None, push=None, push_outputs=False):
         if env.cfg.flags & _abi.FLAG_AUTO_RESET:
             raise ValueError("LegacyListEnv needs a VecQuadrupedEnv created with auto_reset=False")
         if not isinstance(actuator_outputs, (bool, np.bool_)):
@@ -1104,6 +1231,12 @@ class LegacyListEnv(object):
             env.bind_actuator_outputs(True)
         if observation_noise_stdev is not None:     # Minitaur._observation_noise_stdev, passed through to the env
             env.set_sensor_noise(observation_noise_stdev)
+        if not isinstance(push_outputs, (bool, np.bool_)):
+            raise ValueError("push_outputs must be True or False, got %r" % (push_outputs,))
+        if push is not None:                         # external pushes and their outputs, passed through to the env
+            env.set_push(push)
+        if push_outputs:
+            env.bind_push_outputs(True)
         self._env = env
         self._mutate = mutate_actions
         self.num_robot = env.num_robot

@@ -1,5 +1,5 @@
 """Step time of a variant of the step kernel against its baseline, 4096 robots, same process, alternated (train semantics):
-python tools/diag/variant_time.py --case noise|terms|contacts|actuator|sensor|randomizer|anchor
+python tools/diag/variant_time.py --case noise|terms|contacts|actuator|sensor|randomizer|push|anchor
 
   noise     the task-noise variant against the clip-set variant (a two-clip set, so that the plain env runs the clip-set variant)
   terms     reward terms on top of task noise               (two-clip set, noise on in all at one setting: prob 0.5, sigma 0.1)
@@ -16,6 +16,11 @@ python tools/diag/variant_time.py --case noise|terms|contacts|actuator|sensor|ra
   randomizer the table-driven randomiser ("all_params": the built-in six ranges as a table), then the params buffer as well, on top of the
             sensor variant (all three deviations and bindings on, the same set and task noise): the cost of the table-driven reset and
             of the row's store, both outside the sub-step loop; also the episodes each env finished (auto-resets) while timed
+  push      external pushes on top of the randomiser variant with everything else equal (the table "all_params", all three deviations
+            and bindings on, the same set and task noise): the push variant at prob 0 with the outputs bound - the cost of the two
+            settings' loads, block A, the sine / cosine and the row's store, all outside the sub-step loop - then at prob 0.02
+            (lin_vel 0.2 .. 0.6, lin_vel_z 0.2, ang_vel 0.5: block B too, and what the kicks do to the robots); also the episodes each
+            env finished (auto-resets) while timed and the kicks per launch
   anchor    the friction-anchor variant against the default kernel (the task's own clip, no noise)
 
 Every env gets 300 warm-up steps of stress actions, then 5 rounds of 300 back-to-back launches with fixed actions go round the envs in
@@ -53,6 +58,11 @@ CASES = {
                    (("task noise + all three outputs + sensor noise", {}),
                     ("the same + the randomiser's table (all_params)", dict(randomizer_config="all_params")),
                     ("the same + the randomiser's table (all_params) + params buffer", dict(randomizer_config="all_params", randomizer_params=True)))),
+    "push": (dict(TWO_CLIPS, contact_outputs=True, reward_terms=True, actuator_outputs=True, observation_noise_stdev=[0.01, 0.0, 0.0, 0.02, 0.1],
+                  randomizer_config="all_params", **NOISE),
+             (("task noise + all three outputs + sensor noise + the randomiser's table", {}),
+              ("the same + push at prob 0, outputs bound", dict(push=dict(prob=0.0, lin_vel=(0.2, 0.6), lin_vel_z=0.2, ang_vel=0.5), push_outputs=True)),
+              ("the same + push at prob 0.02, outputs bound", dict(push=dict(prob=0.02, lin_vel=(0.2, 0.6), lin_vel_z=0.2, ang_vel=0.5), push_outputs=True)))),
     "anchor": ({}, (("default", {}), ("friction anchors", dict(model_overrides={"laikago": {"friction_anchor": 1}})))),
 }
 
@@ -86,7 +96,10 @@ if case == "contacts":
     gait = envs[1].episode_gait()
     print("gait of the logged episodes (stress actions): duty %s, mean normal force [N] %s" % (
         " ".join("%.3f" % x for x in gait.get("duty", [])), " ".join("%.1f" % x for x in gait.get("normal_force", []))))
-if case == "randomizer":
+if case == "push":
+    for (name, _), env in zip(variants[1:], envs[1:]):
+        print("%-76s %.1f robots kicked in the last launch" % (name, float(env.push_out[:, 6].sum().item())))
+if case in ("randomizer", "push"):
     for (name, _), env, f0 in zip(variants, envs, finished):
         print("%-68s %.1f episodes ended (auto-resets) per launch while timed" % (name, (f0 + int(env.counters[_abi.CNT_EPISODES].item())) / float(ROUNDS * LAUNCHES)))
 if case == "actuator":

@@ -61,6 +61,8 @@ ACTUATOR_STEP_KERNELS = (("_Z15orr_step_kernelILi28ELi1ELb0ELb1ELb1E", "step ker
 SENSOR_STEP_KERNELS = (("_Z15orr_step_kernelILi60ELi1ELb0ELb1ELb1E", "step kernel with sensor noise on top of the actuator variant (one wave per SIMD)"),)
 # the randomiser unit's (orr_kernels_randomizer.hip; MODE = kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0), likewise
 RANDOMIZER_STEP_KERNELS = (("_Z15orr_step_kernelILi124ELi1ELb0ELb1ELb1E", "step kernel with the table-driven randomiser on top of the sensor variant (one wave per SIMD)"),)
+# the push unit's (orr_kernels_push.hip; MODE = kModePush | kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0), likewise
+PUSH_STEP_KERNELS = (("_Z15orr_step_kernelILi252ELi1ELb0ELb1ELb1E", "step kernel with external pushes on top of the randomiser variant (one wave per SIMD)"),)
 
 
 def compile_units(extra_flags=(), only_main=False, units=("env", "w2", "anchor")):
@@ -69,11 +71,11 @@ def compile_units(extra_flags=(), only_main=False, units=("env", "w2", "anchor")
     tests/test_isa_budget.py address by index (0 main, 1 two-wave, 2 friction anchors), "multiclip" adds the clip-set unit, "noise" the
     task-noise unit, "terms" (_lib.TERMS_UNITS, behind them) the reward-terms unit, "contacts" (_lib.CONTACT_UNITS) the
     contact-output unit, "actuator" (_lib.ACTUATOR_UNITS) the actuator unit, "sensor" (_lib.SENSOR_UNITS) the sensor-noise unit, "randomizer"
-    (_lib.RANDOMIZER_UNITS, last) the randomiser unit."""
+    (_lib.RANDOMIZER_UNITS) the randomiser unit, "push" (_lib.PUSH_UNITS, last) the push unit."""
     src_dir = os.path.dirname(os.environ.get("ORR_ISA_SRC", _lib.SRC))      # another tree's orr_kernels.hip (A/B of code generation)
     out_dir = tempfile.mkdtemp()
     listings = []
-    for name, src, flags, _ in (_lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS + _lib.SENSOR_UNITS + _lib.RANDOMIZER_UNITS)[:1 if only_main else None]:
+    for name, src, flags, _ in (_lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS + _lib.SENSOR_UNITS + _lib.RANDOMIZER_UNITS + _lib.PUSH_UNITS)[:1 if only_main else None]:
         src = os.path.join(src_dir, os.path.basename(src))
         if name not in units or not os.path.exists(src):      # (an older tree has fewer units)
             continue
@@ -175,10 +177,10 @@ def resources(meta, sym):
 
 
 def main():
-    lines = [l for u in compile_units(sys.argv[1:], units=[u[0] for u in _lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS + _lib.SENSOR_UNITS + _lib.RANDOMIZER_UNITS]) for l in u]
+    lines = [l for u in compile_units(sys.argv[1:], units=[u[0] for u in _lib.ALL_ENV_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS + _lib.SENSOR_UNITS + _lib.RANDOMIZER_UNITS + _lib.PUSH_UNITS]) for l in u]
     meta = "\n".join(lines)
     # one report per variant of the step kernel (WPE 1: one wave per SIMD, WPE 2: two; see orr_env_kernels.h)
-    for sym, title in STEP_KERNELS + TERMS_STEP_KERNELS + CONTACT_STEP_KERNELS + ACTUATOR_STEP_KERNELS + SENSOR_STEP_KERNELS + RANDOMIZER_STEP_KERNELS:
+    for sym, title in STEP_KERNELS + TERMS_STEP_KERNELS + CONTACT_STEP_KERNELS + ACTUATOR_STEP_KERNELS + SENSOR_STEP_KERNELS + RANDOMIZER_STEP_KERNELS + PUSH_STEP_KERNELS:
         k = parse_kernel(lines, sym)
         if k is None:
             continue

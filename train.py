@@ -44,6 +44,10 @@ def main():
                     help="standard deviations of the sensor noise: motor angle (rad), motor velocity, motor torque, base roll / pitch / yaw (rad) "
                          "and their rates (rad/s), the reference robot's _observation_noise_stdev; velocity and torque are accepted and have no "
                          "consumer (default: none)")
+    ap.add_argument("--push", type=push_arg, default=None, metavar="PROB,LO,HI[,Z,ANG[,GRACE]]",
+                    help="external pushes while training: probability of a velocity kick per robot and env step, its horizontal speed range "
+                         "(m/s), optionally the vertical bound (m/s) and the angular bound per axis (rad/s), optionally the env steps at "
+                         "the start of an episode without kicks; overrides the task YAML's `push` (default: none; never in --eval)")
     ap.add_argument("--reward-terms", action="store_true",
                     help="also output the five unweighted terms of the imitation reward on the device (pose, velocity, end effector, root pose, "
                          "root velocity): every logged record gains \"reward_terms\": {name: mean per step} over the episodes THIS rank finished "
@@ -88,7 +92,7 @@ def main():
                           device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
                           perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise,
                           reward_terms=args.reward_terms, contact_outputs=args.contact_outputs, observation_noise_stdev=args.sensor_noise,
-                          **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
+                          push=args.push, **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     model = ppo.ActorCritic(dev, params=params, seed=args.seed)                     # same seed -> identical replicas
     if not args.torch_policy:
@@ -174,6 +178,23 @@ def sensor_noise_arg(text):
         return [float(x) for x in parts]
     except ValueError:
         raise argparse.ArgumentTypeError("not a number in %r" % (text,))
+
+
+def push_arg(text):
+    """--push prob,lo,hi[,z,ang[,grace]] -> the env's push dict (validated by the env: openroborl_amd.env.push_spec)."""
+    parts = text.split(",")
+    if len(parts) not in (3, 5, 6):
+        raise argparse.ArgumentTypeError("prob,lo,hi or prob,lo,hi,z,ang or prob,lo,hi,z,ang,grace")
+    try:
+        v = [float(x) for x in parts[:5]]
+        push = dict(prob=v[0], lin_vel=(v[1], v[2]))
+        if len(parts) >= 5:
+            push.update(lin_vel_z=v[3], ang_vel=v[4])
+        if len(parts) == 6:
+            push["grace_steps"] = int(parts[5])
+    except ValueError:
+        raise argparse.ArgumentTypeError("not a number in %r" % (text,))
+    return push
 
 
 def clip_time_kwargs(args):
