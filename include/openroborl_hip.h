@@ -430,6 +430,37 @@ int32_t orr_sizeof_push(void);
 #define ORR_PUSH_ROW 8
 int32_t orr_bind_push_outputs(orr_handle* h, float* push_dev /* [N][ORR_PUSH_ROW] */);
 
+/* Privileged observation: what the simulator knows about each robot and no sensor reports, for an asymmetric critic
+ * (orr_policy_forward_priv, openroborl_policy.h).  priv_dev float[N][ORR_PRIV_DIM] (device, 16-byte aligned); done_dev uint8[N] = the
+ * done flags of the step just taken, or NULL (after a reset).  One launch (csrc/orr_kernels_priv.hip); it reads, and changes nothing.
+ * The row of robot i is built from its state record as it stands when the launch runs - the state the current observation belongs
+ * to: after an auto-reset the new episode's - and from the output buffers the handle has bound at that moment:
+ *   words 0..2    R^T LINVEL: the base's linear velocity in the base frame.  R = the rotation matrix of rel = QUAT (x) INIT_QUAT^-1 of
+ *                 the robot's type (the orientation relative to the initial one that the observation's IMU reading starts from), by
+ *                 the standard quaternion-to-matrix formula, rel not renormalised
+ *         3..5    R^T ANGVEL
+ *         6..8    R^T (0, 0, -1): the direction of gravity in the base frame
+ *         9       POS[2]
+ *         10..21  STRENGTH[12]
+ *         22      LATENCY / ((ORR_RING_DEPTH - 2) * sim_dt)
+ *         23      FOOT_MU
+ *         24..27  KNEE_FRICTION[4] * 20
+ *         28..31  MASS_RATIO[2], INERTIA_RATIO[2]
+ *         32..35  per leg 1.0 if the contact row's normal sum (contact_dev[i][leg][0], orr_bind_contact_outputs) is > 0, else 0.0
+ *         36..39  per leg that normal sum / (action_repeat * sim_dt) / 100: the step's mean normal force in units of 100 N
+ *         40..45  push_dev[i][0..5] (orr_bind_push_outputs): dv, dw of the step
+ *         46      EP_STEP / max(MAX_EP_STEPS, 1), both as floats
+ *         47      0
+ *   Words 32..39 are 0 while no contact outputs are bound and words 40..45 while no push outputs are bound.  Words 32..45 are also 0
+ *   for a robot whose done_dev byte is non-zero (those buffers still describe the episode that ended, the record is the new one), and
+ *   for every robot with done_dev == NULL (after a reset the buffers hold no step of the current episode).
+ *   The divisors (ORR_RING_DEPTH - 2) * sim_dt and action_repeat * sim_dt are formed once on the host, in float32; the device
+ *   multiplies and divides in float32 in the order written.
+ * Refused, nothing written: a null handle or buffer, a priv_dev that is not 16-byte aligned, no state bound (orr_bind).  Friction
+ * anchors are not refused: nothing here depends on them. */
+#define ORR_PRIV_DIM 48
+int32_t orr_privileged_obs(orr_handle* h, const uint8_t* done_dev, float* priv_dev, void* stream);
+
 /* reward terms (ImitationTask._calc_reward_pose / _velocity / _end_effector / _root_pose / _root_velocity, imitation_task.py:358-516).
  * terms_dev float[N][5] (device): every orr_step and orr_debug_replay_step writes, for every robot of the shard, the five UNWEIGHTED
  *   terms r_k = exp(-scale_k err_k) of the reward it wrote to reward_dev, in orr_config::reward_w's order: pose, velocity, end effector,

@@ -55,6 +55,15 @@ typedef struct orr_policy_net {
 int32_t orr_policy_forward(const orr_policy_net* net, const float* obs, int32_t n, const float* noise, float std, float clip,
                            float* action, float* raw, float* value, float* mean, void* stream);
 
+/* The same with a privileged critic (the asymmetric actor-critic): the critic's layer 0 reads obs | priv, the actor is untouched.
+ *   net->w0_vf  the packed image of a (160 + 48) x 512 matrix (orr_policy_pack with k = 208): rows 0..159 multiply obs[.][0..159],
+ *               rows 160..207 multiply priv[.][0..47]; every other member as above
+ *   priv        [n][48] the privileged observation (orr_privileged_obs, openroborl_hip.h: ORR_PRIV_DIM has the same value)
+ * The actor path runs the same code on the same inputs: action, raw and mean equal orr_policy_forward's bit for bit. */
+#define ORR_POLICY_PRIV_DIM 48
+int32_t orr_policy_forward_priv(const orr_policy_net* net, const float* obs, const float* priv, int32_t n, const float* noise,
+                                float std, float clip, float* action, float* raw, float* value, float* mean, void* stream);
+
 /* Per-robot GAE(lambda) over a [T][N] rollout segment + per-robot advantage standardisation, one launch
  * (reference: add_vtarg_and_adv, agents/ppo_imitation.py:68-93, and the per-robot normalisation :329-338; device
  * layout and the deliberate use of each robot's own done flags: openroborl_amd/rollout.py).

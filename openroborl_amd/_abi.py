@@ -151,6 +151,11 @@ PUSH_ROW = 8                        # floats per robot in the outputs buffer: dv
 PUSH_BLOCK = 0x50000000             # Philox blocks of the step whose env-step counter before it is s: PUSH_BLOCK + 2 s (A) and + 2 s + 1 (B)
 
 
+# include/openroborl_hip.h: ORR_PRIV_DIM (orr_privileged_obs) = include/openroborl_policy.h: ORR_POLICY_PRIV_DIM (orr_policy_forward_priv)
+PRIV_DIM = 48
+POLICY_PRIV_DIM = 48
+
+
 class OrrPush(C.Structure):
     """include/openroborl_hip.h: orr_push (orr_set_push)."""
     _fields_ = [(n, C.c_float) for n in PUSH_FIELDS] + [("grace_steps", C.c_int32)]

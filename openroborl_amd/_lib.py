@@ -23,6 +23,7 @@ SRC_ACTUATOR = os.path.join(CSRC, "orr_kernels_actuator.hip")    # the variants 
 SRC_SENSOR = os.path.join(CSRC, "orr_kernels_sensor.hip")        # the variants of step and reset whose sensor readings carry Gaussian noise
 SRC_RANDOMIZER = os.path.join(CSRC, "orr_kernels_randomizer.hip")  # the variants of step and reset with the table-driven, controllable randomiser
 SRC_PUSH = os.path.join(CSRC, "orr_kernels_push.hip")            # the variant of the step that kicks the robot's base twist (external pushes)
+SRC_PRIV = os.path.join(CSRC, "orr_kernels_priv.hip")            # the privileged observation (orr_privileged_obs): a gather kernel of its own, plain flags
 SRC_POLICY = os.path.join(CSRC, "orr_policy.hip")
 SRC_LEARNER = os.path.join(CSRC, "orr_learner.hip")              # the non-GEMM part of the PPO update (include/openroborl_learner.h)
 # what the library is built from = what the stale-library check hashes: every source and header under csrc/ + the public headers
@@ -96,13 +97,16 @@ RANDOMIZER_UNITS = [("randomizer", SRC_RANDOMIZER, HIPCC_FLAGS, False)]
 # The eleventh unit of the env kernels, the push variant of the step (orr_set_push, orr_bind_push_outputs): likewise, a table of its own
 # behind RANDOMIZER_UNITS
 PUSH_UNITS = [("push", SRC_PUSH, HIPCC_FLAGS, False)]
+# The twelfth unit of the env kernels, the privileged observation (orr_privileged_obs): a table of its own behind PUSH_UNITS.  Not a variant
+# of step or reset but a small gather kernel: the plain flags, and neither tuning defines nor extra_flags reach it (it has no KParams)
+PRIV_UNITS = [("priv", SRC_PRIV, HIPCC_FLAGS_PLAIN, False)]
 
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
     "orr_layout_offset", "orr_layout_size", "orr_layout_is_int", "orr_sizeof_config", "orr_sizeof_model",
-    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_set_push", "orr_sizeof_push", "orr_bind_push_outputs", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
+    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_set_push", "orr_sizeof_push", "orr_bind_push_outputs", "orr_privileged_obs", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
-    "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_gae", "orr_gae_flags",
+    "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
 ]
 
@@ -180,7 +184,7 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
             tag = ".%d" % os.getpid()
             tmp_so = out_path + tag + ".tmp"
             objs, cmds = [], []
-            for unit in ALL_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS + PUSH_UNITS:
+            for unit in ALL_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS + PUSH_UNITS + PRIV_UNITS:
                 name, src, flags, hashed = unit
                 flags = [f for f in flags if f != "-shared"] + ["-c"]
                 if hashed:
@@ -280,6 +284,8 @@ def load():
     L.orr_sizeof_push.restype = C.c_int32
     L.orr_bind_push_outputs.restype = C.c_int32
     L.orr_bind_push_outputs.argtypes = [vp, vp]
+    L.orr_privileged_obs.restype = C.c_int32
+    L.orr_privileged_obs.argtypes = [vp, vp, vp, vp]
     L.orr_bind_clip_log.restype = C.c_int32
     L.orr_bind_clip_log.argtypes = [vp, vp]
     L.orr_bind_reward_terms.restype = C.c_int32
@@ -321,6 +327,8 @@ def load():
     L.orr_gae_flags.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float, vp, vp, vp]
     L.orr_policy_forward.restype = C.c_int32
     L.orr_policy_forward.argtypes = [C.POINTER(_abi.OrrPolicyNet), vp, C.c_int32, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]
+    L.orr_policy_forward_priv.restype = C.c_int32
+    L.orr_policy_forward_priv.argtypes = [C.POINTER(_abi.OrrPolicyNet), vp, vp, C.c_int32, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]
     # include/openroborl_learner.h
     L.orr_learner_workspace_floats.restype = C.c_int64
     L.orr_learner_workspace_floats.argtypes = [C.c_int32, C.c_int32]

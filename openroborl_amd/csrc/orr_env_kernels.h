@@ -11,6 +11,8 @@
 // orr_bind_actuator_outputs).  orr_kernels_sensor.hip: the variants whose sensor readings carry Gaussian noise (orr_set_sensor_noise).
 // orr_kernels_randomizer.hip: the variants whose resets run the table-driven randomiser (orr_set_randomizer, orr_bind_randomizer_params).
 // orr_kernels_push.hip: the env step that kicks the robot's base twist (orr_set_push, orr_bind_push_outputs).
+// (A twelfth unit, orr_kernels_priv.hip, includes this header for the record's layout and the device table only: it holds the kernel of
+// orr_privileged_obs, no variant of step or reset, and is compiled with the plain flags.)
 // An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
 // per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
 // template` only (bottom of this file).
@@ -1068,6 +1070,11 @@ extern template StepLaunch launch_step<kModeRandomizer | kModeSensor | kModeActu
 extern template StepLaunch launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>;                   //   its parity replay,
 extern template StepLaunch launch_step<kModePush | kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>;   // orr_kernels_push.hip: env step with pushes (replays and resets: the randomiser unit's)
 extern template ResetLaunch launch_randomizer_reset<true>;                                                                                     //   reset (and its parity replay)                                                                       //   reset (and its parity replay)
+
+// The privileged observation (orr_privileged_obs): no template and no variants, one kernel in a unit of its own with the plain flags
+// (orr_kernels_priv.hip).  lat_div = (ORR_RING_DEPTH - 2) * sim_dt, step_dt = action_repeat * sim_dt, formed by the caller
+hipError_t launch_privileged_obs(const DevTables* tab, const float* state, int n, const uint8_t* done, float* priv, float lat_div, float step_dt,
+                                 hipStream_t stream);
 
 #ifdef ORR_STAGE_DUMP
 // the stage dump: instantiated in BOTH step units (orr_kernels.hip: WPE 1, orr_kernels_w2.hip: WPE 2), which compile different forms of

@@ -792,6 +792,17 @@ int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float*
   return 0;
 }
 
+// the privileged observation: its kernel lives in orr_kernels_priv.hip (no variants: it reads the record and whatever outputs are bound)
+int32_t orr_privileged_obs(orr_handle* h, const uint8_t* done_dev, float* priv_dev, void* stream) {
+  if (!h) return fail(-1, "orr_privileged_obs: null handle");
+  if (!priv_dev) return fail(-1, "orr_privileged_obs: null buffer");
+  if (((uintptr_t)priv_dev & 15u) != 0) return fail(-1, "orr_privileged_obs: priv_dev must be 16-byte aligned (rows of ORR_PRIV_DIM floats, written in 16-byte pieces)");
+  if (!h->state) return fail(-1, "orr_privileged_obs: handle not bound");
+  const float lat_div = (float)(ORR_RING_DEPTH - 2) * h->cfg.sim_dt, step_dt = (float)h->cfg.action_repeat * h->cfg.sim_dt;
+  HIPCHK(launch_privileged_obs(h->tab_dev, h->state, h->cfg.num_robots, done_dev, priv_dev, lat_div, step_dt, (hipStream_t)stream), "orr_privileged_obs: launch");
+  return 0;
+}
+
 // parity / debug entry point (not part of the drop-in surface): nsub physics sub-steps with fixed motor torques
 int32_t orr_debug_physics(orr_handle* h, const float* torques_dev, uint8_t* fall_dev, int32_t nsub, void* stream) {
   if (!h || !h->state || !torques_dev) return fail(-1, "orr_debug_physics: bad argument");

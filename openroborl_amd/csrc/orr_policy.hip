@@ -25,8 +25,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kObs = ORR_POLICY_OBS_DIM, kH0 = ORR_POLICY_H0, kH1 = ORR_POLICY_H1, kAct = ORR_POLICY_ACT_DIM;
 constexpr int kRows = 16;                       // robots per workgroup
-constexpr int kObsStride = kObs + 1;            // odd strides: the 16 rows of an A fragment fall into distinct LDS banks
-constexpr int kH0Stride = 2 * kH0 + 1;          // actor | critic hidden 0
+constexpr int kPriv = ORR_POLICY_PRIV_DIM;      // privileged columns of the critic's input (orr_policy_forward_priv)
+constexpr int kH0Stride = 2 * kH0 + 1;          // actor | critic hidden 0 (odd, like the observation tile's stride: forward_kernel)
 constexpr int kH1Stride = 2 * kH1 + 1;          // actor | critic hidden 1
 
 __global__ void pack_kernel(const float* __restrict__ w, int K, int N, float* __restrict__ out, long long total) {
@@ -49,6 +49,7 @@ struct Params {
   float* mean;
   int n;
   float std, clip;
+  const float* priv;   // forward_kernel<kObs + kPriv> only; LAST: the fields above keep their offsets in the plain kernel's arguments
 };
 
 // acc[t] += A(16 x 16 k-group kg, from LDS) * B(tile t, k-group kg): four k-steps of v_mfma_f32_16x16x4_f32 per tile.
@@ -65,18 +66,21 @@ __device__ __forceinline__ void mma_group(f32x4 (&acc)[TILES], const float (&a)[
 // `act` points at column 0 of the A operand in LDS (row stride `stride`).  The weight stream is software-pipelined
 // DEPTH k-groups deep (a k-group = 4 MFMA k-steps = one 16-byte load per lane and tile); the A fragments of the next
 // k-group are read from LDS before the MFMAs of the current one.  K / 16 must be a multiple of DEPTH.
-template <int TILES, int K, int DEPTH>
+// KGS, G0: the call covers k-groups [G0, G0 + K / 16) of a packed matrix of KGS k-groups, `act` pointing at column 16 G0 of the A operand
+// (default: all of it) - a matrix whose k-groups are no multiple of the depth is done as two calls.
+template <int TILES, int K, int DEPTH, int KGS = K / 16, int G0 = 0>
 __device__ __forceinline__ void layer(f32x4 (&acc)[TILES], const float* __restrict__ wp, int nt0, const float* act, int stride, int lane) {
   constexpr int KG = K / 16;
   static_assert(KG % DEPTH == 0, "k-groups must be a multiple of the pipeline depth");
-  const f32x4* w4 = reinterpret_cast<const f32x4*>(wp) + (size_t)nt0 * KG * 64 + lane;   // tile t, k-group g: w4[(t * KG + g) * 64]
+  static_assert(G0 + KG <= KGS, "k-groups of the packed matrix");
+  const f32x4* w4 = reinterpret_cast<const f32x4*>(wp) + ((size_t)nt0 * KGS + G0) * 64 + lane;   // tile t, k-group G0 + g: w4[(t * KGS + g) * 64]
   const float* arow = act + (lane & 15) * stride + (lane >> 4);                             // k-group g, k-step j: arow[16 g + 4 j]
   f32x4 b[DEPTH][TILES];
   float a[2][4];
 #pragma unroll
   for (int d = 0; d < DEPTH - 1; d++)
 #pragma unroll
-    for (int t = 0; t < TILES; t++) b[d][t] = w4[(t * KG + d) * 64];
+    for (int t = 0; t < TILES; t++) b[d][t] = w4[(t * KGS + d) * 64];
 #pragma unroll
   for (int j = 0; j < 4; j++) a[0][j] = arow[4 * j];
 #pragma unroll 1
@@ -86,11 +90,16 @@ __device__ __forceinline__ void layer(f32x4 (&acc)[TILES], const float* __restri
       const int g = g0 + d;
       if (g + DEPTH - 1 < KG) {
 #pragma unroll
-        for (int t = 0; t < TILES; t++) b[(d + DEPTH - 1) % DEPTH][t] = w4[(t * KG + g + DEPTH - 1) * 64];
+        for (int t = 0; t < TILES; t++) b[(d + DEPTH - 1) % DEPTH][t] = w4[(t * KGS + g + DEPTH - 1) * 64];
       }
-      if (g + 1 < KG) {
+      if constexpr (DEPTH % 2 == 0) {
+        if (g + 1 < KG) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) a[(d + 1) & 1][j] = arow[16 * (g + 1) + 4 * j];
+          for (int j = 0; j < 4; j++) a[(d + 1) & 1][j] = arow[16 * (g + 1) + 4 * j];
+        }
+      } else if (g > 0) {   // an odd depth: d does not tell the parity of g, so no second A buffer - the k-group's own fragments, read here
+#pragma unroll
+        for (int j = 0; j < 4; j++) a[d & 1][j] = arow[16 * g + 4 * j];
       }
       mma_group<TILES>(acc, a[d & 1], b[d]);
     }
@@ -109,7 +118,24 @@ __device__ __forceinline__ void store_relu(const f32x4 (&acc)[TILES], const floa
   }
 }
 
+// The critic's layer 0 of forward_kernel<kObs + kPriv>: 208 / 16 = 13 k-groups, which no pipeline depth above 1 divides.
+// 1: twelve k-groups at depth 2 + the last one on its own (its weights are fetched behind the twelve);  0: all thirteen at depth 1 (no
+// weight of the next k-group in flight during the MFMAs of the current one).  12 + 1 ships: MI355X, n = 4096, medians of 5 x 300
+// alternated launches in one process (tools/diag/privileged_time.py --alt-policy-lib, profiles/privileged_critic.txt): the plain kernel
+// 0.0364 ms, 12 + 1 0.0385 (+5.8 %; the 96 added MFMAs on 1728 per wave are +5.6 %), depth 1 0.0387 (+6.3 %).  Both give the same bits
+// (the k-groups are accumulated in the same order).  The switch stays for that tool.
+#ifndef ORR_POLICY_PRIV_SPLIT
+#define ORR_POLICY_PRIV_SPLIT 1
+#endif
+
+// KV: the width of the critic's input.  kObs: actor and critic read the observation (orr_policy_forward).  kObs + kPriv: the critic's
+// layer 0 reads the LDS tile obs | priv against a (kObs + kPriv) x 512 matrix (orr_policy_forward_priv); the actor reads the first kObs
+// columns of the same tile with the same code, so its outputs are bit for bit the plain kernel's.
+template <int KV>
 __global__ __launch_bounds__(256) void forward_kernel(Params P) {
+  constexpr int kObsStride = KV + 1;            // odd strides: the 16 rows of an A fragment fall into distinct LDS banks
+  static_assert(KV >= kObs && KV % 16 == 0 && (kObsStride & 1) == 1, "whole k-groups, odd stride");
+  static_assert((kRows * kObsStride + kRows * kH0Stride + kRows * kH1Stride) * sizeof(float) <= 160 * 1024, "static LDS beyond the 160 KB of a gfx950 CU");
   __shared__ float s_obs[kRows * kObsStride];
   __shared__ float s_h0[kRows * kH0Stride];
   __shared__ float s_h1[kRows * kH1Stride];
@@ -119,6 +145,13 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
   for (int i = tid; i < kRows * kObs; i += 256) {
     const int r = i / kObs, c = i - r * kObs;
     s_obs[r * kObsStride + c] = (row0 + r) < P.n ? P.obs[(size_t)(row0 + r) * kObs + c] : 0.0f;
+  }
+  if constexpr (KV > kObs) {   // privileged columns behind it
+    constexpr int kP = KV - kObs;
+    for (int i = tid; i < kRows * kP; i += 256) {
+      const int r = i / kP, c = i - r * kP;
+      s_obs[r * kObsStride + kObs + c] = (row0 + r) < P.n ? P.priv[(size_t)(row0 + r) * kP + c] : 0.0f;
+    }
   }
   __syncthreads();
   // ---- layer 0: 160 -> 512, actor and critic; this wave: column tiles [8 wave, 8 wave + 8) of each ----
@@ -130,7 +163,15 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
     store_relu<8>(acc, P.net.b0_pi, 8 * wave, s_h0, kH0Stride, lane);
 #pragma unroll
     for (int t = 0; t < 8; t++) acc[t] = f32x4{0, 0, 0, 0};
-    layer<8, kObs, 2>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+    if constexpr (KV == kObs) {
+      layer<8, kObs, 2>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+    } else if constexpr (ORR_POLICY_PRIV_SPLIT) {
+      constexpr int kMain = KV / 32 * 32;       // the k-groups that depth 2 divides
+      layer<8, kMain, 2, KV / 16, 0>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+      layer<8, KV - kMain, 1, KV / 16, kMain / 16>(acc, P.net.w0_vf, 8 * wave, s_obs + kMain, kObsStride, lane);
+    } else {
+      layer<8, KV, 1>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+    }
     store_relu<8>(acc, P.net.b0_vf, 8 * wave, s_h0 + kH0, kH0Stride, lane);
   }
   __syncthreads();
@@ -245,10 +286,26 @@ int32_t orr_policy_forward(const orr_policy_net* net, const float* obs, int32_t 
   if (n == 0) return 0;
   Params P;
   P.net = *net; P.obs = obs; P.noise = noise; P.action = action; P.raw = raw; P.value = value; P.mean = mean;
-  P.n = n; P.std = std; P.clip = clip;
-  hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((n + kRows - 1) / kRows)), dim3(256), 0, (hipStream_t)stream, P);
+  P.n = n; P.std = std; P.clip = clip; P.priv = nullptr;
+  hipLaunchKernelGGL(forward_kernel<kObs>, dim3((unsigned)((n + kRows - 1) / kRows)), dim3(256), 0, (hipStream_t)stream, P);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_policy_forward: launch", e);
+  return 0;
+}
+
+int32_t orr_policy_forward_priv(const orr_policy_net* net, const float* obs, const float* priv, int32_t n, const float* noise, float std, float clip,
+                                float* action, float* raw, float* value, float* mean, void* stream) {
+  if (!net || !obs || !priv || !action || n < 0) return orr_fail(-1, "orr_policy_forward_priv: bad argument", hipSuccess);
+  const float* const* p = reinterpret_cast<const float* const*>(net);
+  for (int i = 0; i < 12; i++)
+    if (!p[i]) return orr_fail(-1, "orr_policy_forward_priv: orr_policy_net has a null pointer", hipSuccess);
+  if (n == 0) return 0;
+  Params P;
+  P.net = *net; P.obs = obs; P.noise = noise; P.action = action; P.raw = raw; P.value = value; P.mean = mean;
+  P.n = n; P.std = std; P.clip = clip; P.priv = priv;
+  hipLaunchKernelGGL(forward_kernel<kObs + kPriv>, dim3((unsigned)((n + kRows - 1) / kRows)), dim3(256), 0, (hipStream_t)stream, P);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_policy_forward_priv: launch", e);
   return 0;
 }
 

@@ -533,6 +533,25 @@ def push_kick(spec, u8, s=None):
     return kicked, np.where(kicked[..., None], dv, 0.0), np.where(kicked[..., None], dw, 0.0)
 
 
+# ---- the privileged observation (orr_privileged_obs): the words of a robot's row, include/openroborl_hip.h ----
+PRIV_DIM = _abi.PRIV_DIM
+PRIV_FIELDS = {"base_lin_vel": slice(0, 3),          # R^T LINVEL, R = the rotation of QUAT (x) INIT_QUAT^-1 (base frame)
+               "base_ang_vel": slice(3, 6),          # R^T ANGVEL
+               "gravity": slice(6, 9),               # R^T (0, 0, -1)
+               "height": slice(9, 10),               # POS[2]
+               "motor_strength": slice(10, 22),      # STRENGTH
+               "latency": slice(22, 23),             # LATENCY / ((RING_DEPTH - 2) * sim_dt)
+               "foot_friction": slice(23, 24),       # FOOT_MU
+               "knee_friction": slice(24, 28),       # KNEE_FRICTION * 20
+               "mass_ratio": slice(28, 30),          # MASS_RATIO
+               "inertia_ratio": slice(30, 32),       # INERTIA_RATIO
+               "foot_contact": slice(32, 36),        # 1.0 / 0.0 per leg (contact outputs)
+               "foot_force": slice(36, 40),          # mean normal force per leg in units of 100 N (contact outputs)
+               "push": slice(40, 46),                # dv, dw of the step (push outputs)
+               "episode_progress": slice(46, 47),    # EP_STEP / max(MAX_EP_STEPS, 1)
+               "reserved": slice(47, 48)}            # 0
+
+
 def action_space():
     """minitaur.py:145-148."""
     return Box(np.array([-2 * math.pi] * 12), np.array([2 * math.pi] * 12), dtype=np.float32)
@@ -1046,6 +1065,24 @@ class VecQuadrupedEnv(object):
                 raise ValueError("step_into: expected a contiguous %s tensor of shape %s on %s" % (dt, shape, self.device))
         _lib.check(self.L.orr_step(self.h, actions.data_ptr(), obs_out.data_ptr(), reward_out.data_ptr(), done_out.data_ptr(), self._stream()), self.L)
         self._env_step_counter += 1
+
+    def privileged_obs(self, out=None, done=None):
+        """The privileged observation (orr_privileged_obs): float32 [N, PRIV_DIM], a robot's row = PRIV_FIELDS, built from its state record
+        as it stands now (the state the current observation belongs to) and from the contact / push outputs while they are bound.
+        done: the uint8 [N] flags of the step just taken - a robot that ended its episode gets zeros in the contact and push words, which
+        still describe that episode; None (after a reset) zeroes them for everybody.  out: a contiguous float32 [N, PRIV_DIM] tensor on
+        the env device (a row of a rollout buffer; 16-byte aligned), allocated when None.  One launch that reads the env and changes
+        nothing; it can be captured into a hipGraph under step_into's conditions (run it once eagerly first: the first launch loads
+        the code object), and a replay reads the buffers that are bound when it runs."""
+        t = self.torch
+        n = self.num_robot
+        if out is None:
+            out = t.empty((n, PRIV_DIM), dtype=t.float32, device=self.device)
+        for x, shape, dt in ((out, (n, PRIV_DIM), t.float32),) + (((done, (n,), t.uint8),) if done is not None else ()):
+            if x.dtype != dt or x.device != self.obs.device or not x.is_contiguous() or tuple(x.shape) != shape:
+                raise ValueError("privileged_obs: expected a contiguous %s tensor of shape %s on %s" % (dt, shape, self.device))
+        _lib.check(self.L.orr_privileged_obs(self.h, None if done is None else done.data_ptr(), out.data_ptr(), self._stream()), self.L)
+        return out
 
     def time_steps(self, actions, num_steps):
         """Bench helper: num_steps back-to-back launches timed with hipEvents on the launch stream (ms)."""

@@ -42,6 +42,9 @@ class FusedPPO(object):
         self.group = group
         self.adam_flags = 1 if mpi_adam_epsilon else 0          # ORR_ADAM_MPI_EPSILON
         self.use_graph = bool(use_graph)
+        # a privileged critic (ppo.ActorCritic(priv_dim=48)): its layer 0 reads x | priv, [M, 160 + 48]; everything behind layer 0 and the
+        # whole actor are what they are without (the kernels of orr_learner.hip see hidden and output layers only)
+        self.priv_dim = int(getattr(model, "priv_dim", 0))
         # ---- one flat buffer for the parameters (16-byte aligned slots), the model's tensors become views of it ----
         names = sorted(model.p)
         self.slots, off = {}, 0
@@ -117,21 +120,25 @@ class FusedPPO(object):
         t = self.torch
         f = lambda *shape: t.empty(shape, dtype=t.float32, device=self.dev)   # noqa: E731
         split = M >= 4096 and M % 16 == 0
+        pd = self.priv_dim
         P = {"B": B, "M": M, "nmb": B // M, "obs": f(B, 160), "aux": f(B, 16), "perm": t.empty(B, dtype=t.int64, device=self.dev),
              "x": f(M, 160), "batch": f(M, 16), "gz2": f(M, 256), "gh1": f(M, 512), "g_pi": f(M, 12), "g_vf": f(M),
              "stats": t.zeros(B // M, 2, dtype=t.float32, device=self.dev),
              "ws": f(int(self.L.orr_learner_workspace_floats(M, 16))), "graphs": None}
         P["aux"].zero_()
+        if pd:      # the privileged observations, gathered with the same permutation; xv = x | xp is the critic's layer-0 input
+            P["priv"], P["xp"], P["xv"] = f(B, pd), f(M, pd), f(M, 160 + pd)
         # the column sums behind the six bias gradients and the two output-layer weight gradients of a minibatch are deferred: each
         # producer leaves its per-workgroup partial sums in its own buffer and ONE launch adds them all up (orr_colsum_finish)
         rows = int(self.L.orr_learner_partial_rows(M))
         jobs = (_abi.OrrColsumJob * 10)()
         for i, (net, k) in enumerate((("pi", 12), ("vf", 1))):
             P["h1_" + net], P["h2_" + net], P["y_" + net] = f(M, 512), f(M, 256), f(M, k)
-            P["part1_" + net], P["part0_" + net] = (f(16, 512, 256), f(16, 160, 512)) if split else (None, None)
+            k0 = 160 + (pd if net == "vf" else 0)          # rows of the net's layer-0 weight
+            P["part1_" + net], P["part0_" + net] = (f(16, 512, 256), f(16, k0, 512)) if split else (None, None)
             if split:
                 jobs[6 + 2 * i] = _abi.OrrColsumJob(P["part1_" + net].data_ptr(), self.g["model/%s_fc1/w:0" % net].data_ptr(), 16, 512 * 256)
-                jobs[7 + 2 * i] = _abi.OrrColsumJob(P["part0_" + net].data_ptr(), self.g["model/%s_fc0/w:0" % net].data_ptr(), 16, 160 * 512)
+                jobs[7 + 2 * i] = _abi.OrrColsumJob(P["part0_" + net].data_ptr(), self.g["model/%s_fc0/w:0" % net].data_ptr(), 16, k0 * 512)
             P["ws2_" + net] = f(int(self.L.orr_learner_workspace_floats(M, 256)))      # [rows][256] | [rows][256 * 12]
             P["ws1_" + net] = f(rows * 512)
             for j, (buf, off, out, cols) in enumerate(((P["ws2_" + net], 0, self.g["model/%s_fc1/b:0" % net], 256),
@@ -150,8 +157,13 @@ class FusedPPO(object):
         t.index_select(P["obs"], 0, idx, out=P["x"])
         t.index_select(P["aux"], 0, idx, out=P["batch"])
         x = P["x"]
+        xin = {"pi": x, "vf": x}                   # each net's layer-0 input
+        if self.priv_dim:
+            t.index_select(P["priv"], 0, idx, out=P["xp"])
+            t.cat((x, P["xp"]), dim=1, out=P["xv"])
+            xin["vf"] = P["xv"]
         for net in NETS:
-            t._addmm_activation(w["model/%s_fc0/b:0" % net], x, w["model/%s_fc0/w:0" % net], out=P["h1_" + net])
+            t._addmm_activation(w["model/%s_fc0/b:0" % net], xin[net], w["model/%s_fc0/w:0" % net], out=P["h1_" + net])
             t._addmm_activation(w["model/%s_fc1/b:0" % net], P["h1_" + net], w["model/%s_fc1/w:0" % net], out=P["h2_" + net])
             t.addmm(w["model/%s/b:0" % net], P["h2_" + net], w["model/%s/w:0" % net], out=P["y_" + net])
         _lib.check(L.orr_ppo_head(P["y_pi"].data_ptr(), P["y_vf"].data_ptr(), P["batch"].data_ptr(), M, float(self.model.std), self.clip,
@@ -164,7 +176,7 @@ class FusedPPO(object):
             self._wgrad(h1, P["gz2"], P["part1_" + net], g["model/%s_fc1/w:0" % net])
             t.mm(P["gz2"], w["model/%s_fc1/w:0" % net].t(), out=P["gh1"])
             _lib.check(L.orr_relu_backward(P["gh1"].data_ptr(), h1.data_ptr(), M, 512, None, P["ws1_" + net].data_ptr(), st), L)
-            self._wgrad(x, P["gh1"], P["part0_" + net], g["model/%s_fc0/w:0" % net])
+            self._wgrad(xin[net], P["gh1"], P["part0_" + net], g["model/%s_fc0/w:0" % net])
         _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
 
     def _allreduce(self):
@@ -217,11 +229,16 @@ class FusedPPO(object):
         P["graphs"] = graphs
 
     # ---- the learner interface (ppo.PPO.update) --------------------------------------------------------------------------
-    def update(self, obs, actions, adv, ret, old_logp=None, epochs=1, generator=None):
-        """obs [B,160], actions [B,12] (unclipped samples), adv [B] (already normalised), ret [B] (TD(lambda) targets);
+    def update(self, obs, actions, adv, ret, old_logp=None, epochs=1, generator=None, priv=None):
+        """obs [B,160], actions [B,12] (unclipped samples), adv [B] (already normalised), ret [B] (TD(lambda) targets); priv [B,48]
+        the privileged observations, for a model with a privileged critic;
         returns the mean (surrogate, value loss) over the minibatches like ppo.PPO.update."""
         t = self.torch
         B = int(obs.shape[0])
+        if (priv is not None) != (self.priv_dim > 0):
+            raise ValueError("FusedPPO: priv is needed by a privileged critic and by no other")
+        if priv is not None and tuple(priv.shape) != (B, self.priv_dim):
+            raise ValueError("FusedPPO: priv must have shape (%d, %d)" % (B, self.priv_dim))
         M = min(self.minibatch, B)
         if B % M:
             raise ValueError("FusedPPO: the number of samples (%d) must be a multiple of the minibatch size (%d); "
@@ -232,6 +249,8 @@ class FusedPPO(object):
                 old_logp = self.model.log_prob(obs, actions)
             P = self._plan(B, M)
             P["obs"].copy_(obs)
+            if priv is not None:
+                P["priv"].copy_(priv)
             aux = P["aux"]
             aux[:, :12].copy_(actions)
             aux[:, 12].copy_(old_logp)

@@ -15,6 +15,7 @@ import zipfile
 import numpy as np
 
 PI_STD = 0.125  # imitation_policies.py:106 pi_init_std
+PRIV_DIM = 48   # width of the privileged observation a privileged critic reads next to the 160 observation words (ppo.ActorCritic(priv_dim=48); no reference counterpart)
 
 
 def _norm_key(k):
@@ -55,7 +56,9 @@ def save_parameters_zip(path, params, data=None):
     for name, shape in SB_PARAMETER_LIST:
         if name in params:
             v = np.asarray(params[name], dtype=np.float32)
-            if v.shape != shape:
+            if name == "model/vf_fc0/w:0" and v.shape == (shape[0] + PRIV_DIM, shape[1]):
+                pass       # a privileged critic (ppo.ActorCritic(priv_dim=48)), written in full: the actor part is what the reference can load
+            elif v.shape != shape:
                 raise ValueError("%s has shape %s, the reference graph expects %s" % (name, v.shape, shape))
         elif name.startswith("model/q/"):
             v = np.zeros(shape, dtype=np.float32)

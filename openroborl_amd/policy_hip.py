@@ -33,10 +33,14 @@ class FusedActorCritic(object):
         self.clip = float(clip)
         self.packed = {}
         self.biases = {}
+        self.priv_dim = 0             # 48 when model/vf_fc0/w:0 has 160 + 48 rows: forward() then takes `priv` and runs orr_policy_forward_priv
         for field, key in KEYS:
             w = params[key]
             if field.startswith("w"):
                 k, n = SHAPES[field]
+                if field == "w0_vf" and tuple(w.shape) == (k + _abi.POLICY_PRIV_DIM, n):
+                    k += _abi.POLICY_PRIV_DIM     # a privileged critic: its layer 0 reads obs | priv (orr_policy_forward_priv)
+                    self.priv_dim = _abi.POLICY_PRIV_DIM
                 if tuple(w.shape) != (k, n):
                     raise ValueError("%s has shape %s, the fused kernel is built for %s" % (key, tuple(w.shape), (k, n)))
                 size = int(self.L.orr_policy_packed_size(k, n))
@@ -64,14 +68,20 @@ class FusedActorCritic(object):
                 self.biases[field].copy_(w)
                 setattr(self.net, field, self.biases[field].data_ptr())
 
-    def forward(self, obs, noise=None, want_mean=False, out_action=None, out_raw=None, out_value=None):
-        """obs [N,160] float32 on the device; noise [N,12] standard normal or None (deterministic).
+    def forward(self, obs, noise=None, want_mean=False, out_action=None, out_raw=None, out_value=None, priv=None):
+        """obs [N,160] float32 on the device; noise [N,12] standard normal or None (deterministic); priv [N,48] float32, the
+        privileged observation, for a privileged critic (and only then).
         Returns (clipped action [N,12], raw action [N,12], value [N], mean [N,12] or None); the out_* tensors
         (contiguous float32 of those shapes, e.g. rows of a rollout buffer) are written in place when given."""
         t = self.torch
         if obs.dtype != t.float32 or not obs.is_contiguous() or obs.device != self.device or obs.dim() != 2 or obs.shape[1] != 160:
             raise ValueError("obs must be a contiguous float32 [N,160] tensor on %s" % (self.device,))
         n = obs.shape[0]
+        if (priv is not None) != (self.priv_dim > 0):
+            raise ValueError("priv is needed by a privileged critic (model/vf_fc0/w:0 with %d rows) and by no other" % (160 + _abi.POLICY_PRIV_DIM))
+        if priv is not None and (priv.dtype != t.float32 or not priv.is_contiguous() or tuple(priv.shape) != (n, self.priv_dim)
+                                 or priv.device != self.device):
+            raise ValueError("priv must be a contiguous float32 [N,%d] tensor on the same device" % self.priv_dim)
         if noise is not None and (noise.dtype != t.float32 or not noise.is_contiguous() or tuple(noise.shape) != (n, 12)
                                   or noise.device != self.device):
             raise ValueError("noise must be a contiguous float32 [N,12] tensor on the same device")
@@ -83,6 +93,12 @@ class FusedActorCritic(object):
             return x
         act, raw, val = out(out_action, (n, 12)), out(out_raw, (n, 12)), out(out_value, (n,))
         mean = t.empty(n, 12, dtype=t.float32, device=self.device) if want_mean else None
+        if priv is not None:
+            _lib.check(self.L.orr_policy_forward_priv(C.byref(self.net), obs.data_ptr(), priv.data_ptr(), int(n),
+                                                      noise.data_ptr() if noise is not None else None, self.std, self.clip, act.data_ptr(),
+                                                      raw.data_ptr(), val.data_ptr(), mean.data_ptr() if mean is not None else None,
+                                                      self._stream()), self.L)
+            return act, raw, val, mean
         _lib.check(self.L.orr_policy_forward(C.byref(self.net), obs.data_ptr(), int(n), noise.data_ptr() if noise is not None else None,
                                              self.std, self.clip, act.data_ptr(), raw.data_ptr(), val.data_ptr(),
                                              mean.data_ptr() if mean is not None else None, self._stream()), self.L)

@@ -50,19 +50,29 @@ def _linear(torch, relu):
 
 
 class ActorCritic(object):
-    """Trainable twin of policy.MLPPolicy (same parameter names as the stable-baselines zips)."""
+    """Trainable twin of policy.MLPPolicy (same parameter names as the stable-baselines zips).
 
-    def __init__(self, device, obs_dim=160, act_dim=12, hidden=(512, 256), std=pol.PI_STD, params=None, seed=0):
+    priv_dim = 48 makes the critic privileged (the asymmetric actor-critic): model/vf_fc0/w:0 is [obs_dim + priv_dim, 512] and reads
+    cat(obs, priv), priv = env.privileged_obs(); the actor is what it is without, so its part of a saved zip loads wherever the plain
+    policy loads.  With `params` the width is taken from that matrix.  priv_dim = 0: every path is the plain one."""
+
+    def __init__(self, device, obs_dim=160, act_dim=12, hidden=(512, 256), std=pol.PI_STD, params=None, seed=0, priv_dim=0):
         import torch
         self.torch = torch
         self.device = torch.device(device)
         self._std = float(std)
+        if params is not None and "model/vf_fc0/w:0" in params:
+            priv_dim = int(np.shape(params["model/vf_fc0/w:0"])[0]) - obs_dim
+        if priv_dim not in (0, pol.PRIV_DIM):
+            raise ValueError("priv_dim must be 0 or %d, got %r" % (pol.PRIV_DIM, priv_dim))
+        self.priv_dim = int(priv_dim)
         g = torch.Generator().manual_seed(seed)
         self.p = {}
         dims = [obs_dim] + list(hidden)
         for net, out in (("pi", act_dim), ("vf", 1)):
             for i in range(len(hidden)):
-                self._init("model/%s_fc%d" % (net, i), dims[i], dims[i + 1], g, math.sqrt(2.0))
+                fan_in = dims[i] + (self.priv_dim if (net, i) == ("vf", 0) else 0)
+                self._init("model/%s_fc%d" % (net, i), fan_in, dims[i + 1], g, math.sqrt(2.0))
             self._init("model/%s" % net, dims[-1], out, g, 0.01 if net == "pi" else 1.0)
         self.extra = {}            # variables of a loaded zip that this learner does not train (model/q/*): re-emitted by state_dict()
         if params is not None:
@@ -119,26 +129,34 @@ class ActorCritic(object):
     def mean(self, obs):
         return self._mlp("pi", obs)
 
-    def value(self, obs):
-        return self._mlp("vf", obs)[:, 0]
+    def _critic_input(self, obs, priv):
+        if (priv is not None) != (self.priv_dim > 0):
+            raise ValueError("priv is needed by a privileged critic (priv_dim = %d) and by no other" % pol.PRIV_DIM)
+        return obs if priv is None else self.torch.cat((obs, priv), dim=1)
 
-    def act(self, obs, deterministic=False, generator=None, noise=None, out_raw=None, out_value=None):
-        """-> (clipped action, raw action, value).  `noise` ([N,12] standard normal) overrides the generator."""
+    def value(self, obs, priv=None):
+        return self._mlp("vf", self._critic_input(obs, priv))[:, 0]
+
+    def act(self, obs, priv=None, deterministic=False, generator=None, noise=None, out_raw=None, out_value=None):
+        """-> (clipped action, raw action, value).  `noise` ([N,12] standard normal) overrides the generator; `priv` ([N,48], the
+        privileged observation) goes to a privileged critic."""
         t = self.torch
+        if (priv is not None) != (self.priv_dim > 0):
+            raise ValueError("priv is needed by a privileged critic (priv_dim = %d) and by no other" % pol.PRIV_DIM)
         if self.fused is not None:
             if self._fused_dirty:
                 self.fused.refresh()
                 self._fused_dirty = False
             if noise is None and not deterministic:
                 noise = t.randn((obs.shape[0], 12), device=obs.device, generator=generator)
-            a, raw, v, _ = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value)
+            a, raw, v, _ = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value, priv=priv)
             return a, raw, v
         with t.no_grad():
             mu = self.mean(obs)
             if noise is None and not deterministic:
                 noise = t.randn(mu.shape, device=mu.device, generator=generator)
             a = mu if deterministic else mu + self.std * noise
-            return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs)
+            return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, priv)
 
     def log_prob(self, obs, actions):
         mu = self.mean(obs)
@@ -179,10 +197,13 @@ class PPO(object):
             p.grad.copy_(flat[off:off + n].view_as(p.grad))
             off += n
 
-    def update(self, obs, actions, adv, ret, old_logp=None, epochs=1, generator=None):
-        """obs [B,160], actions [B,12] (unclipped samples), adv [B] (already normalised), ret [B] (TD(lambda) targets)."""
+    def update(self, obs, actions, adv, ret, old_logp=None, epochs=1, generator=None, priv=None):
+        """obs [B,160], actions [B,12] (unclipped samples), adv [B] (already normalised), ret [B] (TD(lambda) targets); priv [B,48] the
+        privileged observations, for a model with a privileged critic."""
         t = self.torch
         B = obs.shape[0]
+        if (priv is not None) != (getattr(self.model, "priv_dim", 0) > 0):
+            raise ValueError("priv is needed by a privileged critic and by no other")
         if old_logp is None:
             with t.no_grad():
                 old_logp = self.model.log_prob(obs, actions)
@@ -191,13 +212,15 @@ class PPO(object):
             perm = t.randperm(B, device=obs.device, generator=generator)
             # one gather per epoch; the minibatches are then contiguous views
             obs_p, act_p, adv_p, ret_p, old_p = obs[perm], actions[perm], adv[perm], ret[perm], old_logp[perm]
+            priv_p = None if priv is None else priv[perm]
             for s in range(0, B, self.minibatch):
                 e = s + self.minibatch
                 logp = self.model.log_prob(obs_p[s:e], act_p[s:e])
                 ratio = t.exp(logp - old_p[s:e])
                 a = adv_p[s:e]
                 surr = -t.min(ratio * a, t.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip) * a).mean()
-                vf = ((self.model.value(obs_p[s:e]) - ret_p[s:e]) ** 2).mean()
+                v = self.model.value(obs_p[s:e]) if priv_p is None else self.model.value(obs_p[s:e], priv_p[s:e])
+                vf = ((v - ret_p[s:e]) ** 2).mean()
                 loss = surr + self.vf_coef * vf
                 self.opt.zero_grad(set_to_none=True)
                 loss.backward()

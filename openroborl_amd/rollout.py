@@ -16,14 +16,24 @@ robot's flag; `legacy_gae_index=True` reproduces exactly that, for comparisons w
 """
 
 
-def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generator=None, noise=None):
+def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generator=None, noise=None, priv=None):
     """Run `horizon` env steps of all robots.  Returns a dict of [T, N, ...] tensors + the final observation.
-    noise: optional [T, N, 12] standard-normal samples for the fused policy (default: drawn from `generator`)."""
+    noise: optional [T, N, 12] standard-normal samples for the fused policy (default: drawn from `generator`).
+    A policy with a privileged critic (priv_dim > 0) also gets env.privileged_obs() at every step: "priv" [T, N, 48] and "last_priv" are
+    returned; priv: the one that belongs to `obs` (the previous segment's last_priv; None = computed here with done=None)."""
     t = env.torch
     n = env.num_robot
     dev = env.device
     if obs is None:
         obs = env.reset()
+    priv_dim = int(getattr(policy, "priv_dim", 0))
+    pbuf = None
+    if priv_dim:
+        pbuf = t.empty((horizon + 1, n, priv_dim), device=dev)
+        if priv is None:
+            env.privileged_obs(out=pbuf[0], done=None)
+        else:
+            pbuf[0].copy_(priv)
     buf = {
         "obs": t.empty((horizon, n, obs.shape[1]), device=dev), "actions": t.empty((horizon, n, 12), device=dev),
         "rewards": t.empty((horizon, n), device=dev), "dones": t.empty((horizon, n), dtype=t.bool, device=dev),
@@ -37,17 +47,21 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
     for k in range(horizon):
         if fused:   # one fused launch writes the raw action and the value straight into the buffers
             clipped, _, _ = policy.act(obs, deterministic=deterministic, noise=None if noise is None else noise[k],
-                                       out_raw=buf["actions"][k], out_value=buf["vpred"][k])
+                                       out_raw=buf["actions"][k], out_value=buf["vpred"][k], **({"priv": pbuf[k]} if priv_dim else {}))
             buf["obs"][k].copy_(obs)
         else:
-            clipped, raw, v = policy.act(obs, deterministic=deterministic, generator=generator)
+            clipped, raw, v = policy.act(obs, deterministic=deterministic, generator=generator, **({"priv": pbuf[k]} if priv_dim else {}))
             buf["obs"][k].copy_(obs)
             buf["actions"][k].copy_(raw)
             buf["vpred"][k].copy_(v)
         obs, rew, done, _ = env.step(clipped.contiguous())
         buf["rewards"][k].copy_(rew)
         buf["dones"][k].copy_(done.bool())
+        if priv_dim:    # of the state the new observation belongs to; robots that just ended an episode: no contact / push words
+            env.privileged_obs(out=pbuf[k + 1], done=done)
     buf["last_obs"] = obs
+    if priv_dim:
+        buf["priv"], buf["last_priv"] = pbuf[:horizon], pbuf[horizon]
     if noise is not None:
         # log-probability of the sampled actions under the sampling policy: a - mean = std * noise
         import math
@@ -65,6 +79,10 @@ class GraphRollout(object):
     Kernel arguments that are passed by value - the env's configuration incl. the seed (env.seed()), the policy's std - are frozen
     into a captured graph; collect() notices when they change (env.launch_params_generation, policy.std) and captures again.
 
+    With a privileged critic (policy.priv_dim > 0) the segment also holds priv [T + 1, N, 48]: env.privileged_obs(out=priv[k + 1],
+    done=dones[k]) follows every step_into inside the captured segment, priv[k] goes to the forward pass, and "priv" / "last_priv" are
+    returned.
+
     The returned tensors are views of the static buffers: they are overwritten by the next collect() (clone what must survive it,
     e.g. the last row of `dones` that the next segment's GAE takes as first_starts)."""
 
@@ -78,6 +96,8 @@ class GraphRollout(object):
         self.obs, self.actions, self.clipped = f(T + 1, n, 160), f(T, n, 12), f(n, 12)
         self.rewards, self.vpred, self.noise, self.logp = f(T, n), f(T, n), f(T, n, 12), f(T, n)
         self.dones = t.zeros((T, n), dtype=t.uint8, device=dev)
+        self.priv_dim = int(getattr(policy, "priv_dim", 0))
+        self.priv = f(T + 1, n, self.priv_dim) if self.priv_dim else None
         self.graph, self.calls = None, 0
         self._captured_for = None          # (env.launch_params_generation, policy.std) the graph was captured with
 
@@ -89,17 +109,29 @@ class GraphRollout(object):
         t, env, fused = self.env.torch, self.env, self.policy.fused
         fused.refresh()                   # inside the graph: every replay re-packs the weights the learner has just updated
         for k in range(self.T):
-            fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k])
+            if self.priv_dim:
+                fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], priv=self.priv[k])
+            else:
+                fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k])
             env.step_into(self.clipped, self.obs[k + 1], self.rewards[k], self.dones[k])
+            if self.priv_dim:
+                env.privileged_obs(out=self.priv[k + 1], done=self.dones[k])
         # log-probability of the sampled actions under the sampling policy: a - mean = std * noise
         t.sum(self.noise * self.noise, dim=-1, out=self.logp)
         self.logp.mul_(-0.5).sub_(12.0 * math.log(float(self.policy.std) * math.sqrt(2.0 * math.pi)))
 
-    def collect(self, obs, generator=None, noise=None):
+    def collect(self, obs, generator=None, noise=None, priv=None):
+        """priv: the privileged observation that belongs to `obs` (the previous segment's "last_priv"), for a policy with a privileged
+        critic; None = computed here with done=None (right after a reset; otherwise the contact and push words start as zeros)."""
         t, env = self.env.torch, self.env
         with t.no_grad():
             if obs.data_ptr() != self.obs[0].data_ptr():
                 self.obs[0].copy_(obs)
+            if self.priv_dim:
+                if priv is None:
+                    env.privileged_obs(out=self.priv[0], done=None)
+                elif priv.data_ptr() != self.priv[0].data_ptr():
+                    self.priv[0].copy_(priv)
             if noise is not None:
                 self.noise.copy_(noise)
             else:
@@ -122,8 +154,11 @@ class GraphRollout(object):
                 self.graph.replay()
                 env._env_step_counter += self.T
             self.policy._fused_dirty = False
-        return {"obs": self.obs[:self.T], "actions": self.actions, "rewards": self.rewards, "dones": self.dones.view(t.bool),
-                "vpred": self.vpred, "logp": self.logp, "last_obs": self.obs[self.T]}
+        buf = {"obs": self.obs[:self.T], "actions": self.actions, "rewards": self.rewards, "dones": self.dones.view(t.bool),
+               "vpred": self.vpred, "logp": self.logp, "last_obs": self.obs[self.T]}
+        if self.priv_dim:
+            buf["priv"], buf["last_priv"] = self.priv[:self.T], self.priv[self.T]
+        return buf
 
 
 def legacy_nonterminal(dones, first_starts=None):

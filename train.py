@@ -4,6 +4,7 @@ leaves the GPU.  Counterpart of `python3 OpenRoboRL/run.py --task imitation_lear
 (run.py:186-237), restricted to what SURVEY.md section 8f lists as "next" rows.
 
   python train.py --task imitation_learning_laikago --iters 200
+  python train.py --task imitation_learning_laikago --iters 200 --privileged-critic --push 0.02,0.2,0.5   (asymmetric actor-critic)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py ...
 """
 import argparse
@@ -56,9 +57,15 @@ def main():
                     help="also output the foot contact impulses on the device: every logged record gains \"gait\": {\"duty\": [4], \"normal_force\": [4]} "
                          "(per leg: stance steps / steps, mean normal force in N) over the episodes THIS rank finished in the segment (rank-local); "
                          "--eval: over each robot's episode")
+    ap.add_argument("--privileged-critic", action="store_true",
+                    help="asymmetric actor-critic: the value net also reads the simulator's privileged observation (env.privileged_obs: true base "
+                         "twist and gravity direction, the episode's randomised parameters, foot contacts and forces, the step's push), the actor "
+                         "keeps the 160 observation words.  Binds the contact outputs, and the push outputs with --push.  --save then writes the "
+                         "full critic under the usual names (model/vf_fc0/w:0 with 208 rows): the actor part is what the reference can load, "
+                         "--eval of such a zip works here")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
-    ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip")
+    ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip (with --privileged-critic: see there)")
     ap.add_argument("--torch-policy", action="store_true", help="rollout policy through plain torch instead of the fused HIP kernel")
     ap.add_argument("--torch-learner", action="store_true",
                     help="PPO update through autograd + torch.optim.Adam (ppo.PPO, the fp32 reference) instead of the hand-written backward "
@@ -91,10 +98,15 @@ def main():
     env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
                           device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
                           perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise,
-                          reward_terms=args.reward_terms, contact_outputs=args.contact_outputs, observation_noise_stdev=args.sensor_noise,
-                          push=args.push, **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
+                          reward_terms=args.reward_terms, contact_outputs=args.contact_outputs or args.privileged_critic,
+                          observation_noise_stdev=args.sensor_noise, push=args.push,
+                          push_outputs=args.privileged_critic and args.push is not None,
+                          **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
-    model = ppo.ActorCritic(dev, params=params, seed=args.seed)                     # same seed -> identical replicas
+    # same seed -> identical replicas.  (--model-file: the critic's width is the file's)
+    model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic else 0)
+    if bool(model.priv_dim) != args.privileged_critic:
+        raise SystemExit("train.py: --model-file has a %s critic, --privileged-critic says otherwise" % ("privileged" if model.priv_dim else "plain"))
     if not args.torch_policy:
         model.enable_fused()
     if args.torch_learner:
@@ -119,13 +131,16 @@ def main():
     samples = 0
     log = []
     first_starts = None                   # episode_starts of a segment's first step = the last step's done flags of the previous segment
+    priv = None                           # --privileged-critic: the privileged observation that belongs to `obs` (None: right after the reset)
     # static rollout buffers + the segment replayed as one hipGraph (fused policy only); --torch-policy keeps the eager collector
     collector = None if args.torch_policy else rollout.GraphRollout(env, model, args.horizon)
     for it in range(args.iters):
-        buf = collector.collect(obs, generator=gen) if collector else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen)
+        buf = (collector.collect(obs, generator=gen, priv=priv) if collector
+               else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv))
         obs = buf["last_obs"]
+        priv = buf.get("last_priv")
         with torch.no_grad():
-            boot = model.value(obs)
+            boot = model.value(obs, priv)
         # bootstrap with the critic at the segment end (the reference uses 0 there, imitation_runners.py:98-100;
         # with 32-step segments that bias would dominate)
         adv, ret = rollout.gae_fused(buf["rewards"], buf["vpred"], buf["dones"], 0.95, 0.95, bootstrap=boot, normalize=True, eps=1e-8,
@@ -134,7 +149,7 @@ def main():
         T, n = buf["rewards"].shape
         surr, vf = learner.update(buf["obs"].reshape(T * n, -1), buf["actions"].reshape(T * n, -1), adv.reshape(-1),
                                   ret.reshape(-1), old_logp=buf["logp"].reshape(-1) if "logp" in buf else None,
-                                  epochs=args.epochs, generator=gen)
+                                  epochs=args.epochs, generator=gen, priv=buf["priv"].reshape(T * n, -1) if model.priv_dim else None)
         samples += T * n * world
         # (> 1 rank, or ORR_FORCE_DIST=1: the one-rank rehearsal of the several-ranks path on RCCL runs the check too)
         if (world > 1 or os.environ.get("ORR_FORCE_DIST", "0") == "1") and args.sync_check_every > 0 and it % args.sync_check_every == args.sync_check_every - 1 and hasattr(learner, "check_synced"):
@@ -218,6 +233,8 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     if not args.torch_policy:
         model.enable_fused()
     obs = env.reset()
+    # a zip with a privileged critic (--privileged-critic): the fused forward pass takes the privileged observation; only the actor's output is used here
+    priv = env.privileged_obs(done=None) if model.priv_dim else None
     clip_ids = env.active_clip_ids()             # the clip each robot's episode plays
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     ret = torch.zeros(n, device=dev)
@@ -227,8 +244,10 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     normal = torch.zeros(4, dtype=torch.float64, device=dev)
     limit = int(env.field_int("MAX_EP_STEPS").max())
     for _ in range(limit):
-        act, _, _ = model.act(obs, deterministic=True)
+        act, _, _ = model.act(obs, priv, deterministic=True)
         obs, rew, done, _ = env.step(act)
+        if model.priv_dim:
+            env.privileged_obs(out=priv, done=done)
         ret += rew * alive
         if args.reward_terms:
             term_sum += (env.reward_terms * alive[:, None]).sum(0)
