@@ -7,11 +7,13 @@
 // this device: 33 physics sub-steps, observation, reward, termination, optional auto-reset.
 // Specification of every stage: DESIGN.md section 4; CPU restatement: oracle/orr_oracle.c.
 // The kernels and their launchers are templates in orr_env_kernels.h.  This unit instantiates the default ones (env step, debug
-// physics, parity replay, reset) and chooses among all variants (variant_of); the two-wave, friction-anchor, clip-set, task-noise,
-// reward-terms, contact-output and actuator instantiations are compiled in units of their own (orr_kernels_w2.hip, _anchor.hip,
-// _multiclip.hip, _noise.hip, _terms.hip, _contacts.hip, _actuator.hip; why: orr_env_kernels.h).
+// physics, parity replay, reset) and launches all variants (which one: choose_variant, orr_variants.h); the two-wave, friction-anchor,
+// clip-set, task-noise, reward-terms, contact-output, actuator, sensor-noise, randomiser and push instantiations are compiled in units of
+// their own (orr_kernels_w2.hip, _anchor.hip, _multiclip.hip, _noise.hip, _terms.hip, _contacts.hip, _actuator.hip, _sensor.hip,
+// _randomizer.hip, _push.hip; why: orr_env_kernels.h), and so is the privileged observation (_priv.hip).
 #define ORR_TU_MAIN 1
 #include "orr_env_kernels.h"
+#include "orr_variants.h"
 // <0, ORR_WAVES_PER_EU>: one wave per SIMD in the shipped build; development builds (-DORR_WAVES_PER_EU=2 with the timers of this
 // translation unit, tools/wave_pairing.py) get their instrumented two-wave kernel through the default path with ORR_STEP_WAVES_PER_EU=1
 template orr::ResetLaunch orr::launch_reset<false>;
@@ -642,154 +644,126 @@ static KParams make_params(const orr_handle* h) {
 
 static int waves_of(const orr_handle* h) { return (h->cfg.num_robots + kRPW - 1) / kRPW; }
 
-// Which instantiation of the kernels a launch runs.  `clip_types` = the feature mask that selects the clip-set variants: multiclip_types
-// for orr_step / orr_reset, switch_types for the parity replays.  A randomiser table or params buffer comes first of all (env step,
-// parity replays and resets: supersets of the sensor variants; friction anchors are refused).  Then sensor noise comes first (env step, parity replays and resets: supersets
-// of everything below but the friction anchors, which are refused).  Then torque limits and actuator outputs come first (env step, parity replay
-// and the resets, which run the noise variant; the two step variants are supersets that serve the reward terms and - the env step - the
-// contact outputs too, whichever are bound; friction anchors are refused), then the contact outputs (`contacts` = the entry point has a
-// contact variant: not the parity replays, which have no impulses and run what they run without the binding; the env step has one with
-// and one without the reward terms, the resets run the noise variant), then the reward terms (their step variants hold the noise and the
-// clip-set code; the resets of such a handle run the noise variant), then task noise (its variants hold the clip-set code too), then
-// clip sets (both refuse friction anchors: kRefused, the message starts with the entry point's name `who`), then friction anchors, then
-// the batch size; only the env step has a two-wave and only the env step and the debug physics have an anchor instantiation, every other
-// entry point runs its default one instead.
-enum Variant { kRefused = -1, kDefault, kTwoWave, kAnchor, kClips, kNoise, kTerms, kContacts, kActuator, kSensor, kRandomizer, kPush };
-static bool refuse_contacts_with_anchors(const orr_handle* h, const char* who) {   // (a model with anchors set after orr_bind_contact_outputs)
-  if (!(h->contacts_on && h->anchor_types)) return false;
-  char m[256];
-  snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and contact outputs (orr_bind_contact_outputs) cannot be combined", who);
-  fail(-1, m);
-  return true;
+// ---- which instantiation of the kernels a launch runs.  The rule is choose_variant (orr_variants.h); here: what it reads, and what each
+// entry point launches for each answer ----
+static Features features_of(const orr_handle* h, Entry e) {   // the one place that reads the handle's switches for the choice
+  const bool replay = e == kEntryReplayStep || e == kEntryReplayReset;
+  Features f;
+  f.anchors = h->anchor_types != 0;
+  f.clips = (replay ? h->switch_types : h->multiclip_types) != 0;
+  f.noise = h->noise_on;
+  f.terms = h->terms_on;
+  f.contacts = h->contacts_on;
+  f.actuator = h->act_on || h->limit_types;
+  f.sensor = h->sensor_on;
+  f.randomizer = h->rand_on || h->rand_bound;
+  f.push = h->push_on || h->push_bound;
+  f.two_wave = h->force_wpe ? h->force_wpe == 2 : waves_of(h) > h->simds;
+  return f;
 }
-static Variant variant_of(const orr_handle* h, uint32_t clip_types, const char* who, bool contacts = true, bool push = false) {
-  if (h->push_on || h->push_bound) {   // ahead of the randomiser: a superset of its env step.  `push` = the entry point has a push variant (orr_step only)
-    if (h->anchor_types) {   // (a model with anchors set after orr_set_push / orr_bind_push_outputs)
-      char m[256];
-      snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and pushes (orr_set_push, orr_bind_push_outputs) cannot be combined", who);
-      fail(-1, m);
-      return kRefused;
-    }
-    if (push) return kPush;
-  }
-  if (h->rand_on || h->rand_bound) {   // ahead of sensor noise: supersets of its variants
-    if (h->anchor_types) {   // (a model with anchors set after orr_set_randomizer / orr_bind_randomizer_params)
-      char m[256];
-      snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and the randomiser (orr_set_randomizer, orr_bind_randomizer_params) cannot be combined", who);
-      fail(-1, m);
-      return kRefused;
-    }
-    return kRandomizer;
-  }
-  if (h->sensor_on) {
-    if (h->anchor_types) {   // (a model with anchors set after orr_set_sensor_noise)
-      char m[256];
-      snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and sensor noise (orr_set_sensor_noise) cannot be combined", who);
-      fail(-1, m);
-      return kRefused;
-    }
-    return kSensor;
-  }
-  if (h->act_on || h->limit_types) {
-    if (h->anchor_types) {   // (a model with anchors set after orr_set_torque_limits / orr_bind_actuator_outputs)
-      char m[256];
-      snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and torque limits / actuator outputs (orr_set_torque_limits, orr_bind_actuator_outputs) cannot be combined", who);
-      fail(-1, m);
-      return kRefused;
-    }
-    return kActuator;
-  }
-  if (contacts && refuse_contacts_with_anchors(h, who)) return kRefused;
-  if (contacts && h->contacts_on) return kContacts;
-  if (h->terms_on && h->anchor_types) {   // (a model with anchors set after orr_bind_reward_terms)
+static Variant choose(const orr_handle* h, Entry e) {   // kRefused: the message is recorded, the caller returns -1
+  const Choice c = choose_variant(features_of(h, e), e);
+  if (c.variant == kRefused) {
     char m[256];
-    snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and reward terms (orr_bind_reward_terms) cannot be combined", who);
+    format_anchor_conflict(m, sizeof(m), e, c.conflict);
     fail(-1, m);
-    return kRefused;
   }
-  if (h->terms_on) return kTerms;
-  if (h->noise_on && h->anchor_types) {
-    char m[256];
-    snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and task noise (orr_set_task_noise) cannot be combined", who);
-    fail(-1, m);
-    return kRefused;
+  return c.variant;
+}
+
+// The feature masks of the step kernels' MODE, each a superset of the one before it (the unit that instantiates each: the
+// `extern template` lines of orr_env_kernels.h); the parity replays' (| 2) have no contact sums
+constexpr int kStepTerms = kModeTerms, kStepContacts = kModeContacts, kStepContactsTerms = kModeContacts | kModeTerms,
+              kStepActuator = kModeActuator | kStepContactsTerms, kStepSensor = kModeSensor | kStepActuator,
+              kStepRandomizer = kModeRandomizer | kStepSensor, kStepPush = kModePush | kStepRandomizer;
+constexpr int kReplayTerms = kModeTerms | 2, kReplayActuator = kModeActuator | kReplayTerms, kReplaySensor = kModeSensor | kReplayActuator,
+              kReplayRandomizer = kModeRandomizer | kReplaySensor;
+
+// One line per variant and entry point; a variant without a line fails to compile.  nullptr = choose_variant never gives it there.
+#pragma clang diagnostic error "-Wswitch"
+static StepLaunch* step_launcher(Variant v) {   // orr_step: the feature variants run one wave per SIMD at any batch size
+  switch (v) {
+    case kPush: return launch_step<kStepPush, 1, false, true, true>;
+    case kRandomizer: return launch_step<kStepRandomizer, 1, false, true, true>;
+    case kSensor: return launch_step<kStepSensor, 1, false, true, true>;
+    case kActuator: return launch_step<kStepActuator, 1, false, true, true>;
+    case kContactsTerms: return launch_step<kStepContactsTerms, 1, false, true, true>;
+    case kContacts: return launch_step<kStepContacts, 1, false, true, true>;
+    case kTerms: return launch_step<kStepTerms, 1, false, true, true>;
+    case kNoise: return launch_step<0, 1, false, true, true>;
+    case kClips: return launch_step<0, 1, false, true>;
+    case kAnchor: return launch_step<0, 1, true, false>;
+    case kTwoWave: return launch_step<0, 2, false, false>;
+    case kDefault: return launch_step<0, ORR_WAVES_PER_EU, false, false>;
+    case kRefused: case kNumVariants: break;
   }
-  if (h->noise_on) return kNoise;
-  if (clip_types && h->anchor_types) {
-    char m[256];
-    snprintf(m, sizeof(m), "%s: friction anchors (orr_model::friction_anchor) and a clip set of more than one clip cannot be combined", who);
-    fail(-1, m);
-    return kRefused;
+  return nullptr;
+}
+static StepLaunch* replay_step_launcher(Variant v) {   // orr_debug_replay_step: no reset inside, no two-wave or anchor form
+  switch (v) {
+    case kRandomizer: return launch_step<kReplayRandomizer, 1, false, true, true>;   // (no reset inside: the sensor replay's computation)
+    case kSensor: return launch_step<kReplaySensor, 1, false, true, true>;           // the noisy readings' draws come from the Philox stream
+    case kActuator: return launch_step<kReplayActuator, 1, false, true, true>;
+    case kTerms: return launch_step<kReplayTerms, 1, false, true, true>;
+    case kNoise: return launch_step<2, 1, false, true, true>;   // the draws from 28 on, the heading noise included, come from the Philox stream
+    case kClips: return launch_step<2, 1, false, true>;         // likewise
+    case kAnchor: case kTwoWave: case kDefault: return launch_step<2, ORR_WAVES_PER_EU, false, false>;
+    case kPush: case kContacts: case kContactsTerms: case kRefused: case kNumVariants: break;
   }
-  if (clip_types) return kClips;
-  if (h->anchor_types) return kAnchor;
-  return (h->force_wpe ? h->force_wpe == 2 : waves_of(h) > h->simds) ? kTwoWave : kDefault;
+  return nullptr;
+}
+static StepLaunch* physics_launcher(Variant v) {   // orr_debug_physics: choose_variant gives it these three only
+  switch (v) {
+    case kContacts: return launch_step<kModeContacts | 1, 1, false, false>;   // also sums the nsub sub-steps' contact impulses
+    case kAnchor: return launch_step<1, 1, true, false>;
+    case kDefault: return launch_step<1, ORR_WAVES_PER_EU, false, false>;
+    case kTwoWave: case kClips: case kNoise: case kTerms: case kContactsTerms: case kActuator: case kSensor: case kRandomizer: case kPush:
+    case kRefused: case kNumVariants: break;
+  }
+  return nullptr;
+}
+static ResetLaunch* reset_launcher(Variant v) {   // orr_reset and, with the draws 0..27 given, orr_debug_replay_reset (where kContacts cannot occur)
+  switch (v) {
+    case kRandomizer: return launch_randomizer_reset<true>;   // the sensor reset with the table-driven randomiser
+    case kSensor: return launch_sensor_reset<true>;           // three noisy readings per history, a noisy heading of the target observation
+    case kNoise: case kTerms: case kContacts: case kActuator: return launch_reset<true, true>;   // perturbed initial states / noisy target heading, and the clip draw
+    case kClips: return launch_reset<true>;                   // every reset draws the episode's clip
+    case kAnchor: case kTwoWave: case kDefault: return launch_reset<false>;
+    case kPush: case kContactsTerms: case kRefused: case kNumVariants: break;
+  }
+  return nullptr;
+}
+
+static int launch_failed(Entry e, Variant v, hipError_t err) {   // "<entry>: launch (<variant>)"
+  static const char* const labels[] = {"", " (two waves per SIMD)", " (friction anchors)", " (clip sets)", " (task noise)", " (reward terms)", " (contact outputs)",
+                                       " (contact outputs + reward terms)", " (actuator)", " (sensor noise)", " (randomiser)", " (push)"};
+  static_assert(sizeof(labels) / sizeof(labels[0]) == kNumVariants, "one label per variant");
+  char m[128];
+  snprintf(m, sizeof(m), "%s: launch%s", kEntryNames[e], labels[v]);
+  return fail(-2, m, err);
+}
+static int launch(const orr_handle* h, Entry e, Variant v, StepLaunch* fn, void* stream, const float* in, float* obs, float* reward, uint8_t* done, int nsub,
+                  const ReplayArgs& rp) {
+  const hipError_t err = fn ? fn(make_params(h), waves_of(h), (hipStream_t)stream, in, obs, reward, done, nsub, rp) : hipErrorInvalidDeviceFunction;
+  return err == hipSuccess ? 0 : launch_failed(e, v, err);
+}
+static int launch(const orr_handle* h, Entry e, Variant v, ResetLaunch* fn, void* stream, const uint8_t* mask, float* obs, const float* uniforms) {
+  const hipError_t err = fn ? fn(make_params(h), waves_of(h), (hipStream_t)stream, mask, obs, uniforms) : hipErrorInvalidDeviceFunction;
+  return err == hipSuccess ? 0 : launch_failed(e, v, err);
 }
 
 int32_t orr_reset(orr_handle* h, const uint8_t* mask_dev, float* obs_dev, void* stream) {
   if (!h || !h->state) return fail(-1, "orr_reset: handle not bound");
-  const Variant v = variant_of(h, h->multiclip_types, "orr_reset");
-  if (v == kRefused) return -1;
-  if (v == kRandomizer)   // a randomiser table or a params buffer: the sensor reset with the table-driven randomiser
-    HIPCHK((launch_randomizer_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (randomiser)");
-  else if (v == kSensor)   // sensor noise: three noisy readings per history, a noisy heading of the target observation
-    HIPCHK((launch_sensor_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (sensor noise)");
-  else if (v == kNoise || v == kTerms || v == kContacts || v == kActuator)   // task noise: perturbed initial states / noisy target heading (and the clip draw, where a type has a clip set)
-    HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr)), "orr_reset: launch (task noise)");
-  else if (v == kClips)   // some robot type has a clip set of more than one clip: every reset draws the episode's clip
-    HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr), "orr_reset: launch (clip sets)");
-  else
-    HIPCHK(launch_reset<false>(make_params(h), waves_of(h), (hipStream_t)stream, mask_dev, obs_dev, nullptr), "orr_reset: launch");
-  return 0;
+  const Variant v = choose(h, kEntryReset);
+  return v == kRefused ? -1 : launch(h, kEntryReset, v, reset_launcher(v), stream, mask_dev, obs_dev, nullptr);
 }
 
 int32_t orr_step(orr_handle* h, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream) {
   if (!h || !h->state) return fail(-1, "orr_step: handle not bound");
   if (!actions_dev || !obs_dev || !reward_dev || !done_dev) return fail(-1, "orr_step: null buffer");
   if (((uintptr_t)obs_dev & 15u) != 0) return fail(-1, "orr_step: the observation buffer must be 16-byte aligned (it is written in 16-byte pieces)");
-#define ORR_STEP(WPE, ANCHOR, CLIPS, NOISE, msg) \
-  HIPCHK((launch_step<0, WPE, ANCHOR, CLIPS, NOISE>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{})), msg)
-  switch (variant_of(h, h->multiclip_types, "orr_step", true, true)) {
-    case kRefused: return -1;
-    case kPush:   // one wave per SIMD, any batch size; the superset that also serves the randomiser's table, sensor noise, torque limits and every output binding
-      HIPCHK((launch_step<kModePush | kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream,
-                                                                                                                                            actions_dev, obs_dev, reward_dev, done_dev, 0,
-                                                                                                                                            ReplayArgs{})),
-             "orr_step: launch (push)");
-      break;
-    case kRandomizer:   // one wave per SIMD, any batch size; the superset that also serves sensor noise, torque limits and every output binding
-      HIPCHK((launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream,
-                                                                                                                                actions_dev, obs_dev, reward_dev, done_dev, 0,
-                                                                                                                                ReplayArgs{})),
-             "orr_step: launch (randomiser)");
-      break;
-    case kSensor:   // one wave per SIMD, any batch size; the superset that also serves torque limits and every output binding
-      HIPCHK((launch_step<kModeSensor | kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev,
-                                                                                                              obs_dev, reward_dev, done_dev, 0, ReplayArgs{})),
-             "orr_step: launch (sensor noise)");
-      break;
-    case kActuator:   // one wave per SIMD, any batch size; the superset that also serves the reward terms and the contact outputs where bound
-      HIPCHK((launch_step<kModeActuator | kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev,
-                                                                                                reward_dev, done_dev, 0, ReplayArgs{})), "orr_step: launch (actuator)");
-      break;
-    case kContacts:   // one wave per SIMD, any batch size; with the reward terms bound as well, the variant that writes both
-      if (h->terms_on)
-        HIPCHK((launch_step<kModeContacts | kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev,
-                                                                                  done_dev, 0, ReplayArgs{})), "orr_step: launch (contact outputs + reward terms)");
-      else
-        HIPCHK((launch_step<kModeContacts | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0,
-                                                                     ReplayArgs{})), "orr_step: launch (contact outputs)");
-      break;
-    case kTerms: HIPCHK((launch_step<kModeTerms | 0, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0,
-                                                                           ReplayArgs{})), "orr_step: launch (reward terms)"); break;   // one wave per SIMD, any batch size
-    case kNoise: ORR_STEP(1, false, true, true, "orr_step: launch (task noise)"); break;              // one wave per SIMD, any batch size
-    case kClips: ORR_STEP(1, false, true, false, "orr_step: launch (clip sets)"); break;              // one wave per SIMD, any batch size
-    case kAnchor: ORR_STEP(1, true, false, false, "orr_step: launch (friction anchors)"); break;      // one wave per SIMD, any batch size
-    case kTwoWave: ORR_STEP(2, false, false, false, "orr_step: launch (two waves per SIMD)"); break;
-    case kDefault: ORR_STEP(ORR_WAVES_PER_EU, false, false, false, "orr_step: launch"); break;
-  }
-#undef ORR_STEP
-  return 0;
+  const Variant v = choose(h, kEntryStep);
+  return v == kRefused ? -1 : launch(h, kEntryStep, v, step_launcher(v), stream, actions_dev, obs_dev, reward_dev, done_dev, 0, ReplayArgs{});
 }
 
 // the privileged observation: its kernel lives in orr_kernels_priv.hip (no variants: it reads the record and whatever outputs are bound)
@@ -806,17 +780,8 @@ int32_t orr_privileged_obs(orr_handle* h, const uint8_t* done_dev, float* priv_d
 // parity / debug entry point (not part of the drop-in surface): nsub physics sub-steps with fixed motor torques
 int32_t orr_debug_physics(orr_handle* h, const float* torques_dev, uint8_t* fall_dev, int32_t nsub, void* stream) {
   if (!h || !h->state || !torques_dev) return fail(-1, "orr_debug_physics: bad argument");
-  if (refuse_contacts_with_anchors(h, "orr_debug_physics")) return -1;
-  if (h->contacts_on)   // the debug physics that also sums the nsub sub-steps' contact impulses
-    HIPCHK((launch_step<kModeContacts | 1, 1, false, false>(make_params(h), waves_of(h), (hipStream_t)stream, torques_dev, nullptr, nullptr, fall_dev, nsub, ReplayArgs{})),
-           "orr_debug_physics: launch (contact outputs)");
-  else if (h->anchor_types)
-    HIPCHK((launch_step<1, 1, true, false>(make_params(h), waves_of(h), (hipStream_t)stream, torques_dev, nullptr, nullptr, fall_dev, nsub, ReplayArgs{})),
-           "orr_debug_physics: launch (friction anchors)");
-  else
-    HIPCHK((launch_step<1, ORR_WAVES_PER_EU, false, false>(make_params(h), waves_of(h), (hipStream_t)stream, torques_dev, nullptr, nullptr, fall_dev, nsub,
-                                                           ReplayArgs{})), "orr_debug_physics: launch");
-  return 0;
+  const Variant v = choose(h, kEntryDebugPhysics);
+  return v == kRefused ? -1 : launch(h, kEntryDebugPhysics, v, physics_launcher(v), stream, torques_dev, nullptr, nullptr, fall_dev, nsub, ReplayArgs{});
 }
 
 int32_t orr_episode_stats(orr_handle* h, double total_timesteps, int32_t capacity, double* out_dev, void* stream) {
@@ -848,46 +813,13 @@ int32_t orr_debug_replay_step(orr_handle* h, const float* actions_dev, const flo
     return fail(-1, "orr_debug_replay_step: null buffer");
   if (h->cfg.flags & ORR_FLAG_AUTO_RESET) return fail(-1, "orr_debug_replay_step: needs a handle without ORR_FLAG_AUTO_RESET");
   const ReplayArgs rp{traj_dev, eff_dev, fall_dev, tau_out_dev, nullptr};
-  const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_step", false);   // no contact variant: contact_out is left alone
-  if (v == kRefused) return -1;
-  if (v == kRandomizer)   // the sensor replay of a handle with a randomiser table or params buffer (no reset inside: the same computation)
-    HIPCHK((launch_step<kModeRandomizer | kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev,
-                                                                                                              reward_dev, done_dev, 0, rp)), "orr_debug_replay_step: launch (randomiser)");
-  else if (v == kSensor)   // sensor noise: the actuator replay with noisy readings (their draws come from the Philox stream)
-    HIPCHK((launch_step<kModeSensor | kModeActuator | kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev,
-                                                                                            done_dev, 0, rp)), "orr_debug_replay_step: launch (sensor noise)");
-  else if (v == kActuator)   // torque limits / actuator outputs: the noise replay that clips and accumulates the torques (and writes the terms where bound)
-    HIPCHK((launch_step<kModeActuator | kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0,
-                                                                              rp)), "orr_debug_replay_step: launch (actuator)");
-  else if (v == kTerms)   // reward terms: the noise replay that also writes the terms
-    HIPCHK((launch_step<kModeTerms | 2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
-           "orr_debug_replay_step: launch (reward terms)");
-  else if (v == kNoise)   // task noise: the noise replay (its draws from 28 on, the heading noise included, come from the Philox stream)
-    HIPCHK((launch_step<2, 1, false, true, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
-           "orr_debug_replay_step: launch (task noise)");
-  else if (v == kClips)   // a clip switch interval: the multi-clip replay (its draws from 28 on come from the Philox stream)
-    HIPCHK((launch_step<2, 1, false, true>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
-           "orr_debug_replay_step: launch (clip switching)");
-  else
-    HIPCHK((launch_step<2, ORR_WAVES_PER_EU, false, false>(make_params(h), waves_of(h), (hipStream_t)stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp)),
-           "orr_debug_replay_step: launch");
-  return 0;
+  const Variant v = choose(h, kEntryReplayStep);
+  return v == kRefused ? -1 : launch(h, kEntryReplayStep, v, replay_step_launcher(v), stream, actions_dev, obs_dev, reward_dev, done_dev, 0, rp);
 }
 int32_t orr_debug_replay_reset(orr_handle* h, const float* uniforms_dev, float* obs_dev, void* stream) {
   if (!h || !h->state || !uniforms_dev) return fail(-1, "orr_debug_replay_reset: bad argument");
-  const Variant v = variant_of(h, h->switch_types, "orr_debug_replay_reset", false);
-  if (v == kRefused) return -1;
-  if (v == kRandomizer)   // the randomiser reset (draws 0..27 from uniforms_dev; the two newer blocks and everything else from the Philox stream)
-    HIPCHK((launch_randomizer_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (randomiser)");
-  else if (v == kSensor)   // sensor noise: the sensor reset (draws 0..27 from uniforms_dev; everything else from the Philox stream)
-    HIPCHK((launch_sensor_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (sensor noise)");
-  else if (v == kNoise || v == kTerms || v == kActuator)   // task noise: the noise reset (draws 0..27 from uniforms_dev; 28 on and the noise blocks from the Philox stream)
-    HIPCHK((launch_reset<true, true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev)), "orr_debug_replay_reset: launch (task noise)");
-  else if (v == kClips)   // a clip switch interval: the multi-clip reset (draws 0..27 from uniforms_dev, 28 on from the Philox stream)
-    HIPCHK(launch_reset<true>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev), "orr_debug_replay_reset: launch (clip switching)");
-  else
-    HIPCHK(launch_reset<false>(make_params(h), waves_of(h), (hipStream_t)stream, nullptr, obs_dev, uniforms_dev), "orr_debug_replay_reset: launch");
-  return 0;
+  const Variant v = choose(h, kEntryReplayReset);
+  return v == kRefused ? -1 : launch(h, kEntryReplayReset, v, reset_launcher(v), stream, nullptr, obs_dev, uniforms_dev);
 }
 
 int32_t orr_time_steps(orr_handle* h, const float* actions_dev, float* obs_dev, float* reward_dev, uint8_t* done_dev, void* stream,

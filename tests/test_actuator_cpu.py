@@ -17,6 +17,7 @@ from openroborl_amd import _abi, _lib, env as envmod
 from tests import actuator_lib as al
 from tests import contact_lib as cl
 from tests import oracle_lib as ol
+from tests import variant_probe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV_STEP, REPLAY = "_Z15orr_step_kernelILi28ELi1ELb0ELb1ELb1EE", "_Z15orr_step_kernelILi22ELi1ELb0ELb1ELb1EE"
@@ -58,7 +59,7 @@ def test_the_kernel_tuning_knobs_compile_in_the_actuator_unit_too(defs):
     assert r.returncode == 0, "%s:\n%s" % (" ".join(defs), r.stderr[-1500:])
 
 
-def test_unit_tables_exports_and_refusal_texts():
+def test_unit_tables_exports_and_refusal_texts(tmp_path_factory):
     assert [u[0] for u in _lib.ACTUATOR_UNITS] == ["actuator"]
     assert not [u for u in _lib.ACTUATOR_UNITS if u in _lib.ALL_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ALL_ENV_UNITS]
     assert len(_lib.NOISE_UNITS) == 1 and len(_lib.TERMS_UNITS) == 1 and len(_lib.CONTACT_UNITS) == 1 and _lib.ALL_UNITS == _lib.UNITS + _lib.NOISE_UNITS
@@ -89,12 +90,15 @@ def test_unit_tables_exports_and_refusal_texts():
                  "orr_set_torque_limits: friction anchors (orr_model::friction_anchor) and torque limits cannot be combined",
                  "orr_bind_actuator_outputs: null handle", "orr_bind_actuator_outputs: act_dev needs act_ep_dev",
                  "orr_bind_actuator_outputs: the actuator buffers (act_dev, act_ep_dev, act_log_dev) must be 16-byte aligned",
-                 "orr_bind_actuator_outputs: friction anchors (orr_model::friction_anchor) and actuator outputs cannot be combined",
-                 "%s: friction anchors (orr_model::friction_anchor) and torque limits / actuator outputs (orr_set_torque_limits, orr_bind_actuator_outputs) cannot be combined"):
+                 "orr_bind_actuator_outputs: friction anchors (orr_model::friction_anchor) and actuator outputs cannot be combined"):
         assert text in main, text
-    # variant_of tests the actuator variant first
-    body = main[main.index("static Variant variant_of("):]
-    assert body.index("return kActuator;") < body.index("return kContacts;") < body.index("return kTerms;")
+    # the actuator variant comes ahead of the contact outputs and the reward terms
+    probe = variant_probe.lib(tmp_path_factory)
+    assert probe.choose({"actuator", "contacts", "terms"}, "orr_step") == ("kActuator", None)
+    for entry in ("orr_reset", "orr_step"):
+        assert probe.choose({"actuator", "contacts", "terms", "anchors"}, entry) == (
+            "kRefused", entry + ": friction anchors (orr_model::friction_anchor) and torque limits / actuator outputs "
+                                "(orr_set_torque_limits, orr_bind_actuator_outputs) cannot be combined")
     # the main unit calls the actuator variants and cannot compile them
     with open(os.path.join(_lib.CSRC, "orr_env_kernels.h")) as f:
         kernels_h = f.read()

@@ -14,6 +14,7 @@ import pytest
 
 from openroborl_amd import _abi, _lib, env as envmod
 from tests import contact_lib as cl
+from tests import variant_probe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV_STEP, ENV_STEP_TERMS, DEBUG = ("_Z15orr_step_kernelILi8ELi1ELb0ELb1ELb1EE", "_Z15orr_step_kernelILi12ELi1ELb0ELb1ELb1EE",
@@ -57,7 +58,7 @@ def test_the_kernel_tuning_knobs_compile_in_the_contacts_unit_too(defs):
     assert r.returncode == 0, "%s:\n%s" % (" ".join(defs), r.stderr[-1500:])
 
 
-def test_unit_tables_exports_and_refusal_texts():
+def test_unit_tables_exports_and_refusal_texts(tmp_path_factory):
     assert [u[0] for u in _lib.CONTACT_UNITS] == ["contacts"]
     assert not [u for u in _lib.CONTACT_UNITS if u in _lib.ALL_UNITS + _lib.TERMS_UNITS + _lib.ALL_ENV_UNITS]
     assert len(_lib.NOISE_UNITS) == 1 and len(_lib.TERMS_UNITS) == 1 and _lib.ALL_UNITS == _lib.UNITS + _lib.NOISE_UNITS
@@ -78,9 +79,14 @@ def test_unit_tables_exports_and_refusal_texts():
     with open(_lib.SRC) as f:
         main = f.read()
     for text in ("orr_bind_contact_outputs: null handle", "orr_bind_contact_outputs: contact_dev needs contact_ep_dev",
-                 "orr_bind_contact_outputs: friction anchors (orr_model::friction_anchor) and contact outputs cannot be combined",
-                 "%s: friction anchors (orr_model::friction_anchor) and contact outputs (orr_bind_contact_outputs) cannot be combined"):
+                 "orr_bind_contact_outputs: friction anchors (orr_model::friction_anchor) and contact outputs cannot be combined"):
         assert text in main, text
+    probe = variant_probe.lib(tmp_path_factory)
+    for entry in ("orr_reset", "orr_step", "orr_debug_physics"):
+        assert probe.choose({"contacts", "anchors"}, entry) == (
+            "kRefused", entry + ": friction anchors (orr_model::friction_anchor) and contact outputs (orr_bind_contact_outputs) cannot be combined")
+    for entry in ("orr_debug_replay_step", "orr_debug_replay_reset"):        # no contact variant, so no refusal either
+        assert probe.choose({"contacts", "anchors"}, entry) == ("kAnchor", None)
     # the main unit calls the contact variants and cannot compile them
     with open(os.path.join(_lib.CSRC, "orr_env_kernels.h")) as f:
         kernels_h = f.read()

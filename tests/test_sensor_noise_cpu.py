@@ -14,6 +14,7 @@ import pytest
 
 from openroborl_amd import _abi, _lib, env as envmod
 from tests import oracle_lib as ol
+from tests import variant_probe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ol.GOLDEN, "task_laikago_sensor_noise.npz")
@@ -192,7 +193,7 @@ def test_the_sensor_unit_compiles_for_gfx950_with_its_three_kernels_and_no_spill
     assert isa_stats.scratch_accesses([insts[i] for i in side]) == 0
 
 
-def test_unit_tables_exports_and_sizes():
+def test_unit_tables_exports_and_sizes(tmp_path_factory):
     assert [u[0] for u in _lib.SENSOR_UNITS] == ["sensor"]
     older = _lib.ALL_UNITS + _lib.TERMS_UNITS + _lib.CONTACT_UNITS + _lib.ACTUATOR_UNITS
     assert not [u for u in _lib.SENSOR_UNITS if u in older] and len(older) == 10
@@ -209,11 +210,13 @@ def test_unit_tables_exports_and_sizes():
     with open(_lib.SRC) as f:
         main = f.read()
     for text in ("orr_set_sensor_noise: null handle", "orr_set_sensor_noise: %s must be a finite standard deviation >= 0",
-                 "orr_set_sensor_noise: friction anchors (orr_model::friction_anchor) and sensor noise cannot be combined",
-                 "%s: friction anchors (orr_model::friction_anchor) and sensor noise (orr_set_sensor_noise) cannot be combined"):
+                 "orr_set_sensor_noise: friction anchors (orr_model::friction_anchor) and sensor noise cannot be combined"):
         assert text in main, text
-    body = main[main.index("static Variant variant_of("):]
-    assert body.index("return kSensor;") < body.index("return kActuator;")         # sensor noise first
+    probe = variant_probe.lib(tmp_path_factory)
+    for entry in ("orr_step", "orr_reset", "orr_debug_replay_step", "orr_debug_replay_reset"):
+        assert probe.choose({"sensor", "actuator"}, entry) == ("kSensor", None)                       # sensor noise first
+        assert probe.choose({"sensor", "actuator", "anchors"}, entry) == (
+            "kRefused", entry + ": friction anchors (orr_model::friction_anchor) and sensor noise (orr_set_sensor_noise) cannot be combined")
     L = _lib.load()
     for name in _lib.EXPORTS:
         assert hasattr(L, name), name
