@@ -7,6 +7,7 @@
  * autograd graph spends around them - ~70 elementwise / reduction launches per minibatch, more time than the GEMMs themselves - is
  * these launches:
  *   orr_ppo_head       loss terms, d loss / d mean, d loss / d value, bias gradients of the two output layers
+ *   orr_distill_head   the loss head of policy distillation instead: squared error of the actor's mean against a teacher's, its gradient
  *   orr_head_backward  gradient through an output layer (fan-out 12 or 1) + ReLU mask + bias gradient of the layer below + the
  *                      output layer's weight gradient
  *   orr_colsum_finish  the column sums behind all bias gradients of a minibatch in one launch
@@ -43,6 +44,17 @@ int32_t orr_learner_partial_rows(int32_t m);
  *   stats [2]                   surrogate, value loss (means over the minibatch) */
 int32_t orr_ppo_head(const float* mean, const float* value, const float* batch, int32_t m, float std, float clip, float vf_coef,
                      float* g_mean, float* g_value, float* gb_mean, float* gb_value, float* stats, float* workspace, void* stream);
+
+/* Loss head of policy distillation for a minibatch of m samples: the student's means against a teacher's (DAgger labels; host side:
+ * learner_hip.FusedDistill).  loss = (1 / m) sum_i sum_j (mean[i][j] - target[i][j])^2, j over the 12 actions.
+ *   mean [m][12], target [m][12]   the student's and the teacher's actor outputs
+ *   g_mean [m][12]                 d loss / d mean = 2 (mean - target) / m
+ *   gb_mean [12]                   column sums of g_mean = the student's output-layer bias gradient
+ *   stats [1]                      the loss
+ * m, the alignment and the workspace are orr_ppo_head's (orr_learner_workspace_floats(m, 16) floats suffice); the sums run in a fixed
+ * order.  The rest of the student's backward pass is orr_head_backward, orr_relu_backward, orr_colsum_finish and orr_adam_step. */
+int32_t orr_distill_head(const float* mean, const float* target, int32_t m, float* g_mean, float* gb_mean, float* stats, float* workspace,
+                         void* stream);
 
 /* g [m][c] (gradient w.r.t. a ReLU layer's output h [m][c]) becomes the gradient w.r.t. its pre-activation, in place: g *= (h > 0);
  * gb [c] = its column sums (the layer's bias gradient).  c: a multiple of 4 with 1024 % c == 0.

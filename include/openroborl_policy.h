@@ -64,6 +64,19 @@ int32_t orr_policy_forward(const orr_policy_net* net, const float* obs, int32_t 
 int32_t orr_policy_forward_priv(const orr_policy_net* net, const float* obs, const float* priv, int32_t n, const float* noise,
                                 float std, float clip, float* action, float* raw, float* value, float* mean, void* stream);
 
+/* The same with a privileged ACTOR as well (a teacher policy, to be distilled into a plain one: openroborl_learner.h, orr_distill_head):
+ * both layer 0s read obs | priv.
+ *   net->w0_pi, net->w0_vf  packed images of (160 + 48) x 512 matrices (orr_policy_pack with k = 208), rows as above; every other
+ *                           member, and every other argument, as in orr_policy_forward_priv
+ *   value == NULL           also skips the critic's three layers (about half of the pass; a labelling call needs the mean only).
+ *                           action, raw and mean are the same bits with and without a value buffer
+ * With rows 160..207 of the actor's matrix zero, action, raw and mean equal orr_policy_forward's; with the same critic, value equals
+ * orr_policy_forward_priv's, bit for bit.
+ * Refused with a negative code, nothing launched or written: a null net, obs, priv or action, a null member of net, n <= 0, a packed
+ * weight matrix that is not 16-byte aligned, any other buffer that is not 4-byte aligned. */
+int32_t orr_policy_forward_teacher(const orr_policy_net* net, const float* obs, const float* priv, int32_t n, const float* noise,
+                                   float std, float clip, float* action, float* raw, float* value, float* mean, void* stream);
+
 /* Per-robot GAE(lambda) over a [T][N] rollout segment + per-robot advantage standardisation, one launch
  * (reference: add_vtarg_and_adv, agents/ppo_imitation.py:68-93, and the per-robot normalisation :329-338; device
  * layout and the deliberate use of each robot's own done flags: openroborl_amd/rollout.py).

@@ -181,3 +181,13 @@ class OrrPolicyNet(C.Structure):
 class OrrColsumJob(C.Structure):
     """include/openroborl_learner.h: orr_colsum_job."""
     _fields_ = [("partials", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]
+
+
+# include/openroborl_policy.h: int32_t orr_policy_forward_teacher(const orr_policy_net* net, const float* obs, const float* priv, int32_t n,
+#   const float* noise, float std, float clip, float* action, float* raw, float* value | NULL, float* mean, void* stream) - orr_policy_forward_priv's
+# arguments; w0_pi is a packed (160 + 48) x 512 matrix as well
+POLICY_FORWARD_TEACHER_ARGS = [C.POINTER(OrrPolicyNet), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_distill_head(const float* mean [m][12], const float* target [m][12], int32_t m, float* g_mean [m][12],
+#   float* gb_mean [12], float* stats [1], float* workspace, void* stream)
+DISTILL_HEAD_ARGS = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

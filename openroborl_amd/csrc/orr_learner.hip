@@ -96,6 +96,53 @@ __global__ __launch_bounds__(64) void ppo_head_finish_kernel(const float* __rest
   }
 }
 
+// ---- distillation loss head: one thread per sample, the same partials layout (columns 0..11 the bias gradient, 12 the squared error) --------
+__global__ __launch_bounds__(kThreads) void distill_head_kernel(const float* __restrict__ mean, const float* __restrict__ target, int M, float inv_m,
+                                                                float* __restrict__ g_mean, float* __restrict__ partials) {
+  __shared__ float red[kThreads / 64][kHeadCols];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  float acc[kAct + 1];
+#pragma unroll
+  for (int k = 0; k < kAct + 1; k++) acc[k] = 0.0f;
+  if (i < M) {
+    const f4* m4 = reinterpret_cast<const f4*>(mean + (size_t)i * kAct);
+    const f4* t4 = reinterpret_cast<const f4*>(target + (size_t)i * kAct);
+    const f4 d0 = m4[0] - t4[0], d1 = m4[1] - t4[1], d2 = m4[2] - t4[2];
+    const float d[kAct] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w, d2.x, d2.y, d2.z, d2.w};
+    float sq = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kAct; k++) { sq += d[k] * d[k]; acc[k] = 2.0f * d[k] * inv_m; }
+    acc[kAct] = sq;
+    f4* o4 = reinterpret_cast<f4*>(g_mean + (size_t)i * kAct);
+    o4[0] = f4{acc[0], acc[1], acc[2], acc[3]}; o4[1] = f4{acc[4], acc[5], acc[6], acc[7]}; o4[2] = f4{acc[8], acc[9], acc[10], acc[11]};
+  }
+#pragma unroll
+  for (int k = 0; k < kAct + 1; k++) {
+    const float s = wave_sum(acc[k]);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kHeadCols)
+    partials[(size_t)blockIdx.x * kHeadCols + threadIdx.x] =
+        threadIdx.x < kAct + 1 ? (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]) : 0.0f;
+}
+
+__global__ __launch_bounds__(64) void distill_head_finish_kernel(const float* __restrict__ partials, int nblk, float inv_m, float* __restrict__ gb_mean,
+                                                                 float* __restrict__ stats) {
+  // like ppo_head_finish_kernel: 16 columns x 4 interleaved row groups, combined in a fixed order
+  __shared__ float red[4][kHeadCols];
+  const int col = threadIdx.x & 15, part = threadIdx.x >> 4;
+  float s = 0.0f;
+  for (int b = part; b < nblk; b += 4) s += partials[(size_t)b * kHeadCols + col];
+  red[part][col] = s;
+  __syncthreads();
+  if (part == 0) {
+    const float t = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
+    if (col < kAct) gb_mean[col] = t;
+    else if (col == kAct) stats[0] = t * inv_m;
+  }
+}
+
 // ---- ReLU mask (+ the gradient through an output layer of fan-out K) + per-block column sums ------------------------------
 // A workgroup owns kRowsPerBlock rows and all c columns; a thread owns four adjacent columns (one 16-byte access per tensor and
 // row) of every (256 / (c/4))-th row.  K = 0: g holds the incoming gradient and is masked in place.  K > 0 (the layer below an
@@ -305,6 +352,19 @@ int32_t orr_ppo_head(const float* mean, const float* value, const float* batch, 
   hipLaunchKernelGGL(ppo_head_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, nblk, 1.0f / (float)m, gb_mean, gb_value, stats);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_ppo_head: launch", e);
+  return 0;
+}
+
+int32_t orr_distill_head(const float* mean, const float* target, int32_t m, float* g_mean, float* gb_mean, float* stats, float* workspace,
+                         void* stream) {
+  if (!mean || !target || !g_mean || !gb_mean || !stats || !workspace || m <= 0) return orr_fail(-1, "orr_distill_head: bad argument", hipSuccess);
+  if (!aligned16(mean) || !aligned16(target) || !aligned16(g_mean)) return orr_fail(-1, "orr_distill_head: buffers must be 16-byte aligned", hipSuccess);
+  const int nblk = (m + kThreads - 1) / kThreads;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(distill_head_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, st, mean, target, (int)m, 1.0f / (float)m, g_mean, workspace);
+  hipLaunchKernelGGL(distill_head_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, nblk, 1.0f / (float)m, gb_mean, stats);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_distill_head: launch", e);
   return 0;
 }
 

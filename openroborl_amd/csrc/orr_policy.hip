@@ -49,7 +49,7 @@ struct Params {
   float* mean;
   int n;
   float std, clip;
-  const float* priv;   // forward_kernel<kObs + kPriv> only; LAST: the fields above keep their offsets in the plain kernel's arguments
+  const float* priv;   // forward_kernel<kObs + kPriv, ..> only; LAST: the fields above keep their offsets in the plain kernel's arguments
 };
 
 // acc[t] += A(16 x 16 k-group kg, from LDS) * B(tile t, k-group kg): four k-steps of v_mfma_f32_16x16x4_f32 per tile.
@@ -68,7 +68,11 @@ __device__ __forceinline__ void mma_group(f32x4 (&acc)[TILES], const float (&a)[
 // k-group are read from LDS before the MFMAs of the current one.  K / 16 must be a multiple of DEPTH.
 // KGS, G0: the call covers k-groups [G0, G0 + K / 16) of a packed matrix of KGS k-groups, `act` pointing at column 16 G0 of the A operand
 // (default: all of it) - a matrix whose k-groups are no multiple of the depth is done as two calls.
-template <int TILES, int K, int DEPTH, int KGS = K / 16, int G0 = 0>
+// UNIT: names the calling kernel's family (forward_kernel passes its KP) and is used by nothing: kernels of different families then share
+// no instantiation of this function.  Before it is inlined the optimiser folds arguments that all call sites of an instantiation agree
+// on (the LDS tile's address among them) into the function; a third kernel calling the privileged kernel's instantiations took that away
+// from it and changed its instructions (profiles/teacher_policy.txt).
+template <int UNIT, int TILES, int K, int DEPTH, int KGS = K / 16, int G0 = 0>
 __device__ __forceinline__ void layer(f32x4 (&acc)[TILES], const float* __restrict__ wp, int nt0, const float* act, int stride, int lane) {
   constexpr int KG = K / 16;
   static_assert(KG % DEPTH == 0, "k-groups must be a multiple of the pipeline depth");
@@ -131,10 +135,15 @@ __device__ __forceinline__ void store_relu(const f32x4 (&acc)[TILES], const floa
 // KV: the width of the critic's input.  kObs: actor and critic read the observation (orr_policy_forward).  kObs + kPriv: the critic's
 // layer 0 reads the LDS tile obs | priv against a (kObs + kPriv) x 512 matrix (orr_policy_forward_priv); the actor reads the first kObs
 // columns of the same tile with the same code, so its outputs are bit for bit the plain kernel's.
-template <int KV>
+// KP: the width of the actor's input.  kObs + kPriv (orr_policy_forward_teacher, with KV = kObs + kPriv): the actor's layer 0 reads the whole
+// tile too, against its own (kObs + kPriv) x 512 matrix, by the critic's k-groups (twelve at depth 2 + one).  That instantiation also takes
+// value == NULL as "no critic": the test is on a kernel argument, i.e. uniform over the workgroup, it guards the critic's layers only and
+// every barrier is outside it; the actor's instructions and inputs are the same either way, and so are action, raw and mean.
+template <int KV, int KP = kObs>
 __global__ __launch_bounds__(256) void forward_kernel(Params P) {
   constexpr int kObsStride = KV + 1;            // odd strides: the 16 rows of an A fragment fall into distinct LDS banks
   static_assert(KV >= kObs && KV % 16 == 0 && (kObsStride & 1) == 1, "whole k-groups, odd stride");
+  static_assert(KP == kObs || KP == KV, "the actor reads the observation or the critic's whole tile");
   static_assert((kRows * kObsStride + kRows * kH0Stride + kRows * kH1Stride) * sizeof(float) <= 160 * 1024, "static LDS beyond the 160 KB of a gfx950 CU");
   __shared__ float s_obs[kRows * kObsStride];
   __shared__ float s_h0[kRows * kH0Stride];
@@ -159,20 +168,28 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
     f32x4 acc[8];
 #pragma unroll
     for (int t = 0; t < 8; t++) acc[t] = f32x4{0, 0, 0, 0};
-    layer<8, kObs, 2>(acc, P.net.w0_pi, 8 * wave, s_obs, kObsStride, lane);
-    store_relu<8>(acc, P.net.b0_pi, 8 * wave, s_h0, kH0Stride, lane);
-#pragma unroll
-    for (int t = 0; t < 8; t++) acc[t] = f32x4{0, 0, 0, 0};
-    if constexpr (KV == kObs) {
-      layer<8, kObs, 2>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
-    } else if constexpr (ORR_POLICY_PRIV_SPLIT) {
-      constexpr int kMain = KV / 32 * 32;       // the k-groups that depth 2 divides
-      layer<8, kMain, 2, KV / 16, 0>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
-      layer<8, KV - kMain, 1, KV / 16, kMain / 16>(acc, P.net.w0_vf, 8 * wave, s_obs + kMain, kObsStride, lane);
+    if constexpr (KP == kObs) {
+      layer<KP, 8, kObs, 2>(acc, P.net.w0_pi, 8 * wave, s_obs, kObsStride, lane);
     } else {
-      layer<8, KV, 1>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+      constexpr int kMain = KP / 32 * 32;
+      layer<KP, 8, kMain, 2, KP / 16, 0>(acc, P.net.w0_pi, 8 * wave, s_obs, kObsStride, lane);
+      layer<KP, 8, KP - kMain, 1, KP / 16, kMain / 16>(acc, P.net.w0_pi, 8 * wave, s_obs + kMain, kObsStride, lane);
     }
-    store_relu<8>(acc, P.net.b0_vf, 8 * wave, s_h0 + kH0, kH0Stride, lane);
+    store_relu<8>(acc, P.net.b0_pi, 8 * wave, s_h0, kH0Stride, lane);
+    if (KP == kObs || P.value) {       // KP == kObs: a constant, no test in those two kernels
+#pragma unroll
+      for (int t = 0; t < 8; t++) acc[t] = f32x4{0, 0, 0, 0};
+      if constexpr (KV == kObs) {
+        layer<KP, 8, kObs, 2>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+      } else if constexpr (ORR_POLICY_PRIV_SPLIT) {
+        constexpr int kMain = KV / 32 * 32;       // the k-groups that depth 2 divides
+        layer<KP, 8, kMain, 2, KV / 16, 0>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+        layer<KP, 8, KV - kMain, 1, KV / 16, kMain / 16>(acc, P.net.w0_vf, 8 * wave, s_obs + kMain, kObsStride, lane);
+      } else {
+        layer<KP, 8, KV, 1>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+      }
+      store_relu<8>(acc, P.net.b0_vf, 8 * wave, s_h0 + kH0, kH0Stride, lane);
+    }
   }
   __syncthreads();
   // ---- layer 1: 512 -> 256; this wave: column tiles [4 wave, 4 wave + 4) of each net ----
@@ -180,12 +197,14 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) acc[t] = f32x4{0, 0, 0, 0};
-    layer<4, kH0, 4>(acc, P.net.w1_pi, 4 * wave, s_h0, kH0Stride, lane);
+    layer<KP, 4, kH0, 4>(acc, P.net.w1_pi, 4 * wave, s_h0, kH0Stride, lane);
     store_relu<4>(acc, P.net.b1_pi, 4 * wave, s_h1, kH1Stride, lane);
+    if (KP == kObs || P.value) {
 #pragma unroll
-    for (int t = 0; t < 4; t++) acc[t] = f32x4{0, 0, 0, 0};
-    layer<4, kH0, 4>(acc, P.net.w1_vf, 4 * wave, s_h0 + kH0, kH0Stride, lane);
-    store_relu<4>(acc, P.net.b1_vf, 4 * wave, s_h1 + kH1, kH1Stride, lane);
+      for (int t = 0; t < 4; t++) acc[t] = f32x4{0, 0, 0, 0};
+      layer<KP, 4, kH0, 4>(acc, P.net.w1_vf, 4 * wave, s_h0 + kH0, kH0Stride, lane);
+      store_relu<4>(acc, P.net.b1_vf, 4 * wave, s_h1 + kH1, kH1Stride, lane);
+    }
   }
   __syncthreads();
   // ---- heads: wave 0 the actor (12 of 16 columns), wave 1 the critic (1 of 16 columns) ----
@@ -193,7 +212,7 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
   f32x4 acc[1] = {f32x4{0, 0, 0, 0}};
   const int col = lane & 15, r0 = 4 * (lane >> 4);
   if (wave == 0) {
-    layer<1, kH1, 4>(acc, P.net.w2_pi, 0, s_h1, kH1Stride, lane);
+    layer<KP, 1, kH1, 4>(acc, P.net.w2_pi, 0, s_h1, kH1Stride, lane);
     if (col < kAct) {
       const float b = P.net.b2_pi[col];
 #pragma unroll
@@ -209,8 +228,8 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
         }
       }
     }
-  } else {
-    layer<1, kH1, 4>(acc, P.net.w2_vf, 0, s_h1 + kH1, kH1Stride, lane);
+  } else if (KP == kObs || P.value) {
+    layer<KP, 1, kH1, 4>(acc, P.net.w2_vf, 0, s_h1 + kH1, kH1Stride, lane);
     if (col == 0 && P.value) {
       const float b = P.net.b2_vf[0];
 #pragma unroll
@@ -306,6 +325,26 @@ int32_t orr_policy_forward_priv(const orr_policy_net* net, const float* obs, con
   hipLaunchKernelGGL(forward_kernel<kObs + kPriv>, dim3((unsigned)((n + kRows - 1) / kRows)), dim3(256), 0, (hipStream_t)stream, P);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_policy_forward_priv: launch", e);
+  return 0;
+}
+
+int32_t orr_policy_forward_teacher(const orr_policy_net* net, const float* obs, const float* priv, int32_t n, const float* noise, float std,
+                                   float clip, float* action, float* raw, float* value, float* mean, void* stream) {
+  if (!net || !obs || !priv || !action || n <= 0) return orr_fail(-1, "orr_policy_forward_teacher: bad argument", hipSuccess);
+  const float* const* p = reinterpret_cast<const float* const*>(net);
+  for (int i = 0; i < 12; i++) {
+    if (!p[i]) return orr_fail(-1, "orr_policy_forward_teacher: orr_policy_net has a null pointer", hipSuccess);
+    if (reinterpret_cast<uintptr_t>(p[i]) & (i % 2 == 0 ? 15 : 3))     // packed weights are read 16 bytes per lane
+      return orr_fail(-1, "orr_policy_forward_teacher: packed weights must be 16-byte aligned, biases 4-byte aligned", hipSuccess);
+  }
+  for (const void* q : {(const void*)obs, (const void*)priv, (const void*)noise, (const void*)action, (const void*)raw, (const void*)value, (const void*)mean})
+    if (reinterpret_cast<uintptr_t>(q) & 3) return orr_fail(-1, "orr_policy_forward_teacher: buffers must be 4-byte aligned", hipSuccess);
+  Params P;
+  P.net = *net; P.obs = obs; P.noise = noise; P.action = action; P.raw = raw; P.value = value; P.mean = mean;
+  P.n = n; P.std = std; P.clip = clip; P.priv = priv;
+  hipLaunchKernelGGL((forward_kernel<kObs + kPriv, kObs + kPriv>), dim3((unsigned)((n + kRows - 1) / kRows)), dim3(256), 0, (hipStream_t)stream, P);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_policy_forward_teacher: launch", e);
   return 0;
 }
 

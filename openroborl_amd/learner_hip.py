@@ -45,8 +45,10 @@ class FusedPPO(object):
         # a privileged critic (ppo.ActorCritic(priv_dim=48)): its layer 0 reads x | priv, [M, 160 + 48]; everything behind layer 0 and the
         # whole actor are what they are without (the kernels of orr_learner.hip see hidden and output layers only)
         self.priv_dim = int(getattr(model, "priv_dim", 0))
+        # a privileged actor as well (ppo.ActorCritic(actor_priv_dim=48), a teacher): its layer 0 reads the same x | priv
+        self.actor_priv_dim = int(getattr(model, "actor_priv_dim", 0))
         # ---- one flat buffer for the parameters (16-byte aligned slots), the model's tensors become views of it ----
-        names = sorted(model.p)
+        names = self._trained(model)
         self.slots, off = {}, 0
         for k in names:
             n = model.p[k].numel()
@@ -67,6 +69,11 @@ class FusedPPO(object):
         if hasattr(model, "mark_updated"):
             model.mark_updated()
         self._plans = {}
+
+    @staticmethod
+    def _trained(model):
+        """Names of the parameters this learner owns: they move into its flat buffer and take its Adam steps."""
+        return sorted(model.p)
 
     # ---- launches ------------------------------------------------------------------------------------------------------
     def _stream(self):
@@ -134,7 +141,7 @@ class FusedPPO(object):
         jobs = (_abi.OrrColsumJob * 10)()
         for i, (net, k) in enumerate((("pi", 12), ("vf", 1))):
             P["h1_" + net], P["h2_" + net], P["y_" + net] = f(M, 512), f(M, 256), f(M, k)
-            k0 = 160 + (pd if net == "vf" else 0)          # rows of the net's layer-0 weight
+            k0 = 160 + (pd if net == "vf" else self.actor_priv_dim)          # rows of the net's layer-0 weight
             P["part1_" + net], P["part0_" + net] = (f(16, 512, 256), f(16, k0, 512)) if split else (None, None)
             if split:
                 jobs[6 + 2 * i] = _abi.OrrColsumJob(P["part1_" + net].data_ptr(), self.g["model/%s_fc1/w:0" % net].data_ptr(), 16, 512 * 256)
@@ -162,6 +169,8 @@ class FusedPPO(object):
             t.index_select(P["priv"], 0, idx, out=P["xp"])
             t.cat((x, P["xp"]), dim=1, out=P["xv"])
             xin["vf"] = P["xv"]
+            if self.actor_priv_dim:
+                xin["pi"] = P["xv"]
         for net in NETS:
             t._addmm_activation(w["model/%s_fc0/b:0" % net], xin[net], w["model/%s_fc0/w:0" % net], out=P["h1_" + net])
             t._addmm_activation(w["model/%s_fc1/b:0" % net], P["h1_" + net], w["model/%s_fc1/w:0" % net], out=P["h2_" + net])
@@ -246,7 +255,7 @@ class FusedPPO(object):
         world, several = self._world(), self._several()
         with t.no_grad():
             if old_logp is None:
-                old_logp = self.model.log_prob(obs, actions)
+                old_logp = self.model.log_prob(obs, actions, *((priv,) if self.actor_priv_dim else ()))
             P = self._plan(B, M)
             P["obs"].copy_(obs)
             if priv is not None:
@@ -305,3 +314,105 @@ class FusedPPO(object):
         """Raises unless this rank's parameters equal rank 0's bit for bit (mpi_adam.py:72-82; the reference checks every 100 steps)."""
         if self._several() and not bool(self.torch.equal(self._bcast_root(), self.flat_p)):
             raise RuntimeError("FusedPPO.check_synced: this rank's parameters differ from rank 0's")
+
+
+class FusedDistill(FusedPPO):
+    """Policy distillation on the device (the supervised step of DAgger; the torch reference is ppo.Distill): the student's mean is
+    regressed on a teacher's, loss = mean over the samples of sum_j (mean_j - target_j)^2 (orr_distill_head).  FusedPPO's machinery with
+    the actor alone: only model/pi* move into the flat buffer and take Adam steps - the critic's parameters stay where and what they are,
+    and have no moments here -, three forward GEMMs, the loss head, orr_head_backward, orr_relu_backward and one orr_colsum_finish per
+    minibatch, equal minibatches in static buffers, an epoch captured once and replayed as one hipGraph (a single chain on one stream).
+    One rank: there is no gradient all-reduce here."""
+
+    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True):
+        if getattr(student, "actor_priv_dim", 0):
+            raise ValueError("FusedDistill: the student's actor must read the 160 observation words only")
+        FusedPPO.__init__(self, student, lr=lr, adam_eps=adam_eps, minibatch=minibatch, betas=betas, use_graph=use_graph)
+
+    @staticmethod
+    def _trained(model):
+        return sorted(k for k in model.p if k.startswith("model/pi"))
+
+    def _graph_key(self, several):
+        return (self.lr, self.b1, self.b2, self.eps, self.adam_flags)
+
+    def _plan(self, B, M):
+        key = (B, M)
+        if key in self._plans:
+            return self._plans[key]
+        t = self.torch
+        f = lambda *shape: t.empty(shape, dtype=t.float32, device=self.dev)   # noqa: E731
+        split = M >= 4096 and M % 16 == 0
+        rows = int(self.L.orr_learner_partial_rows(M))
+        P = {"B": B, "M": M, "nmb": B // M, "obs": f(B, 160), "target": f(B, 12), "perm": t.empty(B, dtype=t.int64, device=self.dev),
+             "x": f(M, 160), "tgt": f(M, 12), "h1": f(M, 512), "h2": f(M, 256), "y": f(M, 12), "g_y": f(M, 12), "gz2": f(M, 256), "gh1": f(M, 512),
+             "stats": t.zeros(B // M, 1, dtype=t.float32, device=self.dev), "ws": f(int(self.L.orr_learner_workspace_floats(M, 16))),
+             "ws2": f(int(self.L.orr_learner_workspace_floats(M, 256))), "ws1": f(rows * 512),
+             "part1": f(16, 512, 256) if split else None, "part0": f(16, 160, 512) if split else None, "graphs": None}
+        g = self.g
+        jobs = (_abi.OrrColsumJob * 5)()
+        jobs[0] = _abi.OrrColsumJob(P["ws2"].data_ptr(), g["model/pi_fc1/b:0"].data_ptr(), rows, 256)
+        jobs[1] = _abi.OrrColsumJob(P["ws2"].data_ptr() + 4 * rows * 256, g["model/pi/w:0"].data_ptr(), rows, 256 * 12)
+        jobs[2] = _abi.OrrColsumJob(P["ws1"].data_ptr(), g["model/pi_fc0/b:0"].data_ptr(), rows, 512)
+        if split:
+            jobs[3] = _abi.OrrColsumJob(P["part1"].data_ptr(), g["model/pi_fc1/w:0"].data_ptr(), 16, 512 * 256)
+            jobs[4] = _abi.OrrColsumJob(P["part0"].data_ptr(), g["model/pi_fc0/w:0"].data_ptr(), 16, 160 * 512)
+        P["jobs"], P["n_jobs"] = jobs, 5 if split else 3
+        self._plans[key] = P
+        return P
+
+    def _minibatch(self, P, s):
+        """Gather, the actor's forward pass, loss head and backward of minibatch s of the current permutation; gradients land in flat_g."""
+        t, L, M, w, g = self.torch, self.L, P["M"], self.w, self.g
+        st = self._stream()
+        idx = P["perm"][s * M:(s + 1) * M]
+        t.index_select(P["obs"], 0, idx, out=P["x"])
+        t.index_select(P["target"], 0, idx, out=P["tgt"])
+        t._addmm_activation(w["model/pi_fc0/b:0"], P["x"], w["model/pi_fc0/w:0"], out=P["h1"])
+        t._addmm_activation(w["model/pi_fc1/b:0"], P["h1"], w["model/pi_fc1/w:0"], out=P["h2"])
+        t.addmm(w["model/pi/b:0"], P["h2"], w["model/pi/w:0"], out=P["y"])
+        _lib.check(L.orr_distill_head(P["y"].data_ptr(), P["tgt"].data_ptr(), M, P["g_y"].data_ptr(), g["model/pi/b:0"].data_ptr(),
+                                      P["stats"][s].data_ptr(), P["ws"].data_ptr(), st), L)
+        _lib.check(L.orr_head_backward(P["g_y"].data_ptr(), 12, w["model/pi/w:0"].data_ptr(), P["h2"].data_ptr(), M, 256, P["gz2"].data_ptr(),
+                                       None, None, P["ws2"].data_ptr(), st), L)
+        self._wgrad(P["h1"], P["gz2"], P["part1"], g["model/pi_fc1/w:0"])
+        t.mm(P["gz2"], w["model/pi_fc1/w:0"].t(), out=P["gh1"])
+        _lib.check(L.orr_relu_backward(P["gh1"].data_ptr(), P["h1"].data_ptr(), M, 512, None, P["ws1"].data_ptr(), st), L)
+        self._wgrad(P["x"], P["gh1"], P["part0"], g["model/pi_fc0/w:0"])
+        _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
+
+    def update(self, obs, target_mean, epochs=1, generator=None):
+        """obs [B,160], target_mean [B,12] (the teacher's actor output on the same states); returns the mean loss over the minibatches,
+        like ppo.Distill.update."""
+        t = self.torch
+        B = int(obs.shape[0])
+        if tuple(target_mean.shape) != (B, 12):
+            raise ValueError("FusedDistill: target_mean must have shape (%d, 12)" % B)
+        M = min(self.minibatch, B)
+        if B % M:
+            raise ValueError("FusedDistill: the number of samples (%d) must be a multiple of the minibatch size (%d); "
+                             "FusedPPO.fit_minibatch(%d, %d) = %d is the largest size that divides it" % (B, M, B, M, self.fit_minibatch(B, M)))
+        with t.no_grad():
+            P = self._plan(B, M)
+            P["obs"].copy_(obs)
+            P["target"].copy_(target_mean)
+            if self.use_graph and (P["graphs"] is None or P.get("graph_key") != self._graph_key(False)):
+                self._capture(P, False)
+                P["graph_key"] = self._graph_key(False)
+            total = t.zeros(1, dtype=t.float32, device=self.dev)
+            for _ in range(epochs):
+                P["perm"].copy_(t.randperm(B, device=self.dev, generator=generator))
+                if self.use_graph:
+                    P["graphs"][0].replay()
+                else:
+                    self._epoch_eager(P, 1, False)
+                total += P["stats"].sum(dim=0)
+        if hasattr(self.model, "mark_updated"):
+            self.model.mark_updated()
+        return float(total.item() / float(epochs * P["nmb"]))
+
+    def sync(self):
+        pass
+
+    def check_synced(self):
+        pass

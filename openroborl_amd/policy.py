@@ -58,6 +58,8 @@ def save_parameters_zip(path, params, data=None):
             v = np.asarray(params[name], dtype=np.float32)
             if name == "model/vf_fc0/w:0" and v.shape == (shape[0] + PRIV_DIM, shape[1]):
                 pass       # a privileged critic (ppo.ActorCritic(priv_dim=48)), written in full: the actor part is what the reference can load
+            elif name == "model/pi_fc0/w:0" and v.shape == (shape[0] + PRIV_DIM, shape[1]):
+                pass       # a privileged actor (ppo.ActorCritic(actor_priv_dim=48)): a teacher, loadable here only; its distilled student is plain
             elif v.shape != shape:
                 raise ValueError("%s has shape %s, the reference graph expects %s" % (name, v.shape, shape))
         elif name.startswith("model/q/"):

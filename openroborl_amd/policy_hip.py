@@ -34,10 +34,14 @@ class FusedActorCritic(object):
         self.packed = {}
         self.biases = {}
         self.priv_dim = 0             # 48 when model/vf_fc0/w:0 has 160 + 48 rows: forward() then takes `priv` and runs orr_policy_forward_priv
+        self.actor_priv_dim = 0       # 48 when model/pi_fc0/w:0 has 160 + 48 rows as well (a teacher): orr_policy_forward_teacher
         for field, key in KEYS:
             w = params[key]
             if field.startswith("w"):
                 k, n = SHAPES[field]
+                if field == "w0_pi" and tuple(w.shape) == (k + _abi.POLICY_PRIV_DIM, n):
+                    k += _abi.POLICY_PRIV_DIM     # a privileged actor: its layer 0 reads obs | priv too (orr_policy_forward_teacher)
+                    self.actor_priv_dim = _abi.POLICY_PRIV_DIM
                 if field == "w0_vf" and tuple(w.shape) == (k + _abi.POLICY_PRIV_DIM, n):
                     k += _abi.POLICY_PRIV_DIM     # a privileged critic: its layer 0 reads obs | priv (orr_policy_forward_priv)
                     self.priv_dim = _abi.POLICY_PRIV_DIM
@@ -45,6 +49,8 @@ class FusedActorCritic(object):
                     raise ValueError("%s has shape %s, the fused kernel is built for %s" % (key, tuple(w.shape), (k, n)))
                 size = int(self.L.orr_policy_packed_size(k, n))
                 self.packed[field] = torch.empty(size, dtype=torch.float32, device=self.device)
+        if self.actor_priv_dim and not self.priv_dim:
+            raise ValueError("a privileged actor (model/pi_fc0/w:0 with %d rows) needs a privileged critic" % (160 + _abi.POLICY_PRIV_DIM))
         self.net = _abi.OrrPolicyNet()
         self.refresh()
 
@@ -68,11 +74,12 @@ class FusedActorCritic(object):
                 self.biases[field].copy_(w)
                 setattr(self.net, field, self.biases[field].data_ptr())
 
-    def forward(self, obs, noise=None, want_mean=False, out_action=None, out_raw=None, out_value=None, priv=None):
+    def forward(self, obs, noise=None, want_mean=False, out_action=None, out_raw=None, out_value=None, priv=None, out_mean=None, want_value=True):
         """obs [N,160] float32 on the device; noise [N,12] standard normal or None (deterministic); priv [N,48] float32, the
         privileged observation, for a privileged critic (and only then).
         Returns (clipped action [N,12], raw action [N,12], value [N], mean [N,12] or None); the out_* tensors
-        (contiguous float32 of those shapes, e.g. rows of a rollout buffer) are written in place when given."""
+        (contiguous float32 of those shapes, e.g. rows of a rollout buffer) are written in place when given (out_mean implies want_mean).
+        want_value=False: no value is written and None is returned for it; a privileged actor's kernel then skips the critic."""
         t = self.torch
         if obs.dtype != t.float32 or not obs.is_contiguous() or obs.device != self.device or obs.dim() != 2 or obs.shape[1] != 160:
             raise ValueError("obs must be a contiguous float32 [N,160] tensor on %s" % (self.device,))
@@ -91,15 +98,23 @@ class FusedActorCritic(object):
             if x.dtype != t.float32 or not x.is_contiguous() or tuple(x.shape) != shape or x.device != self.device:
                 raise ValueError("output tensor must be contiguous float32 %s on %s" % (shape, self.device))
             return x
-        act, raw, val = out(out_action, (n, 12)), out(out_raw, (n, 12)), out(out_value, (n,))
-        mean = t.empty(n, 12, dtype=t.float32, device=self.device) if want_mean else None
+        if not want_value and out_value is not None:
+            raise ValueError("out_value given with want_value=False")
+        act, raw, val = out(out_action, (n, 12)), out(out_raw, (n, 12)), out(out_value, (n,)) if want_value else None
+        mean = out(out_mean, (n, 12)) if (want_mean or out_mean is not None) else None
+        if self.actor_priv_dim:
+            _lib.check(self.L.orr_policy_forward_teacher(C.byref(self.net), obs.data_ptr(), priv.data_ptr(), int(n),
+                                                         noise.data_ptr() if noise is not None else None, self.std, self.clip, act.data_ptr(),
+                                                         raw.data_ptr(), val.data_ptr() if val is not None else None,
+                                                         mean.data_ptr() if mean is not None else None, self._stream()), self.L)
+            return act, raw, val, mean
         if priv is not None:
             _lib.check(self.L.orr_policy_forward_priv(C.byref(self.net), obs.data_ptr(), priv.data_ptr(), int(n),
                                                       noise.data_ptr() if noise is not None else None, self.std, self.clip, act.data_ptr(),
-                                                      raw.data_ptr(), val.data_ptr(), mean.data_ptr() if mean is not None else None,
+                                                      raw.data_ptr(), val.data_ptr() if val is not None else None, mean.data_ptr() if mean is not None else None,
                                                       self._stream()), self.L)
             return act, raw, val, mean
         _lib.check(self.L.orr_policy_forward(C.byref(self.net), obs.data_ptr(), int(n), noise.data_ptr() if noise is not None else None,
-                                             self.std, self.clip, act.data_ptr(), raw.data_ptr(), val.data_ptr(),
+                                             self.std, self.clip, act.data_ptr(), raw.data_ptr(), val.data_ptr() if val is not None else None,
                                              mean.data_ptr() if mean is not None else None, self._stream()), self.L)
         return act, raw, val, mean

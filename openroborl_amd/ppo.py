@@ -54,9 +54,14 @@ class ActorCritic(object):
 
     priv_dim = 48 makes the critic privileged (the asymmetric actor-critic): model/vf_fc0/w:0 is [obs_dim + priv_dim, 512] and reads
     cat(obs, priv), priv = env.privileged_obs(); the actor is what it is without, so its part of a saved zip loads wherever the plain
-    policy loads.  With `params` the width is taken from that matrix.  priv_dim = 0: every path is the plain one."""
+    policy loads.  With `params` the width is taken from that matrix.  priv_dim = 0: every path is the plain one.
 
-    def __init__(self, device, obs_dim=160, act_dim=12, hidden=(512, 256), std=pol.PI_STD, params=None, seed=0, priv_dim=0):
+    actor_priv_dim = 48 (with priv_dim = 48 only) makes the actor privileged as well - a teacher policy: model/pi_fc0/w:0 is
+    [obs_dim + 48, 512] too, and mean(), log_prob() and act() take `priv`.  Such a policy cannot be deployed (nor loaded by the reference);
+    Distill / learner_hip.FusedDistill turn it into a plain one.  With `params` the width is taken from model/pi_fc0/w:0.
+    actor_priv_dim = 0: every path is the one without."""
+
+    def __init__(self, device, obs_dim=160, act_dim=12, hidden=(512, 256), std=pol.PI_STD, params=None, seed=0, priv_dim=0, actor_priv_dim=0):
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -66,12 +71,19 @@ class ActorCritic(object):
         if priv_dim not in (0, pol.PRIV_DIM):
             raise ValueError("priv_dim must be 0 or %d, got %r" % (pol.PRIV_DIM, priv_dim))
         self.priv_dim = int(priv_dim)
+        if params is not None and "model/pi_fc0/w:0" in params:
+            actor_priv_dim = int(np.shape(params["model/pi_fc0/w:0"])[0]) - obs_dim
+        if actor_priv_dim not in (0, pol.PRIV_DIM):
+            raise ValueError("actor_priv_dim must be 0 or %d, got %r" % (pol.PRIV_DIM, actor_priv_dim))
+        if actor_priv_dim and not self.priv_dim:
+            raise ValueError("a privileged actor (actor_priv_dim = %d) needs the privileged critic (priv_dim = %d)" % (pol.PRIV_DIM, pol.PRIV_DIM))
+        self.actor_priv_dim = int(actor_priv_dim)
         g = torch.Generator().manual_seed(seed)
         self.p = {}
         dims = [obs_dim] + list(hidden)
         for net, out in (("pi", act_dim), ("vf", 1)):
             for i in range(len(hidden)):
-                fan_in = dims[i] + (self.priv_dim if (net, i) == ("vf", 0) else 0)
+                fan_in = dims[i] + (self.priv_dim if (net, i) == ("vf", 0) else 0) + (self.actor_priv_dim if (net, i) == ("pi", 0) else 0)
                 self._init("model/%s_fc%d" % (net, i), fan_in, dims[i + 1], g, math.sqrt(2.0))
             self._init("model/%s" % net, dims[-1], out, g, 0.01 if net == "pi" else 1.0)
         self.extra = {}            # variables of a loaded zip that this learner does not train (model/q/*): re-emitted by state_dict()
@@ -126,8 +138,17 @@ class ActorCritic(object):
         h = f(h, self.p["model/%s_fc1/w:0" % net], self.p["model/%s_fc1/b:0" % net])
         return out(h, self.p["model/%s/w:0" % net], self.p["model/%s/b:0" % net])
 
-    def mean(self, obs):
-        return self._mlp("pi", obs)
+    def _actor_input(self, obs, priv):
+        if (priv is not None) != (self.actor_priv_dim > 0):
+            raise ValueError("priv is needed by a privileged actor (actor_priv_dim = %d) and by no other" % pol.PRIV_DIM)
+        return obs if priv is None else self.torch.cat((obs, priv), dim=1)
+
+    def actor_priv(self, priv):
+        """What mean() and log_prob() take as `priv` when the caller holds the critic's: the vector for a privileged actor, None for a plain one."""
+        return priv if self.actor_priv_dim else None
+
+    def mean(self, obs, priv=None):
+        return self._mlp("pi", self._actor_input(obs, priv))
 
     def _critic_input(self, obs, priv):
         if (priv is not None) != (self.priv_dim > 0):
@@ -139,7 +160,7 @@ class ActorCritic(object):
 
     def act(self, obs, priv=None, deterministic=False, generator=None, noise=None, out_raw=None, out_value=None):
         """-> (clipped action, raw action, value).  `noise` ([N,12] standard normal) overrides the generator; `priv` ([N,48], the
-        privileged observation) goes to a privileged critic."""
+        privileged observation) goes to a privileged critic, and to a privileged actor."""
         t = self.torch
         if (priv is not None) != (self.priv_dim > 0):
             raise ValueError("priv is needed by a privileged critic (priv_dim = %d) and by no other" % pol.PRIV_DIM)
@@ -152,14 +173,14 @@ class ActorCritic(object):
             a, raw, v, _ = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value, priv=priv)
             return a, raw, v
         with t.no_grad():
-            mu = self.mean(obs)
+            mu = self.mean(obs, self.actor_priv(priv))
             if noise is None and not deterministic:
                 noise = t.randn(mu.shape, device=mu.device, generator=generator)
             a = mu if deterministic else mu + self.std * noise
             return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, priv)
 
-    def log_prob(self, obs, actions):
-        mu = self.mean(obs)
+    def log_prob(self, obs, actions, priv=None):
+        mu = self.mean(obs, priv)
         var = self.std * self.std
         return (-0.5 * ((actions - mu) ** 2) / var - 0.5 * math.log(2.0 * math.pi * var)).sum(dim=1)
 
@@ -204,9 +225,11 @@ class PPO(object):
         B = obs.shape[0]
         if (priv is not None) != (getattr(self.model, "priv_dim", 0) > 0):
             raise ValueError("priv is needed by a privileged critic and by no other")
+        # a privileged actor (model.actor_priv_dim) reads the same rows
+        actor_priv = (lambda x: (x,)) if getattr(self.model, "actor_priv_dim", 0) else (lambda x: ())
         if old_logp is None:
             with t.no_grad():
-                old_logp = self.model.log_prob(obs, actions)
+                old_logp = self.model.log_prob(obs, actions, *actor_priv(priv))
         stats = []
         for _ in range(epochs):
             perm = t.randperm(B, device=obs.device, generator=generator)
@@ -215,7 +238,7 @@ class PPO(object):
             priv_p = None if priv is None else priv[perm]
             for s in range(0, B, self.minibatch):
                 e = s + self.minibatch
-                logp = self.model.log_prob(obs_p[s:e], act_p[s:e])
+                logp = self.model.log_prob(obs_p[s:e], act_p[s:e], *actor_priv(None if priv_p is None else priv_p[s:e]))
                 ratio = t.exp(logp - old_p[s:e])
                 a = adv_p[s:e]
                 surr = -t.min(ratio * a, t.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip) * a).mean()
@@ -230,3 +253,38 @@ class PPO(object):
                     self.model.mark_updated()
                 stats.append(t.stack((surr.detach(), vf.detach())))   # stays on the device: no sync per minibatch
         return t.stack(stats).mean(dim=0).cpu().numpy()
+
+
+class Distill(object):
+    """Policy distillation in plain torch (DAgger's supervised step; the fp32 reference of learner_hip.FusedDistill): the student's mean is
+    regressed on a teacher's, loss = mean over the samples of sum_j (mean_j - target_j)^2.  Only the actor (model/pi*) is trained; the
+    critic's parameters are not touched and have no optimiser state.  The student is a plain policy (actor_priv_dim = 0)."""
+
+    def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096):
+        import torch
+        self.torch = torch
+        if getattr(student, "actor_priv_dim", 0):
+            raise ValueError("Distill: the student's actor must read the 160 observation words only")
+        self.model = student
+        self.minibatch = int(minibatch)
+        params = [student.p[k] for k in sorted(student.p) if k.startswith("model/pi")]
+        self.opt = torch.optim.Adam(params, lr=lr, eps=adam_eps, fused=bool(params and params[0].is_cuda))
+
+    def update(self, obs, target_mean, epochs=1, generator=None):
+        """obs [B,160], target_mean [B,12] (the teacher's actor output on the same states); returns the mean loss over the minibatches."""
+        t = self.torch
+        B = obs.shape[0]
+        stats = []
+        for _ in range(epochs):
+            perm = t.randperm(B, device=obs.device, generator=generator)
+            obs_p, tgt_p = obs[perm], target_mean[perm]
+            for s in range(0, B, self.minibatch):
+                e = s + self.minibatch
+                loss = ((self.model.mean(obs_p[s:e]) - tgt_p[s:e]) ** 2).sum(dim=1).mean()
+                self.opt.zero_grad(set_to_none=True)
+                loss.backward()
+                self.opt.step()
+                if hasattr(self.model, "mark_updated"):
+                    self.model.mark_updated()
+                stats.append(loss.detach())
+        return float(t.stack(stats).mean())

@@ -14,22 +14,47 @@ resetting when any robot is done, and the GAE recursion uses each robot's own do
 indexes `episode_starts[(step*num_robot+i) + (1+i)]`, ppo_imitation.py:88, which reads a neighbouring
 robot's flag; `legacy_gae_index=True` reproduces exactly that, for comparisons with the reference at num_robot > 1).
 """
+from ._abi import PRIV_DIM
 
 
-def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generator=None, noise=None, priv=None):
+def _teacher_labels(teacher, obs, priv, out_mean, out_action):
+    """The teacher's actor output on (obs, priv) into out_mean [N,12] and its clipped copy into out_action [N,12]: no noise, no value (a
+    privileged actor's fused pass then skips the critic)."""
+    fused = getattr(teacher, "fused", None)
+    if fused is not None:
+        if teacher._fused_dirty:
+            fused.refresh()
+            teacher._fused_dirty = False
+        fused.forward(obs, None, out_action=out_action, out_mean=out_mean, want_value=False, priv=priv if teacher.priv_dim else None)
+    else:
+        import math
+        import torch
+        with torch.no_grad():
+            out_mean.copy_(teacher.mean(obs, teacher.actor_priv(priv)))
+            torch.clamp(out_mean, -2.0 * math.pi, 2.0 * math.pi, out=out_action)
+
+
+def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generator=None, noise=None, priv=None, teacher=None, teacher_mask=None):
     """Run `horizon` env steps of all robots.  Returns a dict of [T, N, ...] tensors + the final observation.
     noise: optional [T, N, 12] standard-normal samples for the fused policy (default: drawn from `generator`).
     A policy with a privileged critic (priv_dim > 0) also gets env.privileged_obs() at every step: "priv" [T, N, 48] and "last_priv" are
-    returned; priv: the one that belongs to `obs` (the previous segment's last_priv; None = computed here with done=None)."""
+    returned; priv: the one that belongs to `obs` (the previous segment's last_priv; None = computed here with done=None).
+    teacher: a second policy (a ppo.ActorCritic, usually one with a privileged actor) that labels every visited state for distillation
+    (DAgger: the student `policy` drives, the teacher labels): env.privileged_obs() then follows every step whatever the student's
+    priv_dim, and "teacher_mean" [T, N, 12] - the teacher's actor output on (obs[k], priv[k]) - is returned with "priv" and "last_priv".
+    teacher_mask: uint8 [N]; robots with the mask set are stepped with the teacher's clipped mean instead of the student's sampled
+    action ("actions" stays the student's raw sample)."""
     t = env.torch
     n = env.num_robot
     dev = env.device
     if obs is None:
         obs = env.reset()
     priv_dim = int(getattr(policy, "priv_dim", 0))
+    if teacher_mask is not None and teacher is None:
+        raise ValueError("teacher_mask without a teacher")
     pbuf = None
-    if priv_dim:
-        pbuf = t.empty((horizon + 1, n, priv_dim), device=dev)
+    if priv_dim or teacher is not None:
+        pbuf = t.empty((horizon + 1, n, PRIV_DIM), device=dev)
         if priv is None:
             env.privileged_obs(out=pbuf[0], done=None)
         else:
@@ -39,6 +64,8 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
         "rewards": t.empty((horizon, n), device=dev), "dones": t.empty((horizon, n), dtype=t.bool, device=dev),
         "vpred": t.empty((horizon, n), device=dev),
     }
+    if teacher is not None:
+        buf["teacher_mean"], tclip = t.empty((horizon, n, 12), device=dev), t.empty((n, 12), device=dev)
     fused = getattr(policy, "fused", None) is not None
     if fused and not deterministic and noise is None:   # one launch for the whole segment's exploration noise
         noise = t.randn((horizon, n, 12), device=dev, generator=generator)
@@ -54,13 +81,17 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
             buf["obs"][k].copy_(obs)
             buf["actions"][k].copy_(raw)
             buf["vpred"][k].copy_(v)
+        if teacher is not None:
+            _teacher_labels(teacher, obs, pbuf[k], buf["teacher_mean"][k], tclip)
+            if teacher_mask is not None:
+                clipped = t.where(teacher_mask.view(t.bool)[:, None], tclip, clipped)
         obs, rew, done, _ = env.step(clipped.contiguous())
         buf["rewards"][k].copy_(rew)
         buf["dones"][k].copy_(done.bool())
-        if priv_dim:    # of the state the new observation belongs to; robots that just ended an episode: no contact / push words
+        if pbuf is not None:    # of the state the new observation belongs to; robots that just ended an episode: no contact / push words
             env.privileged_obs(out=pbuf[k + 1], done=done)
     buf["last_obs"] = obs
-    if priv_dim:
+    if pbuf is not None:
         buf["priv"], buf["last_priv"] = pbuf[:horizon], pbuf[horizon]
     if noise is not None:
         # log-probability of the sampled actions under the sampling policy: a - mean = std * noise
@@ -83,21 +114,30 @@ class GraphRollout(object):
     done=dones[k]) follows every step_into inside the captured segment, priv[k] goes to the forward pass, and "priv" / "last_priv" are
     returned.
 
+    With a `teacher` (collect_rollout's: the student `policy` drives, the teacher labels - DAgger) the segment holds priv whatever the
+    student's priv_dim, and teacher_mean [T, N, 12]: after the student's forward pass the teacher's (no noise, no value) writes
+    teacher_mean[k] from (obs[k], priv[k]), and the robots whose `teacher_mask` (uint8 [N], a static tensor of the collector: change it
+    in place between collects, no new capture) is set are stepped with the teacher's clipped mean, the others with the student's sampled
+    action; "actions" stays the student's raw sample.  All of it is inside the captured segment, the teacher's weight re-pack included.
+
     The returned tensors are views of the static buffers: they are overwritten by the next collect() (clone what must survive it,
     e.g. the last row of `dones` that the next segment's GAE takes as first_starts)."""
 
-    def __init__(self, env, policy, horizon):
+    def __init__(self, env, policy, horizon, teacher=None):
         t = env.torch
-        if getattr(policy, "fused", None) is None:
+        if getattr(policy, "fused", None) is None or (teacher is not None and getattr(teacher, "fused", None) is None):
             raise RuntimeError("GraphRollout needs the fused policy (ActorCritic.enable_fused()); the plain path is collect_rollout()")
-        self.env, self.policy, self.T = env, policy, int(horizon)
+        self.env, self.policy, self.T, self.teacher = env, policy, int(horizon), teacher
         n, dev, T = env.num_robot, env.device, self.T
         f = lambda *shape: t.empty(shape, dtype=t.float32, device=dev)   # noqa: E731
         self.obs, self.actions, self.clipped = f(T + 1, n, 160), f(T, n, 12), f(n, 12)
         self.rewards, self.vpred, self.noise, self.logp = f(T, n), f(T, n), f(T, n, 12), f(T, n)
         self.dones = t.zeros((T, n), dtype=t.uint8, device=dev)
         self.priv_dim = int(getattr(policy, "priv_dim", 0))
-        self.priv = f(T + 1, n, self.priv_dim) if self.priv_dim else None
+        self.priv = f(T + 1, n, self.priv_dim or PRIV_DIM) if (self.priv_dim or teacher is not None) else None
+        if teacher is not None:
+            self.teacher_mean, self.teacher_clipped, self.step_action = f(T, n, 12), f(n, 12), f(n, 12)
+            self.teacher_mask = t.zeros(n, dtype=t.uint8, device=dev)
         self.graph, self.calls = None, 0
         self._captured_for = None          # (env.launch_params_generation, policy.std) the graph was captured with
 
@@ -108,13 +148,20 @@ class GraphRollout(object):
         import math
         t, env, fused = self.env.torch, self.env, self.policy.fused
         fused.refresh()                   # inside the graph: every replay re-packs the weights the learner has just updated
+        if self.teacher is not None:
+            self.teacher.fused.refresh()
         for k in range(self.T):
             if self.priv_dim:
                 fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], priv=self.priv[k])
             else:
                 fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k])
-            env.step_into(self.clipped, self.obs[k + 1], self.rewards[k], self.dones[k])
-            if self.priv_dim:
+            action = self.clipped
+            if self.teacher is not None:
+                self.teacher.fused.forward(self.obs[k], None, out_action=self.teacher_clipped, out_mean=self.teacher_mean[k], want_value=False,
+                                           priv=self.priv[k] if self.teacher.priv_dim else None)
+                action = t.where(self.teacher_mask.view(t.bool)[:, None], self.teacher_clipped, self.clipped, out=self.step_action)
+            env.step_into(action, self.obs[k + 1], self.rewards[k], self.dones[k])
+            if self.priv is not None:
                 env.privileged_obs(out=self.priv[k + 1], done=self.dones[k])
         # log-probability of the sampled actions under the sampling policy: a - mean = std * noise
         t.sum(self.noise * self.noise, dim=-1, out=self.logp)
@@ -127,7 +174,7 @@ class GraphRollout(object):
         with t.no_grad():
             if obs.data_ptr() != self.obs[0].data_ptr():
                 self.obs[0].copy_(obs)
-            if self.priv_dim:
+            if self.priv is not None:
                 if priv is None:
                     env.privileged_obs(out=self.priv[0], done=None)
                 elif priv.data_ptr() != self.priv[0].data_ptr():
@@ -154,10 +201,14 @@ class GraphRollout(object):
                 self.graph.replay()
                 env._env_step_counter += self.T
             self.policy._fused_dirty = False
+            if self.teacher is not None:
+                self.teacher._fused_dirty = False
         buf = {"obs": self.obs[:self.T], "actions": self.actions, "rewards": self.rewards, "dones": self.dones.view(t.bool),
                "vpred": self.vpred, "logp": self.logp, "last_obs": self.obs[self.T]}
-        if self.priv_dim:
+        if self.priv is not None:
             buf["priv"], buf["last_priv"] = self.priv[:self.T], self.priv[self.T]
+        if self.teacher is not None:
+            buf["teacher_mean"] = self.teacher_mean
         return buf
 
 

@@ -3,7 +3,8 @@ tools/diag/variant_time.py: medians of 5 x 300 back-to-back launches, every cand
 captured graph, so that no host time sits between them):
 python tools/diag/privileged_time.py [--alt-policy-lib PATH]
 
-  forward   orr_policy_forward_priv against orr_policy_forward, random weights; with --alt-policy-lib also the same entry point of a
+  forward   orr_policy_forward_priv, orr_policy_forward_teacher and orr_policy_forward_teacher with value = NULL (the labelling call of
+            distillation: no critic) against orr_policy_forward, random weights; with --alt-policy-lib also orr_policy_forward_priv of a
             second build of csrc/orr_policy.hip (e.g. -DORR_POLICY_PRIV_SPLIT=0: the critic's layer 0 at pipeline depth 1 instead of
             12 + 1 k-groups), loaded next to the shipped library and run on the same packed weights
   row       orr_privileged_obs with contact and push outputs bound against the env step of the same env (train mode, randomiser, pushes
@@ -58,6 +59,7 @@ def report(names, fns):
         print("%-52s %.4f ms (median of %d x %d back-to-back launches; all: %s)" % (name, mid, ROUNDS, LAUNCHES, " ".join("%.4f" % x for x in m)))
     for name, mid in zip(names[1:], med[1:]):
         print("%s against %s: %+.2f %% (ratio %.4f)" % (name, names[0], 100.0 * (mid / med[0] - 1.0), mid / med[0]))
+    return med
 
 
 # ---- forward ----
@@ -68,9 +70,14 @@ fp, f0 = policy_hip.FusedActorCritic(model.p, dev, std=0.125), policy_hip.FusedA
 g = torch.Generator(device=dev).manual_seed(0)
 obs, priv, noise = (torch.randn(N, c, device=dev, generator=g) for c in (160, _abi.POLICY_PRIV_DIM, 12))
 act, raw, val = torch.empty(N, 12, device=dev), torch.empty(N, 12, device=dev), torch.empty(N, device=dev)
-names = ["orr_policy_forward", "orr_policy_forward_priv"]
+teacher = ppo.ActorCritic(dev, seed=3, priv_dim=_abi.POLICY_PRIV_DIM, actor_priv_dim=_abi.POLICY_PRIV_DIM)
+ft = policy_hip.FusedActorCritic(teacher.p, dev, std=0.125)
+mean = torch.empty(N, 12, device=dev)
+names = ["orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_teacher, value = NULL"]
 fns = [lambda: f0.forward(obs, noise, out_action=act, out_raw=raw, out_value=val),
-       lambda: fp.forward(obs, noise, out_action=act, out_raw=raw, out_value=val, priv=priv)]
+       lambda: fp.forward(obs, noise, out_action=act, out_raw=raw, out_value=val, priv=priv),
+       lambda: ft.forward(obs, noise, out_action=act, out_raw=raw, out_value=val, priv=priv),
+       lambda: ft.forward(obs, None, out_action=act, out_raw=raw, out_mean=mean, want_value=False, priv=priv)]
 if args.alt_policy_lib:
     alt = C.CDLL(args.alt_policy_lib)
     alt.orr_policy_forward_priv.restype = C.c_int32
@@ -83,7 +90,10 @@ if args.alt_policy_lib:
         assert rc == 0
     names.append("orr_policy_forward_priv, --alt-policy-lib")
     fns.append(run_alt)
-report(names, fns)
+med = report(names, fns)
+# MFMAs per wave: 1728 plain, 1824 with the critic's 13th k-group pair (+96), 1920 with the actor's too (+96); 992 without the critic
+print("orr_policy_forward_teacher against orr_policy_forward_priv: %+.2f %% (the MFMA counts give %+.2f %%)" % (100.0 * (med[2] / med[1] - 1.0), 100.0 * 96 / 1824))
+print("orr_policy_forward_teacher, value = NULL against orr_policy_forward_teacher: ratio %.4f (the MFMA counts give %.4f)" % (med[3] / med[2], 992.0 / 1920.0))
 if args.alt_policy_lib:
     fns[1](); run_alt(); torch.cuda.synchronize()
     print("the two builds' values are equal bit for bit: %s" % bool(torch.equal(val, val_alt)))

@@ -5,6 +5,8 @@ leaves the GPU.  Counterpart of `python3 OpenRoboRL/run.py --task imitation_lear
 
   python train.py --task imitation_learning_laikago --iters 200
   python train.py --task imitation_learning_laikago --iters 200 --privileged-critic --push 0.02,0.2,0.5   (asymmetric actor-critic)
+  python train.py --task imitation_learning_laikago --iters 200 --privileged-actor --push 0.02,0.2,0.5 --save teacher.zip   (a teacher)
+  python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --push 0.02,0.2,0.5 --save student.zip   (its student)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py ...
 """
 import argparse
@@ -63,6 +65,18 @@ def main():
                          "keeps the 160 observation words.  Binds the contact outputs, and the push outputs with --push.  --save then writes the "
                          "full critic under the usual names (model/vf_fc0/w:0 with 208 rows): the actor part is what the reference can load, "
                          "--eval of such a zip works here")
+    ap.add_argument("--privileged-actor", action="store_true",
+                    help="a teacher policy: the actor reads the privileged observation as well (implies --privileged-critic; model/pi_fc0/w:0 "
+                         "with 208 rows too), trained with PPO.  --save writes a zip that loads here (--eval, --distill) and not in the "
+                         "reference; --distill turns it into a deployable 160-input policy")
+    ap.add_argument("--distill", default="", metavar="TEACHER.zip",
+                    help="train a plain student by distillation instead of PPO (DAgger): every segment is collected with the student's actions "
+                         "and labelled with the teacher's mean on (observation, privileged observation), then regressed on for --epochs "
+                         "(learner_hip.FusedDistill; --torch-learner: ppo.Distill).  The log carries distill_loss; --save writes a plain "
+                         "[160, 512] actor.  One rank")
+    ap.add_argument("--distill-beta", type=float, default=0.0,
+                    help="--distill: the share of robots that are stepped with the teacher's action instead of the student's (default 0)")
+    ap.add_argument("--distill-beta-iters", type=int, default=0, help="--distill: decay --distill-beta linearly to 0 over this many iterations (0: constant)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
     ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip (with --privileged-critic: see there)")
@@ -91,24 +105,35 @@ def main():
         torch.cuda.tunable.enable(True)
     if args.eval:
         return evaluate(args, torch, pol, ppo, VecQuadrupedEnv)
+    args.privileged_critic = args.privileged_critic or args.privileged_actor
+    if args.distill and (args.privileged_critic or args.torch_policy):
+        raise SystemExit("train.py: --distill trains a plain student with the fused rollout; not with --privileged-critic / --privileged-actor / --torch-policy")
+    privileged = args.privileged_critic or bool(args.distill)       # somebody reads env.privileged_obs
     rank, world, local = odist.init_from_env()
+    if args.distill and world > 1:
+        raise SystemExit("train.py: --distill runs on one rank")
     # ORR_BENCH_SINGLE_DEVICE=1 (+ ORR_DIST_BACKEND=gloo): several ranks rehearsed on a one-GPU box (tests), never a measurement
     dev = torch.device("cuda", 0 if os.environ.get("ORR_BENCH_SINGLE_DEVICE") else local)
     torch.cuda.set_device(dev)
     env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
                           device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
                           perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise,
-                          reward_terms=args.reward_terms, contact_outputs=args.contact_outputs or args.privileged_critic,
+                          reward_terms=args.reward_terms, contact_outputs=args.contact_outputs or privileged,
                           observation_noise_stdev=args.sensor_noise, push=args.push,
-                          push_outputs=args.privileged_critic and args.push is not None,
+                          push_outputs=privileged and args.push is not None,
                           **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     # same seed -> identical replicas.  (--model-file: the critic's width is the file's)
-    model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic else 0)
+    model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic else 0,
+                            actor_priv_dim=pol.PRIV_DIM if args.privileged_actor else 0)
     if bool(model.priv_dim) != args.privileged_critic:
         raise SystemExit("train.py: --model-file has a %s critic, --privileged-critic says otherwise" % ("privileged" if model.priv_dim else "plain"))
+    if bool(model.actor_priv_dim) != args.privileged_actor:
+        raise SystemExit("train.py: --model-file has a %s actor, --privileged-actor says otherwise" % ("privileged" if model.actor_priv_dim else "plain"))
     if not args.torch_policy:
         model.enable_fused()
+    if args.distill:
+        return distill(args, torch, pol, ppo, rollout, odist, env, model, dev)
     if args.torch_learner:
         learner = ppo.PPO(model, lr=args.lr, minibatch=args.minibatch)
     else:
@@ -184,6 +209,47 @@ def main():
         torch.distributed.destroy_process_group()
 
 
+def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
+    """--distill TEACHER.zip: DAgger on the device.  Each iteration collects a segment in which the student drives (all robots but the
+    share --distill-beta, which the teacher drives) and the teacher labels every visited state, then regresses the student's mean on the labels."""
+    teacher = ppo.ActorCritic(dev, params=pol.load_parameters(args.distill)).enable_fused()
+    B = args.num_robot * args.horizon
+    if args.torch_learner:
+        learner = ppo.Distill(student, lr=args.lr, minibatch=args.minibatch)
+    else:
+        from openroborl_amd import learner_hip
+        learner = learner_hip.FusedDistill(student, lr=args.lr, minibatch=learner_hip.FusedDistill.fit_minibatch(B, args.minibatch))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(args.seed * 1000)
+    collector = rollout.GraphRollout(env, student, args.horizon, teacher=teacher)
+    obs, priv = env.reset(), None
+    t0, samples, log = time.time(), 0, []
+    for it in range(args.iters):
+        beta = args.distill_beta * (max(0.0, 1.0 - it / float(args.distill_beta_iters)) if args.distill_beta_iters > 0 else 1.0)
+        driven = int(round(beta * args.num_robot))
+        collector.teacher_mask.zero_()
+        collector.teacher_mask[:driven] = 1
+        buf = collector.collect(obs, generator=gen, priv=priv)
+        obs, priv = buf["last_obs"], buf["last_priv"]
+        loss = learner.update(buf["obs"].reshape(B, -1), buf["teacher_mean"].reshape(B, 12), epochs=args.epochs, generator=gen)
+        samples += B
+        stats = odist.gather_env_episodes(env, args.horizon)
+        if it % 10 == 0 or it == args.iters - 1:
+            rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
+                   "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2), "episodes": stats.sums[0],
+                   "distill_loss": round(float(loss), 6), "teacher_driven": driven}
+            log.append(rec)
+            print(json.dumps(rec), flush=True)
+    if args.save:
+        pol.save_parameters_zip(args.save, student.state_dict())
+    if args.log:
+        with open(args.log, "w") as f:
+            json.dump(log, f, indent=1)
+    env.close()
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+
+
 def sensor_noise_arg(text):
     """--sensor-noise a,v,t,r,d -> five floats (validated by the env: openroborl_amd.env.sensor_noise_spec)."""
     parts = text.split(",")
@@ -232,8 +298,11 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     model = ppo.ActorCritic(dev, params=pol.load_parameters(args.eval))
     if not args.torch_policy:
         model.enable_fused()
+    if model.actor_priv_dim and not args.contact_outputs:
+        env.bind_contact_outputs(True)           # a teacher's actor reads the contact words of the row, as it did in training
     obs = env.reset()
-    # a zip with a privileged critic (--privileged-critic): the fused forward pass takes the privileged observation; only the actor's output is used here
+    # a zip with a privileged critic (--privileged-critic): the fused forward pass takes the privileged observation; only the actor's output is used
+    # here.  A teacher's zip (--privileged-actor): the row goes to the actor every step.  A student's zip (--distill) is a plain policy
     priv = env.privileged_obs(done=None) if model.priv_dim else None
     clip_ids = env.active_clip_ids()             # the clip each robot's episode plays
     alive = torch.ones(n, dtype=torch.bool, device=dev)
