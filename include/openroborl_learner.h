@@ -8,6 +8,7 @@
  * these launches:
  *   orr_ppo_head       loss terms, d loss / d mean, d loss / d value, bias gradients of the two output layers
  *   orr_distill_head   the loss head of policy distillation instead: squared error of the actor's mean against a teacher's, its gradient
+ *   orr_regress_head   the loss head of a history student's encoder: squared error of its 48 outputs against the privileged row, its gradient
  *   orr_head_backward  gradient through an output layer (fan-out 12 or 1) + ReLU mask + bias gradient of the layer below + the
  *                      output layer's weight gradient
  *   orr_colsum_finish  the column sums behind all bias gradients of a minibatch in one launch
@@ -54,6 +55,17 @@ int32_t orr_ppo_head(const float* mean, const float* value, const float* batch, 
  * m, the alignment and the workspace are orr_ppo_head's (orr_learner_workspace_floats(m, 16) floats suffice); the sums run in a fixed
  * order.  The rest of the student's backward pass is orr_head_backward, orr_relu_backward, orr_colsum_finish and orr_adam_step. */
 int32_t orr_distill_head(const float* mean, const float* target, int32_t m, float* g_mean, float* gb_mean, float* stats, float* workspace,
+                         void* stream);
+
+/* Regression loss head for a minibatch of m samples of c columns (host side: learner_hip.FusedDistillHistory, where pred is the history
+ * encoder's output and target the recorded privileged rows, c = 48).  loss = (1 / m) sum_i sum_j (pred[i][j] - target[i][j])^2, j < c.
+ *   pred [m][c], target [m][c]
+ *   g [m][c]       d loss / d pred = 2 (pred - target) / m
+ *   gb [c]         column sums of g = the bias gradient of the layer that produced pred
+ *   stats [1]      the loss
+ * c: a multiple of 4, at most 64.  pred, target, g and workspace 16-byte aligned; workspace: orr_learner_workspace_floats(m, 64) floats.
+ * The sums run in a fixed order.  The layers below are torch GEMMs, orr_relu_backward, orr_colsum_finish and orr_adam_step. */
+int32_t orr_regress_head(const float* pred, const float* target, int32_t m, int32_t c, float* g, float* gb, float* stats, float* workspace,
                          void* stream);
 
 /* g [m][c] (gradient w.r.t. a ReLU layer's output h [m][c]) becomes the gradient w.r.t. its pre-activation, in place: g *= (h > 0);

@@ -77,6 +77,44 @@ int32_t orr_policy_forward_priv(const orr_policy_net* net, const float* obs, con
 int32_t orr_policy_forward_teacher(const orr_policy_net* net, const float* obs, const float* priv, int32_t n, const float* noise,
                                    float std, float clip, float* action, float* raw, float* value, float* mean, void* stream);
 
+/* The sensor history a history student reads (orr_policy_forward_history): hist [n][16][32] float32, newest first.  A frame is the newest
+ * reading of each sensor history inside the 160-word observation followed by four zeros:
+ *   obs[0:4] (IMU roll, pitch, roll rate, pitch rate) | obs[12:24] (last action) | obs[48:60] (motor angles) | 0 0 0 0
+ * (the histories in obs are slot-major, newest first: sensors_push, csrc/orr_task.h).  16 x 32 = 512 words = 0.53 s at the 30.3 Hz control
+ * rate = 32 whole k-groups of the matrix-core operand.
+ *   next[i][0] = frame(obs[i]);   next[i][s] = done[i] ? frame(obs[i]) : prev[i][s - 1]     for s = 1..15
+ *   obs   [n][160]  the observation the new frame is taken from
+ *   done  [n] uint8 the flags of the step that produced obs (after an auto-reset obs is the new episode's first observation: that frame
+ *                   fills all 16 slots, as HistoricSensorWrapper.on_reset fills the 3-deep histories); NULL: everybody starts an episode
+ *   prev  [n][512]  the history before the step; may be NULL when done is NULL
+ *   next  [n][512]  the history after it.  prev == next (in place) is allowed: a thread stores only to words of a column it alone has
+ *                   loaded.  Ranges that overlap without being equal are refused
+ * Refused with a negative code, nothing launched or written: a null obs or next, a null prev with a done, n <= 0, prev / next not 16-byte
+ * aligned, obs not 4-byte aligned, partly overlapping prev and next. */
+#define ORR_HISTORY_STEPS 16
+#define ORR_HISTORY_FRAME 32
+#define ORR_HISTORY_DIM 512
+int32_t orr_history_push(const float* obs, const uint8_t* done, const float* prev, float* next, int32_t n, void* stream);
+
+/* A history student (RMA's adaptation module): an encoder estimates the privileged row from the sensor history and the TEACHER's net
+ * reads the estimate in the row's place, all in one launch.
+ *   z = relu(hist W0 + b0) W1 + b1        [n][48]
+ *   action, raw, value, mean = orr_policy_forward_teacher(net, obs, priv = z, ...)        bit for bit
+ *   net     a teacher's net: both layer 0s packed at k = 208
+ *   enc     the encoder: w0 the packed image of a 512 x 256 matrix, b0 [256], w1 of a 256 x 48 matrix, b1 [48]
+ *   hist    [n][512] the history (orr_history_push), 16-byte aligned
+ *   latent  [n][48] receives z; may be NULL
+ *   value == NULL skips the critic as in orr_policy_forward_teacher; neither it nor latent == NULL changes another output bit
+ * Refused like orr_policy_forward_teacher, and: a null enc, a null member of it, a null hist, packed encoder weights or a hist that are
+ * not 16-byte aligned, encoder biases or a latent that are not 4-byte aligned. */
+typedef struct orr_history_encoder {
+  const float* w0; const float* b0;   /* 512 x 256, packed by orr_policy_pack; bias 256 */
+  const float* w1; const float* b1;   /* 256 x 48,  packed;                    bias 48  */
+} orr_history_encoder;
+int32_t orr_policy_forward_history(const orr_policy_net* net, const orr_history_encoder* enc, const float* obs, const float* hist, int32_t n,
+                                   const float* noise, float std, float clip, float* action, float* raw, float* value, float* mean,
+                                   float* latent, void* stream);
+
 /* Per-robot GAE(lambda) over a [T][N] rollout segment + per-robot advantage standardisation, one launch
  * (reference: add_vtarg_and_adv, agents/ppo_imitation.py:68-93, and the per-robot normalisation :329-338; device
  * layout and the deliberate use of each robot's own done flags: openroborl_amd/rollout.py).

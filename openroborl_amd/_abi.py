@@ -178,6 +178,17 @@ class OrrPolicyNet(C.Structure):
                                             "w0_vf", "b0_vf", "w1_vf", "b1_vf", "w2_vf", "b2_vf")]
 
 
+class OrrHistoryEncoder(C.Structure):
+    """include/openroborl_policy.h: orr_history_encoder (packed weights + biases of a history student's encoder, 512 -> 256 -> 48)."""
+    _fields_ = [(n, C.c_void_p) for n in ("w0", "b0", "w1", "b1")]
+
+
+# include/openroborl_policy.h: ORR_HISTORY_STEPS, ORR_HISTORY_FRAME, ORR_HISTORY_DIM (orr_history_push, orr_policy_forward_history)
+HISTORY_STEPS = 16
+HISTORY_FRAME = 32
+HISTORY_DIM = 512
+
+
 class OrrColsumJob(C.Structure):
     """include/openroborl_learner.h: orr_colsum_job."""
     _fields_ = [("partials", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]
@@ -191,3 +202,14 @@ POLICY_FORWARD_TEACHER_ARGS = [C.POINTER(OrrPolicyNet), C.c_void_p, C.c_void_p, 
 # include/openroborl_learner.h: int32_t orr_distill_head(const float* mean [m][12], const float* target [m][12], int32_t m, float* g_mean [m][12],
 #   float* gb_mean [12], float* stats [1], float* workspace, void* stream)
 DISTILL_HEAD_ARGS = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_policy.h: int32_t orr_history_push(const float* obs [n][160], const uint8_t* done [n] | NULL, const float* prev [n][512] | NULL,
+#   float* next [n][512], int32_t n, void* stream)
+HISTORY_PUSH_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+# include/openroborl_policy.h: int32_t orr_policy_forward_history(const orr_policy_net* net, const orr_history_encoder* enc, const float* obs,
+#   const float* hist [n][512], int32_t n, const float* noise, float std, float clip, float* action, float* raw, float* value | NULL, float* mean,
+#   float* latent [n][48] | NULL, void* stream)
+POLICY_FORWARD_HISTORY_ARGS = [C.POINTER(OrrPolicyNet), C.POINTER(OrrHistoryEncoder), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_regress_head(const float* pred [m][c], const float* target [m][c], int32_t m, int32_t c, float* g [m][c],
+#   float* gb [c], float* stats [1], float* workspace, void* stream)
+REGRESS_HEAD_ARGS = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -143,6 +143,44 @@ __global__ __launch_bounds__(64) void distill_head_finish_kernel(const float* __
   }
 }
 
+// ---- regression loss head (orr_regress_head): squared error of c <= 64 columns.  16 threads per row (a thread owns four adjacent columns: one
+// 16-byte access per tensor and row), 16 rows per pass, kRegRows rows per workgroup; partials [block][c] of the column sums and [block] of the
+// loss, added up by colsum_finish_kernel in its fixed order.
+constexpr int kRegRows = 64;
+constexpr int kRegMaxCols = 64;
+__global__ __launch_bounds__(kThreads) void regress_head_kernel(const float* __restrict__ pred, const float* __restrict__ target, int M, int C, float inv_m,
+                                                                float* __restrict__ g, float* __restrict__ partials, float* __restrict__ loss_part) {
+  __shared__ f4 red[kThreads];
+  __shared__ float sq_red[kThreads / 64];
+  const int q = threadIdx.x & 15, rsub = threadIdx.x >> 4;
+  const int row0 = blockIdx.x * kRegRows;
+  const float scale = 2.0f * inv_m;
+  f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+  float sq = 0.0f;
+  if (4 * q < C) {
+    for (int r = rsub; r < kRegRows; r += kThreads / 16) {
+      const int i = row0 + r;
+      if (i >= M) break;
+      const size_t o = (size_t)i * C + 4 * q;
+      const f4 d = *reinterpret_cast<const f4*>(pred + o) - *reinterpret_cast<const f4*>(target + o);
+      const f4 gv = d * scale;
+      *reinterpret_cast<f4*>(g + o) = gv;
+      acc += gv;
+      sq += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+    }
+  }
+  red[threadIdx.x] = acc;
+  const float s = wave_sum(sq);
+  if ((threadIdx.x & 63) == 0) sq_red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (rsub == 0 && 4 * q < C) {
+    f4 t = red[q];
+    for (int k = 1; k < kThreads / 16; k++) t += red[16 * k + q];
+    *reinterpret_cast<f4*>(partials + (size_t)blockIdx.x * C + 4 * q) = t;
+  }
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = ((sq_red[0] + sq_red[1]) + (sq_red[2] + sq_red[3])) * inv_m;
+}
+
 // ---- ReLU mask (+ the gradient through an output layer of fan-out K) + per-block column sums ------------------------------
 // A workgroup owns kRowsPerBlock rows and all c columns; a thread owns four adjacent columns (one 16-byte access per tensor and
 // row) of every (256 / (c/4))-th row.  K = 0: g holds the incoming gradient and is masked in place.  K > 0 (the layer below an
@@ -366,6 +404,24 @@ int32_t orr_distill_head(const float* mean, const float* target, int32_t m, floa
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_distill_head: launch", e);
   return 0;
+}
+
+int32_t orr_regress_head(const float* pred, const float* target, int32_t m, int32_t c, float* g, float* gb, float* stats, float* workspace,
+                         void* stream) {
+  if (!pred || !target || !g || !gb || !stats || !workspace || m <= 0) return orr_fail(-1, "orr_regress_head: bad argument", hipSuccess);
+  if (c < 4 || (c % 4) != 0 || c > kRegMaxCols) return orr_fail(-1, "orr_regress_head: c must be a multiple of 4, at most 64", hipSuccess);
+  if (!aligned16(pred) || !aligned16(target) || !aligned16(g) || !aligned16(workspace))
+    return orr_fail(-1, "orr_regress_head: buffers must be 16-byte aligned", hipSuccess);
+  const int nblk = (m + kRegRows - 1) / kRegRows;
+  hipStream_t st = (hipStream_t)stream;
+  float* loss_part = workspace + (size_t)nblk * c;                // [nblk][c] column sums, then [nblk] shares of the loss
+  hipLaunchKernelGGL(regress_head_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, st, pred, target, (int)m, (int)c, 1.0f / (float)m, g, workspace, loss_part);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_regress_head: launch", e);
+  FinishJobs J{};
+  J.partials[0] = workspace; J.out[0] = gb; J.nblk[0] = nblk; J.cols[0] = c;
+  J.partials[1] = loss_part; J.out[1] = stats; J.nblk[1] = nblk; J.cols[1] = 1;
+  return launch_finish(J, 2, st, "orr_regress_head: launch");
 }
 
 int32_t orr_relu_backward(float* g, const float* h, int32_t m, int32_t c, float* gb, float* workspace, void* stream) {

@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/openroborl_policy.h"
 
 int orr_fail(int code, const char* msg, hipError_t e);  // orr_kernels.hip
@@ -28,6 +30,10 @@ constexpr int kRows = 16;                       // robots per workgroup
 constexpr int kPriv = ORR_POLICY_PRIV_DIM;      // privileged columns of the critic's input (orr_policy_forward_priv)
 constexpr int kH0Stride = 2 * kH0 + 1;          // actor | critic hidden 0 (odd, like the observation tile's stride: forward_kernel)
 constexpr int kH1Stride = 2 * kH1 + 1;          // actor | critic hidden 1
+constexpr int kHist = ORR_HISTORY_DIM;          // the history encoder (orr_policy_forward_history): 512 -> 256 -> 48
+constexpr int kEncH = 256;
+constexpr int kHistStride = kHist + 1;          // the 16 x 512 history tile lives where hidden 0 will, the encoder's hidden layer where hidden 1 will
+static_assert(kHistStride <= kH0Stride && kEncH + 1 <= kH1Stride && kHist % 64 == 0 && kEncH % 64 == 0, "the encoder's tiles fit the hidden layers' LDS");
 
 __global__ void pack_kernel(const float* __restrict__ w, int K, int N, float* __restrict__ out, long long total) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -51,6 +57,12 @@ struct Params {
   float std, clip;
   const float* priv;   // forward_kernel<kObs + kPriv, ..> only; LAST: the fields above keep their offsets in the plain kernel's arguments
 };
+// The history kernel's own arguments (forward_kernel<.., .., true>): Params stays what the three older kernels were compiled against.
+struct HistParams : Params {
+  orr_history_encoder enc;
+  const float* hist;
+  float* latent;
+};
 
 // acc[t] += A(16 x 16 k-group kg, from LDS) * B(tile t, k-group kg): four k-steps of v_mfma_f32_16x16x4_f32 per tile.
 // A fragment of k-step j: lane l holds A[l & 15][16 kg + 4 j + (l >> 4)];  B fragment: element j of the packed float4.
@@ -68,7 +80,7 @@ __device__ __forceinline__ void mma_group(f32x4 (&acc)[TILES], const float (&a)[
 // k-group are read from LDS before the MFMAs of the current one.  K / 16 must be a multiple of DEPTH.
 // KGS, G0: the call covers k-groups [G0, G0 + K / 16) of a packed matrix of KGS k-groups, `act` pointing at column 16 G0 of the A operand
 // (default: all of it) - a matrix whose k-groups are no multiple of the depth is done as two calls.
-// UNIT: names the calling kernel's family (forward_kernel passes its KP) and is used by nothing: kernels of different families then share
+// UNIT: names the calling kernel's family (forward_kernel passes its KP, the history kernel KP + 1) and is used by nothing: kernels of different families then share
 // no instantiation of this function.  Before it is inlined the optimiser folds arguments that all call sites of an instantiation agree
 // on (the LDS tile's address among them) into the function; a third kernel calling the privileged kernel's instantiations took that away
 // from it and changed its instructions (profiles/teacher_policy.txt).
@@ -139,8 +151,14 @@ __device__ __forceinline__ void store_relu(const f32x4 (&acc)[TILES], const floa
 // tile too, against its own (kObs + kPriv) x 512 matrix, by the critic's k-groups (twelve at depth 2 + one).  That instantiation also takes
 // value == NULL as "no critic": the test is on a kernel argument, i.e. uniform over the workgroup, it guards the critic's layers only and
 // every barrier is outside it; the actor's instructions and inputs are the same either way, and so are action, raw and mean.
-template <int KV, int KP = kObs>
-__global__ __launch_bounds__(256) void forward_kernel(Params P) {
+// HIST (orr_policy_forward_history, with KV = KP = kObs + kPriv): the privileged columns of the tile are not read but computed, by an encoder
+// over the robot's sensor history, z = relu(hist W0 + b0) W1 + b1.  The history tile and the encoder's hidden layer use the LDS of the hidden
+// layers before those are written; everything behind the tile is the teacher kernel's code on the same k-groups, hence its bits.  The kernel
+// takes HistParams and calls layer<> with a UNIT of its own (KP + 1), so the three older instantiations keep their arguments and their code.
+template <int KV, int KP = kObs, bool HIST = false>
+__global__ __launch_bounds__(256) void forward_kernel(typename std::conditional<HIST, HistParams, Params>::type P) {
+  constexpr int UNIT = HIST ? KP + 1 : KP;
+  static_assert(!HIST || (KV == kObs + kPriv && KP == KV), "the encoder fills the teacher's privileged columns");
   constexpr int kObsStride = KV + 1;            // odd strides: the 16 rows of an A fragment fall into distinct LDS banks
   static_assert(KV >= kObs && KV % 16 == 0 && (kObsStride & 1) == 1, "whole k-groups, odd stride");
   static_assert(KP == kObs || KP == KV, "the actor reads the observation or the critic's whole tile");
@@ -155,7 +173,36 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
     const int r = i / kObs, c = i - r * kObs;
     s_obs[r * kObsStride + c] = (row0 + r) < P.n ? P.obs[(size_t)(row0 + r) * kObs + c] : 0.0f;
   }
-  if constexpr (KV > kObs) {   // privileged columns behind it
+  if constexpr (HIST) {        // privileged columns behind it: the encoder's output
+    const f32x4* h4 = reinterpret_cast<const f32x4*>(P.hist);
+    for (int i = tid; i < kRows * (kHist / 4); i += 256) {
+      const int r = i / (kHist / 4), c4 = i - r * (kHist / 4);
+      const f32x4 v = (row0 + r) < P.n ? h4[(size_t)(row0 + r) * (kHist / 4) + c4] : f32x4{0, 0, 0, 0};
+      float* d = s_h0 + r * kHistStride + 4 * c4;
+      d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+    }
+    __syncthreads();
+    {   // encoder layer 0: 512 -> 256; this wave: column tiles [4 wave, 4 wave + 4), the shape of layer 1 below
+      f32x4 acc[4];
+#pragma unroll
+      for (int t = 0; t < 4; t++) acc[t] = f32x4{0, 0, 0, 0};
+      layer<UNIT, 4, kHist, 4>(acc, P.enc.w0, 4 * wave, s_h0, kHistStride, lane);
+      store_relu<4>(acc, P.enc.b0, 4 * wave, s_h1, kH1Stride, lane);
+    }
+    __syncthreads();
+    if (wave < kPriv / 16) {   // encoder layer 1: 256 -> 48, one column tile each on waves 0..2; no ReLU
+      f32x4 acc[1] = {f32x4{0, 0, 0, 0}};
+      layer<UNIT, 1, kEncH, 4>(acc, P.enc.w1, wave, s_h1, kH1Stride, lane);
+      const int c = 16 * wave + (lane & 15), r0 = 4 * (lane >> 4);
+      const float b = P.enc.b1[c];
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const float z = acc[0][r] + b;
+        s_obs[(r0 + r) * kObsStride + kObs + c] = z;
+        if (P.latent && row0 + r0 + r < P.n) P.latent[(size_t)(row0 + r0 + r) * kPriv + c] = z;
+      }
+    }
+  } else if constexpr (KV > kObs) {   // privileged columns behind it
     constexpr int kP = KV - kObs;
     for (int i = tid; i < kRows * kP; i += 256) {
       const int r = i / kP, c = i - r * kP;
@@ -169,24 +216,24 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
 #pragma unroll
     for (int t = 0; t < 8; t++) acc[t] = f32x4{0, 0, 0, 0};
     if constexpr (KP == kObs) {
-      layer<KP, 8, kObs, 2>(acc, P.net.w0_pi, 8 * wave, s_obs, kObsStride, lane);
+      layer<UNIT, 8, kObs, 2>(acc, P.net.w0_pi, 8 * wave, s_obs, kObsStride, lane);
     } else {
       constexpr int kMain = KP / 32 * 32;
-      layer<KP, 8, kMain, 2, KP / 16, 0>(acc, P.net.w0_pi, 8 * wave, s_obs, kObsStride, lane);
-      layer<KP, 8, KP - kMain, 1, KP / 16, kMain / 16>(acc, P.net.w0_pi, 8 * wave, s_obs + kMain, kObsStride, lane);
+      layer<UNIT, 8, kMain, 2, KP / 16, 0>(acc, P.net.w0_pi, 8 * wave, s_obs, kObsStride, lane);
+      layer<UNIT, 8, KP - kMain, 1, KP / 16, kMain / 16>(acc, P.net.w0_pi, 8 * wave, s_obs + kMain, kObsStride, lane);
     }
     store_relu<8>(acc, P.net.b0_pi, 8 * wave, s_h0, kH0Stride, lane);
     if (KP == kObs || P.value) {       // KP == kObs: a constant, no test in those two kernels
 #pragma unroll
       for (int t = 0; t < 8; t++) acc[t] = f32x4{0, 0, 0, 0};
       if constexpr (KV == kObs) {
-        layer<KP, 8, kObs, 2>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+        layer<UNIT, 8, kObs, 2>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
       } else if constexpr (ORR_POLICY_PRIV_SPLIT) {
         constexpr int kMain = KV / 32 * 32;       // the k-groups that depth 2 divides
-        layer<KP, 8, kMain, 2, KV / 16, 0>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
-        layer<KP, 8, KV - kMain, 1, KV / 16, kMain / 16>(acc, P.net.w0_vf, 8 * wave, s_obs + kMain, kObsStride, lane);
+        layer<UNIT, 8, kMain, 2, KV / 16, 0>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+        layer<UNIT, 8, KV - kMain, 1, KV / 16, kMain / 16>(acc, P.net.w0_vf, 8 * wave, s_obs + kMain, kObsStride, lane);
       } else {
-        layer<KP, 8, KV, 1>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+        layer<UNIT, 8, KV, 1>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
       }
       store_relu<8>(acc, P.net.b0_vf, 8 * wave, s_h0 + kH0, kH0Stride, lane);
     }
@@ -197,12 +244,12 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) acc[t] = f32x4{0, 0, 0, 0};
-    layer<KP, 4, kH0, 4>(acc, P.net.w1_pi, 4 * wave, s_h0, kH0Stride, lane);
+    layer<UNIT, 4, kH0, 4>(acc, P.net.w1_pi, 4 * wave, s_h0, kH0Stride, lane);
     store_relu<4>(acc, P.net.b1_pi, 4 * wave, s_h1, kH1Stride, lane);
     if (KP == kObs || P.value) {
 #pragma unroll
       for (int t = 0; t < 4; t++) acc[t] = f32x4{0, 0, 0, 0};
-      layer<KP, 4, kH0, 4>(acc, P.net.w1_vf, 4 * wave, s_h0 + kH0, kH0Stride, lane);
+      layer<UNIT, 4, kH0, 4>(acc, P.net.w1_vf, 4 * wave, s_h0 + kH0, kH0Stride, lane);
       store_relu<4>(acc, P.net.b1_vf, 4 * wave, s_h1 + kH1, kH1Stride, lane);
     }
   }
@@ -212,7 +259,7 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
   f32x4 acc[1] = {f32x4{0, 0, 0, 0}};
   const int col = lane & 15, r0 = 4 * (lane >> 4);
   if (wave == 0) {
-    layer<KP, 1, kH1, 4>(acc, P.net.w2_pi, 0, s_h1, kH1Stride, lane);
+    layer<UNIT, 1, kH1, 4>(acc, P.net.w2_pi, 0, s_h1, kH1Stride, lane);
     if (col < kAct) {
       const float b = P.net.b2_pi[col];
 #pragma unroll
@@ -229,7 +276,7 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
       }
     }
   } else if (KP == kObs || P.value) {
-    layer<KP, 1, kH1, 4>(acc, P.net.w2_vf, 0, s_h1 + kH1, kH1Stride, lane);
+    layer<UNIT, 1, kH1, 4>(acc, P.net.w2_vf, 0, s_h1 + kH1, kH1Stride, lane);
     if (col == 0 && P.value) {
       const float b = P.net.b2_vf[0];
 #pragma unroll
@@ -239,6 +286,37 @@ __global__ __launch_bounds__(256) void forward_kernel(Params P) {
       }
     }
   }
+}
+
+// The sensor history's shift (orr_history_push).  A thread owns ONE 16-byte quad of the frame across all 16 slots of one robot: it loads its
+// 15 quads prev[i][0..14][q] into registers, then stores next[i][1..15][q] and the new frame's quad - only to addresses of a column that it
+// alone has loaded, so prev == next needs no barrier (which would not order one wave's loads against another's stores anyway).  prev and next
+// carry no __restrict__ for that reason.  8 threads per robot, 32 robots per workgroup.
+constexpr int kHistSteps = ORR_HISTORY_STEPS, kHistQuads = ORR_HISTORY_FRAME / 4;
+static_assert(kHistSteps * kHistQuads * 4 == kHist && kHistQuads == 8, "16 slots of 8 quads");
+__global__ __launch_bounds__(256) void history_push_kernel(const float* __restrict__ obs, const uint8_t* __restrict__ done, const float* prev,
+                                                           float* next, int n) {
+  const int i = blockIdx.x * (256 / kHistQuads) + threadIdx.x / kHistQuads, q = threadIdx.x % kHistQuads;
+  if (i >= n) return;
+  // quad 0: the IMU's newest reading obs[0:4]; 1..3: the last action obs[12:24]; 4..6: the motor angles obs[48:60]; 7: the pad
+  f32x4 frame = {0, 0, 0, 0};
+  if (q < 7) {
+    const float* o = obs + (size_t)i * kObs + (q == 0 ? 0 : (q < 4 ? 12 + 4 * (q - 1) : 48 + 4 * (q - 4)));
+    frame = f32x4{o[0], o[1], o[2], o[3]};
+  }
+  const bool fresh = done ? done[i] != 0 : true;
+  const f32x4* p4 = reinterpret_cast<const f32x4*>(prev) + (size_t)i * (kHistSteps * kHistQuads) + q;
+  f32x4* n4 = reinterpret_cast<f32x4*>(next) + (size_t)i * (kHistSteps * kHistQuads) + q;
+  f32x4 h[kHistSteps - 1];
+#pragma unroll
+  for (int s = 0; s < kHistSteps - 1; s++) h[s] = frame;
+  if (!fresh) {
+#pragma unroll
+    for (int s = 0; s < kHistSteps - 1; s++) h[s] = p4[s * kHistQuads];
+  }
+  n4[0] = frame;
+#pragma unroll
+  for (int s = 0; s < kHistSteps - 1; s++) n4[(s + 1) * kHistQuads] = h[s];
 }
 
 // One thread per robot: backward recursion over the segment, then mean / variance / standardisation of its own T values.
@@ -345,6 +423,49 @@ int32_t orr_policy_forward_teacher(const orr_policy_net* net, const float* obs, 
   hipLaunchKernelGGL((forward_kernel<kObs + kPriv, kObs + kPriv>), dim3((unsigned)((n + kRows - 1) / kRows)), dim3(256), 0, (hipStream_t)stream, P);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_policy_forward_teacher: launch", e);
+  return 0;
+}
+
+int32_t orr_policy_forward_history(const orr_policy_net* net, const orr_history_encoder* enc, const float* obs, const float* hist, int32_t n,
+                                   const float* noise, float std, float clip, float* action, float* raw, float* value, float* mean,
+                                   float* latent, void* stream) {
+  if (!net || !enc || !obs || !hist || !action || n <= 0) return orr_fail(-1, "orr_policy_forward_history: bad argument", hipSuccess);
+  const float* const* p = reinterpret_cast<const float* const*>(net);
+  for (int i = 0; i < 12; i++) {
+    if (!p[i]) return orr_fail(-1, "orr_policy_forward_history: orr_policy_net has a null pointer", hipSuccess);
+    if (reinterpret_cast<uintptr_t>(p[i]) & (i % 2 == 0 ? 15 : 3))     // packed weights are read 16 bytes per lane
+      return orr_fail(-1, "orr_policy_forward_history: packed weights must be 16-byte aligned, biases 4-byte aligned", hipSuccess);
+  }
+  const float* const* q = reinterpret_cast<const float* const*>(enc);
+  for (int i = 0; i < 4; i++) {
+    if (!q[i]) return orr_fail(-1, "orr_policy_forward_history: orr_history_encoder has a null pointer", hipSuccess);
+    if (reinterpret_cast<uintptr_t>(q[i]) & (i % 2 == 0 ? 15 : 3))
+      return orr_fail(-1, "orr_policy_forward_history: packed weights must be 16-byte aligned, biases 4-byte aligned", hipSuccess);
+  }
+  if (reinterpret_cast<uintptr_t>(hist) & 15) return orr_fail(-1, "orr_policy_forward_history: hist must be 16-byte aligned", hipSuccess);
+  for (const void* b : {(const void*)obs, (const void*)noise, (const void*)action, (const void*)raw, (const void*)value, (const void*)mean, (const void*)latent})
+    if (reinterpret_cast<uintptr_t>(b) & 3) return orr_fail(-1, "orr_policy_forward_history: buffers must be 4-byte aligned", hipSuccess);
+  HistParams P;
+  P.net = *net; P.obs = obs; P.noise = noise; P.action = action; P.raw = raw; P.value = value; P.mean = mean;
+  P.n = n; P.std = std; P.clip = clip; P.priv = nullptr;
+  P.enc = *enc; P.hist = hist; P.latent = latent;
+  hipLaunchKernelGGL((forward_kernel<kObs + kPriv, kObs + kPriv, true>), dim3((unsigned)((n + kRows - 1) / kRows)), dim3(256), 0, (hipStream_t)stream, P);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_policy_forward_history: launch", e);
+  return 0;
+}
+
+int32_t orr_history_push(const float* obs, const uint8_t* done, const float* prev, float* next, int32_t n, void* stream) {
+  if (!obs || !next || n <= 0 || (done && !prev)) return orr_fail(-1, "orr_history_push: bad argument", hipSuccess);
+  if ((reinterpret_cast<uintptr_t>(prev) & 15) || (reinterpret_cast<uintptr_t>(next) & 15) || (reinterpret_cast<uintptr_t>(obs) & 3))
+    return orr_fail(-1, "orr_history_push: prev and next must be 16-byte aligned, obs 4-byte aligned", hipSuccess);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(prev), b = reinterpret_cast<uintptr_t>(next), bytes = (uintptr_t)n * kHist * sizeof(float);
+  if (prev && a != b && a < b + bytes && b < a + bytes)
+    return orr_fail(-1, "orr_history_push: prev and next overlap without being equal", hipSuccess);
+  hipLaunchKernelGGL(history_push_kernel, dim3((unsigned)((n + 256 / kHistQuads - 1) / (256 / kHistQuads))), dim3(256), 0, (hipStream_t)stream, obs,
+                     done, prev, next, (int)n);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_history_push: launch", e);
   return 0;
 }
 

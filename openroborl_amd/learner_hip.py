@@ -27,6 +27,8 @@ NETS = ("pi", "vf")
 
 
 class FusedPPO(object):
+    _takes_history = False        # a history student (ppo.ActorCritic(history=16)) is trained by FusedDistillHistory only
+
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
                  mpi_adam_epsilon=False, use_graph=True):
         import torch
@@ -35,6 +37,9 @@ class FusedPPO(object):
         self.dev = model.device
         if self.dev.type != "cuda":
             raise RuntimeError("FusedPPO needs a GPU device (the torch reference is ppo.PPO)")
+        if bool(getattr(model, "history", 0)) != self._takes_history:
+            raise ValueError("%s: %s" % (type(self).__name__, "the student needs a history encoder (ActorCritic(history=16))" if self._takes_history
+                                         else "a history student is trained by FusedDistillHistory only"))
         self.L = _lib.load()
         self.clip, self.lr, self.eps, self.vf_coef = float(clip_param), float(lr), float(adam_eps), float(vf_coef)
         self.b1, self.b2 = float(betas[0]), float(betas[1])
@@ -416,3 +421,87 @@ class FusedDistill(FusedPPO):
 
     def check_synced(self):
         pass
+
+
+class FusedDistillHistory(FusedDistill):
+    """The learner of a history student's encoder on the device (the torch reference is ppo.DistillHistory): encode(hist) is regressed on the
+    recorded privileged rows, loss = mean over the samples of sum_j (z_j - priv_j)^2 (orr_regress_head).  FusedDistill's machinery with the
+    encoder alone: only model/enc_* move into the flat buffer and take Adam steps - the actor and the critic, the teacher's, stay where and what
+    they are -, two forward GEMMs, the loss head, the two products behind it, orr_relu_backward at c = 256, the layer-0 weight gradient
+    (split for minibatches of 4096 and more) and one orr_colsum_finish per minibatch; an epoch replays as one hipGraph.  One rank."""
+    _takes_history = True
+
+    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True):
+        FusedPPO.__init__(self, student, lr=lr, adam_eps=adam_eps, minibatch=minibatch, betas=betas, use_graph=use_graph)
+
+    @staticmethod
+    def _trained(model):
+        return sorted(k for k in model.p if k.startswith("model/enc_"))
+
+    def _plan(self, B, M):
+        key = (B, M)
+        if key in self._plans:
+            return self._plans[key]
+        t = self.torch
+        f = lambda *shape: t.empty(shape, dtype=t.float32, device=self.dev)   # noqa: E731
+        split = M >= 4096 and M % 16 == 0
+        rows = int(self.L.orr_learner_partial_rows(M))
+        D, H, Z = _abi.HISTORY_DIM, 256, _abi.POLICY_PRIV_DIM
+        P = {"B": B, "M": M, "nmb": B // M, "hist": f(B, D), "target": f(B, Z), "perm": t.empty(B, dtype=t.int64, device=self.dev),
+             "x": f(M, D), "tgt": f(M, Z), "h": f(M, H), "z": f(M, Z), "g_z": f(M, Z), "g_h": f(M, H),
+             "stats": t.zeros(B // M, 1, dtype=t.float32, device=self.dev), "ws": f(int(self.L.orr_learner_workspace_floats(M, 64))),
+             "ws1": f(rows * H), "part0": f(16, D, H) if split else None, "graphs": None}
+        jobs = (_abi.OrrColsumJob * 2)()
+        jobs[0] = _abi.OrrColsumJob(P["ws1"].data_ptr(), self.g["model/enc_fc0/b:0"].data_ptr(), rows, H)
+        if split:
+            jobs[1] = _abi.OrrColsumJob(P["part0"].data_ptr(), self.g["model/enc_fc0/w:0"].data_ptr(), 16, D * H)
+        P["jobs"], P["n_jobs"] = jobs, 2 if split else 1
+        self._plans[key] = P
+        return P
+
+    def _minibatch(self, P, s):
+        """Gather, the encoder's forward pass, loss head and backward of minibatch s of the current permutation; gradients land in flat_g."""
+        t, L, M, w, g = self.torch, self.L, P["M"], self.w, self.g
+        st = self._stream()
+        idx = P["perm"][s * M:(s + 1) * M]
+        t.index_select(P["hist"], 0, idx, out=P["x"])
+        t.index_select(P["target"], 0, idx, out=P["tgt"])
+        t._addmm_activation(w["model/enc_fc0/b:0"], P["x"], w["model/enc_fc0/w:0"], out=P["h"])
+        t.addmm(w["model/enc_fc1/b:0"], P["h"], w["model/enc_fc1/w:0"], out=P["z"])
+        _lib.check(L.orr_regress_head(P["z"].data_ptr(), P["tgt"].data_ptr(), M, _abi.POLICY_PRIV_DIM, P["g_z"].data_ptr(),
+                                      g["model/enc_fc1/b:0"].data_ptr(), P["stats"][s].data_ptr(), P["ws"].data_ptr(), st), L)
+        t.mm(P["h"].t(), P["g_z"], out=g["model/enc_fc1/w:0"])
+        t.mm(P["g_z"], w["model/enc_fc1/w:0"].t(), out=P["g_h"])
+        _lib.check(L.orr_relu_backward(P["g_h"].data_ptr(), P["h"].data_ptr(), M, 256, None, P["ws1"].data_ptr(), st), L)
+        self._wgrad(P["x"], P["g_h"], P["part0"], g["model/enc_fc0/w:0"])
+        _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
+
+    def update(self, hist, target_priv, epochs=1, generator=None):
+        """hist [B,512], target_priv [B,48] (env.privileged_obs on the same states); returns the mean loss over the minibatches, like
+        ppo.DistillHistory.update."""
+        t = self.torch
+        B = int(hist.shape[0])
+        if tuple(hist.shape) != (B, _abi.HISTORY_DIM) or tuple(target_priv.shape) != (B, _abi.POLICY_PRIV_DIM):
+            raise ValueError("FusedDistillHistory: hist must have shape (B, %d) and target_priv (B, %d)" % (_abi.HISTORY_DIM, _abi.POLICY_PRIV_DIM))
+        M = min(self.minibatch, B)
+        if B % M:
+            raise ValueError("FusedDistillHistory: the number of samples (%d) must be a multiple of the minibatch size (%d); "
+                             "FusedPPO.fit_minibatch(%d, %d) = %d is the largest size that divides it" % (B, M, B, M, self.fit_minibatch(B, M)))
+        with t.no_grad():
+            P = self._plan(B, M)
+            P["hist"].copy_(hist)
+            P["target"].copy_(target_priv)
+            if self.use_graph and (P["graphs"] is None or P.get("graph_key") != self._graph_key(False)):
+                self._capture(P, False)
+                P["graph_key"] = self._graph_key(False)
+            total = t.zeros(1, dtype=t.float32, device=self.dev)
+            for _ in range(epochs):
+                P["perm"].copy_(t.randperm(B, device=self.dev, generator=generator))
+                if self.use_graph:
+                    P["graphs"][0].replay()
+                else:
+                    self._epoch_eager(P, 1, False)
+                total += P["stats"].sum(dim=0)
+        if hasattr(self.model, "mark_updated"):
+            self.model.mark_updated()
+        return float(total.item() / float(epochs * P["nmb"]))

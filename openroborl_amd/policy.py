@@ -45,6 +45,11 @@ SB_PARAMETER_LIST = (("model/pi_fc0/w:0", (160, 512)), ("model/pi_fc0/b:0", (512
                      ("model/q/b:0", (12,)))
 
 
+# a history student's encoder (ppo.ActorCritic(history=16)); no reference counterpart
+ENC_PARAMETER_LIST = (("model/enc_fc0/w:0", (512, 256)), ("model/enc_fc0/b:0", (256,)), ("model/enc_fc1/w:0", (256, PRIV_DIM)),
+                      ("model/enc_fc1/b:0", (PRIV_DIM,)))
+
+
 def save_parameters_zip(path, params, data=None):
     """Write weights in the stable-baselines zip layout (`data` JSON, `parameter_list` JSON, `parameters` npz;
     stable_baselines/common/base_class.py:552-590) so that the reference's `agent.load_parameters(model_file)`
@@ -68,6 +73,13 @@ def save_parameters_zip(path, params, data=None):
             raise ValueError("missing variable %s" % name)
         out[name] = v
     names = [n for n, _ in SB_PARAMETER_LIST]
+    for name, shape in ENC_PARAMETER_LIST:       # a history student (ppo.ActorCritic(history=16)): behind the reference's list, loadable here only
+        if ENC_PARAMETER_LIST[0][0] in params:
+            v = np.asarray(params[name], dtype=np.float32)
+            if v.shape != shape:
+                raise ValueError("%s has shape %s, a history encoder has %s" % (name, v.shape, shape))
+            out[name] = v
+            names.append(name)
     buf = io.BytesIO()
     np.savez(buf, **out)
     with zipfile.ZipFile(path, "w") as z:

@@ -12,6 +12,9 @@ from . import _abi, _lib
 KEYS = (("w0_pi", "model/pi_fc0/w:0"), ("b0_pi", "model/pi_fc0/b:0"), ("w1_pi", "model/pi_fc1/w:0"), ("b1_pi", "model/pi_fc1/b:0"),
         ("w2_pi", "model/pi/w:0"), ("b2_pi", "model/pi/b:0"), ("w0_vf", "model/vf_fc0/w:0"), ("b0_vf", "model/vf_fc0/b:0"),
         ("w1_vf", "model/vf_fc1/w:0"), ("b1_vf", "model/vf_fc1/b:0"), ("w2_vf", "model/vf/w:0"), ("b2_vf", "model/vf/b:0"))
+# a history student's encoder (orr_policy_forward_history), packed when the parameter dict holds it
+ENC_KEYS = (("w0", "model/enc_fc0/w:0"), ("b0", "model/enc_fc0/b:0"), ("w1", "model/enc_fc1/w:0"), ("b1", "model/enc_fc1/b:0"))
+ENC_SHAPES = {"w0": (_abi.HISTORY_DIM, 256), "w1": (256, _abi.POLICY_PRIV_DIM)}
 SHAPES = {"w0_pi": (160, 512), "w0_vf": (160, 512), "w1_pi": (512, 256), "w1_vf": (512, 256), "w2_pi": (256, 12), "w2_vf": (256, 1)}
 
 
@@ -51,6 +54,17 @@ class FusedActorCritic(object):
                 self.packed[field] = torch.empty(size, dtype=torch.float32, device=self.device)
         if self.actor_priv_dim and not self.priv_dim:
             raise ValueError("a privileged actor (model/pi_fc0/w:0 with %d rows) needs a privileged critic" % (160 + _abi.POLICY_PRIV_DIM))
+        self.history = 0              # 16 when the dict holds model/enc_fc0/w:0 (a history student): forward() takes `hist` in priv's place
+        self.enc = _abi.OrrHistoryEncoder()
+        if ENC_KEYS[0][1] in params:
+            if not self.actor_priv_dim:
+                raise ValueError("a history encoder (model/enc_fc0/w:0) feeds a privileged actor (model/pi_fc0/w:0 with %d rows)" % (160 + _abi.POLICY_PRIV_DIM))
+            self.history = _abi.HISTORY_STEPS
+            for field, key in ENC_KEYS:
+                if field in ENC_SHAPES:
+                    if tuple(params[key].shape) != ENC_SHAPES[field]:
+                        raise ValueError("%s has shape %s, the fused kernel is built for %s" % (key, tuple(params[key].shape), ENC_SHAPES[field]))
+                    self.packed["enc_" + field] = torch.empty(int(self.L.orr_policy_packed_size(*ENC_SHAPES[field])), dtype=torch.float32, device=self.device)
         self.net = _abi.OrrPolicyNet()
         self.refresh()
 
@@ -58,33 +72,47 @@ class FusedActorCritic(object):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     def refresh(self):
-        """Re-pack the weights (six small launches) and re-read the biases from the parameter tensors."""
+        """Re-pack the weights (six small launches, eight with an encoder) and re-read the biases from the parameter tensors."""
         t = self.torch
-        for field, key in KEYS:
-            w = self.params[key].detach()
-            if w.dtype != t.float32 or not w.is_contiguous() or w.device != self.device:
-                w = w.to(device=self.device, dtype=t.float32).contiguous()
-            if field.startswith("w"):
-                k, n = w.shape
-                _lib.check(self.L.orr_policy_pack(w.data_ptr(), int(k), int(n), self.packed[field].data_ptr(), self._stream()), self.L)
-                setattr(self.net, field, self.packed[field].data_ptr())
-            else:
-                if field not in self.biases:          # own copy (stays valid while the optimiser updates the original) at a fixed address,
-                    self.biases[field] = t.empty_like(w)   # so that a captured forward pass can be replayed after a refresh
-                self.biases[field].copy_(w)
-                setattr(self.net, field, self.biases[field].data_ptr())
+        for struct, prefix, keys in ((self.net, "", KEYS),) + (((self.enc, "enc_", ENC_KEYS),) if self.history else ()):
+            for field, key in keys:
+                w = self.params[key].detach()
+                if w.dtype != t.float32 or not w.is_contiguous() or w.device != self.device:
+                    w = w.to(device=self.device, dtype=t.float32).contiguous()
+                name = prefix + field
+                if field.startswith("w"):
+                    k, n = w.shape
+                    _lib.check(self.L.orr_policy_pack(w.data_ptr(), int(k), int(n), self.packed[name].data_ptr(), self._stream()), self.L)
+                    setattr(struct, field, self.packed[name].data_ptr())
+                else:
+                    if name not in self.biases:          # own copy (stays valid while the optimiser updates the original) at a fixed address,
+                        self.biases[name] = t.empty_like(w)   # so that a captured forward pass can be replayed after a refresh
+                    self.biases[name].copy_(w)
+                    setattr(struct, field, self.biases[name].data_ptr())
 
-    def forward(self, obs, noise=None, want_mean=False, out_action=None, out_raw=None, out_value=None, priv=None, out_mean=None, want_value=True):
+    def forward(self, obs, noise=None, want_mean=False, out_action=None, out_raw=None, out_value=None, priv=None, out_mean=None, want_value=True,
+                hist=None, out_latent=None):
         """obs [N,160] float32 on the device; noise [N,12] standard normal or None (deterministic); priv [N,48] float32, the
         privileged observation, for a privileged critic (and only then).
         Returns (clipped action [N,12], raw action [N,12], value [N], mean [N,12] or None); the out_* tensors
         (contiguous float32 of those shapes, e.g. rows of a rollout buffer) are written in place when given (out_mean implies want_mean).
-        want_value=False: no value is written and None is returned for it; a privileged actor's kernel then skips the critic."""
+        want_value=False: no value is written and None is returned for it; a privileged actor's kernel then skips the critic.
+        hist [N,512] float32 (history_push), for a history student and instead of priv: the encoder's estimate of the row feeds actor and
+        critic (orr_policy_forward_history) and is written to out_latent [N,48] when that is given."""
         t = self.torch
         if obs.dtype != t.float32 or not obs.is_contiguous() or obs.device != self.device or obs.dim() != 2 or obs.shape[1] != 160:
             raise ValueError("obs must be a contiguous float32 [N,160] tensor on %s" % (self.device,))
         n = obs.shape[0]
-        if (priv is not None) != (self.priv_dim > 0):
+        if hist is not None:
+            if priv is not None:
+                raise ValueError("give priv or hist, not both")
+            if not self.history:
+                raise ValueError("hist is for a history student (model/enc_fc0/w:0) and for no other")
+            if hist.dtype != t.float32 or not hist.is_contiguous() or tuple(hist.shape) != (n, _abi.HISTORY_DIM) or hist.device != self.device:
+                raise ValueError("hist must be a contiguous float32 [N,%d] tensor on the same device" % _abi.HISTORY_DIM)
+        elif out_latent is not None:
+            raise ValueError("out_latent belongs to hist")
+        elif (priv is not None) != (self.priv_dim > 0):
             raise ValueError("priv is needed by a privileged critic (model/vf_fc0/w:0 with %d rows) and by no other" % (160 + _abi.POLICY_PRIV_DIM))
         if priv is not None and (priv.dtype != t.float32 or not priv.is_contiguous() or tuple(priv.shape) != (n, self.priv_dim)
                                  or priv.device != self.device):
@@ -102,6 +130,14 @@ class FusedActorCritic(object):
             raise ValueError("out_value given with want_value=False")
         act, raw, val = out(out_action, (n, 12)), out(out_raw, (n, 12)), out(out_value, (n,)) if want_value else None
         mean = out(out_mean, (n, 12)) if (want_mean or out_mean is not None) else None
+        if hist is not None:
+            latent = out(out_latent, (n, _abi.POLICY_PRIV_DIM)) if out_latent is not None else None
+            _lib.check(self.L.orr_policy_forward_history(C.byref(self.net), C.byref(self.enc), obs.data_ptr(), hist.data_ptr(), int(n),
+                                                         noise.data_ptr() if noise is not None else None, self.std, self.clip, act.data_ptr(),
+                                                         raw.data_ptr(), val.data_ptr() if val is not None else None,
+                                                         mean.data_ptr() if mean is not None else None,
+                                                         latent.data_ptr() if latent is not None else None, self._stream()), self.L)
+            return act, raw, val, mean
         if self.actor_priv_dim:
             _lib.check(self.L.orr_policy_forward_teacher(C.byref(self.net), obs.data_ptr(), priv.data_ptr(), int(n),
                                                          noise.data_ptr() if noise is not None else None, self.std, self.clip, act.data_ptr(),
@@ -118,3 +154,24 @@ class FusedActorCritic(object):
                                              self.std, self.clip, act.data_ptr(), raw.data_ptr(), val.data_ptr() if val is not None else None,
                                              mean.data_ptr() if mean is not None else None, self._stream()), self.L)
         return act, raw, val, mean
+
+
+def history_push(obs, done, prev, out):
+    """orr_history_push: out [N,512] = the sensor history after the step that produced obs [N,160] and done [N] (uint8 / bool; None: everybody
+    starts an episode, prev may then be None too), prev [N,512] the one before it.  out may be prev (in place).  Returns out."""
+    import torch
+    n = obs.shape[0]
+    for x, shape, name in ((obs, (n, 160), "obs"), (prev, (n, _abi.HISTORY_DIM), "prev"), (out, (n, _abi.HISTORY_DIM), "out")):
+        if x is not None and (x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != shape or x.device != obs.device or not x.is_cuda):
+            raise ValueError("%s must be a contiguous float32 %s tensor on the GPU" % (name, shape))
+    if out is None or (done is not None and prev is None):
+        raise ValueError("history_push needs out, and prev with done")
+    if done is not None:
+        if done.dtype == torch.bool:
+            done = done.view(torch.uint8)
+        if done.dtype != torch.uint8 or not done.is_contiguous() or tuple(done.shape) != (n,) or done.device != obs.device:
+            raise ValueError("done must be a contiguous uint8 / bool [N] tensor on the same device")
+    L = _lib.load()
+    _lib.check(L.orr_history_push(obs.data_ptr(), done.data_ptr() if done is not None else None, prev.data_ptr() if prev is not None else None,
+                                  out.data_ptr(), int(n), C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)), L)
+    return out

@@ -18,6 +18,34 @@ from . import policy as pol
 
 _LINEAR = {}
 
+# the sensor history of a history student (include/openroborl_policy.h: ORR_HISTORY_*): 16 frames of 32 words, newest first
+HISTORY_STEPS, HISTORY_FRAME, HISTORY_DIM = 16, 32, 512
+ENC_HIDDEN = 256
+
+
+def history_frame(obs):
+    """The newest reading of each sensor history inside obs [N,160] + four zeros: IMU obs[0:4], last action obs[12:24], motor angles obs[48:60]."""
+    import torch
+    return torch.cat((obs[:, 0:4], obs[:, 12:24], obs[:, 48:60], obs.new_zeros(obs.shape[0], 4)), dim=1)
+
+
+def history_push(hist, obs, done):
+    """The plain-torch statement of orr_history_push: hist [N,512] before the step (None with done None), obs [N,160] the observation after
+    it, done [N] the step's flags (None: everybody starts an episode) -> the history after it, a new tensor.  Slot 0 is obs's frame; a robot
+    whose episode just ended has that frame in all 16 slots; everybody else's slots move one back."""
+    import torch
+    frame = history_frame(obs)
+    fresh = frame.repeat(1, HISTORY_STEPS)
+    if done is None:
+        return fresh
+    shifted = torch.cat((frame, hist[:, :HISTORY_DIM - HISTORY_FRAME]), dim=1)
+    return torch.where(done.to(torch.bool)[:, None], fresh, shifted)
+
+
+def _no_history(model, who):
+    if getattr(model, "history", 0):
+        raise ValueError("%s: a history student (history = %d) is trained by DistillHistory / learner_hip.FusedDistillHistory only" % (who, model.history))
+
 
 def _wgrad(torch, x, g):
     """x^T g for a tall batch: hipBLASLt picks a 32x32 macro-tile for these (K = batch) shapes and fills a third of the
@@ -59,9 +87,16 @@ class ActorCritic(object):
     actor_priv_dim = 48 (with priv_dim = 48 only) makes the actor privileged as well - a teacher policy: model/pi_fc0/w:0 is
     [obs_dim + 48, 512] too, and mean(), log_prob() and act() take `priv`.  Such a policy cannot be deployed (nor loaded by the reference);
     Distill / learner_hip.FusedDistill turn it into a plain one.  With `params` the width is taken from model/pi_fc0/w:0.
-    actor_priv_dim = 0: every path is the one without."""
+    actor_priv_dim = 0: every path is the one without.
 
-    def __init__(self, device, obs_dim=160, act_dim=12, hidden=(512, 256), std=pol.PI_STD, params=None, seed=0, priv_dim=0, actor_priv_dim=0):
+    history = 16 (with actor_priv_dim = 48 only) adds an encoder over the last 16 steps' sensors, model/enc_fc0 [512, 256] (ReLU) and
+    model/enc_fc1 [256, 48]: a history student.  encode(hist) estimates the privileged row from hist [N, 512] (history_push), and mean() and
+    act() take `hist` in the row's place - the teacher's actor and critic on cat(obs, encode(hist)).  Such a policy is deployable: it reads
+    its own sensors only.  The encoder is drawn after every other parameter, so history = 0 is the model without, draw for draw.  With
+    `params` the presence of model/enc_fc0/w:0 decides."""
+
+    def __init__(self, device, obs_dim=160, act_dim=12, hidden=(512, 256), std=pol.PI_STD, params=None, seed=0, priv_dim=0, actor_priv_dim=0,
+                 history=0):
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -78,6 +113,13 @@ class ActorCritic(object):
         if actor_priv_dim and not self.priv_dim:
             raise ValueError("a privileged actor (actor_priv_dim = %d) needs the privileged critic (priv_dim = %d)" % (pol.PRIV_DIM, pol.PRIV_DIM))
         self.actor_priv_dim = int(actor_priv_dim)
+        if params is not None:
+            history = HISTORY_STEPS if "model/enc_fc0/w:0" in params else 0
+        if history not in (0, HISTORY_STEPS):
+            raise ValueError("history must be 0 or %d, got %r" % (HISTORY_STEPS, history))
+        if history and not self.actor_priv_dim:
+            raise ValueError("a history encoder (history = %d) feeds a privileged actor (actor_priv_dim = %d)" % (HISTORY_STEPS, pol.PRIV_DIM))
+        self.history = int(history)
         g = torch.Generator().manual_seed(seed)
         self.p = {}
         dims = [obs_dim] + list(hidden)
@@ -86,6 +128,9 @@ class ActorCritic(object):
                 fan_in = dims[i] + (self.priv_dim if (net, i) == ("vf", 0) else 0) + (self.actor_priv_dim if (net, i) == ("pi", 0) else 0)
                 self._init("model/%s_fc%d" % (net, i), fan_in, dims[i + 1], g, math.sqrt(2.0))
             self._init("model/%s" % net, dims[-1], out, g, 0.01 if net == "pi" else 1.0)
+        if self.history:           # after every other draw
+            self._init("model/enc_fc0", HISTORY_DIM, ENC_HIDDEN, g, math.sqrt(2.0))
+            self._init("model/enc_fc1", ENC_HIDDEN, pol.PRIV_DIM, g, 1.0)
         self.extra = {}            # variables of a loaded zip that this learner does not train (model/q/*): re-emitted by state_dict()
         if params is not None:
             for k, v in params.items():
@@ -147,8 +192,24 @@ class ActorCritic(object):
         """What mean() and log_prob() take as `priv` when the caller holds the critic's: the vector for a privileged actor, None for a plain one."""
         return priv if self.actor_priv_dim else None
 
-    def mean(self, obs, priv=None):
-        return self._mlp("pi", self._actor_input(obs, priv))
+    def encode(self, hist):
+        """hist [N, 512] (history_push) -> the encoder's estimate of the privileged row [N, 48]."""
+        if not self.history:
+            raise ValueError("this model has no history encoder (history = 0)")
+        t = self.torch
+        h = _linear(t, True)(hist, self.p["model/enc_fc0/w:0"], self.p["model/enc_fc0/b:0"])
+        return _linear(t, False)(h, self.p["model/enc_fc1/w:0"], self.p["model/enc_fc1/b:0"])
+
+    def _latent(self, priv, hist):
+        """The row the actor and the critic read: `priv` itself, or the encoder's estimate from `hist` (one of the two)."""
+        if hist is None:
+            return priv
+        if priv is not None:
+            raise ValueError("give priv or hist, not both")
+        return self.encode(hist)
+
+    def mean(self, obs, priv=None, hist=None):
+        return self._mlp("pi", self._actor_input(obs, self._latent(priv, hist)))
 
     def _critic_input(self, obs, priv):
         if (priv is not None) != (self.priv_dim > 0):
@@ -158,11 +219,24 @@ class ActorCritic(object):
     def value(self, obs, priv=None):
         return self._mlp("vf", self._critic_input(obs, priv))[:, 0]
 
-    def act(self, obs, priv=None, deterministic=False, generator=None, noise=None, out_raw=None, out_value=None):
+    def act(self, obs, priv=None, deterministic=False, generator=None, noise=None, out_raw=None, out_value=None, hist=None, out_latent=None):
         """-> (clipped action, raw action, value).  `noise` ([N,12] standard normal) overrides the generator; `priv` ([N,48], the
-        privileged observation) goes to a privileged critic, and to a privileged actor."""
+        privileged observation) goes to a privileged critic, and to a privileged actor.  `hist` ([N,512], a history student's input)
+        takes its place: actor and critic read the encoder's estimate, which out_latent [N,48] receives."""
         t = self.torch
-        if (priv is not None) != (self.priv_dim > 0):
+        if hist is not None:
+            if priv is not None:
+                raise ValueError("give priv or hist, not both")
+            if not self.history:
+                raise ValueError("this model has no history encoder (history = 0)")
+            if self.fused is None:
+                with t.no_grad():
+                    priv = self.encode(hist)
+                    if out_latent is not None:
+                        out_latent.copy_(priv)
+        if hist is None and out_latent is not None:
+            raise ValueError("out_latent belongs to hist")
+        if hist is None and (priv is not None) != (self.priv_dim > 0):
             raise ValueError("priv is needed by a privileged critic (priv_dim = %d) and by no other" % pol.PRIV_DIM)
         if self.fused is not None:
             if self._fused_dirty:
@@ -170,7 +244,11 @@ class ActorCritic(object):
                 self._fused_dirty = False
             if noise is None and not deterministic:
                 noise = t.randn((obs.shape[0], 12), device=obs.device, generator=generator)
-            a, raw, v, _ = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value, priv=priv)
+            if hist is not None:
+                a, raw, v, _ = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value, hist=hist,
+                                                  out_latent=out_latent)
+            else:
+                a, raw, v, _ = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value, priv=priv)
             return a, raw, v
         with t.no_grad():
             mu = self.mean(obs, self.actor_priv(priv))
@@ -194,6 +272,7 @@ class PPO(object):
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None):
         import torch
         self.torch = torch
+        _no_history(model, "PPO")
         self.model = model
         self.clip = clip_param
         self.minibatch = int(minibatch)
@@ -263,6 +342,7 @@ class Distill(object):
     def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096):
         import torch
         self.torch = torch
+        _no_history(student, "Distill")
         if getattr(student, "actor_priv_dim", 0):
             raise ValueError("Distill: the student's actor must read the 160 observation words only")
         self.model = student
@@ -281,6 +361,41 @@ class Distill(object):
             for s in range(0, B, self.minibatch):
                 e = s + self.minibatch
                 loss = ((self.model.mean(obs_p[s:e]) - tgt_p[s:e]) ** 2).sum(dim=1).mean()
+                self.opt.zero_grad(set_to_none=True)
+                loss.backward()
+                self.opt.step()
+                if hasattr(self.model, "mark_updated"):
+                    self.model.mark_updated()
+                stats.append(loss.detach())
+        return float(t.stack(stats).mean())
+
+
+class DistillHistory(object):
+    """The learner of a history student's encoder in plain torch (RMA's second phase; the fp32 reference of learner_hip.FusedDistillHistory):
+    encode(hist) is regressed on the recorded privileged rows, loss = mean over the samples of sum_j (z_j - priv_j)^2.  Only model/enc_* train;
+    the actor and the critic - the teacher's - are not touched and have no optimiser state."""
+
+    def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096):
+        import torch
+        self.torch = torch
+        if not getattr(student, "history", 0):
+            raise ValueError("DistillHistory: the student needs a history encoder (ActorCritic(history=16))")
+        self.model = student
+        self.minibatch = int(minibatch)
+        params = [student.p[k] for k in sorted(student.p) if k.startswith("model/enc_")]
+        self.opt = torch.optim.Adam(params, lr=lr, eps=adam_eps, fused=bool(params and params[0].is_cuda))
+
+    def update(self, hist, target_priv, epochs=1, generator=None):
+        """hist [B,512], target_priv [B,48] (env.privileged_obs on the same states); returns the mean loss over the minibatches."""
+        t = self.torch
+        B = hist.shape[0]
+        stats = []
+        for _ in range(epochs):
+            perm = t.randperm(B, device=hist.device, generator=generator)
+            hist_p, tgt_p = hist[perm], target_priv[perm]
+            for s in range(0, B, self.minibatch):
+                e = s + self.minibatch
+                loss = ((self.model.encode(hist_p[s:e]) - tgt_p[s:e]) ** 2).sum(dim=1).mean()
                 self.opt.zero_grad(set_to_none=True)
                 loss.backward()
                 self.opt.step()

@@ -14,7 +14,7 @@ resetting when any robot is done, and the GAE recursion uses each robot's own do
 indexes `episode_starts[(step*num_robot+i) + (1+i)]`, ppo_imitation.py:88, which reads a neighbouring
 robot's flag; `legacy_gae_index=True` reproduces exactly that, for comparisons with the reference at num_robot > 1).
 """
-from ._abi import PRIV_DIM
+from ._abi import HISTORY_DIM, PRIV_DIM
 
 
 def _teacher_labels(teacher, obs, priv, out_mean, out_action):
@@ -34,7 +34,8 @@ def _teacher_labels(teacher, obs, priv, out_mean, out_action):
             torch.clamp(out_mean, -2.0 * math.pi, 2.0 * math.pi, out=out_action)
 
 
-def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generator=None, noise=None, priv=None, teacher=None, teacher_mask=None):
+def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generator=None, noise=None, priv=None, teacher=None, teacher_mask=None,
+                    hist=None):
     """Run `horizon` env steps of all robots.  Returns a dict of [T, N, ...] tensors + the final observation.
     noise: optional [T, N, 12] standard-normal samples for the fused policy (default: drawn from `generator`).
     A policy with a privileged critic (priv_dim > 0) also gets env.privileged_obs() at every step: "priv" [T, N, 48] and "last_priv" are
@@ -43,15 +44,28 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
     (DAgger: the student `policy` drives, the teacher labels): env.privileged_obs() then follows every step whatever the student's
     priv_dim, and "teacher_mean" [T, N, 12] - the teacher's actor output on (obs[k], priv[k]) - is returned with "priv" and "last_priv".
     teacher_mask: uint8 [N]; robots with the mask set are stepped with the teacher's clipped mean instead of the student's sampled
-    action ("actions" stays the student's raw sample)."""
+    action ("actions" stays the student's raw sample).
+    A history student (policy.history > 0) reads hist[k] in the place of priv[k]: "hist" [T, N, 512] and "last_hist" are returned next to
+    "priv" and "last_priv" (the encoder's regression targets); after every step and its privileged_obs the history is pushed
+    (policy_hip.history_push(obs[k + 1], dones[k], hist[k], out=hist[k + 1])).  hist: the one that belongs to `obs` (the previous segment's
+    last_hist; None = computed here with done=None)."""
     t = env.torch
     n = env.num_robot
     dev = env.device
     if obs is None:
         obs = env.reset()
     priv_dim = int(getattr(policy, "priv_dim", 0))
+    history = int(getattr(policy, "history", 0))
     if teacher_mask is not None and teacher is None:
         raise ValueError("teacher_mask without a teacher")
+    hbuf = None
+    if history:
+        from . import policy_hip
+        hbuf = t.empty((horizon + 1, n, HISTORY_DIM), device=dev)
+        if hist is None:
+            policy_hip.history_push(obs, None, None, hbuf[0])
+        else:
+            hbuf[0].copy_(hist)
     pbuf = None
     if priv_dim or teacher is not None:
         pbuf = t.empty((horizon + 1, n, PRIV_DIM), device=dev)
@@ -72,12 +86,13 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
     if not fused or deterministic:
         noise = None
     for k in range(horizon):
+        row = {"hist": hbuf[k]} if history else ({"priv": pbuf[k]} if priv_dim else {})     # what the policy reads next to obs
         if fused:   # one fused launch writes the raw action and the value straight into the buffers
             clipped, _, _ = policy.act(obs, deterministic=deterministic, noise=None if noise is None else noise[k],
-                                       out_raw=buf["actions"][k], out_value=buf["vpred"][k], **({"priv": pbuf[k]} if priv_dim else {}))
+                                       out_raw=buf["actions"][k], out_value=buf["vpred"][k], **row)
             buf["obs"][k].copy_(obs)
         else:
-            clipped, raw, v = policy.act(obs, deterministic=deterministic, generator=generator, **({"priv": pbuf[k]} if priv_dim else {}))
+            clipped, raw, v = policy.act(obs, deterministic=deterministic, generator=generator, **row)
             buf["obs"][k].copy_(obs)
             buf["actions"][k].copy_(raw)
             buf["vpred"][k].copy_(v)
@@ -90,7 +105,11 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
         buf["dones"][k].copy_(done.bool())
         if pbuf is not None:    # of the state the new observation belongs to; robots that just ended an episode: no contact / push words
             env.privileged_obs(out=pbuf[k + 1], done=done)
+        if hbuf is not None:
+            policy_hip.history_push(obs.contiguous(), buf["dones"][k], hbuf[k], hbuf[k + 1])
     buf["last_obs"] = obs
+    if hbuf is not None:
+        buf["hist"], buf["last_hist"] = hbuf[:horizon], hbuf[horizon]
     if pbuf is not None:
         buf["priv"], buf["last_priv"] = pbuf[:horizon], pbuf[horizon]
     if noise is not None:
@@ -120,6 +139,10 @@ class GraphRollout(object):
     in place between collects, no new capture) is set are stepped with the teacher's clipped mean, the others with the student's sampled
     action; "actions" stays the student's raw sample.  All of it is inside the captured segment, the teacher's weight re-pack included.
 
+    With a history student (policy.history > 0) the segment also holds hist [T + 1, N, 512]: hist[k] goes to the forward pass in priv[k]'s
+    place, and after step_into and privileged_obs the push history_push(obs[k + 1], dones[k], hist[k], out=hist[k + 1]) runs inside the
+    captured segment; "hist" and "last_hist" are returned next to "priv" and "last_priv", the encoder's regression targets.
+
     The returned tensors are views of the static buffers: they are overwritten by the next collect() (clone what must survive it,
     e.g. the last row of `dones` that the next segment's GAE takes as first_starts)."""
 
@@ -135,6 +158,8 @@ class GraphRollout(object):
         self.dones = t.zeros((T, n), dtype=t.uint8, device=dev)
         self.priv_dim = int(getattr(policy, "priv_dim", 0))
         self.priv = f(T + 1, n, self.priv_dim or PRIV_DIM) if (self.priv_dim or teacher is not None) else None
+        self.history = int(getattr(policy, "history", 0))
+        self.hist = f(T + 1, n, HISTORY_DIM) if self.history else None
         if teacher is not None:
             self.teacher_mean, self.teacher_clipped, self.step_action = f(T, n, 12), f(n, 12), f(n, 12)
             self.teacher_mask = t.zeros(n, dtype=t.uint8, device=dev)
@@ -146,12 +171,15 @@ class GraphRollout(object):
 
     def _segment(self):
         import math
+        from . import policy_hip
         t, env, fused = self.env.torch, self.env, self.policy.fused
         fused.refresh()                   # inside the graph: every replay re-packs the weights the learner has just updated
         if self.teacher is not None:
             self.teacher.fused.refresh()
         for k in range(self.T):
-            if self.priv_dim:
+            if self.history:
+                fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], hist=self.hist[k])
+            elif self.priv_dim:
                 fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], priv=self.priv[k])
             else:
                 fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k])
@@ -163,17 +191,27 @@ class GraphRollout(object):
             env.step_into(action, self.obs[k + 1], self.rewards[k], self.dones[k])
             if self.priv is not None:
                 env.privileged_obs(out=self.priv[k + 1], done=self.dones[k])
+            if self.history:
+                policy_hip.history_push(self.obs[k + 1], self.dones[k], self.hist[k], self.hist[k + 1])
         # log-probability of the sampled actions under the sampling policy: a - mean = std * noise
         t.sum(self.noise * self.noise, dim=-1, out=self.logp)
         self.logp.mul_(-0.5).sub_(12.0 * math.log(float(self.policy.std) * math.sqrt(2.0 * math.pi)))
 
-    def collect(self, obs, generator=None, noise=None, priv=None):
+    def collect(self, obs, generator=None, noise=None, priv=None, hist=None):
         """priv: the privileged observation that belongs to `obs` (the previous segment's "last_priv"), for a policy with a privileged
-        critic; None = computed here with done=None (right after a reset; otherwise the contact and push words start as zeros)."""
+        critic; None = computed here with done=None (right after a reset; otherwise the contact and push words start as zeros).
+        hist: likewise the history that belongs to `obs` (the previous segment's "last_hist"), for a history student; None = obs's frame
+        in every slot."""
         t, env = self.env.torch, self.env
         with t.no_grad():
             if obs.data_ptr() != self.obs[0].data_ptr():
                 self.obs[0].copy_(obs)
+            if self.hist is not None:
+                if hist is None:
+                    from . import policy_hip
+                    policy_hip.history_push(self.obs[0], None, None, self.hist[0])
+                elif hist.data_ptr() != self.hist[0].data_ptr():
+                    self.hist[0].copy_(hist)
             if self.priv is not None:
                 if priv is None:
                     env.privileged_obs(out=self.priv[0], done=None)
@@ -207,6 +245,8 @@ class GraphRollout(object):
                "vpred": self.vpred, "logp": self.logp, "last_obs": self.obs[self.T]}
         if self.priv is not None:
             buf["priv"], buf["last_priv"] = self.priv[:self.T], self.priv[self.T]
+        if self.hist is not None:
+            buf["hist"], buf["last_hist"] = self.hist[:self.T], self.hist[self.T]
         if self.teacher is not None:
             buf["teacher_mean"] = self.teacher_mean
         return buf

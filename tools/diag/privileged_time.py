@@ -7,6 +7,8 @@ python tools/diag/privileged_time.py [--alt-policy-lib PATH]
             distillation: no critic) against orr_policy_forward, random weights; with --alt-policy-lib also orr_policy_forward_priv of a
             second build of csrc/orr_policy.hip (e.g. -DORR_POLICY_PRIV_SPLIT=0: the critic's layer 0 at pipeline depth 1 instead of
             12 + 1 k-groups), loaded next to the shipped library and run on the same packed weights
+  history   orr_policy_forward_history (a history student: the encoder 512 -> 256 -> 48 in front of the teacher's pass) against
+            orr_policy_forward_teacher, each with and without a value buffer, and orr_history_push per launch (out of place, no resets)
   row       orr_privileged_obs with contact and push outputs bound against the env step of the same env (train mode, randomiser, pushes
             at prob 0.02)"""
 import argparse
@@ -97,6 +99,20 @@ print("orr_policy_forward_teacher, value = NULL against orr_policy_forward_teach
 if args.alt_policy_lib:
     fns[1](); run_alt(); torch.cuda.synchronize()
     print("the two builds' values are equal bit for bit: %s" % bool(torch.equal(val, val_alt)))
+
+# ---- history ----
+student = ppo.ActorCritic(dev, seed=3, priv_dim=_abi.POLICY_PRIV_DIM, actor_priv_dim=_abi.POLICY_PRIV_DIM, history=_abi.HISTORY_STEPS)
+fh = policy_hip.FusedActorCritic(student.p, dev, std=0.125)
+hist, hist2 = torch.randn(N, _abi.HISTORY_DIM, device=dev, generator=g), torch.empty(N, _abi.HISTORY_DIM, device=dev)
+done = torch.zeros(N, dtype=torch.uint8, device=dev)
+med = report(["orr_policy_forward_teacher", "orr_policy_forward_teacher, value = NULL", "orr_policy_forward_history", "orr_policy_forward_history, value = NULL",
+              "orr_history_push"],
+             [fns[2], fns[3], lambda: fh.forward(obs, noise, out_action=act, out_raw=raw, out_value=val, hist=hist),
+              lambda: fh.forward(obs, None, out_action=act, out_raw=raw, out_mean=mean, want_value=False, hist=hist),
+              lambda: policy_hip.history_push(obs, done, hist, hist2)])
+# MFMAs per wave: the encoder adds 512 (layer 0) + 64 (layer 1, on three of the four waves) to the teacher's 1920, or 992 without the critic
+print("orr_policy_forward_history against orr_policy_forward_teacher: ratio %.4f (the MFMA counts give %.4f)" % (med[2] / med[0], (1920.0 + 576.0) / 1920.0))
+print("the same with value = NULL: ratio %.4f (the MFMA counts give %.4f)" % (med[3] / med[1], (992.0 + 576.0) / 992.0))
 
 # ---- row ----
 env = VecQuadrupedEnv(task_name="imitation_learning_laikago", num_robot=N, mode="train", auto_reset=True, seed=7, contact_outputs=True,

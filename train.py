@@ -7,6 +7,7 @@ leaves the GPU.  Counterpart of `python3 OpenRoboRL/run.py --task imitation_lear
   python train.py --task imitation_learning_laikago --iters 200 --privileged-critic --push 0.02,0.2,0.5   (asymmetric actor-critic)
   python train.py --task imitation_learning_laikago --iters 200 --privileged-actor --push 0.02,0.2,0.5 --save teacher.zip   (a teacher)
   python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --push 0.02,0.2,0.5 --save student.zip   (its student)
+  python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --history --push 0.02,0.2,0.5 --save student.zip   (a history student)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py ...
 """
 import argparse
@@ -74,6 +75,11 @@ def main():
                          "and labelled with the teacher's mean on (observation, privileged observation), then regressed on for --epochs "
                          "(learner_hip.FusedDistill; --torch-learner: ppo.Distill).  The log carries distill_loss; --save writes a plain "
                          "[160, 512] actor.  One rank")
+    ap.add_argument("--history", action="store_true",
+                    help="--distill: the student keeps the teacher's actor and critic and gains an encoder over the last 16 steps of its own "
+                         "sensors (IMU, last action, motor angles: 512 words), trained to estimate the privileged observation from them "
+                         "(learner_hip.FusedDistillHistory; --torch-learner: ppo.DistillHistory).  The log carries latent_loss; --save writes "
+                         "the teacher's variables + model/enc_*, a zip that loads here (--eval) and not in the reference")
     ap.add_argument("--distill-beta", type=float, default=0.0,
                     help="--distill: the share of robots that are stepped with the teacher's action instead of the student's (default 0)")
     ap.add_argument("--distill-beta-iters", type=int, default=0, help="--distill: decay --distill-beta linearly to 0 over this many iterations (0: constant)")
@@ -108,6 +114,8 @@ def main():
     args.privileged_critic = args.privileged_critic or args.privileged_actor
     if args.distill and (args.privileged_critic or args.torch_policy):
         raise SystemExit("train.py: --distill trains a plain student with the fused rollout; not with --privileged-critic / --privileged-actor / --torch-policy")
+    if args.history and not args.distill:
+        raise SystemExit("train.py: --history belongs to --distill")
     privileged = args.privileged_critic or bool(args.distill)       # somebody reads env.privileged_obs
     rank, world, local = odist.init_from_env()
     if args.distill and world > 1:
@@ -122,6 +130,8 @@ def main():
                           observation_noise_stdev=args.sensor_noise, push=args.push,
                           push_outputs=privileged and args.push is not None,
                           **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
+    if args.history:
+        return distill(args, torch, pol, ppo, rollout, odist, env, history_student(args, torch, pol, ppo, dev), dev)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     # same seed -> identical replicas.  (--model-file: the critic's width is the file's)
     model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic else 0,
@@ -209,35 +219,59 @@ def main():
         torch.distributed.destroy_process_group()
 
 
+def history_student(args, torch, pol, ppo, dev):
+    """--distill TEACHER.zip --history: the teacher's parameters + a fresh encoder (seeded by --seed), on the fused path."""
+    params = pol.load_parameters(args.distill)
+    if np.shape(params["model/pi_fc0/w:0"])[0] != 160 + pol.PRIV_DIM:
+        raise SystemExit("train.py: --history needs a teacher with a privileged actor (--privileged-actor)")
+    student = ppo.ActorCritic(dev, seed=args.seed, priv_dim=pol.PRIV_DIM, actor_priv_dim=pol.PRIV_DIM, history=ppo.HISTORY_STEPS)
+    with torch.no_grad():
+        for k, v in params.items():
+            if k.startswith("model/enc_"):
+                continue                     # a history student as the teacher: its actor and critic, a fresh encoder all the same
+            if k in student.p:
+                student.p[k].copy_(torch.as_tensor(v))
+            else:
+                student.extra[k] = np.asarray(v, dtype=np.float32).copy()
+    return student.enable_fused()
+
+
 def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
     """--distill TEACHER.zip: DAgger on the device.  Each iteration collects a segment in which the student drives (all robots but the
-    share --distill-beta, which the teacher drives) and the teacher labels every visited state, then regresses the student's mean on the labels."""
-    teacher = ppo.ActorCritic(dev, params=pol.load_parameters(args.distill)).enable_fused()
+    share --distill-beta, which the teacher drives) and the teacher labels every visited state, then regresses the student's mean on the labels.
+    --history: the student reads its sensor history, and its encoder's output is regressed on the segment's privileged observations instead."""
+    teacher_params = {k: v for k, v in pol.load_parameters(args.distill).items() if not k.startswith("model/enc_")}
+    teacher = ppo.ActorCritic(dev, params=teacher_params).enable_fused()
     B = args.num_robot * args.horizon
+    loss_name = "latent_loss" if args.history else "distill_loss"
     if args.torch_learner:
-        learner = ppo.Distill(student, lr=args.lr, minibatch=args.minibatch)
+        learner = (ppo.DistillHistory if args.history else ppo.Distill)(student, lr=args.lr, minibatch=args.minibatch)
     else:
         from openroborl_amd import learner_hip
-        learner = learner_hip.FusedDistill(student, lr=args.lr, minibatch=learner_hip.FusedDistill.fit_minibatch(B, args.minibatch))
+        cls = learner_hip.FusedDistillHistory if args.history else learner_hip.FusedDistill
+        learner = cls(student, lr=args.lr, minibatch=cls.fit_minibatch(B, args.minibatch))
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed * 1000)
     collector = rollout.GraphRollout(env, student, args.horizon, teacher=teacher)
-    obs, priv = env.reset(), None
+    obs, priv, hist = env.reset(), None, None
     t0, samples, log = time.time(), 0, []
     for it in range(args.iters):
         beta = args.distill_beta * (max(0.0, 1.0 - it / float(args.distill_beta_iters)) if args.distill_beta_iters > 0 else 1.0)
         driven = int(round(beta * args.num_robot))
         collector.teacher_mask.zero_()
         collector.teacher_mask[:driven] = 1
-        buf = collector.collect(obs, generator=gen, priv=priv)
-        obs, priv = buf["last_obs"], buf["last_priv"]
-        loss = learner.update(buf["obs"].reshape(B, -1), buf["teacher_mean"].reshape(B, 12), epochs=args.epochs, generator=gen)
+        buf = collector.collect(obs, generator=gen, priv=priv, hist=hist)
+        obs, priv, hist = buf["last_obs"], buf["last_priv"], buf.get("last_hist")
+        if args.history:
+            loss = learner.update(buf["hist"].reshape(B, -1), buf["priv"].reshape(B, -1), epochs=args.epochs, generator=gen)
+        else:
+            loss = learner.update(buf["obs"].reshape(B, -1), buf["teacher_mean"].reshape(B, 12), epochs=args.epochs, generator=gen)
         samples += B
         stats = odist.gather_env_episodes(env, args.horizon)
         if it % 10 == 0 or it == args.iters - 1:
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
                    "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2), "episodes": stats.sums[0],
-                   "distill_loss": round(float(loss), 6), "teacher_driven": driven}
+                   loss_name: round(float(loss), 6), "teacher_driven": driven}
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if args.save:
@@ -298,12 +332,17 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     model = ppo.ActorCritic(dev, params=pol.load_parameters(args.eval))
     if not args.torch_policy:
         model.enable_fused()
-    if model.actor_priv_dim and not args.contact_outputs:
+    if model.actor_priv_dim and not model.history and not args.contact_outputs:
         env.bind_contact_outputs(True)           # a teacher's actor reads the contact words of the row, as it did in training
     obs = env.reset()
     # a zip with a privileged critic (--privileged-critic): the fused forward pass takes the privileged observation; only the actor's output is used
-    # here.  A teacher's zip (--privileged-actor): the row goes to the actor every step.  A student's zip (--distill) is a plain policy
-    priv = env.privileged_obs(done=None) if model.priv_dim else None
+    # here.  A teacher's zip (--privileged-actor): the row goes to the actor every step.  A student's zip (--distill) is a plain policy.
+    # A history student's zip (--distill --history): no row at all; its sensor history is kept in place, one push per step
+    priv = env.privileged_obs(done=None) if model.priv_dim and not model.history else None
+    hist = None
+    if model.history:
+        from openroborl_amd import policy_hip
+        hist = policy_hip.history_push(obs, None, None, torch.empty((n, ppo.HISTORY_DIM), device=dev))
     clip_ids = env.active_clip_ids()             # the clip each robot's episode plays
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     ret = torch.zeros(n, device=dev)
@@ -313,10 +352,12 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     normal = torch.zeros(4, dtype=torch.float64, device=dev)
     limit = int(env.field_int("MAX_EP_STEPS").max())
     for _ in range(limit):
-        act, _, _ = model.act(obs, priv, deterministic=True)
+        act, _, _ = model.act(obs, priv, deterministic=True, hist=hist)
         obs, rew, done, _ = env.step(act)
-        if model.priv_dim:
+        if priv is not None:
             env.privileged_obs(out=priv, done=done)
+        if hist is not None:
+            policy_hip.history_push(obs, done, hist, hist)
         ret += rew * alive
         if args.reward_terms:
             term_sum += (env.reward_terms * alive[:, None]).sum(0)
