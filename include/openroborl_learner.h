@@ -9,6 +9,7 @@
  *   orr_ppo_head       loss terms, d loss / d mean, d loss / d value, bias gradients of the two output layers
  *   orr_distill_head   the loss head of policy distillation instead: squared error of the actor's mean against a teacher's, its gradient
  *   orr_regress_head   the loss head of a history student's encoder: squared error of its 48 outputs against the privileged row, its gradient
+ *   orr_history_student_head  that head with the action loss: forward through the frozen actor, both losses, backward to the latent, one launch
  *   orr_head_backward  gradient through an output layer (fan-out 12 or 1) + ReLU mask + bias gradient of the layer below + the
  *                      output layer's weight gradient
  *   orr_colsum_finish  the column sums behind all bias gradients of a minibatch in one launch
@@ -22,6 +23,8 @@
 #define OPENROBORL_LEARNER_H
 
 #include <stdint.h>
+
+#include "openroborl_policy.h"   /* orr_policy_net, for orr_history_student_head */
 
 #ifdef __cplusplus
 extern "C" {
@@ -67,6 +70,31 @@ int32_t orr_distill_head(const float* mean, const float* target, int32_t m, floa
  * The sums run in a fixed order.  The layers below are torch GEMMs, orr_relu_backward, orr_colsum_finish and orr_adam_step. */
 int32_t orr_regress_head(const float* pred, const float* target, int32_t m, int32_t c, float* g, float* gb, float* stats, float* workspace,
                          void* stream);
+
+/* Loss head of a history student's encoder WITH the action loss, for a minibatch of m samples: the encoder's output z goes through the frozen
+ * teacher's actor, and the actor's mean is regressed on the teacher's next to the latent regression of orr_regress_head (host side:
+ * learner_hip.FusedDistillHistory(action_coef > 0)).  One launch: forward, both losses, backward to the latent; a workgroup owns 16 samples,
+ * no activation leaves LDS and no weight gradient is formed (csrc/orr_policy.hip).
+ *   in_i   = obs_i | z_i                                      (160 + 48)
+ *   mean_i = W2^T relu(W1^T relu(W0^T in_i + b0) + b1) + b2   the actor as orr_policy_forward_teacher computes it, bit for bit (priv = z)
+ *   L_act  = (1 / m) sum_i sum_j (mean_ij - target_mean_ij)^2, j < 12;   L_lat = (1 / m) sum_i sum_c (z_ic - target_priv_ic)^2, c < 48
+ *   g_z    = d (action_coef L_act + latent_coef L_lat) / d z  [m][48]
+ *   net                  only the *_pi members are read (w0_pi packed at k = 208); the vf members may be NULL
+ *   w2t, w1t, w0zt       orr_policy_pack of W2^T zero-padded to [16][256], of W1^T [256][512] and of the transpose of W0's rows 160..207, [512][48]
+ *   obs [m][160], z [m][48], target_mean [m][12], target_priv [m][48]
+ *   g_z [m][48]
+ *   mean [m][12] | NULL  the actor's output; NULL: not written, and no other output bit changes
+ *   partials             ORR_STUDENT_HEAD_PARTIAL_FLOATS(m) floats, rows = ORR_STUDENT_HEAD_ROWS(m) = one per workgroup:
+ *                        [rows][48] the workgroup's column sums of g_z (their sum is the bias gradient of the layer that produced z), followed by
+ *                        [rows][2] its shares of L_act and L_lat (the 1 / m included).  orr_colsum_finish folds them in its fixed order, as two
+ *                        jobs: {partials, gb [48], rows, 48} and {partials + 48 rows, stats [2], rows, 2}
+ * Packed matrices 16-byte aligned, every other buffer 4-byte aligned; m >= 1.  Rows beyond m read as zero and write nothing.  No float atomics:
+ * the same inputs give the same bits.  A refused call launches and writes nothing. */
+#define ORR_STUDENT_HEAD_ROWS(m) (((m) + 15) / 16)
+#define ORR_STUDENT_HEAD_PARTIAL_FLOATS(m) (50 * (int64_t)ORR_STUDENT_HEAD_ROWS(m))
+int32_t orr_history_student_head(const orr_policy_net* net, const float* w2t, const float* w1t, const float* w0zt, const float* obs, const float* z,
+                                 const float* target_mean, const float* target_priv, int32_t m, float action_coef, float latent_coef, float* g_z,
+                                 float* mean, float* partials, void* stream);
 
 /* g [m][c] (gradient w.r.t. a ReLU layer's output h [m][c]) becomes the gradient w.r.t. its pre-activation, in place: g *= (h > 0);
  * gb [c] = its column sums (the layer's bias gradient).  c: a multiple of 4 with 1024 % c == 0.

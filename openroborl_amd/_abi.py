@@ -213,3 +213,14 @@ POLICY_FORWARD_HISTORY_ARGS = [C.POINTER(OrrPolicyNet), C.POINTER(OrrHistoryEnco
 # include/openroborl_learner.h: int32_t orr_regress_head(const float* pred [m][c], const float* target [m][c], int32_t m, int32_t c, float* g [m][c],
 #   float* gb [c], float* stats [1], float* workspace, void* stream)
 REGRESS_HEAD_ARGS = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_history_student_head(const orr_policy_net* net (the *_pi members), const float* w2t, const float* w1t,
+#   const float* w0zt (the three packed transposes), const float* obs [m][160], const float* z [m][48], const float* target_mean [m][12],
+#   const float* target_priv [m][48], int32_t m, float action_coef, float latent_coef, float* g_z [m][48], float* mean [m][12] | NULL,
+#   float* partials [student_head_rows(m)][48] + [rows][2], void* stream)
+HISTORY_STUDENT_HEAD_ARGS = [C.POINTER(OrrPolicyNet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                             C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def student_head_rows(m):
+    """include/openroborl_learner.h: ORR_STUDENT_HEAD_ROWS - the rows of partial sums orr_history_student_head leaves, one per 16 samples."""
+    return (int(m) + 15) // 16

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "../../include/openroborl_policy.h"
+#include "../../include/openroborl_learner.h"   // orr_history_student_head: a learner's launch that needs this file's layer<>
 
 int orr_fail(int code, const char* msg, hipError_t e);  // orr_kernels.hip
 
@@ -356,6 +357,170 @@ __global__ void gae_kernel(const float* __restrict__ rewards, const float* __res
   for (int k = 0; k < T; k++) { const size_t o = (size_t)k * N + n; adv[o] = (adv[o] - mean) * inv; }
 }
 
+// ---- orr_history_student_head (include/openroborl_learner.h): the action loss of a history student through the frozen actor ----------------
+// Forward, loss and backward to the latent for a tile of 16 samples in one launch, the forward kernel's mapping: four waves, the tile
+// obs | z and both hidden layers in LDS, weights streamed in orr_policy_pack's fragments.  The forward layers are forward_kernel<208, 208>'s
+// calls on the same k-groups (hence the teacher kernel's mean, bit for bit); the backward layers are layer<> again, against the packed
+// transposes: g_h1 = g_mean W2^T (K = 16: the 12 actions + 4 zero columns), g_h0 = g_h1 W1^T (K = 256), g_z = g_h0 W0[160:208]^T (K = 512,
+// one column tile on each of three waves).  A masked gradient overwrites the activation it masks (h > 0, orr_relu_backward's convention):
+// a lane reads and writes the four C-layout elements that it owns, and no other lane touches them between the two barriers around a layer.
+// No weight gradient: the actor is frozen.  MFMAs per wave: 416 + 512 + 64 forward, 16 + 512 + 128 backward = 1648.
+// Its own UNIT for layer<> (see there): the forward kernels share no instantiation with it.
+struct HeadParams {
+  const float *w0, *b0, *w1, *b1, *w2, *b2;    // orr_policy_net's actor
+  const float *w2t, *w1t, *w0zt;               // the packed transposes
+  const float *obs, *z, *target_mean, *target_priv;
+  float *g_z, *mean, *partials;
+  int m, nblk;
+  float g_act, g_lat, inv_m;                   // 2 action_coef / m, 2 latent_coef / m, 1 / m
+};
+constexpr int kHeadUnit = 2 * (kObs + kPriv);
+constexpr int kInStride = kObs + kPriv + 1, kG0Stride = kH0 + 1, kG1Stride = kH1 + 1, kGmStride = 17;    // odd, like the forward kernel's tiles
+static_assert(kInStride % 2 == 1 && kG0Stride % 2 == 1 && kG1Stride % 2 == 1 && kGmStride % 2 == 1, "odd LDS strides");
+
+// store_relu's text under a name of this kernel's own, for the reason layer<> takes a UNIT: a fifth caller of store_relu<8> and <4> changed
+// the four forward kernels' instructions (profiles/history_action_loss.txt)
+template <int TILES>
+__device__ __forceinline__ void head_store_relu(const f32x4 (&acc)[TILES], const float* __restrict__ bias, int nt0, float* dst, int stride, int lane) {
+  const int col = lane & 15, r0 = 4 * (lane >> 4);
+#pragma unroll
+  for (int t = 0; t < TILES; t++) {
+    const float b = bias[16 * (nt0 + t) + col];
+#pragma unroll
+    for (int r = 0; r < 4; r++) dst[(r0 + r) * stride + 16 * (nt0 + t) + col] = fmaxf(acc[t][r] + b, 0.0f);
+  }
+}
+
+template <int TILES>
+__device__ __forceinline__ void store_masked(const f32x4 (&acc)[TILES], int nt0, float* h, int stride, int lane) {
+  const int col = lane & 15, r0 = 4 * (lane >> 4);
+#pragma unroll
+  for (int t = 0; t < TILES; t++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      float* p = h + (r0 + r) * stride + 16 * (nt0 + t) + col;
+      *p = *p > 0.0f ? acc[t][r] : 0.0f;
+    }
+}
+
+__device__ __forceinline__ float head_wave_sum(float x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+  return x;
+}
+
+__global__ __launch_bounds__(256) void student_head_kernel(HeadParams P) {
+  constexpr int UNIT = kHeadUnit, KP = kObs + kPriv, kMain = KP / 32 * 32;
+  __shared__ float s_in[kRows * kInStride];
+  __shared__ float s_h0[kRows * kG0Stride];
+  __shared__ float s_h1[kRows * kG1Stride];
+  __shared__ float s_gm[kRows * kGmStride];
+  __shared__ float s_loss[4];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int row0 = blockIdx.x * kRows;
+  const int col = lane & 15, r0 = 4 * (lane >> 4);
+  // the tile obs | z (rows beyond m read as zero)
+  for (int i = tid; i < kRows * kObs; i += 256) {
+    const int r = i / kObs, c = i - r * kObs;
+    s_in[r * kInStride + c] = (row0 + r) < P.m ? P.obs[(size_t)(row0 + r) * kObs + c] : 0.0f;
+  }
+  for (int i = tid; i < kRows * kPriv; i += 256) {
+    const int r = i / kPriv, c = i - r * kPriv;
+    s_in[r * kInStride + kObs + c] = (row0 + r) < P.m ? P.z[(size_t)(row0 + r) * kPriv + c] : 0.0f;
+  }
+  __syncthreads();
+  // ---- forward: the teacher kernel's actor ----
+  {
+    f32x4 acc[8];
+#pragma unroll
+    for (int t = 0; t < 8; t++) acc[t] = f32x4{0, 0, 0, 0};
+    layer<UNIT, 8, kMain, 2, KP / 16, 0>(acc, P.w0, 8 * wave, s_in, kInStride, lane);
+    layer<UNIT, 8, KP - kMain, 1, KP / 16, kMain / 16>(acc, P.w0, 8 * wave, s_in + kMain, kInStride, lane);
+    head_store_relu<8>(acc, P.b0, 8 * wave, s_h0, kG0Stride, lane);
+  }
+  __syncthreads();
+  {
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[t] = f32x4{0, 0, 0, 0};
+    layer<UNIT, 4, kH0, 4>(acc, P.w1, 4 * wave, s_h0, kG0Stride, lane);
+    head_store_relu<4>(acc, P.b1, 4 * wave, s_h1, kG1Stride, lane);
+  }
+  __syncthreads();
+  // ---- the head and the action loss on wave 0: g_mean = 2 action_coef (mean - target) / m, a 16 x 16 tile with columns 12..15 zero ----
+  if (wave == 0) {
+    f32x4 acc[1] = {f32x4{0, 0, 0, 0}};
+    layer<UNIT, 1, kH1, 4>(acc, P.w2, 0, s_h1, kG1Stride, lane);
+    const float b = col < kAct ? P.b2[col] : 0.0f;
+    float sq = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = row0 + r0 + r;
+      float gm = 0.0f;
+      if (col < kAct && row < P.m) {
+        const size_t o = (size_t)row * kAct + col;
+        const float mu = acc[0][r] + b;
+        if (P.mean) P.mean[o] = mu;
+        const float d = mu - P.target_mean[o];
+        gm = P.g_act * d;
+        sq += d * d;
+      }
+      s_gm[(r0 + r) * kGmStride + col] = gm;
+    }
+    sq = head_wave_sum(sq);
+    if (lane == 0) s_loss[0] = sq;
+  }
+  __syncthreads();
+  // ---- backward: 12 (16) -> 256, masked by h1 > 0, over h1 ----
+  {
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[t] = f32x4{0, 0, 0, 0};
+    layer<UNIT, 4, 16, 1>(acc, P.w2t, 4 * wave, s_gm, kGmStride, lane);
+    store_masked<4>(acc, 4 * wave, s_h1, kG1Stride, lane);
+  }
+  __syncthreads();
+  // ---- 256 -> 512, masked by h0 > 0, over h0 ----
+  {
+    f32x4 acc[8];
+#pragma unroll
+    for (int t = 0; t < 8; t++) acc[t] = f32x4{0, 0, 0, 0};
+    layer<UNIT, 8, kH1, 2>(acc, P.w1t, 8 * wave, s_h1, kG1Stride, lane);
+    store_masked<8>(acc, 8 * wave, s_h0, kG0Stride, lane);
+  }
+  __syncthreads();
+  // ---- 512 -> 48 on three waves, + the latent loss's own gradient; column sums and loss shares of the tile ----
+  if (wave < kPriv / 16) {
+    f32x4 acc[1] = {f32x4{0, 0, 0, 0}};
+    layer<UNIT, 1, kH0, 4>(acc, P.w0zt, wave, s_h0, kG0Stride, lane);
+    const int c = 16 * wave + col;
+    float cs = 0.0f, sq = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = row0 + r0 + r;
+      if (row < P.m) {
+        const size_t o = (size_t)row * kPriv + c;
+        const float d = s_in[(r0 + r) * kInStride + kObs + c] - P.target_priv[o];
+        const float g = acc[0][r] + P.g_lat * d;
+        P.g_z[o] = g;
+        cs += g;
+        sq += d * d;
+      }
+    }
+    cs += __shfl_xor(cs, 16, 64);     // the four row groups of a column, in a fixed order
+    cs += __shfl_xor(cs, 32, 64);
+    if (lane < 16) P.partials[(size_t)blockIdx.x * kPriv + c] = cs;
+    sq = head_wave_sum(sq);
+    if (lane == 0) s_loss[1 + wave] = sq;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float* loss = P.partials + (size_t)P.nblk * kPriv + 2 * (size_t)blockIdx.x;
+    loss[0] = s_loss[0] * P.inv_m;
+    loss[1] = ((s_loss[1] + s_loss[2]) + s_loss[3]) * P.inv_m;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -466,6 +631,35 @@ int32_t orr_history_push(const float* obs, const uint8_t* done, const float* pre
                      done, prev, next, (int)n);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_history_push: launch", e);
+  return 0;
+}
+
+int32_t orr_history_student_head(const orr_policy_net* net, const float* w2t, const float* w1t, const float* w0zt, const float* obs, const float* z,
+                                 const float* target_mean, const float* target_priv, int32_t m, float action_coef, float latent_coef, float* g_z,
+                                 float* mean, float* partials, void* stream) {
+  if (!net || !w2t || !w1t || !w0zt || !obs || !z || !target_mean || !target_priv || !g_z || !partials || m <= 0)
+    return orr_fail(-1, "orr_history_student_head: bad argument", hipSuccess);
+  const float* const* p = reinterpret_cast<const float* const*>(net);
+  for (int i = 0; i < 6; i++) {           // the actor's members only: the critic's are not read
+    if (!p[i]) return orr_fail(-1, "orr_history_student_head: orr_policy_net's actor has a null pointer", hipSuccess);
+    if (reinterpret_cast<uintptr_t>(p[i]) & (i % 2 == 0 ? 15 : 3))     // packed weights are read 16 bytes per lane
+      return orr_fail(-1, "orr_history_student_head: packed weights must be 16-byte aligned, biases 4-byte aligned", hipSuccess);
+  }
+  for (const void* q : {(const void*)w2t, (const void*)w1t, (const void*)w0zt})
+    if (reinterpret_cast<uintptr_t>(q) & 15) return orr_fail(-1, "orr_history_student_head: packed weights must be 16-byte aligned", hipSuccess);
+  for (const void* q : {(const void*)obs, (const void*)z, (const void*)target_mean, (const void*)target_priv, (const void*)g_z, (const void*)mean,
+                        (const void*)partials})
+    if (reinterpret_cast<uintptr_t>(q) & 3) return orr_fail(-1, "orr_history_student_head: buffers must be 4-byte aligned", hipSuccess);
+  HeadParams P;
+  P.w0 = net->w0_pi; P.b0 = net->b0_pi; P.w1 = net->w1_pi; P.b1 = net->b1_pi; P.w2 = net->w2_pi; P.b2 = net->b2_pi;
+  P.w2t = w2t; P.w1t = w1t; P.w0zt = w0zt;
+  P.obs = obs; P.z = z; P.target_mean = target_mean; P.target_priv = target_priv;
+  P.g_z = g_z; P.mean = mean; P.partials = partials;
+  P.m = m; P.nblk = ORR_STUDENT_HEAD_ROWS(m);
+  P.inv_m = 1.0f / (float)m; P.g_act = 2.0f * action_coef / (float)m; P.g_lat = 2.0f * latent_coef / (float)m;
+  hipLaunchKernelGGL(student_head_kernel, dim3((unsigned)P.nblk), dim3(256), 0, (hipStream_t)stream, P);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_history_student_head: launch", e);
   return 0;
 }
 

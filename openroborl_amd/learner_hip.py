@@ -428,15 +428,56 @@ class FusedDistillHistory(FusedDistill):
     recorded privileged rows, loss = mean over the samples of sum_j (z_j - priv_j)^2 (orr_regress_head).  FusedDistill's machinery with the
     encoder alone: only model/enc_* move into the flat buffer and take Adam steps - the actor and the critic, the teacher's, stay where and what
     they are -, two forward GEMMs, the loss head, the two products behind it, orr_relu_backward at c = 256, the layer-0 weight gradient
-    (split for minibatches of 4096 and more) and one orr_colsum_finish per minibatch; an epoch replays as one hipGraph.  One rank."""
+    (split for minibatches of 4096 and more) and one orr_colsum_finish per minibatch; an epoch replays as one hipGraph.  One rank.
+
+    action_coef > 0: loss = action_coef * mean_i sum_j (actor(obs, z)_ij - target_mean_ij)^2 + latent_coef * the loss above.  The loss head is then
+    orr_history_student_head - the frozen actor's forward pass, both losses and the backward pass down to d loss / d z in one launch, against a
+    packed copy of the actor and of the three transposes its backward pass streams (made once, and again when somebody else called the
+    model's mark_updated()) -, everything behind it is the same.  The defaults (0, 1) are the path above, launch for launch."""
     _takes_history = True
 
-    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True):
+    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, action_coef=0.0, latent_coef=1.0):
+        self.action_coef, self.latent_coef = float(action_coef), float(latent_coef)
+        if self.action_coef < 0.0 or self.latent_coef < 0.0:
+            raise ValueError("FusedDistillHistory: action_coef and latent_coef must not be negative")
+        self.head = not (self.action_coef == 0.0 and self.latent_coef == 1.0)      # orr_history_student_head instead of orr_regress_head
+        self.last_latent_loss = self.last_action_loss = None     # the means over the last update's minibatches
+        self._actor, self._actor_seen = None, None
         FusedPPO.__init__(self, student, lr=lr, adam_eps=adam_eps, minibatch=minibatch, betas=betas, use_graph=use_graph)
 
     @staticmethod
     def _trained(model):
         return sorted(k for k in model.p if k.startswith("model/enc_"))
+
+    def _graph_key(self, several):
+        return FusedDistill._graph_key(self, several) + (self.action_coef, self.latent_coef)
+
+    def _pack_actor(self):
+        """The frozen actor as orr_history_student_head reads it: its three matrices and the three transposes of the backward pass in
+        orr_policy_pack's fragments, its biases as copies, all at fixed addresses (a captured epoch replays after a re-pack)."""
+        t, L, p = self.torch, self.L, self.model.p
+        Z = _abi.POLICY_PRIV_DIM
+        w0, w1, w2 = (p["model/pi%s/w:0" % s].detach() for s in ("_fc0", "_fc1", ""))
+        if tuple(w0.shape) != (160 + Z, 512) or tuple(w1.shape) != (512, 256) or tuple(w2.shape) != (256, 12):
+            raise ValueError("FusedDistillHistory: the actor must be %d -> 512 -> 256 -> 12" % (160 + Z))
+        w2t = t.zeros(16, 256, dtype=t.float32, device=self.dev)
+        w2t[:12].copy_(w2.t())
+        src = {"w0_pi": w0, "w1_pi": w1, "w2_pi": w2, "w2t": w2t, "w1t": w1.t(), "w0zt": w0[160:].t()}
+        if self._actor is None:
+            A = {"net": _abi.OrrPolicyNet()}                  # the vf members stay NULL: they are not read
+            for name, w in src.items():
+                A[name] = t.empty(int(L.orr_policy_packed_size(int(w.shape[0]), int(w.shape[1]))), dtype=t.float32, device=self.dev)
+            for name, key in (("b0_pi", "model/pi_fc0/b:0"), ("b1_pi", "model/pi_fc1/b:0"), ("b2_pi", "model/pi/b:0")):
+                A[name] = t.empty_like(p[key].detach(), dtype=t.float32, device=self.dev)
+            for name in ("w0_pi", "b0_pi", "w1_pi", "b1_pi", "w2_pi", "b2_pi"):
+                setattr(A["net"], name, A[name].data_ptr())
+            self._actor = A
+        A = self._actor
+        for name, w in src.items():
+            w = w.to(device=self.dev, dtype=t.float32).contiguous()
+            _lib.check(L.orr_policy_pack(w.data_ptr(), int(w.shape[0]), int(w.shape[1]), A[name].data_ptr(), self._stream()), L)
+        for name, key in (("b0_pi", "model/pi_fc0/b:0"), ("b1_pi", "model/pi_fc1/b:0"), ("b2_pi", "model/pi/b:0")):
+            A[name].copy_(p[key].detach())
 
     def _plan(self, B, M):
         key = (B, M)
@@ -449,13 +490,27 @@ class FusedDistillHistory(FusedDistill):
         D, H, Z = _abi.HISTORY_DIM, 256, _abi.POLICY_PRIV_DIM
         P = {"B": B, "M": M, "nmb": B // M, "hist": f(B, D), "target": f(B, Z), "perm": t.empty(B, dtype=t.int64, device=self.dev),
              "x": f(M, D), "tgt": f(M, Z), "h": f(M, H), "z": f(M, Z), "g_z": f(M, Z), "g_h": f(M, H),
-             "stats": t.zeros(B // M, 1, dtype=t.float32, device=self.dev), "ws": f(int(self.L.orr_learner_workspace_floats(M, 64))),
+             "stats": t.zeros(B // M, 2 if self.head else 1, dtype=t.float32, device=self.dev), "ws": f(int(self.L.orr_learner_workspace_floats(M, 64))),
              "ws1": f(rows * H), "part0": f(16, D, H) if split else None, "graphs": None}
         jobs = (_abi.OrrColsumJob * 2)()
         jobs[0] = _abi.OrrColsumJob(P["ws1"].data_ptr(), self.g["model/enc_fc0/b:0"].data_ptr(), rows, H)
         if split:
             jobs[1] = _abi.OrrColsumJob(P["part0"].data_ptr(), self.g["model/enc_fc0/w:0"].data_ptr(), 16, D * H)
         P["jobs"], P["n_jobs"] = jobs, 2 if split else 1
+        if self.head:
+            # obs and the teacher's means, gathered with the same permutation; the head's partial sums (ORR_STUDENT_HEAD_PARTIAL_FLOATS) are two
+            # more jobs of the minibatch's orr_colsum_finish: the bias gradient of enc_fc1 and the two losses, which land in the minibatch's own
+            # row of stats - hence one job list per minibatch
+            hrows = _abi.student_head_rows(M)
+            P.update({"obs": f(B, 160), "tmean": f(B, 12), "xo": f(M, 160), "tm": f(M, 12), "hp": f(50 * hrows)})
+            P["jobs_s"] = []
+            for s in range(P["nmb"]):
+                js = (_abi.OrrColsumJob * 4)()
+                for j in range(P["n_jobs"]):
+                    js[j] = jobs[j]
+                js[P["n_jobs"]] = _abi.OrrColsumJob(P["hp"].data_ptr(), self.g["model/enc_fc1/b:0"].data_ptr(), hrows, Z)
+                js[P["n_jobs"] + 1] = _abi.OrrColsumJob(P["hp"].data_ptr() + 4 * Z * hrows, P["stats"][s].data_ptr(), hrows, 2)
+                P["jobs_s"].append(js)
         self._plans[key] = P
         return P
 
@@ -466,23 +521,40 @@ class FusedDistillHistory(FusedDistill):
         idx = P["perm"][s * M:(s + 1) * M]
         t.index_select(P["hist"], 0, idx, out=P["x"])
         t.index_select(P["target"], 0, idx, out=P["tgt"])
+        if self.head:
+            t.index_select(P["obs"], 0, idx, out=P["xo"])
+            t.index_select(P["tmean"], 0, idx, out=P["tm"])
         t._addmm_activation(w["model/enc_fc0/b:0"], P["x"], w["model/enc_fc0/w:0"], out=P["h"])
         t.addmm(w["model/enc_fc1/b:0"], P["h"], w["model/enc_fc1/w:0"], out=P["z"])
-        _lib.check(L.orr_regress_head(P["z"].data_ptr(), P["tgt"].data_ptr(), M, _abi.POLICY_PRIV_DIM, P["g_z"].data_ptr(),
-                                      g["model/enc_fc1/b:0"].data_ptr(), P["stats"][s].data_ptr(), P["ws"].data_ptr(), st), L)
+        if self.head:
+            A = self._actor
+            _lib.check(L.orr_history_student_head(C.byref(A["net"]), A["w2t"].data_ptr(), A["w1t"].data_ptr(), A["w0zt"].data_ptr(), P["xo"].data_ptr(),
+                                                  P["z"].data_ptr(), P["tm"].data_ptr(), P["tgt"].data_ptr(), M, self.action_coef, self.latent_coef,
+                                                  P["g_z"].data_ptr(), None, P["hp"].data_ptr(), st), L)
+        else:
+            _lib.check(L.orr_regress_head(P["z"].data_ptr(), P["tgt"].data_ptr(), M, _abi.POLICY_PRIV_DIM, P["g_z"].data_ptr(),
+                                          g["model/enc_fc1/b:0"].data_ptr(), P["stats"][s].data_ptr(), P["ws"].data_ptr(), st), L)
         t.mm(P["h"].t(), P["g_z"], out=g["model/enc_fc1/w:0"])
         t.mm(P["g_z"], w["model/enc_fc1/w:0"].t(), out=P["g_h"])
         _lib.check(L.orr_relu_backward(P["g_h"].data_ptr(), P["h"].data_ptr(), M, 256, None, P["ws1"].data_ptr(), st), L)
         self._wgrad(P["x"], P["g_h"], P["part0"], g["model/enc_fc0/w:0"])
-        _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
+        if self.head:
+            _lib.check(L.orr_colsum_finish(P["jobs_s"][s], P["n_jobs"] + 2, st), L)
+        else:
+            _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
 
-    def update(self, hist, target_priv, epochs=1, generator=None):
-        """hist [B,512], target_priv [B,48] (env.privileged_obs on the same states); returns the mean loss over the minibatches, like
-        ppo.DistillHistory.update."""
+    def update(self, hist, target_priv, epochs=1, generator=None, obs=None, target_mean=None):
+        """hist [B,512], target_priv [B,48] (env.privileged_obs on the same states); with action_coef > 0 also obs [B,160] and target_mean [B,12]
+        (the teacher's actor output on the same states).  Returns the mean total loss over the minibatches, like ppo.DistillHistory.update."""
         t = self.torch
         B = int(hist.shape[0])
         if tuple(hist.shape) != (B, _abi.HISTORY_DIM) or tuple(target_priv.shape) != (B, _abi.POLICY_PRIV_DIM):
             raise ValueError("FusedDistillHistory: hist must have shape (B, %d) and target_priv (B, %d)" % (_abi.HISTORY_DIM, _abi.POLICY_PRIV_DIM))
+        if self.action_coef > 0.0:
+            if obs is None or target_mean is None:
+                raise ValueError("FusedDistillHistory: action_coef > 0 needs obs and target_mean")
+            if tuple(obs.shape) != (B, 160) or tuple(target_mean.shape) != (B, 12):
+                raise ValueError("FusedDistillHistory: obs must have shape (%d, 160) and target_mean (%d, 12)" % (B, B))
         M = min(self.minibatch, B)
         if B % M:
             raise ValueError("FusedDistillHistory: the number of samples (%d) must be a multiple of the minibatch size (%d); "
@@ -491,10 +563,21 @@ class FusedDistillHistory(FusedDistill):
             P = self._plan(B, M)
             P["hist"].copy_(hist)
             P["target"].copy_(target_priv)
+            if self.head:
+                if self.action_coef > 0.0:
+                    P["obs"].copy_(obs)
+                    P["tmean"].copy_(target_mean)
+                elif "cleared" not in P:                    # no action loss: its inputs are multiplied by zero, they only have to be finite
+                    P["obs"].zero_()
+                    P["tmean"].zero_()
+                    P["cleared"] = True
+                seen = getattr(self.model, "updates", None)
+                if self._actor is None or seen is None or seen != self._actor_seen:
+                    self._pack_actor()
             if self.use_graph and (P["graphs"] is None or P.get("graph_key") != self._graph_key(False)):
                 self._capture(P, False)
                 P["graph_key"] = self._graph_key(False)
-            total = t.zeros(1, dtype=t.float32, device=self.dev)
+            total = t.zeros(P["stats"].shape[1], dtype=t.float32, device=self.dev)
             for _ in range(epochs):
                 P["perm"].copy_(t.randperm(B, device=self.dev, generator=generator))
                 if self.use_graph:
@@ -504,4 +587,10 @@ class FusedDistillHistory(FusedDistill):
                 total += P["stats"].sum(dim=0)
         if hasattr(self.model, "mark_updated"):
             self.model.mark_updated()
-        return float(total.item() / float(epochs * P["nmb"]))
+        self._actor_seen = getattr(self.model, "updates", None)      # the encoder's steps are this learner's own: the packed actor stands
+        total = [x / float(epochs * P["nmb"]) for x in total.tolist()]
+        if self.head:
+            self.last_action_loss, self.last_latent_loss = total
+            return self.action_coef * total[0] + self.latent_coef * total[1]
+        self.last_action_loss, self.last_latent_loss = 0.0, total[0]
+        return total[0]

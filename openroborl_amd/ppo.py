@@ -166,6 +166,7 @@ class ActorCritic(object):
 
     def mark_updated(self):
         self._fused_dirty = True
+        self.updates = getattr(self, "updates", 0) + 1      # whoever keeps a packed copy of its own compares this count (FusedDistillHistory)
 
     def _init(self, name, fan_in, fan_out, g, gain):
         t = self.torch
@@ -373,33 +374,65 @@ class Distill(object):
 class DistillHistory(object):
     """The learner of a history student's encoder in plain torch (RMA's second phase; the fp32 reference of learner_hip.FusedDistillHistory):
     encode(hist) is regressed on the recorded privileged rows, loss = mean over the samples of sum_j (z_j - priv_j)^2.  Only model/enc_* train;
-    the actor and the critic - the teacher's - are not touched and have no optimiser state."""
+    the actor and the critic - the teacher's - are not touched and have no optimiser state.
 
-    def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096):
+    action_coef > 0 adds the action loss ("Learning quadrupedal locomotion over challenging terrain": action imitation next to the latent
+    regression): loss = action_coef * mean_i sum_j (actor(obs, encode(hist))_ij - target_mean_ij)^2 + latent_coef * the loss above, the
+    gradient flowing through the frozen actor into the encoder.  update() then takes obs and the teacher's means as well.  The defaults
+    (0, 1) are the latent regression alone, by the code path it always had."""
+
+    def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096, action_coef=0.0, latent_coef=1.0):
         import torch
         self.torch = torch
         if not getattr(student, "history", 0):
             raise ValueError("DistillHistory: the student needs a history encoder (ActorCritic(history=16))")
         self.model = student
         self.minibatch = int(minibatch)
+        self.action_coef, self.latent_coef = float(action_coef), float(latent_coef)
+        if self.action_coef < 0.0 or self.latent_coef < 0.0:
+            raise ValueError("DistillHistory: action_coef and latent_coef must not be negative")
+        self.last_latent_loss = self.last_action_loss = None     # the means over the last update's minibatches
         params = [student.p[k] for k in sorted(student.p) if k.startswith("model/enc_")]
+        self.params = params
         self.opt = torch.optim.Adam(params, lr=lr, eps=adam_eps, fused=bool(params and params[0].is_cuda))
 
-    def update(self, hist, target_priv, epochs=1, generator=None):
-        """hist [B,512], target_priv [B,48] (env.privileged_obs on the same states); returns the mean loss over the minibatches."""
+    def update(self, hist, target_priv, epochs=1, generator=None, obs=None, target_mean=None):
+        """hist [B,512], target_priv [B,48] (env.privileged_obs on the same states); with action_coef > 0 also obs [B,160] and target_mean [B,12]
+        (the teacher's actor output on the same states).  Returns the mean total loss over the minibatches."""
         t = self.torch
         B = hist.shape[0]
-        stats = []
+        plain = self.action_coef == 0.0 and self.latent_coef == 1.0
+        if self.action_coef > 0.0:
+            if obs is None or target_mean is None:
+                raise ValueError("DistillHistory: action_coef > 0 needs obs and target_mean")
+            if tuple(obs.shape) != (B, 160) or tuple(target_mean.shape) != (B, 12):
+                raise ValueError("DistillHistory: obs must have shape (%d, 160) and target_mean (%d, 12)" % (B, B))
+        stats, lat, act = [], [], []
         for _ in range(epochs):
             perm = t.randperm(B, device=hist.device, generator=generator)
             hist_p, tgt_p = hist[perm], target_priv[perm]
+            if self.action_coef > 0.0:
+                obs_p, mean_p = obs[perm], target_mean[perm]
             for s in range(0, B, self.minibatch):
                 e = s + self.minibatch
-                loss = ((self.model.encode(hist_p[s:e]) - tgt_p[s:e]) ** 2).sum(dim=1).mean()
                 self.opt.zero_grad(set_to_none=True)
-                loss.backward()
+                if self.action_coef > 0.0:      # z feeds the frozen actor as well: model.mean(obs, hist=hist) with the one encode() shared
+                    z = self.model.encode(hist_p[s:e])
+                    latent = ((z - tgt_p[s:e]) ** 2).sum(dim=1).mean()
+                    action = ((self.model.mean(obs_p[s:e], priv=z) - mean_p[s:e]) ** 2).sum(dim=1).mean()
+                    loss = self.action_coef * action + self.latent_coef * latent
+                    act.append(action.detach())
+                    for p, g in zip(self.params, t.autograd.grad(loss, self.params)):      # the encoder's gradients only: the actor keeps none
+                        p.grad = g
+                else:
+                    latent = ((self.model.encode(hist_p[s:e]) - tgt_p[s:e]) ** 2).sum(dim=1).mean()
+                    loss = latent if plain else self.latent_coef * latent
+                    loss.backward()
                 self.opt.step()
                 if hasattr(self.model, "mark_updated"):
                     self.model.mark_updated()
                 stats.append(loss.detach())
+                lat.append(latent.detach())
+        self.last_latent_loss = float(t.stack(lat).mean())
+        self.last_action_loss = float(t.stack(act).mean()) if act else 0.0
         return float(t.stack(stats).mean())

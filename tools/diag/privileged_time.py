@@ -1,7 +1,7 @@
 """The privileged critic's two kernels against what they sit next to, 4096 robots, same process, alternated (the protocol of
 tools/diag/variant_time.py: medians of 5 x 300 back-to-back launches, every candidate sees the same clocks; the 300 launches are one
 captured graph, so that no host time sits between them):
-python tools/diag/privileged_time.py [--alt-policy-lib PATH]
+python tools/diag/privileged_time.py [--alt-policy-lib PATH] [--sections forward,history,row,head]
 
   forward   orr_policy_forward_priv, orr_policy_forward_teacher and orr_policy_forward_teacher with value = NULL (the labelling call of
             distillation: no critic) against orr_policy_forward, random weights; with --alt-policy-lib also orr_policy_forward_priv of a
@@ -10,7 +10,11 @@ python tools/diag/privileged_time.py [--alt-policy-lib PATH]
   history   orr_policy_forward_history (a history student: the encoder 512 -> 256 -> 48 in front of the teacher's pass) against
             orr_policy_forward_teacher, each with and without a value buffer, and orr_history_push per launch (out of place, no resets)
   row       orr_privileged_obs with contact and push outputs bound against the env step of the same env (train mode, randomiser, pushes
-            at prob 0.02)"""
+            at prob 0.02)
+  head      orr_history_student_head at m = 16384 (a history student's action loss: forward through the frozen actor, both losses, backward
+            to the latent, one launch) against the same mathematics composed from the older pieces on the same inputs: three torch GEMMs
+            with bias / ReLU epilogues, orr_distill_head, orr_head_backward, two torch GEMMs with orr_relu_backward between them,
+            orr_regress_head and the sum of the two gradients; and against orr_regress_head alone (the latent loss without the action loss)"""
 import argparse
 import ctypes as C
 import sys
@@ -25,7 +29,9 @@ N, WARMUP, ROUNDS, LAUNCHES = 4096, 300, 5, 300
 
 ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
 ap.add_argument("--alt-policy-lib", default="")
+ap.add_argument("--sections", default="forward,history,row,head")
 args = ap.parse_args()
+sections = args.sections.split(",")
 dev = torch.device("cuda", 0)
 
 
@@ -92,37 +98,92 @@ if args.alt_policy_lib:
         assert rc == 0
     names.append("orr_policy_forward_priv, --alt-policy-lib")
     fns.append(run_alt)
-med = report(names, fns)
-# MFMAs per wave: 1728 plain, 1824 with the critic's 13th k-group pair (+96), 1920 with the actor's too (+96); 992 without the critic
-print("orr_policy_forward_teacher against orr_policy_forward_priv: %+.2f %% (the MFMA counts give %+.2f %%)" % (100.0 * (med[2] / med[1] - 1.0), 100.0 * 96 / 1824))
-print("orr_policy_forward_teacher, value = NULL against orr_policy_forward_teacher: ratio %.4f (the MFMA counts give %.4f)" % (med[3] / med[2], 992.0 / 1920.0))
-if args.alt_policy_lib:
-    fns[1](); run_alt(); torch.cuda.synchronize()
-    print("the two builds' values are equal bit for bit: %s" % bool(torch.equal(val, val_alt)))
+if "forward" in sections:
+    med = report(names, fns)
+    # MFMAs per wave: 1728 plain, 1824 with the critic's 13th k-group pair (+96), 1920 with the actor's too (+96); 992 without the critic
+    print("orr_policy_forward_teacher against orr_policy_forward_priv: %+.2f %% (the MFMA counts give %+.2f %%)" % (100.0 * (med[2] / med[1] - 1.0), 100.0 * 96 / 1824))
+    print("orr_policy_forward_teacher, value = NULL against orr_policy_forward_teacher: ratio %.4f (the MFMA counts give %.4f)" % (med[3] / med[2], 992.0 / 1920.0))
+    if args.alt_policy_lib:
+        fns[1](); run_alt(); torch.cuda.synchronize()
+        print("the two builds' values are equal bit for bit: %s" % bool(torch.equal(val, val_alt)))
 
 # ---- history ----
-student = ppo.ActorCritic(dev, seed=3, priv_dim=_abi.POLICY_PRIV_DIM, actor_priv_dim=_abi.POLICY_PRIV_DIM, history=_abi.HISTORY_STEPS)
-fh = policy_hip.FusedActorCritic(student.p, dev, std=0.125)
-hist, hist2 = torch.randn(N, _abi.HISTORY_DIM, device=dev, generator=g), torch.empty(N, _abi.HISTORY_DIM, device=dev)
-done = torch.zeros(N, dtype=torch.uint8, device=dev)
-med = report(["orr_policy_forward_teacher", "orr_policy_forward_teacher, value = NULL", "orr_policy_forward_history", "orr_policy_forward_history, value = NULL",
-              "orr_history_push"],
-             [fns[2], fns[3], lambda: fh.forward(obs, noise, out_action=act, out_raw=raw, out_value=val, hist=hist),
-              lambda: fh.forward(obs, None, out_action=act, out_raw=raw, out_mean=mean, want_value=False, hist=hist),
-              lambda: policy_hip.history_push(obs, done, hist, hist2)])
-# MFMAs per wave: the encoder adds 512 (layer 0) + 64 (layer 1, on three of the four waves) to the teacher's 1920, or 992 without the critic
-print("orr_policy_forward_history against orr_policy_forward_teacher: ratio %.4f (the MFMA counts give %.4f)" % (med[2] / med[0], (1920.0 + 576.0) / 1920.0))
-print("the same with value = NULL: ratio %.4f (the MFMA counts give %.4f)" % (med[3] / med[1], (992.0 + 576.0) / 992.0))
+if "history" in sections:
+    student = ppo.ActorCritic(dev, seed=3, priv_dim=_abi.POLICY_PRIV_DIM, actor_priv_dim=_abi.POLICY_PRIV_DIM, history=_abi.HISTORY_STEPS)
+    fh = policy_hip.FusedActorCritic(student.p, dev, std=0.125)
+    hist, hist2 = torch.randn(N, _abi.HISTORY_DIM, device=dev, generator=g), torch.empty(N, _abi.HISTORY_DIM, device=dev)
+    done = torch.zeros(N, dtype=torch.uint8, device=dev)
+    med = report(["orr_policy_forward_teacher", "orr_policy_forward_teacher, value = NULL", "orr_policy_forward_history", "orr_policy_forward_history, value = NULL",
+                  "orr_history_push"],
+                 [fns[2], fns[3], lambda: fh.forward(obs, noise, out_action=act, out_raw=raw, out_value=val, hist=hist),
+                  lambda: fh.forward(obs, None, out_action=act, out_raw=raw, out_mean=mean, want_value=False, hist=hist),
+                  lambda: policy_hip.history_push(obs, done, hist, hist2)])
+    # MFMAs per wave: the encoder adds 512 (layer 0) + 64 (layer 1, on three of the four waves) to the teacher's 1920, or 992 without the critic
+    print("orr_policy_forward_history against orr_policy_forward_teacher: ratio %.4f (the MFMA counts give %.4f)" % (med[2] / med[0], (1920.0 + 576.0) / 1920.0))
+    print("the same with value = NULL: ratio %.4f (the MFMA counts give %.4f)" % (med[3] / med[1], (992.0 + 576.0) / 992.0))
 
 # ---- row ----
-env = VecQuadrupedEnv(task_name="imitation_learning_laikago", num_robot=N, mode="train", auto_reset=True, seed=7, contact_outputs=True,
-                      push=dict(prob=0.02, lin_vel=(0.2, 0.6), lin_vel_z=0.2, ang_vel=0.5), push_outputs=True)
-o = env.reset()
-a = torch.empty(N, 12, device=dev)
-for k in range(WARMUP):
-    env.stress_actions(o, torch.randn(N, 12, device=dev, generator=g) * 0.125, a)
-    o, r, d, _ = env.step(a)
-rows = torch.empty(N, _abi.PRIV_DIM, device=dev)
-report(["env step (push variant, contact + push outputs)", "orr_privileged_obs"],
-       [lambda: env.step_into(a, env.obs, env.reward, env.done), lambda: env.privileged_obs(out=rows, done=env.done)])
-env.close()
+if "row" in sections:
+    env = VecQuadrupedEnv(task_name="imitation_learning_laikago", num_robot=N, mode="train", auto_reset=True, seed=7, contact_outputs=True,
+                          push=dict(prob=0.02, lin_vel=(0.2, 0.6), lin_vel_z=0.2, ang_vel=0.5), push_outputs=True)
+    o = env.reset()
+    a = torch.empty(N, 12, device=dev)
+    for k in range(WARMUP):
+        env.stress_actions(o, torch.randn(N, 12, device=dev, generator=g) * 0.125, a)
+        o, r, d, _ = env.step(a)
+    rows = torch.empty(N, _abi.PRIV_DIM, device=dev)
+    report(["env step (push variant, contact + push outputs)", "orr_privileged_obs"],
+           [lambda: env.step_into(a, env.obs, env.reward, env.done), lambda: env.privileged_obs(out=rows, done=env.done)])
+    env.close()
+
+# ---- head ----
+if "head" in sections:
+    from openroborl_amd import _lib  # noqa: E402
+    M, Z = 16384, _abi.POLICY_PRIV_DIM
+    L = ft.L
+    st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)   # noqa: E731
+    w = {k: v.detach() for k, v in teacher.p.items()}
+    w0, b0, w1, b1, w2, b2 = (w["model/pi%s/%s:0" % (s, x)] for s in ("_fc0", "_fc1", "") for x in ("w", "b"))
+    w2t_pad = torch.zeros(16, 256, device=dev)
+    w2t_pad[:12] = w2.t()
+    packed = []
+    for src in (w2t_pad, w1.t().contiguous(), w0[160:].t().contiguous()):
+        out = torch.empty(int(L.orr_policy_packed_size(src.shape[0], src.shape[1])), device=dev)
+        _lib.check(L.orr_policy_pack(src.data_ptr(), src.shape[0], src.shape[1], out.data_ptr(), st()), L)
+        packed.append(out)
+    xo, z, tm, tp = (torch.randn(M, c, device=dev, generator=g) for c in (160, Z, 12, Z))
+    g_z, hp = torch.empty(M, Z, device=dev), torch.empty(50 * _abi.student_head_rows(M), device=dev)
+    a_c, l_c = 1.0, 0.5
+
+    def fused_head():
+        _lib.check(L.orr_history_student_head(C.byref(ft.net), packed[0].data_ptr(), packed[1].data_ptr(), packed[2].data_ptr(), xo.data_ptr(), z.data_ptr(),
+                                              tm.data_ptr(), tp.data_ptr(), M, a_c, l_c, g_z.data_ptr(), None, hp.data_ptr(), st()), L)
+    # the composition: what the parent commit's pieces need for the same g_z (coefficients folded into two elementwise launches at the end)
+    xin, h1, h2, y = (torch.empty(M, c, device=dev) for c in (160 + Z, 512, 256, 12))
+    g_y, gz2, gh1, gin, g_lat, g_ref = (torch.empty(M, c, device=dev) for c in (12, 256, 512, Z, Z, Z))
+    gb12, gb48, stats = torch.empty(12, device=dev), torch.empty(Z, device=dev), torch.empty(2, device=dev)
+    ws, ws2, ws1 = (torch.empty(int(L.orr_learner_workspace_floats(M, c)), device=dev) for c in (64, 256, 512))
+    w1t, w0zt = w1.t(), w0[160:].t()
+
+    def composed():
+        torch.cat((xo, z), dim=1, out=xin)
+        torch._addmm_activation(b0, xin, w0, out=h1)
+        torch._addmm_activation(b1, h1, w1, out=h2)
+        torch.addmm(b2, h2, w2, out=y)
+        _lib.check(L.orr_distill_head(y.data_ptr(), tm.data_ptr(), M, g_y.data_ptr(), gb12.data_ptr(), stats.data_ptr(), ws.data_ptr(), st()), L)
+        _lib.check(L.orr_head_backward(g_y.data_ptr(), 12, w2.data_ptr(), h2.data_ptr(), M, 256, gz2.data_ptr(), None, None, ws2.data_ptr(), st()), L)
+        torch.mm(gz2, w1t, out=gh1)
+        _lib.check(L.orr_relu_backward(gh1.data_ptr(), h1.data_ptr(), M, 512, None, ws1.data_ptr(), st()), L)
+        torch.mm(gh1, w0zt, out=gin)
+        _lib.check(L.orr_regress_head(z.data_ptr(), tp.data_ptr(), M, Z, g_lat.data_ptr(), gb48.data_ptr(), stats[1:].data_ptr(), ws.data_ptr(), st()), L)
+        torch.add(gin * a_c, g_lat, alpha=l_c, out=g_ref)
+
+    def regress_alone():
+        _lib.check(L.orr_regress_head(z.data_ptr(), tp.data_ptr(), M, Z, g_lat.data_ptr(), gb48.data_ptr(), stats[1:].data_ptr(), ws.data_ptr(), st()), L)
+    fused_head(); composed(); torch.cuda.synchronize()
+    scale = float(g_ref.abs().max())
+    print("m = %d: the fused launch and the composition agree to %.2e of the gradient's scale" % (M, float((g_z - g_ref).abs().max()) / scale))
+    med = report(["the composition (5 GEMMs + 5 launches + 3 elementwise)", "orr_history_student_head", "orr_regress_head alone"], [composed, fused_head, regress_alone])
+    # MFMAs per wave and tile of 16 rows: 416 + 512 + 64 forward, 16 + 512 + 128 backward = 1648; the teacher's full forward pass 1920
+    print("orr_history_student_head: %d workgroups of 1648 MFMAs per wave in %.4f ms; orr_policy_forward_teacher: 256 workgroups of 1920 (section forward)"
+          % (M // 16, med[1]))

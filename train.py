@@ -80,6 +80,12 @@ def main():
                          "sensors (IMU, last action, motor angles: 512 words), trained to estimate the privileged observation from them "
                          "(learner_hip.FusedDistillHistory; --torch-learner: ppo.DistillHistory).  The log carries latent_loss; --save writes "
                          "the teacher's variables + model/enc_*, a zip that loads here (--eval) and not in the reference")
+    ap.add_argument("--distill-action-coef", type=float, default=0.0, metavar="C",
+                    help="--distill --history: weight of the action loss, the squared error of the student's actor output on (observation, "
+                         "encoder output) against the teacher's mean, its gradient flowing through the frozen actor into the encoder "
+                         "(orr_history_student_head).  The log then carries action_loss next to latent_loss.  Default 0: the latent regression alone")
+    ap.add_argument("--distill-latent-coef", type=float, default=1.0, metavar="C",
+                    help="--distill --history: weight of the latent regression (default 1)")
     ap.add_argument("--distill-beta", type=float, default=0.0,
                     help="--distill: the share of robots that are stepped with the teacher's action instead of the student's (default 0)")
     ap.add_argument("--distill-beta-iters", type=int, default=0, help="--distill: decay --distill-beta linearly to 0 over this many iterations (0: constant)")
@@ -116,6 +122,10 @@ def main():
         raise SystemExit("train.py: --distill trains a plain student with the fused rollout; not with --privileged-critic / --privileged-actor / --torch-policy")
     if args.history and not args.distill:
         raise SystemExit("train.py: --history belongs to --distill")
+    if (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0) and not args.history:
+        raise SystemExit("train.py: --distill-action-coef / --distill-latent-coef belong to --distill --history")
+    if args.distill_action_coef < 0.0 or args.distill_latent_coef < 0.0:
+        raise SystemExit("train.py: --distill-action-coef / --distill-latent-coef must not be negative")
     privileged = args.privileged_critic or bool(args.distill)       # somebody reads env.privileged_obs
     rank, world, local = odist.init_from_env()
     if args.distill and world > 1:
@@ -244,12 +254,14 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
     teacher = ppo.ActorCritic(dev, params=teacher_params).enable_fused()
     B = args.num_robot * args.horizon
     loss_name = "latent_loss" if args.history else "distill_loss"
+    coefs = dict(action_coef=args.distill_action_coef, latent_coef=args.distill_latent_coef) if args.history else {}
+    with_actions = args.history and (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0)      # the log carries both losses
     if args.torch_learner:
-        learner = (ppo.DistillHistory if args.history else ppo.Distill)(student, lr=args.lr, minibatch=args.minibatch)
+        learner = (ppo.DistillHistory if args.history else ppo.Distill)(student, lr=args.lr, minibatch=args.minibatch, **coefs)
     else:
         from openroborl_amd import learner_hip
         cls = learner_hip.FusedDistillHistory if args.history else learner_hip.FusedDistill
-        learner = cls(student, lr=args.lr, minibatch=cls.fit_minibatch(B, args.minibatch))
+        learner = cls(student, lr=args.lr, minibatch=cls.fit_minibatch(B, args.minibatch), **coefs)
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed * 1000)
     collector = rollout.GraphRollout(env, student, args.horizon, teacher=teacher)
@@ -262,7 +274,10 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
         collector.teacher_mask[:driven] = 1
         buf = collector.collect(obs, generator=gen, priv=priv, hist=hist)
         obs, priv, hist = buf["last_obs"], buf["last_priv"], buf.get("last_hist")
-        if args.history:
+        if args.history and args.distill_action_coef > 0.0:
+            loss = learner.update(buf["hist"].reshape(B, -1), buf["priv"].reshape(B, -1), epochs=args.epochs, generator=gen,
+                                  obs=buf["obs"].reshape(B, -1), target_mean=buf["teacher_mean"].reshape(B, 12))
+        elif args.history:
             loss = learner.update(buf["hist"].reshape(B, -1), buf["priv"].reshape(B, -1), epochs=args.epochs, generator=gen)
         else:
             loss = learner.update(buf["obs"].reshape(B, -1), buf["teacher_mean"].reshape(B, 12), epochs=args.epochs, generator=gen)
@@ -272,6 +287,9 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
                    "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2), "episodes": stats.sums[0],
                    loss_name: round(float(loss), 6), "teacher_driven": driven}
+            if with_actions:             # loss_name then holds the latent regression's own loss, as it does without the action loss
+                rec.update({"latent_loss": round(learner.last_latent_loss, 6), "action_loss": round(learner.last_action_loss, 6),
+                            "total_loss": round(float(loss), 6)})
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if args.save:
