@@ -7,6 +7,8 @@
  * autograd graph spends around them - ~70 elementwise / reduction launches per minibatch, more time than the GEMMs themselves - is
  * these launches:
  *   orr_ppo_head       loss terms, d loss / d mean, d loss / d value, bias gradients of the two output layers
+ *   orr_ppo_head_logstd  that head for a learned per-dimension log-std read from the device: + its gradient, the entropy bonus, approx-KL, clip fraction
+ *   orr_gauss_prepare  the sampler's half of a learned std: noise scaled by exp(log_std) and its log-probability, a whole rollout segment per launch
  *   orr_distill_head   the loss head of policy distillation instead: squared error of the actor's mean against a teacher's, its gradient
  *   orr_regress_head   the loss head of a history student's encoder: squared error of its 48 outputs against the privileged row, its gradient
  *   orr_history_student_head  that head with the action loss: forward through the frozen actor, both losses, backward to the latent, one launch
@@ -48,6 +50,30 @@ int32_t orr_learner_partial_rows(int32_t m);
  *   stats [2]                   surrogate, value loss (means over the minibatch) */
 int32_t orr_ppo_head(const float* mean, const float* value, const float* batch, int32_t m, float std, float clip, float vf_coef,
                      float* g_mean, float* g_value, float* gb_mean, float* gb_value, float* stats, float* workspace, void* stream);
+
+/* orr_ppo_head for a learned, state-independent std: the twelve log-stds (model/pi/logstd:0; the reference declares pi/logstd and freezes it,
+ * agents/imitation_policies.py:48) are read from the device at run time, so a captured launch follows them as Adam moves them.
+ *   z_k = (a_k - mean_k) exp(-log_std_k),  logp = -1/2 sum_k z_k^2 - sum_k log_std_k - 6 log(2 pi);  ratio, clip and surrogate as orr_ppo_head
+ *   loss = surrogate + vf_coef * value loss - ent_coef * H,  H = sum_k log_std_k + 6 log(2 pi e)    (pol_entpen, agents/ppo_imitation.py:196-210)
+ *   mean, value, batch, m, g_mean, g_value, gb_mean, gb_value, the alignment: orr_ppo_head's
+ *   log_std [12]     device memory, 4-byte aligned (e.g. the parameter's slot in a flat buffer)
+ *   g_logstd [12]    d loss / d log_std: the sum over the samples of (d loss / d logp) (z_k^2 - 1), and - ent_coef once
+ *   stats [5]        surrogate, value loss, H, approx_kl = mean((ratio - 1) - log ratio), clip_fraction = mean(ratio < 1 - c or ratio > 1 + c)
+ *   workspace        orr_learner_workspace_floats(m, 32) floats suffice (32 partial sums per workgroup, added in a fixed order)
+ * A refused call launches and writes nothing. */
+int32_t orr_ppo_head_logstd(const float* mean, const float* value, const float* batch, const float* log_std, int32_t m, float clip, float vf_coef,
+                            float ent_coef, float* g_mean, float* g_value, float* g_logstd, float* gb_mean, float* gb_value, float* stats,
+                            float* workspace, void* stream);
+
+/* The sampler's half of a learned std, for n rows in one launch (a whole rollout segment: n = T N):
+ *   scaled[i][j] = exp(log_std[j]) * noise[i][j]
+ *   logp[i]      = -1/2 sum_j noise[i][j]^2 - sum_j log_std[j] - 6 log(2 pi)      the log-probability of mean + scaled[i] under the sampling policy
+ * The forward passes of openroborl_policy.h are then called with noise = scaled and std = 1: mean + 1 * x is mean + x, bit for bit.
+ *   noise [n][12], scaled [n][12]   16-byte aligned; scaled may be noise itself (in place) and must not overlap it otherwise
+ *   log_std [12]                    device memory, 4-byte aligned, read at run time
+ *   logp [n] | NULL                 NULL: only scaled is written
+ * A refused call launches and writes nothing. */
+int32_t orr_gauss_prepare(const float* noise, const float* log_std, float* scaled, float* logp, int32_t n, void* stream);
 
 /* Loss head of policy distillation for a minibatch of m samples: the student's means against a teacher's (DAgger labels; host side:
  * learner_hip.FusedDistill).  loss = (1 / m) sum_i sum_j (mean[i][j] - target[i][j])^2, j over the 12 actions.

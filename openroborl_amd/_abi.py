@@ -219,6 +219,14 @@ REGRESS_HEAD_ARGS = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C
 #   float* partials [student_head_rows(m)][48] + [rows][2], void* stream)
 HISTORY_STUDENT_HEAD_ARGS = [C.POINTER(OrrPolicyNet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                              C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_ppo_head_logstd(const float* mean [m][12], const float* value [m], const float* batch [m][16],
+#   const float* log_std [12] (device), int32_t m, float clip, float vf_coef, float ent_coef, float* g_mean [m][12], float* g_value [m],
+#   float* g_logstd [12], float* gb_mean [12], float* gb_value [1], float* stats [5], float* workspace, void* stream)
+PPO_HEAD_LOGSTD_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_gauss_prepare(const float* noise [n][12], const float* log_std [12] (device), float* scaled [n][12],
+#   float* logp [n] | NULL, int32_t n, void* stream)
+GAUSS_PREPARE_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
 def student_head_rows(m):

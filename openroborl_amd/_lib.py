@@ -107,7 +107,7 @@ EXPORTS = [
     "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_set_push", "orr_sizeof_push", "orr_bind_push_outputs", "orr_privileged_obs", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_history", "orr_history_push", "orr_gae", "orr_gae_flags",
-    "orr_learner_workspace_floats", "orr_ppo_head", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
+    "orr_learner_workspace_floats", "orr_ppo_head", "orr_ppo_head_logstd", "orr_gauss_prepare", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
 ]
 
 
@@ -340,6 +340,10 @@ def load():
     L.orr_learner_workspace_floats.argtypes = [C.c_int32, C.c_int32]
     L.orr_ppo_head.restype = C.c_int32
     L.orr_ppo_head.argtypes = [vp, vp, vp, C.c_int32, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    L.orr_ppo_head_logstd.restype = C.c_int32
+    L.orr_ppo_head_logstd.argtypes = _abi.PPO_HEAD_LOGSTD_ARGS
+    L.orr_gauss_prepare.restype = C.c_int32
+    L.orr_gauss_prepare.argtypes = _abi.GAUSS_PREPARE_ARGS
     L.orr_distill_head.restype = C.c_int32
     L.orr_distill_head.argtypes = _abi.DISTILL_HEAD_ARGS
     L.orr_regress_head.restype = C.c_int32

@@ -96,6 +96,128 @@ __global__ __launch_bounds__(64) void ppo_head_finish_kernel(const float* __rest
   }
 }
 
+// ---- loss head with a learned, state-independent log-std (orr_ppo_head_logstd): ppo_head_kernel with a per-dimension std read from the
+// device, the entropy bonus and the two diagnostics.  Partials [block][32]: 0..11 the actor's bias gradient, 12 the critic's, 13 surrogate,
+// 14 value loss, 15 (r - 1) - log r, 16 clipped samples, 17..28 d surrogate / d log_std, 29..31 zero.
+constexpr int kLsCols = 32;
+constexpr int kLsUsed = 29;
+constexpr double kLog2Pi = 1.8378770664093454836;
+// The log-density's constant - sum_k log_std_k - 6 log(2 pi): twelve uniform values of ~-2 each, so a float sum would carry the rounding of a
+// ~25 into every sample's ratio; summed in double (twelve adds per thread) it is one rounding of the result.
+__device__ inline float log_norm_of(const float* __restrict__ log_std) {
+  double s = 6.0 * kLog2Pi;
+#pragma unroll
+  for (int k = 0; k < kAct; k++) s += (double)log_std[k];
+  return (float)-s;
+}
+
+__global__ __launch_bounds__(kThreads) void ppo_head_logstd_kernel(const float* __restrict__ mean, const float* __restrict__ value,
+                                                                   const float* __restrict__ batch, const float* __restrict__ log_std, int M,
+                                                                   float clip, float vf_coef, float inv_m, float* __restrict__ g_mean,
+                                                                   float* __restrict__ g_value, float* __restrict__ partials) {
+  __shared__ float red[kThreads / 64][kLsCols];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  float acc[kLsUsed];
+#pragma unroll
+  for (int k = 0; k < kLsUsed; k++) acc[k] = 0.0f;
+  if (i < M) {
+    float inv_std[kAct];
+#pragma unroll
+    for (int k = 0; k < kAct; k++) inv_std[k] = expf(-log_std[k]);
+    const float log_norm = log_norm_of(log_std);
+    const f4* b4 = reinterpret_cast<const f4*>(batch + (size_t)i * ORR_PPO_BATCH_COLS);
+    const f4* m4 = reinterpret_cast<const f4*>(mean + (size_t)i * kAct);
+    const f4 a0 = b4[0], a1 = b4[1], a2 = b4[2], rest = b4[3];
+    const f4 m0 = m4[0], m1 = m4[1], m2 = m4[2];
+    const float d[kAct] = {a0.x - m0.x, a0.y - m0.y, a0.z - m0.z, a0.w - m0.w, a1.x - m1.x, a1.y - m1.y, a1.z - m1.z, a1.w - m1.w,
+                           a2.x - m2.x, a2.y - m2.y, a2.z - m2.z, a2.w - m2.w};
+    float z[kAct], sq = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kAct; k++) { z[k] = d[k] * inv_std[k]; sq += z[k] * z[k]; }
+    const float old_logp = rest.x, A = rest.y, ret = rest.z;
+    const float logp = -0.5f * sq + log_norm;
+    const float log_ratio = logp - old_logp;
+    const float ratio = expf(log_ratio);
+    const float lo = 1.0f - clip, hi = 1.0f + clip;
+    const float s1 = ratio * A, s2 = fminf(fmaxf(ratio, lo), hi) * A;
+    const bool inside = ratio >= lo && ratio <= hi;
+    const float dr = (inside || s1 < s2) ? -A : 0.0f;
+    const float gl = dr * ratio * inv_m;                      // d loss / d logp
+    float gm[kAct];
+#pragma unroll
+    for (int k = 0; k < kAct; k++) {
+      gm[k] = gl * z[k] * inv_std[k];
+      acc[k] = gm[k];
+      acc[17 + k] = gl * (z[k] * z[k] - 1.0f);                // d logp / d log_std_k = z_k^2 - 1
+    }
+    f4* o4 = reinterpret_cast<f4*>(g_mean + (size_t)i * kAct);
+    o4[0] = f4{gm[0], gm[1], gm[2], gm[3]}; o4[1] = f4{gm[4], gm[5], gm[6], gm[7]}; o4[2] = f4{gm[8], gm[9], gm[10], gm[11]};
+    const float dv = value[i] - ret;
+    const float gv = vf_coef * 2.0f * dv * inv_m;
+    g_value[i] = gv;
+    acc[12] = gv; acc[13] = -fminf(s1, s2); acc[14] = dv * dv;
+    acc[15] = (ratio - 1.0f) - log_ratio; acc[16] = inside ? 0.0f : 1.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < kLsUsed; k++) {
+    const float s = wave_sum(acc[k]);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kLsCols)
+    partials[(size_t)blockIdx.x * kLsCols + threadIdx.x] =
+        threadIdx.x < kLsUsed ? (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]) : 0.0f;
+}
+
+__global__ __launch_bounds__(4 * kLsCols) void ppo_head_logstd_finish_kernel(const float* __restrict__ partials, int nblk, float m, float ent_coef,
+                                                                             const float* __restrict__ log_std, float* __restrict__ gb_mean,
+                                                                             float* __restrict__ gb_value, float* __restrict__ g_logstd,
+                                                                             float* __restrict__ stats) {
+  // 32 columns x 4 interleaved row groups, combined in a fixed order
+  __shared__ float red[4][kLsCols];
+  const int col = threadIdx.x & (kLsCols - 1), part = threadIdx.x / kLsCols;
+  float s = 0.0f;
+  for (int b = part; b < nblk; b += 4) s += partials[(size_t)b * kLsCols + col];
+  red[part][col] = s;
+  __syncthreads();
+  if (part == 0) {
+    const float t = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
+    const float inv_m = 1.0f / m;
+    if (col < kAct) gb_mean[col] = t;
+    else if (col == 12) gb_value[0] = t;
+    else if (col == 13) stats[0] = t * inv_m;
+    else if (col == 14) stats[1] = t * inv_m;
+    else if (col == 15) stats[3] = t * inv_m;
+    else if (col == 16) stats[4] = t / m;                     // a count over m: the nearest float to the fraction
+    else if (col < 17 + kAct) g_logstd[col - 17] = t - ent_coef;   // - ent_coef dH / d log_std_k, once
+    else if (col == 29) {                                     // H = sum_k log_std_k + 6 log(2 pi e)
+      stats[2] = 6.0f - log_norm_of(log_std);
+    }
+  }
+}
+
+// ---- the sampler's half of a learned std (orr_gauss_prepare): one thread per row of 12, three 16-byte accesses each way.  A thread reads
+// its whole row before it writes it, so scaled may be noise itself (hence no __restrict__ on the two).
+__global__ __launch_bounds__(kThreads) void gauss_prepare_kernel(const float* noise, const float* __restrict__ log_std, float* scaled,
+                                                                 float* __restrict__ logp, long long n) {
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  float sd[kAct];
+#pragma unroll
+  for (int k = 0; k < kAct; k++) sd[k] = expf(log_std[k]);
+  const f4* x4 = reinterpret_cast<const f4*>(noise + i * kAct);
+  const f4 x0 = x4[0], x1 = x4[1], x2 = x4[2];
+  f4* o4 = reinterpret_cast<f4*>(scaled + i * kAct);
+  o4[0] = f4{sd[0] * x0.x, sd[1] * x0.y, sd[2] * x0.z, sd[3] * x0.w};
+  o4[1] = f4{sd[4] * x1.x, sd[5] * x1.y, sd[6] * x1.z, sd[7] * x1.w};
+  o4[2] = f4{sd[8] * x2.x, sd[9] * x2.y, sd[10] * x2.z, sd[11] * x2.w};
+  if (logp) {
+    const float sq = ((x0.x * x0.x + x0.y * x0.y) + (x0.z * x0.z + x0.w * x0.w)) + ((x1.x * x1.x + x1.y * x1.y) + (x1.z * x1.z + x1.w * x1.w)) +
+                     ((x2.x * x2.x + x2.y * x2.y) + (x2.z * x2.z + x2.w * x2.w));
+    logp[i] = -0.5f * sq + log_norm_of(log_std);
+  }
+}
+
 // ---- distillation loss head: one thread per sample, the same partials layout (columns 0..11 the bias gradient, 12 the squared error) --------
 __global__ __launch_bounds__(kThreads) void distill_head_kernel(const float* __restrict__ mean, const float* __restrict__ target, int M, float inv_m,
                                                                 float* __restrict__ g_mean, float* __restrict__ partials) {
@@ -390,6 +512,39 @@ int32_t orr_ppo_head(const float* mean, const float* value, const float* batch, 
   hipLaunchKernelGGL(ppo_head_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, nblk, 1.0f / (float)m, gb_mean, gb_value, stats);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_ppo_head: launch", e);
+  return 0;
+}
+
+int32_t orr_ppo_head_logstd(const float* mean, const float* value, const float* batch, const float* log_std, int32_t m, float clip, float vf_coef,
+                            float ent_coef, float* g_mean, float* g_value, float* g_logstd, float* gb_mean, float* gb_value, float* stats,
+                            float* workspace, void* stream) {
+  if (!mean || !value || !batch || !log_std || !g_mean || !g_value || !g_logstd || !gb_mean || !gb_value || !stats || !workspace || m <= 0 ||
+      !(clip >= 0.0f) || !(ent_coef == ent_coef))
+    return orr_fail(-1, "orr_ppo_head_logstd: bad argument", hipSuccess);
+  if (!aligned16(mean) || !aligned16(batch) || !aligned16(g_mean))
+    return orr_fail(-1, "orr_ppo_head_logstd: buffers must be 16-byte aligned", hipSuccess);
+  const int nblk = (m + kThreads - 1) / kThreads;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(ppo_head_logstd_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, st, mean, value, batch, log_std, (int)m, clip, vf_coef,
+                     1.0f / (float)m, g_mean, g_value, workspace);
+  hipLaunchKernelGGL(ppo_head_logstd_finish_kernel, dim3(1), dim3(4 * kLsCols), 0, st, (const float*)workspace, nblk, (float)m, ent_coef, log_std,
+                     gb_mean, gb_value, g_logstd, stats);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_ppo_head_logstd: launch", e);
+  return 0;
+}
+
+int32_t orr_gauss_prepare(const float* noise, const float* log_std, float* scaled, float* logp, int32_t n, void* stream) {
+  if (!noise || !log_std || !scaled || n <= 0) return orr_fail(-1, "orr_gauss_prepare: bad argument", hipSuccess);
+  if (!aligned16(noise) || !aligned16(scaled)) return orr_fail(-1, "orr_gauss_prepare: buffers must be 16-byte aligned", hipSuccess);
+  const size_t bytes = (size_t)n * kAct * sizeof(float);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(noise), b = reinterpret_cast<uintptr_t>(scaled);
+  if (a != b && a < b + bytes && b < a + bytes)
+    return orr_fail(-1, "orr_gauss_prepare: scaled must be noise itself or not overlap it", hipSuccess);
+  hipLaunchKernelGGL(gauss_prepare_kernel, dim3((unsigned)(((long long)n + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, noise,
+                     log_std, scaled, logp, (long long)n);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_gauss_prepare: launch", e);
   return 0;
 }
 

@@ -15,7 +15,7 @@ share stands once, in _FusedLearner:
     minibatch cost no host time.  FusedPPO alone has ranks; several ranks: one graph per minibatch, the all-reduce (RCCL) and Adam between
     replays.  ORR_FORCE_DIST=1 with an initialised process group takes the several-ranks path even for ONE rank (a one-GPU box can then run
     per-minibatch graphs + the RCCL all-reduce + Adam between replays; the result equals the one-graph path bit for bit).
-Scalar hyper-parameters (lr, betas, eps, clip, vf_coef, the policy's std, the loss coefficients, the world size) are by-value kernel
+Scalar hyper-parameters (lr, betas, eps, clip, vf_coef, a fixed policy std, the loss coefficients, the world size) are by-value kernel
 arguments, i.e. frozen into a captured graph: the driver compares them with the values the graphs were captured with and captures again
 when one changed (the reference feeds optim_stepsize * cur_lrmult every step: ppo1/pposgd_simple.py; run.py uses schedule='constant').
 There is no fallback: without a GPU and the HIP library the constructors raise.
@@ -24,6 +24,7 @@ import ctypes as C
 import os
 
 from . import _abi, _lib
+from .policy import LOGSTD         # the learned log-std of ppo.ActorCritic(learn_std=True)
 
 NETS = ("pi", "vf")
 
@@ -239,13 +240,21 @@ class _FusedLearner(object):
 
 
 class FusedPPO(_FusedLearner):
-    """The PPO update on the device, the only learner with ranks (see the module's text)."""
+    """The PPO update on the device, the only learner with ranks (see the module's text).
+
+    A learn-std model (ppo.ActorCritic(learn_std=True)): model/pi/logstd:0 is one more slot of the flat buffer - Adam, the all-reduce, sync and
+    check_synced cover it as they cover every slot -, the loss head is orr_ppo_head_logstd, which reads the twelve from that slot and writes
+    their gradient into flat_g's (loss - ent_coef * H), and a clamp of the slot to log_std_bounds follows every orr_adam_step (inside the
+    captured epoch on one rank, between replays on several).  update() then returns ppo.STAT_NAMES' five.  No std is frozen into the graphs:
+    they are captured once while log_std moves.  A fixed-std model is the path it always was; ent_coef != 0 is refused for it."""
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
-                 mpi_adam_epsilon=False, use_graph=True):
+                 mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None):
+        from . import ppo
         self._need_gpu(model)
         if getattr(model, "history", 0):
             raise ValueError("FusedPPO: a history student is trained by FusedDistillHistory only")
+        self.learn_std, self.ent_coef, self.log_std_bounds = ppo._entropy_args(model, "FusedPPO", ent_coef, log_std_bounds or ppo.LOG_STD_BOUNDS)
         self.clip, self.vf_coef = float(clip_param), float(vf_coef)
         self.group = group
         # a privileged critic (ppo.ActorCritic(priv_dim=48)): its layer 0 reads x | priv, [M, 160 + 48]; everything behind layer 0 and the
@@ -253,15 +262,22 @@ class FusedPPO(_FusedLearner):
         self.priv_dim = int(getattr(model, "priv_dim", 0))
         # a privileged actor as well (ppo.ActorCritic(actor_priv_dim=48), a teacher): its layer 0 reads the same x | priv
         self.actor_priv_dim = int(getattr(model, "actor_priv_dim", 0))
-        _FusedLearner.__init__(self, model, sorted(model.p), 2, lr, adam_eps, minibatch, betas, use_graph, mpi_adam_epsilon)
+        _FusedLearner.__init__(self, model, sorted(model.p), 5 if self.learn_std else 2, lr, adam_eps, minibatch, betas, use_graph, mpi_adam_epsilon)
 
     def _graph_key(self):
+        if self.learn_std:          # the std is read on the device: not a key
+            return _FusedLearner._graph_key(self) + (self.clip, self.vf_coef, self.ent_coef) + self.log_std_bounds
         return _FusedLearner._graph_key(self) + (self.clip, self.vf_coef, float(self.model.std))
+
+    def _adam(self, world):
+        _FusedLearner._adam(self, world)
+        if self.learn_std:
+            self.w[LOGSTD].clamp_(*self.log_std_bounds)
 
     def _buffers(self, P, f, split, rows):
         B, M, pd = P["B"], P["M"], self.priv_dim
         P.update({"obs": f(B, 160), "aux": f(B, 16), "x": f(M, 160), "batch": f(M, 16), "gz2": f(M, 256), "gh1": f(M, 512), "g_pi": f(M, 12),
-                  "g_vf": f(M), "ws": f(int(self.L.orr_learner_workspace_floats(M, 16)))})
+                  "g_vf": f(M), "ws": f(int(self.L.orr_learner_workspace_floats(M, 32 if self.learn_std else 16)))})
         P["aux"].zero_()
         if pd:      # the privileged observations, gathered with the same permutation; xv = x | xp is the critic's layer-0 input
             P["priv"], P["xp"], P["xv"] = f(B, pd), f(M, pd), f(M, 160 + pd)
@@ -286,9 +302,14 @@ class FusedPPO(_FusedLearner):
                 xin["pi"] = P["xv"]
         for net in NETS:
             self._mlp_forward(P, net, "_" + net, xin[net])
-        _lib.check(L.orr_ppo_head(P["y_pi"].data_ptr(), P["y_vf"].data_ptr(), P["batch"].data_ptr(), M, float(self.model.std), self.clip,
-                                  self.vf_coef, P["g_pi"].data_ptr(), P["g_vf"].data_ptr(), g["model/pi/b:0"].data_ptr(),
-                                  g["model/vf/b:0"].data_ptr(), P["stats"][s].data_ptr(), ws, st), L)
+        if self.learn_std:
+            _lib.check(L.orr_ppo_head_logstd(P["y_pi"].data_ptr(), P["y_vf"].data_ptr(), P["batch"].data_ptr(), self.w[LOGSTD].data_ptr(), M, self.clip,
+                                             self.vf_coef, self.ent_coef, P["g_pi"].data_ptr(), P["g_vf"].data_ptr(), g[LOGSTD].data_ptr(),
+                                             g["model/pi/b:0"].data_ptr(), g["model/vf/b:0"].data_ptr(), P["stats"][s].data_ptr(), ws, st), L)
+        else:
+            _lib.check(L.orr_ppo_head(P["y_pi"].data_ptr(), P["y_vf"].data_ptr(), P["batch"].data_ptr(), M, float(self.model.std), self.clip,
+                                      self.vf_coef, P["g_pi"].data_ptr(), P["g_vf"].data_ptr(), g["model/pi/b:0"].data_ptr(),
+                                      g["model/vf/b:0"].data_ptr(), P["stats"][s].data_ptr(), ws, st), L)
         for net, k, gy in (("pi", 12, P["g_pi"]), ("vf", 1, P["g_vf"])):
             self._mlp_backward(P, net, "_" + net, xin[net], gy, k, st)
         _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
@@ -297,7 +318,7 @@ class FusedPPO(_FusedLearner):
     def update(self, obs, actions, adv, ret, old_logp=None, epochs=1, generator=None, priv=None):
         """obs [B,160], actions [B,12] (unclipped samples), adv [B] (already normalised), ret [B] (TD(lambda) targets); priv [B,48]
         the privileged observations, for a model with a privileged critic;
-        returns the mean (surrogate, value loss) over the minibatches like ppo.PPO.update."""
+        returns the mean (surrogate, value loss) over the minibatches like ppo.PPO.update; of a learn-std model the means of ppo.STAT_NAMES' five."""
         B = int(obs.shape[0])
         if (priv is not None) != (self.priv_dim > 0):
             raise ValueError("FusedPPO: priv is needed by a privileged critic and by no other")
@@ -384,7 +405,7 @@ class FusedDistill(_FusedLearner):
         self._need_gpu(student)
         if getattr(student, "history", 0):
             raise ValueError("FusedDistill: a history student is trained by FusedDistillHistory only")
-        _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/pi")), 1, lr, adam_eps, minibatch, betas, use_graph)
+        _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/pi") and k != LOGSTD), 1, lr, adam_eps, minibatch, betas, use_graph)
 
     def _buffers(self, P, f, split, rows):
         B, M = P["B"], P["M"]

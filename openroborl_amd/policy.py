@@ -50,12 +50,19 @@ ENC_PARAMETER_LIST = (("model/enc_fc0/w:0", (512, 256)), ("model/enc_fc0/b:0", (
                       ("model/enc_fc1/b:0", (PRIV_DIM,)))
 
 
+# the learned log-std of ppo.ActorCritic(learn_std=True).  The reference's graph declares this very variable (pi/logstd, [1, 12], filled with
+# log(pi_init_std): agents/imitation_policies.py:48) but with trainable=False, which keeps it out of the zips it saves and loads
+LOGSTD = "model/pi/logstd:0"
+LOGSTD_PARAMETER = (LOGSTD, (1, 12))
+
+
 def save_parameters_zip(path, params, data=None):
     """Write weights in the stable-baselines zip layout (`data` JSON, `parameter_list` JSON, `parameters` npz;
     stable_baselines/common/base_class.py:552-590) so that the reference's `agent.load_parameters(model_file)`
     (run.py:220-221, exact_match=True) can read a policy trained here: the FULL variable set of the reference graph in its
     saved order.  The unused q head is carried over when `params` holds one (a policy warm-started from a reference zip) and
-    zero-filled otherwise.  `data` carries no pickled objects (load_parameters ignores it)."""
+    zero-filled otherwise.  `data` carries no pickled objects (load_parameters ignores it).  Variables the reference's list does not
+    have - a history encoder's, a learned log-std (model/pi/logstd:0) - follow its fourteen names; such a zip loads here, not in the reference."""
     import json
     out = {}
     for name, shape in SB_PARAMETER_LIST:
@@ -80,6 +87,13 @@ def save_parameters_zip(path, params, data=None):
                 raise ValueError("%s has shape %s, a history encoder has %s" % (name, v.shape, shape))
             out[name] = v
             names.append(name)
+    name, shape = LOGSTD_PARAMETER               # a learned log-std (ppo.ActorCritic(learn_std=True)): likewise behind the list, loadable here only -
+    if name in params:                           # the reference's exact_match load refuses a zip with a fifteenth name
+        v = np.asarray(params[name], dtype=np.float32)
+        if v.shape != shape:
+            raise ValueError("%s has shape %s, a learned log-std has %s" % (name, v.shape, shape))
+        out[name] = v
+        names.append(name)
     buf = io.BytesIO()
     np.savez(buf, **out)
     with zipfile.ZipFile(path, "w") as z:
@@ -97,6 +111,9 @@ class MLPPolicy(object):
         g = lambda k: torch.tensor(params[k], dtype=torch.float32, device=self.device)
         self.pi = [(g("model/pi_fc0/w:0"), g("model/pi_fc0/b:0")), (g("model/pi_fc1/w:0"), g("model/pi_fc1/b:0")),
                    (g("model/pi/w:0"), g("model/pi/b:0"))]
+        # a zip saved from a learn-std model: sample with its twelve stds instead of `std`
+        self.log_std = g(LOGSTD).reshape(1, 12) if LOGSTD in params else None
+        self.learn_std = self.log_std is not None      # as ppo.ActorCritic says it: whoever forms a log-probability asks this one attribute
         self.vf = None
         if "model/vf_fc0/w:0" in params:
             self.vf = [(g("model/vf_fc0/w:0"), g("model/vf_fc0/b:0")), (g("model/vf_fc1/w:0"), g("model/vf_fc1/b:0")),
@@ -125,11 +142,15 @@ class MLPPolicy(object):
         (imitation_runners.py:140-143)."""
         t = self.torch
         mu = self.mean(obs)
-        a = mu if deterministic else mu + self.std * t.randn(mu.shape, device=mu.device, generator=generator)
+        std = self.std if self.log_std is None else self.log_std.exp()
+        a = mu if deterministic else mu + std * t.randn(mu.shape, device=mu.device, generator=generator)
         return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs)
 
     def log_prob(self, obs, actions):
         t = self.torch
         mu = self.mean(obs)
+        if self.log_std is not None:
+            z = (actions - mu) * t.exp(-self.log_std)
+            return (-0.5 * z * z - self.log_std - 0.5 * math.log(2.0 * math.pi)).sum(dim=1)
         var = self.std * self.std
         return (-0.5 * ((actions - mu) ** 2) / var - 0.5 * math.log(2.0 * math.pi * var)).sum(dim=1)

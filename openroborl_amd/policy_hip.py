@@ -8,6 +8,7 @@ import ctypes as C
 import math
 
 from . import _abi, _lib
+from .policy import LOGSTD     # a learned log-std [1, 12] (ppo.ActorCritic(learn_std=True)): sampled with when the parameter dict holds it
 
 KEYS = (("w0_pi", "model/pi_fc0/w:0"), ("b0_pi", "model/pi_fc0/b:0"), ("w1_pi", "model/pi_fc1/w:0"), ("b1_pi", "model/pi_fc1/b:0"),
         ("w2_pi", "model/pi/w:0"), ("b2_pi", "model/pi/b:0"), ("w0_vf", "model/vf_fc0/w:0"), ("b0_vf", "model/vf_fc0/b:0"),
@@ -20,7 +21,11 @@ SHAPES = {"w0_pi": (160, 512), "w0_vf": (160, 512), "w1_pi": (512, 256), "w1_vf"
 
 class FusedActorCritic(object):
     """Device-resident packed copy of an actor-critic parameter dict (stable-baselines names, torch tensors on the GPU).
-    Call `refresh()` after the parameters changed (e.g. after an optimiser step) and `forward()` once per env step."""
+    Call `refresh()` after the parameters changed (e.g. after an optimiser step) and `forward()` once per env step.
+
+    A dict with model/pi/logstd:0 samples with it instead of `std`: forward() first scales the noise by exp(log_std) (orr_gauss_prepare, into a
+    static buffer) and then runs the forward kernel it would run anyway with std = 1, mean + 1 * x being mean + x.  The twelve values are
+    read on the device, from this object's own copy at a fixed address (refresh() renews it), never on the host."""
 
     def __init__(self, params, device, std, clip=2.0 * math.pi):
         import torch
@@ -65,6 +70,12 @@ class FusedActorCritic(object):
                     if tuple(params[key].shape) != ENC_SHAPES[field]:
                         raise ValueError("%s has shape %s, the fused kernel is built for %s" % (key, tuple(params[key].shape), ENC_SHAPES[field]))
                     self.packed["enc_" + field] = torch.empty(int(self.L.orr_policy_packed_size(*ENC_SHAPES[field])), dtype=torch.float32, device=self.device)
+        self.log_std = None           # the sampler's copy of model/pi/logstd:0, [12]
+        self._scaled = {}             # n -> the static [n, 12] buffer of exp(log_std) * noise
+        if LOGSTD in params:
+            if params[LOGSTD].numel() != 12:
+                raise ValueError("%s has shape %s, the sampler is built for (1, 12)" % (LOGSTD, tuple(params[LOGSTD].shape)))
+            self.log_std = torch.empty(12, dtype=torch.float32, device=self.device)
         self.net = _abi.OrrPolicyNet()
         self.refresh()
 
@@ -74,6 +85,8 @@ class FusedActorCritic(object):
     def refresh(self):
         """Re-pack the weights (six small launches, eight with an encoder) and re-read the biases from the parameter tensors."""
         t = self.torch
+        if self.log_std is not None:
+            self.log_std.copy_(self.params[LOGSTD].detach().reshape(12))
         for struct, prefix, keys in ((self.net, "", KEYS),) + (((self.enc, "enc_", ENC_KEYS),) if self.history else ()):
             for field, key in keys:
                 w = self.params[key].detach()
@@ -90,15 +103,30 @@ class FusedActorCritic(object):
                     self.biases[name].copy_(w)
                     setattr(struct, field, self.biases[name].data_ptr())
 
+    def prepare(self, noise, scaled, logp=None):
+        """orr_gauss_prepare with this policy's log-std: scaled [n,12] = exp(log_std) * noise [n,12] and, when given, logp [n] = the
+        log-probability of mean + scaled under the sampling policy.  One launch for any n (a whole rollout segment); scaled may be noise."""
+        t = self.torch
+        if self.log_std is None:
+            raise ValueError("prepare() is for a policy with %s" % LOGSTD)
+        n = noise.shape[0]
+        for x, shape in ((noise, (n, 12)), (scaled, (n, 12)), (logp, (n,))):
+            if x is not None and (x.dtype != t.float32 or not x.is_contiguous() or tuple(x.shape) != shape or x.device != self.device):
+                raise ValueError("noise and scaled must be contiguous float32 [n,12] tensors and logp [n] on %s" % (self.device,))
+        _lib.check(self.L.orr_gauss_prepare(noise.data_ptr(), self.log_std.data_ptr(), scaled.data_ptr(), logp.data_ptr() if logp is not None else None,
+                                            int(n), self._stream()), self.L)
+        return scaled
+
     def forward(self, obs, noise=None, want_mean=False, out_action=None, out_raw=None, out_value=None, priv=None, out_mean=None, want_value=True,
-                hist=None, out_latent=None):
+                hist=None, out_latent=None, scaled=False):
         """obs [N,160] float32 on the device; noise [N,12] standard normal or None (deterministic); priv [N,48] float32, the
         privileged observation, for a privileged critic (and only then).
         Returns (clipped action [N,12], raw action [N,12], value [N], mean [N,12] or None); the out_* tensors
         (contiguous float32 of those shapes, e.g. rows of a rollout buffer) are written in place when given (out_mean implies want_mean).
         want_value=False: no value is written and None is returned for it; a privileged actor's kernel then skips the critic.
         hist [N,512] float32 (history_push), for a history student and instead of priv: the encoder's estimate of the row feeds actor and
-        critic (orr_policy_forward_history) and is written to out_latent [N,48] when that is given."""
+        critic (orr_policy_forward_history) and is written to out_latent [N,48] when that is given.
+        scaled=True, for a policy with a learned log-std: `noise` already is exp(log_std) * noise (prepare(), e.g. once for a whole segment)."""
         t = self.torch
         if obs.dtype != t.float32 or not obs.is_contiguous() or obs.device != self.device or obs.dim() != 2 or obs.shape[1] != 160:
             raise ValueError("obs must be a contiguous float32 [N,160] tensor on %s" % (self.device,))
@@ -130,28 +158,37 @@ class FusedActorCritic(object):
             raise ValueError("out_value given with want_value=False")
         act, raw, val = out(out_action, (n, 12)), out(out_raw, (n, 12)), out(out_value, (n,)) if want_value else None
         mean = out(out_mean, (n, 12)) if (want_mean or out_mean is not None) else None
+        std = self.std
+        if self.log_std is not None:
+            if noise is not None and not scaled:
+                if n not in self._scaled:
+                    self._scaled[n] = t.empty((n, 12), dtype=t.float32, device=self.device)
+                noise = self.prepare(noise, self._scaled[n])
+            std = 1.0
+        elif scaled:
+            raise ValueError("scaled=True is for a policy with %s" % LOGSTD)
         if hist is not None:
             latent = out(out_latent, (n, _abi.POLICY_PRIV_DIM)) if out_latent is not None else None
             _lib.check(self.L.orr_policy_forward_history(C.byref(self.net), C.byref(self.enc), obs.data_ptr(), hist.data_ptr(), int(n),
-                                                         noise.data_ptr() if noise is not None else None, self.std, self.clip, act.data_ptr(),
+                                                         noise.data_ptr() if noise is not None else None, std, self.clip, act.data_ptr(),
                                                          raw.data_ptr(), val.data_ptr() if val is not None else None,
                                                          mean.data_ptr() if mean is not None else None,
                                                          latent.data_ptr() if latent is not None else None, self._stream()), self.L)
             return act, raw, val, mean
         if self.actor_priv_dim:
             _lib.check(self.L.orr_policy_forward_teacher(C.byref(self.net), obs.data_ptr(), priv.data_ptr(), int(n),
-                                                         noise.data_ptr() if noise is not None else None, self.std, self.clip, act.data_ptr(),
+                                                         noise.data_ptr() if noise is not None else None, std, self.clip, act.data_ptr(),
                                                          raw.data_ptr(), val.data_ptr() if val is not None else None,
                                                          mean.data_ptr() if mean is not None else None, self._stream()), self.L)
             return act, raw, val, mean
         if priv is not None:
             _lib.check(self.L.orr_policy_forward_priv(C.byref(self.net), obs.data_ptr(), priv.data_ptr(), int(n),
-                                                      noise.data_ptr() if noise is not None else None, self.std, self.clip, act.data_ptr(),
+                                                      noise.data_ptr() if noise is not None else None, std, self.clip, act.data_ptr(),
                                                       raw.data_ptr(), val.data_ptr() if val is not None else None, mean.data_ptr() if mean is not None else None,
                                                       self._stream()), self.L)
             return act, raw, val, mean
         _lib.check(self.L.orr_policy_forward(C.byref(self.net), obs.data_ptr(), int(n), noise.data_ptr() if noise is not None else None,
-                                             self.std, self.clip, act.data_ptr(), raw.data_ptr(), val.data_ptr() if val is not None else None,
+                                             std, self.clip, act.data_ptr(), raw.data_ptr(), val.data_ptr() if val is not None else None,
                                              mean.data_ptr() if mean is not None else None, self._stream()), self.L)
         return act, raw, val, mean
 

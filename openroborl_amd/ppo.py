@@ -18,6 +18,11 @@ from . import policy as pol
 
 _LINEAR = {}
 
+LOGSTD = pol.LOGSTD                # the learned log-std [1, 12] of ActorCritic(learn_std=True); the reference declares it and freezes it (imitation_policies.py:48)
+ENTROPY_CONST = 6.0 * math.log(2.0 * math.pi * math.e)     # H of a 12-dimensional diagonal Gaussian = sum_k log_std_k + this
+LOG_STD_BOUNDS = (math.log(0.01), math.log(1.0))
+STAT_NAMES = ("surr", "vf", "entropy", "approx_kl", "clip_fraction")     # what a learner of a learn-std model returns (a fixed-std one: the first two)
+
 # the sensor history of a history student (include/openroborl_policy.h: ORR_HISTORY_*): 16 frames of 32 words, newest first
 HISTORY_STEPS, HISTORY_FRAME, HISTORY_DIM = 16, 32, 512
 ENC_HIDDEN = 256
@@ -45,6 +50,18 @@ def history_push(hist, obs, done):
 def _no_history(model, who):
     if getattr(model, "history", 0):
         raise ValueError("%s: a history student (history = %d) is trained by DistillHistory / learner_hip.FusedDistillHistory only" % (who, model.history))
+
+
+def _entropy_args(model, who, ent_coef, log_std_bounds):
+    """-> (learn_std, ent_coef, (lo, hi)) of a PPO learner, checked."""
+    learn = bool(getattr(model, "learn_std", False))
+    ent_coef = float(ent_coef)
+    lo, hi = float(log_std_bounds[0]), float(log_std_bounds[1])
+    if not learn and ent_coef != 0.0:
+        raise ValueError("%s: ent_coef = %g needs a learn-std model (ActorCritic(learn_std=True)): the entropy of a fixed std has no gradient" % (who, ent_coef))
+    if not (math.isfinite(ent_coef) and lo < hi and math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError("%s: ent_coef must be finite and log_std_bounds (lo, hi) finite with lo < hi" % who)
+    return learn, ent_coef, (lo, hi)
 
 
 def _wgrad(torch, x, g):
@@ -93,10 +110,15 @@ class ActorCritic(object):
     model/enc_fc1 [256, 48]: a history student.  encode(hist) estimates the privileged row from hist [N, 512] (history_push), and mean() and
     act() take `hist` in the row's place - the teacher's actor and critic on cat(obs, encode(hist)).  Such a policy is deployable: it reads
     its own sensors only.  The encoder is drawn after every other parameter, so history = 0 is the model without, draw for draw.  With
-    `params` the presence of model/enc_fc0/w:0 decides."""
+    `params` the presence of model/enc_fc0/w:0 decides.
+
+    learn_std = True adds model/pi/logstd:0 [1, 12], filled with log(std): a state-independent log-std that PPO / learner_hip.FusedPPO train
+    (with an entropy bonus, ent_coef).  act() then samples mean + exp(log_std) * noise and log_prob() is the per-dimension Gaussian's.  It is
+    filled, not drawn: every other parameter is what it is without, draw for draw.  With `params` the presence of the key decides.  `log_std`
+    is the device tensor, and the one thing rollout and update paths read; `std` is then the twelve values on the host, for logging only."""
 
     def __init__(self, device, obs_dim=160, act_dim=12, hidden=(512, 256), std=pol.PI_STD, params=None, seed=0, priv_dim=0, actor_priv_dim=0,
-                 history=0):
+                 history=0, learn_std=False):
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -131,6 +153,13 @@ class ActorCritic(object):
         if self.history:           # after every other draw
             self._init("model/enc_fc0", HISTORY_DIM, ENC_HIDDEN, g, math.sqrt(2.0))
             self._init("model/enc_fc1", ENC_HIDDEN, pol.PRIV_DIM, g, 1.0)
+        if params is not None:
+            learn_std = LOGSTD in params
+        self.learn_std = bool(learn_std)
+        if self.learn_std:         # filled, no draw
+            if not self._std > 0.0:
+                raise ValueError("learn_std needs std > 0, got %r" % (std,))
+            self.p[LOGSTD] = torch.full((1, act_dim), math.log(self._std), dtype=torch.float32, device=self.device)
         self.extra = {}            # variables of a loaded zip that this learner does not train (model/q/*): re-emitted by state_dict()
         if params is not None:
             for k, v in params.items():
@@ -145,13 +174,26 @@ class ActorCritic(object):
 
     @property
     def std(self):
+        """The fixed std; of a learn-std model the twelve current values as a host array - a device read, for logging only."""
+        if self.learn_std:
+            return self.p[LOGSTD].detach().exp().reshape(-1).cpu().numpy()
         return self._std
+
+    @property
+    def log_std(self):
+        """The learned log-std on the device, [1, 12] (a view of the learner's flat buffer once a fused learner owns it)."""
+        if not self.learn_std:
+            raise AttributeError("this model has a fixed std (learn_std = False)")
+        return self.p[LOGSTD]
 
     @std.setter
     def std(self, value):
         """One number for the sampler AND the log-probabilities: the fused forward pass takes std by value at every launch, so a policy
         whose std is changed after enable_fused() must hand it on (a re-captured rollout graph sampled with the old std while
         the log-probabilities used the new one)."""
+        if self.learn_std:
+            raise AttributeError("a learn-std model's std is exp(log_std), a trained parameter: write model.log_std on the device and call "
+                                 "mark_updated(), which makes the fused sampler renew its copy")
         self._std = float(value)
         if getattr(self, "fused", None) is not None:
             self.fused.std = self._std
@@ -160,7 +202,7 @@ class ActorCritic(object):
         """Route act() through the fused matrix-core forward pass (csrc/orr_policy.hip).  The packed weight copy is
         refreshed lazily after mark_updated() (the learner calls it after every optimiser step)."""
         from . import policy_hip
-        self.fused = policy_hip.FusedActorCritic(self.p, self.device, std=self.std)
+        self.fused = policy_hip.FusedActorCritic(self.p, self.device, std=self._std)
         self._fused_dirty = False
         return self
 
@@ -255,26 +297,38 @@ class ActorCritic(object):
             mu = self.mean(obs, self.actor_priv(priv))
             if noise is None and not deterministic:
                 noise = t.randn(mu.shape, device=mu.device, generator=generator)
-            a = mu if deterministic else mu + self.std * noise
+            a = mu if deterministic else mu + (self.p[LOGSTD].exp() if self.learn_std else self.std) * noise
             return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, priv)
 
     def log_prob(self, obs, actions, priv=None):
         mu = self.mean(obs, priv)
+        if self.learn_std:
+            ls = self.p[LOGSTD]
+            z = (actions - mu) * self.torch.exp(-ls)
+            return (-0.5 * z * z - ls - 0.5 * math.log(2.0 * math.pi)).sum(dim=1)
         var = self.std * self.std
         return (-0.5 * ((actions - mu) ** 2) / var - 0.5 * math.log(2.0 * math.pi * var)).sum(dim=1)
 
     def state_dict(self):
         d = {k: v.detach().cpu().numpy() for k, v in self.p.items()}
         d.update(self.extra)
+        if not self.learn_std:      # carried from a learn-std teacher (train.py: history_student) but not sampled with: a zip that held it would
+            d.pop(LOGSTD, None)     # reload as a learn-std policy with the teacher's stds, not the fixed std this model was rolled out with
         return d
 
 
 class PPO(object):
-    def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None):
+    """With a learn-std model (ActorCritic(learn_std=True)) the loss gains -ent_coef * H (pol_entpen, agents/ppo_imitation.py:196-210),
+    log_std is clamped to log_std_bounds after every optimiser step, and update() returns the five STAT_NAMES.  A fixed-std model is the
+    code path it always was and returns (surrogate, value loss); ent_coef != 0 is refused for it, the term would have no gradient."""
+
+    def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, ent_coef=0.0,
+                 log_std_bounds=LOG_STD_BOUNDS):
         import torch
         self.torch = torch
         _no_history(model, "PPO")
         self.model = model
+        self.learn_std, self.ent_coef, self.log_std_bounds = _entropy_args(model, "PPO", ent_coef, log_std_bounds)
         self.clip = clip_param
         self.minibatch = int(minibatch)
         self.vf_coef = vf_coef
@@ -325,13 +379,26 @@ class PPO(object):
                 v = self.model.value(obs_p[s:e]) if priv_p is None else self.model.value(obs_p[s:e], priv_p[s:e])
                 vf = ((v - ret_p[s:e]) ** 2).mean()
                 loss = surr + self.vf_coef * vf
+                if self.learn_std:
+                    ent = self.model.p[LOGSTD].sum() + ENTROPY_CONST
+                    loss = loss - self.ent_coef * ent
                 self.opt.zero_grad(set_to_none=True)
                 loss.backward()
                 self._allreduce_grads()
                 self.opt.step()
+                if self.learn_std:
+                    with t.no_grad():
+                        self.model.p[LOGSTD].clamp_(*self.log_std_bounds)
+                        log_ratio = (logp - old_p[s:e]).detach()
+                        r = ratio.detach()
+                        kl = ((r - 1.0) - log_ratio).mean()
+                        clipped = ((r < 1.0 - self.clip) | (r > 1.0 + self.clip)).to(r.dtype).mean()
                 if hasattr(self.model, "mark_updated"):
                     self.model.mark_updated()
-                stats.append(t.stack((surr.detach(), vf.detach())))   # stays on the device: no sync per minibatch
+                if self.learn_std:
+                    stats.append(t.stack((surr.detach(), vf.detach(), ent.detach(), kl, clipped)))
+                else:
+                    stats.append(t.stack((surr.detach(), vf.detach())))   # stays on the device: no sync per minibatch
         return t.stack(stats).mean(dim=0).cpu().numpy()
 
 
@@ -348,7 +415,7 @@ class Distill(object):
             raise ValueError("Distill: the student's actor must read the 160 observation words only")
         self.model = student
         self.minibatch = int(minibatch)
-        params = [student.p[k] for k in sorted(student.p) if k.startswith("model/pi")]
+        params = [student.p[k] for k in sorted(student.p) if k.startswith("model/pi") and k != LOGSTD]     # a log-std is neither read nor trained here
         self.opt = torch.optim.Adam(params, lr=lr, eps=adam_eps, fused=bool(params and params[0].is_cuda))
 
     def update(self, obs, target_mean, epochs=1, generator=None):

@@ -115,8 +115,11 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
     if noise is not None:
         # log-probability of the sampled actions under the sampling policy: a - mean = std * noise
         import math
-        std = float(policy.std)
-        buf["logp"] = -0.5 * (noise * noise).sum(dim=-1) - 12.0 * math.log(std * math.sqrt(2.0 * math.pi))
+        if getattr(policy, "learn_std", False):     # from the tensor, on the device: -1/2 sum noise^2 - sum log_std - 6 log(2 pi)
+            buf["logp"] = -0.5 * (noise * noise).sum(dim=-1) - policy.log_std.detach().sum() - 6.0 * math.log(2.0 * math.pi)
+        else:
+            std = float(policy.std)
+            buf["logp"] = -0.5 * (noise * noise).sum(dim=-1) - 12.0 * math.log(std * math.sqrt(2.0 * math.pi))
     return buf
 
 
@@ -143,6 +146,11 @@ class GraphRollout(object):
     place, and after step_into and privileged_obs the push history_push(obs[k + 1], dones[k], hist[k], out=hist[k + 1]) runs inside the
     captured segment; "hist" and "last_hist" are returned next to "priv" and "last_priv", the encoder's regression targets.
 
+    With a learned log-std (policy.learn_std) the segment opens with ONE orr_gauss_prepare over noise [T N][12]: it writes scaled [T, N, 12] =
+    exp(log_std) * noise and logp, the forward passes read scaled[k] with std = 1, and no std is among the launch parameters - log_std is read
+    on the device, from the copy the segment's weight re-pack renews, so the graph is captured once and replayed for good while the learner
+    moves it.
+
     The returned tensors are views of the static buffers: they are overwritten by the next collect() (clone what must survive it,
     e.g. the last row of `dones` that the next segment's GAE takes as first_starts)."""
 
@@ -163,10 +171,14 @@ class GraphRollout(object):
         if teacher is not None:
             self.teacher_mean, self.teacher_clipped, self.step_action = f(T, n, 12), f(n, 12), f(n, 12)
             self.teacher_mask = t.zeros(n, dtype=t.uint8, device=dev)
+        self.learn_std = bool(getattr(policy, "learn_std", False))
+        self.scaled = f(T, n, 12) if self.learn_std else None
         self.graph, self.calls = None, 0
         self._captured_for = None          # (env.launch_params_generation, policy.std) the graph was captured with
 
     def _launch_params(self):
+        if self.learn_std:         # no std by value: the twelve are read on the device
+            return (getattr(self.env, "launch_params_generation", 0),)
         return (getattr(self.env, "launch_params_generation", 0), float(self.policy.std))
 
     def _segment(self):
@@ -176,13 +188,18 @@ class GraphRollout(object):
         fused.refresh()                   # inside the graph: every replay re-packs the weights the learner has just updated
         if self.teacher is not None:
             self.teacher.fused.refresh()
+        noise, more = self.noise, {}
+        if self.learn_std:
+            T, n = self.T, self.env.num_robot
+            fused.prepare(self.noise.view(T * n, 12), self.scaled.view(T * n, 12), self.logp.view(T * n))
+            noise, more = self.scaled, {"scaled": True}
         for k in range(self.T):
             if self.history:
-                fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], hist=self.hist[k])
+                fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], hist=self.hist[k], **more)
             elif self.priv_dim:
-                fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], priv=self.priv[k])
+                fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], priv=self.priv[k], **more)
             else:
-                fused.forward(self.obs[k], self.noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k])
+                fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], **more)
             action = self.clipped
             if self.teacher is not None:
                 self.teacher.fused.forward(self.obs[k], None, out_action=self.teacher_clipped, out_mean=self.teacher_mean[k], want_value=False,
@@ -193,6 +210,8 @@ class GraphRollout(object):
                 env.privileged_obs(out=self.priv[k + 1], done=self.dones[k])
             if self.history:
                 policy_hip.history_push(self.obs[k + 1], self.dones[k], self.hist[k], self.hist[k + 1])
+        if self.learn_std:
+            return                        # orr_gauss_prepare wrote logp
         # log-probability of the sampled actions under the sampling policy: a - mean = std * noise
         t.sum(self.noise * self.noise, dim=-1, out=self.logp)
         self.logp.mul_(-0.5).sub_(12.0 * math.log(float(self.policy.std) * math.sqrt(2.0 * math.pi)))

@@ -1,7 +1,8 @@
 """Where one train.py iteration spends its time (development aid, GPU box): rollout / GAE / PPO update by HIP events, and the pieces of
 one minibatch update (forward, backward, optimiser) timed separately.
 
-usage:  python tools/train_breakdown.py [robots=4096] [horizon=32] [minibatch=16384] [epochs=2] [torch-learner]
+usage:  python tools/train_breakdown.py [robots=4096] [horizon=32] [minibatch=16384] [epochs=2] [torch-learner] [learn-std]
+        learn-std: a model with a learned log-std and ent_coef = 0.01 (train.py --learn-std --ent-coef 0.01)
         rocprofv3 --kernel-trace --stats -- python3 tools/train_breakdown.py ... update-only      (per-kernel view of the update alone)
 """
 import os
@@ -12,9 +13,11 @@ import torch  # noqa: E402
 from openroborl_amd import learner_hip, ppo, rollout  # noqa: E402
 from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
 
-argv = [a for a in sys.argv[1:] if a not in ("update-only", "torch-learner")]
+argv = [a for a in sys.argv[1:] if a not in ("update-only", "torch-learner", "learn-std")]
 update_only = "update-only" in sys.argv
 torch_learner = "torch-learner" in sys.argv
+learn_std = "learn-std" in sys.argv
+entropy = dict(ent_coef=0.01) if learn_std else {}
 n = int(argv[0]) if len(argv) > 0 else 4096
 T = int(argv[1]) if len(argv) > 1 else 32
 mb = int(argv[2]) if len(argv) > 2 else 16384
@@ -35,8 +38,8 @@ def ms(f, reps):
     return e0.elapsed_time(e1) / reps
 
 
-model = ppo.ActorCritic(dev, seed=0).enable_fused()
-learner = ppo.PPO(model, lr=1e-4, minibatch=mb) if torch_learner else learner_hip.FusedPPO(model, lr=1e-4, minibatch=mb)
+model = ppo.ActorCritic(dev, seed=0, learn_std=learn_std).enable_fused()
+learner = ppo.PPO(model, lr=1e-4, minibatch=mb, **entropy) if torch_learner else learner_hip.FusedPPO(model, lr=1e-4, minibatch=mb, **entropy)
 gen = torch.Generator(device=dev).manual_seed(0)
 B = T * n
 obs = torch.randn(B, 160, device=dev)
@@ -71,7 +74,7 @@ def fwd_bwd():
 
 
 # the autograd path (ppo.PPO), whichever learner is being measured above
-ref = learner if torch_learner else ppo.PPO(ppo.ActorCritic(dev, seed=0), lr=1e-4, minibatch=mb)
+ref = learner if torch_learner else ppo.PPO(ppo.ActorCritic(dev, seed=0, learn_std=learn_std), lr=1e-4, minibatch=mb, **entropy)
 pm = ref.model
 t_f = ms(fwd, 50)
 t_fb = ms(fwd_bwd, 50)

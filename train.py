@@ -4,6 +4,7 @@ leaves the GPU.  Counterpart of `python3 OpenRoboRL/run.py --task imitation_lear
 (run.py:186-237), restricted to what SURVEY.md section 8f lists as "next" rows.
 
   python train.py --task imitation_learning_laikago --iters 200
+  python train.py --task imitation_learning_laikago --iters 200 --learn-std --ent-coef 0.01   (a learned exploration width, entropy / KL / clip fraction in the log)
   python train.py --task imitation_learning_laikago --iters 200 --privileged-critic --push 0.02,0.2,0.5   (asymmetric actor-critic)
   python train.py --task imitation_learning_laikago --iters 200 --privileged-actor --push 0.02,0.2,0.5 --save teacher.zip   (a teacher)
   python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --push 0.02,0.2,0.5 --save student.zip   (its student)
@@ -89,6 +90,15 @@ def main():
     ap.add_argument("--distill-beta", type=float, default=0.0,
                     help="--distill: the share of robots that are stepped with the teacher's action instead of the student's (default 0)")
     ap.add_argument("--distill-beta-iters", type=int, default=0, help="--distill: decay --distill-beta linearly to 0 over this many iterations (0: constant)")
+    ap.add_argument("--learn-std", action="store_true",
+                    help="train a state-independent log-std of the twelve actions with PPO (model/pi/logstd:0, on the device) instead of "
+                         "sampling with a fixed std.  The log gains entropy, approx_kl, clip_fraction and the smallest and largest std; "
+                         "--save writes the variable behind the reference's list: a zip that loads here and not in the reference")
+    ap.add_argument("--ent-coef", type=float, default=0.0, metavar="C", help="--learn-std: weight of the entropy bonus, loss - C * H (default 0)")
+    ap.add_argument("--init-std", type=float, default=0.125, metavar="S",
+                    help="the std of the action noise; with --learn-std where log-std starts (default 0.125, the reference's pi_init_std)")
+    ap.add_argument("--log-std-bounds", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                    help="--learn-std: log-std is clamped to [LO, HI] after every optimiser step (default log 0.01, log 1)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
     ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip (with --privileged-critic: see there)")
@@ -126,6 +136,10 @@ def main():
         raise SystemExit("train.py: --distill-action-coef / --distill-latent-coef belong to --distill --history")
     if args.distill_action_coef < 0.0 or args.distill_latent_coef < 0.0:
         raise SystemExit("train.py: --distill-action-coef / --distill-latent-coef must not be negative")
+    if args.learn_std and args.distill:
+        raise SystemExit("train.py: --learn-std belongs to PPO; the distillation learners neither read nor train a log-std")
+    if (args.ent_coef != 0.0 or args.log_std_bounds is not None) and not args.learn_std:
+        raise SystemExit("train.py: --ent-coef / --log-std-bounds belong to --learn-std")
     privileged = args.privileged_critic or bool(args.distill)       # somebody reads env.privileged_obs
     rank, world, local = odist.init_from_env()
     if args.distill and world > 1:
@@ -145,7 +159,9 @@ def main():
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     # same seed -> identical replicas.  (--model-file: the critic's width is the file's)
     model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic else 0,
-                            actor_priv_dim=pol.PRIV_DIM if args.privileged_actor else 0)
+                            actor_priv_dim=pol.PRIV_DIM if args.privileged_actor else 0, std=args.init_std, learn_std=args.learn_std)
+    if model.learn_std != args.learn_std and not args.distill:
+        raise SystemExit("train.py: --model-file has %s, --learn-std says otherwise" % ("a learned log-std" if model.learn_std else "no log-std"))
     if bool(model.priv_dim) != args.privileged_critic:
         raise SystemExit("train.py: --model-file has a %s critic, --privileged-critic says otherwise" % ("privileged" if model.priv_dim else "plain"))
     if bool(model.actor_priv_dim) != args.privileged_actor:
@@ -154,8 +170,10 @@ def main():
         model.enable_fused()
     if args.distill:
         return distill(args, torch, pol, ppo, rollout, odist, env, model, dev)
+    # --learn-std: the entropy bonus and the clamp; without it no keyword at all, the learners' defaults
+    entropy = dict(ent_coef=args.ent_coef, log_std_bounds=tuple(args.log_std_bounds or ppo.LOG_STD_BOUNDS)) if args.learn_std else {}
     if args.torch_learner:
-        learner = ppo.PPO(model, lr=args.lr, minibatch=args.minibatch)
+        learner = ppo.PPO(model, lr=args.lr, minibatch=args.minibatch, **entropy)
     else:
         from openroborl_amd import learner_hip
         # equal minibatches only (static buffers of the graph-replayed update): the largest size <= --minibatch that divides the
@@ -167,7 +185,7 @@ def main():
         if mb < 256 and args.num_robot * args.horizon >= 4096:
             raise SystemExit("train.py: %d samples per segment have no divisor between 256 and %d; pick another --num-robot / --horizon "
                              "or use --torch-learner (handles a short last minibatch)" % (args.num_robot * args.horizon, args.minibatch))
-        learner = learner_hip.FusedPPO(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam)
+        learner = learner_hip.FusedPPO(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam, **entropy)
         learner.sync()                                        # MpiAdam.sync before training (ppo_imitation.py:274)
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed * 1000 + rank)
@@ -192,9 +210,10 @@ def main():
                                      legacy_gae_index=args.legacy_gae_index, first_starts=first_starts)
         first_starts = buf["dones"][-1].clone()               # the collector's buffers are overwritten by the next segment
         T, n = buf["rewards"].shape
-        surr, vf = learner.update(buf["obs"].reshape(T * n, -1), buf["actions"].reshape(T * n, -1), adv.reshape(-1),
-                                  ret.reshape(-1), old_logp=buf["logp"].reshape(-1) if "logp" in buf else None,
-                                  epochs=args.epochs, generator=gen, priv=buf["priv"].reshape(T * n, -1) if model.priv_dim else None)
+        losses = learner.update(buf["obs"].reshape(T * n, -1), buf["actions"].reshape(T * n, -1), adv.reshape(-1),
+                                ret.reshape(-1), old_logp=buf["logp"].reshape(-1) if "logp" in buf else None,
+                                epochs=args.epochs, generator=gen, priv=buf["priv"].reshape(T * n, -1) if model.priv_dim else None)
+        surr, vf = losses[0], losses[1]      # --learn-std: three more, ppo.STAT_NAMES
         samples += T * n * world
         # (> 1 rank, or ORR_FORCE_DIST=1: the one-rank rehearsal of the several-ranks path on RCCL runs the check too)
         if (world > 1 or os.environ.get("ORR_FORCE_DIST", "0") == "1") and args.sync_check_every > 0 and it % args.sync_check_every == args.sync_check_every - 1 and hasattr(learner, "check_synced"):
@@ -211,6 +230,10 @@ def main():
                    "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2),
                    "episodes": stats.sums[0], "episodes_unlogged": stats[3] - max(stats.sums[0] - int(stats[0].numel()), 0),
                    "max_ep_steps": int(env.field_int("MAX_EP_STEPS").max()), "surr": round(float(surr), 4), "vf": round(float(vf), 4)}
+            if args.learn_std:           # the twelve stds: one device read per logged record
+                std = model.std
+                rec.update({k: round(float(v), 6) for k, v in zip(ppo.STAT_NAMES[2:], losses[2:])})
+                rec.update({"std_min": round(float(std.min()), 5), "std_max": round(float(std.max()), 5)})
             if by_clip is not None:
                 rec["ep_ret_mean_by_clip"] = {clip_name(env, c): round(r, 2) for c, (r, _) in sorted(by_clip.items())}
             if by_term is not None:
