@@ -12,6 +12,7 @@
  *   orr_distill_head   the loss head of policy distillation instead: squared error of the actor's mean against a teacher's, its gradient
  *   orr_regress_head   the loss head of a history student's encoder: squared error of its 48 outputs against the privileged row, its gradient
  *   orr_history_student_head  that head with the action loss: forward through the frozen actor, both losses, backward to the latent, one launch
+ *   orr_latent_backward  PPO on a history policy: the gradient from the actor's layer 0 into the encoder's output + the auxiliary estimation loss
  *   orr_head_backward  gradient through an output layer (fan-out 12 or 1) + ReLU mask + bias gradient of the layer below + the
  *                      output layer's weight gradient
  *   orr_colsum_finish  the column sums behind all bias gradients of a minibatch in one launch
@@ -121,6 +122,27 @@ int32_t orr_regress_head(const float* pred, const float* target, int32_t m, int3
 int32_t orr_history_student_head(const orr_policy_net* net, const float* w2t, const float* w1t, const float* w0zt, const float* obs, const float* z,
                                  const float* target_mean, const float* target_priv, int32_t m, float action_coef, float latent_coef, float* g_z,
                                  float* mean, float* partials, void* stream);
+
+/* The PPO gradient of a history policy from the actor's layer 0 into the encoder's output, for a minibatch of m samples (host side:
+ * learner_hip.FusedPPOHistory).  The actor's layer 0 reads obs | z; g0 is the gradient at its pre-activation (what orr_relu_backward leaves),
+ * and the latent's share of it is an N = 48 GEMM with a reduction and the auxiliary estimation loss fused behind it.  One launch, 16 samples
+ * per workgroup, on the f32 matrix cores (csrc/orr_policy.hip):
+ *   g_z[i][c] = sum_k g0[i][k] W0_pi[160 + c][k]  +  latent_coef * 2 (z[i][c] - target_priv[i][c]) / m          [m][48]
+ *   L_lat     = (1 / m) sum_i sum_c (z_ic - target_priv_ic)^2
+ *   g0 [m][512]
+ *   w0zt                 orr_policy_pack of the transpose of W0_pi's rows 160..207, [512][48] (orr_history_student_head's w0zt)
+ *   z [m][48], target_priv [m][48]    with latent_coef == 0 they may be NULL and are not read; the loss shares are then 0
+ *   partials             ORR_LATENT_BACKWARD_PARTIAL_FLOATS(m) floats, rows = ORR_LATENT_BACKWARD_ROWS(m) = one per workgroup:
+ *                        [rows][48] the workgroup's column sums of g_z (their sum is the bias gradient of the layer that produced z), followed by
+ *                        [rows][1] its share of L_lat (the 1 / m included).  orr_colsum_finish folds them as two jobs:
+ *                        {partials, gb [48], rows, 48} and {partials + 48 rows, loss [1], rows, 1}
+ * Packed matrix 16-byte aligned, every other buffer 4-byte aligned; m >= 1.  Rows beyond m read as zero and write nothing.  No float atomics
+ * and a fixed summation order: the same inputs give the same bits, and with latent_coef == 0 a row of g_z does not depend on m.  A refused
+ * call launches and writes nothing. */
+#define ORR_LATENT_BACKWARD_ROWS(m) (((m) + 15) / 16)
+#define ORR_LATENT_BACKWARD_PARTIAL_FLOATS(m) (49 * (int64_t)ORR_LATENT_BACKWARD_ROWS(m))
+int32_t orr_latent_backward(const float* g0, const float* w0zt, const float* z, const float* target_priv, int32_t m, float latent_coef,
+                            float* g_z, float* partials, void* stream);
 
 /* g [m][c] (gradient w.r.t. a ReLU layer's output h [m][c]) becomes the gradient w.r.t. its pre-activation, in place: g *= (h > 0);
  * gb [c] = its column sums (the layer's bias gradient).  c: a multiple of 4 with 1024 % c == 0.

@@ -115,6 +115,18 @@ int32_t orr_policy_forward_history(const orr_policy_net* net, const orr_history_
                                    const float* noise, float std, float clip, float* action, float* raw, float* value, float* mean,
                                    float* latent, void* stream);
 
+/* A history policy with an ASYMMETRIC critic, for reinforcement learning on the deployable policy itself (RMA's third phase; host side:
+ * learner_hip.FusedPPOHistory): the actor reads obs | z as above, the critic reads obs | priv - the true privileged row, which the simulator
+ * has at training time and deployment does not need.  One launch.
+ *   action, raw, mean, latent = orr_policy_forward_history(net, enc, obs, hist, ...)     bit for bit
+ *   value                     = orr_policy_forward_teacher(net, obs, priv, ...)          bit for bit
+ *   priv    [n][48] the privileged observation (orr_privileged_obs); may be NULL with value == NULL, which skips the critic as above
+ *   every other argument as in orr_policy_forward_history; neither value == NULL nor latent == NULL changes another output bit
+ * Refused like orr_policy_forward_history, and: a null priv with a value, a priv that is not 4-byte aligned. */
+int32_t orr_policy_forward_history_priv(const orr_policy_net* net, const orr_history_encoder* enc, const float* obs, const float* hist,
+                                        const float* priv, int32_t n, const float* noise, float std, float clip, float* action, float* raw,
+                                        float* value, float* mean, float* latent, void* stream);
+
 /* Per-robot GAE(lambda) over a [T][N] rollout segment + per-robot advantage standardisation, one launch
  * (reference: add_vtarg_and_adv, agents/ppo_imitation.py:68-93, and the per-robot normalisation :329-338; device
  * layout and the deliberate use of each robot's own done flags: openroborl_amd/rollout.py).

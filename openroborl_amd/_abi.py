@@ -227,8 +227,22 @@ PPO_HEAD_LOGSTD_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int3
 # include/openroborl_learner.h: int32_t orr_gauss_prepare(const float* noise [n][12], const float* log_std [12] (device), float* scaled [n][12],
 #   float* logp [n] | NULL, int32_t n, void* stream)
 GAUSS_PREPARE_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+# include/openroborl_policy.h: int32_t orr_policy_forward_history_priv(const orr_policy_net* net, const orr_history_encoder* enc, const float* obs,
+#   const float* hist [n][512], const float* priv [n][48] | NULL with value NULL, int32_t n, const float* noise, float std, float clip, float* action,
+#   float* raw, float* value | NULL, float* mean, float* latent [n][48] | NULL, void* stream)
+POLICY_FORWARD_HISTORY_PRIV_ARGS = [C.POINTER(OrrPolicyNet), C.POINTER(OrrHistoryEncoder), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_latent_backward(const float* g0 [m][512], const float* w0zt (packed [512][48]), const float* z [m][48] | NULL,
+#   const float* target_priv [m][48] | NULL (both NULL with latent_coef 0 only), int32_t m, float latent_coef, float* g_z [m][48],
+#   float* partials [latent_backward_rows(m)][48] + [rows][1], void* stream)
+LATENT_BACKWARD_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 def student_head_rows(m):
     """include/openroborl_learner.h: ORR_STUDENT_HEAD_ROWS - the rows of partial sums orr_history_student_head leaves, one per 16 samples."""
+    return (int(m) + 15) // 16
+
+
+def latent_backward_rows(m):
+    """include/openroborl_learner.h: ORR_LATENT_BACKWARD_ROWS - the rows of partial sums orr_latent_backward leaves, one per 16 samples."""
     return (int(m) + 15) // 16

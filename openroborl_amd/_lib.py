@@ -106,8 +106,8 @@ EXPORTS = [
     "orr_layout_offset", "orr_layout_size", "orr_layout_is_int", "orr_sizeof_config", "orr_sizeof_model",
     "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_set_push", "orr_sizeof_push", "orr_bind_push_outputs", "orr_privileged_obs", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
-    "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_history", "orr_history_push", "orr_gae", "orr_gae_flags",
-    "orr_learner_workspace_floats", "orr_ppo_head", "orr_ppo_head_logstd", "orr_gauss_prepare", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
+    "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_history", "orr_policy_forward_history_priv", "orr_history_push", "orr_gae", "orr_gae_flags",
+    "orr_learner_workspace_floats", "orr_ppo_head", "orr_ppo_head_logstd", "orr_gauss_prepare", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_latent_backward", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
 ]
 
 
@@ -333,6 +333,8 @@ def load():
     L.orr_policy_forward_teacher.argtypes = _abi.POLICY_FORWARD_TEACHER_ARGS
     L.orr_policy_forward_history.restype = C.c_int32
     L.orr_policy_forward_history.argtypes = _abi.POLICY_FORWARD_HISTORY_ARGS
+    L.orr_policy_forward_history_priv.restype = C.c_int32
+    L.orr_policy_forward_history_priv.argtypes = _abi.POLICY_FORWARD_HISTORY_PRIV_ARGS
     L.orr_history_push.restype = C.c_int32
     L.orr_history_push.argtypes = _abi.HISTORY_PUSH_ARGS
     # include/openroborl_learner.h
@@ -350,6 +352,8 @@ def load():
     L.orr_regress_head.argtypes = _abi.REGRESS_HEAD_ARGS
     L.orr_history_student_head.restype = C.c_int32
     L.orr_history_student_head.argtypes = _abi.HISTORY_STUDENT_HEAD_ARGS
+    L.orr_latent_backward.restype = C.c_int32
+    L.orr_latent_backward.argtypes = _abi.LATENT_BACKWARD_ARGS
     L.orr_relu_backward.restype = C.c_int32
     L.orr_relu_backward.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
     L.orr_head_backward.restype = C.c_int32

@@ -156,13 +156,18 @@ __device__ __forceinline__ void store_relu(const f32x4 (&acc)[TILES], const floa
 // over the robot's sensor history, z = relu(hist W0 + b0) W1 + b1.  The history tile and the encoder's hidden layer use the LDS of the hidden
 // layers before those are written; everything behind the tile is the teacher kernel's code on the same k-groups, hence its bits.  The kernel
 // takes HistParams and calls layer<> with a UNIT of its own (KP + 1), so the three older instantiations keep their arguments and their code.
+// HIST with KV = KP + kPriv (orr_policy_forward_history_priv): the asymmetric critic of a history policy.  The tile is obs | z | priv, KV words
+// wide: the actor reads obs | z, the history kernel's code on the same k-groups, the critic reads obs | priv - the TRUE row, P.priv - against its
+// (kObs + kPriv) x 512 matrix: k-groups 0..9 from the observation's columns, 10..12 from the row's behind z, accumulated in the teacher
+// kernel's order (hence its value, bit for bit).  A UNIT of its own again (KP + 2).
 template <int KV, int KP = kObs, bool HIST = false>
 __global__ __launch_bounds__(256) void forward_kernel(typename std::conditional<HIST, HistParams, Params>::type P) {
-  constexpr int UNIT = HIST ? KP + 1 : KP;
-  static_assert(!HIST || (KV == kObs + kPriv && KP == KV), "the encoder fills the teacher's privileged columns");
+  constexpr bool CPRIV = HIST && KV == KP + kPriv;
+  constexpr int UNIT = HIST ? (CPRIV ? KP + 2 : KP + 1) : KP;
+  static_assert(!HIST || (KP == kObs + kPriv && (KV == KP || CPRIV)), "the encoder fills the teacher's privileged columns");
   constexpr int kObsStride = KV + 1;            // odd strides: the 16 rows of an A fragment fall into distinct LDS banks
   static_assert(KV >= kObs && KV % 16 == 0 && (kObsStride & 1) == 1, "whole k-groups, odd stride");
-  static_assert(KP == kObs || KP == KV, "the actor reads the observation or the critic's whole tile");
+  static_assert(KP == kObs || KP == KV || CPRIV, "the actor reads the observation or the critic's whole tile");
   static_assert((kRows * kObsStride + kRows * kH0Stride + kRows * kH1Stride) * sizeof(float) <= 160 * 1024, "static LDS beyond the 160 KB of a gfx950 CU");
   __shared__ float s_obs[kRows * kObsStride];
   __shared__ float s_h0[kRows * kH0Stride];
@@ -181,6 +186,14 @@ __global__ __launch_bounds__(256) void forward_kernel(typename std::conditional<
       const f32x4 v = (row0 + r) < P.n ? h4[(size_t)(row0 + r) * (kHist / 4) + c4] : f32x4{0, 0, 0, 0};
       float* d = s_h0 + r * kHistStride + 4 * c4;
       d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+    }
+    if constexpr (CPRIV) {     // the true row behind the estimate's columns, for the critic alone (no critic: P.priv may be NULL)
+      if (P.value) {
+        for (int i = tid; i < kRows * kPriv; i += 256) {
+          const int r = i / kPriv, c = i - r * kPriv;
+          s_obs[r * kObsStride + KP + c] = (row0 + r) < P.n ? P.priv[(size_t)(row0 + r) * kPriv + c] : 0.0f;
+        }
+      }
     }
     __syncthreads();
     {   // encoder layer 0: 512 -> 256; this wave: column tiles [4 wave, 4 wave + 4), the shape of layer 1 below
@@ -227,7 +240,12 @@ __global__ __launch_bounds__(256) void forward_kernel(typename std::conditional<
     if (KP == kObs || P.value) {       // KP == kObs: a constant, no test in those two kernels
 #pragma unroll
       for (int t = 0; t < 8; t++) acc[t] = f32x4{0, 0, 0, 0};
-      if constexpr (KV == kObs) {
+      if constexpr (CPRIV) {                      // the teacher kernel's order: twelve k-groups at depth 2 (ten of obs, two of priv), then one
+        constexpr int kMain = KP / 32 * 32;
+        layer<UNIT, 8, kObs, 2, KP / 16, 0>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
+        layer<UNIT, 8, kMain - kObs, 2, KP / 16, kObs / 16>(acc, P.net.w0_vf, 8 * wave, s_obs + KP, kObsStride, lane);
+        layer<UNIT, 8, KP - kMain, 1, KP / 16, kMain / 16>(acc, P.net.w0_vf, 8 * wave, s_obs + KP + (kMain - kObs), kObsStride, lane);
+      } else if constexpr (KV == kObs) {
         layer<UNIT, 8, kObs, 2>(acc, P.net.w0_vf, 8 * wave, s_obs, kObsStride, lane);
       } else if constexpr (ORR_POLICY_PRIV_SPLIT) {
         constexpr int kMain = KV / 32 * 32;       // the k-groups that depth 2 divides
@@ -521,6 +539,63 @@ __global__ __launch_bounds__(256) void student_head_kernel(HeadParams P) {
   }
 }
 
+// ---- orr_latent_backward (include/openroborl_learner.h): the PPO gradient from the actor's layer 0 into a history policy's latent ------------
+// The last stage of student_head_kernel as a launch of its own: a workgroup owns 16 samples, their g0 tile [16][512] goes to LDS, and waves
+// 0..2 each form one 16-column tile of g_z = g0 W0[160:208]^T (K = 512: 128 MFMAs, a k-ordered chain per element, so a row's bits do not
+// depend on m), add the latent loss's own gradient, and leave the tile's column sums and its share of the loss.  latent_coef == 0 reaches the
+// kernel as a NULL z, a test on a kernel argument: z and target_priv are then not read.  Its own UNIT for layer<>, like every kernel of this file.
+struct LatentParams {
+  const float *g0, *w0zt, *z, *target_priv;
+  float *g_z, *partials;
+  int m, nblk;
+  float g_lat;                                 // 2 latent_coef / m
+};
+constexpr int kLatentUnit = kHeadUnit + 1;
+
+__global__ __launch_bounds__(256) void latent_backward_kernel(LatentParams P) {
+  __shared__ float s_g[kRows * kG0Stride];
+  __shared__ double s_loss[kPriv / 16];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int row0 = blockIdx.x * kRows;
+  for (int i = tid; i < kRows * kH0; i += 256) {      // rows beyond m read as zero
+    const int r = i / kH0, c = i - r * kH0;
+    s_g[r * kG0Stride + c] = (row0 + r) < P.m ? P.g0[(size_t)(row0 + r) * kH0 + c] : 0.0f;
+  }
+  __syncthreads();
+  if (wave < kPriv / 16) {
+    f32x4 acc[1] = {f32x4{0, 0, 0, 0}};
+    layer<kLatentUnit, 1, kH0, 4>(acc, P.w0zt, wave, s_g, kG0Stride, lane);
+    const int c = 16 * wave + (lane & 15), r0 = 4 * (lane >> 4);
+    const bool latent = P.z != nullptr;        // NULL with latent_coef == 0 (the host function sees to it)
+    float cs = 0.0f;
+    double sq = 0.0;                           // the tile's 768 squares in float64 (exact differences): the share is rounded once, on its way out
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = row0 + r0 + r;
+      if (row < P.m) {
+        const size_t o = (size_t)row * kPriv + c;
+        float g = acc[0][r];
+        if (latent) {
+          const float zv = P.z[o], tv = P.target_priv[o];
+          const double d = (double)zv - (double)tv;
+          g += P.g_lat * (zv - tv);
+          sq += d * d;
+        }
+        P.g_z[o] = g;
+        cs += g;
+      }
+    }
+    cs += __shfl_xor(cs, 16, 64);     // the four row groups of a column, in a fixed order
+    cs += __shfl_xor(cs, 32, 64);
+    if (lane < 16) P.partials[(size_t)blockIdx.x * kPriv + c] = cs;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_down(sq, o, 64);
+    if (lane == 0) s_loss[wave] = sq;
+  }
+  __syncthreads();
+  if (tid == 0) P.partials[(size_t)P.nblk * kPriv + blockIdx.x] = (float)(((s_loss[0] + s_loss[1]) + s_loss[2]) / (double)P.m);
+}
+
 }  // namespace
 
 extern "C" {
@@ -620,6 +695,37 @@ int32_t orr_policy_forward_history(const orr_policy_net* net, const orr_history_
   return 0;
 }
 
+int32_t orr_policy_forward_history_priv(const orr_policy_net* net, const orr_history_encoder* enc, const float* obs, const float* hist,
+                                        const float* priv, int32_t n, const float* noise, float std, float clip, float* action, float* raw,
+                                        float* value, float* mean, float* latent, void* stream) {
+  if (!net || !enc || !obs || !hist || !action || n <= 0 || (value && !priv))
+    return orr_fail(-1, "orr_policy_forward_history_priv: bad argument", hipSuccess);
+  const float* const* p = reinterpret_cast<const float* const*>(net);
+  for (int i = 0; i < 12; i++) {
+    if (!p[i]) return orr_fail(-1, "orr_policy_forward_history_priv: orr_policy_net has a null pointer", hipSuccess);
+    if (reinterpret_cast<uintptr_t>(p[i]) & (i % 2 == 0 ? 15 : 3))     // packed weights are read 16 bytes per lane
+      return orr_fail(-1, "orr_policy_forward_history_priv: packed weights must be 16-byte aligned, biases 4-byte aligned", hipSuccess);
+  }
+  const float* const* q = reinterpret_cast<const float* const*>(enc);
+  for (int i = 0; i < 4; i++) {
+    if (!q[i]) return orr_fail(-1, "orr_policy_forward_history_priv: orr_history_encoder has a null pointer", hipSuccess);
+    if (reinterpret_cast<uintptr_t>(q[i]) & (i % 2 == 0 ? 15 : 3))
+      return orr_fail(-1, "orr_policy_forward_history_priv: packed weights must be 16-byte aligned, biases 4-byte aligned", hipSuccess);
+  }
+  if (reinterpret_cast<uintptr_t>(hist) & 15) return orr_fail(-1, "orr_policy_forward_history_priv: hist must be 16-byte aligned", hipSuccess);
+  for (const void* b : {(const void*)obs, (const void*)priv, (const void*)noise, (const void*)action, (const void*)raw, (const void*)value,
+                        (const void*)mean, (const void*)latent})
+    if (reinterpret_cast<uintptr_t>(b) & 3) return orr_fail(-1, "orr_policy_forward_history_priv: buffers must be 4-byte aligned", hipSuccess);
+  HistParams P;
+  P.net = *net; P.obs = obs; P.noise = noise; P.action = action; P.raw = raw; P.value = value; P.mean = mean;
+  P.n = n; P.std = std; P.clip = clip; P.priv = priv;
+  P.enc = *enc; P.hist = hist; P.latent = latent;
+  hipLaunchKernelGGL((forward_kernel<kObs + 2 * kPriv, kObs + kPriv, true>), dim3((unsigned)((n + kRows - 1) / kRows)), dim3(256), 0, (hipStream_t)stream, P);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_policy_forward_history_priv: launch", e);
+  return 0;
+}
+
 int32_t orr_history_push(const float* obs, const uint8_t* done, const float* prev, float* next, int32_t n, void* stream) {
   if (!obs || !next || n <= 0 || (done && !prev)) return orr_fail(-1, "orr_history_push: bad argument", hipSuccess);
   if ((reinterpret_cast<uintptr_t>(prev) & 15) || (reinterpret_cast<uintptr_t>(next) & 15) || (reinterpret_cast<uintptr_t>(obs) & 3))
@@ -660,6 +766,23 @@ int32_t orr_history_student_head(const orr_policy_net* net, const float* w2t, co
   hipLaunchKernelGGL(student_head_kernel, dim3((unsigned)P.nblk), dim3(256), 0, (hipStream_t)stream, P);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_history_student_head: launch", e);
+  return 0;
+}
+
+int32_t orr_latent_backward(const float* g0, const float* w0zt, const float* z, const float* target_priv, int32_t m, float latent_coef,
+                            float* g_z, float* partials, void* stream) {
+  if (!g0 || !w0zt || !g_z || !partials || m <= 0 || (latent_coef != 0.0f && (!z || !target_priv)))
+    return orr_fail(-1, "orr_latent_backward: bad argument", hipSuccess);
+  if (reinterpret_cast<uintptr_t>(w0zt) & 15) return orr_fail(-1, "orr_latent_backward: packed weights must be 16-byte aligned", hipSuccess);
+  for (const void* q : {(const void*)g0, (const void*)z, (const void*)target_priv, (const void*)g_z, (const void*)partials})
+    if (reinterpret_cast<uintptr_t>(q) & 3) return orr_fail(-1, "orr_latent_backward: buffers must be 4-byte aligned", hipSuccess);
+  LatentParams P;
+  P.g0 = g0; P.w0zt = w0zt; P.z = latent_coef != 0.0f ? z : nullptr; P.target_priv = latent_coef != 0.0f ? target_priv : nullptr; P.g_z = g_z; P.partials = partials;
+  P.m = m; P.nblk = ORR_LATENT_BACKWARD_ROWS(m);
+  P.g_lat = 2.0f * latent_coef / (float)m;
+  hipLaunchKernelGGL(latent_backward_kernel, dim3((unsigned)P.nblk), dim3(256), 0, (hipStream_t)stream, P);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_latent_backward: launch", e);
   return 0;
 }
 

@@ -1,9 +1,10 @@
-"""The three learners whose non-GEMM part is hand-written HIP and whose whole epoch replays as one hipGraph
+"""The four learners whose non-GEMM part is hand-written HIP and whose whole epoch replays as one hipGraph
 (include/openroborl_learner.h, csrc/orr_learner.hip):
   FusedPPO             the PPO update of both nets (the torch reference is ppo.PPO: agents/ppo_imitation.py:156-258 + Adam);
+  FusedPPOHistory      that update on a history policy: the actor on obs | encode(hist), the critic on the true privileged row (ppo.PPOHistory);
   FusedDistill         a student's actor regressed on a teacher's means (ppo.Distill);
   FusedDistillHistory  a history student's encoder regressed on the privileged rows, optionally through the frozen actor (ppo.DistillHistory).
-Same arithmetic as their references (which stay the fp32 yardsticks the tests compare these against), different execution.  What the three
+Same arithmetic as their references (which stay the fp32 yardsticks the tests compare these against), different execution.  What they
 share stands once, in _FusedLearner:
   * the trained parameters, their gradients and Adam moments live in ONE flat buffer each (the model's tensors become views of it): the
     gradient all-reduce needs no packing and Adam is one launch (434 k floats for PPO);
@@ -248,13 +249,16 @@ class FusedPPO(_FusedLearner):
     captured epoch on one rank, between replays on several).  update() then returns ppo.STAT_NAMES' five.  No std is frozen into the graphs:
     they are captured once while log_std moves.  A fixed-std model is the path it always was; ent_coef != 0 is refused for it."""
 
+    _history = False            # FusedPPOHistory alone takes a model with an encoder
+
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
                  mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None):
         from . import ppo
         self._need_gpu(model)
-        if getattr(model, "history", 0):
-            raise ValueError("FusedPPO: a history student is trained by FusedDistillHistory only")
-        self.learn_std, self.ent_coef, self.log_std_bounds = ppo._entropy_args(model, "FusedPPO", ent_coef, log_std_bounds or ppo.LOG_STD_BOUNDS)
+        if getattr(model, "history", 0) and not self._history:
+            raise ValueError("FusedPPO: a history policy is trained by FusedPPOHistory (PPO with the critic on the true privileged row) or by "
+                             "FusedDistillHistory")
+        self.learn_std, self.ent_coef, self.log_std_bounds = ppo._entropy_args(model, type(self).__name__, ent_coef, log_std_bounds or ppo.LOG_STD_BOUNDS)
         self.clip, self.vf_coef = float(clip_param), float(vf_coef)
         self.group = group
         # a privileged critic (ppo.ActorCritic(priv_dim=48)): its layer 0 reads x | priv, [M, 160 + 48]; everything behind layer 0 and the
@@ -262,7 +266,9 @@ class FusedPPO(_FusedLearner):
         self.priv_dim = int(getattr(model, "priv_dim", 0))
         # a privileged actor as well (ppo.ActorCritic(actor_priv_dim=48), a teacher): its layer 0 reads the same x | priv
         self.actor_priv_dim = int(getattr(model, "actor_priv_dim", 0))
-        _FusedLearner.__init__(self, model, sorted(model.p), 5 if self.learn_std else 2, lr, adam_eps, minibatch, betas, use_graph, mpi_adam_epsilon)
+        self.head_stats = 5 if self.learn_std else 2          # what the loss head writes; FusedPPOHistory's latent loss follows them
+        _FusedLearner.__init__(self, model, sorted(model.p), self.head_stats + (1 if self._history else 0), lr, adam_eps, minibatch, betas, use_graph,
+                               mpi_adam_epsilon)
 
     def _graph_key(self):
         if self.learn_std:          # the std is read on the device: not a key
@@ -287,8 +293,8 @@ class FusedPPO(_FusedLearner):
 
     def _minibatch(self, P, s):
         """Gather, forward, loss head and backward of minibatch s of the current permutation; gradients land in flat_g."""
-        t, L, M, g = self.torch, self.L, P["M"], self.g
-        st, ws = self._stream(), P["ws"].data_ptr()
+        t, L, M = self.torch, self.L, P["M"]
+        st = self._stream()
         idx = P["perm"][s * M:(s + 1) * M]
         t.index_select(P["obs"], 0, idx, out=P["x"])
         t.index_select(P["aux"], 0, idx, out=P["batch"])
@@ -302,6 +308,14 @@ class FusedPPO(_FusedLearner):
                 xin["pi"] = P["xv"]
         for net in NETS:
             self._mlp_forward(P, net, "_" + net, xin[net])
+        self._loss_head(P, s, st)
+        for net, k, gy in (("pi", 12, P["g_pi"]), ("vf", 1, P["g_vf"])):
+            self._mlp_backward(P, net, "_" + net, xin[net], gy, k, st)
+        _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
+
+    def _loss_head(self, P, s, st):
+        """orr_ppo_head or orr_ppo_head_logstd on the two nets' outputs: g_pi, g_vf, the output layers' bias gradients, stats[s]."""
+        L, M, g, ws = self.L, P["M"], self.g, P["ws"].data_ptr()
         if self.learn_std:
             _lib.check(L.orr_ppo_head_logstd(P["y_pi"].data_ptr(), P["y_vf"].data_ptr(), P["batch"].data_ptr(), self.w[LOGSTD].data_ptr(), M, self.clip,
                                              self.vf_coef, self.ent_coef, P["g_pi"].data_ptr(), P["g_vf"].data_ptr(), g[LOGSTD].data_ptr(),
@@ -310,9 +324,6 @@ class FusedPPO(_FusedLearner):
             _lib.check(L.orr_ppo_head(P["y_pi"].data_ptr(), P["y_vf"].data_ptr(), P["batch"].data_ptr(), M, float(self.model.std), self.clip,
                                       self.vf_coef, P["g_pi"].data_ptr(), P["g_vf"].data_ptr(), g["model/pi/b:0"].data_ptr(),
                                       g["model/vf/b:0"].data_ptr(), P["stats"][s].data_ptr(), ws, st), L)
-        for net, k, gy in (("pi", 12, P["g_pi"]), ("vf", 1, P["g_vf"])):
-            self._mlp_backward(P, net, "_" + net, xin[net], gy, k, st)
-        _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
 
     # ---- the learner interface (ppo.PPO.update) --------------------------------------------------------------------------
     def update(self, obs, actions, adv, ret, old_logp=None, epochs=1, generator=None, priv=None):
@@ -391,6 +402,110 @@ class FusedPPO(_FusedLearner):
             raise RuntimeError("FusedPPO.check_synced: this rank's parameters differ from rank 0's")
 
 
+class FusedPPOHistory(FusedPPO):
+    """PPO on a history policy with an asymmetric critic, on the device (the torch reference is ppo.PPOHistory; RMA's third phase, or
+    one-stage training with an auxiliary estimation loss): the actor reads obs | z, z = encode(hist), the critic obs | priv, the TRUE row.
+      loss = FusedPPO's on those two inputs + latent_coef * mean_i sum_c (z_ic - priv_ic)^2
+    Everything trains.  The flat buffer over all slots (model/enc_* among them), Adam, the log-std clamp, the all-reduce, sync and
+    check_synced are FusedPPO's.  A minibatch: the gathers of obs, hist, priv and aux, the encoder's two GEMMs, the two 3-layer chains and
+    the loss head as in FusedPPO, the critic's backward pass and then the actor's - which leaves d loss / d (the pre-activation of the
+    actor's layer 0) in the shared scratch -, orr_policy_pack of W0_pi[160:]^T (inside the captured epoch, at a fixed address: the actor
+    moves every step), orr_latent_backward from there to d loss / d z (+ the latent loss's own gradient, the column sums behind enc_fc1's
+    bias gradient and the loss), the encoder's backward pass as in FusedDistillHistory, and two orr_colsum_finish: FusedPPO's jobs, then
+    the encoder's (14 jobs for a split minibatch, ORR_COLSUM_MAX_JOBS is 12).  update() returns FusedPPO's stats followed by the latent
+    loss; with latent_coef = 0 orr_latent_backward reads neither z nor priv, and the loss that is still reported costs an orr_regress_head."""
+
+    _history = True
+
+    def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
+                 mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, latent_coef=0.0):
+        import math
+        if not getattr(model, "history", 0):
+            raise ValueError("FusedPPOHistory: the model needs a history encoder (ActorCritic(history=16)); a model without is trained by FusedPPO")
+        self.latent_coef = float(latent_coef)
+        if not (self.latent_coef >= 0.0 and math.isfinite(self.latent_coef)):
+            raise ValueError("FusedPPOHistory: latent_coef must be finite and not negative")
+        FusedPPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, betas, mpi_adam_epsilon, use_graph, ent_coef, log_std_bounds)
+
+    def _graph_key(self):
+        return FusedPPO._graph_key(self) + (self.latent_coef,)
+
+    def _buffers(self, P, f, split, rows):
+        FusedPPO._buffers(self, P, f, split, rows)           # obs, aux, priv and both nets at k0 = 160 + 48; xv = x | xp feeds the critic
+        M, g = P["M"], self.g
+        D, H, Z = _abi.HISTORY_DIM, 256, _abi.POLICY_PRIV_DIM
+        lrows = _abi.latent_backward_rows(M)
+        P.update({"hist": f(P["B"], D), "xh": f(M, D), "he": f(M, H), "z": f(M, Z), "xz": f(M, 160 + Z), "g_z": f(M, Z), "g_he": f(M, H),
+                  "ws1e": f(rows * H), "parte": f(16, D, H) if split else None, "lp": f(49 * lrows), "w0z": f(512, Z),
+                  "w0zt": f(int(self.L.orr_policy_packed_size(512, Z)))})
+        own = [(P["ws1e"], g["model/enc_fc0/b:0"], rows, H)] + ([(P["parte"], g["model/enc_fc0/w:0"], 16, D * H)] if split else [])
+        own.append((P["lp"], g["model/enc_fc1/b:0"], lrows, Z))
+        k = self.head_stats                                  # the latent loss lands behind the head's stats, in the minibatch's own row
+        if self.latent_coef != 0.0:
+            P["jobs_e"] = [_jobs(own + [(P["lp"][Z * lrows:], P["stats"][s][k:], lrows, 1)]) for s in range(P["nmb"])]
+        else:                                                # orr_latent_backward leaves no loss then: orr_regress_head reports it
+            P.update({"wsr": f(int(self.L.orr_learner_workspace_floats(M, 64))), "gr": f(M, Z), "gbr": f(Z)})
+            P["jobs_e"] = [_jobs(own)] * P["nmb"]
+
+    def _minibatch(self, P, s):
+        """Gather, forward, loss head and backward of minibatch s of the current permutation; gradients land in flat_g."""
+        t, L, M, w, g = self.torch, self.L, P["M"], self.w, self.g
+        st = self._stream()
+        Z = _abi.POLICY_PRIV_DIM
+        idx = P["perm"][s * M:(s + 1) * M]
+        for src, dst in (("obs", "x"), ("hist", "xh"), ("priv", "xp"), ("aux", "batch")):
+            t.index_select(P[src], 0, idx, out=P[dst])
+        t._addmm_activation(w["model/enc_fc0/b:0"], P["xh"], w["model/enc_fc0/w:0"], out=P["he"])
+        t.addmm(w["model/enc_fc1/b:0"], P["he"], w["model/enc_fc1/w:0"], out=P["z"])
+        t.cat((P["x"], P["z"]), dim=1, out=P["xz"])
+        t.cat((P["x"], P["xp"]), dim=1, out=P["xv"])
+        xin = {"pi": P["xz"], "vf": P["xv"]}
+        for net in NETS:
+            self._mlp_forward(P, net, "_" + net, xin[net])
+        self._loss_head(P, s, st)
+        # the critic first: the actor's pass then leaves ITS layer-0 gradient in the scratch the two share (gh1, masked by orr_relu_backward)
+        for net, k, gy in (("vf", 1, P["g_vf"]), ("pi", 12, P["g_pi"])):
+            self._mlp_backward(P, net, "_" + net, xin[net], gy, k, st)
+        P["w0z"].copy_(w["model/pi_fc0/w:0"][160:].t())
+        _lib.check(L.orr_policy_pack(P["w0z"].data_ptr(), 512, Z, P["w0zt"].data_ptr(), st), L)
+        lat = self.latent_coef != 0.0
+        _lib.check(L.orr_latent_backward(P["gh1"].data_ptr(), P["w0zt"].data_ptr(), P["z"].data_ptr() if lat else None,
+                                         P["xp"].data_ptr() if lat else None, M, self.latent_coef, P["g_z"].data_ptr(), P["lp"].data_ptr(), st), L)
+        if not lat:
+            _lib.check(L.orr_regress_head(P["z"].data_ptr(), P["xp"].data_ptr(), M, Z, P["gr"].data_ptr(), P["gbr"].data_ptr(),
+                                          P["stats"][s][self.head_stats:].data_ptr(), P["wsr"].data_ptr(), st), L)
+        t.mm(P["he"].t(), P["g_z"], out=g["model/enc_fc1/w:0"])
+        t.mm(P["g_z"], w["model/enc_fc1/w:0"].t(), out=P["g_he"])
+        _lib.check(L.orr_relu_backward(P["g_he"].data_ptr(), P["he"].data_ptr(), M, 256, None, P["ws1e"].data_ptr(), st), L)
+        self._wgrad(P["xh"], P["g_he"], P["parte"], g["model/enc_fc0/w:0"])
+        _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
+        jobs, n_jobs = P["jobs_e"][s]
+        _lib.check(L.orr_colsum_finish(jobs, n_jobs, st), L)
+
+    def update(self, obs, hist, priv, actions, adv, ret, old_logp=None, epochs=1, generator=None):
+        """obs [B,160], hist [B,512] (history_push), priv [B,48] (env.privileged_obs on the same states), actions [B,12] (unclipped samples),
+        adv [B] (already normalised), ret [B] (TD(lambda) targets); returns FusedPPO's stats followed by the latent loss, like
+        ppo.PPOHistory.update."""
+        B = int(obs.shape[0])
+        if tuple(hist.shape) != (B, _abi.HISTORY_DIM) or tuple(priv.shape) != (B, _abi.POLICY_PRIV_DIM):
+            raise ValueError("FusedPPOHistory: hist must have shape (%d, %d) and priv (%d, %d)" % (B, _abi.HISTORY_DIM, B, _abi.POLICY_PRIV_DIM))
+
+        def fill(P):
+            logp = old_logp
+            if logp is None:
+                logp = self.model.log_prob(obs, actions, hist=hist)
+            P["obs"].copy_(obs)
+            P["hist"].copy_(hist)
+            P["priv"].copy_(priv)
+            aux = P["aux"]
+            aux[:, :12].copy_(actions)
+            aux[:, 12].copy_(logp)
+            aux[:, 13].copy_(adv)
+            aux[:, 14].copy_(ret)
+        total, n = self._run(B, fill, epochs, generator, self._world(), self._allreduce if self._several() else None)
+        return (total / n).cpu().numpy()
+
+
 class FusedDistill(_FusedLearner):
     """Policy distillation on the device (the supervised step of DAgger; the torch reference is ppo.Distill): the student's mean is
     regressed on a teacher's, loss = mean over the samples of sum_j (mean_j - target_j)^2 (orr_distill_head).  The actor alone: only
@@ -404,7 +519,7 @@ class FusedDistill(_FusedLearner):
             raise ValueError("FusedDistill: the student's actor must read the 160 observation words only")
         self._need_gpu(student)
         if getattr(student, "history", 0):
-            raise ValueError("FusedDistill: a history student is trained by FusedDistillHistory only")
+            raise ValueError("FusedDistill: a history student is trained by FusedDistillHistory, or with PPO by FusedPPOHistory")
         _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/pi") and k != LOGSTD), 1, lr, adam_eps, minibatch, betas, use_graph)
 
     def _buffers(self, P, f, split, rows):

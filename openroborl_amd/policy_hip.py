@@ -118,7 +118,7 @@ class FusedActorCritic(object):
         return scaled
 
     def forward(self, obs, noise=None, want_mean=False, out_action=None, out_raw=None, out_value=None, priv=None, out_mean=None, want_value=True,
-                hist=None, out_latent=None, scaled=False):
+                hist=None, out_latent=None, scaled=False, critic_priv=None):
         """obs [N,160] float32 on the device; noise [N,12] standard normal or None (deterministic); priv [N,48] float32, the
         privileged observation, for a privileged critic (and only then).
         Returns (clipped action [N,12], raw action [N,12], value [N], mean [N,12] or None); the out_* tensors
@@ -126,6 +126,8 @@ class FusedActorCritic(object):
         want_value=False: no value is written and None is returned for it; a privileged actor's kernel then skips the critic.
         hist [N,512] float32 (history_push), for a history student and instead of priv: the encoder's estimate of the row feeds actor and
         critic (orr_policy_forward_history) and is written to out_latent [N,48] when that is given.
+        critic_priv [N,48] float32, with hist only: the critic reads obs | critic_priv, the TRUE row, while the actor reads the estimate
+        (orr_policy_forward_history_priv: the actor's outputs are orr_policy_forward_history's, the value orr_policy_forward_teacher's).
         scaled=True, for a policy with a learned log-std: `noise` already is exp(log_std) * noise (prepare(), e.g. once for a whole segment)."""
         t = self.torch
         if obs.dtype != t.float32 or not obs.is_contiguous() or obs.device != self.device or obs.dim() != 2 or obs.shape[1] != 160:
@@ -138,6 +140,11 @@ class FusedActorCritic(object):
                 raise ValueError("hist is for a history student (model/enc_fc0/w:0) and for no other")
             if hist.dtype != t.float32 or not hist.is_contiguous() or tuple(hist.shape) != (n, _abi.HISTORY_DIM) or hist.device != self.device:
                 raise ValueError("hist must be a contiguous float32 [N,%d] tensor on the same device" % _abi.HISTORY_DIM)
+            if critic_priv is not None and (critic_priv.dtype != t.float32 or not critic_priv.is_contiguous() or critic_priv.device != self.device
+                                            or tuple(critic_priv.shape) != (n, _abi.POLICY_PRIV_DIM)):
+                raise ValueError("critic_priv must be a contiguous float32 [N,%d] tensor on the same device" % _abi.POLICY_PRIV_DIM)
+        elif critic_priv is not None:
+            raise ValueError("critic_priv goes with hist: the actor reads the encoder's estimate, the critic the true row")
         elif out_latent is not None:
             raise ValueError("out_latent belongs to hist")
         elif (priv is not None) != (self.priv_dim > 0):
@@ -169,6 +176,14 @@ class FusedActorCritic(object):
             raise ValueError("scaled=True is for a policy with %s" % LOGSTD)
         if hist is not None:
             latent = out(out_latent, (n, _abi.POLICY_PRIV_DIM)) if out_latent is not None else None
+            if critic_priv is not None:
+                _lib.check(self.L.orr_policy_forward_history_priv(C.byref(self.net), C.byref(self.enc), obs.data_ptr(), hist.data_ptr(),
+                                                                  critic_priv.data_ptr(), int(n), noise.data_ptr() if noise is not None else None,
+                                                                  std, self.clip, act.data_ptr(), raw.data_ptr(),
+                                                                  val.data_ptr() if val is not None else None,
+                                                                  mean.data_ptr() if mean is not None else None,
+                                                                  latent.data_ptr() if latent is not None else None, self._stream()), self.L)
+                return act, raw, val, mean
             _lib.check(self.L.orr_policy_forward_history(C.byref(self.net), C.byref(self.enc), obs.data_ptr(), hist.data_ptr(), int(n),
                                                          noise.data_ptr() if noise is not None else None, std, self.clip, act.data_ptr(),
                                                          raw.data_ptr(), val.data_ptr() if val is not None else None,

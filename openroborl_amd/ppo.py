@@ -49,7 +49,8 @@ def history_push(hist, obs, done):
 
 def _no_history(model, who):
     if getattr(model, "history", 0):
-        raise ValueError("%s: a history student (history = %d) is trained by DistillHistory / learner_hip.FusedDistillHistory only" % (who, model.history))
+        raise ValueError("%s: a history policy (history = %d) is trained by PPOHistory / learner_hip.FusedPPOHistory (PPO with the critic on the "
+                         "true privileged row) or by DistillHistory / learner_hip.FusedDistillHistory" % (who, model.history))
 
 
 def _entropy_args(model, who, ent_coef, log_std_bounds):
@@ -110,7 +111,8 @@ class ActorCritic(object):
     model/enc_fc1 [256, 48]: a history student.  encode(hist) estimates the privileged row from hist [N, 512] (history_push), and mean() and
     act() take `hist` in the row's place - the teacher's actor and critic on cat(obs, encode(hist)).  Such a policy is deployable: it reads
     its own sensors only.  The encoder is drawn after every other parameter, so history = 0 is the model without, draw for draw.  With
-    `params` the presence of model/enc_fc0/w:0 decides.
+    `params` the presence of model/enc_fc0/w:0 decides.  act(obs, hist=hist, critic_priv=priv) is the asymmetric form PPOHistory trains: the
+    actor on the estimate, the value from the true row.
 
     learn_std = True adds model/pi/logstd:0 [1, 12], filled with log(std): a state-independent log-std that PPO / learner_hip.FusedPPO train
     (with an entropy bonus, ent_coef).  act() then samples mean + exp(log_std) * noise and log_prob() is the per-dimension Gaussian's.  It is
@@ -262,11 +264,19 @@ class ActorCritic(object):
     def value(self, obs, priv=None):
         return self._mlp("vf", self._critic_input(obs, priv))[:, 0]
 
-    def act(self, obs, priv=None, deterministic=False, generator=None, noise=None, out_raw=None, out_value=None, hist=None, out_latent=None):
+    def act(self, obs, priv=None, deterministic=False, generator=None, noise=None, out_raw=None, out_value=None, hist=None, out_latent=None,
+            critic_priv=None):
         """-> (clipped action, raw action, value).  `noise` ([N,12] standard normal) overrides the generator; `priv` ([N,48], the
         privileged observation) goes to a privileged critic, and to a privileged actor.  `hist` ([N,512], a history student's input)
-        takes its place: actor and critic read the encoder's estimate, which out_latent [N,48] receives."""
+        takes its place: actor and critic read the encoder's estimate, which out_latent [N,48] receives.  `critic_priv` ([N,48], with
+        `hist` only) makes the critic asymmetric: the actor still reads the estimate, the value comes from the true row -
+        mean(obs, hist=hist) and value(obs, critic_priv), what PPOHistory trains."""
         t = self.torch
+        if critic_priv is not None:
+            if hist is None:
+                raise ValueError("critic_priv goes with hist: the actor reads the encoder's estimate, the critic the true row")
+            if tuple(critic_priv.shape) != (obs.shape[0], pol.PRIV_DIM):
+                raise ValueError("critic_priv must have shape (%d, %d), got %s" % (obs.shape[0], pol.PRIV_DIM, tuple(critic_priv.shape)))
         if hist is not None:
             if priv is not None:
                 raise ValueError("give priv or hist, not both")
@@ -289,7 +299,7 @@ class ActorCritic(object):
                 noise = t.randn((obs.shape[0], 12), device=obs.device, generator=generator)
             if hist is not None:
                 a, raw, v, _ = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value, hist=hist,
-                                                  out_latent=out_latent)
+                                                  out_latent=out_latent, **({} if critic_priv is None else {"critic_priv": critic_priv}))
             else:
                 a, raw, v, _ = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value, priv=priv)
             return a, raw, v
@@ -298,10 +308,10 @@ class ActorCritic(object):
             if noise is None and not deterministic:
                 noise = t.randn(mu.shape, device=mu.device, generator=generator)
             a = mu if deterministic else mu + (self.p[LOGSTD].exp() if self.learn_std else self.std) * noise
-            return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, priv)
+            return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, priv if critic_priv is None else critic_priv)
 
-    def log_prob(self, obs, actions, priv=None):
-        mu = self.mean(obs, priv)
+    def log_prob(self, obs, actions, priv=None, hist=None):
+        mu = self.mean(obs, priv, hist)
         if self.learn_std:
             ls = self.p[LOGSTD]
             z = (actions - mu) * self.torch.exp(-ls)
@@ -322,13 +332,16 @@ class PPO(object):
     log_std is clamped to log_std_bounds after every optimiser step, and update() returns the five STAT_NAMES.  A fixed-std model is the
     code path it always was and returns (surrogate, value loss); ent_coef != 0 is refused for it, the term would have no gradient."""
 
+    _history = False            # PPOHistory alone takes a model with an encoder
+
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, ent_coef=0.0,
                  log_std_bounds=LOG_STD_BOUNDS):
         import torch
         self.torch = torch
-        _no_history(model, "PPO")
+        if not self._history:
+            _no_history(model, "PPO")
         self.model = model
-        self.learn_std, self.ent_coef, self.log_std_bounds = _entropy_args(model, "PPO", ent_coef, log_std_bounds)
+        self.learn_std, self.ent_coef, self.log_std_bounds = _entropy_args(model, type(self).__name__, ent_coef, log_std_bounds)
         self.clip = clip_param
         self.minibatch = int(minibatch)
         self.vf_coef = vf_coef
@@ -399,6 +412,72 @@ class PPO(object):
                     stats.append(t.stack((surr.detach(), vf.detach(), ent.detach(), kl, clipped)))
                 else:
                     stats.append(t.stack((surr.detach(), vf.detach())))   # stays on the device: no sync per minibatch
+        return t.stack(stats).mean(dim=0).cpu().numpy()
+
+
+class PPOHistory(PPO):
+    """PPO on a history policy with an asymmetric critic, in plain torch (RMA's third phase, or one-stage training with an auxiliary
+    estimation loss; the fp32 reference of learner_hip.FusedPPOHistory).  The actor reads obs | encode(hist) and is trained by the clipped
+    surrogate, the gradient flowing through its layer 0 into the encoder; the critic reads obs | priv, the TRUE privileged row:
+      loss = surrogate(log_prob(obs, a, hist=hist)) + vf_coef * mean((value(obs, priv) - ret)^2) [- ent_coef * H]
+             + latent_coef * mean_i sum_c (encode(hist)_ic - priv_ic)^2
+    All parameters train: actor, critic, encoder, and the log-std of a learn-std model.  update() returns PPO's stats followed by the latent
+    loss, which is reported even when its coefficient is 0."""
+
+    _history = True
+
+    def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, ent_coef=0.0,
+                 log_std_bounds=LOG_STD_BOUNDS, latent_coef=0.0):
+        if not getattr(model, "history", 0):
+            raise ValueError("PPOHistory: the model needs a history encoder (ActorCritic(history=16)); a model without is trained by PPO")
+        self.latent_coef = float(latent_coef)
+        if not (self.latent_coef >= 0.0 and math.isfinite(self.latent_coef)):
+            raise ValueError("PPOHistory: latent_coef must be finite and not negative")
+        PPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, ent_coef, log_std_bounds)
+
+    def update(self, obs, hist, priv, actions, adv, ret, old_logp=None, epochs=1, generator=None):
+        """obs [B,160], hist [B,512] (history_push), priv [B,48] (env.privileged_obs on the same states), actions [B,12] (unclipped
+        samples), adv [B] (already normalised), ret [B] (TD(lambda) targets)."""
+        t = self.torch
+        B = obs.shape[0]
+        if tuple(hist.shape) != (B, HISTORY_DIM) or tuple(priv.shape) != (B, pol.PRIV_DIM):
+            raise ValueError("PPOHistory: hist must have shape (%d, %d) and priv (%d, %d)" % (B, HISTORY_DIM, B, pol.PRIV_DIM))
+        if old_logp is None:
+            with t.no_grad():
+                old_logp = self.model.log_prob(obs, actions, hist=hist)
+        stats = []
+        for _ in range(epochs):
+            perm = t.randperm(B, device=obs.device, generator=generator)
+            obs_p, hist_p, priv_p, act_p, adv_p, ret_p, old_p = (x[perm] for x in (obs, hist, priv, actions, adv, ret, old_logp))
+            for s in range(0, B, self.minibatch):
+                e = s + self.minibatch
+                z = self.model.encode(hist_p[s:e])             # one encode() for the actor and the latent loss
+                logp = self.model.log_prob(obs_p[s:e], act_p[s:e], priv=z)
+                ratio = t.exp(logp - old_p[s:e])
+                a = adv_p[s:e]
+                surr = -t.min(ratio * a, t.clamp(ratio, 1.0 - self.clip, 1.0 + self.clip) * a).mean()
+                vf = ((self.model.value(obs_p[s:e], priv_p[s:e]) - ret_p[s:e]) ** 2).mean()
+                latent = ((z - priv_p[s:e]) ** 2).sum(dim=1).mean()
+                loss = surr + self.vf_coef * vf
+                if self.learn_std:
+                    ent = self.model.p[LOGSTD].sum() + ENTROPY_CONST
+                    loss = loss - self.ent_coef * ent
+                if self.latent_coef != 0.0:
+                    loss = loss + self.latent_coef * latent
+                self.opt.zero_grad(set_to_none=True)
+                loss.backward()
+                self._allreduce_grads()
+                self.opt.step()
+                row = [surr.detach(), vf.detach()]
+                if self.learn_std:
+                    with t.no_grad():
+                        self.model.p[LOGSTD].clamp_(*self.log_std_bounds)
+                        log_ratio = (logp - old_p[s:e]).detach()
+                        r = ratio.detach()
+                        row += [ent.detach(), ((r - 1.0) - log_ratio).mean(), ((r < 1.0 - self.clip) | (r > 1.0 + self.clip)).to(r.dtype).mean()]
+                if hasattr(self.model, "mark_updated"):
+                    self.model.mark_updated()
+                stats.append(t.stack(row + [latent.detach()]))
         return t.stack(stats).mean(dim=0).cpu().numpy()
 
 

@@ -35,7 +35,7 @@ def _teacher_labels(teacher, obs, priv, out_mean, out_action):
 
 
 def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generator=None, noise=None, priv=None, teacher=None, teacher_mask=None,
-                    hist=None):
+                    hist=None, critic_priv=False):
     """Run `horizon` env steps of all robots.  Returns a dict of [T, N, ...] tensors + the final observation.
     noise: optional [T, N, 12] standard-normal samples for the fused policy (default: drawn from `generator`).
     A policy with a privileged critic (priv_dim > 0) also gets env.privileged_obs() at every step: "priv" [T, N, 48] and "last_priv" are
@@ -48,7 +48,9 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
     A history student (policy.history > 0) reads hist[k] in the place of priv[k]: "hist" [T, N, 512] and "last_hist" are returned next to
     "priv" and "last_priv" (the encoder's regression targets); after every step and its privileged_obs the history is pushed
     (policy_hip.history_push(obs[k + 1], dones[k], hist[k], out=hist[k + 1])).  hist: the one that belongs to `obs` (the previous segment's
-    last_hist; None = computed here with done=None)."""
+    last_hist; None = computed here with done=None).
+    critic_priv=True, for a history policy only (PPO on it: ppo.PPOHistory): the critic is asymmetric, step k's forward pass gets hist[k] for
+    the actor and priv[k], the true row, for the value.  False: the estimate feeds both."""
     t = env.torch
     n = env.num_robot
     dev = env.device
@@ -58,6 +60,8 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
     history = int(getattr(policy, "history", 0))
     if teacher_mask is not None and teacher is None:
         raise ValueError("teacher_mask without a teacher")
+    if critic_priv and not history:
+        raise ValueError("critic_priv is for a history policy (policy.history > 0): every other critic reads what its actor reads or its own priv")
     hbuf = None
     if history:
         from . import policy_hip
@@ -87,6 +91,8 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
         noise = None
     for k in range(horizon):
         row = {"hist": hbuf[k]} if history else ({"priv": pbuf[k]} if priv_dim else {})     # what the policy reads next to obs
+        if critic_priv:
+            row["critic_priv"] = pbuf[k]
         if fused:   # one fused launch writes the raw action and the value straight into the buffers
             clipped, _, _ = policy.act(obs, deterministic=deterministic, noise=None if noise is None else noise[k],
                                        out_raw=buf["actions"][k], out_value=buf["vpred"][k], **row)
@@ -144,7 +150,9 @@ class GraphRollout(object):
 
     With a history student (policy.history > 0) the segment also holds hist [T + 1, N, 512]: hist[k] goes to the forward pass in priv[k]'s
     place, and after step_into and privileged_obs the push history_push(obs[k + 1], dones[k], hist[k], out=hist[k + 1]) runs inside the
-    captured segment; "hist" and "last_hist" are returned next to "priv" and "last_priv", the encoder's regression targets.
+    captured segment; "hist" and "last_hist" are returned next to "priv" and "last_priv", the encoder's regression targets.  critic_priv=True
+    (a history policy only; PPO on it) also hands priv[k] to the forward pass: the actor reads the estimate, the value comes from the true row
+    (orr_policy_forward_history_priv).  False is the segment without, launch for launch.
 
     With a learned log-std (policy.learn_std) the segment opens with ONE orr_gauss_prepare over noise [T N][12]: it writes scaled [T, N, 12] =
     exp(log_std) * noise and logp, the forward passes read scaled[k] with std = 1, and no std is among the launch parameters - log_std is read
@@ -154,7 +162,7 @@ class GraphRollout(object):
     The returned tensors are views of the static buffers: they are overwritten by the next collect() (clone what must survive it,
     e.g. the last row of `dones` that the next segment's GAE takes as first_starts)."""
 
-    def __init__(self, env, policy, horizon, teacher=None):
+    def __init__(self, env, policy, horizon, teacher=None, critic_priv=False):
         t = env.torch
         if getattr(policy, "fused", None) is None or (teacher is not None and getattr(teacher, "fused", None) is None):
             raise RuntimeError("GraphRollout needs the fused policy (ActorCritic.enable_fused()); the plain path is collect_rollout()")
@@ -168,6 +176,9 @@ class GraphRollout(object):
         self.priv = f(T + 1, n, self.priv_dim or PRIV_DIM) if (self.priv_dim or teacher is not None) else None
         self.history = int(getattr(policy, "history", 0))
         self.hist = f(T + 1, n, HISTORY_DIM) if self.history else None
+        if critic_priv and not self.history:
+            raise ValueError("critic_priv is for a history policy (policy.history > 0)")
+        self.critic_priv = bool(critic_priv)
         if teacher is not None:
             self.teacher_mean, self.teacher_clipped, self.step_action = f(T, n, 12), f(n, 12), f(n, 12)
             self.teacher_mask = t.zeros(n, dtype=t.uint8, device=dev)
@@ -194,7 +205,10 @@ class GraphRollout(object):
             fused.prepare(self.noise.view(T * n, 12), self.scaled.view(T * n, 12), self.logp.view(T * n))
             noise, more = self.scaled, {"scaled": True}
         for k in range(self.T):
-            if self.history:
+            if self.critic_priv:
+                fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], hist=self.hist[k],
+                              critic_priv=self.priv[k], **more)
+            elif self.history:
                 fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], hist=self.hist[k], **more)
             elif self.priv_dim:
                 fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], priv=self.priv[k], **more)

@@ -1,7 +1,7 @@
 """The privileged critic's two kernels against what they sit next to, 4096 robots, same process, alternated (the protocol of
 tools/diag/variant_time.py: medians of 5 x 300 back-to-back launches, every candidate sees the same clocks; the 300 launches are one
 captured graph, so that no host time sits between them):
-python tools/diag/privileged_time.py [--alt-policy-lib PATH] [--sections forward,history,row,head]
+python tools/diag/privileged_time.py [--alt-policy-lib PATH] [--sections forward,history,row,head,history_priv,latent]
 
   forward   orr_policy_forward_priv, orr_policy_forward_teacher and orr_policy_forward_teacher with value = NULL (the labelling call of
             distillation: no critic) against orr_policy_forward, random weights; with --alt-policy-lib also orr_policy_forward_priv of a
@@ -14,7 +14,11 @@ python tools/diag/privileged_time.py [--alt-policy-lib PATH] [--sections forward
   head      orr_history_student_head at m = 16384 (a history student's action loss: forward through the frozen actor, both losses, backward
             to the latent, one launch) against the same mathematics composed from the older pieces on the same inputs: three torch GEMMs
             with bias / ReLU epilogues, orr_distill_head, orr_head_backward, two torch GEMMs with orr_relu_backward between them,
-            orr_regress_head and the sum of the two gradients; and against orr_regress_head alone (the latent loss without the action loss)"""
+            orr_regress_head and the sum of the two gradients; and against orr_regress_head alone (the latent loss without the action loss)
+  history_priv  orr_policy_forward_history_priv (a history policy with an asymmetric critic: the critic's layer 0 reads the true row) against
+            orr_policy_forward_history, each with and without a value buffer; the MFMA counts are the same
+  latent    orr_latent_backward at m = 16384 (PPO on a history policy: the gradient from the actor's layer 0 into the latent, the latent loss,
+            the column sums) against the same mathematics composed from torch.mm, orr_regress_head, an add and a column sum"""
 import argparse
 import ctypes as C
 import sys
@@ -29,7 +33,7 @@ N, WARMUP, ROUNDS, LAUNCHES = 4096, 300, 5, 300
 
 ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
 ap.add_argument("--alt-policy-lib", default="")
-ap.add_argument("--sections", default="forward,history,row,head")
+ap.add_argument("--sections", default="forward,history,row,head,history_priv,latent")
 args = ap.parse_args()
 sections = args.sections.split(",")
 dev = torch.device("cuda", 0)
@@ -187,3 +191,58 @@ if "head" in sections:
     # MFMAs per wave and tile of 16 rows: 416 + 512 + 64 forward, 16 + 512 + 128 backward = 1648; the teacher's full forward pass 1920
     print("orr_history_student_head: %d workgroups of 1648 MFMAs per wave in %.4f ms; orr_policy_forward_teacher: 256 workgroups of 1920 (section forward)"
           % (M // 16, med[1]))
+
+# ---- history_priv ----
+if "history_priv" in sections:
+    student = ppo.ActorCritic(dev, seed=3, priv_dim=_abi.POLICY_PRIV_DIM, actor_priv_dim=_abi.POLICY_PRIV_DIM, history=_abi.HISTORY_STEPS)
+    fh = policy_hip.FusedActorCritic(student.p, dev, std=0.125)
+    hist = torch.randn(N, _abi.HISTORY_DIM, device=dev, generator=g)
+    med = report(["orr_policy_forward_history", "orr_policy_forward_history_priv", "orr_policy_forward_history, value = NULL",
+                  "orr_policy_forward_history_priv, value = NULL"],
+                 [lambda: fh.forward(obs, noise, out_action=act, out_raw=raw, out_value=val, hist=hist),
+                  lambda: fh.forward(obs, noise, out_action=act, out_raw=raw, out_value=val, hist=hist, critic_priv=priv),
+                  lambda: fh.forward(obs, None, out_action=act, out_raw=raw, out_mean=mean, want_value=False, hist=hist),
+                  lambda: fh.forward(obs, None, out_action=act, out_raw=raw, out_mean=mean, want_value=False, hist=hist, critic_priv=priv)])
+    # MFMAs per wave: 2496 in both; the asymmetric critic's layer 0 is three layer<> calls (10 + 2 + 1 k-groups) instead of two (12 + 1), and
+    # the tile is 48 words wider (a 3 KB load of the true row)
+    print("orr_policy_forward_history_priv against orr_policy_forward_history: ratio %.4f (the MFMA counts give 1.0000)" % (med[1] / med[0]))
+    print("the same with value = NULL: ratio %.4f (the same code but the kernel's LDS, 112.2 -> 115.2 KB)" % (med[3] / med[2]))
+
+# ---- latent ----
+if "latent" in sections:
+    from openroborl_amd import _lib  # noqa: E402,F811
+    M, Z = 16384, _abi.POLICY_PRIV_DIM
+    L = ft.L
+    st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)   # noqa: E731
+    w0z = teacher.p["model/pi_fc0/w:0"].detach()[160:]                    # [48][512]
+    w0zt = w0z.t().contiguous()
+    packed = torch.empty(int(L.orr_policy_packed_size(512, Z)), device=dev)
+    _lib.check(L.orr_policy_pack(w0zt.data_ptr(), 512, Z, packed.data_ptr(), st()), L)
+    g0 = torch.randn(M, 512, device=dev, generator=g) * (torch.rand(M, 512, device=dev, generator=g) < 0.5) / M
+    z, tp = (torch.randn(M, Z, device=dev, generator=g) for _ in range(2))
+    rows = _abi.latent_backward_rows(M)
+    g_z, lp, gb, loss = torch.empty(M, Z, device=dev), torch.empty(49 * rows, device=dev), torch.empty(Z, device=dev), torch.empty(1, device=dev)
+    jobs = (_abi.OrrColsumJob * 2)(_abi.OrrColsumJob(lp.data_ptr(), gb.data_ptr(), rows, Z), _abi.OrrColsumJob(lp.data_ptr() + 4 * Z * rows, loss.data_ptr(), rows, 1))
+    coef = 0.5
+
+    def fused_latent():
+        _lib.check(L.orr_latent_backward(g0.data_ptr(), packed.data_ptr(), z.data_ptr(), tp.data_ptr(), M, coef, g_z.data_ptr(), lp.data_ptr(), st()), L)
+        _lib.check(L.orr_colsum_finish(jobs, 2, st()), L)
+
+    def kernel_alone():
+        _lib.check(L.orr_latent_backward(g0.data_ptr(), packed.data_ptr(), z.data_ptr(), tp.data_ptr(), M, coef, g_z.data_ptr(), lp.data_ptr(), st()), L)
+    gin, g_lat, g_ref, gb_ref, gb48, stat = (torch.empty(s, device=dev) for s in ((M, Z), (M, Z), (M, Z), (Z,), (Z,), (1,)))
+    ws = torch.empty(int(L.orr_learner_workspace_floats(M, 64)), device=dev)
+    w0z_t = w0z.t()
+
+    def composed():          # the library GEMM (N = 48), the latent loss head, the sum of the two gradients, and a column sum in torch's order
+        torch.mm(g0, w0z_t, out=gin)
+        _lib.check(L.orr_regress_head(z.data_ptr(), tp.data_ptr(), M, Z, g_lat.data_ptr(), gb48.data_ptr(), stat.data_ptr(), ws.data_ptr(), st()), L)
+        torch.add(gin, g_lat, alpha=coef, out=g_ref)
+        torch.sum(g_ref, dim=0, out=gb_ref)
+    fused_latent(); composed(); torch.cuda.synchronize()
+    scale = float(g_ref.abs().max())
+    print("m = %d: orr_latent_backward and the composition agree to %.2e of the gradient's scale, the column sums to %.2e, the loss to %.2e"
+          % (M, float((g_z - g_ref).abs().max()) / scale, float((gb - gb_ref).abs().max()) / float(gb_ref.abs().max()), abs(loss.item() - stat.item()) / stat.item()))
+    report(["the composition (torch.mm + orr_regress_head + add + column sum)", "orr_latent_backward + orr_colsum_finish", "orr_latent_backward alone"],
+           [composed, fused_latent, kernel_alone])

@@ -3,6 +3,8 @@ one minibatch update (forward, backward, optimiser) timed separately.
 
 usage:  python tools/train_breakdown.py [robots=4096] [horizon=32] [minibatch=16384] [epochs=2] [torch-learner] [learn-std]
         learn-std: a model with a learned log-std and ent_coef = 0.01 (train.py --learn-std --ent-coef 0.01)
+        privileged-actor | history-ppo | history-ppo-latent: the update alone of a teacher (train.py --privileged-actor) or of a history policy
+        (train.py --history-ppo, and with --latent-coef 0.5): FusedPPO / FusedPPOHistory, or their torch references with torch-learner
         rocprofv3 --kernel-trace --stats -- python3 tools/train_breakdown.py ... update-only      (per-kernel view of the update alone)
 """
 import os
@@ -13,7 +15,9 @@ import torch  # noqa: E402
 from openroborl_amd import learner_hip, ppo, rollout  # noqa: E402
 from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
 
-argv = [a for a in sys.argv[1:] if a not in ("update-only", "torch-learner", "learn-std")]
+MODES = ("privileged-actor", "history-ppo", "history-ppo-latent")
+argv = [a for a in sys.argv[1:] if a not in ("update-only", "torch-learner", "learn-std") + MODES]
+mode = next((a for a in sys.argv[1:] if a in MODES), None)
 update_only = "update-only" in sys.argv
 torch_learner = "torch-learner" in sys.argv
 learn_std = "learn-std" in sys.argv
@@ -38,10 +42,26 @@ def ms(f, reps):
     return e0.elapsed_time(e1) / reps
 
 
-model = ppo.ActorCritic(dev, seed=0, learn_std=learn_std).enable_fused()
-learner = ppo.PPO(model, lr=1e-4, minibatch=mb, **entropy) if torch_learner else learner_hip.FusedPPO(model, lr=1e-4, minibatch=mb, **entropy)
 gen = torch.Generator(device=dev).manual_seed(0)
 B = T * n
+if mode:     # a wide model's update, and nothing else
+    history = mode.startswith("history-ppo")
+    model = ppo.ActorCritic(dev, seed=0, learn_std=learn_std, priv_dim=48, actor_priv_dim=48, history=16 if history else 0).enable_fused()
+    more = dict(entropy, latent_coef=0.5 if mode.endswith("latent") else 0.0) if history else entropy
+    cls = ((ppo.PPOHistory if history else ppo.PPO) if torch_learner else (learner_hip.FusedPPOHistory if history else learner_hip.FusedPPO))
+    learner = cls(model, lr=1e-4, minibatch=mb, **more)
+    obs, hist, priv, act = (torch.randn(B, c, device=dev) for c in (160, 512, 48, 12))
+    adv, ret, logp = torch.randn(B, device=dev), torch.randn(B, device=dev), torch.randn(B, device=dev) * 0.1 - 10.0
+    if history:
+        run = lambda: learner.update(obs, hist, priv, act * 0.2, adv, ret, old_logp=logp, epochs=epochs, generator=gen)   # noqa: E731
+    else:
+        run = lambda: learner.update(obs, act * 0.2, adv, ret, old_logp=logp, epochs=epochs, generator=gen, priv=priv)   # noqa: E731
+    t_update = ms(run, 30)
+    print("%s, %s update: %.2f ms per iteration (%d samples, minibatch %d, %d epochs = %d optimiser steps: %.3f ms each)"
+          % (mode, cls.__name__, t_update, B, mb, epochs, epochs * (B // mb), t_update / (epochs * (B // mb))))
+    sys.exit(0)
+model = ppo.ActorCritic(dev, seed=0, learn_std=learn_std).enable_fused()
+learner = ppo.PPO(model, lr=1e-4, minibatch=mb, **entropy) if torch_learner else learner_hip.FusedPPO(model, lr=1e-4, minibatch=mb, **entropy)
 obs = torch.randn(B, 160, device=dev)
 act = torch.randn(B, 12, device=dev) * 0.2
 adv = torch.randn(B, device=dev)

@@ -9,6 +9,7 @@ leaves the GPU.  Counterpart of `python3 OpenRoboRL/run.py --task imitation_lear
   python train.py --task imitation_learning_laikago --iters 200 --privileged-actor --push 0.02,0.2,0.5 --save teacher.zip   (a teacher)
   python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --push 0.02,0.2,0.5 --save student.zip   (its student)
   python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --history --push 0.02,0.2,0.5 --save student.zip   (a history student)
+  python train.py --task imitation_learning_laikago --iters 200 --history-ppo --model-file student.zip --push 0.02,0.2,0.5 --save tuned.zip   (PPO on it)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py ...
 """
 import argparse
@@ -81,6 +82,15 @@ def main():
                          "sensors (IMU, last action, motor angles: 512 words), trained to estimate the privileged observation from them "
                          "(learner_hip.FusedDistillHistory; --torch-learner: ppo.DistillHistory).  The log carries latent_loss; --save writes "
                          "the teacher's variables + model/enc_*, a zip that loads here (--eval) and not in the reference")
+    ap.add_argument("--history-ppo", action="store_true",
+                    help="PPO on a history policy (RMA's third phase, or one-stage training): the actor reads its observation and the encoder's "
+                         "estimate from the last 16 steps of its own sensors, the critic reads the simulator's TRUE privileged observation, and "
+                         "actor, critic and encoder all train (learner_hip.FusedPPOHistory; --torch-learner: ppo.PPOHistory).  --model-file: a "
+                         "history student's zip is fine-tuned, a teacher's zip (--privileged-actor) gets a fresh encoder, none: fresh weights.  "
+                         "The environment is --privileged-actor's.  The log carries latent_loss; --save writes a history zip that --eval runs")
+    ap.add_argument("--latent-coef", type=float, default=0.0, metavar="C",
+                    help="--history-ppo: weight of the auxiliary estimation loss, the squared error of the encoder's output against the "
+                         "privileged observation (default 0: the encoder is trained by the PPO gradient through the actor alone)")
     ap.add_argument("--distill-action-coef", type=float, default=0.0, metavar="C",
                     help="--distill --history: weight of the action loss, the squared error of the student's actor output on (observation, "
                          "encoder output) against the teacher's mean, its gradient flowing through the frozen actor into the encoder "
@@ -127,11 +137,17 @@ def main():
         torch.cuda.tunable.enable(True)
     if args.eval:
         return evaluate(args, torch, pol, ppo, VecQuadrupedEnv)
+    if args.history_ppo and (args.distill or args.history or args.privileged_critic or args.privileged_actor):
+        raise SystemExit("train.py: --history-ppo is a mode of its own; not with --distill / --history / --privileged-critic / --privileged-actor")
+    if args.latent_coef != 0.0 and not args.history_ppo:
+        raise SystemExit("train.py: --latent-coef belongs to --history-ppo")
+    if not args.latent_coef >= 0.0:
+        raise SystemExit("train.py: --latent-coef must not be negative")
     args.privileged_critic = args.privileged_critic or args.privileged_actor
     if args.distill and (args.privileged_critic or args.torch_policy):
         raise SystemExit("train.py: --distill trains a plain student with the fused rollout; not with --privileged-critic / --privileged-actor / --torch-policy")
     if args.history and not args.distill:
-        raise SystemExit("train.py: --history belongs to --distill")
+        raise SystemExit("train.py: --history belongs to --distill (PPO on a history policy is --history-ppo)")
     if (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0) and not args.history:
         raise SystemExit("train.py: --distill-action-coef / --distill-latent-coef belong to --distill --history")
     if args.distill_action_coef < 0.0 or args.distill_latent_coef < 0.0:
@@ -140,7 +156,7 @@ def main():
         raise SystemExit("train.py: --learn-std belongs to PPO; the distillation learners neither read nor train a log-std")
     if (args.ent_coef != 0.0 or args.log_std_bounds is not None) and not args.learn_std:
         raise SystemExit("train.py: --ent-coef / --log-std-bounds belong to --learn-std")
-    privileged = args.privileged_critic or bool(args.distill)       # somebody reads env.privileged_obs
+    privileged = args.privileged_critic or bool(args.distill) or args.history_ppo       # somebody reads env.privileged_obs
     rank, world, local = odist.init_from_env()
     if args.distill and world > 1:
         raise SystemExit("train.py: --distill runs on one rank")
@@ -157,11 +173,19 @@ def main():
     if args.history:
         return distill(args, torch, pol, ppo, rollout, odist, env, history_student(args, torch, pol, ppo, dev), dev)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
-    # same seed -> identical replicas.  (--model-file: the critic's width is the file's)
-    model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic else 0,
-                            actor_priv_dim=pol.PRIV_DIM if args.privileged_actor else 0, std=args.init_std, learn_std=args.learn_std)
+    if args.history_ppo and params is not None and "model/enc_fc0/w:0" not in params:
+        # a teacher's zip: its nets + a fresh encoder (the rule of --distill --history); the log-std, if any, is the teacher's
+        model = history_student(args, torch, pol, ppo, dev, path=args.model_file, fused=False, std=args.init_std, learn_std=args.learn_std)
+    else:
+        # same seed -> identical replicas.  (--model-file: the critic's width is the file's)
+        wide = args.privileged_actor or args.history_ppo
+        model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic or wide else 0,
+                                actor_priv_dim=pol.PRIV_DIM if wide else 0, std=args.init_std, learn_std=args.learn_std,
+                                history=ppo.HISTORY_STEPS if args.history_ppo else 0)
     if model.learn_std != args.learn_std and not args.distill:
         raise SystemExit("train.py: --model-file has %s, --learn-std says otherwise" % ("a learned log-std" if model.learn_std else "no log-std"))
+    if args.history_ppo:
+        return history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, world)
     if bool(model.priv_dim) != args.privileged_critic:
         raise SystemExit("train.py: --model-file has a %s critic, --privileged-critic says otherwise" % ("privileged" if model.priv_dim else "plain"))
     if bool(model.actor_priv_dim) != args.privileged_actor:
@@ -252,12 +276,13 @@ def main():
         torch.distributed.destroy_process_group()
 
 
-def history_student(args, torch, pol, ppo, dev):
-    """--distill TEACHER.zip --history: the teacher's parameters + a fresh encoder (seeded by --seed), on the fused path."""
-    params = pol.load_parameters(args.distill)
+def history_student(args, torch, pol, ppo, dev, path=None, fused=True, **model_kw):
+    """--distill TEACHER.zip --history: the teacher's parameters + a fresh encoder (seeded by --seed), on the fused path.  --history-ppo with a
+    teacher's --model-file (`path`): the same rule, the model's std arguments in model_kw."""
+    params = pol.load_parameters(path or args.distill)
     if np.shape(params["model/pi_fc0/w:0"])[0] != 160 + pol.PRIV_DIM:
-        raise SystemExit("train.py: --history needs a teacher with a privileged actor (--privileged-actor)")
-    student = ppo.ActorCritic(dev, seed=args.seed, priv_dim=pol.PRIV_DIM, actor_priv_dim=pol.PRIV_DIM, history=ppo.HISTORY_STEPS)
+        raise SystemExit("train.py: %s needs a teacher with a privileged actor (--privileged-actor)" % ("--history-ppo --model-file" if path else "--history"))
+    student = ppo.ActorCritic(dev, seed=args.seed, priv_dim=pol.PRIV_DIM, actor_priv_dim=pol.PRIV_DIM, history=ppo.HISTORY_STEPS, **model_kw)
     with torch.no_grad():
         for k, v in params.items():
             if k.startswith("model/enc_"):
@@ -266,7 +291,67 @@ def history_student(args, torch, pol, ppo, dev):
                 student.p[k].copy_(torch.as_tensor(v))
             else:
                 student.extra[k] = np.asarray(v, dtype=np.float32).copy()
-    return student.enable_fused()
+    return student.enable_fused() if fused else student
+
+
+def history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, world):
+    """--history-ppo: PPO on a history policy.  The collector hands hist[k] to the actor and priv[k], the true row, to the critic
+    (critic_priv=True), the bootstrap is the critic on the last true row, and the learner trains actor, critic and encoder."""
+    if not model.history:
+        raise SystemExit("train.py: --history-ppo could not make a history policy of --model-file")
+    if not args.torch_policy:
+        model.enable_fused()
+    B = args.num_robot * args.horizon
+    entropy = dict(ent_coef=args.ent_coef, log_std_bounds=tuple(args.log_std_bounds or ppo.LOG_STD_BOUNDS)) if args.learn_std else {}
+    if args.torch_learner:
+        learner = ppo.PPOHistory(model, lr=args.lr, minibatch=args.minibatch, latent_coef=args.latent_coef, **entropy)
+    else:
+        from openroborl_amd import learner_hip
+        mb = learner_hip.FusedPPOHistory.fit_minibatch(B, args.minibatch)
+        if mb < 256 and B >= 4096:
+            raise SystemExit("train.py: %d samples per segment have no divisor between 256 and %d; pick another --num-robot / --horizon "
+                             "or use --torch-learner (handles a short last minibatch)" % (B, args.minibatch))
+        learner = learner_hip.FusedPPOHistory(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam, latent_coef=args.latent_coef, **entropy)
+        learner.sync()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(args.seed * 1000 + rank)
+    collector = None if args.torch_policy else rollout.GraphRollout(env, model, args.horizon, critic_priv=True)
+    obs, priv, hist, first_starts = env.reset(), None, None, None
+    t0, samples, log = time.time(), 0, []
+    for it in range(args.iters):
+        buf = (collector.collect(obs, generator=gen, priv=priv, hist=hist) if collector
+               else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv, hist=hist, critic_priv=True))
+        obs, priv, hist = buf["last_obs"], buf["last_priv"], buf["last_hist"]
+        with torch.no_grad():
+            boot = model.value(obs, priv)
+        adv, ret = rollout.gae_fused(buf["rewards"], buf["vpred"], buf["dones"], 0.95, 0.95, bootstrap=boot, normalize=True, eps=1e-8,
+                                     legacy_gae_index=args.legacy_gae_index, first_starts=first_starts)
+        first_starts = buf["dones"][-1].clone()
+        losses = learner.update(buf["obs"].reshape(B, -1), buf["hist"].reshape(B, -1), buf["priv"].reshape(B, -1), buf["actions"].reshape(B, -1),
+                                adv.reshape(-1), ret.reshape(-1), old_logp=buf["logp"].reshape(-1) if "logp" in buf else None,
+                                epochs=args.epochs, generator=gen)
+        samples += B * world
+        if (world > 1 or os.environ.get("ORR_FORCE_DIST", "0") == "1") and args.sync_check_every > 0 and it % args.sync_check_every == args.sync_check_every - 1 and hasattr(learner, "check_synced"):
+            learner.check_synced()
+        stats = odist.gather_env_episodes(env, args.horizon)
+        if rank == 0 and (it % 10 == 0 or it == args.iters - 1):
+            rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
+                   "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2), "episodes": stats.sums[0],
+                   "surr": round(float(losses[0]), 4), "vf": round(float(losses[1]), 4), "latent_loss": round(float(losses[-1]), 6)}
+            if args.learn_std:
+                std = model.std
+                rec.update({k: round(float(v), 6) for k, v in zip(ppo.STAT_NAMES[2:], losses[2:5])})
+                rec.update({"std_min": round(float(std.min()), 5), "std_max": round(float(std.max()), 5)})
+            log.append(rec)
+            print(json.dumps(rec), flush=True)
+    if rank == 0 and args.save:
+        pol.save_parameters_zip(args.save, model.state_dict())
+    if rank == 0 and args.log:
+        with open(args.log, "w") as f:
+            json.dump(log, f, indent=1)
+    env.close()
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
 
 
 def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
