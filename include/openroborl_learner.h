@@ -18,6 +18,8 @@
  *   orr_colsum_finish  the column sums behind all bias gradients of a minibatch in one launch
  *   orr_relu_backward  ReLU mask in place + bias gradient
  *   orr_adam_step      Adam on the flat parameter vector, step counter on the device (the whole update replays as one hipGraph)
+ *   orr_update_control the controls of a step from the flat gradient, on the device: clip coefficient of its norm, non-finite guard, KL gate
+ *   orr_adam_step_ctl  orr_adam_step reading those controls and a learning-rate multiplier from device memory (no capture when they change)
  * All pointers are device pointers, float32, row-major and 16-byte aligned; calls are asynchronous on the caller's stream; every
  * reduction runs in a fixed order (no float atomics: the same inputs give the same bits).  Return 0 or a negative code with text in
  * orr_last_error() (openroborl_hip.h).
@@ -178,6 +180,61 @@ int32_t orr_colsum_finish(const orr_colsum_job* jobs, int32_t n_jobs, void* stre
 #define ORR_ADAM_MPI_EPSILON 1
 int32_t orr_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                       float grad_scale, int32_t flags, int32_t* state, void* stream);
+
+/* The controls of an optimiser step, in caller-owned DEVICE memory: twelve 32-bit words, 16-byte aligned.  orr_adam_step_ctl reads them at run
+ * time, so a captured step follows a learning-rate schedule, a gradient clip, a non-finite guard and a KL gate without being captured again.
+ * The caller initialises the record once: lr_mult = kl_lr_mult = grad_scale = 1, every other word 0. */
+typedef struct orr_update_ctl {
+  /* written by the host */
+  float lr_mult;          /* the schedule's multiplier of lr */
+  /* written by orr_update_control */
+  float kl_lr_mult;       /* the KL-adaptive multiplier of lr, within [kl_lr_lo, kl_lr_hi]; starts at 1 */
+  float grad_scale;       /* the clip coefficient of the last call: 1, max_norm / (norm + 1e-6) when that is smaller, 0 for a non-finite norm */
+  int32_t skip;           /* != 0: orr_adam_step_ctl changes nothing.  bit 0: the last call saw a non-finite norm or KL (rewritten by every
+                           * call); bit 1: KL stop, set by a call and kept until the host clears it */
+  /* diagnostics */
+  float grad_norm;        /* the last call's norm (may be Inf or NaN) */
+  float grad_norm_max;    /* the largest finite norm since the host last cleared the counters */
+  float grad_norm_sum;    /* the sum of the finite norms, and */
+  int32_t n_calls;        /* how many there were: calls with a finite norm and KL */
+  int32_t n_clipped;      /* calls with grad_scale < 1 and a finite norm */
+  int32_t n_nonfinite;    /* calls that set bit 0 */
+  int32_t n_kl_skipped;   /* calls that left bit 1 set, i.e. steps skipped by the KL stop (the one that tripped it included) */
+  int32_t reserved;
+} __attribute__((aligned(16))) orr_update_ctl;
+int32_t orr_sizeof_update_ctl(void);
+
+/* Floats of `partials` orr_update_control needs for a gradient of n floats (one per workgroup of ORR_UPDATE_CONTROL_BLOCK_FLOATS); -1 for n <= 0. */
+#define ORR_UPDATE_CONTROL_BLOCK_FLOATS 1024
+int64_t orr_update_control_partials(int64_t n);
+
+/* Produces the controls of the next orr_adam_step_ctl from the flat gradient, in two launches (a streaming pass that leaves one partial sum of
+ * squares per workgroup, and one wave that adds them in index order and writes the record).
+ *   norm = pre_scale * ||g||_2     g [n] 16-byte aligned, n need not be a multiple of 4 and nothing at or beyond n is read; pre_scale is
+ *                                  orr_adam_step's grad_scale (1 / world size).  float32 accumulation in an order fixed by n alone: no float
+ *                                  atomics, the same inputs give the same bits; the sum of squares is within (17 + ceil(P / 64)) * 2^-24
+ *                                  relative of the exact one, P = orr_update_control_partials(n)
+ *   max_norm > 0                   grad_scale = min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s formula; n_clipped counts
+ *                                  grad_scale < 1.  max_norm <= 0: grad_scale = 1
+ *   a non-finite norm              (a NaN or Inf element; or a square or the sum above float32's range, i.e. |g_i| > 1.8e19 or a norm above that:
+ *                                  this overflow is reported as non-finite, not computed in a wider format) sets bit 0 of skip, counts in
+ *                                  n_nonfinite and gives grad_scale = 0.  A non-finite *kl counts the same.  A finite call clears bit 0
+ *   kl | NULL                      device pointer to this minibatch's approx_kl (stats[3] of orr_ppo_head_logstd), 4-byte aligned, read at run time
+ *   kl_stop > 0                    *kl > kl_stop sets bit 1 of skip, which stays set until the host clears it.  Every call that leaves it set
+ *                                  counts in n_kl_skipped
+ *   kl_target > 0                  on a call that leaves skip == 0 (a step that is taken), once:  *kl > 2 kl_target: kl_lr_mult =
+ *                                  max(kl_lr_lo, kl_lr_mult / 1.5);  otherwise 0 < *kl < kl_target / 2: kl_lr_mult = min(kl_lr_hi, kl_lr_mult * 1.5)
+ * Refused (nothing is launched or written): a NULL g, partials or ctl, g or ctl not 16-byte aligned, n <= 0, kl_lr_lo > kl_lr_hi (or a NaN
+ * bound), kl_stop > 0 or kl_target > 0 with kl == NULL. */
+int32_t orr_update_control(const float* g, int64_t n, float pre_scale, float max_norm, const float* kl, float kl_stop, float kl_target,
+                           float kl_lr_lo, float kl_lr_hi, float* partials, orr_update_ctl* ctl, void* stream);
+
+/* orr_adam_step under a control record written earlier on the same stream: lr * ctl->lr_mult * ctl->kl_lr_mult and
+ * grad_scale * ctl->grad_scale take the places of lr and grad_scale.  With ctl->skip != 0 the launch changes nothing - not p, m, v nor state:
+ * a skipped step is no Adam step and the bias correction does not advance.  With the record's three factors 1 and skip 0 it gives
+ * orr_adam_step's bits (one kernel body; times 1.0f is exact).  ctl 16-byte aligned; everything else as orr_adam_step. */
+int32_t orr_adam_step_ctl(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                          float grad_scale, int32_t flags, int32_t* state, const orr_update_ctl* ctl, void* stream);
 
 #ifdef __cplusplus
 }

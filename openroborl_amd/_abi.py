@@ -194,6 +194,25 @@ class OrrColsumJob(C.Structure):
     _fields_ = [("partials", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]
 
 
+class OrrUpdateCtl(C.Structure):
+    """include/openroborl_learner.h: orr_update_ctl, twelve 32-bit words in device memory (UPDATE_CTL_WORDS names them in order)."""
+    _fields_ = [("lr_mult", C.c_float), ("kl_lr_mult", C.c_float), ("grad_scale", C.c_float), ("skip", C.c_int32),
+                ("grad_norm", C.c_float), ("grad_norm_max", C.c_float), ("grad_norm_sum", C.c_float), ("n_calls", C.c_int32),
+                ("n_clipped", C.c_int32), ("n_nonfinite", C.c_int32), ("n_kl_skipped", C.c_int32), ("reserved", C.c_int32)]
+
+
+UPDATE_CTL_WORDS = tuple(n for n, _ in OrrUpdateCtl._fields_)
+UPDATE_CTL_SKIP_NONFINITE, UPDATE_CTL_SKIP_KL = 1, 2          # the bits of orr_update_ctl::skip
+UPDATE_CONTROL_BLOCK_FLOATS = 1024                            # ORR_UPDATE_CONTROL_BLOCK_FLOATS
+# include/openroborl_learner.h: int32_t orr_update_control(const float* g, int64_t n, float pre_scale, float max_norm, const float* kl | NULL,
+#   float kl_stop, float kl_target, float kl_lr_lo, float kl_lr_hi, float* partials, orr_update_ctl* ctl, void* stream)
+UPDATE_CONTROL_ARGS = [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                       C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_adam_step_ctl(orr_adam_step's arguments up to state, const orr_update_ctl* ctl, void* stream)
+ADAM_STEP_CTL_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
+                      C.c_void_p, C.c_void_p, C.c_void_p]
+
+
 # include/openroborl_policy.h: int32_t orr_policy_forward_teacher(const orr_policy_net* net, const float* obs, const float* priv, int32_t n,
 #   const float* noise, float std, float clip, float* action, float* raw, float* value | NULL, float* mean, void* stream) - orr_policy_forward_priv's
 # arguments; w0_pi is a packed (160 + 48) x 512 matrix as well

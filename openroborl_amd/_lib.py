@@ -108,6 +108,7 @@ EXPORTS = [
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_history", "orr_policy_forward_history_priv", "orr_history_push", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_ppo_head_logstd", "orr_gauss_prepare", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_latent_backward", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
+    "orr_sizeof_update_ctl", "orr_update_control_partials", "orr_update_control", "orr_adam_step_ctl",
 ]
 
 
@@ -364,12 +365,20 @@ def load():
     L.orr_colsum_finish.argtypes = [C.POINTER(_abi.OrrColsumJob), C.c_int32, vp]
     L.orr_adam_step.restype = C.c_int32
     L.orr_adam_step.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp]
+    L.orr_sizeof_update_ctl.restype = C.c_int32
+    L.orr_update_control_partials.restype = C.c_int64
+    L.orr_update_control_partials.argtypes = [C.c_int64]
+    L.orr_update_control.restype = C.c_int32
+    L.orr_update_control.argtypes = _abi.UPDATE_CONTROL_ARGS
+    L.orr_adam_step_ctl.restype = C.c_int32
+    L.orr_adam_step_ctl.argtypes = _abi.ADAM_STEP_CTL_ARGS
     if L.orr_abi_version() != _abi.ABI_VERSION:
         raise RuntimeError("libopenroborl_hip.so ABI version mismatch")
     if (L.orr_sizeof_config() != C.sizeof(_abi.OrrConfig) or L.orr_sizeof_model() != C.sizeof(_abi.OrrModel)
             or L.orr_sizeof_task_noise() != C.sizeof(_abi.OrrTaskNoise) or L.orr_sizeof_sensor_noise() != C.sizeof(_abi.OrrSensorNoise)
-            or L.orr_sizeof_randomizer() != C.sizeof(_abi.OrrRandomizer) or L.orr_sizeof_push() != C.sizeof(_abi.OrrPush)):
-        raise RuntimeError("ctypes struct layout does not match include/openroborl_hip.h")
+            or L.orr_sizeof_randomizer() != C.sizeof(_abi.OrrRandomizer) or L.orr_sizeof_push() != C.sizeof(_abi.OrrPush)
+            or L.orr_sizeof_update_ctl() != C.sizeof(_abi.OrrUpdateCtl)):
+        raise RuntimeError("ctypes struct layout does not match include/openroborl_hip.h / openroborl_learner.h")
     _lib = L
     return L
 

@@ -437,9 +437,9 @@ __global__ __launch_bounds__(kThreads) void colsum_finish_kernel(FinishJobs J, i
 // ---- Adam on the flat parameter vector ----------------------------------------------------------------------------------------
 // Every workgroup reads the step count when it starts; the LAST one to finish (ticket) advances it, so a captured launch replays.
 constexpr int kAdamThreads = 64;     // 434 k parameters = 1700 one-wave workgroups: enough of them in flight to cover the load latency
-__global__ __launch_bounds__(kAdamThreads) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, long long n, float lr, float b1, float b2, float eps, float gscale,
-                                                        int flags, int* __restrict__ state) {
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                          long long n, float lr, float b1, float b2, float eps, float gscale, int flags,
+                                          int* __restrict__ state) {
   const int t = __atomic_load_n(&state[0], __ATOMIC_RELAXED) + 1;
   const float bc1 = 1.0f - powf(b1, (float)t), bc2 = 1.0f - powf(b2, (float)t);
   const float sq2 = sqrtf(bc2);
@@ -470,6 +470,98 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(float* __restrict__ 
       __atomic_store_n(&state[1], 0, __ATOMIC_RELAXED);
     }
   }
+}
+
+__global__ __launch_bounds__(kAdamThreads) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, long long n, float lr, float b1, float b2, float eps, float gscale,
+                                                        int flags, int* __restrict__ state) {
+  adam_body(p, g, m, v, n, lr, b1, b2, eps, gscale, flags, state);
+}
+
+// orr_adam_step_ctl: the same step with its controls read from the device.  Every workgroup reads the record (written earlier on the stream:
+// no workgroup of this launch writes it); a set skip word ends them all before the first load, so nobody takes a ticket and state stands.
+// Times 1.0f is exact: the neutral record gives adam_kernel's bits.
+__global__ __launch_bounds__(kAdamThreads) void adam_ctl_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, long long n, float lr, float b1, float b2, float eps,
+                                                            float gscale, int flags, int* __restrict__ state, const orr_update_ctl* __restrict__ ctl) {
+  if (ctl->skip != 0) return;
+  adam_body(p, g, m, v, n, lr * ctl->lr_mult * ctl->kl_lr_mult, b1, b2, eps, gscale * ctl->grad_scale, flags, state);
+}
+
+// ---- the update controls: gradient norm -> clip coefficient, non-finite guard, KL gate (orr_update_control) ---------------------------------
+// One streaming pass over the flat gradient (434 k floats = 1.7 MB for PPO): 16-byte loads, two of them in flight per lane, 1024 floats per
+// two-wave workgroup = 425 workgroups for PPO (the launch is latency-bound like adam_kernel's: many small workgroups cover it).  A workgroup's
+// sum of squares goes to partials[blockIdx.x]; a second one-wave launch adds the partials in index order and writes the record, so the order
+// of every addition is fixed by n alone: no float atomics, no ticket, the same inputs give the same bits.
+// Error bound of the sum of squares S (all terms >= 0, so every rounding is relative to a partial sum <= S): the longest chain of roundings
+// a term passes is 1 (its square) + 2 (the four of a load) + 1 (the lane's two loads) + 6 (wave tree) + 1 (the two waves) = 11 in the first
+// launch, ceil(P / 64) (a lane's partials, one after the other) + 6 (wave tree) in the second, P = ceil(n / 1024):
+//   |S - S_exact| <= (17 + ceil(P / 64)) * 2^-24 * S_exact        (n = 434701: P = 425, 24 * 2^-24 = 1.4e-6)
+// A square above 3.4e38 (|x| > 1.8e19) or a sum that passes it overflows to Inf: the norm then counts as non-finite like a NaN or Inf element.
+constexpr int kCtlThreads = 128, kCtlLoads = 2;
+constexpr int kCtlBlockFloats = kCtlThreads * 4 * kCtlLoads;
+static_assert(kCtlBlockFloats == ORR_UPDATE_CONTROL_BLOCK_FLOATS, "the header's partials count");
+static_assert(sizeof(orr_update_ctl) == 48 && alignof(orr_update_ctl) == 16, "orr_update_ctl: twelve 32-bit words, 16-byte aligned");
+
+__device__ inline float sumsq4(f4 a) { return (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w); }
+
+__global__ __launch_bounds__(kCtlThreads) void grad_sumsq_kernel(const float* __restrict__ g, long long n, float* __restrict__ partials) {
+  __shared__ float red[kCtlThreads / 64];
+  const long long base = (long long)blockIdx.x * kCtlBlockFloats + (long long)threadIdx.x * 4;
+  f4 a[kCtlLoads];
+#pragma unroll
+  for (int u = 0; u < kCtlLoads; u++) {
+    const long long i4 = base + (long long)u * kCtlThreads * 4;
+    if (i4 + 3 < n) {
+      a[u] = *reinterpret_cast<const f4*>(g + i4);
+    } else {          // the tail: nothing at or beyond n is read
+      a[u] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (i4 < n) a[u].x = g[i4];
+      if (i4 + 1 < n) a[u].y = g[i4 + 1];
+      if (i4 + 2 < n) a[u].z = g[i4 + 2];
+    }
+  }
+  const float s = wave_sum(sumsq4(a[0]) + sumsq4(a[1]));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1];
+}
+
+__device__ inline bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+__global__ __launch_bounds__(64) void update_control_kernel(const float* __restrict__ partials, long long nparts, float pre_scale, float max_norm,
+                                                            const float* __restrict__ kl_ptr, float kl_stop, float kl_target, float kl_lr_lo,
+                                                            float kl_lr_hi, orr_update_ctl* __restrict__ ctl) {
+  float s = 0.0f;
+  for (long long b = threadIdx.x; b < nparts; b += 64) s += partials[b];
+  s = wave_sum(s);
+  if (threadIdx.x != 0) return;
+  const float norm = pre_scale * sqrtf(s);
+  const float kl = kl_ptr ? *kl_ptr : 0.0f;
+  const bool bad = !finite_f(s) || !finite_f(norm) || !finite_f(kl);
+  int skip = (ctl->skip & 2) | (bad ? 1 : 0);
+  if (!bad && kl_stop > 0.0f && kl > kl_stop) skip |= 2;
+  if (skip == 0 && kl_target > 0.0f) {         // the rsl_rl rule, once per step that is taken
+    float mult = ctl->kl_lr_mult;
+    if (kl > 2.0f * kl_target) mult = fmaxf(kl_lr_lo, mult / 1.5f);
+    else if (kl > 0.0f && kl < 0.5f * kl_target) mult = fminf(kl_lr_hi, mult * 1.5f);
+    ctl->kl_lr_mult = mult;
+  }
+  float scale = 1.0f;
+  if (bad) {
+    scale = 0.0f;
+    ctl->n_nonfinite += 1;
+  } else {
+    if (max_norm > 0.0f) scale = fminf(1.0f, max_norm / (norm + 1e-6f));
+    if (scale < 1.0f) ctl->n_clipped += 1;
+    ctl->grad_norm_max = fmaxf(ctl->grad_norm_max, norm);
+    ctl->grad_norm_sum += norm;
+    ctl->n_calls += 1;
+  }
+  if (skip & 2) ctl->n_kl_skipped += 1;
+  ctl->grad_norm = norm;
+  ctl->grad_scale = scale;
+  ctl->skip = skip;
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -639,6 +731,42 @@ int32_t orr_adam_step(float* p, const float* g, float* m, float* v, int64_t n, f
                      beta1, beta2, eps, grad_scale, (int)flags, (int*)state);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_adam_step: launch", e);
+  return 0;
+}
+
+int32_t orr_sizeof_update_ctl(void) { return (int32_t)sizeof(orr_update_ctl); }
+
+int64_t orr_update_control_partials(int64_t n) { return n > 0 ? (n + kCtlBlockFloats - 1) / kCtlBlockFloats : -1; }
+
+int32_t orr_update_control(const float* g, int64_t n, float pre_scale, float max_norm, const float* kl, float kl_stop, float kl_target,
+                           float kl_lr_lo, float kl_lr_hi, float* partials, orr_update_ctl* ctl, void* stream) {
+  if (!g || !partials || !ctl || n <= 0) return orr_fail(-1, "orr_update_control: bad argument", hipSuccess);
+  if (!aligned16(g) || !aligned16(ctl)) return orr_fail(-1, "orr_update_control: g and ctl must be 16-byte aligned", hipSuccess);
+  if ((reinterpret_cast<uintptr_t>(partials) & 3) || (reinterpret_cast<uintptr_t>(kl) & 3))
+    return orr_fail(-1, "orr_update_control: partials and kl must be 4-byte aligned", hipSuccess);
+  if (!(kl_lr_lo <= kl_lr_hi)) return orr_fail(-1, "orr_update_control: kl_lr_lo must not exceed kl_lr_hi", hipSuccess);
+  if (!kl && (kl_stop > 0.0f || kl_target > 0.0f)) return orr_fail(-1, "orr_update_control: a KL threshold needs kl", hipSuccess);
+  const long long nparts = (n + kCtlBlockFloats - 1) / kCtlBlockFloats;
+  if (nparts > 0x7fffffffLL) return orr_fail(-1, "orr_update_control: n too large", hipSuccess);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nparts), dim3(kCtlThreads), 0, (hipStream_t)stream, g, (long long)n, partials);
+  hipLaunchKernelGGL(update_control_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)partials, nparts, pre_scale, max_norm, kl, kl_stop,
+                     kl_target, kl_lr_lo, kl_lr_hi, ctl);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_update_control: launch", e);
+  return 0;
+}
+
+int32_t orr_adam_step_ctl(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                          float grad_scale, int32_t flags, int32_t* state, const orr_update_ctl* ctl, void* stream) {
+  if (!p || !g || !m || !v || !state || !ctl || n <= 0) return orr_fail(-1, "orr_adam_step_ctl: bad argument", hipSuccess);
+  if (flags & ~ORR_ADAM_MPI_EPSILON) return orr_fail(-1, "orr_adam_step_ctl: unknown flag", hipSuccess);
+  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || !aligned16(ctl))
+    return orr_fail(-1, "orr_adam_step_ctl: buffers must be 16-byte aligned", hipSuccess);
+  const long long per_block = 4LL * kAdamThreads;
+  hipLaunchKernelGGL(adam_ctl_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kAdamThreads), 0, (hipStream_t)stream, p, g, m, v,
+                     (long long)n, lr, beta1, beta2, eps, grad_scale, (int)flags, (int*)state, ctl);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_adam_step_ctl: launch", e);
   return 0;
 }
 

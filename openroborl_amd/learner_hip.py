@@ -19,6 +19,12 @@ share stands once, in _FusedLearner:
 Scalar hyper-parameters (lr, betas, eps, clip, vf_coef, a fixed policy std, the loss coefficients, the world size) are by-value kernel
 arguments, i.e. frozen into a captured graph: the driver compares them with the values the graphs were captured with and captures again
 when one changed (the reference feeds optim_stepsize * cur_lrmult every step: ppo1/pposgd_simple.py; run.py uses schedule='constant').
+The update controls are the exception: with max_grad_norm, device_lr or (FusedPPO, FusedPPOHistory) a KL rule the optimiser step reads a
+record in device memory (orr_update_ctl) that orr_update_control writes inside the captured epoch from the flat gradient's norm and the
+minibatch's approx_kl - the clip coefficient, a guard that skips the step of a non-finite gradient, the KL stop of the rest of an update()
+and the KL-adaptive learning rate -, and that set_lr_mult() writes for a schedule (the reference's schedule='linear',
+agents/ppo_imitation.py:296-299): none of them captures again and none costs a host round trip; control_stats() reads the diagnostics.
+Without those arguments a learner launches what it always did (orr_adam_step, self.ctl is None).
 There is no fallback: without a GPU and the HIP library the constructors raise.
 """
 import ctypes as C
@@ -39,9 +45,15 @@ class _FusedLearner(object):
     """What the fused learners share: the flat buffers of the parameters `names` of `model`, Adam, the plan cache, the chain of a 3-layer
     net and the update driver.  A learner adds its plan's buffers (_buffers), its _minibatch and its update."""
 
-    def __init__(self, model, names, stats, lr, adam_eps, minibatch, betas, use_graph, mpi_adam_epsilon=False):
+    def __init__(self, model, names, stats, lr, adam_eps, minibatch, betas, use_graph, mpi_adam_epsilon=False, max_grad_norm=None, device_lr=False,
+                 kl_stop=None, kl_target=None, kl_lr_bounds=None):
         import torch
+        from . import ppo
         self.torch = torch
+        self.max_grad_norm, self.kl_stop, self.kl_target, self.kl_lr_bounds = ppo._control_args(type(self).__name__, max_grad_norm, kl_stop, kl_target,
+                                                                                                kl_lr_bounds or ppo.KL_LR_BOUNDS)
+        self.kl_on = self.kl_stop is not None or self.kl_target is not None
+        control = self.max_grad_norm is not None or self.kl_on or bool(device_lr)
         self.model = model
         self.dev = model.device
         self.L = _lib.load()
@@ -70,6 +82,42 @@ class _FusedLearner(object):
                 model.p[k] = self.w[k].detach().requires_grad_(True)        # same storage: the torch path and the zip export keep working
         self._mark_updated()
         self._plans = {}
+        # ---- the update controls (orr_update_control + orr_adam_step_ctl): one orr_update_ctl on the device and the norm's partial sums ----
+        self.ctl = None                      # None: the path without, orr_adam_step
+        self.lr_mult = 1.0
+        if control:
+            self.ctl = torch.zeros(len(_abi.UPDATE_CTL_WORDS), dtype=torch.int32, device=self.dev)
+            self.ctl_f = self.ctl.view(torch.float32)            # the same twelve words, for the float members
+            self.ctl_f[:3].fill_(1.0)                            # lr_mult, kl_lr_mult, grad_scale
+            self.ctl_partials = torch.zeros(int(self.L.orr_update_control_partials(self.total)), dtype=torch.float32, device=self.dev)
+
+    # ---- the update controls -------------------------------------------------------------------------------------------------
+    def _need_ctl(self, who):
+        if self.ctl is None:
+            raise RuntimeError("%s.%s needs the control path: construct the learner with device_lr=True (or max_grad_norm / a KL rule)"
+                               % (type(self).__name__, who))
+
+    def set_lr_mult(self, x):
+        """The schedule's multiplier of lr from the next step on: one device word, written on the stream.  Never a capture."""
+        self._need_ctl("set_lr_mult")
+        self.lr_mult = float(x)
+        self.ctl_f[_abi.UPDATE_CTL_WORDS.index("lr_mult")].fill_(self.lr_mult)
+
+    def control_stats(self):
+        """The diagnostics of the control path since the last call (one sync), and clears the counters on the device."""
+        self._need_ctl("control_stats")
+        raw = self.ctl.cpu()
+        w = dict(zip(_abi.UPDATE_CTL_WORDS, zip(raw.tolist(), raw.view(self.torch.float32).tolist())))       # name -> (as int, as float)
+        first = _abi.UPDATE_CTL_WORDS.index("grad_norm_max")
+        self.ctl[first:].zero_()
+        calls = w["n_calls"][0]
+        return {"grad_norm": w["grad_norm"][1], "grad_norm_max": w["grad_norm_max"][1], "grad_norm_mean": w["grad_norm_sum"][1] / max(calls, 1),
+                "calls": calls, "clipped": w["n_clipped"][0], "skipped_nonfinite": w["n_nonfinite"][0], "skipped_kl": w["n_kl_skipped"][0],
+                "lr_mult": w["lr_mult"][1], "kl_lr_mult": w["kl_lr_mult"][1]}
+
+    def _kl_ptr(self, P, s):
+        """Device address of minibatch s's approx_kl for the KL rules; None: no rule (the learners without a PPO loss head)."""
+        return None
 
     @staticmethod
     def _need_gpu(model):
@@ -85,7 +133,10 @@ class _FusedLearner(object):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
     def _graph_key(self):
-        return (self.lr, self.b1, self.b2, self.eps, self.adam_flags)
+        key = (self.lr, self.b1, self.b2, self.eps, self.adam_flags)
+        if self.ctl is not None:      # orr_update_control's by-value arguments (the multipliers and the gate live on the device: no keys)
+            key += ("ctl", self.max_grad_norm, self.kl_stop, self.kl_target) + self.kl_lr_bounds
+        return key
 
     @staticmethod
     def fit_minibatch(num_samples, minibatch):
@@ -95,10 +146,19 @@ class _FusedLearner(object):
             m -= 1
         return m
 
-    def _adam(self, world):
-        _lib.check(self.L.orr_adam_step(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.total,
-                                        self.lr, self.b1, self.b2, self.eps, 1.0 / world, self.adam_flags, self.state.data_ptr(),
-                                        self._stream()), self.L)
+    def _adam(self, world, kl=None):
+        """The optimiser step on flat_g; on the control path orr_update_control first (kl: _kl_ptr of the minibatch), then the step under it."""
+        L, st = self.L, self._stream()
+        if self.ctl is None:
+            _lib.check(L.orr_adam_step(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.total,
+                                       self.lr, self.b1, self.b2, self.eps, 1.0 / world, self.adam_flags, self.state.data_ptr(), st), L)
+            return
+        lo, hi = self.kl_lr_bounds
+        _lib.check(L.orr_update_control(self.flat_g.data_ptr(), self.total, 1.0 / world, self.max_grad_norm or 0.0, kl, self.kl_stop or 0.0,
+                                        self.kl_target or 0.0, lo, hi, self.ctl_partials.data_ptr(), self.ctl.data_ptr(), st), L)
+        _lib.check(L.orr_adam_step_ctl(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.total,
+                                       self.lr, self.b1, self.b2, self.eps, 1.0 / world, self.adam_flags, self.state.data_ptr(),
+                                       self.ctl.data_ptr(), st), L)
 
     def _wgrad(self, x, g, part, out):
         """out = x^T g.  Tall batches: 16 partial products in one batched GEMM (see ppo._wgrad: the library's plain GEMM fills a
@@ -161,20 +221,21 @@ class _FusedLearner(object):
         for s in range(P["nmb"]):
             self._minibatch(P, s)
             if reduce:
-                reduce()
-            self._adam(world)
+                reduce(P, s)
+            self._adam(world, self._kl_ptr(P, s))
 
     def _capture(self, P, several):
         """One rank: one graph for the whole epoch.  Several ranks: one graph per minibatch (the collective runs between replays)."""
         t = self.torch
-        keep = [x.clone() for x in (self.flat_p, self.m, self.v, self.state)]
+        live = (self.flat_p, self.m, self.v, self.state) + (() if self.ctl is None else (self.ctl,))
+        keep = [x.clone() for x in live]
         P["perm"].copy_(t.arange(P["B"], device=self.dev))
         side = t.cuda.Stream(device=self.dev)
         side.wait_stream(t.cuda.current_stream(self.dev))
         with t.cuda.stream(side):                    # warm-up outside the capture: library handles, workspaces, kernel selection
             for _ in range(2):
                 self._minibatch(P, 0)
-                self._adam(1)
+                self._adam(1, self._kl_ptr(P, 0))
         t.cuda.current_stream(self.dev).wait_stream(side)
         graphs = []
         if not several:
@@ -182,7 +243,7 @@ class _FusedLearner(object):
             with t.cuda.graph(gr):
                 for s in range(P["nmb"]):
                     self._minibatch(P, s)
-                    self._adam(1)
+                    self._adam(1, self._kl_ptr(P, s))
             graphs.append(gr)
         else:
             pool = None
@@ -192,7 +253,7 @@ class _FusedLearner(object):
                     self._minibatch(P, s)
                 pool = pool or gr.pool()
                 graphs.append(gr)
-        for dst, src in zip((self.flat_p, self.m, self.v, self.state), keep):     # the warm-up took real optimiser steps: undo them
+        for dst, src in zip(live, keep):     # the warm-up took real optimiser steps (and control calls): undo them
             dst.copy_(src)
         P["graphs"] = graphs
 
@@ -215,6 +276,8 @@ class _FusedLearner(object):
                 self._capture(P, several)
                 P["graph_key"] = key
             total = t.zeros(self.n_stats, dtype=t.float32, device=self.dev)
+            if self.ctl is not None:         # the KL stop holds for one update(): clear the gate (bit 0 is rewritten by every control call)
+                self.ctl[_abi.UPDATE_CTL_WORDS.index("skip")].zero_()
             for _ in range(epochs):
                 P["perm"].copy_(t.randperm(B, device=self.dev, generator=generator))
                 if not self.use_graph:
@@ -222,10 +285,10 @@ class _FusedLearner(object):
                 elif not several:
                     P["graphs"][0].replay()
                 else:
-                    for gr in P["graphs"]:
+                    for s, gr in enumerate(P["graphs"]):
                         gr.replay()
-                        reduce()
-                        self._adam(world)
+                        reduce(P, s)
+                        self._adam(world, self._kl_ptr(P, s))
                 total += P["stats"].sum(dim=0)
         self._mark_updated()
         return total, float(epochs * P["nmb"])
@@ -252,7 +315,8 @@ class FusedPPO(_FusedLearner):
     _history = False            # FusedPPOHistory alone takes a model with an encoder
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
-                 mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None):
+                 mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, max_grad_norm=None, device_lr=False, kl_stop=None,
+                 kl_target=None, kl_lr_bounds=None):
         from . import ppo
         self._need_gpu(model)
         if getattr(model, "history", 0) and not self._history:
@@ -266,24 +330,45 @@ class FusedPPO(_FusedLearner):
         self.priv_dim = int(getattr(model, "priv_dim", 0))
         # a privileged actor as well (ppo.ActorCritic(actor_priv_dim=48), a teacher): its layer 0 reads the same x | priv
         self.actor_priv_dim = int(getattr(model, "actor_priv_dim", 0))
-        self.head_stats = 5 if self.learn_std else 2          # what the loss head writes; FusedPPOHistory's latent loss follows them
+        # a KL rule needs approx_kl on the device: the loss head is then orr_ppo_head_logstd for a fixed-std model too, on a constant buffer of
+        # log(std) (renewed by every update()), with ent_coef = 0 and the log-std's gradient sent to scratch; update() still returns its two stats
+        self.logstd_head = self.learn_std or kl_stop is not None or kl_target is not None
+        self.head_stats = 5 if self.logstd_head else 2        # what the loss head writes; FusedPPOHistory's latent loss follows them
         _FusedLearner.__init__(self, model, sorted(model.p), self.head_stats + (1 if self._history else 0), lr, adam_eps, minibatch, betas, use_graph,
-                               mpi_adam_epsilon)
+                               mpi_adam_epsilon, max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds)
+        if self.logstd_head and not self.learn_std:
+            self.fixed_logstd = self.torch.zeros(12, dtype=self.torch.float32, device=self.dev)
+            self.g_fixed_logstd = self.torch.zeros(12, dtype=self.torch.float32, device=self.dev)
 
     def _graph_key(self):
         if self.learn_std:          # the std is read on the device: not a key
             return _FusedLearner._graph_key(self) + (self.clip, self.vf_coef, self.ent_coef) + self.log_std_bounds
         return _FusedLearner._graph_key(self) + (self.clip, self.vf_coef, float(self.model.std))
 
-    def _adam(self, world):
-        _FusedLearner._adam(self, world)
+    def _adam(self, world, kl=None):
+        _FusedLearner._adam(self, world, kl)
         if self.learn_std:
             self.w[LOGSTD].clamp_(*self.log_std_bounds)
+
+    def _kl_ptr(self, P, s):
+        return P["stats"][s][3:].data_ptr() if self.kl_on else None
+
+    def _refresh_std(self):
+        """A fixed-std model under a KL rule: the loss head's constant log-std buffer follows model.std."""
+        if self.logstd_head and not self.learn_std:
+            import math
+            self.fixed_logstd.fill_(math.log(float(self.model.std)))
+
+    def _returned(self, stats):
+        """What update() returns of a minibatch's mean stats row: everything, or a fixed-std model's two (+ the latent loss) under a KL rule."""
+        if self.logstd_head and not self.learn_std:
+            return self.torch.cat((stats[:2], stats[5:]))
+        return stats
 
     def _buffers(self, P, f, split, rows):
         B, M, pd = P["B"], P["M"], self.priv_dim
         P.update({"obs": f(B, 160), "aux": f(B, 16), "x": f(M, 160), "batch": f(M, 16), "gz2": f(M, 256), "gh1": f(M, 512), "g_pi": f(M, 12),
-                  "g_vf": f(M), "ws": f(int(self.L.orr_learner_workspace_floats(M, 32 if self.learn_std else 16)))})
+                  "g_vf": f(M), "ws": f(int(self.L.orr_learner_workspace_floats(M, 32 if self.logstd_head else 16)))})
         P["aux"].zero_()
         if pd:      # the privileged observations, gathered with the same permutation; xv = x | xp is the critic's layer-0 input
             P["priv"], P["xp"], P["xv"] = f(B, pd), f(M, pd), f(M, 160 + pd)
@@ -316,9 +401,10 @@ class FusedPPO(_FusedLearner):
     def _loss_head(self, P, s, st):
         """orr_ppo_head or orr_ppo_head_logstd on the two nets' outputs: g_pi, g_vf, the output layers' bias gradients, stats[s]."""
         L, M, g, ws = self.L, P["M"], self.g, P["ws"].data_ptr()
-        if self.learn_std:
-            _lib.check(L.orr_ppo_head_logstd(P["y_pi"].data_ptr(), P["y_vf"].data_ptr(), P["batch"].data_ptr(), self.w[LOGSTD].data_ptr(), M, self.clip,
-                                             self.vf_coef, self.ent_coef, P["g_pi"].data_ptr(), P["g_vf"].data_ptr(), g[LOGSTD].data_ptr(),
+        if self.logstd_head:
+            log_std, g_log_std = (self.w[LOGSTD], g[LOGSTD]) if self.learn_std else (self.fixed_logstd, self.g_fixed_logstd)
+            _lib.check(L.orr_ppo_head_logstd(P["y_pi"].data_ptr(), P["y_vf"].data_ptr(), P["batch"].data_ptr(), log_std.data_ptr(), M, self.clip,
+                                             self.vf_coef, self.ent_coef, P["g_pi"].data_ptr(), P["g_vf"].data_ptr(), g_log_std.data_ptr(),
                                              g["model/pi/b:0"].data_ptr(), g["model/vf/b:0"].data_ptr(), P["stats"][s].data_ptr(), ws, st), L)
         else:
             _lib.check(L.orr_ppo_head(P["y_pi"].data_ptr(), P["y_vf"].data_ptr(), P["batch"].data_ptr(), M, float(self.model.std), self.clip,
@@ -340,6 +426,7 @@ class FusedPPO(_FusedLearner):
             logp = old_logp
             if logp is None:
                 logp = self.model.log_prob(obs, actions, *((priv,) if self.actor_priv_dim else ()))
+            self._refresh_std()
             P["obs"].copy_(obs)
             if priv is not None:
                 P["priv"].copy_(priv)
@@ -349,7 +436,7 @@ class FusedPPO(_FusedLearner):
             aux[:, 13].copy_(adv)
             aux[:, 14].copy_(ret)
         total, n = self._run(B, fill, epochs, generator, self._world(), self._allreduce if self._several() else None)
-        return (total / n).cpu().numpy()
+        return self._returned(total / n).cpu().numpy()
 
     # ---- ranks: the gradient all-reduce and replica consistency (MpiAdam, stable_baselines/common/mpi_adam.py) -----------------------
     def _world(self):
@@ -366,15 +453,23 @@ class FusedPPO(_FusedLearner):
             return False
         return dist.get_world_size(self.group) > 1 or (os.environ.get("ORR_FORCE_DIST", "0") == "1")
 
-    def _allreduce(self):
-        """Sum of the flat gradient over the ranks; orr_adam_step divides by the world size (mpi_adam.py:51-53)."""
+    def _allreduce(self, P=None, s=0):
+        """Sum of the flat gradient over the ranks; orr_adam_step divides by the world size (mpi_adam.py:51-53).  Under a KL rule minibatch
+        s's approx_kl becomes its mean over the ranks as well, in place in the plan's stats, before orr_update_control reads it: every replica
+        then takes the same decision."""
         import torch.distributed as dist
+        kl = P["stats"][s][3:4] if (self.kl_on and P is not None) else None
         if dist.get_backend(self.group) == "gloo":            # rehearsal of the multi-rank path on a one-GPU box: stage through the host
-            tmp = self.flat_g.cpu()
-            dist.all_reduce(tmp, group=self.group)
-            self.flat_g.copy_(tmp)
+            for x in (self.flat_g,) + (() if kl is None else (kl,)):
+                tmp = x.cpu()
+                dist.all_reduce(tmp, group=self.group)
+                x.copy_(tmp)
         else:
             dist.all_reduce(self.flat_g, group=self.group)   # RCCL, in place on the device
+            if kl is not None:
+                dist.all_reduce(kl, group=self.group)
+        if kl is not None:
+            kl /= dist.get_world_size(self.group)
 
     def _bcast_root(self):
         import torch.distributed as dist
@@ -418,14 +513,16 @@ class FusedPPOHistory(FusedPPO):
     _history = True
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
-                 mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, latent_coef=0.0):
+                 mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, latent_coef=0.0, max_grad_norm=None, device_lr=False,
+                 kl_stop=None, kl_target=None, kl_lr_bounds=None):
         import math
         if not getattr(model, "history", 0):
             raise ValueError("FusedPPOHistory: the model needs a history encoder (ActorCritic(history=16)); a model without is trained by FusedPPO")
         self.latent_coef = float(latent_coef)
         if not (self.latent_coef >= 0.0 and math.isfinite(self.latent_coef)):
             raise ValueError("FusedPPOHistory: latent_coef must be finite and not negative")
-        FusedPPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, betas, mpi_adam_epsilon, use_graph, ent_coef, log_std_bounds)
+        FusedPPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, betas, mpi_adam_epsilon, use_graph, ent_coef, log_std_bounds,
+                          max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds)
 
     def _graph_key(self):
         return FusedPPO._graph_key(self) + (self.latent_coef,)
@@ -494,6 +591,7 @@ class FusedPPOHistory(FusedPPO):
             logp = old_logp
             if logp is None:
                 logp = self.model.log_prob(obs, actions, hist=hist)
+            self._refresh_std()
             P["obs"].copy_(obs)
             P["hist"].copy_(hist)
             P["priv"].copy_(priv)
@@ -503,7 +601,7 @@ class FusedPPOHistory(FusedPPO):
             aux[:, 13].copy_(adv)
             aux[:, 14].copy_(ret)
         total, n = self._run(B, fill, epochs, generator, self._world(), self._allreduce if self._several() else None)
-        return (total / n).cpu().numpy()
+        return self._returned(total / n).cpu().numpy()
 
 
 class FusedDistill(_FusedLearner):
@@ -514,13 +612,14 @@ class FusedDistill(_FusedLearner):
     orr_relu_backward and one orr_colsum_finish per minibatch, equal minibatches in static buffers, an epoch captured once and replayed as
     one hipGraph (a single chain on one stream).  One rank: there is no gradient all-reduce here."""
 
-    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True):
+    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, max_grad_norm=None, device_lr=False):
         if getattr(student, "actor_priv_dim", 0):
             raise ValueError("FusedDistill: the student's actor must read the 160 observation words only")
         self._need_gpu(student)
         if getattr(student, "history", 0):
             raise ValueError("FusedDistill: a history student is trained by FusedDistillHistory, or with PPO by FusedPPOHistory")
-        _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/pi") and k != LOGSTD), 1, lr, adam_eps, minibatch, betas, use_graph)
+        _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/pi") and k != LOGSTD), 1, lr, adam_eps, minibatch, betas, use_graph,
+                               max_grad_norm=max_grad_norm, device_lr=device_lr)
 
     def _buffers(self, P, f, split, rows):
         B, M = P["B"], P["M"]
@@ -568,7 +667,8 @@ class FusedDistillHistory(_FusedLearner):
     packed copy of the actor and of the three transposes its backward pass streams (made once, and again when somebody else called the
     model's mark_updated()) -, everything behind it is the same.  The defaults (0, 1) are the path above, launch for launch."""
 
-    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, action_coef=0.0, latent_coef=1.0):
+    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, action_coef=0.0, latent_coef=1.0,
+                 max_grad_norm=None, device_lr=False):
         self.action_coef, self.latent_coef = float(action_coef), float(latent_coef)
         if self.action_coef < 0.0 or self.latent_coef < 0.0:
             raise ValueError("FusedDistillHistory: action_coef and latent_coef must not be negative")
@@ -579,7 +679,7 @@ class FusedDistillHistory(_FusedLearner):
         if not getattr(student, "history", 0):
             raise ValueError("FusedDistillHistory: the student needs a history encoder (ActorCritic(history=16))")
         _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/enc_")), 2 if self.head else 1, lr, adam_eps,
-                               minibatch, betas, use_graph)
+                               minibatch, betas, use_graph, max_grad_norm=max_grad_norm, device_lr=device_lr)
 
     def _graph_key(self):
         return _FusedLearner._graph_key(self) + (self.action_coef, self.latent_coef)

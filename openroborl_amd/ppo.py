@@ -65,6 +65,112 @@ def _entropy_args(model, who, ent_coef, log_std_bounds):
     return learn, ent_coef, (lo, hi)
 
 
+KL_LR_BOUNDS = (0.01, 10.0)        # the KL-adaptive learning rate stays within these multiples of lr
+
+
+def _control_args(who, max_grad_norm=None, kl_stop=None, kl_target=None, kl_lr_bounds=KL_LR_BOUNDS):
+    """-> (max_grad_norm, kl_stop, kl_target, (lo, hi)) of a learner's update controls, checked; None: that control is off."""
+    out = []
+    for name, x in (("max_grad_norm", max_grad_norm), ("kl_stop", kl_stop), ("kl_target", kl_target)):
+        if x is not None and not (float(x) > 0.0 and math.isfinite(float(x))):
+            raise ValueError("%s: %s must be positive and finite (None: off)" % (who, name))
+        out.append(None if x is None else float(x))
+    lo, hi = float(kl_lr_bounds[0]), float(kl_lr_bounds[1])
+    if not (0.0 < lo <= hi and math.isfinite(hi)):
+        raise ValueError("%s: kl_lr_bounds (lo, hi) are multipliers of lr with 0 < lo <= hi" % who)
+    return out[0], out[1], out[2], (lo, hi)
+
+
+class _UpdateControl(object):
+    """The update controls of the torch learners, the yardstick of learner_hip's device path (orr_update_control, orr_adam_step_ctl) with the
+    same float32 arithmetic: the global gradient norm and torch.nn.utils.clip_grad_norm_'s coefficient, a guard that skips the step of a
+    non-finite gradient (or KL), a learning-rate multiplier set by the caller (set_lr_mult), an early stop of the update() once a minibatch's
+    approx_kl exceeds kl_stop, and the KL-adaptive learning rate (above 2 kl_target: / 1.5, below kl_target / 2: * 1.5, within kl_lr_bounds).
+    A skipped step skips opt.step() altogether: the optimiser's step count stands.  The KL rules read the minibatch's KL on the host, one
+    sync per minibatch.  Without any of the arguments the learners call opt.step() as they always did."""
+
+    def _control_init(self, max_grad_norm=None, kl_stop=None, kl_target=None, kl_lr_bounds=KL_LR_BOUNDS, device_lr=False):
+        self.max_grad_norm, self.kl_stop, self.kl_target, self.kl_lr_bounds = _control_args(type(self).__name__, max_grad_norm, kl_stop, kl_target,
+                                                                                            kl_lr_bounds)
+        self.kl_on = self.kl_stop is not None or self.kl_target is not None
+        self.control_on = self.max_grad_norm is not None or self.kl_on or bool(device_lr)
+        self.base_lr = float(self.opt.param_groups[0]["lr"])
+        self.lr_mult, self.kl_lr_mult, self.kl_stopped = 1.0, 1.0, False
+        self.grad_norms = []                 # every minibatch's norm since construction, in order (the tests place their thresholds by it)
+        self.kls = []                        # likewise the KLs the rules saw
+        self._clear_counters()
+
+    def _clear_counters(self):
+        self.ctl = {"grad_norm": 0.0, "grad_norm_max": 0.0, "grad_norm_sum": 0.0, "calls": 0, "clipped": 0, "skipped_nonfinite": 0, "skipped_kl": 0}
+
+    def set_lr_mult(self, x):
+        """The schedule's multiplier of lr from the next step on."""
+        self.control_on = True
+        self.lr_mult = float(x)
+
+    def control_stats(self):
+        """The diagnostics since the last call, and clears the counters (learner_hip's control_stats())."""
+        c = self.ctl
+        out = dict(c, grad_norm_mean=c["grad_norm_sum"] / max(c["calls"], 1), lr_mult=self.lr_mult, kl_lr_mult=self.kl_lr_mult)
+        del out["grad_norm_sum"]
+        self._clear_counters()
+        return out
+
+    def _begin_update(self):
+        self.kl_stopped = False              # the stop holds for one update()
+
+    def _step(self, kl=None):
+        """opt.step() under the controls; kl: the minibatch's approx_kl (a tensor) when a KL rule is on.  Returns whether the step was taken."""
+        if not self.control_on:
+            self.opt.step()
+            return True
+        t, f32, c = self.torch, np.float32, self.ctl
+        grads = [p.grad for grp in self.opt.param_groups for p in grp["params"] if p.grad is not None]
+        norm = f32(float(t.linalg.vector_norm(t.stack([t.linalg.vector_norm(g) for g in grads]))))
+        kl = f32(float(kl)) if (kl is not None and self.kl_on) else f32(0.0)
+        self.grad_norms.append(float(norm))
+        self.kls.append(float(kl))
+        bad = not (np.isfinite(norm) and np.isfinite(kl))
+        if not bad and self.kl_stop is not None and kl > f32(self.kl_stop):
+            self.kl_stopped = True
+        skip = bad or self.kl_stopped
+        if not skip and self.kl_target is not None:
+            tgt, m = f32(self.kl_target), f32(self.kl_lr_mult)
+            if kl > f32(2.0) * tgt:
+                m = max(f32(self.kl_lr_bounds[0]), m / f32(1.5))
+            elif kl > 0.0 and kl < f32(0.5) * tgt:
+                m = min(f32(self.kl_lr_bounds[1]), m * f32(1.5))
+            self.kl_lr_mult = float(m)
+        scale = f32(1.0)
+        if bad:
+            c["skipped_nonfinite"] += 1
+        else:
+            if self.max_grad_norm is not None:
+                scale = min(f32(1.0), f32(self.max_grad_norm) / (norm + f32(1e-6)))
+            c["clipped"] += int(scale < 1.0)
+            c["grad_norm_max"] = max(c["grad_norm_max"], float(norm))
+            c["grad_norm_sum"] += float(norm)
+            c["calls"] += 1
+        c["skipped_kl"] += int(self.kl_stopped)
+        c["grad_norm"] = float(norm)
+        if skip:
+            return False
+        if self.max_grad_norm is not None:
+            for g in grads:
+                g.mul_(float(scale))
+        lr = float(f32(self.base_lr) * f32(self.lr_mult) * f32(self.kl_lr_mult))
+        for grp in self.opt.param_groups:
+            grp["lr"] = lr
+        self.opt.step()
+        return True
+
+
+def _approx_kl(logp, old_logp):
+    """mean((ratio - 1) - log ratio), the estimator of orr_ppo_head_logstd's stats[3]."""
+    log_ratio = (logp - old_logp).detach()
+    return ((log_ratio.exp() - 1.0) - log_ratio).mean()
+
+
 def _wgrad(torch, x, g):
     """x^T g for a tall batch: hipBLASLt picks a 32x32 macro-tile for these (K = batch) shapes and fills a third of the
     chip; a 16-way split over the batch (one bmm + a sum) is 2.5-3x faster on MI355X (100 -> 35 us at 16384 x 160 x 512)."""
@@ -327,15 +433,16 @@ class ActorCritic(object):
         return d
 
 
-class PPO(object):
+class PPO(_UpdateControl):
     """With a learn-std model (ActorCritic(learn_std=True)) the loss gains -ent_coef * H (pol_entpen, agents/ppo_imitation.py:196-210),
     log_std is clamped to log_std_bounds after every optimiser step, and update() returns the five STAT_NAMES.  A fixed-std model is the
-    code path it always was and returns (surrogate, value loss); ent_coef != 0 is refused for it, the term would have no gradient."""
+    code path it always was and returns (surrogate, value loss); ent_coef != 0 is refused for it, the term would have no gradient.
+    max_grad_norm, kl_stop, kl_target / kl_lr_bounds and set_lr_mult(): _UpdateControl."""
 
     _history = False            # PPOHistory alone takes a model with an encoder
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, ent_coef=0.0,
-                 log_std_bounds=LOG_STD_BOUNDS):
+                 log_std_bounds=LOG_STD_BOUNDS, max_grad_norm=None, kl_stop=None, kl_target=None, kl_lr_bounds=KL_LR_BOUNDS):
         import torch
         self.torch = torch
         if not self._history:
@@ -349,6 +456,18 @@ class PPO(object):
         params = model.parameters()
         # one fused multi-tensor kernel per step on the GPU (the default foreach path is ~7 launches, 0.2 ms per step)
         self.opt = torch.optim.Adam(params, lr=lr, eps=adam_eps, fused=bool(params and params[0].is_cuda))
+        self._control_init(max_grad_norm, kl_stop, kl_target, kl_lr_bounds)
+
+    def _mean_kl(self, logp, old_logp):
+        """The minibatch's approx_kl for the KL rules, averaged over the ranks so that every replica decides alike; None when no rule is on."""
+        if not self.kl_on:
+            return None
+        import torch.distributed as dist
+        kl = _approx_kl(logp, old_logp)
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            dist.all_reduce(kl, group=self.group)
+            kl = kl / dist.get_world_size(self.group)
+        return kl
 
     def _allreduce_grads(self):
         import torch.distributed as dist
@@ -378,6 +497,7 @@ class PPO(object):
             with t.no_grad():
                 old_logp = self.model.log_prob(obs, actions, *actor_priv(priv))
         stats = []
+        self._begin_update()
         for _ in range(epochs):
             perm = t.randperm(B, device=obs.device, generator=generator)
             # one gather per epoch; the minibatches are then contiguous views
@@ -398,7 +518,7 @@ class PPO(object):
                 self.opt.zero_grad(set_to_none=True)
                 loss.backward()
                 self._allreduce_grads()
-                self.opt.step()
+                self._step(self._mean_kl(logp, old_p[s:e]))
                 if self.learn_std:
                     with t.no_grad():
                         self.model.p[LOGSTD].clamp_(*self.log_std_bounds)
@@ -427,13 +547,14 @@ class PPOHistory(PPO):
     _history = True
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, ent_coef=0.0,
-                 log_std_bounds=LOG_STD_BOUNDS, latent_coef=0.0):
+                 log_std_bounds=LOG_STD_BOUNDS, latent_coef=0.0, max_grad_norm=None, kl_stop=None, kl_target=None, kl_lr_bounds=KL_LR_BOUNDS):
         if not getattr(model, "history", 0):
             raise ValueError("PPOHistory: the model needs a history encoder (ActorCritic(history=16)); a model without is trained by PPO")
         self.latent_coef = float(latent_coef)
         if not (self.latent_coef >= 0.0 and math.isfinite(self.latent_coef)):
             raise ValueError("PPOHistory: latent_coef must be finite and not negative")
-        PPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, ent_coef, log_std_bounds)
+        PPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, ent_coef, log_std_bounds, max_grad_norm, kl_stop, kl_target,
+                     kl_lr_bounds)
 
     def update(self, obs, hist, priv, actions, adv, ret, old_logp=None, epochs=1, generator=None):
         """obs [B,160], hist [B,512] (history_push), priv [B,48] (env.privileged_obs on the same states), actions [B,12] (unclipped
@@ -446,6 +567,7 @@ class PPOHistory(PPO):
             with t.no_grad():
                 old_logp = self.model.log_prob(obs, actions, hist=hist)
         stats = []
+        self._begin_update()
         for _ in range(epochs):
             perm = t.randperm(B, device=obs.device, generator=generator)
             obs_p, hist_p, priv_p, act_p, adv_p, ret_p, old_p = (x[perm] for x in (obs, hist, priv, actions, adv, ret, old_logp))
@@ -467,7 +589,7 @@ class PPOHistory(PPO):
                 self.opt.zero_grad(set_to_none=True)
                 loss.backward()
                 self._allreduce_grads()
-                self.opt.step()
+                self._step(self._mean_kl(logp, old_p[s:e]))
                 row = [surr.detach(), vf.detach()]
                 if self.learn_std:
                     with t.no_grad():
@@ -481,12 +603,12 @@ class PPOHistory(PPO):
         return t.stack(stats).mean(dim=0).cpu().numpy()
 
 
-class Distill(object):
+class Distill(_UpdateControl):
     """Policy distillation in plain torch (DAgger's supervised step; the fp32 reference of learner_hip.FusedDistill): the student's mean is
     regressed on a teacher's, loss = mean over the samples of sum_j (mean_j - target_j)^2.  Only the actor (model/pi*) is trained; the
     critic's parameters are not touched and have no optimiser state.  The student is a plain policy (actor_priv_dim = 0)."""
 
-    def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096):
+    def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096, max_grad_norm=None):
         import torch
         self.torch = torch
         _no_history(student, "Distill")
@@ -496,6 +618,7 @@ class Distill(object):
         self.minibatch = int(minibatch)
         params = [student.p[k] for k in sorted(student.p) if k.startswith("model/pi") and k != LOGSTD]     # a log-std is neither read nor trained here
         self.opt = torch.optim.Adam(params, lr=lr, eps=adam_eps, fused=bool(params and params[0].is_cuda))
+        self._control_init(max_grad_norm)            # max_grad_norm and set_lr_mult(): _UpdateControl
 
     def update(self, obs, target_mean, epochs=1, generator=None):
         """obs [B,160], target_mean [B,12] (the teacher's actor output on the same states); returns the mean loss over the minibatches."""
@@ -510,14 +633,14 @@ class Distill(object):
                 loss = ((self.model.mean(obs_p[s:e]) - tgt_p[s:e]) ** 2).sum(dim=1).mean()
                 self.opt.zero_grad(set_to_none=True)
                 loss.backward()
-                self.opt.step()
+                self._step()
                 if hasattr(self.model, "mark_updated"):
                     self.model.mark_updated()
                 stats.append(loss.detach())
         return float(t.stack(stats).mean())
 
 
-class DistillHistory(object):
+class DistillHistory(_UpdateControl):
     """The learner of a history student's encoder in plain torch (RMA's second phase; the fp32 reference of learner_hip.FusedDistillHistory):
     encode(hist) is regressed on the recorded privileged rows, loss = mean over the samples of sum_j (z_j - priv_j)^2.  Only model/enc_* train;
     the actor and the critic - the teacher's - are not touched and have no optimiser state.
@@ -527,7 +650,7 @@ class DistillHistory(object):
     gradient flowing through the frozen actor into the encoder.  update() then takes obs and the teacher's means as well.  The defaults
     (0, 1) are the latent regression alone, by the code path it always had."""
 
-    def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096, action_coef=0.0, latent_coef=1.0):
+    def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096, action_coef=0.0, latent_coef=1.0, max_grad_norm=None):
         import torch
         self.torch = torch
         if not getattr(student, "history", 0):
@@ -541,6 +664,7 @@ class DistillHistory(object):
         params = [student.p[k] for k in sorted(student.p) if k.startswith("model/enc_")]
         self.params = params
         self.opt = torch.optim.Adam(params, lr=lr, eps=adam_eps, fused=bool(params and params[0].is_cuda))
+        self._control_init(max_grad_norm)            # max_grad_norm and set_lr_mult(): _UpdateControl
 
     def update(self, hist, target_priv, epochs=1, generator=None, obs=None, target_mean=None):
         """hist [B,512], target_priv [B,48] (env.privileged_obs on the same states); with action_coef > 0 also obs [B,160] and target_mean [B,12]
@@ -574,7 +698,7 @@ class DistillHistory(object):
                     latent = ((self.model.encode(hist_p[s:e]) - tgt_p[s:e]) ** 2).sum(dim=1).mean()
                     loss = latent if plain else self.latent_coef * latent
                     loss.backward()
-                self.opt.step()
+                self._step()
                 if hasattr(self.model, "mark_updated"):
                     self.model.mark_updated()
                 stats.append(loss.detach())

@@ -5,6 +5,7 @@ leaves the GPU.  Counterpart of `python3 OpenRoboRL/run.py --task imitation_lear
 
   python train.py --task imitation_learning_laikago --iters 200
   python train.py --task imitation_learning_laikago --iters 200 --learn-std --ent-coef 0.01   (a learned exploration width, entropy / KL / clip fraction in the log)
+  python train.py --task imitation_learning_laikago --iters 200 --max-grad-norm 0.5 --lr-schedule linear --kl-target 0.01   (update controls on the device)
   python train.py --task imitation_learning_laikago --iters 200 --privileged-critic --push 0.02,0.2,0.5   (asymmetric actor-critic)
   python train.py --task imitation_learning_laikago --iters 200 --privileged-actor --push 0.02,0.2,0.5 --save teacher.zip   (a teacher)
   python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --push 0.02,0.2,0.5 --save student.zip   (its student)
@@ -22,6 +23,58 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+
+def control_args(ap):
+    """The flags of the update controls (learner_hip: orr_update_control + orr_adam_step_ctl; --torch-learner: ppo._UpdateControl)."""
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the global gradient norm to X before every optimiser step (torch.nn.utils.clip_grad_norm_'s formula); with any of "
+                         "these flags a step whose gradient is not finite is skipped and counted instead of taken")
+    ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="constant",
+                    help="linear: lr * max(1 - it / iters, 0), the reference's schedule='linear' (agents/ppo_imitation.py:296-299), set once per "
+                         "iteration on the device: the captured update is not captured again")
+    ap.add_argument("--kl-stop", type=float, default=None, metavar="X",
+                    help="PPO: stop the rest of an update once a minibatch's approx_kl exceeds X (that minibatch's step included)")
+    ap.add_argument("--kl-target", type=float, default=None, metavar="X",
+                    help="PPO: KL-adaptive learning rate, per step: approx_kl > 2 X: lr / 1.5; 0 < approx_kl < X / 2: lr * 1.5")
+    ap.add_argument("--kl-lr-bounds", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                    help="--kl-target: the adaptive learning rate stays within [LO, HI] times --lr (default 0.01 10)")
+
+
+def control_kwargs(args, kl=True):
+    """The learners' keywords for the flags of control_args; no flag, no keyword.  kl: a PPO learner (the distillation learners have no KL)."""
+    if not kl and (args.kl_stop is not None or args.kl_target is not None):
+        raise SystemExit("train.py: --kl-stop / --kl-target belong to PPO; the distillation learners have no KL")
+    if args.kl_lr_bounds is not None and args.kl_target is None:
+        raise SystemExit("train.py: --kl-lr-bounds belongs to --kl-target")
+    kw = {}
+    if args.max_grad_norm is not None:
+        kw["max_grad_norm"] = args.max_grad_norm
+    if args.kl_stop is not None:
+        kw["kl_stop"] = args.kl_stop
+    if args.kl_target is not None:
+        kw["kl_target"] = args.kl_target
+        if args.kl_lr_bounds is not None:
+            kw["kl_lr_bounds"] = tuple(args.kl_lr_bounds)
+    if args.lr_schedule != "constant" and not args.torch_learner:
+        kw["device_lr"] = True
+    return kw
+
+
+def control_on(args):
+    return (args.max_grad_norm is not None or args.kl_stop is not None or args.kl_target is not None or args.lr_schedule != "constant")
+
+
+def lr_mult(args, it):
+    """--lr-schedule: the multiplier of --lr in iteration `it` (linear: the reference's max(1 - it / iters, 0))."""
+    return max(1.0 - it / float(args.iters), 0.0) if args.lr_schedule == "linear" else 1.0
+
+
+def control_record(learner):
+    """What the log line gains when the control path is on; reads and clears the learner's counters (one sync per logged record)."""
+    c = learner.control_stats()
+    return {"grad_norm": round(c["grad_norm_mean"], 5), "grad_norm_max": round(c["grad_norm_max"], 5), "clipped": c["clipped"],
+            "skipped_nonfinite": c["skipped_nonfinite"], "skipped_kl": c["skipped_kl"], "lr_mult": round(c["lr_mult"] * c["kl_lr_mult"], 6)}
 
 
 def main():
@@ -109,6 +162,7 @@ def main():
                     help="the std of the action noise; with --learn-std where log-std starts (default 0.125, the reference's pi_init_std)")
     ap.add_argument("--log-std-bounds", type=float, nargs=2, metavar=("LO", "HI"), default=None,
                     help="--learn-std: log-std is clamped to [LO, HI] after every optimiser step (default log 0.01, log 1)")
+    control_args(ap)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
     ap.add_argument("--save", default="", help="write the trained weights as a stable-baselines style zip (with --privileged-critic: see there)")
@@ -197,7 +251,7 @@ def main():
     # --learn-std: the entropy bonus and the clamp; without it no keyword at all, the learners' defaults
     entropy = dict(ent_coef=args.ent_coef, log_std_bounds=tuple(args.log_std_bounds or ppo.LOG_STD_BOUNDS)) if args.learn_std else {}
     if args.torch_learner:
-        learner = ppo.PPO(model, lr=args.lr, minibatch=args.minibatch, **entropy)
+        learner = ppo.PPO(model, lr=args.lr, minibatch=args.minibatch, **entropy, **control_kwargs(args))
     else:
         from openroborl_amd import learner_hip
         # equal minibatches only (static buffers of the graph-replayed update): the largest size <= --minibatch that divides the
@@ -209,7 +263,7 @@ def main():
         if mb < 256 and args.num_robot * args.horizon >= 4096:
             raise SystemExit("train.py: %d samples per segment have no divisor between 256 and %d; pick another --num-robot / --horizon "
                              "or use --torch-learner (handles a short last minibatch)" % (args.num_robot * args.horizon, args.minibatch))
-        learner = learner_hip.FusedPPO(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam, **entropy)
+        learner = learner_hip.FusedPPO(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam, **entropy, **control_kwargs(args))
         learner.sync()                                        # MpiAdam.sync before training (ppo_imitation.py:274)
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed * 1000 + rank)
@@ -234,6 +288,8 @@ def main():
                                      legacy_gae_index=args.legacy_gae_index, first_starts=first_starts)
         first_starts = buf["dones"][-1].clone()               # the collector's buffers are overwritten by the next segment
         T, n = buf["rewards"].shape
+        if args.lr_schedule != "constant":
+            learner.set_lr_mult(lr_mult(args, it))
         losses = learner.update(buf["obs"].reshape(T * n, -1), buf["actions"].reshape(T * n, -1), adv.reshape(-1),
                                 ret.reshape(-1), old_logp=buf["logp"].reshape(-1) if "logp" in buf else None,
                                 epochs=args.epochs, generator=gen, priv=buf["priv"].reshape(T * n, -1) if model.priv_dim else None)
@@ -258,6 +314,8 @@ def main():
                 std = model.std
                 rec.update({k: round(float(v), 6) for k, v in zip(ppo.STAT_NAMES[2:], losses[2:])})
                 rec.update({"std_min": round(float(std.min()), 5), "std_max": round(float(std.max()), 5)})
+            if control_on(args):
+                rec.update(control_record(learner))
             if by_clip is not None:
                 rec["ep_ret_mean_by_clip"] = {clip_name(env, c): round(r, 2) for c, (r, _) in sorted(by_clip.items())}
             if by_term is not None:
@@ -304,14 +362,15 @@ def history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, wo
     B = args.num_robot * args.horizon
     entropy = dict(ent_coef=args.ent_coef, log_std_bounds=tuple(args.log_std_bounds or ppo.LOG_STD_BOUNDS)) if args.learn_std else {}
     if args.torch_learner:
-        learner = ppo.PPOHistory(model, lr=args.lr, minibatch=args.minibatch, latent_coef=args.latent_coef, **entropy)
+        learner = ppo.PPOHistory(model, lr=args.lr, minibatch=args.minibatch, latent_coef=args.latent_coef, **entropy, **control_kwargs(args))
     else:
         from openroborl_amd import learner_hip
         mb = learner_hip.FusedPPOHistory.fit_minibatch(B, args.minibatch)
         if mb < 256 and B >= 4096:
             raise SystemExit("train.py: %d samples per segment have no divisor between 256 and %d; pick another --num-robot / --horizon "
                              "or use --torch-learner (handles a short last minibatch)" % (B, args.minibatch))
-        learner = learner_hip.FusedPPOHistory(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam, latent_coef=args.latent_coef, **entropy)
+        learner = learner_hip.FusedPPOHistory(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam, latent_coef=args.latent_coef, **entropy,
+                                              **control_kwargs(args))
         learner.sync()
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed * 1000 + rank)
@@ -327,6 +386,8 @@ def history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, wo
         adv, ret = rollout.gae_fused(buf["rewards"], buf["vpred"], buf["dones"], 0.95, 0.95, bootstrap=boot, normalize=True, eps=1e-8,
                                      legacy_gae_index=args.legacy_gae_index, first_starts=first_starts)
         first_starts = buf["dones"][-1].clone()
+        if args.lr_schedule != "constant":
+            learner.set_lr_mult(lr_mult(args, it))
         losses = learner.update(buf["obs"].reshape(B, -1), buf["hist"].reshape(B, -1), buf["priv"].reshape(B, -1), buf["actions"].reshape(B, -1),
                                 adv.reshape(-1), ret.reshape(-1), old_logp=buf["logp"].reshape(-1) if "logp" in buf else None,
                                 epochs=args.epochs, generator=gen)
@@ -342,6 +403,8 @@ def history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, wo
                 std = model.std
                 rec.update({k: round(float(v), 6) for k, v in zip(ppo.STAT_NAMES[2:], losses[2:5])})
                 rec.update({"std_min": round(float(std.min()), 5), "std_max": round(float(std.max()), 5)})
+            if control_on(args):
+                rec.update(control_record(learner))
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if rank == 0 and args.save:
@@ -365,11 +428,12 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
     coefs = dict(action_coef=args.distill_action_coef, latent_coef=args.distill_latent_coef) if args.history else {}
     with_actions = args.history and (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0)      # the log carries both losses
     if args.torch_learner:
-        learner = (ppo.DistillHistory if args.history else ppo.Distill)(student, lr=args.lr, minibatch=args.minibatch, **coefs)
+        learner = (ppo.DistillHistory if args.history else ppo.Distill)(student, lr=args.lr, minibatch=args.minibatch, **coefs,
+                                                                        **control_kwargs(args, kl=False))
     else:
         from openroborl_amd import learner_hip
         cls = learner_hip.FusedDistillHistory if args.history else learner_hip.FusedDistill
-        learner = cls(student, lr=args.lr, minibatch=cls.fit_minibatch(B, args.minibatch), **coefs)
+        learner = cls(student, lr=args.lr, minibatch=cls.fit_minibatch(B, args.minibatch), **coefs, **control_kwargs(args, kl=False))
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed * 1000)
     collector = rollout.GraphRollout(env, student, args.horizon, teacher=teacher)
@@ -382,6 +446,8 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
         collector.teacher_mask[:driven] = 1
         buf = collector.collect(obs, generator=gen, priv=priv, hist=hist)
         obs, priv, hist = buf["last_obs"], buf["last_priv"], buf.get("last_hist")
+        if args.lr_schedule != "constant":
+            learner.set_lr_mult(lr_mult(args, it))
         if args.history and args.distill_action_coef > 0.0:
             loss = learner.update(buf["hist"].reshape(B, -1), buf["priv"].reshape(B, -1), epochs=args.epochs, generator=gen,
                                   obs=buf["obs"].reshape(B, -1), target_mean=buf["teacher_mean"].reshape(B, 12))
@@ -398,6 +464,8 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
             if with_actions:             # loss_name then holds the latent regression's own loss, as it does without the action loss
                 rec.update({"latent_loss": round(learner.last_latent_loss, 6), "action_loss": round(learner.last_action_loss, 6),
                             "total_loss": round(float(loss), 6)})
+            if control_on(args):
+                rec.update(control_record(learner))
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if args.save:
