@@ -162,6 +162,16 @@ def test_loss_head_kernel_matches_autograd(m):
     # samples outside the clip range on the clipped side, and zero advantages, get exactly zero gradient (as autograd gives them)
     dead = (mu64.grad.abs().sum(dim=1) == 0)
     assert dead.any() and bool((gm[dead] == 0).all())
+    # and every output within the bound tests/learner_refs.py derives for it at this shape (never looser than the heuristics above where both apply)
+    from tests import learner_refs as R
+    args = (mu.cpu().numpy(), value.cpu().numpy(), batch.cpu().numpy(), 0.125, 0.2, 0.5)
+    ref, restated = R.ppo_head_ref(*args), R.ppo_head_restate(*args)
+    B = R.ppo_head_bounds(ref, restated, 0.5)
+    got = {"g_mean": gm, "g_value": gv, "gb_mean": gb_m, "gb_value": gb_v[0], "surr": stats[0], "vloss": stats[1]}
+    for k in sorted(B):
+        r = R.ratio_of(got[k].cpu().numpy(), ref[k], B[k])
+        print("m=%d %s: error / bound %.3f" % (m, k, r))
+        assert r <= 1.0, (k, r)
 
 
 @pytest.mark.parametrize("m,c", [(16384, 512), (16384, 256), (1000, 512), (33, 64)])
@@ -180,6 +190,10 @@ def test_relu_backward_kernel_matches_torch(m, c):
     assert torch.equal(got, want)                                     # a select: bit-exact
     ref = want.double().sum(dim=0)
     assert (gb.double() - ref).abs().max().item() < 1e-5 * math.sqrt(m)
+    from tests import learner_refs as R               # the counted bound as well: the tighter of the two at the small shapes
+    r = R.ratio_of(gb.cpu().numpy(), *R.relu_backward_ref(gh.cpu().numpy(), h.cpu().numpy()))
+    print("m=%d c=%d gb: error / bound %.3f" % (m, c, r))
+    assert r <= 1.0, r
     gb2 = torch.empty(c, device=dev)                                  # fixed summation order: the same bits every time
     got2 = gh.clone()
     _lib.check(L.orr_relu_backward(_ptr(got2), _ptr(h), m, c, _ptr(gb2), _ptr(ws), _stream(dev)), L)
@@ -207,6 +221,12 @@ def test_head_backward_kernel_matches_torch(m, k):
     assert bool((gz[h == 0] == 0).all())
     assert (gb.double() - want.sum(dim=0)).abs().max().item() < 1e-5 * math.sqrt(m) * math.sqrt(k)
     assert (gw.double() - want_gw).abs().max().item() < 2e-5 * math.sqrt(m)
+    from tests import learner_refs as R               # the counted bounds as well: tighter than the three above for gz everywhere, for the sums at the small shapes
+    ref = R.head_backward_ref(gy.cpu().numpy(), w.cpu().numpy(), h.cpu().numpy())
+    for name, x in (("gz", gz), ("gb", gb), ("gw", gw)):
+        r = R.ratio_of(x.cpu().numpy(), *ref[name])
+        print("m=%d k=%d %s: error / bound %.3f" % (m, k, name, r))
+        assert r <= 1.0, (name, r)
     # deferred: the same sums through orr_colsum_finish, bit for bit
     rows = int(L.orr_learner_partial_rows(m))
     gz2, gb2, gw2 = torch.empty_like(gz), torch.empty_like(gb), torch.empty_like(gw)
