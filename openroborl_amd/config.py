@@ -38,13 +38,13 @@ PYBULLET_REMEMBERED = {"contact_erp": 0.08, "warmstart_factor": 0.1, "friction_e
 
 # The reference's randomiser configuration "all_params" (minitaur_env_randomizer_config.py:22-36), name -> [lower, upper]: what
 # ORR_FLAG_RANDOMIZER alone applies.  A task section of the training YAML may carry a dictionary of this form (or the name "all_params")
-# under the key `env_randomizer_config`; env.randomizer_spec lists the accepted names
+# under the key `env_randomizer_config`; env_spec.randomizer_spec lists the accepted names
 RANDOMIZER_ALL_PARAMS = {"mass": [0.8, 1.2], "inertia": [0.5, 1.5], "motor strength": [0.8, 1.2], "motor friction": [0, 0.05],
                          "latency": [0.0, 0.04], "lateral friction": [0.5, 1.25], "battery": [14.0, 16.8], "joint friction": [0, 0.05]}
 
 
 # External pushes (orr_set_push): a task section of the training YAML may carry the env's `push` dictionary under the key `push`, e.g.
-# push: {interval_s: 5.0, lin_vel: [0.2, 0.6], lin_vel_z: 0.2, ang_vel: 0.5, grace_steps: 10}; env.push_spec lists the accepted keys
+# push: {interval_s: 5.0, lin_vel: [0.2, 0.6], lin_vel_z: 0.2, ang_vel: 0.5, grace_steps: 10}; env_spec.push_spec lists the accepted keys
 PUSH_KEY = "push"
 
 

@@ -14,6 +14,7 @@
 #define ORR_TU_MAIN 1
 #include "orr_env_kernels.h"
 #include "orr_variants.h"
+#include <cstdarg>
 // <0, ORR_WAVES_PER_EU>: one wave per SIMD in the shipped build; development builds (-DORR_WAVES_PER_EU=2 with the timers of this
 // translation unit, tools/wave_pairing.py) get their instrumented two-wave kernel through the default path with ORR_STEP_WAVES_PER_EU=1
 template orr::ResetLaunch orr::launch_reset<false>;
@@ -151,6 +152,62 @@ static orr_randomizer builtin_randomizer() {
   return r;
 }
 
+// ---- what the setters of the C-ABI share.  Each of them goes: null handle, type range, validate, anchor conflict, device copy, host
+// mirror, variant switch.  All of these return 0, or record the message and return the entry's code
+__attribute__((format(printf, 1, 2))) static int refuse(const char* fmt, ...) {   // -1: a refused argument
+  char m[sizeof(g_err)];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(m, sizeof(m), fmt, ap);
+  va_end(ap);
+  return fail(-1, m);
+}
+static int type_range(const char* entry, int32_t t) {
+  return t < 0 || t >= ORR_MAX_ROBOT_TYPES ? refuse("%s: robot_type out of range", entry) : 0;
+}
+static void set_bit(uint32_t& mask, int t, bool on) { mask = on ? mask | 1u << t : mask & ~(1u << t); }
+// the features that have no friction-anchor form of the kernels: refused while some robot type has orr_model::friction_anchor
+static int anchor_conflict(const orr_handle* h, const char* entry, const char* what) {
+  return h->anchor_types ? refuse("%s: friction anchors (orr_model::friction_anchor) and %s cannot be combined", entry, what) : 0;
+}
+struct named_value { const char* name; float v; };
+template <size_t N> static int check_stds(const char* entry, const named_value (&table)[N]) {
+  for (const auto& f : table)
+    if (!(f.v >= 0.0f && f.v < INFINITY)) return refuse("%s: %s must be a finite standard deviation >= 0", entry, f.name);   // NaN fails the comparison
+  return 0;
+}
+// `bytes` at src -> the member of the device table that mirrors host_field (a member of h->tab_host), then -> host_field.  The device
+// copy first: a failed copy (-2, "<entry>: hipMemcpy: ...") leaves the host table, and the variant choice the caller makes next, as they were
+static int upload(orr_handle* h, const char* entry, void* host_field, const void* src, size_t bytes) {
+  void* dev_field = (char*)h->tab_dev + ((char*)host_field - (char*)&h->tab_host);
+  const hipError_t e = hipMemcpy(dev_field, src, bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    char m[96];
+    snprintf(m, sizeof(m), "%s: hipMemcpy", entry);
+    return fail(-2, m, e);
+  }
+  memcpy(host_field, src, bytes);
+  return 0;
+}
+// The three output binds of a per-step buffer a (NULL = unbind: b and c are ignored), its per-episode companion b (required with a)
+// and the per-episode log c (optional): three consecutive pointers of the tables from `first` on, and the handle's switch `flag`.
+// needs_b / misaligned: the entry's own texts; misaligned = NULL where the buffers need no 16-byte alignment
+static int bind_three(orr_handle* h, const char* entry, float* DevTables::*first, bool orr_handle::*flag, float* a, float* b, float* c,
+                      const char* needs_b, const char* misaligned, const char* what) {
+  if (!h) return refuse("%s: null handle", entry);
+  const bool on = a != nullptr;
+  if (on && !b) return refuse("%s: %s", entry, needs_b);
+  if (on && misaligned && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) != 0) return refuse("%s: %s", entry, misaligned);
+  if (on && anchor_conflict(h, entry, what)) return -1;
+  float* p[3] = {a, on ? b : nullptr, on ? c : nullptr};
+  if (const int r = upload(h, entry, &(h->tab_host.*first), p, sizeof(p))) return r;
+  h->*flag = on;
+  return 0;
+}
+#define ORR_THREE_POINTERS(a, b, c)                                                               \
+  static_assert(offsetof(DevTables, b) == offsetof(DevTables, a) + sizeof(float*) &&              \
+                offsetof(DevTables, c) == offsetof(DevTables, a) + 2 * sizeof(float*), "bind_three copies three consecutive pointers")
+
 extern "C" {
 
 #ifndef ORR_SOURCE_HASH
@@ -203,20 +260,19 @@ int32_t orr_create(const orr_config* cfg, orr_handle** out) {
     const char* f = getenv("ORR_STEP_WAVES_PER_EU");
     h->force_wpe = (f && (f[0] == '1' || f[0] == '2') && f[1] == 0) ? f[0] - '0' : 0;
   }
-  e = hipMalloc((void**)&h->tab_dev, sizeof(DevTables));
-  if (e != hipSuccess) { delete h; return fail(-2, "orr_create: hipMalloc", e); }
-  e = hipMemset(h->tab_dev, 0, sizeof(DevTables));
-  if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemset", e); }
-  for (int t = 0; t < ORR_MAX_ROBOT_TYPES; t++) h->tab_host.clip_switch[t][0] = h->tab_host.clip_switch[t][1] = INFINITY;   // no switching
-  e = hipMemcpy(h->tab_dev->clip_switch, h->tab_host.clip_switch, sizeof(h->tab_host.clip_switch), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemcpy", e); }
-  for (int t = 0; t < ORR_MAX_ROBOT_TYPES; t++)
-    for (int i = 0; i < 12; i++) h->tab_host.torque_limit[t][i] = INFINITY;   // no torque limit
-  e = hipMemcpy(h->tab_dev->torque_limit, h->tab_host.torque_limit, sizeof(h->tab_host.torque_limit), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemcpy", e); }
+  // the initial table: zeros (the memset of the handle above) but for these three, and the device's copy of it
+  for (int t = 0; t < ORR_MAX_ROBOT_TYPES; t++) {
+    h->tab_host.clip_switch[t][0] = h->tab_host.clip_switch[t][1] = INFINITY;   // no switching
+    for (int i = 0; i < 12; i++) h->tab_host.torque_limit[t][i] = INFINITY;     // no torque limit
+  }
   h->tab_host.rnd = builtin_randomizer();   // what a bound params buffer applies until orr_set_randomizer gives a table
-  e = hipMemcpy(&h->tab_dev->rnd, &h->tab_host.rnd, sizeof(h->tab_host.rnd), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, "orr_create: hipMemcpy", e); }
+  const char* what = "orr_create: hipMalloc";
+  e = hipMalloc((void**)&h->tab_dev, sizeof(DevTables));
+  if (e == hipSuccess) {
+    what = "orr_create: hipMemcpy";
+    e = hipMemcpy(h->tab_dev, &h->tab_host, sizeof(DevTables), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) { hipFree(h->tab_dev); delete h; return fail(-2, what, e); }   // tab_dev is NULL where the allocation failed
   hipEventCreate(&h->ev0);
   hipEventCreate(&h->ev1);
   *out = h;
@@ -240,7 +296,7 @@ int32_t orr_destroy(orr_handle* h) {
 
 int32_t orr_set_model(orr_handle* h, int32_t robot_type, const orr_model* m) {
   if (!h || !m) return fail(-1, "orr_set_model: null argument");
-  if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_model: robot_type out of range");
+  if (type_range("orr_set_model", robot_type)) return -1;
   if (m->num_fall_proxies < 0 || m->num_fall_proxies > ORR_MAX_FALL_PROXIES) return fail(-1, "orr_set_model: bad num_fall_proxies");
   for (int i = 0; i < 12; i++) {
     if (m->joint_of_motor[i] < 0 || m->joint_of_motor[i] > 11) return fail(-1, "orr_set_model: joint_of_motor out of range");
@@ -320,9 +376,8 @@ int32_t orr_set_model(orr_handle* h, int32_t robot_type, const orr_model* m) {
     Cd.group[j + 1] = m->link_group[j];
     for (int k = 0; k < 6; k++) { Cd.inertia[j + 1][k] = m->link_inertia[j][k]; Cd.inertia_pa[j + 1][k] = m->link_inertia_pa[j][k]; }
   }
-  HIPCHK(hipMemcpy(&h->tab_dev->model[robot_type], &d, sizeof(DevModel), hipMemcpyHostToDevice), "orr_set_model: hipMemcpy");
-  h->tab_host.model[robot_type] = d;
-  if (m->friction_anchor) h->anchor_types |= 1u << robot_type; else h->anchor_types &= ~(1u << robot_type);
+  if (const int r = upload(h, "orr_set_model", &h->tab_host.model[robot_type], &d, sizeof(d))) return r;
+  set_bit(h->anchor_types, robot_type, m->friction_anchor != 0);
   return 0;
 }
 
@@ -343,7 +398,7 @@ int32_t orr_set_motion(orr_handle* h, int32_t clip_id, const float* frames_dev, 
 
 int32_t orr_set_clip_set(orr_handle* h, int32_t robot_type, const int32_t* clip_ids_host, int32_t n) {
   if (!h || !clip_ids_host) return fail(-1, "orr_set_clip_set: null argument");
-  if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_clip_set: robot_type out of range");
+  if (type_range("orr_set_clip_set", robot_type)) return -1;
   if (n < 1 || n > ORR_MAX_CLIPS) return fail(-1, "orr_set_clip_set: a clip set holds 1 .. ORR_MAX_CLIPS clips");
   int ids[ORR_MAX_CLIPS] = {0};
   for (int i = 0; i < n; i++) {
@@ -357,108 +412,64 @@ int32_t orr_set_clip_set(orr_handle* h, int32_t robot_type, const int32_t* clip_
   HIPCHK(hipMemcpy(&h->tab_dev->clip_set_n[robot_type], &n, sizeof(int), hipMemcpyHostToDevice), "orr_set_clip_set: hipMemcpy");
   memcpy(h->tab_host.clip_set[robot_type], ids, sizeof(ids));
   h->tab_host.clip_set_n[robot_type] = n;
-  if (n > 1) h->multiclip_types |= 1u << robot_type; else h->multiclip_types &= ~(1u << robot_type);
+  set_bit(h->multiclip_types, robot_type, n > 1);
   return 0;
 }
 
 int32_t orr_bind_clip_log(orr_handle* h, int32_t* clip_log_dev) {
   if (!h) return fail(-1, "orr_bind_clip_log: null handle");
   int* p = clip_log_dev;
-  HIPCHK(hipMemcpy(&h->tab_dev->clip_log, &p, sizeof(p), hipMemcpyHostToDevice), "orr_bind_clip_log: hipMemcpy");
-  h->tab_host.clip_log = p;
-  return 0;
+  return upload(h, "orr_bind_clip_log", &h->tab_host.clip_log, &p, sizeof(p));
 }
 
 int32_t orr_bind_reward_terms(orr_handle* h, float* terms_dev, float* term_sums_dev, float* term_log_dev) {
-  if (!h) return fail(-1, "orr_bind_reward_terms: null handle");
-  const bool on = terms_dev != nullptr;
-  if (on && !term_sums_dev) return fail(-1, "orr_bind_reward_terms: terms_dev needs term_sums_dev (the running sums of the current episode)");
-  if (on && h->anchor_types)
-    return fail(-1, "orr_bind_reward_terms: friction anchors (orr_model::friction_anchor) and reward terms cannot be combined");
-  float* p[3] = {terms_dev, on ? term_sums_dev : nullptr, on ? term_log_dev : nullptr};
-  static_assert(offsetof(DevTables, term_sums) == offsetof(DevTables, terms) + sizeof(float*) &&
-                offsetof(DevTables, term_log) == offsetof(DevTables, terms) + 2 * sizeof(float*), "copied as three consecutive pointers");
-  // the device copy first: a failed copy leaves the host table and the variant choice as they were
-  HIPCHK(hipMemcpy(&h->tab_dev->terms, p, sizeof(p), hipMemcpyHostToDevice), "orr_bind_reward_terms: hipMemcpy");
-  h->tab_host.terms = p[0]; h->tab_host.term_sums = p[1]; h->tab_host.term_log = p[2];
-  h->terms_on = on;
-  return 0;
+  ORR_THREE_POINTERS(terms, term_sums, term_log);
+  return bind_three(h, "orr_bind_reward_terms", &DevTables::terms, &orr_handle::terms_on, terms_dev, term_sums_dev, term_log_dev,
+                    "terms_dev needs term_sums_dev (the running sums of the current episode)", nullptr, "reward terms");
 }
 
 int32_t orr_bind_contact_outputs(orr_handle* h, float* contact_dev, float* contact_ep_dev, float* contact_log_dev) {
-  if (!h) return fail(-1, "orr_bind_contact_outputs: null handle");
-  const bool on = contact_dev != nullptr;
-  if (on && !contact_ep_dev) return fail(-1, "orr_bind_contact_outputs: contact_dev needs contact_ep_dev (the totals of the current episode)");
-  if (on && ((((uintptr_t)contact_dev | (uintptr_t)contact_ep_dev | (uintptr_t)contact_log_dev) & 15u) != 0))
-    return fail(-1, "orr_bind_contact_outputs: the contact buffers must be 16-byte aligned (rows of 16 and 8 floats)");
-  if (on && h->anchor_types)
-    return fail(-1, "orr_bind_contact_outputs: friction anchors (orr_model::friction_anchor) and contact outputs cannot be combined");
-  float* p[3] = {contact_dev, on ? contact_ep_dev : nullptr, on ? contact_log_dev : nullptr};
-  static_assert(offsetof(DevTables, contact_ep) == offsetof(DevTables, contact_out) + sizeof(float*) &&
-                offsetof(DevTables, contact_log) == offsetof(DevTables, contact_out) + 2 * sizeof(float*), "copied as three consecutive pointers");
-  // the device copy first: a failed copy leaves the host table and the variant choice as they were
-  HIPCHK(hipMemcpy(&h->tab_dev->contact_out, p, sizeof(p), hipMemcpyHostToDevice), "orr_bind_contact_outputs: hipMemcpy");
-  h->tab_host.contact_out = p[0]; h->tab_host.contact_ep = p[1]; h->tab_host.contact_log = p[2];
-  h->contacts_on = on;
-  return 0;
+  ORR_THREE_POINTERS(contact_out, contact_ep, contact_log);
+  return bind_three(h, "orr_bind_contact_outputs", &DevTables::contact_out, &orr_handle::contacts_on, contact_dev, contact_ep_dev, contact_log_dev,
+                    "contact_dev needs contact_ep_dev (the totals of the current episode)",
+                    "the contact buffers must be 16-byte aligned (rows of 16 and 8 floats)", "contact outputs");
+}
+
+int32_t orr_bind_actuator_outputs(orr_handle* h, float* act_dev, float* act_ep_dev, float* act_log_dev) {
+  ORR_THREE_POINTERS(act_out, act_ep, act_log);
+  return bind_three(h, "orr_bind_actuator_outputs", &DevTables::act_out, &orr_handle::act_on, act_dev, act_ep_dev, act_log_dev,
+                    "act_dev needs act_ep_dev (the totals of the current episode)",
+                    "the actuator buffers (act_dev, act_ep_dev, act_log_dev) must be 16-byte aligned (rows of 4 floats)", "actuator outputs");
 }
 
 int32_t orr_set_torque_limits(orr_handle* h, int32_t robot_type, const float* limits_host) {
   if (!h) return fail(-1, "orr_set_torque_limits: null handle");
-  if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_torque_limits: robot_type out of range");
+  if (type_range("orr_set_torque_limits", robot_type)) return -1;
   float v[12];
   bool finite = false;
   for (int i = 0; i < 12; i++) {
     v[i] = limits_host ? limits_host[i] : INFINITY;
-    if (!(v[i] >= 0.0f)) {      // NaN fails the comparison
-      char m[160];
-      snprintf(m, sizeof(m), "orr_set_torque_limits: limits_host[%d] must be a torque >= 0 or +inf (no limit)", i);
-      return fail(-1, m);
-    }
+    if (!(v[i] >= 0.0f)) return refuse("orr_set_torque_limits: limits_host[%d] must be a torque >= 0 or +inf (no limit)", i);   // NaN fails the comparison
     finite = finite || v[i] < INFINITY;
   }
-  if (finite && h->anchor_types)
-    return fail(-1, "orr_set_torque_limits: friction anchors (orr_model::friction_anchor) and torque limits cannot be combined");
-  // the device copy first: a failed copy leaves the host table and the variant choice as they were
-  HIPCHK(hipMemcpy(&h->tab_dev->torque_limit[robot_type][0], v, sizeof(v), hipMemcpyHostToDevice), "orr_set_torque_limits: hipMemcpy");
-  memcpy(h->tab_host.torque_limit[robot_type], v, sizeof(v));
-  if (finite) h->limit_types |= 1u << robot_type; else h->limit_types &= ~(1u << robot_type);
-  return 0;
-}
-
-int32_t orr_bind_actuator_outputs(orr_handle* h, float* act_dev, float* act_ep_dev, float* act_log_dev) {
-  if (!h) return fail(-1, "orr_bind_actuator_outputs: null handle");
-  const bool on = act_dev != nullptr;
-  if (on && !act_ep_dev) return fail(-1, "orr_bind_actuator_outputs: act_dev needs act_ep_dev (the totals of the current episode)");
-  if (on && ((((uintptr_t)act_dev | (uintptr_t)act_ep_dev | (uintptr_t)act_log_dev) & 15u) != 0))
-    return fail(-1, "orr_bind_actuator_outputs: the actuator buffers (act_dev, act_ep_dev, act_log_dev) must be 16-byte aligned (rows of 4 floats)");
-  if (on && h->anchor_types)
-    return fail(-1, "orr_bind_actuator_outputs: friction anchors (orr_model::friction_anchor) and actuator outputs cannot be combined");
-  float* p[3] = {act_dev, on ? act_ep_dev : nullptr, on ? act_log_dev : nullptr};
-  static_assert(offsetof(DevTables, act_ep) == offsetof(DevTables, act_out) + sizeof(float*) &&
-                offsetof(DevTables, act_log) == offsetof(DevTables, act_out) + 2 * sizeof(float*), "copied as three consecutive pointers");
-  // the device copy first: a failed copy leaves the host table and the variant choice as they were
-  HIPCHK(hipMemcpy(&h->tab_dev->act_out, p, sizeof(p), hipMemcpyHostToDevice), "orr_bind_actuator_outputs: hipMemcpy");
-  h->tab_host.act_out = p[0]; h->tab_host.act_ep = p[1]; h->tab_host.act_log = p[2];
-  h->act_on = on;
+  if (finite && anchor_conflict(h, "orr_set_torque_limits", "torque limits")) return -1;
+  if (const int r = upload(h, "orr_set_torque_limits", h->tab_host.torque_limit[robot_type], v, sizeof(v))) return r;
+  set_bit(h->limit_types, robot_type, finite);
   return 0;
 }
 
 int32_t orr_set_clip_switch(orr_handle* h, int32_t robot_type, float tmin, float tmax) {
   if (!h) return fail(-1, "orr_set_clip_switch: null handle");
-  if (robot_type < 0 || robot_type >= ORR_MAX_ROBOT_TYPES) return fail(-1, "orr_set_clip_switch: robot_type out of range");
+  if (type_range("orr_set_clip_switch", robot_type)) return -1;
   if (isnan(tmin) || isnan(tmax)) return fail(-1, "orr_set_clip_switch: NaN bound");
   if (tmin < 0.0f || tmax < 0.0f) return fail(-1, "orr_set_clip_switch: negative bound");
   if (tmin > tmax) return fail(-1, "orr_set_clip_switch: tmin > tmax");
   const bool off = isinf(tmin) && isinf(tmax);
   if (!off && (isinf(tmin) || isinf(tmax))) return fail(-1, "orr_set_clip_switch: both bounds finite, or both +inf (off)");
-  if (!off && h->anchor_types)
-    return fail(-1, "orr_set_clip_switch: friction anchors (orr_model::friction_anchor) and clip switching cannot be combined");
+  if (!off && anchor_conflict(h, "orr_set_clip_switch", "clip switching")) return -1;
   const float v[2] = {tmin, tmax};
-  HIPCHK(hipMemcpy(&h->tab_dev->clip_switch[robot_type][0], v, sizeof(v), hipMemcpyHostToDevice), "orr_set_clip_switch: hipMemcpy");
-  h->tab_host.clip_switch[robot_type][0] = tmin;
-  h->tab_host.clip_switch[robot_type][1] = tmax;
-  if (off) h->switch_types &= ~(1u << robot_type); else h->switch_types |= 1u << robot_type;
+  if (const int r = upload(h, "orr_set_clip_switch", h->tab_host.clip_switch[robot_type], v, sizeof(v))) return r;
+  set_bit(h->switch_types, robot_type, !off);
   return 0;
 }
 
@@ -467,23 +478,15 @@ int32_t orr_set_task_noise(orr_handle* h, const orr_task_noise* noise_host) {
   orr_task_noise n;
   memset(&n, 0, sizeof(n));
   if (noise_host) n = *noise_host;
-  const struct { const char* name; float v; } stds[] = {
+  const named_value stds[] = {
       {"root_pos_std", n.root_pos_std}, {"root_rot_std", n.root_rot_std}, {"joint_pose_std", n.joint_pose_std}, {"root_vel_std", n.root_vel_std},
       {"root_ang_vel_std", n.root_ang_vel_std}, {"joint_vel_std", n.joint_vel_std}, {"tar_heading_std", n.tar_heading_std}};
-  char m[160];
   if (!(n.perturb_init_state_prob >= 0.0f && n.perturb_init_state_prob <= 1.0f))      // NaN fails the comparison
     return fail(-1, "orr_set_task_noise: perturb_init_state_prob must be a probability in [0, 1]");
-  for (const auto& f : stds)
-    if (!(f.v >= 0.0f && f.v < INFINITY)) {
-      snprintf(m, sizeof(m), "orr_set_task_noise: %s must be a finite standard deviation >= 0", f.name);
-      return fail(-1, m);
-    }
+  if (check_stds("orr_set_task_noise", stds)) return -1;
   const bool on = n.perturb_init_state_prob > 0.0f || n.tar_heading_std > 0.0f;
-  if (on && h->anchor_types)
-    return fail(-1, "orr_set_task_noise: friction anchors (orr_model::friction_anchor) and task noise cannot be combined");
-  // the device copy first: a failed copy leaves the host table and the variant choice as they were
-  HIPCHK(hipMemcpy(&h->tab_dev->noise, &n, sizeof(n), hipMemcpyHostToDevice), "orr_set_task_noise: hipMemcpy");
-  h->tab_host.noise = n;
+  if (on && anchor_conflict(h, "orr_set_task_noise", "task noise")) return -1;
+  if (const int r = upload(h, "orr_set_task_noise", &h->tab_host.noise, &n, sizeof(n))) return r;
   h->noise_on = on;
   return 0;
 }
@@ -493,32 +496,21 @@ int32_t orr_set_sensor_noise(orr_handle* h, const orr_sensor_noise* noise_host) 
   orr_sensor_noise n;
   memset(&n, 0, sizeof(n));
   if (noise_host) n = *noise_host;
-  const struct { const char* name; float v; } stds[] = {
+  const named_value stds[] = {
       {"motor_angle_std", n.motor_angle_std}, {"motor_velocity_std", n.motor_velocity_std}, {"motor_torque_std", n.motor_torque_std},
       {"base_rpy_std", n.base_rpy_std}, {"base_rpy_rate_std", n.base_rpy_rate_std}};
-  for (const auto& f : stds)
-    if (!(f.v >= 0.0f && f.v < INFINITY)) {      // NaN fails the comparison
-      char m[160];
-      snprintf(m, sizeof(m), "orr_set_sensor_noise: %s must be a finite standard deviation >= 0", f.name);
-      return fail(-1, m);
-    }
+  if (check_stds("orr_set_sensor_noise", stds)) return -1;
   const bool on = n.motor_angle_std > 0.0f || n.base_rpy_std > 0.0f || n.base_rpy_rate_std > 0.0f;
-  if (on && h->anchor_types)
-    return fail(-1, "orr_set_sensor_noise: friction anchors (orr_model::friction_anchor) and sensor noise cannot be combined");
-  // the device copy first: a failed copy leaves the host table and the variant choice as they were
-  HIPCHK(hipMemcpy(&h->tab_dev->sensor, &n, sizeof(n), hipMemcpyHostToDevice), "orr_set_sensor_noise: hipMemcpy");
-  h->tab_host.sensor = n;
+  if (on && anchor_conflict(h, "orr_set_sensor_noise", "sensor noise")) return -1;
+  if (const int r = upload(h, "orr_set_sensor_noise", &h->tab_host.sensor, &n, sizeof(n))) return r;
   h->sensor_on = on;
   return 0;
 }
 
 // DevTables::push_table follows rand_on / rand_bound: whether the push variant's auto-reset is the table-driven one
-static int32_t sync_push_table(orr_handle* h, const char* what) {
+static int32_t sync_push_table(orr_handle* h, const char* entry) {
   const int t = h->rand_on || h->rand_bound ? 1 : 0;
-  if (t == h->tab_host.push_table) return 0;
-  HIPCHK(hipMemcpy(&h->tab_dev->push_table, &t, sizeof(t), hipMemcpyHostToDevice), what);
-  h->tab_host.push_table = t;
-  return 0;
+  return t == h->tab_host.push_table ? 0 : upload(h, entry, &h->tab_host.push_table, &t, sizeof(t));
 }
 
 int32_t orr_set_randomizer(orr_handle* h, const orr_randomizer* host) {
@@ -527,7 +519,6 @@ int32_t orr_set_randomizer(orr_handle* h, const orr_randomizer* host) {
   // the ring reader (ctrl_obs / ring_prefetch, orr_robot_io.h) blends the entries n = int(latency / sim_dt) and n + 1 back from the
   // newest one, and clamps to the oldest where n + 1 >= the ring's length: exact while n + 1 <= ORR_RING_DEPTH - 1
   const float latency_max = (float)(ORR_RING_DEPTH - 2) * h->cfg.sim_dt;
-  char m[200];
   for (int p = 0; p < ORR_RAND_NUM_PARAMS; p++) {
     r.enabled[p] = r.enabled[p] != 0;
     if (!r.enabled[p]) { r.lo[p] = r.hi[p] = 0.0f; continue; }   // not read: kept as zeros
@@ -539,32 +530,23 @@ int32_t orr_set_randomizer(orr_handle* h, const orr_randomizer* host) {
     else if (positive && !(lo > 0.0f)) why = "lo must be > 0 (a ratio of a mass or an inertia)";
     else if (lo < 0.0f) why = "lo must be >= 0";
     else if (p == ORR_RAND_LATENCY && hi > latency_max) why = "hi is beyond what the latency ring holds, (ORR_RING_DEPTH - 2) * sim_dt";
-    if (why) {
-      snprintf(m, sizeof(m), "orr_set_randomizer: %s: %s", g_rand_names[p], why);
-      return fail(-1, m);
-    }
+    if (why) return refuse("orr_set_randomizer: %s: %s", g_rand_names[p], why);
   }
-  if (host && h->anchor_types)
-    return fail(-1, "orr_set_randomizer: friction anchors (orr_model::friction_anchor) and a randomiser table cannot be combined");
-  // the device copy first: a failed copy leaves the host table and the variant choice as they were
-  HIPCHK(hipMemcpy(&h->tab_dev->rnd, &r, sizeof(r), hipMemcpyHostToDevice), "orr_set_randomizer: hipMemcpy");
-  h->tab_host.rnd = r;
+  if (host && anchor_conflict(h, "orr_set_randomizer", "a randomiser table")) return -1;
+  if (const int e = upload(h, "orr_set_randomizer", &h->tab_host.rnd, &r, sizeof(r))) return e;
   h->rand_on = host != nullptr;
-  return sync_push_table(h, "orr_set_randomizer: hipMemcpy");
+  return sync_push_table(h, "orr_set_randomizer");
 }
 
 int32_t orr_bind_randomizer_params(orr_handle* h, float* params_dev, int32_t suspend) {
   if (!h) return fail(-1, "orr_bind_randomizer_params: null handle");
   if (((uintptr_t)params_dev & 15u) != 0) return fail(-1, "orr_bind_randomizer_params: params_dev must be 16-byte aligned (rows of ORR_RAND_ROW floats)");
-  if (params_dev && h->anchor_types)
-    return fail(-1, "orr_bind_randomizer_params: friction anchors (orr_model::friction_anchor) and a randomiser params buffer cannot be combined");
+  if (params_dev && anchor_conflict(h, "orr_bind_randomizer_params", "a randomiser params buffer")) return -1;
   struct { float* p; int s; } v = {params_dev, params_dev && suspend ? 1 : 0};
   static_assert(offsetof(DevTables, rand_suspend) == offsetof(DevTables, rand_params) + sizeof(float*), "copied as a pointer and the word behind it");
-  HIPCHK(hipMemcpy(&h->tab_dev->rand_params, &v, sizeof(float*) + sizeof(int), hipMemcpyHostToDevice), "orr_bind_randomizer_params: hipMemcpy");
-  h->tab_host.rand_params = v.p;
-  h->tab_host.rand_suspend = v.s;
+  if (const int r = upload(h, "orr_bind_randomizer_params", &h->tab_host.rand_params, &v, sizeof(float*) + sizeof(int))) return r;
   h->rand_bound = params_dev != nullptr;
-  return sync_push_table(h, "orr_bind_randomizer_params: hipMemcpy");
+  return sync_push_table(h, "orr_bind_randomizer_params");
 }
 
 int32_t orr_set_push(orr_handle* h, const orr_push* push_host) {
@@ -575,26 +557,19 @@ int32_t orr_set_push(orr_handle* h, const orr_push* push_host) {
   const float vmax = h->cfg.max_coord_velocity;   // the physics clamps every coordinate velocity there: a larger kick would not arrive
   const struct { const char* name; float v; bool speed; } fields[] = {
       {"prob", p.prob, false}, {"lin_lo", p.lin_lo, true}, {"lin_hi", p.lin_hi, true}, {"lin_z", p.lin_z, true}, {"ang", p.ang, true}};
-  char m[200];
-  for (const auto& f : fields) {
+  for (const auto& f : fields) {      // its own wordings, not check_stds': a probability and four speeds
     const char* why = nullptr;
     if (!(fabsf(f.v) < INFINITY)) why = "must be a finite number";      // NaN fails the comparison
     else if (f.v < 0.0f) why = "must be >= 0";
     else if (!f.speed && f.v > 1.0f) why = "must be a probability in [0, 1]";
     else if (f.speed && f.v > vmax) why = "is above orr_config::max_coord_velocity";
-    if (why) {
-      snprintf(m, sizeof(m), "orr_set_push: %s %s", f.name, why);
-      return fail(-1, m);
-    }
+    if (why) return refuse("orr_set_push: %s %s", f.name, why);
   }
   if (p.lin_lo > p.lin_hi) return fail(-1, "orr_set_push: lin_lo > lin_hi");
   if (p.grace_steps < 0) return fail(-1, "orr_set_push: grace_steps must be >= 0");
   const bool on = p.prob > 0.0f;
-  if (on && h->anchor_types)
-    return fail(-1, "orr_set_push: friction anchors (orr_model::friction_anchor) and pushes cannot be combined");
-  // the device copy first: a failed copy leaves the host table and the variant choice as they were
-  HIPCHK(hipMemcpy(&h->tab_dev->push, &p, sizeof(p), hipMemcpyHostToDevice), "orr_set_push: hipMemcpy");
-  h->tab_host.push = p;
+  if (on && anchor_conflict(h, "orr_set_push", "pushes")) return -1;
+  if (const int r = upload(h, "orr_set_push", &h->tab_host.push, &p, sizeof(p))) return r;
   h->push_on = on;
   return 0;
 }
@@ -602,10 +577,8 @@ int32_t orr_set_push(orr_handle* h, const orr_push* push_host) {
 int32_t orr_bind_push_outputs(orr_handle* h, float* push_dev) {
   if (!h) return fail(-1, "orr_bind_push_outputs: null handle");
   if (((uintptr_t)push_dev & 15u) != 0) return fail(-1, "orr_bind_push_outputs: push_dev must be 16-byte aligned (rows of ORR_PUSH_ROW floats)");
-  if (push_dev && h->anchor_types)
-    return fail(-1, "orr_bind_push_outputs: friction anchors (orr_model::friction_anchor) and push outputs cannot be combined");
-  HIPCHK(hipMemcpy(&h->tab_dev->push_out, &push_dev, sizeof(push_dev), hipMemcpyHostToDevice), "orr_bind_push_outputs: hipMemcpy");
-  h->tab_host.push_out = push_dev;
+  if (push_dev && anchor_conflict(h, "orr_bind_push_outputs", "push outputs")) return -1;
+  if (const int r = upload(h, "orr_bind_push_outputs", &h->tab_host.push_out, &push_dev, sizeof(push_dev))) return r;
   h->push_bound = push_dev != nullptr;
   return 0;
 }

@@ -10,7 +10,9 @@ LegacyListEnv    the reference's exact list-of-numpy protocol (wrapper_env.py:58
                  agents/imitation_runners.py:185-205, so a stable-baselines-style loop runs unchanged.
 
 PyTorch only owns the device buffers and the stream; all per-robot work happens inside the HIP
-kernels behind the C-ABI (include/openroborl_hip.h).
+kernels behind the C-ABI (include/openroborl_hip.h).  The validators that turn the arguments into the C-ABI's
+structs are in env_spec.py, the float64 predictors of the device's draw rules (for tests and golden makers) in
+env_draws.py; both are imported here by name, so `openroborl_amd.env.<name>` keeps resolving.
 """
 import ctypes as C
 import math
@@ -18,6 +20,13 @@ import math
 import numpy as np
 
 from . import _abi, _lib, config as cfgmod, motion, robots, state as statemod
+from .env_draws import (CLIP_CHANGE_DRAW, CLIP_DRAW, NOISE_HEADING_BLOCK, NOISE_RESET_BLOCK, PRIV_DIM, PRIV_FIELDS, RAND_LEG_WORD,  # noqa: F401
+                        RAND_ROW_WORDS, SENSOR_NOISE_BLOCK, SENSOR_SLOT_FILTER, SENSOR_SLOT_HIST, SENSOR_SLOT_TARGET, clip_change_time,
+                        clip_draw_index, clip_switch_draws, init_perturb_draw_indices, init_perturb_draws, normal_pair, push_block, push_kick,
+                        randomizer_apply, randomizer_draw_indices, randomizer_row, sensor_noise_block, sensor_noise_normals, tar_noise_block)
+from .env_spec import (INIT_PERTURB_STD, PUSH_KEYS, RAND_NOOP_NAMES, RAND_POSITIVE_NAMES, RAND_REFUSED_NAMES, clip_switch_spec,  # noqa: F401
+                       motion_spec, push_on, push_spec, randomizer_latency_max, randomizer_spec, sensor_noise_on, sensor_noise_spec,
+                       task_noise_spec, torque_limit_spec)
 
 
 class Box(object):
@@ -68,493 +77,16 @@ def observation_space(clips):
     return Box(np.concatenate([pl, tl]), np.concatenate([ph, th]), dtype=np.float32)
 
 
-def motion_spec(motion_file, robot_names, mixed=False):
-    """The motion-file argument -> (files in clip-id order, {robot name: clip set = list of clip ids}).
-
-    Homogeneous batch (robot_names[0]): a path, or a list of paths = the robot's clip set (ImitationTask's ref_motion_filenames:
-    every reset draws the episode's clip from it, imitation_task.py:694-701,1077-1085).  Mixed batch: one entry per robot name, each a
-    path or a list.  Nothing is de-duplicated: a file listed twice is two clips (twice the weight).  A robot's initial CLIP_ID is its
-    set's first entry."""
-    def as_list(e):
-        if isinstance(e, (list, tuple)):
-            if not e:
-                raise ValueError("a motion-file list must not be empty")
-            for f in e:
-                if isinstance(f, (list, tuple)):
-                    raise ValueError("a clip set is a flat list of motion files")
-            return list(e)
-        if e is None:
-            raise ValueError("no input robot or task")
-        return [e]
-    names = list(robot_names)
-    if mixed:
-        if not isinstance(motion_file, (list, tuple)) or len(motion_file) != len(names):
-            raise ValueError("mixed batch needs one motion file (or list of motion files) per robot name")
-        entries = list(motion_file)
-    else:
-        names, entries = names[:1], [motion_file]
-    files, sets = [], {}
-    for name, e in zip(names, entries):
-        ids = []
-        for f in as_list(e):
-            ids.append(len(files))
-            files.append(f)
-        sets[name] = ids
-    if len(files) > _abi.MAX_CLIPS:
-        raise ValueError("%d motion clips; a batch holds at most %d" % (len(files), _abi.MAX_CLIPS))
-    return files, sets
-
-
-CLIP_DRAW = 28      # index of the clip draw in a reset's Philox stream (block 7, word 0; draws 0..27: randomiser, ref-state-init, time offset)
-
-
-def clip_draw_index(m, n):
-    """The entry of an n-clip set a reset picks (csrc/orr_task.h, reset_robot_state<true>): (m * n) >> 24, m = the 24-bit integer of draw
-    CLIP_DRAW (the draw in [0, 1) is m / 2^24).  Integer arithmetic; works on numpy integer arrays."""
-    return (np.asarray(m, dtype=np.int64) * int(n)) >> 24
-
-
-CLIP_CHANGE_DRAW = 29   # the first clip change of an episode: draw 29 of the reset's stream (block 7, word 1)
-
-
-def clip_switch_draws(ep_step):
-    """Draw indices (clip, next change, time offset) of a mid-episode clip switch in the step whose env-step counter before the step
-    is ep_step (csrc/orr_env_kernels.h, orr_step_kernel<.., CLIPS>): 32 + 4 s, 33 + 4 s, 34 + 4 s = Philox block 8 + s, words 0..2 of the
-    episode's (seed, robot index, episode) stream.  The clip is set[clip_draw_index(m, n)] with m the 24-bit integer of the first."""
-    d = 32 + 4 * np.asarray(ep_step, dtype=np.int64)
-    return d, d + 1, d + 2
-
-
-def clip_change_time(t, tmin, tmax, u):
-    """The next clip change at motion time t (_reset_clip_change_time, imitation_task.py:1057-1069): t + tmin + (tmax - tmin) u in
-    float64, stored as float32 (the record's CLIP_CHANGE_TIME); +inf where switching is off."""
-    if not math.isfinite(tmax):
-        return np.float32(np.inf)
-    return np.float32(float(t) + (float(np.float32(tmin)) + (float(np.float32(tmax)) - float(np.float32(tmin))) * float(u)))
-
-
-def clip_switch_spec(clip_time_min, clip_time_max, robot_names):
-    """clip_time_min / clip_time_max (ImitationTask's kwargs: a float, or a dict by robot name for mixed batches; None = +inf) ->
-    {robot name: (tmin, tmax)}.  (+inf, +inf) = no switching (the reference's default); otherwise both finite, 0 <= tmin <= tmax.
-    ValueError on anything the C-ABI (orr_set_clip_switch) would refuse."""
-    def per_name(v, name, what):
-        if isinstance(v, dict):
-            unknown = set(v) - set(robot_names)
-            if unknown:
-                raise ValueError("%s names robots that are not in this batch: %s" % (what, sorted(unknown)))
-            v = v.get(name)
-        if v is None:
-            return math.inf
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError("%s must be a number or a dict by robot name, not %r" % (what, v))
-        return float(v)
-    out = {}
-    for name in robot_names:
-        lo, hi = per_name(clip_time_min, name, "clip_time_min"), per_name(clip_time_max, name, "clip_time_max")
-        if math.isnan(lo) or math.isnan(hi):
-            raise ValueError("clip_time_min / clip_time_max of %s: NaN" % name)
-        if lo < 0 or hi < 0:
-            raise ValueError("clip_time_min / clip_time_max of %s must not be negative" % name)
-        if lo > hi:
-            raise ValueError("clip_time_min > clip_time_max for %s" % name)
-        if math.isinf(lo) != math.isinf(hi):
-            raise ValueError("clip_time_min / clip_time_max of %s: both finite, or both inf (no switching)" % name)
-        out[name] = (lo, hi)
-    return out
-
-
-def torque_limit_spec(torque_limits, robot_names):
-    """torque_limits (MotorModel's kwarg, minitaur_motor.py:57-66: None, a float, 12 floats in motor order, or a dict of robot name to
-    either, for mixed batches) -> {robot name: float32 [12]}, +inf = no limit.  ValueError on anything the C-ABI
-    (orr_set_torque_limits) would refuse: NaN, a negative limit, a wrong length."""
-    def one(v, name):
-        if v is None:
-            return np.full(12, np.inf, dtype=np.float32)
-        if isinstance(v, (bool, np.bool_, str, dict)):
-            raise ValueError("torque_limits of %s must be None, a number or 12 numbers in motor order, not %r" % (name, v))
-        try:
-            a = np.asarray(v, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError("torque_limits of %s must be None, a number or 12 numbers in motor order, not %r" % (name, v))
-        if a.ndim == 0:
-            a = np.full(12, float(a))
-        if a.shape != (12,):
-            raise ValueError("torque_limits of %s must be a number or 12 numbers in motor order, got shape %s" % (name, a.shape))
-        if np.isnan(a).any() or (a < 0).any():
-            raise ValueError("torque_limits of %s must be >= 0 (0 = the motor is off, inf = no limit), got %r" % (name, v))
-        return a.astype(np.float32)
-    if isinstance(torque_limits, dict):
-        unknown = set(torque_limits) - set(robot_names)
-        if unknown:
-            raise ValueError("torque_limits names robots that are not in this batch: %s" % sorted(unknown))
-        return {name: one(torque_limits.get(name), name) for name in robot_names}
-    return {name: one(torque_limits, name) for name in robot_names}
-
-
-# ---- task noise (orr_set_task_noise; ImitationTask's perturb_init_state_prob and tar_obs_noise) ------------------------------------
-NOISE_RESET_BLOCK = 0x20000000      # Philox blocks 0x20000000 .. 0x20000008 of the episode's stream: the 36 uniforms U(k) of a reset's perturbation
-NOISE_HEADING_BLOCK = 0x30000000    # block 0x30000000 + i: the heading noise of target observation i of the episode (tar_noise_block)
-# _apply_state_perturb's standard deviations (imitation_task.py:1201-1206), by the names of orr_task_noise's fields
-INIT_PERTURB_STD = {"root_pos_std": 0.025, "root_rot_std": 0.025 * math.pi, "joint_pose_std": 0.05 * math.pi, "root_vel_std": 0.1,
-                    "root_ang_vel_std": 0.05 * math.pi, "joint_vel_std": 0.05 * math.pi}
-
-
-def normal_pair(ua, ub):
-    """The pair of standard normals the device makes of two stream uniforms (csrc/orr_device.h, normal_pair), in float64:
-    r = sqrt(-2 ln(1 - ua)), (z0, z1) = r (cos, sin)(2 pi ub).  ua, ub in [0, 1) (either may be 0); works on arrays."""
-    ua, ub = np.asarray(ua, dtype=np.float64), np.asarray(ub, dtype=np.float64)
-    r = np.sqrt(-2.0 * np.log1p(-ua))
-    phi = 2.0 * np.pi * ub
-    return r * np.cos(phi), r * np.sin(phi)
-
-
-def init_perturb_draw_indices():
-    """Draw indices (4 * block + word) of U(0) .. U(35), the uniforms of a reset's perturbation."""
-    return 4 * NOISE_RESET_BLOCK + np.arange(36, dtype=np.int64)
-
-
-def init_perturb_draws(U, prob, std=None):
-    """What a reset does with its 36 uniforms U(k) (the stream's draws init_perturb_draw_indices(); shape [..., 36]) - the draw rule of
-    include/openroborl_hip.h, orr_set_task_noise, in float64 with the float32 deviations the device holds.  Returns a dict:
-    perturbed [...] bool (U(0) < prob), z [..., 32] the normals, axis [..., 3] (normalised; zero where its squared norm is below 1e-30),
-    and the offsets the perturbed robots get on top of the reference state - pos [..., 2] (x, y), angle [...] (about axis), joints
-    [..., 12], vel [..., 2], ang_vel [..., 3], joint_vel [..., 12] - and rot [..., 4], the xyzw quaternion that multiplies the reference
-    rotation from the left."""
-    U = np.asarray(U, dtype=np.float64)
-    sd = {k: float(np.float32(v)) for k, v in dict(INIT_PERTURB_STD, **(std or {})).items()}
-    z0, z1 = normal_pair(U[..., 4:36:2], U[..., 5:36:2])
-    z = np.stack([z0, z1], axis=-1).reshape(U.shape[:-1] + (32,))
-    a = -1.0 + 2.0 * U[..., 1:4]
-    n2 = (a * a).sum(axis=-1, keepdims=True)
-    axis = np.where(n2 < 1e-30, 0.0, a / np.sqrt(np.maximum(n2, 1e-300)))
-    angle = sd["root_rot_std"] * z[..., 2]
-    rot = np.concatenate([axis * np.sin(0.5 * angle)[..., None], np.cos(0.5 * angle)[..., None]], axis=-1)
-    rot = np.where(n2 < 1e-30, np.array([0.0, 0.0, 0.0, 1.0]), rot)
-    return {"perturbed": U[..., 0] < float(np.float32(prob)), "z": z, "axis": axis, "pos": sd["root_pos_std"] * z[..., 0:2], "angle": angle,
-            "joints": sd["joint_pose_std"] * z[..., 3:15], "vel": sd["root_vel_std"] * z[..., 15:17],
-            "ang_vel": sd["root_ang_vel_std"] * z[..., 17:20], "joint_vel": sd["joint_vel_std"] * z[..., 20:32], "rot": rot}
-
-
-def tar_noise_block(ep_step_or_reset=None):
-    """Philox block of a target observation's heading noise: NOISE_HEADING_BLOCK for the observation of a reset (None; the auto-reset
-    inside a step included: the NEW episode's stream), NOISE_HEADING_BLOCK + 1 + s for the step whose env-step counter before the step
-    is s.  The noise is tar_heading_std * z0 of normal_pair(word 0, word 1) = draws 4 * block, 4 * block + 1.  Works on integer arrays."""
-    if ep_step_or_reset is None:
-        return NOISE_HEADING_BLOCK
-    return NOISE_HEADING_BLOCK + 1 + np.asarray(ep_step_or_reset, dtype=np.int64)
-
-
-def task_noise_spec(perturb_init_state_prob=0.0, tar_obs_noise=None, init_perturb_std=None):
-    """ImitationTask's perturb_init_state_prob / tar_obs_noise (a float, or a list whose first entry is used: the reference reads only
-    [0]; None = off) and an optional dict overriding some of INIT_PERTURB_STD -> the orr_task_noise struct.  ValueError on anything
-    the C-ABI (orr_set_task_noise) would refuse."""
-    def number(v, what):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError("%s must be a number, not %r" % (what, v))
-        return float(v)
-    prob = number(0.0 if perturb_init_state_prob is None else perturb_init_state_prob, "perturb_init_state_prob")
-    if not (0.0 <= prob <= 1.0):
-        raise ValueError("perturb_init_state_prob must be a probability in [0, 1], not %r" % (prob,))
-    if isinstance(tar_obs_noise, (list, tuple, np.ndarray)):
-        if len(tar_obs_noise) == 0:
-            raise ValueError("tar_obs_noise must not be empty (its first entry is the heading's standard deviation)")
-        tar_obs_noise = number(tar_obs_noise[0], "tar_obs_noise[0]")
-    vals = dict(INIT_PERTURB_STD, tar_heading_std=0.0 if tar_obs_noise is None else number(tar_obs_noise, "tar_obs_noise"))
-    unknown = set(init_perturb_std or {}) - set(INIT_PERTURB_STD)
-    if unknown:
-        raise ValueError("init_perturb_std: unknown entries %s (known: %s)" % (sorted(unknown), sorted(INIT_PERTURB_STD)))
-    for k, v in (init_perturb_std or {}).items():
-        vals[k] = number(v, "init_perturb_std[%r]" % k)
-    for k, v in vals.items():
-        if not (0.0 <= v < math.inf):
-            raise ValueError("%s must be a finite standard deviation >= 0, not %r" % ("tar_obs_noise" if k == "tar_heading_std" else k, v))
-    return _abi.OrrTaskNoise(perturb_init_state_prob=prob, **vals)
-
-
-# ---- sensor noise (orr_set_sensor_noise; Minitaur._observation_noise_stdev) ---------------------------------------------------------
-SENSOR_NOISE_BLOCK = 0x10000000     # block 0x10000000 + (i << 9) + (slot << 4) + lane of the episode's stream (sensor_noise_block)
-SENSOR_SLOT_HIST, SENSOR_SLOT_FILTER, SENSOR_SLOT_TARGET = 17, 18, 19   # slots 0..16: the sub-steps' motor-angle readings, two sub-steps a slot
-
-
-def sensor_noise_block(i, slot, lane):
-    """Philox block of a sensor-noise draw (include/openroborl_hip.h, orr_set_sensor_noise): i = 0 for a reset of the episode (the
-    auto-reset inside a step included: the NEW episode's stream), 1 + s for the step whose env-step counter before it is s; slot
-    0..16 = sub-steps 2 slot (words 0, 1) and 2 slot + 1 (words 2, 3), lane = motor; 17 = the sensor histories, lane = column (0..11
-    motor angle, 12 roll, 13 pitch, 14 roll rate, 15 pitch rate); 18 = the filter history's initial value, lane = motor; 19 = the
-    target observation's rpy, lane 0.  Works on integer arrays."""
-    i, slot, lane = np.asarray(i, dtype=np.int64), np.asarray(slot, dtype=np.int64), np.asarray(lane, dtype=np.int64)
-    if (i < 0).any() or (i >= 1 << 19).any() or (slot < 0).any() or (slot >= 32).any() or (lane < 0).any() or (lane >= 16).any():
-        raise ValueError("sensor_noise_block: i in [0, 2^19), slot in [0, 32), lane in [0, 16)")
-    return SENSOR_NOISE_BLOCK + (i << 9) + (slot << 4) + lane
-
-
-def sensor_noise_normals(u4):
-    """The four normals of a sensor-noise block from its four uniforms (shape [..., 4]): z0, z1 of the pair (word 0, word 1), then z0,
-    z1 of the pair (word 2, word 3), by normal_pair, in float64.  Which of them a slot uses: sensor_noise_block."""
-    u4 = np.asarray(u4, dtype=np.float64)
-    a0, a1 = normal_pair(u4[..., 0], u4[..., 1])
-    b0, b1 = normal_pair(u4[..., 2], u4[..., 3])
-    return np.stack([a0, a1, b0, b1], axis=-1)
-
-
-def sensor_noise_spec(observation_noise_stdev=None):
-    """Minitaur._observation_noise_stdev (None = off, or five numbers: motor angle, motor velocity, motor torque, base rpy, base rpy
-    rate; velocity and torque are kept and have no consumer on this path) -> the orr_sensor_noise struct.  ValueError on anything the
-    C-ABI (orr_set_sensor_noise) would refuse; the message names the field."""
-    if observation_noise_stdev is None:
-        return _abi.OrrSensorNoise()
-    if isinstance(observation_noise_stdev, (str, dict, bool, np.bool_)) or np.ndim(observation_noise_stdev) != 1 or len(observation_noise_stdev) != 5:
-        raise ValueError("observation_noise_stdev must be None or five numbers (%s), not %r" % (", ".join(_abi.SENSOR_NOISE_FIELDS), observation_noise_stdev))
-    vals = {}
-    for name, v in zip(_abi.SENSOR_NOISE_FIELDS, observation_noise_stdev):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError("%s must be a number, not %r" % (name, v))
-        if not (0.0 <= float(v) < math.inf):       # NaN fails the comparison
-            raise ValueError("%s must be a finite standard deviation >= 0, not %r" % (name, v))
-        vals[name] = float(v)
-    return _abi.OrrSensorNoise(**vals)
-
-
-def sensor_noise_on(spec):
-    """Whether the setting selects the sensor variants of the kernels: a deviation with a consumer is above 0."""
-    return spec.motor_angle_std > 0.0 or spec.base_rpy_std > 0.0 or spec.base_rpy_rate_std > 0.0
-
-
-# ---- domain randomisation (orr_set_randomizer, orr_bind_randomizer_params; ControllableEnvRandomizerFromConfig) ----------------------
-RAND_NOOP_NAMES = ("battery", "motor friction")       # accepted and ignored: no-ops in the reference (minitaur_motor.py:86-102)
-RAND_REFUSED_NAMES = {"control step": "every robot of a batch takes the same number of sub-steps per step",
-                      "individual mass": "the engine scales masses by two ratios (base, legs), not per link",
-                      "individual inertia": "the engine scales inertias by two ratios (base, legs), not per link",
-                      "restitution": "the contact model has no restitution"}
-RAND_POSITIVE_NAMES = ("base mass", "inertia", "mass")   # ratios that scale a mass or an inertia: lo > 0
-# row words of the params buffer (include/openroborl_hip.h, orr_bind_randomizer_params) by parameter
-RAND_ROW_WORDS = {"inertia": slice(0, 2), "joint friction": slice(2, 10), "latency": slice(10, 11), "lateral friction": slice(11, 12),
-                  "mass": slice(12, 14), "motor strength": slice(14, 26), "base mass": slice(26, 27), "global motor strength": slice(27, 28),
-                  "leg weaken": slice(28, 30), "single leg weaken": slice(30, 31)}
-RAND_LEG_WORD = 28                                       # the weakened leg, as a float 0..3: not a draw in [0, 1)
-
-
-def randomizer_latency_max(sim_dt=0.001):
-    """The largest latency bound orr_set_randomizer accepts, in float32 as the C-ABI computes it: the ring reader blends the entries
-    int(latency / sim_dt) and int(latency / sim_dt) + 1 back from the newest, and a ring of RING_DEPTH entries holds those while
-    int(latency / sim_dt) + 1 <= RING_DEPTH - 1."""
-    return float(np.float32(_abi.RING_DEPTH - 2) * np.float32(sim_dt))
-
-
-def randomizer_spec(config, sim_dt=0.001):
-    """The reference's randomiser configuration -> the orr_randomizer struct.  config: None (the built-in six ranges: what
-    orr_set_randomizer(NULL) restores), "all_params" (the reference's dictionary of that name: the same six, as a table), or a dict of
-    name -> [lo, hi] with the reference's names (_abi.RAND_PARAM_NAMES; "battery" and "motor friction" are accepted and ignored).
-    ValueError, naming the entry, on "control step", "individual mass", "individual inertia", "restitution", an unknown name, a
-    four-entry rejection range and anything the C-ABI would refuse."""
-    if config is None or (isinstance(config, str) and config == "all_params"):
-        config = cfgmod.RANDOMIZER_ALL_PARAMS
-    if not isinstance(config, dict):
-        raise ValueError("randomizer config must be None, \"all_params\" or a dict of parameter name to [lo, hi], not %r" % (config,))
-    spec = _abi.OrrRandomizer()
-    for name, rng in config.items():
-        if name in RAND_REFUSED_NAMES:
-            raise ValueError("randomizer parameter %r is not supported: %s" % (name, RAND_REFUSED_NAMES[name]))
-        if name not in _abi.RAND_PARAM_NAMES and name not in RAND_NOOP_NAMES:
-            raise ValueError("unknown randomizer parameter %r (known: %s)" % (name, ", ".join(_abi.RAND_PARAM_NAMES + RAND_NOOP_NAMES)))
-        if isinstance(rng, (str, dict, bool, np.bool_)) or np.ndim(rng) != 1:
-            raise ValueError("randomizer parameter %r: the range must be [lo, hi], not %r" % (name, rng))
-        if len(rng) == 4:
-            raise ValueError("randomizer parameter %r: four-entry rejection ranges [lo, hi, reject_lo, reject_hi] are not supported" % (name,))
-        if len(rng) != 2:
-            raise ValueError("randomizer parameter %r: the range must be [lo, hi], not %r" % (name, rng))
-        for v in rng:
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-                raise ValueError("randomizer parameter %r: the bounds must be numbers, not %r" % (name, rng))
-        lo, hi = float(np.float32(rng[0])), float(np.float32(rng[1]))    # as the device holds them
-        if not (math.isfinite(lo) and math.isfinite(hi)):
-            raise ValueError("randomizer parameter %r: the bounds must be finite numbers, not %r" % (name, rng))
-        if lo > hi:
-            raise ValueError("randomizer parameter %r: lo > hi in %r" % (name, rng))
-        if name in RAND_NOOP_NAMES:
-            continue
-        if name in RAND_POSITIVE_NAMES and not lo > 0.0:
-            raise ValueError("randomizer parameter %r: lo must be > 0 (a ratio of a mass or an inertia), not %r" % (name, rng))
-        if lo < 0.0:
-            raise ValueError("randomizer parameter %r: lo must be >= 0, not %r" % (name, rng))
-        if name == "latency" and hi > randomizer_latency_max(sim_dt):
-            raise ValueError("randomizer parameter 'latency': hi = %r is beyond what the latency ring holds, (RING_DEPTH - 2) * sim_dt = %g s"
-                             % (rng[1], randomizer_latency_max(sim_dt)))
-        p = _abi.RAND_PARAM_NAMES.index(name)
-        spec.enabled[p], spec.lo[p], spec.hi[p] = 1, lo, hi
-    return spec
-
-
-def randomizer_draw_indices():
-    """Draw indices (4 * block + word; beyond 32 bits) on the episode's stream of the 31 uniforms behind a row of the params buffer, in
-    row order: draws 0..25, then block RAND_BLOCK words 0..3 (base mass, global motor strength, the weakened leg's draw, leg weaken's
-    ratio) and block RAND_BLOCK + 1 word 0 (single leg weaken).  Row word 28 is not the draw itself but the leg made of it
-    (randomizer_row)."""
-    return np.concatenate([np.arange(26, dtype=np.int64), 4 * _abi.RAND_BLOCK + np.arange(4, dtype=np.int64),
-                           4 * (_abi.RAND_BLOCK + 1) + np.arange(1, dtype=np.int64)])
-
-
-def randomizer_row(U):
-    """The params-buffer row [..., RAND_ROW] (float64) that a reset writes for the 31 uniforms U [..., 31] of randomizer_draw_indices():
-    the draws as they are, word 28 = the weakened leg (m * 4) >> 24 with m the draw's 24-bit integer, word 31 = 0."""
-    U = np.asarray(U, dtype=np.float64)
-    row = np.zeros(U.shape[:-1] + (_abi.RAND_ROW,))
-    row[..., :31] = U
-    m = np.floor(U[..., RAND_LEG_WORD] * 16777216.0).astype(np.int64)
-    row[..., RAND_LEG_WORD] = ((m * 4) >> 24).astype(np.float64)
-    return row
-
-
-def randomizer_apply(spec, row):
-    """What a reset writes into the record for a params-buffer row [..., RAND_ROW] under the table `spec` (randomizer_spec's struct):
-    float64 predictions by the C-ABI's rule - value = lo + u (hi - lo) with the float32 bounds the device holds, a disabled parameter
-    writes nothing, parameters apply in the reference's order (sorted by name) and a later one overwrites an earlier one's words.
-    Returns a dict of record field -> array: STRENGTH [..., 12], MASS_RATIO [..., 2], INERTIA_RATIO [..., 2], KNEE_FRICTION [..., 4],
-    LATENCY [..., 1], FOOT_MU [..., 1]; NaN marks a word that no enabled parameter writes (the record keeps its value)."""
-    row = np.asarray(row, dtype=np.float64)
-    lead = row.shape[:-1]
-    out = {k: np.full(lead + (n,), np.nan) for k, n in (("STRENGTH", 12), ("MASS_RATIO", 2), ("INERTIA_RATIO", 2), ("KNEE_FRICTION", 4),
-                                                        ("LATENCY", 1), ("FOOT_MU", 1))}
-    leg = row[..., RAND_LEG_WORD]
-    for p, name in enumerate(_abi.RAND_PARAM_NAMES):        # the application order
-        if not spec.enabled[p]:
-            continue
-        lo, hi = float(spec.lo[p]), float(spec.hi[p])
-        w = row[..., RAND_ROW_WORDS[name]]
-        v = lo + (w[..., -1:] if name == "leg weaken" else w) * (hi - lo)
-        if name == "base mass":
-            out["MASS_RATIO"][..., 0:1] = v
-        elif name == "global motor strength":
-            out["STRENGTH"][...] = v
-        elif name == "inertia":
-            out["INERTIA_RATIO"][...] = v
-        elif name == "joint friction":
-            out["KNEE_FRICTION"][...] = v[..., 0::2]      # the knee joints take the even ones of the eight draws
-        elif name == "latency":
-            out["LATENCY"][...] = v
-        elif name == "lateral friction":
-            out["FOOT_MU"][...] = v
-        elif name == "mass":
-            out["MASS_RATIO"][...] = v
-        elif name == "motor strength":
-            out["STRENGTH"][...] = v
-        else:                                             # leg weaken (the drawn leg), single leg weaken (leg 0)
-            which = leg if name == "leg weaken" else np.zeros(lead)
-            on = (np.arange(12) // 3) == which[..., None]
-            out["STRENGTH"][...] = np.where(on, v, 1.0)
-    return out
-
-
-# ---- external pushes (orr_set_push, orr_bind_push_outputs) --------------------------------------------------------------------------
-PUSH_KEYS = ("prob", "interval_s", "lin_vel", "lin_vel_z", "ang_vel", "grace_steps")
-
-
-def push_spec(push=None, action_repeat=cfgmod.ACTION_REPEAT, sim_dt=0.001, max_coord_velocity=100.0):
-    """The push setting -> the orr_push struct.  push: None (off) or a dict with `prob` (probability of a kick per robot and env step) or
-    `interval_s` (mean time between kicks: prob = action_repeat * sim_dt / interval_s), `lin_vel` = (lo, hi) the kick's horizontal
-    speed in m/s, `lin_vel_z` (vertical component in U(-z, z)), `ang_vel` (each component of the angular kick in U(-a, a), rad/s) and
-    `grace_steps` (no kick while the episode's env-step counter is below it); every key but one of prob / interval_s is optional (0).
-    ValueError on anything the C-ABI (orr_set_push) would refuse; the message names the field."""
-    if push is None:
-        return _abi.OrrPush()
-    if not isinstance(push, dict):
-        raise ValueError("push must be None or a dict with the keys %s, not %r" % (", ".join(PUSH_KEYS), push))
-    for k in push:
-        if k not in PUSH_KEYS:
-            raise ValueError("unknown push key %r (known: %s)" % (k, ", ".join(PUSH_KEYS)))
-
-    def number(name, v):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError("push: %s must be a number, not %r" % (name, v))
-        if not math.isfinite(float(v)):
-            raise ValueError("push: %s must be a finite number, not %r" % (name, v))
-        if float(v) < 0.0:
-            raise ValueError("push: %s must be >= 0, not %r" % (name, v))
-        return float(v)
-
-    if ("prob" in push) == ("interval_s" in push):
-        raise ValueError("push: give exactly one of prob and interval_s")
-    if "prob" in push:
-        prob = number("prob", push["prob"])
-    else:
-        interval = number("interval_s", push["interval_s"])
-        if not interval > 0.0:
-            raise ValueError("push: interval_s must be > 0, not %r" % (push["interval_s"],))
-        prob = float(action_repeat) * float(sim_dt) / interval
-    if prob > 1.0:
-        raise ValueError("push: %s gives a probability of %r per env step; it must lie in [0, 1]" % ("prob" if "prob" in push else "interval_s", prob))
-    lin = push.get("lin_vel", (0.0, 0.0))
-    if isinstance(lin, (str, dict)) or np.ndim(lin) != 1 or len(lin) != 2:
-        raise ValueError("push: lin_vel must be (lo, hi), not %r" % (lin,))
-    lo, hi = number("lin_vel lo", lin[0]), number("lin_vel hi", lin[1])
-    if lo > hi:
-        raise ValueError("push: lin_vel lo > hi in %r" % (lin,))
-    z, ang = number("lin_vel_z", push.get("lin_vel_z", 0.0)), number("ang_vel", push.get("ang_vel", 0.0))
-    for name, v in (("lin_vel hi", hi), ("lin_vel_z", z), ("ang_vel", ang)):
-        if float(np.float32(v)) > float(np.float32(max_coord_velocity)):
-            raise ValueError("push: %s = %r is above max_coord_velocity = %g (the physics clamps every coordinate velocity there)" % (name, v, max_coord_velocity))
-    grace = push.get("grace_steps", 0)
-    if isinstance(grace, (bool, np.bool_)) or not isinstance(grace, (int, np.integer)):
-        raise ValueError("push: grace_steps must be an integer, not %r" % (grace,))
-    if grace < 0 or grace >= 1 << 31:
-        raise ValueError("push: grace_steps must be >= 0 (and below 2^31), not %r" % (grace,))
-    return _abi.OrrPush(prob=prob, lin_lo=lo, lin_hi=hi, lin_z=z, ang=ang, grace_steps=int(grace))
-
-
-def push_on(spec):
-    """Whether the setting selects the push variant of the step kernel: the probability is above 0."""
-    return spec.prob > 0.0
-
-
-def push_block(s):
-    """Philox blocks (A, B) of the push of the step whose env-step counter before it is s (include/openroborl_hip.h, orr_set_push):
-    A = PUSH_BLOCK + 2 s, B = A + 1, on the stream (seed, robot index, episode) as they are before the step.  Works on integer arrays."""
-    s = np.asarray(s, dtype=np.int64)
-    if (s < 0).any() or (s >= 1 << 27).any():
-        raise ValueError("push_block: s in [0, 2^27)")
-    return _abi.PUSH_BLOCK + 2 * s, _abi.PUSH_BLOCK + 2 * s + 1
-
-
-def push_kick(spec, u8, s=None):
-    """What a step does with the eight uniforms u8 [..., 8] of its blocks A (words 0..3) and B (4..7) under the setting `spec`
-    (push_spec's struct) - the draw rule of orr_set_push in float64, with the float32 settings the device holds (lin_hi - lin_lo as
-    its one float32 subtraction).  s: the env-step counter(s) before the step, for the grace period (None = past it).
-    -> (kicked [...] bool, dv [..., 3], dw [..., 3]); dv = dw = 0 where not kicked."""
-    u8 = np.asarray(u8, dtype=np.float64)
-    prob, lo, z, ang = (float(np.float32(getattr(spec, k))) for k in ("prob", "lin_lo", "lin_z", "ang"))
-    span = float(np.float32(spec.lin_hi) - np.float32(spec.lin_lo))
-    kicked = u8[..., 0] < prob
-    if s is not None:
-        kicked = kicked & (np.asarray(s, dtype=np.int64) >= int(spec.grace_steps))
-    theta = 2.0 * np.pi * u8[..., 1]
-    m = u8[..., 2] * span + lo
-    dv = np.stack([m * np.cos(theta), m * np.sin(theta), u8[..., 3] * (2.0 * z) - z], axis=-1)
-    dw = u8[..., 4:7] * (2.0 * ang) - ang if ang > 0.0 else np.zeros(u8.shape[:-1] + (3,))
-    return kicked, np.where(kicked[..., None], dv, 0.0), np.where(kicked[..., None], dw, 0.0)
-
-
-# ---- the privileged observation (orr_privileged_obs): the words of a robot's row, include/openroborl_hip.h ----
-PRIV_DIM = _abi.PRIV_DIM
-PRIV_FIELDS = {"base_lin_vel": slice(0, 3),          # R^T LINVEL, R = the rotation of QUAT (x) INIT_QUAT^-1 (base frame)
-               "base_ang_vel": slice(3, 6),          # R^T ANGVEL
-               "gravity": slice(6, 9),               # R^T (0, 0, -1)
-               "height": slice(9, 10),               # POS[2]
-               "motor_strength": slice(10, 22),      # STRENGTH
-               "latency": slice(22, 23),             # LATENCY / ((RING_DEPTH - 2) * sim_dt)
-               "foot_friction": slice(23, 24),       # FOOT_MU
-               "knee_friction": slice(24, 28),       # KNEE_FRICTION * 20
-               "mass_ratio": slice(28, 30),          # MASS_RATIO
-               "inertia_ratio": slice(30, 32),       # INERTIA_RATIO
-               "foot_contact": slice(32, 36),        # 1.0 / 0.0 per leg (contact outputs)
-               "foot_force": slice(36, 40),          # mean normal force per leg in units of 100 N (contact outputs)
-               "push": slice(40, 46),                # dv, dw of the step (push outputs)
-               "episode_progress": slice(46, 47),    # EP_STEP / max(MAX_EP_STEPS, 1)
-               "reserved": slice(47, 48)}            # 0
-
-
 def action_space():
     """minitaur.py:145-148."""
     return Box(np.array([-2 * math.pi] * 12), np.array([2 * math.pi] * 12), dtype=np.float32)
+
+
+def _check_flags(**flags):
+    """The on / off arguments of the two env classes, in the order given."""
+    for name, v in flags.items():
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("%s must be True or False, got %r" % (name, v))
 
 
 class VecQuadrupedEnv(object):
@@ -569,16 +101,8 @@ class VecQuadrupedEnv(object):
                  init_perturb_std=None, reward_terms=False, contact_outputs=False, torque_limits=None, actuator_outputs=False,
                  observation_noise_stdev=None, randomizer_config=None, randomizer_params=False, push=None, push_outputs=False):
         import torch
-        if not isinstance(push_outputs, (bool, np.bool_)):
-            raise ValueError("push_outputs must be True or False, got %r" % (push_outputs,))
-        if not isinstance(randomizer_params, (bool, np.bool_)):
-            raise ValueError("randomizer_params must be True or False, got %r" % (randomizer_params,))
-        if not isinstance(reward_terms, (bool, np.bool_)):
-            raise ValueError("reward_terms must be True or False, got %r" % (reward_terms,))
-        if not isinstance(contact_outputs, (bool, np.bool_)):
-            raise ValueError("contact_outputs must be True or False, got %r" % (contact_outputs,))
-        if not isinstance(actuator_outputs, (bool, np.bool_)):
-            raise ValueError("actuator_outputs must be True or False, got %r" % (actuator_outputs,))
+        _check_flags(push_outputs=push_outputs, randomizer_params=randomizer_params, reward_terms=reward_terms,
+                     contact_outputs=contact_outputs, actuator_outputs=actuator_outputs)
         # the values here, ahead of everything that needs the device; a dict's robot names below, once the batch's robots are known
         torque_limit_spec(torque_limits, sorted(torque_limits) if isinstance(torque_limits, dict) else ["every robot"])
         # sensor noise (Minitaur._observation_noise_stdev): off by default, as the reference ships it
@@ -792,6 +316,21 @@ class VecQuadrupedEnv(object):
         except Exception:
             pass
 
+    def _zeros(self, *shapes):
+        t = self.torch
+        return tuple(t.zeros(s, dtype=t.float32, device=self.device) for s in shapes)
+
+    def _bind_outputs(self, bind, attrs, bufs):
+        """The one rule of the output binds: hand the C-ABI entry `bind` the device pointers of the tensors `bufs` (None = unbind: NULL
+        for each), then keep the tensors (or None) in the attributes `attrs`.  Synchronises first: launches in flight still write the
+        buffers that an unbind or a new bind lets go.  A bound buffer selects the kernel variant, so launch_params_generation moves."""
+        self.torch.cuda.synchronize(self.device)
+        bufs = bufs if bufs is not None else (None,) * len(attrs)
+        _lib.check(bind(self.h, *[None if b is None else b.data_ptr() for b in bufs]), self.L)
+        for a, b in zip(attrs, bufs):
+            setattr(self, a, b)
+        self.launch_params_generation += 1
+
     def set_task_noise(self, perturb_init_state_prob=0.0, tar_obs_noise=None, init_perturb_std=None):
         """Change the task noise of a running env (orr_set_task_noise): read from the next launch on.  All defaults = off.  A launch
         takes nothing of it by value, but it selects the kernel variant: holders of captured graphs re-capture (launch_params_generation)."""
@@ -825,21 +364,14 @@ class VecQuadrupedEnv(object):
         reset writes the new episode's row.  suspend=True (the reference's suspend_randomization): resets draw nothing and apply the
         rows as they stand (set_randomization_parameters).  It selects the kernel variant: holders of captured graphs re-capture
         (launch_params_generation); the variant's first launch in a process loads its code object, so step once eagerly before a capture."""
-        t = self.torch
-        if on:
-            rows = self.randomizer_rows
-            if rows is None:
-                rows = t.zeros((self.num_robot, _abi.RAND_ROW), dtype=t.float32, device=self.device)
-                rows[:, :31] = 0.5          # mid-range until a reset writes them (suspended from the start: every parameter at its centre)
-                rows[:, RAND_LEG_WORD] = 0.0
-            t.cuda.synchronize(self.device)
-            _lib.check(self.L.orr_bind_randomizer_params(self.h, rows.data_ptr(), 1 if suspend else 0), self.L)
-            self.randomizer_rows, self.randomizer_suspended = rows, bool(suspend)
-        else:
-            t.cuda.synchronize(self.device)      # launches in flight still write the buffer
-            _lib.check(self.L.orr_bind_randomizer_params(self.h, None, 0), self.L)
-            self.randomizer_rows, self.randomizer_suspended = None, False
-        self.launch_params_generation += 1
+        rows = self.randomizer_rows if on else None
+        if on and rows is None:
+            rows, = self._zeros((self.num_robot, _abi.RAND_ROW))
+            rows[:, :31] = 0.5          # mid-range until a reset writes them (suspended from the start: every parameter at its centre)
+            rows[:, RAND_LEG_WORD] = 0.0
+        suspend = bool(on and suspend)
+        self._bind_outputs(lambda h, p: self.L.orr_bind_randomizer_params(h, p, int(suspend)), ("randomizer_rows",), (rows,) if on else None)
+        self.randomizer_suspended = suspend
 
     def set_push(self, push=None):
         """Change the external pushes of a running env (orr_set_push; see push_spec for `push`, None = off): read from the next step on.
@@ -856,16 +388,10 @@ class VecQuadrupedEnv(object):
         number of kicks in its current episode including that step; None while unbound.  Privileged information: no observation holds
         it.  A bound buffer selects the push variant whatever the probability: holders of captured graphs re-capture
         (launch_params_generation); the variant's first launch in a process loads its code object, so step once eagerly before a capture."""
-        t = self.torch
-        t.cuda.synchronize(self.device)          # launches in flight still write the buffer
-        if on:
-            out = self.push_out if self.push_out is not None else t.zeros((self.num_robot, _abi.PUSH_ROW), dtype=t.float32, device=self.device)
-            _lib.check(self.L.orr_bind_push_outputs(self.h, out.data_ptr()), self.L)
-            self.push_out = out
-        else:
-            _lib.check(self.L.orr_bind_push_outputs(self.h, None), self.L)
-            self.push_out = None
-        self.launch_params_generation += 1
+        bufs = None
+        if on:       # the buffer is kept across binds
+            bufs = (self.push_out,) if self.push_out is not None else self._zeros((self.num_robot, _abi.PUSH_ROW))
+        self._bind_outputs(self.L.orr_bind_push_outputs, ("push_out",), bufs)
 
     def get_randomization_parameters(self):
         """ControllableEnvRandomizerFromConfig.get_randomization_parameters for the whole batch: a dict of parameter name -> tensor [N,
@@ -915,18 +441,9 @@ class VecQuadrupedEnv(object):
         """Bind (allocating on first use) or unbind the per-term reward outputs (orr_bind_reward_terms): env.reward_terms [N, 5], valid
         after step / replay_step, env.episode_term_sums [N, 5] and env.term_log [ep_log_capacity, 5]; all None while unbound.  It
         selects the kernel variant: holders of captured graphs re-capture (launch_params_generation)."""
-        t = self.torch
-        if on:
-            n = _abi.NUM_REWARD_TERMS
-            bufs = (t.zeros((self.num_robot, n), dtype=t.float32, device=self.device), t.zeros((self.num_robot, n), dtype=t.float32, device=self.device),
-                    t.zeros((self.ep_log.shape[0], n), dtype=t.float32, device=self.device))
-            _lib.check(self.L.orr_bind_reward_terms(self.h, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr()), self.L)
-            self.reward_terms, self.episode_term_sums, self.term_log = bufs
-        else:
-            t.cuda.synchronize(self.device)      # launches in flight still write the buffers
-            _lib.check(self.L.orr_bind_reward_terms(self.h, None, None, None), self.L)
-            self.reward_terms = self.episode_term_sums = self.term_log = None
-        self.launch_params_generation += 1
+        n = _abi.NUM_REWARD_TERMS
+        self._bind_outputs(self.L.orr_bind_reward_terms, ("reward_terms", "episode_term_sums", "term_log"),
+                           self._zeros((self.num_robot, n), (self.num_robot, n), (self.ep_log.shape[0], n)) if on else None)
 
     def bind_contact_outputs(self, on=True):
         """Bind (allocating on first use) or unbind the foot contact outputs (orr_bind_contact_outputs): env.contact_out [N, 16] (row =
@@ -934,18 +451,8 @@ class VecQuadrupedEnv(object):
         [N, 8] (row = [leg][stance steps, normal sum] of the robot's current episode) and env.contact_log [ep_log_capacity, 8]; all None
         while unbound.  It selects the kernel variant: holders of captured graphs re-capture (launch_params_generation); the variant's
         first launch in a process loads its code object, so step once eagerly before a capture (GraphRollout's first segment does)."""
-        t = self.torch
-        if on:
-            bufs = (t.zeros((self.num_robot, _abi.CONTACT_OUT_DIM), dtype=t.float32, device=self.device),
-                    t.zeros((self.num_robot, _abi.CONTACT_EP_DIM), dtype=t.float32, device=self.device),
-                    t.zeros((self.ep_log.shape[0], _abi.CONTACT_EP_DIM), dtype=t.float32, device=self.device))
-            _lib.check(self.L.orr_bind_contact_outputs(self.h, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr()), self.L)
-            self.contact_out, self.episode_contact, self.contact_log = bufs
-        else:
-            t.cuda.synchronize(self.device)      # launches in flight still write the buffers
-            _lib.check(self.L.orr_bind_contact_outputs(self.h, None, None, None), self.L)
-            self.contact_out = self.episode_contact = self.contact_log = None
-        self.launch_params_generation += 1
+        shapes = ((self.num_robot, _abi.CONTACT_OUT_DIM), (self.num_robot, _abi.CONTACT_EP_DIM), (self.ep_log.shape[0], _abi.CONTACT_EP_DIM))
+        self._bind_outputs(self.L.orr_bind_contact_outputs, ("contact_out", "episode_contact", "contact_log"), self._zeros(*shapes) if on else None)
 
     def _contact_rows(self):
         if self.contact_out is None:
@@ -982,18 +489,8 @@ class VecQuadrupedEnv(object):
         [N, 4] (work, sum tau^2, largest |tau|, saturated steps of the robot's current episode) and env.actuator_log [ep_log_capacity,
         4]; all None while unbound.  It selects the kernel variant: holders of captured graphs re-capture (launch_params_generation); the
         variant's first launch in a process loads its code object, so step once eagerly before a capture."""
-        t = self.torch
-        if on:
-            bufs = (t.zeros((self.num_robot, _abi.NUM_MOTORS, _abi.ACTUATOR_OUT_DIM), dtype=t.float32, device=self.device),
-                    t.zeros((self.num_robot, _abi.ACTUATOR_EP_DIM), dtype=t.float32, device=self.device),
-                    t.zeros((self.ep_log.shape[0], _abi.ACTUATOR_EP_DIM), dtype=t.float32, device=self.device))
-            _lib.check(self.L.orr_bind_actuator_outputs(self.h, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr()), self.L)
-            self.actuator_out, self.episode_actuator, self.actuator_log = bufs
-        else:
-            t.cuda.synchronize(self.device)      # launches in flight still write the buffers
-            _lib.check(self.L.orr_bind_actuator_outputs(self.h, None, None, None), self.L)
-            self.actuator_out = self.episode_actuator = self.actuator_log = None
-        self.launch_params_generation += 1
+        shapes = ((self.num_robot, _abi.NUM_MOTORS, _abi.ACTUATOR_OUT_DIM), (self.num_robot, _abi.ACTUATOR_EP_DIM), (self.ep_log.shape[0], _abi.ACTUATOR_EP_DIM))
+        self._bind_outputs(self.L.orr_bind_actuator_outputs, ("actuator_out", "episode_actuator", "actuator_log"), self._zeros(*shapes) if on else None)
 
     def _actuator_rows(self):
         if self.actuator_out is None:
@@ -1051,6 +548,12 @@ class VecQuadrupedEnv(object):
         self._env_step_counter += 1
         return self.obs, self.reward, self.done, {}
 
+    def _check_tensors(self, who, *args):
+        """Each of args = (tensor, shape, dtype): a contiguous tensor of exactly that on the env device, or ValueError in who's name."""
+        for x, shape, dt in args:
+            if x.dtype != dt or x.device != self.obs.device or not x.is_contiguous() or tuple(x.shape) != shape:
+                raise ValueError("%s: expected a contiguous %s tensor of shape %s on %s" % (who, dt, shape, self.device))
+
     def step_into(self, actions, obs_out, reward_out, done_out):
         """step() writing its three outputs into the caller's tensors (rows of a rollout buffer) instead of env.obs / env.reward /
         env.done: contiguous float32 [N,160] (16-byte aligned), float32 [N], uint8 [N] on the env device.  Nothing here depends on
@@ -1059,10 +562,8 @@ class VecQuadrupedEnv(object):
         replays the old seed; `launch_params_generation` counts such changes and rollout.GraphRollout re-captures when it moves."""
         t = self.torch
         n = self.num_robot
-        for x, shape, dt in ((actions, (n, _abi.NUM_MOTORS), t.float32), (obs_out, (n, _abi.OBS_DIM), t.float32), (reward_out, (n,), t.float32),
-                             (done_out, (n,), t.uint8)):
-            if x.dtype != dt or x.device != self.obs.device or not x.is_contiguous() or tuple(x.shape) != shape:
-                raise ValueError("step_into: expected a contiguous %s tensor of shape %s on %s" % (dt, shape, self.device))
+        self._check_tensors("step_into", (actions, (n, _abi.NUM_MOTORS), t.float32), (obs_out, (n, _abi.OBS_DIM), t.float32),
+                            (reward_out, (n,), t.float32), (done_out, (n,), t.uint8))
         _lib.check(self.L.orr_step(self.h, actions.data_ptr(), obs_out.data_ptr(), reward_out.data_ptr(), done_out.data_ptr(), self._stream()), self.L)
         self._env_step_counter += 1
 
@@ -1078,9 +579,7 @@ class VecQuadrupedEnv(object):
         n = self.num_robot
         if out is None:
             out = t.empty((n, PRIV_DIM), dtype=t.float32, device=self.device)
-        for x, shape, dt in ((out, (n, PRIV_DIM), t.float32),) + (((done, (n,), t.uint8),) if done is not None else ()):
-            if x.dtype != dt or x.device != self.obs.device or not x.is_contiguous() or tuple(x.shape) != shape:
-                raise ValueError("privileged_obs: expected a contiguous %s tensor of shape %s on %s" % (dt, shape, self.device))
+        self._check_tensors("privileged_obs", (out, (n, PRIV_DIM), t.float32), *(((done, (n,), t.uint8),) if done is not None else ()))
         _lib.check(self.L.orr_privileged_obs(self.h, None if done is None else done.data_ptr(), out.data_ptr(), self._stream()), self.L)
         return out
 
@@ -1151,12 +650,17 @@ class VecQuadrupedEnv(object):
         """The clip each robot is playing (its CLIP_ID word): int32 [N] on the device."""
         return self.field_int("CLIP_ID")[:, 0].clone()
 
+    def _logged(self):
+        """(k, steps) of the episode log as it stands (syncs): the episodes logged since it was last cleared and the sum of their lengths."""
+        k = int(self.torch.clamp(self.counters[_abi.CNT_EPISODES], max=self.ep_log.shape[0]).item())
+        return k, float(self.ep_log[:k, 1].double().sum().item())
+
     def episode_returns_by_clip(self):
         """{clip id: (mean return, episodes)} of the episodes logged since the log was last cleared, without clearing it (syncs).
         Needs a clip set of more than one clip (see episode_log)."""
         if self.clip_log is None:
             raise ValueError("no clip log: no robot type of this env has a clip set of more than one clip")
-        k = int(self.torch.clamp(self.counters[_abi.CNT_EPISODES], max=self.ep_log.shape[0]).item())
+        k, _ = self._logged()
         ret = self.ep_log[:k, 0].double().cpu().numpy()
         cid = self.clip_log[:k].cpu().numpy()
         return {int(c): (float(ret[cid == c].mean()), int((cid == c).sum())) for c in np.unique(cid)}
@@ -1167,10 +671,9 @@ class VecQuadrupedEnv(object):
         log, like episode_returns_by_clip.  Needs reward_terms=True."""
         if self.term_log is None:
             raise ValueError("no term log: the env was built without reward_terms=True")
-        k = int(self.torch.clamp(self.counters[_abi.CNT_EPISODES], max=self.ep_log.shape[0]).item())
+        k, steps = self._logged()
         if k == 0:
             return {}
-        steps = float(self.ep_log[:k, 1].double().sum().item())
         sums = self.term_log[:k].double().sum(0).cpu().numpy()
         return {name: float(sums[i] / steps) for i, name in enumerate(self.TERM_NAMES)}
 
@@ -1180,10 +683,9 @@ class VecQuadrupedEnv(object):
         action_repeat x sim_dt)); {} when no episode is logged.  Read it before a gather clears the log.  Needs contact_outputs=True."""
         if self.contact_log is None:
             raise ValueError("no contact log: the env was built without contact_outputs=True")
-        k = int(self.torch.clamp(self.counters[_abi.CNT_EPISODES], max=self.ep_log.shape[0]).item())
+        k, steps = self._logged()
         if k == 0:
             return {}
-        steps = float(self.ep_log[:k, 1].double().sum().item())
         sums = self.contact_log[:k].double().sum(0).cpu().numpy().reshape(4, 2)
         return {"duty": [float(x / steps) for x in sums[:, 0]],
                 "normal_force": [float(x / (steps * self.cfg.action_repeat * self.cfg.sim_dt)) for x in sums[:, 1]]}
@@ -1195,10 +697,9 @@ class VecQuadrupedEnv(object):
         {} when no episode is logged.  Read it before a gather clears the log.  Needs actuator_outputs=True."""
         if self.actuator_log is None:
             raise ValueError("no actuator log: the env was built without actuator_outputs=True")
-        k = int(self.torch.clamp(self.counters[_abi.CNT_EPISODES], max=self.ep_log.shape[0]).item())
+        k, steps = self._logged()
         if k == 0:
             return {}
-        steps = float(self.ep_log[:k, 1].double().sum().item())
         rows = self.actuator_log[:k].double().cpu().numpy()
         return {"work_per_step": float(rows[:, 0].sum() / steps),
                 "torque_rms": float(np.sqrt(rows[:, 1].sum() / (steps * self.cfg.action_repeat * _abi.NUM_MOTORS))),
@@ -1260,17 +761,15 @@ class LegacyListEnv(object):
     def __init__(self, env, mutate_actions=True, torque_limits=None, actuator_outputs=False, observation_noise_stdev=None, push=None, push_outputs=False):
         if env.cfg.flags & _abi.FLAG_AUTO_RESET:
             raise ValueError("LegacyListEnv needs a VecQuadrupedEnv created with auto_reset=False")
-        if not isinstance(actuator_outputs, (bool, np.bool_)):
-            raise ValueError("actuator_outputs must be True or False, got %r" % (actuator_outputs,))
-        if torque_limits is not None:        # MotorModel's torque_limits / the actuator outputs, passed through to the env
+        _check_flags(actuator_outputs=actuator_outputs)
+        if torque_limits is not None:       # MotorModel's torque_limits / the actuator outputs, passed through to the env
             env.set_torque_limits(torque_limits)
         if actuator_outputs:
             env.bind_actuator_outputs(True)
         if observation_noise_stdev is not None:     # Minitaur._observation_noise_stdev, passed through to the env
             env.set_sensor_noise(observation_noise_stdev)
-        if not isinstance(push_outputs, (bool, np.bool_)):
-            raise ValueError("push_outputs must be True or False, got %r" % (push_outputs,))
-        if push is not None:                         # external pushes and their outputs, passed through to the env
+        _check_flags(push_outputs=push_outputs)      # where it always was: after the settings above have reached the env
+        if push is not None:                        # external pushes and their outputs, passed through to the env
             env.set_push(push)
         if push_outputs:
             env.bind_push_outputs(True)

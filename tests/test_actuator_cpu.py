@@ -85,12 +85,16 @@ def test_unit_tables_exports_and_refusal_texts(tmp_path_factory):
         assert text in device_h, text
     with open(_lib.SRC) as f:
         main = f.read()
-    for text in ("orr_set_torque_limits: null handle", "orr_set_torque_limits: robot_type out of range",
+    # the same refusal texts as ever, as the main unit now puts them together: the entry's own literals, and the setters' shared helpers
+    # (type_range, anchor_conflict, bind_three) with the entry's name and their one format string each.  What the calls return on a
+    # device: tests/test_gpu_setters_refused.py
+    for text in ("orr_set_torque_limits: null handle", 'type_range("orr_set_torque_limits", robot_type)', '"%s: robot_type out of range"',
                  "orr_set_torque_limits: limits_host[%d] must be a torque >= 0 or +inf (no limit)",
-                 "orr_set_torque_limits: friction anchors (orr_model::friction_anchor) and torque limits cannot be combined",
-                 "orr_bind_actuator_outputs: null handle", "orr_bind_actuator_outputs: act_dev needs act_ep_dev",
-                 "orr_bind_actuator_outputs: the actuator buffers (act_dev, act_ep_dev, act_log_dev) must be 16-byte aligned",
-                 "orr_bind_actuator_outputs: friction anchors (orr_model::friction_anchor) and actuator outputs cannot be combined"):
+                 'anchor_conflict(h, "orr_set_torque_limits", "torque limits")',
+                 '"%s: friction anchors (orr_model::friction_anchor) and %s cannot be combined"',
+                 'bind_three(h, "orr_bind_actuator_outputs", &DevTables::act_out, &orr_handle::act_on, act_dev, act_ep_dev, act_log_dev,',
+                 '"%s: null handle"', '"act_dev needs act_ep_dev (the totals of the current episode)"',
+                 '"the actuator buffers (act_dev, act_ep_dev, act_log_dev) must be 16-byte aligned (rows of 4 floats)", "actuator outputs");'):
         assert text in main, text
     # the actuator variant comes ahead of the contact outputs and the reward terms
     probe = variant_probe.lib(tmp_path_factory)

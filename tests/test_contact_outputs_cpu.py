@@ -78,8 +78,12 @@ def test_unit_tables_exports_and_refusal_texts(tmp_path_factory):
     assert re.search(r"constexpr int kModeTerms = 4;", device_h) and re.search(r"constexpr int kModeContacts = 8;", device_h)
     with open(_lib.SRC) as f:
         main = f.read()
-    for text in ("orr_bind_contact_outputs: null handle", "orr_bind_contact_outputs: contact_dev needs contact_ep_dev",
-                 "orr_bind_contact_outputs: friction anchors (orr_model::friction_anchor) and contact outputs cannot be combined"):
+    # the same refusal texts as ever, as the main unit now puts them together: bind_three with the entry's name and texts, and the
+    # shared format strings.  What the calls return on a device: tests/test_gpu_setters_refused.py
+    for text in ('bind_three(h, "orr_bind_contact_outputs", &DevTables::contact_out, &orr_handle::contacts_on, contact_dev, contact_ep_dev, contact_log_dev,',
+                 '"%s: null handle"', '"contact_dev needs contact_ep_dev (the totals of the current episode)"',
+                 '"the contact buffers must be 16-byte aligned (rows of 16 and 8 floats)", "contact outputs");',
+                 '"%s: friction anchors (orr_model::friction_anchor) and %s cannot be combined"'):
         assert text in main, text
     probe = variant_probe.lib(tmp_path_factory)
     for entry in ("orr_reset", "orr_step", "orr_debug_physics"):

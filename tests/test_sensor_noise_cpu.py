@@ -209,8 +209,11 @@ def test_unit_tables_exports_and_sizes(tmp_path_factory):
         assert "constexpr int kModeSensor = 32;" in f.read()
     with open(_lib.SRC) as f:
         main = f.read()
-    for text in ("orr_set_sensor_noise: null handle", "orr_set_sensor_noise: %s must be a finite standard deviation >= 0",
-                 "orr_set_sensor_noise: friction anchors (orr_model::friction_anchor) and sensor noise cannot be combined"):
+    # the same refusal texts as ever, as the main unit now puts them together: the setters' shared helpers (check_stds, anchor_conflict)
+    # with the entry's name and their one format string each.  What the calls return on a device: tests/test_gpu_setters_refused.py
+    for text in ("orr_set_sensor_noise: null handle", 'check_stds("orr_set_sensor_noise", stds)', '"%s: %s must be a finite standard deviation >= 0"',
+                 'anchor_conflict(h, "orr_set_sensor_noise", "sensor noise")',
+                 '"%s: friction anchors (orr_model::friction_anchor) and %s cannot be combined"'):
         assert text in main, text
     probe = variant_probe.lib(tmp_path_factory)
     for entry in ("orr_step", "orr_reset", "orr_debug_replay_step", "orr_debug_replay_reset"):
