@@ -255,6 +255,8 @@ int32_t orr_bind(orr_handle* h, void* state_dev, int64_t* counters_dev, float* e
  * n = 1 .. ORR_MAX_CLIPS ids, each loaded with orr_set_motion (repeats allowed).  At every reset of a robot of that type (orr_reset and
  * the auto-reset inside orr_step) its CLIP_ID becomes clip_ids[(m * n) >> 24], m = the 24-bit integer of draw 28 of the episode's
  * (seed, robot index, episode) stream (Philox block 7, word 0; draws 0..27 keep their meaning), before anything reads the clip.
+ * That is the uniform draw, which this call (re)installs for the type; orr_set_clip_weights and orr_clip_curriculum_update below
+ * replace it by a weighted one on the same m.
  * While some type's set has more than one clip, orr_step and orr_reset launch the multi-clip variants of the kernels (one wave per SIMD
  * at any batch size; refused together with friction anchors).  A type without a set keeps the record's CLIP_ID.  A rejected call
  * changes nothing. */
@@ -278,6 +280,47 @@ int32_t orr_bind_clip_log(orr_handle* h, int32_t* clip_log_dev);
  * Pose, velocity, target frames and termination of that step use the new clip at the new time.  The multi-clip kernel variants do
  * this (orr_set_clip_set); the parity replays (orr_debug_replay_step / _reset) run them while some type has a switch range. */
 int32_t orr_set_clip_switch(orr_handle* h, int32_t robot_type, float tmin, float tmax);
+
+/* weighted clip draws.  The draw of a clip (at a reset and at a mid-episode switch) goes by a table of 24-bit-scale thresholds per robot
+ * type in DEVICE memory, cum[0 .. n]: cum[0] = 0, cum[n] = 2^24, non-decreasing, and entry k of the set is drawn iff cum[k] <= m <
+ * cum[k + 1], m = the 24-bit integer of the same draw as before (draw 28 at a reset, 32 + 4 s at a switch; no draw moves).  The kernels
+ * read the table in memory, so new thresholds hold from the next launch on, in a replayed hipGraph as well, and select no kernel variant.
+ * orr_set_clip_set writes the UNIFORM thresholds cum[k] = (k * 2^24 + n - 1) / n (integer ceil), which pick exactly (m * n) >> 24.
+ * orr_set_clip_weights: n float32 weights in entry order (n = the set's size); cum[k] = ceil(2^24 * W_k / W) in double, W_k = the
+ * running sum of the weights, W their total.  A zero weight = the entry is never drawn; equal weights give the uniform thresholds
+ * exactly.  NULL restores the uniform thresholds.  Refused, changing nothing: a bad type, a type without a set, n != the set's size, a
+ * negative, NaN or infinite weight, all weights zero. */
+int32_t orr_set_clip_weights(orr_handle* h, int32_t robot_type, const float* weights_host, int32_t n);
+/* the thresholds of a type as the DEVICE holds them (the curriculum's kernel below writes them there) and the set's size; synchronises */
+int32_t orr_get_clip_thresholds(orr_handle* h, int32_t robot_type, uint32_t out_host[ORR_MAX_CLIPS + 1], int32_t* n);
+
+/* failure-adaptive clip sampling: one kernel turns the episode log into per-clip scores, a running score per clip id and new thresholds,
+ * without a host round trip.  The episode score of a logged episode of clip c is q = floor(65536 * clamp(x / ref[c], 0, 1) + 0.5), x
+ * the float32 metric of its log row (LENGTH: its length, RETURN: its return, STEP_REWARD: return / max(length, 1) in float32), the
+ * quotient in double. */
+#define ORR_CLIP_METRIC_LENGTH 0
+#define ORR_CLIP_METRIC_RETURN 1
+#define ORR_CLIP_METRIC_STEP_REWARD 2
+typedef struct orr_clip_curriculum {
+  float alpha;                 /* weight of an update's mean score in the running score, in (0, 1] */
+  float eps;                   /* share of the uniform distribution in the new probabilities, in [0, 1] */
+  int32_t metric;              /* ORR_CLIP_METRIC_* */
+  float ref[ORR_MAX_CLIPS];    /* per clip id: the metric's value that counts as mastered (score 1) */
+} orr_clip_curriculum;
+int32_t orr_sizeof_clip_curriculum(void);
+/* uploads the settings and zeroes the running scores.  Refused, changing nothing: alpha outside (0, 1], eps outside [0, 1], an unknown
+ * metric, a ref that is not finite and > 0 for a clip id that occurs in some type's set. */
+int32_t orr_set_clip_curriculum(orr_handle* h, const orr_clip_curriculum* cur_host);
+/* ONE launch on `stream`, asynchronous and capturable into a hipGraph.  Needs a bound episode log (orr_bind), a bound clip log
+ * (orr_bind_clip_log) and settings (orr_set_clip_curriculum): otherwise a negative code, and nothing is launched.  Reads the rows [0,
+ * min(counters[ORR_CNT_EPISODES], ep_log_capacity)) of both logs and clears NOTHING: call it once between two clears of the log
+ * (orr_episode_stats, or the owner of the counters, clears it).  Per clip id c (rows whose clip id lies outside [0, ORR_MAX_CLIPS) are
+ * ignored): n_c = its rows, S_c = the sum of their q as INTEGERS (the rows land in the log in no fixed order; integer sums make the
+ * result independent of it); if n_c > 0, ema_c = (1 - alpha) ema_c + alpha S_c / (65536 n_c) in double, else ema_c stays.  Then for
+ * every type whose set has n > 1 entries, entry k with clip id c_k: f_k = 1 - ema_{c_k}, F = their sum in entry order; F < 1e-12 gives the
+ * uniform thresholds, else p_k = (1 - eps) f_k / F + eps / n and the thresholds follow from p by orr_set_clip_weights' rule, in double.
+ * stats_dev: double [ORR_MAX_CLIPS][4] on the device = (n_c, S_c, S_c / (65536 n_c) or 0, ema_c after the update) per clip id, or NULL. */
+int32_t orr_clip_curriculum_update(orr_handle* h, double* stats_dev, void* stream);
 
 /* task noise of the handle (ImitationTask's perturb_init_state_prob with _apply_state_perturb, and tar_obs_noise[0]: imitation_task.py:
  * 192-197, 273-275, 778-793, 1195-1243).  A task option, not a robot-type one: one setting per handle, read from the next launch on. */

@@ -161,6 +161,17 @@ class OrrPush(C.Structure):
     _fields_ = [(n, C.c_float) for n in PUSH_FIELDS] + [("grace_steps", C.c_int32)]
 
 
+# include/openroborl_hip.h: ORR_CLIP_METRIC_* and orr_clip_curriculum (orr_set_clip_curriculum); a stats row of orr_clip_curriculum_update
+CLIP_METRICS = ("length", "return", "step_reward")       # the index is the ORR_CLIP_METRIC_* value
+CLIP_SCORE_ONE = 65536                                   # an episode's score is an integer in [0, CLIP_SCORE_ONE]
+CLIP_STATS_COLS = 4                                      # n_c, S_c, S_c / (65536 n_c) or 0, ema_c
+
+
+class OrrClipCurriculum(C.Structure):
+    """include/openroborl_hip.h: orr_clip_curriculum (orr_set_clip_curriculum)."""
+    _fields_ = [("alpha", C.c_float), ("eps", C.c_float), ("metric", C.c_int32), ("ref", C.c_float * MAX_CLIPS)]
+
+
 def fill(struct, name, values):
     """Assign a (nested) python sequence / scalar to a ctypes struct field."""
     import numpy as np

@@ -104,7 +104,7 @@ PRIV_UNITS = [("priv", SRC_PRIV, HIPCC_FLAGS_PLAIN, False)]
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
     "orr_layout_offset", "orr_layout_size", "orr_layout_is_int", "orr_sizeof_config", "orr_sizeof_model",
-    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_set_push", "orr_sizeof_push", "orr_bind_push_outputs", "orr_privileged_obs", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
+    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_clip_weights", "orr_get_clip_thresholds", "orr_sizeof_clip_curriculum", "orr_set_clip_curriculum", "orr_clip_curriculum_update", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_set_push", "orr_sizeof_push", "orr_bind_push_outputs", "orr_privileged_obs", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_history", "orr_policy_forward_history_priv", "orr_history_push", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_ppo_head_logstd", "orr_gauss_prepare", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_latent_backward", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
@@ -269,6 +269,15 @@ def load():
     L.orr_set_clip_set.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32]
     L.orr_set_clip_switch.restype = C.c_int32
     L.orr_set_clip_switch.argtypes = [vp, C.c_int32, C.c_float, C.c_float]
+    L.orr_set_clip_weights.restype = C.c_int32
+    L.orr_set_clip_weights.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.c_int32]
+    L.orr_get_clip_thresholds.restype = C.c_int32
+    L.orr_get_clip_thresholds.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+    L.orr_sizeof_clip_curriculum.restype = C.c_int32
+    L.orr_set_clip_curriculum.restype = C.c_int32
+    L.orr_set_clip_curriculum.argtypes = [vp, C.POINTER(_abi.OrrClipCurriculum)]
+    L.orr_clip_curriculum_update.restype = C.c_int32
+    L.orr_clip_curriculum_update.argtypes = [vp, vp, vp]
     L.orr_set_task_noise.restype = C.c_int32
     L.orr_set_task_noise.argtypes = [vp, C.POINTER(_abi.OrrTaskNoise)]
     L.orr_sizeof_task_noise.restype = C.c_int32
@@ -377,7 +386,7 @@ def load():
     if (L.orr_sizeof_config() != C.sizeof(_abi.OrrConfig) or L.orr_sizeof_model() != C.sizeof(_abi.OrrModel)
             or L.orr_sizeof_task_noise() != C.sizeof(_abi.OrrTaskNoise) or L.orr_sizeof_sensor_noise() != C.sizeof(_abi.OrrSensorNoise)
             or L.orr_sizeof_randomizer() != C.sizeof(_abi.OrrRandomizer) or L.orr_sizeof_push() != C.sizeof(_abi.OrrPush)
-            or L.orr_sizeof_update_ctl() != C.sizeof(_abi.OrrUpdateCtl)):
+            or L.orr_sizeof_update_ctl() != C.sizeof(_abi.OrrUpdateCtl) or L.orr_sizeof_clip_curriculum() != C.sizeof(_abi.OrrClipCurriculum)):
         raise RuntimeError("ctypes struct layout does not match include/openroborl_hip.h / openroborl_learner.h")
     _lib = L
     return L

@@ -140,6 +140,16 @@ struct DevTables {
   orr_push push;                                      // all zero = off
   float* push_out;                                    // [N][ORR_PUSH_ROW] dv, dw, kicked, kicks of the episode per robot, or NULL = not bound
   int push_table;                                     // != 0: the handle has a randomiser table or params buffer, so the push variant's auto-reset is the table-driven one; 0: the built-in literal ranges, as in the kernels below the randomiser variants
+  // weighted clip draws (orr_set_clip_set writes the uniform thresholds, orr_set_clip_weights others), read by the multi-clip variants
+  // only; the clip curriculum's kernel (orr_clip_curriculum_update) WRITES them, so the device's copy is the truth: past orr_create
+  // nothing copies the host's mirror of these two members over it.  APPENDED likewise
+  unsigned int clip_cum[ORR_MAX_ROBOT_TYPES][ORR_MAX_CLIPS + 1];   // 24-bit-scale thresholds: entry k is drawn iff cum[k] <= m < cum[k + 1]; cum[0] = 0, cum[n] = 2^24
+  struct ClipCurriculum {
+    float alpha, eps;                                 // orr_clip_curriculum's settings
+    int metric;
+    float ref[ORR_MAX_CLIPS];
+    double ema[ORR_MAX_CLIPS];                        // per clip id: the running score in [0, 1]; the kernel's own state
+  } cur;
 };
 // Flag bit of orr_step_kernel's MODE: the variant that also writes the reward terms.  MODE & 3 is the mode proper (0 env step, 1 debug
 // physics, 2 parity replay).  A bit of MODE rather than a template parameter of its own: the older variants keep their mangled names

@@ -600,14 +600,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
       if (set_n > 1 && sw_max < INFINITY) {
         // draws 32 + 4 s .. 34 + 4 s of the episode's stream (Philox block 8 + s, s = the env step counter before this step): the clip
         // (as reset_robot_state<true> draws it), the next change, the new time offset (_sample_time_offset, :1112-1123)
+        // The lane that holds the drawn entry writes CLIP_ID (clip_drawn: the thresholds' rule), and every lane reads it back
+        const ClipDraw cdraw = clip_draw_issue(P, type, lane);
         float u4[4];
         philox_block(c.seed, (uint32_t)geti(S, O(ROBOT_INDEX)), (uint32_t)geti(S, O(EPISODE_IDX)), 8u + (uint32_t)geti(S, O(EP_STEP)), u4);
         const uint32_t m = (uint32_t)(u4[0] * 16777216.0f);
-        const int k = (int)((m * (uint32_t)set_n) >> 24);
-        const int id = ((gip)&P.tab->clip_set[type][0])[k];
         clip_change = clip_change_time(t, sw_min, sw_max, u4[1]);
         WSYNC();
-        if (lane == 0) seti(S, O(CLIP_ID), id);
+        if (clip_drawn(cdraw, m, lane)) seti(S, O(CLIP_ID), cdraw.set_id);
+        WSYNC();
+        const int id = geti(S, O(CLIP_ID));
         const unsigned int* cg = reinterpret_cast<const unsigned int*>(&P.tab->clip[id]);
         unsigned int* cl = reinterpret_cast<unsigned int*>(&S.clip);
         if (lane < (int)(sizeof(DevClip) / 4)) cl[lane] = cg[lane];

@@ -10,7 +10,8 @@
 // physics, parity replay, reset) and launches all variants (which one: choose_variant, orr_variants.h); the two-wave, friction-anchor,
 // clip-set, task-noise, reward-terms, contact-output, actuator, sensor-noise, randomiser and push instantiations are compiled in units of
 // their own (orr_kernels_w2.hip, _anchor.hip, _multiclip.hip, _noise.hip, _terms.hip, _contacts.hip, _actuator.hip, _sensor.hip,
-// _randomizer.hip, _push.hip; why: orr_env_kernels.h), and so is the privileged observation (_priv.hip).
+// _randomizer.hip, _push.hip; why: orr_env_kernels.h), and so is the privileged observation (_priv.hip).  Two small kernels that read the
+// episode log live here as well: its pack for the rollout boundary (orr_episode_stats) and the clip curriculum (orr_clip_curriculum_update).
 #define ORR_TU_MAIN 1
 #include "orr_env_kernels.h"
 #include "orr_variants.h"
@@ -63,6 +64,84 @@ __global__ __launch_bounds__(1024) void orr_eplog_pack_kernel(long long* counter
   }
 }
 
+// The clip curriculum (orr_clip_curriculum_update, include/openroborl_hip.h): the episode log and the clip log as they stand -> per clip
+// id the number n_c of logged episodes and the INTEGER sum S_c of their 16-bit scores, the running score ema_c, and the thresholds of
+// every clip set of more than one clip (DevTables::clip_cum, what the multi-clip kernels draw by).  ONE launch of one workgroup; reads
+// the logs and clears nothing.  The rows land in the log in the order the waves of a step finish, so everything that depends on more
+// than one row is an integer sum: the result does not depend on the order of the rows.
+// Phase 1, all threads: a row's (1, q) goes into the bin [clip][lane of the wave] of LDS with two non-returning integer atomics - the
+// lanes of a wave hit 64 different words, so none of them serialises on an address.  Phase 2, 16 threads: one clip id each, its bins
+// summed in a fixed order and the EMA in double.  Phase 3, one thread per robot type: the type's thresholds from the EMAs, in double.
+__host__ __device__ __forceinline__ unsigned int uniform_threshold(int k, int n) {   // ceil(k 2^24 / n)
+  return (unsigned int)((((unsigned long long)k << 24) + (unsigned long long)(n - 1)) / (unsigned long long)n); }
+__global__ __launch_bounds__(1024) void orr_clip_curriculum_kernel(const long long* __restrict__ counters, const float* __restrict__ ep_log, int cap_log,
+                                                                   const int* __restrict__ clip_log, DevTables* tab, double* stats) {
+  __shared__ unsigned int bin_n[ORR_MAX_CLIPS][64];
+  __shared__ unsigned long long bin_s[ORR_MAX_CLIPS][64];
+  __shared__ double ema_s[ORR_MAX_CLIPS];
+  __shared__ double f_s[ORR_MAX_ROBOT_TYPES][ORR_MAX_CLIPS];    // phase 3's per-entry weights (LDS, not a thread's array: no scratch)
+  const int tid = threadIdx.x, slot = tid & 63;
+  bin_n[tid >> 6][slot] = 0u; bin_s[tid >> 6][slot] = 0ull;      // 1024 threads = 16 x 64 bins
+  const long long cnt_all = counters[ORR_CNT_EPISODES];
+  const long long cnt = cnt_all < (long long)cap_log ? cnt_all : (long long)cap_log;   // logged rows (cap_log <= 0: none)
+  const int metric = tab->cur.metric;
+  __syncthreads();
+  const float2* log2 = reinterpret_cast<const float2*>(ep_log);
+  for (long long i0 = tid; i0 < cnt; i0 += 4096) {   // four independent rows in flight per thread
+    float2 e[4];
+    int cid[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const long long i = i0 + 1024 * u;
+      e[u] = i < cnt ? log2[i] : make_float2(0.0f, 0.0f);
+      cid[u] = i < cnt ? clip_log[i] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      if ((unsigned int)cid[u] >= (unsigned int)ORR_MAX_CLIPS) continue;   // a clip id outside [0, 16): ignored (and the rows past cnt)
+      const float x = metric == ORR_CLIP_METRIC_RETURN ? e[u].x : (metric == ORR_CLIP_METRIC_LENGTH ? e[u].y : __fdiv_rn(e[u].x, fmaxf(e[u].y, 1.0f)));
+      const double r = fmin(fmax((double)x / (double)tab->cur.ref[cid[u]], 0.0), 1.0);   // NaN -> 0 (fmax returns its other argument)
+      const unsigned int q = (unsigned int)floor(65536.0 * r + 0.5);
+      atomicAdd(&bin_n[cid[u]][slot], 1u);
+      atomicAdd(&bin_s[cid[u]][slot], (unsigned long long)q);
+    }
+  }
+  __syncthreads();
+  if (tid < ORR_MAX_CLIPS) {
+    unsigned long long n = 0ull, s = 0ull;
+    for (int j = 0; j < 64; j++) { n += bin_n[tid][j]; s += bin_s[tid][j]; }
+    double ema = tab->cur.ema[tid];
+    const double mean = n ? (double)s / (65536.0 * (double)n) : 0.0, alpha = (double)tab->cur.alpha;
+    if (n) {
+      ema = (1.0 - alpha) * ema + alpha * mean;
+      tab->cur.ema[tid] = ema;
+    }
+    ema_s[tid] = ema;
+    if (stats) { stats[4 * tid] = (double)n; stats[4 * tid + 1] = (double)s; stats[4 * tid + 2] = mean; stats[4 * tid + 3] = ema; }
+  }
+  __syncthreads();
+  if (tid < ORR_MAX_ROBOT_TYPES) {
+    int n = tab->clip_set_n[tid];
+    n = n < ORR_MAX_CLIPS ? n : ORR_MAX_CLIPS;
+    if (n > 1) {
+      const double eps = (double)tab->cur.eps;
+      double* const f = f_s[tid];
+      double F = 0.0;
+      for (int k = 0; k < n; k++) { f[k] = 1.0 - ema_s[tab->clip_set[tid][k] & (ORR_MAX_CLIPS - 1)]; F += f[k]; }
+      unsigned int* cum = tab->clip_cum[tid];
+      if (F < 1e-12) {
+        for (int k = 0; k <= n; k++) cum[k] = uniform_threshold(k, n);
+      } else {
+        double P = 0.0;
+        for (int k = 0; k < n; k++) { f[k] = (1.0 - eps) * f[k] / F + eps / (double)n; P += f[k]; }
+        double Pk = 0.0;
+        cum[0] = 0u;
+        for (int k = 0; k < n; k++) { Pk += f[k]; cum[k + 1] = (unsigned int)ceil(16777216.0 * Pk / P); }
+      }
+    }
+  }
+}
+
 // Policy-free stress input of SURVEY.md section 8d (i): action = (reference joint pose one control step ahead, taken from the first
 // target frame of the observation, mapped joint -> motor space with the robot's own table) - INIT_MOTOR_ANGLES + noise, clipped to
 // the action space (imitation_runners.py:140-143).  One thread per (robot, motor), ONE launch whatever the mix of robot types: a
@@ -100,6 +179,7 @@ struct orr_handle {
   bool rand_bound;            // orr_bind_randomizer_params with a buffer: env step, parity replays and resets run the randomiser variants (orr_kernels_randomizer.hip)
   bool push_on;               // orr_set_push with prob > 0, or
   bool push_bound;            // orr_bind_push_outputs with a buffer: the env step runs the push variant (orr_kernels_push.hip); every other entry point launches what it launches without
+  bool curriculum_on;         // orr_set_clip_curriculum gave settings: orr_clip_curriculum_update may launch (it selects no variant)
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -164,6 +244,10 @@ __attribute__((format(printf, 1, 2))) static int refuse(const char* fmt, ...) { 
 }
 static int type_range(const char* entry, int32_t t) {
   return t < 0 || t >= ORR_MAX_ROBOT_TYPES ? refuse("%s: robot_type out of range", entry) : 0;
+}
+// the uniform thresholds of an n-entry clip set, in integer arithmetic; the entries past n are zero
+static void uniform_thresholds(int n, unsigned int cum[ORR_MAX_CLIPS + 1]) {
+  for (int k = 0; k <= ORR_MAX_CLIPS; k++) cum[k] = k <= n ? uniform_threshold(k, n) : 0u;
 }
 static void set_bit(uint32_t& mask, int t, bool on) { mask = on ? mask | 1u << t : mask & ~(1u << t); }
 // the features that have no friction-anchor form of the kernels: refused while some robot type has orr_model::friction_anchor
@@ -407,12 +491,89 @@ int32_t orr_set_clip_set(orr_handle* h, int32_t robot_type, const int32_t* clip_
     if (!h->tab_host.clip[id].frames) return fail(-1, "orr_set_clip_set: clip id was not loaded with orr_set_motion");
     ids[i] = id;
   }
+  // a new set draws uniformly: thresholds ceil(k 2^24 / n), which pick (m n) >> 24 for every m
+  unsigned int cum[ORR_MAX_CLIPS + 1];
+  uniform_thresholds(n, cum);
   // the device copy first: a failed copy leaves the host table and the variant choice as they were
+  HIPCHK(hipMemcpy(&h->tab_dev->clip_cum[robot_type][0], cum, sizeof(cum), hipMemcpyHostToDevice), "orr_set_clip_set: hipMemcpy");
   HIPCHK(hipMemcpy(&h->tab_dev->clip_set[robot_type][0], ids, sizeof(ids), hipMemcpyHostToDevice), "orr_set_clip_set: hipMemcpy");
   HIPCHK(hipMemcpy(&h->tab_dev->clip_set_n[robot_type], &n, sizeof(int), hipMemcpyHostToDevice), "orr_set_clip_set: hipMemcpy");
   memcpy(h->tab_host.clip_set[robot_type], ids, sizeof(ids));
   h->tab_host.clip_set_n[robot_type] = n;
   set_bit(h->multiclip_types, robot_type, n > 1);
+  return 0;
+}
+
+// thresholds -> the device table only: the host's mirror of clip_cum is never read (the curriculum's kernel writes the device's copy)
+static int put_thresholds(orr_handle* h, const char* entry, int robot_type, const unsigned int* cum) {
+  const hipError_t e = hipMemcpy(&h->tab_dev->clip_cum[robot_type][0], cum, (ORR_MAX_CLIPS + 1) * sizeof(unsigned int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) return 0;
+  char m[96];
+  snprintf(m, sizeof(m), "%s: hipMemcpy", entry);
+  return fail(-2, m, e);
+}
+
+int32_t orr_set_clip_weights(orr_handle* h, int32_t robot_type, const float* weights_host, int32_t n) {
+  if (!h) return fail(-1, "orr_set_clip_weights: null handle");
+  if (type_range("orr_set_clip_weights", robot_type)) return -1;
+  const int set_n = h->tab_host.clip_set_n[robot_type];
+  if (set_n < 1) return fail(-1, "orr_set_clip_weights: the robot type has no clip set (orr_set_clip_set)");
+  if (n != set_n) return refuse("orr_set_clip_weights: %d weights for a clip set of %d entries", n, set_n);
+  unsigned int cum[ORR_MAX_CLIPS + 1];
+  uniform_thresholds(set_n, cum);
+  if (weights_host) {
+    double W = 0.0;
+    for (int k = 0; k < n; k++) {
+      if (!(weights_host[k] >= 0.0f && weights_host[k] < INFINITY)) return refuse("orr_set_clip_weights: weights_host[%d] must be a finite number >= 0", k);   // NaN fails the comparison
+      W += (double)weights_host[k];
+    }
+    if (!(W > 0.0)) return fail(-1, "orr_set_clip_weights: all weights are zero");
+    double Wk = 0.0;
+    for (int k = 0; k < n; k++) { Wk += (double)weights_host[k]; cum[k + 1] = (unsigned int)ceil(16777216.0 * Wk / W); }
+  }
+  return put_thresholds(h, "orr_set_clip_weights", robot_type, cum);
+}
+
+int32_t orr_get_clip_thresholds(orr_handle* h, int32_t robot_type, uint32_t out_host[ORR_MAX_CLIPS + 1], int32_t* n) {
+  if (!h || !out_host || !n) return fail(-1, "orr_get_clip_thresholds: null argument");
+  if (type_range("orr_get_clip_thresholds", robot_type)) return -1;
+  HIPCHK(hipDeviceSynchronize(), "orr_get_clip_thresholds: sync");     // the curriculum's kernel may still be writing them
+  HIPCHK(hipMemcpy(out_host, &h->tab_dev->clip_cum[robot_type][0], (ORR_MAX_CLIPS + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost), "orr_get_clip_thresholds: hipMemcpy");
+  *n = h->tab_host.clip_set_n[robot_type];
+  return 0;
+}
+
+int32_t orr_sizeof_clip_curriculum(void) { return (int32_t)sizeof(orr_clip_curriculum); }
+
+int32_t orr_set_clip_curriculum(orr_handle* h, const orr_clip_curriculum* cur_host) {
+  if (!h || !cur_host) return fail(-1, "orr_set_clip_curriculum: null argument");
+  const orr_clip_curriculum& c = *cur_host;
+  if (!(c.alpha > 0.0f && c.alpha <= 1.0f)) return fail(-1, "orr_set_clip_curriculum: alpha must lie in (0, 1]");     // NaN fails the comparisons
+  if (!(c.eps >= 0.0f && c.eps <= 1.0f)) return fail(-1, "orr_set_clip_curriculum: eps must lie in [0, 1]");
+  if (c.metric != ORR_CLIP_METRIC_LENGTH && c.metric != ORR_CLIP_METRIC_RETURN && c.metric != ORR_CLIP_METRIC_STEP_REWARD)
+    return fail(-1, "orr_set_clip_curriculum: unknown metric");
+  for (int t = 0; t < ORR_MAX_ROBOT_TYPES; t++)
+    for (int k = 0; k < h->tab_host.clip_set_n[t]; k++) {
+      const int id = h->tab_host.clip_set[t][k];
+      if (!(c.ref[id] > 0.0f && c.ref[id] < INFINITY)) return refuse("orr_set_clip_curriculum: ref[%d] must be finite and > 0 (the clip is in a clip set)", id);
+    }
+  DevTables::ClipCurriculum d;
+  memset(&d, 0, sizeof(d));      // the EMAs start at zero
+  d.alpha = c.alpha; d.eps = c.eps; d.metric = c.metric;
+  memcpy(d.ref, c.ref, sizeof(d.ref));
+  if (const int r = upload(h, "orr_set_clip_curriculum", &h->tab_host.cur, &d, sizeof(d))) return r;
+  h->curriculum_on = true;
+  return 0;
+}
+
+int32_t orr_clip_curriculum_update(orr_handle* h, double* stats_dev, void* stream) {
+  if (!h) return fail(-1, "orr_clip_curriculum_update: null handle");
+  if (!h->counters || !h->ep_log) return fail(-1, "orr_clip_curriculum_update: needs a bound episode log (orr_bind)");
+  if (!h->tab_host.clip_log) return fail(-1, "orr_clip_curriculum_update: needs a bound clip log (orr_bind_clip_log)");
+  if (!h->curriculum_on) return fail(-1, "orr_clip_curriculum_update: needs settings (orr_set_clip_curriculum)");
+  hipLaunchKernelGGL(orr_clip_curriculum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, h->counters, h->ep_log, h->ep_log_cap, h->tab_host.clip_log,
+                     h->tab_dev, stats_dev);
+  HIPCHK(hipGetLastError(), "orr_clip_curriculum_update: launch");
   return 0;
 }
 

@@ -507,13 +507,35 @@ __device__ static void sensors_push_noisy(Shared& S, int lane, bool fill_all, co
   WSYNC();
 }
 
+// The clip draw of the CLIPS variants, at a reset (draw 28) and at a mid-episode switch (draw 32 + 4 s): lane l of the robot holds entry
+// l of its type's clip set and the entry's interval [cum[l], cum[l + 1]) of the 24-bit thresholds (DevTables::clip_cum), and the entry
+// whose interval holds m, the draw's 24-bit integer, is the one drawn.  clip_draw_issue starts the loads (global_load: nothing waits
+// for them until clip_drawn reads them).  The uniform thresholds ceil(k 2^24 / n) that orr_set_clip_set writes pick (m n) >> 24.
+struct ClipDraw {
+  int set_id = 0, set_n = 0;
+  uint32_t lo = 0, hi = 0;
+};
+__device__ __forceinline__ ClipDraw clip_draw_issue(const KParams& P, int type, int lane) {
+  static_assert(ORR_MAX_CLIPS == kLanes, "one clip-set entry per lane");
+  typedef const int __attribute__((address_space(1)))* gip;
+  typedef const unsigned int __attribute__((address_space(1)))* gup;
+  ClipDraw d;
+  d.set_id = ((gip)&P.tab->clip_set[type][0])[lane];
+  d.set_n = ((gip)&P.tab->clip_set_n[0])[type];
+  d.lo = ((gup)&P.tab->clip_cum[type][0])[lane];
+  d.hi = ((gup)&P.tab->clip_cum[type][0])[lane + 1];
+  return d;
+}
+// -> this lane's entry is the one drawn (one lane of the robot at most; none for a type without a set: it keeps its CLIP_ID)
+__device__ __forceinline__ bool clip_drawn(const ClipDraw& d, uint32_t m, int lane) { return lane < d.set_n && d.lo <= m && m < d.hi; }
+
 // ================================================================================================
 // reset of one robot (wrapper_env.py:87-107 -> quadruped_gym_env.py:63-104 -> minitaur.py:232-278 ->
 // imitation_task.py:166-199); SURVEY.md Appendix A.2.
 // ================================================================================================
 // uni_replay (parity replay only, else NULL): 28 draws in [0, 1) that replace the Philox stream
 // CLIPS (the multi-clip variants, orr_kernels_multiclip.hip): the episode's clip is drawn from the robot type's clip set (DevTables::clip_set)
-// with draw 28 (Philox block 7, word 0) before anything reads the clip, and CLIP_ID / S.clip hold it from then on; the record's
+// by the type's thresholds (DevTables::clip_cum; clip_draw_issue / clip_drawn above) with draw 28 (Philox block 7, word 0) before anything reads the clip, and CLIP_ID / S.clip hold it from then on; the record's
 // CLIP_CHANGE_TIME (behind the ring, in memory: store_reset_extras) gets the episode's first clip change, draw 29 (orr_set_clip_switch)
 // RC: the lane's cold-table constants (load_reset_const; the step kernel issues those loads right past its sub-steps)
 // NOISE (the noise variants, orr_kernels_noise.hip; always with CLIPS): perturb_init_state_prob / _apply_state_perturb of the reference
@@ -550,15 +572,12 @@ __device__ static uint32_t reset_robot_state(const KParams& P, Shared& S, int la
   // block b once and parks its four numbers in LDS
   float* draws = S.ph.end.red + 24;    // 28 words (CLIPS: 32, block 7 in red[52..55], free until ring entry #2 takes red[56..75])
   static_assert(kLanes == 16, "reset_robot_state / the pose sampler assume 16 lanes per robot");
-  int set_id = 0, set_n = 0;
+  ClipDraw cdraw;
   float sw_min = 0.0f, sw_max = 0.0f;
-  if constexpr (CLIPS) {   // the type's clip set, one id per lane, and switch interval, in flight while the Philox blocks are evaluated
-    static_assert(ORR_MAX_CLIPS == kLanes, "one clip-set entry per lane");
-    typedef const int __attribute__((address_space(1)))* gip;
+  if constexpr (CLIPS) {   // the type's clip set, one id and one threshold interval per lane, and switch interval, in flight while the Philox blocks are evaluated
     typedef const float __attribute__((address_space(1)))* gfp;
     const int type = geti(S, O(ROBOT_TYPE));
-    set_id = ((gip)&P.tab->clip_set[type][0])[lane];
-    set_n = ((gip)&P.tab->clip_set_n[0])[type];
+    cdraw = clip_draw_issue(P, type, lane);
     sw_min = ((gfp)&P.tab->clip_switch[type][0])[0];
     sw_max = ((gfp)&P.tab->clip_switch[type][0])[1];
   }
@@ -607,12 +626,12 @@ __device__ static uint32_t reset_robot_state(const KParams& P, Shared& S, int la
   WSYNC();
   float u_change = 0.0f;   // CLIPS: draw 29, the first clip change (red[] is reused before it is needed)
   if constexpr (CLIPS) {
-    // draw 28 -> k = (m n) >> 24, m = its 24-bit integer (u = m / 2^24 exactly): integer arithmetic, uniform over the n entries.  The lane
-    // that holds set[k] writes CLIP_ID; then the clip header is staged again, one word per lane (as load_robot does)
+    // draw 28 -> the entry k with cum[k] <= m < cum[k + 1], m = its 24-bit integer (u = m / 2^24 exactly): integer arithmetic; with the
+    // uniform thresholds k = (m n) >> 24.  The lane that holds set[k] writes CLIP_ID; then the clip header is staged again, one word per
+    // lane (as load_robot does)
     u_change = draws[29];
     const uint32_t m = (uint32_t)(draws[28] * 16777216.0f);
-    const int k = (int)((m * (uint32_t)set_n) >> 24);
-    if (set_n > 0 && lane == k) seti(S, O(CLIP_ID), set_id);
+    if (clip_drawn(cdraw, m, lane)) seti(S, O(CLIP_ID), cdraw.set_id);
     WSYNC();
     const unsigned int* cg = reinterpret_cast<const unsigned int*>(&P.tab->clip[geti(S, O(CLIP_ID))]);
     unsigned int* cl = reinterpret_cast<unsigned int*>(&S.clip);

@@ -19,7 +19,7 @@ import math
 
 import numpy as np
 
-from . import _abi, _lib, config as cfgmod, motion, robots, state as statemod
+from . import _abi, _lib, config as cfgmod, env_draws, env_spec, motion, robots, state as statemod
 from .env_draws import (CLIP_CHANGE_DRAW, CLIP_DRAW, NOISE_HEADING_BLOCK, NOISE_RESET_BLOCK, PRIV_DIM, PRIV_FIELDS, RAND_LEG_WORD,  # noqa: F401
                         RAND_ROW_WORDS, SENSOR_NOISE_BLOCK, SENSOR_SLOT_FILTER, SENSOR_SLOT_HIST, SENSOR_SLOT_TARGET, clip_change_time,
                         clip_draw_index, clip_switch_draws, init_perturb_draw_indices, init_perturb_draws, normal_pair, push_block, push_kick,
@@ -99,7 +99,8 @@ class VecQuadrupedEnv(object):
                  robot_index_offset=0, legacy_grid=False, mixed_robots=None, ep_log_capacity=65536, config_overrides=None,
                  model_overrides=None, clip_time_min=None, clip_time_max=None, perturb_init_state_prob=None, tar_obs_noise=None,
                  init_perturb_std=None, reward_terms=False, contact_outputs=False, torque_limits=None, actuator_outputs=False,
-                 observation_noise_stdev=None, randomizer_config=None, randomizer_params=False, push=None, push_outputs=False):
+                 observation_noise_stdev=None, randomizer_config=None, randomizer_params=False, push=None, push_outputs=False,
+                 clip_weights=None, clip_curriculum=None):
         import torch
         _check_flags(push_outputs=push_outputs, randomizer_params=randomizer_params, reward_terms=reward_terms,
                      contact_outputs=contact_outputs, actuator_outputs=actuator_outputs)
@@ -172,6 +173,12 @@ class VecQuadrupedEnv(object):
         clip_time_min = clip_time_min if clip_time_min is not None else params.get("clip_time_min")
         clip_time_max = clip_time_max if clip_time_max is not None else params.get("clip_time_max")
         self.clip_switch = clip_switch_spec(clip_time_min, clip_time_max, sorted(set(self.robot_names)))
+        # weighted clip draws (orr_set_clip_weights; the task YAML may carry clip_weights) and the failure-adaptive clip curriculum
+        # (orr_set_clip_curriculum): uniform draws and no curriculum by default.  Validated here, ahead of anything that needs the device
+        if clip_weights is None:
+            clip_weights = params.get("clip_weights")
+        self.clip_weights = env_spec.clip_weights_spec(clip_weights, self.clip_sets)
+        self.clip_curriculum = env_spec.clip_curriculum_spec(clip_curriculum, self.clip_sets, default_ref=float(self.cfg.ep_len_end))
         # task noise (ImitationTask's perturb_init_state_prob / tar_obs_noise; the task YAML may carry the same keys): off by default, as in
         # the reference.  Validated here, ahead of anything that needs the device
         if perturb_init_state_prob is None:
@@ -275,6 +282,12 @@ class VecQuadrupedEnv(object):
             self.set_randomizer(randomizer_config)
         if randomizer_params:
             self.bind_randomizer_params(True)
+        # the clip curriculum's stats of the last clip_curriculum_update ([MAX_CLIPS, 4] float64 on the device): None until it is set
+        self.clip_stats = None
+        if any(w is not None for w in self.clip_weights.values()):
+            self.set_clip_weights(clip_weights)
+        if self.clip_curriculum is not None:
+            self.set_clip_curriculum(clip_curriculum)
         # what the pushes did to each robot (orr_bind_push_outputs): None while unbound
         self.push_out = None
         if push_on(self.push):
@@ -347,6 +360,52 @@ class VecQuadrupedEnv(object):
         _lib.check(self.L.orr_set_sensor_noise(self.h, C.byref(spec)), self.L)
         self.sensor_noise = spec
         self.launch_params_generation += 1
+
+    def set_clip_weights(self, clip_weights=None):
+        """Change the weights of the clip draws of a running env (orr_set_clip_weights; see env_spec.clip_weights_spec: None = uniform, a
+        list of one weight per clip of the set, or a dict by robot name): every reset and every mid-episode switch from the next launch on
+        draws entry k with probability w_k / sum w (to 2^-24).  The kernels read the thresholds in device memory: no kernel variant
+        changes, launch_params_generation does not move and captured graphs stay valid."""
+        spec = env_spec.clip_weights_spec(clip_weights, self.clip_sets)
+        for name, w in spec.items():
+            arr = None if w is None else (C.c_float * len(w))(*[float(x) for x in w])
+            _lib.check(self.L.orr_set_clip_weights(self.h, robots.ROBOT_TYPE_ID[name], arr, len(self.clip_sets[name])), self.L)
+        self.clip_weights = spec
+
+    def clip_thresholds(self):
+        """{robot name: int64 [n + 1]}: the 24-bit thresholds each type's clip draws go by, as the DEVICE holds them (set_clip_weights or
+        the last clip_curriculum_update wrote them); env_draws.clip_draw_weighted predicts the draws from them.  Syncs."""
+        out = {}
+        for name, ids in self.clip_sets.items():
+            buf, n = (C.c_uint32 * (_abi.MAX_CLIPS + 1))(), C.c_int32()
+            _lib.check(self.L.orr_get_clip_thresholds(self.h, robots.ROBOT_TYPE_ID[name], buf, C.byref(n)), self.L)
+            out[name] = np.array(buf[:n.value + 1], dtype=np.int64)
+        return out
+
+    def clip_probabilities(self):
+        """{robot name: float64 [n]}: the probability of each entry of the type's clip set under clip_thresholds().  Syncs."""
+        return {name: np.diff(cum) / float(1 << 24) for name, cum in self.clip_thresholds().items()}
+
+    def set_clip_curriculum(self, clip_curriculum):
+        """Give the failure-adaptive clip curriculum its settings (orr_set_clip_curriculum; see env_spec.clip_curriculum_spec) and zero
+        its running scores; clip_curriculum_update then moves the thresholds.  Like set_clip_weights it changes no kernel variant."""
+        spec = env_spec.clip_curriculum_spec(clip_curriculum, self.clip_sets, default_ref=float(self.cfg.ep_len_end))
+        if spec is None:
+            raise ValueError("set_clip_curriculum needs settings; to stop adapting, stop calling clip_curriculum_update (set_clip_weights(None) restores uniform draws)")
+        _lib.check(self.L.orr_set_clip_curriculum(self.h, C.byref(spec)), self.L)
+        self.clip_curriculum = spec
+        if self.clip_stats is None:
+            self.clip_stats = self.torch.zeros((_abi.MAX_CLIPS, _abi.CLIP_STATS_COLS), dtype=self.torch.float64, device=self.device)
+
+    def clip_curriculum_update(self):
+        """One launch (orr_clip_curriculum_update), no host sync: the episode log and the clip log as they stand -> per-clip scores, the
+        running scores and new thresholds for every clip set of more than one clip.  It clears nothing: call it once between two clears
+        of the log (episode_log*, dist.gather_env_episodes).  Returns env.clip_stats, float64 [MAX_CLIPS, 4] on the device, a clip id's
+        row = (episodes, integer score sum, mean score, running score); the next call overwrites it.  Capturable into a hipGraph
+        (run it once eagerly first: the first launch loads the code object).  Needs a clip set of more than one clip (the clip log) and
+        set_clip_curriculum: RuntimeError otherwise."""
+        _lib.check(self.L.orr_clip_curriculum_update(self.h, None if self.clip_stats is None else self.clip_stats.data_ptr(), self._stream()), self.L)
+        return self.clip_stats
 
     def set_randomizer(self, config=None):
         """Change the randomiser's table of a running env (orr_set_randomizer; see randomizer_spec for `config`): read by every reset
@@ -758,7 +817,8 @@ class LegacyListEnv(object):
     INIT_MOTOR_ANGLES added in place (minitaur.py:281).
     """
 
-    def __init__(self, env, mutate_actions=True, torque_limits=None, actuator_outputs=False, observation_noise_stdev=None, push=None, push_outputs=False):
+    def __init__(self, env, mutate_actions=True, torque_limits=None, actuator_outputs=False, observation_noise_stdev=None, push=None, push_outputs=False,
+                 clip_weights=None, clip_curriculum=None):
         if env.cfg.flags & _abi.FLAG_AUTO_RESET:
             raise ValueError("LegacyListEnv needs a VecQuadrupedEnv created with auto_reset=False")
         _check_flags(actuator_outputs=actuator_outputs)
@@ -773,6 +833,10 @@ class LegacyListEnv(object):
             env.set_push(push)
         if push_outputs:
             env.bind_push_outputs(True)
+        if clip_weights is not None:                # weighted clip draws and the clip curriculum, passed through to the env
+            env.set_clip_weights(clip_weights)
+        if clip_curriculum is not None:
+            env.set_clip_curriculum(clip_curriculum)
         self._env = env
         self._mutate = mutate_actions
         self.num_robot = env.num_robot

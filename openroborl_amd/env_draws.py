@@ -17,6 +17,88 @@ def clip_draw_index(m, n):
     return (np.asarray(m, dtype=np.int64) * int(n)) >> 24
 
 
+def clip_thresholds_uniform(n):
+    """The thresholds orr_set_clip_set writes for an n-entry set: cum[k] = ceil(k 2^24 / n) in integer arithmetic, k = 0..n (int64 [n +
+    1]).  They pick clip_draw_index(m, n) for every m."""
+    n = int(n)
+    if not 1 <= n <= _abi.MAX_CLIPS:
+        raise ValueError("a clip set holds 1 .. %d clips" % _abi.MAX_CLIPS)
+    return np.array([((k << 24) + n - 1) // n for k in range(n + 1)], dtype=np.int64)
+
+
+def clip_thresholds(weights):
+    """The thresholds orr_set_clip_weights writes (None: the uniform ones cannot be told without the set's size, so weights are
+    required): cum[k] = ceil(2^24 W_k / W) in float64, W_k the running sum of the float32 weights in entry order, W their total.
+    int64 [n + 1]; a zero weight gives an empty interval, equal weights the uniform thresholds."""
+    w = np.asarray(weights, dtype=np.float32).astype(np.float64).reshape(-1)
+    if not 1 <= len(w) <= _abi.MAX_CLIPS:
+        raise ValueError("a clip set holds 1 .. %d clips" % _abi.MAX_CLIPS)
+    if not (np.isfinite(w).all() and (w >= 0.0).all()):
+        raise ValueError("clip weights must be finite numbers >= 0")
+    run, total = 0.0, 0.0
+    for x in w:
+        total += float(x)
+    if not total > 0.0:
+        raise ValueError("all clip weights are zero")
+    cum = [0]
+    for x in w:
+        run += float(x)
+        cum.append(int(math.ceil(16777216.0 * run / total)))
+    return np.array(cum, dtype=np.int64)
+
+
+def clip_draw_weighted(m, thresholds):
+    """The entry a draw's 24-bit integer m picks under the thresholds cum[0..n]: the k with cum[k] <= m < cum[k + 1] (csrc/orr_task.h,
+    clip_drawn).  Works on numpy integer arrays."""
+    cum = np.asarray(thresholds, dtype=np.int64)
+    return np.searchsorted(cum[1:], np.asarray(m, dtype=np.int64), side="right")
+
+
+def clip_episode_score(x, ref):
+    """An episode's 16-bit score (orr_clip_curriculum_update): floor(65536 clamp(x / ref, 0, 1) + 0.5) with the float32 metric x and the
+    float32 ref widened to float64; a NaN quotient scores 0.  int64; works on arrays."""
+    x = np.asarray(x, dtype=np.float32).astype(np.float64)
+    ref = np.asarray(ref, dtype=np.float32).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.fmin(np.fmax(x / ref, 0.0), 1.0)
+    return np.floor(65536.0 * r + 0.5).astype(np.int64)
+
+
+def clip_curriculum_step(ema, n, S, sets, alpha, eps):
+    """One orr_clip_curriculum_update in float64 from the per-clip-id counts n[c] and integer score sums S[c]: ema_c <- (1 - alpha) ema_c +
+    alpha S_c / (65536 n_c) where n_c > 0; then for every set of more than one entry (sets: {type: list of clip ids}) f_k = 1 -
+    ema[c_k], F = their sum in entry order, uniform thresholds if F < 1e-12, else p_k = (1 - eps) f_k / F + eps / len and
+    clip_thresholds' rule on p.  alpha and eps as the device holds them (float32).  -> (ema' float64 [MAX_CLIPS], {type: int64
+    thresholds}); sets of one entry are left out."""
+    alpha, eps = float(np.float32(alpha)), float(np.float32(eps))
+    ema = np.array(ema, dtype=np.float64).reshape(_abi.MAX_CLIPS).copy()
+    for c in range(_abi.MAX_CLIPS):
+        if int(n[c]) > 0:
+            ema[c] = (1.0 - alpha) * ema[c] + alpha * (float(int(S[c])) / (65536.0 * float(int(n[c]))))
+    out = {}
+    for t, ids in sets.items():
+        k = len(ids)
+        if k < 2:
+            continue
+        f = [1.0 - ema[c] for c in ids]
+        F = 0.0
+        for x in f:
+            F += x
+        if F < 1e-12:
+            out[t] = clip_thresholds_uniform(k)
+            continue
+        p = [(1.0 - eps) * x / F + eps / float(k) for x in f]
+        run, total = 0.0, 0.0
+        for x in p:
+            total += x
+        cum = [0]
+        for x in p:
+            run += x
+            cum.append(int(math.ceil(16777216.0 * run / total)))
+        out[t] = np.array(cum, dtype=np.int64)
+    return ema, out
+
+
 CLIP_CHANGE_DRAW = 29   # the first clip change of an episode: draw 29 of the reset's stream (block 7, word 1)
 
 

@@ -86,6 +86,92 @@ def clip_switch_spec(clip_time_min, clip_time_max, robot_names):
     return out
 
 
+def clip_weights_spec(clip_weights, clip_sets):
+    """clip_weights (None = uniform; a list of one weight per entry of the clip set; or a dict by robot name of either, for mixed
+    batches) -> {robot name: None or float32 [n]} for the robots of clip_sets ({robot name: clip ids}, motion_spec's).  ValueError on
+    anything the C-ABI (orr_set_clip_weights) would refuse: a wrong length, a negative, NaN or infinite weight, all weights zero."""
+    def one(v, name):
+        if v is None:
+            return None
+        if isinstance(v, (bool, np.bool_, str, dict)) or np.ndim(v) != 1:
+            raise ValueError("clip_weights of %s must be None or a list of one weight per clip, not %r" % (name, v))
+        for x in v:
+            _number(x, "clip_weights of %s must be numbers, not %r", name, v)
+        a = np.asarray(v, dtype=np.float32)
+        if len(a) != len(clip_sets[name]):
+            raise ValueError("clip_weights of %s: %d weights for a clip set of %d clips" % (name, len(a), len(clip_sets[name])))
+        if not (np.isfinite(a).all() and (a >= 0).all()):
+            raise ValueError("clip_weights of %s must be finite numbers >= 0, got %r" % (name, v))
+        if not float(a.astype(np.float64).sum()) > 0.0:
+            raise ValueError("clip_weights of %s: all weights are zero" % name)
+        return a
+    names = sorted(clip_sets)
+    return {name: one(_for_robot(clip_weights, name, names, "clip_weights"), name) for name in names}
+
+
+def clip_curriculum_spec(clip_curriculum, clip_sets, default_ref=None):
+    """clip_curriculum -> the orr_clip_curriculum struct, or None for None.  A list (alpha, eps) or (alpha, eps, metric), or a dict with
+    `alpha` (weight of an update's mean score in the running score, in (0, 1]), `eps` (share of the uniform distribution, in [0, 1]),
+    `metric` ("length", the default, "return" or "step_reward") and `ref`: the metric's value that counts as mastered - a number for
+    every clip, a list by clip id, or a dict by robot name of a number or a list by entry of that robot's clip set, for mixed batches.
+    default_ref: the episode length that stands for ref when none is given (the env passes the task's final episode step limit) -
+    "length" and "return" (one reward unit per step) take it, "step_reward" takes 1.  ValueError on anything the C-ABI (orr_set_clip_curriculum) would refuse."""
+    if clip_curriculum is None:
+        return None
+    if isinstance(clip_curriculum, dict):
+        unknown = set(clip_curriculum) - {"alpha", "eps", "metric", "ref"}
+        if unknown:
+            raise ValueError("clip_curriculum: unknown keys %s (known: alpha, eps, metric, ref)" % sorted(unknown))
+        if "alpha" not in clip_curriculum or "eps" not in clip_curriculum:
+            raise ValueError("clip_curriculum needs alpha and eps")
+        cur = dict(clip_curriculum)
+    elif isinstance(clip_curriculum, (list, tuple)) and len(clip_curriculum) in (2, 3):
+        cur = dict(zip(("alpha", "eps", "metric"), clip_curriculum))
+    else:
+        raise ValueError("clip_curriculum must be None, (alpha, eps[, metric]) or a dict with alpha, eps, metric, ref, not %r" % (clip_curriculum,))
+    alpha = _number(cur["alpha"], "clip_curriculum: alpha must be a number, not %r", cur["alpha"])
+    eps = _number(cur["eps"], "clip_curriculum: eps must be a number, not %r", cur["eps"])
+    if not (0.0 < alpha <= 1.0):
+        raise ValueError("clip_curriculum: alpha must lie in (0, 1], not %r" % (alpha,))
+    if not (0.0 <= eps <= 1.0):
+        raise ValueError("clip_curriculum: eps must lie in [0, 1], not %r" % (eps,))
+    metric = cur.get("metric", "length")
+    if metric not in _abi.CLIP_METRICS:
+        raise ValueError("clip_curriculum: unknown metric %r (known: %s)" % (metric, ", ".join(_abi.CLIP_METRICS)))
+    ref = cur.get("ref")
+    if ref is None:
+        if metric != "step_reward" and default_ref is None:
+            raise ValueError("clip_curriculum: the metric %r needs a ref (the value that counts as mastered)" % (metric,))
+        ref = 1.0 if metric == "step_reward" else default_ref
+    names = sorted(clip_sets)
+    spec = _abi.OrrClipCurriculum(alpha=alpha, eps=eps, metric=_abi.CLIP_METRICS.index(metric))
+    for c in range(_abi.MAX_CLIPS):
+        spec.ref[c] = 1.0                 # clip ids outside every set: never read for a logged episode of this env
+    for name in names:
+        ids = clip_sets[name]
+        r = _for_robot(ref, name, names, "clip_curriculum: ref")
+        if isinstance(ref, dict) and r is None:
+            raise ValueError("clip_curriculum: ref names no value for %s" % name)
+        if isinstance(r, (bool, np.bool_, str, dict)) or np.ndim(r) > 1:
+            raise ValueError("clip_curriculum: ref of %s must be a number or a list, not %r" % (name, r))
+        if np.ndim(r) == 0:
+            vals = {c: r for c in ids}
+        elif isinstance(ref, dict):
+            if len(r) != len(ids):
+                raise ValueError("clip_curriculum: ref of %s: %d values for a clip set of %d clips" % (name, len(r), len(ids)))
+            vals = dict(zip(ids, r))
+        else:
+            if len(r) <= max(ids):
+                raise ValueError("clip_curriculum: ref lists %d values; clip id %d of %s needs one" % (len(r), max(ids), name))
+            vals = {c: r[c] for c in ids}
+        for c, v in vals.items():
+            v = _number(v, "clip_curriculum: ref must hold numbers, not %r", v)
+            if not (0.0 < float(np.float32(v)) < math.inf):      # NaN fails the comparison
+                raise ValueError("clip_curriculum: ref of clip %d must be finite and > 0, not %r" % (c, v))
+            spec.ref[c] = v
+    return spec
+
+
 def torque_limit_spec(torque_limits, robot_names):
     """torque_limits (MotorModel's kwarg, minitaur_motor.py:57-66: None, a float, 12 floats in motor order, or a dict of robot name to
     either, for mixed batches) -> {robot name: float32 [12]}, +inf = no limit.  ValueError on anything the C-ABI

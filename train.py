@@ -93,6 +93,14 @@ def main():
     ap.add_argument("--clip-time", type=float, nargs=2, metavar=("MIN", "MAX"), default=None,
                     help="switch to a newly drawn clip of the set every U(MIN, MAX) seconds of motion time, mid-episode (ImitationTask's "
                          "clip_time_min / clip_time_max; overrides the task YAML's; default: never)")
+    ap.add_argument("--clip-weights", type=float, nargs="+", metavar="W", default=None,
+                    help="one weight per --motion-file: every reset and mid-episode switch draws clip k with probability W_k / sum W "
+                         "(overrides the task YAML's clip_weights; default: uniform)")
+    ap.add_argument("--clip-curriculum", type=clip_curriculum_arg, default=None, metavar="ALPHA,EPS[,METRIC]",
+                    help="failure-adaptive clip sampling on the device: once per iteration the logged episodes' scores (METRIC: length, the "
+                         "default, against the task's final episode step limit; return or step_reward against 1 per step) move a running "
+                         "score per clip with weight ALPHA, and clip k is drawn with probability (1 - EPS) (1 - score_k) / sum + EPS / n.  "
+                         "Logged records gain \"clip_prob\".  One rank")
     ap.add_argument("--perturb-init-state-prob", type=float, default=None,
                     help="probability that a reset starts the robot on a Gaussian-perturbed copy of the reference state (ImitationTask's "
                          "perturb_init_state_prob; overrides the task YAML's; default: 0)")
@@ -212,6 +220,9 @@ def main():
         raise SystemExit("train.py: --ent-coef / --log-std-bounds belong to --learn-std")
     privileged = args.privileged_critic or bool(args.distill) or args.history_ppo       # somebody reads env.privileged_obs
     rank, world, local = odist.init_from_env()
+    if args.clip_curriculum is not None and world > 1:
+        raise SystemExit("train.py: --clip-curriculum runs on one rank: each rank would adapt to its own episodes and the shards would no "
+                         "longer draw what one env draws (merging the statistics over ranks is not built)")
     if args.distill and world > 1:
         raise SystemExit("train.py: --distill runs on one rank")
     # ORR_BENCH_SINGLE_DEVICE=1 (+ ORR_DIST_BACKEND=gloo): several ranks rehearsed on a one-GPU box (tests), never a measurement
@@ -223,7 +234,9 @@ def main():
                           reward_terms=args.reward_terms, contact_outputs=args.contact_outputs or privileged,
                           observation_noise_stdev=args.sensor_noise, push=args.push,
                           push_outputs=privileged and args.push is not None,
-                          **clip_time_kwargs(args))     # (bound here, before the rollout graph is captured)
+                          **clip_time_kwargs(args), **clip_draw_kwargs(args))     # (bound here, before the rollout graph is captured)
+    if args.clip_curriculum is not None and not env.multi_clip:
+        raise SystemExit("train.py: --clip-curriculum needs several --motion-file")
     if args.history:
         return distill(args, torch, pol, ppo, rollout, odist, env, history_student(args, torch, pol, ppo, dev), dev)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
@@ -303,6 +316,8 @@ def main():
         by_clip = env.episode_returns_by_clip() if log_it and env.multi_clip else None
         by_term = env.episode_reward_terms() if log_it and args.reward_terms else None     # likewise; rank-local
         gait = env.episode_gait() if log_it and args.contact_outputs else None             # likewise
+        if args.clip_curriculum is not None:
+            env.clip_curriculum_update()                       # one launch on the log as it stands, before the gather clears it; no sync
         stats = odist.gather_env_episodes(env, args.horizon)   # means come from the exact per-rank sums, not the truncated list
         if log_it:
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2),
@@ -318,6 +333,8 @@ def main():
                 rec.update(control_record(learner))
             if by_clip is not None:
                 rec["ep_ret_mean_by_clip"] = {clip_name(env, c): round(r, 2) for c, (r, _) in sorted(by_clip.items())}
+            if args.clip_curriculum is not None or args.clip_weights is not None:
+                rec["clip_prob"] = clip_prob_record(env)
             if by_term is not None:
                 rec["reward_terms"] = {k: round(v, 4) for k, v in by_term.items()}
             if gait is not None:
@@ -394,6 +411,8 @@ def history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, wo
         samples += B * world
         if (world > 1 or os.environ.get("ORR_FORCE_DIST", "0") == "1") and args.sync_check_every > 0 and it % args.sync_check_every == args.sync_check_every - 1 and hasattr(learner, "check_synced"):
             learner.check_synced()
+        if args.clip_curriculum is not None:
+            env.clip_curriculum_update()
         stats = odist.gather_env_episodes(env, args.horizon)
         if rank == 0 and (it % 10 == 0 or it == args.iters - 1):
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
@@ -456,6 +475,8 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
         else:
             loss = learner.update(buf["obs"].reshape(B, -1), buf["teacher_mean"].reshape(B, 12), epochs=args.epochs, generator=gen)
         samples += B
+        if args.clip_curriculum is not None:
+            env.clip_curriculum_update()
         stats = odist.gather_env_episodes(env, args.horizon)
         if it % 10 == 0 or it == args.iters - 1:
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
@@ -504,6 +525,41 @@ def push_arg(text):
     except ValueError:
         raise argparse.ArgumentTypeError("not a number in %r" % (text,))
     return push
+
+
+def clip_curriculum_arg(s):
+    """ALPHA,EPS[,METRIC] -> the env's clip_curriculum dict; the refs are the env's defaults (env_spec.clip_curriculum_spec)."""
+    parts = s.split(",")
+    if len(parts) not in (2, 3):
+        raise argparse.ArgumentTypeError("expected ALPHA,EPS[,METRIC], got %r" % (s,))
+    try:
+        cur = {"alpha": float(parts[0]), "eps": float(parts[1])}
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected ALPHA,EPS[,METRIC] with two numbers, got %r" % (s,))
+    cur["metric"] = parts[2] if len(parts) == 3 else "length"
+    if cur["metric"] not in ("length", "return", "step_reward"):
+        raise argparse.ArgumentTypeError("METRIC is length, return or step_reward, not %r" % (cur["metric"],))
+    return cur
+
+
+def clip_draw_kwargs(args):
+    """--clip-weights / --clip-curriculum -> the env's clip_weights / clip_curriculum (nothing given: the task YAML's weights, no
+    curriculum)."""
+    kw = {}
+    if args.clip_weights is not None:
+        kw["clip_weights"] = list(args.clip_weights)
+    if args.clip_curriculum is not None:
+        kw["clip_curriculum"] = dict(args.clip_curriculum)
+    return kw
+
+
+def clip_prob_record(env):
+    """{clip name: probability} of the clip draws as the device holds them (one sync; logged iterations only)."""
+    out = {}
+    for name, p in env.clip_probabilities().items():
+        for c, x in zip(env.clip_sets[name], p):
+            out[clip_name(env, c)] = round(float(x), 6)
+    return out
 
 
 def clip_time_kwargs(args):
