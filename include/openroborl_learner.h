@@ -20,6 +20,9 @@
  *   orr_adam_step      Adam on the flat parameter vector, step counter on the device (the whole update replays as one hipGraph)
  *   orr_update_control the controls of a step from the flat gradient, on the device: clip coefficient of its norm, non-finite guard, KL gate
  *   orr_adam_step_ctl  orr_adam_step reading those controls and a learning-rate multiplier from device memory (no capture when they change)
+ *   orr_running_stats_update  running mean / variance of the network inputs over a whole rollout segment, one pass, merged on the device
+ *   orr_normalize_rows (x - mean) * rstd for the learner's batch (the rollout's forward pass has the normaliser folded into layer 0:
+ *                      orr_policy_pack_norm, openroborl_policy.h)
  * All pointers are device pointers, float32, row-major and 16-byte aligned; calls are asynchronous on the caller's stream; every
  * reduction runs in a fixed order (no float atomics: the same inputs give the same bits).  Return 0 or a negative code with text in
  * orr_last_error() (openroborl_hip.h).
@@ -235,6 +238,58 @@ int32_t orr_update_control(const float* g, int64_t n, float pre_scale, float max
  * orr_adam_step's bits (one kernel body; times 1.0f is exact).  ctl 16-byte aligned; everything else as orr_adam_step. */
 int32_t orr_adam_step_ctl(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                           float grad_scale, int32_t flags, int32_t* state, const orr_update_ctl* ctl, void* stream);
+
+/* ---- running observation normalisation (host side: ppo.RunningNorm) ------------------------------------------------------------------
+ * The statistics record of d columns, in caller-owned DEVICE memory, 16-byte aligned, ORR_RUNNING_STATS_FLOATS(d) 32-bit words:
+ *   word 0..1      int64 count (rows seen so far); words 2..3 pad
+ *   word 4         float mean[d]
+ *   word 4 + d     float var[d]     population variance
+ *   word 4 + 2 d   float rstd[d]    1 / (sqrt(var) + eps), formed from the float32 var as stored (a record rebuilt from count, mean, var has the same bits)
+ * d is a multiple of 4, so every array starts on 16 bytes.  The host initialises the record once: count 0, mean 0, var 1, rstd 1 - the
+ * identity. */
+#define ORR_RUNNING_STATS_FLOATS(d) (4 + 3 * (int64_t)(d))
+#define ORR_RUNNING_STATS_MEAN(d) 4
+#define ORR_RUNNING_STATS_VAR(d) (4 + (d))
+#define ORR_RUNNING_STATS_RSTD(d) (4 + 2 * (d))
+/* Bytes of the record of d columns; -1 for a d the kernels refuse. */
+int64_t orr_sizeof_running_stats(int32_t d);
+
+/* The streaming pass of the update: workgroups of ORR_RUNNING_STATS_THREADS threads, a thread owns four adjacent columns (one 16-byte load per
+ * row), a pass covers ORR_RUNNING_STATS_PASS_ROWS(d) whole rows = one contiguous range of x, a workgroup makes ORR_RUNNING_STATS_PASSES of them. */
+#define ORR_RUNNING_STATS_THREADS 320
+#define ORR_RUNNING_STATS_PASSES 32
+#define ORR_RUNNING_STATS_PASS_ROWS(d) (ORR_RUNNING_STATS_THREADS / ((d) / 4))
+#define ORR_RUNNING_STATS_BLOCK_ROWS(d) (ORR_RUNNING_STATS_PASSES * ORR_RUNNING_STATS_PASS_ROWS(d))
+/* Floats of `partials` for a batch of n rows of d columns: [workgroups][2][d], workgroups = ceil(n / ORR_RUNNING_STATS_BLOCK_ROWS(d)); -1 for
+ * arguments the update refuses. */
+int64_t orr_running_stats_partials(int64_t n, int32_t d);
+
+/* Merges the moments of a batch x [n][d] into the record, in two launches (like orr_update_control):
+ *   1. one pass over x, every element read exactly once by a 16-byte load.  A thread keeps the float32 sums of (x - s) and (x - s)^2 of its
+ *      four columns, s = the batch's FIRST row (a shift: the sums never see the column's offset, and sum(x^2) - sum(x)^2 / n is never formed in
+ *      float32); a workgroup adds its threads' sums row group by row group and leaves [2][d] floats in partials.  The grid is a function of n
+ *      and d alone;
+ *   2. one workgroup: the partials are added in float64, consecutive index ranges one after the other, each in index order; then one thread
+ *      per column forms the batch's mean = s + S1 / n and M2 = S2 - S1^2 / n (float64) and merges them with the record by the parallel formula
+ *      (Chan et al.), n_a, mean_a, M2_a = n_a var_a the record's:
+ *          n = n_a + n_b,  delta = mean_b - mean_a,  mean = mean_a + delta n_b / n,  M2 = M2_a + M2_b + delta^2 n_a n_b / n,  var = M2 / n
+ *      count 0: the batch replaces the record.  rstd = 1 / (sqrt(var) + eps), rsl_rl's form: at most 1 / eps.  The count is an integer sum.
+ * No float atomics and a fixed order of every addition: the same inputs give the same bits.
+ * Conditioning: the shift is one sample, not the mean.  With the first row D standard deviations from the column's mean, S2 - S1^2 / n
+ * cancels about 1 + D^2 of the partials' float32 digits: the batch's M2 carries a relative error of about (1 + D^2) x a few 2^-24 (D = 4:
+ * 1e-5 at most; a first row that is an outlier by 100 sigma: 1e-2).  The mean is not affected beyond the float32 sums' own rounding.
+ *   x [n][d] float32, 16-byte aligned; d a multiple of 4, 4 <= d <= 256; n >= 1; eps > 0 and finite
+ *   rec        the record, 16-byte aligned
+ *   partials   orr_running_stats_partials(n, d) floats, 16-byte aligned
+ * A refused call launches and writes nothing. */
+int32_t orr_running_stats_update(const float* x, int64_t n, int32_t d, float eps, float* rec, float* partials, void* stream);
+
+/* out[i][c] = (x[i][c] - mean[c]) * rstd[c] in float32: two roundings, no clip (a normaliser folded into a layer cannot clip either, and the
+ * learner must see the function the rollout ran).
+ *   x, out [n][d] 16-byte aligned; out may be x itself (in place) and must not overlap it otherwise
+ *   mean, rstd [d] 16-byte aligned (e.g. the record's arrays); d and n as above
+ * A refused call launches and writes nothing. */
+int32_t orr_normalize_rows(const float* x, int64_t n, int32_t d, const float* mean, const float* rstd, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,19 @@ int64_t orr_policy_packed_size(int32_t k, int32_t n);
  * so that one 16-byte load per lane yields its B operands of four consecutive MFMA k-steps. */
 int32_t orr_policy_pack(const float* w_dev, int32_t k, int32_t n, float* out_dev, void* stream);
 
+/* orr_policy_pack of a layer that has an input normaliser (x - mean) * rstd in front of it, folded into the layer: the forward kernels then
+ * run on RAW inputs, unchanged.  ((x - mean) * rstd) W + b = x (diag(rstd) W) + (b - (mean * rstd) W):
+ *   out_w     orr_policy_pack's image of diag(rstd) W: every element W[i][j] * rstd[i], one float32 multiplication
+ *   out_b[j]  = b[j] - sum_i (mean[i] * rstd[i]) * W[i][j]: the product mean * rstd rounded to float32, then a float32 fused multiply-add per
+ *             row, i = 0 .. k - 1 in that order from +0, then one subtraction
+ *   w [k][n] row-major, b [n], mean [k], rstd [k] (for a 208-row matrix the caller concatenates the tables: the observation's statistics,
+ *   then the privileged row's, or mean 0 and rstd 1 for rows that are not normalised); out_b [n], which may be b itself
+ * With mean 0 and rstd 1 the image and the bias equal orr_policy_pack's and b, bit for bit.  One launch, no atomics: the same inputs give the
+ * same bits.  Refused, nothing launched or written: what orr_policy_pack refuses, a null b, out_b, mean or rstd, an out_dev, mean or rstd that
+ * is not 16-byte aligned, a w, b or out_b that is not 4-byte aligned. */
+int32_t orr_policy_pack_norm(const float* w_dev, int32_t k, int32_t n, const float* mean, const float* rstd, const float* b, float* out_dev,
+                             float* out_b, void* stream);
+
 typedef struct orr_policy_net {
   /* packed weights (orr_policy_pack) and plain biases of the actor ("pi") and the critic ("vf") */
   const float* w0_pi; const float* b0_pi;   /* 160 x 512 */

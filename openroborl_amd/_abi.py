@@ -268,6 +268,39 @@ POLICY_FORWARD_HISTORY_PRIV_ARGS = [C.POINTER(OrrPolicyNet), C.POINTER(OrrHistor
 LATENT_BACKWARD_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
+# include/openroborl_learner.h: the statistics record of running observation normalisation, ORR_RUNNING_STATS_* (32-bit words of a record of
+# d columns: int64 count + pad, then mean [d], var [d], rstd [d]) and the streaming pass's geometry
+RUNNING_STATS_THREADS = 320
+RUNNING_STATS_PASSES = 32
+# int32_t orr_running_stats_update(const float* x [n][d], int64_t n, int32_t d, float eps, float* rec, float* partials, void* stream)
+RUNNING_STATS_UPDATE_ARGS = [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+# int32_t orr_normalize_rows(const float* x [n][d], int64_t n, int32_t d, const float* mean [d], const float* rstd [d], float* out [n][d], void* stream)
+NORMALIZE_ROWS_ARGS = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_policy.h: int32_t orr_policy_pack_norm(const float* w [k][n], int32_t k, int32_t n, const float* mean [k], const float* rstd [k],
+#   const float* b [n], float* out_w (packed), float* out_b [n], void* stream)
+POLICY_PACK_NORM_ARGS = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def running_stats_floats(d):
+    """ORR_RUNNING_STATS_FLOATS"""
+    return 4 + 3 * int(d)
+
+
+def running_stats_offsets(d):
+    """ORR_RUNNING_STATS_MEAN, _VAR, _RSTD: the word offsets of the three arrays"""
+    return 4, 4 + int(d), 4 + 2 * int(d)
+
+
+def running_stats_pass_rows(d):
+    """ORR_RUNNING_STATS_PASS_ROWS: whole rows a workgroup of the streaming pass reads at once"""
+    return RUNNING_STATS_THREADS // (int(d) // 4)
+
+
+def running_stats_block_rows(d):
+    """ORR_RUNNING_STATS_BLOCK_ROWS: rows per workgroup = rows behind one [2][d] partial"""
+    return RUNNING_STATS_PASSES * running_stats_pass_rows(d)
+
+
 def student_head_rows(m):
     """include/openroborl_learner.h: ORR_STUDENT_HEAD_ROWS - the rows of partial sums orr_history_student_head leaves, one per 16 samples."""
     return (int(m) + 15) // 16

@@ -109,6 +109,7 @@ EXPORTS = [
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_history", "orr_policy_forward_history_priv", "orr_history_push", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_ppo_head_logstd", "orr_gauss_prepare", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_latent_backward", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
     "orr_sizeof_update_ctl", "orr_update_control_partials", "orr_update_control", "orr_adam_step_ctl",
+    "orr_sizeof_running_stats", "orr_running_stats_partials", "orr_running_stats_update", "orr_normalize_rows", "orr_policy_pack_norm",
 ]
 
 
@@ -381,6 +382,16 @@ def load():
     L.orr_update_control.argtypes = _abi.UPDATE_CONTROL_ARGS
     L.orr_adam_step_ctl.restype = C.c_int32
     L.orr_adam_step_ctl.argtypes = _abi.ADAM_STEP_CTL_ARGS
+    L.orr_sizeof_running_stats.restype = C.c_int64
+    L.orr_sizeof_running_stats.argtypes = [C.c_int32]
+    L.orr_running_stats_partials.restype = C.c_int64
+    L.orr_running_stats_partials.argtypes = [C.c_int64, C.c_int32]
+    L.orr_running_stats_update.restype = C.c_int32
+    L.orr_running_stats_update.argtypes = _abi.RUNNING_STATS_UPDATE_ARGS
+    L.orr_normalize_rows.restype = C.c_int32
+    L.orr_normalize_rows.argtypes = _abi.NORMALIZE_ROWS_ARGS
+    L.orr_policy_pack_norm.restype = C.c_int32
+    L.orr_policy_pack_norm.argtypes = _abi.POLICY_PACK_NORM_ARGS
     if L.orr_abi_version() != _abi.ABI_VERSION:
         raise RuntimeError("libopenroborl_hip.so ABI version mismatch")
     if (L.orr_sizeof_config() != C.sizeof(_abi.OrrConfig) or L.orr_sizeof_model() != C.sizeof(_abi.OrrModel)

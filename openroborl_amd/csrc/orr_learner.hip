@@ -564,7 +564,133 @@ __global__ __launch_bounds__(64) void update_control_kernel(const float* __restr
   ctl->skip = skip;
 }
 
+// ---- running observation normalisation: orr_running_stats_update, orr_normalize_rows ---------------------------------------------------
+// The streaming pass.  A workgroup's kStatThreads / (d / 4) * (d / 4) working threads read consecutive 16-byte quads: thread t of pass p
+// reads quad t of the pass's rows, so a pass is ONE contiguous range of x (d = 160: 40 column groups x 8 rows = 320 threads = 5120 bytes) and
+// a thread keeps its column group over all passes.  A thread's loads of eight passes are issued before the first is used.  The moments are
+// shifted sums around the batch's first row s: S1 = sum (x - s), S2 = sum (x - s)^2, float32 over a thread's <= 32 rows, then over the
+// workgroup's row groups one after the other.  For a column of offset 1000 and spread 0.01 every x - s is exact and of the spread's size:
+// the offset never enters a sum.  Launch-bound partial sums [block][2][d]; 262144 x 160: 1024 workgroups, 1.3 MB of partials behind 168 MB.
+constexpr int kStatThreads = ORR_RUNNING_STATS_THREADS, kStatPasses = ORR_RUNNING_STATS_PASSES, kStatUnroll = 8;
+static_assert(kStatPasses % kStatUnroll == 0, "whole groups of loads");
+
+__device__ inline void stat_add(f4& s1, f4& s2, f4 v, f4 shift) {
+  const f4 e = v - shift;
+  s1 += e;
+  s2.x = fmaf(e.x, e.x, s2.x); s2.y = fmaf(e.y, e.y, s2.y); s2.z = fmaf(e.z, e.z, s2.z); s2.w = fmaf(e.w, e.w, s2.w);
+}
+
+__global__ __launch_bounds__(kStatThreads) void running_stats_partial_kernel(const float* __restrict__ x, long long n, int d,
+                                                                            float* __restrict__ partials) {
+  __shared__ f4 red1[kStatThreads];
+  __shared__ f4 red2[kStatThreads];
+  const int c4n = d >> 2, side = kStatThreads / c4n, t = threadIdx.x;
+  const int c4 = t % c4n, r = t / c4n;
+  f4 s1 = {0.0f, 0.0f, 0.0f, 0.0f}, s2 = {0.0f, 0.0f, 0.0f, 0.0f};
+  const long long first = (long long)blockIdx.x * side * kStatPasses + r;      // this thread's rows: first, first + side, ...
+  if (r < side && first < n) {
+    const f4 shift = *reinterpret_cast<const f4*>(x + 4 * c4);
+    const long long left = (n - first + side - 1) / side;
+    const int np = left < kStatPasses ? (int)left : kStatPasses;
+    const f4* q = reinterpret_cast<const f4*>(x + first * d + 4 * c4);
+    const long long step = (long long)side * c4n;                               // quads from a row to the thread's next
+    int p = 0;
+    for (; p + kStatUnroll <= np; p += kStatUnroll) {
+      f4 v[kStatUnroll];
+#pragma unroll
+      for (int u = 0; u < kStatUnroll; u++) v[u] = q[(p + u) * step];
+#pragma unroll
+      for (int u = 0; u < kStatUnroll; u++) stat_add(s1, s2, v[u], shift);
+    }
+    for (; p < np; p++) stat_add(s1, s2, q[p * step], shift);
+  }
+  red1[t] = s1;
+  red2[t] = s2;
+  __syncthreads();
+  if (t < c4n) {
+    f4 a1 = red1[t], a2 = red2[t];
+    for (int k = 1; k < side; k++) { a1 += red1[k * c4n + t]; a2 += red2[k * c4n + t]; }
+    float* o = partials + (size_t)blockIdx.x * 2 * d + 4 * t;
+    *reinterpret_cast<f4*>(o) = a1;
+    *reinterpret_cast<f4*>(o + d) = a2;
+  }
+}
+
+// The merge: one workgroup.  kMergeThreads / d threads share a column: each adds a consecutive range of the partials in index order, in
+// float64, and the ranges are added in their order; then one thread per column does the batch's moments and the merge with the record in
+// float64.  Every thread reads the record's count before the barrier, thread 0 writes it behind it.
+constexpr int kMergeThreads = 1024;
+__global__ __launch_bounds__(kMergeThreads) void running_stats_merge_kernel(const float* __restrict__ partials, long long nparts, long long n, int d,
+                                                                           float eps, const float* __restrict__ x, float* __restrict__ rec) {
+  __shared__ double red1[kMergeThreads];
+  __shared__ double red2[kMergeThreads];
+  const int segs = kMergeThreads / d, t = threadIdx.x;
+  const int c = t % d, seg = t / d;
+  const long long per = (nparts + segs - 1) / segs;
+  double a1 = 0.0, a2 = 0.0;
+  if (seg < segs) {
+    const long long b0 = seg * per, b1 = b0 + per < nparts ? b0 + per : nparts;
+#pragma unroll 8
+    for (long long b = b0; b < b1; b++) {
+      a1 += (double)partials[(size_t)b * 2 * d + c];
+      a2 += (double)partials[(size_t)b * 2 * d + d + c];
+    }
+  }
+  red1[t] = a1;
+  red2[t] = a2;
+  long long* count = reinterpret_cast<long long*>(rec);
+  const long long na = *count;
+  __syncthreads();
+  if (t < d) {
+    double S1 = red1[t], S2 = red2[t];
+    for (int k = 1; k < segs; k++) { S1 += red1[k * d + t]; S2 += red2[k * d + t]; }
+    const double nb = (double)n;
+    double mean = (double)x[t] + S1 / nb;
+    double M2 = S2 - S1 * S1 / nb;
+    M2 = M2 > 0.0 ? M2 : 0.0;
+    double tot = nb;
+    float* mean_r = rec + ORR_RUNNING_STATS_MEAN(d);
+    float* var_r = rec + ORR_RUNNING_STATS_VAR(d);
+    float* rstd_r = rec + ORR_RUNNING_STATS_RSTD(d);
+    if (na > 0) {
+      const double a = (double)na, mean_a = (double)mean_r[t], delta = mean - mean_a;
+      tot = a + nb;
+      M2 = (double)var_r[t] * a + M2 + delta * delta * (a * nb / tot);
+      mean = mean_a + delta * (nb / tot);
+    }
+    const float var = (float)(M2 / tot);
+    mean_r[t] = (float)mean;
+    var_r[t] = var;
+    rstd_r[t] = (float)(1.0 / (sqrt((double)var) + (double)eps));
+  }
+  if (t == 0) *count = (na > 0 ? na : 0) + n;
+}
+
+// (x - mean) * rstd: a thread owns kNormLoads quads a workgroup's width apart, reads them all, then writes them - out may be x itself
+// (no __restrict__ on the two).  A subtraction and a multiplication: nothing for the compiler to contract.
+constexpr int kNormLoads = 4;
+__global__ __launch_bounds__(kThreads) void normalize_rows_kernel(const float* x, long long quads, int c4n, const float* __restrict__ mean,
+                                                                  const float* __restrict__ rstd, float* out) {
+  const long long base = (long long)blockIdx.x * (kThreads * kNormLoads) + threadIdx.x;
+  f4 v[kNormLoads];
+#pragma unroll
+  for (int u = 0; u < kNormLoads; u++) {
+    const long long i = base + (long long)u * kThreads;
+    if (i < quads) v[u] = reinterpret_cast<const f4*>(x)[i];
+  }
+#pragma unroll
+  for (int u = 0; u < kNormLoads; u++) {
+    const long long i = base + (long long)u * kThreads;
+    if (i < quads) {
+      const int c4 = (int)(i % c4n);
+      const f4 m = reinterpret_cast<const f4*>(mean)[c4], r = reinterpret_cast<const f4*>(rstd)[c4];
+      reinterpret_cast<f4*>(out)[i] = (v[u] - m) * r;
+    }
+  }
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool stats_dims_ok(int d) { return d >= 4 && d <= 256 && (d % 4) == 0; }
 inline int nblocks_rows(int m) { return (m + kRowsPerBlock - 1) / kRowsPerBlock; }
 inline bool cols_ok(int c) { return c >= 4 && (c % 4) == 0 && (c / 4) <= kThreads && (kThreads % (c / 4)) == 0; }
 
@@ -753,6 +879,47 @@ int32_t orr_update_control(const float* g, int64_t n, float pre_scale, float max
                      kl_target, kl_lr_lo, kl_lr_hi, ctl);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_update_control: launch", e);
+  return 0;
+}
+
+int64_t orr_sizeof_running_stats(int32_t d) { return stats_dims_ok(d) ? (int64_t)sizeof(float) * ORR_RUNNING_STATS_FLOATS(d) : -1; }
+
+int64_t orr_running_stats_partials(int64_t n, int32_t d) {
+  if (n < 1 || !stats_dims_ok(d)) return -1;
+  const int64_t rows = ORR_RUNNING_STATS_BLOCK_ROWS(d);
+  return (n + rows - 1) / rows * 2 * d;
+}
+
+int32_t orr_running_stats_update(const float* x, int64_t n, int32_t d, float eps, float* rec, float* partials, void* stream) {
+  if (!x || !rec || !partials || n < 1) return orr_fail(-1, "orr_running_stats_update: bad argument", hipSuccess);
+  if (!stats_dims_ok(d)) return orr_fail(-1, "orr_running_stats_update: d must be a multiple of 4 from 4 to 256", hipSuccess);
+  if (!(eps > 0.0f && eps <= 3.4e38f)) return orr_fail(-1, "orr_running_stats_update: eps must be positive and finite", hipSuccess);
+  if (!aligned16(x) || !aligned16(rec) || !aligned16(partials))
+    return orr_fail(-1, "orr_running_stats_update: x, rec and partials must be 16-byte aligned", hipSuccess);
+  const int64_t rows = ORR_RUNNING_STATS_BLOCK_ROWS(d);
+  const long long nparts = (n + rows - 1) / rows;
+  if (nparts > 0x7fffffffLL) return orr_fail(-1, "orr_running_stats_update: n too large", hipSuccess);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(running_stats_partial_kernel, dim3((unsigned)nparts), dim3(kStatThreads), 0, st, x, (long long)n, (int)d, partials);
+  hipLaunchKernelGGL(running_stats_merge_kernel, dim3(1), dim3(kMergeThreads), 0, st, (const float*)partials, nparts, (long long)n, (int)d, eps, x, rec);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_running_stats_update: launch", e);
+  return 0;
+}
+
+int32_t orr_normalize_rows(const float* x, int64_t n, int32_t d, const float* mean, const float* rstd, float* out, void* stream) {
+  if (!x || !mean || !rstd || !out || n < 1) return orr_fail(-1, "orr_normalize_rows: bad argument", hipSuccess);
+  if (!stats_dims_ok(d)) return orr_fail(-1, "orr_normalize_rows: d must be a multiple of 4 from 4 to 256", hipSuccess);
+  if (!aligned16(x) || !aligned16(out) || !aligned16(mean) || !aligned16(rstd))
+    return orr_fail(-1, "orr_normalize_rows: buffers must be 16-byte aligned", hipSuccess);
+  const long long quads = (long long)n * (d / 4);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(out), bytes = (uintptr_t)quads * 16;
+  if (a != b && a < b + bytes && b < a + bytes) return orr_fail(-1, "orr_normalize_rows: out must be x itself or not overlap it", hipSuccess);
+  const long long per_block = (long long)kThreads * kNormLoads, nblk = (quads + per_block - 1) / per_block;
+  if (nblk > 0x7fffffffLL) return orr_fail(-1, "orr_normalize_rows: n too large", hipSuccess);
+  hipLaunchKernelGGL(normalize_rows_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, (hipStream_t)stream, x, quads, (int)(d / 4), mean, rstd, out);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_normalize_rows: launch", e);
   return 0;
 }
 

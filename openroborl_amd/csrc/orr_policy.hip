@@ -46,6 +46,34 @@ __global__ void pack_kernel(const float* __restrict__ w, int K, int N, float* __
   out[i] = c < N ? w[(size_t)k * N + c] : 0.0f;
 }
 
+// orr_policy_pack_norm: pack_kernel on diag(rstd) W, and behind its workgroups those of the folded bias - a thread per output column walks
+// the k rows in order (eight loads in flight, one fmaf chain from +0: with mean 0 every term is a zero and b comes out as it went in).
+__global__ __launch_bounds__(256) void pack_norm_kernel(const float* __restrict__ w, int K, int N, const float* __restrict__ mean,
+                                                        const float* __restrict__ rstd, const float* b, float* __restrict__ out, float* out_b,
+                                                        long long total, int pack_blocks) {
+  if ((int)blockIdx.x < pack_blocks) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int j = (int)(i & 3), l = (int)((i >> 2) & 63);
+    const long long t = i >> 8;                 // nt * (K / 16) + kg
+    const int kgs = K / 16, kg = (int)(t % kgs), nt = (int)(t / kgs);
+    const int k = 16 * kg + 4 * j + (l >> 4), c = 16 * nt + (l & 15);
+    out[i] = c < N ? w[(size_t)k * N + c] * rstd[k] : 0.0f;
+    return;
+  }
+  const int c = ((int)blockIdx.x - pack_blocks) * 256 + threadIdx.x;
+  if (c >= N) return;
+  float s = 0.0f;
+  for (int k0 = 0; k0 < K; k0 += 8) {           // K is a multiple of 16
+    float wv[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) wv[u] = w[(size_t)(k0 + u) * N + c];
+#pragma unroll
+    for (int u = 0; u < 8; u++) s = fmaf(mean[k0 + u] * rstd[k0 + u], wv[u], s);
+  }
+  out_b[c] = b[c] - s;
+}
+
 struct Params {
   orr_policy_net net;
   const float* obs;
@@ -611,6 +639,23 @@ int32_t orr_policy_pack(const float* w_dev, int32_t k, int32_t n, float* out_dev
   hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_dev, (int)k, (int)n, out_dev, total);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return orr_fail(-2, "orr_policy_pack: launch", e);
+  return 0;
+}
+
+int32_t orr_policy_pack_norm(const float* w_dev, int32_t k, int32_t n, const float* mean, const float* rstd, const float* b, float* out_dev,
+                             float* out_b, void* stream) {
+  const long long total = orr_policy_packed_size(k, n);
+  if (!w_dev || !out_dev || total < 0) return orr_fail(-1, "orr_policy_pack_norm: bad argument (K must be a multiple of 16)", hipSuccess);
+  if (!mean || !rstd || !b || !out_b) return orr_fail(-1, "orr_policy_pack_norm: null statistics table or bias", hipSuccess);
+  if ((reinterpret_cast<uintptr_t>(mean) & 15) || (reinterpret_cast<uintptr_t>(rstd) & 15) || (reinterpret_cast<uintptr_t>(out_dev) & 15))
+    return orr_fail(-1, "orr_policy_pack_norm: mean, rstd and the packed image must be 16-byte aligned", hipSuccess);
+  if ((reinterpret_cast<uintptr_t>(w_dev) & 3) || (reinterpret_cast<uintptr_t>(b) & 3) || (reinterpret_cast<uintptr_t>(out_b) & 3))
+    return orr_fail(-1, "orr_policy_pack_norm: w, b and out_b must be 4-byte aligned", hipSuccess);
+  const int pack_blocks = (int)((total + 255) / 256), bias_blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(pack_norm_kernel, dim3((unsigned)(pack_blocks + bias_blocks)), dim3(256), 0, (hipStream_t)stream, w_dev, (int)k, (int)n, mean, rstd,
+                     b, out_dev, out_b, total, pack_blocks);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return orr_fail(-2, "orr_policy_pack_norm: launch", e);
   return 0;
 }
 

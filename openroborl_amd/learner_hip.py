@@ -25,6 +25,8 @@ minibatch's approx_kl - the clip coefficient, a guard that skips the step of a n
 and the KL-adaptive learning rate -, and that set_lr_mult() writes for a schedule (the reference's schedule='linear',
 agents/ppo_imitation.py:296-299): none of them captures again and none costs a host round trip; control_stats() reads the diagnostics.
 Without those arguments a learner launches what it always did (orr_adam_step, self.ctl is None).
+A model with an observation normaliser (ppo.ActorCritic(obs_norm=True)) is FusedPPO's alone: its update() fills the plan's static obs /
+priv inputs through orr_normalize_rows instead of a copy, so the captured epoch is the one it would be without; the other three refuse it.
 There is no fallback: without a GPU and the HIP library the constructors raise.
 """
 import ctypes as C
@@ -32,6 +34,8 @@ import os
 
 from . import _abi, _lib
 from .policy import LOGSTD         # the learned log-std of ppo.ActorCritic(learn_std=True)
+
+from .ppo import _no_obs_norm      # the learners without a normalising fill() refuse a model with an observation normaliser
 
 NETS = ("pi", "vf")
 
@@ -427,9 +431,18 @@ class FusedPPO(_FusedLearner):
             if logp is None:
                 logp = self.model.log_prob(obs, actions, *((priv,) if self.actor_priv_dim else ()))
             self._refresh_std()
-            P["obs"].copy_(obs)
+            # a model with an observation normaliser: the static inputs hold (x - mean) * rstd (orr_normalize_rows instead of the copy),
+            # so nothing inside the captured epoch changes; the statistics are the ones the rollout ran with
+            norm, pnorm = getattr(self.model, "obs_norm", None), getattr(self.model, "priv_norm", None)
+            if norm is not None:
+                norm.normalize(obs.contiguous(), out=P["obs"])
+            else:
+                P["obs"].copy_(obs)
             if priv is not None:
-                P["priv"].copy_(priv)
+                if pnorm is not None:
+                    pnorm.normalize(priv.contiguous(), out=P["priv"])
+                else:
+                    P["priv"].copy_(priv)
             aux = P["aux"]
             aux[:, :12].copy_(actions)
             aux[:, 12].copy_(logp)
@@ -516,6 +529,7 @@ class FusedPPOHistory(FusedPPO):
                  mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, latent_coef=0.0, max_grad_norm=None, device_lr=False,
                  kl_stop=None, kl_target=None, kl_lr_bounds=None):
         import math
+        _no_obs_norm(model, "FusedPPOHistory")
         if not getattr(model, "history", 0):
             raise ValueError("FusedPPOHistory: the model needs a history encoder (ActorCritic(history=16)); a model without is trained by FusedPPO")
         self.latent_coef = float(latent_coef)
@@ -613,6 +627,7 @@ class FusedDistill(_FusedLearner):
     one hipGraph (a single chain on one stream).  One rank: there is no gradient all-reduce here."""
 
     def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, max_grad_norm=None, device_lr=False):
+        _no_obs_norm(student, "FusedDistill")
         if getattr(student, "actor_priv_dim", 0):
             raise ValueError("FusedDistill: the student's actor must read the 160 observation words only")
         self._need_gpu(student)
@@ -675,6 +690,7 @@ class FusedDistillHistory(_FusedLearner):
         self.head = not (self.action_coef == 0.0 and self.latent_coef == 1.0)      # orr_history_student_head instead of orr_regress_head
         self.last_latent_loss = self.last_action_loss = None     # the means over the last update's minibatches
         self._actor, self._actor_seen = None, None
+        _no_obs_norm(student, "FusedDistillHistory")
         self._need_gpu(student)
         if not getattr(student, "history", 0):
             raise ValueError("FusedDistillHistory: the student needs a history encoder (ActorCritic(history=16))")

@@ -22,16 +22,26 @@ def _norm_key(k):
     return k.replace("__", "/").replace("_0", ":0") if "__" in k else k
 
 
+# the statistics of an observation normaliser (ppo.ActorCritic(obs_norm=True)): <prefix>/count (int64), /mean, /var, /eps; no reference counterpart
+NORM_PREFIXES = ("obs_norm", "priv_norm")
+NORM_FIELDS = (("count", np.int64), ("mean", np.float32), ("var", np.float32), ("eps", np.float32))
+
+
+def _as_loaded(k, v):
+    """float32, but a normaliser's row count as the integer it is (it passes 2^24 within a few hundred iterations)."""
+    return v.astype(np.int64) if k.endswith("_norm/count") else v.astype(np.float32)
+
+
 def load_parameters(path):
-    """dict name -> float32 array from a stable-baselines zip or an npz."""
+    """dict name -> float32 array from a stable-baselines zip or an npz (a normaliser's obs_norm/count: int64)."""
     if zipfile.is_zipfile(path):
         with zipfile.ZipFile(path) as z:
             names = z.namelist()
             if "parameters" in names:            # stable-baselines model zip
                 params = np.load(io.BytesIO(z.read("parameters")))
-                return {k: params[k].astype(np.float32) for k in params.files}
+                return {k: _as_loaded(k, params[k]) for k in params.files}
     params = np.load(path)
-    return {_norm_key(k): params[k].astype(np.float32) for k in params.files}
+    return {_norm_key(k): _as_loaded(_norm_key(k), params[k]) for k in params.files}
 
 
 # variables of the reference's ImitationPolicy graph in the order stable-baselines saves them (parameter_list of the shipped
@@ -94,6 +104,12 @@ def save_parameters_zip(path, params, data=None):
             raise ValueError("%s has shape %s, a learned log-std has %s" % (name, v.shape, shape))
         out[name] = v
         names.append(name)
+    for prefix in NORM_PREFIXES:                 # an observation normaliser's statistics (ppo.ActorCritic(obs_norm=True)): likewise behind the list.
+        if prefix + "/count" in params:          # The nets of such a zip expect normalised inputs: the reference must not load it as a plain policy,
+            for field, dtype in NORM_FIELDS:     # and with these names in the list its exact_match load refuses it (save_folded writes one it can run)
+                if "%s/%s" % (prefix, field) in params:
+                    out["%s/%s" % (prefix, field)] = np.asarray(params["%s/%s" % (prefix, field)], dtype=dtype)
+                    names.append("%s/%s" % (prefix, field))
     buf = io.BytesIO()
     np.savez(buf, **out)
     with zipfile.ZipFile(path, "w") as z:
@@ -102,12 +118,55 @@ def save_parameters_zip(path, params, data=None):
         z.writestr("parameters", buf.getvalue())
 
 
+NORM_EPS = 1e-2       # ppo.NORM_EPS: what a zip without <prefix>/eps was normalised with
+
+
+def fold_norm(params):
+    """The parameters of a model with an observation normaliser (its state_dict(): obs_norm/*, priv_norm/*) as those of the SAME function
+    on raw inputs, without statistics: ((x - mean) * rstd) W + b = x (diag(rstd) W) + (b - (mean * rstd) W) for both layer 0s.
+    rstd = 1 / (sqrt(var) + eps) as the record forms it (float64 on the float32 var, rounded once); the matrix is the float32 product
+    rstd_i * W_ij (what orr_policy_pack_norm packs), the bias is summed in float64 and rounded once.  Rows 160.. of a 208-row matrix take
+    priv_norm's statistics.  A dict without statistics comes back as a copy."""
+    out = {k: np.asarray(v) for k, v in params.items() if not k.startswith(tuple(p + "/" for p in NORM_PREFIXES))}
+    if "obs_norm/count" not in params:
+        return out
+    tab = {}
+    for prefix in NORM_PREFIXES:
+        if prefix + "/count" in params:
+            var = np.asarray(params[prefix + "/var"], dtype=np.float32)
+            eps = np.float32(np.asarray(params.get(prefix + "/eps", NORM_EPS)).reshape(-1)[0])
+            tab[prefix] = (np.asarray(params[prefix + "/mean"], dtype=np.float32),
+                           (1.0 / (np.sqrt(var.astype(np.float64)) + np.float64(eps))).astype(np.float32))
+    for net in ("pi", "vf"):
+        w = np.asarray(params["model/%s_fc0/w:0" % net], dtype=np.float32)
+        b = np.asarray(params["model/%s_fc0/b:0" % net], dtype=np.float32)
+        mean, rstd = tab["obs_norm"]
+        if w.shape[0] > mean.shape[0]:
+            if "priv_norm" not in tab:
+                raise ValueError("model/%s_fc0/w:0 has %d rows and the dict no priv_norm/*" % (net, w.shape[0]))
+            mean, rstd = np.concatenate((mean, tab["priv_norm"][0])), np.concatenate((rstd, tab["priv_norm"][1]))
+        if w.shape[0] != mean.shape[0]:
+            raise ValueError("model/%s_fc0/w:0 has %d rows, the statistics %d columns" % (net, w.shape[0], mean.shape[0]))
+        out["model/%s_fc0/w:0" % net] = rstd[:, None] * w
+        out["model/%s_fc0/b:0" % net] = (b.astype(np.float64) - (mean * rstd).astype(np.float64) @ w.astype(np.float64)).astype(np.float32)
+    return out
+
+
+def save_folded(path, params, data=None):
+    """save_parameters_zip of fold_norm(params): a zip with no statistics whose layer-0 matrices and biases carry the normaliser.  For a
+    model without privileged rows that is a plain 160 -> 512 -> 256 -> 12 policy: MLPPolicy.from_file and the reference's run.py load it
+    and run it on raw observations."""
+    save_parameters_zip(path, fold_norm(params), data)
+
+
 class MLPPolicy(object):
     def __init__(self, params, device, std=PI_STD):
         import torch
         self.torch = torch
         self.device = torch.device(device)
         self.std = float(std)
+        if "obs_norm/count" in params:           # a zip with a normaliser's statistics: the same function on raw observations
+            params = fold_norm(params)
         g = lambda k: torch.tensor(params[k], dtype=torch.float32, device=self.device)
         self.pi = [(g("model/pi_fc0/w:0"), g("model/pi_fc0/b:0")), (g("model/pi_fc1/w:0"), g("model/pi_fc1/b:0")),
                    (g("model/pi/w:0"), g("model/pi/b:0"))]

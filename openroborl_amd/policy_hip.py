@@ -27,7 +27,7 @@ class FusedActorCritic(object):
     static buffer) and then runs the forward kernel it would run anyway with std = 1, mean + 1 * x being mean + x.  The twelve values are
     read on the device, from this object's own copy at a fixed address (refresh() renews it), never on the host."""
 
-    def __init__(self, params, device, std, clip=2.0 * math.pi):
+    def __init__(self, params, device, std, clip=2.0 * math.pi, obs_norm=None, priv_norm=None):
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -76,6 +76,24 @@ class FusedActorCritic(object):
             if params[LOGSTD].numel() != 12:
                 raise ValueError("%s has shape %s, the sampler is built for (1, 12)" % (LOGSTD, tuple(params[LOGSTD].shape)))
             self.log_std = torch.empty(12, dtype=torch.float32, device=self.device)
+        # an observation normaliser (ppo.RunningNorm over the 160 words; priv_norm over the 48 of the privileged row): folded into the two
+        # layer-0 images and biases by refresh(), so forward() launches what it launches without.  The statistics are read on the device, from
+        # the records' fixed addresses (a captured refresh() follows them); a 208-row matrix reads a table of its own, obs | priv
+        self.obs_norm, self.priv_norm = obs_norm, priv_norm
+        self._norm_tab = None
+        if obs_norm is not None:
+            if self.history:
+                raise ValueError("an observation normaliser with a history encoder is not built")
+            def here(norm):     # the record's device against this object's, both resolved (a tensor on "cuda" reports cuda:<current>)
+                d = norm.rec.device
+                return d.type == self.device.type and (torch.cuda.current_device() if d.index is None else d.index) == self.device.index
+            if obs_norm.dim != 160 or not here(obs_norm) or (priv_norm is not None and (priv_norm.dim != _abi.POLICY_PRIV_DIM or not here(priv_norm))):
+                raise ValueError("obs_norm must be a RunningNorm(160) and priv_norm a RunningNorm(%d) on %s" % (_abi.POLICY_PRIV_DIM, self.device))
+            if self.priv_dim:
+                k = 160 + _abi.POLICY_PRIV_DIM
+                self._norm_tab = (torch.zeros(k, dtype=torch.float32, device=self.device), torch.ones(k, dtype=torch.float32, device=self.device))
+        elif priv_norm is not None:
+            raise ValueError("priv_norm goes with obs_norm")
         self.net = _abi.OrrPolicyNet()
         self.refresh()
 
@@ -83,17 +101,41 @@ class FusedActorCritic(object):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     def refresh(self):
-        """Re-pack the weights (six small launches, eight with an encoder) and re-read the biases from the parameter tensors."""
+        """Re-pack the weights (six small launches, eight with an encoder) and re-read the biases from the parameter tensors.  With an
+        observation normaliser the two layer-0 matrices go through orr_policy_pack_norm, which also writes their folded biases."""
         t = self.torch
         if self.log_std is not None:
             self.log_std.copy_(self.params[LOGSTD].detach().reshape(12))
+        if self._norm_tab is not None:         # the table of a 208-row layer 0: the observation's statistics, then the row's (or 0, 1 as built)
+            for tab, name in zip(self._norm_tab, ("mean", "rstd")):
+                tab[:160].copy_(getattr(self.obs_norm, name))
+                if self.priv_norm is not None:
+                    tab[160:].copy_(getattr(self.priv_norm, name))
         for struct, prefix, keys in ((self.net, "", KEYS),) + (((self.enc, "enc_", ENC_KEYS),) if self.history else ()):
+            done = set()                       # biases the folded pack has written
             for field, key in keys:
                 w = self.params[key].detach()
                 if w.dtype != t.float32 or not w.is_contiguous() or w.device != self.device:
                     w = w.to(device=self.device, dtype=t.float32).contiguous()
                 name = prefix + field
-                if field.startswith("w"):
+                if self.obs_norm is not None and name in ("w0_pi", "w0_vf"):
+                    # layer 0 behind the normaliser: the packed image of diag(rstd) W and the folded bias, straight into the bias copy
+                    k, n = w.shape
+                    b = self.params[dict(keys)["b0" + field[2:]]].detach()
+                    if b.dtype != t.float32 or not b.is_contiguous() or b.device != self.device:
+                        b = b.to(device=self.device, dtype=t.float32).contiguous()
+                    bname = "b0" + field[2:]
+                    if bname not in self.biases:
+                        self.biases[bname] = t.empty_like(b)
+                    mean, rstd = (self.obs_norm.mean, self.obs_norm.rstd) if int(k) == 160 else self._norm_tab
+                    _lib.check(self.L.orr_policy_pack_norm(w.data_ptr(), int(k), int(n), mean.data_ptr(), rstd.data_ptr(), b.data_ptr(),
+                                                           self.packed[name].data_ptr(), self.biases[bname].data_ptr(), self._stream()), self.L)
+                    setattr(struct, field, self.packed[name].data_ptr())
+                    setattr(struct, bname, self.biases[bname].data_ptr())
+                    done.add(bname)
+                elif name in done:
+                    pass
+                elif field.startswith("w"):
                     k, n = w.shape
                     _lib.check(self.L.orr_policy_pack(w.data_ptr(), int(k), int(n), self.packed[name].data_ptr(), self._stream()), self.L)
                     setattr(struct, field, self.packed[name].data_ptr())

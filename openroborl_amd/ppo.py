@@ -47,6 +47,143 @@ def history_push(hist, obs, done):
     return torch.where(done.to(torch.bool)[:, None], fresh, shifted)
 
 
+NORM_EPS = pol.NORM_EPS            # rstd = 1 / (sqrt(var) + eps), rsl_rl's EmpiricalNormalization: at most 100
+NORM_KEYS = ("count", "mean", "var")
+
+
+class RunningNorm(object):
+    """Running mean / variance of `dim` network inputs and the normaliser (x - mean) * rstd they define, rstd = 1 / (sqrt(var) + eps).
+
+    The statistics are ONE record of 4 + 3 dim 32-bit words (include/openroborl_learner.h: an int64 count and pad, then mean, var, rstd), on
+    the GPU at a fixed address: update() is orr_running_stats_update on it (one pass over the batch, merged by the parallel formula, no host
+    round trip), and whoever folds or applies the normaliser inside a captured graph reads the same words after every update.  A record on
+    the CPU has the same layout; update() is then the torch statement of the same merge, in float64 on float32 inputs with float32
+    results - the yardstick of the kernel.  A fresh record is the identity: count 0, mean 0, var 1, rstd 1.  `frozen` makes update() a
+    no-op."""
+
+    def __init__(self, device, dim, eps=NORM_EPS):
+        import torch
+        from . import _abi
+        self.torch = torch
+        self.device = torch.device(device)
+        self.dim, self.eps = int(dim), float(np.float32(eps))
+        if self.dim < 4 or self.dim > 256 or self.dim % 4:
+            raise ValueError("RunningNorm: dim must be a multiple of 4 from 4 to 256, got %r" % (dim,))
+        if not (self.eps > 0.0 and math.isfinite(self.eps)):
+            raise ValueError("RunningNorm: eps must be positive and finite")
+        self.rec = torch.zeros(_abi.running_stats_floats(self.dim), dtype=torch.float32, device=self.device)
+        om, ov, orr = _abi.running_stats_offsets(self.dim)
+        self.count_word = self.rec[:2].view(torch.int64)          # [1]
+        self.mean, self.var, self.rstd = self.rec[om:om + self.dim], self.rec[ov:ov + self.dim], self.rec[orr:orr + self.dim]
+        self.var.fill_(1.0)
+        self.rstd.fill_(1.0)
+        self.frozen = False
+        self._partials = None
+
+    @property
+    def count(self):
+        """Rows seen so far - a device read."""
+        return int(self.count_word.item())
+
+    def _check(self, x, name):
+        t = self.torch
+        if x.dtype != t.float32 or x.dim() != 2 or x.shape[1] != self.dim or x.shape[0] < 1 or x.device != self.rec.device or not x.is_contiguous():
+            raise ValueError("RunningNorm: %s must be a contiguous float32 [n, %d] tensor on %s" % (name, self.dim, self.rec.device))
+
+    def _rstd_of(self, var):
+        """float32 var -> float32 rstd, the kernel's arithmetic: float64 on the stored float32 value, rounded once."""
+        return (1.0 / (var.double().sqrt() + self.eps)).float()
+
+    def update(self, x):
+        """Merge the moments of x [n, dim] into the record.  Returns self."""
+        if self.frozen:
+            return self
+        t = self.torch
+        x = x.detach()
+        self._check(x, "x")
+        n = int(x.shape[0])
+        with t.no_grad():
+            if x.is_cuda:
+                import ctypes as C
+                from . import _lib
+                L = _lib.load()
+                need = int(L.orr_running_stats_partials(n, self.dim))
+                if self._partials is None or self._partials.numel() < need:
+                    self._partials = t.empty(need, dtype=t.float32, device=self.rec.device)
+                _lib.check(L.orr_running_stats_update(x.data_ptr(), n, self.dim, self.eps, self.rec.data_ptr(), self._partials.data_ptr(),
+                                                      C.c_void_p(t.cuda.current_stream(self.rec.device).cuda_stream)), L)
+                return self
+            xd = x.double()
+            mean_b = xd.mean(dim=0)
+            m2_b = ((xd - mean_b) ** 2).sum(dim=0)
+            na = int(self.count_word.item())
+            if na > 0:
+                tot = float(na + n)
+                delta = mean_b - self.mean.double()
+                m2_b = self.var.double() * float(na) + m2_b + delta * delta * (float(na) * float(n) / tot)
+                mean_b = self.mean.double() + delta * (float(n) / tot)
+            self.mean.copy_(mean_b.float())
+            self.var.copy_((m2_b / float(max(na, 0) + n)).float())
+            self.rstd.copy_(self._rstd_of(self.var))
+            self.count_word.fill_(max(na, 0) + n)
+        return self
+
+    def apply(self, x):
+        """(x - mean) * rstd as a torch expression, float32, two roundings: the reference of orr_normalize_rows and of the folded layer."""
+        return (x - self.mean) * self.rstd
+
+    def normalize(self, x, out=None):
+        """(x - mean) * rstd into `out` (default: a new tensor; `out` may be x).  On the GPU one orr_normalize_rows launch."""
+        t = self.torch
+        self._check(x, "x")
+        if out is None:
+            out = t.empty_like(x)
+        else:
+            self._check(out, "out")
+        with t.no_grad():
+            if x.is_cuda:
+                import ctypes as C
+                from . import _lib
+                L = _lib.load()
+                _lib.check(L.orr_normalize_rows(x.data_ptr(), int(x.shape[0]), self.dim, self.mean.data_ptr(), self.rstd.data_ptr(), out.data_ptr(),
+                                                C.c_void_p(t.cuda.current_stream(self.rec.device).cuda_stream)), L)
+            else:
+                out.copy_(self.apply(x))
+        return out
+
+    def state_dict(self):
+        """{"count": int64 [], "mean": float32 [dim], "var": float32 [dim], "eps": float32 []}; rstd follows from var and eps."""
+        return {"count": np.asarray(self.count, dtype=np.int64), "mean": self.mean.detach().cpu().numpy().copy(),
+                "var": self.var.detach().cpu().numpy().copy(), "eps": np.asarray(self.eps, dtype=np.float32)}
+
+    def load_state_dict(self, d):
+        t = self.torch
+        mean, var = (np.asarray(d[k], dtype=np.float32).reshape(-1) for k in ("mean", "var"))
+        if mean.shape != (self.dim,) or var.shape != (self.dim,) or not (var >= 0.0).all() or int(np.asarray(d["count"]).reshape(-1)[0]) < 0:
+            raise ValueError("RunningNorm: statistics of %d columns with var >= 0 and count >= 0 expected" % self.dim)
+        if "eps" in d:
+            self.eps = float(np.float32(np.asarray(d["eps"]).reshape(-1)[0]))
+        with t.no_grad():
+            self.mean.copy_(t.from_numpy(mean))
+            self.var.copy_(t.from_numpy(var))
+            self.rstd.copy_(self._rstd_of(self.var))
+            self.count_word.fill_(int(np.asarray(d["count"]).reshape(-1)[0]))
+        return self
+
+
+def _norm_state(params, prefix):
+    """The statistics a parameter dict carries under `prefix`/ (policy.save_parameters_zip), or None."""
+    if params is None or prefix + "/count" not in params:
+        return None
+    return {k: params["%s/%s" % (prefix, k)] for k in NORM_KEYS + ("eps",) if "%s/%s" % (prefix, k) in params}
+
+
+def _no_obs_norm(model, who):
+    if getattr(model, "obs_norm", None) is not None:
+        raise ValueError("%s: a model with an observation normaliser (ActorCritic(obs_norm=True)) is trained by PPO / learner_hip.FusedPPO; "
+                         "normalisers for the history and distillation learners are not built" % who)
+
+
 def _no_history(model, who):
     if getattr(model, "history", 0):
         raise ValueError("%s: a history policy (history = %d) is trained by PPOHistory / learner_hip.FusedPPOHistory (PPO with the critic on the "
@@ -223,10 +360,17 @@ class ActorCritic(object):
     learn_std = True adds model/pi/logstd:0 [1, 12], filled with log(std): a state-independent log-std that PPO / learner_hip.FusedPPO train
     (with an entropy bonus, ent_coef).  act() then samples mean + exp(log_std) * noise and log_prob() is the per-dimension Gaussian's.  It is
     filled, not drawn: every other parameter is what it is without, draw for draw.  With `params` the presence of the key decides.  `log_std`
-    is the device tensor, and the one thing rollout and update paths read; `std` is then the twelve values on the host, for logging only."""
+    is the device tensor, and the one thing rollout and update paths read; `std` is then the twelve values on the host, for logging only.
+
+    obs_norm = True puts a running normaliser in front of both nets: `obs_norm`, a RunningNorm over the 160 observation words, and with
+    priv_dim `priv_norm` over the 48 of the privileged row.  mean(), value(), log_prob() and the torch path of act() normalise what they
+    are given, (x - mean) * rstd spelled out; the fused path runs on raw inputs with the normaliser folded into the packed layer 0
+    (orr_policy_pack_norm).  The statistics are not parameters: nothing trains them, update_obs_norm() merges a rollout segment into them,
+    state_dict() carries them as obs_norm/count, /mean, /var, /eps (priv_norm/*), and with `params` their presence decides.  A history
+    policy with obs_norm is refused."""
 
     def __init__(self, device, obs_dim=160, act_dim=12, hidden=(512, 256), std=pol.PI_STD, params=None, seed=0, priv_dim=0, actor_priv_dim=0,
-                 history=0, learn_std=False):
+                 history=0, learn_std=False, obs_norm=False):
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -268,9 +412,28 @@ class ActorCritic(object):
             if not self._std > 0.0:
                 raise ValueError("learn_std needs std > 0, got %r" % (std,))
             self.p[LOGSTD] = torch.full((1, act_dim), math.log(self._std), dtype=torch.float32, device=self.device)
+        # obs_norm: a RunningNorm over the 160 observation words, and one over the privileged row of a model that reads it.  With `params`
+        # the presence of obs_norm/count decides, and the statistics are the file's.  No draw: every parameter is what it is without
+        obs_state, priv_state = _norm_state(params, "obs_norm"), _norm_state(params, "priv_norm")
+        if params is not None:
+            obs_norm = obs_state is not None
+        self.obs_norm = self.priv_norm = None
+        if obs_norm:
+            if self.history:
+                raise ValueError("obs_norm with a history policy is not built: the encoder's frames are a subset of the observation and would "
+                                 "need the same statistics; train the history policy on raw observations")
+            self.obs_norm = RunningNorm(self.device, obs_dim)
+            if obs_state is not None:
+                self.obs_norm.load_state_dict(obs_state)
+            if self.priv_dim:
+                self.priv_norm = RunningNorm(self.device, self.priv_dim)
+                if priv_state is not None:
+                    self.priv_norm.load_state_dict(priv_state)
         self.extra = {}            # variables of a loaded zip that this learner does not train (model/q/*): re-emitted by state_dict()
         if params is not None:
             for k, v in params.items():
+                if k.startswith(("obs_norm/", "priv_norm/")):
+                    continue
                 if k in self.p:
                     self.p[k].data.copy_(torch.as_tensor(np.asarray(v), dtype=torch.float32))
                 else:
@@ -310,9 +473,23 @@ class ActorCritic(object):
         """Route act() through the fused matrix-core forward pass (csrc/orr_policy.hip).  The packed weight copy is
         refreshed lazily after mark_updated() (the learner calls it after every optimiser step)."""
         from . import policy_hip
-        self.fused = policy_hip.FusedActorCritic(self.p, self.device, std=self._std)
+        self.fused = policy_hip.FusedActorCritic(self.p, self.device, std=self._std, obs_norm=self.obs_norm, priv_norm=self.priv_norm)
         self._fused_dirty = False
         return self
+
+    def update_obs_norm(self, obs, priv=None):
+        """Merge a rollout segment into the statistics: obs [T N, 160] (and priv [T N, 48] for a model that reads the row), one
+        orr_running_stats_update per record on the GPU.  Call it AFTER the learner's update - old log-probabilities, old values and the
+        learner's first forward pass must all see the function the rollout ran - and mark_updated() behind it: the fused forward pass
+        folds the new statistics into layer 0 at its next refresh()."""
+        if self.obs_norm is None:
+            raise ValueError("this model has no observation normaliser (obs_norm = False)")
+        if (priv is not None) != (self.priv_norm is not None):
+            raise ValueError("priv is needed by a model that normalises the privileged row (priv_dim = %d) and by no other" % pol.PRIV_DIM)
+        self.obs_norm.update(obs)
+        if priv is not None:
+            self.priv_norm.update(priv)
+        self._fused_dirty = True
 
     def mark_updated(self):
         self._fused_dirty = True
@@ -337,7 +514,15 @@ class ActorCritic(object):
     def _actor_input(self, obs, priv):
         if (priv is not None) != (self.actor_priv_dim > 0):
             raise ValueError("priv is needed by a privileged actor (actor_priv_dim = %d) and by no other" % pol.PRIV_DIM)
+        obs, priv = self._normalized(obs, priv)
         return obs if priv is None else self.torch.cat((obs, priv), dim=1)
+
+    def _normalized(self, obs, priv):
+        """What layer 0 reads of (obs, priv): themselves, or with obs_norm (x - mean) * rstd of each, spelled out in torch - the reference of
+        the fused forward pass's folded layer 0 and of the learners' normalised batch."""
+        if self.obs_norm is None:
+            return obs, priv
+        return self.obs_norm.apply(obs), (None if priv is None else self.priv_norm.apply(priv))
 
     def actor_priv(self, priv):
         """What mean() and log_prob() take as `priv` when the caller holds the critic's: the vector for a privileged actor, None for a plain one."""
@@ -365,6 +550,7 @@ class ActorCritic(object):
     def _critic_input(self, obs, priv):
         if (priv is not None) != (self.priv_dim > 0):
             raise ValueError("priv is needed by a privileged critic (priv_dim = %d) and by no other" % pol.PRIV_DIM)
+        obs, priv = self._normalized(obs, priv)
         return obs if priv is None else self.torch.cat((obs, priv), dim=1)
 
     def value(self, obs, priv=None):
@@ -430,6 +616,9 @@ class ActorCritic(object):
         d.update(self.extra)
         if not self.learn_std:      # carried from a learn-std teacher (train.py: history_student) but not sampled with: a zip that held it would
             d.pop(LOGSTD, None)     # reload as a learn-std policy with the teacher's stds, not the fixed std this model was rolled out with
+        for prefix, norm in (("obs_norm", self.obs_norm), ("priv_norm", self.priv_norm)):
+            if norm is not None:
+                d.update({"%s/%s" % (prefix, k): v for k, v in norm.state_dict().items()})
         return d
 
 

@@ -6,6 +6,7 @@ leaves the GPU.  Counterpart of `python3 OpenRoboRL/run.py --task imitation_lear
   python train.py --task imitation_learning_laikago --iters 200
   python train.py --task imitation_learning_laikago --iters 200 --learn-std --ent-coef 0.01   (a learned exploration width, entropy / KL / clip fraction in the log)
   python train.py --task imitation_learning_laikago --iters 200 --max-grad-norm 0.5 --lr-schedule linear --kl-target 0.01   (update controls on the device)
+  python train.py --task imitation_learning_laikago --iters 200 --obs-norm --save normed.zip --save-folded plain.zip   (running observation normalisation, folded into layer 0)
   python train.py --task imitation_learning_laikago --iters 200 --privileged-critic --push 0.02,0.2,0.5   (asymmetric actor-critic)
   python train.py --task imitation_learning_laikago --iters 200 --privileged-actor --push 0.02,0.2,0.5 --save teacher.zip   (a teacher)
   python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --push 0.02,0.2,0.5 --save student.zip   (its student)
@@ -75,6 +76,28 @@ def control_record(learner):
     c = learner.control_stats()
     return {"grad_norm": round(c["grad_norm_mean"], 5), "grad_norm_max": round(c["grad_norm_max"], 5), "clipped": c["clipped"],
             "skipped_nonfinite": c["skipped_nonfinite"], "skipped_kl": c["skipped_kl"], "lr_mult": round(c["lr_mult"] * c["kl_lr_mult"], 6)}
+
+
+def obs_norm_check(args, world):
+    """--obs-norm and its flags against the modes that have no normaliser; SystemExit with the reason."""
+    if not args.obs_norm:
+        if args.obs_norm_freeze_after is not None or args.save_folded:
+            raise SystemExit("train.py: --obs-norm-freeze-after / --save-folded belong to --obs-norm")
+        return
+    if world > 1:
+        raise SystemExit("train.py: --obs-norm runs on one rank: every rank would keep the statistics of its own shard and the replicas would "
+                         "no longer be one policy (merging the records over ranks is not built)")
+    if args.distill or args.history or args.history_ppo:
+        raise SystemExit("train.py: --obs-norm belongs to PPO on a plain, privileged-critic or privileged-actor policy; the history and "
+                         "distillation learners have no normaliser")
+    if args.obs_norm_freeze_after is not None and args.obs_norm_freeze_after < 0:
+        raise SystemExit("train.py: --obs-norm-freeze-after must not be negative")
+
+
+def obs_norm_record(model):
+    """What the log line gains with --obs-norm: the rows behind the statistics and the range of 1 / (sqrt(var) + eps) (one device read)."""
+    rstd = model.obs_norm.rstd
+    return {"obs_norm_count": model.obs_norm.count, "obs_rstd_min": round(float(rstd.min()), 4), "obs_rstd_max": round(float(rstd.max()), 4)}
 
 
 def main():
@@ -170,6 +193,17 @@ def main():
                     help="the std of the action noise; with --learn-std where log-std starts (default 0.125, the reference's pi_init_std)")
     ap.add_argument("--log-std-bounds", type=float, nargs=2, metavar=("LO", "HI"), default=None,
                     help="--learn-std: log-std is clamped to [LO, HI] after every optimiser step (default log 0.01, log 1)")
+    ap.add_argument("--obs-norm", action="store_true",
+                    help="running mean / std normalisation of the network inputs (the 160 observation words; with --privileged-critic / "
+                         "--privileged-actor the 48 privileged ones too), on the device: the statistics are frozen from the start of a rollout to "
+                         "the end of its update, then the segment is merged into them (one pass) and folded into the packed layer 0 of the fused "
+                         "forward pass, which runs on raw observations as before.  One extra segment before the first iteration seeds them.  "
+                         "The log gains obs_norm_count, obs_rstd_min, obs_rstd_max; --save writes the statistics next to the weights (loads here: "
+                         "--eval, --model-file).  One rank")
+    ap.add_argument("--obs-norm-freeze-after", type=int, default=None, metavar="ITERS", help="--obs-norm: no update of the statistics after this many iterations")
+    ap.add_argument("--save-folded", default="", metavar="PATH",
+                    help="--obs-norm: also write a zip WITHOUT statistics whose layer-0 matrices and biases carry the normaliser: the same "
+                         "function on raw observations; for a plain policy a zip the reference's run.py loads")
     control_args(ap)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log", default="")
@@ -220,6 +254,7 @@ def main():
         raise SystemExit("train.py: --ent-coef / --log-std-bounds belong to --learn-std")
     privileged = args.privileged_critic or bool(args.distill) or args.history_ppo       # somebody reads env.privileged_obs
     rank, world, local = odist.init_from_env()
+    obs_norm_check(args, world)
     if args.clip_curriculum is not None and world > 1:
         raise SystemExit("train.py: --clip-curriculum runs on one rank: each rank would adapt to its own episodes and the shards would no "
                          "longer draw what one env draws (merging the statistics over ranks is not built)")
@@ -248,7 +283,9 @@ def main():
         wide = args.privileged_actor or args.history_ppo
         model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic or wide else 0,
                                 actor_priv_dim=pol.PRIV_DIM if wide else 0, std=args.init_std, learn_std=args.learn_std,
-                                history=ppo.HISTORY_STEPS if args.history_ppo else 0)
+                                history=ppo.HISTORY_STEPS if args.history_ppo else 0, obs_norm=args.obs_norm)
+    if (model.obs_norm is not None) != args.obs_norm:
+        raise SystemExit("train.py: --model-file has %s, --obs-norm says otherwise" % ("a normaliser's statistics" if model.obs_norm is not None else "no statistics"))
     if model.learn_std != args.learn_std and not args.distill:
         raise SystemExit("train.py: --model-file has %s, --learn-std says otherwise" % ("a learned log-std" if model.learn_std else "no log-std"))
     if args.history_ppo:
@@ -288,6 +325,19 @@ def main():
     priv = None                           # --privileged-critic: the privileged observation that belongs to `obs` (None: right after the reset)
     # static rollout buffers + the segment replayed as one hipGraph (fused policy only); --torch-policy keeps the eager collector
     collector = None if args.torch_policy else rollout.GraphRollout(env, model, args.horizon)
+
+    def merge_segment(buf):
+        """--obs-norm: the segment into the statistics, and the fold into the fused layer 0 at the next refresh; after the update, never before"""
+        T, n = buf["rewards"].shape
+        model.update_obs_norm(buf["obs"].reshape(T * n, -1), *((buf["priv"].reshape(T * n, -1),) if model.priv_norm is not None else ()))
+        model.mark_updated()
+    if args.obs_norm and model.obs_norm.count == 0:
+        # one segment whose only use is to seed the statistics: the policy never acts, and the learner never learns, on the identity
+        buf = (collector.collect(obs, generator=gen, priv=priv) if collector
+               else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv))
+        obs, priv, first_starts = buf["last_obs"], buf.get("last_priv"), buf["dones"][-1].clone()
+        merge_segment(buf)
+        odist.gather_env_episodes(env, args.horizon)       # its episodes are not the first iteration's
     for it in range(args.iters):
         buf = (collector.collect(obs, generator=gen, priv=priv) if collector
                else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv))
@@ -307,6 +357,8 @@ def main():
                                 ret.reshape(-1), old_logp=buf["logp"].reshape(-1) if "logp" in buf else None,
                                 epochs=args.epochs, generator=gen, priv=buf["priv"].reshape(T * n, -1) if model.priv_dim else None)
         surr, vf = losses[0], losses[1]      # --learn-std: three more, ppo.STAT_NAMES
+        if args.obs_norm and (args.obs_norm_freeze_after is None or it < args.obs_norm_freeze_after):
+            merge_segment(buf)
         samples += T * n * world
         # (> 1 rank, or ORR_FORCE_DIST=1: the one-rank rehearsal of the several-ranks path on RCCL runs the check too)
         if (world > 1 or os.environ.get("ORR_FORCE_DIST", "0") == "1") and args.sync_check_every > 0 and it % args.sync_check_every == args.sync_check_every - 1 and hasattr(learner, "check_synced"):
@@ -331,6 +383,8 @@ def main():
                 rec.update({"std_min": round(float(std.min()), 5), "std_max": round(float(std.max()), 5)})
             if control_on(args):
                 rec.update(control_record(learner))
+            if args.obs_norm:
+                rec.update(obs_norm_record(model))
             if by_clip is not None:
                 rec["ep_ret_mean_by_clip"] = {clip_name(env, c): round(r, 2) for c, (r, _) in sorted(by_clip.items())}
             if args.clip_curriculum is not None or args.clip_weights is not None:
@@ -343,6 +397,8 @@ def main():
             print(json.dumps(rec), flush=True)
     if rank == 0 and args.save:
         pol.save_parameters_zip(args.save, model.state_dict())
+    if rank == 0 and args.save_folded:
+        pol.save_folded(args.save_folded, model.state_dict())
     if rank == 0 and args.log:
         with open(args.log, "w") as f:
             json.dump(log, f, indent=1)
@@ -355,6 +411,12 @@ def history_student(args, torch, pol, ppo, dev, path=None, fused=True, **model_k
     """--distill TEACHER.zip --history: the teacher's parameters + a fresh encoder (seeded by --seed), on the fused path.  --history-ppo with a
     teacher's --model-file (`path`): the same rule, the model's std arguments in model_kw."""
     params = pol.load_parameters(path or args.distill)
+    if any(k.startswith(pol.NORM_PREFIXES) for k in params):
+        # the teacher's layer 0 expects normalised inputs, and a history policy has no normaliser: copying its weights would run them on raw
+        # observations and on the encoder's raw estimate, without a word
+        raise SystemExit("train.py: %s is a teacher trained with --obs-norm; a history policy with an observation normaliser is not built "
+                         "(the encoder's frames are a subset of the observation): train the teacher without --obs-norm"
+                         % (path or args.distill))
     if np.shape(params["model/pi_fc0/w:0"])[0] != 160 + pol.PRIV_DIM:
         raise SystemExit("train.py: %s needs a teacher with a privileged actor (--privileged-actor)" % ("--history-ppo --model-file" if path else "--history"))
     student = ppo.ActorCritic(dev, seed=args.seed, priv_dim=pol.PRIV_DIM, actor_priv_dim=pol.PRIV_DIM, history=ppo.HISTORY_STEPS, **model_kw)
