@@ -7,6 +7,7 @@
 // atomics (column sums go through per-block partials that a second small launch adds in a fixed order).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/openroborl_learner.h"
 
@@ -27,6 +28,35 @@ __device__ inline float wave_sum(float x) {
   return x;
 }
 
+// ---- what the one-thread-per-sample loss heads and their single-workgroup finish kernels share -----------------------------------------
+// The end of a head: a thread's USED sums -> the workgroup's row of partials [block][COLS], the columns from USED on zero.  A wave's sum per
+// column, lane 0 of each wave to LDS, one barrier, the four waves combined in a fixed order.
+template <int COLS, int USED>
+__device__ __forceinline__ void head_partials(const float (&acc)[USED], float* __restrict__ partials) {
+  __shared__ float red[kThreads / 64][COLS];
+#pragma unroll
+  for (int k = 0; k < USED; k++) {
+    const float s = wave_sum(acc[k]);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < COLS)
+    partials[(size_t)blockIdx.x * COLS + threadIdx.x] =
+        threadIdx.x < USED ? (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]) : 0.0f;
+}
+
+// The opening of a finish kernel (4 * COLS threads, thread = part * COLS + col): COLS columns x 4 interleaved row groups of the nblk rows,
+// combined in a fixed order.  The threads of part 0 get their column's total (the others 0) and route it to its output.
+template <int COLS>
+__device__ __forceinline__ float head_total(const float* __restrict__ partials, int nblk, int col, int part) {
+  __shared__ float red[4][COLS];
+  float s = 0.0f;
+  for (int b = part; b < nblk; b += 4) s += partials[(size_t)b * COLS + col];
+  red[part][col] = s;
+  __syncthreads();
+  return part == 0 ? (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]) : 0.0f;
+}
+
 // ---- loss head: one thread per sample --------------------------------------------------------------------------------------
 // d(-min(r A, clip(r) A)) / dr as autograd forms it (ppo.PPO.update): inside the clip range both branches are the same value and
 // together pass -A; outside it the clipped branch is constant, so -A passes only while the unclipped branch is the smaller one.
@@ -34,7 +64,6 @@ __global__ __launch_bounds__(kThreads) void ppo_head_kernel(const float* __restr
                                                             const float* __restrict__ batch, int M, float inv_var, float log_norm, float clip,
                                                             float vf_coef, float inv_m, float* __restrict__ g_mean,
                                                             float* __restrict__ g_value, float* __restrict__ partials) {
-  __shared__ float red[kThreads / 64][kHeadCols];
   const int i = blockIdx.x * kThreads + threadIdx.x;
   float acc[kHeadCols - 1];
 #pragma unroll
@@ -67,28 +96,14 @@ __global__ __launch_bounds__(kThreads) void ppo_head_kernel(const float* __restr
     g_value[i] = gv;
     acc[12] = gv; acc[13] = -fminf(s1, s2); acc[14] = dv * dv;
   }
-#pragma unroll
-  for (int k = 0; k < kHeadCols - 1; k++) {
-    const float s = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kHeadCols)
-    partials[(size_t)blockIdx.x * kHeadCols + threadIdx.x] =
-        threadIdx.x < kHeadCols - 1 ? (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]) : 0.0f;
+  head_partials<kHeadCols>(acc, partials);
 }
 
 __global__ __launch_bounds__(64) void ppo_head_finish_kernel(const float* __restrict__ partials, int nblk, float inv_m, float* __restrict__ gb_mean,
                                                              float* __restrict__ gb_value, float* __restrict__ stats) {
-  // 16 columns x 4 interleaved row groups, combined in a fixed order
-  __shared__ float red[4][kHeadCols];
   const int col = threadIdx.x & 15, part = threadIdx.x >> 4;
-  float s = 0.0f;
-  for (int b = part; b < nblk; b += 4) s += partials[(size_t)b * kHeadCols + col];
-  red[part][col] = s;
-  __syncthreads();
+  const float t = head_total<kHeadCols>(partials, nblk, col, part);
   if (part == 0) {
-    const float t = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
     if (col < kAct) gb_mean[col] = t;
     else if (col == 12) gb_value[0] = t;
     else if (col == 13) stats[0] = t * inv_m;
@@ -115,7 +130,6 @@ __global__ __launch_bounds__(kThreads) void ppo_head_logstd_kernel(const float* 
                                                                    const float* __restrict__ batch, const float* __restrict__ log_std, int M,
                                                                    float clip, float vf_coef, float inv_m, float* __restrict__ g_mean,
                                                                    float* __restrict__ g_value, float* __restrict__ partials) {
-  __shared__ float red[kThreads / 64][kLsCols];
   const int i = blockIdx.x * kThreads + threadIdx.x;
   float acc[kLsUsed];
 #pragma unroll
@@ -158,30 +172,16 @@ __global__ __launch_bounds__(kThreads) void ppo_head_logstd_kernel(const float* 
     acc[12] = gv; acc[13] = -fminf(s1, s2); acc[14] = dv * dv;
     acc[15] = (ratio - 1.0f) - log_ratio; acc[16] = inside ? 0.0f : 1.0f;
   }
-#pragma unroll
-  for (int k = 0; k < kLsUsed; k++) {
-    const float s = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kLsCols)
-    partials[(size_t)blockIdx.x * kLsCols + threadIdx.x] =
-        threadIdx.x < kLsUsed ? (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]) : 0.0f;
+  head_partials<kLsCols>(acc, partials);
 }
 
 __global__ __launch_bounds__(4 * kLsCols) void ppo_head_logstd_finish_kernel(const float* __restrict__ partials, int nblk, float m, float ent_coef,
                                                                              const float* __restrict__ log_std, float* __restrict__ gb_mean,
                                                                              float* __restrict__ gb_value, float* __restrict__ g_logstd,
                                                                              float* __restrict__ stats) {
-  // 32 columns x 4 interleaved row groups, combined in a fixed order
-  __shared__ float red[4][kLsCols];
   const int col = threadIdx.x & (kLsCols - 1), part = threadIdx.x / kLsCols;
-  float s = 0.0f;
-  for (int b = part; b < nblk; b += 4) s += partials[(size_t)b * kLsCols + col];
-  red[part][col] = s;
-  __syncthreads();
+  const float t = head_total<kLsCols>(partials, nblk, col, part);
   if (part == 0) {
-    const float t = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
     const float inv_m = 1.0f / m;
     if (col < kAct) gb_mean[col] = t;
     else if (col == 12) gb_value[0] = t;
@@ -221,7 +221,6 @@ __global__ __launch_bounds__(kThreads) void gauss_prepare_kernel(const float* no
 // ---- distillation loss head: one thread per sample, the same partials layout (columns 0..11 the bias gradient, 12 the squared error) --------
 __global__ __launch_bounds__(kThreads) void distill_head_kernel(const float* __restrict__ mean, const float* __restrict__ target, int M, float inv_m,
                                                                 float* __restrict__ g_mean, float* __restrict__ partials) {
-  __shared__ float red[kThreads / 64][kHeadCols];
   const int i = blockIdx.x * kThreads + threadIdx.x;
   float acc[kAct + 1];
 #pragma unroll
@@ -238,28 +237,14 @@ __global__ __launch_bounds__(kThreads) void distill_head_kernel(const float* __r
     f4* o4 = reinterpret_cast<f4*>(g_mean + (size_t)i * kAct);
     o4[0] = f4{acc[0], acc[1], acc[2], acc[3]}; o4[1] = f4{acc[4], acc[5], acc[6], acc[7]}; o4[2] = f4{acc[8], acc[9], acc[10], acc[11]};
   }
-#pragma unroll
-  for (int k = 0; k < kAct + 1; k++) {
-    const float s = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kHeadCols)
-    partials[(size_t)blockIdx.x * kHeadCols + threadIdx.x] =
-        threadIdx.x < kAct + 1 ? (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]) : 0.0f;
+  head_partials<kHeadCols>(acc, partials);
 }
 
 __global__ __launch_bounds__(64) void distill_head_finish_kernel(const float* __restrict__ partials, int nblk, float inv_m, float* __restrict__ gb_mean,
                                                                  float* __restrict__ stats) {
-  // like ppo_head_finish_kernel: 16 columns x 4 interleaved row groups, combined in a fixed order
-  __shared__ float red[4][kHeadCols];
   const int col = threadIdx.x & 15, part = threadIdx.x >> 4;
-  float s = 0.0f;
-  for (int b = part; b < nblk; b += 4) s += partials[(size_t)b * kHeadCols + col];
-  red[part][col] = s;
-  __syncthreads();
+  const float t = head_total<kHeadCols>(partials, nblk, col, part);
   if (part == 0) {
-    const float t = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
     if (col < kAct) gb_mean[col] = t;
     else if (col == kAct) stats[0] = t * inv_m;
   }
@@ -694,13 +679,37 @@ inline bool stats_dims_ok(int d) { return d >= 4 && d <= 256 && (d % 4) == 0; }
 inline int nblocks_rows(int m) { return (m + kRowsPerBlock - 1) / kRowsPerBlock; }
 inline bool cols_ok(int c) { return c >= 4 && (c % 4) == 0 && (c / 4) <= kThreads && (kThreads % (c / 4)) == 0; }
 
+// behind an entry point's launches: 0, or the entry's failure with the runtime's error behind `who`
+int launched(const char* who) {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? orr_fail(-2, who, e) : 0;
+}
+
+// the checks and the launch of orr_adam_step (ctl NULL: adam_kernel) and of orr_adam_step_ctl (which has looked at its ctl: adam_ctl_kernel)
+int adam_step(const char* who, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+              float grad_scale, int32_t flags, int32_t* state, const orr_update_ctl* ctl, void* stream) {
+  char msg[64];
+  const auto fail = [&](const char* what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return orr_fail(-1, msg, hipSuccess); };
+  if (!p || !g || !m || !v || !state || n <= 0) return fail("bad argument");
+  if (flags & ~ORR_ADAM_MPI_EPSILON) return fail("unknown flag");
+  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || !aligned16(ctl)) return fail("buffers must be 16-byte aligned");
+  const long long per_block = 4LL * kAdamThreads;
+  const dim3 grid((unsigned)((n + per_block - 1) / per_block));
+  if (ctl)
+    hipLaunchKernelGGL(adam_ctl_kernel, grid, dim3(kAdamThreads), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr, beta1, beta2, eps, grad_scale,
+                       (int)flags, (int*)state, ctl);
+  else
+    hipLaunchKernelGGL(adam_kernel, grid, dim3(kAdamThreads), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr, beta1, beta2, eps, grad_scale,
+                       (int)flags, (int*)state);
+  snprintf(msg, sizeof(msg), "%s: launch", who);
+  return launched(msg);
+}
+
 int launch_finish(FinishJobs& J, int n_jobs, hipStream_t st, const char* who) {
   J.first[0] = 0;
   for (int j = 0; j < n_jobs; j++) J.first[j + 1] = J.first[j] + (J.nblk[j] <= kFewRows ? (J.cols[j] + kThreads - 1) / kThreads : (J.cols[j] + 15) / 16);
   hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)J.first[n_jobs]), dim3(kThreads), 0, st, J, n_jobs);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, who, e);
-  return 0;
+  return launched(who);
 }
 
 }  // namespace
@@ -728,9 +737,7 @@ int32_t orr_ppo_head(const float* mean, const float* value, const float* batch, 
   hipLaunchKernelGGL(ppo_head_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, st, mean, value, batch, (int)m, 1.0f / var, log_norm, clip, vf_coef,
                      1.0f / (float)m, g_mean, g_value, workspace);
   hipLaunchKernelGGL(ppo_head_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, nblk, 1.0f / (float)m, gb_mean, gb_value, stats);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_ppo_head: launch", e);
-  return 0;
+  return launched("orr_ppo_head: launch");
 }
 
 int32_t orr_ppo_head_logstd(const float* mean, const float* value, const float* batch, const float* log_std, int32_t m, float clip, float vf_coef,
@@ -747,9 +754,7 @@ int32_t orr_ppo_head_logstd(const float* mean, const float* value, const float* 
                      1.0f / (float)m, g_mean, g_value, workspace);
   hipLaunchKernelGGL(ppo_head_logstd_finish_kernel, dim3(1), dim3(4 * kLsCols), 0, st, (const float*)workspace, nblk, (float)m, ent_coef, log_std,
                      gb_mean, gb_value, g_logstd, stats);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_ppo_head_logstd: launch", e);
-  return 0;
+  return launched("orr_ppo_head_logstd: launch");
 }
 
 int32_t orr_gauss_prepare(const float* noise, const float* log_std, float* scaled, float* logp, int32_t n, void* stream) {
@@ -761,9 +766,7 @@ int32_t orr_gauss_prepare(const float* noise, const float* log_std, float* scale
     return orr_fail(-1, "orr_gauss_prepare: scaled must be noise itself or not overlap it", hipSuccess);
   hipLaunchKernelGGL(gauss_prepare_kernel, dim3((unsigned)(((long long)n + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, noise,
                      log_std, scaled, logp, (long long)n);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_gauss_prepare: launch", e);
-  return 0;
+  return launched("orr_gauss_prepare: launch");
 }
 
 int32_t orr_distill_head(const float* mean, const float* target, int32_t m, float* g_mean, float* gb_mean, float* stats, float* workspace,
@@ -774,9 +777,7 @@ int32_t orr_distill_head(const float* mean, const float* target, int32_t m, floa
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(distill_head_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, st, mean, target, (int)m, 1.0f / (float)m, g_mean, workspace);
   hipLaunchKernelGGL(distill_head_finish_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, nblk, 1.0f / (float)m, gb_mean, stats);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_distill_head: launch", e);
-  return 0;
+  return launched("orr_distill_head: launch");
 }
 
 int32_t orr_regress_head(const float* pred, const float* target, int32_t m, int32_t c, float* g, float* gb, float* stats, float* workspace,
@@ -789,8 +790,7 @@ int32_t orr_regress_head(const float* pred, const float* target, int32_t m, int3
   hipStream_t st = (hipStream_t)stream;
   float* loss_part = workspace + (size_t)nblk * c;                // [nblk][c] column sums, then [nblk] shares of the loss
   hipLaunchKernelGGL(regress_head_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, st, pred, target, (int)m, (int)c, 1.0f / (float)m, g, workspace, loss_part);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_regress_head: launch", e);
+  if (const int rc = launched("orr_regress_head: launch")) return rc;
   FinishJobs J{};
   J.partials[0] = workspace; J.out[0] = gb; J.nblk[0] = nblk; J.cols[0] = c;
   J.partials[1] = loss_part; J.out[1] = stats; J.nblk[1] = nblk; J.cols[1] = 1;
@@ -805,8 +805,7 @@ int32_t orr_relu_backward(float* g, const float* h, int32_t m, int32_t c, float*
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(relu_backward_kernel<0>, dim3((unsigned)nblk), dim3(kThreads), 0, st, g, h, (const float*)nullptr, (const float*)nullptr, (int)m,
                      (int)c, workspace, (float*)nullptr);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_relu_backward: launch", e);
+  if (const int rc = launched("orr_relu_backward: launch")) return rc;
   if (!gb) return 0;                                 // deferred: the caller sums workspace [rows][c] with orr_colsum_finish
   FinishJobs J{};
   J.partials[0] = workspace; J.out[0] = gb; J.nblk[0] = nblk; J.cols[0] = c;
@@ -828,8 +827,7 @@ int32_t orr_head_backward(const float* gy, int32_t k, const float* w, const floa
     hipLaunchKernelGGL(relu_backward_kernel<12>, dim3((unsigned)nblk), dim3(kThreads), 0, st, gz, h, gy, w, (int)m, (int)c, workspace, wpart);
   else
     hipLaunchKernelGGL(relu_backward_kernel<1>, dim3((unsigned)nblk), dim3(kThreads), 0, st, gz, h, gy, w, (int)m, (int)c, workspace, wpart);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_head_backward: launch", e);
+  if (const int rc = launched("orr_head_backward: launch")) return rc;
   if (!gb) return 0;                                 // deferred: workspace [rows][c] then [rows][c * k]
   FinishJobs J{};
   J.partials[0] = workspace; J.out[0] = gb; J.nblk[0] = nblk; J.cols[0] = c;
@@ -849,15 +847,7 @@ int32_t orr_colsum_finish(const orr_colsum_job* jobs, int32_t n_jobs, void* stre
 
 int32_t orr_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                       float grad_scale, int32_t flags, int32_t* state, void* stream) {
-  if (!p || !g || !m || !v || !state || n <= 0) return orr_fail(-1, "orr_adam_step: bad argument", hipSuccess);
-  if (flags & ~ORR_ADAM_MPI_EPSILON) return orr_fail(-1, "orr_adam_step: unknown flag", hipSuccess);
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v)) return orr_fail(-1, "orr_adam_step: buffers must be 16-byte aligned", hipSuccess);
-  const long long per_block = 4LL * kAdamThreads;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kAdamThreads), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr,
-                     beta1, beta2, eps, grad_scale, (int)flags, (int*)state);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_adam_step: launch", e);
-  return 0;
+  return adam_step("orr_adam_step", p, g, m, v, n, lr, beta1, beta2, eps, grad_scale, flags, state, nullptr, stream);
 }
 
 int32_t orr_sizeof_update_ctl(void) { return (int32_t)sizeof(orr_update_ctl); }
@@ -877,9 +867,7 @@ int32_t orr_update_control(const float* g, int64_t n, float pre_scale, float max
   hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nparts), dim3(kCtlThreads), 0, (hipStream_t)stream, g, (long long)n, partials);
   hipLaunchKernelGGL(update_control_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)partials, nparts, pre_scale, max_norm, kl, kl_stop,
                      kl_target, kl_lr_lo, kl_lr_hi, ctl);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_update_control: launch", e);
-  return 0;
+  return launched("orr_update_control: launch");
 }
 
 int64_t orr_sizeof_running_stats(int32_t d) { return stats_dims_ok(d) ? (int64_t)sizeof(float) * ORR_RUNNING_STATS_FLOATS(d) : -1; }
@@ -902,9 +890,7 @@ int32_t orr_running_stats_update(const float* x, int64_t n, int32_t d, float eps
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(running_stats_partial_kernel, dim3((unsigned)nparts), dim3(kStatThreads), 0, st, x, (long long)n, (int)d, partials);
   hipLaunchKernelGGL(running_stats_merge_kernel, dim3(1), dim3(kMergeThreads), 0, st, (const float*)partials, nparts, (long long)n, (int)d, eps, x, rec);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_running_stats_update: launch", e);
-  return 0;
+  return launched("orr_running_stats_update: launch");
 }
 
 int32_t orr_normalize_rows(const float* x, int64_t n, int32_t d, const float* mean, const float* rstd, float* out, void* stream) {
@@ -918,23 +904,13 @@ int32_t orr_normalize_rows(const float* x, int64_t n, int32_t d, const float* me
   const long long per_block = (long long)kThreads * kNormLoads, nblk = (quads + per_block - 1) / per_block;
   if (nblk > 0x7fffffffLL) return orr_fail(-1, "orr_normalize_rows: n too large", hipSuccess);
   hipLaunchKernelGGL(normalize_rows_kernel, dim3((unsigned)nblk), dim3(kThreads), 0, (hipStream_t)stream, x, quads, (int)(d / 4), mean, rstd, out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_normalize_rows: launch", e);
-  return 0;
+  return launched("orr_normalize_rows: launch");
 }
 
 int32_t orr_adam_step_ctl(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                           float grad_scale, int32_t flags, int32_t* state, const orr_update_ctl* ctl, void* stream) {
-  if (!p || !g || !m || !v || !state || !ctl || n <= 0) return orr_fail(-1, "orr_adam_step_ctl: bad argument", hipSuccess);
-  if (flags & ~ORR_ADAM_MPI_EPSILON) return orr_fail(-1, "orr_adam_step_ctl: unknown flag", hipSuccess);
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || !aligned16(ctl))
-    return orr_fail(-1, "orr_adam_step_ctl: buffers must be 16-byte aligned", hipSuccess);
-  const long long per_block = 4LL * kAdamThreads;
-  hipLaunchKernelGGL(adam_ctl_kernel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kAdamThreads), 0, (hipStream_t)stream, p, g, m, v,
-                     (long long)n, lr, beta1, beta2, eps, grad_scale, (int)flags, (int*)state, ctl);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return orr_fail(-2, "orr_adam_step_ctl: launch", e);
-  return 0;
+  if (!ctl) return orr_fail(-1, "orr_adam_step_ctl: bad argument", hipSuccess);
+  return adam_step("orr_adam_step_ctl", p, g, m, v, n, lr, beta1, beta2, eps, grad_scale, flags, state, ctl, stream);       // its alignment: there
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@ share stands once, in _FusedLearner:
     GEMMs written out by hand (no autograd graph) with the ReLU masks, the gradient through an output layer of fan-out 12 or 1 (no GEMM),
     every bias gradient and the loss head in a handful of HIP launches (7 per PPO minibatch) - autograd spends ~70 elementwise / reduction
     launches per minibatch on the same work, more GPU time than the GEMMs;
+  * the two chains a minibatch is made of, each as buffers / forward / backward: a 3-layer net (_mlp_*) and the history encoder (_enc_*,
+    the two history learners'); where a loss lands in the minibatch's own row of stats, P["jobs_s"][s] is that minibatch's job table;
   * one update driver: an epoch (gathers of all minibatches, forward, backward, Adam) is captured once and replayed - ~30 launches per
     minibatch cost no host time.  FusedPPO alone has ranks; several ranks: one graph per minibatch, the all-reduce (RCCL) and Adam between
     replays.  ORR_FORCE_DIST=1 with an initialised process group takes the several-ranks path even for ONE rank (a one-GPU box can then run
@@ -33,9 +35,9 @@ import ctypes as C
 import os
 
 from . import _abi, _lib
-from .policy import LOGSTD         # the learned log-std of ppo.ActorCritic(learn_std=True)
-
-from .ppo import _no_obs_norm      # the learners without a normalising fill() refuse a model with an observation normaliser
+from .actor_critic import LOG_STD_BOUNDS, LOGSTD     # LOGSTD: the learned log-std of ppo.ActorCritic(learn_std=True)
+# the argument checks the torch learners share; _no_obs_norm: the learners without a normalising fill() refuse a model with a normaliser
+from .update_control import KL_LR_BOUNDS, _control_args, _entropy_args, _no_obs_norm
 
 NETS = ("pi", "vf")
 
@@ -46,16 +48,15 @@ def _jobs(entries):
 
 
 class _FusedLearner(object):
-    """What the fused learners share: the flat buffers of the parameters `names` of `model`, Adam, the plan cache, the chain of a 3-layer
-    net and the update driver.  A learner adds its plan's buffers (_buffers), its _minibatch and its update."""
+    """What the fused learners share: the flat buffers of the parameters `names` of `model`, Adam, the plan cache, the chains of a 3-layer
+    net and of the history encoder and the update driver.  A learner adds its plan's buffers (_buffers), its _minibatch and its update."""
 
     def __init__(self, model, names, stats, lr, adam_eps, minibatch, betas, use_graph, mpi_adam_epsilon=False, max_grad_norm=None, device_lr=False,
                  kl_stop=None, kl_target=None, kl_lr_bounds=None):
         import torch
-        from . import ppo
         self.torch = torch
-        self.max_grad_norm, self.kl_stop, self.kl_target, self.kl_lr_bounds = ppo._control_args(type(self).__name__, max_grad_norm, kl_stop, kl_target,
-                                                                                                kl_lr_bounds or ppo.KL_LR_BOUNDS)
+        self.max_grad_norm, self.kl_stop, self.kl_target, self.kl_lr_bounds = _control_args(type(self).__name__, max_grad_norm, kl_stop, kl_target,
+                                                                                            kl_lr_bounds or KL_LR_BOUNDS)
         self.kl_on = self.kl_stop is not None or self.kl_target is not None
         control = self.max_grad_norm is not None or self.kl_on or bool(device_lr)
         self.model = model
@@ -123,10 +124,10 @@ class _FusedLearner(object):
         """Device address of minibatch s's approx_kl for the KL rules; None: no rule (the learners without a PPO loss head)."""
         return None
 
-    @staticmethod
-    def _need_gpu(model):
+    def _need_gpu(self, model):
         if model.device.type != "cuda":
-            raise RuntimeError("FusedPPO needs a GPU device (the torch reference is ppo.PPO)")
+            name = type(self).__name__
+            raise RuntimeError("%s needs a GPU device (the torch reference is ppo.%s)" % (name, name[len("Fused"):]))
 
     def _mark_updated(self):
         if hasattr(self.model, "mark_updated"):
@@ -219,6 +220,28 @@ class _FusedLearner(object):
         t.mm(P["gz2"], w["model/%s_fc1/w:0" % net].t(), out=P["gh1"])
         _lib.check(L.orr_relu_backward(P["gh1"].data_ptr(), h1.data_ptr(), M, 512, None, P["ws1" + sfx].data_ptr(), st), L)
         self._wgrad(x, P["gh1"], P["part0" + sfx], g["model/%s_fc0/w:0" % net])
+
+    # ---- the history encoder model/enc_*: 512 -> 256 -> 48, its buffers under the plan keys xh, he, z, g_z, g_he, ws1e, part0 ---------------
+    def _enc_buffers(self, P, f, split, rows):
+        """The encoder's activations and the partial sums of its backward pass; returns the jobs that finish enc_fc0's bias gradient and, when
+        split, its weight gradient.  enc_fc1's bias gradient is left by whoever produces g_z, the learner's loss head: a job of its own."""
+        M, g = P["M"], self.g
+        D, H, Z = _abi.HISTORY_DIM, 256, _abi.POLICY_PRIV_DIM
+        P.update({"xh": f(M, D), "he": f(M, H), "z": f(M, Z), "g_z": f(M, Z), "g_he": f(M, H), "ws1e": f(rows * H), "part0": f(16, D, H) if split else None})
+        return [(P["ws1e"], g["model/enc_fc0/b:0"], rows, H)] + ([(P["part0"], g["model/enc_fc0/w:0"], 16, D * H)] if split else [])
+
+    def _enc_forward(self, P):
+        t, w = self.torch, self.w
+        t._addmm_activation(w["model/enc_fc0/b:0"], P["xh"], w["model/enc_fc0/w:0"], out=P["he"])
+        t.addmm(w["model/enc_fc1/b:0"], P["he"], w["model/enc_fc1/w:0"], out=P["z"])
+
+    def _enc_backward(self, P, st):
+        """From P["g_z"] = d loss / d z [M, 48] to the encoder's weight gradients and the partial sums of enc_fc0's bias gradient."""
+        t, L, w, g = self.torch, self.L, self.w, self.g
+        t.mm(P["he"].t(), P["g_z"], out=g["model/enc_fc1/w:0"])
+        t.mm(P["g_z"], w["model/enc_fc1/w:0"].t(), out=P["g_he"])
+        _lib.check(L.orr_relu_backward(P["g_he"].data_ptr(), P["he"].data_ptr(), P["M"], 256, None, P["ws1e"].data_ptr(), st), L)
+        self._wgrad(P["xh"], P["g_he"], P["part0"], g["model/enc_fc0/w:0"])
 
     # ---- the update driver ----------------------------------------------------------------------------------------------
     def _epoch_eager(self, P, world, reduce):
@@ -321,12 +344,11 @@ class FusedPPO(_FusedLearner):
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
                  mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, max_grad_norm=None, device_lr=False, kl_stop=None,
                  kl_target=None, kl_lr_bounds=None):
-        from . import ppo
         self._need_gpu(model)
         if getattr(model, "history", 0) and not self._history:
             raise ValueError("FusedPPO: a history policy is trained by FusedPPOHistory (PPO with the critic on the true privileged row) or by "
                              "FusedDistillHistory")
-        self.learn_std, self.ent_coef, self.log_std_bounds = ppo._entropy_args(model, type(self).__name__, ent_coef, log_std_bounds or ppo.LOG_STD_BOUNDS)
+        self.learn_std, self.ent_coef, self.log_std_bounds = _entropy_args(model, type(self).__name__, ent_coef, log_std_bounds or LOG_STD_BOUNDS)
         self.clip, self.vf_coef = float(clip_param), float(vf_coef)
         self.group = group
         # a privileged critic (ppo.ActorCritic(priv_dim=48)): its layer 0 reads x | priv, [M, 160 + 48]; everything behind layer 0 and the
@@ -427,9 +449,7 @@ class FusedPPO(_FusedLearner):
             raise ValueError("FusedPPO: priv must have shape (%d, %d)" % (B, self.priv_dim))
 
         def fill(P):
-            logp = old_logp
-            if logp is None:
-                logp = self.model.log_prob(obs, actions, *((priv,) if self.actor_priv_dim else ()))
+            logp = self.model.log_prob(obs, actions, *((priv,) if self.actor_priv_dim else ())) if old_logp is None else old_logp
             self._refresh_std()
             # a model with an observation normaliser: the static inputs hold (x - mean) * rstd (orr_normalize_rows instead of the copy),
             # so nothing inside the captured epoch changes; the statistics are the ones the rollout ran with
@@ -443,13 +463,17 @@ class FusedPPO(_FusedLearner):
                     pnorm.normalize(priv.contiguous(), out=P["priv"])
                 else:
                     P["priv"].copy_(priv)
-            aux = P["aux"]
-            aux[:, :12].copy_(actions)
-            aux[:, 12].copy_(logp)
-            aux[:, 13].copy_(adv)
-            aux[:, 14].copy_(ret)
+            self._fill_aux(P, actions, logp, adv, ret)
         total, n = self._run(B, fill, epochs, generator, self._world(), self._allreduce if self._several() else None)
         return self._returned(total / n).cpu().numpy()
+
+    def _fill_aux(self, P, actions, logp, adv, ret):
+        """The loss head's per-sample row (ORR_PPO_BATCH_COLS): the actions, then old log-probability, advantage and return."""
+        aux = P["aux"]
+        aux[:, :12].copy_(actions)
+        aux[:, 12].copy_(logp)
+        aux[:, 13].copy_(adv)
+        aux[:, 14].copy_(ret)
 
     # ---- ranks: the gradient all-reduce and replica consistency (MpiAdam, stable_baselines/common/mpi_adam.py) -----------------------
     def _world(self):
@@ -543,31 +567,26 @@ class FusedPPOHistory(FusedPPO):
 
     def _buffers(self, P, f, split, rows):
         FusedPPO._buffers(self, P, f, split, rows)           # obs, aux, priv and both nets at k0 = 160 + 48; xv = x | xp feeds the critic
-        M, g = P["M"], self.g
-        D, H, Z = _abi.HISTORY_DIM, 256, _abi.POLICY_PRIV_DIM
+        M, Z = P["M"], _abi.POLICY_PRIV_DIM
         lrows = _abi.latent_backward_rows(M)
-        P.update({"hist": f(P["B"], D), "xh": f(M, D), "he": f(M, H), "z": f(M, Z), "xz": f(M, 160 + Z), "g_z": f(M, Z), "g_he": f(M, H),
-                  "ws1e": f(rows * H), "parte": f(16, D, H) if split else None, "lp": f(49 * lrows), "w0z": f(512, Z),
+        own = self._enc_buffers(P, f, split, rows)
+        P.update({"hist": f(P["B"], _abi.HISTORY_DIM), "xz": f(M, 160 + Z), "lp": f(49 * lrows), "w0z": f(512, Z),
                   "w0zt": f(int(self.L.orr_policy_packed_size(512, Z)))})
-        own = [(P["ws1e"], g["model/enc_fc0/b:0"], rows, H)] + ([(P["parte"], g["model/enc_fc0/w:0"], 16, D * H)] if split else [])
-        own.append((P["lp"], g["model/enc_fc1/b:0"], lrows, Z))
-        k = self.head_stats                                  # the latent loss lands behind the head's stats, in the minibatch's own row
-        if self.latent_coef != 0.0:
-            P["jobs_e"] = [_jobs(own + [(P["lp"][Z * lrows:], P["stats"][s][k:], lrows, 1)]) for s in range(P["nmb"])]
-        else:                                                # orr_latent_backward leaves no loss then: orr_regress_head reports it
+        own.append((P["lp"], self.g["model/enc_fc1/b:0"], lrows, Z))
+        lat = self.latent_coef != 0.0     # the latent loss then lands behind the head's stats, in the minibatch's own row: a table per minibatch
+        P["jobs_s"] = [_jobs(own + ([(P["lp"][Z * lrows:], P["stats"][s][self.head_stats:], lrows, 1)] if lat else [])) for s in range(P["nmb"])]
+        if not lat:                       # orr_latent_backward leaves no loss: orr_regress_head reports it
             P.update({"wsr": f(int(self.L.orr_learner_workspace_floats(M, 64))), "gr": f(M, Z), "gbr": f(Z)})
-            P["jobs_e"] = [_jobs(own)] * P["nmb"]
 
     def _minibatch(self, P, s):
         """Gather, forward, loss head and backward of minibatch s of the current permutation; gradients land in flat_g."""
-        t, L, M, w, g = self.torch, self.L, P["M"], self.w, self.g
+        t, L, M, w = self.torch, self.L, P["M"], self.w
         st = self._stream()
         Z = _abi.POLICY_PRIV_DIM
         idx = P["perm"][s * M:(s + 1) * M]
         for src, dst in (("obs", "x"), ("hist", "xh"), ("priv", "xp"), ("aux", "batch")):
             t.index_select(P[src], 0, idx, out=P[dst])
-        t._addmm_activation(w["model/enc_fc0/b:0"], P["xh"], w["model/enc_fc0/w:0"], out=P["he"])
-        t.addmm(w["model/enc_fc1/b:0"], P["he"], w["model/enc_fc1/w:0"], out=P["z"])
+        self._enc_forward(P)
         t.cat((P["x"], P["z"]), dim=1, out=P["xz"])
         t.cat((P["x"], P["xp"]), dim=1, out=P["xv"])
         xin = {"pi": P["xz"], "vf": P["xv"]}
@@ -585,13 +604,9 @@ class FusedPPOHistory(FusedPPO):
         if not lat:
             _lib.check(L.orr_regress_head(P["z"].data_ptr(), P["xp"].data_ptr(), M, Z, P["gr"].data_ptr(), P["gbr"].data_ptr(),
                                           P["stats"][s][self.head_stats:].data_ptr(), P["wsr"].data_ptr(), st), L)
-        t.mm(P["he"].t(), P["g_z"], out=g["model/enc_fc1/w:0"])
-        t.mm(P["g_z"], w["model/enc_fc1/w:0"].t(), out=P["g_he"])
-        _lib.check(L.orr_relu_backward(P["g_he"].data_ptr(), P["he"].data_ptr(), M, 256, None, P["ws1e"].data_ptr(), st), L)
-        self._wgrad(P["xh"], P["g_he"], P["parte"], g["model/enc_fc0/w:0"])
+        self._enc_backward(P, st)
         _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
-        jobs, n_jobs = P["jobs_e"][s]
-        _lib.check(L.orr_colsum_finish(jobs, n_jobs, st), L)
+        _lib.check(L.orr_colsum_finish(*P["jobs_s"][s], st), L)
 
     def update(self, obs, hist, priv, actions, adv, ret, old_logp=None, epochs=1, generator=None):
         """obs [B,160], hist [B,512] (history_push), priv [B,48] (env.privileged_obs on the same states), actions [B,12] (unclipped samples),
@@ -602,18 +617,12 @@ class FusedPPOHistory(FusedPPO):
             raise ValueError("FusedPPOHistory: hist must have shape (%d, %d) and priv (%d, %d)" % (B, _abi.HISTORY_DIM, B, _abi.POLICY_PRIV_DIM))
 
         def fill(P):
-            logp = old_logp
-            if logp is None:
-                logp = self.model.log_prob(obs, actions, hist=hist)
+            logp = self.model.log_prob(obs, actions, hist=hist) if old_logp is None else old_logp
             self._refresh_std()
             P["obs"].copy_(obs)
             P["hist"].copy_(hist)
             P["priv"].copy_(priv)
-            aux = P["aux"]
-            aux[:, :12].copy_(actions)
-            aux[:, 12].copy_(logp)
-            aux[:, 13].copy_(adv)
-            aux[:, 14].copy_(ret)
+            self._fill_aux(P, actions, logp, adv, ret)
         total, n = self._run(B, fill, epochs, generator, self._world(), self._allreduce if self._several() else None)
         return self._returned(total / n).cpu().numpy()
 
@@ -729,11 +738,9 @@ class FusedDistillHistory(_FusedLearner):
             A[name].copy_(p[key].detach())
 
     def _buffers(self, P, f, split, rows):
-        B, M, g = P["B"], P["M"], self.g
-        D, H, Z = _abi.HISTORY_DIM, 256, _abi.POLICY_PRIV_DIM
-        P.update({"hist": f(B, D), "target": f(B, Z), "x": f(M, D), "tgt": f(M, Z), "h": f(M, H), "z": f(M, Z), "g_z": f(M, Z), "g_h": f(M, H),
-                  "ws": f(int(self.L.orr_learner_workspace_floats(M, 64))), "ws1": f(rows * H), "part0": f(16, D, H) if split else None})
-        own = [(P["ws1"], g["model/enc_fc0/b:0"], rows, H)] + ([(P["part0"], g["model/enc_fc0/w:0"], 16, D * H)] if split else [])
+        B, M, g, Z = P["B"], P["M"], self.g, _abi.POLICY_PRIV_DIM
+        own = self._enc_buffers(P, f, split, rows)
+        P.update({"hist": f(B, _abi.HISTORY_DIM), "target": f(B, Z), "tgt": f(M, Z), "ws": f(int(self.L.orr_learner_workspace_floats(M, 64)))})
         P["jobs"], P["n_jobs"] = _jobs(own)
         if self.head:
             # obs and the teacher's means, gathered with the same permutation; the head's partial sums (ORR_STUDENT_HEAD_PARTIAL_FLOATS) are two
@@ -741,21 +748,17 @@ class FusedDistillHistory(_FusedLearner):
             # row of stats - hence one job list per minibatch
             hrows = _abi.student_head_rows(M)
             P.update({"obs": f(B, 160), "tmean": f(B, 12), "xo": f(M, 160), "tm": f(M, 12), "hp": f(50 * hrows)})
-            P["jobs_s"] = [_jobs(own + [(P["hp"], g["model/enc_fc1/b:0"], hrows, Z), (P["hp"][Z * hrows:], P["stats"][s], hrows, 2)])[0]
+            P["jobs_s"] = [_jobs(own + [(P["hp"], g["model/enc_fc1/b:0"], hrows, Z), (P["hp"][Z * hrows:], P["stats"][s], hrows, 2)])
                            for s in range(P["nmb"])]
 
     def _minibatch(self, P, s):
         """Gather, the encoder's forward pass, loss head and backward of minibatch s of the current permutation; gradients land in flat_g."""
-        t, L, M, w, g = self.torch, self.L, P["M"], self.w, self.g
+        t, L, M = self.torch, self.L, P["M"]
         st = self._stream()
         idx = P["perm"][s * M:(s + 1) * M]
-        t.index_select(P["hist"], 0, idx, out=P["x"])
-        t.index_select(P["target"], 0, idx, out=P["tgt"])
-        if self.head:
-            t.index_select(P["obs"], 0, idx, out=P["xo"])
-            t.index_select(P["tmean"], 0, idx, out=P["tm"])
-        t._addmm_activation(w["model/enc_fc0/b:0"], P["x"], w["model/enc_fc0/w:0"], out=P["h"])
-        t.addmm(w["model/enc_fc1/b:0"], P["h"], w["model/enc_fc1/w:0"], out=P["z"])
+        for src, dst in (("hist", "xh"), ("target", "tgt")) + ((("obs", "xo"), ("tmean", "tm")) if self.head else ()):
+            t.index_select(P[src], 0, idx, out=P[dst])
+        self._enc_forward(P)
         if self.head:
             A = self._actor
             _lib.check(L.orr_history_student_head(C.byref(A["net"]), A["w2t"].data_ptr(), A["w1t"].data_ptr(), A["w0zt"].data_ptr(), P["xo"].data_ptr(),
@@ -763,15 +766,9 @@ class FusedDistillHistory(_FusedLearner):
                                                   P["g_z"].data_ptr(), None, P["hp"].data_ptr(), st), L)
         else:
             _lib.check(L.orr_regress_head(P["z"].data_ptr(), P["tgt"].data_ptr(), M, _abi.POLICY_PRIV_DIM, P["g_z"].data_ptr(),
-                                          g["model/enc_fc1/b:0"].data_ptr(), P["stats"][s].data_ptr(), P["ws"].data_ptr(), st), L)
-        t.mm(P["h"].t(), P["g_z"], out=g["model/enc_fc1/w:0"])
-        t.mm(P["g_z"], w["model/enc_fc1/w:0"].t(), out=P["g_h"])
-        _lib.check(L.orr_relu_backward(P["g_h"].data_ptr(), P["h"].data_ptr(), M, 256, None, P["ws1"].data_ptr(), st), L)
-        self._wgrad(P["x"], P["g_h"], P["part0"], g["model/enc_fc0/w:0"])
-        if self.head:
-            _lib.check(L.orr_colsum_finish(P["jobs_s"][s], P["n_jobs"] + 2, st), L)
-        else:
-            _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
+                                          self.g["model/enc_fc1/b:0"].data_ptr(), P["stats"][s].data_ptr(), P["ws"].data_ptr(), st), L)
+        self._enc_backward(P, st)
+        _lib.check(L.orr_colsum_finish(*(P["jobs_s"][s] if self.head else (P["jobs"], P["n_jobs"])), st), L)
 
     def update(self, hist, target_priv, epochs=1, generator=None, obs=None, target_mean=None):
         """hist [B,512], target_priv [B,48] (env.privileged_obs on the same states); with action_coef > 0 also obs [B,160] and target_mean [B,12]

@@ -323,9 +323,9 @@ def test_fused_ppo_history_matches_the_torch_learner(graph, B, M):
     P = fused._plan(B, M)
     assert tuple(P["xv"].shape) == (M, 208) and tuple(P["xz"].shape) == (M, 208) and tuple(P["stats"].shape) == (B // M, 3)
     if M >= 4096:                                                    # 10 + 4 column-sum jobs in two launches
-        assert P["n_jobs"] == 10 and P["jobs_e"][0][1] == 4 and tuple(P["parte"].shape) == (16, 512, 256)
+        assert P["n_jobs"] == 10 and P["jobs_s"][0][1] == 4 and tuple(P["part0"].shape) == (16, 512, 256)
     else:
-        assert P["n_jobs"] == 6 and P["jobs_e"][0][1] == (3 if coef else 2)
+        assert P["n_jobs"] == 6 and P["jobs_s"][0][1] == (3 if coef else 2)
     steps = 2 * 2 * (B // M)
     for it in range(2):
         g1, g2 = torch.Generator(device=dev), torch.Generator(device=dev)

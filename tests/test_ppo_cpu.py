@@ -45,6 +45,21 @@ def test_parameter_names_match_stable_baselines_zip_layout():
     np.testing.assert_array_equal(m2.state_dict()["model/pi_fc0/w:0"], w["model/pi_fc0/w:0"])
 
 
+# every name that train.py, tools/, tests/, learner_hip.py and the documents reach through `ppo.` (a list, not a computation: the modules
+# behind ppo may be split and moved, these stay)
+PPO_NAMES = ("ActorCritic", "PPO", "PPOHistory", "Distill", "DistillHistory", "RunningNorm", "history_push", "history_frame", "STAT_NAMES",
+             "LOG_STD_BOUNDS", "LOGSTD", "ENTROPY_CONST", "HISTORY_STEPS", "HISTORY_FRAME", "HISTORY_DIM", "NORM_EPS", "KL_LR_BOUNDS",
+             "_wgrad", "_UpdateControl", "_entropy_args", "_control_args", "_no_obs_norm")
+
+
+def test_ppo_exposes_every_name_its_callers_use_and_imports_without_torch():
+    missing = [n for n in PPO_NAMES if not hasattr(ppo, n)]
+    assert not missing, missing
+    code = "import sys; sys.path.insert(0, %r); import openroborl_amd.ppo; assert 'torch' not in sys.modules, 'torch was imported'" % ROOT
+    out = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert out.returncode == 0, out.stdout.decode()
+
+
 WORKER = r"""
 import os, sys, torch
 sys.path.insert(0, %r)
