@@ -504,6 +504,60 @@ int32_t orr_bind_push_outputs(orr_handle* h, float* push_dev /* [N][ORR_PUSH_ROW
 #define ORR_PRIV_DIM 48
 int32_t orr_privileged_obs(orr_handle* h, const uint8_t* done_dev, float* priv_dev, void* stream);
 
+/* Reward shaping: effort, smoothness, impact and failure penalties taken off the imitation reward on the device.  This project's own:
+ * the reference's reward is its five imitation terms and nothing else.  A post-step kernel (csrc/orr_kernels_shaping.hip), no variant of
+ * the step: orr_step, orr_reset and the replays launch what they launch without it, and EP_RETURN, the episode log and the clip
+ * curriculum's scores stay on the imitation reward.
+ * orr_shaped_reward is ONE launch, called after the orr_step whose actions_dev [N][12], reward (reward_in_dev [N]) and done_dev [N] it is
+ * given; reward_out_dev [N] may be reward_in_dev.  It reads the state record as it stands and the actuator / contact buffers the handle
+ * has bound when the launch RUNS (orr_bind_actuator_outputs, orr_bind_contact_outputs), as orr_privileged_obs does.  For robot i, with
+ *   a = its action row, A[m] = its act_dev row of motor m, C[leg] = its contact_dev row, r = reward_in[i], d = done[i] != 0,
+ *   reason = DONE_REASON, n_step = d ? LAST_EP_LEN : EP_STEP (the number of the step just taken within its episode; both survive the
+ *   auto-reset), a1 = prev[i][0..11], a2 = prev[i][12..23] (the actions of the two steps before),
+ * the terms p_k, unweighted, in ORR_SHAPING_* order:
+ *   0 torque        (sum_m A[m][2]) * inv_nsub: the mean square torque summed over the 12 motors, (N m)^2; inv_nsub = 1 / action_repeat
+ *   1 work          sum_m |A[m][3]|, J
+ *   2 action_rate   sum_j (a_j - a1_j)^2 if n_step >= 2, else 0
+ *   3 action_accel  sum_j (a_j - 2 a1_j + a2_j)^2 if n_step >= 3, else 0
+ *   4 impact        (sum_leg C[leg][3]) * inv_dt: the sum of the legs' peak normal forces, N; inv_dt = 1 / sim_dt
+ *   5 failure       1.0 if d and reason & (CONTACT_FALL | ROOT_POS | ROOT_ROT | NAN), else 0.0: a time limit or a clip played to its
+ *                   end is no failure
+ *   inv_nsub and inv_dt are formed once on the host in float32; the 12- and 4-element sums are float32 adds in a fixed tree.  A step
+ *   with reason & ORR_DONE_NAN writes terms 0..4 as 0 (the step has zeroed the buffers; the actions may be non-finite).  Terms 0 and 1
+ *   are 0 while no actuator outputs are bound, term 4 while no contact outputs are bound.
+ *   pen = sum_k w[k] p_k: float32, k ascending, a chain of fused multiply-adds from +0.  shaped = fmaxf(r - pen, floor), built from the
+ *   very term values stored.
+ * Stores (every row two 16-byte pieces; padding lanes store nothing; no atomics: the same inputs give the same bits):
+ *   shape_dev[i]     = {p0..p5, shaped, 1.0f}
+ *   shape_ep_dev[i]  is OVERWRITTEN with that row when n_step <= 1, otherwise it gets one float32 add per column (the rule of
+ *                    term_sums_dev; no reset touches the buffer)
+ *   shape_tot_dev[i] += shape_ep_dev[i] (its new value) when d; the kernel never restarts it, so column 7 counts the steps of the
+ *                    robot's finished episodes
+ *   prev_dev[i]      = {a, a1}
+ *   reward_out[i]    = shaped
+ * The weights and the floor live in the handle's device table, where the kernel reads them: a replayed graph follows
+ * orr_set_reward_shaping without a re-capture.  The setter writes them in stream order on `stream` and synchronises nothing.
+ * host NULL = off.  floor = -inf: none.  shape_dev NULL unbinds all four buffers.
+ * Refused with a negative code, nothing launched or written (the message starts with the entry point's name): a null handle or
+ *   pointer; no state bound (orr_bind); orr_shaped_reward while shaping is not set or the buffers are not bound; shape_dev without any
+ *   of the other three; a row buffer, prev_dev or actions_dev that is not 16-byte aligned; reward_in / reward_out not 4-byte aligned; a
+ *   weight that is negative, NaN or infinite; a floor that is NaN or +inf; at launch w[0] or w[1] != 0 without bound actuator outputs,
+ *   or w[4] != 0 without bound contact outputs. */
+#define ORR_SHAPING_TERMS 6
+#define ORR_SHAPING_ROW 8
+#define ORR_SHAPING_PREV 24 /* floats per robot of prev_dev */
+enum orr_shaping_term_e { ORR_SHAPING_TORQUE, ORR_SHAPING_WORK, ORR_SHAPING_ACTION_RATE, ORR_SHAPING_ACTION_ACCEL, ORR_SHAPING_IMPACT, ORR_SHAPING_FAILURE };
+typedef struct orr_reward_shaping {
+  float w[ORR_SHAPING_TERMS];
+  float floor;
+} orr_reward_shaping;
+int32_t orr_sizeof_reward_shaping(void);
+int32_t orr_set_reward_shaping(orr_handle* h, const orr_reward_shaping* host /* NULL = off */, void* stream);
+int32_t orr_bind_reward_shaping(orr_handle* h, float* shape_dev /* [N][8] */, float* shape_ep_dev /* [N][8] */, float* shape_tot_dev /* [N][8] */,
+                                float* prev_dev /* [N][24] */);
+int32_t orr_shaped_reward(orr_handle* h, const float* actions_dev, const float* reward_in_dev, const uint8_t* done_dev, float* reward_out_dev,
+                          void* stream);
+
 /* reward terms (ImitationTask._calc_reward_pose / _velocity / _end_effector / _root_pose / _root_velocity, imitation_task.py:358-516).
  * terms_dev float[N][5] (device): every orr_step and orr_debug_replay_step writes, for every robot of the shard, the five UNWEIGHTED
  *   terms r_k = exp(-scale_k err_k) of the reward it wrote to reward_dev, in orr_config::reward_w's order: pose, velocity, end effector,

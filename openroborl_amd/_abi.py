@@ -156,6 +156,20 @@ PRIV_DIM = 48
 POLICY_PRIV_DIM = 48
 
 
+# include/openroborl_hip.h: ORR_SHAPING_* and orr_reward_shaping (orr_set_reward_shaping, orr_bind_reward_shaping, orr_shaped_reward).  A row
+# of the three sum buffers = the six unweighted terms in SHAPING_NAMES' order, the shaped reward, 1.0 (a step count once summed)
+SHAPING_TERMS = 6
+SHAPING_ROW = 8
+SHAPING_PREV = 24                   # floats per robot of the prev buffer: the last two actions, the newer first
+SHAPING_NAMES = ("torque", "work", "action_rate", "action_accel", "impact", "failure")
+SHAPING_COLUMNS = SHAPING_NAMES + ("shaped_reward", "steps")
+
+
+class OrrRewardShaping(C.Structure):
+    """include/openroborl_hip.h: orr_reward_shaping (orr_set_reward_shaping)."""
+    _fields_ = [("w", C.c_float * SHAPING_TERMS), ("floor", C.c_float)]
+
+
 class OrrPush(C.Structure):
     """include/openroborl_hip.h: orr_push (orr_set_push)."""
     _fields_ = [(n, C.c_float) for n in PUSH_FIELDS] + [("grace_steps", C.c_int32)]

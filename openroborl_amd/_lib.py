@@ -24,6 +24,7 @@ SRC_SENSOR = os.path.join(CSRC, "orr_kernels_sensor.hip")        # the variants 
 SRC_RANDOMIZER = os.path.join(CSRC, "orr_kernels_randomizer.hip")  # the variants of step and reset with the table-driven, controllable randomiser
 SRC_PUSH = os.path.join(CSRC, "orr_kernels_push.hip")            # the variant of the step that kicks the robot's base twist (external pushes)
 SRC_PRIV = os.path.join(CSRC, "orr_kernels_priv.hip")            # the privileged observation (orr_privileged_obs): a gather kernel of its own, plain flags
+SRC_SHAPING = os.path.join(CSRC, "orr_kernels_shaping.hip")      # the shaped reward (orr_shaped_reward): a post-step kernel of its own, plain flags
 SRC_POLICY = os.path.join(CSRC, "orr_policy.hip")
 SRC_LEARNER = os.path.join(CSRC, "orr_learner.hip")              # the non-GEMM part of the PPO update (include/openroborl_learner.h)
 # what the library is built from = what the stale-library check hashes: every source and header under csrc/ + the public headers
@@ -100,11 +101,14 @@ PUSH_UNITS = [("push", SRC_PUSH, HIPCC_FLAGS, False)]
 # The twelfth unit of the env kernels, the privileged observation (orr_privileged_obs): a table of its own behind PUSH_UNITS.  Not a variant
 # of step or reset but a small gather kernel: the plain flags, and neither tuning defines nor extra_flags reach it (it has no KParams)
 PRIV_UNITS = [("priv", SRC_PRIV, HIPCC_FLAGS_PLAIN, False)]
+# The thirteenth unit of the env kernels, the shaped reward (orr_shaped_reward, orr_set_reward_shaping): a table of its own behind
+# PRIV_UNITS and like it no variant of step or reset: the plain flags, and neither tuning defines nor extra_flags reach it
+SHAPING_UNITS = [("shaping", SRC_SHAPING, HIPCC_FLAGS_PLAIN, False)]
 
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
     "orr_layout_offset", "orr_layout_size", "orr_layout_is_int", "orr_sizeof_config", "orr_sizeof_model",
-    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_clip_weights", "orr_get_clip_thresholds", "orr_sizeof_clip_curriculum", "orr_set_clip_curriculum", "orr_clip_curriculum_update", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_set_push", "orr_sizeof_push", "orr_bind_push_outputs", "orr_privileged_obs", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
+    "orr_create", "orr_destroy", "orr_set_seed", "orr_set_model", "orr_set_motion", "orr_set_clip_set", "orr_set_clip_switch", "orr_set_clip_weights", "orr_get_clip_thresholds", "orr_sizeof_clip_curriculum", "orr_set_clip_curriculum", "orr_clip_curriculum_update", "orr_set_task_noise", "orr_sizeof_task_noise", "orr_set_sensor_noise", "orr_sizeof_sensor_noise", "orr_set_randomizer", "orr_sizeof_randomizer", "orr_bind_randomizer_params", "orr_set_push", "orr_sizeof_push", "orr_bind_push_outputs", "orr_privileged_obs", "orr_sizeof_reward_shaping", "orr_set_reward_shaping", "orr_bind_reward_shaping", "orr_shaped_reward", "orr_bind_clip_log", "orr_bind_reward_terms", "orr_bind_contact_outputs", "orr_set_torque_limits", "orr_bind_actuator_outputs", "orr_bind", "orr_reset", "orr_step",
     "orr_episode_stats", "orr_time_steps", "orr_stress_actions", "orr_debug_physics", "orr_debug_replay_step", "orr_debug_replay_reset",
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_history", "orr_policy_forward_history_priv", "orr_history_push", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_ppo_head_logstd", "orr_gauss_prepare", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_latent_backward", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
@@ -186,7 +190,10 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
             tag = ".%d" % os.getpid()
             tmp_so = out_path + tag + ".tmp"
             objs, cmds = [], []
+            units = []      # the tables up to PRIV_UNITS in the order the older tests read off the next line, then the newest
             for unit in ALL_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS + PUSH_UNITS + PRIV_UNITS:
+                units.append(unit)
+            for unit in units + SHAPING_UNITS:       # the newest table last
                 name, src, flags, hashed = unit
                 flags = [f for f in flags if f != "-shared"] + ["-c"]
                 if hashed:
@@ -297,6 +304,13 @@ def load():
     L.orr_bind_push_outputs.argtypes = [vp, vp]
     L.orr_privileged_obs.restype = C.c_int32
     L.orr_privileged_obs.argtypes = [vp, vp, vp, vp]
+    L.orr_sizeof_reward_shaping.restype = C.c_int32
+    L.orr_set_reward_shaping.restype = C.c_int32
+    L.orr_set_reward_shaping.argtypes = [vp, C.POINTER(_abi.OrrRewardShaping), vp]
+    L.orr_bind_reward_shaping.restype = C.c_int32
+    L.orr_bind_reward_shaping.argtypes = [vp, vp, vp, vp, vp]
+    L.orr_shaped_reward.restype = C.c_int32
+    L.orr_shaped_reward.argtypes = [vp, vp, vp, vp, vp, vp]
     L.orr_bind_clip_log.restype = C.c_int32
     L.orr_bind_clip_log.argtypes = [vp, vp]
     L.orr_bind_reward_terms.restype = C.c_int32
@@ -397,7 +411,8 @@ def load():
     if (L.orr_sizeof_config() != C.sizeof(_abi.OrrConfig) or L.orr_sizeof_model() != C.sizeof(_abi.OrrModel)
             or L.orr_sizeof_task_noise() != C.sizeof(_abi.OrrTaskNoise) or L.orr_sizeof_sensor_noise() != C.sizeof(_abi.OrrSensorNoise)
             or L.orr_sizeof_randomizer() != C.sizeof(_abi.OrrRandomizer) or L.orr_sizeof_push() != C.sizeof(_abi.OrrPush)
-            or L.orr_sizeof_update_ctl() != C.sizeof(_abi.OrrUpdateCtl) or L.orr_sizeof_clip_curriculum() != C.sizeof(_abi.OrrClipCurriculum)):
+            or L.orr_sizeof_update_ctl() != C.sizeof(_abi.OrrUpdateCtl) or L.orr_sizeof_clip_curriculum() != C.sizeof(_abi.OrrClipCurriculum)
+            or L.orr_sizeof_reward_shaping() != C.sizeof(_abi.OrrRewardShaping)):
         raise RuntimeError("ctypes struct layout does not match include/openroborl_hip.h / openroborl_learner.h")
     _lib = L
     return L

@@ -150,6 +150,13 @@ struct DevTables {
     float ref[ORR_MAX_CLIPS];
     double ema[ORR_MAX_CLIPS];                        // per clip id: the running score in [0, 1]; the kernel's own state
   } cur;
+  // reward shaping of the handle (orr_set_reward_shaping, orr_bind_reward_shaping), read by orr_shaped_reward's kernel only
+  // (orr_kernels_shaping.hip), which follows the step and is no variant of it.  APPENDED likewise
+  float* shape_out;                                   // [N][ORR_SHAPING_ROW] the step's six unweighted terms, the shaped reward, 1.0; NULL = not bound
+  float* shape_ep;                                    // [N][ORR_SHAPING_ROW] their sums over the robot's current episode
+  float* shape_tot;                                   // [N][ORR_SHAPING_ROW] the sums of the robot's finished episodes
+  float* shape_prev;                                  // [N][24] the robot's last two actions, the newer first
+  orr_reward_shaping shaping;                         // the weights and the floor; its kernel's setter writes the device's copy in stream order
 };
 // Flag bit of orr_step_kernel's MODE: the variant that also writes the reward terms.  MODE & 3 is the mode proper (0 env step, 1 debug
 // physics, 2 parity replay).  A bit of MODE rather than a template parameter of its own: the older variants keep their mangled names

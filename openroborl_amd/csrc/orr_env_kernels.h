@@ -12,7 +12,8 @@
 // orr_kernels_randomizer.hip: the variants whose resets run the table-driven randomiser (orr_set_randomizer, orr_bind_randomizer_params).
 // orr_kernels_push.hip: the env step that kicks the robot's base twist (orr_set_push, orr_bind_push_outputs).
 // (A twelfth unit, orr_kernels_priv.hip, includes this header for the record's layout and the device table only: it holds the kernel of
-// orr_privileged_obs, no variant of step or reset, and is compiled with the plain flags.)
+// orr_privileged_obs, no variant of step or reset, and is compiled with the plain flags.  A thirteenth, orr_kernels_shaping.hip, does the
+// same for the kernel of orr_shaped_reward.)
 // An instantiation compiled next to the default ones moves the default kernels' code (round 5: +6 instructions
 // per sub-step, +0.7 % run time with the anchor variants alongside), so the main unit sees the other units' launchers as `extern
 // template` only (bottom of this file).
@@ -1077,6 +1078,12 @@ extern template ResetLaunch launch_randomizer_reset<true>;                      
 // (orr_kernels_priv.hip).  lat_div = (ORR_RING_DEPTH - 2) * sim_dt, step_dt = action_repeat * sim_dt, formed by the caller
 hipError_t launch_privileged_obs(const DevTables* tab, const float* state, int n, const uint8_t* done, float* priv, float lat_div, float step_dt,
                                  hipStream_t stream);
+
+// The shaped reward (orr_shaped_reward) and the setter of its weights (orr_set_reward_shaping): likewise one kernel each in a unit of their
+// own with the plain flags (orr_kernels_shaping.hip).  inv_nsub = 1 / action_repeat, inv_dt = 1 / sim_dt, formed by the caller in float32
+hipError_t launch_shaped_reward(const DevTables* tab, const float* state, int n, const float* actions, const float* reward_in, const uint8_t* done,
+                                float* reward_out, float inv_nsub, float inv_dt, hipStream_t stream);
+hipError_t launch_set_shaping(DevTables* tab, const orr_reward_shaping& s, hipStream_t stream);
 
 #ifdef ORR_STAGE_DUMP
 // the stage dump: instantiated in BOTH step units (orr_kernels.hip: WPE 1, orr_kernels_w2.hip: WPE 2), which compile different forms of

@@ -180,6 +180,7 @@ struct orr_handle {
   bool push_on;               // orr_set_push with prob > 0, or
   bool push_bound;            // orr_bind_push_outputs with a buffer: the env step runs the push variant (orr_kernels_push.hip); every other entry point launches what it launches without
   bool curriculum_on;         // orr_set_clip_curriculum gave settings: orr_clip_curriculum_update may launch (it selects no variant)
+  bool shaping_on;            // orr_set_reward_shaping gave weights: orr_shaped_reward may launch (it selects no variant; orr_kernels_shaping.hip)
   DevTables* tab_dev;
   DevTables tab_host;
   float fb[3], fa[3];
@@ -908,6 +909,63 @@ int32_t orr_privileged_obs(orr_handle* h, const uint8_t* done_dev, float* priv_d
   if (!h->state) return fail(-1, "orr_privileged_obs: handle not bound");
   const float lat_div = (float)(ORR_RING_DEPTH - 2) * h->cfg.sim_dt, step_dt = (float)h->cfg.action_repeat * h->cfg.sim_dt;
   HIPCHK(launch_privileged_obs(h->tab_dev, h->state, h->cfg.num_robots, done_dev, priv_dev, lat_div, step_dt, (hipStream_t)stream), "orr_privileged_obs: launch");
+  return 0;
+}
+
+// reward shaping: its kernels live in orr_kernels_shaping.hip (no variants: a post-step kernel that reads the record, the bound actuator /
+// contact outputs and the weights in the device table)
+int32_t orr_sizeof_reward_shaping(void) { return (int32_t)sizeof(orr_reward_shaping); }
+
+int32_t orr_set_reward_shaping(orr_handle* h, const orr_reward_shaping* host, void* stream) {
+  if (!h) return fail(-1, "orr_set_reward_shaping: null handle");
+  if (!h->state) return fail(-1, "orr_set_reward_shaping: handle not bound");
+  orr_reward_shaping s;
+  memset(&s, 0, sizeof(s));
+  if (host) {
+    s = *host;
+    for (int k = 0; k < ORR_SHAPING_TERMS; k++)
+      if (!(s.w[k] >= 0.0f && s.w[k] < INFINITY)) return refuse("orr_set_reward_shaping: w[%d] must be a finite number >= 0", k);   // NaN fails the comparison
+    if (!(s.floor < INFINITY)) return fail(-1, "orr_set_reward_shaping: floor must be a number below +inf (-inf = none)");
+  }
+  // in stream order, without a synchronisation: a kernel that takes the seven words by value writes the device's copy
+  HIPCHK(launch_set_shaping(h->tab_dev, s, (hipStream_t)stream), "orr_set_reward_shaping: launch");
+  h->tab_host.shaping = s;
+  h->shaping_on = host != nullptr;
+  return 0;
+}
+
+int32_t orr_bind_reward_shaping(orr_handle* h, float* shape_dev, float* shape_ep_dev, float* shape_tot_dev, float* prev_dev) {
+  static_assert(offsetof(DevTables, shape_ep) == offsetof(DevTables, shape_out) + sizeof(float*) &&
+                offsetof(DevTables, shape_tot) == offsetof(DevTables, shape_out) + 2 * sizeof(float*) &&
+                offsetof(DevTables, shape_prev) == offsetof(DevTables, shape_out) + 3 * sizeof(float*), "copied as four consecutive pointers");
+  if (!h) return fail(-1, "orr_bind_reward_shaping: null handle");
+  if (!h->state) return fail(-1, "orr_bind_reward_shaping: handle not bound");
+  const bool on = shape_dev != nullptr;
+  if (on && (!shape_ep_dev || !shape_tot_dev || !prev_dev))
+    return fail(-1, "orr_bind_reward_shaping: shape_dev needs shape_ep_dev, shape_tot_dev and prev_dev");
+  if (on && (((uintptr_t)shape_dev | (uintptr_t)shape_ep_dev | (uintptr_t)shape_tot_dev | (uintptr_t)prev_dev) & 15u) != 0)
+    return fail(-1, "orr_bind_reward_shaping: the buffers must be 16-byte aligned (rows of 8 and 24 floats, read and written in 16-byte pieces)");
+  float* p[4] = {shape_dev, on ? shape_ep_dev : nullptr, on ? shape_tot_dev : nullptr, on ? prev_dev : nullptr};
+  return upload(h, "orr_bind_reward_shaping", &h->tab_host.shape_out, p, sizeof(p));
+}
+
+int32_t orr_shaped_reward(orr_handle* h, const float* actions_dev, const float* reward_in_dev, const uint8_t* done_dev, float* reward_out_dev,
+                          void* stream) {
+  if (!h) return fail(-1, "orr_shaped_reward: null handle");
+  if (!actions_dev || !reward_in_dev || !done_dev || !reward_out_dev) return fail(-1, "orr_shaped_reward: null buffer");
+  if (!h->state) return fail(-1, "orr_shaped_reward: handle not bound");
+  if (!h->shaping_on) return fail(-1, "orr_shaped_reward: reward shaping is not set (orr_set_reward_shaping)");
+  if (!h->tab_host.shape_out) return fail(-1, "orr_shaped_reward: the shaping buffers are not bound (orr_bind_reward_shaping)");
+  if (((uintptr_t)actions_dev & 15u) != 0) return fail(-1, "orr_shaped_reward: actions_dev must be 16-byte aligned (rows of 12 floats, read in 16-byte pieces)");
+  if ((((uintptr_t)reward_in_dev | (uintptr_t)reward_out_dev) & 3u) != 0) return fail(-1, "orr_shaped_reward: reward_in_dev and reward_out_dev must be 4-byte aligned");
+  const orr_reward_shaping& s = h->tab_host.shaping;
+  if ((s.w[ORR_SHAPING_TORQUE] != 0.0f || s.w[ORR_SHAPING_WORK] != 0.0f) && !h->tab_host.act_out)
+    return fail(-1, "orr_shaped_reward: a torque or work weight needs bound actuator outputs (orr_bind_actuator_outputs)");
+  if (s.w[ORR_SHAPING_IMPACT] != 0.0f && !h->tab_host.contact_out)
+    return fail(-1, "orr_shaped_reward: an impact weight needs bound contact outputs (orr_bind_contact_outputs)");
+  const float inv_nsub = 1.0f / (float)h->cfg.action_repeat, inv_dt = 1.0f / h->cfg.sim_dt;
+  HIPCHK(launch_shaped_reward(h->tab_dev, h->state, h->cfg.num_robots, actions_dev, reward_in_dev, done_dev, reward_out_dev, inv_nsub, inv_dt,
+                              (hipStream_t)stream), "orr_shaped_reward: launch");
   return 0;
 }
 

@@ -100,10 +100,11 @@ class VecQuadrupedEnv(object):
                  model_overrides=None, clip_time_min=None, clip_time_max=None, perturb_init_state_prob=None, tar_obs_noise=None,
                  init_perturb_std=None, reward_terms=False, contact_outputs=False, torque_limits=None, actuator_outputs=False,
                  observation_noise_stdev=None, randomizer_config=None, randomizer_params=False, push=None, push_outputs=False,
-                 clip_weights=None, clip_curriculum=None):
+                 clip_weights=None, clip_curriculum=None, reward_shaping=None):
         import torch
         _check_flags(push_outputs=push_outputs, randomizer_params=randomizer_params, reward_terms=reward_terms,
                      contact_outputs=contact_outputs, actuator_outputs=actuator_outputs)
+        env_spec.reward_shaping_spec(reward_shaping)     # the values here, ahead of everything that needs the device
         # the values here, ahead of everything that needs the device; a dict's robot names below, once the batch's robots are known
         torque_limit_spec(torque_limits, sorted(torque_limits) if isinstance(torque_limits, dict) else ["every robot"])
         # sensor noise (Minitaur._observation_noise_stdev): off by default, as the reference ships it
@@ -294,6 +295,13 @@ class VecQuadrupedEnv(object):
             self.set_push(push)
         if push_outputs:
             self.bind_push_outputs(True)
+        # reward shaping (orr_set_reward_shaping; this project's own, the reference has none): None = off, and step() / step_into() issue the
+        # one call they always issued.  The per-step rows, their sums over each robot's current episode and over its finished episodes,
+        # and the imitation reward that orr_step writes while shaping is on: all None while off
+        self.reward_shaping = None
+        self.shaping_out = self.episode_shaping = self.shaping_totals = self.imitation_reward = self._shaping_prev = None
+        if reward_shaping is not None:
+            self.set_reward_shaping(reward_shaping)
 
     # ---- reference attribute surface -------------------------------------------------------
     @property
@@ -452,6 +460,54 @@ class VecQuadrupedEnv(object):
             bufs = (self.push_out,) if self.push_out is not None else self._zeros((self.num_robot, _abi.PUSH_ROW))
         self._bind_outputs(self.L.orr_bind_push_outputs, ("push_out",), bufs)
 
+    def set_reward_shaping(self, spec=None, scale=1.0):
+        """Switch the shaped reward on, change its weights, or switch it off (orr_set_reward_shaping; see env_spec.reward_shaping_spec for
+        `spec` and `scale`; None = off).  While on, step() and step_into() hand orr_step env.imitation_reward [N] as its reward buffer
+        and follow it with ONE more launch, orr_shaped_reward, which writes the caller's reward tensor = max(imitation reward - sum of the
+        weighted penalties, floor) and env.shaping_out [N, 8] (a robot's row = the six unweighted terms in _abi.SHAPING_NAMES' order, the
+        shaped reward, 1.0), env.episode_shaping [N, 8] (their sums over its current episode) and env.shaping_totals [N, 8] (the sums
+        of its finished episodes; column 7 = their steps).  EP_RETURN, the episode log and the clip curriculum stay on the imitation
+        reward.  Switching on allocates and binds those buffers and - where a non-zero weight needs them and they are unbound - the
+        actuator / contact outputs.  Switching on or off changes the launch sequence: holders of captured graphs re-capture
+        (launch_params_generation); step once eagerly before a capture, as for every kernel's first launch.  A change of the weights
+        while on is read by the kernel in device memory, in stream order: launch_params_generation does not move and a captured graph
+        follows it - unless the new weights need outputs that are not bound yet, which binds them and moves it."""
+        struct = env_spec.reward_shaping_spec(spec, scale)
+        was_on, on = self.reward_shaping is not None, spec is not None
+        if on:
+            need_act, need_contact = env_spec.reward_shaping_needs(struct)
+            if need_act and self.actuator_out is None:
+                self.bind_actuator_outputs(True)
+            if need_contact and self.contact_out is None:
+                self.bind_contact_outputs(True)
+        if on and not was_on:
+            n = self.num_robot
+            bufs = self._zeros((n, _abi.SHAPING_ROW), (n, _abi.SHAPING_ROW), (n, _abi.SHAPING_ROW), (n, _abi.SHAPING_PREV))
+            self.imitation_reward, = self._zeros((n,))
+            self._bind_outputs(self.L.orr_bind_reward_shaping, ("shaping_out", "episode_shaping", "shaping_totals", "_shaping_prev"), bufs)
+        _lib.check(self.L.orr_set_reward_shaping(self.h, C.byref(struct) if on else None, self._stream()), self.L)
+        if was_on and not on:
+            self._bind_outputs(self.L.orr_bind_reward_shaping, ("shaping_out", "episode_shaping", "shaping_totals", "_shaping_prev"), None)
+            self.imitation_reward = None
+        self.reward_shaping = struct if on else None
+
+    def reward_shaping_stats(self):
+        """{name: mean per step} of the six unweighted terms and `shaped_reward` over the episodes finished since the totals were last
+        cleared (sum over robots of shaping_totals[:, k] / sum over robots of shaping_totals[:, 7], in float64); {} when no episode
+        has finished or shaping is off.  Syncs."""
+        if self.shaping_totals is None:
+            return {}
+        tot = self.shaping_totals.double().sum(0).cpu().numpy()
+        if not tot[_abi.SHAPING_ROW - 1] > 0.0:
+            return {}
+        return {name: float(tot[k] / tot[_abi.SHAPING_ROW - 1]) for k, name in enumerate(_abi.SHAPING_COLUMNS[:-1])}
+
+    def clear_shaping_totals(self):
+        """Zero env.shaping_totals (a device fill in stream order, no sync): reward_shaping_stats then covers the episodes that finish from
+        here on."""
+        if self.shaping_totals is not None:
+            self.shaping_totals.zero_()
+
     def get_randomization_parameters(self):
         """ControllableEnvRandomizerFromConfig.get_randomization_parameters for the whole batch: a dict of parameter name -> tensor [N,
         k] of the current episodes' samples in the reference's param_bounds units, -1 + 2 u ("leg weaken": [leg index as it is, -1 + 2 u]),
@@ -602,10 +658,21 @@ class VecQuadrupedEnv(object):
             actions = actions.to(device=self.device, dtype=t.float32).contiguous()
         if tuple(actions.shape) != (self.num_robot, _abi.NUM_MOTORS):
             raise ValueError("actions must have shape (%d, %d)" % (self.num_robot, _abi.NUM_MOTORS))
-        _lib.check(self.L.orr_step(self.h, actions.data_ptr(), self.obs.data_ptr(), self.reward.data_ptr(),
-                                   self.done.data_ptr(), self._stream()), self.L)
+        if self.reward_shaping is not None:
+            self._step_shaped(actions, self.obs, self.reward, self.done)
+        else:
+            _lib.check(self.L.orr_step(self.h, actions.data_ptr(), self.obs.data_ptr(), self.reward.data_ptr(),
+                                       self.done.data_ptr(), self._stream()), self.L)
         self._env_step_counter += 1
         return self.obs, self.reward, self.done, {}
+
+    def _step_shaped(self, actions, obs_out, reward_out, done_out):
+        """The two launches of a step while reward shaping is on: orr_step with env.imitation_reward as its reward buffer, then
+        orr_shaped_reward from it into reward_out."""
+        stream = self._stream()
+        _lib.check(self.L.orr_step(self.h, actions.data_ptr(), obs_out.data_ptr(), self.imitation_reward.data_ptr(), done_out.data_ptr(), stream), self.L)
+        _lib.check(self.L.orr_shaped_reward(self.h, actions.data_ptr(), self.imitation_reward.data_ptr(), done_out.data_ptr(), reward_out.data_ptr(),
+                                            stream), self.L)
 
     def _check_tensors(self, who, *args):
         """Each of args = (tensor, shape, dtype): a contiguous tensor of exactly that on the env device, or ValueError in who's name."""
@@ -623,7 +690,10 @@ class VecQuadrupedEnv(object):
         n = self.num_robot
         self._check_tensors("step_into", (actions, (n, _abi.NUM_MOTORS), t.float32), (obs_out, (n, _abi.OBS_DIM), t.float32),
                             (reward_out, (n,), t.float32), (done_out, (n,), t.uint8))
-        _lib.check(self.L.orr_step(self.h, actions.data_ptr(), obs_out.data_ptr(), reward_out.data_ptr(), done_out.data_ptr(), self._stream()), self.L)
+        if self.reward_shaping is not None:
+            self._step_shaped(actions, obs_out, reward_out, done_out)
+        else:
+            _lib.check(self.L.orr_step(self.h, actions.data_ptr(), obs_out.data_ptr(), reward_out.data_ptr(), done_out.data_ptr(), self._stream()), self.L)
         self._env_step_counter += 1
 
     def privileged_obs(self, out=None, done=None):
@@ -818,7 +888,7 @@ class LegacyListEnv(object):
     """
 
     def __init__(self, env, mutate_actions=True, torque_limits=None, actuator_outputs=False, observation_noise_stdev=None, push=None, push_outputs=False,
-                 clip_weights=None, clip_curriculum=None):
+                 clip_weights=None, clip_curriculum=None, reward_shaping=None):
         if env.cfg.flags & _abi.FLAG_AUTO_RESET:
             raise ValueError("LegacyListEnv needs a VecQuadrupedEnv created with auto_reset=False")
         _check_flags(actuator_outputs=actuator_outputs)
@@ -837,6 +907,8 @@ class LegacyListEnv(object):
             env.set_clip_weights(clip_weights)
         if clip_curriculum is not None:
             env.set_clip_curriculum(clip_curriculum)
+        if reward_shaping is not None:              # reward shaping, passed through to the env
+            env.set_reward_shaping(reward_shaping)
         self._env = env
         self._mutate = mutate_actions
         self.num_robot = env.num_robot

@@ -360,3 +360,42 @@ def push_spec(push=None, action_repeat=cfgmod.ACTION_REPEAT, sim_dt=0.001, max_c
 def push_on(spec):
     """Whether the setting selects the push variant of the step kernel: the probability is above 0."""
     return spec.prob > 0.0
+
+
+# ---- reward shaping (orr_set_reward_shaping, orr_bind_reward_shaping, orr_shaped_reward) ---------------------------------------------
+SHAPING_KEYS = _abi.SHAPING_NAMES + ("floor",)
+
+
+def reward_shaping_spec(spec=None, scale=1.0):
+    """The shaping setting -> the orr_reward_shaping struct.  spec: None (all weights 0, no floor) or a dict with the weights `torque`,
+    `work`, `action_rate`, `action_accel`, `impact`, `failure` (each >= 0; a missing key is 0) and `floor` (the smallest shaped reward;
+    missing = -inf = none).  The weights - not the floor - are multiplied by `scale` (a ramp's factor, >= 0) in float64 and rounded to
+    float32 once.  ValueError on an unknown key and on anything the C-ABI (orr_set_reward_shaping) would refuse; the message names the key."""
+    out = _abi.OrrRewardShaping()
+    out.floor = -math.inf
+    scale = _number(scale, "reward_shaping: scale must be a number, not %r", scale)
+    if not (0.0 <= scale < math.inf):
+        raise ValueError("reward_shaping: scale must be a finite number >= 0, not %r" % (scale,))
+    if spec is None:
+        return out
+    if not isinstance(spec, dict):
+        raise ValueError("reward_shaping must be None or a dict with the keys %s, not %r" % (", ".join(SHAPING_KEYS), spec))
+    for k in spec:
+        if k not in SHAPING_KEYS:
+            raise ValueError("unknown reward_shaping key %r (known: %s)" % (k, ", ".join(SHAPING_KEYS)))
+    for i, name in enumerate(_abi.SHAPING_NAMES):
+        w = _number(spec.get(name, 0.0), "reward_shaping: %s must be a number, not %r", name, spec.get(name)) * scale
+        if not 0.0 <= w <= float(np.finfo(np.float32).max):        # NaN fails the comparison; beyond float32's range the C side would see +inf
+            raise ValueError("reward_shaping: %s must be a finite weight >= 0, not %r (scale %r)" % (name, spec.get(name), scale))
+        out.w[i] = w
+    floor = _number(spec.get("floor", -math.inf), "reward_shaping: floor must be a number, not %r", spec.get("floor"))
+    if not floor < math.inf:
+        raise ValueError("reward_shaping: floor must be a number below +inf (-inf = none), not %r" % (spec.get("floor"),))
+    out.floor = floor
+    return out
+
+
+def reward_shaping_needs(spec):
+    """(actuator outputs, contact outputs): whether a non-zero weight of the struct needs them bound (torque or work; impact)."""
+    i = _abi.SHAPING_NAMES.index
+    return (spec.w[i("torque")] != 0.0 or spec.w[i("work")] != 0.0), spec.w[i("impact")] != 0.0

@@ -78,6 +78,42 @@ def control_record(learner):
             "skipped_nonfinite": c["skipped_nonfinite"], "skipped_kl": c["skipped_kl"], "lr_mult": round(c["lr_mult"] * c["kl_lr_mult"], 6)}
 
 
+def reward_shaping_arg(text):
+    """--reward-shaping: "torque=1e-4,work=1e-3,failure=1,floor=0" -> the dict of env_spec.reward_shaping_spec (which validates it)."""
+    from openroborl_amd import env_spec
+    out = {}
+    for item in text.split(","):
+        key, sep, value = item.partition("=")
+        try:
+            out[key.strip()] = float(value)
+        except ValueError:
+            sep = ""
+        if not sep:
+            raise argparse.ArgumentTypeError("expected NAME=VALUE[,NAME=VALUE...] with the names %s, got %r" % (", ".join(env_spec.SHAPING_KEYS), item))
+    try:
+        env_spec.reward_shaping_spec(out)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return out
+
+
+def shaping_ramp(args, env, it):
+    """--reward-shaping-ramp: the weights' scale in iteration `it`, 0 -> 1 linearly over the first ITERS iterations; one setter call per
+    iteration until it stands at 1.  The shaping kernel reads the weights in device memory: the captured rollout is not captured again."""
+    if args.reward_shaping is not None and args.reward_shaping_ramp > 0 and it <= args.reward_shaping_ramp:
+        env.set_reward_shaping(args.reward_shaping, scale=min(it / float(args.reward_shaping_ramp), 1.0))
+
+
+def shaping_record(args, env, log_it):
+    """--reward-shaping: {name: mean per step} over the episodes THIS rank finished since the totals were cleared (None without the flag
+    or when the record is not logged), read and cleared where the episode log is."""
+    if args.reward_shaping is None:
+        return None
+    out = {k: round(v, 6) for k, v in env.reward_shaping_stats().items()} if log_it else None
+    env.clear_shaping_totals()
+    return out
+
+
 def obs_norm_check(args, world):
     """--obs-norm and its flags against the modes that have no normaliser; SystemExit with the reason."""
     if not args.obs_norm:
@@ -138,6 +174,14 @@ def main():
                     help="external pushes while training: probability of a velocity kick per robot and env step, its horizontal speed range "
                          "(m/s), optionally the vertical bound (m/s) and the angular bound per axis (rad/s), optionally the env steps at "
                          "the start of an episode without kicks; overrides the task YAML's `push` (default: none; never in --eval)")
+    ap.add_argument("--reward-shaping", type=reward_shaping_arg, default=None, metavar="NAME=W[,NAME=W...]",
+                    help="penalties taken off the imitation reward on the device, inside the captured rollout: weights for torque (mean square "
+                         "torque over the motors, (N m)^2), work (J), action_rate, action_accel (squared first and second differences of the "
+                         "actions), impact (sum of the legs' peak normal forces, N) and failure (1 at a fall, not at a time limit), and floor, "
+                         "the smallest shaped reward (default: none).  Every learner trains on the shaped reward; the return columns stay the "
+                         "imitation return, and every logged record gains \"shaping\": {name: mean per step} over the episodes THIS rank finished")
+    ap.add_argument("--reward-shaping-ramp", type=int, default=0, metavar="ITERS",
+                    help="--reward-shaping: scale the weights from 0 to 1 linearly over the first ITERS iterations (default: full weights from the start)")
     ap.add_argument("--reward-terms", action="store_true",
                     help="also output the five unweighted terms of the imitation reward on the device (pose, velocity, end effector, root pose, "
                          "root velocity): every logged record gains \"reward_terms\": {name: mean per step} over the episodes THIS rank finished "
@@ -252,6 +296,10 @@ def main():
         raise SystemExit("train.py: --learn-std belongs to PPO; the distillation learners neither read nor train a log-std")
     if (args.ent_coef != 0.0 or args.log_std_bounds is not None) and not args.learn_std:
         raise SystemExit("train.py: --ent-coef / --log-std-bounds belong to --learn-std")
+    if args.reward_shaping_ramp and args.reward_shaping is None:
+        raise SystemExit("train.py: --reward-shaping-ramp belongs to --reward-shaping")
+    if args.reward_shaping_ramp < 0:
+        raise SystemExit("train.py: --reward-shaping-ramp must not be negative")
     privileged = args.privileged_critic or bool(args.distill) or args.history_ppo       # somebody reads env.privileged_obs
     rank, world, local = odist.init_from_env()
     obs_norm_check(args, world)
@@ -268,7 +316,7 @@ def main():
                           perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise,
                           reward_terms=args.reward_terms, contact_outputs=args.contact_outputs or privileged,
                           observation_noise_stdev=args.sensor_noise, push=args.push,
-                          push_outputs=privileged and args.push is not None,
+                          push_outputs=privileged and args.push is not None, reward_shaping=args.reward_shaping,
                           **clip_time_kwargs(args), **clip_draw_kwargs(args))     # (bound here, before the rollout graph is captured)
     if args.clip_curriculum is not None and not env.multi_clip:
         raise SystemExit("train.py: --clip-curriculum needs several --motion-file")
@@ -339,6 +387,7 @@ def main():
         merge_segment(buf)
         odist.gather_env_episodes(env, args.horizon)       # its episodes are not the first iteration's
     for it in range(args.iters):
+        shaping_ramp(args, env, it)
         buf = (collector.collect(obs, generator=gen, priv=priv) if collector
                else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv))
         obs = buf["last_obs"]
@@ -368,6 +417,7 @@ def main():
         by_clip = env.episode_returns_by_clip() if log_it and env.multi_clip else None
         by_term = env.episode_reward_terms() if log_it and args.reward_terms else None     # likewise; rank-local
         gait = env.episode_gait() if log_it and args.contact_outputs else None             # likewise
+        shaping = shaping_record(args, env, log_it)                                        # likewise, and cleared where the log is
         if args.clip_curriculum is not None:
             env.clip_curriculum_update()                       # one launch on the log as it stands, before the gather clears it; no sync
         stats = odist.gather_env_episodes(env, args.horizon)   # means come from the exact per-rank sums, not the truncated list
@@ -393,6 +443,8 @@ def main():
                 rec["reward_terms"] = {k: round(v, 4) for k, v in by_term.items()}
             if gait is not None:
                 rec["gait"] = {k: [round(x, 3) for x in v] for k, v in gait.items()}
+            if shaping is not None:
+                rec["shaping"] = shaping
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if rank == 0 and args.save:
@@ -457,6 +509,7 @@ def history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, wo
     obs, priv, hist, first_starts = env.reset(), None, None, None
     t0, samples, log = time.time(), 0, []
     for it in range(args.iters):
+        shaping_ramp(args, env, it)
         buf = (collector.collect(obs, generator=gen, priv=priv, hist=hist) if collector
                else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv, hist=hist, critic_priv=True))
         obs, priv, hist = buf["last_obs"], buf["last_priv"], buf["last_hist"]
@@ -475,6 +528,7 @@ def history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, wo
             learner.check_synced()
         if args.clip_curriculum is not None:
             env.clip_curriculum_update()
+        shaping = shaping_record(args, env, rank == 0 and (it % 10 == 0 or it == args.iters - 1))
         stats = odist.gather_env_episodes(env, args.horizon)
         if rank == 0 and (it % 10 == 0 or it == args.iters - 1):
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
@@ -486,6 +540,8 @@ def history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, wo
                 rec.update({"std_min": round(float(std.min()), 5), "std_max": round(float(std.max()), 5)})
             if control_on(args):
                 rec.update(control_record(learner))
+            if shaping is not None:
+                rec["shaping"] = shaping
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if rank == 0 and args.save:
@@ -523,6 +579,7 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
     for it in range(args.iters):
         beta = args.distill_beta * (max(0.0, 1.0 - it / float(args.distill_beta_iters)) if args.distill_beta_iters > 0 else 1.0)
         driven = int(round(beta * args.num_robot))
+        shaping_ramp(args, env, it)
         collector.teacher_mask.zero_()
         collector.teacher_mask[:driven] = 1
         buf = collector.collect(obs, generator=gen, priv=priv, hist=hist)
@@ -539,6 +596,7 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
         samples += B
         if args.clip_curriculum is not None:
             env.clip_curriculum_update()
+        shaping = shaping_record(args, env, it % 10 == 0 or it == args.iters - 1)
         stats = odist.gather_env_episodes(env, args.horizon)
         if it % 10 == 0 or it == args.iters - 1:
             rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
@@ -549,6 +607,8 @@ def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
                             "total_loss": round(float(loss), 6)})
             if control_on(args):
                 rec.update(control_record(learner))
+            if shaping is not None:
+                rec["shaping"] = shaping
             log.append(rec)
             print(json.dumps(rec), flush=True)
     if args.save:
