@@ -1,8 +1,10 @@
 """What the GPU tests share: the robots' default clips, the env builders with the tests' usual keyword arguments, stress actions,
-float64 copies of the device's records, crafted single-robot records (robot_state), and the canonical forms of the episode log that
-the optional outputs' tests compare.
+float64 copies of the device's records, crafted single-robot records (robot_state), the canonical forms of the episode log that
+the optional outputs' tests compare, and train.py in a child process (run_train, train_refuses).
 torch and the env are imported inside the functions that need them: CPU test helpers import this module for its constants."""
 import os
+import subprocess
+import sys
 
 import numpy as np
 
@@ -15,6 +17,26 @@ CLIP = {"laikago": "laikago_pace", "mini_cheetah": "minicheetah_trot"}
 EPS = 2.0 ** -24
 SOFT_TOES = {"contact_stiffness": 30000.0, "contact_damping": 1000.0, "foot_friction": 3.0}
 HIP, THIGH, KNEE = 0, 1, 2      # the parts of a leg: joint 3 * leg + part
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _train(argv, timeout):
+    return subprocess.run([sys.executable, os.path.join(ROOT, "train.py")] + list(argv), cwd=ROOT, stdout=subprocess.PIPE,
+                          stderr=subprocess.STDOUT, timeout=timeout)
+
+
+def run_train(*argv, timeout=240):
+    """train.py with `argv` in a child process: exit status 0, -> what it printed (stdout and stderr)."""
+    r = _train(argv, timeout)
+    assert r.returncode == 0, r.stdout.decode()[-3000:]
+    return r.stdout.decode()
+
+
+def train_refuses(argv, text):
+    """train.py refuses `argv`: a non-zero exit status and "train.py: " + text in what it printed."""
+    r = _train(argv, 120)
+    out = r.stdout.decode()
+    assert r.returncode != 0 and "train.py: " + text in out, out[-2000:]
 
 
 def make_env(n, files="laikago_pace", **kw):

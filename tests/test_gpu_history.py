@@ -15,18 +15,14 @@ and a cosine above 0.99999)."""
 import ctypes as C
 import json
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests.gpu_kit import mixed_env, short_episodes, stress
+from tests.gpu_kit import mixed_env, run_train, short_episodes, stress
 from tests.test_gpu_teacher import CLIP, PUSH, SENTINEL, mlp64, raw_forward, teacher_model
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENC = {"model/enc_fc0/w:0": (512, 256), "model/enc_fc0/b:0": (256,), "model/enc_fc1/w:0": (256, 48), "model/enc_fc1/b:0": (48,)}
 
 
@@ -527,12 +523,8 @@ def test_train_a_teacher_distill_a_history_student_and_evaluate_it(tmp_path):
     teacher_zip, student_zip, log_path = str(tmp_path / "teacher.zip"), str(tmp_path / "s.zip"), str(tmp_path / "log.json")
     common = ["--num-robot", "64", "--horizon", "8", "--iters", "2", "--push", "0.05,0.2,0.5"]
 
-    def run(*argv):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "train.py")] + list(argv), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)
-        assert r.returncode == 0, r.stdout.decode()[-3000:]
-        return r.stdout.decode()
-    run("--privileged-actor", "--save", teacher_zip, *common)
-    run("--distill", teacher_zip, "--history", "--distill-beta", "0.5", "--save", student_zip, "--log", log_path, *common)
+    run_train("--privileged-actor", "--save", teacher_zip, *common)
+    run_train("--distill", teacher_zip, "--history", "--distill-beta", "0.5", "--save", student_zip, "--log", log_path, *common)
     log = json.load(open(log_path))
     assert log and log[-1]["iter"] == 1 and log[0]["teacher_driven"] == 32
     for rec in log:
@@ -544,5 +536,5 @@ def test_train_a_teacher_distill_a_history_student_and_evaluate_it(tmp_path):
     for k in t:
         if k.startswith("model/pi") or k.startswith("model/vf"):
             assert w[k].tobytes() == t[k].tobytes(), k               # the teacher's actor and critic, bit for bit
-    rec = json.loads(run("--eval", student_zip, "--num-robot", "16").strip().splitlines()[-1])
+    rec = json.loads(run_train("--eval", student_zip, "--num-robot", "16").strip().splitlines()[-1])
     assert rec["robots"] == 16 and math.isfinite(rec["return_mean"])

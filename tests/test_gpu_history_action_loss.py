@@ -13,19 +13,16 @@ at most and 2e-3 steps lr on average)."""
 import ctypes as C
 import json
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests.gpu_kit import run_train
 from tests.test_gpu_history import regress_data, stream, student_model
 from tests.test_gpu_teacher import CLIP, SENTINEL, mlp64
 from tests.test_history_action_loss_cpu import _data as cpu_data, _student as cpu_student
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 5
 SIZES = [1, 15, 16, 17, 33]           # one row; a workgroup's edge on both sides; a third workgroup
 COEFS = [(1.0, 0.0), (0.0, 1.0), (0.7, 0.3)]
@@ -368,16 +365,12 @@ def test_train_a_history_student_with_the_action_loss_and_evaluate_it(tmp_path):
     teacher_zip, student_zip, log_path = str(tmp_path / "T.zip"), str(tmp_path / "s.zip"), str(tmp_path / "log.json")
     common = ["--num-robot", "64", "--horizon", "8", "--iters", "2", "--push", "0.05,0.2,0.5"]
 
-    def run(*argv):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "train.py")] + list(argv), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)
-        assert r.returncode == 0, r.stdout.decode()[-3000:]
-        return r.stdout.decode()
-    run("--privileged-actor", "--save", teacher_zip, *common)
-    run("--distill", teacher_zip, "--history", "--distill-action-coef", "1", "--save", student_zip, "--log", log_path, *common)
+    run_train("--privileged-actor", "--save", teacher_zip, *common)
+    run_train("--distill", teacher_zip, "--history", "--distill-action-coef", "1", "--save", student_zip, "--log", log_path, *common)
     log = json.load(open(log_path))
     assert log and log[-1]["iter"] == 1
     for rec in log:
         assert math.isfinite(rec["action_loss"]) and rec["action_loss"] > 0.0 and math.isfinite(rec["latent_loss"]) and rec["latent_loss"] > 0.0
         assert rec["total_loss"] == pytest.approx(rec["action_loss"] + rec["latent_loss"], rel=1e-4, abs=1e-5)
-    rec = json.loads(run("--eval", student_zip, "--num-robot", "16").strip().splitlines()[-1])
+    rec = json.loads(run_train("--eval", student_zip, "--num-robot", "16").strip().splitlines()[-1])
     assert rec["robots"] == 16 and math.isfinite(rec["return_mean"])

@@ -14,19 +14,15 @@ average; gradients 2e-3 of their scale and a cosine above 0.99999)."""
 import ctypes as C
 import json
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests.gpu_kit import mixed_env, short_episodes
+from tests.gpu_kit import mixed_env, run_train, short_episodes
 from tests.test_gpu_history import ENC, enc64, hinputs, raw_history, stream, student_model
 from tests.test_gpu_teacher import CLIP, PUSH, SENTINEL, mlp64, raw_forward
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 5
 SIZES = [1, 15, 16, 17, 33]           # one row; a workgroup's edge on both sides; a third workgroup
 U = 2.0 ** -24
@@ -493,16 +489,12 @@ def test_train_history_ppo_from_scratch_and_from_its_own_zip_and_evaluate_it(tmp
     first_zip, tuned_zip, log_path = str(tmp_path / "first.zip"), str(tmp_path / "tuned.zip"), str(tmp_path / "log.json")
     common = ["--history-ppo", "--num-robot", "64", "--horizon", "8", "--iters", "2", "--push", "0.05,0.2,0.5"]
 
-    def run(*argv):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "train.py")] + list(argv), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)
-        assert r.returncode == 0, r.stdout.decode()[-3000:]
-        return r.stdout.decode()
-    run("--save", first_zip, *common)
+    run_train("--save", first_zip, *common)
     first = pol.load_parameters(first_zip)
     assert first["model/pi_fc0/w:0"].shape == (208, 512) and first["model/vf_fc0/w:0"].shape == (208, 512)
     for k, shape in ENC.items():
         assert first[k].shape == shape, k
-    run("--model-file", first_zip, "--latent-coef", "0.5", "--save", tuned_zip, "--log", log_path, *common)
+    run_train("--model-file", first_zip, "--latent-coef", "0.5", "--save", tuned_zip, "--log", log_path, *common)
     log = json.load(open(log_path))
     assert log and log[-1]["iter"] == 1
     for rec in log:
@@ -512,5 +504,5 @@ def test_train_history_ppo_from_scratch_and_from_its_own_zip_and_evaluate_it(tmp
     assert sorted(tuned) == sorted(first)
     for k in ("model/enc_fc0/w:0", "model/enc_fc1/w:0", "model/pi_fc0/w:0", "model/vf_fc0/w:0"):       # fine-tuning moves encoder, actor and critic
         assert tuned[k].tobytes() != first[k].tobytes(), k
-    rec = json.loads(run("--eval", tuned_zip, "--num-robot", "16").strip().splitlines()[-1])
+    rec = json.loads(run_train("--eval", tuned_zip, "--num-robot", "16").strip().splitlines()[-1])
     assert rec["robots"] == 16 and math.isfinite(rec["return_mean"])

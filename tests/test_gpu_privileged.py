@@ -14,19 +14,15 @@ quaternion product, the quaternion-to-matrix formula and a three-term dot produc
 max(1, |v|): bound 1e-5 max(1, |v|), a tenfold margin."""
 import ctypes as C
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from openroborl_amd import _abi
 from openroborl_amd import env as envmod
-from tests.gpu_kit import mixed_env, short_episodes
+from tests.gpu_kit import mixed_env, run_train, short_episodes
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = -777.25
 PAD = 5
 PUSH = dict(prob=1.0, lin_vel=(0.1, 0.4), lin_vel_z=0.1, ang_vel=0.3)
@@ -457,10 +453,8 @@ def test_fused_update_with_priv_is_reproducible_bit_for_bit():
 def test_train_with_a_privileged_critic_runs_saves_and_evaluates(tmp_path):
     import json
     zip_path, log_path = str(tmp_path / "priv.zip"), str(tmp_path / "log.json")
-    cmd = [sys.executable, os.path.join(ROOT, "train.py"), "--privileged-critic", "--num-robot", "64", "--horizon", "4", "--iters", "3",
-           "--push", "0.05,0.2,0.5", "--save", zip_path, "--log", log_path]
-    r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)
-    assert r.returncode == 0, r.stdout.decode()[-3000:]
+    run_train("--privileged-critic", "--num-robot", "64", "--horizon", "4", "--iters", "3", "--push", "0.05,0.2,0.5", "--save", zip_path,
+              "--log", log_path)
     log = json.load(open(log_path))
     assert log and log[-1]["iter"] == 2
     for rec in log:
@@ -468,8 +462,5 @@ def test_train_with_a_privileged_critic_runs_saves_and_evaluates(tmp_path):
     from openroborl_amd import policy as pol
     w = pol.load_parameters(zip_path)
     assert w["model/vf_fc0/w:0"].shape == (208, 512) and w["model/pi_fc0/w:0"].shape == (160, 512)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "train.py"), "--eval", zip_path, "--num-robot", "16"], cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)
-    assert r.returncode == 0, r.stdout.decode()[-3000:]
-    rec = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    rec = json.loads(run_train("--eval", zip_path, "--num-robot", "16").strip().splitlines()[-1])
     assert rec["robots"] == 16 and math.isfinite(rec["return_mean"])

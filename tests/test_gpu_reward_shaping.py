@@ -8,9 +8,6 @@ float64 reference and the counted bounds of tests/shaping_refs.py:
   6. train.py --reward-shaping in a child process."""
 import ctypes as C
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,7 +17,6 @@ from tests import gpu_kit as kit
 from tests import shaping_refs as sr
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = -777.25
 SPEC = dict(zip(sr.NAMES, sr.WEIGHTS), floor=-0.5)
 ATTRS = ("shaping_out", "episode_shaping", "shaping_totals", "_shaping_prev")
@@ -333,11 +329,9 @@ def test_the_python_side_refuses_what_the_c_side_would():
 def test_train_with_reward_shaping_and_a_ramp(tmp_path):
     log_path = str(tmp_path / "log.json")
     # --init-std 1: exploration noise of a radian per joint, so that episodes end within the sixteen steps of the run
-    cmd = [sys.executable, os.path.join(ROOT, "train.py"), "--iters", "2", "--num-robot", "64", "--horizon", "8", "--init-std", "1.0",
-           "--reward-shaping", "torque=1e-5,work=0.05,action_rate=0.01,action_accel=0.005,impact=0.002,failure=0.7,floor=-0.5",
-           "--reward-shaping-ramp", "2", "--log", log_path]
-    r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)
-    assert r.returncode == 0, r.stdout.decode()[-3000:]
+    kit.run_train("--iters", "2", "--num-robot", "64", "--horizon", "8", "--init-std", "1.0",
+                  "--reward-shaping", "torque=1e-5,work=0.05,action_rate=0.01,action_accel=0.005,impact=0.002,failure=0.7,floor=-0.5",
+                  "--reward-shaping-ramp", "2", "--log", log_path)
     with open(log_path) as f:
         log = json.load(f)
     assert len(log) == 2

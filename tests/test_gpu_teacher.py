@@ -15,17 +15,13 @@ on average; gradients 2e-3 of their scale and a cosine above 0.99999)."""
 import ctypes as C
 import json
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests.gpu_kit import mixed_env, short_episodes
+from tests.gpu_kit import mixed_env, run_train, short_episodes
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = -777.25
 CLIP = 2.0 * math.pi
 PUSH = dict(prob=1.0, lin_vel=(0.1, 0.4), lin_vel_z=0.1, ang_vel=0.3)
@@ -495,14 +491,10 @@ def test_train_a_teacher_distill_a_student_and_evaluate_both(tmp_path):
     teacher_zip, student_zip, log_path = str(tmp_path / "teacher.zip"), str(tmp_path / "student.zip"), str(tmp_path / "log.json")
     common = ["--num-robot", "64", "--horizon", "8", "--iters", "2", "--push", "0.05,0.2,0.5"]
 
-    def run(*argv):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "train.py")] + list(argv), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240)
-        assert r.returncode == 0, r.stdout.decode()[-3000:]
-        return r.stdout.decode()
-    run("--privileged-actor", "--save", teacher_zip, *common)
+    run_train("--privileged-actor", "--save", teacher_zip, *common)
     w = pol.load_parameters(teacher_zip)
     assert w["model/pi_fc0/w:0"].shape == (208, 512) and w["model/vf_fc0/w:0"].shape == (208, 512)
-    run("--distill", teacher_zip, "--distill-beta", "0.5", "--distill-beta-iters", "2", "--save", student_zip, "--log", log_path, *common)
+    run_train("--distill", teacher_zip, "--distill-beta", "0.5", "--distill-beta-iters", "2", "--save", student_zip, "--log", log_path, *common)
     log = json.load(open(log_path))
     assert log and log[-1]["iter"] == 1 and log[0]["teacher_driven"] == 32 and log[-1]["teacher_driven"] == 16
     for rec in log:
@@ -512,5 +504,5 @@ def test_train_a_teacher_distill_a_student_and_evaluate_both(tmp_path):
         assert w[name].shape == shape, name
     assert w["model/pi_fc0/w:0"].shape == (160, 512)
     for z in (teacher_zip, student_zip):
-        rec = json.loads(run("--eval", z, "--num-robot", "16").strip().splitlines()[-1])
+        rec = json.loads(run_train("--eval", z, "--num-robot", "16").strip().splitlines()[-1])
         assert rec["robots"] == 16 and math.isfinite(rec["return_mean"])

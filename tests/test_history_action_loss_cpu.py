@@ -3,13 +3,12 @@ here, the default coefficients against a learner built without them (bit for bit
 declaration and host-side refusals of orr_history_student_head, and train.py's argument refusals in child processes."""
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 import torch
 
 from openroborl_amd import _abi, _lib, ppo
+from tests.gpu_kit import train_refuses
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B, M = 32, 16
@@ -178,6 +177,4 @@ def test_the_entry_point_is_declared_and_refuses_on_the_host():
     (["--distill", "teacher.zip", "--history", "--distill-latent-coef", "-0.5"], "must not be negative"),
 ])
 def test_train_refuses_the_coefficients_where_they_do_not_belong(argv, text):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "train.py")] + argv, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    out = r.stdout.decode()
-    assert r.returncode != 0 and "train.py: --distill-action-coef / --distill-latent-coef " + text in out, out[-2000:]
+    train_refuses(argv, "--distill-action-coef / --distill-latent-coef " + text)

@@ -6,13 +6,12 @@ Tolerances: the gradients' are tests/test_gpu_teacher.py's for FusedPPO (2e-3 of
 import math
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 import torch
 
 from openroborl_amd import _abi, _lib, ppo
+from tests.gpu_kit import train_refuses
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B = 48
@@ -233,6 +232,4 @@ def test_the_entry_points_are_declared_and_refuse_on_the_host():
     (["--history"], "--history belongs to --distill"),
 ])
 def test_train_refuses_the_arguments_where_they_do_not_belong(argv, text):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "train.py")] + argv, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    out = r.stdout.decode()
-    assert r.returncode != 0 and "train.py: " + text in out, out[-2000:]
+    train_refuses(argv, text)

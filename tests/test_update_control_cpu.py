@@ -282,4 +282,28 @@ def test_train_flags_and_the_linear_schedule():
     with pytest.raises(SystemExit):
         ap.parse_args(["--lr-schedule", "cosine"])
     src = open(os.path.join(ROOT, "train.py")).read()
-    assert src.count("control_kwargs(args") == 7 and src.count("learner.set_lr_mult(lr_mult(args, it))") == 3     # all six learners, all three loops
+    assert src.count("learner.set_lr_mult(lr_mult(args, it))") == 1      # the one training loop
+
+
+def test_make_learner_hands_the_controls_to_every_learner():
+    """train.make_learner on the CPU (--torch-learner): each of the four learners comes back with its control path on and the flags' values;
+    the distillation learners refuse the KL flags."""
+    import pytest
+    from openroborl_amd import ppo
+    train = _train()
+    hist = dict(priv_dim=48, actor_priv_dim=48, history=16)
+    flags = "--torch-learner --lr 3e-4 --minibatch 64 --iters 4 --max-grad-norm 0.5 --lr-schedule linear"
+    for mode, model_kw, more in (("PPO", {}, " --kl-stop 0.05"), ("PPOHistory", hist, " --kl-stop 0.05 --history-ppo --latent-coef 0.25"),
+                                 ("Distill", {}, ""), ("DistillHistory", hist, " --distill-action-coef 0.5")):
+        args = train.arg_parser().parse_args((flags + more).split())
+        learner = train.make_learner(args, ppo.ActorCritic("cpu", seed=4, **model_kw), mode, 256, 0)
+        assert type(learner) is getattr(ppo, mode) and learner.minibatch == 64 and learner.base_lr == 3e-4
+        assert learner.control_on and learner.max_grad_norm == 0.5 and learner.kl_target is None
+        assert learner.kl_stop == (0.05 if mode.startswith("PPO") else None) and learner.kl_on == mode.startswith("PPO")
+        assert getattr(learner, "latent_coef", None) == {"PPOHistory": 0.25, "DistillHistory": 1.0}.get(mode)
+        assert getattr(learner, "action_coef", None) == {"DistillHistory": 0.5}.get(mode)
+        learner.set_lr_mult(train.lr_mult(args, 1))
+        assert learner.lr_mult == 0.75
+    for mode, model_kw in (("Distill", {}), ("DistillHistory", hist)):
+        with pytest.raises(SystemExit, match="belong to PPO"):
+            train.make_learner(train.arg_parser().parse_args((flags + " --kl-stop 0.05").split()), ppo.ActorCritic("cpu", seed=4, **model_kw), mode, 256, 0)

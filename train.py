@@ -26,56 +26,47 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
-def control_args(ap):
-    """The flags of the update controls (learner_hip: orr_update_control + orr_adam_step_ctl; --torch-learner: ppo._UpdateControl)."""
-    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
-                    help="clip the global gradient norm to X before every optimiser step (torch.nn.utils.clip_grad_norm_'s formula); with any of "
-                         "these flags a step whose gradient is not finite is skipped and counted instead of taken")
-    ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="constant",
-                    help="linear: lr * max(1 - it / iters, 0), the reference's schedule='linear' (agents/ppo_imitation.py:296-299), set once per "
-                         "iteration on the device: the captured update is not captured again")
-    ap.add_argument("--kl-stop", type=float, default=None, metavar="X",
-                    help="PPO: stop the rest of an update once a minibatch's approx_kl exceeds X (that minibatch's step included)")
-    ap.add_argument("--kl-target", type=float, default=None, metavar="X",
-                    help="PPO: KL-adaptive learning rate, per step: approx_kl > 2 X: lr / 1.5; 0 < approx_kl < X / 2: lr * 1.5")
-    ap.add_argument("--kl-lr-bounds", type=float, nargs=2, metavar=("LO", "HI"), default=None,
-                    help="--kl-target: the adaptive learning rate stays within [LO, HI] times --lr (default 0.01 10)")
+def sensor_noise_arg(text):
+    """--sensor-noise a,v,t,r,d -> five floats (validated by the env: openroborl_amd.env.sensor_noise_spec)."""
+    parts = text.split(",")
+    if len(parts) != 5:
+        raise argparse.ArgumentTypeError("five comma-separated numbers: motor angle, motor velocity, motor torque, base rpy, base rpy rate")
+    try:
+        return [float(x) for x in parts]
+    except ValueError:
+        raise argparse.ArgumentTypeError("not a number in %r" % (text,))
 
 
-def control_kwargs(args, kl=True):
-    """The learners' keywords for the flags of control_args; no flag, no keyword.  kl: a PPO learner (the distillation learners have no KL)."""
-    if not kl and (args.kl_stop is not None or args.kl_target is not None):
-        raise SystemExit("train.py: --kl-stop / --kl-target belong to PPO; the distillation learners have no KL")
-    if args.kl_lr_bounds is not None and args.kl_target is None:
-        raise SystemExit("train.py: --kl-lr-bounds belongs to --kl-target")
-    kw = {}
-    if args.max_grad_norm is not None:
-        kw["max_grad_norm"] = args.max_grad_norm
-    if args.kl_stop is not None:
-        kw["kl_stop"] = args.kl_stop
-    if args.kl_target is not None:
-        kw["kl_target"] = args.kl_target
-        if args.kl_lr_bounds is not None:
-            kw["kl_lr_bounds"] = tuple(args.kl_lr_bounds)
-    if args.lr_schedule != "constant" and not args.torch_learner:
-        kw["device_lr"] = True
-    return kw
+def push_arg(text):
+    """--push prob,lo,hi[,z,ang[,grace]] -> the env's push dict (validated by the env: openroborl_amd.env.push_spec)."""
+    parts = text.split(",")
+    if len(parts) not in (3, 5, 6):
+        raise argparse.ArgumentTypeError("prob,lo,hi or prob,lo,hi,z,ang or prob,lo,hi,z,ang,grace")
+    try:
+        v = [float(x) for x in parts[:5]]
+        push = dict(prob=v[0], lin_vel=(v[1], v[2]))
+        if len(parts) >= 5:
+            push.update(lin_vel_z=v[3], ang_vel=v[4])
+        if len(parts) == 6:
+            push["grace_steps"] = int(parts[5])
+    except ValueError:
+        raise argparse.ArgumentTypeError("not a number in %r" % (text,))
+    return push
 
 
-def control_on(args):
-    return (args.max_grad_norm is not None or args.kl_stop is not None or args.kl_target is not None or args.lr_schedule != "constant")
-
-
-def lr_mult(args, it):
-    """--lr-schedule: the multiplier of --lr in iteration `it` (linear: the reference's max(1 - it / iters, 0))."""
-    return max(1.0 - it / float(args.iters), 0.0) if args.lr_schedule == "linear" else 1.0
-
-
-def control_record(learner):
-    """What the log line gains when the control path is on; reads and clears the learner's counters (one sync per logged record)."""
-    c = learner.control_stats()
-    return {"grad_norm": round(c["grad_norm_mean"], 5), "grad_norm_max": round(c["grad_norm_max"], 5), "clipped": c["clipped"],
-            "skipped_nonfinite": c["skipped_nonfinite"], "skipped_kl": c["skipped_kl"], "lr_mult": round(c["lr_mult"] * c["kl_lr_mult"], 6)}
+def clip_curriculum_arg(s):
+    """ALPHA,EPS[,METRIC] -> the env's clip_curriculum dict; the refs are the env's defaults (env_spec.clip_curriculum_spec)."""
+    parts = s.split(",")
+    if len(parts) not in (2, 3):
+        raise argparse.ArgumentTypeError("expected ALPHA,EPS[,METRIC], got %r" % (s,))
+    try:
+        cur = {"alpha": float(parts[0]), "eps": float(parts[1])}
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected ALPHA,EPS[,METRIC] with two numbers, got %r" % (s,))
+    cur["metric"] = parts[2] if len(parts) == 3 else "length"
+    if cur["metric"] not in ("length", "return", "step_reward"):
+        raise argparse.ArgumentTypeError("METRIC is length, return or step_reward, not %r" % (cur["metric"],))
+    return cur
 
 
 def reward_shaping_arg(text):
@@ -97,46 +88,23 @@ def reward_shaping_arg(text):
     return out
 
 
-def shaping_ramp(args, env, it):
-    """--reward-shaping-ramp: the weights' scale in iteration `it`, 0 -> 1 linearly over the first ITERS iterations; one setter call per
-    iteration until it stands at 1.  The shaping kernel reads the weights in device memory: the captured rollout is not captured again."""
-    if args.reward_shaping is not None and args.reward_shaping_ramp > 0 and it <= args.reward_shaping_ramp:
-        env.set_reward_shaping(args.reward_shaping, scale=min(it / float(args.reward_shaping_ramp), 1.0))
+def control_args(ap):
+    """The flags of the update controls (learner_hip: orr_update_control + orr_adam_step_ctl; --torch-learner: ppo._UpdateControl)."""
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the global gradient norm to X before every optimiser step (torch.nn.utils.clip_grad_norm_'s formula); with any of "
+                         "these flags a step whose gradient is not finite is skipped and counted instead of taken")
+    ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="constant",
+                    help="linear: lr * max(1 - it / iters, 0), the reference's schedule='linear' (agents/ppo_imitation.py:296-299), set once per "
+                         "iteration on the device: the captured update is not captured again")
+    ap.add_argument("--kl-stop", type=float, default=None, metavar="X",
+                    help="PPO: stop the rest of an update once a minibatch's approx_kl exceeds X (that minibatch's step included)")
+    ap.add_argument("--kl-target", type=float, default=None, metavar="X",
+                    help="PPO: KL-adaptive learning rate, per step: approx_kl > 2 X: lr / 1.5; 0 < approx_kl < X / 2: lr * 1.5")
+    ap.add_argument("--kl-lr-bounds", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                    help="--kl-target: the adaptive learning rate stays within [LO, HI] times --lr (default 0.01 10)")
 
 
-def shaping_record(args, env, log_it):
-    """--reward-shaping: {name: mean per step} over the episodes THIS rank finished since the totals were cleared (None without the flag
-    or when the record is not logged), read and cleared where the episode log is."""
-    if args.reward_shaping is None:
-        return None
-    out = {k: round(v, 6) for k, v in env.reward_shaping_stats().items()} if log_it else None
-    env.clear_shaping_totals()
-    return out
-
-
-def obs_norm_check(args, world):
-    """--obs-norm and its flags against the modes that have no normaliser; SystemExit with the reason."""
-    if not args.obs_norm:
-        if args.obs_norm_freeze_after is not None or args.save_folded:
-            raise SystemExit("train.py: --obs-norm-freeze-after / --save-folded belong to --obs-norm")
-        return
-    if world > 1:
-        raise SystemExit("train.py: --obs-norm runs on one rank: every rank would keep the statistics of its own shard and the replicas would "
-                         "no longer be one policy (merging the records over ranks is not built)")
-    if args.distill or args.history or args.history_ppo:
-        raise SystemExit("train.py: --obs-norm belongs to PPO on a plain, privileged-critic or privileged-actor policy; the history and "
-                         "distillation learners have no normaliser")
-    if args.obs_norm_freeze_after is not None and args.obs_norm_freeze_after < 0:
-        raise SystemExit("train.py: --obs-norm-freeze-after must not be negative")
-
-
-def obs_norm_record(model):
-    """What the log line gains with --obs-norm: the rows behind the statistics and the range of 1 / (sqrt(var) + eps) (one device read)."""
-    rstd = model.obs_norm.rstd
-    return {"obs_norm_count": model.obs_norm.count, "obs_rstd_min": round(float(rstd.min()), 4), "obs_rstd_max": round(float(rstd.max()), 4)}
-
-
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", default="imitation_learning_laikago")
     ap.add_argument("--num-robot", type=int, default=4096)
@@ -267,401 +235,82 @@ def main():
                          "effective epsilon is ~30x larger in the first steps.  Default off: the recorded training runs used torch's form")
     ap.add_argument("--sync-check-every", type=int, default=100, help="replica consistency check (MpiAdam.check_synced, mpi_adam.py:47-48: every 100 updates)")
     ap.add_argument("--tune-gemms", action="store_true", help="let PyTorch's TunableOp pick the learner's GEMM kernels (graph-replayed learner: 16.8 -> 16.3 ms per iteration after ~3 s of tuning)")
-    args = ap.parse_args()
-
-    import torch
-    from openroborl_amd import dist as odist, policy as pol, ppo, rollout
-    from openroborl_amd.env import VecQuadrupedEnv
-
-    if args.tune_gemms:
-        torch.cuda.tunable.enable(True)
-    if args.eval:
-        return evaluate(args, torch, pol, ppo, VecQuadrupedEnv)
-    if args.history_ppo and (args.distill or args.history or args.privileged_critic or args.privileged_actor):
-        raise SystemExit("train.py: --history-ppo is a mode of its own; not with --distill / --history / --privileged-critic / --privileged-actor")
-    if args.latent_coef != 0.0 and not args.history_ppo:
-        raise SystemExit("train.py: --latent-coef belongs to --history-ppo")
-    if not args.latent_coef >= 0.0:
-        raise SystemExit("train.py: --latent-coef must not be negative")
-    args.privileged_critic = args.privileged_critic or args.privileged_actor
-    if args.distill and (args.privileged_critic or args.torch_policy):
-        raise SystemExit("train.py: --distill trains a plain student with the fused rollout; not with --privileged-critic / --privileged-actor / --torch-policy")
-    if args.history and not args.distill:
-        raise SystemExit("train.py: --history belongs to --distill (PPO on a history policy is --history-ppo)")
-    if (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0) and not args.history:
-        raise SystemExit("train.py: --distill-action-coef / --distill-latent-coef belong to --distill --history")
-    if args.distill_action_coef < 0.0 or args.distill_latent_coef < 0.0:
-        raise SystemExit("train.py: --distill-action-coef / --distill-latent-coef must not be negative")
-    if args.learn_std and args.distill:
-        raise SystemExit("train.py: --learn-std belongs to PPO; the distillation learners neither read nor train a log-std")
-    if (args.ent_coef != 0.0 or args.log_std_bounds is not None) and not args.learn_std:
-        raise SystemExit("train.py: --ent-coef / --log-std-bounds belong to --learn-std")
-    if args.reward_shaping_ramp and args.reward_shaping is None:
-        raise SystemExit("train.py: --reward-shaping-ramp belongs to --reward-shaping")
-    if args.reward_shaping_ramp < 0:
-        raise SystemExit("train.py: --reward-shaping-ramp must not be negative")
-    privileged = args.privileged_critic or bool(args.distill) or args.history_ppo       # somebody reads env.privileged_obs
-    rank, world, local = odist.init_from_env()
-    obs_norm_check(args, world)
-    if args.clip_curriculum is not None and world > 1:
-        raise SystemExit("train.py: --clip-curriculum runs on one rank: each rank would adapt to its own episodes and the shards would no "
-                         "longer draw what one env draws (merging the statistics over ranks is not built)")
-    if args.distill and world > 1:
-        raise SystemExit("train.py: --distill runs on one rank")
-    # ORR_BENCH_SINGLE_DEVICE=1 (+ ORR_DIST_BACKEND=gloo): several ranks rehearsed on a one-GPU box (tests), never a measurement
-    dev = torch.device("cuda", 0 if os.environ.get("ORR_BENCH_SINGLE_DEVICE") else local)
-    torch.cuda.set_device(dev)
-    env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
-                          device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
-                          perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise,
-                          reward_terms=args.reward_terms, contact_outputs=args.contact_outputs or privileged,
-                          observation_noise_stdev=args.sensor_noise, push=args.push,
-                          push_outputs=privileged and args.push is not None, reward_shaping=args.reward_shaping,
-                          **clip_time_kwargs(args), **clip_draw_kwargs(args))     # (bound here, before the rollout graph is captured)
-    if args.clip_curriculum is not None and not env.multi_clip:
-        raise SystemExit("train.py: --clip-curriculum needs several --motion-file")
-    if args.history:
-        return distill(args, torch, pol, ppo, rollout, odist, env, history_student(args, torch, pol, ppo, dev), dev)
-    params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
-    if args.history_ppo and params is not None and "model/enc_fc0/w:0" not in params:
-        # a teacher's zip: its nets + a fresh encoder (the rule of --distill --history); the log-std, if any, is the teacher's
-        model = history_student(args, torch, pol, ppo, dev, path=args.model_file, fused=False, std=args.init_std, learn_std=args.learn_std)
-    else:
-        # same seed -> identical replicas.  (--model-file: the critic's width is the file's)
-        wide = args.privileged_actor or args.history_ppo
-        model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic or wide else 0,
-                                actor_priv_dim=pol.PRIV_DIM if wide else 0, std=args.init_std, learn_std=args.learn_std,
-                                history=ppo.HISTORY_STEPS if args.history_ppo else 0, obs_norm=args.obs_norm)
-    if (model.obs_norm is not None) != args.obs_norm:
-        raise SystemExit("train.py: --model-file has %s, --obs-norm says otherwise" % ("a normaliser's statistics" if model.obs_norm is not None else "no statistics"))
-    if model.learn_std != args.learn_std and not args.distill:
-        raise SystemExit("train.py: --model-file has %s, --learn-std says otherwise" % ("a learned log-std" if model.learn_std else "no log-std"))
-    if args.history_ppo:
-        return history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, world)
-    if bool(model.priv_dim) != args.privileged_critic:
-        raise SystemExit("train.py: --model-file has a %s critic, --privileged-critic says otherwise" % ("privileged" if model.priv_dim else "plain"))
-    if bool(model.actor_priv_dim) != args.privileged_actor:
-        raise SystemExit("train.py: --model-file has a %s actor, --privileged-actor says otherwise" % ("privileged" if model.actor_priv_dim else "plain"))
-    if not args.torch_policy:
-        model.enable_fused()
-    if args.distill:
-        return distill(args, torch, pol, ppo, rollout, odist, env, model, dev)
-    # --learn-std: the entropy bonus and the clamp; without it no keyword at all, the learners' defaults
-    entropy = dict(ent_coef=args.ent_coef, log_std_bounds=tuple(args.log_std_bounds or ppo.LOG_STD_BOUNDS)) if args.learn_std else {}
-    if args.torch_learner:
-        learner = ppo.PPO(model, lr=args.lr, minibatch=args.minibatch, **entropy, **control_kwargs(args))
-    else:
-        from openroborl_amd import learner_hip
-        # equal minibatches only (static buffers of the graph-replayed update): the largest size <= --minibatch that divides the
-        # segment, e.g. --num-robot 1000 x horizon 32 = 32000 samples run as 2 x 16000 instead of failing on 16384
-        mb = learner_hip.FusedPPO.fit_minibatch(args.num_robot * args.horizon, args.minibatch)
-        if mb != min(args.minibatch, args.num_robot * args.horizon) and rank == 0:
-            print("train.py: minibatch %d -> %d (must divide the %d samples of a segment)" % (args.minibatch, mb, args.num_robot * args.horizon),
-                  file=sys.stderr)
-        if mb < 256 and args.num_robot * args.horizon >= 4096:
-            raise SystemExit("train.py: %d samples per segment have no divisor between 256 and %d; pick another --num-robot / --horizon "
-                             "or use --torch-learner (handles a short last minibatch)" % (args.num_robot * args.horizon, args.minibatch))
-        learner = learner_hip.FusedPPO(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam, **entropy, **control_kwargs(args))
-        learner.sync()                                        # MpiAdam.sync before training (ppo_imitation.py:274)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(args.seed * 1000 + rank)
-    obs = env.reset()
-    t0 = time.time()
-    samples = 0
-    log = []
-    first_starts = None                   # episode_starts of a segment's first step = the last step's done flags of the previous segment
-    priv = None                           # --privileged-critic: the privileged observation that belongs to `obs` (None: right after the reset)
-    # static rollout buffers + the segment replayed as one hipGraph (fused policy only); --torch-policy keeps the eager collector
-    collector = None if args.torch_policy else rollout.GraphRollout(env, model, args.horizon)
-
-    def merge_segment(buf):
-        """--obs-norm: the segment into the statistics, and the fold into the fused layer 0 at the next refresh; after the update, never before"""
-        T, n = buf["rewards"].shape
-        model.update_obs_norm(buf["obs"].reshape(T * n, -1), *((buf["priv"].reshape(T * n, -1),) if model.priv_norm is not None else ()))
-        model.mark_updated()
-    if args.obs_norm and model.obs_norm.count == 0:
-        # one segment whose only use is to seed the statistics: the policy never acts, and the learner never learns, on the identity
-        buf = (collector.collect(obs, generator=gen, priv=priv) if collector
-               else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv))
-        obs, priv, first_starts = buf["last_obs"], buf.get("last_priv"), buf["dones"][-1].clone()
-        merge_segment(buf)
-        odist.gather_env_episodes(env, args.horizon)       # its episodes are not the first iteration's
-    for it in range(args.iters):
-        shaping_ramp(args, env, it)
-        buf = (collector.collect(obs, generator=gen, priv=priv) if collector
-               else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv))
-        obs = buf["last_obs"]
-        priv = buf.get("last_priv")
-        with torch.no_grad():
-            boot = model.value(obs, priv)
-        # bootstrap with the critic at the segment end (the reference uses 0 there, imitation_runners.py:98-100;
-        # with 32-step segments that bias would dominate)
-        adv, ret = rollout.gae_fused(buf["rewards"], buf["vpred"], buf["dones"], 0.95, 0.95, bootstrap=boot, normalize=True, eps=1e-8,
-                                     legacy_gae_index=args.legacy_gae_index, first_starts=first_starts)
-        first_starts = buf["dones"][-1].clone()               # the collector's buffers are overwritten by the next segment
-        T, n = buf["rewards"].shape
-        if args.lr_schedule != "constant":
-            learner.set_lr_mult(lr_mult(args, it))
-        losses = learner.update(buf["obs"].reshape(T * n, -1), buf["actions"].reshape(T * n, -1), adv.reshape(-1),
-                                ret.reshape(-1), old_logp=buf["logp"].reshape(-1) if "logp" in buf else None,
-                                epochs=args.epochs, generator=gen, priv=buf["priv"].reshape(T * n, -1) if model.priv_dim else None)
-        surr, vf = losses[0], losses[1]      # --learn-std: three more, ppo.STAT_NAMES
-        if args.obs_norm and (args.obs_norm_freeze_after is None or it < args.obs_norm_freeze_after):
-            merge_segment(buf)
-        samples += T * n * world
-        # (> 1 rank, or ORR_FORCE_DIST=1: the one-rank rehearsal of the several-ranks path on RCCL runs the check too)
-        if (world > 1 or os.environ.get("ORR_FORCE_DIST", "0") == "1") and args.sync_check_every > 0 and it % args.sync_check_every == args.sync_check_every - 1 and hasattr(learner, "check_synced"):
-            learner.check_synced()                            # like MpiAdam every 100 updates (mpi_adam.py:47-48)
-        log_it = rank == 0 and (it % 10 == 0 or it == args.iters - 1)
-        # this rank's episodes of the segment by clip (read before the gather below clears the log)
-        by_clip = env.episode_returns_by_clip() if log_it and env.multi_clip else None
-        by_term = env.episode_reward_terms() if log_it and args.reward_terms else None     # likewise; rank-local
-        gait = env.episode_gait() if log_it and args.contact_outputs else None             # likewise
-        shaping = shaping_record(args, env, log_it)                                        # likewise, and cleared where the log is
-        if args.clip_curriculum is not None:
-            env.clip_curriculum_update()                       # one launch on the log as it stands, before the gather clears it; no sync
-        stats = odist.gather_env_episodes(env, args.horizon)   # means come from the exact per-rank sums, not the truncated list
-        if log_it:
-            rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2),
-                   "mean_step_reward": round(float(buf["rewards"].mean()), 4),
-                   "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2),
-                   "episodes": stats.sums[0], "episodes_unlogged": stats[3] - max(stats.sums[0] - int(stats[0].numel()), 0),
-                   "max_ep_steps": int(env.field_int("MAX_EP_STEPS").max()), "surr": round(float(surr), 4), "vf": round(float(vf), 4)}
-            if args.learn_std:           # the twelve stds: one device read per logged record
-                std = model.std
-                rec.update({k: round(float(v), 6) for k, v in zip(ppo.STAT_NAMES[2:], losses[2:])})
-                rec.update({"std_min": round(float(std.min()), 5), "std_max": round(float(std.max()), 5)})
-            if control_on(args):
-                rec.update(control_record(learner))
-            if args.obs_norm:
-                rec.update(obs_norm_record(model))
-            if by_clip is not None:
-                rec["ep_ret_mean_by_clip"] = {clip_name(env, c): round(r, 2) for c, (r, _) in sorted(by_clip.items())}
-            if args.clip_curriculum is not None or args.clip_weights is not None:
-                rec["clip_prob"] = clip_prob_record(env)
-            if by_term is not None:
-                rec["reward_terms"] = {k: round(v, 4) for k, v in by_term.items()}
-            if gait is not None:
-                rec["gait"] = {k: [round(x, 3) for x in v] for k, v in gait.items()}
-            if shaping is not None:
-                rec["shaping"] = shaping
-            log.append(rec)
-            print(json.dumps(rec), flush=True)
-    if rank == 0 and args.save:
-        pol.save_parameters_zip(args.save, model.state_dict())
-    if rank == 0 and args.save_folded:
-        pol.save_folded(args.save_folded, model.state_dict())
-    if rank == 0 and args.log:
-        with open(args.log, "w") as f:
-            json.dump(log, f, indent=1)
-    env.close()
-    if torch.distributed.is_available() and torch.distributed.is_initialized():
-        torch.distributed.destroy_process_group()
+    return ap
 
 
-def history_student(args, torch, pol, ppo, dev, path=None, fused=True, **model_kw):
-    """--distill TEACHER.zip --history: the teacher's parameters + a fresh encoder (seeded by --seed), on the fused path.  --history-ppo with a
-    teacher's --model-file (`path`): the same rule, the model's std arguments in model_kw."""
-    params = pol.load_parameters(path or args.distill)
-    if any(k.startswith(pol.NORM_PREFIXES) for k in params):
-        # the teacher's layer 0 expects normalised inputs, and a history policy has no normaliser: copying its weights would run them on raw
-        # observations and on the encoder's raw estimate, without a word
-        raise SystemExit("train.py: %s is a teacher trained with --obs-norm; a history policy with an observation normaliser is not built "
-                         "(the encoder's frames are a subset of the observation): train the teacher without --obs-norm"
-                         % (path or args.distill))
-    if np.shape(params["model/pi_fc0/w:0"])[0] != 160 + pol.PRIV_DIM:
-        raise SystemExit("train.py: %s needs a teacher with a privileged actor (--privileged-actor)" % ("--history-ppo --model-file" if path else "--history"))
-    student = ppo.ActorCritic(dev, seed=args.seed, priv_dim=pol.PRIV_DIM, actor_priv_dim=pol.PRIV_DIM, history=ppo.HISTORY_STEPS, **model_kw)
-    with torch.no_grad():
-        for k, v in params.items():
-            if k.startswith("model/enc_"):
-                continue                     # a history student as the teacher: its actor and critic, a fresh encoder all the same
-            if k in student.p:
-                student.p[k].copy_(torch.as_tensor(v))
-            else:
-                student.extra[k] = np.asarray(v, dtype=np.float32).copy()
-    return student.enable_fused() if fused else student
+def control_kwargs(args, kl=True):
+    """The learners' keywords for the flags of control_args; no flag, no keyword.  kl: a PPO learner (the distillation learners have no KL)."""
+    if not kl and (args.kl_stop is not None or args.kl_target is not None):
+        raise SystemExit("train.py: --kl-stop / --kl-target belong to PPO; the distillation learners have no KL")
+    if args.kl_lr_bounds is not None and args.kl_target is None:
+        raise SystemExit("train.py: --kl-lr-bounds belongs to --kl-target")
+    kw = {}
+    if args.max_grad_norm is not None:
+        kw["max_grad_norm"] = args.max_grad_norm
+    if args.kl_stop is not None:
+        kw["kl_stop"] = args.kl_stop
+    if args.kl_target is not None:
+        kw["kl_target"] = args.kl_target
+        if args.kl_lr_bounds is not None:
+            kw["kl_lr_bounds"] = tuple(args.kl_lr_bounds)
+    if args.lr_schedule != "constant" and not args.torch_learner:
+        kw["device_lr"] = True
+    return kw
 
 
-def history_ppo(args, torch, pol, ppo, rollout, odist, env, model, dev, rank, world):
-    """--history-ppo: PPO on a history policy.  The collector hands hist[k] to the actor and priv[k], the true row, to the critic
-    (critic_priv=True), the bootstrap is the critic on the last true row, and the learner trains actor, critic and encoder."""
-    if not model.history:
-        raise SystemExit("train.py: --history-ppo could not make a history policy of --model-file")
-    if not args.torch_policy:
-        model.enable_fused()
-    B = args.num_robot * args.horizon
-    entropy = dict(ent_coef=args.ent_coef, log_std_bounds=tuple(args.log_std_bounds or ppo.LOG_STD_BOUNDS)) if args.learn_std else {}
-    if args.torch_learner:
-        learner = ppo.PPOHistory(model, lr=args.lr, minibatch=args.minibatch, latent_coef=args.latent_coef, **entropy, **control_kwargs(args))
-    else:
-        from openroborl_amd import learner_hip
-        mb = learner_hip.FusedPPOHistory.fit_minibatch(B, args.minibatch)
-        if mb < 256 and B >= 4096:
-            raise SystemExit("train.py: %d samples per segment have no divisor between 256 and %d; pick another --num-robot / --horizon "
-                             "or use --torch-learner (handles a short last minibatch)" % (B, args.minibatch))
-        learner = learner_hip.FusedPPOHistory(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam, latent_coef=args.latent_coef, **entropy,
-                                              **control_kwargs(args))
-        learner.sync()
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(args.seed * 1000 + rank)
-    collector = None if args.torch_policy else rollout.GraphRollout(env, model, args.horizon, critic_priv=True)
-    obs, priv, hist, first_starts = env.reset(), None, None, None
-    t0, samples, log = time.time(), 0, []
-    for it in range(args.iters):
-        shaping_ramp(args, env, it)
-        buf = (collector.collect(obs, generator=gen, priv=priv, hist=hist) if collector
-               else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv, hist=hist, critic_priv=True))
-        obs, priv, hist = buf["last_obs"], buf["last_priv"], buf["last_hist"]
-        with torch.no_grad():
-            boot = model.value(obs, priv)
-        adv, ret = rollout.gae_fused(buf["rewards"], buf["vpred"], buf["dones"], 0.95, 0.95, bootstrap=boot, normalize=True, eps=1e-8,
-                                     legacy_gae_index=args.legacy_gae_index, first_starts=first_starts)
-        first_starts = buf["dones"][-1].clone()
-        if args.lr_schedule != "constant":
-            learner.set_lr_mult(lr_mult(args, it))
-        losses = learner.update(buf["obs"].reshape(B, -1), buf["hist"].reshape(B, -1), buf["priv"].reshape(B, -1), buf["actions"].reshape(B, -1),
-                                adv.reshape(-1), ret.reshape(-1), old_logp=buf["logp"].reshape(-1) if "logp" in buf else None,
-                                epochs=args.epochs, generator=gen)
-        samples += B * world
-        if (world > 1 or os.environ.get("ORR_FORCE_DIST", "0") == "1") and args.sync_check_every > 0 and it % args.sync_check_every == args.sync_check_every - 1 and hasattr(learner, "check_synced"):
-            learner.check_synced()
-        if args.clip_curriculum is not None:
-            env.clip_curriculum_update()
-        shaping = shaping_record(args, env, rank == 0 and (it % 10 == 0 or it == args.iters - 1))
-        stats = odist.gather_env_episodes(env, args.horizon)
-        if rank == 0 and (it % 10 == 0 or it == args.iters - 1):
-            rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
-                   "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2), "episodes": stats.sums[0],
-                   "surr": round(float(losses[0]), 4), "vf": round(float(losses[1]), 4), "latent_loss": round(float(losses[-1]), 6)}
-            if args.learn_std:
-                std = model.std
-                rec.update({k: round(float(v), 6) for k, v in zip(ppo.STAT_NAMES[2:], losses[2:5])})
-                rec.update({"std_min": round(float(std.min()), 5), "std_max": round(float(std.max()), 5)})
-            if control_on(args):
-                rec.update(control_record(learner))
-            if shaping is not None:
-                rec["shaping"] = shaping
-            log.append(rec)
-            print(json.dumps(rec), flush=True)
-    if rank == 0 and args.save:
-        pol.save_parameters_zip(args.save, model.state_dict())
-    if rank == 0 and args.log:
-        with open(args.log, "w") as f:
-            json.dump(log, f, indent=1)
-    env.close()
-    if torch.distributed.is_available() and torch.distributed.is_initialized():
-        torch.distributed.destroy_process_group()
+def control_on(args):
+    return (args.max_grad_norm is not None or args.kl_stop is not None or args.kl_target is not None or args.lr_schedule != "constant")
 
 
-def distill(args, torch, pol, ppo, rollout, odist, env, student, dev):
-    """--distill TEACHER.zip: DAgger on the device.  Each iteration collects a segment in which the student drives (all robots but the
-    share --distill-beta, which the teacher drives) and the teacher labels every visited state, then regresses the student's mean on the labels.
-    --history: the student reads its sensor history, and its encoder's output is regressed on the segment's privileged observations instead."""
-    teacher_params = {k: v for k, v in pol.load_parameters(args.distill).items() if not k.startswith("model/enc_")}
-    teacher = ppo.ActorCritic(dev, params=teacher_params).enable_fused()
-    B = args.num_robot * args.horizon
-    loss_name = "latent_loss" if args.history else "distill_loss"
-    coefs = dict(action_coef=args.distill_action_coef, latent_coef=args.distill_latent_coef) if args.history else {}
-    with_actions = args.history and (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0)      # the log carries both losses
-    if args.torch_learner:
-        learner = (ppo.DistillHistory if args.history else ppo.Distill)(student, lr=args.lr, minibatch=args.minibatch, **coefs,
-                                                                        **control_kwargs(args, kl=False))
-    else:
-        from openroborl_amd import learner_hip
-        cls = learner_hip.FusedDistillHistory if args.history else learner_hip.FusedDistill
-        learner = cls(student, lr=args.lr, minibatch=cls.fit_minibatch(B, args.minibatch), **coefs, **control_kwargs(args, kl=False))
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(args.seed * 1000)
-    collector = rollout.GraphRollout(env, student, args.horizon, teacher=teacher)
-    obs, priv, hist = env.reset(), None, None
-    t0, samples, log = time.time(), 0, []
-    for it in range(args.iters):
-        beta = args.distill_beta * (max(0.0, 1.0 - it / float(args.distill_beta_iters)) if args.distill_beta_iters > 0 else 1.0)
-        driven = int(round(beta * args.num_robot))
-        shaping_ramp(args, env, it)
-        collector.teacher_mask.zero_()
-        collector.teacher_mask[:driven] = 1
-        buf = collector.collect(obs, generator=gen, priv=priv, hist=hist)
-        obs, priv, hist = buf["last_obs"], buf["last_priv"], buf.get("last_hist")
-        if args.lr_schedule != "constant":
-            learner.set_lr_mult(lr_mult(args, it))
-        if args.history and args.distill_action_coef > 0.0:
-            loss = learner.update(buf["hist"].reshape(B, -1), buf["priv"].reshape(B, -1), epochs=args.epochs, generator=gen,
-                                  obs=buf["obs"].reshape(B, -1), target_mean=buf["teacher_mean"].reshape(B, 12))
-        elif args.history:
-            loss = learner.update(buf["hist"].reshape(B, -1), buf["priv"].reshape(B, -1), epochs=args.epochs, generator=gen)
-        else:
-            loss = learner.update(buf["obs"].reshape(B, -1), buf["teacher_mean"].reshape(B, 12), epochs=args.epochs, generator=gen)
-        samples += B
-        if args.clip_curriculum is not None:
-            env.clip_curriculum_update()
-        shaping = shaping_record(args, env, it % 10 == 0 or it == args.iters - 1)
-        stats = odist.gather_env_episodes(env, args.horizon)
-        if it % 10 == 0 or it == args.iters - 1:
-            rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
-                   "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2), "episodes": stats.sums[0],
-                   loss_name: round(float(loss), 6), "teacher_driven": driven}
-            if with_actions:             # loss_name then holds the latent regression's own loss, as it does without the action loss
-                rec.update({"latent_loss": round(learner.last_latent_loss, 6), "action_loss": round(learner.last_action_loss, 6),
-                            "total_loss": round(float(loss), 6)})
-            if control_on(args):
-                rec.update(control_record(learner))
-            if shaping is not None:
-                rec["shaping"] = shaping
-            log.append(rec)
-            print(json.dumps(rec), flush=True)
-    if args.save:
-        pol.save_parameters_zip(args.save, student.state_dict())
-    if args.log:
-        with open(args.log, "w") as f:
-            json.dump(log, f, indent=1)
-    env.close()
-    if torch.distributed.is_available() and torch.distributed.is_initialized():
-        torch.distributed.destroy_process_group()
+def lr_mult(args, it):
+    """--lr-schedule: the multiplier of --lr in iteration `it` (linear: the reference's max(1 - it / iters, 0))."""
+    return max(1.0 - it / float(args.iters), 0.0) if args.lr_schedule == "linear" else 1.0
 
 
-def sensor_noise_arg(text):
-    """--sensor-noise a,v,t,r,d -> five floats (validated by the env: openroborl_amd.env.sensor_noise_spec)."""
-    parts = text.split(",")
-    if len(parts) != 5:
-        raise argparse.ArgumentTypeError("five comma-separated numbers: motor angle, motor velocity, motor torque, base rpy, base rpy rate")
-    try:
-        return [float(x) for x in parts]
-    except ValueError:
-        raise argparse.ArgumentTypeError("not a number in %r" % (text,))
+def control_record(learner):
+    """What the log line gains when the control path is on; reads and clears the learner's counters (one sync per logged record)."""
+    c = learner.control_stats()
+    return {"grad_norm": round(c["grad_norm_mean"], 5), "grad_norm_max": round(c["grad_norm_max"], 5), "clipped": c["clipped"],
+            "skipped_nonfinite": c["skipped_nonfinite"], "skipped_kl": c["skipped_kl"], "lr_mult": round(c["lr_mult"] * c["kl_lr_mult"], 6)}
 
 
-def push_arg(text):
-    """--push prob,lo,hi[,z,ang[,grace]] -> the env's push dict (validated by the env: openroborl_amd.env.push_spec)."""
-    parts = text.split(",")
-    if len(parts) not in (3, 5, 6):
-        raise argparse.ArgumentTypeError("prob,lo,hi or prob,lo,hi,z,ang or prob,lo,hi,z,ang,grace")
-    try:
-        v = [float(x) for x in parts[:5]]
-        push = dict(prob=v[0], lin_vel=(v[1], v[2]))
-        if len(parts) >= 5:
-            push.update(lin_vel_z=v[3], ang_vel=v[4])
-        if len(parts) == 6:
-            push["grace_steps"] = int(parts[5])
-    except ValueError:
-        raise argparse.ArgumentTypeError("not a number in %r" % (text,))
-    return push
+def shaping_ramp(args, env, it):
+    """--reward-shaping-ramp: the weights' scale in iteration `it`, 0 -> 1 linearly over the first ITERS iterations; one setter call per
+    iteration until it stands at 1.  The shaping kernel reads the weights in device memory: the captured rollout is not captured again."""
+    if args.reward_shaping is not None and args.reward_shaping_ramp > 0 and it <= args.reward_shaping_ramp:
+        env.set_reward_shaping(args.reward_shaping, scale=min(it / float(args.reward_shaping_ramp), 1.0))
 
 
-def clip_curriculum_arg(s):
-    """ALPHA,EPS[,METRIC] -> the env's clip_curriculum dict; the refs are the env's defaults (env_spec.clip_curriculum_spec)."""
-    parts = s.split(",")
-    if len(parts) not in (2, 3):
-        raise argparse.ArgumentTypeError("expected ALPHA,EPS[,METRIC], got %r" % (s,))
-    try:
-        cur = {"alpha": float(parts[0]), "eps": float(parts[1])}
-    except ValueError:
-        raise argparse.ArgumentTypeError("expected ALPHA,EPS[,METRIC] with two numbers, got %r" % (s,))
-    cur["metric"] = parts[2] if len(parts) == 3 else "length"
-    if cur["metric"] not in ("length", "return", "step_reward"):
-        raise argparse.ArgumentTypeError("METRIC is length, return or step_reward, not %r" % (cur["metric"],))
-    return cur
+def shaping_record(args, env, log_it):
+    """--reward-shaping: {name: mean per step} over the episodes THIS rank finished since the totals were cleared (None without the flag
+    or when the record is not logged), read and cleared where the episode log is."""
+    if args.reward_shaping is None:
+        return None
+    out = {k: round(v, 6) for k, v in env.reward_shaping_stats().items()} if log_it else None
+    env.clear_shaping_totals()
+    return out
+
+
+def obs_norm_check(args, world):
+    """--obs-norm and its flags against the modes that have no normaliser; SystemExit with the reason."""
+    if not args.obs_norm:
+        if args.obs_norm_freeze_after is not None or args.save_folded:
+            raise SystemExit("train.py: --obs-norm-freeze-after / --save-folded belong to --obs-norm")
+        return
+    if world > 1:
+        raise SystemExit("train.py: --obs-norm runs on one rank: every rank would keep the statistics of its own shard and the replicas would "
+                         "no longer be one policy (merging the records over ranks is not built)")
+    if args.distill or args.history or args.history_ppo:
+        raise SystemExit("train.py: --obs-norm belongs to PPO on a plain, privileged-critic or privileged-actor policy; the history and "
+                         "distillation learners have no normaliser")
+    if args.obs_norm_freeze_after is not None and args.obs_norm_freeze_after < 0:
+        raise SystemExit("train.py: --obs-norm-freeze-after must not be negative")
+
+
+def obs_norm_record(model):
+    """What the log line gains with --obs-norm: the rows behind the statistics and the range of 1 / (sqrt(var) + eps) (one device read)."""
+    rstd = model.obs_norm.rstd
+    return {"obs_norm_count": model.obs_norm.count, "obs_rstd_min": round(float(rstd.min()), 4), "obs_rstd_max": round(float(rstd.max()), 4)}
 
 
 def clip_draw_kwargs(args):
@@ -692,6 +341,353 @@ def clip_time_kwargs(args):
 def clip_name(env, clip_id):
     """'<id>:<file name>' of a clip of the env (ids keep a file listed twice apart)."""
     return "%d:%s" % (clip_id, os.path.splitext(os.path.basename(env.clips[clip_id].path))[0])
+
+
+def check_args(args, world):
+    """The flags against the modes and the rank count they do not belong to (args.privileged_critic includes --privileged-actor by now)."""
+    if args.history_ppo and (args.distill or args.history or args.privileged_critic or args.privileged_actor):
+        raise SystemExit("train.py: --history-ppo is a mode of its own; not with --distill / --history / --privileged-critic / --privileged-actor")
+    if args.latent_coef != 0.0 and not args.history_ppo:
+        raise SystemExit("train.py: --latent-coef belongs to --history-ppo")
+    if not args.latent_coef >= 0.0:
+        raise SystemExit("train.py: --latent-coef must not be negative")
+    if args.distill and (args.privileged_critic or args.torch_policy):
+        raise SystemExit("train.py: --distill trains a plain student with the fused rollout; not with --privileged-critic / --privileged-actor / --torch-policy")
+    if args.history and not args.distill:
+        raise SystemExit("train.py: --history belongs to --distill (PPO on a history policy is --history-ppo)")
+    if (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0) and not args.history:
+        raise SystemExit("train.py: --distill-action-coef / --distill-latent-coef belong to --distill --history")
+    if args.distill_action_coef < 0.0 or args.distill_latent_coef < 0.0:
+        raise SystemExit("train.py: --distill-action-coef / --distill-latent-coef must not be negative")
+    if args.learn_std and args.distill:
+        raise SystemExit("train.py: --learn-std belongs to PPO; the distillation learners neither read nor train a log-std")
+    if (args.ent_coef != 0.0 or args.log_std_bounds is not None) and not args.learn_std:
+        raise SystemExit("train.py: --ent-coef / --log-std-bounds belong to --learn-std")
+    if args.reward_shaping_ramp and args.reward_shaping is None:
+        raise SystemExit("train.py: --reward-shaping-ramp belongs to --reward-shaping")
+    if args.reward_shaping_ramp < 0:
+        raise SystemExit("train.py: --reward-shaping-ramp must not be negative")
+    obs_norm_check(args, world)
+    if args.clip_curriculum is not None and world > 1:
+        raise SystemExit("train.py: --clip-curriculum runs on one rank: each rank would adapt to its own episodes and the shards would no "
+                         "longer draw what one env draws (merging the statistics over ranks is not built)")
+    if args.distill and world > 1:
+        raise SystemExit("train.py: --distill runs on one rank")
+
+
+def history_student(args, torch, pol, ppo, dev, path=None, fused=True, **model_kw):
+    """--distill TEACHER.zip --history: the teacher's parameters + a fresh encoder (seeded by --seed), on the fused path.  --history-ppo with a
+    teacher's --model-file (`path`): the same rule, the model's std arguments in model_kw."""
+    params = pol.load_parameters(path or args.distill)
+    if any(k.startswith(pol.NORM_PREFIXES) for k in params):
+        # the teacher's layer 0 expects normalised inputs, and a history policy has no normaliser: copying its weights would run them on raw
+        # observations and on the encoder's raw estimate, without a word
+        raise SystemExit("train.py: %s is a teacher trained with --obs-norm; a history policy with an observation normaliser is not built "
+                         "(the encoder's frames are a subset of the observation): train the teacher without --obs-norm"
+                         % (path or args.distill))
+    if np.shape(params["model/pi_fc0/w:0"])[0] != 160 + pol.PRIV_DIM:
+        raise SystemExit("train.py: %s needs a teacher with a privileged actor (--privileged-actor)" % ("--history-ppo --model-file" if path else "--history"))
+    student = ppo.ActorCritic(dev, seed=args.seed, priv_dim=pol.PRIV_DIM, actor_priv_dim=pol.PRIV_DIM, history=ppo.HISTORY_STEPS, **model_kw)
+    with torch.no_grad():
+        for k, v in params.items():
+            if k.startswith("model/enc_"):
+                continue                     # a history student as the teacher: its actor and critic, a fresh encoder all the same
+            if k in student.p:
+                student.p[k].copy_(torch.as_tensor(v))
+            else:
+                student.extra[k] = np.asarray(v, dtype=np.float32).copy()
+    return student.enable_fused() if fused else student
+
+
+def make_model(args, dev):
+    """The policy of the run: fresh, from --model-file, or (--distill --history; --history-ppo on a teacher's zip) a teacher's nets + a fresh
+    encoder.  SystemExit where --model-file and the flags disagree.  On the fused path unless --torch-policy."""
+    import torch
+    from openroborl_amd import policy as pol, ppo
+    if args.history:
+        return history_student(args, torch, pol, ppo, dev)
+    params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
+    if args.history_ppo and params is not None and "model/enc_fc0/w:0" not in params:
+        # a teacher's zip: its nets + a fresh encoder (the rule of --distill --history); the log-std, if any, is the teacher's
+        model = history_student(args, torch, pol, ppo, dev, path=args.model_file, fused=False, std=args.init_std, learn_std=args.learn_std)
+    else:
+        # same seed -> identical replicas.  (--model-file: the critic's width is the file's)
+        wide = args.privileged_actor or args.history_ppo
+        model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM if args.privileged_critic or wide else 0,
+                                actor_priv_dim=pol.PRIV_DIM if wide else 0, std=args.init_std, learn_std=args.learn_std,
+                                history=ppo.HISTORY_STEPS if args.history_ppo else 0, obs_norm=args.obs_norm)
+    if (model.obs_norm is not None) != args.obs_norm:
+        raise SystemExit("train.py: --model-file has %s, --obs-norm says otherwise" % ("a normaliser's statistics" if model.obs_norm is not None else "no statistics"))
+    if model.learn_std != args.learn_std and not args.distill:
+        raise SystemExit("train.py: --model-file has %s, --learn-std says otherwise" % ("a learned log-std" if model.learn_std else "no log-std"))
+    if args.history_ppo and not model.history:
+        raise SystemExit("train.py: --history-ppo could not make a history policy of --model-file")
+    if not args.history_ppo and bool(model.priv_dim) != args.privileged_critic:
+        raise SystemExit("train.py: --model-file has a %s critic, --privileged-critic says otherwise" % ("privileged" if model.priv_dim else "plain"))
+    if not args.history_ppo and bool(model.actor_priv_dim) != args.privileged_actor:
+        raise SystemExit("train.py: --model-file has a %s actor, --privileged-actor says otherwise" % ("privileged" if model.actor_priv_dim else "plain"))
+    if not args.torch_policy:
+        model.enable_fused()
+    return model
+
+
+def make_learner(args, model, mode, num_samples, rank):
+    """The learner of `mode` ("PPO", "PPOHistory", "Distill" or "DistillHistory"): ppo.<mode> with --torch-learner, else learner_hip.Fused<mode>
+    with the largest minibatch <= --minibatch that divides the segment's `num_samples`."""
+    from openroborl_amd import ppo
+    is_ppo = mode.startswith("PPO")
+    kw = control_kwargs(args, kl=is_ppo)
+    if is_ppo and args.learn_std:        # the entropy bonus and the clamp; without the flag no keyword at all, the learners' defaults
+        kw.update(ent_coef=args.ent_coef, log_std_bounds=tuple(args.log_std_bounds or ppo.LOG_STD_BOUNDS))
+    if mode == "PPOHistory":
+        kw["latent_coef"] = args.latent_coef
+    if mode == "DistillHistory":
+        kw.update(action_coef=args.distill_action_coef, latent_coef=args.distill_latent_coef)
+    if args.torch_learner:
+        return getattr(ppo, mode)(model, lr=args.lr, minibatch=args.minibatch, **kw)
+    from openroborl_amd import learner_hip
+    cls = getattr(learner_hip, "Fused" + mode)
+    # equal minibatches only (static buffers of the graph-replayed update): the largest size <= --minibatch that divides the
+    # segment, e.g. --num-robot 1000 x horizon 32 = 32000 samples run as 2 x 16000 instead of failing on 16384
+    mb = cls.fit_minibatch(num_samples, args.minibatch)
+    if not is_ppo:
+        return cls(model, lr=args.lr, minibatch=mb, **kw)
+    if mode == "PPO" and mb != min(args.minibatch, num_samples) and rank == 0:
+        print("train.py: minibatch %d -> %d (must divide the %d samples of a segment)" % (args.minibatch, mb, num_samples), file=sys.stderr)
+    if mb < 256 and num_samples >= 4096:
+        raise SystemExit("train.py: %d samples per segment have no divisor between 256 and %d; pick another --num-robot / --horizon "
+                         "or use --torch-learner (handles a short last minibatch)" % (num_samples, args.minibatch))
+    learner = cls(model, lr=args.lr, minibatch=mb, mpi_adam_epsilon=args.mpi_adam, **kw)
+    learner.sync()                                        # MpiAdam.sync before training (ppo_imitation.py:274)
+    return learner
+
+
+class Mode(object):
+    """What a training mode adds to train(): `learner`, make_learner's name of its learner; `gae`, whether it is PPO (advantages, returns
+    and the old log-probabilities join update_args'); `collector_kw`, what its collectors are built with; `full_record`, whether the log
+    line carries the per-clip, per-term and per-leg fields (PPOMode alone, so far); and three methods: before_collect(it, collector),
+    update_args(buf, flat) -> the learner's tensors and keywords, record(env, stats, learner, out) -> its own keys of the log line."""
+    gae, full_record, collector_kw = True, False, {}
+
+    def __init__(self, args, model, dev):
+        self.args, self.model = args, model
+
+    def before_collect(self, it, collector):
+        pass
+
+    def ppo_record(self, losses, **more):
+        """surr, vf and `more`; --learn-std: ppo.STAT_NAMES' other three and the range of the twelve stds (one device read per logged record)"""
+        from openroborl_amd import ppo
+        rec = dict({"surr": round(float(losses[0]), 4), "vf": round(float(losses[1]), 4)}, **more)
+        if self.args.learn_std:
+            std = self.model.std
+            rec.update({k: round(float(v), 6) for k, v in zip(ppo.STAT_NAMES[2:], losses[2:])})
+            rec.update({"std_min": round(float(std.min()), 5), "std_max": round(float(std.max()), 5)})
+        return rec
+
+
+class PPOMode(Mode):
+    """PPO on a plain, privileged-critic or privileged-actor policy."""
+    learner, full_record = "PPO", True
+
+    def update_args(self, buf, flat):
+        return [flat(buf["obs"]), flat(buf["actions"])], {"priv": flat(buf["priv"]) if self.model.priv_dim else None}
+
+    def record(self, env, stats, learner, losses):
+        return dict({"episodes_unlogged": stats[3] - max(stats.sums[0] - int(stats[0].numel()), 0),
+                     "max_ep_steps": int(env.field_int("MAX_EP_STEPS").max())}, **self.ppo_record(losses))
+
+
+class HistoryPPOMode(Mode):
+    """--history-ppo: PPO on a history policy.  The collector hands hist[k] to the actor and priv[k], the true row, to the critic
+    (critic_priv=True), the bootstrap is the critic on the last true row, and the learner trains actor, critic and encoder."""
+    learner, collector_kw = "PPOHistory", {"critic_priv": True}
+
+    def update_args(self, buf, flat):
+        return [flat(buf[k]) for k in ("obs", "hist", "priv", "actions")], {}
+
+    def record(self, env, stats, learner, losses):
+        return self.ppo_record(losses, latent_loss=round(float(losses[-1]), 6))
+
+
+class DistillMode(Mode):
+    """--distill TEACHER.zip: DAgger on the device.  Each iteration collects a segment in which the student drives (all robots but the
+    share --distill-beta, which the teacher drives) and the teacher labels every visited state, then regresses the student's mean on the labels.
+    --history: the student reads its sensor history, and its encoder's output is regressed on the segment's privileged observations instead."""
+    gae = False
+
+    def __init__(self, args, model, dev):
+        from openroborl_amd import policy as pol, ppo
+        self.args, self.learner = args, "DistillHistory" if args.history else "Distill"
+        teacher_params = {k: v for k, v in pol.load_parameters(args.distill).items() if not k.startswith("model/enc_")}
+        self.collector_kw = {"teacher": ppo.ActorCritic(dev, params=teacher_params).enable_fused()}
+
+    def before_collect(self, it, collector):
+        args = self.args
+        beta = args.distill_beta * (max(0.0, 1.0 - it / float(args.distill_beta_iters)) if args.distill_beta_iters > 0 else 1.0)
+        self.driven = int(round(beta * args.num_robot))
+        collector.teacher_mask.zero_()
+        collector.teacher_mask[:self.driven] = 1
+
+    def update_args(self, buf, flat):
+        if not self.args.history:
+            return [flat(buf["obs"]), flat(buf["teacher_mean"])], {}
+        action = dict(obs=flat(buf["obs"]), target_mean=flat(buf["teacher_mean"])) if self.args.distill_action_coef > 0.0 else {}
+        return [flat(buf["hist"]), flat(buf["priv"])], action
+
+    def record(self, env, stats, learner, loss):
+        args = self.args
+        rec = {"latent_loss" if args.history else "distill_loss": round(float(loss), 6), "teacher_driven": self.driven}
+        if args.history and (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0):
+            # the log carries both losses: latent_loss then holds the latent regression's own loss, as it does without the action loss
+            rec.update({"latent_loss": round(learner.last_latent_loss, 6), "action_loss": round(learner.last_action_loss, 6),
+                        "total_loss": round(float(loss), 6)})
+        return rec
+
+
+def merge_segment(model, buf):
+    """--obs-norm: the segment into the statistics, and the fold into the fused layer 0 at the next refresh; after the update, never before"""
+    T, n = buf["rewards"].shape
+    model.update_obs_norm(buf["obs"].reshape(T * n, -1), *((buf["priv"].reshape(T * n, -1),) if model.priv_norm is not None else ()))
+    model.mark_updated()
+
+
+def train(args, env, model, mode, dev, rank, world):
+    """--iters iterations of `mode` (PPOMode, HistoryPPOMode, DistillMode): every step all modes share is written here, once.  The order of
+    the steps after the update matters: the gather clears the episode log that the reads, the curriculum and the shaping record go by.
+    -> the logged records (rank 0; [] elsewhere)."""
+    import torch
+    from openroborl_amd import dist as odist, rollout
+    B = args.num_robot * args.horizon
+    flat = lambda x: x.reshape(B, -1)   # noqa: E731
+    learner = make_learner(args, model, mode.learner, B, rank)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(args.seed * 1000 + rank)
+    # what belongs to `obs`: the privileged observation and the sensor history of the policies that read them (None: right after the reset),
+    # and episode_starts of a segment's first step = the last step's done flags of the previous segment
+    obs, priv, hist, first_starts = env.reset(), None, None, None
+    t0, samples, log = time.time(), 0, []
+    # static rollout buffers + the segment replayed as one hipGraph (fused policy only); --torch-policy keeps the eager collector
+    collector = None if args.torch_policy else rollout.GraphRollout(env, model, args.horizon, **mode.collector_kw)
+
+    def collect():
+        nonlocal obs, priv, hist
+        buf = (collector.collect(obs, generator=gen, priv=priv, hist=hist) if collector
+               else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv, hist=hist, **mode.collector_kw))
+        obs, priv, hist = buf["last_obs"], buf.get("last_priv"), buf.get("last_hist")
+        return buf
+    # (--obs-norm, here and after the update, is plain PPO's alone: obs_norm_check refuses it to the other modes)
+    if args.obs_norm and model.obs_norm.count == 0:
+        # one segment whose only use is to seed the statistics: the policy never acts, and the learner never learns, on the identity
+        buf = collect()
+        first_starts = buf["dones"][-1].clone()
+        merge_segment(model, buf)
+        odist.gather_env_episodes(env, args.horizon)       # its episodes are not the first iteration's
+    for it in range(args.iters):
+        shaping_ramp(args, env, it)
+        mode.before_collect(it, collector)
+        buf = collect()
+        tensors, kw = mode.update_args(buf, flat)
+        if mode.gae:
+            with torch.no_grad():
+                boot = model.value(obs, priv)
+            # bootstrap with the critic at the segment end (the reference uses 0 there, imitation_runners.py:98-100;
+            # with 32-step segments that bias would dominate)
+            adv, ret = rollout.gae_fused(buf["rewards"], buf["vpred"], buf["dones"], 0.95, 0.95, bootstrap=boot, normalize=True, eps=1e-8,
+                                         legacy_gae_index=args.legacy_gae_index, first_starts=first_starts)
+            first_starts = buf["dones"][-1].clone()               # the collector's buffers are overwritten by the next segment
+            tensors += [adv.reshape(-1), ret.reshape(-1)]
+            kw["old_logp"] = buf["logp"].reshape(-1) if "logp" in buf else None
+        if args.lr_schedule != "constant":
+            learner.set_lr_mult(lr_mult(args, it))
+        out = learner.update(*tensors, epochs=args.epochs, generator=gen, **kw)
+        if args.obs_norm and (args.obs_norm_freeze_after is None or it < args.obs_norm_freeze_after):
+            merge_segment(model, buf)
+        samples += B * world
+        # (> 1 rank, or ORR_FORCE_DIST=1: the one-rank rehearsal of the several-ranks path on RCCL runs the check too)
+        if (world > 1 or os.environ.get("ORR_FORCE_DIST", "0") == "1") and args.sync_check_every > 0 and it % args.sync_check_every == args.sync_check_every - 1 and hasattr(learner, "check_synced"):
+            learner.check_synced()                            # like MpiAdam every 100 updates (mpi_adam.py:47-48)
+        log_it = rank == 0 and (it % 10 == 0 or it == args.iters - 1)
+        # this rank's episodes of the segment by clip, term and leg (read before the gather below clears the log; rank-local).  Only
+        # PPOMode logs them, with clip_prob, so far
+        detail = log_it and mode.full_record
+        by_clip = env.episode_returns_by_clip() if detail and env.multi_clip else None
+        by_term = env.episode_reward_terms() if detail and args.reward_terms else None
+        gait = env.episode_gait() if detail and args.contact_outputs else None
+        if args.clip_curriculum is not None:
+            env.clip_curriculum_update()                       # one launch on the log as it stands, before the gather clears it; no sync
+        shaping = shaping_record(args, env, log_it)            # its totals are cleared where the log is
+        stats = odist.gather_env_episodes(env, args.horizon)   # means come from the exact per-rank sums, not the truncated list
+        if not log_it:
+            continue
+        rec = {"iter": it, "samples": samples, "sec": round(time.time() - t0, 2), "mean_step_reward": round(float(buf["rewards"].mean()), 4),
+               "ep_len_mean": round(stats.mean_length, 1), "ep_ret_mean": round(stats.mean_return, 2), "episodes": stats.sums[0]}
+        rec.update(mode.record(env, stats, learner, out))
+        if control_on(args):
+            rec.update(control_record(learner))
+        if args.obs_norm:
+            rec.update(obs_norm_record(model))
+        if by_clip is not None:
+            rec["ep_ret_mean_by_clip"] = {clip_name(env, c): round(r, 2) for c, (r, _) in sorted(by_clip.items())}
+        if mode.full_record and (args.clip_curriculum is not None or args.clip_weights is not None):
+            rec["clip_prob"] = clip_prob_record(env)
+        if by_term is not None:
+            rec["reward_terms"] = {k: round(v, 4) for k, v in by_term.items()}
+        if gait is not None:
+            rec["gait"] = {k: [round(x, 3) for x in v] for k, v in gait.items()}
+        if shaping is not None:
+            rec["shaping"] = shaping
+        log.append(rec)
+        print(json.dumps(rec), flush=True)
+    return log
+
+
+def finish(args, env, model, log, rank):
+    """What every mode ends with: rank 0 writes --save, --save-folded and --log; every rank closes its env and leaves the process group."""
+    import torch
+    from openroborl_amd import policy as pol
+    if rank == 0 and args.save:
+        pol.save_parameters_zip(args.save, model.state_dict())
+    if rank == 0 and args.save_folded:
+        pol.save_folded(args.save_folded, model.state_dict())
+    if rank == 0 and args.log:
+        with open(args.log, "w") as f:
+            json.dump(log, f, indent=1)
+    env.close()
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+
+
+def main():
+    args = arg_parser().parse_args()
+    import torch
+    from openroborl_amd import dist as odist, policy as pol, ppo
+    from openroborl_amd.env import VecQuadrupedEnv
+    if args.tune_gemms:
+        torch.cuda.tunable.enable(True)
+    if args.eval:
+        return evaluate(args, torch, pol, ppo, VecQuadrupedEnv)
+    args.privileged_critic = args.privileged_critic or args.privileged_actor
+    rank, world, local = odist.init_from_env()
+    check_args(args, world)
+    privileged = args.privileged_critic or bool(args.distill) or args.history_ppo       # somebody reads env.privileged_obs
+    # ORR_BENCH_SINGLE_DEVICE=1 (+ ORR_DIST_BACKEND=gloo): several ranks rehearsed on a one-GPU box (tests), never a measurement
+    dev = torch.device("cuda", 0 if os.environ.get("ORR_BENCH_SINGLE_DEVICE") else local)
+    torch.cuda.set_device(dev)
+    env = VecQuadrupedEnv(task_name=args.task, num_robot=args.num_robot, mode="train", auto_reset=True, seed=args.seed,
+                          device=dev, num_procs=world, robot_index_offset=rank * args.num_robot, motion_file=args.motion_file,
+                          perturb_init_state_prob=args.perturb_init_state_prob, tar_obs_noise=args.tar_obs_noise,
+                          reward_terms=args.reward_terms, contact_outputs=args.contact_outputs or privileged,
+                          observation_noise_stdev=args.sensor_noise, push=args.push,
+                          push_outputs=privileged and args.push is not None, reward_shaping=args.reward_shaping,
+                          **clip_time_kwargs(args), **clip_draw_kwargs(args))     # (bound here, before the rollout graph is captured)
+    if args.clip_curriculum is not None and not env.multi_clip:
+        raise SystemExit("train.py: --clip-curriculum needs several --motion-file")
+    model = make_model(args, dev)
+    mode = (DistillMode if args.distill else HistoryPPOMode if args.history_ppo else PPOMode)(args, model, dev)
+    finish(args, env, model, train(args, env, model, mode, dev, rank, world), rank)
+
+
 
 
 def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
