@@ -3,9 +3,10 @@
  *
  * The reference builds the update as a TF1 graph (agents/ppo_imitation.py:156-258: clipped surrogate + value loss on the two
  * 160 -> 512 -> 256 -> {12, 1} ReLU networks of agents/imitation_policies.py:44-51) and applies it with MpiAdam
- * (stable_baselines/common/mpi_adam.py:40-62).  Here the dense contractions stay library GEMMs (hipBLASLt through torch); what the
- * autograd graph spends around them - ~70 elementwise / reduction launches per minibatch, more time than the GEMMs themselves - is
- * these launches:
+ * (stable_baselines/common/mpi_adam.py:40-62).  Here the forward contractions are library GEMMs (hipBLASLt through torch) and so, by
+ * default, are the backward ones; orr_wgrad and orr_dgrad_relu (csrc/orr_learner_gemm.hip) are the backward contractions of the hidden
+ * layers on the f32 matrix cores, opt-in (learner_hip: hip_backward=True).  What the autograd graph spends around the GEMMs - ~70
+ * elementwise / reduction launches per minibatch, more time than the GEMMs themselves - is these launches:
  *   orr_ppo_head       loss terms, d loss / d mean, d loss / d value, bias gradients of the two output layers
  *   orr_ppo_head_logstd  that head for a learned per-dimension log-std read from the device: + its gradient, the entropy bonus, approx-KL, clip fraction
  *   orr_gauss_prepare  the sampler's half of a learned std: noise scaled by exp(log_std) and its log-probability, a whole rollout segment per launch
@@ -17,6 +18,8 @@
  *                      output layer's weight gradient
  *   orr_colsum_finish  the column sums behind all bias gradients of a minibatch in one launch
  *   orr_relu_backward  ReLU mask in place + bias gradient
+ *   orr_wgrad          a hidden layer's weight gradient x^T g as batch-slice partial products, for orr_colsum_finish
+ *   orr_dgrad_relu     a hidden layer's input gradient (gz . W^T) with the ReLU mask and the bias partials in its epilogue
  *   orr_adam_step      Adam on the flat parameter vector, step counter on the device (the whole update replays as one hipGraph)
  *   orr_update_control the controls of a step from the flat gradient, on the device: clip coefficient of its norm, non-finite guard, KL gate
  *   orr_adam_step_ctl  orr_adam_step reading those controls and a learning-rate multiplier from device memory (no capture when they change)
@@ -172,6 +175,26 @@ typedef struct orr_colsum_job {
   int32_t cols;
 } orr_colsum_job;
 int32_t orr_colsum_finish(const orr_colsum_job* jobs, int32_t n_jobs, void* stream);
+
+/* ---- the backward GEMMs of the hidden layers on the f32 matrix cores (csrc/orr_learner_gemm.hip) -----------------------------------------
+ * The weight gradient gw [k][n] = x^T g of a layer with input x [m][k] and pre-activation gradient g [m][n], split over the batch:
+ *   partials [S][k][n]   slice s holds the product over its own contiguous range of batch rows, S = orr_wgrad_slices(m, k, n) >= 1, a pure
+ *                        function of the shape (-1 for a shape orr_wgrad refuses).  Their sum is one job {partials, gw, S, k * n} of
+ *                        orr_colsum_finish.  A last slice may be short or empty; an empty slice holds zeros
+ * k and n: multiples of 16; m >= 1; rows beyond m are not read.  x, g and partials 16-byte aligned.  Nothing outside partials' S k n floats
+ * is written.  No float atomics, an order fixed by (m, k, n): the same inputs give the same bits.  A refused call launches and writes nothing. */
+int32_t orr_wgrad_slices(int32_t m, int32_t k, int32_t n);
+int32_t orr_wgrad(const float* x, int32_t k, const float* g, int32_t n, int32_t m, float* partials, void* stream);
+
+/* The input gradient of a layer w [k][n] (as stored: k inputs, n outputs) behind a ReLU layer h [m][k], from gz [m][n], the gradient at
+ * the layer's pre-activation: what mm(gz, w^T) followed by orr_relu_backward(gh, h) leave, in one launch.
+ *   gh [m][k] = (gz . w^T) where h > 0, +0 elsewhere (orr_relu_backward's mask)
+ *   ws        [orr_dgrad_partial_rows(m)][k] column sums of gh over a workgroup's batch rows (one row per 64): the bias gradient of the layer
+ *             that produced h is the job {ws, gb, rows, k} of orr_colsum_finish
+ * n and k: multiples of 16; m >= 1; rows beyond m are neither read nor written.  Every buffer 16-byte aligned.  No float atomics, a fixed
+ * order.  A refused call launches and writes nothing.  orr_dgrad_partial_rows(m): -1 for m < 1. */
+int32_t orr_dgrad_partial_rows(int32_t m);
+int32_t orr_dgrad_relu(const float* gz, const float* w, const float* h, int32_t m, int32_t n, int32_t k, float* gh, float* ws, void* stream);
 
 /* One Adam step on n parameters; t = state[0] + 1, the gradient is multiplied by grad_scale first (1 / world size after an
  * all-reduce sum: mpi_adam.py:51-53).

@@ -280,6 +280,12 @@ POLICY_FORWARD_HISTORY_PRIV_ARGS = [C.POINTER(OrrPolicyNet), C.POINTER(OrrHistor
 #   const float* target_priv [m][48] | NULL (both NULL with latent_coef 0 only), int32_t m, float latent_coef, float* g_z [m][48],
 #   float* partials [latent_backward_rows(m)][48] + [rows][1], void* stream)
 LATENT_BACKWARD_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_wgrad(const float* x [m][k], int32_t k, const float* g [m][n], int32_t n, int32_t m,
+#   float* partials [orr_wgrad_slices(m, k, n)][k][n], void* stream)
+WGRAD_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_dgrad_relu(const float* gz [m][n], const float* w [k][n], const float* h [m][k], int32_t m, int32_t n,
+#   int32_t k, float* gh [m][k], float* ws [orr_dgrad_partial_rows(m)][k], void* stream)
+DGRAD_RELU_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 # include/openroborl_learner.h: the statistics record of running observation normalisation, ORR_RUNNING_STATS_* (32-bit words of a record of

@@ -29,6 +29,10 @@ agents/ppo_imitation.py:296-299): none of them captures again and none costs a h
 Without those arguments a learner launches what it always did (orr_adam_step, self.ctl is None).
 A model with an observation normaliser (ppo.ActorCritic(obs_norm=True)) is FusedPPO's alone: its update() fills the plan's static obs /
 priv inputs through orr_normalize_rows instead of a copy, so the captured epoch is the one it would be without; the other three refuse it.
+hip_backward=True (all four): the hidden layers' weight gradients and input gradients leave the library for csrc/orr_learner_gemm.hip -
+orr_wgrad (x^T g as batch-slice partial products, for every minibatch size; their sum is a job of the minibatch's orr_colsum_finish) and
+orr_dgrad_relu (gz W^T, the ReLU mask and the bias partials in one launch, in place of mm + orr_relu_backward).  Everything else, and every
+learner without the flag, is what it was, bit for bit.
 There is no fallback: without a GPU and the HIP library the constructors raise.
 """
 import ctypes as C
@@ -52,9 +56,10 @@ class _FusedLearner(object):
     net and of the history encoder and the update driver.  A learner adds its plan's buffers (_buffers), its _minibatch and its update."""
 
     def __init__(self, model, names, stats, lr, adam_eps, minibatch, betas, use_graph, mpi_adam_epsilon=False, max_grad_norm=None, device_lr=False,
-                 kl_stop=None, kl_target=None, kl_lr_bounds=None):
+                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False):
         import torch
         self.torch = torch
+        self.hip_backward = bool(hip_backward)                  # the hidden layers' backward GEMMs: orr_wgrad + orr_dgrad_relu (see _wgrad_hip)
         self.max_grad_norm, self.kl_stop, self.kl_target, self.kl_lr_bounds = _control_args(type(self).__name__, max_grad_norm, kl_stop, kl_target,
                                                                                             kl_lr_bounds or KL_LR_BOUNDS)
         self.kl_on = self.kl_stop is not None or self.kl_target is not None
@@ -175,6 +180,20 @@ class _FusedLearner(object):
         else:
             t.mm(x.t(), g, out=out)
 
+    # ---- hip_backward: the hidden layers' backward GEMMs on the matrix cores (csrc/orr_learner_gemm.hip) ---------------------------------
+    def _slices(self, M, k, n):
+        """Partial products a weight gradient [k][n] of M rows is finished from: 16 bmm products, or orr_wgrad's slices."""
+        return int(self.L.orr_wgrad_slices(M, k, n)) if self.hip_backward else 16
+
+    def _wgrad_hip(self, x, g, part, st):
+        """part [S][k][n] = the batch slices' shares of x^T g (orr_wgrad); their sum is a job of the minibatch's orr_colsum_finish."""
+        _lib.check(self.L.orr_wgrad(x.data_ptr(), x.shape[1], g.data_ptr(), g.shape[1], x.shape[0], part.data_ptr(), st), self.L)
+
+    def _dgrad_hip(self, gz, w, h, gh, ws, st):
+        """gh = (gz w^T) * (h > 0) and the partial sums of its columns in ws (orr_dgrad_relu): mm + orr_relu_backward in one launch."""
+        _lib.check(self.L.orr_dgrad_relu(gz.data_ptr(), w.data_ptr(), h.data_ptr(), gz.shape[0], gz.shape[1], h.shape[1], gh.data_ptr(),
+                                         ws.data_ptr(), st), self.L)
+
     def _plan(self, B, M):
         """Static buffers for B samples per update in minibatches of M."""
         key = (B, M)
@@ -184,7 +203,9 @@ class _FusedLearner(object):
             P = {"B": B, "M": M, "nmb": B // M, "perm": t.empty(B, dtype=t.int64, device=self.dev),
                  "stats": t.zeros(B // M, self.n_stats, dtype=t.float32, device=self.dev), "graphs": None}
             # split: the weight gradients of a tall minibatch are 16 partial products (_wgrad); rows: of partial sums a kernel leaves per column
-            self._buffers(P, f, M >= 4096 and M % 16 == 0, int(self.L.orr_learner_partial_rows(M)))
+            # hip_backward: every minibatch size is split (orr_wgrad's slices); P["drows"]: the rows orr_dgrad_relu leaves instead of `rows`
+            P["drows"] = int(self.L.orr_dgrad_partial_rows(M)) if self.hip_backward else int(self.L.orr_learner_partial_rows(M))
+            self._buffers(P, f, self.hip_backward or (M >= 4096 and M % 16 == 0), int(self.L.orr_learner_partial_rows(M)))
             self._plans[key] = P
         return self._plans[key]
 
@@ -195,14 +216,15 @@ class _FusedLearner(object):
         deferred: each producer leaves its per-workgroup partial sums in its own buffer and ONE launch adds them all up (orr_colsum_finish)."""
         M, g = P["M"], self.g
         P["h1" + sfx], P["h2" + sfx], P["y" + sfx] = f(M, 512), f(M, 256), f(M, k)
-        P["part1" + sfx], P["part0" + sfx] = (f(16, 512, 256), f(16, k0, 512)) if split else (None, None)
+        s1, s0, drows = self._slices(M, 512, 256), self._slices(M, k0, 512), P["drows"]
+        P["part1" + sfx], P["part0" + sfx] = (f(s1, 512, 256), f(s0, k0, 512)) if split else (None, None)
         ws2 = P["ws2" + sfx] = f(int(self.L.orr_learner_workspace_floats(M, 256)))      # [rows][256] | [rows][256 * 12]
-        ws1 = P["ws1" + sfx] = f(rows * 512)
+        ws1 = P["ws1" + sfx] = f(drows * 512)
         sums = [(ws2, g["model/%s_fc1/b:0" % net], rows, 256), (ws2[rows * 256:], g["model/%s/w:0" % net], rows, 256 * k),
-                (ws1, g["model/%s_fc0/b:0" % net], rows, 512)]
+                (ws1, g["model/%s_fc0/b:0" % net], drows, 512)]
         if not split:
             return sums, []
-        return sums, [(P["part1" + sfx], g["model/%s_fc1/w:0" % net], 16, 512 * 256), (P["part0" + sfx], g["model/%s_fc0/w:0" % net], 16, k0 * 512)]
+        return sums, [(P["part1" + sfx], g["model/%s_fc1/w:0" % net], s1, 512 * 256), (P["part0" + sfx], g["model/%s_fc0/w:0" % net], s0, k0 * 512)]
 
     def _mlp_forward(self, P, net, sfx, x):
         t, w = self.torch, self.w
@@ -216,6 +238,11 @@ class _FusedLearner(object):
         h1 = P["h1" + sfx]
         _lib.check(L.orr_head_backward(gy.data_ptr(), k, w["model/%s/w:0" % net].data_ptr(), P["h2" + sfx].data_ptr(), M, 256, P["gz2"].data_ptr(),
                                        None, None, P["ws2" + sfx].data_ptr(), st), L)
+        if self.hip_backward:
+            self._wgrad_hip(h1, P["gz2"], P["part1" + sfx], st)
+            self._dgrad_hip(P["gz2"], w["model/%s_fc1/w:0" % net], h1, P["gh1"], P["ws1" + sfx], st)
+            self._wgrad_hip(x, P["gh1"], P["part0" + sfx], st)
+            return
         self._wgrad(h1, P["gz2"], P["part1" + sfx], g["model/%s_fc1/w:0" % net])
         t.mm(P["gz2"], w["model/%s_fc1/w:0" % net].t(), out=P["gh1"])
         _lib.check(L.orr_relu_backward(P["gh1"].data_ptr(), h1.data_ptr(), M, 512, None, P["ws1" + sfx].data_ptr(), st), L)
@@ -224,11 +251,18 @@ class _FusedLearner(object):
     # ---- the history encoder model/enc_*: 512 -> 256 -> 48, its buffers under the plan keys xh, he, z, g_z, g_he, ws1e, part0 ---------------
     def _enc_buffers(self, P, f, split, rows):
         """The encoder's activations and the partial sums of its backward pass; returns the jobs that finish enc_fc0's bias gradient and, when
-        split, its weight gradient.  enc_fc1's bias gradient is left by whoever produces g_z, the learner's loss head: a job of its own."""
-        M, g = P["M"], self.g
+        split, its weight gradient (hip_backward: enc_fc1's weight gradient as well, orr_wgrad's slices like the other).  enc_fc1's bias
+        gradient is left by whoever produces g_z, the learner's loss head: a job of its own."""
+        M, g, drows = P["M"], self.g, P["drows"]
         D, H, Z = _abi.HISTORY_DIM, 256, _abi.POLICY_PRIV_DIM
-        P.update({"xh": f(M, D), "he": f(M, H), "z": f(M, Z), "g_z": f(M, Z), "g_he": f(M, H), "ws1e": f(rows * H), "part0": f(16, D, H) if split else None})
-        return [(P["ws1e"], g["model/enc_fc0/b:0"], rows, H)] + ([(P["part0"], g["model/enc_fc0/w:0"], 16, D * H)] if split else [])
+        s0 = self._slices(M, D, H)
+        P.update({"xh": f(M, D), "he": f(M, H), "z": f(M, Z), "g_z": f(M, Z), "g_he": f(M, H), "ws1e": f(drows * H), "part0": f(s0, D, H) if split else None})
+        jobs = [(P["ws1e"], g["model/enc_fc0/b:0"], drows, H)] + ([(P["part0"], g["model/enc_fc0/w:0"], s0, D * H)] if split else [])
+        if self.hip_backward:
+            s1 = self._slices(M, H, Z)
+            P["part1e"] = f(s1, H, Z)
+            jobs.append((P["part1e"], g["model/enc_fc1/w:0"], s1, H * Z))
+        return jobs
 
     def _enc_forward(self, P):
         t, w = self.torch, self.w
@@ -238,6 +272,11 @@ class _FusedLearner(object):
     def _enc_backward(self, P, st):
         """From P["g_z"] = d loss / d z [M, 48] to the encoder's weight gradients and the partial sums of enc_fc0's bias gradient."""
         t, L, w, g = self.torch, self.L, self.w, self.g
+        if self.hip_backward:
+            self._wgrad_hip(P["he"], P["g_z"], P["part1e"], st)
+            self._dgrad_hip(P["g_z"], w["model/enc_fc1/w:0"], P["he"], P["g_he"], P["ws1e"], st)
+            self._wgrad_hip(P["xh"], P["g_he"], P["part0"], st)
+            return
         t.mm(P["he"].t(), P["g_z"], out=g["model/enc_fc1/w:0"])
         t.mm(P["g_z"], w["model/enc_fc1/w:0"].t(), out=P["g_he"])
         _lib.check(L.orr_relu_backward(P["g_he"].data_ptr(), P["he"].data_ptr(), P["M"], 256, None, P["ws1e"].data_ptr(), st), L)
@@ -343,7 +382,7 @@ class FusedPPO(_FusedLearner):
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
                  mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, max_grad_norm=None, device_lr=False, kl_stop=None,
-                 kl_target=None, kl_lr_bounds=None):
+                 kl_target=None, kl_lr_bounds=None, hip_backward=False):
         self._need_gpu(model)
         if getattr(model, "history", 0) and not self._history:
             raise ValueError("FusedPPO: a history policy is trained by FusedPPOHistory (PPO with the critic on the true privileged row) or by "
@@ -361,7 +400,7 @@ class FusedPPO(_FusedLearner):
         self.logstd_head = self.learn_std or kl_stop is not None or kl_target is not None
         self.head_stats = 5 if self.logstd_head else 2        # what the loss head writes; FusedPPOHistory's latent loss follows them
         _FusedLearner.__init__(self, model, sorted(model.p), self.head_stats + (1 if self._history else 0), lr, adam_eps, minibatch, betas, use_graph,
-                               mpi_adam_epsilon, max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds)
+                               mpi_adam_epsilon, max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward)
         if self.logstd_head and not self.learn_std:
             self.fixed_logstd = self.torch.zeros(12, dtype=self.torch.float32, device=self.dev)
             self.g_fixed_logstd = self.torch.zeros(12, dtype=self.torch.float32, device=self.dev)
@@ -551,7 +590,7 @@ class FusedPPOHistory(FusedPPO):
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
                  mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, latent_coef=0.0, max_grad_norm=None, device_lr=False,
-                 kl_stop=None, kl_target=None, kl_lr_bounds=None):
+                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False):
         import math
         _no_obs_norm(model, "FusedPPOHistory")
         if not getattr(model, "history", 0):
@@ -560,7 +599,7 @@ class FusedPPOHistory(FusedPPO):
         if not (self.latent_coef >= 0.0 and math.isfinite(self.latent_coef)):
             raise ValueError("FusedPPOHistory: latent_coef must be finite and not negative")
         FusedPPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, betas, mpi_adam_epsilon, use_graph, ent_coef, log_std_bounds,
-                          max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds)
+                          max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward)
 
     def _graph_key(self):
         return FusedPPO._graph_key(self) + (self.latent_coef,)
@@ -635,7 +674,8 @@ class FusedDistill(_FusedLearner):
     orr_relu_backward and one orr_colsum_finish per minibatch, equal minibatches in static buffers, an epoch captured once and replayed as
     one hipGraph (a single chain on one stream).  One rank: there is no gradient all-reduce here."""
 
-    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, max_grad_norm=None, device_lr=False):
+    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, max_grad_norm=None, device_lr=False,
+                 hip_backward=False):
         _no_obs_norm(student, "FusedDistill")
         if getattr(student, "actor_priv_dim", 0):
             raise ValueError("FusedDistill: the student's actor must read the 160 observation words only")
@@ -643,7 +683,7 @@ class FusedDistill(_FusedLearner):
         if getattr(student, "history", 0):
             raise ValueError("FusedDistill: a history student is trained by FusedDistillHistory, or with PPO by FusedPPOHistory")
         _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/pi") and k != LOGSTD), 1, lr, adam_eps, minibatch, betas, use_graph,
-                               max_grad_norm=max_grad_norm, device_lr=device_lr)
+                               max_grad_norm=max_grad_norm, device_lr=device_lr, hip_backward=hip_backward)
 
     def _buffers(self, P, f, split, rows):
         B, M = P["B"], P["M"]
@@ -692,7 +732,7 @@ class FusedDistillHistory(_FusedLearner):
     model's mark_updated()) -, everything behind it is the same.  The defaults (0, 1) are the path above, launch for launch."""
 
     def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, action_coef=0.0, latent_coef=1.0,
-                 max_grad_norm=None, device_lr=False):
+                 max_grad_norm=None, device_lr=False, hip_backward=False):
         self.action_coef, self.latent_coef = float(action_coef), float(latent_coef)
         if self.action_coef < 0.0 or self.latent_coef < 0.0:
             raise ValueError("FusedDistillHistory: action_coef and latent_coef must not be negative")
@@ -704,7 +744,7 @@ class FusedDistillHistory(_FusedLearner):
         if not getattr(student, "history", 0):
             raise ValueError("FusedDistillHistory: the student needs a history encoder (ActorCritic(history=16))")
         _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/enc_")), 2 if self.head else 1, lr, adam_eps,
-                               minibatch, betas, use_graph, max_grad_norm=max_grad_norm, device_lr=device_lr)
+                               minibatch, betas, use_graph, max_grad_norm=max_grad_norm, device_lr=device_lr, hip_backward=hip_backward)
 
     def _graph_key(self):
         return _FusedLearner._graph_key(self) + (self.action_coef, self.latent_coef)

@@ -1,7 +1,8 @@
 """Where one train.py iteration spends its time (development aid, GPU box): rollout / GAE / PPO update by HIP events, and the pieces of
 one minibatch update (forward, backward, optimiser) timed separately.
 
-usage:  python tools/train_breakdown.py [robots=4096] [horizon=32] [minibatch=16384] [epochs=2] [torch-learner] [learn-std]
+usage:  python tools/train_breakdown.py [robots=4096] [horizon=32] [minibatch=16384] [epochs=2] [torch-learner] [learn-std] [hip-backward]
+        hip-backward: the fused learner with hip_backward=True (train.py --hip-backward)
         learn-std: a model with a learned log-std and ent_coef = 0.01 (train.py --learn-std --ent-coef 0.01)
         privileged-actor | history-ppo | history-ppo-latent: the update alone of a teacher (train.py --privileged-actor) or of a history policy
         (train.py --history-ppo, and with --latent-coef 0.5): FusedPPO / FusedPPOHistory, or their torch references with torch-learner
@@ -16,12 +17,13 @@ from openroborl_amd import learner_hip, ppo, rollout  # noqa: E402
 from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
 
 MODES = ("privileged-actor", "history-ppo", "history-ppo-latent")
-argv = [a for a in sys.argv[1:] if a not in ("update-only", "torch-learner", "learn-std") + MODES]
+argv = [a for a in sys.argv[1:] if a not in ("update-only", "torch-learner", "learn-std", "hip-backward") + MODES]
 mode = next((a for a in sys.argv[1:] if a in MODES), None)
 update_only = "update-only" in sys.argv
 torch_learner = "torch-learner" in sys.argv
 learn_std = "learn-std" in sys.argv
 entropy = dict(ent_coef=0.01) if learn_std else {}
+fused_kw = dict(entropy, hip_backward=True) if "hip-backward" in sys.argv else entropy        # the fused learners' keywords
 n = int(argv[0]) if len(argv) > 0 else 4096
 T = int(argv[1]) if len(argv) > 1 else 32
 mb = int(argv[2]) if len(argv) > 2 else 16384
@@ -47,7 +49,8 @@ B = T * n
 if mode:     # a wide model's update, and nothing else
     history = mode.startswith("history-ppo")
     model = ppo.ActorCritic(dev, seed=0, learn_std=learn_std, priv_dim=48, actor_priv_dim=48, history=16 if history else 0).enable_fused()
-    more = dict(entropy, latent_coef=0.5 if mode.endswith("latent") else 0.0) if history else entropy
+    more = entropy if torch_learner else fused_kw
+    more = dict(more, latent_coef=0.5 if mode.endswith("latent") else 0.0) if history else more
     cls = ((ppo.PPOHistory if history else ppo.PPO) if torch_learner else (learner_hip.FusedPPOHistory if history else learner_hip.FusedPPO))
     learner = cls(model, lr=1e-4, minibatch=mb, **more)
     obs, hist, priv, act = (torch.randn(B, c, device=dev) for c in (160, 512, 48, 12))
@@ -61,7 +64,7 @@ if mode:     # a wide model's update, and nothing else
           % (mode, cls.__name__, t_update, B, mb, epochs, epochs * (B // mb), t_update / (epochs * (B // mb))))
     sys.exit(0)
 model = ppo.ActorCritic(dev, seed=0, learn_std=learn_std).enable_fused()
-learner = ppo.PPO(model, lr=1e-4, minibatch=mb, **entropy) if torch_learner else learner_hip.FusedPPO(model, lr=1e-4, minibatch=mb, **entropy)
+learner = ppo.PPO(model, lr=1e-4, minibatch=mb, **entropy) if torch_learner else learner_hip.FusedPPO(model, lr=1e-4, minibatch=mb, **fused_kw)
 obs = torch.randn(B, 160, device=dev)
 act = torch.randn(B, 12, device=dev) * 0.2
 adv = torch.randn(B, device=dev)

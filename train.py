@@ -224,6 +224,9 @@ def arg_parser():
     ap.add_argument("--torch-learner", action="store_true",
                     help="PPO update through autograd + torch.optim.Adam (ppo.PPO, the fp32 reference) instead of the hand-written backward "
                          "replayed as a hipGraph (learner_hip.FusedPPO)")
+    ap.add_argument("--hip-backward", action="store_true",
+                    help="the fused learners' backward GEMMs of the hidden layers on hand-written matrix-core kernels (orr_wgrad, orr_dgrad_relu: "
+                         "learner_hip's hip_backward=True) instead of library GEMMs + orr_relu_backward; every mode; not with --torch-learner")
     ap.add_argument("--eval", default="", help="evaluate a policy zip instead of training: deterministic actions, test mode "
                                                  "(no randomiser, full-length episodes), like `run.py --mode test`")
     ap.add_argument("--legacy-gae-index", action="store_true",
@@ -444,7 +447,11 @@ def make_learner(args, model, mode, num_samples, rank):
     if mode == "DistillHistory":
         kw.update(action_coef=args.distill_action_coef, latent_coef=args.distill_latent_coef)
     if args.torch_learner:
+        if args.hip_backward:
+            raise SystemExit("train.py: --hip-backward is the fused learners'; drop --torch-learner")
         return getattr(ppo, mode)(model, lr=args.lr, minibatch=args.minibatch, **kw)
+    if args.hip_backward:                # no keyword without the flag: the learners' default
+        kw["hip_backward"] = True
     from openroborl_amd import learner_hip
     cls = getattr(learner_hip, "Fused" + mode)
     # equal minibatches only (static buffers of the graph-replayed update): the largest size <= --minibatch that divides the
