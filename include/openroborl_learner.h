@@ -3,9 +3,12 @@
  *
  * The reference builds the update as a TF1 graph (agents/ppo_imitation.py:156-258: clipped surrogate + value loss on the two
  * 160 -> 512 -> 256 -> {12, 1} ReLU networks of agents/imitation_policies.py:44-51) and applies it with MpiAdam
- * (stable_baselines/common/mpi_adam.py:40-62).  Here the forward contractions are library GEMMs (hipBLASLt through torch) and so, by
- * default, are the backward ones; orr_wgrad and orr_dgrad_relu (csrc/orr_learner_gemm.hip) are the backward contractions of the hidden
- * layers on the f32 matrix cores, opt-in (learner_hip: hip_backward=True).  What the autograd graph spends around the GEMMs - ~70
+ * (stable_baselines/common/mpi_adam.py:40-62).  Here the contractions are by default library GEMMs (hipBLASLt through torch), forward and
+ * backward; orr_wgrad and orr_dgrad_relu (csrc/orr_learner_gemm.hip) are the backward contractions of the hidden layers on the f32 matrix
+ * cores, opt-in (learner_hip: hip_backward=True), and orr_dense_forward (csrc/orr_learner_forward.hip) is every forward layer there, in the
+ * rollout's arithmetic and with the minibatch's gathers in its loader, opt-in as well (hip_forward=True); with both a captured epoch holds
+ * no library GEMM.  Whether either wins is measured in profiles/hip_backward.txt and profiles/hip_forward.txt: the
+ * defaults stay off.  What the autograd graph spends around the GEMMs - ~70
  * elementwise / reduction launches per minibatch, more time than the GEMMs themselves - is these launches:
  *   orr_ppo_head       loss terms, d loss / d mean, d loss / d value, bias gradients of the two output layers
  *   orr_ppo_head_logstd  that head for a learned per-dimension log-std read from the device: + its gradient, the entropy bonus, approx-KL, clip fraction
@@ -20,6 +23,7 @@
  *   orr_relu_backward  ReLU mask in place + bias gradient
  *   orr_wgrad          a hidden layer's weight gradient x^T g as batch-slice partial products, for orr_colsum_finish
  *   orr_dgrad_relu     a hidden layer's input gradient (gz . W^T) with the ReLU mask and the bias partials in its epilogue
+ *   orr_dense_forward  a forward layer act(in . W + b) on gathered, concatenated input rows, bit for bit the rollout's layer
  *   orr_adam_step      Adam on the flat parameter vector, step counter on the device (the whole update replays as one hipGraph)
  *   orr_update_control the controls of a step from the flat gradient, on the device: clip coefficient of its norm, non-finite guard, KL gate
  *   orr_adam_step_ctl  orr_adam_step reading those controls and a learning-rate multiplier from device memory (no capture when they change)
@@ -195,6 +199,22 @@ int32_t orr_wgrad(const float* x, int32_t k, const float* g, int32_t n, int32_t 
  * order.  A refused call launches and writes nothing.  orr_dgrad_partial_rows(m): -1 for m < 1. */
 int32_t orr_dgrad_partial_rows(int32_t m);
 int32_t orr_dgrad_relu(const float* gz, const float* w, const float* h, int32_t m, int32_t n, int32_t k, float* gh, float* ws, void* stream);
+
+/* ---- the forward layers on the f32 matrix cores (csrc/orr_learner_forward.hip) ------------------------------------------------------------
+ * y[i][0..n) = act(in(i) . W + b),   in(i) = xa[ra(i)][0..ka) | xb[rb(i)][0..kb),   ra(i) = rows_a ? rows_a[i] : i, rb likewise
+ *   xa [.][ka], xb [.][kb] | NULL with kb = 0; rows_a, rows_b: int64 [m] | NULL (what torch.randperm hands index_select); m >= 1
+ *   w [ka + kb][n] as stored (fan_in x fan_out, row-major), b [n]; relu != 0: act = max(., +0)
+ *   y [m][n];  x_out [m][ka + kb] | NULL: receives in(i), bit for bit (the layer's input for its weight gradient)
+ * Arithmetic: one accumulator per output, k = 0 .. ka + kb - 1 ascending from +0 on the f32 matrix cores, then + b[j], then act:
+ *   the bits of orr_policy_forward*'s layers for the same inputs and weights (openroborl_policy.h), for the output layers as well.
+ * ka >= 16 and kb: multiples of 16; n: a multiple of 16, or at most 15 (an output layer: a second, small kernel).  xa, xb, w, y and x_out
+ * 16-byte aligned, b and the row tables aligned to their element size.  Rows at or beyond m are neither read nor written; nothing outside
+ * y's m n floats and x_out's m (ka + kb) floats is written.  No atomics: the same inputs give the same bits.  Refused, launching and
+ * writing nothing: a null required pointer, a bad shape, a misaligned buffer, xb without kb or kb without xb (or rows_b without xb), y or
+ * x_out overlapping an input or each other (of a source read through a row table the first m rows are checked: its height is the
+ * caller's).  Row indices are the caller's responsibility and are not checked. */
+int32_t orr_dense_forward(const float* xa, int32_t ka, const int64_t* rows_a, const float* xb, int32_t kb, const int64_t* rows_b, int32_t m,
+                          const float* w, const float* b, int32_t n, int32_t relu, float* y, float* x_out, void* stream);
 
 /* One Adam step on n parameters; t = state[0] + 1, the gradient is multiplied by grad_scale first (1 / world size after an
  * all-reduce sum: mpi_adam.py:51-53).

@@ -286,6 +286,11 @@ WGRAD_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_
 # include/openroborl_learner.h: int32_t orr_dgrad_relu(const float* gz [m][n], const float* w [k][n], const float* h [m][k], int32_t m, int32_t n,
 #   int32_t k, float* gh [m][k], float* ws [orr_dgrad_partial_rows(m)][k], void* stream)
 DGRAD_RELU_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+# include/openroborl_learner.h: int32_t orr_dense_forward(const float* xa [.][ka], int32_t ka, const int64_t* rows_a [m] | NULL, const float* xb [.][kb] | NULL,
+#   int32_t kb, const int64_t* rows_b [m] | NULL, int32_t m, const float* w [ka + kb][n], const float* b [n], int32_t n, int32_t relu, float* y [m][n],
+#   float* x_out [m][ka + kb] | NULL, void* stream)
+DENSE_FORWARD_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                      C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 # include/openroborl_learner.h: the statistics record of running observation normalisation, ORR_RUNNING_STATS_* (32-bit words of a record of

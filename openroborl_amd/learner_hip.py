@@ -33,6 +33,12 @@ hip_backward=True (all four): the hidden layers' weight gradients and input grad
 orr_wgrad (x^T g as batch-slice partial products, for every minibatch size; their sum is a job of the minibatch's orr_colsum_finish) and
 orr_dgrad_relu (gz W^T, the ReLU mask and the bias partials in one launch, in place of mm + orr_relu_backward).  Everything else, and every
 learner without the flag, is what it was, bit for bit.
+hip_forward=True (all four): every forward layer leaves the library for csrc/orr_learner_forward.hip - orr_dense_forward, the rollout's
+arithmetic (one accumulator per output over k ascending, then the bias, then ReLU: the learner differentiates the function the rollout ran,
+bit for bit) with the minibatch's gathers of obs, priv and hist and the obs | priv / obs | z concatenations in layer 0's loader, which also
+writes the gathered input once for the weight gradient.  The aux / target gathers stay index_selects, and so does FusedPPOHistory's of priv
+(its latent loss reads the rows on their own).  Without the flag every learner launches what it launched; with both flags a captured epoch
+holds no library GEMM.
 There is no fallback: without a GPU and the HIP library the constructors raise.
 """
 import ctypes as C
@@ -56,9 +62,10 @@ class _FusedLearner(object):
     net and of the history encoder and the update driver.  A learner adds its plan's buffers (_buffers), its _minibatch and its update."""
 
     def __init__(self, model, names, stats, lr, adam_eps, minibatch, betas, use_graph, mpi_adam_epsilon=False, max_grad_norm=None, device_lr=False,
-                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False):
+                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False, hip_forward=False):
         import torch
         self.torch = torch
+        self.hip_forward = bool(hip_forward)                    # every forward layer: orr_dense_forward, the gathers in its loader (see _dense)
         self.hip_backward = bool(hip_backward)                  # the hidden layers' backward GEMMs: orr_wgrad + orr_dgrad_relu (see _wgrad_hip)
         self.max_grad_norm, self.kl_stop, self.kl_target, self.kl_lr_bounds = _control_args(type(self).__name__, max_grad_norm, kl_stop, kl_target,
                                                                                             kl_lr_bounds or KL_LR_BOUNDS)
@@ -194,6 +201,15 @@ class _FusedLearner(object):
         _lib.check(self.L.orr_dgrad_relu(gz.data_ptr(), w.data_ptr(), h.data_ptr(), gz.shape[0], gz.shape[1], h.shape[1], gh.data_ptr(),
                                          ws.data_ptr(), st), self.L)
 
+    # ---- hip_forward: the forward layers on the matrix cores, in the rollout's arithmetic (csrc/orr_learner_forward.hip) --------------------
+    def _dense(self, src, w, b, y, relu, st):
+        """y = act(in . w + b) (orr_dense_forward).  src: a tensor [M][k], or (xa, rows_a | None, xb | None, rows_b | None, x_out | None) -
+        in(i) = xa[rows_a[i]] | xb[rows_b[i]], a missing table meaning row i, and x_out receives in."""
+        xa, ra, xb, rb, x_out = src if isinstance(src, tuple) else (src, None, None, None, None)
+        ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+        _lib.check(self.L.orr_dense_forward(xa.data_ptr(), xa.shape[1], ptr(ra), ptr(xb), 0 if xb is None else xb.shape[1], ptr(rb), y.shape[0],
+                                            w.data_ptr(), b.data_ptr(), w.shape[1], relu, y.data_ptr(), ptr(x_out), st), self.L)
+
     def _plan(self, B, M):
         """Static buffers for B samples per update in minibatches of M."""
         key = (B, M)
@@ -227,7 +243,14 @@ class _FusedLearner(object):
         return sums, [(P["part1" + sfx], g["model/%s_fc1/w:0" % net], s1, 512 * 256), (P["part0" + sfx], g["model/%s_fc0/w:0" % net], s0, k0 * 512)]
 
     def _mlp_forward(self, P, net, sfx, x):
+        """x: the layer-0 input [M][k0]; hip_forward: or the sources _dense gathers it from."""
         t, w = self.torch, self.w
+        if self.hip_forward:
+            st = self._stream()
+            self._dense(x, w["model/%s_fc0/w:0" % net], w["model/%s_fc0/b:0" % net], P["h1" + sfx], 1, st)
+            self._dense(P["h1" + sfx], w["model/%s_fc1/w:0" % net], w["model/%s_fc1/b:0" % net], P["h2" + sfx], 1, st)
+            self._dense(P["h2" + sfx], w["model/%s/w:0" % net], w["model/%s/b:0" % net], P["y" + sfx].view(P["M"], -1), 0, st)
+            return
         t._addmm_activation(w["model/%s_fc0/b:0" % net], x, w["model/%s_fc0/w:0" % net], out=P["h1" + sfx])
         t._addmm_activation(w["model/%s_fc1/b:0" % net], P["h1" + sfx], w["model/%s_fc1/w:0" % net], out=P["h2" + sfx])
         t.addmm(w["model/%s/b:0" % net], P["h2" + sfx], w["model/%s/w:0" % net], out=P["y" + sfx])
@@ -264,8 +287,14 @@ class _FusedLearner(object):
             jobs.append((P["part1e"], g["model/enc_fc1/w:0"], s1, H * Z))
         return jobs
 
-    def _enc_forward(self, P):
+    def _enc_forward(self, P, idx=None):
+        """P["xh"] -> he -> z; hip_forward: idx, the minibatch's rows of P["hist"], which layer 0 gathers and leaves in P["xh"]."""
         t, w = self.torch, self.w
+        if self.hip_forward:
+            st = self._stream()
+            self._dense((P["hist"], idx, None, None, P["xh"]), w["model/enc_fc0/w:0"], w["model/enc_fc0/b:0"], P["he"], 1, st)
+            self._dense(P["he"], w["model/enc_fc1/w:0"], w["model/enc_fc1/b:0"], P["z"], 0, st)
+            return
         t._addmm_activation(w["model/enc_fc0/b:0"], P["xh"], w["model/enc_fc0/w:0"], out=P["he"])
         t.addmm(w["model/enc_fc1/b:0"], P["he"], w["model/enc_fc1/w:0"], out=P["z"])
 
@@ -382,7 +411,7 @@ class FusedPPO(_FusedLearner):
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
                  mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, max_grad_norm=None, device_lr=False, kl_stop=None,
-                 kl_target=None, kl_lr_bounds=None, hip_backward=False):
+                 kl_target=None, kl_lr_bounds=None, hip_backward=False, hip_forward=False):
         self._need_gpu(model)
         if getattr(model, "history", 0) and not self._history:
             raise ValueError("FusedPPO: a history policy is trained by FusedPPOHistory (PPO with the critic on the true privileged row) or by "
@@ -400,7 +429,7 @@ class FusedPPO(_FusedLearner):
         self.logstd_head = self.learn_std or kl_stop is not None or kl_target is not None
         self.head_stats = 5 if self.logstd_head else 2        # what the loss head writes; FusedPPOHistory's latent loss follows them
         _FusedLearner.__init__(self, model, sorted(model.p), self.head_stats + (1 if self._history else 0), lr, adam_eps, minibatch, betas, use_graph,
-                               mpi_adam_epsilon, max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward)
+                               mpi_adam_epsilon, max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward, hip_forward)
         if self.logstd_head and not self.learn_std:
             self.fixed_logstd = self.torch.zeros(12, dtype=self.torch.float32, device=self.dev)
             self.g_fixed_logstd = self.torch.zeros(12, dtype=self.torch.float32, device=self.dev)
@@ -446,10 +475,22 @@ class FusedPPO(_FusedLearner):
         t, L, M = self.torch, self.L, P["M"]
         st = self._stream()
         idx = P["perm"][s * M:(s + 1) * M]
-        t.index_select(P["obs"], 0, idx, out=P["x"])
+        if not self.hip_forward:
+            t.index_select(P["obs"], 0, idx, out=P["x"])
         t.index_select(P["aux"], 0, idx, out=P["batch"])
         x = P["x"]
         xin = {"pi": x, "vf": x}                   # each net's layer-0 input
+        if self.hip_forward:                       # layer 0 gathers: the first reader of x / xv fills it, a second reads it there
+            fwd = {"pi": (P["obs"], idx, None, None, x), "vf": x}
+            if self.priv_dim:
+                xin["vf"] = P["xv"]
+                if self.actor_priv_dim:
+                    xin["pi"], fwd = P["xv"], {"pi": (P["obs"], idx, P["priv"], idx, P["xv"]), "vf": P["xv"]}
+                else:
+                    fwd["vf"] = (x, None, P["priv"], idx, P["xv"])
+            for net in NETS:
+                self._mlp_forward(P, net, "_" + net, fwd[net])
+            return self._minibatch_tail(P, s, xin, st)
         if self.priv_dim:
             t.index_select(P["priv"], 0, idx, out=P["xp"])
             t.cat((x, P["xp"]), dim=1, out=P["xv"])
@@ -458,6 +499,11 @@ class FusedPPO(_FusedLearner):
                 xin["pi"] = P["xv"]
         for net in NETS:
             self._mlp_forward(P, net, "_" + net, xin[net])
+        self._minibatch_tail(P, s, xin, st)
+
+    def _minibatch_tail(self, P, s, xin, st):
+        """Behind the two forward chains: the loss head, both backward passes on the layer-0 inputs xin, the column sums."""
+        L = self.L
         self._loss_head(P, s, st)
         for net, k, gy in (("pi", 12, P["g_pi"]), ("vf", 1, P["g_vf"])):
             self._mlp_backward(P, net, "_" + net, xin[net], gy, k, st)
@@ -590,7 +636,7 @@ class FusedPPOHistory(FusedPPO):
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
                  mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, latent_coef=0.0, max_grad_norm=None, device_lr=False,
-                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False):
+                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False, hip_forward=False):
         import math
         _no_obs_norm(model, "FusedPPOHistory")
         if not getattr(model, "history", 0):
@@ -599,7 +645,7 @@ class FusedPPOHistory(FusedPPO):
         if not (self.latent_coef >= 0.0 and math.isfinite(self.latent_coef)):
             raise ValueError("FusedPPOHistory: latent_coef must be finite and not negative")
         FusedPPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, betas, mpi_adam_epsilon, use_graph, ent_coef, log_std_bounds,
-                          max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward)
+                          max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward, hip_forward)
 
     def _graph_key(self):
         return FusedPPO._graph_key(self) + (self.latent_coef,)
@@ -623,14 +669,21 @@ class FusedPPOHistory(FusedPPO):
         st = self._stream()
         Z = _abi.POLICY_PRIV_DIM
         idx = P["perm"][s * M:(s + 1) * M]
-        for src, dst in (("obs", "x"), ("hist", "xh"), ("priv", "xp"), ("aux", "batch")):
-            t.index_select(P[src], 0, idx, out=P[dst])
-        self._enc_forward(P)
-        t.cat((P["x"], P["z"]), dim=1, out=P["xz"])
-        t.cat((P["x"], P["xp"]), dim=1, out=P["xv"])
         xin = {"pi": P["xz"], "vf": P["xv"]}
-        for net in NETS:
-            self._mlp_forward(P, net, "_" + net, xin[net])
+        if self.hip_forward:      # obs gathered, z and the gathered priv not: the two row tables; the layers leave xz and xv for the backward pass
+            for src, dst in (("priv", "xp"), ("aux", "batch")):
+                t.index_select(P[src], 0, idx, out=P[dst])
+            self._enc_forward(P, idx)
+            self._mlp_forward(P, "pi", "_pi", (P["obs"], idx, P["z"], None, P["xz"]))
+            self._mlp_forward(P, "vf", "_vf", (P["obs"], idx, P["xp"], None, P["xv"]))
+        else:
+            for src, dst in (("obs", "x"), ("hist", "xh"), ("priv", "xp"), ("aux", "batch")):
+                t.index_select(P[src], 0, idx, out=P[dst])
+            self._enc_forward(P)
+            t.cat((P["x"], P["z"]), dim=1, out=P["xz"])
+            t.cat((P["x"], P["xp"]), dim=1, out=P["xv"])
+            for net in NETS:
+                self._mlp_forward(P, net, "_" + net, xin[net])
         self._loss_head(P, s, st)
         # the critic first: the actor's pass then leaves ITS layer-0 gradient in the scratch the two share (gh1, masked by orr_relu_backward)
         for net, k, gy in (("vf", 1, P["g_vf"]), ("pi", 12, P["g_pi"])):
@@ -675,7 +728,7 @@ class FusedDistill(_FusedLearner):
     one hipGraph (a single chain on one stream).  One rank: there is no gradient all-reduce here."""
 
     def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, max_grad_norm=None, device_lr=False,
-                 hip_backward=False):
+                 hip_backward=False, hip_forward=False):
         _no_obs_norm(student, "FusedDistill")
         if getattr(student, "actor_priv_dim", 0):
             raise ValueError("FusedDistill: the student's actor must read the 160 observation words only")
@@ -683,7 +736,7 @@ class FusedDistill(_FusedLearner):
         if getattr(student, "history", 0):
             raise ValueError("FusedDistill: a history student is trained by FusedDistillHistory, or with PPO by FusedPPOHistory")
         _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/pi") and k != LOGSTD), 1, lr, adam_eps, minibatch, betas, use_graph,
-                               max_grad_norm=max_grad_norm, device_lr=device_lr, hip_backward=hip_backward)
+                               max_grad_norm=max_grad_norm, device_lr=device_lr, hip_backward=hip_backward, hip_forward=hip_forward)
 
     def _buffers(self, P, f, split, rows):
         B, M = P["B"], P["M"]
@@ -697,9 +750,10 @@ class FusedDistill(_FusedLearner):
         t, L, M = self.torch, self.L, P["M"]
         st = self._stream()
         idx = P["perm"][s * M:(s + 1) * M]
-        t.index_select(P["obs"], 0, idx, out=P["x"])
+        if not self.hip_forward:
+            t.index_select(P["obs"], 0, idx, out=P["x"])
         t.index_select(P["target"], 0, idx, out=P["tgt"])
-        self._mlp_forward(P, "pi", "", P["x"])
+        self._mlp_forward(P, "pi", "", (P["obs"], idx, None, None, P["x"]) if self.hip_forward else P["x"])
         _lib.check(L.orr_distill_head(P["y"].data_ptr(), P["tgt"].data_ptr(), M, P["g_y"].data_ptr(), self.g["model/pi/b:0"].data_ptr(),
                                       P["stats"][s].data_ptr(), P["ws"].data_ptr(), st), L)
         self._mlp_backward(P, "pi", "", P["x"], P["g_y"], 12, st)
@@ -732,7 +786,7 @@ class FusedDistillHistory(_FusedLearner):
     model's mark_updated()) -, everything behind it is the same.  The defaults (0, 1) are the path above, launch for launch."""
 
     def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, action_coef=0.0, latent_coef=1.0,
-                 max_grad_norm=None, device_lr=False, hip_backward=False):
+                 max_grad_norm=None, device_lr=False, hip_backward=False, hip_forward=False):
         self.action_coef, self.latent_coef = float(action_coef), float(latent_coef)
         if self.action_coef < 0.0 or self.latent_coef < 0.0:
             raise ValueError("FusedDistillHistory: action_coef and latent_coef must not be negative")
@@ -744,7 +798,8 @@ class FusedDistillHistory(_FusedLearner):
         if not getattr(student, "history", 0):
             raise ValueError("FusedDistillHistory: the student needs a history encoder (ActorCritic(history=16))")
         _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/enc_")), 2 if self.head else 1, lr, adam_eps,
-                               minibatch, betas, use_graph, max_grad_norm=max_grad_norm, device_lr=device_lr, hip_backward=hip_backward)
+                               minibatch, betas, use_graph, max_grad_norm=max_grad_norm, device_lr=device_lr, hip_backward=hip_backward,
+                               hip_forward=hip_forward)
 
     def _graph_key(self):
         return _FusedLearner._graph_key(self) + (self.action_coef, self.latent_coef)
@@ -796,9 +851,9 @@ class FusedDistillHistory(_FusedLearner):
         t, L, M = self.torch, self.L, P["M"]
         st = self._stream()
         idx = P["perm"][s * M:(s + 1) * M]
-        for src, dst in (("hist", "xh"), ("target", "tgt")) + ((("obs", "xo"), ("tmean", "tm")) if self.head else ()):
+        for src, dst in ((() if self.hip_forward else (("hist", "xh"),)) + (("target", "tgt"),) + ((("obs", "xo"), ("tmean", "tm")) if self.head else ())):
             t.index_select(P[src], 0, idx, out=P[dst])
-        self._enc_forward(P)
+        self._enc_forward(P, idx)
         if self.head:
             A = self._actor
             _lib.check(L.orr_history_student_head(C.byref(A["net"]), A["w2t"].data_ptr(), A["w1t"].data_ptr(), A["w0zt"].data_ptr(), P["xo"].data_ptr(),

@@ -227,6 +227,10 @@ def arg_parser():
     ap.add_argument("--hip-backward", action="store_true",
                     help="the fused learners' backward GEMMs of the hidden layers on hand-written matrix-core kernels (orr_wgrad, orr_dgrad_relu: "
                          "learner_hip's hip_backward=True) instead of library GEMMs + orr_relu_backward; every mode; not with --torch-learner")
+    ap.add_argument("--hip-forward", action="store_true",
+                    help="the fused learners' forward layers on a hand-written matrix-core kernel in the rollout's arithmetic, the minibatch's "
+                         "gathers in its loader (orr_dense_forward: learner_hip's hip_forward=True) instead of index_select + cat + library GEMMs; "
+                         "every mode; combines with --hip-backward; not with --torch-learner")
     ap.add_argument("--eval", default="", help="evaluate a policy zip instead of training: deterministic actions, test mode "
                                                  "(no randomiser, full-length episodes), like `run.py --mode test`")
     ap.add_argument("--legacy-gae-index", action="store_true",
@@ -449,9 +453,13 @@ def make_learner(args, model, mode, num_samples, rank):
     if args.torch_learner:
         if args.hip_backward:
             raise SystemExit("train.py: --hip-backward is the fused learners'; drop --torch-learner")
+        if args.hip_forward:
+            raise SystemExit("train.py: --hip-forward is the fused learners'; drop --torch-learner")
         return getattr(ppo, mode)(model, lr=args.lr, minibatch=args.minibatch, **kw)
     if args.hip_backward:                # no keyword without the flag: the learners' default
         kw["hip_backward"] = True
+    if args.hip_forward:
+        kw["hip_forward"] = True
     from openroborl_amd import learner_hip
     cls = getattr(learner_hip, "Fused" + mode)
     # equal minibatches only (static buffers of the graph-replayed update): the largest size <= --minibatch that divides the
