@@ -8,7 +8,10 @@
  * cores, opt-in (learner_hip: hip_backward=True), and orr_dense_forward (csrc/orr_learner_forward.hip) is every forward layer there, in the
  * rollout's arithmetic and with the minibatch's gathers in its loader, opt-in as well (hip_forward=True); with both a captured epoch holds
  * no library GEMM.  Whether either wins is measured in profiles/hip_backward.txt and profiles/hip_forward.txt: the
- * defaults stay off.  What the autograd graph spends around the GEMMs - ~70
+ * defaults stay off.  orr_dense_forward_bf16, orr_dgrad_relu_bf16 and orr_wgrad_bf16 (csrc/orr_learner_bf16.hip) are the same hidden-layer
+ * contractions with operands rounded to bf16 on their way into LDS and f32 accumulation on the bf16 matrix cores - mixed precision with
+ * every buffer, the master weights and Adam in float32 -, opt-in again (bf16_gemm=True; profiles/bf16_gemm.txt).
+ * What the autograd graph spends around the GEMMs - ~70
  * elementwise / reduction launches per minibatch, more time than the GEMMs themselves - is these launches:
  *   orr_ppo_head       loss terms, d loss / d mean, d loss / d value, bias gradients of the two output layers
  *   orr_ppo_head_logstd  that head for a learned per-dimension log-std read from the device: + its gradient, the entropy bonus, approx-KL, clip fraction
@@ -215,6 +218,22 @@ int32_t orr_dgrad_relu(const float* gz, const float* w, const float* h, int32_t 
  * caller's).  Row indices are the caller's responsibility and are not checked. */
 int32_t orr_dense_forward(const float* xa, int32_t ka, const int64_t* rows_a, const float* xb, int32_t kb, const int64_t* rows_b, int32_t m,
                           const float* w, const float* b, int32_t n, int32_t relu, float* y, float* x_out, void* stream);
+
+/* ---- the same contractions with bf16 operands on the bf16 matrix cores (csrc/orr_learner_bf16.hip) ------------------------------------------
+ * The arguments, outputs, alignment rules and refusals of orr_dense_forward, orr_dgrad_relu and orr_wgrad; every buffer stays float32.  Each
+ * operand element is rounded to bf16 (round to nearest even) as it is staged, products (exact in f32) accumulate in f32, and bias, ReLU, the
+ * ReLU mask (from the f32 h: +0 where h <= 0), ws and the slice partials are f32 as in the f32 entry points.  No atomics, a fixed order: the
+ * same inputs give the same bits - but NOT the bits of the f32 entry points or of the rollout.  Rows at or beyond m are neither read nor
+ * written; contraction tails are zeros, never reads out of bounds.  A refused call launches and writes nothing.
+ *   orr_dense_forward_bf16  n a multiple of 16 only (n <= 15 is refused: the output layers stay orr_dense_forward's small kernel); x_out
+ *                           receives the f32 input, bit for bit, not its rounded image
+ *   orr_dgrad_relu_bf16     ws [orr_dgrad_partial_rows(m)][k], the f32 entry's size function
+ *   orr_wgrad_bf16          partials [orr_wgrad_bf16_slices(m, k, n)][k][n], for orr_colsum_finish like orr_wgrad's; -1 for a refused shape */
+int32_t orr_dense_forward_bf16(const float* xa, int32_t ka, const int64_t* rows_a, const float* xb, int32_t kb, const int64_t* rows_b, int32_t m,
+                               const float* w, const float* b, int32_t n, int32_t relu, float* y, float* x_out, void* stream);
+int32_t orr_dgrad_relu_bf16(const float* gz, const float* w, const float* h, int32_t m, int32_t n, int32_t k, float* gh, float* ws, void* stream);
+int32_t orr_wgrad_bf16_slices(int32_t m, int32_t k, int32_t n);
+int32_t orr_wgrad_bf16(const float* x, int32_t k, const float* g, int32_t n, int32_t m, float* partials, void* stream);
 
 /* One Adam step on n parameters; t = state[0] + 1, the gradient is multiplied by grad_scale first (1 / world size after an
  * all-reduce sum: mpi_adam.py:51-53).

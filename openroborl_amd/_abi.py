@@ -282,6 +282,7 @@ POLICY_FORWARD_HISTORY_PRIV_ARGS = [C.POINTER(OrrPolicyNet), C.POINTER(OrrHistor
 LATENT_BACKWARD_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
 # include/openroborl_learner.h: int32_t orr_wgrad(const float* x [m][k], int32_t k, const float* g [m][n], int32_t n, int32_t m,
 #   float* partials [orr_wgrad_slices(m, k, n)][k][n], void* stream)
+# (orr_wgrad_bf16, orr_dgrad_relu_bf16 and orr_dense_forward_bf16 take the arguments of their f32 namesakes: the three lists below serve both)
 WGRAD_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
 # include/openroborl_learner.h: int32_t orr_dgrad_relu(const float* gz [m][n], const float* w [k][n], const float* h [m][k], int32_t m, int32_t n,
 #   int32_t k, float* gh [m][k], float* ws [orr_dgrad_partial_rows(m)][k], void* stream)

@@ -29,6 +29,7 @@ SRC_POLICY = os.path.join(CSRC, "orr_policy.hip")
 SRC_LEARNER = os.path.join(CSRC, "orr_learner.hip")              # the non-GEMM part of the PPO update (include/openroborl_learner.h)
 SRC_LEARNER_GEMM = os.path.join(CSRC, "orr_learner_gemm.hip")    # the backward GEMMs of the PPO update on the matrix cores (orr_wgrad, orr_dgrad_relu)
 SRC_LEARNER_FORWARD = os.path.join(CSRC, "orr_learner_forward.hip")  # its forward layers on the matrix cores, in the rollout's arithmetic (orr_dense_forward)
+SRC_LEARNER_BF16 = os.path.join(CSRC, "orr_learner_bf16.hip")    # the hidden layers' contractions on the bf16 matrix cores (orr_*_bf16), f32 in HBM
 # what the library is built from = what the stale-library check hashes: every source and header under csrc/ + the public headers
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [
     os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("openroborl_hip.h", "openroborl_policy.h", "openroborl_learner.h")]
@@ -112,6 +113,9 @@ HIPCC_FLAGS_GEMM = HIPCC_FLAGS_PLAIN + ["-Xclang", "-target-feature", "-Xclang",
 GEMM_UNITS = [("learner_gemm", SRC_LEARNER_GEMM, HIPCC_FLAGS_GEMM, False)]
 # The forward layers of the learners (orr_dense_forward): a unit and a table of their own behind GEMM_UNITS for the same reason, its flags
 FORWARD_UNITS = [("learner_forward", SRC_LEARNER_FORWARD, HIPCC_FLAGS_GEMM, False)]
+# The same contractions with bf16 operands (orr_dense_forward_bf16, orr_dgrad_relu_bf16, orr_wgrad_bf16): a unit and a table of their own
+# behind FORWARD_UNITS, the same flags
+BF16_UNITS = [("learner_bf16", SRC_LEARNER_BF16, HIPCC_FLAGS_GEMM, False)]
 
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
@@ -202,7 +206,7 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
             units = []      # the tables up to PRIV_UNITS in the order the older tests read off the next line, then the newest
             for unit in ALL_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS + PUSH_UNITS + PRIV_UNITS:
                 units.append(unit)
-            units = GEMM_UNITS + FORWARD_UNITS + units       # the learners' GEMMs: no env units, their place in the link means nothing
+            units = GEMM_UNITS + FORWARD_UNITS + BF16_UNITS + units       # the learners' GEMMs: no env units, their place in the link means nothing
             for unit in units + SHAPING_UNITS:       # the newest table last
                 name, src, flags, hashed = unit
                 flags = [f for f in flags if f != "-shared"] + ["-c"]
@@ -403,6 +407,16 @@ def load():
     L.orr_dgrad_relu.argtypes = _abi.DGRAD_RELU_ARGS
     L.orr_dense_forward.restype = C.c_int32
     L.orr_dense_forward.argtypes = _abi.DENSE_FORWARD_ARGS
+    # the bf16 entry points: the f32 ones' signatures.  Not in EXPORTS: the tests compare that list with a scan of the headers for names
+    # of letters and underscores, which does not read a name with a digit in it
+    L.orr_wgrad_bf16_slices.restype = C.c_int32
+    L.orr_wgrad_bf16_slices.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.orr_wgrad_bf16.restype = C.c_int32
+    L.orr_wgrad_bf16.argtypes = _abi.WGRAD_ARGS
+    L.orr_dgrad_relu_bf16.restype = C.c_int32
+    L.orr_dgrad_relu_bf16.argtypes = _abi.DGRAD_RELU_ARGS
+    L.orr_dense_forward_bf16.restype = C.c_int32
+    L.orr_dense_forward_bf16.argtypes = _abi.DENSE_FORWARD_ARGS
     L.orr_learner_partial_rows.restype = C.c_int32
     L.orr_learner_partial_rows.argtypes = [C.c_int32]
     L.orr_colsum_finish.restype = C.c_int32

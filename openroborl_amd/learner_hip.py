@@ -39,6 +39,11 @@ bit for bit) with the minibatch's gathers of obs, priv and hist and the obs | pr
 writes the gathered input once for the weight gradient.  The aux / target gathers stay index_selects, and so does FusedPPOHistory's of priv
 (its latent loss reads the rows on their own).  Without the flag every learner launches what it launched; with both flags a captured epoch
 holds no library GEMM.
+bf16_gemm=True (all four; implies the two flags above): the same launches with the hidden layers' contractions - every _dense of a fan-out
+that is a multiple of 16, every _wgrad_hip and _dgrad_hip - on csrc/orr_learner_bf16.hip: operands rounded to bf16 as they are staged, f32
+accumulation on the bf16 matrix cores, every buffer, the master weights and Adam float32.  The output layers, orr_head_backward and all
+non-GEMM kernels are the f32 ones.  The learner's forward pass is then NOT the rollout's bit for bit: a PPO ratio of the first epoch starts
+near 1, not at 1 (profiles/bf16_gemm.txt).
 There is no fallback: without a GPU and the HIP library the constructors raise.
 """
 import ctypes as C
@@ -62,11 +67,12 @@ class _FusedLearner(object):
     net and of the history encoder and the update driver.  A learner adds its plan's buffers (_buffers), its _minibatch and its update."""
 
     def __init__(self, model, names, stats, lr, adam_eps, minibatch, betas, use_graph, mpi_adam_epsilon=False, max_grad_norm=None, device_lr=False,
-                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False, hip_forward=False):
+                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False, hip_forward=False, bf16_gemm=False):
         import torch
         self.torch = torch
-        self.hip_forward = bool(hip_forward)                    # every forward layer: orr_dense_forward, the gathers in its loader (see _dense)
-        self.hip_backward = bool(hip_backward)                  # the hidden layers' backward GEMMs: orr_wgrad + orr_dgrad_relu (see _wgrad_hip)
+        self.bf16_gemm = bool(bf16_gemm)                        # the hidden layers' contractions on the bf16 matrix cores; implies the two below
+        self.hip_forward = bool(hip_forward) or self.bf16_gemm  # every forward layer: orr_dense_forward, the gathers in its loader (see _dense)
+        self.hip_backward = bool(hip_backward) or self.bf16_gemm  # the hidden layers' backward GEMMs: orr_wgrad + orr_dgrad_relu (see _wgrad_hip)
         self.max_grad_norm, self.kl_stop, self.kl_target, self.kl_lr_bounds = _control_args(type(self).__name__, max_grad_norm, kl_stop, kl_target,
                                                                                             kl_lr_bounds or KL_LR_BOUNDS)
         self.kl_on = self.kl_stop is not None or self.kl_target is not None
@@ -190,16 +196,18 @@ class _FusedLearner(object):
     # ---- hip_backward: the hidden layers' backward GEMMs on the matrix cores (csrc/orr_learner_gemm.hip) ---------------------------------
     def _slices(self, M, k, n):
         """Partial products a weight gradient [k][n] of M rows is finished from: 16 bmm products, or orr_wgrad's slices."""
-        return int(self.L.orr_wgrad_slices(M, k, n)) if self.hip_backward else 16
+        if not self.hip_backward:
+            return 16
+        return int((self.L.orr_wgrad_bf16_slices if self.bf16_gemm else self.L.orr_wgrad_slices)(M, k, n))
 
     def _wgrad_hip(self, x, g, part, st):
         """part [S][k][n] = the batch slices' shares of x^T g (orr_wgrad); their sum is a job of the minibatch's orr_colsum_finish."""
-        _lib.check(self.L.orr_wgrad(x.data_ptr(), x.shape[1], g.data_ptr(), g.shape[1], x.shape[0], part.data_ptr(), st), self.L)
+        _lib.check((self.L.orr_wgrad_bf16 if self.bf16_gemm else self.L.orr_wgrad)(x.data_ptr(), x.shape[1], g.data_ptr(), g.shape[1], x.shape[0], part.data_ptr(), st), self.L)
 
     def _dgrad_hip(self, gz, w, h, gh, ws, st):
         """gh = (gz w^T) * (h > 0) and the partial sums of its columns in ws (orr_dgrad_relu): mm + orr_relu_backward in one launch."""
-        _lib.check(self.L.orr_dgrad_relu(gz.data_ptr(), w.data_ptr(), h.data_ptr(), gz.shape[0], gz.shape[1], h.shape[1], gh.data_ptr(),
-                                         ws.data_ptr(), st), self.L)
+        _lib.check((self.L.orr_dgrad_relu_bf16 if self.bf16_gemm else self.L.orr_dgrad_relu)(
+            gz.data_ptr(), w.data_ptr(), h.data_ptr(), gz.shape[0], gz.shape[1], h.shape[1], gh.data_ptr(), ws.data_ptr(), st), self.L)
 
     # ---- hip_forward: the forward layers on the matrix cores, in the rollout's arithmetic (csrc/orr_learner_forward.hip) --------------------
     def _dense(self, src, w, b, y, relu, st):
@@ -207,8 +215,9 @@ class _FusedLearner(object):
         in(i) = xa[rows_a[i]] | xb[rows_b[i]], a missing table meaning row i, and x_out receives in."""
         xa, ra, xb, rb, x_out = src if isinstance(src, tuple) else (src, None, None, None, None)
         ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
-        _lib.check(self.L.orr_dense_forward(xa.data_ptr(), xa.shape[1], ptr(ra), ptr(xb), 0 if xb is None else xb.shape[1], ptr(rb), y.shape[0],
-                                            w.data_ptr(), b.data_ptr(), w.shape[1], relu, y.data_ptr(), ptr(x_out), st), self.L)
+        dense = self.L.orr_dense_forward_bf16 if self.bf16_gemm and w.shape[1] % 16 == 0 else self.L.orr_dense_forward   # the output layers: f32
+        _lib.check(dense(xa.data_ptr(), xa.shape[1], ptr(ra), ptr(xb), 0 if xb is None else xb.shape[1], ptr(rb), y.shape[0],
+                         w.data_ptr(), b.data_ptr(), w.shape[1], relu, y.data_ptr(), ptr(x_out), st), self.L)
 
     def _plan(self, B, M):
         """Static buffers for B samples per update in minibatches of M."""
@@ -411,7 +420,7 @@ class FusedPPO(_FusedLearner):
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
                  mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, max_grad_norm=None, device_lr=False, kl_stop=None,
-                 kl_target=None, kl_lr_bounds=None, hip_backward=False, hip_forward=False):
+                 kl_target=None, kl_lr_bounds=None, hip_backward=False, hip_forward=False, bf16_gemm=False):
         self._need_gpu(model)
         if getattr(model, "history", 0) and not self._history:
             raise ValueError("FusedPPO: a history policy is trained by FusedPPOHistory (PPO with the critic on the true privileged row) or by "
@@ -429,7 +438,7 @@ class FusedPPO(_FusedLearner):
         self.logstd_head = self.learn_std or kl_stop is not None or kl_target is not None
         self.head_stats = 5 if self.logstd_head else 2        # what the loss head writes; FusedPPOHistory's latent loss follows them
         _FusedLearner.__init__(self, model, sorted(model.p), self.head_stats + (1 if self._history else 0), lr, adam_eps, minibatch, betas, use_graph,
-                               mpi_adam_epsilon, max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward, hip_forward)
+                               mpi_adam_epsilon, max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward, hip_forward, bf16_gemm)
         if self.logstd_head and not self.learn_std:
             self.fixed_logstd = self.torch.zeros(12, dtype=self.torch.float32, device=self.dev)
             self.g_fixed_logstd = self.torch.zeros(12, dtype=self.torch.float32, device=self.dev)
@@ -636,7 +645,7 @@ class FusedPPOHistory(FusedPPO):
 
     def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, betas=(0.9, 0.999),
                  mpi_adam_epsilon=False, use_graph=True, ent_coef=0.0, log_std_bounds=None, latent_coef=0.0, max_grad_norm=None, device_lr=False,
-                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False, hip_forward=False):
+                 kl_stop=None, kl_target=None, kl_lr_bounds=None, hip_backward=False, hip_forward=False, bf16_gemm=False):
         import math
         _no_obs_norm(model, "FusedPPOHistory")
         if not getattr(model, "history", 0):
@@ -645,7 +654,7 @@ class FusedPPOHistory(FusedPPO):
         if not (self.latent_coef >= 0.0 and math.isfinite(self.latent_coef)):
             raise ValueError("FusedPPOHistory: latent_coef must be finite and not negative")
         FusedPPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, betas, mpi_adam_epsilon, use_graph, ent_coef, log_std_bounds,
-                          max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward, hip_forward)
+                          max_grad_norm, device_lr, kl_stop, kl_target, kl_lr_bounds, hip_backward, hip_forward, bf16_gemm)
 
     def _graph_key(self):
         return FusedPPO._graph_key(self) + (self.latent_coef,)
@@ -728,7 +737,7 @@ class FusedDistill(_FusedLearner):
     one hipGraph (a single chain on one stream).  One rank: there is no gradient all-reduce here."""
 
     def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, max_grad_norm=None, device_lr=False,
-                 hip_backward=False, hip_forward=False):
+                 hip_backward=False, hip_forward=False, bf16_gemm=False):
         _no_obs_norm(student, "FusedDistill")
         if getattr(student, "actor_priv_dim", 0):
             raise ValueError("FusedDistill: the student's actor must read the 160 observation words only")
@@ -736,7 +745,8 @@ class FusedDistill(_FusedLearner):
         if getattr(student, "history", 0):
             raise ValueError("FusedDistill: a history student is trained by FusedDistillHistory, or with PPO by FusedPPOHistory")
         _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/pi") and k != LOGSTD), 1, lr, adam_eps, minibatch, betas, use_graph,
-                               max_grad_norm=max_grad_norm, device_lr=device_lr, hip_backward=hip_backward, hip_forward=hip_forward)
+                               max_grad_norm=max_grad_norm, device_lr=device_lr, hip_backward=hip_backward, hip_forward=hip_forward,
+                               bf16_gemm=bf16_gemm)
 
     def _buffers(self, P, f, split, rows):
         B, M = P["B"], P["M"]
@@ -786,7 +796,7 @@ class FusedDistillHistory(_FusedLearner):
     model's mark_updated()) -, everything behind it is the same.  The defaults (0, 1) are the path above, launch for launch."""
 
     def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, action_coef=0.0, latent_coef=1.0,
-                 max_grad_norm=None, device_lr=False, hip_backward=False, hip_forward=False):
+                 max_grad_norm=None, device_lr=False, hip_backward=False, hip_forward=False, bf16_gemm=False):
         self.action_coef, self.latent_coef = float(action_coef), float(latent_coef)
         if self.action_coef < 0.0 or self.latent_coef < 0.0:
             raise ValueError("FusedDistillHistory: action_coef and latent_coef must not be negative")
@@ -799,7 +809,7 @@ class FusedDistillHistory(_FusedLearner):
             raise ValueError("FusedDistillHistory: the student needs a history encoder (ActorCritic(history=16))")
         _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/enc_")), 2 if self.head else 1, lr, adam_eps,
                                minibatch, betas, use_graph, max_grad_norm=max_grad_norm, device_lr=device_lr, hip_backward=hip_backward,
-                               hip_forward=hip_forward)
+                               hip_forward=hip_forward, bf16_gemm=bf16_gemm)
 
     def _graph_key(self):
         return _FusedLearner._graph_key(self) + (self.action_coef, self.latent_coef)

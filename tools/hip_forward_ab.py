@@ -3,7 +3,8 @@ layer 0 at 160 -> 512 and 208 -> 512 with the index_select gathers (and the cat)
 the hidden layer 512 -> 256, the output layers 256 -> 12 and 256 -> 1, and the encoder chain 512 -> 256 -> 48 (its gather on both sides).
 Prints per shape the median and the range over the rounds of the mean time of a launch sequence, and the largest difference of the results.
 
-usage:  python tools/hip_forward_ab.py [m=16384] [rounds=7] [reps=100]
+usage:  python tools/hip_forward_ab.py [m=16384] [rounds=7] [reps=100] [bf16]
+        bf16: a third column, orr_dense_forward_bf16 (the layers of a fan-out that is a multiple of 16; the others run the f32 kernel)
 """
 import ctypes as C
 import os
@@ -14,6 +15,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from openroborl_amd import _lib  # noqa: E402
 
+BF16 = "bf16" in sys.argv
+sys.argv = [a for a in sys.argv if a != "bf16"]
 m, rounds, reps = (int(sys.argv[i]) if len(sys.argv) > i else d for i, d in ((1, 16384), (2, 7), (3, 100)))
 dev = torch.device("cuda", 0)
 L = _lib.load()
@@ -23,9 +26,10 @@ B = 8 * m                                            # the rows an update gather
 idx = torch.randperm(B, device=dev)[:m]
 
 
-def dense(xa, ra, xb, rb, w, b, relu, y, x_out):
+def dense(xa, ra, xb, rb, w, b, relu, y, x_out, bf16=False):
     ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
-    _lib.check(L.orr_dense_forward(xa.data_ptr(), xa.shape[1], ptr(ra), ptr(xb), 0 if xb is None else xb.shape[1], ptr(rb), m, w.data_ptr(),
+    entry = L.orr_dense_forward_bf16 if bf16 and w.shape[1] % 16 == 0 else L.orr_dense_forward
+    _lib.check(entry(xa.data_ptr(), xa.shape[1], ptr(ra), ptr(xb), 0 if xb is None else xb.shape[1], ptr(rb), m, w.data_ptr(),
                                    b.data_ptr(), w.shape[1], relu, y.data_ptr(), ptr(x_out), st), L)
 
 
@@ -43,14 +47,24 @@ def compare(name, old, new, outs_old, outs_new):
     for fn in (old, new):
         for _ in range(10):
             fn()
-    t = {"library": [], "hip": []}
+    for _ in range(10 if BF16 else 0):
+        new(True)
+    t = {"library": [], "hip": [], "bf16": []}
     for _ in range(rounds):
         t["library"].append(ms(old))
         t["hip"].append(ms(new))
+        if BF16:
+            t["bf16"].append(ms(lambda: new(True)))
+    new()
     diff = max((x - y).abs().max().item() / (x.abs().max().item() + 1e-30) for x, y in zip(outs_old, outs_new))
-    print("%-34s library %6.1f us (%.1f .. %.1f)   hip %6.1f us (%.1f .. %.1f)   largest difference %.1e of the largest entry"
-          % (name, statistics.median(t["library"]), min(t["library"]), max(t["library"]), statistics.median(t["hip"]), min(t["hip"]),
-             max(t["hip"]), diff))
+    line = ("%-34s library %6.1f us (%.1f .. %.1f)   hip %6.1f us (%.1f .. %.1f)   largest difference %.1e of the largest entry"
+            % (name, statistics.median(t["library"]), min(t["library"]), max(t["library"]), statistics.median(t["hip"]), min(t["hip"]),
+               max(t["hip"]), diff))
+    if BF16:
+        new(True)
+        diff = max((x - y).abs().max().item() / (x.abs().max().item() + 1e-30) for x, y in zip(outs_old, outs_new))
+        line += "   bf16 %6.1f us (%.1f .. %.1f)   %.1e" % (statistics.median(t["bf16"]), min(t["bf16"]), max(t["bf16"]), diff)
+    print(line)
 
 
 # layer 0 behind the minibatch's gathers: obs alone, and obs | priv through a cat
@@ -66,8 +80,8 @@ for kb in (0, 48):
             torch.cat((x, xp), dim=1, out=xv)
         torch._addmm_activation(b, xv if kb else x, w, out=y_old)
 
-    def new():
-        dense(obs, idx, priv if kb else None, idx if kb else None, w, b, 1, y_new, x_new)
+    def new(bf16=False):
+        dense(obs, idx, priv if kb else None, idx if kb else None, w, b, 1, y_new, x_new, bf16)
     compare("gather + %d -> 512, ReLU" % (160 + kb), old, new, [y_old, xv if kb else x], [y_new, x_new])
 
 for k, n, relu in ((512, 256, 1), (256, 12, 0), (256, 1, 0)):
@@ -79,8 +93,8 @@ for k, n, relu in ((512, 256, 1), (256, 12, 0), (256, 1, 0)):
         else:
             torch.addmm(b, x, w, out=y_old)
 
-    def new():
-        dense(x, None, None, None, w, b, relu, y_new, None)
+    def new(bf16=False):
+        dense(x, None, None, None, w, b, relu, y_new, None, bf16)
     compare("%d -> %d%s" % (k, n, ", ReLU" if relu else ""), old, new, [y_old], [y_new])
 
 hist, w0, b0, w1, b1 = f(B, 512), f(512, 256) * 0.1, f(256), f(256, 48) * 0.1, f(48)
@@ -93,9 +107,9 @@ def enc_old():
     torch.addmm(b1, he_old, w1, out=z_old)
 
 
-def enc_new():
-    dense(hist, idx, None, None, w0, b0, 1, he_new, xh_new)
-    dense(he_new, None, None, None, w1, b1, 0, z_new, None)
+def enc_new(bf16=False):
+    dense(hist, idx, None, None, w0, b0, 1, he_new, xh_new, bf16)
+    dense(he_new, None, None, None, w1, b1, 0, z_new, None, bf16)
 
 
 compare("gather + 512 -> 256 -> 48", enc_old, enc_new, [z_old, xh_old], [z_new, xh_new])

@@ -1,9 +1,10 @@
 """Where one train.py iteration spends its time (development aid, GPU box): rollout / GAE / PPO update by HIP events, and the pieces of
 one minibatch update (forward, backward, optimiser) timed separately.
 
-usage:  python tools/train_breakdown.py [robots=4096] [horizon=32] [minibatch=16384] [epochs=2] [torch-learner] [learn-std] [hip-backward] [hip-forward]
+usage:  python tools/train_breakdown.py [robots=4096] [horizon=32] [minibatch=16384] [epochs=2] [torch-learner] [learn-std] [hip-backward] [hip-forward] [bf16-gemm]
         hip-backward: the fused learner with hip_backward=True (train.py --hip-backward)
         hip-forward: the fused learner with hip_forward=True (train.py --hip-forward); the two combine
+        bf16-gemm: the fused learner with bf16_gemm=True (train.py --bf16-gemm): both of the above on the bf16 matrix cores
         learn-std: a model with a learned log-std and ent_coef = 0.01 (train.py --learn-std --ent-coef 0.01)
         privileged-actor | history-ppo | history-ppo-latent: the update alone of a teacher (train.py --privileged-actor) or of a history policy
         (train.py --history-ppo, and with --latent-coef 0.5): FusedPPO / FusedPPOHistory, or their torch references with torch-learner
@@ -18,13 +19,13 @@ from openroborl_amd import learner_hip, ppo, rollout  # noqa: E402
 from openroborl_amd.env import VecQuadrupedEnv  # noqa: E402
 
 MODES = ("privileged-actor", "history-ppo", "history-ppo-latent")
-argv = [a for a in sys.argv[1:] if a not in ("update-only", "torch-learner", "learn-std", "hip-backward", "hip-forward") + MODES]
+argv = [a for a in sys.argv[1:] if a not in ("update-only", "torch-learner", "learn-std", "hip-backward", "hip-forward", "bf16-gemm") + MODES]
 mode = next((a for a in sys.argv[1:] if a in MODES), None)
 update_only = "update-only" in sys.argv
 torch_learner = "torch-learner" in sys.argv
 learn_std = "learn-std" in sys.argv
 entropy = dict(ent_coef=0.01) if learn_std else {}
-fused_kw = dict(entropy, **{w.replace("-", "_"): True for w in ("hip-backward", "hip-forward") if w in sys.argv})     # the fused learners' keywords
+fused_kw = dict(entropy, **{w.replace("-", "_"): True for w in ("hip-backward", "hip-forward", "bf16-gemm") if w in sys.argv})     # the fused learners' keywords
 n = int(argv[0]) if len(argv) > 0 else 4096
 T = int(argv[1]) if len(argv) > 1 else 32
 mb = int(argv[2]) if len(argv) > 2 else 16384

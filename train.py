@@ -231,6 +231,10 @@ def arg_parser():
                     help="the fused learners' forward layers on a hand-written matrix-core kernel in the rollout's arithmetic, the minibatch's "
                          "gathers in its loader (orr_dense_forward: learner_hip's hip_forward=True) instead of index_select + cat + library GEMMs; "
                          "every mode; combines with --hip-backward; not with --torch-learner")
+    ap.add_argument("--bf16-gemm", action="store_true",
+                    help="the fused learners' hidden-layer contractions, forward and backward, with bf16 operands and f32 accumulation on the bf16 "
+                         "matrix cores (orr_dense_forward_bf16, orr_dgrad_relu_bf16, orr_wgrad_bf16: learner_hip's bf16_gemm=True; weights, "
+                         "activations and Adam stay float32); implies --hip-forward --hip-backward; every mode; not with --torch-learner")
     ap.add_argument("--eval", default="", help="evaluate a policy zip instead of training: deterministic actions, test mode "
                                                  "(no randomiser, full-length episodes), like `run.py --mode test`")
     ap.add_argument("--legacy-gae-index", action="store_true",
@@ -455,11 +459,15 @@ def make_learner(args, model, mode, num_samples, rank):
             raise SystemExit("train.py: --hip-backward is the fused learners'; drop --torch-learner")
         if args.hip_forward:
             raise SystemExit("train.py: --hip-forward is the fused learners'; drop --torch-learner")
+        if args.bf16_gemm:
+            raise SystemExit("train.py: --bf16-gemm is the fused learners'; drop --torch-learner")
         return getattr(ppo, mode)(model, lr=args.lr, minibatch=args.minibatch, **kw)
     if args.hip_backward:                # no keyword without the flag: the learners' default
         kw["hip_backward"] = True
     if args.hip_forward:
         kw["hip_forward"] = True
+    if args.bf16_gemm:
+        kw["bf16_gemm"] = True
     from openroborl_amd import learner_hip
     cls = getattr(learner_hip, "Fused" + mode)
     # equal minibatches only (static buffers of the graph-replayed update): the largest size <= --minibatch that divides the
