@@ -20,6 +20,7 @@
  *   orr_regress_head   the loss head of a history student's encoder: squared error of its 48 outputs against the privileged row, its gradient
  *   orr_history_student_head  that head with the action loss: forward through the frozen actor, both losses, backward to the latent, one launch
  *   orr_latent_backward  PPO on a history policy: the gradient from the actor's layer 0 into the encoder's output + the auxiliary estimation loss
+ *   orr_gru_backward   the recurrent student's GRU backward through the T steps of a segment, a workgroup per 16 robots (csrc/orr_recurrent.hip)
  *   orr_head_backward  gradient through an output layer (fan-out 12 or 1) + ReLU mask + bias gradient of the layer below + the
  *                      output layer's weight gradient
  *   orr_colsum_finish  the column sums behind all bias gradients of a minibatch in one launch
@@ -158,6 +159,33 @@ int32_t orr_history_student_head(const orr_policy_net* net, const float* w2t, co
 #define ORR_LATENT_BACKWARD_PARTIAL_FLOATS(m) (49 * (int64_t)ORR_LATENT_BACKWARD_ROWS(m))
 int32_t orr_latent_backward(const float* g0, const float* w0zt, const float* z, const float* target_priv, int32_t m, float latent_coef,
                             float* g_z, float* partials, void* stream);
+
+/* Backward through time of the recurrent student's GRU (orr_gru_forward, openroborl_policy.h; csrc/orr_recurrent.hip; host side:
+ * learner_hip.FusedDistillRecurrent): truncated BPTT over a segment of T steps for n robots, t descending, one launch.  A workgroup owns 16
+ * robots for all T steps and carries dh in its accumulators:
+ *   dh  += g_latent_t Wo^T
+ *   du   = dh * (h' - c);  dc = dh * (1 - u);  dc_pre = dc (1 - c^2);  du_pre = du u (1 - u);  dr_pre = dc_pre * q * r (1 - r)
+ *   g_x[t] = dr_pre | du_pre | dc_pre          g_h[t] = dr_pre | du_pre | r * dc_pre
+ *   dh   = start_t ? 0 : (u * dh + g_h[t] Wh^T)
+ * g_x and g_h are the gradients at the pre-activations of the x and the h' contraction: Wx, Wh and Wo's gradients are frames^T g_x,
+ * hprev^T g_h and hid^T g_latent (three orr_wgrad).  The gradient with respect to h0 is not produced: h0 is data.
+ *   enc       wht: orr_policy_pack of Wh^T [768][256];  wot: of Wo^T zero-padded to [48][256]
+ *   g_latent  [T][n][48] d loss / d z;  saved [T][n][4][256], hprev [T][n][256]: orr_gru_forward's;  starts [T][n] uint8: its input
+ *   g_x, g_h  [T][n][768]
+ *   partials  ORR_GRU_BACKWARD_PARTIAL_FLOATS(n) floats, rows = ORR_GRU_BACKWARD_ROWS(n) = one per workgroup: [rows][768] the workgroup's
+ *             column sums of g_x over its robots and all steps, followed by [rows][768] those of g_h.  orr_colsum_finish folds them as two
+ *             jobs, {partials, d bx [768], rows, 768} and {partials + 768 rows, d bh [768], rows, 768}
+ * No float atomics and a fixed order: the same inputs give the same bits.  Refused with a negative code, nothing launched or written: a null
+ * pointer; T < 1 or n < 1; packed matrices, saved, g_x or g_h not 16-byte aligned; another buffer not aligned to its element; outputs that
+ * overlap each other or an input. */
+#define ORR_GRU_BACKWARD_ROWS(n) (((n) + 15) / 16)
+#define ORR_GRU_BACKWARD_PARTIAL_FLOATS(n) (2 * 768 * (int64_t)ORR_GRU_BACKWARD_ROWS(n))
+typedef struct orr_gru_transposed {
+  const float* wht;   /* 768 x 256, packed by orr_policy_pack */
+  const float* wot;   /* 48 x 256,  packed */
+} orr_gru_transposed;
+int32_t orr_gru_backward(const orr_gru_transposed* enc, const float* g_latent, const float* saved, const float* hprev, const uint8_t* starts,
+                         int32_t t, int32_t n, float* g_x, float* g_h, float* partials, void* stream);
 
 /* g [m][c] (gradient w.r.t. a ReLU layer's output h [m][c]) becomes the gradient w.r.t. its pre-activation, in place: g *= (h > 0);
  * gb [c] = its column sums (the layer's bias gradient).  c: a multiple of 4 with 1024 % c == 0.

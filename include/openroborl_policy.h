@@ -140,6 +140,36 @@ int32_t orr_policy_forward_history_priv(const orr_policy_net* net, const orr_his
                                         const float* priv, int32_t n, const float* noise, float std, float clip, float* action, float* raw,
                                         float* value, float* mean, float* latent, void* stream);
 
+/* A RECURRENT history student: a GRU over the per-step sensor frame estimates the privileged row, its hidden state living as long as the
+ * episode (csrc/orr_recurrent.hip; host side: ppo.ActorCritic(recurrent=256), learner_hip.FusedDistillRecurrent).  With x_t the 32-word frame
+ * of obs_t (orr_history_push's: obs[0:4] | obs[12:24] | obs[48:60] | four zeros) and the gate order r | u | c along the 768 columns:
+ *   h'  = start_t ? 0 : h_{t-1}
+ *   r   = sigmoid(x_t Wx_r + bx_r + h' Wh_r + bh_r)        u = sigmoid(x_t Wx_u + bx_u + h' Wh_u + bh_u)
+ *   q   = h' Wh_c + bh_c                                    c = tanh(x_t Wx_c + bx_c + r * q)
+ *   h_t = (1 - u) * c + u * h'                              z_t = h_t Wo + bo
+ * One launch runs T steps for n robots; a workgroup keeps its 16 robots' hidden state in LDS over all of them, on the f32 matrix cores.
+ *   enc     wx, wh, wo: orr_policy_pack of the 32 x 768, 256 x 768 and 256 x 48 matrices; bx [768], bh [768], bo [48]
+ *   obs     [T][n][160]
+ *   starts  [T][n] uint8: starts[t][i] != 0 = obs[t][i] is the first observation of an episode (the done flag of the step that produced it).
+ *           NULL: everybody starts at t = 0, allowed with T = 1 only
+ *   h0      [n][256] the state before step 0; NULL: zeros
+ *   hid     [T][n][256] receives h_t.  It may BE h0 when T = 1 (the rollout's step, in place); any other overlap is refused
+ *   latent  [T][n][48] receives z_t, what orr_policy_forward_teacher then reads as priv; may be NULL
+ *   frames  [T][n][32] x_t;  hprev [T][n][256] the h' each step consumed;  saved [T][n][4][256] r, u, c, q: the training outputs (what
+ *           orr_gru_backward and the weight gradients read).  Each may be NULL, which changes no other output bit
+ * T chained calls with T = 1 (hid -> h0, starts[t]) give the bits of one call over T.  No atomics: the same inputs give the same bits.
+ * Refused with a negative code, nothing launched or written: a null enc, member of it, obs or hid; T < 1 or n < 1; a null starts with T > 1;
+ * packed matrices, hid or saved not 16-byte aligned; another buffer not aligned to its element; outputs that overlap each other or an input. */
+#define ORR_GRU_HIDDEN 256
+#define ORR_GRU_GATES 768
+typedef struct orr_gru_encoder {
+  const float* wx; const float* bx;   /* 32 x 768,  packed by orr_policy_pack; bias 768 */
+  const float* wh; const float* bh;   /* 256 x 768, packed;                    bias 768 */
+  const float* wo; const float* bo;   /* 256 x 48,  packed;                    bias 48  */
+} orr_gru_encoder;
+int32_t orr_gru_forward(const orr_gru_encoder* enc, const float* obs, const uint8_t* starts, const float* h0, int32_t t, int32_t n, float* hid,
+                        float* latent, float* frames, float* hprev, float* saved, void* stream);
+
 /* Per-robot GAE(lambda) over a [T][N] rollout segment + per-robot advantage standardisation, one launch
  * (reference: add_vtarg_and_adv, agents/ppo_imitation.py:68-93, and the per-robot normalisation :329-338; device
  * layout and the deliberate use of each robot's own done flags: openroborl_amd/rollout.py).

@@ -214,6 +214,38 @@ HISTORY_FRAME = 32
 HISTORY_DIM = 512
 
 
+# include/openroborl_policy.h: ORR_GRU_HIDDEN, ORR_GRU_GATES and orr_gru_encoder (orr_gru_forward); include/openroborl_learner.h:
+# orr_gru_transposed, ORR_GRU_BACKWARD_ROWS (orr_gru_backward)
+GRU_HIDDEN = 256
+GRU_GATES = 768
+
+
+class OrrGruEncoder(C.Structure):
+    """include/openroborl_policy.h: orr_gru_encoder (packed weights + biases of a recurrent student's GRU and its output layer)."""
+    _fields_ = [(n, C.c_void_p) for n in ("wx", "bx", "wh", "bh", "wo", "bo")]
+
+
+class OrrGruTransposed(C.Structure):
+    """include/openroborl_learner.h: orr_gru_transposed (the packed transposes orr_gru_backward contracts with)."""
+    _fields_ = [(n, C.c_void_p) for n in ("wht", "wot")]
+
+
+# int32_t orr_gru_forward(const orr_gru_encoder* enc, const float* obs [T][n][160], const uint8_t* starts [T][n] | NULL, const float* h0 [n][256] | NULL,
+#   int32_t t, int32_t n, float* hid [T][n][256], float* latent [T][n][48] | NULL, float* frames [T][n][32] | NULL, float* hprev [T][n][256] | NULL,
+#   float* saved [T][n][4][256] | NULL, void* stream)
+GRU_FORWARD_ARGS = [C.POINTER(OrrGruEncoder), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                    C.c_void_p, C.c_void_p]
+# int32_t orr_gru_backward(const orr_gru_transposed* enc, const float* g_latent [T][n][48], const float* saved, const float* hprev, const uint8_t* starts,
+#   int32_t t, int32_t n, float* g_x [T][n][768], float* g_h [T][n][768], float* partials [2][gru_backward_rows(n)][768], void* stream)
+GRU_BACKWARD_ARGS = [C.POINTER(OrrGruTransposed), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                     C.c_void_p]
+
+
+def gru_backward_rows(n):
+    """include/openroborl_learner.h: ORR_GRU_BACKWARD_ROWS - the rows of partial sums orr_gru_backward leaves, one per 16 robots."""
+    return (int(n) + 15) // 16
+
+
 class OrrColsumJob(C.Structure):
     """include/openroborl_learner.h: orr_colsum_job."""
     _fields_ = [("partials", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]

@@ -30,6 +30,7 @@ SRC_LEARNER = os.path.join(CSRC, "orr_learner.hip")              # the non-GEMM 
 SRC_LEARNER_GEMM = os.path.join(CSRC, "orr_learner_gemm.hip")    # the backward GEMMs of the PPO update on the matrix cores (orr_wgrad, orr_dgrad_relu)
 SRC_LEARNER_FORWARD = os.path.join(CSRC, "orr_learner_forward.hip")  # its forward layers on the matrix cores, in the rollout's arithmetic (orr_dense_forward)
 SRC_LEARNER_BF16 = os.path.join(CSRC, "orr_learner_bf16.hip")    # the hidden layers' contractions on the bf16 matrix cores (orr_*_bf16), f32 in HBM
+SRC_RECURRENT = os.path.join(CSRC, "orr_recurrent.hip")          # the recurrent student's GRU, forward and backward through time (orr_gru_*)
 # what the library is built from = what the stale-library check hashes: every source and header under csrc/ + the public headers
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [
     os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("openroborl_hip.h", "openroborl_policy.h", "openroborl_learner.h")]
@@ -116,6 +117,8 @@ FORWARD_UNITS = [("learner_forward", SRC_LEARNER_FORWARD, HIPCC_FLAGS_GEMM, Fals
 # The same contractions with bf16 operands (orr_dense_forward_bf16, orr_dgrad_relu_bf16, orr_wgrad_bf16): a unit and a table of their own
 # behind FORWARD_UNITS, the same flags
 BF16_UNITS = [("learner_bf16", SRC_LEARNER_BF16, HIPCC_FLAGS_GEMM, False)]
+# The recurrent student's GRU (orr_gru_forward, orr_gru_backward): a unit and a table of their own behind BF16_UNITS, the same flags
+RECURRENT_UNITS = [("recurrent", SRC_RECURRENT, HIPCC_FLAGS_GEMM, False)]
 
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
@@ -125,6 +128,7 @@ EXPORTS = [
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_history", "orr_policy_forward_history_priv", "orr_history_push", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_ppo_head_logstd", "orr_gauss_prepare", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_latent_backward", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
     "orr_wgrad_slices", "orr_wgrad", "orr_dgrad_partial_rows", "orr_dgrad_relu", "orr_dense_forward",
+    "orr_gru_forward", "orr_gru_backward",
     "orr_sizeof_update_ctl", "orr_update_control_partials", "orr_update_control", "orr_adam_step_ctl",
     "orr_sizeof_running_stats", "orr_running_stats_partials", "orr_running_stats_update", "orr_normalize_rows", "orr_policy_pack_norm",
 ]
@@ -206,7 +210,7 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
             units = []      # the tables up to PRIV_UNITS in the order the older tests read off the next line, then the newest
             for unit in ALL_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS + PUSH_UNITS + PRIV_UNITS:
                 units.append(unit)
-            units = GEMM_UNITS + FORWARD_UNITS + BF16_UNITS + units       # the learners' GEMMs: no env units, their place in the link means nothing
+            units = GEMM_UNITS + FORWARD_UNITS + BF16_UNITS + RECURRENT_UNITS + units       # the learners' GEMMs: no env units, their place in the link means nothing
             for unit in units + SHAPING_UNITS:       # the newest table last
                 name, src, flags, hashed = unit
                 flags = [f for f in flags if f != "-shared"] + ["-c"]
@@ -417,6 +421,10 @@ def load():
     L.orr_dgrad_relu_bf16.argtypes = _abi.DGRAD_RELU_ARGS
     L.orr_dense_forward_bf16.restype = C.c_int32
     L.orr_dense_forward_bf16.argtypes = _abi.DENSE_FORWARD_ARGS
+    L.orr_gru_forward.restype = C.c_int32
+    L.orr_gru_forward.argtypes = _abi.GRU_FORWARD_ARGS
+    L.orr_gru_backward.restype = C.c_int32
+    L.orr_gru_backward.argtypes = _abi.GRU_BACKWARD_ARGS
     L.orr_learner_partial_rows.restype = C.c_int32
     L.orr_learner_partial_rows.argtypes = [C.c_int32]
     L.orr_colsum_finish.restype = C.c_int32

@@ -5,7 +5,7 @@ import math
 import numpy as np
 
 from . import policy as pol
-from .history import ENC_HIDDEN, HISTORY_DIM, HISTORY_STEPS
+from .history import ENC_HIDDEN, GRU_HIDDEN, HISTORY_DIM, HISTORY_FRAME, HISTORY_STEPS, encode_seq, gru_step, history_frame
 from .obs_norm import RunningNorm, _norm_state
 
 _LINEAR = {}
@@ -65,6 +65,12 @@ class ActorCritic(object):
     `params` the presence of model/enc_fc0/w:0 decides.  act(obs, hist=hist, critic_priv=priv) is the asymmetric form PPOHistory trains: the
     actor on the estimate, the value from the true row.
 
+    recurrent = 256 (with actor_priv_dim = 48 only, and instead of history) adds a GRU over the per-step sensor frame, model/gru_x [32, 768],
+    model/gru_h [256, 768] (gate order r | u | c) and model/gru_out [256, 48]: a recurrent student, whose hidden state lives as long as the
+    episode.  encode_seq(obs, starts, h0) is the recurrence over a segment (history.encode_seq); mean() and act() take `hidden` [N, 256] and
+    `start` [N] in the row's place and return the new state behind what they return without.  Drawn after every other parameter, so
+    recurrent = 0 is the model without, draw for draw; with `params` the presence of model/gru_x/w:0 decides.  obs_norm is refused with it.
+
     learn_std = True adds model/pi/logstd:0 [1, 12], filled with log(std): a state-independent log-std that PPO / learner_hip.FusedPPO train
     (with an entropy bonus, ent_coef).  act() then samples mean + exp(log_std) * noise and log_prob() is the per-dimension Gaussian's.  It is
     filled, not drawn: every other parameter is what it is without, draw for draw.  With `params` the presence of the key decides.  `log_std`
@@ -78,7 +84,7 @@ class ActorCritic(object):
     policy with obs_norm is refused."""
 
     def __init__(self, device, obs_dim=160, act_dim=12, hidden=(512, 256), std=pol.PI_STD, params=None, seed=0, priv_dim=0, actor_priv_dim=0,
-                 history=0, learn_std=False, obs_norm=False):
+                 history=0, learn_std=False, obs_norm=False, recurrent=0):
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -102,6 +108,15 @@ class ActorCritic(object):
         if history and not self.actor_priv_dim:
             raise ValueError("a history encoder (history = %d) feeds a privileged actor (actor_priv_dim = %d)" % (HISTORY_STEPS, pol.PRIV_DIM))
         self.history = int(history)
+        if params is not None:
+            recurrent = GRU_HIDDEN if "model/gru_x/w:0" in params else 0
+        if recurrent not in (0, GRU_HIDDEN):
+            raise ValueError("recurrent must be 0 or %d, got %r" % (GRU_HIDDEN, recurrent))
+        if recurrent and self.history:
+            raise ValueError("recurrent and history are two estimators of the same row: give one")
+        if recurrent and not self.actor_priv_dim:
+            raise ValueError("a recurrent encoder (recurrent = %d) feeds a privileged actor (actor_priv_dim = %d)" % (GRU_HIDDEN, pol.PRIV_DIM))
+        self.recurrent = int(recurrent)
         g = torch.Generator().manual_seed(seed)
         self.p = {}
         dims = [obs_dim] + list(hidden)
@@ -113,6 +128,10 @@ class ActorCritic(object):
         if self.history:           # after every other draw
             self._init("model/enc_fc0", HISTORY_DIM, ENC_HIDDEN, g, math.sqrt(2.0))
             self._init("model/enc_fc1", ENC_HIDDEN, pol.PRIV_DIM, g, 1.0)
+        if self.recurrent:         # after every other draw
+            self._init("model/gru_x", HISTORY_FRAME, 3 * GRU_HIDDEN, g, 1.0)
+            self._init("model/gru_h", GRU_HIDDEN, 3 * GRU_HIDDEN, g, 1.0)
+            self._init("model/gru_out", GRU_HIDDEN, pol.PRIV_DIM, g, 1.0)
         if params is not None:
             learn_std = LOGSTD in params
         self.learn_std = bool(learn_std)
@@ -127,7 +146,7 @@ class ActorCritic(object):
             obs_norm = obs_state is not None
         self.obs_norm = self.priv_norm = None
         if obs_norm:
-            if self.history:
+            if self.history or self.recurrent:
                 raise ValueError("obs_norm with a history policy is not built: the encoder's frames are a subset of the observation and would "
                                  "need the same statistics; train the history policy on raw observations")
             self.obs_norm = RunningNorm(self.device, obs_dim)
@@ -244,6 +263,24 @@ class ActorCritic(object):
         h = _linear(t, True)(hist, self.p["model/enc_fc0/w:0"], self.p["model/enc_fc0/b:0"])
         return _linear(t, False)(h, self.p["model/enc_fc1/w:0"], self.p["model/enc_fc1/b:0"])
 
+    def encode_seq(self, obs, starts, h0):
+        """obs [T, N, 160], starts [T, N], h0 [N, 256] -> (hid [T, N, 256], z [T, N, 48]): the recurrent student's estimate over a segment."""
+        if not self.recurrent:
+            raise ValueError("this model has no recurrent encoder (recurrent = 0)")
+        return encode_seq(self.p, obs, starts, h0)
+
+    def encode_step(self, obs, hidden, start):
+        """One step of encode_seq: obs [N, 160], hidden [N, 256] (None: zeros), start [N] (None: everybody starts) -> (new hidden, z [N, 48])."""
+        if not self.recurrent:
+            raise ValueError("this model has no recurrent encoder (recurrent = 0)")
+        t = self.torch
+        if hidden is None:
+            hidden = obs.new_zeros(obs.shape[0], GRU_HIDDEN)
+        if start is None:
+            start = t.ones(obs.shape[0], dtype=t.bool, device=obs.device)
+        h = gru_step(self.p, history_frame(obs), start, hidden)
+        return h, h @ self.p["model/gru_out/w:0"] + self.p["model/gru_out/b:0"]
+
     def _latent(self, priv, hist):
         """The row the actor and the critic read: `priv` itself, or the encoder's estimate from `hist` (one of the two)."""
         if hist is None:
@@ -252,7 +289,11 @@ class ActorCritic(object):
             raise ValueError("give priv or hist, not both")
         return self.encode(hist)
 
-    def mean(self, obs, priv=None, hist=None):
+    def mean(self, obs, priv=None, hist=None, hidden=None, start=None):
+        """The actor's mean; of a recurrent student (hidden [N, 256] | None, start [N] | None in priv's place): (mean, the new hidden state)."""
+        if self.recurrent and priv is None:
+            h, z = self.encode_step(obs, hidden, start)
+            return self._mlp("pi", self._actor_input(obs, z)), h
         return self._mlp("pi", self._actor_input(obs, self._latent(priv, hist)))
 
     def _critic_input(self, obs, priv):
@@ -265,13 +306,22 @@ class ActorCritic(object):
         return self._mlp("vf", self._critic_input(obs, priv))[:, 0]
 
     def act(self, obs, priv=None, deterministic=False, generator=None, noise=None, out_raw=None, out_value=None, hist=None, out_latent=None,
-            critic_priv=None):
+            critic_priv=None, hidden=None, start=None, out_hidden=None):
         """-> (clipped action, raw action, value).  `noise` ([N,12] standard normal) overrides the generator; `priv` ([N,48], the
         privileged observation) goes to a privileged critic, and to a privileged actor.  `hist` ([N,512], a history student's input)
         takes its place: actor and critic read the encoder's estimate, which out_latent [N,48] receives.  `critic_priv` ([N,48], with
         `hist` only) makes the critic asymmetric: the actor still reads the estimate, the value comes from the true row -
-        mean(obs, hist=hist) and value(obs, critic_priv), what PPOHistory trains."""
+        mean(obs, hist=hist) and value(obs, critic_priv), what PPOHistory trains.
+        A recurrent student takes `hidden` ([N,256], the state before; None: zeros) and `start` ([N] bool / uint8, the done flags of the step
+        that produced obs; None: everybody starts) instead, and returns (clipped action, raw action, value, new hidden state): actor and
+        critic read the GRU's estimate, which out_latent receives; out_hidden [N,256] receives the new state (it may be `hidden`)."""
         t = self.torch
+        if self.recurrent:
+            if priv is not None or hist is not None or critic_priv is not None:
+                raise ValueError("a recurrent student reads hidden and start, not priv / hist / critic_priv")
+            return self._act_recurrent(obs, hidden, start, deterministic, generator, noise, out_raw, out_value, out_latent, out_hidden)
+        if hidden is not None or start is not None or out_hidden is not None:
+            raise ValueError("hidden, start and out_hidden are for a recurrent student (recurrent = %d)" % GRU_HIDDEN)
         if critic_priv is not None:
             if hist is None:
                 raise ValueError("critic_priv goes with hist: the actor reads the encoder's estimate, the critic the true row")
@@ -309,6 +359,29 @@ class ActorCritic(object):
                 noise = t.randn(mu.shape, device=mu.device, generator=generator)
             a = mu if deterministic else mu + (self.p[LOGSTD].exp() if self.learn_std else self.std) * noise
             return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, priv if critic_priv is None else critic_priv)
+
+    def _act_recurrent(self, obs, hidden, start, deterministic, generator, noise, out_raw, out_value, out_latent, out_hidden):
+        t = self.torch
+        if self.fused is not None:
+            if self._fused_dirty:
+                self.fused.refresh()
+                self._fused_dirty = False
+            if noise is None and not deterministic:
+                noise = t.randn((obs.shape[0], 12), device=obs.device, generator=generator)
+            a, raw, v, _, h = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value, hidden=hidden, start=start,
+                                                 out_hidden=out_hidden, out_latent=out_latent)
+            return a, raw, v, h
+        with t.no_grad():
+            h, z = self.encode_step(obs, hidden, start)
+            if out_hidden is not None:
+                h = out_hidden.copy_(h)
+            if out_latent is not None:
+                out_latent.copy_(z)
+            mu = self._mlp("pi", self._actor_input(obs, z))
+            if noise is None and not deterministic:
+                noise = t.randn(mu.shape, device=mu.device, generator=generator)
+            a = mu if deterministic else mu + (self.p[LOGSTD].exp() if self.learn_std else self.std) * noise
+            return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, z), h
 
     def log_prob(self, obs, actions, priv=None, hist=None):
         mu = self.mean(obs, priv, hist)

@@ -1,9 +1,10 @@
-"""The four learners whose non-GEMM part is hand-written HIP and whose whole epoch replays as one hipGraph
+"""The five learners whose non-GEMM part is hand-written HIP and whose whole epoch replays as one hipGraph
 (include/openroborl_learner.h, csrc/orr_learner.hip):
   FusedPPO             the PPO update of both nets (the torch reference is ppo.PPO: agents/ppo_imitation.py:156-258 + Adam);
   FusedPPOHistory      that update on a history policy: the actor on obs | encode(hist), the critic on the true privileged row (ppo.PPOHistory);
   FusedDistill         a student's actor regressed on a teacher's means (ppo.Distill);
-  FusedDistillHistory  a history student's encoder regressed on the privileged rows, optionally through the frozen actor (ppo.DistillHistory).
+  FusedDistillHistory  a history student's encoder regressed on the privileged rows, optionally through the frozen actor (ppo.DistillHistory);
+  FusedDistillRecurrent  a recurrent student's GRU regressed on them through the segment's T steps, in kernels of its own (ppo.DistillRecurrent).
 Same arithmetic as their references (which stay the fp32 yardsticks the tests compare these against), different execution.  What they
 share stands once, in _FusedLearner:
   * the trained parameters, their gradients and Adam moments live in ONE flat buffer each (the model's tensors become views of it): the
@@ -425,6 +426,8 @@ class FusedPPO(_FusedLearner):
         if getattr(model, "history", 0) and not self._history:
             raise ValueError("FusedPPO: a history policy is trained by FusedPPOHistory (PPO with the critic on the true privileged row) or by "
                              "FusedDistillHistory")
+        if getattr(model, "recurrent", 0):
+            raise ValueError("%s: PPO on a recurrent policy is not built; its GRU is trained by FusedDistillRecurrent" % type(self).__name__)
         self.learn_std, self.ent_coef, self.log_std_bounds = _entropy_args(model, type(self).__name__, ent_coef, log_std_bounds or LOG_STD_BOUNDS)
         self.clip, self.vf_coef = float(clip_param), float(vf_coef)
         self.group = group
@@ -909,3 +912,106 @@ class FusedDistillHistory(_FusedLearner):
             return self.action_coef * total[0] + self.latent_coef * total[1]
         self.last_action_loss, self.last_latent_loss = 0.0, total[0]
         return total[0]
+
+
+class FusedDistillRecurrent(_FusedLearner):
+    """The learner of a recurrent student's GRU on the device (the torch reference is ppo.DistillRecurrent): the estimate z_t = h_t Wo + bo over
+    a rollout segment is regressed on the recorded privileged rows, loss = mean over the T * robots samples of sum_j (z_j - priv_j)^2, with the
+    gradient carried back through the segment's T steps (truncated BPTT: h0 is data).  Only model/gru_* move into the flat buffer and take Adam
+    steps; the actor and the critic - the teacher's - stay where and what they are.  A minibatch is a set of WHOLE robots, minibatch // T of
+    them: the permutation is over robots, and their T steps are gathered once into contiguous [T][m] buffers.  Per minibatch: the re-pack of
+    the three matrices and of the two transposes the backward pass streams (the weights move every step), orr_gru_forward over the T steps,
+    orr_regress_head (T m samples of 48 columns: the loss, d loss / d z and gru_out's bias gradient), orr_gru_backward, three orr_wgrad
+    (frames^T g_x, hprev^T g_h, hid^T g_z) and one orr_colsum_finish (the two bias gradients and the three weight gradients); an epoch replays
+    as one hipGraph.  f32 only, one rank, the latent loss only: action_coef > 0, bf16_gemm and a process group are refused."""
+
+    def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, action_coef=0.0, max_grad_norm=None,
+                 device_lr=False, bf16_gemm=False, group=None):
+        _no_obs_norm(student, "FusedDistillRecurrent")
+        self._need_gpu(student)
+        if not getattr(student, "recurrent", 0):
+            raise ValueError("FusedDistillRecurrent: the student needs a recurrent encoder (ActorCritic(recurrent=256))")
+        if float(action_coef) != 0.0:
+            raise ValueError("FusedDistillRecurrent: the action loss is not built for a recurrent student (action_coef must be 0)")
+        if bf16_gemm:
+            raise ValueError("FusedDistillRecurrent: the GRU kernels are f32 only (bf16_gemm must be False)")
+        if group is not None:
+            raise ValueError("FusedDistillRecurrent: one rank only (no gradient all-reduce is built for it)")
+        self.minibatch_samples, self.T = int(minibatch), None
+        self.last_latent_loss, self.last_action_loss = None, 0.0
+        _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/gru_")), 1, lr, adam_eps, minibatch, betas, use_graph,
+                               max_grad_norm=max_grad_norm, device_lr=device_lr)
+        from . import policy_hip
+        self.gru = policy_hip.GruEncoder(self.w, self.dev)       # the forward images, of the flat buffer's views
+        self.encT = _abi.OrrGruTransposed()
+
+    def _buffers(self, P, f, split, rows):
+        t, L, g = self.torch, self.L, self.g
+        N, m, T = P["B"], P["M"], self.T
+        H, G, Z, F = _abi.GRU_HIDDEN, _abi.GRU_GATES, _abi.POLICY_PRIV_DIM, _abi.HISTORY_FRAME
+        u8 = lambda *shape: t.zeros(shape, dtype=t.uint8, device=self.dev)   # noqa: E731
+        brows = _abi.gru_backward_rows(m)
+        P.update({"obs": f(T, N, 160), "starts": u8(T, N), "h0": f(N, H), "target": f(T, N, Z),
+                  "xo": f(T, m, 160), "st": u8(T, m), "xh0": f(m, H), "tgt": f(T, m, Z),
+                  "hid": f(T, m, H), "z": f(T, m, Z), "frames": f(T, m, F), "hprev": f(T, m, H), "saved": f(T, m, 4, H),
+                  "g_z": f(T, m, Z), "g_x": f(T, m, G), "g_h": f(T, m, G), "gp": f(2 * G * brows),
+                  "ws": f(int(L.orr_learner_workspace_floats(T * m, 64))),
+                  "whT": f(G, H), "woT": f(Z, H), "wht": f(int(L.orr_policy_packed_size(G, H))), "wot": f(int(L.orr_policy_packed_size(Z, H)))})
+        jobs = [(P["gp"], g["model/gru_x/b:0"], brows, G), (P["gp"][G * brows:], g["model/gru_h/b:0"], brows, G)]
+        # the three weight gradients: orr_wgrad's batch slices, one job each; a shape it refuses goes to the library (_wgrad) instead
+        P["wg"] = []
+        for x, gy, key in (("frames", "g_x", "model/gru_x/w:0"), ("hprev", "g_h", "model/gru_h/w:0"), ("hid", "g_z", "model/gru_out/w:0")):
+            k, n = int(P[x].shape[-1]), int(P[gy].shape[-1])
+            s = int(L.orr_wgrad_slices(T * m, k, n))
+            part = f(s, k, n) if s > 0 else None
+            P["wg"].append((P[x].view(T * m, k), P[gy].view(T * m, n), part, g[key]))
+            if part is not None:
+                jobs.append((part, g[key], s, k * n))
+        P["jobs"], P["n_jobs"] = _jobs(jobs)
+
+    def _minibatch(self, P, s):
+        """Gather of the minibatch's robots, re-pack, forward over the T steps, loss head, backward through time, weight gradients."""
+        t, L, w, g = self.torch, self.L, self.w, self.g
+        m, T = P["M"], self.T
+        st = self._stream()
+        idx = P["perm"][s * m:(s + 1) * m]
+        for src, dst, dim in (("obs", "xo", 1), ("starts", "st", 1), ("target", "tgt", 1), ("h0", "xh0", 0)):
+            t.index_select(P[src], dim, idx, out=P[dst])
+        self.gru.refresh()
+        P["whT"].copy_(w["model/gru_h/w:0"].t())
+        P["woT"].copy_(w["model/gru_out/w:0"].t())
+        _lib.check(L.orr_policy_pack(P["whT"].data_ptr(), _abi.GRU_GATES, _abi.GRU_HIDDEN, P["wht"].data_ptr(), st), L)
+        _lib.check(L.orr_policy_pack(P["woT"].data_ptr(), _abi.POLICY_PRIV_DIM, _abi.GRU_HIDDEN, P["wot"].data_ptr(), st), L)
+        self.encT.wht, self.encT.wot = P["wht"].data_ptr(), P["wot"].data_ptr()
+        self.gru.forward(P["xo"], P["st"], P["xh0"], hid=P["hid"], latent=P["z"], frames=P["frames"], hprev=P["hprev"], saved=P["saved"])
+        _lib.check(L.orr_regress_head(P["z"].data_ptr(), P["tgt"].data_ptr(), T * m, _abi.POLICY_PRIV_DIM, P["g_z"].data_ptr(),
+                                      g["model/gru_out/b:0"].data_ptr(), P["stats"][s].data_ptr(), P["ws"].data_ptr(), st), L)
+        _lib.check(L.orr_gru_backward(C.byref(self.encT), P["g_z"].data_ptr(), P["saved"].data_ptr(), P["hprev"].data_ptr(), P["st"].data_ptr(), T, m,
+                                      P["g_x"].data_ptr(), P["g_h"].data_ptr(), P["gp"].data_ptr(), st), L)
+        for x, gy, part, out in P["wg"]:
+            if part is not None:
+                _lib.check(L.orr_wgrad(x.data_ptr(), x.shape[1], gy.data_ptr(), gy.shape[1], x.shape[0], part.data_ptr(), st), L)
+            else:
+                self._wgrad(x, gy, None, out)
+        _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)
+
+    def update(self, obs, starts, h0, target_priv, epochs=1, generator=None):
+        """obs [T,N,160], starts [T,N] (bool / uint8), h0 [N,256] (the rollout's "hidden"), target_priv [T,N,48] (env.privileged_obs on the same
+        states).  Returns the mean loss over the minibatches, like ppo.DistillRecurrent.update."""
+        t = self.torch
+        T, N = int(obs.shape[0]), int(obs.shape[1])
+        if (tuple(obs.shape) != (T, N, 160) or tuple(starts.shape) != (T, N) or tuple(h0.shape) != (N, _abi.GRU_HIDDEN)
+                or tuple(target_priv.shape) != (T, N, _abi.POLICY_PRIV_DIM)):
+            raise ValueError("FusedDistillRecurrent: obs [T,N,160], starts [T,N], h0 [N,%d] and target_priv [T,N,%d]" % (_abi.GRU_HIDDEN, _abi.POLICY_PRIV_DIM))
+        if T != self.T:                   # the plans' buffers are [T][.]: another segment length, other plans
+            self.T, self._plans = T, {}
+        self.minibatch = max(1, self.minibatch_samples // T)      # robots per minibatch
+
+        def fill(P):
+            P["obs"].copy_(obs)
+            P["starts"].copy_(starts.view(t.uint8) if starts.dtype == t.bool else starts)
+            P["h0"].copy_(h0)
+            P["target"].copy_(target_priv)
+        total, n = self._run(N, fill, epochs, generator)
+        self.last_latent_loss = float(total.item() / n)
+        return self.last_latent_loss

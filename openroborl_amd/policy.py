@@ -59,6 +59,10 @@ SB_PARAMETER_LIST = (("model/pi_fc0/w:0", (160, 512)), ("model/pi_fc0/b:0", (512
 ENC_PARAMETER_LIST = (("model/enc_fc0/w:0", (512, 256)), ("model/enc_fc0/b:0", (256,)), ("model/enc_fc1/w:0", (256, PRIV_DIM)),
                       ("model/enc_fc1/b:0", (PRIV_DIM,)))
 
+# a recurrent student's GRU and its output layer (ppo.ActorCritic(recurrent=256)), gate order r | u | c; no reference counterpart
+GRU_PARAMETER_LIST = (("model/gru_x/w:0", (32, 768)), ("model/gru_x/b:0", (768,)), ("model/gru_h/w:0", (256, 768)), ("model/gru_h/b:0", (768,)),
+                      ("model/gru_out/w:0", (256, PRIV_DIM)), ("model/gru_out/b:0", (PRIV_DIM,)))
+
 
 # the learned log-std of ppo.ActorCritic(learn_std=True).  The reference's graph declares this very variable (pi/logstd, [1, 12], filled with
 # log(pi_init_std): agents/imitation_policies.py:48) but with trainable=False, which keeps it out of the zips it saves and loads
@@ -90,8 +94,9 @@ def save_parameters_zip(path, params, data=None):
             raise ValueError("missing variable %s" % name)
         out[name] = v
     names = [n for n, _ in SB_PARAMETER_LIST]
-    for name, shape in ENC_PARAMETER_LIST:       # a history student (ppo.ActorCritic(history=16)): behind the reference's list, loadable here only
-        if ENC_PARAMETER_LIST[0][0] in params:
+    # a history student (ppo.ActorCritic(history=16)) or a recurrent one (recurrent=256): behind the reference's list, loadable here only
+    for name, shape in ENC_PARAMETER_LIST + GRU_PARAMETER_LIST:
+        if (ENC_PARAMETER_LIST if name.startswith("model/enc_") else GRU_PARAMETER_LIST)[0][0] in params:
             v = np.asarray(params[name], dtype=np.float32)
             if v.shape != shape:
                 raise ValueError("%s has shape %s, a history encoder has %s" % (name, v.shape, shape))

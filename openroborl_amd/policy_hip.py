@@ -16,7 +16,76 @@ KEYS = (("w0_pi", "model/pi_fc0/w:0"), ("b0_pi", "model/pi_fc0/b:0"), ("w1_pi", 
 # a history student's encoder (orr_policy_forward_history), packed when the parameter dict holds it
 ENC_KEYS = (("w0", "model/enc_fc0/w:0"), ("b0", "model/enc_fc0/b:0"), ("w1", "model/enc_fc1/w:0"), ("b1", "model/enc_fc1/b:0"))
 ENC_SHAPES = {"w0": (_abi.HISTORY_DIM, 256), "w1": (256, _abi.POLICY_PRIV_DIM)}
+# a recurrent student's GRU and its output layer (orr_gru_forward), packed when the parameter dict holds them
+GRU_KEYS = (("wx", "model/gru_x/w:0"), ("bx", "model/gru_x/b:0"), ("wh", "model/gru_h/w:0"), ("bh", "model/gru_h/b:0"),
+            ("wo", "model/gru_out/w:0"), ("bo", "model/gru_out/b:0"))
+GRU_SHAPES = {"wx": (_abi.HISTORY_FRAME, _abi.GRU_GATES), "wh": (_abi.GRU_HIDDEN, _abi.GRU_GATES), "wo": (_abi.GRU_HIDDEN, _abi.POLICY_PRIV_DIM)}
 SHAPES = {"w0_pi": (160, 512), "w0_vf": (160, 512), "w1_pi": (512, 256), "w1_vf": (512, 256), "w2_pi": (256, 12), "w2_vf": (256, 1)}
+
+
+def _checked(x, dtype, shape, device, name):
+    if x is not None and (x.dtype != dtype or not x.is_contiguous() or tuple(x.shape) != shape or x.device != device):
+        raise ValueError("%s must be a contiguous %s %s tensor on %s" % (name, dtype, shape, device))
+    return x
+
+
+class GruEncoder(object):
+    """The packed copy of a recurrent student's GRU (model/gru_x, model/gru_h, model/gru_out of a parameter dict) at fixed addresses, and
+    orr_gru_forward on it.  refresh() packs the three matrices and copies the three biases (six small launches), e.g. inside a captured
+    rollout segment or learner epoch."""
+
+    def __init__(self, params, device):
+        import torch
+        self.torch, self.params, self.device = torch, params, device
+        self.L = _lib.load()
+        self.enc = _abi.OrrGruEncoder()
+        self.buf = {}
+        for field, key in GRU_KEYS:
+            w = params[key]
+            if field in GRU_SHAPES:
+                if tuple(w.shape) != GRU_SHAPES[field]:
+                    raise ValueError("%s has shape %s, the GRU kernel is built for %s" % (key, tuple(w.shape), GRU_SHAPES[field]))
+                self.buf[field] = torch.empty(int(self.L.orr_policy_packed_size(*GRU_SHAPES[field])), dtype=torch.float32, device=device)
+            else:
+                self.buf[field] = torch.empty(w.numel(), dtype=torch.float32, device=device)
+            setattr(self.enc, field, self.buf[field].data_ptr())
+        self.refresh()
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def refresh(self):
+        t = self.torch
+        for field, key in GRU_KEYS:
+            w = self.params[key].detach()
+            if w.dtype != t.float32 or not w.is_contiguous() or w.device != self.device:
+                w = w.to(device=self.device, dtype=t.float32).contiguous()
+            if field in GRU_SHAPES:
+                _lib.check(self.L.orr_policy_pack(w.data_ptr(), int(w.shape[0]), int(w.shape[1]), self.buf[field].data_ptr(), self._stream()), self.L)
+            else:
+                self.buf[field].copy_(w.reshape(-1))
+
+    def forward(self, obs, starts=None, h0=None, hid=None, latent=None, frames=None, hprev=None, saved=None):
+        """orr_gru_forward: obs [T,n,160], starts [T,n] uint8 / bool (None: everybody starts, T = 1 only), h0 [n,256] (None: zeros) -> hid
+        [T,n,256], allocated unless given (with T = 1 it may be h0's storage).  latent [T,n,48], frames [T,n,32], hprev [T,n,256] and saved
+        [T,n,4,256] are written when given.  Returns hid."""
+        t = self.torch
+        if obs.dim() != 3:
+            raise ValueError("obs must be [T,n,160]")
+        T, n = int(obs.shape[0]), int(obs.shape[1])
+        H, f32 = _abi.GRU_HIDDEN, t.float32
+        if starts is not None and starts.dtype == t.bool:
+            starts = starts.view(t.uint8)
+        if hid is None:
+            hid = t.empty((T, n, H), dtype=f32, device=self.device)
+        for x, dtype, shape, name in ((obs, f32, (T, n, 160), "obs"), (starts, t.uint8, (T, n), "starts"), (h0, f32, (n, H), "h0"), (hid, f32, (T, n, H), "hid"),
+                                      (latent, f32, (T, n, _abi.POLICY_PRIV_DIM), "latent"), (frames, f32, (T, n, _abi.HISTORY_FRAME), "frames"),
+                                      (hprev, f32, (T, n, H), "hprev"), (saved, f32, (T, n, 4, H), "saved")):
+            _checked(x, dtype, shape, self.device, name)
+        ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+        _lib.check(self.L.orr_gru_forward(C.byref(self.enc), obs.data_ptr(), ptr(starts), ptr(h0), T, n, hid.data_ptr(), ptr(latent), ptr(frames),
+                                          ptr(hprev), ptr(saved), self._stream()), self.L)
+        return hid
 
 
 class FusedActorCritic(object):
@@ -70,6 +139,15 @@ class FusedActorCritic(object):
                     if tuple(params[key].shape) != ENC_SHAPES[field]:
                         raise ValueError("%s has shape %s, the fused kernel is built for %s" % (key, tuple(params[key].shape), ENC_SHAPES[field]))
                     self.packed["enc_" + field] = torch.empty(int(self.L.orr_policy_packed_size(*ENC_SHAPES[field])), dtype=torch.float32, device=self.device)
+        self.recurrent = 0            # 256 when the dict holds model/gru_x/w:0 (a recurrent student): forward() takes hidden / start in priv's place
+        self.gru = None
+        if GRU_KEYS[0][1] in params:
+            if not self.actor_priv_dim or self.history:
+                raise ValueError("a recurrent encoder (model/gru_x/w:0) feeds a privileged actor (model/pi_fc0/w:0 with %d rows) and goes "
+                                 "without a history encoder" % (160 + _abi.POLICY_PRIV_DIM))
+            self.recurrent = _abi.GRU_HIDDEN
+            self.gru = GruEncoder(params, self.device)
+            self._latent = {}         # n -> the static [n, 48] estimate the teacher kernel reads
         self.log_std = None           # the sampler's copy of model/pi/logstd:0, [12]
         self._scaled = {}             # n -> the static [n, 12] buffer of exp(log_std) * noise
         if LOGSTD in params:
@@ -82,7 +160,7 @@ class FusedActorCritic(object):
         self.obs_norm, self.priv_norm = obs_norm, priv_norm
         self._norm_tab = None
         if obs_norm is not None:
-            if self.history:
+            if self.history or self.recurrent:
                 raise ValueError("an observation normaliser with a history encoder is not built")
             def here(norm):     # the record's device against this object's, both resolved (a tensor on "cuda" reports cuda:<current>)
                 d = norm.rec.device
@@ -104,6 +182,8 @@ class FusedActorCritic(object):
         """Re-pack the weights (six small launches, eight with an encoder) and re-read the biases from the parameter tensors.  With an
         observation normaliser the two layer-0 matrices go through orr_policy_pack_norm, which also writes their folded biases."""
         t = self.torch
+        if self.gru is not None:
+            self.gru.refresh()
         if self.log_std is not None:
             self.log_std.copy_(self.params[LOGSTD].detach().reshape(12))
         if self._norm_tab is not None:         # the table of a 208-row layer 0: the observation's statistics, then the row's (or 0, 1 as built)
@@ -160,7 +240,7 @@ class FusedActorCritic(object):
         return scaled
 
     def forward(self, obs, noise=None, want_mean=False, out_action=None, out_raw=None, out_value=None, priv=None, out_mean=None, want_value=True,
-                hist=None, out_latent=None, scaled=False, critic_priv=None):
+                hist=None, out_latent=None, scaled=False, critic_priv=None, hidden=None, start=None, out_hidden=None):
         """obs [N,160] float32 on the device; noise [N,12] standard normal or None (deterministic); priv [N,48] float32, the
         privileged observation, for a privileged critic (and only then).
         Returns (clipped action [N,12], raw action [N,12], value [N], mean [N,12] or None); the out_* tensors
@@ -170,8 +250,29 @@ class FusedActorCritic(object):
         critic (orr_policy_forward_history) and is written to out_latent [N,48] when that is given.
         critic_priv [N,48] float32, with hist only: the critic reads obs | critic_priv, the TRUE row, while the actor reads the estimate
         (orr_policy_forward_history_priv: the actor's outputs are orr_policy_forward_history's, the value orr_policy_forward_teacher's).
-        scaled=True, for a policy with a learned log-std: `noise` already is exp(log_std) * noise (prepare(), e.g. once for a whole segment)."""
+        scaled=True, for a policy with a learned log-std: `noise` already is exp(log_std) * noise (prepare(), e.g. once for a whole segment).
+        A recurrent student (model/gru_x/w:0) takes hidden [N,256] (the state before; None: zeros) and start [N] uint8 / bool (None: everybody
+        starts) instead of priv: orr_gru_forward (T = 1) writes the new state to out_hidden [N,256] (allocated unless given; it may be `hidden`)
+        and the estimate of the row to out_latent, then orr_policy_forward_teacher reads the estimate as priv.  Two launches; the return
+        value is then (action, raw, value, mean, new hidden)."""
         t = self.torch
+        if self.recurrent:
+            if priv is not None or hist is not None or critic_priv is not None:
+                raise ValueError("a recurrent student reads hidden and start, not priv / hist / critic_priv")
+            n = obs.shape[0]
+            if out_latent is None:
+                if n not in self._latent:
+                    self._latent[n] = t.empty((n, _abi.POLICY_PRIV_DIM), dtype=t.float32, device=self.device)
+                out_latent = self._latent[n]
+            _checked(obs, t.float32, (n, 160), self.device, "obs")
+            _checked(out_latent, t.float32, (n, _abi.POLICY_PRIV_DIM), self.device, "out_latent")
+            _checked(out_hidden, t.float32, (n, _abi.GRU_HIDDEN), self.device, "out_hidden")
+            new = self.gru.forward(obs.view(1, n, 160), None if start is None else start.view(1, n), hidden,
+                                   hid=None if out_hidden is None else out_hidden.view(1, n, _abi.GRU_HIDDEN),
+                                   latent=out_latent.view(1, n, _abi.POLICY_PRIV_DIM))[0]
+            priv = out_latent
+        elif hidden is not None or start is not None or out_hidden is not None:
+            raise ValueError("hidden, start and out_hidden are for a recurrent student (model/gru_x/w:0)")
         if obs.dtype != t.float32 or not obs.is_contiguous() or obs.device != self.device or obs.dim() != 2 or obs.shape[1] != 160:
             raise ValueError("obs must be a contiguous float32 [N,160] tensor on %s" % (self.device,))
         n = obs.shape[0]
@@ -187,7 +288,7 @@ class FusedActorCritic(object):
                 raise ValueError("critic_priv must be a contiguous float32 [N,%d] tensor on the same device" % _abi.POLICY_PRIV_DIM)
         elif critic_priv is not None:
             raise ValueError("critic_priv goes with hist: the actor reads the encoder's estimate, the critic the true row")
-        elif out_latent is not None:
+        elif out_latent is not None and not self.recurrent:
             raise ValueError("out_latent belongs to hist")
         elif (priv is not None) != (self.priv_dim > 0):
             raise ValueError("priv is needed by a privileged critic (model/vf_fc0/w:0 with %d rows) and by no other" % (160 + _abi.POLICY_PRIV_DIM))
@@ -237,7 +338,7 @@ class FusedActorCritic(object):
                                                          noise.data_ptr() if noise is not None else None, std, self.clip, act.data_ptr(),
                                                          raw.data_ptr(), val.data_ptr() if val is not None else None,
                                                          mean.data_ptr() if mean is not None else None, self._stream()), self.L)
-            return act, raw, val, mean
+            return (act, raw, val, mean, new) if self.recurrent else (act, raw, val, mean)
         if priv is not None:
             _lib.check(self.L.orr_policy_forward_priv(C.byref(self.net), obs.data_ptr(), priv.data_ptr(), int(n),
                                                       noise.data_ptr() if noise is not None else None, std, self.clip, act.data_ptr(),

@@ -17,7 +17,7 @@ import math
 
 from . import policy as pol
 from .actor_critic import ENTROPY_CONST, LOG_STD_BOUNDS, LOGSTD, STAT_NAMES, ActorCritic, _linear, _wgrad  # noqa: F401
-from .history import ENC_HIDDEN, HISTORY_DIM, HISTORY_FRAME, HISTORY_STEPS, history_frame, history_push  # noqa: F401
+from .history import ENC_HIDDEN, GRU_HIDDEN, HISTORY_DIM, HISTORY_FRAME, HISTORY_STEPS, encode_seq, gru_step, history_frame, history_push  # noqa: F401
 from .obs_norm import NORM_EPS, NORM_KEYS, RunningNorm, _norm_state  # noqa: F401
 from .update_control import KL_LR_BOUNDS, _control_args, _entropy_args, _no_history, _no_obs_norm, _UpdateControl  # noqa: F401
 
@@ -286,3 +286,45 @@ class DistillHistory(_UpdateControl):
         self.last_latent_loss = float(t.stack(lat).mean())
         self.last_action_loss = float(t.stack(act).mean()) if act else 0.0
         return float(t.stack(stats).mean())
+
+
+class DistillRecurrent(_UpdateControl):
+    """The learner of a recurrent student's GRU in plain torch (the fp32 reference of learner_hip.FusedDistillRecurrent): encode_seq over a
+    rollout segment is regressed on the recorded privileged rows, loss = mean over the T * robots samples of sum_j (z_j - priv_j)^2, by
+    autograd through the segment's T steps (truncated BPTT: h0 is data).  Only model/gru_* train; the actor and the critic - the teacher's -
+    are not touched.  A minibatch is a set of whole robots, minibatch // T of them, with all their T steps."""
+
+    def __init__(self, student, lr=1e-4, adam_eps=1e-5, minibatch=4096, max_grad_norm=None):
+        import torch
+        self.torch = torch
+        if not getattr(student, "recurrent", 0):
+            raise ValueError("DistillRecurrent: the student needs a recurrent encoder (ActorCritic(recurrent=256))")
+        self.model = student
+        self.minibatch = int(minibatch)
+        self.last_latent_loss, self.last_action_loss = None, 0.0
+        self.params = [student.p[k] for k in sorted(student.p) if k.startswith("model/gru_")]
+        self.opt = torch.optim.Adam(self.params, lr=lr, eps=adam_eps, fused=bool(self.params[0].is_cuda))
+        self._control_init(max_grad_norm)            # max_grad_norm and set_lr_mult(): _UpdateControl
+
+    def update(self, obs, starts, h0, target_priv, epochs=1, generator=None):
+        """obs [T,N,160], starts [T,N], h0 [N,256] (the rollout's "hidden"), target_priv [T,N,48]; returns the mean loss over the minibatches."""
+        t = self.torch
+        T, N = int(obs.shape[0]), int(obs.shape[1])
+        m = max(1, min(self.minibatch // T, N))
+        if N % m:
+            raise ValueError("DistillRecurrent: the number of robots (%d) must be a multiple of the robots per minibatch (%d = minibatch // T)" % (N, m))
+        stats = []
+        for _ in range(epochs):
+            perm = t.randperm(N, device=obs.device, generator=generator)
+            for s in range(0, N, m):
+                idx = perm[s:s + m]
+                _, z = self.model.encode_seq(obs[:, idx], starts[:, idx], h0[idx])
+                loss = ((z - target_priv[:, idx]) ** 2).sum(dim=-1).mean()
+                self.opt.zero_grad(set_to_none=True)
+                loss.backward()
+                self._step()
+                if hasattr(self.model, "mark_updated"):
+                    self.model.mark_updated()
+                stats.append(loss.detach())
+        self.last_latent_loss = float(t.stack(stats).mean())
+        return self.last_latent_loss

@@ -14,7 +14,7 @@ resetting when any robot is done, and the GAE recursion uses each robot's own do
 indexes `episode_starts[(step*num_robot+i) + (1+i)]`, ppo_imitation.py:88, which reads a neighbouring
 robot's flag; `legacy_gae_index=True` reproduces exactly that, for comparisons with the reference at num_robot > 1).
 """
-from ._abi import HISTORY_DIM, PRIV_DIM
+from ._abi import GRU_HIDDEN, HISTORY_DIM, PRIV_DIM
 
 
 def _teacher_labels(teacher, obs, priv, out_mean, out_action):
@@ -35,7 +35,7 @@ def _teacher_labels(teacher, obs, priv, out_mean, out_action):
 
 
 def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generator=None, noise=None, priv=None, teacher=None, teacher_mask=None,
-                    hist=None, critic_priv=False):
+                    hist=None, critic_priv=False, hidden=None, start=None):
     """Run `horizon` env steps of all robots.  Returns a dict of [T, N, ...] tensors + the final observation.
     noise: optional [T, N, 12] standard-normal samples for the fused policy (default: drawn from `generator`).
     A policy with a privileged critic (priv_dim > 0) also gets env.privileged_obs() at every step: "priv" [T, N, 48] and "last_priv" are
@@ -50,7 +50,12 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
     (policy_hip.history_push(obs[k + 1], dones[k], hist[k], out=hist[k + 1])).  hist: the one that belongs to `obs` (the previous segment's
     last_hist; None = computed here with done=None).
     critic_priv=True, for a history policy only (PPO on it: ppo.PPOHistory): the critic is asymmetric, step k's forward pass gets hist[k] for
-    the actor and priv[k], the true row, for the value.  False: the estimate feeds both."""
+    the actor and priv[k], the true row, for the value.  False: the estimate feeds both.
+    A recurrent student (policy.recurrent > 0) carries hid [T + 1, N, 256] and starts [T + 1, N]: step k's forward pass reads hid[k] and
+    starts[k] and writes hid[k + 1], and starts[k + 1] = dones[k].  "hidden" (hid[0], the segment's h0), "last_hidden" (hid[T]), "starts"
+    [T, N] and "hid" (hid[1:], the state after every step) are returned next to "priv" and "last_priv" (the GRU's regression targets).
+    hidden, start: the state and the flags that belong to `obs` (the previous segment's last_hidden and last row of dones; None = zeros and
+    everybody starts, right after a reset)."""
     t = env.torch
     n = env.num_robot
     dev = env.device
@@ -62,6 +67,15 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
         raise ValueError("teacher_mask without a teacher")
     if critic_priv and not history:
         raise ValueError("critic_priv is for a history policy (policy.history > 0): every other critic reads what its actor reads or its own priv")
+    recurrent = int(getattr(policy, "recurrent", 0))
+    if (hidden is not None or start is not None) and not recurrent:
+        raise ValueError("hidden and start are for a recurrent student (policy.recurrent > 0)")
+    if recurrent:
+        gbuf, sbuf = t.zeros((horizon + 1, n, GRU_HIDDEN), device=dev), t.ones((horizon + 1, n), dtype=t.uint8, device=dev)
+        if hidden is not None:
+            gbuf[0].copy_(hidden)
+        if start is not None:
+            sbuf[0].copy_(start)
     hbuf = None
     if history:
         from . import policy_hip
@@ -91,14 +105,16 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
         noise = None
     for k in range(horizon):
         row = {"hist": hbuf[k]} if history else ({"priv": pbuf[k]} if priv_dim else {})     # what the policy reads next to obs
+        if recurrent:
+            row = {"hidden": gbuf[k], "start": sbuf[k], "out_hidden": gbuf[k + 1]}
         if critic_priv:
             row["critic_priv"] = pbuf[k]
         if fused:   # one fused launch writes the raw action and the value straight into the buffers
-            clipped, _, _ = policy.act(obs, deterministic=deterministic, noise=None if noise is None else noise[k],
-                                       out_raw=buf["actions"][k], out_value=buf["vpred"][k], **row)
+            clipped = policy.act(obs, deterministic=deterministic, noise=None if noise is None else noise[k],
+                                 out_raw=buf["actions"][k], out_value=buf["vpred"][k], **row)[0]
             buf["obs"][k].copy_(obs)
         else:
-            clipped, raw, v = policy.act(obs, deterministic=deterministic, generator=generator, **row)
+            clipped, raw, v = policy.act(obs, deterministic=deterministic, generator=generator, **row)[:3]
             buf["obs"][k].copy_(obs)
             buf["actions"][k].copy_(raw)
             buf["vpred"][k].copy_(v)
@@ -113,7 +129,11 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
             env.privileged_obs(out=pbuf[k + 1], done=done)
         if hbuf is not None:
             policy_hip.history_push(obs.contiguous(), buf["dones"][k], hbuf[k], hbuf[k + 1])
+        if recurrent:
+            sbuf[k + 1].copy_(buf["dones"][k])
     buf["last_obs"] = obs
+    if recurrent:
+        buf.update({"hidden": gbuf[0], "last_hidden": gbuf[horizon], "starts": sbuf[:horizon].view(t.bool), "hid": gbuf[1:]})
     if hbuf is not None:
         buf["hist"], buf["last_hist"] = hbuf[:horizon], hbuf[horizon]
     if pbuf is not None:
@@ -159,6 +179,11 @@ class GraphRollout(object):
     on the device, from the copy the segment's weight re-pack renews, so the graph is captured once and replayed for good while the learner
     moves it.
 
+    With a recurrent student (policy.recurrent > 0) the segment holds hid [T + 1, N, 256] and starts [T + 1, N], whose rows 1.. ARE the done
+    flags (dones = starts[1:], one buffer): step k's forward pass - orr_gru_forward with T = 1, then the teacher's kernel on its estimate -
+    reads hid[k] and starts[k] and writes hid[k + 1], all inside the captured segment, the GRU's weight re-pack included.  "hidden" (hid[0]),
+    "last_hidden" (hid[T]), "starts" [T, N] and "hid" (hid[1:]) are returned next to "priv" and "last_priv".
+
     The returned tensors are views of the static buffers: they are overwritten by the next collect() (clone what must survive it,
     e.g. the last row of `dones` that the next segment's GAE takes as first_starts)."""
 
@@ -172,6 +197,10 @@ class GraphRollout(object):
         self.obs, self.actions, self.clipped = f(T + 1, n, 160), f(T, n, 12), f(n, 12)
         self.rewards, self.vpred, self.noise, self.logp = f(T, n), f(T, n), f(T, n, 12), f(T, n)
         self.dones = t.zeros((T, n), dtype=t.uint8, device=dev)
+        self.recurrent = int(getattr(policy, "recurrent", 0))
+        if self.recurrent:
+            self.hid, self.starts = t.zeros((T + 1, n, GRU_HIDDEN), device=dev), t.ones((T + 1, n), dtype=t.uint8, device=dev)
+            self.dones = self.starts[1:]
         self.priv_dim = int(getattr(policy, "priv_dim", 0))
         self.priv = f(T + 1, n, self.priv_dim or PRIV_DIM) if (self.priv_dim or teacher is not None) else None
         self.history = int(getattr(policy, "history", 0))
@@ -205,7 +234,10 @@ class GraphRollout(object):
             fused.prepare(self.noise.view(T * n, 12), self.scaled.view(T * n, 12), self.logp.view(T * n))
             noise, more = self.scaled, {"scaled": True}
         for k in range(self.T):
-            if self.critic_priv:
+            if self.recurrent:
+                fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], hidden=self.hid[k],
+                              start=self.starts[k], out_hidden=self.hid[k + 1], **more)
+            elif self.critic_priv:
                 fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], hist=self.hist[k],
                               critic_priv=self.priv[k], **more)
             elif self.history:
@@ -230,15 +262,28 @@ class GraphRollout(object):
         t.sum(self.noise * self.noise, dim=-1, out=self.logp)
         self.logp.mul_(-0.5).sub_(12.0 * math.log(float(self.policy.std) * math.sqrt(2.0 * math.pi)))
 
-    def collect(self, obs, generator=None, noise=None, priv=None, hist=None):
+    def collect(self, obs, generator=None, noise=None, priv=None, hist=None, hidden=None, start=None):
         """priv: the privileged observation that belongs to `obs` (the previous segment's "last_priv"), for a policy with a privileged
         critic; None = computed here with done=None (right after a reset; otherwise the contact and push words start as zeros).
         hist: likewise the history that belongs to `obs` (the previous segment's "last_hist"), for a history student; None = obs's frame
-        in every slot."""
+        in every slot.
+        hidden, start: likewise a recurrent student's state and episode-start flags that belong to `obs` (the previous segment's "last_hidden"
+        and last row of "dones"); None = zeros and everybody starts."""
         t, env = self.env.torch, self.env
+        if (hidden is not None or start is not None) and not self.recurrent:
+            raise ValueError("hidden and start are for a recurrent student (policy.recurrent > 0)")
         with t.no_grad():
             if obs.data_ptr() != self.obs[0].data_ptr():
                 self.obs[0].copy_(obs)
+            if self.recurrent:
+                if hidden is None:
+                    self.hid[0].zero_()
+                else:
+                    self.hid[0].copy_(hidden)
+                if start is None:
+                    self.starts[0].fill_(1)
+                else:
+                    self.starts[0].copy_(start)
             if self.hist is not None:
                 if hist is None:
                     from . import policy_hip
@@ -282,6 +327,8 @@ class GraphRollout(object):
             buf["hist"], buf["last_hist"] = self.hist[:self.T], self.hist[self.T]
         if self.teacher is not None:
             buf["teacher_mean"] = self.teacher_mean
+        if self.recurrent:
+            buf.update({"hidden": self.hid[0], "last_hidden": self.hid[self.T], "starts": self.starts[:self.T].view(t.bool), "hid": self.hid[1:]})
         return buf
 
 

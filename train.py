@@ -178,6 +178,11 @@ def arg_parser():
                          "sensors (IMU, last action, motor angles: 512 words), trained to estimate the privileged observation from them "
                          "(learner_hip.FusedDistillHistory; --torch-learner: ppo.DistillHistory).  The log carries latent_loss; --save writes "
                          "the teacher's variables + model/enc_*, a zip that loads here (--eval) and not in the reference")
+    ap.add_argument("--recurrent", action="store_true",
+                    help="--distill: like --history, but the estimator is a GRU of 256 units over the per-step sensor frame whose hidden state "
+                         "lives as long as the episode, trained by backpropagation through the segment's --horizon steps "
+                         "(learner_hip.FusedDistillRecurrent; --torch-learner: ppo.DistillRecurrent).  The log carries latent_loss; --save "
+                         "writes the teacher's variables + model/gru_*, a zip that --eval runs.  One rank, not with --history / --obs-norm")
     ap.add_argument("--history-ppo", action="store_true",
                     help="PPO on a history policy (RMA's third phase, or one-stage training): the actor reads its observation and the encoder's "
                          "estimate from the last 16 steps of its own sensors, the critic reads the simulator's TRUE privileged observation, and "
@@ -311,7 +316,7 @@ def obs_norm_check(args, world):
     if world > 1:
         raise SystemExit("train.py: --obs-norm runs on one rank: every rank would keep the statistics of its own shard and the replicas would "
                          "no longer be one policy (merging the records over ranks is not built)")
-    if args.distill or args.history or args.history_ppo:
+    if args.distill or args.history or args.history_ppo:        # (--recurrent belongs to --distill: check_args)
         raise SystemExit("train.py: --obs-norm belongs to PPO on a plain, privileged-critic or privileged-actor policy; the history and "
                          "distillation learners have no normaliser")
     if args.obs_norm_freeze_after is not None and args.obs_norm_freeze_after < 0:
@@ -364,6 +369,12 @@ def check_args(args, world):
         raise SystemExit("train.py: --latent-coef must not be negative")
     if args.distill and (args.privileged_critic or args.torch_policy):
         raise SystemExit("train.py: --distill trains a plain student with the fused rollout; not with --privileged-critic / --privileged-actor / --torch-policy")
+    if args.recurrent and not args.distill:
+        raise SystemExit("train.py: --recurrent belongs to --distill")
+    if args.recurrent and args.history:
+        raise SystemExit("train.py: --recurrent and --history are two estimators of the same row: give one")
+    if args.recurrent and (args.hip_backward or args.hip_forward or args.bf16_gemm):
+        raise SystemExit("train.py: --recurrent has kernels of its own, f32 only; not with --hip-backward / --hip-forward / --bf16-gemm")
     if args.history and not args.distill:
         raise SystemExit("train.py: --history belongs to --distill (PPO on a history policy is --history-ppo)")
     if (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0) and not args.history:
@@ -386,9 +397,10 @@ def check_args(args, world):
         raise SystemExit("train.py: --distill runs on one rank")
 
 
-def history_student(args, torch, pol, ppo, dev, path=None, fused=True, **model_kw):
+def history_student(args, torch, pol, ppo, dev, path=None, fused=True, recurrent=False, **model_kw):
     """--distill TEACHER.zip --history: the teacher's parameters + a fresh encoder (seeded by --seed), on the fused path.  --history-ppo with a
-    teacher's --model-file (`path`): the same rule, the model's std arguments in model_kw."""
+    teacher's --model-file (`path`): the same rule, the model's std arguments in model_kw.  recurrent (--distill --recurrent): a fresh GRU
+    in the encoder's place."""
     params = pol.load_parameters(path or args.distill)
     if any(k.startswith(pol.NORM_PREFIXES) for k in params):
         # the teacher's layer 0 expects normalised inputs, and a history policy has no normaliser: copying its weights would run them on raw
@@ -398,10 +410,11 @@ def history_student(args, torch, pol, ppo, dev, path=None, fused=True, **model_k
                          % (path or args.distill))
     if np.shape(params["model/pi_fc0/w:0"])[0] != 160 + pol.PRIV_DIM:
         raise SystemExit("train.py: %s needs a teacher with a privileged actor (--privileged-actor)" % ("--history-ppo --model-file" if path else "--history"))
-    student = ppo.ActorCritic(dev, seed=args.seed, priv_dim=pol.PRIV_DIM, actor_priv_dim=pol.PRIV_DIM, history=ppo.HISTORY_STEPS, **model_kw)
+    estimator = {"recurrent": ppo.GRU_HIDDEN} if recurrent else {"history": ppo.HISTORY_STEPS}
+    student = ppo.ActorCritic(dev, seed=args.seed, priv_dim=pol.PRIV_DIM, actor_priv_dim=pol.PRIV_DIM, **estimator, **model_kw)
     with torch.no_grad():
         for k, v in params.items():
-            if k.startswith("model/enc_"):
+            if k.startswith(("model/enc_", "model/gru_")):
                 continue                     # a history student as the teacher: its actor and critic, a fresh encoder all the same
             if k in student.p:
                 student.p[k].copy_(torch.as_tensor(v))
@@ -415,8 +428,8 @@ def make_model(args, dev):
     encoder.  SystemExit where --model-file and the flags disagree.  On the fused path unless --torch-policy."""
     import torch
     from openroborl_amd import policy as pol, ppo
-    if args.history:
-        return history_student(args, torch, pol, ppo, dev)
+    if args.history or args.recurrent:
+        return history_student(args, torch, pol, ppo, dev, recurrent=args.recurrent)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
     if args.history_ppo and params is not None and "model/enc_fc0/w:0" not in params:
         # a teacher's zip: its nets + a fresh encoder (the rule of --distill --history); the log-std, if any, is the teacher's
@@ -473,6 +486,8 @@ def make_learner(args, model, mode, num_samples, rank):
     # equal minibatches only (static buffers of the graph-replayed update): the largest size <= --minibatch that divides the
     # segment, e.g. --num-robot 1000 x horizon 32 = 32000 samples run as 2 x 16000 instead of failing on 16384
     mb = cls.fit_minibatch(num_samples, args.minibatch)
+    if mode == "DistillRecurrent":       # whole robots: the largest number of them <= --minibatch / horizon that divides the shard
+        mb = args.horizon * cls.fit_minibatch(args.num_robot, max(1, args.minibatch // args.horizon))
     if not is_ppo:
         return cls(model, lr=args.lr, minibatch=mb, **kw)
     if mode == "PPO" and mb != min(args.minibatch, num_samples) and rank == 0:
@@ -541,8 +556,8 @@ class DistillMode(Mode):
 
     def __init__(self, args, model, dev):
         from openroborl_amd import policy as pol, ppo
-        self.args, self.learner = args, "DistillHistory" if args.history else "Distill"
-        teacher_params = {k: v for k, v in pol.load_parameters(args.distill).items() if not k.startswith("model/enc_")}
+        self.args, self.learner = args, "DistillRecurrent" if args.recurrent else "DistillHistory" if args.history else "Distill"
+        teacher_params = {k: v for k, v in pol.load_parameters(args.distill).items() if not k.startswith(("model/enc_", "model/gru_"))}
         self.collector_kw = {"teacher": ppo.ActorCritic(dev, params=teacher_params).enable_fused()}
 
     def before_collect(self, it, collector):
@@ -553,6 +568,8 @@ class DistillMode(Mode):
         collector.teacher_mask[:self.driven] = 1
 
     def update_args(self, buf, flat):
+        if self.args.recurrent:              # whole segments: the learner's minibatches are sets of robots with all their steps
+            return [buf["obs"], buf["starts"], buf["hidden"], buf["priv"]], {}
         if not self.args.history:
             return [flat(buf["obs"]), flat(buf["teacher_mean"])], {}
         action = dict(obs=flat(buf["obs"]), target_mean=flat(buf["teacher_mean"])) if self.args.distill_action_coef > 0.0 else {}
@@ -560,7 +577,7 @@ class DistillMode(Mode):
 
     def record(self, env, stats, learner, loss):
         args = self.args
-        rec = {"latent_loss" if args.history else "distill_loss": round(float(loss), 6), "teacher_driven": self.driven}
+        rec = {"latent_loss" if args.history or args.recurrent else "distill_loss": round(float(loss), 6), "teacher_driven": self.driven}
         if args.history and (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0):
             # the log carries both losses: latent_loss then holds the latent regression's own loss, as it does without the action loss
             rec.update({"latent_loss": round(learner.last_latent_loss, 6), "action_loss": round(learner.last_action_loss, 6),
@@ -589,15 +606,18 @@ def train(args, env, model, mode, dev, rank, world):
     # what belongs to `obs`: the privileged observation and the sensor history of the policies that read them (None: right after the reset),
     # and episode_starts of a segment's first step = the last step's done flags of the previous segment
     obs, priv, hist, first_starts = env.reset(), None, None, None
+    state = {}              # a recurrent student's hidden state and episode-start flags that belong to `obs` (none: zeros, everybody starts)
     t0, samples, log = time.time(), 0, []
     # static rollout buffers + the segment replayed as one hipGraph (fused policy only); --torch-policy keeps the eager collector
     collector = None if args.torch_policy else rollout.GraphRollout(env, model, args.horizon, **mode.collector_kw)
 
     def collect():
         nonlocal obs, priv, hist
-        buf = (collector.collect(obs, generator=gen, priv=priv, hist=hist) if collector
-               else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv, hist=hist, **mode.collector_kw))
+        buf = (collector.collect(obs, generator=gen, priv=priv, hist=hist, **state) if collector
+               else rollout.collect_rollout(env, model, args.horizon, obs=obs, generator=gen, priv=priv, hist=hist, **state, **mode.collector_kw))
         obs, priv, hist = buf["last_obs"], buf.get("last_priv"), buf.get("last_hist")
+        if "last_hidden" in buf:
+            state.update(hidden=buf["last_hidden"], start=buf["dones"][-1])
         return buf
     # (--obs-norm, here and after the update, is plain PPO's alone: obs_norm_check refuses it to the other modes)
     if args.obs_norm and model.obs_norm.count == 0:
@@ -723,14 +743,15 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     model = ppo.ActorCritic(dev, params=pol.load_parameters(args.eval))
     if not args.torch_policy:
         model.enable_fused()
-    if model.actor_priv_dim and not model.history and not args.contact_outputs:
+    if model.actor_priv_dim and not model.history and not model.recurrent and not args.contact_outputs:
         env.bind_contact_outputs(True)           # a teacher's actor reads the contact words of the row, as it did in training
     obs = env.reset()
     # a zip with a privileged critic (--privileged-critic): the fused forward pass takes the privileged observation; only the actor's output is used
     # here.  A teacher's zip (--privileged-actor): the row goes to the actor every step.  A student's zip (--distill) is a plain policy.
     # A history student's zip (--distill --history): no row at all; its sensor history is kept in place, one push per step
-    priv = env.privileged_obs(done=None) if model.priv_dim and not model.history else None
+    priv = env.privileged_obs(done=None) if model.priv_dim and not model.history and not model.recurrent else None
     hist = None
+    rec_kw = {"hidden": None, "start": None} if model.recurrent else None     # a recurrent student's zip: its hidden state, carried in place
     if model.history:
         from openroborl_amd import policy_hip
         hist = policy_hip.history_push(obs, None, None, torch.empty((n, ppo.HISTORY_DIM), device=dev))
@@ -743,8 +764,13 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
     normal = torch.zeros(4, dtype=torch.float64, device=dev)
     limit = int(env.field_int("MAX_EP_STEPS").max())
     for _ in range(limit):
-        act, _, _ = model.act(obs, priv, deterministic=True, hist=hist)
+        if rec_kw is not None:
+            act, _, _, hidden = model.act(obs, deterministic=True, **rec_kw)
+        else:
+            act, _, _ = model.act(obs, priv, deterministic=True, hist=hist)
         obs, rew, done, _ = env.step(act)
+        if rec_kw is not None:
+            rec_kw = {"hidden": hidden, "start": done.bool(), "out_hidden": hidden}
         if priv is not None:
             env.privileged_obs(out=priv, done=done)
         if hist is not None:
