@@ -21,6 +21,7 @@
  *   orr_history_student_head  that head with the action loss: forward through the frozen actor, both losses, backward to the latent, one launch
  *   orr_latent_backward  PPO on a history policy: the gradient from the actor's layer 0 into the encoder's output + the auxiliary estimation loss
  *   orr_gru_backward   the recurrent student's GRU backward through the T steps of a segment, a workgroup per 16 robots (csrc/orr_recurrent.hip)
+ *   orr_gru_backward_bf16  the same on the bf16 matrix cores, operands rounded on their way into LDS (csrc/orr_recurrent_bf16.hip)
  *   orr_head_backward  gradient through an output layer (fan-out 12 or 1) + ReLU mask + bias gradient of the layer below + the
  *                      output layer's weight gradient
  *   orr_colsum_finish  the column sums behind all bias gradients of a minibatch in one launch
@@ -186,6 +187,18 @@ typedef struct orr_gru_transposed {
 } orr_gru_transposed;
 int32_t orr_gru_backward(const orr_gru_transposed* enc, const float* g_latent, const float* saved, const float* hprev, const uint8_t* starts,
                          int32_t t, int32_t n, float* g_x, float* g_h, float* partials, void* stream);
+
+/* orr_gru_backward on the bf16 matrix cores (csrc/orr_recurrent_bf16.hip; host side: FusedDistillRecurrent(bf16_gemm=True)): its contract,
+ * its partials layout (orr_colsum_finish and ORR_GRU_BACKWARD_ROWS serve both) and its refusals.  enc points at orr_gru_pack_bf16's images
+ * (openroborl_policy.h) of Wh^T and Wo^T, which its transpose flag writes straight from Wh [256][768] and Wo [256][48].  The A operands of the
+ * two contractions, g_latent_t and the step's g_h, are rounded to bf16 (nearest even) as they go into LDS; accumulation is float32, and dh,
+ * the gate derivatives, g_x / g_h as written to memory and the bias sums are float32.  saved and hprev are orr_gru_forward_bf16's. */
+typedef struct orr_gru_transposed_bf16 {
+  const uint16_t* wht;   /* image of Wh^T, 768 x 256: orr_gru_pack_bf16(Wh, 256, 768, 1, ..) */
+  const uint16_t* wot;   /* image of Wo^T, 48 x 256 (k padded to 64 with zeros): orr_gru_pack_bf16(Wo, 256, 48, 1, ..) */
+} orr_gru_transposed_bf16;
+int32_t orr_gru_backward_bf16(const orr_gru_transposed_bf16* enc, const float* g_latent, const float* saved, const float* hprev, const uint8_t* starts,
+                              int32_t t, int32_t n, float* g_x, float* g_h, float* partials, void* stream);
 
 /* g [m][c] (gradient w.r.t. a ReLU layer's output h [m][c]) becomes the gradient w.r.t. its pre-activation, in place: g *= (h > 0);
  * gb [c] = its column sums (the layer's bias gradient).  c: a multiple of 4 with 1024 % c == 0.

@@ -170,6 +170,38 @@ typedef struct orr_gru_encoder {
 int32_t orr_gru_forward(const orr_gru_encoder* enc, const float* obs, const uint8_t* starts, const float* h0, int32_t t, int32_t n, float* hid,
                         float* latent, float* frames, float* hprev, float* saved, void* stream);
 
+/* The same recurrence on the bf16 matrix cores (csrc/orr_recurrent_bf16.hip; host side: policy_hip.GruEncoder(bf16=True)): mixed precision
+ * in the sense of orr_dense_forward_bf16 (openroborl_learner.h) - every buffer in memory is float32, operands of v_mfma_f32_16x16x32_bf16
+ * are rounded to bf16 (nearest even), accumulation is float32.
+ *
+ * orr_gru_pack_bf16 turns a float32 [k][n] matrix into the fragment-major bf16 image the two kernels stream: for column tile nt (16 columns)
+ * and k-step ks (32 rows), lane l owns the eight elements W[32 ks + 8 (l >> 4) + e][16 nt + (l & 15)], e < 8:
+ *   out[((nt * ceil(k / 32) + ks) * 64 + l) * 8 + e]          (0 beyond row k or column n)
+ * one 16-byte load per lane, 1 KB per tile and k-step.  With transpose != 0 it is the image of w^T ([n][k]), written straight from w.  Each
+ * element is rounded ONCE, here: the image is a packed, derived buffer like orr_policy_pack's, re-made when the weights move.  (The MLP kernels
+ * read each weight once per launch and round it as they stage it; the GRU reads each weight T times per launch from every workgroup, so the
+ * pack is the place to round.)  The size function gives the image's length in 16-bit elements for a [k][n] matrix; the image of a transpose
+ * has the size of (n, k).  Refused: a null pointer, k < 1 or n < 1, a w that is not 4-byte or an image that is not 16-byte aligned, an image
+ * that overlaps w. */
+int64_t orr_gru_packed_bf16_size(int32_t k, int32_t n);
+int32_t orr_gru_pack_bf16(const float* w, int32_t k, int32_t n, int32_t transpose, uint16_t* out, void* stream);
+
+/* orr_gru_forward with bf16 operands: its arguments, outputs, optional outputs, alignment and overlap rules, the in-place hid == h0 at T = 1
+ * and its refusals; enc points at bf16 images.  The arithmetic is orr_gru_forward's with exactly these differences:
+ *   - the A operands of the matrix instructions are RNE_bf16 of the float32 values: the frame x_t, the masked state h', and h_t for the
+ *     latent; the B operands are the images; accumulation is float32 (the matrix cores' summation order, not an fmaf chain)
+ *   - everything else is float32 as before: both bias adds in orr_gru_forward's order, expf / tanhf, the combine (1 - u) c + u h' with the
+ *     UNROUNDED h', and every output.  hprev[t] is bit for bit starts[t] ? 0 : hid[t - 1] (h0 at t = 0), and the A operand of step t is
+ *     exactly RNE_bf16(hprev[t])
+ * T chained calls with T = 1 give the bits of one call over T; the same inputs give the same bits; rows at or beyond n write nothing. */
+typedef struct orr_gru_encoder_bf16 {
+  const uint16_t* wx; const float* bx;   /* orr_gru_pack_bf16 of the 32 x 768 matrix;  bias 768, float32 */
+  const uint16_t* wh; const float* bh;   /* of the 256 x 768 matrix;                   bias 768 */
+  const uint16_t* wo; const float* bo;   /* of the 256 x 48 matrix;                    bias 48  */
+} orr_gru_encoder_bf16;
+int32_t orr_gru_forward_bf16(const orr_gru_encoder_bf16* enc, const float* obs, const uint8_t* starts, const float* h0, int32_t t, int32_t n,
+                             float* hid, float* latent, float* frames, float* hprev, float* saved, void* stream);
+
 /* Per-robot GAE(lambda) over a [T][N] rollout segment + per-robot advantage standardisation, one launch
  * (reference: add_vtarg_and_adv, agents/ppo_imitation.py:68-93, and the per-robot normalisation :329-338; device
  * layout and the deliberate use of each robot's own done flags: openroborl_amd/rollout.py).

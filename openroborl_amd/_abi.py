@@ -241,6 +241,11 @@ GRU_BACKWARD_ARGS = [C.POINTER(OrrGruTransposed), C.c_void_p, C.c_void_p, C.c_vo
                      C.c_void_p]
 
 
+# orr_gru_forward_bf16 and orr_gru_backward_bf16 (csrc/orr_recurrent_bf16.hip) take the two argument lists above: orr_gru_encoder_bf16 and
+# orr_gru_transposed_bf16 have the members of their f32 namesakes, the weight pointers at orr_gru_pack_bf16's images (16-bit elements,
+# orr_gru_packed_bf16_size of them).  The two structures above, all void pointers, serve both.
+
+
 def gru_backward_rows(n):
     """include/openroborl_learner.h: ORR_GRU_BACKWARD_ROWS - the rows of partial sums orr_gru_backward leaves, one per 16 robots."""
     return (int(n) + 15) // 16

@@ -31,6 +31,7 @@ SRC_LEARNER_GEMM = os.path.join(CSRC, "orr_learner_gemm.hip")    # the backward 
 SRC_LEARNER_FORWARD = os.path.join(CSRC, "orr_learner_forward.hip")  # its forward layers on the matrix cores, in the rollout's arithmetic (orr_dense_forward)
 SRC_LEARNER_BF16 = os.path.join(CSRC, "orr_learner_bf16.hip")    # the hidden layers' contractions on the bf16 matrix cores (orr_*_bf16), f32 in HBM
 SRC_RECURRENT = os.path.join(CSRC, "orr_recurrent.hip")          # the recurrent student's GRU, forward and backward through time (orr_gru_*)
+SRC_RECURRENT_BF16 = os.path.join(CSRC, "orr_recurrent_bf16.hip")   # the same on the bf16 matrix cores (orr_gru_*_bf16), f32 in HBM
 # what the library is built from = what the stale-library check hashes: every source and header under csrc/ + the public headers
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [
     os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("openroborl_hip.h", "openroborl_policy.h", "openroborl_learner.h")]
@@ -118,7 +119,8 @@ FORWARD_UNITS = [("learner_forward", SRC_LEARNER_FORWARD, HIPCC_FLAGS_GEMM, Fals
 # behind FORWARD_UNITS, the same flags
 BF16_UNITS = [("learner_bf16", SRC_LEARNER_BF16, HIPCC_FLAGS_GEMM, False)]
 # The recurrent student's GRU (orr_gru_forward, orr_gru_backward): a unit and a table of their own behind BF16_UNITS, the same flags
-RECURRENT_UNITS = [("recurrent", SRC_RECURRENT, HIPCC_FLAGS_GEMM, False)]
+# and next to it, a unit of its own again, the GRU with bf16 operands (orr_gru_pack_bf16, orr_gru_forward_bf16, orr_gru_backward_bf16)
+RECURRENT_UNITS = [("recurrent", SRC_RECURRENT, HIPCC_FLAGS_GEMM, False), ("recurrent_bf16", SRC_RECURRENT_BF16, HIPCC_FLAGS_GEMM, False)]
 
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
@@ -425,6 +427,14 @@ def load():
     L.orr_gru_forward.argtypes = _abi.GRU_FORWARD_ARGS
     L.orr_gru_backward.restype = C.c_int32
     L.orr_gru_backward.argtypes = _abi.GRU_BACKWARD_ARGS
+    L.orr_gru_packed_bf16_size.restype = C.c_int64
+    L.orr_gru_packed_bf16_size.argtypes = [C.c_int32, C.c_int32]
+    L.orr_gru_pack_bf16.restype = C.c_int32
+    L.orr_gru_pack_bf16.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    L.orr_gru_forward_bf16.restype = C.c_int32
+    L.orr_gru_forward_bf16.argtypes = _abi.GRU_FORWARD_ARGS
+    L.orr_gru_backward_bf16.restype = C.c_int32
+    L.orr_gru_backward_bf16.argtypes = _abi.GRU_BACKWARD_ARGS
     L.orr_learner_partial_rows.restype = C.c_int32
     L.orr_learner_partial_rows.argtypes = [C.c_int32]
     L.orr_colsum_finish.restype = C.c_int32

@@ -196,11 +196,12 @@ class ActorCritic(object):
         if getattr(self, "fused", None) is not None:
             self.fused.std = self._std
 
-    def enable_fused(self):
+    def enable_fused(self, bf16_gru=False):
         """Route act() through the fused matrix-core forward pass (csrc/orr_policy.hip).  The packed weight copy is
-        refreshed lazily after mark_updated() (the learner calls it after every optimiser step)."""
+        refreshed lazily after mark_updated() (the learner calls it after every optimiser step).  bf16_gru: a recurrent student's step with
+        bf16 operands (orr_gru_forward_bf16)."""
         from . import policy_hip
-        self.fused = policy_hip.FusedActorCritic(self.p, self.device, std=self._std, obs_norm=self.obs_norm, priv_norm=self.priv_norm)
+        self.fused = policy_hip.FusedActorCritic(self.p, self.device, std=self._std, obs_norm=self.obs_norm, priv_norm=self.priv_norm, bf16_gru=bf16_gru)
         self._fused_dirty = False
         return self
 

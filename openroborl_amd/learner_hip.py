@@ -45,6 +45,9 @@ that is a multiple of 16, every _wgrad_hip and _dgrad_hip - on csrc/orr_learner_
 accumulation on the bf16 matrix cores, every buffer, the master weights and Adam float32.  The output layers, orr_head_backward and all
 non-GEMM kernels are the f32 ones.  The learner's forward pass is then NOT the rollout's bit for bit: a PPO ratio of the first epoch starts
 near 1, not at 1 (profiles/bf16_gemm.txt).
+FusedDistillRecurrent(bf16_gemm=True) is the recurrent student's variant of that flag: the GRU's own bf16 kernels (csrc/orr_recurrent_bf16.hip:
+orr_gru_pack_bf16 rounds each weight once into a bf16 image, orr_gru_forward_bf16 and orr_gru_backward_bf16 round the activations on their way
+into LDS) and orr_wgrad_bf16 for the three weight gradients; every buffer, the master weights and Adam float32 (profiles/gru_bf16.txt).
 There is no fallback: without a GPU and the HIP library the constructors raise.
 """
 import ctypes as C
@@ -923,7 +926,11 @@ class FusedDistillRecurrent(_FusedLearner):
     the three matrices and of the two transposes the backward pass streams (the weights move every step), orr_gru_forward over the T steps,
     orr_regress_head (T m samples of 48 columns: the loss, d loss / d z and gru_out's bias gradient), orr_gru_backward, three orr_wgrad
     (frames^T g_x, hprev^T g_h, hid^T g_z) and one orr_colsum_finish (the two bias gradients and the three weight gradients); an epoch replays
-    as one hipGraph.  f32 only, one rank, the latent loss only: action_coef > 0, bf16_gemm and a process group are refused."""
+    as one hipGraph.  One rank, the latent loss only: action_coef > 0 and a process group are refused.
+    bf16_gemm=True: the same launches on csrc/orr_recurrent_bf16.hip - a bf16 GruEncoder (orr_gru_pack_bf16 rounds each weight once),
+    orr_gru_forward_bf16 and orr_gru_backward_bf16, the two transposed images written straight from the weights by the pack's transpose flag
+    (no .t() copies), and the three weight gradients on orr_wgrad_bf16 where it takes the shape.  Every buffer, the master weights and Adam
+    stay float32."""
 
     def __init__(self, student, lr=1e-4, minibatch=4096, adam_eps=1e-5, betas=(0.9, 0.999), use_graph=True, action_coef=0.0, max_grad_norm=None,
                  device_lr=False, bf16_gemm=False, group=None):
@@ -933,8 +940,6 @@ class FusedDistillRecurrent(_FusedLearner):
             raise ValueError("FusedDistillRecurrent: the student needs a recurrent encoder (ActorCritic(recurrent=256))")
         if float(action_coef) != 0.0:
             raise ValueError("FusedDistillRecurrent: the action loss is not built for a recurrent student (action_coef must be 0)")
-        if bf16_gemm:
-            raise ValueError("FusedDistillRecurrent: the GRU kernels are f32 only (bf16_gemm must be False)")
         if group is not None:
             raise ValueError("FusedDistillRecurrent: one rank only (no gradient all-reduce is built for it)")
         self.minibatch_samples, self.T = int(minibatch), None
@@ -942,7 +947,8 @@ class FusedDistillRecurrent(_FusedLearner):
         _FusedLearner.__init__(self, student, sorted(k for k in student.p if k.startswith("model/gru_")), 1, lr, adam_eps, minibatch, betas, use_graph,
                                max_grad_norm=max_grad_norm, device_lr=device_lr)
         from . import policy_hip
-        self.gru = policy_hip.GruEncoder(self.w, self.dev)       # the forward images, of the flat buffer's views
+        self.bf16_gru = bool(bf16_gemm)
+        self.gru = policy_hip.GruEncoder(self.w, self.dev, bf16=self.bf16_gru)       # the forward images, of the flat buffer's views
         self.encT = _abi.OrrGruTransposed()
 
     def _buffers(self, P, f, split, rows):
@@ -955,16 +961,22 @@ class FusedDistillRecurrent(_FusedLearner):
                   "xo": f(T, m, 160), "st": u8(T, m), "xh0": f(m, H), "tgt": f(T, m, Z),
                   "hid": f(T, m, H), "z": f(T, m, Z), "frames": f(T, m, F), "hprev": f(T, m, H), "saved": f(T, m, 4, H),
                   "g_z": f(T, m, Z), "g_x": f(T, m, G), "g_h": f(T, m, G), "gp": f(2 * G * brows),
-                  "ws": f(int(L.orr_learner_workspace_floats(T * m, 64))),
-                  "whT": f(G, H), "woT": f(Z, H), "wht": f(int(L.orr_policy_packed_size(G, H))), "wot": f(int(L.orr_policy_packed_size(Z, H)))})
+                  "ws": f(int(L.orr_learner_workspace_floats(T * m, 64)))})
+        if self.bf16_gru:       # the images of Wh^T [768][256] and Wo^T [48][256]: the pack's transpose flag, no copies
+            P.update({k: t.empty(int(L.orr_gru_packed_bf16_size(*shape)), dtype=t.bfloat16, device=self.dev) for k, shape in (("wht", (G, H)), ("wot", (Z, H)))})
+        else:
+            P.update({"whT": f(G, H), "woT": f(Z, H), "wht": f(int(L.orr_policy_packed_size(G, H))), "wot": f(int(L.orr_policy_packed_size(Z, H)))})
         jobs = [(P["gp"], g["model/gru_x/b:0"], brows, G), (P["gp"][G * brows:], g["model/gru_h/b:0"], brows, G)]
-        # the three weight gradients: orr_wgrad's batch slices, one job each; a shape it refuses goes to the library (_wgrad) instead
+        # the three weight gradients: orr_wgrad's batch slices, one job each, on orr_wgrad_bf16 where bf16_gemm is set and it takes the shape,
+        # else on the f32 orr_wgrad; a shape that one refuses too goes to the library (_wgrad) instead, as it does without the flag
         P["wg"] = []
         for x, gy, key in (("frames", "g_x", "model/gru_x/w:0"), ("hprev", "g_h", "model/gru_h/w:0"), ("hid", "g_z", "model/gru_out/w:0")):
             k, n = int(P[x].shape[-1]), int(P[gy].shape[-1])
-            s = int(L.orr_wgrad_slices(T * m, k, n))
+            fn, s = L.orr_wgrad_bf16, int(L.orr_wgrad_bf16_slices(T * m, k, n)) if self.bf16_gru else 0
+            if s <= 0:
+                fn, s = L.orr_wgrad, int(L.orr_wgrad_slices(T * m, k, n))
             part = f(s, k, n) if s > 0 else None
-            P["wg"].append((P[x].view(T * m, k), P[gy].view(T * m, n), part, g[key]))
+            P["wg"].append((P[x].view(T * m, k), P[gy].view(T * m, n), part, g[key], fn))
             if part is not None:
                 jobs.append((part, g[key], s, k * n))
         P["jobs"], P["n_jobs"] = _jobs(jobs)
@@ -978,19 +990,23 @@ class FusedDistillRecurrent(_FusedLearner):
         for src, dst, dim in (("obs", "xo", 1), ("starts", "st", 1), ("target", "tgt", 1), ("h0", "xh0", 0)):
             t.index_select(P[src], dim, idx, out=P[dst])
         self.gru.refresh()
-        P["whT"].copy_(w["model/gru_h/w:0"].t())
-        P["woT"].copy_(w["model/gru_out/w:0"].t())
-        _lib.check(L.orr_policy_pack(P["whT"].data_ptr(), _abi.GRU_GATES, _abi.GRU_HIDDEN, P["wht"].data_ptr(), st), L)
-        _lib.check(L.orr_policy_pack(P["woT"].data_ptr(), _abi.POLICY_PRIV_DIM, _abi.GRU_HIDDEN, P["wot"].data_ptr(), st), L)
+        if self.bf16_gru:
+            _lib.check(L.orr_gru_pack_bf16(w["model/gru_h/w:0"].data_ptr(), _abi.GRU_HIDDEN, _abi.GRU_GATES, 1, P["wht"].data_ptr(), st), L)
+            _lib.check(L.orr_gru_pack_bf16(w["model/gru_out/w:0"].data_ptr(), _abi.GRU_HIDDEN, _abi.POLICY_PRIV_DIM, 1, P["wot"].data_ptr(), st), L)
+        else:
+            P["whT"].copy_(w["model/gru_h/w:0"].t())
+            P["woT"].copy_(w["model/gru_out/w:0"].t())
+            _lib.check(L.orr_policy_pack(P["whT"].data_ptr(), _abi.GRU_GATES, _abi.GRU_HIDDEN, P["wht"].data_ptr(), st), L)
+            _lib.check(L.orr_policy_pack(P["woT"].data_ptr(), _abi.POLICY_PRIV_DIM, _abi.GRU_HIDDEN, P["wot"].data_ptr(), st), L)
         self.encT.wht, self.encT.wot = P["wht"].data_ptr(), P["wot"].data_ptr()
         self.gru.forward(P["xo"], P["st"], P["xh0"], hid=P["hid"], latent=P["z"], frames=P["frames"], hprev=P["hprev"], saved=P["saved"])
         _lib.check(L.orr_regress_head(P["z"].data_ptr(), P["tgt"].data_ptr(), T * m, _abi.POLICY_PRIV_DIM, P["g_z"].data_ptr(),
                                       g["model/gru_out/b:0"].data_ptr(), P["stats"][s].data_ptr(), P["ws"].data_ptr(), st), L)
-        _lib.check(L.orr_gru_backward(C.byref(self.encT), P["g_z"].data_ptr(), P["saved"].data_ptr(), P["hprev"].data_ptr(), P["st"].data_ptr(), T, m,
+        _lib.check((L.orr_gru_backward_bf16 if self.bf16_gru else L.orr_gru_backward)(C.byref(self.encT), P["g_z"].data_ptr(), P["saved"].data_ptr(), P["hprev"].data_ptr(), P["st"].data_ptr(), T, m,
                                       P["g_x"].data_ptr(), P["g_h"].data_ptr(), P["gp"].data_ptr(), st), L)
-        for x, gy, part, out in P["wg"]:
+        for x, gy, part, out, fn in P["wg"]:
             if part is not None:
-                _lib.check(L.orr_wgrad(x.data_ptr(), x.shape[1], gy.data_ptr(), gy.shape[1], x.shape[0], part.data_ptr(), st), L)
+                _lib.check(fn(x.data_ptr(), x.shape[1], gy.data_ptr(), gy.shape[1], x.shape[0], part.data_ptr(), st), L)
             else:
                 self._wgrad(x, gy, None, out)
         _lib.check(L.orr_colsum_finish(P["jobs"], P["n_jobs"], st), L)

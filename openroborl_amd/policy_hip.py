@@ -32,11 +32,12 @@ def _checked(x, dtype, shape, device, name):
 class GruEncoder(object):
     """The packed copy of a recurrent student's GRU (model/gru_x, model/gru_h, model/gru_out of a parameter dict) at fixed addresses, and
     orr_gru_forward on it.  refresh() packs the three matrices and copies the three biases (six small launches), e.g. inside a captured
-    rollout segment or learner epoch."""
+    rollout segment or learner epoch.  bf16=True: the three images are orr_gru_pack_bf16's (each weight rounded to bf16 once, in the pack) and
+    forward() is orr_gru_forward_bf16 - bf16 operands, f32 accumulation, every tensor float32 as before (csrc/orr_recurrent_bf16.hip)."""
 
-    def __init__(self, params, device):
+    def __init__(self, params, device, bf16=False):
         import torch
-        self.torch, self.params, self.device = torch, params, device
+        self.torch, self.params, self.device, self.bf16 = torch, params, device, bool(bf16)
         self.L = _lib.load()
         self.enc = _abi.OrrGruEncoder()
         self.buf = {}
@@ -45,7 +46,10 @@ class GruEncoder(object):
             if field in GRU_SHAPES:
                 if tuple(w.shape) != GRU_SHAPES[field]:
                     raise ValueError("%s has shape %s, the GRU kernel is built for %s" % (key, tuple(w.shape), GRU_SHAPES[field]))
-                self.buf[field] = torch.empty(int(self.L.orr_policy_packed_size(*GRU_SHAPES[field])), dtype=torch.float32, device=device)
+                if self.bf16:
+                    self.buf[field] = torch.empty(int(self.L.orr_gru_packed_bf16_size(*GRU_SHAPES[field])), dtype=torch.bfloat16, device=device)
+                else:
+                    self.buf[field] = torch.empty(int(self.L.orr_policy_packed_size(*GRU_SHAPES[field])), dtype=torch.float32, device=device)
             else:
                 self.buf[field] = torch.empty(w.numel(), dtype=torch.float32, device=device)
             setattr(self.enc, field, self.buf[field].data_ptr())
@@ -60,13 +64,15 @@ class GruEncoder(object):
             w = self.params[key].detach()
             if w.dtype != t.float32 or not w.is_contiguous() or w.device != self.device:
                 w = w.to(device=self.device, dtype=t.float32).contiguous()
-            if field in GRU_SHAPES:
+            if field in GRU_SHAPES and self.bf16:
+                _lib.check(self.L.orr_gru_pack_bf16(w.data_ptr(), int(w.shape[0]), int(w.shape[1]), 0, self.buf[field].data_ptr(), self._stream()), self.L)
+            elif field in GRU_SHAPES:
                 _lib.check(self.L.orr_policy_pack(w.data_ptr(), int(w.shape[0]), int(w.shape[1]), self.buf[field].data_ptr(), self._stream()), self.L)
             else:
                 self.buf[field].copy_(w.reshape(-1))
 
     def forward(self, obs, starts=None, h0=None, hid=None, latent=None, frames=None, hprev=None, saved=None):
-        """orr_gru_forward: obs [T,n,160], starts [T,n] uint8 / bool (None: everybody starts, T = 1 only), h0 [n,256] (None: zeros) -> hid
+        """orr_gru_forward (orr_gru_forward_bf16 with bf16=True): obs [T,n,160], starts [T,n] uint8 / bool (None: everybody starts, T = 1 only), h0 [n,256] (None: zeros) -> hid
         [T,n,256], allocated unless given (with T = 1 it may be h0's storage).  latent [T,n,48], frames [T,n,32], hprev [T,n,256] and saved
         [T,n,4,256] are written when given.  Returns hid."""
         t = self.torch
@@ -83,8 +89,9 @@ class GruEncoder(object):
                                       (hprev, f32, (T, n, H), "hprev"), (saved, f32, (T, n, 4, H), "saved")):
             _checked(x, dtype, shape, self.device, name)
         ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
-        _lib.check(self.L.orr_gru_forward(C.byref(self.enc), obs.data_ptr(), ptr(starts), ptr(h0), T, n, hid.data_ptr(), ptr(latent), ptr(frames),
-                                          ptr(hprev), ptr(saved), self._stream()), self.L)
+        entry = self.L.orr_gru_forward_bf16 if self.bf16 else self.L.orr_gru_forward
+        _lib.check(entry(C.byref(self.enc), obs.data_ptr(), ptr(starts), ptr(h0), T, n, hid.data_ptr(), ptr(latent), ptr(frames),
+                         ptr(hprev), ptr(saved), self._stream()), self.L)
         return hid
 
 
@@ -96,7 +103,7 @@ class FusedActorCritic(object):
     static buffer) and then runs the forward kernel it would run anyway with std = 1, mean + 1 * x being mean + x.  The twelve values are
     read on the device, from this object's own copy at a fixed address (refresh() renews it), never on the host."""
 
-    def __init__(self, params, device, std, clip=2.0 * math.pi, obs_norm=None, priv_norm=None):
+    def __init__(self, params, device, std, clip=2.0 * math.pi, obs_norm=None, priv_norm=None, bf16_gru=False):
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -146,9 +153,11 @@ class FusedActorCritic(object):
                 raise ValueError("a recurrent encoder (model/gru_x/w:0) feeds a privileged actor (model/pi_fc0/w:0 with %d rows) and goes "
                                  "without a history encoder" % (160 + _abi.POLICY_PRIV_DIM))
             self.recurrent = _abi.GRU_HIDDEN
-            self.gru = GruEncoder(params, self.device)
+            self.gru = GruEncoder(params, self.device, bf16=bf16_gru)       # bf16_gru: the recurrent step on the bf16 matrix cores
             self._latent = {}         # n -> the static [n, 48] estimate the teacher kernel reads
-        self.log_std = None           # the sampler's copy of model/pi/logstd:0, [12]
+        elif bf16_gru:
+            raise ValueError("bf16_gru=True is a recurrent student's (model/gru_x/w:0); this policy has no GRU")
+        self.log_std = None          # the sampler's copy of model/pi/logstd:0, [12]
         self._scaled = {}             # n -> the static [n, 12] buffer of exp(log_std) * noise
         if LOGSTD in params:
             if params[LOGSTD].numel() != 12:

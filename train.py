@@ -239,7 +239,10 @@ def arg_parser():
     ap.add_argument("--bf16-gemm", action="store_true",
                     help="the fused learners' hidden-layer contractions, forward and backward, with bf16 operands and f32 accumulation on the bf16 "
                          "matrix cores (orr_dense_forward_bf16, orr_dgrad_relu_bf16, orr_wgrad_bf16: learner_hip's bf16_gemm=True; weights, "
-                         "activations and Adam stay float32); implies --hip-forward --hip-backward; every mode; not with --torch-learner")
+                         "activations and Adam stay float32); implies --hip-forward --hip-backward; every mode; not with --torch-learner.  With --distill "
+                         "--recurrent: the GRU's own bf16 kernels (orr_gru_forward_bf16, orr_gru_backward_bf16) in the learner and in the student's "
+                         "rollout step; with --eval of a recurrent student's zip: the bf16 step (--eval of any other zip, and --eval --torch-policy, "
+                         "run no learner and no GRU kernel: the flag changes nothing there)")
     ap.add_argument("--eval", default="", help="evaluate a policy zip instead of training: deterministic actions, test mode "
                                                  "(no randomiser, full-length episodes), like `run.py --mode test`")
     ap.add_argument("--legacy-gae-index", action="store_true",
@@ -373,8 +376,8 @@ def check_args(args, world):
         raise SystemExit("train.py: --recurrent belongs to --distill")
     if args.recurrent and args.history:
         raise SystemExit("train.py: --recurrent and --history are two estimators of the same row: give one")
-    if args.recurrent and (args.hip_backward or args.hip_forward or args.bf16_gemm):
-        raise SystemExit("train.py: --recurrent has kernels of its own, f32 only; not with --hip-backward / --hip-forward / --bf16-gemm")
+    if args.recurrent and (args.hip_backward or args.hip_forward):
+        raise SystemExit("train.py: --recurrent has kernels of its own; not with --hip-backward / --hip-forward (their bf16 variant: --bf16-gemm)")
     if args.history and not args.distill:
         raise SystemExit("train.py: --history belongs to --distill (PPO on a history policy is --history-ppo)")
     if (args.distill_action_coef != 0.0 or args.distill_latent_coef != 1.0) and not args.history:
@@ -420,7 +423,7 @@ def history_student(args, torch, pol, ppo, dev, path=None, fused=True, recurrent
                 student.p[k].copy_(torch.as_tensor(v))
             else:
                 student.extra[k] = np.asarray(v, dtype=np.float32).copy()
-    return student.enable_fused() if fused else student
+    return student.enable_fused(bf16_gru=recurrent and args.bf16_gemm) if fused else student
 
 
 def make_model(args, dev):
@@ -742,7 +745,7 @@ def evaluate(args, torch, pol, ppo, VecQuadrupedEnv):
                           observation_noise_stdev=args.sensor_noise, **clip_time_kwargs(args))
     model = ppo.ActorCritic(dev, params=pol.load_parameters(args.eval))
     if not args.torch_policy:
-        model.enable_fused()
+        model.enable_fused(bf16_gru=bool(model.recurrent) and args.bf16_gemm)      # a recurrent student's zip with --bf16-gemm: the bf16 step
     if model.actor_priv_dim and not model.history and not model.recurrent and not args.contact_outputs:
         env.bind_contact_outputs(True)           # a teacher's actor reads the contact words of the row, as it did in training
     obs = env.reset()
