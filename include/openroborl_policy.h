@@ -170,6 +170,27 @@ typedef struct orr_gru_encoder {
 int32_t orr_gru_forward(const orr_gru_encoder* enc, const float* obs, const uint8_t* starts, const float* h0, int32_t t, int32_t n, float* hid,
                         float* latent, float* frames, float* hprev, float* saved, void* stream);
 
+/* One policy step of a RECURRENT policy in ONE launch (csrc/orr_policy_recurrent.hip; host side: policy_hip.FusedActorCritic.forward(hidden=,
+ * start=, priv=)): the recurrence above for one step, the teacher-shaped actor on obs | z and the critic on obs | priv - the asymmetric critic
+ * of a recurrent policy, as orr_policy_forward_history_priv is a history policy's - or on obs | z.
+ *   h' = start ? 0 : h0;   hid = h_t and latent = z of the recurrence above
+ *   mean = actor(obs | z);   action = clip(mean + std * noise);   raw = mean + std * noise
+ *   value = critic(obs | priv) with a priv, critic(obs | z) with priv == NULL
+ *   net     a teacher's net: both layer 0s packed at k = 208
+ *   enc     orr_gru_forward's encoder, the same images
+ *   start   [n] uint8, NULL: everybody starts;   h0 [n][256], NULL: zeros;   priv [n][48] or NULL
+ *   hid     [n][256]; it may BE h0 (in place).  latent [n][48], raw, mean and value may each be NULL, which changes no other output bit;
+ *           value == NULL also skips the critic's three layers
+ * Every accumulator runs over k ascending, in the order of the two kernels it replaces: a row's bits depend on neither n nor its neighbours,
+ * hid and latent are orr_gru_forward(T = 1)'s, and with priv == NULL action, raw, mean and value are orr_policy_forward_teacher(priv = latent)'s.
+ * No atomics: the same inputs give the same bits.
+ * Refused with a negative code, nothing launched or written: a null net, enc, obs, action or hid, a null member of net or enc; n < 1; packed
+ * matrices or a hid that are not 16-byte aligned, another buffer that is not 4-byte aligned; a hid that overlaps h0 without being equal to it,
+ * outputs that overlap each other or an input. */
+int32_t orr_policy_forward_recurrent(const orr_policy_net* net, const orr_gru_encoder* enc, const float* obs, const uint8_t* start, const float* h0,
+                                     const float* priv, int32_t n, const float* noise, float std, float clip, float* action, float* raw,
+                                     float* value, float* mean, float* hid, float* latent, void* stream);
+
 /* The same recurrence on the bf16 matrix cores (csrc/orr_recurrent_bf16.hip; host side: policy_hip.GruEncoder(bf16=True)): mixed precision
  * in the sense of orr_dense_forward_bf16 (openroborl_learner.h) - every buffer in memory is float32, operands of v_mfma_f32_16x16x32_bf16
  * are rounded to bf16 (nearest even), accumulation is float32.

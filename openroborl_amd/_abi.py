@@ -240,6 +240,12 @@ GRU_FORWARD_ARGS = [C.POINTER(OrrGruEncoder), C.c_void_p, C.c_void_p, C.c_void_p
 GRU_BACKWARD_ARGS = [C.POINTER(OrrGruTransposed), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                      C.c_void_p]
 
+# int32_t orr_policy_forward_recurrent(const orr_policy_net* net, const orr_gru_encoder* enc, const float* obs [n][160], const uint8_t* start [n] | NULL,
+#   const float* h0 [n][256] | NULL, const float* priv [n][48] | NULL, int32_t n, const float* noise [n][12] | NULL, float std, float clip,
+#   float* action [n][12], float* raw | NULL, float* value [n] | NULL, float* mean | NULL, float* hid [n][256], float* latent [n][48] | NULL, void* stream)
+POLICY_FORWARD_RECURRENT_ARGS = [C.POINTER(OrrPolicyNet), C.POINTER(OrrGruEncoder), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                 C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+
 
 # orr_gru_forward_bf16 and orr_gru_backward_bf16 (csrc/orr_recurrent_bf16.hip) take the two argument lists above: orr_gru_encoder_bf16 and
 # orr_gru_transposed_bf16 have the members of their f32 namesakes, the weight pointers at orr_gru_pack_bf16's images (16-bit elements,

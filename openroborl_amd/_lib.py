@@ -32,6 +32,7 @@ SRC_LEARNER_FORWARD = os.path.join(CSRC, "orr_learner_forward.hip")  # its forwa
 SRC_LEARNER_BF16 = os.path.join(CSRC, "orr_learner_bf16.hip")    # the hidden layers' contractions on the bf16 matrix cores (orr_*_bf16), f32 in HBM
 SRC_RECURRENT = os.path.join(CSRC, "orr_recurrent.hip")          # the recurrent student's GRU, forward and backward through time (orr_gru_*)
 SRC_RECURRENT_BF16 = os.path.join(CSRC, "orr_recurrent_bf16.hip")   # the same on the bf16 matrix cores (orr_gru_*_bf16), f32 in HBM
+SRC_POLICY_RECURRENT = os.path.join(CSRC, "orr_policy_recurrent.hip")   # a recurrent policy's step in one launch (orr_policy_forward_recurrent)
 # what the library is built from = what the stale-library check hashes: every source and header under csrc/ + the public headers
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [
     os.path.join(os.path.dirname(PKG_DIR), "include", h) for h in ("openroborl_hip.h", "openroborl_policy.h", "openroborl_learner.h")]
@@ -121,6 +122,8 @@ BF16_UNITS = [("learner_bf16", SRC_LEARNER_BF16, HIPCC_FLAGS_GEMM, False)]
 # The recurrent student's GRU (orr_gru_forward, orr_gru_backward): a unit and a table of their own behind BF16_UNITS, the same flags
 # and next to it, a unit of its own again, the GRU with bf16 operands (orr_gru_pack_bf16, orr_gru_forward_bf16, orr_gru_backward_bf16)
 RECURRENT_UNITS = [("recurrent", SRC_RECURRENT, HIPCC_FLAGS_GEMM, False), ("recurrent_bf16", SRC_RECURRENT_BF16, HIPCC_FLAGS_GEMM, False)]
+# A recurrent policy's step in one launch (orr_policy_forward_recurrent): a unit and a table of its own behind RECURRENT_UNITS, the same flags
+RECURRENT_STEP_UNITS = [("policy_recurrent", SRC_POLICY_RECURRENT, HIPCC_FLAGS_GEMM, False)]
 
 EXPORTS = [
     "orr_last_error", "orr_abi_version", "orr_source_hash", "orr_state_stride", "orr_layout_count", "orr_layout_name",
@@ -130,7 +133,7 @@ EXPORTS = [
     "orr_policy_packed_size", "orr_policy_pack", "orr_policy_forward", "orr_policy_forward_priv", "orr_policy_forward_teacher", "orr_policy_forward_history", "orr_policy_forward_history_priv", "orr_history_push", "orr_gae", "orr_gae_flags",
     "orr_learner_workspace_floats", "orr_ppo_head", "orr_ppo_head_logstd", "orr_gauss_prepare", "orr_distill_head", "orr_regress_head", "orr_history_student_head", "orr_latent_backward", "orr_relu_backward", "orr_head_backward", "orr_colsum_finish", "orr_learner_partial_rows", "orr_adam_step",
     "orr_wgrad_slices", "orr_wgrad", "orr_dgrad_partial_rows", "orr_dgrad_relu", "orr_dense_forward",
-    "orr_gru_forward", "orr_gru_backward",
+    "orr_gru_forward", "orr_gru_backward", "orr_policy_forward_recurrent",
     "orr_sizeof_update_ctl", "orr_update_control_partials", "orr_update_control", "orr_adam_step_ctl",
     "orr_sizeof_running_stats", "orr_running_stats_partials", "orr_running_stats_update", "orr_normalize_rows", "orr_policy_pack_norm",
 ]
@@ -212,7 +215,7 @@ def build(force=False, verbose=False, out_path=None, extra_flags=()):
             units = []      # the tables up to PRIV_UNITS in the order the older tests read off the next line, then the newest
             for unit in ALL_UNITS + TERMS_UNITS + CONTACT_UNITS + ACTUATOR_UNITS + SENSOR_UNITS + RANDOMIZER_UNITS + PUSH_UNITS + PRIV_UNITS:
                 units.append(unit)
-            units = GEMM_UNITS + FORWARD_UNITS + BF16_UNITS + RECURRENT_UNITS + units       # the learners' GEMMs: no env units, their place in the link means nothing
+            units = GEMM_UNITS + FORWARD_UNITS + BF16_UNITS + RECURRENT_UNITS + RECURRENT_STEP_UNITS + units       # the learners' GEMMs: no env units, their place in the link means nothing
             for unit in units + SHAPING_UNITS:       # the newest table last
                 name, src, flags, hashed = unit
                 flags = [f for f in flags if f != "-shared"] + ["-c"]
@@ -427,6 +430,8 @@ def load():
     L.orr_gru_forward.argtypes = _abi.GRU_FORWARD_ARGS
     L.orr_gru_backward.restype = C.c_int32
     L.orr_gru_backward.argtypes = _abi.GRU_BACKWARD_ARGS
+    L.orr_policy_forward_recurrent.restype = C.c_int32
+    L.orr_policy_forward_recurrent.argtypes = _abi.POLICY_FORWARD_RECURRENT_ARGS
     L.orr_gru_packed_bf16_size.restype = C.c_int64
     L.orr_gru_packed_bf16_size.argtypes = [C.c_int32, C.c_int32]
     L.orr_gru_pack_bf16.restype = C.c_int32

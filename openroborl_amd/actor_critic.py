@@ -315,12 +315,16 @@ class ActorCritic(object):
         mean(obs, hist=hist) and value(obs, critic_priv), what PPOHistory trains.
         A recurrent student takes `hidden` ([N,256], the state before; None: zeros) and `start` ([N] bool / uint8, the done flags of the step
         that produced obs; None: everybody starts) instead, and returns (clipped action, raw action, value, new hidden state): actor and
-        critic read the GRU's estimate, which out_latent receives; out_hidden [N,256] receives the new state (it may be `hidden`)."""
+        critic read the GRU's estimate, which out_latent receives; out_hidden [N,256] receives the new state (it may be `hidden`).  With a
+        `priv` the critic of a recurrent policy is asymmetric: the actor still reads the estimate, the value comes from the true row -
+        value(obs, priv), what PPORecurrent trains; the fused path runs both in orr_policy_forward_recurrent's one launch."""
         t = self.torch
         if self.recurrent:
-            if priv is not None or hist is not None or critic_priv is not None:
-                raise ValueError("a recurrent student reads hidden and start, not priv / hist / critic_priv")
-            return self._act_recurrent(obs, hidden, start, deterministic, generator, noise, out_raw, out_value, out_latent, out_hidden)
+            if hist is not None or critic_priv is not None:
+                raise ValueError("a recurrent policy reads hidden and start (and priv, for its critic alone), not hist / critic_priv")
+            if priv is not None and tuple(priv.shape) != (obs.shape[0], pol.PRIV_DIM):
+                raise ValueError("priv must have shape (%d, %d), got %s" % (obs.shape[0], pol.PRIV_DIM, tuple(priv.shape)))
+            return self._act_recurrent(obs, hidden, start, deterministic, generator, noise, out_raw, out_value, out_latent, out_hidden, priv)
         if hidden is not None or start is not None or out_hidden is not None:
             raise ValueError("hidden, start and out_hidden are for a recurrent student (recurrent = %d)" % GRU_HIDDEN)
         if critic_priv is not None:
@@ -361,7 +365,7 @@ class ActorCritic(object):
             a = mu if deterministic else mu + (self.p[LOGSTD].exp() if self.learn_std else self.std) * noise
             return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, priv if critic_priv is None else critic_priv)
 
-    def _act_recurrent(self, obs, hidden, start, deterministic, generator, noise, out_raw, out_value, out_latent, out_hidden):
+    def _act_recurrent(self, obs, hidden, start, deterministic, generator, noise, out_raw, out_value, out_latent, out_hidden, priv=None):
         t = self.torch
         if self.fused is not None:
             if self._fused_dirty:
@@ -370,7 +374,7 @@ class ActorCritic(object):
             if noise is None and not deterministic:
                 noise = t.randn((obs.shape[0], 12), device=obs.device, generator=generator)
             a, raw, v, _, h = self.fused.forward(obs, None if deterministic else noise, out_raw=out_raw, out_value=out_value, hidden=hidden, start=start,
-                                                 out_hidden=out_hidden, out_latent=out_latent)
+                                                 out_hidden=out_hidden, out_latent=out_latent, **({} if priv is None else {"priv": priv}))
             return a, raw, v, h
         with t.no_grad():
             h, z = self.encode_step(obs, hidden, start)
@@ -382,7 +386,7 @@ class ActorCritic(object):
             if noise is None and not deterministic:
                 noise = t.randn(mu.shape, device=mu.device, generator=generator)
             a = mu if deterministic else mu + (self.p[LOGSTD].exp() if self.learn_std else self.std) * noise
-            return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, z), h
+            return t.clamp(a, -2.0 * math.pi, 2.0 * math.pi), a, self.value(obs, z if priv is None else priv), h
 
     def log_prob(self, obs, actions, priv=None, hist=None):
         mu = self.mean(obs, priv, hist)

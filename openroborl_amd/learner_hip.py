@@ -430,7 +430,8 @@ class FusedPPO(_FusedLearner):
             raise ValueError("FusedPPO: a history policy is trained by FusedPPOHistory (PPO with the critic on the true privileged row) or by "
                              "FusedDistillHistory")
         if getattr(model, "recurrent", 0):
-            raise ValueError("%s: PPO on a recurrent policy is not built; its GRU is trained by FusedDistillRecurrent" % type(self).__name__)
+            raise ValueError("%s: the fused PPO learner of a recurrent policy is not built; PPO on it runs on the torch learner ppo.PPORecurrent "
+                             "(train.py --recurrent-ppo), its GRU alone is trained by FusedDistillRecurrent" % type(self).__name__)
         self.learn_std, self.ent_coef, self.log_std_bounds = _entropy_args(model, type(self).__name__, ent_coef, log_std_bounds or LOG_STD_BOUNDS)
         self.clip, self.vf_coef = float(clip_param), float(vf_coef)
         self.group = group

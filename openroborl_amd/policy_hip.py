@@ -260,14 +260,21 @@ class FusedActorCritic(object):
         critic_priv [N,48] float32, with hist only: the critic reads obs | critic_priv, the TRUE row, while the actor reads the estimate
         (orr_policy_forward_history_priv: the actor's outputs are orr_policy_forward_history's, the value orr_policy_forward_teacher's).
         scaled=True, for a policy with a learned log-std: `noise` already is exp(log_std) * noise (prepare(), e.g. once for a whole segment).
-        A recurrent student (model/gru_x/w:0) takes hidden [N,256] (the state before; None: zeros) and start [N] uint8 / bool (None: everybody
-        starts) instead of priv: orr_gru_forward (T = 1) writes the new state to out_hidden [N,256] (allocated unless given; it may be `hidden`)
-        and the estimate of the row to out_latent, then orr_policy_forward_teacher reads the estimate as priv.  Two launches; the return
-        value is then (action, raw, value, mean, new hidden)."""
+        A recurrent policy (model/gru_x/w:0) takes hidden [N,256] (the state before; None: zeros) and start [N] uint8 / bool (None: everybody
+        starts): ONE launch (orr_policy_forward_recurrent) runs the GRU step, writes the new state to out_hidden [N,256] (allocated unless given;
+        it may be `hidden`) and the estimate of the row to out_latent, and runs the teacher-shaped nets, the actor on obs | estimate, the critic
+        on obs | priv when priv [N,48] (the TRUE row: the asymmetric critic of PPO on a recurrent policy) is given and on obs | estimate
+        otherwise.  With bf16_gru=True it is two launches, orr_gru_forward_bf16 (T = 1) and orr_policy_forward_teacher on its estimate, and priv
+        is refused.  The return value is then (action, raw, value, mean, new hidden)."""
         t = self.torch
         if self.recurrent:
-            if priv is not None or hist is not None or critic_priv is not None:
-                raise ValueError("a recurrent student reads hidden and start, not priv / hist / critic_priv")
+            if hist is not None or critic_priv is not None:
+                raise ValueError("a recurrent policy reads hidden and start (and priv, for its critic alone), not hist / critic_priv")
+            if not self.gru.bf16:
+                return self._forward_recurrent(obs, noise, want_mean, out_action, out_raw, out_value, priv, out_mean, want_value, out_latent, scaled,
+                                               hidden, start, out_hidden)
+            if priv is not None:
+                raise ValueError("bf16_gru=True has no fused step: priv (the asymmetric critic) goes with the float32 GRU")
             n = obs.shape[0]
             if out_latent is None:
                 if n not in self._latent:
@@ -358,6 +365,42 @@ class FusedActorCritic(object):
                                              std, self.clip, act.data_ptr(), raw.data_ptr(), val.data_ptr() if val is not None else None,
                                              mean.data_ptr() if mean is not None else None, self._stream()), self.L)
         return act, raw, val, mean
+
+
+    def _forward_recurrent(self, obs, noise, want_mean, out_action, out_raw, out_value, priv, out_mean, want_value, out_latent, scaled, hidden, start,
+                           out_hidden):
+        """forward() of a recurrent policy with the float32 GRU: orr_policy_forward_recurrent, one launch."""
+        t, f32 = self.torch, self.torch.float32
+        if obs.dim() != 2:
+            raise ValueError("obs must be a contiguous float32 [N,160] tensor on %s" % (self.device,))
+        n, H, Z = int(obs.shape[0]), _abi.GRU_HIDDEN, _abi.POLICY_PRIV_DIM
+        if start is not None and start.dtype == t.bool:
+            start = start.view(t.uint8)
+        if not want_value and out_value is not None:
+            raise ValueError("out_value given with want_value=False")
+        for x, dtype, shape, name in ((obs, f32, (n, 160), "obs"), (noise, f32, (n, 12), "noise"), (priv, f32, (n, Z), "priv"), (hidden, f32, (n, H), "hidden"),
+                                      (start, t.uint8, (n,), "start"), (out_hidden, f32, (n, H), "out_hidden"), (out_latent, f32, (n, Z), "out_latent"),
+                                      (out_action, f32, (n, 12), "out_action"), (out_raw, f32, (n, 12), "out_raw"), (out_value, f32, (n,), "out_value"),
+                                      (out_mean, f32, (n, 12), "out_mean")):
+            _checked(x, dtype, shape, self.device, name)
+        new = lambda x, *shape: t.empty(shape, dtype=f32, device=self.device) if x is None else x   # noqa: E731
+        act, raw, hid = new(out_action, n, 12), new(out_raw, n, 12), new(out_hidden, n, H)
+        val = new(out_value, n) if want_value else None
+        mean = new(out_mean, n, 12) if (want_mean or out_mean is not None) else None
+        std = self.std
+        if self.log_std is not None:
+            if noise is not None and not scaled:
+                if n not in self._scaled:
+                    self._scaled[n] = t.empty((n, 12), dtype=f32, device=self.device)
+                noise = self.prepare(noise, self._scaled[n])
+            std = 1.0
+        elif scaled:
+            raise ValueError("scaled=True is for a policy with %s" % LOGSTD)
+        ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+        _lib.check(self.L.orr_policy_forward_recurrent(C.byref(self.net), C.byref(self.gru.enc), obs.data_ptr(), ptr(start), ptr(hidden), ptr(priv), n,
+                                                       ptr(noise), std, self.clip, act.data_ptr(), raw.data_ptr(), ptr(val), ptr(mean), hid.data_ptr(),
+                                                       ptr(out_latent), self._stream()), self.L)
+        return act, raw, val, mean, hid
 
 
 def history_push(obs, done, prev, out):

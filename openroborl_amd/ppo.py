@@ -9,7 +9,7 @@ Restates the update of agents/ppo_imitation.py:156-258,352-382 (stable-baselines
     (RCCL over xGMI; replaces MpiAdam's Allreduce, stable_baselines/common/mpi_adam.py:40-62).
 The env never leaves the device, so a full iteration is: collect_rollout -> gae -> normalize_per_robot -> update.
 
-This module holds the four torch learners - PPO, PPOHistory, Distill, DistillHistory: the float32 yardsticks of learner_hip's - and is the
+This module holds the torch learners - PPO, PPOHistory, PPORecurrent, Distill, DistillHistory, DistillRecurrent: the float32 yardsticks of learner_hip's - and is the
 public face of what they train and share, which lives in actor_critic.py (ActorCritic and its layers), obs_norm.py (RunningNorm),
 history.py (the sensor history) and update_control.py (the argument checks and _UpdateControl): every name of theirs is a name of ppo.
 """
@@ -90,6 +90,10 @@ class PPO(_UpdateControl):
         logp = self.model.log_prob(mb["obs"], mb["actions"], *self._actor_priv(priv))
         return logp, (self.model.value(mb["obs"]) if priv is None else self.model.value(mb["obs"], priv)), ()
 
+    def _minibatch_rows(self, batch):
+        """The rows of `batch` in a minibatch: samples here, whole robots in PPORecurrent."""
+        return self.minibatch
+
     def _update(self, batch, epochs, generator):
         """The PPO epochs over `batch`: [B, ...] tensors by name, obs, actions, adv, ret and old_logp among them, and what _forward reads."""
         t = self.torch
@@ -100,8 +104,9 @@ class PPO(_UpdateControl):
             perm = t.randperm(B, device=batch["obs"].device, generator=generator)
             # one gather per epoch; the minibatches are then contiguous views
             shuffled = {k: x[perm] for k, x in batch.items()}
-            for s in range(0, B, self.minibatch):
-                mb = {k: x[s:s + self.minibatch] for k, x in shuffled.items()}
+            rows = self._minibatch_rows(batch)
+            for s in range(0, B, rows):
+                mb = {k: x[s:s + rows] for k, x in shuffled.items()}
                 logp, v, more = self._forward(mb)
                 ratio = t.exp(logp - mb["old_logp"])
                 a = mb["adv"]
@@ -181,6 +186,55 @@ class PPOHistory(PPO):
             with self.torch.no_grad():
                 old_logp = self.model.log_prob(obs, actions, hist=hist)
         return self._update(dict(obs=obs, hist=hist, priv=priv, actions=actions, adv=adv, ret=ret, old_logp=old_logp), epochs, generator)
+
+
+class PPORecurrent(PPO):
+    """PPO on a recurrent policy with an asymmetric critic, in plain torch: the specification of the update behind train.py --recurrent-ppo
+    (a fused learner is not built yet).  The forward pass is encode_seq over the rollout segment - truncated BPTT: h0, the state the segment
+    began with, is data - the actor reads obs | z and is trained by the clipped surrogate, the gradient flowing through its layer 0 and the T
+    steps into the GRU; the critic reads obs | priv, the TRUE privileged row:
+      loss = surrogate(log_prob(obs, a, priv=z)) + vf_coef * mean((value(obs, priv) - ret)^2) [- ent_coef * H]
+             + latent_coef * mean_ti sum_c (z_tic - priv_tic)^2
+    All parameters train: actor, critic, GRU, and the log-std of a learn-std model.  A minibatch is a set of whole robots, minibatch // T of
+    them, with all their T steps (DistillRecurrent's).  update() returns PPO's stats followed by the latent loss, like PPOHistory."""
+
+    def __init__(self, model, clip_param=0.2, lr=1e-5, adam_eps=1e-5, minibatch=4096, vf_coef=1.0, group=None, ent_coef=0.0,
+                 log_std_bounds=LOG_STD_BOUNDS, latent_coef=0.0, max_grad_norm=None, kl_stop=None, kl_target=None, kl_lr_bounds=KL_LR_BOUNDS):
+        if not getattr(model, "recurrent", 0):
+            raise ValueError("PPORecurrent: the model needs a recurrent encoder (ActorCritic(recurrent=256)); a model without is trained by PPO")
+        self.latent_coef = float(latent_coef)
+        if not (self.latent_coef >= 0.0 and math.isfinite(self.latent_coef)):
+            raise ValueError("PPORecurrent: latent_coef must be finite and not negative")
+        PPO.__init__(self, model, clip_param, lr, adam_eps, minibatch, vf_coef, group, ent_coef, log_std_bounds, max_grad_norm, kl_stop, kl_target,
+                     kl_lr_bounds)
+
+    def _minibatch_rows(self, batch):
+        return max(1, min(self.minibatch // int(batch["obs"].shape[1]), int(batch["obs"].shape[0])))
+
+    def _forward(self, mb):
+        """mb: robot-major [m, T, ...] tensors and h0 [m, 256] -> log-probabilities and values [m, T]."""
+        m, T = mb["actions"].shape[:2]
+        _, z = self.model.encode_seq(mb["obs"].transpose(0, 1), mb["starts"].transpose(0, 1), mb["h0"])        # one pass for the actor and the latent loss
+        z = z.transpose(0, 1)
+        obs, priv = mb["obs"].reshape(m * T, -1), mb["priv"].reshape(m * T, -1)
+        logp = self.model.log_prob(obs, mb["actions"].reshape(m * T, -1), priv=z.reshape(m * T, -1))
+        return logp.view(m, T), self.model.value(obs, priv).view(m, T), ((self.latent_coef, ((z - mb["priv"]) ** 2).sum(dim=-1).mean()),)
+
+    def update(self, obs, starts, h0, priv, actions, adv, ret, old_logp=None, epochs=1, generator=None):
+        """obs [T,N,160], starts [T,N], h0 [N,256] (the rollout's "hidden"), priv [T,N,48] (env.privileged_obs on the same states), actions
+        [T,N,12] (unclipped samples), adv (already normalised), ret (TD(lambda) targets) and old_logp [T,N] or flat [T N]."""
+        T, N = int(obs.shape[0]), int(obs.shape[1])
+        if tuple(starts.shape) != (T, N) or tuple(h0.shape) != (N, GRU_HIDDEN) or tuple(priv.shape) != (T, N, pol.PRIV_DIM) or tuple(actions.shape) != (T, N, 12):
+            raise ValueError("PPORecurrent: obs [T,N,160], starts [T,N], h0 [N,%d], priv [T,N,%d] and actions [T,N,12]" % (GRU_HIDDEN, pol.PRIV_DIM))
+        batch = dict(obs=obs, starts=starts, priv=priv, actions=actions, adv=adv.reshape(T, N), ret=ret.reshape(T, N))
+        if N % self._minibatch_rows({"obs": obs.transpose(0, 1)}):
+            raise ValueError("PPORecurrent: the number of robots (%d) must be a multiple of the robots per minibatch (minibatch // T)" % N)
+        if old_logp is None:
+            with self.torch.no_grad():
+                _, z = self.model.encode_seq(obs, starts, h0)
+                old_logp = self.model.log_prob(obs.reshape(T * N, -1), actions.reshape(T * N, -1), priv=z.reshape(T * N, -1))
+        batch["old_logp"] = old_logp.reshape(T, N)
+        return self._update(dict({k: x.transpose(0, 1) for k, x in batch.items()}, h0=h0), epochs, generator)
 
 
 class Distill(_UpdateControl):

@@ -50,7 +50,8 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
     (policy_hip.history_push(obs[k + 1], dones[k], hist[k], out=hist[k + 1])).  hist: the one that belongs to `obs` (the previous segment's
     last_hist; None = computed here with done=None).
     critic_priv=True, for a history policy only (PPO on it: ppo.PPOHistory): the critic is asymmetric, step k's forward pass gets hist[k] for
-    the actor and priv[k], the true row, for the value.  False: the estimate feeds both.
+    the actor and priv[k], the true row, for the value.  False: the estimate feeds both.  A recurrent policy (PPO on it: ppo.PPORecurrent)
+    takes it too: hid[k] and starts[k] for the GRU and the actor, priv[k] for the value.
     A recurrent student (policy.recurrent > 0) carries hid [T + 1, N, 256] and starts [T + 1, N]: step k's forward pass reads hid[k] and
     starts[k] and writes hid[k + 1], and starts[k + 1] = dones[k].  "hidden" (hid[0], the segment's h0), "last_hidden" (hid[T]), "starts"
     [T, N] and "hid" (hid[1:], the state after every step) are returned next to "priv" and "last_priv" (the GRU's regression targets).
@@ -65,9 +66,10 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
     history = int(getattr(policy, "history", 0))
     if teacher_mask is not None and teacher is None:
         raise ValueError("teacher_mask without a teacher")
-    if critic_priv and not history:
-        raise ValueError("critic_priv is for a history policy (policy.history > 0): every other critic reads what its actor reads or its own priv")
     recurrent = int(getattr(policy, "recurrent", 0))
+    if critic_priv and not (history or recurrent):
+        raise ValueError("critic_priv is for a history or a recurrent policy (policy.history > 0, policy.recurrent > 0): every other critic reads "
+                         "what its actor reads or its own priv")
     if (hidden is not None or start is not None) and not recurrent:
         raise ValueError("hidden and start are for a recurrent student (policy.recurrent > 0)")
     if recurrent:
@@ -108,7 +110,7 @@ def collect_rollout(env, policy, horizon, obs=None, deterministic=False, generat
         if recurrent:
             row = {"hidden": gbuf[k], "start": sbuf[k], "out_hidden": gbuf[k + 1]}
         if critic_priv:
-            row["critic_priv"] = pbuf[k]
+            row["priv" if recurrent else "critic_priv"] = pbuf[k]
         if fused:   # one fused launch writes the raw action and the value straight into the buffers
             clipped = policy.act(obs, deterministic=deterministic, noise=None if noise is None else noise[k],
                                  out_raw=buf["actions"][k], out_value=buf["vpred"][k], **row)[0]
@@ -172,7 +174,8 @@ class GraphRollout(object):
     place, and after step_into and privileged_obs the push history_push(obs[k + 1], dones[k], hist[k], out=hist[k + 1]) runs inside the
     captured segment; "hist" and "last_hist" are returned next to "priv" and "last_priv", the encoder's regression targets.  critic_priv=True
     (a history policy only; PPO on it) also hands priv[k] to the forward pass: the actor reads the estimate, the value comes from the true row
-    (orr_policy_forward_history_priv).  False is the segment without, launch for launch.
+    (orr_policy_forward_history_priv).  False is the segment without, launch for launch.  A recurrent policy takes critic_priv=True as well:
+    priv[k] goes to its one-launch step (orr_policy_forward_recurrent) next to hid[k] and starts[k], and vpred[k] is the critic on obs[k] | priv[k].
 
     With a learned log-std (policy.learn_std) the segment opens with ONE orr_gauss_prepare over noise [T N][12]: it writes scaled [T, N, 12] =
     exp(log_std) * noise and logp, the forward passes read scaled[k] with std = 1, and no std is among the launch parameters - log_std is read
@@ -180,8 +183,8 @@ class GraphRollout(object):
     moves it.
 
     With a recurrent student (policy.recurrent > 0) the segment holds hid [T + 1, N, 256] and starts [T + 1, N], whose rows 1.. ARE the done
-    flags (dones = starts[1:], one buffer): step k's forward pass - orr_gru_forward with T = 1, then the teacher's kernel on its estimate -
-    reads hid[k] and starts[k] and writes hid[k + 1], all inside the captured segment, the GRU's weight re-pack included.  "hidden" (hid[0]),
+    flags (dones = starts[1:], one buffer): step k's forward pass - orr_policy_forward_recurrent, one launch (with a bf16 GRU orr_gru_forward_bf16
+    with T = 1, then the teacher's kernel on its estimate) - reads hid[k] and starts[k] and writes hid[k + 1], all inside the captured segment, the GRU's weight re-pack included.  "hidden" (hid[0]),
     "last_hidden" (hid[T]), "starts" [T, N] and "hid" (hid[1:]) are returned next to "priv" and "last_priv".
 
     The returned tensors are views of the static buffers: they are overwritten by the next collect() (clone what must survive it,
@@ -205,8 +208,8 @@ class GraphRollout(object):
         self.priv = f(T + 1, n, self.priv_dim or PRIV_DIM) if (self.priv_dim or teacher is not None) else None
         self.history = int(getattr(policy, "history", 0))
         self.hist = f(T + 1, n, HISTORY_DIM) if self.history else None
-        if critic_priv and not self.history:
-            raise ValueError("critic_priv is for a history policy (policy.history > 0)")
+        if critic_priv and not (self.history or self.recurrent):
+            raise ValueError("critic_priv is for a history or a recurrent policy (policy.history > 0, policy.recurrent > 0)")
         self.critic_priv = bool(critic_priv)
         if teacher is not None:
             self.teacher_mean, self.teacher_clipped, self.step_action = f(T, n, 12), f(n, 12), f(n, 12)
@@ -236,7 +239,7 @@ class GraphRollout(object):
         for k in range(self.T):
             if self.recurrent:
                 fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], hidden=self.hid[k],
-                              start=self.starts[k], out_hidden=self.hid[k + 1], **more)
+                              start=self.starts[k], out_hidden=self.hid[k + 1], **({"priv": self.priv[k]} if self.critic_priv else {}), **more)
             elif self.critic_priv:
                 fused.forward(self.obs[k], noise[k], out_action=self.clipped, out_raw=self.actions[k], out_value=self.vpred[k], hist=self.hist[k],
                               critic_priv=self.priv[k], **more)

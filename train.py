@@ -12,6 +12,7 @@ leaves the GPU.  Counterpart of `python3 OpenRoboRL/run.py --task imitation_lear
   python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --push 0.02,0.2,0.5 --save student.zip   (its student)
   python train.py --task imitation_learning_laikago --iters 200 --distill teacher.zip --history --push 0.02,0.2,0.5 --save student.zip   (a history student)
   python train.py --task imitation_learning_laikago --iters 200 --history-ppo --model-file student.zip --push 0.02,0.2,0.5 --save tuned.zip   (PPO on it)
+  python train.py --task imitation_learning_laikago --iters 200 --recurrent-ppo --model-file recurrent_student.zip --push 0.02,0.2,0.5 --save tuned.zip   (PPO on a recurrent student)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py ...
 """
 import argparse
@@ -189,8 +190,16 @@ def arg_parser():
                          "actor, critic and encoder all train (learner_hip.FusedPPOHistory; --torch-learner: ppo.PPOHistory).  --model-file: a "
                          "history student's zip is fine-tuned, a teacher's zip (--privileged-actor) gets a fresh encoder, none: fresh weights.  "
                          "The environment is --privileged-actor's.  The log carries latent_loss; --save writes a history zip that --eval runs")
+    ap.add_argument("--recurrent-ppo", action="store_true",
+                    help="PPO on a recurrent policy: the actor reads its observation and the estimate of a GRU of 256 units over the per-step "
+                         "sensor frame, the critic reads the simulator's TRUE privileged observation; the rollout step is ONE launch "
+                         "(orr_policy_forward_recurrent), and actor, critic and GRU all train, by backpropagation through the segment's --horizon "
+                         "steps, on the torch learner ppo.PPORecurrent (a fused learner is not built yet).  --model-file: a recurrent student's "
+                         "zip is fine-tuned, a teacher's zip (--privileged-actor) gets a fresh GRU, none: fresh weights.  The environment is "
+                         "--privileged-actor's.  The log carries latent_loss; --save writes a recurrent zip that --eval runs.  One rank; not with "
+                         "--history / --history-ppo / --distill / --hip-forward / --hip-backward / --bf16-gemm / --obs-norm")
     ap.add_argument("--latent-coef", type=float, default=0.0, metavar="C",
-                    help="--history-ppo: weight of the auxiliary estimation loss, the squared error of the encoder's output against the "
+                    help="--history-ppo, --recurrent-ppo: weight of the auxiliary estimation loss, the squared error of the encoder's output against the "
                          "privileged observation (default 0: the encoder is trained by the PPO gradient through the actor alone)")
     ap.add_argument("--distill-action-coef", type=float, default=0.0, metavar="C",
                     help="--distill --history: weight of the action loss, the squared error of the student's actor output on (observation, "
@@ -366,8 +375,15 @@ def check_args(args, world):
     """The flags against the modes and the rank count they do not belong to (args.privileged_critic includes --privileged-actor by now)."""
     if args.history_ppo and (args.distill or args.history or args.privileged_critic or args.privileged_actor):
         raise SystemExit("train.py: --history-ppo is a mode of its own; not with --distill / --history / --privileged-critic / --privileged-actor")
-    if args.latent_coef != 0.0 and not args.history_ppo:
-        raise SystemExit("train.py: --latent-coef belongs to --history-ppo")
+    if args.recurrent_ppo:
+        if (args.history or args.history_ppo or args.distill or args.recurrent or args.hip_forward or args.hip_backward or args.bf16_gemm or args.obs_norm
+                or args.privileged_critic or args.privileged_actor):
+            raise SystemExit("train.py: --recurrent-ppo is a mode of its own; not with --history / --history-ppo / --distill / --recurrent / "
+                             "--hip-forward / --hip-backward / --bf16-gemm / --obs-norm / --privileged-critic / --privileged-actor")
+        if world > 1:
+            raise SystemExit("train.py: --recurrent-ppo runs on one rank")
+    if args.latent_coef != 0.0 and not (args.history_ppo or args.recurrent_ppo):
+        raise SystemExit("train.py: --latent-coef belongs to --history-ppo / --recurrent-ppo")
     if not args.latent_coef >= 0.0:
         raise SystemExit("train.py: --latent-coef must not be negative")
     if args.distill and (args.privileged_critic or args.torch_policy):
@@ -434,6 +450,17 @@ def make_model(args, dev):
     if args.history or args.recurrent:
         return history_student(args, torch, pol, ppo, dev, recurrent=args.recurrent)
     params = pol.load_parameters(args.model_file) if args.model_file else None     # run.py:220-221
+    if args.recurrent_ppo:
+        if params is not None and "model/gru_x/w:0" not in params:      # a teacher's zip: its nets + a fresh GRU (the rule of --distill --recurrent)
+            model = history_student(args, torch, pol, ppo, dev, path=args.model_file, fused=False, recurrent=True, std=args.init_std, learn_std=args.learn_std)
+        else:
+            model = ppo.ActorCritic(dev, params=params, seed=args.seed, priv_dim=pol.PRIV_DIM, actor_priv_dim=pol.PRIV_DIM, std=args.init_std,
+                                    learn_std=args.learn_std, recurrent=ppo.GRU_HIDDEN)
+        if not model.recurrent:
+            raise SystemExit("train.py: --recurrent-ppo could not make a recurrent policy of --model-file")
+        if model.learn_std != args.learn_std:
+            raise SystemExit("train.py: --model-file has %s, --learn-std says otherwise" % ("a learned log-std" if model.learn_std else "no log-std"))
+        return model if args.torch_policy else model.enable_fused()
     if args.history_ppo and params is not None and "model/enc_fc0/w:0" not in params:
         # a teacher's zip: its nets + a fresh encoder (the rule of --distill --history); the log-std, if any, is the teacher's
         model = history_student(args, torch, pol, ppo, dev, path=args.model_file, fused=False, std=args.init_std, learn_std=args.learn_std)
@@ -466,8 +493,11 @@ def make_learner(args, model, mode, num_samples, rank):
     kw = control_kwargs(args, kl=is_ppo)
     if is_ppo and args.learn_std:        # the entropy bonus and the clamp; without the flag no keyword at all, the learners' defaults
         kw.update(ent_coef=args.ent_coef, log_std_bounds=tuple(args.log_std_bounds or ppo.LOG_STD_BOUNDS))
-    if mode == "PPOHistory":
+    if mode in ("PPOHistory", "PPORecurrent"):
         kw["latent_coef"] = args.latent_coef
+    if mode == "PPORecurrent":           # whole robots, on the torch learner (main says so): the largest number of them <= --minibatch / horizon that divides the shard
+        robots = max(r for r in range(1, max(1, args.minibatch // args.horizon) + 1) if args.num_robot % r == 0)
+        return ppo.PPORecurrent(model, lr=args.lr, minibatch=args.horizon * robots, **kw)
     if mode == "DistillHistory":
         kw.update(action_coef=args.distill_action_coef, latent_coef=args.distill_latent_coef)
     if args.torch_learner:
@@ -546,6 +576,19 @@ class HistoryPPOMode(Mode):
 
     def update_args(self, buf, flat):
         return [flat(buf[k]) for k in ("obs", "hist", "priv", "actions")], {}
+
+    def record(self, env, stats, learner, losses):
+        return self.ppo_record(losses, latent_loss=round(float(losses[-1]), 6))
+
+
+class RecurrentPPOMode(Mode):
+    """--recurrent-ppo: PPO on a recurrent policy.  The collector's one-launch step gets hid[k] and starts[k] for the GRU and the actor and
+    priv[k], the true row, for the critic (critic_priv=True), the bootstrap is the critic on the last true row, and the learner (ppo.PPORecurrent,
+    whole segments: its minibatches are sets of robots with all their steps) trains actor, critic and GRU."""
+    learner, collector_kw = "PPORecurrent", {"critic_priv": True}
+
+    def update_args(self, buf, flat):
+        return [buf[k] for k in ("obs", "starts", "hidden", "priv", "actions")], {}
 
     def record(self, env, stats, learner, losses):
         return self.ppo_record(losses, latent_loss=round(float(losses[-1]), 6))
@@ -716,7 +759,12 @@ def main():
     args.privileged_critic = args.privileged_critic or args.privileged_actor
     rank, world, local = odist.init_from_env()
     check_args(args, world)
-    privileged = args.privileged_critic or bool(args.distill) or args.history_ppo       # somebody reads env.privileged_obs
+    privileged = args.privileged_critic or bool(args.distill) or args.history_ppo or args.recurrent_ppo       # somebody reads env.privileged_obs
+    if args.recurrent_ppo:
+        args.torch_learner = True
+        if rank == 0:
+            print("train.py: --recurrent-ppo: the rollout runs on the fused one-launch step, the update on the torch learner ppo.PPORecurrent "
+                  "(the fused learner is not built yet)", file=sys.stderr)
     # ORR_BENCH_SINGLE_DEVICE=1 (+ ORR_DIST_BACKEND=gloo): several ranks rehearsed on a one-GPU box (tests), never a measurement
     dev = torch.device("cuda", 0 if os.environ.get("ORR_BENCH_SINGLE_DEVICE") else local)
     torch.cuda.set_device(dev)
@@ -730,7 +778,7 @@ def main():
     if args.clip_curriculum is not None and not env.multi_clip:
         raise SystemExit("train.py: --clip-curriculum needs several --motion-file")
     model = make_model(args, dev)
-    mode = (DistillMode if args.distill else HistoryPPOMode if args.history_ppo else PPOMode)(args, model, dev)
+    mode = (DistillMode if args.distill else HistoryPPOMode if args.history_ppo else RecurrentPPOMode if args.recurrent_ppo else PPOMode)(args, model, dev)
     finish(args, env, model, train(args, env, model, mode, dev, rank, world), rank)
 
 
